@@ -15,10 +15,10 @@ per-iteration ghost refreshes and all-reduced residuals); --replicas runs indepe
 by device stores into the neighbour's hipIpc-mapped inbox ("push", self-tested at set-up) with RCCL send/recv as the all-ranks fall-back;
 SPH_COMM_TRANSPORT=shm+ipc / shm lets several ranks share one GPU (test rig).
 
-Timing: W untimed warm-up steps, then 3 repetitions of exactly K steps, each enqueued on the library's HIP stream
-between two (device synchronise + barrier) fences, max over ranks; `ms_per_step` is the MEDIAN repetition
-(`repeat_ms_per_step` lists all three; from rest the lattice relaxes, so later repetitions are 1-2 % faster).  The
-device synchronise is sph_synchronize: a one-wave kernel behind the queued steps publishes a number into pinned host
+Timing: W untimed warm-up steps and PREPASS_STEPS untimed steps with every kernel's events on, then exactly K timed steps,
+enqueued on the library's HIP stream between two (device synchronise + barrier) fences, max over ranks; `ms_per_step` =
+that time / K.  --repeats R times R such windows of K steps and reports the MEDIAN one (`repeat_ms_per_step` lists all;
+from rest the lattice relaxes, so later repetitions are 1-2 % faster).  The device synchronise is sph_synchronize: a one-wave kernel behind the queued steps publishes a number into pinned host
 memory and the host spins on it (it returns ~30 us sooner than hipStreamSynchronize's interrupt; SPH_SLOW_SYNC=1).  `value` = fluid particles advanced per second by the whole job with all state
 resident in HBM (scene upload outside the region).  The same scene is then advanced to step 2500 and timed again
 (`in_motion`): the rest lattice holds 29 neighbours per particle, the collapsing column ~39.
@@ -35,6 +35,10 @@ solvers' stop tests, CG iterations per step, microseconds per CG iteration, 224 
 the headline itself is the metric as BASELINE.json words it -- the 1.23 M scene split over the N ranks (`scaling: strong`);
 `c2_weak_scaling` (one C2 block per rank) and `c4_strong_scaling` (configs[3]) follow on communicators of their own, with the
 halo transport in effect.
+--dump-outputs DIR (N=1): after the timed window, i.e. at step presteps + W + PREPASS_STEPS + repeats x K whatever kernels a build
+launches, what its last step left a caller of solver.step() -- positions, velocities and densities in particle-id order -- is
+written as DIR/<name>.npy (float32; a seeded sample of particle ids above 64 MB),
+so that two builds can be compared output for output on the same inputs (the scenes are synthetic lattices, no RNG).
 """
 import argparse
 import json
@@ -56,6 +60,7 @@ ALG_BYTES = {
     "pcisph_rho_star": 40, "pcisph_pressure_accel": 64,
 }
 N_KERNEL_IDS = 19
+PREPASS_STEPS = 5   # untimed all-kernel event steps between the warm-up and the timed window
 
 
 def parse_args(argv=None):
@@ -71,7 +76,7 @@ def parse_args(argv=None):
     ap.add_argument("--force-global", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=3, help="repetitions of the K timed steps (median reported)")
+    ap.add_argument("--repeats", type=int, default=1, help="repetitions of the K timed steps (median reported)")
     ap.add_argument("--measured-iterations", action="store_true",
                     help="c3: the solver's own convergence tests (DFSPH.py:150/:239) instead of 2+2 fixed iterations; "
                          "iteration counts of the last step are reported in config")
@@ -86,6 +91,9 @@ def parse_args(argv=None):
                          "object `c2_weak_scaling` of the line")
     ap.add_argument("--replicas", action="store_true", help="N>1: independent copies instead of z-slab sharding")
     ap.add_argument("--no-c4", action="store_true", help="N>1: skip the extra C4 (4 M particles, strong scaling) measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: write the state the last timed step left (positions, velocities, densities by particle id) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the extra objects of the line: N=1: C3 (DFSPH) and C5 (implicit-viscosity buckling scene); "
                          "N>1: the 1.23 M scene and C4 under strong scaling")
@@ -288,6 +296,38 @@ def pmc_figures(config, kernel):
                 "traffic_source": f"{src}: 2*FETCH_SIZE + WRITE_SIZE per launch from separate rocprofv3 --pmc passes; NOT measured in this run"}
     except Exception:  # noqa: BLE001
         return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_arrays(ids, fields, limit=DUMP_LIMIT_BYTES):
+    """The arrays --dump-outputs writes: every field (rows in the library's current order) put into particle-id order (the sort permutes
+    the arrays every step; ids stay), as float32.  Above `limit` bytes in all, the rows of a fixed sample of ids (seed 0, ascending)."""
+    import numpy as np
+    n = len(ids)
+    if not np.array_equal(np.sort(ids), np.arange(n)):
+        raise RuntimeError("--dump-outputs: particle ids are not a permutation of 0..n-1")
+    keep = None
+    per_particle = 4 * sum(a.size for a in fields.values()) // max(n, 1)   # float32 bytes of one particle's rows
+    if n * per_particle > limit:
+        keep = np.sort(np.random.default_rng(0).choice(n, limit // per_particle, replace=False))
+    out = {}
+    for name, a in fields.items():
+        by_id = np.empty_like(a)
+        by_id[ids] = a
+        out[name] = np.ascontiguousarray(by_id if keep is None else by_id[keep], dtype=np.float32)
+    return out
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: positions, velocities and densities as a caller of solver.step() reads them, as DIR/<name>.npy."""
+    import numpy as np
+    from sph_project_amd import _lib as L
+    fields = {"position": eng.download(L.F_POSITION), "velocity": eng.download(L.F_VELOCITY), "density": eng.download(L.F_DENSITY)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in dump_arrays(eng.download(L.F_PARTICLE_ID), fields).items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def median(v):
@@ -521,7 +561,7 @@ def run_rank(args, rank, world, local_rank):
     # pre-pass: which kernel dominates?  (all-kernel events perturb the stream slightly -> untimed)
     eng.profile_enable(-1, True)
     eng.profile_reset()
-    run(5); steps_done += 5
+    run(PREPASS_STEPS); steps_done += PREPASS_STEPS
     eng.synchronize()
     table = {names[k]: eng.profile_read(k) for k in range(N_KERNEL_IDS)}
     table = {k: v for k, v in table.items() if v[0] > 0}
@@ -535,19 +575,6 @@ def run_rank(args, rank, world, local_rank):
         for k, (n, ms) in sorted(table.items(), key=lambda kv: -kv[1][1]):
             print(f"  {k:24s} launches {n:5d}  avg {1e3 * ms / n:9.1f} us", file=sys.stderr)
     eng.profile_enable(-1, False)
-    # ... and every kernel that carries algorithmic bytes once more ALONE (one kernel id's events at a time): with all ids enabled the
-    # event pairs of neighbouring launches serialise the stream and inflate a walk by 6-8 % (VERDICT r04).  `all_kernels` / `runner_up`
-    # quote these solo figures; the all-event one is kept beside them.
-    solo = {}
-    if not os.environ.get("SPH_BENCH_NO_EVENTS"):
-        for k in [k for k in table if k in ALG_BYTES]:
-            eng.profile_enable(names.index(k), True); eng.profile_reset()
-            run(3); steps_done += 3
-            eng.synchronize()
-            solo[k] = eng.profile_read(names.index(k))
-            eng.profile_enable(-1, False)
-    table_all = dict(table)
-    table = {k: (solo[k] if k in solo and solo[k][0] > 0 else v) for k, v in table.items()}
 
     def timed(reps):
         """reps x (fence, K steps, fence); returns the per-repetition max-over-ranks seconds"""
@@ -569,6 +596,22 @@ def run_rank(args, rank, world, local_rank):
     launches, ms = eng.profile_read(names.index(dom))
     eng.profile_enable(-1, False)
     stats = solver.stats()
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs)
+    # ... and every kernel that carries algorithmic bytes once more ALONE (one kernel id's events at a time): with all ids enabled the
+    # event pairs of neighbouring launches serialise the stream and inflate a walk by 6-8 % (VERDICT r04).  `all_kernels` / `runner_up`
+    # quote these solo figures; the all-event one is kept beside them.  They run AFTER the timed window (and the dump): how many steps they
+    # take depends on the kernels a build launches, the state the timed window starts from must not.
+    solo = {}
+    if not os.environ.get("SPH_BENCH_NO_EVENTS"):
+        for k in [k for k in table if k in ALG_BYTES]:
+            eng.profile_enable(names.index(k), True); eng.profile_reset()
+            run(3); steps_done += 3
+            eng.synchronize()
+            solo[k] = eng.profile_read(names.index(k))
+            eng.profile_enable(-1, False)
+    table_all = dict(table)
+    table = {k: (solo[k] if k in solo and solo[k][0] > 0 else v) for k, v in table.items()}
     # Which sort path did the timed region take?  Inside one sph_step_async(K) of an unsharded all-fluid WCSPH scene the force pass of
     # every step but the last is also the next step's init_grid (NextHash): it then moves the hash's 16 B per particle as well, and
     # its algorithmic bytes are 96 + 16 = 112 (the step's 204 B are unchanged: the hash kernel's 16 B moved, they did not vanish).
@@ -751,6 +794,10 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("bench.py: --dump-outputs needs --gpus 1")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         return spawn_ranks(args.gpus)

@@ -293,7 +293,7 @@ def test_c3_full_size_dfsph_in_motion_own_stop_tests(gpu, from_step=1000):
 
 def test_c4_full_size_wcsph_one_gpu(gpu):
     """BASELINE configs[3]'s scene (4,000,000 particles, WCSPH) on ONE GPU, 5 steps in one advance(5) -- the timed path, with the
-    force pass hashing for the next sort (its 8-GPU sharding: tests/test_hip_slab.py, 8 ranks on one GPU; real devices: the driver's)."""
+    force pass hashing for the next sort (its 8-GPU sharding: tests/test_hip_slab.py, 4 ranks on one GPU; real devices: the driver's)."""
     _full_size_vs_oracle(P.c4_scene(), 5, 0, 1e-4, advance=True)
 
 
@@ -551,11 +551,11 @@ def test_handles_release_their_memory(gpu):
 def test_bench_spawns_two_ranks_without_torch(gpu):
     """`python bench.py --gpus 2` with no launcher: two ranks, z-slab sharded, halo exchange through the shared-memory
     transport (two ranks on this box's one GPU), barriers / reductions through sph_comm_*; no torch import."""
-    out = _bench(["--gpus", "2", "--config", "c1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--motion-step", "0"],
+    out = _bench(["--gpus", "2", "--config", "c1", "--steps", "5", "--warmup", "2", "--repeats", "3", "--no-cpu-baseline", "--motion-step", "0"],
                  {"SPH_COMM_TRANSPORT": "shm+ipc", "SPH_BENCH_SELFTEST": "1"})
     assert out["n_gpus"] == 2 and out["config"]["parallelism"].startswith("z-slab x2, ipc-push+shm"), out["config"]
     assert out["config"]["particles"] == 8000 and out["value"] > 0 and len(out["repeat_ms_per_step"]) == 3
-    one = _bench(["--gpus", "1", "--config", "c1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--motion-step", "0"], {})
+    one = _bench(["--gpus", "1", "--config", "c1", "--steps", "5", "--warmup", "2", "--repeats", "3", "--no-cpu-baseline", "--motion-step", "0"], {})
     assert one["n_gpus"] == 1
     # the same steps of the same scene: the sharded run finds exactly the pairs the single-GPU run finds
     assert out["config"]["pair_interactions_per_step"] == one["config"]["pair_interactions_per_step"]
@@ -563,25 +563,55 @@ def test_bench_spawns_two_ranks_without_torch(gpu):
     assert "import torch" not in src and "torch.distributed" not in src.replace("torch.distributed.run", "")
 
 
-def test_bench_eight_ranks_share_one_gpu(gpu):
-    """The driver's 8-rank job -- BASELINE.json's metric as written: the 1,231,200-particle scene itself split over the 8 ranks (strong
-    scaling; every rank topology: two edge ranks, six with both neighbours; 5-7 cell layers per rank) -- and the same job with one C2 block
-    per rank (--scaling weak, 8 x 1,231,200 particles), with all ranks on this box's ONE GPU -- push transport, asynchronous steps, 8-way control plane.  Round 3 found here that workgroups spinning on a
-    neighbour's message hold their CU slots: with every workgroup of the consuming kernels polling, 8 ranks filled the chip with pollers and
-    the kernels that had to produce the awaited messages were never scheduled (all waits timed out); the waiting kernels are capped at 64
-    workgroups now.  Oversubscription only -- one rank per GPU cannot starve itself -- but a hang is a hang."""
-    common = ["--gpus", "8", "--steps", "5", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--motion-step", "0", "--no-extras"]
+def test_bench_dumps_the_state_of_its_last_timed_step(gpu, tmp_path):
+    """`--steps K --dump-outputs DIR`: ONE timed window of exactly K steps, starting at a step fixed by the arguments (warm-up + the
+    all-event pre-pass; the per-kernel event passes, whose count depends on the kernels a build launches, come after it), then positions /
+    velocities / densities in particle-id order as float32 .npy -- bit-equal to the product advanced by itself to that step (bench.py builds
+    it the same way: fast build, deterministic sort), and bit-equal between a run with kernel events and one without (SPH_BENCH_NO_EVENTS)."""
+    import bench
+    k, warmup = 7, 2
+    args = ["--gpus", "1", "--config", "c1", "--steps", str(k), "--warmup", str(warmup), "--no-cpu-baseline", "--motion-step", "0", "--no-extras"]
+    outs = [_bench(args + ["--dump-outputs", str(tmp_path / d)], env) for d, env in (("a", {}), ("b", {"SPH_BENCH_NO_EVENTS": "1"}))]
+    last = warmup + bench.PREPASS_STEPS + k
+    for out in outs:
+        assert out["steps"] == k and len(out["repeat_ms_per_step"]) == 1 and out["ms_per_step"] == out["repeat_ms_per_step"][0]
+        assert out["config"]["state"] == "steps %d..%d from the initial lattice" % (last - k, last), out["config"]["state"]
+    dumped = {name: np.load(tmp_path / "a" / (name + ".npy")) for name in ("position", "velocity", "density")}
+    for name, a in dumped.items():
+        assert a.dtype == np.float32 and len(a) == 8000
+        np.testing.assert_array_equal(a, np.load(tmp_path / "b" / (name + ".npy")))
+    container, solver = P.build_product(P.dam_break_scene(), fast_math=1, deterministic=1)
+    e = container.engine
+    solver.prepare()
+    e.step_async(last)
+    e.synchronize()
+    ids = e.download(L.F_PARTICLE_ID)
+    for name, f in (("position", L.F_POSITION), ("velocity", L.F_VELOCITY), ("density", L.F_DENSITY)):
+        np.testing.assert_array_equal(dumped[name], H.by_id(ids, e.download(f)))
+    e.close()
+
+
+def test_bench_four_ranks_share_one_gpu(gpu):
+    """The driver's multi-rank job -- BASELINE.json's metric as written: the 1,231,200-particle scene itself split over 4 ranks (strong
+    scaling; every rank topology: two edge ranks, two with both neighbours; 10-14 cell layers per rank) -- and the same job with one C2 block
+    per rank (--scaling weak, 4 x 1,231,200 particles), with all ranks on this box's ONE GPU -- push transport, asynchronous steps, 4-way
+    control plane.  Four ranks, because the test process has the GPU open too and a shared GPU takes at most six processes at once.
+    Round 3 found here that workgroups spinning on a neighbour's message hold their CU slots: with every workgroup of the consuming kernels
+    polling, 8 ranks filled the chip with pollers and the kernels that had to produce the awaited messages were never scheduled (all waits
+    timed out); the waiting kernels are capped at 64 workgroups now.  Oversubscription only -- one rank per GPU cannot starve itself -- but a
+    hang is a hang."""
+    common = ["--gpus", "4", "--steps", "5", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--motion-step", "0", "--no-extras"]
     env = {"SPH_COMM_TRANSPORT": "shm+ipc", "SPH_COMM_TIMEOUT_S": "60"}
     out = _bench(common, env, timeout=900)
-    assert out["n_gpus"] == 8 and out["config"]["particles"] == 1231200 and out["scaling"] == "strong"
+    assert out["n_gpus"] == 4 and out["config"]["particles"] == 1231200 and out["scaling"] == "strong"
     assert out["config"]["workload"] == "C2 1,231,200-particle dam break"   # the N = 1 line's workload, byte for byte
-    assert out["config"]["parallelism"].startswith("z-slab x8, ipc-push+shm") and out["value"] > 0
+    assert out["config"]["parallelism"].startswith("z-slab x4, ipc-push+shm") and out["value"] > 0
     # ~26 lattice neighbours (+ some of the 6 at exactly h, decided by rounding; fewer at the block's faces) x 4 reference passes
     assert 4 * 24 * 1231200 < out["config"]["pair_interactions_per_step"] < 4 * 33 * 1231200
     out = _bench(common + ["--scaling", "weak"], env, timeout=900)
-    assert out["n_gpus"] == 8 and out["config"]["particles"] == 8 * 1231200 and out["scaling"] == "weak"
-    assert out["config"]["workload"] == "C2 1,231,200-particle dam break x8 in z"
-    assert out["config"]["parallelism"].startswith("z-slab x8, ipc-push+shm") and out["value"] > 0
+    assert out["n_gpus"] == 4 and out["config"]["particles"] == 4 * 1231200 and out["scaling"] == "weak"
+    assert out["config"]["workload"] == "C2 1,231,200-particle dam break x4 in z"
+    assert out["config"]["parallelism"].startswith("z-slab x4, ipc-push+shm") and out["value"] > 0
 
 
 def test_bench_stops_all_ranks_when_one_dies(gpu):

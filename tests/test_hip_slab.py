@@ -36,6 +36,11 @@ def _pairs_agree(got, want):
     assert abs(int(got) - int(want)) <= max(2, 2e-5 * int(want)), (got, want)
 
 
+# Worker processes of one run.  The test process has the GPU open as well, and a GPU shared with other users takes at most six processes
+# at once: more ranks than this share processes (rank r runs in process r % MAX_PROCS, in a thread of its own; no two neighbours share one).
+MAX_PROCS = 4
+
+
 def _run_ranks(cfg, nranks, steps, tmp_path, jitter=0.0, seed=0, fixed_iterations=0, rebalance=0, advance=False, extra_env=None, timeout=None):
     tmp_path.mkdir(parents=True, exist_ok=True)
     scene_path = tmp_path / "scene.json"
@@ -46,18 +51,20 @@ def _run_ranks(cfg, nranks, steps, tmp_path, jitter=0.0, seed=0, fixed_iteration
     if LAYOUT[0]:
         env["SPH_SLAB_LAYOUT"] = LAYOUT[0]
     env.update(extra_env or {})
+    nprocs = min(nranks, MAX_PROCS)
+    groups = [list(range(i, nranks, nprocs)) for i in range(nprocs)]
     procs = []
-    for r in range(nranks):
-        out = tmp_path / f"rank{r}.npz"
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "slab_worker.py"), str(r), str(nranks), uid,
-                                       str(scene_path), str(steps), str(out), str(jitter), str(seed)], env=env,
+    for g in groups:
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "slab_worker.py"), ",".join(map(str, g)), str(nranks), uid,
+                                       str(scene_path), str(steps), str(tmp_path / "rank{rank}.npz"), str(jitter), str(seed)], env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    logs = []
+    plogs = []
     for p in procs:
         o, _ = p.communicate(timeout=timeout or int(os.environ.get("SPH_TEST_RANK_TIMEOUT", "300")))
-        logs.append(o.decode())
+        plogs.append(o.decode())
     if any(p.returncode != 0 for p in procs):   # (the rank that reports "a neighbour failed" is rarely the one that says why)
-        raise AssertionError("\n".join(f"---- rank {r} (exit {p.returncode}):\n{logs[r][-1500:]}" for r, p in enumerate(procs)))
+        raise AssertionError("\n".join(f"---- ranks {g} (exit {p.returncode}):\n{plogs[i][-1500:]}" for i, (g, p) in enumerate(zip(groups, procs))))
+    logs = [plogs[r % nprocs] for r in range(nranks)]   # (the log of the process that ran the rank)
     outs = [np.load(tmp_path / f"rank{r}.npz") for r in range(nranks)]
     if extra_env and "SPH_COMM_TRANSPORT" in extra_env:
         return outs, logs
@@ -70,9 +77,8 @@ def _run_ranks(cfg, nranks, steps, tmp_path, jitter=0.0, seed=0, fixed_iteration
 def slow_layout(transport):
     """SPH_SLAB_LAYOUT=slow for the ranks of this test: the scene's z is mapped onto the library's x (its slowest sort axis, library axes =
     scene z, x, y at the C-ABI boundary), WCSPH passes run boundary tiles first and the halo messages go out behind them (round 4; measured
-    slower than the default layout on thin slabs, kept as an option: DESIGN.md).  Push transport only."""
-    if transport != "shm+ipc":
-        pytest.skip("the overlap of the slow-axis layout rides on the push transport")
+    slower than the default layout on thin slabs, kept as an option: DESIGN.md).  The overlap rides on the push transport; over the
+    mailboxes the same permuted frame runs without it."""
     LAYOUT[0] = "slow"
     yield
     LAYOUT[0] = ""
@@ -447,8 +453,6 @@ def test_dead_neighbour_is_an_error_not_a_hang(gpu, tmp_path):
 def test_push_transport_is_all_ranks_or_none(gpu, tmp_path, transport):
     """The push data plane is used by every rank or by none: a rank that cannot set it up (test hook; on a real node: no peer mapping, no
     coherent memory, a failed self-test) takes all ranks to the control plane's own transport at set-up, and the run is still right."""
-    if transport != "shm+ipc":
-        pytest.skip("one transport variant is enough")
     cfg = H.dam_break_scene(domain_end=(1.0, 1.0, 1.2), start=(0.1, 0.1, 0.08), end=(0.3, 0.3, 1.12), translation=(0, 0, 0),
                             velocity=(0.0, -0.3, 2.0), particleSpacing=0.019)
     steps = 12
@@ -465,23 +469,23 @@ def test_push_transport_is_all_ranks_or_none(gpu, tmp_path, transport):
         x[o["ids"]] = o["pos"]
     _, geo, _b = H.scene_particles(cfg)
     assert H.drift(x, x_ref, geo.dh).max() <= 1e-5
-    # and without the hook the same command line comes up with the push transport
-    outs2, _ = _run_ranks(cfg, 2, 3, tmp_path, extra_env={"SPH_COMM_TRANSPORT": "shm+auto"})
-    assert [str(o["transport"]) for o in outs2] == ["ipc-push+shm"] * 2
+    # and without the hook the same command line comes up with the push transport -- unless the mailboxes are asked for by name
+    request, want = ("shm+auto", "ipc-push+shm") if transport == "shm+ipc" else ("shm", "shm")
+    outs2, _ = _run_ranks(cfg, 2, 3, tmp_path, extra_env={"SPH_COMM_TRANSPORT": request})
+    assert [str(o["transport"]) for o in outs2] == [want] * 2
 
 
 def test_exact_launch_flavour_of_the_push_transport(gpu, tmp_path, transport):
     """SPH_SLAB_ASYNC=0: WCSPH steps over the push transport with the counts read back once per step and exact launch grids (what the
-    iterative solvers always use) -- same particles, same pairs as the asynchronous flavour."""
-    if transport != "shm+ipc":
-        pytest.skip("push transport only")
+    iterative solvers always use) -- same particles, same pairs as the asynchronous flavour.  The mailbox transport always runs exact
+    launches: there the switch must change nothing at all."""
     cfg = H.dam_break_scene(domain_end=(1.0, 1.0, 1.2), start=(0.1, 0.1, 0.08), end=(0.3, 0.3, 1.12), translation=(0, 0, 0),
                             velocity=(0.0, -0.3, 2.0), particleSpacing=0.019)
     (tmp_path / "a").mkdir(); (tmp_path / "s").mkdir()
     outs_a, _ = _run_ranks(cfg, 2, 15, tmp_path / "a", advance=True)
-    outs_s, _ = _run_ranks(cfg, 2, 15, tmp_path / "s", advance=True, extra_env={"SPH_SLAB_ASYNC": "0", "SPH_COMM_TRANSPORT": "shm+ipc"})
+    outs_s, _ = _run_ranks(cfg, 2, 15, tmp_path / "s", advance=True, extra_env={"SPH_SLAB_ASYNC": "0", "SPH_COMM_TRANSPORT": transport})
     for a, b in zip(outs_a, outs_s):
-        assert str(b["transport"]) == "ipc-push+shm"
+        assert str(b["transport"]) == ("ipc-push+shm" if transport == "shm+ipc" else "shm")
         oa, ob = np.argsort(a["ids"]), np.argsort(b["ids"])
         np.testing.assert_array_equal(a["ids"][oa], b["ids"][ob])
         np.testing.assert_array_equal(a["pos"][oa], b["pos"][ob])     # the same kernels in the same order: bit-identical
@@ -506,9 +510,9 @@ def test_stalled_consumer_exposes_the_single_header_race_and_only_that(gpu, tmp_
       * header per message parity (the protocol in the tree): nothing changes -- bit-identical to the run without the stall, equal to
         the oracle;
       * SPH_TEST_SINGLE_HEADER (pre-round-5): rank 1 takes message 2's record count for message 1's payload -- the run fails or
-        ends in a different particle set.  If it ever passes, the stall no longer reaches the seam and this test says so."""
-    if transport != "shm+ipc":
-        pytest.skip("push transport only")
+        ends in a different particle set.  If it ever passes, the stall no longer reaches the seam and this test says so.
+    The mailbox transport has no shared header (every message carries its own count): there the stall and the single-header switch
+    change nothing."""
     assert os.path.exists(HOOKS_LIB), "build() makes libsph_hip_testhooks.so"
     # The two messages of the seam must DIFFER for the mix-up to show (same positions -> same records -> same count, and a header taken
     # from the wrong message is then harmless).  They differ when particles change owner in prepare's exchange: the lattice (spacing 0.02
@@ -535,6 +539,12 @@ def test_stalled_consumer_exposes_the_single_header_race_and_only_that(gpu, tmp_
     ids = H.oracle_ids(ref)
     assert np.array_equal(b[0], np.arange(len(ids)))
     assert H.drift(b[1], H.by_id(ids, ref.field("particle_positions").copy()), geo.dh).max() <= 1e-5
+    if transport != "shm+ipc":
+        bad, _ = _run_ranks(cfg, 2, steps, tmp_path / "bad", jitter=0.002, seed=3, advance=True, extra_env=dict(stall, SPH_TEST_SINGLE_HEADER="1"))
+        c = _owned_state(bad)
+        np.testing.assert_array_equal(c[0], a[0])
+        assert H.drift(c[1], a[1], geo.dh).max() <= 1e-6
+        return
     fired = False
     try:
         bad, _ = _run_ranks(cfg, 2, steps, tmp_path / "bad", jitter=0.002, seed=3, advance=True, extra_env=dict(stall, SPH_TEST_SINGLE_HEADER="1"))
@@ -551,9 +561,8 @@ def test_stalled_consumer_exposes_the_single_header_race_and_only_that(gpu, tmp_
 def test_stalled_consumers_everywhere_change_nothing(gpu, tmp_path, transport):
     """Stress of the rest of the protocol (header-less field messages under presend + fused field send, SlabDyn / halo_counts banks): every
     waiting workgroup of every rank stalls 0.1-0.4 ms before it polls -- workgroup 0 between its announce and its poll, the others
-    staggered -- in three ranks over 12 asynchronous steps.  Same particles, same state (to the last bit or two) as without stalls."""
-    if transport != "shm+ipc":
-        pytest.skip("push transport only")
+    staggered -- in three ranks over 12 asynchronous steps.  Same particles, same state (to the last bit or two) as without stalls.  (Over
+    the mailbox transport nothing waits on the device: the same comparison holds trivially and guards the hooks' reach.)"""
     cfg = H.dam_break_scene(domain_end=(1.0, 1.0, 1.2), start=(0.1, 0.1, 0.08), end=(0.4, 0.4, 1.12), translation=(0, 0, 0),
                             velocity=(0.0, -0.3, 2.5), particleSpacing=0.019)
     hooks = {"SPH_HIP_LIB": HOOKS_LIB}
@@ -568,7 +577,8 @@ def test_stalled_consumers_everywhere_change_nothing(gpu, tmp_path, transport):
 
 
 def _eight_way(cfg, steps, tmp_path, jitter, seed, exact_pairs, build="strict"):
-    """8 ranks on this box's single GPU over the push transport, all `steps` in ONE advance() call, against the undecomposed CPU oracle.
+    """8 ranks on this box's single GPU (two per worker process, see MAX_PROCS), all `steps` in ONE advance() call, against the undecomposed
+    CPU oracle, over the transport of the running test (the push transport is the production data plane).
     build = "fast": the kernels `bench.py --gpus N` runs (v_rcp / v_rsq, FMA, the presend / fused-field-send force and density passes of
     the fast object) -- the sharded path that is TIMED is the one compared with the oracle."""
     nranks = 8
@@ -623,8 +633,6 @@ def test_c4_sharded_over_8_ranks_matches_oracle(gpu, tmp_path, transport, varian
     (0.5 M particles, 10-12 cell layers each) over the push transport, 5 asynchronous steps, against the undecomposed oracle.
     as_written: the scene of SURVEY 8d C4 (rest lattice, v = (0, -0.5, 0): nobody crosses a z face in 5 steps).  jitter_vz: the same
     block on a seeded perturbed lattice with a z velocity, so that particles migrate across all seven faces."""
-    if transport != "shm+ipc":
-        pytest.skip("the production data plane; the mailbox rig is covered at small sizes")
     from sph_project_amd import product as P
     cfg = P.c4_scene()
     if variant == "as_written":
@@ -640,8 +648,6 @@ def test_c2_scene_sharded_over_8_ranks_matches_oracle(gpu, tmp_path, transport, 
     """The 1.23 M scene of configs[1] split eight ways: five cell layers of ~31 k particles per rank -- the thin-slab regime (one staged
     stretch per x-offset group, sph_device.hpp nbr_plan "chain") where a whole layer is a fifth of a rank.  Perturbed lattice + z velocity:
     migration across every face, 5 asynchronous steps."""
-    if transport != "shm+ipc":
-        pytest.skip("the production data plane; the mailbox rig is covered at small sizes")
     from sph_project_amd import product as P
     cfg = P.c2_scene()
     cfg["FluidBlocks"][0]["velocity"] = [0.0, -0.5, 1.5]
@@ -656,8 +662,6 @@ def test_c2_in_motion_state_sharded_over_8_ranks_matches_oracle(gpu, tmp_path, t
     undecomposed product produces the state, the ranks are seeded with it (tests/slab_worker.py SPH_WORKER_STATE: slab membership and cuts
     from these positions), so is the oracle (H.oracle_from_state); 5 asynchronous steps over the push transport; by particle id against
     the oracle."""
-    if transport != "shm+ipc":
-        pytest.skip("the production data plane; the mailbox rig is covered at small sizes")
     from sph_project_amd import product as P
     cfg = P.c2_scene()
     container, solver = H.build_product(cfg, fast_math=1)

@@ -375,3 +375,29 @@ def test_run_list_stable_rank_model():
             assert (inv[d] == -1).all()
             inv[d] = h + np.arange(L)
         np.testing.assert_array_equal(inv, np.argsort(cell, kind="stable"))
+
+
+def test_bench_dump_reorders_by_id_and_samples_above_the_limit():
+    """bench.py --dump-outputs (dump_arrays): rows go to particle-id order as float32; above the byte limit the rows of an ascending
+    sample of ids are kept, within the limit and the same from call to call; ids that are not a permutation are refused."""
+    import bench
+    rng = np.random.default_rng(5)
+    n = 1000
+    ids = rng.permutation(n).astype(np.int32)
+    fields = {"position": rng.random((n, 3), dtype=np.float32), "density": rng.random(n, dtype=np.float32)}
+    full = bench.dump_arrays(ids, fields)
+    for name, a in fields.items():
+        assert full[name].dtype == np.float32
+        np.testing.assert_array_equal(full[name][ids], a)
+    limit = 4000                                   # 16 B per particle: 250 of the 1000
+    s1, s2 = bench.dump_arrays(ids, fields, limit), bench.dump_arrays(ids, fields, limit)
+    assert len(s1["density"]) == 250 and sum(a.nbytes for a in s1.values()) <= limit
+    for name in fields:
+        np.testing.assert_array_equal(s1[name], s2[name])
+    keep = np.array([np.flatnonzero((full["position"] == row).all(axis=1))[0] for row in s1["position"]])
+    assert np.all(np.diff(keep) > 0)
+    np.testing.assert_array_equal(s1["density"], full["density"][keep])
+    bad = ids.copy()
+    bad[0] = bad[1]
+    with pytest.raises(RuntimeError):
+        bench.dump_arrays(bad, fields)

@@ -1,5 +1,5 @@
 """Known-answer tests of the mesh -> particles path on the reference's OWN models
-(/root/reference/data/models/{cube,sphere,torus,icosphere,cone}.obj), placed the way its scene files place them
+(its data/models/{cube,sphere,torus,icosphere,cone}.obj, stored unchanged under tests/golden/models/), placed the way its scene files place them
 (final_scene1.json: sphere.obj scale 0.6; test.json: cube.obj scale 1; particleRadius 0.01 -> pitch 0.02).
 
 trimesh is absent, so `mesh.voxelized(pitch).fill().points` (base_container.py:641-642) and `mesh.contains` (:686-694)
@@ -16,10 +16,7 @@ cannot be run; what CAN be checked without them, and independently of the numpy 
     occupied voxel (trimesh's subdivision voxeliser samples exactly the vertices of the subdivided mesh, the original ones
     among them); point symmetry about the origin for the centrally symmetric models (round() is odd, so the set of
     round(v / pitch) is symmetric when the triangulated model is: exactly for the cube, up to grazed voxels for the rest);
-  * the torus keeps its hole through the fill.
-
-The models are read from /root/reference at test time (CPU suite, this container); nothing of them is copied into the
-repo.  Skipped where the reference is absent (the GPU box)."""
+  * the torus keeps its hole through the fill."""
 import os
 
 import numpy as np
@@ -27,8 +24,7 @@ import pytest
 
 from sph_project_amd import meshgen as M
 
-MODELS = "/root/reference/data/models"
-pytestmark = pytest.mark.skipif(not os.path.isdir(MODELS), reason="reference models not present (GPU box)")
+MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "models")
 PITCH = 0.02   # particle diameter of every reference scene that loads a mesh (particleRadius 0.01)
 
 
