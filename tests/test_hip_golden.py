@@ -54,7 +54,7 @@ def test_hip_matches_golden(gpu, path, fast_math):
     slot_fluid, slot_fluid_step = z["prep_materials"] == 1, 0   # who occupied each slot before the last sort
     for cp in z["checkpoints"]:
         while step < cp:
-            if method == "wcsph" and step == cp - 1:   # the positions the checkpoint's forces are evaluated at
+            if method in ACC_METHODS and step == cp - 1:   # the positions the checkpoint's forces are evaluated at
                 ids_before, x_before, mat_before = e.download(L.F_PARTICLE_ID), e.download(L.F_POSITION), e.download(L.F_MATERIAL)
             solver.step()
             step += 1
@@ -95,16 +95,15 @@ def test_hip_matches_golden(gpu, path, fast_math):
             scale = max(float(np.abs(ref).max()), 1e-30)
             err = np.abs(mine.astype(np.float64) - ref.astype(np.float64))
             if key == "alphas" and pre + "densities" in z.files:
-                # alpha_i = -1 / (sum_j |V_j grad W_ij|^2 + |sum_j V_j grad W_ij|^2), grad W ~ (1 - q)^2 for q > 1/2: a particle
+                # alpha_i = 1 / (sum_j |V_j grad W_ij|^2 + |sum_j V_j grad W_ij|^2), grad W ~ (1 - q)^2 for q > 1/2: a particle
                 # whose few neighbours all sit near the edge of its support (rho_i well below rho0: spray, the first particles out of
                 # an emitter) has every term carry the cancellation 1 - q, amplification 4 / (1 - q) per term -- the fast build's
                 # v_rcp / v_rsq (1 ulp in q) then show up as ~1e-4 in alpha of that ONE particle (tools/debug_alpha.py:
                 # dfsph_implicit_box, particle 1019 at rho = 272: 4.6e-5 or 8.8e-5 depending on how the compiler contracts the
-                # surrounding code into FMAs; median over the fluid 7e-7, p99 5e-6; the strict build 1e-6 everywhere).  Parity is
-                # asserted on the particles with a populated neighbourhood; the sparse ones get a guard.
+                # surrounding code into FMAs; median over the fluid 7e-7, p99 5e-6; the strict build 1e-6 everywhere).  Parity with the
+                # fixture is asserted on the particles with a populated neighbourhood; EVERY particle gets the per-term check below.
                 rho = H.by_id(z[pre + "ids"], z[pre + "densities"])[fluid]
                 dense = rho >= 0.5 * float(cfg["Configuration"]["density0"])
-                worst["alphas_sparse"] = float(err[~dense].max()) / scale if (~dense).any() else 0.0
                 err = err[dense] if dense.any() else err[:0]
             worst[key] = (float(err.max()) / scale) if err.size else 0.0
         if pre + "cg_x" in z.files:
@@ -124,7 +123,8 @@ def test_hip_matches_golden(gpu, path, fast_math):
         # (20 u * 1 ~ 1e-6 per particle; 2e-5 leaves room for pow() vs t*t*t near q = 1 and for the fast build's v_rcp / v_rsq),
         # velocities / positions integrated from them over <= 30 steps (derivation: tests/test_big_golden.py).
         parity = {"positions": 1e-5, "velocities": 5e-5, "densities": 2e-5, "rest_volumes": 5e-6, "masses": 5e-6, "alphas": 5e-5,
-                  "densities_star": 1e-5, "cg_x": 2e-5, "rigid_forces": 2e-5, "rigid_torques": 5e-5, "acc_backward": 1.0, "drho_backward": 5e-6}
+                  "densities_star": 1e-5, "cg_x": 2e-5, "rigid_forces": 2e-5, "rigid_torques": 5e-5, "acc_backward": 1.0, "drho_backward": 5e-6,
+                  "alpha_backward": 1.0}
         # REGRESSION GUARDS, not parity claims: quantities that cancel (D rho / Dt, kappa, accelerations: |sum| << sum |terms|) or
         # amplify (p = 50000 ((rho/rho0)^7 - 1): a density difference times 7 * 50000 / max|p|).  Their error relative to the
         # field's maximum is the conditioning of the scene, not of the code; the numbers below are a few times the worst error the
@@ -135,8 +135,8 @@ def test_hip_matches_golden(gpu, path, fast_math):
         # but since round 6 only as regression guards: their formulas are pinned from the product's own inputs in tests/test_hip_solvers.py
         # (test_dfsph_kappa_per_term: kappa = (rho* - 1) alpha / dt to 3 u against the pass's own rho* and alpha, kappa_v = D rho / Dt x alpha
         # bit for bit; test_pcisph_pressure_update_per_term: p = max(0, p_prev + k (rho0 - rho*)) bit for bit), their inputs by the parity
-        # limits above.  What is left fitted with nothing behind it: alpha of particles with a near-empty neighbourhood (conditioning, see above).
-        guard = {"kappa": 1e-3, "kappa_v": 1e-3, "densities_derivatives": 4e-3, "pressures": 2e-3, "accelerations": 2e-3, "alphas_sparse": 1e-3}
+        # limits above.  PCISPH accelerations and alphas of sparse particles are checked per term below, no longer by a fitted number.
+        guard = {"kappa": 1e-3, "kappa_v": 1e-3, "densities_derivatives": 4e-3, "pressures": 2e-3, "accelerations": 2e-3}
         if method == "wcsph" and pre + "pressures" in z.files:
             # PER-TERM check instead of the fitted guard: the EOS p = 50000 ((rho / rho0)^7 - 1) (WCSPH.py:17-24) on the
             # product's OWN stored (clamped) density -- the density is pinned to the fixture by the parity limit above, the formula here:
@@ -148,24 +148,53 @@ def test_hip_matches_golden(gpu, path, fast_math):
                 err = np.abs(pp.astype(np.float64) - 50000.0 * (x7 - 1.0)) / (50000.0 * x7)
                 assert rr.min() >= rho0 and err.max() <= 4e-6, (cp, tag, float(err.max()))
             worst.pop("pressures", None)
-            # ... and the pressure acceleration, the field the step leaves in `accelerations` (WCSPH.py:63-70): every pair term recomputed
+        if method in ACC_METHODS and pre + "pressures" in z.files:
+            # The pressure acceleration, the field the step leaves in `accelerations` (WCSPH.py:63-70; PCISPH.py:170-175: after the
+            # solve, base_solver.py:136-178 on the solved pressures at the positions the step started from): every pair term recomputed
             # in float64 from the product's own density / pressure and the positions the step started from.  Bound per component:
             # ~12 roundings per term (difference, r, q, the polynomial, p / rho^2 twice, three products; v_rsq / v_rcp 1 ulp each in the
             # fast build) + a sum of <= 64 terms in any order: (12 + 64) u = 4.5e-6 of sum_j |term_j|; 1e-5 asserted -- plus the ~3
             # roundings that reach q = r / h times the conditioning of the kernel gradient in q (amp_j, see the helper: a neighbour
             # near the edge of the support contributes (1 - q)^2, i.e. 2 q / (1 - q) times the error of q): 5e-7 of sum_j |term_j| amp_j.
             # This is a backward-error statement (relative to sum |terms|, not to |sum|), so it holds however badly the scene cancels.
-            if len(ids_before) == len(ids):   # no emitter / late block came in during the step
-                get = lambda fid: H.by_id(ids, e.download(fid))
-                mat_now = get(L.F_MATERIAL)
-                if np.array_equal(mat_now, H.by_id(ids_before, mat_before)) and not (set(np.unique(mat_now)) - {1, 2}):
-                    a64, mag, mag_amp = H.wcsph_pressure_accel_f64(H.by_id(ids_before, x_before), get(L.F_DENSITY), get(L.F_PRESSURE), get(L.F_MASS),
-                                                          get(L.F_REST_VOLUME), mat_now, container.dh, rho0)
-                    err = np.abs(get(L.F_ACCELERATION).astype(np.float64) - a64)[fluid]
-                    bound = 1e-5 * mag[fluid] + 5e-7 * mag_amp[fluid] + 1e-30
-                    assert (err <= bound).all(), (cp, "pressure acceleration", float((err / bound).max()))
-                    worst.pop("accelerations", None)
-                    worst["acc_backward"] = float((err / bound).max())   # fraction of the derived bound
+            # The particles and materials are those of the time of the force pass: a block that came in during the step (ids beyond
+            # the old count, no neighbour of anyone then) and fluid the emitter released at its end (material 2 then: acceleration 0).
+            rho0 = float(cfg["Configuration"]["density0"])
+            n0 = len(ids_before)
+            get = lambda fid: H.by_id(ids, e.download(fid))[:n0]
+            mat0 = H.by_id(ids_before, mat_before)
+            if not (set(np.unique(mat0)) - {1, 2}):
+                a64, mag, mag_amp = H.wcsph_pressure_accel_f64(H.by_id(ids_before, x_before), get(L.F_DENSITY), get(L.F_PRESSURE), get(L.F_MASS),
+                                                               get(L.F_REST_VOLUME), mat0, container.dh, rho0)
+                rows = fluid[:n0] | (mat0 == 1)
+                err = np.abs(get(L.F_ACCELERATION).astype(np.float64) - a64)[rows]
+                bound = 1e-5 * mag[rows] + 5e-7 * mag_amp[rows] + 1e-30
+                assert (err <= bound).all(), (cp, "pressure acceleration", float((err / bound).max()))
+                worst.pop("accelerations", None)
+                worst["acc_backward"] = float((err / bound).max())   # fraction of the derived bound
+            assert method != "pcisph" or "accelerations" not in worst, (cp, "PCISPH accelerations went unchecked")
+        if method == "dfsph" and pre + "alphas" in z.files:
+            # PER-TERM check of alpha on EVERY fluid particle (sparse ones included), instead of a fitted guard: alpha belongs to the
+            # stored positions (DFSPH.py:316-319: computed after the end-of-step sort, before the divergence solve, which moves only
+            # velocities); S and its backward-error bound B in float64 from the product's own positions / rest volumes / materials
+            # (derivation: H.dfsph_alpha_f64).  Where [S - B, S + B] straddles the 1e-5 cut either branch is accepted.
+            getn = lambda fid: H.by_id(ids, e.download(fid))
+            mat_now = getn(L.F_MATERIAL)
+            S, B = H.dfsph_alpha_f64(getn(L.F_POSITION), getn(L.F_REST_VOLUME), mat_now, container.dh)
+            al = getn(L.F_DFSPH_ALPHA).astype(np.float64)
+            u = 2.0 ** -24
+            fl = mat_now == 1
+            with np.errstate(divide="ignore"):
+                lo = (1 - 2 * u) / (S + B)
+                hi = (1 + 2 * u) / np.maximum(S - B, 1e-5)
+            a64 = np.where(S > 1e-5, 1.0 / np.maximum(S, 1e-300), 0.0)
+            pos, zero = fl & (S - B > 1e-5), fl & (S + B <= 1e-5)
+            amb = fl & ~pos & ~zero
+            in_range = (al >= lo) & (al <= hi)
+            assert in_range[pos].all() and (al[zero] == 0).all() and ((al[amb] == 0) | in_range[amb]).all(), (
+                cp, "alpha", float(np.abs(al - a64)[fl].max()))
+            half = np.maximum(hi - a64, a64 - lo)
+            worst["alpha_backward"] = float((np.abs(al - a64) / half)[pos].max()) if pos.any() else 0.0   # fraction of the derived bound
         if method == "dfsph" and "densities_derivatives" in worst:
             # PER-TERM check instead of the fitted guard: the divergence solve is the last thing a DFSPH step does (DFSPH.py:316-319), so
             # the stored D rho / Dt belongs to the stored positions and velocities: max(sum_j V_j (v_i - v_j) . grad W_ij, 0), zero below
