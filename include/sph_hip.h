@@ -35,7 +35,13 @@ typedef enum {
     SPH_ERR_UNSUPPORTED = -6
 } SphStatus;
 
-typedef enum { SPH_METHOD_WCSPH = 0, SPH_METHOD_DFSPH = 1, SPH_METHOD_PCISPH = 2 } SphMethod;
+/* SPH_METHOD_IISPH: SPH/fluid_solvers/IISPH.py as written (omega 0.2, eta 0.001, at most 20 relaxed-Jacobi iterations, :12-14),
+   with ONE deviation: for a rigid neighbour, compute_dii (:40-44) divides by rho_i^2 -- the density this step's compute_density
+   wrote for particle i -- where the reference reads particle_densities_star[p_i], which it has not computed yet in that step
+   (zero on the first step: division by zero) and which its sort does not move (another particle's value afterwards).  rho_i
+   is the d_ii of the IISPH paper and is defined at every step.  All-fluid scenes never take that branch.  Single GPU only:
+   a sharded handle (sph_comm_set_slab) fails in sph_prepare with SPH_ERR_UNSUPPORTED. */
+typedef enum { SPH_METHOD_WCSPH = 0, SPH_METHOD_DFSPH = 1, SPH_METHOD_PCISPH = 2, SPH_METHOD_IISPH = 3 } SphMethod;
 
 /* Scene / solver constants.  Mirrors what BaseContainer.__init__ (base_container.py:10-60)
    and BaseSolver.__init__ (SPH/fluid_solvers/base_solver.py:9-54) derive from the JSON. */
@@ -56,7 +62,7 @@ typedef struct {
     int32_t particle_max_num;/* base_container.py:116 */
     int32_t viscosity_implicit; /* base_solver.py:40 viscosityMethod == "implicit" */
     int32_t method;          /* SphMethod; run_simulation.py:46-63 */
-    int32_t fixed_iterations;/* 0: reference stopping rules; >0: exactly this many DFSPH/PCISPH/CG iterations */
+    int32_t fixed_iterations;/* 0: reference stopping rules; >0: exactly this many DFSPH/PCISPH/IISPH/CG iterations */
     int32_t fast_math;       /* 0: IEEE div/sqrt, no FMA contraction; 1: v_rcp/v_rsq + FMA */
     int32_t device;          /* HIP device ordinal, -1: current */
     int32_t force_global;    /* debug mode of the neighbour passes: 0 normal; 1 every candidate run through the tile in chunks; 4 every group down the ordered walk; ... */
@@ -100,6 +106,11 @@ typedef enum {
     SPH_F_DFSPH_KAPPA_V_NEXT = 25, /* f32[n] D rho_i / Dt * alpha_i of the LAST density_derivative pass (pairs with SPH_F_DENSITY_DERIV) */
     SPH_F_DEBUG_CAPTURE = 26,      /* f32[n] libsph_hip_testhooks.so only: PCISPH pressure BEFORE the last executed update_pressure
                                       (PCISPH.py:66-73); the production library leaves the density pass's scratch there */
+    /* IISPH (iisph_container.py:14-20; allocated for SPH_METHOD_IISPH only; rho* is SPH_F_DENSITY_STAR, IISPH.py:71): */
+    SPH_F_IISPH_DII = 27,          /* f32[n][3] dii    (IISPH.py:18 compute_dii, rigid term: see SphMethod) */
+    SPH_F_IISPH_AII = 28,          /* f32[n]    iisph_aii (IISPH.py:47 compute_aii) */
+    SPH_F_IISPH_DIJ_PJ = 29,       /* f32[n][3] dij_pj (IISPH.py:125 compute_dij_pj, last executed iteration) */
+    SPH_F_IISPH_SUM_I = 30,        /* f32[n]    sum_i  (IISPH.py:148 compute_sum_i, last executed iteration) */
     SPH_F_COUNT_
 } SphField;
 
@@ -114,6 +125,8 @@ typedef enum {
     SPH_PH_DFSPH_ALPHA = 5,      /* DFSPH.py:23 */
     SPH_PH_DFSPH_DIVERGENCE = 6, /* DFSPH.py:139 */
     SPH_PH_DFSPH_DENSITY = 7,    /* DFSPH.py:225 */
+    SPH_PH_IISPH_PREPARE = 8,    /* IISPH.py:93 init_step + :18 compute_dii + :47 compute_aii + :71 compute_density_star */
+    SPH_PH_IISPH_ITERATION = 9,  /* one iteration of IISPH.py:185 refine: compute_dij_pj, compute_sum_i, update_pressure (+ error) */
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -137,6 +150,8 @@ typedef struct {
     int64_t list_sorts;          /* deterministic sorts since create that ranked the particles from per-cell run lists filed by whoever
                                     hashed them (reorder_particles, base_container.py:506-515, in two launches: rank + gather with the
                                     per-tile preparation of the neighbour passes fused in) instead of run records filed after the scan */
+    int32_t iter_iisph;          /* IISPH.py:185 refine: iterations of the last step (last SPH_PH_IISPH_ITERATION phase: 1) */
+    float   err_iisph;           /* its density_error (IISPH.py:118-121; 0 with fixed_iterations > 0, as err_* of the others) */
 } SphStats;
 
 /* Kernel ids for the HIP-event profiler (sph_profile_*). */
@@ -146,7 +161,8 @@ typedef enum {
     SPH_K_DFSPH_DENSITY_ALPHA = 7, SPH_K_DFSPH_RHO_ADV = 8, SPH_K_DFSPH_CORRECT = 9,
     SPH_K_REDUCE = 10, SPH_K_PCISPH_RHO_STAR = 11, SPH_K_PCISPH_PRESSURE_ACCEL = 12,
     SPH_K_CG_PREPARE = 13, SPH_K_CG_AP = 14, SPH_K_CG_VECTOR = 15, SPH_K_MISC = 16,
-    SPH_K_HALO = 17, SPH_K_WCSPH_FORCES = 18, SPH_K_COUNT_
+    SPH_K_HALO = 17, SPH_K_WCSPH_FORCES = 18,
+    SPH_K_IISPH_PREPARE = 19, SPH_K_IISPH_DIJ_PJ = 20, SPH_K_IISPH_SUM_I = 21, SPH_K_COUNT_
 } SphKernelId;
 
 /* --- lifetime -------------------------------------------------------------------------- */

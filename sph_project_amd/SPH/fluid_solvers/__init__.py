@@ -1,3 +1,4 @@
 from .DFSPH import DFSPHSolver
 from .WCSPH import WCSPHSolver
 from .PCISPH import PCISPHSolver
+from .IISPH import IISPHSolver

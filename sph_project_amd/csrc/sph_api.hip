@@ -225,7 +225,8 @@ extern "C" const char *sph_kernel_name(int k) {
     static const char *names[SPH_K_COUNT_] = {
         "hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate", "rigid_volume",
         "dfsph_density_alpha", "dfsph_rho_adv", "dfsph_correct", "reduce", "pcisph_rho_star",
-        "pcisph_pressure_accel", "cg_prepare", "cg_ap", "cg_vector", "misc", "halo", "wcsph_forces"};
+        "pcisph_pressure_accel", "cg_prepare", "cg_ap", "cg_vector", "misc", "halo", "wcsph_forces",
+        "iisph_prepare", "iisph_dij_pj", "iisph_sum_i"};
     return (k >= 0 && k < SPH_K_COUNT_) ? names[k] : "?";
 }
 
@@ -263,7 +264,7 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     // sharding: 2^28 - 1 particles per handle (~70 GB of state; a bigger scene is sharded over GPUs)
     if (p.particle_max_num > 0x0fffffff)
         return fail(nullptr, SPH_ERR_CAPACITY, "sph_create: particle_max_num %d exceeds 268435455 per GPU; shard the scene (sph_comm_set_slab)", p.particle_max_num);
-    if (p.method < 0 || p.method > 2) return fail(nullptr, SPH_ERR_INVALID, "sph_create: unknown method %d", p.method);
+    if (p.method < 0 || p.method > SPH_METHOD_IISPH) return fail(nullptr, SPH_ERR_INVALID, "sph_create: unknown method %d", p.method);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(nullptr, SPH_ERR_NO_DEVICE, "sph_create: no HIP device visible (libsph_hip has no CPU path)");
@@ -340,6 +341,7 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     if (s.nbr_mask && !getenv("SPH_NO_LANE_PERM")) CHK_CREATE(dalloc(h, &s.lane_perm, (cap + 255) / 256 * 256));
     s.alpha = s.kappa = s.kappa_v = s.rho_star = s.rho_deriv = s.kappa_next = s.kappa_v_next = nullptr; s.kr = nullptr;
     s.pacc = s.pvel = s.ppos = s.acc_np = nullptr; s.np_acc_out = nullptr; s.np_visc_vel = nullptr;
+    s.iisph_dii = s.iisph_dij = s.iisph_w = nullptr;
     s.cg_p2 = nullptr; s.cg_fuse = s.cg_fused_loop = 0;
     s.cg_p = s.cg_Ap = s.cg_x = s.cg_b = s.cg_r = s.cg_v0 = nullptr; s.cg_dinv = nullptr; s.cg_part = nullptr; s.cg_split = 0; s.cg_nocombine = 0; s.split_next_pass = 0;
     if (p.method == SPH_METHOD_DFSPH) {
@@ -351,6 +353,10 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
         CHK_CREATE(dalloc(h, &s.pacc, cap)); CHK_CREATE(dalloc(h, &s.pvel, cap)); CHK_CREATE(dalloc(h, &s.ppos, cap));
         CHK_CREATE(dalloc(h, &s.rho_star, cap)); CHK_CREATE(dalloc(h, &s.acc_np, cap));
         s.np_acc_out = s.acc_np;
+    }
+    if (p.method == SPH_METHOD_IISPH) {   // IISPH.py scratch: 52 bytes per particle, only for this method
+        CHK_CREATE(dalloc(h, &s.iisph_dii, cap)); CHK_CREATE(dalloc(h, &s.iisph_dij, cap)); CHK_CREATE(dalloc(h, &s.iisph_w, cap));
+        CHK_CREATE(dalloc(h, &s.rho_star, cap));
     }
     if (p.viscosity_implicit) {
         CHK_CREATE(dalloc(h, &s.cg_p, cap)); CHK_CREATE(dalloc(h, &s.cg_Ap, cap)); CHK_CREATE(dalloc(h, &s.cg_x, cap));
@@ -733,6 +739,8 @@ extern "C" int sph_prepare(SphHandle *h) {
     HIPCHK(h, hipSetDevice(h->device));
     refresh_counts(h);
     State &s = h->st;
+    if (s.slab_active && h->prm.method == SPH_METHOD_IISPH)
+        return fail(h, SPH_ERR_UNSUPPORTED, "sph_prepare: IISPH runs on one GPU only (no sharded IISPH solve: sph_comm_set_slab)");
     int rc = upload_pose(h); if (rc) return rc;
     // base_solver.py:683 prepare: prepare_emitter, renew_rigid_particle_state, neighbour search,
     // compute_rigid_particle_volume (+ DFSPH.py:321 / PCISPH.py:188)
@@ -775,6 +783,7 @@ static int step_first_half(SphHandle *h, bool allow_readback) {
     switch (h->prm.method) {
         case SPH_METHOD_WCSPH: rc = wcsph_step(h); break;                     // WCSPH.py:28-36 (:45 boundary fused into the position update)
         case SPH_METHOD_DFSPH: rc = dfsph_step_begin(h, allow_readback); break;
+        case SPH_METHOD_IISPH: rc = iisph_step(h, allow_readback); break;     // IISPH.py:204-220
         default: rc = pcisph_step(h, allow_readback); break;                  // PCISPH.py:166-177
     }
     if (rc) return rc;
@@ -936,6 +945,8 @@ static const float4 *vec_field(SphHandle *h, int field) {
         case SPH_F_PREDICTED_POS: return s.ppos;
         case SPH_F_CG_X: return s.cg_x;
         case SPH_F_ORIG_POSITION: return s.orig.cur() ? s.orig.cur() : s.posv.cur();
+        case SPH_F_IISPH_DII: case SPH_F_IISPH_AII: return s.iisph_dii;     // (dii, aii)
+        case SPH_F_IISPH_DIJ_PJ: case SPH_F_IISPH_SUM_I: return s.iisph_dij; // (dij_pj, sum_i)
         default: return nullptr;
     }
 }
@@ -965,7 +976,7 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
     HIPCHK(h, hipStreamSynchronize(s.stream));
     const bool is_vec3 = field == SPH_F_POSITION || field == SPH_F_VELOCITY || field == SPH_F_ACCELERATION ||
                          field == SPH_F_PRESSURE_ACCEL || field == SPH_F_PREDICTED_VEL || field == SPH_F_PREDICTED_POS ||
-                         field == SPH_F_CG_X || field == SPH_F_ORIG_POSITION;
+                         field == SPH_F_CG_X || field == SPH_F_ORIG_POSITION || field == SPH_F_IISPH_DII || field == SPH_F_IISPH_DIJ_PJ;
     if (is_vec3) {
         const float4 *src = vec_field(h, field);
         if (!src) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);
@@ -977,10 +988,12 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
         for (size_t i = 0; i < n; ++i) { const float v[3] = {tmp[i].x, tmp[i].y, tmp[i].z}; d[3 * i] = v[ix0]; d[3 * i + 1] = v[ix1]; d[3 * i + 2] = v[ix2]; }
         return SPH_OK;
     }
-    if (field == SPH_F_REST_VOLUME || field == SPH_F_MASS) {
+    if (field == SPH_F_REST_VOLUME || field == SPH_F_MASS || field == SPH_F_IISPH_AII || field == SPH_F_IISPH_SUM_I) {
         if (bytes != n * 4) return fail(h, SPH_ERR_INVALID, "download: size mismatch");
+        const float4 *src = vec_field(h, field);
+        if (!src) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);
         std::vector<float4> tmp(n);
-        HIPCHK(h, hipMemcpy(tmp.data(), vec_field(h, field), n * sizeof(float4), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(tmp.data(), src, n * sizeof(float4), hipMemcpyDeviceToHost));
         float *d = (float *)dst;
         for (size_t i = 0; i < n; ++i) d[i] = tmp[i].w;
         return SPH_OK;

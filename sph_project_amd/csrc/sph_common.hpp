@@ -15,6 +15,10 @@
 #include <stdint.h>
 
 #define SPH_NOBJ 20
+// IISPH.py:12-14: relaxation factor, stop threshold of the average density error, iteration cap
+#define SPH_IISPH_OMEGA 0.2f
+#define SPH_IISPH_ETA 0.001
+#define SPH_IISPH_MAX_ITER 20
 
 // meta packing
 #define META_OBJ(m) (((m) & 0xff) - 1)
@@ -231,6 +235,8 @@ struct State {
     float2 *kr;          // (kappa, rho) staging pair for the correction pass
     // PCISPH
     float4 *pacc, *pvel, *ppos, *acc_np;
+    // IISPH (allocated for that method only): (dii, aii), (dij_pj, sum_i), w = dii p + dij_pj; rho* in rho_star
+    float4 *iisph_dii, *iisph_dij, *iisph_w;
     // CG (implicit viscosity)
     float4 *cg_p, *cg_Ap, *cg_x, *cg_b, *cg_r, *cg_v0;
     float4 *cg_p2;       // second search-direction buffer (fused p update: the A p pass reads the old one and writes the new one)
@@ -347,6 +353,10 @@ struct Launch {
     void (*pcisph_init)(State &);
     void (*pcisph_rho_star)(State &);
     void (*pcisph_pressure_accel)(State &);
+    // IISPH
+    void (*iisph_prepare)(State &);             // dii + aii + rho* (IISPH.py:18-90), p = 0
+    void (*iisph_dij_pj)(State &);              // first walk of an iteration (IISPH.py:125, + w = dii p + dij_pj)
+    void (*iisph_sum_i)(State &);               // second walk: sum_i + update_pressure + the error's reduction (IISPH.py:148, :98)
     // z-slab sharding
     void (*halo_classify_pack)(State &, int n);
     void (*halo_unpack_append)(State &, int side, int count, int offset);

@@ -405,3 +405,190 @@ struct PcisphPressureAccelPass {
     }
     __device__ void passive(const Consts &, int i, const float4 &) const { pacc[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
 };
+
+// ---------------------------------------------------------------------------------------
+// IISPH.py:18 compute_dii (+task :27) + :47 compute_aii (+task :56) + :71 compute_density_star (+task :81), one walk.
+// aii needs its neighbours only through sum m0_j grad W_ij and sum m0_j |grad W_ij|^2 (rigid and fluid neighbours alike, :65):
+//   aii_i = dt^2 (dii_i . sum m0_j grad W - m0_i / rho_i^2 sum m0_j |grad W|^2),
+// so dii, aii and rho* come out of the same neighbours (summation order differs from the reference's three loops).  The rigid
+// branch of dii (:38-44) divides by rho_i^2 where the reference reads particle_densities_star[p_i], a value it has not computed
+// yet in this step (0 on the first one) and does not carry through the sort.  The pass also clears p and p / rho^2
+// (init_step, :93-95).  Staged: V_j (negative for rigid neighbours) and (v_j, rho0 V_j / rho_j^2).
+// Bytes / particle: R posv 16 + velm 16 + rho 4 -> W (dii, aii) 16 + rho* 4 + prs 4 + ptm 4.
+template <bool AF>
+struct IisphPreparePass {
+    static constexpr int BLOCK = 256, GROUPS = 3;
+    static constexpr bool USES_J = !AF;   // pair() looks at j only for rigid neighbours
+    static constexpr bool HAS_B = true, COUNT_PAIRS = true, HAS_REDUCE = false;
+    static constexpr int PAIR_WEIGHT = 3;   // compute_dii + compute_aii + compute_density_star of the reference
+    struct BT { float x, y, z, q; };        // v_j, rho0 V_j / rho_j^2 (0 for a rigid neighbour)
+    struct Own { float vx, vy, vz, gx, gy, gz, s2, d, fx, fy, fz, rx, ry, rz; };
+    const float4 *posv, *velm; const int *meta; const float *rho;
+    float4 *dii_aii; float *rho_star, *prs, *ptm; float rho0; float *red_out;
+
+    __device__ float4 stage_impl(int j, BT &bj) const {
+        float4 p = ldg_idx(posv, j);
+        const float4 v = ldg_idx(velm, j);
+        bj.x = v.x; bj.y = v.y; bj.z = v.z;
+        if (!AF && META_MAT(meta[j]) != 1) { p.w = -p.w; bj.q = 0.0f; return p; }
+        const float r = ldg_idx(rho, j);
+        bj.q = fdiv(rho0 * p.w, r * r);
+        return p;
+    }
+    __device__ float4 loadA(int j) const { BT b; return stage_impl(j, b); }
+    __device__ BT loadB(int j) const { BT b; stage_impl(j, b); return b; }
+    __device__ float4 stage(const Consts &, int j, BT &bj) const { return stage_impl(j, bj); }
+    __device__ bool begin(const Consts &c, int i, const float4 &, Own &o) const {
+        bool ok = true;   // no early return: begin()'s loads go out with the rest of the prologue (k_nbr_pass)
+        if (!AF || c.ghosts) ok = META_ACTIVE_FLUID(meta[i]);
+        const float4 v = velm[i];
+        o.vx = v.x; o.vy = v.y; o.vz = v.z;
+        o.gx = o.gy = o.gz = o.s2 = o.d = 0.0f;
+        o.fx = o.fy = o.fz = o.rx = o.ry = o.rz = 0.0f;
+        return ok;
+    }
+    __device__ void pair(const Consts &c, Own &o, float dx, float dy, float dz, float r2, const float4 &a, const BT &bj, int) const {
+        float gx, gy, gz;
+        kernGrad(c, dx, dy, dz, geom(c, r2), gx, gy, gz);
+        const float V = fabsf(a.w);
+        const float vgx = V * gx, vgy = V * gy, vgz = V * gz;
+        o.gx += vgx; o.gy += vgy; o.gz += vgz;
+        o.s2 += vgx * gx + vgy * gy + vgz * gz;
+        o.d += (o.vx - bj.x) * vgx + (o.vy - bj.y) * vgy + (o.vz - bj.z) * vgz;
+        o.fx -= bj.q * gx; o.fy -= bj.q * gy; o.fz -= bj.q * gz;   // fluid neighbour (:33-38); bj.q = 0 for a rigid one
+        if (!AF && a.w < 0.0f) { o.rx -= vgx; o.ry -= vgy; o.rz -= vgz; }   // rigid neighbour (:40-44), / rho_i^2 in finish()
+    }
+    __device__ float finish(const Consts &c, int i, const float4 &pi, Own &o) const {
+        const float r = rho[i];
+        const float r2 = r * r;
+        float dx = o.fx, dy = o.fy, dz = o.fz;
+        if (!AF) { dx += fdiv(rho0 * o.rx, r2); dy += fdiv(rho0 * o.ry, r2); dz += fdiv(rho0 * o.rz, r2); }
+        const float gx = rho0 * o.gx, gy = rho0 * o.gy, gz = rho0 * o.gz;
+        const float dji = fdiv(rho0 * pi.w, r2);   // m0_i / rho_i^2 (:62)
+        const float aii = ((dx * gx + dy * gy + dz * gz) - dji * (rho0 * o.s2)) * c.dt * c.dt;
+        dii_aii[i] = make_float4(dx, dy, dz, aii);
+        rho_star[i] = r + c.dt * (rho0 * o.d);
+        prs[i] = 0.0f; ptm[i] = 0.0f;
+        return 0.0f;
+    }
+    __device__ void passive(const Consts &, int i, const float4 &) const { prs[i] = 0.0f; ptm[i] = 0.0f; }
+};
+
+// IISPH.py:125 compute_dij_pj (+task :133): fluid neighbours only.  finish() also stores w_i = dii_i p_i + dij_pj_i, the only
+// thing the sum_i pass needs of a fluid neighbour.  Staged: V_j (0 for a rigid neighbour) and p_j / rho_j^2.
+// Bytes / particle: R posv 16 + ptm 4 + (dii, aii) 16 + prs 4 -> W (dij_pj, sum_i) 12 + w 16.
+template <bool AF>
+struct IisphDijPjPass {
+    static constexpr bool FLUID_BLOCKS_ONLY = true;   // active for fluid only, passive() empty
+    static constexpr int BLOCK = 256, GROUPS = 3;
+    static constexpr bool USES_J = !AF;   // pair() looks at j only for rigid neighbours
+    static constexpr bool HAS_B = true, COUNT_PAIRS = true, HAS_REDUCE = false;
+    static constexpr int PAIR_WEIGHT = 1;
+    typedef float BT;
+    struct Own { float x, y, z; };
+    const float4 *posv; const int *meta; const float *ptm, *prs; const float4 *dii_aii;
+    float4 *dij_sum, *w; float rho0; float *red_out;
+
+    __device__ float4 stage_impl(int j, BT &bj) const {
+        float4 p = posv[j];
+        if (!AF && META_MAT(meta[j]) != 1) { p.w = 0.0f; bj = 0.0f; return p; }
+        bj = ptm[j];
+        return p;
+    }
+    __device__ float4 loadA(int j) const { BT b; return stage_impl(j, b); }
+    __device__ BT loadB(int j) const { BT b; stage_impl(j, b); return b; }
+    __device__ float4 stage(const Consts &, int j, BT &bj) const { return stage_impl(j, bj); }
+    __device__ bool begin(const Consts &c, int i, const float4 &, Own &o) const {
+        bool ok = true;   // no early return: begin()'s loads go out with the rest of the prologue (k_nbr_pass)
+        if (!AF || c.ghosts) ok = META_ACTIVE_FLUID(meta[i]);
+        o.x = o.y = o.z = 0.0f;
+        return ok;
+    }
+    __device__ void pair(const Consts &c, Own &o, float dx, float dy, float dz, float r2, const float4 &a, const BT &bj, int) const {
+#if SPH_FAST
+        const float k = (-a.w * bj) * kernGradScale(c, geom(c, r2));   // scalar x (x_i - x_j)
+        o.x += k * dx; o.y += k * dy; o.z += k * dz;
+#else
+        float gx, gy, gz;
+        kernGrad(c, dx, dy, dz, geom(c, r2), gx, gy, gz);
+        const float k = -a.w * bj;
+        o.x += k * gx; o.y += k * gy; o.z += k * gz;
+#endif
+    }
+    __device__ float finish(const Consts &, int i, const float4 &, Own &o) const {
+        const float x = rho0 * o.x, y = rho0 * o.y, z = rho0 * o.z;
+        float *ds = reinterpret_cast<float *>(dij_sum + i);   // (.w holds sum_i: IisphSumIPass)
+        ds[0] = x; ds[1] = y; ds[2] = z;
+        const float4 d = dii_aii[i];
+        const float p = prs[i];
+        w[i] = make_float4(d.x * p + x, d.y * p + y, d.z * p + z, 0.0f);
+        return 0.0f;
+    }
+    __device__ void passive(const Consts &, int, const float4 &) const {}
+};
+
+// IISPH.py:148 compute_sum_i (+task :157) + :98 update_pressure, fused; the reduction leaves the partial sums of the error.
+// With w_j = dii_j p_j + dij_pj_j the fluid term of :166-174 is m0_j (dij_pj_i - w_j + m0_i / rho_i^2 p_i grad W_ij) . grad W_ij,
+// the rigid one (:176-181) m0_j dij_pj_i . grad W_ij.  Staged: V_j (negative for a rigid neighbour) and w_j (0 for a rigid one).
+// Bytes / particle: R posv 16 + w 16 + (dij_pj, sum_i) 16 + (dii, aii) 16 + prs 4 + rho 4 + rho* 4 -> W sum_i 4 + prs 4 + ptm 4.
+template <bool AF>
+struct IisphSumIPass {
+    static constexpr bool FLUID_BLOCKS_ONLY = true;   // active for fluid only, passive() empty
+    static constexpr int BLOCK = 256, GROUPS = 3;
+    static constexpr bool USES_J = !AF;   // pair() looks at j only for rigid neighbours
+    static constexpr bool HAS_B = true, COUNT_PAIRS = true, HAS_REDUCE = true;
+    static constexpr int PAIR_WEIGHT = 1;
+    struct BT { float x, y, z; };   // w_j
+    struct Own { float px, py, pz, cp, s; };
+    const float4 *posv, *w; const int *meta; const float *rho, *rho_star; const float4 *dii_aii;
+    float4 *dij_sum; float *prs, *ptm; float rho0, omega; float *red_out;
+
+    __device__ float4 stage_impl(int j, BT &bj) const {
+        float4 p = ldg_idx(posv, j);
+        if (!AF && META_MAT(meta[j]) != 1) { p.w = -p.w; bj.x = bj.y = bj.z = 0.0f; return p; }
+        const float4 q = ldg_idx(w, j);
+        bj.x = q.x; bj.y = q.y; bj.z = q.z;
+        return p;
+    }
+    __device__ float4 loadA(int j) const { BT b; return stage_impl(j, b); }
+    __device__ float4 stage(const Consts &, int j, BT &bj) const { return stage_impl(j, bj); }
+    __device__ bool begin(const Consts &c, int i, const float4 &pi, Own &o) const {
+        bool ok = true;   // no early return: begin()'s loads go out with the rest of the prologue (k_nbr_pass)
+        if (!AF || c.ghosts) ok = META_ACTIVE_FLUID(meta[i]);
+        const float4 d = dij_sum[i];
+        o.px = d.x; o.py = d.y; o.pz = d.z;
+        const float r = rho[i];
+        o.cp = fdiv(rho0 * pi.w, r * r) * prs[i];   // d_ji p_i / grad W_ij (:160-163)
+        o.s = 0.0f;
+        return ok;
+    }
+    __device__ void pair(const Consts &c, Own &o, float dx, float dy, float dz, float r2, const float4 &a, const BT &bj, int) const {
+        const float cp = (AF || a.w > 0.0f) ? o.cp : 0.0f;
+        const float V = fabsf(a.w);
+#if SPH_FAST
+        const float k = kernGradScale(c, geom(c, r2));   // grad W = k (x_i - x_j)
+        o.s += (V * k) * (((o.px - bj.x) * dx + (o.py - bj.y) * dy + (o.pz - bj.z) * dz) + (cp * k) * r2);
+#else
+        float gx, gy, gz;
+        kernGrad(c, dx, dy, dz, geom(c, r2), gx, gy, gz);
+        const float tx = o.px - bj.x + cp * gx, ty = o.py - bj.y + cp * gy, tz = o.pz - bj.z + cp * gz;
+        o.s += V * (tx * gx + ty * gy + tz * gz);
+#endif
+    }
+    __device__ float finish(const Consts &c, int i, const float4 &, Own &o) const {
+        const float sum_i = (rho0 * o.s) * c.dt * c.dt;
+        reinterpret_cast<float *>(dij_sum + i)[3] = sum_i;
+        const float aii = dii_aii[i].w;
+        const float si = rho0 - rho_star[i];
+        float p = 0.0f;
+        if (aii > 1e-10f || aii < -1e-10f) {   // :103-110
+            p = (1.0f - omega) * prs[i] + fdiv(omega, aii) * (si - sum_i);
+            p = fmaxf(0.0f, p);
+        }
+        prs[i] = p;
+        const float r = rho[i];
+        ptm[i] = fdiv(p, r * r);
+        return p > 1e-10f ? aii * p + sum_i - si : 0.0f;   // :114-117
+    }
+    __device__ void passive(const Consts &, int, const float4 &) const {}
+};

@@ -163,6 +163,30 @@ static void l_pcisph_pressure_accel(State &s) {
     if (s.c.n > 0 && !s.skip_residual) l_reduce_sum(s, 2, cdiv(s.c.n, NBR_BLOCK));   // density error of this iteration's rho* pass
 }
 
+// IISPH.py:18-90 (dii, aii, rho*; p = 0): after the non-pressure pass, velm.cur() = v*
+static void l_iisph_prepare(State &s) {
+    if (s.c.all_fluid) { IisphPreparePass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.iisph_dii, s.rho_star, s.prs, s.ptm, s.c.rho0, s.red_partial}; launch_pass(s, p, 2); }
+    else { IisphPreparePass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.iisph_dii, s.rho_star, s.prs, s.ptm, s.c.rho0, s.red_partial}; launch_pass(s, p, 2); }
+}
+
+// IISPH.py:125 compute_dij_pj (+ w = dii p + dij_pj), the first walk of an iteration of refine (:185)
+static void l_iisph_dij_pj(State &s) {
+    if (s.c.all_fluid) { IisphDijPjPass<true> p{s.posv.cur(), s.meta.cur(), s.ptm, s.prs, s.iisph_dii, s.iisph_dij, s.iisph_w, s.c.rho0, s.red_partial}; launch_pass(s, p, 2); }
+    else { IisphDijPjPass<false> p{s.posv.cur(), s.meta.cur(), s.ptm, s.prs, s.iisph_dii, s.iisph_dij, s.iisph_w, s.c.rho0, s.red_partial}; launch_pass(s, p, 2); }
+}
+
+// IISPH.py:148 compute_sum_i + :98 update_pressure, the second walk; the error's reduction closes the iteration
+static void l_iisph_sum_i(State &s) {
+    if (s.c.all_fluid) {
+        IisphSumIPass<true> p{s.posv.cur(), s.iisph_w, s.meta.cur(), s.rho.cur(), s.rho_star, s.iisph_dii, s.iisph_dij, s.prs, s.ptm, s.c.rho0, SPH_IISPH_OMEGA, s.red_partial};
+        launch_pass(s, p, 2);
+    } else {
+        IisphSumIPass<false> p{s.posv.cur(), s.iisph_w, s.meta.cur(), s.rho.cur(), s.rho_star, s.iisph_dii, s.iisph_dij, s.prs, s.ptm, s.c.rho0, SPH_IISPH_OMEGA, s.red_partial};
+        launch_pass(s, p, 2);
+    }
+    if (s.c.n > 0 && !s.skip_residual) l_reduce_sum(s, 2, cdiv(s.c.n, NBR_BLOCK));   // IISPH.py:114-121 (slot 2: the pressure solve's, as PCISPH's)
+}
+
 // ---- implicit viscosity
 // WCSPH clamps particle_densities only after the non-pressure accelerations (WCSPH.py:29-33): its solve reads the unclamped
 // densities, like the explicit viscosity does (see l_non_pressure)
@@ -271,4 +295,7 @@ static void register_solver_launchers(Launch &L) {
     L.pcisph_init = l_pcisph_init;
     L.pcisph_rho_star = l_pcisph_rho_star;
     L.pcisph_pressure_accel = l_pcisph_pressure_accel;
+    L.iisph_prepare = l_iisph_prepare;
+    L.iisph_dij_pj = l_iisph_dij_pj;
+    L.iisph_sum_i = l_iisph_sum_i;
 }

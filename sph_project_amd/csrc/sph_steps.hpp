@@ -407,6 +407,49 @@ static int pcisph_step(SphHandle *h, bool allow_readback) {
     return SPH_OK;
 }
 
+// IISPH.py:185 refine: relaxed Jacobi, at least one iteration, stops when the average density error drops below eta (a negative
+// error stops it too) or after max_iterations.  The criterion is tested on the device (device_loop, kind 2: error < (float)eta,
+// error = sum / (fluid_particle_num rho0), :118-121).  fixed_iterations > 0: exactly that many, no read-back, error reported 0.
+static int iisph_refine(SphHandle *h, bool allow_readback) {
+    State &s = h->st;
+    SkipResidual skip(h);
+    const int fixed = h->prm.fixed_iterations;
+    const int max_itr = fixed > 0 ? fixed : SPH_IISPH_MAX_ITER;
+    const float denom = (float)h->n_fluid * (float)h->prm.density_0;
+    auto iteration = [&]() {
+        { ProfScope p(h, SPH_K_IISPH_DIJ_PJ); h->L->iisph_dij_pj(s); }     // :188
+        { ProfScope p(h, SPH_K_IISPH_SUM_I); h->L->iisph_sum_i(s); }       // :189-190 (+ the error's partial sums)
+    };
+    int itr = 0;
+    float err = 0.0f;
+    if (fixed <= 0) {
+        if (!allow_readback) return fail(h, SPH_ERR_UNSUPPORTED, "iisph needs host read-back unless fixed_iterations > 0");
+        int launched = 0; float sum = 0.0f;
+        int rc = device_loop(h, max_itr, 2, 2, denom, SPH_IISPH_ETA, iteration, &itr, &launched, &sum);   // :194-197
+        if (rc) return rc;
+        err = h->n_fluid > 0 ? sum / denom : 0.0f;
+    } else {
+        for (; itr < max_itr; ++itr) iteration();
+    }
+    h->last.iter_iisph = itr; h->last.err_iisph = err;
+    return SPH_OK;
+}
+
+// IISPH.py:203 _step up to the rigid solver: the sort, compute_density (no EOS), init_step + non-pressure forces + v* (:206-208, the
+// pressures are cleared by the prepare pass), dii / aii / rho* (:210-213), refine (:215), pressure acceleration + v, x update +
+// boundary (:218-220, :227: the same tail as PCISPH's)
+static int iisph_step(SphHandle *h, bool allow_readback) {
+    State &s = h->st;
+    s.sort_skip_rho = s.c.all_fluid; ph_neighbor_search(h);                  // :204 (:205 below rewrites every rho)
+    ph_rigid_volume(h);
+    { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 0); }                   // :205
+    int rc = run_non_pressure(h); if (rc) return rc;                          // :207-208
+    { ProfScope p(h, SPH_K_IISPH_PREPARE); h->L->iisph_prepare(s); }          // :206, :210-213
+    rc = iisph_refine(h, allow_readback); if (rc) return rc;                  // :215
+    { ProfScope p(h, SPH_K_PRESSURE_INTEGRATE); h->L->pressure_integrate(s); } // :218-220, :227
+    return SPH_OK;
+}
+
 // host replica of PCISPH.py:129 compute_pcisph_k (same arithmetic as oracle/sph_ref.c)
 static float host_pcisph_k(const SphParams &p) {
     const double hd = p.support_radius;
@@ -457,6 +500,20 @@ static int method_run_phase(SphHandle *h, int phase) {
             case SPH_PH_DFSPH_ALPHA: { ProfScope p(h, SPH_K_DFSPH_DENSITY_ALPHA); h->L->dfsph_density_alpha(s); } return SPH_OK;
             case SPH_PH_DFSPH_DIVERGENCE: return dfsph_divergence(h, true);
             case SPH_PH_DFSPH_DENSITY: return dfsph_density(h, true);
+            default: break;
+        }
+    } else if (h->prm.method == SPH_METHOD_IISPH) {
+        switch (phase) {
+            case SPH_PH_IISPH_PREPARE: { ProfScope p(h, SPH_K_IISPH_PREPARE); h->L->iisph_prepare(s); } return SPH_OK;
+            case SPH_PH_IISPH_ITERATION: {   // one iteration, no stop test; its error is read back
+                h->L->iisph_dij_pj(s);
+                h->L->iisph_sum_i(s);
+                float sum = 0.0f;
+                int rc = read_red(h, 2, &sum); if (rc) return rc;
+                const float denom = (float)h->n_fluid * (float)h->prm.density_0;
+                h->last.iter_iisph = 1; h->last.err_iisph = h->n_fluid > 0 ? sum / denom : 0.0f;
+                return SPH_OK;
+            }
             default: break;
         }
     }

@@ -90,6 +90,26 @@ def c5_scene(domain_end=(4.0, 20.0, 8.0), start=(1.12, 1.0, 1.0), end=(1.88, 12.
     }
 
 
+def iisph_bath_scene(domain_end=(5.0, 3.0, 2.0), start=(0.3, 0.2, 0.5), end=(1.2, 2.8, 1.6)):
+    """The configuration of the reference's IISPH scene data/scenes/dragon_bath_iisph.json: a 5 x 3 x 2 domain box, dx 0.01,
+    dt 8e-4, mu 10, mu_b 5, one fluid block (translated by (0.2, 0, 0.2)) falling at 1 m/s.  The arguments shrink the domain
+    and the block for tests; the defaults are the reference's numbers."""
+    return {
+        "Configuration": {
+            "domainStart": [0.0, 0.0, 0.0], "domainEnd": list(domain_end), "addDomainBox": True,
+            "particleRadius": 0.01, "fps": 30.0, "totalTime": 8.0, "density0": 1000,
+            "gravitation": [0.0, -9.81, 0.0], "simulationMethod": "iisph", "viscosityMethod": "standard",
+            "timeStepSize": 0.0008, "viscosity": 10.0, "viscosity_b": 5.0, "boundaryHandlingMethod": 0,
+            "exportFrame": True, "exportPly": False, "exportObj": False,
+        },
+        "FluidBlocks": [{
+            "objectId": 0, "start": list(start), "end": list(end), "translation": [0.2, 0.0, 0.2],
+            "scale": [1, 1, 1], "velocity": [0.0, -1.0, 0.0], "density": 1000.0, "color": [50, 100, 200],
+            "entryTime": -1.0,
+        }],
+    }
+
+
 def scene_particles(cfg_dict):
     """Host lattice of every object present at prepare(), in the reference's insertion order
     (domain box first: base_container.py:192, then FluidBlocks: :215).  Blocks with entryTime > 0 are listed with
@@ -122,8 +142,10 @@ def build_product(cfg_dict, **engine_opts):
     from .SPH import containers, fluid_solvers
     cfg = SimConfig(config=copy.deepcopy(cfg_dict))
     method = cfg.get_cfg("simulationMethod")
-    ccls = {"wcsph": containers.WCSPHContainer, "dfsph": containers.DFSPHContainer, "pcisph": containers.PCISPHContainer}[method]
-    scls = {"wcsph": fluid_solvers.WCSPHSolver, "dfsph": fluid_solvers.DFSPHSolver, "pcisph": fluid_solvers.PCISPHSolver}[method]
+    ccls = {"wcsph": containers.WCSPHContainer, "dfsph": containers.DFSPHContainer, "pcisph": containers.PCISPHContainer,
+            "iisph": containers.IISPHContainer}[method]
+    scls = {"wcsph": fluid_solvers.WCSPHSolver, "dfsph": fluid_solvers.DFSPHSolver, "pcisph": fluid_solvers.PCISPHSolver,
+            "iisph": fluid_solvers.IISPHSolver}[method]
     container = ccls(cfg, GGUI=False, **engine_opts)
     solver = scls(container)
     return container, solver
