@@ -199,7 +199,7 @@ static void fill_consts(SphHandle *h) {
     c.force_global = p.force_global;
     c.stat_bank = 0;
     c.run_grouping = 0;
-    { static const int xc = getenv("SPH_XCD_CHUNK") ? atoi(getenv("SPH_XCD_CHUNK")) : 0; c.xcd_chunk = xc > 0 ? xc : 0; }
+    c.xcd_chunk = 0;
     c.ghosts = 0;
 }
 
@@ -209,12 +209,8 @@ static void refresh_counts(SphHandle *h) {
     h->st.c.all_fluid = (h->n_nonfluid == 0 && !h->st.has_emitter && !(h->st.slab_active && h->any_rigid_object)) ? 1 : 0;
     h->st.c.ghosts = h->st.slab_active ? 1 : 0;
     // staging groups of the neighbour passes (sph_device.hpp run_of): outer runs mixed in the fast build on unsharded grids that are not thin
-    // (a slab's runs overlap and are staged once, nbr_plan "chain": x-offset groups there); SPH_RUN_GROUPING=0|1 overrides (A/B)
-    {
-        static const int env = getenv("SPH_RUN_GROUPING") ? atoi(getenv("SPH_RUN_GROUPING")) : -1;
-        const int want = (h->prm.fast_math && !h->st.slab_active && h->st.c.nz >= 40) ? 1 : 0;
-        h->st.c.run_grouping = (env >= 0 ? (env != 0) : want) && h->prm.fast_math ? 1 : 0;
-    }
+    // (a slab's runs overlap and are staged once, nbr_plan "chain": x-offset groups there)
+    h->st.c.run_grouping = (h->prm.fast_math && !h->st.slab_active && h->st.c.nz >= 40) ? 1 : 0;
     h->st.has_rigid = h->n_nonfluid > 0;
     h->st.uniform_mass = (h->st.c.all_fluid && h->fluid_mass_uniform && !h->st.slab_active && !getenv("SPH_NO_UNIFORM_MASS")) ? 1 : 0;
 }
@@ -302,9 +298,6 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     memset(&s.c, 0, sizeof(s.c));
     s.stream = nullptr;
     HIP_CREATE(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    if (const char *ord = getenv("SPH_AXIS_ORDER")) {   // which scene axes the library's (x, y, z) are, e.g. "zxy" (A/B of the cell order; sph_comm_set_slab picks one for sharded runs)
-        if (!set_axis_order(h, ord)) { fail(nullptr, SPH_ERR_INVALID, "sph_create: SPH_AXIS_ORDER must be a permutation of xyz"); sph_destroy(h); return SPH_ERR_INVALID; }
-    }
     fill_consts(h);
     const size_t cap = (size_t)p.particle_max_num;
     s.cap = p.particle_max_num;
@@ -322,23 +315,22 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     if (h->prm.deterministic && !getenv("SPH_NO_RUN_LISTS")) { CHK_CREATE(dalloc(h, &s.run_head, G + 1)); CHK_CREATE(dalloc(h, &s.run_rec, cap + G + 1)); CHK_CREATE(dalloc(h, &s.sort_inv, cap)); CHK_CREATE(dalloc(h, &s.color_home, cap)); s.color_home_ok = 1; }   // deterministic sort by run lists (RunList, sph_common.hpp)
     s.scan_blocks = (int)((G + SPH_NGRAVE + 2047) / 2048);
     if (s.scan_blocks < SPH_STAT_SLOTS / 256) s.scan_blocks = SPH_STAT_SLOTS / 256;   // k_scan_final also clears the statistics slots
-    s.scan_tile_state = nullptr; if (!getenv("SPH_SCAN_ALL_TILES")) CHK_CREATE(dalloc(h, &s.scan_tile_state, (size_t)s.scan_blocks + 1));
+    CHK_CREATE(dalloc(h, &s.scan_tile_state, (size_t)s.scan_blocks + 1));
     CHK_CREATE(dalloc(h, &s.scan_partial, 2 * ((size_t)s.scan_blocks + 1) * 8));   // two banks of tile sums, SCAN_PARTIAL_STRIDE ints apart (State::scan_bank)
     s.scan_bank = 0; s.tile_sums_ready = 0; s.skip_residual = 0; s.hist_taken = 0; s.state_error = 0;
     s.cell_count_clean = 1;
     CHK_CREATE(dalloc(h, &s.rho_raw, cap)); CHK_CREATE(dalloc(h, &s.prs, cap)); CHK_CREATE(dalloc(h, &s.ptm, cap));
     CHK_CREATE(dalloc(h, &s.acc, cap));
-    s.nbr_mask = nullptr; s.masks_valid = 0; s.density_books_forces = 0; s.uniform_mass = 0;
-    s.nbr_mask_hi = nullptr;
-    if (!getenv("SPH_NO_MASK_REUSE")) { CHK_CREATE(dalloc(h, &s.nbr_mask, cap * 9 + 256)); CHK_CREATE(dalloc(h, &s.nbr_mask_hi, cap * 9 + 256)); }   // + 256: the lanes past the last particle of the last tile read (and drop) a word too
-    s.lane_perm = nullptr; s.perm_n = -1;
+    s.masks_valid = 0; s.density_books_forces = 0; s.uniform_mass = 0;
+    CHK_CREATE(dalloc(h, &s.nbr_mask, cap * 9 + 256)); CHK_CREATE(dalloc(h, &s.nbr_mask_hi, cap * 9 + 256));   // + 256: the lanes past the last particle of the last tile read (and drop) a word too
+    s.perm_n = -1;
     s.loop_flag = nullptr; s.loop_slot = 0; s.loop_kind = 0; s.loop_denom = 1.0f; s.loop_thr = 0.0;
     CHK_CREATE(dalloc(h, &s.blk_hdr, (cap + 255) / 256 * (20 + 256)));   // headers of all tiles, then one cell word per particle slot (k_block_prep)
     s.blk_flag = s.blk_list = s.blk_count = nullptr; s.list_n = -1; s.last_pass_listed = 0; s.list_count_pinned = nullptr; s.list_count_event = nullptr; s.list_count_known = -1; s.nexthash = NextHash{0, nullptr, nullptr, nullptr, nullptr, RunList{nullptr, nullptr, 0, 0u}}; s.prehashed = 0; s.n_hash_launches = s.n_prehashed_sorts = 0;
     if (!getenv("SPH_NO_BLOCK_LIST")) {
         CHK_CREATE(dalloc(h, &s.blk_flag, (cap + 255) / 256)); CHK_CREATE(dalloc(h, &s.blk_list, (cap + 255) / 256)); CHK_CREATE(dalloc(h, &s.blk_count, 1));
     }
-    if (s.nbr_mask && !getenv("SPH_NO_LANE_PERM")) CHK_CREATE(dalloc(h, &s.lane_perm, (cap + 255) / 256 * 256));
+    CHK_CREATE(dalloc(h, &s.lane_perm, (cap + 255) / 256 * 256));
     s.alpha = s.kappa = s.kappa_v = s.rho_star = s.rho_deriv = s.kappa_next = s.kappa_v_next = nullptr; s.kr = nullptr;
     s.pacc = s.pvel = s.ppos = s.acc_np = nullptr; s.np_acc_out = nullptr; s.np_visc_vel = nullptr;
     s.iisph_dii = s.iisph_dij = s.iisph_w = nullptr;
@@ -684,8 +676,7 @@ static void step_begin(SphHandle *h) {
 
 static int read_scalars(SphHandle *h) {
     { int rc = slab_settle_if_needed(h); if (rc) return rc; }
-    static const bool no_publish = getenv("SPH_NO_LOOP_PUBLISH") != nullptr;
-    if (!no_publish && h->loop_pub) {   // the sums of the last step's bank, added up on the device and published into pinned memory (sph_steps.hpp)
+    if (h->loop_pub) {   // the sums of the last step's bank, added up on the device and published into pinned memory (sph_steps.hpp)
         StatsPub *pub = (StatsPub *)((char *)h->loop_pub + 64);
         const unsigned want = ++h->stats_seq;
         const int bank_d = h->steps > 0 ? (int)((h->steps - 1) & 1) : 0;
@@ -717,18 +708,9 @@ static int read_scalars(SphHandle *h) {
 // step went 1.39 -> 1.75 ms.  The statistics are therefore added up on the device and published into pinned host memory like the solver
 // loops' residuals (read_scalars -> k_publish_stats; sph_steps.hpp), no copy at all; sph_step / sph_step_end just wait.
 // sph_synchronize -- the fence a caller times asynchronous steps with -- waits by the same publish + spin (ends ~30 us sooner than the
-// interrupt-driven hipStreamSynchronize: C2 in the driver's 3 x 20-step configuration -0.5 %); SPH_SLOW_SYNC=1: plain hipStreamSynchronize.
-static int fast_stream_sync(SphHandle *h) {
-    static const bool slow = getenv("SPH_SLOW_SYNC") != nullptr;
-    if (!slow) return loop_readback(h);          // (returns only when the stream has reached the kernel it appended)
-    HIPCHK(h, hipStreamSynchronize(h->st.stream));
-    return SPH_OK;
-}
+// interrupt-driven hipStreamSynchronize: C2 in the driver's 3 x 20-step configuration -0.5 %).
 // sph_step / sph_step_end are synchronous on return; the statistics are brought over when somebody asks (sph_get_stats)
-static int read_scalars(SphHandle *h);
 static int finish_sync(SphHandle *h) {
-    static const bool copy_stats = getenv("SPH_STEP_COPIES_STATS") != nullptr;   // A/B: as until round 6
-    if (copy_stats) return read_scalars(h);
     { int rc = slab_settle_if_needed(h); if (rc) return rc; }
     HIPCHK(h, hipStreamSynchronize(h->st.stream));
     return SPH_OK;
@@ -879,7 +861,7 @@ extern "C" int sph_synchronize(SphHandle *h) {
     if (!h) return SPH_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->n_exact) return slab_settle(h);   // drains the stream (bounded) and brings the counts of the asynchronous steps back
-    return fast_stream_sync(h);
+    return loop_readback(h);   // (returns only when the stream has reached the kernel it appended)
 }
 
 extern "C" int sph_step(SphHandle *h, int nsteps) {

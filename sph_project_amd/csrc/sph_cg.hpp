@@ -421,9 +421,6 @@ k_cg_update_xr2(const Consts c, int n, int nb, const int *meta, int all_fluid, f
     } else a = Ap[ic];
     __shared__ float s8[8];
     float num_a, den_a;
-#ifdef SPH_NO_EARLY_LOADS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // A/B: the operands first, then the sums (two round trips, as before round 5)
-#endif
     // (split walks without a combining kernel: part_den = [3][den_stride], CgApPass::partial)
     if (glob) { num_a = glob[0]; den_a = glob[1]; }
     else cg_total2(part_rr, part_den, nb, blk_list, blk_count, s8, num_a, den_a, part3 ? den_stride : 0);

@@ -196,20 +196,17 @@ extern "C" int sph_comm_set_slab(SphHandle *h, int z_lo, int z_hi) {
     if (!h->comm.slab_ready) {
         // Which library axis the slabs are cut along (Consts::slab_axis, sph_common.hpp).  Default: z, the scene's own z and the fastest
         // axis of the cell order -- no permutation.  SPH_SLAB_LAYOUT=slow: the scene's z becomes the library's x, the slowest axis
-        // (library axes = scene z, x, y; SPH_AXIS_ORDER may name another order that starts with z), which is what the boundary-first /
-        // interior-later launches of the compute / halo overlap need.  Nothing has been appended yet; the constants are derived again.
+        // (library axes = scene z, x, y), which is what the boundary-first / interior-later launches of the compute / halo overlap need.
+        // Nothing has been appended yet; the constants are derived again.
         const char *lay = getenv("SPH_SLAB_LAYOUT");
         const bool slow = lay && (lay[0] == 's' || lay[0] == 'S');
-        const char *ord = getenv("SPH_AXIS_ORDER");
         if (slow) {
             // (the permutation is derived HERE, after sph_create: a pose pushed earlier sits in pose_h in the old library frame and would
             //  be silently wrong -- ADVICE r04; poses go in after the slab is set)
             if (h->pose_given) return fail(h, SPH_ERR_INVALID, "comm_set_slab: SPH_SLAB_LAYOUT=slow changes the library frame; call sph_set_rigid_pose after sph_comm_set_slab, not before");
-            if (!set_axis_order(h, ord ? ord : "zxy") || h->perm[0] != 2)
-                return fail(h, SPH_ERR_INVALID, "comm_set_slab: with SPH_SLAB_LAYOUT=slow, SPH_AXIS_ORDER must be a permutation of xyz that starts with z");
+            set_axis_order(h, "zxy");
             h->slab_axis = 0;
         } else {
-            if (h->perm[2] != 2) return fail(h, SPH_ERR_INVALID, "comm_set_slab: SPH_AXIS_ORDER must end with z unless SPH_SLAB_LAYOUT=slow");
             h->slab_axis = 2;
         }
         fill_consts(h);
@@ -228,7 +225,7 @@ extern "C" int sph_comm_set_slab(SphHandle *h, int z_lo, int z_hi) {
         }
         for (int k = 0; k < 8; ++k) { int rc = dalloc(h, &s.halo_tab[k], cap); if (rc) return rc; }
         { int rc = dalloc(h, &s.halo_counts, 2 * HC_BANK); if (rc) return rc; }
-        if (h->slab_axis == 0 && !getenv("SPH_NO_SLAB_OVERLAP")) {   // boundary / interior tile lists (State::tile_list): slowest-axis slabs only
+        if (h->slab_axis == 0) {   // boundary / interior tile lists (State::tile_list): slowest-axis slabs only
             for (int k = 0; k < 2; ++k) { int rc = dalloc(h, &s.tile_list[k], ((size_t)s.cap + 255) / 256 + 1); if (rc) return rc; }
             int rc = dalloc(h, &s.tile_cnt, 2); if (rc) return rc;
             rc = dalloc(h, &s.tile_class, ((size_t)s.cap + 255) / 256 + 1); if (rc) return rc;
@@ -499,9 +496,11 @@ static int push_setup(SphHandle *h) {
         return r;
     };
     int size_class = 0;
-    if (const char *fr = getenv("SPH_COMM_TEST_FAIL_PUSH_RANK")) {   // test hook: this rank cannot set the push transport up
+#ifdef SPH_TEST_HOOKS
+    if (const char *fr = getenv("SPH_COMM_TEST_FAIL_PUSH_RANK")) {   // test-hook library only: this rank cannot set the push transport up
         if (atoi(fr) == c.rank) { ok = 0; snprintf(why, sizeof(why), "SPH_COMM_TEST_FAIL_PUSH_RANK (test hook)"); }
     }
+#endif
     e = alloc_inbox(0);
     if (e != hipSuccess && caps[1] != caps[0]) { size_class = 1; e = alloc_inbox(1); }
     // the layout of an inbox depends on the message capacity: every rank uses the same one (the smallest anybody got)

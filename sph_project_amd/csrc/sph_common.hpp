@@ -222,7 +222,7 @@ struct State {
     int *scan_tile_state;   // per scan tile: (particles before it) + 1 if its cells hold that constant because it was EMPTY at the last scan, else 0 (k_scan_final)
     int scan_bank;       // bank the hashers of the coming sort add to / the coming scan reads
     int skip_residual;   // fixed-iteration solves (no stop test, nobody reads the residual): the walks leave their partial sums, k_reduce_partials is not launched
-    int tile_sums_ready; // ... and they did (else l_scan launches k_scan_reduce first: SPH_NO_SCAN_FOLD)
+    int tile_sums_ready; // ... and they did (else l_scan launches k_scan_reduce first: slab ranks)
     int cell_count_clean;              // cell_count is all zero (the scan clears it behind itself)
     int hist_taken;                    // the histogram of the coming sort has been taken (by k_hash_count, a NextHash epilogue, the slab kernels) and not yet scanned
     int state_error;                   // sticky: a launcher met a state it must never see (l_scan without a histogram: ADVICE r05); reported by check_async

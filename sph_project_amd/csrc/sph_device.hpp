@@ -177,9 +177,6 @@ template <class T> __device__ __forceinline__ T ldg_idx(const T *base, int j) {
 // consecutive tiles, XCD k takes chunks k, k + 8, ... -- neighbouring tiles still share an L2, and every XCD sees every part of the scene
 // (Consts::xcd_chunk).  Bijective on [0, nb): the ragged end (fewer than 8 C tiles) keeps the dispatch order.
 __device__ __forceinline__ int xcd_remap(int b, int nb, int chunk = 0) {
-#ifdef SPH_NO_XCD_REMAP
-    return b;
-#endif
     if (chunk > 0) {
         const int full = nb / (8 * chunk) * (8 * chunk);
         if (b >= full) return b;
@@ -560,13 +557,9 @@ __device__ __forceinline__ void lds_load_half_imm(unsigned a, v2f (&xy)[4], floa
         : "v"(a), "n"(ZW_OFF)
         : "memory");
 }
-#ifndef SPH_P1_CHUNK
-#define SPH_P1_CHUNK 4   // candidates per LDS round trip of the unrolled phase 1 (8: r01 layout, 4: fits 96 VGPRs)
-#endif
-#ifndef SPH_P1_TRIP
-#define SPH_P1_TRIP 4    // candidates per wave-uniform trip of phase 1.  8 (until round 6): two LDS round trips of 4 per loop test; 4: one -- 3.6 % / 6.9 % fewer
-                         // tests from rest / in motion (tools/analysis/zbin_estimate.py) for one more loop test per 8: C2 +-0 from rest, -1.1 % in motion (profiles/r06_p1_trip4_ab.txt)
-#endif
+constexpr int SPH_P1_CHUNK = 4;   // candidates per LDS round trip of the unrolled phase 1 (8: r01 layout, 4: fits 96 VGPRs)
+constexpr int SPH_P1_TRIP = 4;    // candidates per wave-uniform trip of phase 1.  8 (until round 6): two LDS round trips of 4 per loop test; 4: one -- 3.6 % / 6.9 % fewer
+                                  // tests from rest / in motion (tools/analysis/zbin_estimate.py) for one more loop test per 8: C2 +-0 from rest, -1.1 % in motion (profiles/r06_p1_trip4_ab.txt)
 typedef __attribute__((address_space(3))) const unsigned long long lds_cu64;
 typedef __attribute__((address_space(3))) const int lds_ci32;
 __device__ __forceinline__ int lds_ld_i32(const int *p) { return *(lds_ci32 *)p; }
@@ -752,19 +745,10 @@ __device__ __forceinline__ void process_chunk(const Consts &c, const P &p, typen
     }
 }
 
-#ifndef SPH_P2_PAIR2_MEDIUM
-#define SPH_P2_PAIR2_MEDIUM 1
-#endif
+constexpr bool SPH_P2_PAIR2_MEDIUM = true;
 template <class P> constexpr bool pass_is_medium();
 template <class P> constexpr bool pass_pair2() {
-#ifdef SPH_P2_PAIR2
-    return true;
-#else
-#ifdef SPH_P2_PAIR2_LIGHT
-    if (!P::HAS_B) return true;
-#endif
     return SPH_P2_PAIR2_MEDIUM && pass_is_medium<P>();
-#endif
 }
 
 // pair() receives the neighbour's sorted index j only where the functor needs it (rigid-body wrench):
@@ -797,7 +781,7 @@ __device__ __forceinline__ void merged_phase2(const Consts &c, const P &p, typen
     // Two accepted neighbours of a run per trip -- all their LDS reads issued before the first pair is evaluated, half the loop control;
     // order of accumulation unchanged (first, then second).  Pays where runs hold several accepted neighbours and the pair is light: the
     // 20-28-byte solver walks (pass_is_medium) in motion, C3 -2.7 % at step 1000, +-0 from rest; the WCSPH force pass loses 1.2 % from rest
-    // with it (profiles/r06_pair2_ab.txt).  -DSPH_P2_PAIR2: every pass (A/B); -DSPH_P2_PAIR2_MEDIUM=0: none.
+    // with it (profiles/r06_pair2_ab.txt).
     while (cur) {
         const int t = (sizeof(M) == 8 ? __ffsll((long long)cur) : __ffs((int)cur)) - 1;
         cur &= cur - 1;
@@ -1056,21 +1040,11 @@ k_compact_blocks(const int *__restrict__ flag, int nb, int *__restrict__ list, i
 // walks spill 10 VGPRs, with 2 nothing spills in either the all-fluid or the rigid-aware instantiations).  Measured at C3 / PCISPH
 // (profiles/r03n_ab_medium_occupancy.txt): 24-byte subset -2 %, 28 bytes with spills -3.5 %, 28 bytes / batches of 2 (this) -3 % from
 // rest and -6 % in motion, no spills.  0 bytes = off.
-#ifndef SPH_NBR_LIGHT_CAP
-#define SPH_NBR_LIGHT_CAP 1280
-#endif
-#ifndef SPH_NBR_HEAVY_BUDGET
-#define SPH_NBR_HEAVY_BUDGET 40960   // LDS bytes per workgroup of the functors that are neither light nor medium (A/B: 32768 with SPH_NBR_WAVES_HEAVY=5)
-#endif
-#ifndef SPH_NBR_MEDIUM_BYTES
-#define SPH_NBR_MEDIUM_BYTES 28
-#endif
-#ifndef SPH_HEAVY_SB
-#define SPH_HEAVY_SB 3   // staging slots per batch of the wide records (32-36 B per slot; all 5 at once spill at 128 VGPRs)
-#endif
-#ifndef SPH_MEDIUM_SB
-#define SPH_MEDIUM_SB 3   // staging slots per batch of a medium functor (round 6: 3 -- no spills any more; C3 -0.5 % from rest, -1.2 % in motion: profiles/r06_maskpipe_ab.txt)
-#endif
+constexpr int SPH_NBR_LIGHT_CAP = 1280;
+constexpr int SPH_NBR_HEAVY_BUDGET = 40960;   // LDS bytes per workgroup of the functors that are neither light nor medium (measured against 32768 with 5 waves)
+constexpr int SPH_NBR_MEDIUM_BYTES = 28;
+constexpr int SPH_HEAVY_SB = 3;    // staging slots per batch of the wide records (32-36 B per slot; all 5 at once spill at 128 VGPRs)
+constexpr int SPH_MEDIUM_SB = 3;   // staging slots per batch of a medium functor (round 6: 3 -- no spills any more; C3 -0.5 % from rest, -1.2 % in motion: profiles/r06_maskpipe_ab.txt)
 template <class P> constexpr int pass_slot_bytes() {
     return 16 + (P::HAS_B ? (int)sizeof(typename P::BT) : 0) + (PassC<P>::value ? (int)sizeof(typename PassC<P>::type) : 0);
 }
@@ -1156,12 +1130,8 @@ template <class P, int MASKMODE> constexpr int nbr_lds_bytes() {
 // the 4-candidate phase-1 chunks and without SLP packing they fit without spilling, and the density pass of C2 went
 // 141 -> 127 us (profiles/r02_ab_*.txt).  The functors with payload arrays are capped at 4 by their 33-38 KB tiles; the
 // strict build and the 5-float DFSPH density+alpha accumulator spill at 96 and stay at 4 (tools/check_spills.py gates).
-#ifndef SPH_NBR_WAVES_LIGHT
-#define SPH_NBR_WAVES_LIGHT (SPH_FAST ? 6 : 4)
-#endif
-#ifndef SPH_NBR_WAVES_HEAVY
-#define SPH_NBR_WAVES_HEAVY (SPH_FAST ? 4 : 3)   // strict build (IEEE division / sqrt sequences): 3, i.e. <= 168 VGPRs, rather than spills
-#endif
+constexpr int SPH_NBR_WAVES_LIGHT = SPH_FAST ? 6 : 4;
+constexpr int SPH_NBR_WAVES_HEAVY = SPH_FAST ? 4 : 3;   // strict build (IEEE division / sqrt sequences): 3, i.e. <= 168 VGPRs, rather than spills
 // P::MAX_WAVES: a functor that runs rarely and would spill at its class's register budget asks for fewer waves (RigidVolumePass)
 template <class P, class = void> struct PassMaxWaves { static constexpr int value = 8; };
 template <class P> struct PassMaxWaves<P, decltype((void)P::MAX_WAVES)> { static constexpr int value = P::MAX_WAVES; };
@@ -1215,22 +1185,13 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
     const int i0 = b * BLOCK;
     // Second round trip, requested BEFORE a functor's prologue (whose barriers keep later loads behind its own: the CG walk's prologue adds
     // up two arrays of partial sums first): the lane permutation, the header, the skip flag of a slab's interior launch.
-#ifndef SPH_NO_EARLY_LOADS
     const int who_early = lane_perm ? (int)lane_perm[i0 + tid] : tid;
     const int *hdr = blk_hdr + (size_t)b * BLK_HDR_INTS;
     const int cfirst = hdr[0], clast = hdr[1];
     const int skip_tile = tile_skip ? (int)tile_skip[b] : 0;
     const int n_live = live_n(c);
-#endif
     if constexpr (PassWrench<P>::value) wrench_init_all(p.pose);   // (published by the prologue's barrier)
     if constexpr (PassPrologue<P>::value) { if (!p.prologue(scal)) return; }   // workgroup-uniform
-#ifdef SPH_NO_EARLY_LOADS
-    const int who_early = lane_perm ? (int)lane_perm[i0 + tid] : tid;
-    const int *hdr = blk_hdr + (size_t)b * BLK_HDR_INTS;
-    const int cfirst = hdr[0], clast = hdr[1];
-    const int skip_tile = tile_skip ? (int)tile_skip[b] : 0;
-    const int n_live = live_n(c);
-#endif
     if (i0 >= n_live) {   // launch bound of an asynchronous slab step: no such tile (its header was never written)
         if constexpr (P::HAS_REDUCE) {
             if (tid == 0) {
@@ -1262,10 +1223,8 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
     // gets an `s_waitcnt vmcnt(0)` at the end of its block (the merge of its result), which used to serialise the prologue into
     // five memory round trips (permutation -> position -> windows -> begin() -> first staging round).  begin() only reads.
     const int ic = valid ? i : i0;
-#ifndef SPH_NO_CELL_WORD
     // the lane's cell word (k_block_prep), filed behind the headers of all tiles (mask_stride = particle capacity)
     const unsigned cw = reinterpret_cast<const unsigned *>(blk_hdr + (size_t)((mask_stride + 255) >> 8) * BLK_HDR_INTS)[ic];
-#endif
     const float4 pi = p.posv[ic];
     Own own;
     bool active = p.begin(c, ic, pi, own) && valid;
@@ -1275,36 +1234,11 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
 #pragma unroll
         for (int q = 0; q < 3; ++q) mk0[q] = nbr_mask[(size_t)run_of(c.run_grouping, g0, q) * mask_stride + i];   // (the array has a tile of slack)
     }
-    // -DSPH_PRESTAGE (off): the first staging round depends on the header alone, so its global loads can go out HERE and be written to
-    // the tile after the prologue's barrier; the records sit in registers only across the prologue, where little else is live.  One
-    // round trip less per workgroup -- and 1-2 % SLOWER at C2 / C3 (profiles/r03w_ab_round_trips.txt): kept as a switch, like PAIR2.
     typedef typename PassC<P>::type CT;
+    // (unused since the prestaged first round went; dropping this read of gridDim.y changes the register allocation of the CgApPass walks
+    //  -- an SGPR spill in the fast build -- so it stays until a kernel change measures the difference)
     const int g_first = (PassSplit<P>::value && gridDim.y > 1) ? split_lo((int)gridDim.y, (int)blockIdx.y) : 0;
-#ifdef SPH_PRESTAGE
-    constexpr bool PRESTAGE = SPH_FAST || sizeof(BT) < 16;   // (the strict build's widest functors sit at the 128-VGPR limit already)
-#else
-    constexpr bool PRESTAGE = false;
-#endif
-    float4 pa_[PRESTAGE ? NS : 1];
-    BT pb_[PRESTAGE ? NS : 1];
-    CT pc_[PRESTAGE ? NS : 1];
-    int ptotal = 0;
-    if constexpr (PRESTAGE) {
-        int rs_[RPG], ln_[RPG], lo_[RPG], qb; unsigned rm; bool overflow;
-        nbr_plan<CAP>(hdr, g_first, 0, c.force_global, rs_, ln_, lo_, ptotal, qb, rm, overflow, c.run_grouping);
-        if (c.force_global == 10 || c.force_global == 11) ptotal = 0;
-        const int n0 = lo_[0] != INT_MIN ? ln_[0] : 0;
-        const int n01 = n0 + (lo_[1] != INT_MIN ? ln_[1] : 0);
-        if (ptotal > 0) {   // uniform.  Slots past the end re-read the last record (same cache line) instead of branching:
-#pragma unroll              // the whole prologue stays one basic block, and the scheduler puts every load ahead of the first wait
-            for (int u = 0; u < NS; ++u) {
-                int t = tid + u * BLOCK;
-                t = t < ptotal ? t : ptotal - 1;
-                const int j = t < n0 ? t - lo_[0] : (t < n01 ? t - lo_[1] : t - lo_[2]);
-                pa_[u] = pass_stage(p, c, j, pb_[u], pc_[u]);
-            }
-        }
-    }
+    (void)g_first;
     if (cs_lds && tid < NBR_CS_PITCH) {   // uniform per wave (a window has <= 128 entries: the upper two waves have nothing to fetch); threads past the window re-read its last entry
         const int tc = tid < span + 4 ? tid : span + 3;
         int cs_[9];
@@ -1321,28 +1255,9 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
     }
     // What the group loop keeps of this lane's cell: two window-cache entries and nine "column exists" bits (three registers instead of
     // cx, cy, z0, z1 - z0; the rare path that reads the windows from global memory recomputes the cell from the position).
-    int e0, e1;
-    unsigned dom = 0u;
-#ifndef SPH_NO_CELL_WORD
-    e0 = (int)(cw & 0xffu);
-    e1 = e0 + (int)((cw >> 8) & 7u);
-    dom = cw >> 11;
-#else
-    {
-        const int cx = cell_coord_x(c, pi.x);
-        const int cy = cell_coord(pi.y, c.grid_size, c.ny);
-        const int cz = cell_coord_z(c, pi.z);
-        const int lin = (cx * c.ny + cy) * c.nz + cz;
-        const int z0 = cz > 0 ? cz - 1 : 0;
-        const int z1 = cz < c.nz - 1 ? cz + 1 : c.nz - 1;
-        e0 = (lin - cfirst) + (z0 - cz) + 1;   // s_cs entry of (.., .., z0) in every run
-        e1 = e0 + (z1 - z0) + 1;
-        // bit k = 3 (ox + 1) + (oy + 1): column (cx + ox, cy + oy) lies inside the grid.  The three y bits, copied to where the x offsets
-        // that exist put them (nine range tests -> four)
-        const unsigned by = (cy > 0 ? 1u : 0u) | 2u | (cy < c.ny - 1 ? 4u : 0u);
-        dom = (cx > 0 ? by : 0u) | (by << 3) | (cx < c.nx - 1 ? by << 6 : 0u);
-    }
-#endif
+    const int e0 = (int)(cw & 0xffu);
+    const int e1 = e0 + (int)((cw >> 8) & 7u);
+    const unsigned dom = cw >> 11;
     if (skip_tile) return;   // (uniform)
     if (__syncthreads_or(active ? 1 : 0)) {  // workgroup-uniform; also publishes s_cs
         NBR_STAMP(1);
@@ -1351,21 +1266,7 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
         const bool is_split = PassSplit<P>::value && gridDim.y > 1;
         const int g_lo = is_split ? split_lo((int)gridDim.y, (int)blockIdx.y) : 0;
         const int g_hi = is_split ? split_hi((int)gridDim.y, (int)blockIdx.y) : GROUPS;
-        bool prestaged = false;   // the first round's records are already on their way (above)
         unsigned mkn[RPG] = {mk0[0], mk0[1], mk0[2]};   // first mask words of the coming round's group
-        if constexpr (PRESTAGE) {
-#pragma unroll
-            for (int u = 0; u < NS; ++u) {
-                const int t = tid + u * BLOCK;
-                if (t < ptotal) {
-                    sXY[t] = make_float2(pa_[u].x, pa_[u].y);
-                    sZW[t] = make_float2(pa_[u].z, pa_[u].w);
-                    if (P::HAS_B) sB[t] = pb_[u];
-                    if (PassC<P>::value) sC[t] = pc_[u];
-                }
-            }
-            prestaged = true;
-        }
 #pragma unroll 1
         for (int g = g_lo, qa = 0; g < (c.force_global == 11 ? 0 : g_hi); ) {
             // One group = the three runs of an x offset.  Its runs are staged in ROUNDS (uniform plan): a round takes the longest
@@ -1402,7 +1303,7 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
                                                    : ((P::HAS_B && sizeof(BT) >= 16) ? ((PassUsesJ0<P>::value || !SPH_FAST) ? 2 : (SPH_HEAVY_SB < NS ? SPH_HEAVY_SB : NS)) : NS);
             const int n0 = lo_[0] != INT_MIN ? ln_[0] : 0;
             const int n01 = n0 + (lo_[1] != INT_MIN ? ln_[1] : 0);
-            const bool stage_now = total > 0 && c.force_global != 10 && !prestaged;   // uniform
+            const bool stage_now = total > 0 && c.force_global != 10;   // uniform
             float4 a_[SB];
             BT b_[SB];
             CT c_[SB];
@@ -1489,7 +1390,6 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
                     }
                 }
             }
-            prestaged = false;
             __syncthreads();
             NBR_STAMP(2 + g * 4);
             // the merged loop handles runs of <= 64 candidates out of the tile (one or two mask words per run); anything

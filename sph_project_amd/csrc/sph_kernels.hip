@@ -24,13 +24,11 @@ namespace SPH_NS {
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// tile sums of the coming scan (State::scan_partial): the bank the hashers add to, or null (k_scan_reduce computes them: SPH_NO_SCAN_FOLD, and
-// every slab-sharded rank -- there the fold LOSES: the arrivals take one more atomic each in a waiting kernel of 64 workgroups and a thin slab's
+// tile sums of the coming scan (State::scan_partial): the bank the hashers add to, or null (k_scan_reduce computes them) on every slab-sharded
+// rank -- there the fold LOSES: the arrivals take one more atomic each in a waiting kernel of 64 workgroups and a thin slab's
 // waves straddle tiles; two ranks on one GPU +1.4 ... +2.3 %, eight ranks +19 %, profiles/r06_two_ranks_scanfold_ab.txt)
 static int *tile_sum_bank(State &s) {
-    static const bool off = getenv("SPH_NO_SCAN_FOLD") != nullptr;
-    static const bool force = getenv("SPH_SCAN_FOLD_SLAB") != nullptr;
-    if (off || (s.slab_active && !force)) return nullptr;
+    if (s.slab_active) return nullptr;
     return s.scan_partial + (size_t)s.scan_bank * (s.scan_blocks + 1) * SCAN_PARTIAL_STRIDE;
 }
 // the histogram is about to be taken on a cell_count that is not known to be clean: clear it, and the tile sums with it
@@ -84,7 +82,7 @@ void l_scan(State &s) {
     if (!s.tile_sums_ready) hipLaunchKernelGGL(k_scan_reduce, dim3(nb), dim3(SCAN_TPB), 0, s.stream, s.cell_count, G, part);
     hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(SCAN_TPB), 0, s.stream, s.cell_count, G, part,
                        s.cell_start, s.c.n, s.scal, 1 - s.c.stat_bank, s.c.n_dev, part_next,
-                       (s.scan_tile_state && !s.slab_active) ? s.scan_tile_state : nullptr);   // (a slab's grid moves with its cuts: every tile scanned)
+                       s.slab_active ? nullptr : s.scan_tile_state);   // (a slab's grid moves with its cuts: every tile scanned)
     s.cell_count_clean = 1;   // ... and so is the bank of tile sums the next histogram adds to
     s.scan_bank = 1 - s.scan_bank;
     s.tile_sums_ready = 0;
@@ -155,9 +153,8 @@ void l_scatter_impl(State &s, bool stable) {
     if (by_lists) {
         // bytes that need not move: the colours (at home, keyed by the particle id, while the ids are the append order) and a density that
         // the next kernel recomputes for every particle
-        static const bool move_all = getenv("SPH_SORT_MOVE_ALL") != nullptr;   // A/B
-        if (s.color_home && s.color_home_ok && !move_all) { a.color_in = nullptr; s.color_stale = 1; }
-        if (skip_rho && !move_all) a.rho_in = nullptr;
+        if (s.color_home && s.color_home_ok) { a.color_in = nullptr; s.color_stale = 1; }
+        if (skip_rho) a.rho_in = nullptr;
         hipLaunchKernelGGL(k_sort_rank, dim3(cdiv(n, 256)), dim3(256), 0, s.stream, n, s.cellid, s.cell_start,
                            RunList{s.run_head, s.run_rec, s.cap, s.sort_epoch}, s.sort_inv);
         const bool lst = !s.c.all_fluid && s.blk_list;
@@ -188,8 +185,7 @@ void l_scatter_stable(State &s) { l_scatter_impl(s, true); }
 // one per tile of the scene until then (the kernels send the surplus home at their top).  Never zero: a functor whose prologue keeps a
 // solver loop's books needs workgroup (0, 0) even when the list is empty.
 int list_grid(State &s, int nb) {
-    static const bool off = getenv("SPH_NO_LIST_GRID") != nullptr;
-    if (off || !s.list_count_pinned) return nb;
+    if (!s.list_count_pinned) return nb;
     if (s.list_count_known < 0 && s.list_count_event) {
         const hipError_t q = hipEventQuery(s.list_count_event);
         if (q == hipSuccess) s.list_count_known = *s.list_count_pinned;
@@ -204,13 +200,13 @@ template <class P> void launch_pass(State &s, const P &p, int mask_mode = 0) {
     const int n = s.c.n;
     if (n == 0) return;
     const int nb = cdiv(n, P::BLOCK);
-    if (!s.nbr_mask || s.c.force_global == 1) mask_mode = 0;
+    if (s.c.force_global == 1) mask_mode = 0;
     if (mask_mode == 2 && !s.masks_valid) mask_mode = 0;
     // lane permutation (k_lane_perm): only for the passes that reuse stored masks -- a pass that runs phase 1 keeps
     // neighbouring lanes on neighbouring cells, which is what makes its LDS reads conflict-free
     if (s.perm_n != n) l_block_prep(s);   // particles were appended since the last sort
     if (!(PassModes<P>::value & (1 << mask_mode))) mask_mode = 0;
-    const unsigned char *perm = (mask_mode == 2 && s.lane_perm) ? s.lane_perm : nullptr;
+    const unsigned char *perm = mask_mode == 2 ? s.lane_perm : nullptr;
     // workgroups without fluid are not launched for functors that have nothing to do there
     const bool use_list = PassFluidOnly<P>::value && !s.c.all_fluid && s.list_n == n && s.c.force_global == 0;
     const int *bl = use_list ? s.blk_list : nullptr, *bc = use_list ? s.blk_count : nullptr;
@@ -228,10 +224,7 @@ template <class P> void launch_pass(State &s, const P &p, int mask_mode = 0) {
     if (!(MODES & (1 << mask_mode))) mask_mode = 0;   // every functor has mode 0
     const int gy = (PassSplit<P>::value && s.split_next_pass) ? s.split_next_pass : 1;   // 3: one workgroup per (tile, x-offset group); 2: groups {0, 1} / {2}
     s.split_next_pass = 0;
-    // debug ("time against resident workgroups"): SPH_DEBUG_EXTRA_LDS=<bytes> of unused dynamic LDS per workgroup lower the
-    // number of workgroups a CU can hold without touching the code
-    static const int extra_lds = getenv("SPH_DEBUG_EXTRA_LDS") ? atoi(getenv("SPH_DEBUG_EXTRA_LDS")) : 0;
-#define SPH_LAUNCH_NBR(M) hipLaunchKernelGGL((k_nbr_pass<P, M>), dim3(nb_launch, gy), dim3(P::BLOCK), extra_lds, s.stream, s.c, s.cell_start, p, s.scal, nb, s.nbr_mask, s.nbr_mask_hi, s.cap, s.blk_hdr, perm, tl, s.loop_flag, bl, bc, skip)
+#define SPH_LAUNCH_NBR(M) hipLaunchKernelGGL((k_nbr_pass<P, M>), dim3(nb_launch, gy), dim3(P::BLOCK), 0, s.stream, s.c, s.cell_start, p, s.scal, nb, s.nbr_mask, s.nbr_mask_hi, s.cap, s.blk_hdr, perm, tl, s.loop_flag, bl, bc, skip)
     if (mask_mode == 1) {
         if constexpr ((MODES & 0b010) != 0) { SPH_LAUNCH_NBR(1); s.masks_valid = 1; }
     } else if (mask_mode == 2) {

@@ -208,15 +208,14 @@ static void l_cg_prepare(State &s) {
 #define CG_GRID(nb) (CG_LISTED ? list_grid(s, (nb)) : (nb))
 static void l_cg_ap(State &s) {
     const bool split = s.cg_split && s.cg_part && s.c.n > 0;
-    s.split_next_pass = split ? s.cg_split : 0;   // 2 or 3 ways (sph_cg_steps.hpp)
+    s.split_next_pass = split ? s.cg_split : 0;   // 3 ways (sph_cg_steps.hpp)
     // s.cg_fuse: this A p pass applies the previous iteration's p update on the fly (CgApPass::fuse), p_old = cg_p, p_new = cg_p2
     const int fuse = s.cg_fuse ? 1 : 0;
     const bool lst = CG_LISTED;
     const int nb = s.c.n > 0 ? cdiv(s.c.n, 256) : 0;
     // inside the unsharded loop with the fused p update the split walks leave their shares of p . A p themselves (CG_PART(4..6)) and the
-    // x / r update adds the three parts up: no combining kernel (SPH_CG_COMBINE=1: the round-3 sequence, for A/B)
-    static const bool keep_combine = getenv("SPH_CG_COMBINE") != nullptr;
-    const bool nocombine = split && s.cg_fused_loop && !s.slab_active && !keep_combine && s.red_blocks >= nb;
+    // x / r update adds the three parts up: no combining kernel
+    const bool nocombine = split && s.cg_fused_loop && !s.slab_active && s.red_blocks >= nb;
     s.cg_nocombine = nocombine ? 1 : 0;
     float *pdot = nocombine ? CG_PART(4) : nullptr;
     if (s.c.all_fluid) {

@@ -19,7 +19,7 @@ static int implicit_viscosity_non_pressure(SphHandle *h);
 // step of the buckling scene: a fifth of its step.  Instead a one-wave kernel behind the batch stores the residuals and the flags into pinned
 // host memory, the batch number last (system-scope release), and the host spins on that number: the wait ends a few microseconds after the
 // batch's last kernel.  (The same kernel -> pinned memory -> polling host pattern as the slab counts' mirror, sph_halo.hpp.)  Bounded: the host
-// looks at hipStreamQuery every few microseconds and falls back to the copy when the stream is idle or broken.  SPH_NO_LOOP_PUBLISH=1: the copy.
+// looks at hipStreamQuery every few microseconds and falls back to the copy when the stream is idle or broken.
 struct LoopPub { float red[8]; int flags[4]; unsigned seq; unsigned pad[3]; };
 static_assert(sizeof(LoopPub) == 64, "LoopPub layout");
 __global__ void __launch_bounds__(64) k_publish_loop(DevScalars *scal, LoopPub *pub, unsigned seq) {
@@ -73,8 +73,7 @@ __global__ void __launch_bounds__(256) k_publish_stats(const DevScalars *scal, i
 // brings scal->red[0..8) and scal->flags[0..4) of the stream's current end into h->scal_h
 static int loop_readback(SphHandle *h) {
     State &s = h->st;
-    static const bool no_publish = getenv("SPH_NO_LOOP_PUBLISH") != nullptr;
-    if (!no_publish && h->loop_pub) {
+    if (h->loop_pub) {
         const unsigned want = ++h->loop_seq;
         volatile LoopPub *pub = h->loop_pub;
         hipLaunchKernelGGL(k_publish_loop, dim3(1), dim3(64), 0, s.stream, s.scal, h->loop_pub, want);
@@ -108,7 +107,7 @@ static long long dfsph_particle_num(SphHandle *h) { return h->st.slab_active ? h
 // loop then goes on in small batches -- two read-backs per solve instead of five to seven.  Every read-back is a
 // stream drain plus the host's launch latency before the GPU has work again (~25-40 us of idle chip: the rocprofv3
 // traces of round 5 show 188 us of kernels per DFSPH iteration in motion against 285 us of wall time, profiles/
-// r05_rocprofv3_c3_motion_summary.txt).  Without a hint (first step, SPH_NO_LOOP_HINT): 2, 4, 8, 8, ... as before.
+// r05_rocprofv3_c3_motion_summary.txt).  Without a hint (first step): 2, 4, 8, 8, ... as before.
 template <class F>
 static int device_loop(SphHandle *h, int max_itr, int slot, int kind, float denom, double thr, F body, int *executed,
                        int *launched, float *last_val, void (*batch_end)(State &) = nullptr) {
@@ -117,8 +116,7 @@ static int device_loop(SphHandle *h, int max_itr, int slot, int kind, float deno
     h->loop_flags_clean = false;
     s.loop_flag = &s.scal->flags[0];
     s.loop_slot = slot; s.loop_kind = kind; s.loop_denom = denom; s.loop_thr = thr;
-    static const bool no_hint = getenv("SPH_NO_LOOP_HINT") != nullptr;
-    const int hint = (no_hint || slot < 0 || slot >= 4) ? 0 : h->loop_hint[slot];
+    const int hint = (slot < 0 || slot >= 4) ? 0 : h->loop_hint[slot];
     int n_launched = 0, batch = hint > 3 ? hint - 1 : 2, rc = SPH_OK;
     bool predicted = hint > 3;
     // red[8] and flags[4] are neighbours in DevScalars: one 48-byte copy brings the residual and the flags
@@ -157,7 +155,7 @@ static int wcsph_step(SphHandle *h) {
     State &s = h->st;
     // sharded: + migration / ghost exchange; over the push transport a plain WCSPH step needs nothing back from the device
     // (slab_neighbor_search_push, "async"): implicit viscosity and the unfused force passes launch exact grids instead
-    const bool fused = !h->prm.viscosity_implicit && !getenv("SPH_NO_FUSED_FORCES");
+    const bool fused = !h->prm.viscosity_implicit;
     if (s.slab_active) { int rc = slab_neighbor_search(h, fused); if (rc) return rc; }
     else { s.sort_skip_rho = s.c.all_fluid; ph_neighbor_search(h); }          // WCSPH.py:28 (the density pass below rewrites every rho: the sort need not move it)
     ph_rigid_volume(h);                                                       // base_solver.py:696 (see ph_rigid_volume)
@@ -176,7 +174,7 @@ static int wcsph_step(SphHandle *h) {
         { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1); }
         s.tile_sel = 0;
         { ProfScope p(h, SPH_K_HALO); h->L->halo_pull_fields(s, 2, nullptr, nullptr, hint); }
-    } else if (s.slab_active && s.push.on && !getenv("SPH_NO_SLAB_FUSED_FIELDS")) {
+    } else if (s.slab_active && s.push.on) {
         // ghost rho, p: the density pass stores the values of its boundary particles straight into the neighbours' field message
         // (HaloFieldSend) -- no gather kernel, and the message travels while the pass is still running; then the usual wait + scatter
         const int hint = slab_field_hint(h);
@@ -187,7 +185,7 @@ static int wcsph_step(SphHandle *h) {
         { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1); }               // :29 + :33 (EOS fused)
         if (s.slab_active) { int rc = slab_exchange_fields(h); if (rc) return rc; }   // ghost rho, p
     }
-    if (!h->prm.viscosity_implicit && !getenv("SPH_NO_FUSED_FORCES")) {
+    if (fused) {
         // Another step of this call follows (sph_step_async(n)) and nothing on the host happens in between: the force pass classifies its
         // own particles and stores the NEXT step's message into the neighbours' inboxes as its workgroups finish (HaloSend,
         // sph_halo_defs.hpp) -- the records travel while the pass is still running, and the next step starts with the hash alone.  Not
@@ -195,12 +193,11 @@ static int wcsph_step(SphHandle *h) {
         const SlabComm &cm = h->comm;
         const bool rebalance_next = cm.rebalance_every > 0 && (h->steps + 1) % cm.rebalance_every == 0 && !h->any_rigid_object;
         if (s.slab_active && s.push.on && h->steps_to_follow > 0 && !rebalance_next && !s.has_emitter && !h->any_rigid_object &&
-            !h->sort_dirty && !getenv("SPH_NO_SLAB_PRESEND"))
+            !h->sort_dirty)
             h->L->halo_presend_begin(s);
         // Unsharded, all fluid, another step of this call queued right behind (nothing can touch the particles in between): the force pass
         // hashes the positions it stores for the next step's sort (NextHash) -- one launch less per step.
-        static const bool no_nexthash = getenv("SPH_NO_NEXT_HASH") != nullptr;
-        s.nexthash.on = (!no_nexthash && !s.slab_active && s.c.all_fluid && h->steps_to_follow > 0 && !s.has_emitter && !h->any_rigid_object &&
+        s.nexthash.on = (!s.slab_active && s.c.all_fluid && h->steps_to_follow > 0 && !s.has_emitter && !h->any_rigid_object &&
                          !h->sort_dirty) ? 1 : 0;
         ProfScope p(h, SPH_K_WCSPH_FORCES); h->L->wcsph_forces(s);            // :30-31 + :34-36, :45 in one neighbour walk
         return SPH_OK;
@@ -213,12 +210,11 @@ static int wcsph_step(SphHandle *h) {
 // A solve with a FIXED iteration count (SphParams::fixed_iterations: bench mode, sph_step_async) has no stop test, and nothing reads
 // the residual of an iteration (SphStats::err_* report 0 in this mode): the walks still leave their per-workgroup partial sums, but the
 // one-workgroup kernel that adds them up -- 5 us and a launch boundary per iteration, 2.4 % of a C3 step -- is not launched.  Unsharded
-// only (a sharded solve all-reduces the residual either way).  SPH_FIXED_KEEP_RESIDUAL=1: launch it as before (A/B).
+// only (a sharded solve all-reduces the residual either way).
 struct SkipResidual {
     State &s;
     SkipResidual(SphHandle *h) : s(h->st) {
-        static const bool keep = getenv("SPH_FIXED_KEEP_RESIDUAL") != nullptr;
-        s.skip_residual = (h->prm.fixed_iterations > 0 && !s.slab_active && !keep) ? 1 : 0;
+        s.skip_residual = (h->prm.fixed_iterations > 0 && !s.slab_active) ? 1 : 0;
     }
     ~SkipResidual() { s.skip_residual = 0; }
 };
@@ -331,8 +327,7 @@ static int dfsph_step_begin(SphHandle *h, bool allow_readback) {
     if (s.slab_active) { rc = slab_exchange_vel(h); if (rc) return rc; }      // the density solver reads v_j of the ghosts
     rc = dfsph_density(h, allow_readback); if (rc) return rc;                 // :301
     // the sort of this step's second half follows at once when the whole step is one call (step_once): the position update hashes for it
-    static const bool no_nexthash = getenv("SPH_NO_NEXT_HASH") != nullptr;
-    s.nexthash.on = (!no_nexthash && h->whole_step && !s.slab_active && s.c.all_fluid && !s.has_emitter && !h->any_rigid_object &&
+    s.nexthash.on = (h->whole_step && !s.slab_active && s.c.all_fluid && !s.has_emitter && !h->any_rigid_object &&
                      !h->sort_dirty && !h->pose_dirty) ? 1 : 0;
     { ProfScope p(h, SPH_K_MISC); h->L->advect_boundary(s); }                 // :303, :311-314 (boundary fused: it only looks at the particle itself)
     return SPH_OK;
@@ -345,11 +340,9 @@ static int dfsph_step_end(SphHandle *h, bool allow_readback) {
     if (s.slab_active) { int rc = slab_neighbor_search(h); if (rc) return rc; }   // + migration / ghost exchange
     else { s.sort_skip_rho = s.c.all_fluid; ph_neighbor_search(h); }          // :316 (the density pass below rewrites every rho: the sort need not move it)
     ph_rigid_volume(h);
-    static const bool unfused = getenv("SPH_NO_DFSPH_FUSED_DIV") != nullptr;   // A/B switch
-    if (unfused) { ProfScope p(h, SPH_K_DFSPH_DENSITY_ALPHA); h->L->dfsph_density_alpha(s); } // :317-318
-    else { ProfScope p(h, SPH_K_DFSPH_DENSITY_ALPHA); h->L->dfsph_density_alpha_div(s); }     // :317-318 + the D rho / Dt of :140
+    { ProfScope p(h, SPH_K_DFSPH_DENSITY_ALPHA); h->L->dfsph_density_alpha_div(s); }     // :317-318 + the D rho / Dt of :140
     if (s.slab_active) { int rc = slab_exchange_scalar(h, s.rho.cur()); if (rc) return rc; }   // ghost densities (kappa_j / rho_j, viscosity)
-    return dfsph_divergence(h, allow_readback, !unfused);                     // :319
+    return dfsph_divergence(h, allow_readback, true);                         // :319
 }
 
 // PCISPH.py:110 refine.  Under slab sharding the ghosts' p / rho^2 goes out between the two passes of an

@@ -450,13 +450,14 @@ def test_dead_neighbour_is_an_error_not_a_hang(gpu, tmp_path):
     assert time.time() - t0 < 150
 
 
-def test_push_transport_is_all_ranks_or_none(gpu, tmp_path, transport):
-    """The push data plane is used by every rank or by none: a rank that cannot set it up (test hook; on a real node: no peer mapping, no
+def test_push_transport_is_all_ranks_or_none_under_the_hook_library(gpu, tmp_path, transport):
+    """The push data plane is used by every rank or by none: a rank that cannot set it up (test-hook library; on a real node: no peer mapping, no
     coherent memory, a failed self-test) takes all ranks to the control plane's own transport at set-up, and the run is still right."""
     cfg = H.dam_break_scene(domain_end=(1.0, 1.0, 1.2), start=(0.1, 0.1, 0.08), end=(0.3, 0.3, 1.12), translation=(0, 0, 0),
                             velocity=(0.0, -0.3, 2.0), particleSpacing=0.019)
     steps = 12
-    outs, logs = _run_ranks(cfg, 3, steps, tmp_path, advance=True, extra_env={"SPH_COMM_TRANSPORT": "shm+auto", "SPH_COMM_TEST_FAIL_PUSH_RANK": "1"})
+    outs, logs = _run_ranks(cfg, 3, steps, tmp_path, advance=True, extra_env={"SPH_COMM_TRANSPORT": "shm+auto", "SPH_COMM_TEST_FAIL_PUSH_RANK": "1",
+                                                                           "SPH_HIP_LIB": HOOKS_LIB})
     assert [str(o["transport"]) for o in outs] == ["shm", "shm", "shm"], [str(o["transport"]) for o in outs]
     assert any("push transport not available" in l for l in logs)
     ref = H.build_oracle(cfg)

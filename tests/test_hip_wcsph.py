@@ -358,7 +358,7 @@ def test_c2_full_size_in_motion_vs_oracle(gpu, fast_math, from_step=2500):
 def test_next_hash_changes_nothing(gpu, fast_math):
     """NextHash A/B: a collapsing block advanced with sph_step_async(n) in calls of several lengths (the force
     pass hashes for the next sort inside a call, k_hash_count runs at the head of every call) against the same scene with
-    SPH_NO_NEXT_HASH semantics (one step per call): ids, positions, velocities, densities and pair counts array_equal after
+    no NextHash at all (one step per call): ids, positions, velocities, densities and pair counts array_equal after
     every call, and the counters say which path ran.  The block is perturbed and moving, so cells change population every step
     (runs of equal cells break up: the histogram atomics of the epilogue and of k_hash_count hand out different slots -- the
     stable rank must not care)."""

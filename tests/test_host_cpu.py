@@ -56,14 +56,27 @@ int main(void) {
     assert [int(x) for x in out] == got
 
 
+# runtime switches retired with the alternatives they selected: neither library may still read them
+RETIRED_SWITCHES = (
+    "SPH_XCD_CHUNK", "SPH_RUN_GROUPING", "SPH_SCAN_ALL_TILES", "SPH_NO_MASK_REUSE", "SPH_NO_LANE_PERM", "SPH_NO_LOOP_PUBLISH",
+    "SPH_SLOW_SYNC", "SPH_STEP_COPIES_STATS", "SPH_NO_LOOP_HINT", "SPH_NO_FUSED_FORCES", "SPH_NO_SLAB_FUSED_FIELDS",
+    "SPH_NO_SLAB_PRESEND", "SPH_NO_SLAB_OVERLAP", "SPH_NO_NEXT_HASH", "SPH_FIXED_KEEP_RESIDUAL", "SPH_NO_DFSPH_FUSED_DIV",
+    "SPH_NO_CG_SPLIT", "SPH_CG_SPLIT_WAYS", "SPH_NO_CG_FUSED_P", "SPH_CG_COMBINE", "SPH_NO_SCAN_FOLD", "SPH_SCAN_FOLD_SLAB",
+    "SPH_SORT_MOVE_ALL", "SPH_NO_LIST_GRID", "SPH_DEBUG_EXTRA_LDS", "SPH_AXIS_ORDER")
+
+
 def test_test_hooks_live_in_their_own_library():
-    """the pre-round-5 single halo header (a protocol with a known race) and the consumer stall are compiled into
-    libsph_hip_testhooks.so only (-DSPH_TEST_HOOKS); the production library does not even contain the switches' names."""
+    """the pre-round-5 single halo header (a protocol with a known race), the consumer stall, the injected step failure and
+    the rank that cannot set the push transport up are compiled into libsph_hip_testhooks.so only (-DSPH_TEST_HOOKS); the production
+    library does not even contain the switches' names.  Nor does it contain the name of any retired switch."""
     here = os.path.join(ROOT, "sph_project_amd")
     prod = open(os.path.join(here, "libsph_hip.so"), "rb").read()
     hooks = open(os.path.join(here, "libsph_hip_testhooks.so"), "rb").read()
-    for name in (b"SPH_TEST_SINGLE_HEADER", b"SPH_TEST_HALO_DELAY_US"):
-        assert name not in prod and name in hooks
+    for name in (b"SPH_TEST_SINGLE_HEADER", b"SPH_TEST_HALO_DELAY_US", b"SPH_TEST_FAIL_STEP", b"SPH_COMM_TEST_FAIL_PUSH_RANK"):
+        assert name not in prod and name in hooks, name
+    for name in RETIRED_SWITCHES:
+        word = re.compile(re.escape(name.encode()) + rb"(?![A-Z0-9_])")   # the whole name, not a prefix of a longer one
+        assert not word.search(prod) and not word.search(hooks), name
 
 
 @pytest.mark.skipif(_has_gpu(), reason="only meaningful on a machine without a GPU")

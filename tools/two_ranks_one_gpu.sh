@@ -2,7 +2,7 @@
 # Two ranks x 1.23 M particles sharing ONE MI355X over the push transport: the per-rank cost of sharding with a live neighbour (dead particles,
 # records, waits) that a one-rank run cannot show.  Prints ms/step for the variants given as label:ENV pairs and a rocprofv3 kernel-stats table
 # of one rank (profiles/r04_two_ranks_one_gpu.txt was made with this).
-#   tools/two_ranks_one_gpu.sh r04x "fused:" "none:SPH_NO_SLAB_PRESEND=1 SPH_NO_SLAB_FUSED_FIELDS=1" "slow:SPH_SLAB_LAYOUT=slow"
+#   tools/two_ranks_one_gpu.sh r04x "fast:" "slow:SPH_SLAB_LAYOUT=slow" "sync:SPH_SLAB_ASYNC=0"
 set -u
 O=gpurun_out/$1; shift; mkdir -p $O
 export SPH_COMM_TRANSPORT=shm+ipc
