@@ -41,7 +41,14 @@ typedef enum {
    (zero on the first step: division by zero) and which its sort does not move (another particle's value afterwards).  rho_i
    is the d_ii of the IISPH paper and is defined at every step.  All-fluid scenes never take that branch.  Single GPU only:
    a sharded handle (sph_comm_set_slab) fails in sph_prepare with SPH_ERR_UNSUPPORTED. */
-typedef enum { SPH_METHOD_WCSPH = 0, SPH_METHOD_DFSPH = 1, SPH_METHOD_PCISPH = 2, SPH_METHOD_IISPH = 3 } SphMethod;
+/* SPH_METHOD_PBF: SPH/fluid_solvers/PBF.py (Position Based Fluids; 5 refine iterations, lambda_eps 100, corrK 0.001, deltaQ 0.3 h,
+   :11-13), poly6 W and spiky gradient in EVERY sum of its step (surface tension, viscosity, rigid volumes included).  The refine walks
+   use the step-start cell lists with the centre cell and the distances taken from the CURRENT positions (base_container.py:550-560).
+   Two deviations: fix_position is Jacobi (all deltas from the positions at the start of the pass, then applied: the reference's
+   in-place update is a data race in parallel), and the PBF fields are sized particle_max_num (the reference sizes them with a
+   particle_num that is still 0).  Under PBF, objects with a later entryTime are never inserted and rigid bodies never move (PBF.py's
+   _step calls neither).  sph_prepare refuses (SPH_ERR_UNSUPPORTED) a sharded handle and viscosity_implicit. */
+typedef enum { SPH_METHOD_WCSPH = 0, SPH_METHOD_DFSPH = 1, SPH_METHOD_PCISPH = 2, SPH_METHOD_IISPH = 3, SPH_METHOD_PBF = 4 } SphMethod;
 
 /* Scene / solver constants.  Mirrors what BaseContainer.__init__ (base_container.py:10-60)
    and BaseSolver.__init__ (SPH/fluid_solvers/base_solver.py:9-54) derive from the JSON. */
@@ -111,6 +118,9 @@ typedef enum {
     SPH_F_IISPH_AII = 28,          /* f32[n]    iisph_aii (IISPH.py:47 compute_aii) */
     SPH_F_IISPH_DIJ_PJ = 29,       /* f32[n][3] dij_pj (IISPH.py:125 compute_dij_pj, last executed iteration) */
     SPH_F_IISPH_SUM_I = 30,        /* f32[n]    sum_i  (IISPH.py:148 compute_sum_i, last executed iteration) */
+    /* PBF (pbf_container.py:11-13; allocated for SPH_METHOD_PBF only, particle_max_num): */
+    SPH_F_PBF_OLD_POSITION = 31,   /* f32[n][3] particle_old_positions (PBF.py:145 save_old_position: the positions at the step's sort) */
+    SPH_F_PBF_LAMBDA = 32,         /* f32[n]    particle_pbf_lambdas (PBF.py:68 compute_lambda, last executed iteration) */
     SPH_F_COUNT_
 } SphField;
 
@@ -127,6 +137,10 @@ typedef enum {
     SPH_PH_DFSPH_DENSITY = 7,    /* DFSPH.py:225 */
     SPH_PH_IISPH_PREPARE = 8,    /* IISPH.py:93 init_step + :18 compute_dii + :47 compute_aii + :71 compute_density_star */
     SPH_PH_IISPH_ITERATION = 9,  /* one iteration of IISPH.py:185 refine: compute_dij_pj, compute_sum_i, update_pressure (+ error) */
+    SPH_PH_PBF_DENSITY_LAMBDA = 10, /* PBF.py:64-65 compute_density + compute_lambda on the current positions and the last sort's cells */
+    SPH_PH_PBF_FIX_POSITION = 11,   /* PBF.py:66 fix_position (Jacobi) on the same */
+    SPH_PH_PBF_PREDICT = 12,        /* PBF.py:150-154 save_old_position + update_fluid_position + enforce_domain_boundary */
+    SPH_PH_PBF_FINISH = 13,         /* PBF.py:156-158 enforce_domain_boundary + recompute_fluid_velocity */
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -152,6 +166,8 @@ typedef struct {
                                     per-tile preparation of the neighbour passes fused in) instead of run records filed after the scan */
     int32_t iter_iisph;          /* IISPH.py:185 refine: iterations of the last step (last SPH_PH_IISPH_ITERATION phase: 1) */
     float   err_iisph;           /* its density_error (IISPH.py:118-121; 0 with fixed_iterations > 0, as err_* of the others) */
+    int64_t pbf_recentred;       /* PBF: refine walks of the last step (or phase) whose particle's current cell differed from its sorted cell
+                                    (base_container.py:550: the 27 cells around the current cell, not the sorted one) */
 } SphStats;
 
 /* Kernel ids for the HIP-event profiler (sph_profile_*). */
@@ -162,7 +178,8 @@ typedef enum {
     SPH_K_REDUCE = 10, SPH_K_PCISPH_RHO_STAR = 11, SPH_K_PCISPH_PRESSURE_ACCEL = 12,
     SPH_K_CG_PREPARE = 13, SPH_K_CG_AP = 14, SPH_K_CG_VECTOR = 15, SPH_K_MISC = 16,
     SPH_K_HALO = 17, SPH_K_WCSPH_FORCES = 18,
-    SPH_K_IISPH_PREPARE = 19, SPH_K_IISPH_DIJ_PJ = 20, SPH_K_IISPH_SUM_I = 21, SPH_K_COUNT_
+    SPH_K_IISPH_PREPARE = 19, SPH_K_IISPH_DIJ_PJ = 20, SPH_K_IISPH_SUM_I = 21,
+    SPH_K_PBF_DENSITY_LAMBDA = 22, SPH_K_PBF_FIX_POSITION = 23, SPH_K_PBF_UPDATE = 24, SPH_K_COUNT_
 } SphKernelId;
 
 /* --- lifetime -------------------------------------------------------------------------- */

@@ -15,14 +15,14 @@ LIB_PATH = os.environ.get("SPH_HIP_LIB", os.path.join(_HERE, "libsph_hip.so"))  
 
 MAX_OBJECTS = 20
 MAT_FLUID, MAT_RIGID = 1, 2
-METHOD = {"wcsph": 0, "dfsph": 1, "pcisph": 2, "iisph": 3}
+METHOD = {"wcsph": 0, "dfsph": 1, "pcisph": 2, "iisph": 3, "pbf": 4}
 
 # enum SphField
 (F_POSITION, F_VELOCITY, F_ACCELERATION, F_DENSITY, F_PRESSURE, F_REST_VOLUME, F_MASS, F_MATERIAL,
  F_OBJECT_ID, F_IS_DYNAMIC, F_COLOR, F_PARTICLE_ID, F_GRID_ID, F_DFSPH_ALPHA, F_DFSPH_KAPPA,
  F_DFSPH_KAPPA_V, F_DENSITY_STAR, F_DENSITY_DERIV, F_PRESSURE_ACCEL, F_PREDICTED_VEL, F_PREDICTED_POS,
  F_CG_X, F_ORIG_POSITION, F_GHOST, F_DFSPH_KAPPA_NEXT, F_DFSPH_KAPPA_V_NEXT, F_DEBUG_CAPTURE,
- F_IISPH_DII, F_IISPH_AII, F_IISPH_DIJ_PJ, F_IISPH_SUM_I) = range(31)
+ F_IISPH_DII, F_IISPH_AII, F_IISPH_DIJ_PJ, F_IISPH_SUM_I, F_PBF_OLD_POSITION, F_PBF_LAMBDA) = range(33)
 
 _FIELD_SPEC = {  # field -> (dtype, components)
     F_POSITION: (np.float32, 3), F_VELOCITY: (np.float32, 3), F_ACCELERATION: (np.float32, 3),
@@ -35,17 +35,20 @@ _FIELD_SPEC = {  # field -> (dtype, components)
     F_CG_X: (np.float32, 3), F_ORIG_POSITION: (np.float32, 3), F_GHOST: (np.int32, 1),
     F_DFSPH_KAPPA_NEXT: (np.float32, 1), F_DFSPH_KAPPA_V_NEXT: (np.float32, 1), F_DEBUG_CAPTURE: (np.float32, 1),
     F_IISPH_DII: (np.float32, 3), F_IISPH_AII: (np.float32, 1), F_IISPH_DIJ_PJ: (np.float32, 3), F_IISPH_SUM_I: (np.float32, 1),
+    F_PBF_OLD_POSITION: (np.float32, 3), F_PBF_LAMBDA: (np.float32, 1),
 }
 
 # enum SphPhase
 (PH_NEIGHBOR_SEARCH, PH_RIGID_VOLUME, PH_DENSITY, PH_NON_PRESSURE, PH_PRESSURE_INTEGRATE, PH_DFSPH_ALPHA,
- PH_DFSPH_DIVERGENCE, PH_DFSPH_DENSITY, PH_IISPH_PREPARE, PH_IISPH_ITERATION) = range(10)
+ PH_DFSPH_DIVERGENCE, PH_DFSPH_DENSITY, PH_IISPH_PREPARE, PH_IISPH_ITERATION, PH_PBF_DENSITY_LAMBDA,
+ PH_PBF_FIX_POSITION, PH_PBF_PREDICT, PH_PBF_FINISH) = range(14)
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
               "rigid_volume", "dfsph_density_alpha", "dfsph_rho_adv", "dfsph_correct", "reduce",
               "pcisph_rho_star", "pcisph_pressure_accel", "cg_prepare", "cg_ap", "cg_vector", "misc", "halo",
-              "wcsph_forces", "iisph_prepare", "iisph_dij_pj", "iisph_sum_i"]
+              "wcsph_forces", "iisph_prepare", "iisph_dij_pj", "iisph_sum_i", "pbf_density_lambda", "pbf_fix_position",
+              "pbf_update"]
 
 
 class SphParams(C.Structure):
@@ -68,7 +71,7 @@ class SphStats(C.Structure):
         ("err_density", C.c_float), ("err_pcisph", C.c_float), ("err_cg", C.c_float),
         ("lds_fallback_blocks", C.c_int64), ("total_time", C.c_double), ("pair_evaluations", C.c_int64),
         ("hash_launches", C.c_int64), ("prehashed_sorts", C.c_int64), ("list_sorts", C.c_int64),
-        ("iter_iisph", C.c_int32), ("err_iisph", C.c_float),
+        ("iter_iisph", C.c_int32), ("err_iisph", C.c_float), ("pbf_recentred", C.c_int64),
     ]
 
 

@@ -40,6 +40,7 @@ struct SphHandle {
     bool fluid_mass_seen = false, fluid_mass_uniform = true; float fluid_mass0 = 0.0f;
     bool any_rigid_object = false;   // a non-fluid object was registered (slab sharding: its particles may live on another rank)
     int64_t steps = 0;
+    int pbf_bank = 0;              // PBF: statistics bank of State::pbf_recentred the last step / phase counted into
     int steps_to_follow = 0;       // sph_step_async(n): steps of this call still to come after the running one
     bool whole_step = false;       // both halves of the running step are ONE call (step_once): nothing on the host happens between them
     double total_time = 0.0;
@@ -222,7 +223,7 @@ extern "C" const char *sph_kernel_name(int k) {
         "hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate", "rigid_volume",
         "dfsph_density_alpha", "dfsph_rho_adv", "dfsph_correct", "reduce", "pcisph_rho_star",
         "pcisph_pressure_accel", "cg_prepare", "cg_ap", "cg_vector", "misc", "halo", "wcsph_forces",
-        "iisph_prepare", "iisph_dij_pj", "iisph_sum_i"};
+        "iisph_prepare", "iisph_dij_pj", "iisph_sum_i", "pbf_density_lambda", "pbf_fix_position", "pbf_update"};
     return (k >= 0 && k < SPH_K_COUNT_) ? names[k] : "?";
 }
 
@@ -260,7 +261,7 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     // sharding: 2^28 - 1 particles per handle (~70 GB of state; a bigger scene is sharded over GPUs)
     if (p.particle_max_num > 0x0fffffff)
         return fail(nullptr, SPH_ERR_CAPACITY, "sph_create: particle_max_num %d exceeds 268435455 per GPU; shard the scene (sph_comm_set_slab)", p.particle_max_num);
-    if (p.method < 0 || p.method > SPH_METHOD_IISPH) return fail(nullptr, SPH_ERR_INVALID, "sph_create: unknown method %d", p.method);
+    if (p.method < 0 || p.method > SPH_METHOD_PBF) return fail(nullptr, SPH_ERR_INVALID, "sph_create: unknown method %d", p.method);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(nullptr, SPH_ERR_NO_DEVICE, "sph_create: no HIP device visible (libsph_hip has no CPU path)");
@@ -334,6 +335,7 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     s.alpha = s.kappa = s.kappa_v = s.rho_star = s.rho_deriv = s.kappa_next = s.kappa_v_next = nullptr; s.kr = nullptr;
     s.pacc = s.pvel = s.ppos = s.acc_np = nullptr; s.np_acc_out = nullptr; s.np_visc_vel = nullptr;
     s.iisph_dii = s.iisph_dij = s.iisph_w = nullptr;
+    s.pbf_old = s.pbf_pos = nullptr; s.pbf_lambda = nullptr; s.pbf_recentred = nullptr; s.poly6 = 0;
     s.cg_p2 = nullptr; s.cg_fuse = s.cg_fused_loop = 0;
     s.cg_p = s.cg_Ap = s.cg_x = s.cg_b = s.cg_r = s.cg_v0 = nullptr; s.cg_dinv = nullptr; s.cg_part = nullptr; s.cg_split = 0; s.cg_nocombine = 0; s.split_next_pass = 0;
     if (p.method == SPH_METHOD_DFSPH) {
@@ -349,6 +351,11 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     if (p.method == SPH_METHOD_IISPH) {   // IISPH.py scratch: 52 bytes per particle, only for this method
         CHK_CREATE(dalloc(h, &s.iisph_dii, cap)); CHK_CREATE(dalloc(h, &s.iisph_dij, cap)); CHK_CREATE(dalloc(h, &s.iisph_w, cap));
         CHK_CREATE(dalloc(h, &s.rho_star, cap));
+    }
+    if (p.method == SPH_METHOD_PBF) {   // pbf_container.py:11-13, sized particle_max_num (D2); 36 bytes per particle
+        CHK_CREATE(dalloc(h, &s.pbf_old, cap)); CHK_CREATE(dalloc(h, &s.pbf_pos, cap)); CHK_CREATE(dalloc(h, &s.pbf_lambda, cap));
+        CHK_CREATE(dalloc(h, &s.pbf_recentred, 2));
+        s.poly6 = 1;
     }
     if (p.viscosity_implicit) {
         CHK_CREATE(dalloc(h, &s.cg_p, cap)); CHK_CREATE(dalloc(h, &s.cg_Ap, cap)); CHK_CREATE(dalloc(h, &s.cg_x, cap));
@@ -723,6 +730,10 @@ extern "C" int sph_prepare(SphHandle *h) {
     State &s = h->st;
     if (s.slab_active && h->prm.method == SPH_METHOD_IISPH)
         return fail(h, SPH_ERR_UNSUPPORTED, "sph_prepare: IISPH runs on one GPU only (no sharded IISPH solve: sph_comm_set_slab)");
+    if (s.slab_active && h->prm.method == SPH_METHOD_PBF)
+        return fail(h, SPH_ERR_UNSUPPORTED, "sph_prepare: PBF runs on one GPU only (no sharded PBF step: sph_comm_set_slab)");
+    if (h->prm.viscosity_implicit && h->prm.method == SPH_METHOD_PBF)
+        return fail(h, SPH_ERR_UNSUPPORTED, "sph_prepare: PBF with implicit viscosity is not supported (its CG walks would need the spiky gradient)");
     int rc = upload_pose(h); if (rc) return rc;
     // base_solver.py:683 prepare: prepare_emitter, renew_rigid_particle_state, neighbour search,
     // compute_rigid_particle_volume (+ DFSPH.py:321 / PCISPH.py:188)
@@ -766,6 +777,7 @@ static int step_first_half(SphHandle *h, bool allow_readback) {
         case SPH_METHOD_WCSPH: rc = wcsph_step(h); break;                     // WCSPH.py:28-36 (:45 boundary fused into the position update)
         case SPH_METHOD_DFSPH: rc = dfsph_step_begin(h, allow_readback); break;
         case SPH_METHOD_IISPH: rc = iisph_step(h, allow_readback); break;     // IISPH.py:204-220
+        case SPH_METHOD_PBF: rc = pbf_step(h); break;                         // PBF.py:145-158 (the whole _step: no rigid step, no insertion)
         default: rc = pcisph_step(h, allow_readback); break;                  // PCISPH.py:166-177
     }
     if (rc) return rc;
@@ -844,8 +856,8 @@ extern "C" int sph_step_end(SphHandle *h) {
 extern "C" int sph_step_async(SphHandle *h, int nsteps) {
     if (!h || nsteps < 0) return SPH_ERR_INVALID;
     if (!h->prepared) return fail(h, SPH_ERR_INVALID, "sph_step before sph_prepare");
-    if (h->prm.method != SPH_METHOD_WCSPH && h->prm.fixed_iterations <= 0)
-        return fail(h, SPH_ERR_UNSUPPORTED, "sph_step_async needs wcsph or fixed_iterations > 0");
+    if (h->prm.method != SPH_METHOD_WCSPH && h->prm.method != SPH_METHOD_PBF && h->prm.fixed_iterations <= 0)
+        return fail(h, SPH_ERR_UNSUPPORTED, "sph_step_async needs wcsph, pbf or fixed_iterations > 0");
     HIPCHK(h, hipSetDevice(h->device));
     refresh_counts(h);
     for (int k = 0; k < nsteps; ++k) {
@@ -912,6 +924,11 @@ extern "C" int sph_get_stats(SphHandle *h, SphStats *out) {
     h->last.hash_launches = h->st.n_hash_launches;
     h->last.prehashed_sorts = h->st.n_prehashed_sorts;
     h->last.list_sorts = h->st.n_list_sorts;
+    if (h->st.pbf_recentred) {   // the bank of the last completed step (or phase)
+        unsigned long long r[2];
+        HIPCHK(h, hipMemcpy(r, h->st.pbf_recentred, sizeof(r), hipMemcpyDeviceToHost));
+        h->last.pbf_recentred = (int64_t)r[h->pbf_bank];
+    }
     *out = h->last;
     return SPH_OK;
 }
@@ -929,6 +946,7 @@ static const float4 *vec_field(SphHandle *h, int field) {
         case SPH_F_ORIG_POSITION: return s.orig.cur() ? s.orig.cur() : s.posv.cur();
         case SPH_F_IISPH_DII: case SPH_F_IISPH_AII: return s.iisph_dii;     // (dii, aii)
         case SPH_F_IISPH_DIJ_PJ: case SPH_F_IISPH_SUM_I: return s.iisph_dij; // (dij_pj, sum_i)
+        case SPH_F_PBF_OLD_POSITION: return s.pbf_old;                       // (x_old, sorted cell id)
         default: return nullptr;
     }
 }
@@ -945,6 +963,7 @@ static const float *scalar_field(SphHandle *h, int field) {
         case SPH_F_DFSPH_KAPPA_NEXT: return s.kappa_next;
         case SPH_F_DFSPH_KAPPA_V_NEXT: return s.kappa_v_next;
         case SPH_F_DEBUG_CAPTURE: return s.rho_raw;   // (test-hook build: PcisphRhoStarPass::cap_prev points here)
+        case SPH_F_PBF_LAMBDA: return s.pbf_lambda;
         default: return nullptr;
     }
 }
@@ -958,7 +977,8 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
     HIPCHK(h, hipStreamSynchronize(s.stream));
     const bool is_vec3 = field == SPH_F_POSITION || field == SPH_F_VELOCITY || field == SPH_F_ACCELERATION ||
                          field == SPH_F_PRESSURE_ACCEL || field == SPH_F_PREDICTED_VEL || field == SPH_F_PREDICTED_POS ||
-                         field == SPH_F_CG_X || field == SPH_F_ORIG_POSITION || field == SPH_F_IISPH_DII || field == SPH_F_IISPH_DIJ_PJ;
+                         field == SPH_F_CG_X || field == SPH_F_ORIG_POSITION || field == SPH_F_IISPH_DII || field == SPH_F_IISPH_DIJ_PJ ||
+                         field == SPH_F_PBF_OLD_POSITION;
     if (is_vec3) {
         const float4 *src = vec_field(h, field);
         if (!src) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);

@@ -19,6 +19,11 @@
 #define SPH_IISPH_OMEGA 0.2f
 #define SPH_IISPH_ETA 0.001
 #define SPH_IISPH_MAX_ITER 20
+// PBF.py:11-13 (lambda_eps, corrK, corr_deltaQ_coeff) and :63 (refine iterations per step)
+#define SPH_PBF_LAMBDA_EPS 100.0f
+#define SPH_PBF_CORR_K 0.001f
+#define SPH_PBF_CORR_DQ 0.3f
+#define SPH_PBF_ITERATIONS 5
 
 // meta packing
 #define META_OBJ(m) (((m) & 0xff) - 1)
@@ -237,6 +242,10 @@ struct State {
     float4 *pacc, *pvel, *ppos, *acc_np;
     // IISPH (allocated for that method only): (dii, aii), (dij_pj, sum_i), w = dii p + dij_pj; rho* in rho_star
     float4 *iisph_dii, *iisph_dij, *iisph_w;
+    // PBF (allocated for that method only, particle_max_num each): x_old = (position at the sort, sorted cell id), lambda, the second position
+    // buffer of the Jacobi fix_position (swapped with posv.cur() behind every pass), recentred walks per statistics bank
+    float4 *pbf_old, *pbf_pos; float *pbf_lambda; unsigned long long *pbf_recentred;
+    int poly6;           // the shared passes (NonPressurePass, RigidVolumePass) use PBF.py's poly6 / spiky kernels
     // CG (implicit viscosity)
     float4 *cg_p, *cg_Ap, *cg_x, *cg_b, *cg_r, *cg_v0;
     float4 *cg_p2;       // second search-direction buffer (fused p update: the A p pass reads the old one and writes the new one)
@@ -357,6 +366,11 @@ struct Launch {
     void (*iisph_prepare)(State &);             // dii + aii + rho* (IISPH.py:18-90), p = 0
     void (*iisph_dij_pj)(State &);              // first walk of an iteration (IISPH.py:125, + w = dii p + dij_pj)
     void (*iisph_sum_i)(State &);               // second walk: sum_i + update_pressure + the error's reduction (IISPH.py:148, :98)
+    // PBF
+    void (*pbf_predict)(State &);               // save_old_position + update_fluid_position + boundary (PBF.py:151-154)
+    void (*pbf_density_lambda)(State &);        // compute_density + compute_lambda, one walk (PBF.py:64-65)
+    void (*pbf_fix_position)(State &);          // fix_position, Jacobi (PBF.py:66, :104)
+    void (*pbf_finish)(State &);                // boundary + recompute_fluid_velocity (PBF.py:156-158)
     // z-slab sharding
     void (*halo_classify_pack)(State &, int n);
     void (*halo_unpack_append)(State &, int side, int count, int offset);

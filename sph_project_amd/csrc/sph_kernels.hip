@@ -275,7 +275,15 @@ void l_density(State &s, int eos) {
 // rho_src: WCSPH viscosity reads the unclamped density (rho_raw); DFSPH/PCISPH read particle_densities.
 void l_non_pressure(State &s) {
     const float *rho_src = s.visc_rho_raw ? s.rho_raw : s.rho.cur();
-    if (s.c.all_fluid) {
+    if (s.poly6) {   // PBF: poly6 surface tension, spiky viscosity (PBF.py:22-48)
+        if (s.c.all_fluid) {
+            NonPressurePass<true, Poly6Kernel> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, s.np_visc_vel};
+            launch_pass(s, p, 2);
+        } else {
+            NonPressurePass<false, Poly6Kernel> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, s.np_visc_vel};
+            launch_pass(s, p, 2);
+        }
+    } else if (s.c.all_fluid) {
         NonPressurePass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, s.np_visc_vel};
         launch_pass(s, p, 2);
     } else {
@@ -361,7 +369,8 @@ void l_wcsph_forces(State &s) {
 }
 
 void l_rigid_volume(State &s) {
-    RigidVolumePass p{s.posv.cur(), s.velm.cur(), s.meta.cur()};
+    if (s.poly6) { RigidVolumePass<Poly6Kernel> p{s.posv.cur(), s.velm.cur(), s.meta.cur()}; launch_pass(s, p); return; }   // PBF: W(0) = 0
+    RigidVolumePass<> p{s.posv.cur(), s.velm.cur(), s.meta.cur()};
     launch_pass(s, p);
 }
 
@@ -442,6 +451,7 @@ void l_clear_fresh(State &s) {
 }
 
 #include "sph_solvers_impl.hpp"
+#include "sph_pbf.hpp"
 #include "sph_halo_impl.hpp"
 }  // namespace SPH_NS
 
@@ -466,6 +476,7 @@ const Launch *SPH_LAUNCH_FN() {
         L.post_insert = l_post_insert;
         L.clear_fresh = l_clear_fresh;
         register_solver_launchers(L);
+        register_pbf_launchers(L);
         L.halo_classify_pack = l_halo_classify_pack; L.halo_unpack_append = l_halo_unpack_append;
         L.halo_build_tables = l_halo_build_tables; L.halo_pack_fields = l_halo_pack_fields;
         L.halo_unpack_fields = l_halo_unpack_fields;

@@ -131,10 +131,78 @@ struct DensityPass {
 };
 
 // ---------------------------------------------------------------------------------------
+// Smoothing-kernel family of the passes PBF shares with the other methods (NonPressurePass, RigidVolumePass): a compile-time
+// parameter.  CubicKernel is base_solver.py:57 kernel_W / :81 kernel_gradient (the functions of sph_device.hpp, unchanged);
+// Poly6Kernel is PBF.py's override of both (:22-48): poly6 W = 315 / (64 pi h^9) (h^2 - r^2)^3 and the spiky gradient
+// -45 / (pi h^6) (h - r)^2 R / r, h = dh, both zero unless 0 < r < h -- so W(0) = 0 (the self terms of compute_density and
+// compute_rigid_particle_volume vanish).  Wpoly / Wd_poly / Wscale: the fast forms that fold a constant factor of W into a
+// per-particle coefficient (W = Wscale Wpoly).
+struct CubicKernel {
+    static __device__ __forceinline__ float W(const Consts &c, const Geom &g) { return kernW(c, g); }
+    static __device__ __forceinline__ float W0(const Consts &c) { return c.W0; }
+    static __device__ __forceinline__ float Wd(const Consts &c) { return c.Wd; }
+    static __device__ __forceinline__ void grad(const Consts &c, float dx, float dy, float dz, const Geom &g, float &gx, float &gy, float &gz) {
+        kernGrad(c, dx, dy, dz, g, gx, gy, gz);
+    }
+    static __device__ __forceinline__ float gradScale(const Consts &c, const Geom &g) { return kernGradScale(c, g); }
+    static __device__ __forceinline__ float Wpoly(const Consts &, const Geom &g) { return kernWpoly(g); }
+    static __device__ __forceinline__ float Wd_poly(const Consts &c) { return c.Wd_poly; }
+    static __device__ __forceinline__ float Wscale(const Consts &c) { return c.kW; }
+};
+
+#define SPH_POLY6_FAC 1.5666814710608448f    /* PBF.py:16 poly6d_fac = 315 / 64 / pi */
+#define SPH_SPIKY_FAC -14.323944878270580f   /* PBF.py:17 spiky_grad_fac = -45 / pi */
+// PBF.py:22 kernel_W at a distance rn (the reference's operation order: x = (h h - r r) / (h h h), fac x x x)
+__device__ __forceinline__ float poly6W(const Consts &c, float rn) {
+    if (!(rn > 0.0f && rn < c.h)) return 0.0f;
+#if SPH_FAST
+    const float x = (c.h * c.h - rn * rn) * (c.inv_h * c.inv_h * c.inv_h);
+#else
+    const float x = (c.h * c.h - rn * rn) / (c.h * c.h * c.h);
+#endif
+    return SPH_POLY6_FAC * x * x * x;
+}
+// PBF.py:36 kernel_gradient = spikyScale * R
+__device__ __forceinline__ float spikyScale(const Consts &c, float rn) {
+    if (!(rn > 0.0f && rn < c.h)) return 0.0f;
+#if SPH_FAST
+    const float x = (c.h - rn) * (c.inv_h * c.inv_h * c.inv_h);
+    return ((SPH_SPIKY_FAC * x) * x) * __builtin_amdgcn_rcpf(rn);
+#else
+    const float x = (c.h - rn) / (c.h * c.h * c.h);
+    return ((SPH_SPIKY_FAC * x) * x) / rn;
+#endif
+}
+struct Poly6Kernel {
+    static __device__ __forceinline__ float W(const Consts &c, const Geom &g) { return poly6W(c, g.rn); }
+    static __device__ __forceinline__ float W0(const Consts &) { return 0.0f; }
+    // kernel_W(norm([diameter, 0, 0])) (base_solver.py:229); only the compressed pairs r <= diameter take it
+    static __device__ __forceinline__ float Wd(const Consts &c) { return poly6W(c, fsqrt(c.diameter2)); }
+    static __device__ __forceinline__ void grad(const Consts &c, float dx, float dy, float dz, const Geom &g, float &gx, float &gy, float &gz) {
+#if SPH_FAST
+        const float s = spikyScale(c, g.rn);
+        gx = s * dx; gy = s * dy; gz = s * dz;
+#else
+        // ((fac x) x) R / r, component by component as the reference's vector expression
+        gx = gy = gz = 0.0f;
+        if (g.rn > 0.0f && g.rn < c.h) {
+            const float x = (c.h - g.rn) / (c.h * c.h * c.h);
+            const float f = (SPH_SPIKY_FAC * x) * x;
+            gx = (f * dx) / g.rn; gy = (f * dy) / g.rn; gz = (f * dz) / g.rn;
+        }
+#endif
+    }
+    static __device__ __forceinline__ float gradScale(const Consts &c, const Geom &g) { return spikyScale(c, g.rn); }
+    static __device__ __forceinline__ float Wpoly(const Consts &c, const Geom &g) { return poly6W(c, g.rn); }
+    static __device__ __forceinline__ float Wd_poly(const Consts &c) { return Wd(c); }
+    static __device__ __forceinline__ float Wscale(const Consts &) { return 1.0f; }
+};
+
+// ---------------------------------------------------------------------------------------
 // base_solver.py:203 gravity + :210 surface tension (+task :218) + :232 explicit viscosity
 // (+task :240) + :643 update_fluid_velocity, fused: v* = v + dt (g + a_st + a_visc / rho0).
 // Bytes / particle: R posv 16 + velm 16 + rho_raw 4 -> W velm 16.
-template <bool AF>
+template <bool AF, class K = CubicKernel>
 struct NonPressurePass {
     static constexpr bool HAS_WRENCH = !AF;   // pair() may call add_wrench: k_nbr_pass opens / flushes the per-wave rows
     static constexpr int BLOCK = 256, GROUPS = 3;
@@ -176,7 +244,7 @@ struct NonPressurePass {
         o.vx = v.x; o.vy = v.y; o.vz = v.z; o.m = v.w;
         o.rho = rho_raw[i];
 #if SPH_FAST
-        o.st_m = (fdiv(c.st, v.w) * c.rho0) * c.kW;   // (the fast pair() keeps rho0 x (surface tension + viscosity) in o.ax and takes W without its kW)
+        o.st_m = (fdiv(c.st, v.w) * c.rho0) * K::Wscale(c);   // (the fast pair() keeps rho0 x (surface tension + viscosity) in o.ax and takes W without its kW)
 #else
         o.st_m = fdiv(c.st, v.w);
 #endif
@@ -190,18 +258,18 @@ struct NonPressurePass {
 #if SPH_FAST
         // scalar-coefficient form (see WcsphForcePass::pair): o.ax accumulates rho0 x (surface tension + viscosity), one fma per component
         if (AF || bj.w >= 0.0f) {
-            const float w = r2 > c.diameter2 ? kernWpoly(g) : c.Wd_poly;
+            const float w = r2 > c.diameter2 ? K::Wpoly(c, g) : K::Wd_poly(c);
             float k = -((o.st_m * a.w) * w);                       // (st_m carries rho0 and kW)
             if (!skip_viscosity) {
                 const float v_xy = (o.vx - bj.x) * dx + (o.vy - bj.y) * dy + (o.vz - bj.z) * dz;
                 const float m_ij = (o.m + a.w) * 0.5f;
-                k += (fdiv2(c.cv * m_ij, bj.w, r2 + c.visc_eps) * v_xy) * kernGradScale(c, g);
+                k += (fdiv2(c.cv * m_ij, bj.w, r2 + c.visc_eps) * v_xy) * K::gradScale(c, g);
             }
             o.ax += k * dx; o.ay += k * dy; o.az += k * dz;
         } else {
             if (skip_viscosity) return;
             const float v_xy = (o.vx - bj.x) * dx + (o.vy - bj.y) * dy + (o.vz - bj.z) * dz;
-            const float k = (fdiv2(c.cvb * a.w, o.rho, r2 + c.visc_eps) * v_xy) * kernGradScale(c, g);
+            const float k = (fdiv2(c.cvb * a.w, o.rho, r2 + c.visc_eps) * v_xy) * K::gradScale(c, g);
             const float acx = k * dx, acy = k * dy, acz = k * dz;
             o.ax += acx; o.ay += acy; o.az += acz;
             if (bj.w <= -2.0f) {  // dynamic rigid neighbour: base_solver.py:272-278
@@ -217,17 +285,17 @@ struct NonPressurePass {
         if (AF || bj.w >= 0.0f) {
             // surface tension
             const float cst = o.st_m * a.w;
-            const float w = r2 > c.diameter2 ? kernW(c, g) : c.Wd;
+            const float w = r2 > c.diameter2 ? K::W(c, g) : K::Wd(c);
             o.sx -= (cst * dx) * w; o.sy -= (cst * dy) * w; o.sz -= (cst * dz) * w;
             if (skip_viscosity) return;
-            kernGrad(c, dx, dy, dz, g, gx, gy, gz);
+            K::grad(c, dx, dy, dz, g, gx, gy, gz);
             const float v_xy = (o.vx - bj.x) * dx + (o.vy - bj.y) * dy + (o.vz - bj.z) * dz;
             const float m_ij = (o.m + a.w) * 0.5f;
             const float cc = fdiv2(c.cv * m_ij, bj.w, rn2 + c.visc_eps) * v_xy;
             o.ax += cc * gx; o.ay += cc * gy; o.az += cc * gz;
         } else {
             if (skip_viscosity) return;
-            kernGrad(c, dx, dy, dz, g, gx, gy, gz);
+            K::grad(c, dx, dy, dz, g, gx, gy, gz);
             const float v_xy = (o.vx - bj.x) * dx + (o.vy - bj.y) * dy + (o.vz - bj.z) * dz;
             const float cc = fdiv2(c.cvb * a.w, o.rho, rn2 + c.visc_eps) * v_xy;
             const float acx = cc * gx, acy = cc * gy, acz = cc * gz;
@@ -559,7 +627,8 @@ struct WcsphForcePass {
 };
 
 // ---------------------------------------------------------------------------------------
-// base_solver.py:106 compute_rigid_particle_volume (+task :117).  i rigid, j same object.
+// base_solver.py:106 compute_rigid_particle_volume (+task :117).  i rigid, j same object.  K: the smoothing kernel (PBF: poly6, W(0) = 0).
+template <class K = CubicKernel>
 struct RigidVolumePass {
     static constexpr int MODES = 0b001;               // runs before the density pass (no masks yet), rarely
     static constexpr int MAX_WAVES = 5;               // (one register over the six-wave budget since phase 1 became bottom-tested; it runs once per body)
@@ -585,12 +654,12 @@ struct RigidVolumePass {
         const int m = meta[i];
         if (META_MAT(m) != 2 || META_GHOST(m) || META_FRESH(m) || !(up_coord(c, pi) <= c.g_upper)) return false;
         o.obj = META_OBJ(m);
-        o.sum = c.W0;
+        o.sum = K::W0(c);
         return true;
     }
     __device__ void pair(const Consts &c, Own &o, float, float, float, float r2, const float4 &a, const BT &,
                          int) const {
-        if (__float_as_int(a.w) == o.obj) o.sum += kernW(c, geom(c, r2));
+        if (__float_as_int(a.w) == o.obj) o.sum += K::W(c, geom(c, r2));
     }
     __device__ float finish(const Consts &c, int i, const float4 &pi, Own &o) const {
         const float V = 1.0f / o.sum;

@@ -443,6 +443,32 @@ static int iisph_step(SphHandle *h, bool allow_readback) {
     return SPH_OK;
 }
 
+// PBF.py:145 _step, whole: the sort (it carries rho: compute_non_pressure_acceleration reads the densities the previous step's last
+// refine iteration left, PBF.py:146-147), the non-pressure forces + v* with poly6 / spiky kernels (:147-148), save_old_position +
+// x += dt v + boundary (:149-152), five refine iterations on the cell lists of this step's sort (:154, :62-66), boundary + v =
+// (x - x_old) / dt (:156-158).  No rigid_solver.step(), no insert_object(), no renew_rigid_particle_state: PBF.py calls none of
+// them.  Nothing is read back: fixed iteration count, asynchronous steps allowed.
+static void pbf_begin_count(SphHandle *h) {
+    State &s = h->st;
+    h->pbf_bank = s.c.stat_bank;
+    hipMemsetAsync(s.pbf_recentred + s.c.stat_bank, 0, sizeof(unsigned long long), s.stream);
+}
+
+static int pbf_step(SphHandle *h) {
+    State &s = h->st;
+    pbf_begin_count(h);
+    s.sort_skip_rho = 0; ph_neighbor_search(h);                              // :146
+    ph_rigid_volume(h);
+    int rc = run_non_pressure(h); if (rc) return rc;                          // :147-148
+    { ProfScope p(h, SPH_K_PBF_UPDATE); h->L->pbf_predict(s); }               // :149-152
+    for (int k = 0; k < SPH_PBF_ITERATIONS; ++k) {                            // :154 refine
+        { ProfScope p(h, SPH_K_PBF_DENSITY_LAMBDA); h->L->pbf_density_lambda(s); }
+        { ProfScope p(h, SPH_K_PBF_FIX_POSITION); h->L->pbf_fix_position(s); }
+    }
+    { ProfScope p(h, SPH_K_PBF_UPDATE); h->L->pbf_finish(s); }                // :156-158
+    return SPH_OK;
+}
+
 // host replica of PCISPH.py:129 compute_pcisph_k (same arithmetic as oracle/sph_ref.c)
 static float host_pcisph_k(const SphParams &p) {
     const double hd = p.support_radius;
@@ -507,6 +533,14 @@ static int method_run_phase(SphHandle *h, int phase) {
                 h->last.iter_iisph = 1; h->last.err_iisph = h->n_fluid > 0 ? sum / denom : 0.0f;
                 return SPH_OK;
             }
+            default: break;
+        }
+    } else if (h->prm.method == SPH_METHOD_PBF) {   // one refine walk on the current positions and the last sort's cell lists
+        switch (phase) {
+            case SPH_PH_PBF_DENSITY_LAMBDA: { pbf_begin_count(h); ProfScope p(h, SPH_K_PBF_DENSITY_LAMBDA); h->L->pbf_density_lambda(s); } return SPH_OK;
+            case SPH_PH_PBF_FIX_POSITION: { pbf_begin_count(h); ProfScope p(h, SPH_K_PBF_FIX_POSITION); h->L->pbf_fix_position(s); } return SPH_OK;
+            case SPH_PH_PBF_PREDICT: { ProfScope p(h, SPH_K_PBF_UPDATE); h->L->pbf_predict(s); } return SPH_OK;
+            case SPH_PH_PBF_FINISH: { ProfScope p(h, SPH_K_PBF_UPDATE); h->L->pbf_finish(s); } return SPH_OK;
             default: break;
         }
     }

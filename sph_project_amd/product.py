@@ -110,6 +110,26 @@ def iisph_bath_scene(domain_end=(5.0, 3.0, 2.0), start=(0.3, 0.2, 0.5), end=(1.2
     }
 
 
+def pbf_scene(domain_end=(2.0, 1.6, 1.0), start=(0.1, 0.1, 0.1), end=(0.6, 1.0, 0.9), add_domain_box=True, dt=4e-4):
+    """A 3-D dam break under PBF for the driver and the benchmarks: one fluid block in the corner of a domain box (the
+    reference's only PBF scene, data/scenes/high_fluid_pbf_2d.json, is 2-D, which neither it nor this project runs in 3-D
+    form).  tools/bench_pbf.py times PBF on c2_scene("pbf") instead."""
+    return {
+        "Configuration": {
+            "domainStart": [0.0, 0.0, 0.0], "domainEnd": list(domain_end), "addDomainBox": add_domain_box,
+            "particleRadius": 0.01, "fps": 30.0, "totalTime": 2.0, "density0": 1000,
+            "gravitation": [0.0, -9.81, 0.0], "simulationMethod": "pbf", "viscosityMethod": "standard",
+            "timeStepSize": dt, "viscosity": 10.0, "viscosity_b": 5.0, "boundaryHandlingMethod": 0,
+            "exportFrame": True, "exportPly": False, "exportObj": False,
+        },
+        "FluidBlocks": [{
+            "objectId": 0, "start": list(start), "end": list(end), "translation": [0.0, 0.0, 0.0],
+            "scale": [1, 1, 1], "velocity": [0.0, 0.0, 0.0], "density": 1000.0, "color": [50, 100, 200],
+            "entryTime": -1.0,
+        }],
+    }
+
+
 def scene_particles(cfg_dict):
     """Host lattice of every object present at prepare(), in the reference's insertion order
     (domain box first: base_container.py:192, then FluidBlocks: :215).  Blocks with entryTime > 0 are listed with
@@ -143,9 +163,9 @@ def build_product(cfg_dict, **engine_opts):
     cfg = SimConfig(config=copy.deepcopy(cfg_dict))
     method = cfg.get_cfg("simulationMethod")
     ccls = {"wcsph": containers.WCSPHContainer, "dfsph": containers.DFSPHContainer, "pcisph": containers.PCISPHContainer,
-            "iisph": containers.IISPHContainer}[method]
+            "iisph": containers.IISPHContainer, "pbf": containers.PBFContainer}[method]
     scls = {"wcsph": fluid_solvers.WCSPHSolver, "dfsph": fluid_solvers.DFSPHSolver, "pcisph": fluid_solvers.PCISPHSolver,
-            "iisph": fluid_solvers.IISPHSolver}[method]
+            "iisph": fluid_solvers.IISPHSolver, "pbf": fluid_solvers.PBFSolver}[method]
     container = ccls(cfg, GGUI=False, **engine_opts)
     solver = scls(container)
     return container, solver

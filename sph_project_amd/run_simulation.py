@@ -19,8 +19,8 @@ if _HERE not in sys.path:
 
 import numpy as np  # noqa: E402
 from SPH.utils import SimConfig  # noqa: E402
-from SPH.containers import DFSPHContainer, WCSPHContainer, PCISPHContainer, IISPHContainer  # noqa: E402
-from SPH.fluid_solvers import DFSPHSolver, WCSPHSolver, PCISPHSolver, IISPHSolver  # noqa: E402
+from SPH.containers import DFSPHContainer, WCSPHContainer, PCISPHContainer, IISPHContainer, PBFContainer  # noqa: E402
+from SPH.fluid_solvers import DFSPHSolver, WCSPHSolver, PCISPHSolver, IISPHSolver, PBFSolver  # noqa: E402
 
 
 PLY_COMMENT = "created by PLYWriter"   # taichi.tools.PLYWriter's default `comment`
@@ -94,7 +94,8 @@ def main(argv=None):
 
     method = config.get_cfg("simulationMethod")
     table = {"dfsph": (DFSPHContainer, DFSPHSolver), "wcsph": (WCSPHContainer, WCSPHSolver),
-             "pcisph": (PCISPHContainer, PCISPHSolver), "iisph": (IISPHContainer, IISPHSolver)}
+             "pcisph": (PCISPHContainer, PCISPHSolver), "iisph": (IISPHContainer, IISPHSolver),
+             "pbf": (PBFContainer, PBFSolver)}
     if method not in table:
         raise NotImplementedError(f"Simulation method {method} not implemented")
     container = table[method][0](config, GGUI=False)
