@@ -121,6 +121,9 @@ typedef enum {
     /* PBF (pbf_container.py:11-13; allocated for SPH_METHOD_PBF only, particle_max_num): */
     SPH_F_PBF_OLD_POSITION = 31,   /* f32[n][3] particle_old_positions (PBF.py:145 save_old_position: the positions at the step's sort) */
     SPH_F_PBF_LAMBDA = 32,         /* f32[n]    particle_pbf_lambdas (PBF.py:68 compute_lambda, last executed iteration) */
+    /* rigid contact (allocated by sph_set_rigid_contact; written for contact targets only, zeroed by SPH_PH_RIGID_CONTACT): */
+    SPH_F_RIGID_CONTACT_DN = 33,   /* f32[n][3] sum of depth * n over the target's contacts in the last contact pass */
+    SPH_F_RIGID_CONTACT_COUNT = 34,/* f32[n]    the number of those contacts (partner particles + wall planes) */
     SPH_F_COUNT_
 } SphField;
 
@@ -141,6 +144,8 @@ typedef enum {
     SPH_PH_PBF_FIX_POSITION = 11,   /* PBF.py:66 fix_position (Jacobi) on the same */
     SPH_PH_PBF_PREDICT = 12,        /* PBF.py:150-154 save_old_position + update_fluid_position + enforce_domain_boundary */
     SPH_PH_PBF_FINISH = 13,         /* PBF.py:156-158 enforce_domain_boundary + recompute_fluid_velocity */
+    SPH_PH_RIGID_CONTACT = 14,      /* the rigid contact pass (sph_set_rigid_contact) on the current positions and the last sort's cells;
+                                       the per-particle contact fields are zeroed first; the table accumulates as in a step */
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -179,7 +184,8 @@ typedef enum {
     SPH_K_CG_PREPARE = 13, SPH_K_CG_AP = 14, SPH_K_CG_VECTOR = 15, SPH_K_MISC = 16,
     SPH_K_HALO = 17, SPH_K_WCSPH_FORCES = 18,
     SPH_K_IISPH_PREPARE = 19, SPH_K_IISPH_DIJ_PJ = 20, SPH_K_IISPH_SUM_I = 21,
-    SPH_K_PBF_DENSITY_LAMBDA = 22, SPH_K_PBF_FIX_POSITION = 23, SPH_K_PBF_UPDATE = 24, SPH_K_COUNT_
+    SPH_K_PBF_DENSITY_LAMBDA = 22, SPH_K_PBF_FIX_POSITION = 23, SPH_K_PBF_UPDATE = 24,
+    SPH_K_RIGID_CONTACT = 25, SPH_K_COUNT_
 } SphKernelId;
 
 /* --- lifetime -------------------------------------------------------------------------- */
@@ -213,6 +219,30 @@ int sph_set_rigid_pose(SphHandle *h, int object_id, const float *com, const floa
 /* rigid_body_forces / rigid_body_torques read by bullet_solver.py:150-156; reset != 0 zeroes them.  On a sharded scene
    (sph_comm_set_slab) this is a collective: every rank calls it at the same point of the step and gets the sum over the ranks. */
 int sph_get_rigid_wrench(SphHandle *h, float *force, float *torque, int reset);
+
+/* Rigid contact (opt-in; the host's "contact" rigid backend).  Once per step, right after the method's passes of the first half
+   (where sph_get_rigid_wrench is read; rigid particles have not moved since the last sort), a pass walks the 27 cells around every
+   particle of a DYNAMIC rigid object and accepts every rigid particle j of ANOTHER object (dynamic, static, the domain box; ghosts
+   included, fluid skipped) with 1e-6 < |x_i - x_j| < distance.  Without a domain box the six planes wall_lo / wall_hi are partners too:
+   a particle touches a plane when it is closer than distance / 2 (depth = distance / 2 - its signed distance, contact point = its
+   projection onto the plane).  Per pair: n = (x_i - x_j) / |x_i - x_j|, depth = distance - |x_i - x_j|, bin = 2 * (dominant axis of n,
+   first of equal ones) + (that component < 0).  The pass files every pair under the key (A = i's object, B, bin), B = j's object id,
+   or 20 + bin for the domain box (object id -1) and the wall planes.  Per key the table holds
+     [0] pairs  [1..3] sum of the midpoints (x_i + x_j) / 2  [4..6] sum of depth * n  [7] maximum depth
+   accumulated as 64-bit fixed point (2^-32 per unit): bit-reproducible, and summed until read with reset != 0.
+   sph_set_rigid_contact: distance <= the grid cell size; wall_lo / wall_hi (3-vectors, scene frame) both null in a scene with a domain
+   box.  on = 0 turns the pass off.  SPH_ERR_UNSUPPORTED on a PBF handle (PBF moves no rigid body).
+   sph_get_rigid_contacts: table = double[SPH_MAX_OBJECTS][SPH_CONTACT_PARTNERS][SPH_CONTACT_BINS][SPH_CONTACT_VALUES] in the scene frame
+   (bins and vectors mapped back under SPH_SLAB_LAYOUT=slow).  On a sharded scene a collective like sph_get_rigid_wrench: every rank
+   walks its own targets (ghosts are partners) and gets the sum over the ranks (maximum for [7]). */
+#define SPH_CONTACT_PARTNERS 26
+#define SPH_CONTACT_BINS 6
+#define SPH_CONTACT_VALUES 8
+int sph_set_rigid_contact(SphHandle *h, int on, float distance, const float *wall_lo, const float *wall_hi);
+int sph_get_rigid_contacts(SphHandle *h, double *table, int reset);
+/* accepted contacts (partner particles + wall planes) of the last contact pass on this handle (this rank's targets).  A query of its
+   own rather than a SphStats field: the statistics struct ends at pbf_recentred by contract. */
+int sph_get_rigid_contact_pairs(SphHandle *h, int64_t *pairs);
 
 /* --- time stepping --------------------------------------------------------------------- */
 /* replaces XSolver.prepare() (base_solver.py:683, DFSPH.py:321, PCISPH.py:188); particles of

@@ -147,6 +147,7 @@ class BaseContainer:
         # multi-GPU: engine_opts["slab"] = dict(rank=, nranks=, unique_id=<128 bytes>, cuts=[...]) -> this container
         # only inserts the particles of its own z-slab (sph_project_amd/slab.py)
         self.slab = engine_opts.get("slab")
+        self.rigid_backend = engine_opts.get("rigid_backend")   # host rigid solver backend (None: SPH_RIGID_BACKEND, else native)
         self._global_ids = []
         self._next_global_id = 0
         comm = engine_opts.get("comm")   # communicator without sharding (bench replicas: barrier / all-reduce only)

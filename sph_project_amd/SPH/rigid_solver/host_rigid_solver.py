@@ -15,6 +15,12 @@ Two backends:
     contacts, no friction, no contact torque: that is Bullet's job, and a scene that needs it diverges from the
     reference -- the first dynamic body integrated by this backend therefore prints a one-time warning to stderr
     (silence it with SPH_RIGID_NATIVE_OK=1).  Unit-tested (tests/test_rigid_host.py).
+  * "contact" (opt-in, SPH_RIGID_BACKEND=contact): the native integrator plus body-body and body-wall contact.  The device's
+    rigid contact pass (sph_set_rigid_contact) reduces the touching particle pairs of every step to a table keyed by (dynamic body,
+    partner, normal bin); each non-empty key becomes ONE contact (mean midpoint, normalised sum of depth * n, maximum depth), and a
+    sequential-impulse solver resolves all of them together: restitution, Coulomb friction, split-impulse position correction;
+    static bodies, the domain box and the wall planes have infinite mass.  No AABB clamp.  Parameters: the optional Configuration keys
+    rigidContactRestitution / rigidContactFriction / rigidContactIterations.  Unit-tested (tests/test_contact_host.py).
   * "pybullet": the reference's calls (URDF from the mesh file, applyExternalForce / Torque at the base,
     stepSimulation, base pose read-back) when the package is importable.  It is not installed in this image, so this
     backend has never run here; select it with SPH_RIGID_BACKEND=pybullet.
@@ -27,6 +33,12 @@ import sys
 import numpy as np
 
 _WARNED = [False]
+# contact backend: resting contacts keep this much depth (in units of the contact distance D), so that the touching particle set of a
+# resting face -- and with it the contact point -- does not flicker from step to step
+CONTACT_SLOP = 0.05
+# ... and every contact resists rolling within mu lambda_n times this radius (units of D): one aggregated point per key cannot carry the
+# torque the pressure distribution of a face does.  Both are Configuration keys (rigidContactSlop, rigidContactRollingRadius).
+CONTACT_ROLLING_RADIUS = 1.0
 
 
 def _rotation(angle, axis):
@@ -71,7 +83,8 @@ class HostRigidSolver:
         self.rigid_bodies = container.cfg.get_rigid_bodies()
         self.rigid_blocks = container.cfg.get_rigid_blocks()
         self.bodies = {}   # object id -> _Body (dynamic ones)
-        self.backend = os.environ.get("SPH_RIGID_BACKEND", "native")
+        # the container's rigid_backend option (run_simulation.py --rigid_backend) first, then SPH_RIGID_BACKEND
+        self.backend = getattr(container, "rigid_backend", None) or os.environ.get("SPH_RIGID_BACKEND", "native")
         self._bullet = None
         if not self.rigid_bodies and not self.rigid_blocks:
             print("No rigid body in the scene, skip bullet solver initialization.")
@@ -80,12 +93,30 @@ class HostRigidSolver:
                 self._bullet = _BulletBackend(container, self.gravity, self.dt)
             except ImportError as e:   # asked for explicitly: never fall back silently
                 raise NotImplementedError("SPH_RIGID_BACKEND=pybullet, but pybullet is not importable") from e
-        elif self.backend != "native":
-            raise ValueError(f"SPH_RIGID_BACKEND={self.backend!r}: expected 'native' or 'pybullet'")
+        elif self.backend not in ("native", "contact"):
+            raise ValueError(f"SPH_RIGID_BACKEND={self.backend!r}: expected 'native', 'contact' or 'pybullet'")
         # walls no part of a body may cross (bullet_solver.py:57-61)
         eps = container.padding + container.particle_diameter + container.domain_box_thickness
         self.wall_lo = np.asarray(container.domain_start, dtype=np.float64) + eps
         self.wall_hi = np.asarray(container.domain_end, dtype=np.float64) - eps
+        self.contact = None
+        dynamic = any(b["isDynamic"] for b in self.rigid_bodies)
+        if self.backend == "contact" and getattr(container, "METHOD", None) == "pbf":
+            print("SPH_RIGID_BACKEND=contact: PBF moves no rigid body (PBF.py _step), contact stays off.")
+        elif self.backend == "contact" and dynamic:   # (static bodies alone: nothing would read the table)
+            cfg = container.cfg
+            get = lambda k, d: d if cfg.get_cfg(k) is None else cfg.get_cfg(k)
+            self.contact = ContactSolver(restitution=float(get("rigidContactRestitution", 0.2)),
+                                         friction=float(get("rigidContactFriction", 0.5)),
+                                         iterations=int(get("rigidContactIterations", 10)),
+                                         gravity=self.gravity, dt=self.dt)
+            # D: the pitch bodies and box are sampled at; wall planes only where no domain box stands in for them
+            self.contact_distance = float(getattr(container, "particle_spacing", container.particle_diameter))
+            self.contact.slop = float(get("rigidContactSlop", CONTACT_SLOP)) * self.contact_distance
+            self.contact.patch = float(get("rigidContactRollingRadius", CONTACT_ROLLING_RADIUS)) * self.contact_distance
+            walls = not getattr(container, "add_domain_box", False)
+            container.engine.set_rigid_contact(True, self.contact_distance, self.wall_lo if walls else None,
+                                               self.wall_hi if walls else None)
 
     # ------------------------------------------------------------------ bullet_solver.py:46-51, :75-131
     def insert_rigid_object(self):
@@ -112,13 +143,14 @@ class HostRigidSolver:
             mass = float(c.rigid_body_masses[oid]) or m_p * len(pts)
             self.bodies[oid] = _Body(oid, mass, inertia, translation, rot, vel)
             self.bodies[oid].points = pts
-            if self._bullet is None and not _WARNED[0] and not os.environ.get("SPH_RIGID_NATIVE_OK"):
+            if self._bullet is None and self.contact is None and not _WARNED[0] and not os.environ.get("SPH_RIGID_NATIVE_OK"):
                 _WARNED[0] = True
                 print("WARNING: dynamic rigid body %d is integrated by the built-in 'native' rigid backend: free-body motion under "
                       "gravity + the fluid wrench, wall contact by the body's axis-aligned extent, NO body-body contacts, friction or "
                       "contact torque (the reference uses PyBullet, bullet_solver.py).  Trajectories of bodies in contact diverge "
                       "from the reference; install pybullet and set SPH_RIGID_BACKEND=pybullet for its behaviour "
-                      "(SPH_RIGID_NATIVE_OK=1 silences this)." % oid, file=sys.stderr, flush=True)
+                      "(SPH_RIGID_NATIVE_OK=1 silences this).  SPH_RIGID_BACKEND=contact adds body-body contact, friction and "
+                      "contact torque." % oid, file=sys.stderr, flush=True)
             if self._bullet is not None:
                 self._bullet.add(body, mass, translation, angle, vel)
             self._push(self.bodies[oid], com0=np.zeros(3))
@@ -134,7 +166,10 @@ class HostRigidSolver:
         if not self.bodies:
             return
         force, torque = self.container.engine.get_rigid_wrench(reset=True)
-        if self._bullet is not None:
+        if self.contact is not None:
+            table = self.container.engine.get_rigid_contacts(reset=True)
+            self.contact.step(self.bodies, force.astype(np.float64), torque.astype(np.float64), contacts_from_table(table, self.bodies))
+        elif self._bullet is not None:
             self._bullet.step(self.bodies, force, torque)
         else:
             for b in self.bodies.values():
@@ -173,6 +208,150 @@ class HostRigidSolver:
         b = self.bodies[container_idx]
         return {"position": b.com.copy(), "rotation_matrix": b.rot.copy(), "linear_velocity": b.vel.copy(),
                 "angular_velocity": b.angvel.copy()}
+
+
+def contacts_from_table(table, bodies):
+    """One contact per non-empty key (A, B, bin) of a dynamic body A: (A, B or None for an infinite-mass partner, point = mean midpoint,
+    normal = normalised sum of depth * n (from B towards A), depth = maximum depth).  For the domain box and the wall planes (B >= 20)
+    the normal is the bin's axis: their faces are axis-aligned planes, and the pair normals of a lattice sliding over the box's lattice
+    tilt by up to 45 degrees with the offset between the two.  A pair of dynamic bodies is taken from the row of
+    the lower id only: the other row holds the same pairs with opposite normals."""
+    out = []
+    A_idx, B_idx, bins = np.nonzero(table[..., 0] > 0)
+    for a, b, k in zip(A_idx.tolist(), B_idx.tolist(), bins.tolist()):
+        if a not in bodies:
+            continue
+        partner = b if (b < 20 and b in bodies) else None
+        if partner is not None and partner < a:
+            continue
+        v = table[a, b, k]
+        dn = v[4:7]
+        nrm = float(np.linalg.norm(dn))
+        if nrm <= 0.0:
+            continue
+        n = dn / nrm
+        if b >= 20:   # the domain box / a wall plane: an axis-aligned face, its normal is the bin's axis
+            n = np.zeros(3)
+            n[k // 2] = -1.0 if k % 2 else 1.0
+        out.append((a, partner, v[1:4] / v[0], n, float(v[7])))
+    return out
+
+
+def _tangents(n):
+    t1 = np.cross(n, [1.0, 0.0, 0.0] if abs(n[0]) < 0.9 else [0.0, 1.0, 0.0])
+    t1 /= np.linalg.norm(t1)
+    return t1, np.cross(n, t1)
+
+
+class ContactSolver:
+    """Sequential impulses on aggregated contacts, one body-level solve per step.
+
+    Per step: v += dt (F / m + g), w += dt I^-1 (tau - w x I w) (the native integrator's velocity half); then `iterations` sweeps over
+    all contacts with accumulated, clamped impulses -- normal lambda >= 0 towards the target normal velocity max(-e v_n, 0) (restitution
+    only for approach speeds above 2 |g| dt, so a resting contact does not bounce), friction lambda_t within the Coulomb disc mu lambda_n
+    -- and a rolling resistance within mu lambda_n * patch about the tangents (one aggregated point cannot carry the torque a face's
+    pressure distribution does) -- then `iterations` sweeps of split impulses on pseudo-velocities that remove beta (depth - slop) / dt of the depth; positions move
+    with v + the pseudo-velocity, which is then dropped (position correction adds no energy)."""
+
+    def __init__(self, restitution=0.2, friction=0.5, iterations=10, gravity=(0.0, -9.81, 0.0), dt=1e-3, beta=0.2, slop=0.0):
+        self.e, self.mu, self.iterations = float(restitution), float(friction), int(iterations)
+        self.gravity, self.dt = np.asarray(gravity, dtype=np.float64), float(dt)
+        self.beta, self.slop = float(beta), float(slop)
+        self.patch = 0.0   # rolling-resistance radius of a contact patch (the backend sets D)
+
+    def step(self, bodies, force, torque, contacts):
+        dt = self.dt
+        inv_i = {}
+        for oid, b in bodies.items():
+            b.vel = b.vel + dt * (force[oid] / b.mass + self.gravity)
+            I_w = b.rot @ b.I_body @ b.rot.T
+            inv_i[oid] = b.rot @ b.I_body_inv @ b.rot.T
+            b.angvel = b.angvel + dt * (inv_i[oid] @ (torque[oid] - np.cross(b.angvel, I_w @ b.angvel)))
+        pv = {oid: np.zeros(3) for oid in bodies}
+        pw = {oid: np.zeros(3) for oid in bodies}
+        rows = []
+        v_thr = 2.0 * float(np.linalg.norm(self.gravity)) * dt
+        for a, bb, p, n, depth in contacts:
+            ra = p - bodies[a].com
+            rb = p - bodies[bb].com if bb is not None else None
+            t1, t2 = _tangents(n)
+
+            def k_of(d):
+                k = 1.0 / bodies[a].mass + d @ np.cross(inv_i[a] @ np.cross(ra, d), ra)
+                if bb is not None:
+                    k += 1.0 / bodies[bb].mass + d @ np.cross(inv_i[bb] @ np.cross(rb, d), rb)
+                return k
+            vn0 = self._rel(bodies, a, bb, ra, rb) @ n
+            target = -self.e * vn0 if vn0 < -v_thr else 0.0
+            bias = self.beta * max(depth - self.slop, 0.0) / dt
+            kr = tuple(t @ inv_i[a] @ t + (t @ inv_i[bb] @ t if bb is not None else 0.0) for t in (t1, t2))
+            rows.append(dict(a=a, b=bb, ra=ra, rb=rb, n=n, t=(t1, t2), kn=k_of(n), kt=(k_of(t1), k_of(t2)), kr=kr, target=target,
+                             bias=bias, ln=0.0, lt=np.zeros(2), lr=np.zeros(2), lp=0.0))
+        for _ in range(self.iterations):
+            for c in rows:
+                vrel = self._rel(bodies, c["a"], c["b"], c["ra"], c["rb"])
+                ln = max(c["ln"] + (c["target"] - vrel @ c["n"]) / c["kn"], 0.0)
+                self._apply(bodies, inv_i, c, (ln - c["ln"]) * c["n"])
+                c["ln"] = ln
+                vrel = self._rel(bodies, c["a"], c["b"], c["ra"], c["rb"])
+                lt = c["lt"] - np.array([vrel @ c["t"][0] / c["kt"][0], vrel @ c["t"][1] / c["kt"][1]])
+                cap, mag = self.mu * c["ln"], float(np.linalg.norm(lt))
+                if mag > cap:
+                    lt = lt * (cap / mag)
+                d = lt - c["lt"]
+                self._apply(bodies, inv_i, c, d[0] * c["t"][0] + d[1] * c["t"][1])
+                c["lt"] = lt
+                # rolling resistance of the contact patch (radius D): the relative spin about the tangents, within mu lambda_n D
+                wrel = bodies[c["a"]].angvel - (bodies[c["b"]].angvel if c["b"] is not None else 0.0)
+                lr = c["lr"] - np.array([wrel @ c["t"][0] / c["kr"][0], wrel @ c["t"][1] / c["kr"][1]])
+                cap, mag = self.mu * c["ln"] * self.patch, float(np.linalg.norm(lr))
+                if mag > cap:
+                    lr = lr * (cap / mag)
+                d = lr - c["lr"]
+                self._apply_angular(bodies, inv_i, c, d[0] * c["t"][0] + d[1] * c["t"][1])
+                c["lr"] = lr
+        for _ in range(self.iterations):
+            for c in rows:
+                a, bb = c["a"], c["b"]
+                vp = pv[a] + np.cross(pw[a], c["ra"])
+                if bb is not None:
+                    vp = vp - pv[bb] - np.cross(pw[bb], c["rb"])
+                lp = max(c["lp"] + (c["bias"] - vp @ c["n"]) / c["kn"], 0.0)
+                j = (lp - c["lp"]) * c["n"]
+                c["lp"] = lp
+                pv[a] = pv[a] + j / bodies[a].mass
+                pw[a] = pw[a] + inv_i[a] @ np.cross(c["ra"], j)
+                if bb is not None:
+                    pv[bb] = pv[bb] - j / bodies[bb].mass
+                    pw[bb] = pw[bb] - inv_i[bb] @ np.cross(c["rb"], j)
+        for oid, b in bodies.items():
+            b.com = b.com + dt * (b.vel + pv[oid])
+            b.rot = _skew_exp(dt * (b.angvel + pw[oid])) @ b.rot
+            u, _, vt = np.linalg.svd(b.rot)
+            b.rot = u @ vt
+        return rows
+
+    @staticmethod
+    def _rel(bodies, a, bb, ra, rb):
+        v = bodies[a].vel + np.cross(bodies[a].angvel, ra)
+        if bb is not None:
+            v = v - bodies[bb].vel - np.cross(bodies[bb].angvel, rb)
+        return v
+
+    @staticmethod
+    def _apply_angular(bodies, inv_i, c, m):
+        bodies[c["a"]].angvel = bodies[c["a"]].angvel + inv_i[c["a"]] @ m
+        if c["b"] is not None:
+            bodies[c["b"]].angvel = bodies[c["b"]].angvel - inv_i[c["b"]] @ m
+
+    @staticmethod
+    def _apply(bodies, inv_i, c, j):
+        a, bb = c["a"], c["b"]
+        bodies[a].vel = bodies[a].vel + j / bodies[a].mass
+        bodies[a].angvel = bodies[a].angvel + inv_i[a] @ np.cross(c["ra"], j)
+        if bb is not None:
+            bodies[bb].vel = bodies[bb].vel - j / bodies[bb].mass
+            bodies[bb].angvel = bodies[bb].angvel - inv_i[bb] @ np.cross(c["rb"], j)
 
 
 class _BulletBackend:   # pragma: no cover - needs pybullet (absent in this image)

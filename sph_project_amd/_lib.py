@@ -22,7 +22,8 @@ METHOD = {"wcsph": 0, "dfsph": 1, "pcisph": 2, "iisph": 3, "pbf": 4}
  F_OBJECT_ID, F_IS_DYNAMIC, F_COLOR, F_PARTICLE_ID, F_GRID_ID, F_DFSPH_ALPHA, F_DFSPH_KAPPA,
  F_DFSPH_KAPPA_V, F_DENSITY_STAR, F_DENSITY_DERIV, F_PRESSURE_ACCEL, F_PREDICTED_VEL, F_PREDICTED_POS,
  F_CG_X, F_ORIG_POSITION, F_GHOST, F_DFSPH_KAPPA_NEXT, F_DFSPH_KAPPA_V_NEXT, F_DEBUG_CAPTURE,
- F_IISPH_DII, F_IISPH_AII, F_IISPH_DIJ_PJ, F_IISPH_SUM_I, F_PBF_OLD_POSITION, F_PBF_LAMBDA) = range(33)
+ F_IISPH_DII, F_IISPH_AII, F_IISPH_DIJ_PJ, F_IISPH_SUM_I, F_PBF_OLD_POSITION, F_PBF_LAMBDA, F_RIGID_CONTACT_DN,
+ F_RIGID_CONTACT_COUNT) = range(35)
 
 _FIELD_SPEC = {  # field -> (dtype, components)
     F_POSITION: (np.float32, 3), F_VELOCITY: (np.float32, 3), F_ACCELERATION: (np.float32, 3),
@@ -36,12 +37,13 @@ _FIELD_SPEC = {  # field -> (dtype, components)
     F_DFSPH_KAPPA_NEXT: (np.float32, 1), F_DFSPH_KAPPA_V_NEXT: (np.float32, 1), F_DEBUG_CAPTURE: (np.float32, 1),
     F_IISPH_DII: (np.float32, 3), F_IISPH_AII: (np.float32, 1), F_IISPH_DIJ_PJ: (np.float32, 3), F_IISPH_SUM_I: (np.float32, 1),
     F_PBF_OLD_POSITION: (np.float32, 3), F_PBF_LAMBDA: (np.float32, 1),
+    F_RIGID_CONTACT_DN: (np.float32, 3), F_RIGID_CONTACT_COUNT: (np.float32, 1),
 }
 
 # enum SphPhase
 (PH_NEIGHBOR_SEARCH, PH_RIGID_VOLUME, PH_DENSITY, PH_NON_PRESSURE, PH_PRESSURE_INTEGRATE, PH_DFSPH_ALPHA,
  PH_DFSPH_DIVERGENCE, PH_DFSPH_DENSITY, PH_IISPH_PREPARE, PH_IISPH_ITERATION, PH_PBF_DENSITY_LAMBDA,
- PH_PBF_FIX_POSITION, PH_PBF_PREDICT, PH_PBF_FINISH) = range(14)
+ PH_PBF_FIX_POSITION, PH_PBF_PREDICT, PH_PBF_FINISH, PH_RIGID_CONTACT) = range(15)
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
@@ -49,6 +51,12 @@ KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "press
               "pcisph_rho_star", "pcisph_pressure_accel", "cg_prepare", "cg_ap", "cg_vector", "misc", "halo",
               "wcsph_forces", "iisph_prepare", "iisph_dij_pj", "iisph_sum_i", "pbf_density_lambda", "pbf_fix_position",
               "pbf_update"]
+K_RIGID_CONTACT = 25   # sph_kernel_name(25) == "rigid_contact" (KERNEL_IDS keeps its PBF tail)
+
+# rigid contact table (sph_get_rigid_contacts): [object A][partner B][normal bin][value]; partners 20..25 are the domain box /
+# the wall planes, one per bin; values: pairs, midpoint sum (3), depth * n sum (3), maximum depth
+CONTACT_PARTNERS, CONTACT_BINS, CONTACT_VALUES = 26, 6, 8
+CONTACT_WALL0 = 20
 
 
 class SphParams(C.Structure):
@@ -92,6 +100,9 @@ _SIGNATURES = [
     ("sph_set_object", C.c_int, [_VP, C.c_int, C.c_int, C.c_int]),
     ("sph_set_rigid_pose", C.c_int, [_VP, C.c_int] + [_VP] * 5),
     ("sph_get_rigid_wrench", C.c_int, [_VP, _VP, _VP, C.c_int]),
+    ("sph_set_rigid_contact", C.c_int, [_VP, C.c_int, C.c_float, _VP, _VP]),
+    ("sph_get_rigid_contacts", C.c_int, [_VP, _VP, C.c_int]),
+    ("sph_get_rigid_contact_pairs", C.c_int, [_VP, C.POINTER(C.c_int64)]),
     ("sph_prepare", C.c_int, [_VP]),
     ("sph_step", C.c_int, [_VP, C.c_int]),
     ("sph_step_async", C.c_int, [_VP, C.c_int]),
@@ -212,6 +223,21 @@ class Engine:
         torque = np.zeros((MAX_OBJECTS, 3), np.float32)
         self._chk(self.lib.sph_get_rigid_wrench(self.h, _ptr(force), _ptr(torque), int(reset)), "sph_get_rigid_wrench")
         return force, torque
+
+    def set_rigid_contact(self, on=True, distance=0.0, wall_lo=None, wall_hi=None):
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(3)
+        lo, hi = f(wall_lo), f(wall_hi)
+        self._chk(self.lib.sph_set_rigid_contact(self.h, int(bool(on)), float(distance), _ptr(lo), _ptr(hi)), "sph_set_rigid_contact")
+
+    def get_rigid_contacts(self, reset=True):
+        table = np.zeros((MAX_OBJECTS, CONTACT_PARTNERS, CONTACT_BINS, CONTACT_VALUES), np.float64)
+        self._chk(self.lib.sph_get_rigid_contacts(self.h, _ptr(table), int(reset)), "sph_get_rigid_contacts")
+        return table
+
+    def get_rigid_contact_pairs(self):
+        n = C.c_int64(0)
+        self._chk(self.lib.sph_get_rigid_contact_pairs(self.h, C.byref(n)), "sph_get_rigid_contact_pairs")
+        return n.value
 
     # -- stepping
     def prepare(self):

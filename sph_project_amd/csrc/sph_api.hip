@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include <utility>
 #include <array>
+#include <algorithm>
 #include "sph_voxel.hpp"
 #include "sph_export.hpp"
 
@@ -223,7 +224,8 @@ extern "C" const char *sph_kernel_name(int k) {
         "hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate", "rigid_volume",
         "dfsph_density_alpha", "dfsph_rho_adv", "dfsph_correct", "reduce", "pcisph_rho_star",
         "pcisph_pressure_accel", "cg_prepare", "cg_ap", "cg_vector", "misc", "halo", "wcsph_forces",
-        "iisph_prepare", "iisph_dij_pj", "iisph_sum_i", "pbf_density_lambda", "pbf_fix_position", "pbf_update"};
+        "iisph_prepare", "iisph_dij_pj", "iisph_sum_i", "pbf_density_lambda", "pbf_fix_position", "pbf_update",
+        "rigid_contact"};
     return (k >= 0 && k < SPH_K_COUNT_) ? names[k] : "?";
 }
 
@@ -336,6 +338,7 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     s.pacc = s.pvel = s.ppos = s.acc_np = nullptr; s.np_acc_out = nullptr; s.np_visc_vel = nullptr;
     s.iisph_dii = s.iisph_dij = s.iisph_w = nullptr;
     s.pbf_old = s.pbf_pos = nullptr; s.pbf_lambda = nullptr; s.pbf_recentred = nullptr; s.poly6 = 0;
+    s.contact_on = 0; s.contact = ContactArgs{}; s.contact_table = s.contact_pairs = nullptr; s.contact_part = nullptr;
     s.cg_p2 = nullptr; s.cg_fuse = s.cg_fused_loop = 0;
     s.cg_p = s.cg_Ap = s.cg_x = s.cg_b = s.cg_r = s.cg_v0 = nullptr; s.cg_dinv = nullptr; s.cg_part = nullptr; s.cg_split = 0; s.cg_nocombine = 0; s.split_next_pass = 0;
     if (p.method == SPH_METHOD_DFSPH) {
@@ -534,6 +537,99 @@ extern "C" int sph_get_rigid_wrench(SphHandle *h, float *force, float *torque, i
     }
     if (reset)
         HIPCHK(h, hipMemsetAsync((char *)h->st.scal + offsetof(DevScalars, wrench), 0, sizeof(long long) * 2 * SPH_NOBJ * 3, h->st.stream));
+    return SPH_OK;
+}
+
+extern "C" int sph_set_rigid_contact(SphHandle *h, int on, float distance, const float *wall_lo, const float *wall_hi) {
+    if (!h) return SPH_ERR_INVALID;
+    if (h->prm.method == SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "set_rigid_contact: PBF moves no rigid body (PBF.py _step)");
+    State &s = h->st;
+    if (!on) { s.contact_on = 0; return SPH_OK; }
+    if (!(distance > 0.0f) || distance > s.c.grid_size)
+        return fail(h, SPH_ERR_INVALID, "set_rigid_contact: distance %g outside (0, cell size %g]", (double)distance, (double)s.c.grid_size);
+    if (!wall_lo != !wall_hi) return fail(h, SPH_ERR_INVALID, "set_rigid_contact: give both wall planes or neither");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!s.contact_table) {
+        int rc = dalloc(h, &s.contact_table, (size_t)SPH_CT_KEYS * SPH_CT_VALUES); if (rc) return rc;
+        rc = dalloc(h, &s.contact_pairs, 1); if (rc) return rc;
+        rc = dalloc(h, &s.contact_part, (size_t)s.cap); if (rc) return rc;
+    }
+    ContactArgs a{};
+    a.D = distance;
+    a.walls = wall_lo ? 1 : 0;
+    for (int k = 0; k < 3; ++k) {   // scene frame -> library frame
+        a.lo[k] = wall_lo ? wall_lo[h->perm[k]] : 0.0f;
+        a.hi[k] = wall_hi ? wall_hi[h->perm[k]] : 0.0f;
+    }
+    s.contact = a;
+    s.contact_on = 1;
+    return SPH_OK;
+}
+
+// the table in the scene frame: bin 2 a + s of library axis a is bin 2 perm[a] + s of the scene, vectors are permuted back like the wrench
+static void contact_to_scene(const SphHandle *h, const unsigned long long *dev, double *out) {
+    const size_t row = SPH_CT_VALUES;
+    for (int A = 0; A < SPH_NOBJ; ++A)
+        for (int B = 0; B < SPH_CT_PARTNERS; ++B)
+            for (int b = 0; b < SPH_CT_BINS; ++b) {
+                const int bs = 2 * h->perm[b / 2] + (b & 1);
+                const int Bs = B >= 20 ? 20 + (2 * h->perm[(B - 20) / 2] + ((B - 20) & 1)) : B;
+                const long long *v = (const long long *)dev + ((size_t)(A * SPH_CT_PARTNERS + B) * SPH_CT_BINS + b) * row;
+                double *o = out + ((size_t)(A * SPH_CT_PARTNERS + Bs) * SPH_CT_BINS + bs) * row;
+                o[0] = (double)v[0];
+                for (int a = 0; a < 3; ++a) {
+                    o[1 + a] = (double)v[1 + h->inv[a]] / SPH_WRENCH_SCALE;
+                    o[4 + a] = (double)v[4 + h->inv[a]] / SPH_WRENCH_SCALE;
+                }
+                o[7] = (double)(unsigned long long)v[7] / SPH_WRENCH_SCALE;
+            }
+}
+
+extern "C" int sph_get_rigid_contacts(SphHandle *h, double *table, int reset) {
+    if (!h || !table) return fail(h, SPH_ERR_INVALID, "get_rigid_contacts: null");
+    State &s = h->st;
+    const size_t words = (size_t)SPH_CT_KEYS * SPH_CT_VALUES;
+    if (!s.contact_table) return fail(h, SPH_ERR_INVALID, "get_rigid_contacts: sph_set_rigid_contact was never enabled");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::vector<unsigned long long> dev(words);
+    HIPCHK(h, hipMemcpyAsync(dev.data(), s.contact_table, words * 8, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(h, hipStreamSynchronize(s.stream));
+    contact_to_scene(h, dev.data(), table);
+    if (s.slab_active && h->comm.nranks > 1) {
+        // Collective, like the wrench: every rank walked its own targets.  The union of the non-empty keys first -- 4-bit digits, 12 keys
+        // per double (a digit sums at most nranks <= 15 flags: no carry) -- then the sums and maxima of those keys only, 128 at a time.
+        if (h->comm.nranks > 15) return fail(h, SPH_ERR_UNSUPPORTED, "get_rigid_contacts: more than 15 ranks");
+        const int per = 12, nd = (SPH_CT_KEYS + per - 1) / per;
+        std::vector<double> dig(nd, 0.0);
+        for (int k = 0; k < SPH_CT_KEYS; ++k) if (table[(size_t)k * 8] > 0.0) dig[k / per] += (double)(1ll << (4 * (k % per)));
+        for (int o = 0; o < nd; o += SHM_RED_MAX) { int rc = sph_comm_allreduce(h, dig.data() + o, std::min(SHM_RED_MAX, nd - o), 0); if (rc) return rc; }
+        std::vector<int> keys;
+        for (int k = 0; k < SPH_CT_KEYS; ++k) if (((long long)dig[k / per] >> (4 * (k % per))) & 15) keys.push_back(k);
+        std::vector<double> sum(keys.size() * 7), mx(keys.size());
+        for (size_t q = 0; q < keys.size(); ++q) {
+            for (int v = 0; v < 7; ++v) sum[7 * q + v] = table[(size_t)keys[q] * 8 + v];
+            mx[q] = table[(size_t)keys[q] * 8 + 7];
+        }
+        for (size_t o = 0; o < sum.size(); o += SHM_RED_MAX) { int rc = sph_comm_allreduce(h, sum.data() + o, (int)std::min((size_t)SHM_RED_MAX, sum.size() - o), 0); if (rc) return rc; }
+        for (size_t o = 0; o < mx.size(); o += SHM_RED_MAX) { int rc = sph_comm_allreduce(h, mx.data() + o, (int)std::min((size_t)SHM_RED_MAX, mx.size() - o), 1); if (rc) return rc; }
+        for (size_t q = 0; q < keys.size(); ++q) {
+            for (int v = 0; v < 7; ++v) table[(size_t)keys[q] * 8 + v] = sum[7 * q + v];
+            table[(size_t)keys[q] * 8 + 7] = mx[q];
+        }
+    }
+    if (reset) HIPCHK(h, hipMemsetAsync(s.contact_table, 0, words * 8, s.stream));
+    return SPH_OK;
+}
+
+extern "C" int sph_get_rigid_contact_pairs(SphHandle *h, int64_t *pairs) {
+    if (!h || !pairs) return fail(h, SPH_ERR_INVALID, "get_rigid_contact_pairs: null");
+    *pairs = 0;
+    if (!h->st.contact_pairs) return SPH_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    unsigned long long r = 0;
+    HIPCHK(h, hipMemcpyAsync(&r, h->st.contact_pairs, sizeof(r), hipMemcpyDeviceToHost, h->st.stream));
+    HIPCHK(h, hipStreamSynchronize(h->st.stream));
+    *pairs = (int64_t)r;
     return SPH_OK;
 }
 
@@ -781,6 +877,8 @@ static int step_first_half(SphHandle *h, bool allow_readback) {
         default: rc = pcisph_step(h, allow_readback); break;                  // PCISPH.py:166-177
     }
     if (rc) return rc;
+    // rigid contact, where the host reads the wrench: the rigid particles still sit where the last sort put them
+    if (h->st.contact_on) { ProfScope p(h, SPH_K_RIGID_CONTACT); h->L->rigid_contact(h->st); }
     h->n_mark = h->n;
     h->in_step = true;
     return SPH_OK;
@@ -898,6 +996,11 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
         case SPH_PH_DENSITY: { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, h->prm.method == SPH_METHOD_WCSPH); } break;
         case SPH_PH_NON_PRESSURE: { int rc = run_non_pressure(h); if (rc) return rc; } break;
         case SPH_PH_PRESSURE_INTEGRATE: { ProfScope p(h, SPH_K_PRESSURE_INTEGRATE); h->L->pressure_integrate(s); } break;
+        case SPH_PH_RIGID_CONTACT: {
+            if (!s.contact_on) return fail(h, SPH_ERR_INVALID, "SPH_PH_RIGID_CONTACT: sph_set_rigid_contact is off");
+            HIPCHK(h, hipMemsetAsync(s.contact_part, 0, sizeof(float4) * (size_t)s.cap, s.stream));
+            ProfScope p(h, SPH_K_RIGID_CONTACT); h->L->rigid_contact(s);
+        } break;
         default: { int rc = method_run_phase(h, phase); if (rc) return rc; }
     }
     int rc = check_async(h); if (rc) return rc;
@@ -947,6 +1050,7 @@ static const float4 *vec_field(SphHandle *h, int field) {
         case SPH_F_IISPH_DII: case SPH_F_IISPH_AII: return s.iisph_dii;     // (dii, aii)
         case SPH_F_IISPH_DIJ_PJ: case SPH_F_IISPH_SUM_I: return s.iisph_dij; // (dij_pj, sum_i)
         case SPH_F_PBF_OLD_POSITION: return s.pbf_old;                       // (x_old, sorted cell id)
+        case SPH_F_RIGID_CONTACT_DN: case SPH_F_RIGID_CONTACT_COUNT: return s.contact_part;   // (sum of depth * n, contacts)
         default: return nullptr;
     }
 }
@@ -978,7 +1082,7 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
     const bool is_vec3 = field == SPH_F_POSITION || field == SPH_F_VELOCITY || field == SPH_F_ACCELERATION ||
                          field == SPH_F_PRESSURE_ACCEL || field == SPH_F_PREDICTED_VEL || field == SPH_F_PREDICTED_POS ||
                          field == SPH_F_CG_X || field == SPH_F_ORIG_POSITION || field == SPH_F_IISPH_DII || field == SPH_F_IISPH_DIJ_PJ ||
-                         field == SPH_F_PBF_OLD_POSITION;
+                         field == SPH_F_PBF_OLD_POSITION || field == SPH_F_RIGID_CONTACT_DN;
     if (is_vec3) {
         const float4 *src = vec_field(h, field);
         if (!src) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);
@@ -990,7 +1094,8 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
         for (size_t i = 0; i < n; ++i) { const float v[3] = {tmp[i].x, tmp[i].y, tmp[i].z}; d[3 * i] = v[ix0]; d[3 * i + 1] = v[ix1]; d[3 * i + 2] = v[ix2]; }
         return SPH_OK;
     }
-    if (field == SPH_F_REST_VOLUME || field == SPH_F_MASS || field == SPH_F_IISPH_AII || field == SPH_F_IISPH_SUM_I) {
+    if (field == SPH_F_REST_VOLUME || field == SPH_F_MASS || field == SPH_F_IISPH_AII || field == SPH_F_IISPH_SUM_I ||
+        field == SPH_F_RIGID_CONTACT_COUNT) {
         if (bytes != n * 4) return fail(h, SPH_ERR_INVALID, "download: size mismatch");
         const float4 *src = vec_field(h, field);
         if (!src) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);

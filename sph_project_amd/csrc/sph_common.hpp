@@ -178,6 +178,14 @@ struct NextHash { int on; int *cellid, *rank, *cell_count, *tile_sum; RunList rl
 // exchange tags of this sort, dyn = this step's counts (the echo part of a message starts behind its n_send records)
 struct HaloFieldSend { int on; float4 *out[2]; const int *xidx; const SlabDyn *dyn; };
 
+// Rigid contact pass (sph_contact.hpp): contact distance D (the pitch bodies and box are sampled at), the domain planes of a scene
+// without a domain box (library frame), and the table's shape: key = (A * SPH_CT_PARTNERS + B) * SPH_CT_BINS + bin, SPH_CT_VALUES words
+#define SPH_CT_PARTNERS 26
+#define SPH_CT_BINS 6
+#define SPH_CT_VALUES 8
+#define SPH_CT_KEYS (SPH_NOBJ * SPH_CT_PARTNERS * SPH_CT_BINS)
+struct ContactArgs { float D; int walls; float lo[3], hi[3]; };
+
 template <class T> struct DBuf {
     T *b[2] = {nullptr, nullptr};
     int c = 0;
@@ -246,6 +254,12 @@ struct State {
     // buffer of the Jacobi fix_position (swapped with posv.cur() behind every pass), recentred walks per statistics bank
     float4 *pbf_old, *pbf_pos; float *pbf_lambda; unsigned long long *pbf_recentred;
     int poly6;           // the shared passes (NonPressurePass, RigidVolumePass) use PBF.py's poly6 / spiky kernels
+    // rigid contact (sph_set_rigid_contact; allocated when first enabled): the per-key table (64-bit fixed point, sph_contact.hpp),
+    // the per-particle (sum of depth * n, contacts) of the targets, the accepted contacts of the last pass
+    int contact_on;
+    ContactArgs contact;
+    unsigned long long *contact_table, *contact_pairs;
+    float4 *contact_part;
     // CG (implicit viscosity)
     float4 *cg_p, *cg_Ap, *cg_x, *cg_b, *cg_r, *cg_v0;
     float4 *cg_p2;       // second search-direction buffer (fused p update: the A p pass reads the old one and writes the new one)
@@ -371,6 +385,8 @@ struct Launch {
     void (*pbf_density_lambda)(State &);        // compute_density + compute_lambda, one walk (PBF.py:64-65)
     void (*pbf_fix_position)(State &);          // fix_position, Jacobi (PBF.py:66, :104)
     void (*pbf_finish)(State &);                // boundary + recompute_fluid_velocity (PBF.py:156-158)
+    // rigid contact: one walk over the dynamic rigid particles, per-key table + per-particle sums (sph_contact.hpp)
+    void (*rigid_contact)(State &);
     // z-slab sharding
     void (*halo_classify_pack)(State &, int n);
     void (*halo_unpack_append)(State &, int side, int count, int offset);

@@ -130,6 +130,42 @@ def pbf_scene(domain_end=(2.0, 1.6, 1.0), start=(0.1, 0.1, 0.1), end=(0.6, 1.0, 
     }
 
 
+def coupling_scene(method="dfsph", models_dir=None, fluid_end=(2.3, 1.4, 2.38)):
+    """The reference's rigid-fluid coupling showcase data/scenes/final_scene1.json: its box, fluid block, dt and the placements of its
+    nine dynamic bodies, with tests/golden/models/cube.obj in place of the dragon and sphere.obj in place of the rubber ducks (those
+    meshes are not in this tree).  fluid_end shrinks the block for tests."""
+    import os
+    models = models_dir or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "models")
+    body = lambda oid, mesh, t, axis, angle, density, v: {
+        "objectId": oid, "geometryFile": os.path.join(models, mesh), "translation": list(t), "rotationAxis": list(axis),
+        "rotationAngle": angle, "scale": [0.6, 0.6, 0.6], "velocity": list(v), "density": density, "color": [255, 255, 255],
+        "isDynamic": True, "entryTime": -1.0}
+    down = (0.0, -0.5, 0.0)
+    return {
+        "Configuration": {
+            "domainStart": [0.0, 0.0, 0.0], "domainEnd": [2.5, 7.0, 2.5], "addDomainBox": True, "particleRadius": 0.01,
+            "fps": 60.0, "totalTime": 10.0, "numberOfStepsPerRenderUpdate": 1, "density0": 1000, "gravitation": [0.0, -9.81, 0.0],
+            "simulationMethod": method, "viscosityMethod": "standard", "timeStepSize": 0.0007, "viscosity": 13.0, "viscosity_b": 0.3,
+            "boundaryHandlingMethod": 0, "exportFrame": True, "exportPly": False, "exportObj": False,
+        },
+        "RigidBodies": [
+            body(1, "cube.obj", (1.5, 3.4, 1.5), (0, 0, 1), 45, 900.0, (0.0, 0.0, 0.0)),
+            body(2, "sphere.obj", (0.3, 2.4, 1.25), (0, 1, 0), 0, 500.0, down),
+            body(3, "sphere.obj", (1.1, 2.8, 0.3), (0, 1, 0), 0, 500.0, down),
+            body(4, "sphere.obj", (2.2, 2.7, 1.15), (0, 1, 0), 0, 500.0, down),
+            body(5, "sphere.obj", (2.2, 2.2, 2.2), (0, 1, 0), 0, 500.0, down),
+            body(6, "sphere.obj", (0.8, 2.3, 0.7), (0, 1, 0), 0, 300.0, down),
+            body(7, "sphere.obj", (2.25, 2.6, 1.7), (0, 1, 0), 180, 300.0, down),
+            body(8, "sphere.obj", (2.1, 2.2, 1.2), (0, 1, 0), 180, 300.0, down),
+            body(9, "sphere.obj", (1.4, 2.0, 1.4), (0, 1, 0), 0, 300.0, down),
+        ],
+        "FluidBlocks": [{
+            "objectId": 0, "start": [0.2, 0.09, 0.11], "end": list(fluid_end), "translation": [0.0, 0.0, 0.0],
+            "scale": [1, 1, 1], "velocity": [0.0, -0.5, 0.0], "density": 1000.0, "color": [50, 100, 200], "entryTime": -1.0,
+        }],
+    }
+
+
 def scene_particles(cfg_dict):
     """Host lattice of every object present at prepare(), in the reference's insertion order
     (domain box first: base_container.py:192, then FluidBlocks: :215).  Blocks with entryTime > 0 are listed with

@@ -71,6 +71,8 @@ def main(argv=None):
     parser.add_argument("--scene_file", default="", help="scene file")
     parser.add_argument("--max_steps", type=int, default=None, help="stop early (not in the reference)")
     parser.add_argument("--output_dir", default=None, help="default: {scene_name}_output in the cwd (reference behaviour)")
+    parser.add_argument("--rigid_backend", default=None, choices=["native", "contact", "pybullet"],
+                        help="rigid-body backend (default: SPH_RIGID_BACKEND, else native); 'contact' adds body-body contact")
     args = parser.parse_args(argv)
     scene_path = args.scene_file
     config = SimConfig(scene_file_path=scene_path)
@@ -98,7 +100,7 @@ def main(argv=None):
              "pbf": (PBFContainer, PBFSolver)}
     if method not in table:
         raise NotImplementedError(f"Simulation method {method} not implemented")
-    container = table[method][0](config, GGUI=False)
+    container = table[method][0](config, GGUI=False, rigid_backend=args.rigid_backend)
     solver = table[method][1](container)
     print(f"Simulation method: {method}")
     solver.prepare()
