@@ -349,6 +349,69 @@ int sph_points_in_mesh(const double *vertices, int n_vertices, const int32_t *fa
 int sph_write_ply_ascii(const char *path, const float *xyz, int64_t n);
 /* str(np.float32(v)) -- the number format of that file -- into out (>= 48 bytes, no terminator); returns the length */
 int sph_format_f32(float v, char *out);
+/* the OBJ of one reconstructed surface (what splashsurf's `-o particle_object_{id}.obj` of surface_reconstruction.py:8 wrote): "v x y z"
+   per vertex, "vn x y z" per normal (normals_or_NULL), then per triangle "f a//a b//b c//c" with 1-based indices ("f a b c" without
+   normals); every number in sph_format_f32's format.  vertices / normals: f32[nv][3]; triangles: i32[nt][3] (0-based).
+   SPH_ERR_UNSUPPORTED: the file could not be written. */
+int sph_write_obj_ascii(const char *path, const float *vertices, int64_t nv, const float *normals_or_NULL, const int32_t *triangles,
+                        int64_t nt);
+
+/* --- surface reconstruction: fluid particles -> triangle mesh --------------- */
+/* replaces `splashsurf reconstruct {ply} -o {obj} -r={radius} -l={smoothing_length} -c=0.5 -t=0.6 ... --normals=on` of
+   surface_reconstruction.py:8 (run per frame and fluid object by surface_reconstruction.py:20-24).  Not splashsurf's algorithm: a
+   Shepard colour field and marching cubes, defined here and in DESIGN.md 14 (no mesh cleanup, no smoothing):
+     h = 2 smoothing_length radius (support of the project's cubic spline), V_j = 1 / sum_k W(x_j - x_k) over the input set,
+     phi(x) = sum_j V_j W(x - x_j), surface phi = iso, inside phi > iso; grid points at integer multiples of e = cube_size radius from
+     the origin; bricks of B^3 points, B = ceil(h / e), evaluated where a particle lies in the 3x3x3 coarse cells around them (phi = 0
+     elsewhere); marching cubes with ambiguous faces resolved from their corners alone; a vertex per crossed grid edge (linear
+     interpolation), shared by index; triangles counter-clockwise seen from outside; normals -grad phi / |grad phi| at the vertices.
+   The mesh is a function of the particle SET (not of its order), bit for bit; vertices in (brick, point, axis) order, triangles in
+   (brick, cube, case table) order.  One HIP stream per object; one host thread per object. */
+typedef struct {
+    double radius;           /* particle radius r (--radius; the scene's particleRadius) */
+    double smoothing_length; /* -l, in multiples of r (3.5) */
+    double cube_size;        /* -c, in multiples of r (0.5) */
+    double iso;              /* -t, surface threshold (0.6) */
+    int32_t normals;         /* --normals=on (1) */
+    int32_t fast_math;       /* 0: IEEE div / sqrt, no FMA contraction; 1: the fast build */
+    int32_t device;          /* HIP device ordinal, -1: current */
+    int32_t reserved;        /* 0 */
+    int64_t memory_cap_bytes;/* device bytes the object may hold at once (0: no cap); a frame that needs more fails with SPH_ERR_CAPACITY
+                                before it allocates */
+} SphSurfaceParams;
+
+typedef struct {
+    int64_t particles;        /* input particles of the last reconstruction */
+    int64_t active_bricks;
+    int64_t points_evaluated; /* active_bricks * B^3 */
+    int64_t pair_tests;       /* (grid point, particle) candidates of the field pass: points x particles of their 27 coarse cells */
+    int64_t vertices, triangles;
+    int64_t bytes_allocated;  /* device bytes held by the object */
+    int32_t B;                /* grid points per brick edge */
+    int32_t reserved;
+    double ms_bin;            /* HIP events: input, bounds, bin + key order + V_j */
+    double ms_bricks;         /* active bricks */
+    double ms_field;          /* phi (the hot pass) */
+    double ms_mesh;           /* classify, count, scan, emit */
+    double ms_normals;
+    double ms_total;          /* first event to last (host waits for the three counts included) */
+} SphSurfaceStats;
+
+typedef struct SphSurface SphSurface;
+int sph_surface_create(const SphSurfaceParams *params, SphSurface **out);
+void sph_surface_destroy(SphSurface *s);
+const char *sph_surface_last_error(SphSurface *s);
+/* host positions f32[n][3] (e.g. one frame's particle_object_{id}.ply, read by splashsurf from disk in the reference); synchronous */
+int sph_surface_reconstruct(SphSurface *s, const float *xyz, int64_t n);
+/* the particles of object_id (SPH_F_OBJECT_ID, ghosts excluded) of a live handle, compacted on the device with no host round trip
+   (run_simulation.py:139-144 writes them to a PLY that surface_reconstruction.py then reads); the handle must be on the same device.
+   SPH_ERR_UNSUPPORTED on a sharded handle (sph_comm_set_slab); synchronous. */
+int sph_surface_reconstruct_object(SphSurface *s, SphHandle *h, int object_id);
+int sph_surface_mesh_size(SphSurface *s, int64_t *n_vertices, int64_t *n_triangles);
+/* vertices f32[nv][3], normals f32[nv][3] (NULL: skipped; SPH_ERR_INVALID when the object was created without normals),
+   triangles i32[nt][3] */
+int sph_surface_download(SphSurface *s, float *vertices, float *normals_or_NULL, int32_t *triangles);
+int sph_surface_stats(SphSurface *s, SphSurfaceStats *out);
 
 #ifdef __cplusplus
 }

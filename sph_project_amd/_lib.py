@@ -83,6 +83,23 @@ class SphStats(C.Structure):
     ]
 
 
+class SphSurfaceParams(C.Structure):
+    _fields_ = [
+        ("radius", C.c_double), ("smoothing_length", C.c_double), ("cube_size", C.c_double), ("iso", C.c_double),
+        ("normals", C.c_int32), ("fast_math", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32),
+        ("memory_cap_bytes", C.c_int64),
+    ]
+
+
+class SphSurfaceStats(C.Structure):
+    _fields_ = [
+        ("particles", C.c_int64), ("active_bricks", C.c_int64), ("points_evaluated", C.c_int64), ("pair_tests", C.c_int64),
+        ("vertices", C.c_int64), ("triangles", C.c_int64), ("bytes_allocated", C.c_int64), ("B", C.c_int32), ("reserved", C.c_int32),
+        ("ms_bin", C.c_double), ("ms_bricks", C.c_double), ("ms_field", C.c_double), ("ms_mesh", C.c_double),
+        ("ms_normals", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class SphError(RuntimeError):
     pass
 
@@ -133,6 +150,15 @@ _SIGNATURES = [
     ("sph_points_in_mesh", C.c_int, [_VP, C.c_int, _VP, C.c_int] + [_VP, C.c_int] * 3 + [_VP]),
     ("sph_write_ply_ascii", C.c_int, [C.c_char_p, _VP, C.c_int64]),
     ("sph_format_f32", C.c_int, [C.c_float, C.c_char_p]),
+    ("sph_write_obj_ascii", C.c_int, [C.c_char_p, _VP, C.c_int64, _VP, _VP, C.c_int64]),
+    ("sph_surface_create", C.c_int, [C.POINTER(SphSurfaceParams), C.POINTER(_VP)]),
+    ("sph_surface_destroy", None, [_VP]),
+    ("sph_surface_last_error", C.c_char_p, [_VP]),
+    ("sph_surface_reconstruct", C.c_int, [_VP, _VP, C.c_int64]),
+    ("sph_surface_reconstruct_object", C.c_int, [_VP, _VP, C.c_int]),
+    ("sph_surface_mesh_size", C.c_int, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("sph_surface_download", C.c_int, [_VP, _VP, _VP, _VP]),
+    ("sph_surface_stats", C.c_int, [_VP, C.POINTER(SphSurfaceStats)]),
     ("sph_comm_allreduce", C.c_int, [_VP, C.POINTER(C.c_double), C.c_int, C.c_int]),
     ("sph_comm_barrier", C.c_int, [_VP]),
     ("sph_comm_selftest", C.c_int, [_VP, C.c_int]),

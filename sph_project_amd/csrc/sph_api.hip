@@ -1211,6 +1211,12 @@ extern "C" int sph_write_ply_ascii(const char *path, const float *xyz, int64_t n
     const int rc = sphexp::write_ply_ascii(path, xyz, n);
     return rc == 0 ? SPH_OK : (rc == -1 ? SPH_ERR_INVALID : SPH_ERR_UNSUPPORTED);
 }
+// the OBJ of a reconstructed surface (splashsurf's output in surface_reconstruction.py:8)
+extern "C" int sph_write_obj_ascii(const char *path, const float *vertices, int64_t nv, const float *normals_or_NULL, const int32_t *triangles,
+                                   int64_t nt) {
+    const int rc = sphexp::write_obj_ascii(path, vertices, nv, normals_or_NULL, triangles, nt);
+    return rc == 0 ? SPH_OK : (rc == -1 ? SPH_ERR_INVALID : SPH_ERR_UNSUPPORTED);
+}
 // str(np.float32(v)) into out (>= 48 bytes), returns its length: the number format of the PLY body, exported for the tests
 extern "C" int sph_format_f32(float v, char *out) { return out ? sphexp::format_f32(v, out) : SPH_ERR_INVALID; }
 
@@ -1238,3 +1244,5 @@ extern "C" int sph_points_in_mesh(const double *vertices, int n_vertices, const 
     for (int k = 0; k < 3 * n_faces; ++k) if (faces[k] < 0 || faces[k] >= n_vertices) return SPH_ERR_INVALID;
     return sphvox::contains_lattice(vertices, n_vertices, faces, n_faces, xs, nx, ys, ny, zs, nz, inside) == 0 ? SPH_OK : SPH_ERR_INVALID;
 }
+
+#include "sph_surface_api.hpp"

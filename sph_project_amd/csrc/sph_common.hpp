@@ -186,6 +186,33 @@ struct HaloFieldSend { int on; float4 *out[2]; const int *xidx; const SlabDyn *d
 #define SPH_CT_KEYS (SPH_NOBJ * SPH_CT_PARTNERS * SPH_CT_BINS)
 struct ContactArgs { float D; int walls; float lo[3], hi[3]; };
 
+// Surface reconstruction (sph_surface.hpp): the constants and device buffers of one SphSurface.  Coarse cells (= bricks of
+// B^3 grid points) are counted from the absolute coarse coordinate cmin[] on a grid of cn[] cells that keeps one empty cell around the
+// particles; coarse linear index (x * cn[1] + y) * cn[2] + z.
+struct SurfDev {
+    float h, h2, kW, kG, e, be, iso;   // support, support^2, 8 / (pi h^3), 6 kW / h, cube edge, coarse edge B e, iso value
+    int B, P;                          // points per brick edge, B^3
+    int cmin[3], cn[3], G;             // coarse grid frame
+    int n, nb;                         // particles, active bricks
+    float4 *xin;                       // [n] input positions (w unused)
+    float4 *xtmp, *xs;                 // [n] binned in arrival order / in key order with w = V_j
+    int *pcell, *pslot;                // [n] coarse cell and arrival slot of xin[i]
+    int *cell_start;                   // [G + 1] particle counts -> their exclusive scan
+    int *flag;                         // [G + 1] active-brick flags -> their exclusive scan (flag[G] = nb)
+    int *brick_id;                     // [G] brick index of a coarse cell, -1 when inactive
+    int *brick_cell;                   // [nb] coarse linear index of each brick (ascending)
+    float *phi;                        // [nb * P] the field at every point of every active brick
+    unsigned *edge;                    // [nb * P] (vertex offset inside the brick) << 11 | cube case << 3 | crossing mask of the point's 3 edges
+    int *vbase, *tbase;                // [nb + 1] per-brick vertex / triangle counts -> their exclusive scans
+    float *vert, *nrm;                 // [nv * 3]
+    int *tri;                          // [nt * 3]
+    int *bounds;                       // [7] min / max coarse coordinates of the particles, non-finite flag
+    int *counter;                      // [1] particles compacted from a handle
+    unsigned long long *pairs;         // [1] candidate pair tests of the field pass
+    int *scan_tmp;                     // tile sums of surf_scan
+    hipStream_t stream;
+};
+
 template <class T> struct DBuf {
     T *b[2] = {nullptr, nullptr};
     int c = 0;
@@ -398,6 +425,15 @@ struct Launch {
     void (*halo_pack_vel)(State &, int side, int n_send, int n_recv, const float4 *arr);   // xyz of a float4 array
     void (*halo_unpack_vel)(State &, int side, int n_recv, int n_send, float4 *arr);
     void (*count_ghosts)(State &, int *out);
+    // surface reconstruction (sph_surface.hpp)
+    void (*surf_compact)(SurfDev &, const float4 *posv, const int *meta, int n, int object_id);   // one object's particles -> xin, counter
+    void (*surf_bounds)(SurfDev &);             // coarse bounds of xin[0, n)
+    void (*surf_bin)(SurfDev &);                // bin by coarse cell, order each cell by key, V_j (-> xs)
+    void (*surf_flags)(SurfDev &);              // active bricks: flags and their scan (flag[G] = nb)
+    void (*surf_field)(SurfDev &);              // brick list + phi at every point of every active brick (the hot pass)
+    void (*surf_count)(SurfDev &);              // classify cubes and edges, per-brick vertex / triangle counts and their scans
+    void (*surf_emit)(SurfDev &);               // vertices and triangles
+    void (*surf_normals)(SurfDev &, int nv);    // -grad phi / |grad phi| at every vertex
     void (*layer_hist)(State &, int *hist);      // owned particles per global cell layer
     void (*loop_criterion)(State &, int slot);   // stop test on an all-reduced residual (sharded solver loops)
     // push transport: the step message is written by halo_classify_pack itself; then

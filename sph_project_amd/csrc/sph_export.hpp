@@ -66,4 +66,42 @@ static int write_ply_ascii(const char *path, const float *xyz, int64_t n) {
     return rc;
 }
 
+// one reconstructed surface as ASCII OBJ: "v x y z" per vertex, "vn x y z" per normal, "f a//a b//b c//c" (1-based; "f a b c" without
+// normals) per triangle, numbers as format_f32
+static int write_obj_ascii(const char *path, const float *v, int64_t nv, const float *nrm, const int32_t *tri, int64_t nt) {
+    if (!path || nv < 0 || nt < 0 || (nv > 0 && !v) || (nt > 0 && !tri)) return -1;
+    for (int64_t k = 0; k < 3 * nt; ++k) if (tri[k] < 0 || tri[k] >= nv) return -1;
+    FILE *f = fopen(path, "wb");
+    if (!f) return -2;
+    int rc = 0;
+    std::vector<char> buf(1 << 20);
+    size_t used = 0;
+    auto flush = [&](size_t room) {
+        if (used + room > buf.size()) { if (fwrite(buf.data(), 1, used, f) != used) rc = -3; used = 0; }
+    };
+    for (int pass = 0; pass < 2; ++pass) {
+        const float *a = pass == 0 ? v : nrm;
+        if (!a) continue;
+        for (int64_t i = 0; i < nv && rc == 0; ++i) {
+            flush(3 * 48 + 8);
+            buf[used++] = 'v';
+            if (pass == 1) buf[used++] = 'n';
+            for (int c = 0; c < 3; ++c) { buf[used++] = ' '; used += (size_t)format_f32(a[3 * i + c], buf.data() + used); }
+            buf[used++] = '\n';
+        }
+    }
+    for (int64_t i = 0; i < nt && rc == 0; ++i) {
+        flush(3 * 48 + 8);
+        buf[used++] = 'f';
+        for (int c = 0; c < 3; ++c) {
+            const long long k = (long long)tri[3 * i + c] + 1;
+            used += (size_t)(nrm ? snprintf(buf.data() + used, 48, " %lld//%lld", k, k) : snprintf(buf.data() + used, 48, " %lld", k));
+        }
+        buf[used++] = '\n';
+    }
+    if (rc == 0 && used && fwrite(buf.data(), 1, used, f) != used) rc = -3;
+    if (fclose(f) != 0 && rc == 0) rc = -3;
+    return rc;
+}
+
 }  // namespace sphexp

@@ -1,0 +1,287 @@
+// sph_surface_api.hpp -- the SphSurface object of include/sph_hip.h: its buffers under the memory cap, the pass sequence with its three
+// host reads (coarse bounds, active bricks, vertex / triangle totals) and the stage events.  Host code, included at the end of
+// sph_api.hip; the kernels are in sph_surface.hpp, the method in DESIGN.md 14.
+#pragma once
+#include <climits>
+
+enum SurfBufId { SB_XIN, SB_XTMP, SB_XS, SB_PCELL, SB_PSLOT, SB_CELL_START, SB_FLAG, SB_BRICK_ID, SB_BRICK_CELL, SB_PHI, SB_EDGE, SB_VBASE,
+                 SB_TBASE, SB_VERT, SB_NRM, SB_TRI, SB_SMALL, SB_SCAN, SB_COUNT_ };
+
+struct SphSurface {
+    SphSurfaceParams prm;
+    const Launch *L = nullptr;
+    int device = 0;
+    std::string err;
+    SurfDev d{};
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[6] = {};
+    void *buf[SB_COUNT_] = {};
+    size_t bytes[SB_COUNT_] = {};
+    bool live[SB_COUNT_] = {};   // holds data of the reconstruction running now
+    int64_t nv = 0, nt = 0;
+    bool have_mesh = false;
+    SphSurfaceStats stats{};
+};
+
+static int surf_fail(SphSurface *s, int code, const char *fmt, ...) {
+    char b[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(b, sizeof(b), fmt, ap);
+    va_end(ap);
+    if (s) s->err = b; else g_create_error = b;
+    return code;
+}
+#define SURFCHK(s, call)                                                                                                   \
+    do {                                                                                                                    \
+        hipError_t e_ = (call);                                                                                             \
+        if (e_ != hipSuccess) return surf_fail((s), SPH_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+static size_t surf_total(const SphSurface *s) {
+    size_t t = 0;
+    for (int k = 0; k < SB_COUNT_; ++k) t += s->bytes[k];
+    return t;
+}
+// buffer k with room for `need` bytes.  Past the cap, the buffers that hold nothing of this reconstruction go first; if it still does not
+// fit: SPH_ERR_CAPACITY, nothing allocated.
+static int surf_ensure(SphSurface *s, int k, size_t need, const char *what) {
+    if (need == 0) need = 16;
+    s->live[k] = true;
+    if (s->bytes[k] >= need) return SPH_OK;
+    const size_t cap = (size_t)s->prm.memory_cap_bytes;
+    if (cap && surf_total(s) - s->bytes[k] + need > cap) {
+        for (int j = 0; j < SB_COUNT_; ++j)
+            if (!s->live[j] && s->buf[j]) { hipFree(s->buf[j]); s->buf[j] = nullptr; s->bytes[j] = 0; }
+        if (surf_total(s) - s->bytes[k] + need > cap)
+            return surf_fail(s, SPH_ERR_CAPACITY, "surface: %s needs %zu bytes, %zu held, cap %zu", what, need, surf_total(s) - s->bytes[k], cap);
+    }
+    if (s->buf[k]) { hipFree(s->buf[k]); s->buf[k] = nullptr; s->bytes[k] = 0; }
+    SURFCHK(s, hipMalloc(&s->buf[k], need));
+    s->bytes[k] = need;
+    return SPH_OK;
+}
+#define SURF_ENSURE(s, k, need, what) do { int rc_ = surf_ensure((s), (k), (need), (what)); if (rc_) return rc_; } while (0)
+
+extern "C" int sph_surface_create(const SphSurfaceParams *params, SphSurface **out) {
+    if (!params || !out) return surf_fail(nullptr, SPH_ERR_INVALID, "sph_surface_create: null argument");
+    *out = nullptr;
+    const SphSurfaceParams p = *params;
+    if (!(p.radius > 0.0) || !(p.smoothing_length > 0.0) || !(p.cube_size > 0.0) || !std::isfinite(p.radius) ||
+        !std::isfinite(p.smoothing_length) || !std::isfinite(p.cube_size) || !std::isfinite(p.iso) || !(p.iso > 0.0) || p.memory_cap_bytes < 0)
+        return surf_fail(nullptr, SPH_ERR_INVALID, "sph_surface_create: radius, smoothing_length, cube_size and iso must be positive and finite, the cap >= 0");
+    const double h = 2.0 * p.smoothing_length * p.radius, e = p.cube_size * p.radius;
+    const double Bd = ceil(h / e - 1e-9);
+    // the edge word keeps a vertex offset of 21 bits (3 B^3 < 2^21): B <= 64 is far beyond any useful grid
+    if (!(Bd >= 1.0 && Bd <= 64.0))
+        return surf_fail(nullptr, SPH_ERR_INVALID, "sph_surface_create: %.0f grid points per brick edge (smoothing_length / cube_size * 2); at most 64", Bd);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return surf_fail(nullptr, SPH_ERR_NO_DEVICE, "sph_surface_create: no HIP device visible (libsph_hip has no CPU path)");
+    int dev = p.device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (dev >= ndev) return surf_fail(nullptr, SPH_ERR_NO_DEVICE, "sph_surface_create: device %d not present", dev);
+    hipDeviceProp_t prop;
+    if (hipSetDevice(dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
+        return surf_fail(nullptr, SPH_ERR_HIP, "sph_surface_create: device %d unusable", dev);
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return surf_fail(nullptr, SPH_ERR_NO_DEVICE, "sph_surface_create: device %d is %s, this library is built for gfx950 only", dev, prop.gcnArchName);
+    SphSurface *s = new SphSurface();
+    s->prm = p;
+    s->device = dev;
+    s->L = p.fast_math ? sph_launch_fast() : sph_launch_strict();
+    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; return surf_fail(nullptr, SPH_ERR_HIP, "sph_surface_create: stream"); }
+    for (auto &e_ : s->ev)
+        if (hipEventCreate(&e_) != hipSuccess) { sph_surface_destroy(s); return surf_fail(nullptr, SPH_ERR_HIP, "sph_surface_create: event"); }
+    SurfDev &d = s->d;
+    d.h = (float)h;
+    d.h2 = (float)(h * h);
+    d.kW = (float)(8.0 / (M_PI * h * h * h));
+    d.kG = (float)(6.0 * 8.0 / (M_PI * h * h * h * h));
+    d.e = (float)e;
+    d.B = (int)Bd;
+    d.P = d.B * d.B * d.B;
+    d.be = (float)(d.B * e);
+    d.iso = (float)p.iso;
+    d.stream = s->stream;
+    s->stats.B = d.B;
+    *out = s;
+    return SPH_OK;
+}
+
+extern "C" void sph_surface_destroy(SphSurface *s) {
+    if (!s) return;
+    hipSetDevice(s->device);
+    if (s->stream) hipStreamSynchronize(s->stream);
+    for (int k = 0; k < SB_COUNT_; ++k) if (s->buf[k]) hipFree(s->buf[k]);
+    for (auto e_ : s->ev) if (e_) hipEventDestroy(e_);
+    if (s->stream) hipStreamDestroy(s->stream);
+    delete s;
+}
+
+extern "C" const char *sph_surface_last_error(SphSurface *s) { return s ? s->err.c_str() : g_create_error.c_str(); }
+
+static float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0.0f; hipEventElapsedTime(&ms, a, b); return ms; }
+
+// the passes after the input is in xin[0, n) and ev[0] has been recorded before it was put there
+static int surf_run(SphSurface *s, int n) {
+    SurfDev &d = s->d;
+    hipStream_t st = s->stream;
+    d.n = n;
+    d.nb = 0;
+    d.cmin[0] = d.cmin[1] = d.cmin[2] = 0;
+    if (n == 0) {   // no particle: the empty mesh
+        SURFCHK(s, hipStreamSynchronize(st));
+        s->have_mesh = true;
+        s->stats.bytes_allocated = (int64_t)surf_total(s);
+        return SPH_OK;
+    }
+    SURF_ENSURE(s, SB_SMALL, 64, "counters");
+    d.bounds = (int *)s->buf[SB_SMALL];
+    d.counter = d.bounds + 8;
+    d.pairs = (unsigned long long *)(d.bounds + 10);
+    const int init[7] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0};
+    SURFCHK(s, hipMemcpyAsync(d.bounds, init, sizeof(init), hipMemcpyHostToDevice, st));
+    s->L->surf_bounds(d);
+    int bnd[7];
+    SURFCHK(s, hipMemcpyAsync(bnd, d.bounds, sizeof(bnd), hipMemcpyDeviceToHost, st));
+    SURFCHK(s, hipStreamSynchronize(st));
+    if (bnd[6]) return surf_fail(s, SPH_ERR_INVALID, "surface: non-finite particle position (or one beyond 1e8 coarse cells)");
+    int64_t G = 1;
+    for (int a = 0; a < 3; ++a) {
+        d.cmin[a] = bnd[a] - 1;                       // one empty coarse cell around the particles
+        d.cn[a] = bnd[3 + a] - bnd[a] + 3;
+        G *= d.cn[a];
+    }
+    if (G > (int64_t)INT_MAX / 2) return surf_fail(s, SPH_ERR_CAPACITY, "surface: coarse grid of %lld cells", (long long)G);
+    d.G = (int)G;
+    SURF_ENSURE(s, SB_XTMP, sizeof(float4) * (size_t)n, "particles");
+    SURF_ENSURE(s, SB_XS, sizeof(float4) * (size_t)n, "particles");
+    SURF_ENSURE(s, SB_PCELL, sizeof(int) * (size_t)n, "particles");
+    SURF_ENSURE(s, SB_PSLOT, sizeof(int) * (size_t)n, "particles");
+    SURF_ENSURE(s, SB_CELL_START, sizeof(int) * ((size_t)G + 1), "coarse grid");
+    SURF_ENSURE(s, SB_FLAG, sizeof(int) * ((size_t)G + 1), "coarse grid");
+    SURF_ENSURE(s, SB_BRICK_ID, sizeof(int) * (size_t)G, "coarse grid");
+    SURF_ENSURE(s, SB_SCAN, sizeof(int) * ((size_t)(G + 1) / 1024 + 2), "scan");
+    d.xtmp = (float4 *)s->buf[SB_XTMP]; d.xs = (float4 *)s->buf[SB_XS];
+    d.pcell = (int *)s->buf[SB_PCELL]; d.pslot = (int *)s->buf[SB_PSLOT];
+    d.cell_start = (int *)s->buf[SB_CELL_START]; d.flag = (int *)s->buf[SB_FLAG]; d.brick_id = (int *)s->buf[SB_BRICK_ID];
+    d.scan_tmp = (int *)s->buf[SB_SCAN];
+    s->L->surf_bin(d);   // (leaves xs = the key-ordered particles with V)
+    SURFCHK(s, hipEventRecord(s->ev[1], st));
+    s->L->surf_flags(d);
+    SURFCHK(s, hipEventRecord(s->ev[2], st));
+    int nb = 0;
+    SURFCHK(s, hipMemcpyAsync(&nb, d.flag + G, sizeof(int), hipMemcpyDeviceToHost, st));
+    SURFCHK(s, hipStreamSynchronize(st));
+    d.nb = nb;
+    const size_t points = (size_t)nb * (size_t)d.P;
+    SURF_ENSURE(s, SB_BRICK_CELL, sizeof(int) * (size_t)nb, "bricks");
+    SURF_ENSURE(s, SB_PHI, sizeof(float) * points, "grid values");
+    SURF_ENSURE(s, SB_EDGE, sizeof(unsigned) * points, "grid values");
+    SURF_ENSURE(s, SB_VBASE, sizeof(int) * ((size_t)nb + 1), "bricks");
+    SURF_ENSURE(s, SB_TBASE, sizeof(int) * ((size_t)nb + 1), "bricks");
+    if ((size_t)nb + 1 > (size_t)(G + 1)) return surf_fail(s, SPH_ERR_INVALID, "surface: internal brick count");
+    d.brick_cell = (int *)s->buf[SB_BRICK_CELL]; d.phi = (float *)s->buf[SB_PHI]; d.edge = (unsigned *)s->buf[SB_EDGE];
+    d.vbase = (int *)s->buf[SB_VBASE]; d.tbase = (int *)s->buf[SB_TBASE];
+    s->L->surf_field(d);
+    SURFCHK(s, hipEventRecord(s->ev[3], st));
+    s->L->surf_count(d);
+    int tot[2] = {0, 0};
+    SURFCHK(s, hipMemcpyAsync(&tot[0], d.vbase + nb, sizeof(int), hipMemcpyDeviceToHost, st));
+    SURFCHK(s, hipMemcpyAsync(&tot[1], d.tbase + nb, sizeof(int), hipMemcpyDeviceToHost, st));
+    SURFCHK(s, hipStreamSynchronize(st));
+    if (tot[0] < 0 || tot[1] < 0 || tot[1] > INT_MAX / 3 || tot[0] > INT_MAX / 3)
+        return surf_fail(s, SPH_ERR_CAPACITY, "surface: more than 2^31 / 3 vertices or triangles");
+    SURF_ENSURE(s, SB_VERT, sizeof(float) * 3 * (size_t)tot[0], "vertices");
+    SURF_ENSURE(s, SB_TRI, sizeof(int) * 3 * (size_t)tot[1], "triangles");
+    if (s->prm.normals) SURF_ENSURE(s, SB_NRM, sizeof(float) * 3 * (size_t)tot[0], "normals");
+    d.vert = (float *)s->buf[SB_VERT]; d.tri = (int *)s->buf[SB_TRI]; d.nrm = s->prm.normals ? (float *)s->buf[SB_NRM] : nullptr;
+    s->L->surf_emit(d);
+    SURFCHK(s, hipEventRecord(s->ev[4], st));
+    if (s->prm.normals) s->L->surf_normals(d, tot[0]);
+    SURFCHK(s, hipEventRecord(s->ev[5], st));
+    unsigned long long pairs = 0;
+    SURFCHK(s, hipMemcpyAsync(&pairs, d.pairs, sizeof(pairs), hipMemcpyDeviceToHost, st));
+    SURFCHK(s, hipStreamSynchronize(st));
+    SURFCHK(s, hipGetLastError());
+    s->nv = tot[0];
+    s->nt = tot[1];
+    s->have_mesh = true;
+    SphSurfaceStats &o = s->stats;
+    o.particles = n; o.active_bricks = nb; o.points_evaluated = (int64_t)points; o.pair_tests = (int64_t)pairs;
+    o.vertices = s->nv; o.triangles = s->nt; o.bytes_allocated = (int64_t)surf_total(s); o.B = d.B;
+    o.ms_bin = ev_ms(s->ev[0], s->ev[1]); o.ms_bricks = ev_ms(s->ev[1], s->ev[2]); o.ms_field = ev_ms(s->ev[2], s->ev[3]);
+    o.ms_mesh = ev_ms(s->ev[3], s->ev[4]); o.ms_normals = ev_ms(s->ev[4], s->ev[5]); o.ms_total = ev_ms(s->ev[0], s->ev[5]);
+    return SPH_OK;
+}
+
+static void surf_begin(SphSurface *s) {
+    s->have_mesh = false;
+    s->nv = s->nt = 0;
+    for (bool &l : s->live) l = false;
+    s->stats = SphSurfaceStats{};
+    s->stats.B = s->d.B;
+}
+
+extern "C" int sph_surface_reconstruct(SphSurface *s, const float *xyz, int64_t n) {
+    if (!s) return SPH_ERR_INVALID;
+    if (n < 0 || n > INT_MAX / 2 || (n > 0 && !xyz)) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_reconstruct: bad particle array (n = %lld)", (long long)n);
+    SURFCHK(s, hipSetDevice(s->device));
+    surf_begin(s);
+    std::vector<float4> tmp((size_t)n);
+    for (int64_t i = 0; i < n; ++i) tmp[i] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 0.0f);
+    SURF_ENSURE(s, SB_XIN, sizeof(float4) * (size_t)n, "particles");
+    s->d.xin = (float4 *)s->buf[SB_XIN];
+    SURFCHK(s, hipEventRecord(s->ev[0], s->stream));
+    if (n) SURFCHK(s, hipMemcpyAsync(s->d.xin, tmp.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s->stream));
+    return surf_run(s, (int)n);
+}
+
+extern "C" int sph_surface_reconstruct_object(SphSurface *s, SphHandle *h, int object_id) {
+    if (!s || !h) return SPH_ERR_INVALID;
+    if (h->st.slab_active || h->swap_axis)
+        return surf_fail(s, SPH_ERR_UNSUPPORTED, "sph_surface_reconstruct_object: sharded handle (reconstruct each rank's download instead)");
+    if (h->device != s->device) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_reconstruct_object: handle on device %d, surface on %d", h->device, s->device);
+    if (object_id < 0 || object_id >= SPH_MAX_OBJECTS) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_reconstruct_object: object id %d", object_id);
+    SURFCHK(s, hipSetDevice(s->device));
+    SURFCHK(s, hipStreamSynchronize(h->st.stream));   // the handle's last step has written the positions
+    surf_begin(s);
+    const int n_all = h->n;
+    SURF_ENSURE(s, SB_XIN, sizeof(float4) * (size_t)n_all, "particles");
+    SURF_ENSURE(s, SB_SMALL, 64, "counters");
+    s->d.xin = (float4 *)s->buf[SB_XIN];
+    s->d.counter = (int *)s->buf[SB_SMALL] + 8;
+    SURFCHK(s, hipEventRecord(s->ev[0], s->stream));
+    s->L->surf_compact(s->d, h->st.posv.cur(), h->st.meta.cur(), n_all, object_id);
+    int n = 0;
+    SURFCHK(s, hipMemcpyAsync(&n, s->d.counter, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    SURFCHK(s, hipStreamSynchronize(s->stream));
+    return surf_run(s, n);
+}
+
+extern "C" int sph_surface_mesh_size(SphSurface *s, int64_t *n_vertices, int64_t *n_triangles) {
+    if (!s || !n_vertices || !n_triangles) return SPH_ERR_INVALID;
+    if (!s->have_mesh) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_mesh_size: no reconstruction has succeeded yet");
+    *n_vertices = s->nv;
+    *n_triangles = s->nt;
+    return SPH_OK;
+}
+
+extern "C" int sph_surface_download(SphSurface *s, float *vertices, float *normals_or_NULL, int32_t *triangles) {
+    if (!s) return SPH_ERR_INVALID;
+    if (!s->have_mesh) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_download: no reconstruction has succeeded yet");
+    if ((s->nv && !vertices) || (s->nt && !triangles)) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_download: null output");
+    if (normals_or_NULL && !s->prm.normals) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_download: created without normals");
+    SURFCHK(s, hipSetDevice(s->device));
+    if (s->nv) SURFCHK(s, hipMemcpy(vertices, s->d.vert, sizeof(float) * 3 * (size_t)s->nv, hipMemcpyDeviceToHost));
+    if (s->nv && normals_or_NULL) SURFCHK(s, hipMemcpy(normals_or_NULL, s->d.nrm, sizeof(float) * 3 * (size_t)s->nv, hipMemcpyDeviceToHost));
+    if (s->nt) SURFCHK(s, hipMemcpy(triangles, s->d.tri, sizeof(int) * 3 * (size_t)s->nt, hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
+
+extern "C" int sph_surface_stats(SphSurface *s, SphSurfaceStats *out) {
+    if (!s || !out) return SPH_ERR_INVALID;
+    *out = s->stats;
+    return SPH_OK;
+}

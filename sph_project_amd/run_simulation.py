@@ -73,6 +73,9 @@ def main(argv=None):
     parser.add_argument("--output_dir", default=None, help="default: {scene_name}_output in the cwd (reference behaviour)")
     parser.add_argument("--rigid_backend", default=None, choices=["native", "contact", "pybullet"],
                         help="rigid-body backend (default: SPH_RIGID_BACKEND, else native); 'contact' adds body-body contact")
+    parser.add_argument("--reconstruct", action="store_true",
+                        help="with every PLY frame also write particle_object_{id}.obj: the fluid object's surface, reconstructed on the "
+                             "GPU from the device state (surface_reconstruction.py's defaults; not in the reference)")
     args = parser.parse_args(argv)
     scene_path = args.scene_file
     config = SimConfig(scene_file_path=scene_path)
@@ -105,6 +108,10 @@ def main(argv=None):
     print(f"Simulation method: {method}")
     solver.prepare()
 
+    recon = None
+    if args.reconstruct:
+        from sph_project_amd.surface import SurfaceReconstructor
+        recon = SurfaceReconstructor(container.dx)
     cnt = 0
     limit = total_rounds if args.max_steps is None else min(total_rounds, args.max_steps)
     limit = max(limit, 1)   # the reference's loop steps once before it looks at the round count
@@ -128,6 +135,9 @@ def main(argv=None):
             os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
             for f_body_id in container.object_id_fluid_body:
                 write_ply_ascii(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.ply", container.dump(obj_id=f_body_id)["position"])
+                if recon is not None:   # what surface_reconstruction.py would make of that PLY, without reading it back
+                    recon.from_container(container, f_body_id)
+                    recon.write_obj(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.obj")
                 wrote = True
         if output_obj:   # run_simulation.py:146-150
             os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)

@@ -1,0 +1,102 @@
+"""Surface reconstruction on the GPU: fluid particles -> triangle mesh (C-ABI sph_surface_* in include/sph_hip.h).
+
+Replaces the reference's `splashsurf reconstruct` call (surface_reconstruction.py:8) with the project's own method: a Shepard colour
+field of the project's cubic spline and marching cubes, evaluated by the HIP passes of csrc/sph_surface.hpp.  No CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib as L
+
+SPH_ERR_CAPACITY = -2
+
+
+class SurfaceError(L.SphError):
+    def __init__(self, msg, code):
+        super().__init__(msg)
+        self.code = code
+
+
+class SurfaceReconstructor:
+    """One reconstruction object (device buffers reused from frame to frame).  Defaults: the reference's splashsurf command
+    (`-l 3.5 -c=0.5 -t=0.6 --normals=on`)."""
+
+    def __init__(self, radius, smoothing_length=3.5, cube_size=0.5, iso=0.6, normals=True, memory_cap_bytes=0, fast_math=False,
+                 device=-1):
+        self.lib = L.load()
+        self.normals = bool(normals)
+        p = L.SphSurfaceParams(radius=float(radius), smoothing_length=float(smoothing_length), cube_size=float(cube_size), iso=float(iso),
+                               normals=int(self.normals), fast_math=int(bool(fast_math)), device=int(device), reserved=0,
+                               memory_cap_bytes=int(memory_cap_bytes))
+        h = C.c_void_p()
+        rc = self.lib.sph_surface_create(C.byref(p), C.byref(h))
+        if rc != 0:
+            msg = self.lib.sph_surface_last_error(None)
+            raise SurfaceError(f"sph_surface_create failed ({rc}): {msg.decode() if msg else ''}", rc)
+        self.h = h
+        self.mesh = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.sph_surface_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            msg = self.lib.sph_surface_last_error(self.h)
+            raise SurfaceError(f"{what} failed ({rc}): {msg.decode() if msg else ''}", rc)
+
+    def _download(self):
+        nv, nt = C.c_int64(), C.c_int64()
+        self._chk(self.lib.sph_surface_mesh_size(self.h, C.byref(nv), C.byref(nt)), "sph_surface_mesh_size")
+        v = np.empty((nv.value, 3), np.float32)
+        n = np.empty((nv.value, 3), np.float32) if self.normals else None
+        t = np.empty((nt.value, 3), np.int32)
+        self._chk(self.lib.sph_surface_download(self.h, v.ctypes.data, None if n is None else n.ctypes.data, t.ctypes.data),
+                  "sph_surface_download")
+        self.mesh = (v, t, n)
+        return self.mesh
+
+    def from_points(self, xyz):
+        """(vertices f32[nv,3], triangles i32[nt,3], normals f32[nv,3] or None) of the particles xyz f32[n,3]."""
+        x = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        self._chk(self.lib.sph_surface_reconstruct(self.h, x.ctypes.data, x.shape[0]), "sph_surface_reconstruct")
+        return self._download()
+
+    def from_container(self, container, obj_id):
+        """The same for object obj_id of a live container (or an Engine), compacted on the device."""
+        engine = getattr(container, "engine", container)
+        self._chk(self.lib.sph_surface_reconstruct_object(self.h, engine.h, int(obj_id)), "sph_surface_reconstruct_object")
+        return self._download()
+
+    def stats(self):
+        st = L.SphSurfaceStats()
+        self._chk(self.lib.sph_surface_stats(self.h, C.byref(st)), "sph_surface_stats")
+        return {k: getattr(st, k) for k, _ in L.SphSurfaceStats._fields_ if k != "reserved"}
+
+    def write_obj(self, path):
+        """The last mesh as ASCII OBJ (write_obj below)."""
+        if self.mesh is None:
+            raise SurfaceError("write_obj: no mesh reconstructed yet", -1)
+        write_obj(path, *self.mesh)
+
+
+def write_obj(path, vertices, triangles, normals=None):
+    """v / vn / `f a//a b//b c//c` (1-based) in the PLY writer's number format, by the native writer (sph_write_obj_ascii)."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+    n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    rc = L.load().sph_write_obj_ascii(os.fsencode(path), v.ctypes.data, v.shape[0], None if n is None else n.ctypes.data,
+                                      t.ctypes.data, t.shape[0])
+    if rc != 0:
+        raise OSError(f"sph_write_obj_ascii({path!r}) failed ({rc})")

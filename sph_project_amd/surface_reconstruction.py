@@ -1,0 +1,59 @@
+#!/usr/bin/env python
+"""Drop-in for the reference's surface_reconstruction.py: every frame directory under --input_dir, every particle_object_{id}.ply in
+it -> the .obj beside it (ply_path.replace(".ply", ".obj")).  The reference runs `splashsurf reconstruct` per file in a process pool;
+here one GPU reconstructs the frames in order (sph_project_amd/surface.py), so --num_workers is accepted and ignored.
+
+    python sph_project_amd/surface_reconstruction.py --input_dir final_scene0_output --radius 0.01 [--smoothing-length 3.5]
+"""
+import argparse
+import os
+import sys
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _ROOT not in sys.path:
+    sys.path.insert(0, _ROOT)
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--input_dir", type=str, required=True)
+    parser.add_argument("--num_workers", type=int, default=4, help="accepted for compatibility; frames run in order on one GPU")
+    parser.add_argument("--radius", type=float, default=0.01)
+    parser.add_argument("--smoothing-length", type=float, default=3.5)
+    parser.add_argument("--cube-size", type=float, default=0.5, help="splashsurf -c (multiples of the radius)")
+    parser.add_argument("--surface-threshold", type=float, default=0.6, help="splashsurf -t")
+    parser.add_argument("--no-normals", action="store_true", help="no vn lines (splashsurf --normals=off)")
+    return parser.parse_args(argv)
+
+
+def frame_jobs(input_dir):
+    """(ply_path, obj_path) of every frame in the reference's order: frame directories by int(name), .ply files in listdir order."""
+    frames = sorted(os.listdir(input_dir), key=lambda x: int(x))
+    jobs = []
+    for frame in frames:
+        frame_dir = os.path.join(input_dir, frame)
+        for ply_file in [f for f in os.listdir(frame_dir) if f.endswith(".ply")]:
+            ply_path = os.path.join(frame_dir, ply_file)
+            jobs.append((ply_path, ply_path.replace(".ply", ".obj")))
+    return jobs
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    jobs = frame_jobs(args.input_dir)
+    from sph_project_amd.run_simulation import read_ply_ascii
+    from sph_project_amd.surface import SurfaceReconstructor
+    recon = SurfaceReconstructor(args.radius, smoothing_length=args.smoothing_length, cube_size=args.cube_size,
+                                 iso=args.surface_threshold, normals=not args.no_normals)
+    for ply_path, obj_path in jobs:
+        try:
+            recon.from_points(read_ply_ascii(ply_path))
+            recon.write_obj(obj_path)
+        except Exception as e:   # the reference's worker reports a failed frame and goes on
+            print(f"failed to process {os.path.dirname(ply_path)}")
+            print(e)
+    return jobs
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,247 @@
+"""CPU: surface reconstruction without a GPU -- the marching-cubes table, the float64 model (tests/surface_model.py) on
+lattice shapes, the OBJ writer, the drop-in CLI up to the library call, and the C-ABI mirror."""
+import ctypes
+import os
+import shutil
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from sph_project_amd import _lib as L
+from sph_project_amd import mc_table as MC
+from tests import surface_model as SM
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# --- the case table ---------------------------------------------------------------------------------------------------------------
+
+def test_committed_header_is_the_generator_output():
+    assert open(MC.HEADER_PATH).read() == MC.header_text()
+
+
+def _boundary(case):
+    """Directed triangle edges of a case that have no reverse inside the case: the loops on the cube's boundary."""
+    d = {(t[i], t[(i + 1) % 3]) for t in MC.TABLE[case] for i in range(3)}
+    inner = {e for e in d if (e[1], e[0]) in d}
+    return d - inner, inner
+
+
+def _face_of(e0, e1):
+    fs = [f for f in range(6) if e0 in MC.face_edges(f) and e1 in MC.face_edges(f)]
+    return fs[0] if fs else None
+
+
+def test_every_case_closes_into_loops_on_the_cube_boundary():
+    for case in range(256):
+        bnd, inner = _boundary(case)
+        crossing = {e for e, (a, b) in enumerate(MC.EDGE_CORNERS) if ((case >> a) & 1) != ((case >> b) & 1)}
+        # every boundary edge lies in a face; every crossing edge has one edge in and one out; no used edge is not a crossing
+        assert all(_face_of(a, b) is not None for a, b in bnd), case
+        outs = [a for a, _ in bnd]
+        ins = [b for _, b in bnd]
+        assert sorted(outs) == sorted(crossing) == sorted(ins), case
+        # interior diagonals never lie in a face (else the neighbour could use the same edge: four triangles on it)
+        assert all(_face_of(a, b) is None for a, b in inner), case
+        # each triangle appears once, directed edges are unique
+        flat = [(t[i], t[(i + 1) % 3]) for t in MC.TABLE[case] for i in range(3)]
+        assert len(flat) == len(set(flat)), case
+
+
+def test_shared_faces_are_cut_identically_all_256_by_6():
+    """Two cubes that share a face with equal corner signs cut it into the same segments, in opposite directions."""
+    for case in range(256):
+        bnd, _ = _boundary(case)
+        for f, (axis, side, cyc) in enumerate(MC.FACES):
+            mine = {(MC.edge_mid(a).tobytes(), MC.edge_mid(b).tobytes()) for a, b in bnd if _face_of(a, b) == f}
+            # the neighbour across this face: its corners on the face take our signs, the other four run over all 16 patterns
+            shift = np.zeros(3)
+            shift[axis] = 1.0 if side == 1 else -1.0
+            own = [k for k in range(8) if ((k >> axis) & 1) == side]
+            for rest in range(16):
+                nb = 0
+                for k in own:
+                    nk = k ^ (1 << axis)
+                    nb |= ((case >> k) & 1) << nk
+                others = [k for k in range(8) if ((k >> axis) & 1) == side]   # the neighbour's far corners
+                for i, k in enumerate(others):
+                    nb |= ((rest >> i) & 1) << k
+                nbnd, _ = _boundary(nb)
+                f_nb = [g for g, (ax2, sd2, _) in enumerate(MC.FACES) if ax2 == axis and sd2 == 1 - side][0]
+                theirs = {((MC.edge_mid(a) + shift).tobytes(), (MC.edge_mid(b) + shift).tobytes()) for a, b in nbnd if _face_of(a, b) == f_nb}
+                assert {(b, a) for a, b in theirs} == mine, (case, f, nb)
+
+
+# --- the model on lattice shapes ----------------------------------------------------------------------------------------------------
+
+def _inside_check(m, iso=0.6, margin=1e-3):
+    """sph_points_in_mesh agrees with sign(phi - iso) at sample points off the grid lines with |phi - iso| > margin."""
+    e = m["e"]
+    lo = m["vertices"].min(axis=0) - 2 * e
+    hi = m["vertices"].max(axis=0) + 2 * e
+    axes = [np.arange(lo[a], hi[a], 2.3 * e) + 0.3137 * e for a in range(3)]
+    xs, ys, zs = axes
+    inside = np.zeros(len(xs) * len(ys) * len(zs), np.uint8)
+    v = np.ascontiguousarray(m["vertices"], dtype=np.float64)
+    t = np.ascontiguousarray(m["triangles"], dtype=np.int32)
+    lib = L.load()
+    rc = lib.sph_points_in_mesh(v.ctypes.data, len(v), t.ctypes.data, len(t), xs.ctypes.data, len(xs), ys.ctypes.data, len(ys),
+                                zs.ctypes.data, len(zs), inside.ctypes.data)
+    assert rc == 0
+    pts = np.stack(np.meshgrid(xs, ys, zs, indexing="ij"), axis=-1).reshape(-1, 3)
+    phi = m["field"].phi(pts)
+    sel = np.abs(phi - iso) > margin
+    assert sel.sum() > 100 and (phi[sel] > iso).sum() > 20
+    assert ((inside[sel] == 1) == (phi[sel] > iso)).all()
+
+
+@pytest.mark.parametrize("shape", ["ball", "torus"])
+def test_model_mesh_is_closed_oriented_with_the_right_topology(shape):
+    if shape == "ball":
+        x = SM.lattice_ball((0.31, 0.27, 0.33), 0.08, 0.02)
+        want = (1, 2)
+    else:
+        x = SM.lattice_torus((0.5, 0.5, 0.5), 0.15, 0.06, 0.02)
+        want = (1, 0)
+    m = SM.reconstruct(x, 0.01)
+    assert len(m["triangles"]) > 1000
+    assert SM.closed_and_oriented(m["triangles"])
+    assert SM.components_and_euler(len(m["vertices"]), m["triangles"]) == want
+    # counter-clockwise seen from outside: the triangle normals agree with -grad phi (the model's normals)
+    t = m["triangles"]
+    v = m["vertices"]
+    tn = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+    assert (np.einsum("ij,ij->i", tn, m["normals"][t].mean(axis=1)) > 0).mean() > 0.99
+    _inside_check(m)
+
+
+def test_model_mesh_does_not_depend_on_particle_order():
+    x = SM.lattice_ball((0.2, 0.2, 0.2), 0.06, 0.02)
+    a = SM.reconstruct(x, 0.01, normals=False)
+    b = SM.reconstruct(x[np.random.default_rng(3).permutation(len(x))], 0.01, normals=False)
+    assert np.array_equal(a["triangles"], b["triangles"]) and np.allclose(a["vertices"], b["vertices"], rtol=0, atol=1e-12)
+
+
+# --- OBJ writer ------------------------------------------------------------------------------------------------------------------
+
+def _read_obj(path):
+    v, vn, f = [], [], []
+    for line in open(path):
+        tok = line.split()
+        if tok[0] == "v":
+            v.append([float(a) for a in tok[1:]])
+        elif tok[0] == "vn":
+            vn.append([float(a) for a in tok[1:]])
+        elif tok[0] == "f":
+            f.append([int(a.split("//")[0]) - 1 for a in tok[1:]])
+    return np.array(v, np.float32), np.array(vn, np.float32), np.array(f, np.int64)
+
+
+def test_obj_writer_round_trip(tmp_path):
+    from sph_project_amd.surface import write_obj
+    rng = np.random.default_rng(0)
+    v = rng.normal(size=(50, 3)).astype(np.float32)
+    n = rng.normal(size=(50, 3)).astype(np.float32)
+    t = rng.integers(0, 50, size=(70, 3)).astype(np.int32)
+    p = tmp_path / "m.obj"
+    write_obj(str(p), v, t, n)
+    v2, n2, t2 = _read_obj(p)
+    assert np.array_equal(v2, v) and np.array_equal(n2, n) and np.array_equal(t2, t)
+    lines = p.read_text().splitlines()
+    buf = ctypes.create_string_buffer(48)
+    k = L.load().sph_format_f32(ctypes.c_float(v[0, 0]), buf)
+    assert lines[0].split()[1] == buf.raw[:k].decode()
+    assert lines[100] == "f " + " ".join(f"{a + 1}//{a + 1}" for a in t[0])
+    write_obj(str(p), v, t)   # no normals: "f a b c"
+    lines = p.read_text().splitlines()
+    assert len(lines) == 120 and lines[50] == "f " + " ".join(str(a + 1) for a in t[0])
+    # an index out of range is refused, nothing is written
+    with pytest.raises(OSError):
+        write_obj(str(tmp_path / "bad.obj"), v, np.array([[0, 1, 50]], np.int32))
+
+
+# --- the drop-in CLI -------------------------------------------------------------------------------------------------------------
+
+def test_cli_parses_the_reference_arguments_and_walks_frames_in_order(tmp_path, monkeypatch):
+    from sph_project_amd import surface, surface_reconstruction as SR
+    from sph_project_amd.run_simulation import write_ply_ascii
+    for frame in ("10", "2", "0"):
+        os.makedirs(tmp_path / frame)
+        for obj in (0, 3):
+            write_ply_ascii(str(tmp_path / frame / f"particle_object_{obj}.ply"), np.full((2, 3), int(frame) + obj, np.float32))
+    (tmp_path / "2" / "notes.txt").write_text("not a frame file")
+    calls = []
+
+    class Fake:
+        def __init__(self, radius, smoothing_length, cube_size, iso, normals):
+            calls.append(("create", radius, smoothing_length, cube_size, iso, normals))
+
+        def from_points(self, xyz):
+            calls.append(("points", float(xyz[0, 0])))
+
+        def write_obj(self, path):
+            calls.append(("obj", os.path.relpath(path, tmp_path)))
+
+    monkeypatch.setattr(surface, "SurfaceReconstructor", Fake)
+    SR.main(["--input_dir", str(tmp_path), "--num_workers", "8", "--radius", "0.02", "--smoothing-length", "2.0", "--cube-size", "0.75",
+             "--surface-threshold", "0.5", "--no-normals"])
+    assert calls[0] == ("create", 0.02, 2.0, 0.75, 0.5, False)
+    objs = [c[1] for c in calls if c[0] == "obj"]
+    frames = [int(o.split(os.sep)[0]) for o in objs]
+    assert frames == sorted(frames) == [0, 0, 2, 2, 10, 10]
+    assert all(o.endswith(".obj") and "particle_object_" in o for o in objs)
+    pts = [c[1] for c in calls if c[0] == "points"]
+    assert sorted(pts) == sorted(float(int(o.split(os.sep)[0]) + int(o[-5])) for o in objs)
+    a = SR.parse_args(["--input_dir", "x"])
+    assert (a.radius, a.smoothing_length, a.cube_size, a.surface_threshold, a.no_normals, a.num_workers) == (0.01, 3.5, 0.5, 0.6, False, 4)
+
+
+def test_driver_has_the_reconstruct_flag():
+    src = open(os.path.join(ROOT, "sph_project_amd", "run_simulation.py")).read()
+    assert '"--reconstruct"' in src and 'particle_object_{f_body_id}.obj' in src
+
+
+# --- C-ABI -----------------------------------------------------------------------------------------------------------------------
+
+NEW_SYMBOLS = ["sph_write_obj_ascii", "sph_surface_create", "sph_surface_destroy", "sph_surface_last_error", "sph_surface_reconstruct",
+               "sph_surface_reconstruct_object", "sph_surface_mesh_size", "sph_surface_download", "sph_surface_stats"]
+
+
+def test_new_symbols_are_declared_and_exported():
+    header = open(os.path.join(ROOT, "include", "sph_hip.h")).read()
+    lib = L.load()
+    for name in NEW_SYMBOLS:
+        assert f"{name}(" in header and name in L.EXPORTED_SYMBOLS
+        assert getattr(lib, name) is not None
+
+
+@pytest.mark.parametrize("struct", ["SphSurfaceParams", "SphSurfaceStats"])
+def test_surface_structs_match_the_header(struct):
+    cc = shutil.which("cc") or shutil.which("gcc")
+    assert cc is not None
+    cls = getattr(L, struct)
+    names = [n for n, _ in cls._fields_]
+    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"sph_hip.h\"\nint main(void){\n"
+    src += "".join(f'printf("%zu\\n", offsetof({struct}, {n}));\n' for n in names)
+    src += f'printf("%zu\\n", sizeof({struct})); return 0; }}\n'
+    with tempfile.TemporaryDirectory() as d:
+        c, exe = os.path.join(d, "o.c"), os.path.join(d, "o")
+        open(c, "w").write(src)
+        subprocess.check_call([cc, "-I", os.path.join(ROOT, "include"), c, "-o", exe])
+        vals = [int(v) for v in subprocess.check_output([exe]).split()]
+    assert [getattr(cls, n).offset for n in names] == vals[:-1]
+    assert ctypes.sizeof(cls) == vals[-1]
+
+
+def test_create_refuses_bad_parameters_before_touching_a_device():
+    lib = L.load()
+    h = ctypes.c_void_p()
+    for bad in (dict(radius=0.0), dict(cube_size=-1.0), dict(iso=float("nan")), dict(cube_size=0.01), dict(memory_cap_bytes=-1)):
+        kw = dict(radius=0.01, smoothing_length=3.5, cube_size=0.5, iso=0.6, normals=1, fast_math=0, device=-1, reserved=0,
+                  memory_cap_bytes=0)
+        kw.update(bad)
+        assert lib.sph_surface_create(ctypes.byref(L.SphSurfaceParams(**kw)), ctypes.byref(h)) == -1, bad   # SPH_ERR_INVALID
+        assert not h.value
+        assert lib.sph_surface_last_error(None)
