@@ -47,10 +47,10 @@ struct SphHandle {
     double total_time = 0.0;
     bool prepared = false;
     bool pose_dirty = false;
-    int loop_hint[4] = {0, 0, 0, 0};   // iterations the last solve of each device-controlled loop took (sph_steps.hpp device_loop), by reduction slot
+    int loop_hint[4] = {0, 0, 0, 0};   // iterations the last solve of each device-controlled loop took (sph_steps.hpp run_solve), by reduction slot
     struct LoopPub *loop_pub = nullptr;   // pinned: residual + flags of a solver loop's batch, published by a kernel (sph_steps.hpp k_publish_loop)
     unsigned loop_seq = 0, stats_seq = 0;
-    bool loop_flags_clean = false;   // scal->flags[0..1] are zero (the publishing kernel of a stopped loop reset them): device_loop needs no memset
+    bool loop_flags_clean = false;   // scal->flags[0..1] are zero (the publishing kernel of a stopped loop reset them): run_solve needs no memset
     int dev_cus = 256;           // compute units of the device (sizing of grids that should be resident at once)
     bool pose_given = false;     // sph_set_rigid_pose was called: pose_h holds library-frame vectors of the CURRENT axis order
     bool rigid_volume_done = false;
@@ -865,16 +865,16 @@ extern "C" int sph_prepare(SphHandle *h) {
 }
 
 // First half of a step: everything the reference's _step() does before `self.rigid_solver.step()`.
-static int step_first_half(SphHandle *h, bool allow_readback) {
+static int step_first_half(SphHandle *h) {
     if (h->in_step) return fail(h, SPH_ERR_INVALID, "sph_step_begin: the previous step was not ended");
     step_begin(h);
     int rc;
     switch (h->prm.method) {
         case SPH_METHOD_WCSPH: rc = wcsph_step(h); break;                     // WCSPH.py:28-36 (:45 boundary fused into the position update)
-        case SPH_METHOD_DFSPH: rc = dfsph_step_begin(h, allow_readback); break;
-        case SPH_METHOD_IISPH: rc = iisph_step(h, allow_readback); break;     // IISPH.py:204-220
+        case SPH_METHOD_DFSPH: rc = dfsph_step_begin(h); break;
+        case SPH_METHOD_IISPH: rc = iisph_step(h); break;                     // IISPH.py:204-220
         case SPH_METHOD_PBF: rc = pbf_step(h); break;                         // PBF.py:145-158 (the whole _step: no rigid step, no insertion)
-        default: rc = pcisph_step(h, allow_readback); break;                  // PCISPH.py:166-177
+        default: rc = pcisph_step(h); break;                                  // PCISPH.py:166-177
     }
     if (rc) return rc;
     // rigid contact, where the host reads the wrench: the rigid particles still sit where the last sort put them
@@ -886,7 +886,7 @@ static int step_first_half(SphHandle *h, bool allow_readback) {
 
 // Second half: renew_rigid_particle_state (:616) for a pose the host pushed in between, the boundary (and the stale-grid
 // rigid volume) for particles the host appended in between, DFSPH's post-insertion passes, then step()'s tail.
-static int step_second_half(SphHandle *h, bool allow_readback) {
+static int step_second_half(SphHandle *h) {
     if (!h->in_step) return fail(h, SPH_ERR_INVALID, "sph_step_end without sph_step_begin");
     State &s = h->st;
     h->in_step = false;
@@ -899,7 +899,7 @@ static int step_second_half(SphHandle *h, bool allow_readback) {
     // (late entry under sharding: every rank appended the part of the object that lies in its slab, possibly nothing; the
     //  host tells the library the object's whole size through sph_comm_add_global_count -- no collective per step)
     if (h->prm.method == SPH_METHOD_DFSPH) {
-        int rc = dfsph_step_end(h, allow_readback); if (rc) return rc;
+        int rc = dfsph_step_end(h); if (rc) return rc;
         if (h->fresh_state == 1) { h->fresh_state = 2; ph_rigid_volume(h); }  // base_solver.py:696 on the fresh grid: now it sees them
     } else if (h->fresh_state == 2) {
         // WCSPH / PCISPH, one step after the insertion: this step's sort took the new body in, so the reference's
@@ -912,9 +912,9 @@ static int step_second_half(SphHandle *h, bool allow_readback) {
     return SPH_OK;
 }
 
-static int step_once(SphHandle *h, bool allow_readback) {
+static int step_once(SphHandle *h) {
     h->whole_step = true;
-    int rc = step_first_half(h, allow_readback);
+    int rc = step_first_half(h);
     h->whole_step = false;
 #ifdef SPH_TEST_HOOKS
     // test-hook library only: SPH_TEST_FAIL_STEP=k makes the step with h->steps == k fail between its halves, ONCE -- what a device or
@@ -924,7 +924,7 @@ static int step_once(SphHandle *h, bool allow_readback) {
         if (!rc && fail_at >= 0 && h->steps == fail_at) { fail_at = -1; h->in_step = false; rc = fail(h, SPH_ERR_INVALID, "SPH_TEST_FAIL_STEP: injected failure"); }
     }
 #endif
-    if (!rc) rc = step_second_half(h, allow_readback);
+    if (!rc) rc = step_second_half(h);
     // a failed step may leave a hash made for a sort that will not come (NextHash: the WCSPH force pass for the next step's sort, the
     // DFSPH position update for this step's): the next sort, whoever asks for it, must hash for itself on a clean histogram
     if (rc && h->st.prehashed) { h->st.prehashed = 0; h->st.cell_count_clean = 0; h->st.hist_taken = 0; h->st.run_lists_filed = 0; }
@@ -936,7 +936,7 @@ extern "C" int sph_step_begin(SphHandle *h) {
     if (!h->prepared) return fail(h, SPH_ERR_INVALID, "sph_step_begin before sph_prepare");
     HIPCHK(h, hipSetDevice(h->device));
     refresh_counts(h);
-    int rc = step_first_half(h, true); if (rc) return rc;
+    int rc = step_first_half(h); if (rc) return rc;
     rc = slab_settle_if_needed(h); if (rc) return rc;   // the host may append next: it needs the count
     h->n_mark = h->n;
     return check_async(h);
@@ -946,7 +946,7 @@ extern "C" int sph_step_end(SphHandle *h) {
     if (!h) return SPH_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
     refresh_counts(h);
-    int rc = step_second_half(h, true); if (rc) return rc;
+    int rc = step_second_half(h); if (rc) return rc;
     rc = check_async(h); if (rc) return rc;
     return finish_sync(h);
 }
@@ -954,13 +954,14 @@ extern "C" int sph_step_end(SphHandle *h) {
 extern "C" int sph_step_async(SphHandle *h, int nsteps) {
     if (!h || nsteps < 0) return SPH_ERR_INVALID;
     if (!h->prepared) return fail(h, SPH_ERR_INVALID, "sph_step before sph_prepare");
+    // the only check that keeps the pressure solves' stop tests (a read-back per batch) out of asynchronous steps
     if (h->prm.method != SPH_METHOD_WCSPH && h->prm.method != SPH_METHOD_PBF && h->prm.fixed_iterations <= 0)
         return fail(h, SPH_ERR_UNSUPPORTED, "sph_step_async needs wcsph, pbf or fixed_iterations > 0");
     HIPCHK(h, hipSetDevice(h->device));
     refresh_counts(h);
     for (int k = 0; k < nsteps; ++k) {
         h->steps_to_follow = nsteps - 1 - k;   // (a sharded WCSPH step may start the next step's halo message behind its own force pass)
-        int rc = step_once(h, false);
+        int rc = step_once(h);
         h->steps_to_follow = 0;
         if (rc) return rc;   // (step_once drops a hash made for a sort that will not come)
     }
@@ -979,7 +980,7 @@ extern "C" int sph_step(SphHandle *h, int nsteps) {
     if (!h->prepared) return fail(h, SPH_ERR_INVALID, "sph_step before sph_prepare");
     HIPCHK(h, hipSetDevice(h->device));
     refresh_counts(h);
-    for (int k = 0; k < nsteps; ++k) { int rc = step_once(h, true); if (rc) return rc; }
+    for (int k = 0; k < nsteps; ++k) { int rc = step_once(h); if (rc) return rc; }
     int rc = check_async(h); if (rc) return rc;
     return finish_sync(h);
 }

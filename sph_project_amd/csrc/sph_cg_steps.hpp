@@ -4,9 +4,7 @@
 // gravity + surface tension + implicit viscosity + v += dt a  (base_solver.py:190-198, :643)
 static int implicit_viscosity_non_pressure(SphHandle *h) {
     State &s = h->st;
-    const int fixed = h->prm.fixed_iterations;
     const bool slab = s.slab_active != 0;
-    int comm_rc = SPH_OK;
     // few fluid particles (the buckling sheet of C5: 106 k of 2.2 M particles = 416 tiles, one wave per SIMD): every A p pass is
     // pure latency; splitting it by x-offset group triples the waves in flight (PassSplit).  A scene that fills the chip
     // anyway (> ~1500 tiles) gains nothing from it and keeps the single launch.
@@ -15,11 +13,11 @@ static int implicit_viscosity_non_pressure(SphHandle *h) {
     // Slab sharding: the ghosts are the neighbour ranks' rows of the system.  Their search direction goes out before every
     // A p pass (12 B per ghost through the slot tables), the three dot products of an iteration are summed over the ranks
     // (k_cg_fold + one 1-float and one 2-float all-reduce), and the solved velocities of the ghosts after the loop.
-    auto refresh = [&](float4 *arr) { if (slab && !comm_rc) comm_rc = slab_exchange_vel(h, arr); };
-    auto dots = [&](int which) {
-        if (!slab || comm_rc) return;
+    auto refresh = [&](float4 *arr) -> int { return slab ? slab_exchange_vel(h, arr) : SPH_OK; };
+    auto dots = [&](int which) -> int {
+        if (!slab) return SPH_OK;
         { ProfScope p(h, SPH_K_CG_VECTOR); h->L->cg_fold(s, which); }
-        comm_rc = which == 1 ? slab_allreduce_dev(h, &s.scal->red[7], 1) : slab_allreduce_dev(h, &s.scal->red[6], which == 0 ? 1 : 2);
+        return which == 1 ? slab_allreduce_dev(h, &s.scal->red[7], 1) : slab_allreduce_dev(h, &s.scal->red[6], which == 0 ? 1 : 2);
     };
     // One CG iteration = A p pass (+ combine when split), x / r update, p update.  Unsharded, the p update is folded into the
     // NEXT iteration's A p pass (CgApPass::fuse: p = r + beta p_old on the fly while staging; beta, the error and the stop flag
@@ -28,40 +26,31 @@ static int implicit_viscosity_non_pressure(SphHandle *h) {
     const bool fused = !slab && s.cg_p2;
     s.cg_fused_loop = 0;   // (set for the loop only: the A p pass in front of it feeds prepare2 through cg_Ap)
     bool first = true;
-    auto iteration = [&]() {
-        refresh(s.cg_p);
+    auto iteration = [&]() -> int {
+        int rc = refresh(s.cg_p); if (rc) return rc;
         s.cg_fuse = (fused && !first) ? 1 : 0;
         { ProfScope p(h, SPH_K_CG_AP); h->L->cg_ap(s); }
         s.cg_fuse = 0;
-        dots(1);
+        rc = dots(1); if (rc) return rc;
         { ProfScope p(h, SPH_K_CG_VECTOR); h->L->cg_update_xr(s); }
-        dots(2);
+        rc = dots(2); if (rc) return rc;
         if (!fused) { ProfScope p(h, SPH_K_CG_VECTOR); h->L->cg_update_p(s); }
         first = false;
+        return SPH_OK;
     };
     { ProfScope p(h, SPH_K_CG_PREPARE); h->L->cg_prepare(s); }                     // :510
-    refresh(s.cg_p);                                                               // the ghosts' initial guess
+    int rc = refresh(s.cg_p); if (rc) return rc;                                   // the ghosts' initial guess
     { ProfScope p(h, SPH_K_CG_AP); h->L->cg_ap(s); }                               // :511
     { ProfScope p(h, SPH_K_CG_VECTOR); h->L->cg_prepare2(s); h->L->cg_alpha(s); }  // :512 (+ |r0|^2 for the first alpha)
-    dots(0);
+    rc = dots(0); if (rc) return rc;
+    // :445 conjugate_gradient_loop; tol starts at 1000 (:446), the residual reported with fixed_iterations
+    const SolveSpec sp{.slot = 3, .kind = 3, .thr = 1e-6, .denom = 1.0f, .max_itr = 1000, .fixed_err = 1000.0f,
+                       .iter = &h->last.iter_cg, .err = &h->last.err_cg, .batch_end = fused ? h->L->cg_check : nullptr};
     s.cg_fused_loop = fused ? 1 : 0;
-    float tol = 1000.0f;
-    int itr = 0;
-    const int max_itr = fixed > 0 ? fixed : 1000;
-    if (fixed <= 0) {   // :445 conjugate_gradient_loop, stop test on the device (see device_loop)
-        int launched = 0;
-        int rc = device_loop(h, max_itr, 3, 3, 1.0f, 1e-6, iteration, &itr, &launched, &tol, fused ? h->L->cg_check : nullptr);
-        if (rc) return rc;
-    }
-    while (fixed > 0 && itr < max_itr) {
-        iteration();
-        itr++;
-    }
+    rc = run_solve(h, sp, [] {}, iteration);
     s.cg_fused_loop = 0;
-    if (comm_rc) return comm_rc;
-    refresh(s.cg_x);                                                               // solved velocities of the ghosts (:514)
-    if (comm_rc) return comm_rc;
-    h->last.iter_cg = itr; h->last.err_cg = tol;
+    if (rc) return rc;
+    rc = refresh(s.cg_x); if (rc) return rc;                                       // solved velocities of the ghosts (:514)
     // :514-516: the explicit viscosity formula evaluated with the solved velocities gives the acceleration; the
     // fused pass adds gravity + surface tension and advances the ORIGINAL velocities (:470, :643)
     s.np_visc_vel = s.cg_x;

@@ -3,8 +3,7 @@
 #pragma once
 #include <sched.h>
 
-// reads scal->red[slot] (one small D2H copy + stream sync: the reference's python loops read one
-// scalar per iteration too, DFSPH.py:150, :236; PCISPH.py:122)
+// reads scal->red[slot] (one small D2H copy + stream sync): the residual of the single IISPH iteration phase
 static int read_red(SphHandle *h, int slot, float *out) {
     HIPCHK(h, hipMemcpyAsync(&h->scal_h->red[slot], &h->st.scal->red[slot], sizeof(float), hipMemcpyDeviceToHost, h->st.stream));
     HIPCHK(h, hipStreamSynchronize(h->st.stream));
@@ -96,48 +95,83 @@ static int loop_readback(SphHandle *h) {
 // particle_num the reference's residual means divide by (DFSPH.py:212, :293): the whole scene's, not this slab's
 static long long dfsph_particle_num(SphHandle *h) { return h->st.slab_active ? h->comm_n_global : (long long)h->n; }
 
-// Solver loop with the stop test on the device.  `body` launches one iteration; its last reduction kernel evaluates
-// the reference's criterion (kind / denom / thr, see State::loop_kind), counts the iteration and raises
-// scal->flags[0]; every kernel of a later iteration starts with a look at that flag and returns.  Iterations go out in
-// batches with ONE read-back per batch instead of one error read-back per iteration (the reference, and this code before,
-// synchronise with the host every iteration).  The state after the loop is the state after exactly the iteration the
-// reference would have stopped at, whatever the batch sizes.
+// A solve with a FIXED iteration count (SphParams::fixed_iterations: bench mode, sph_step_async) has no stop test, and nothing reads
+// the residual of an iteration (SphStats::err_* report the reference's initial value in this mode): the walks still leave their
+// per-workgroup partial sums, but the one-workgroup kernel that adds them up -- 5 us and a launch boundary per iteration, 2.4 % of a
+// C3 step -- is not launched.  Unsharded only (a sharded solve all-reduces the residual either way).
+struct SkipResidual {
+    State &s;
+    SkipResidual(SphHandle *h) : s(h->st) {
+        s.skip_residual = (h->prm.fixed_iterations > 0 && !s.slab_active) ? 1 : 0;
+    }
+    ~SkipResidual() { s.skip_residual = 0; }
+};
+
+// What run_solve needs to know about one iterative solve.
+struct SolveSpec {
+    int slot;          // reduction slot of the residual (scal->red[slot]); also indexes loop_hint
+    int kind;          // the reference's stop test, evaluated by the iteration's last reduction (State::loop_kind)
+    double thr;        // its threshold
+    float denom;       // residual = red[slot] / denom (0 when denom is not positive)
+    int max_itr;       // iteration cap without fixed_iterations
+    float fixed_err;   // residual reported with fixed_iterations: the reference's initial value
+    int32_t *iter;     // where the iteration count and the residual go (h->last)
+    float *err;
+    void (*batch_end)(State &);   // optional: launched behind every batch, before its read-back (CG: cg_check)
+};
+
+// Solver loop.  `pre` launches the passes in front of the loop, `body` one iteration and returns the rc of its exchanges: the first
+// non-zero rc ends the solve.  With fixed_iterations > 0: exactly that many iterations, no stop test, no read-back.  Otherwise the
+// stop test runs on the device: the iteration's last reduction kernel evaluates the reference's criterion, counts the iteration and
+// raises scal->flags[0]; every kernel of a later iteration starts with a look at that flag and returns.  Iterations go out in
+// batches with ONE read-back per batch (loop_readback) instead of one per iteration (the reference synchronises with the host every
+// iteration).  The state after the loop is the state after exactly the iteration the reference would have stopped at, whatever the
+// batch sizes.
 // Batch sizes (round 5): a solve takes about as many iterations as the same solve of the last step (C5: 41.5 +- 1 CG
 // iterations; C3 in motion: 26.5 +- 1 density iterations), so the FIRST batch is last step's count less one and the
 // loop then goes on in small batches -- two read-backs per solve instead of five to seven.  Every read-back is a
 // stream drain plus the host's launch latency before the GPU has work again (~25-40 us of idle chip: the rocprofv3
 // traces of round 5 show 188 us of kernels per DFSPH iteration in motion against 285 us of wall time, profiles/
-// r05_rocprofv3_c3_motion_summary.txt).  Without a hint (first step): 2, 4, 8, 8, ... as before.
-template <class F>
-static int device_loop(SphHandle *h, int max_itr, int slot, int kind, float denom, double thr, F body, int *executed,
-                       int *launched, float *last_val, void (*batch_end)(State &) = nullptr) {
+// r05_rocprofv3_c3_motion_summary.txt).  Without a hint (first step): 2, 4, 8, 8, ...
+// *launched (optional): the iterations enqueued; past the stop they are no-ops, so it can exceed *sp.iter by up to a batch.
+template <class Pre, class Body>
+static int run_solve(SphHandle *h, const SolveSpec &sp, Pre pre, Body body, int *launched = nullptr) {
     State &s = h->st;
-    if (!h->loop_flags_clean) HIPCHK(h, hipMemsetAsync(&s.scal->flags[0], 0, 2 * sizeof(int), s.stream));
-    h->loop_flags_clean = false;
-    s.loop_flag = &s.scal->flags[0];
-    s.loop_slot = slot; s.loop_kind = kind; s.loop_denom = denom; s.loop_thr = thr;
-    const int hint = (slot < 0 || slot >= 4) ? 0 : h->loop_hint[slot];
-    int n_launched = 0, batch = hint > 3 ? hint - 1 : 2, rc = SPH_OK;
-    bool predicted = hint > 3;
-    // red[8] and flags[4] are neighbours in DevScalars: one 48-byte copy brings the residual and the flags
-    static_assert(offsetof(DevScalars, flags) == offsetof(DevScalars, red) + 8 * sizeof(float), "red / flags layout");
-    while (n_launched < max_itr) {
-        const int nb = batch < max_itr - n_launched ? batch : max_itr - n_launched;
-        for (int k = 0; k < nb; ++k) body();
-        if (batch_end) batch_end(s);
-        n_launched += nb;
-        rc = loop_readback(h);
-        if (rc) break;
-        if (h->scal_h->flags[0]) break;
-        if (predicted) { batch = 2; predicted = false; }
-        else if (batch < 8) batch *= 2;
+    SkipResidual skip(h);
+    pre();
+    const int fixed = h->prm.fixed_iterations;
+    int n = 0;
+    if (fixed > 0) {
+        for (; n < fixed; ++n) { int rc = body(); if (rc) return rc; }
+        *sp.iter = fixed; *sp.err = sp.fixed_err;
+    } else {
+        if (!h->loop_flags_clean) HIPCHK(h, hipMemsetAsync(&s.scal->flags[0], 0, 2 * sizeof(int), s.stream));
+        h->loop_flags_clean = false;
+        s.loop_flag = &s.scal->flags[0];
+        s.loop_slot = sp.slot; s.loop_kind = sp.kind; s.loop_denom = sp.denom; s.loop_thr = sp.thr;
+        const int hint = h->loop_hint[sp.slot];
+        int batch = hint > 3 ? hint - 1 : 2, rc = SPH_OK;
+        bool predicted = hint > 3;
+        // red[8] and flags[4] are neighbours in DevScalars: one 48-byte copy brings the residual and the flags
+        static_assert(offsetof(DevScalars, flags) == offsetof(DevScalars, red) + 8 * sizeof(float), "red / flags layout");
+        while (n < sp.max_itr) {
+            const int nb = std::min(batch, sp.max_itr - n);
+            for (int k = 0; k < nb && !rc; ++k) rc = body();
+            if (rc) break;
+            if (sp.batch_end) sp.batch_end(s);
+            n += nb;
+            rc = loop_readback(h);
+            if (rc || h->scal_h->flags[0]) break;
+            if (predicted) { batch = 2; predicted = false; }
+            else if (batch < 8) batch *= 2;
+        }
+        s.loop_flag = nullptr;
+        if (rc) return rc;
+        *sp.iter = h->loop_hint[sp.slot] = h->scal_h->flags[1];
+        *sp.err = sp.denom > 0 ? h->scal_h->red[sp.slot] / sp.denom : 0.0f;
     }
-    s.loop_flag = nullptr;
-    *executed = h->scal_h->flags[1];
-    *launched = n_launched;
-    *last_val = h->scal_h->red[slot];
-    if (slot >= 0 && slot < 4 && rc == SPH_OK) h->loop_hint[slot] = h->scal_h->flags[1];
-    return rc;
+    if (launched) *launched = n;
+    return SPH_OK;
 }
 
 // base_solver.py:190 compute_non_pressure_acceleration + :643 update_fluid_velocity
@@ -207,109 +241,51 @@ static int wcsph_step(SphHandle *h) {
     return SPH_OK;
 }
 
-// A solve with a FIXED iteration count (SphParams::fixed_iterations: bench mode, sph_step_async) has no stop test, and nothing reads
-// the residual of an iteration (SphStats::err_* report 0 in this mode): the walks still leave their per-workgroup partial sums, but the
-// one-workgroup kernel that adds them up -- 5 us and a launch boundary per iteration, 2.4 % of a C3 step -- is not launched.  Unsharded
-// only (a sharded solve all-reduces the residual either way).
-struct SkipResidual {
-    State &s;
-    SkipResidual(SphHandle *h) : s(h->st) {
-        s.skip_residual = (h->prm.fixed_iterations > 0 && !s.slab_active) ? 1 : 0;
-    }
-    ~SkipResidual() { s.skip_residual = 0; }
-};
-
-// DFSPH.py:139 correct_divergence_error
-static int dfsph_divergence(SphHandle *h, bool allow_readback, bool first_derivative_done = false) {
+// DFSPH.py:139 correct_divergence_error.  Under slab sharding the ghosts' kappa_v goes out before the correction and their velocities
+// after it, and the residual is summed over the ranks.
+static int dfsph_divergence(SphHandle *h, bool first_derivative_done = false) {
     State &s = h->st;
-    SkipResidual skip(h);
-    const int fixed = h->prm.fixed_iterations;
-    const int max_itr = fixed > 0 ? fixed : 1000;
-    // DFSPH.py:140 compute_density_derivative before the loop (dfsph_step_end has it fused into the density + alpha walk)
-    if (!first_derivative_done) { ProfScope p(h, SPH_K_DFSPH_RHO_ADV); h->L->dfsph_rho_adv(s, 0); }
-    int itr = 0;
-    float avg = 0.0f;
-    const float n_all = (float)dfsph_particle_num(h);   // DFSPH.py:212 divides by particle_num (every rank's, under sharding)
-    int comm_rc = SPH_OK;
-    // one solver iteration; under slab sharding the ghosts' kappa_v goes out before the correction and their velocities
-    // after it, and the residual is summed over the ranks
-    auto iteration = [&]() {
+    const SolveSpec sp{.slot = 0, .kind = 1, .thr = 0.001 * h->prm.density_0 / (double)s.c.dt,   // :150
+                       .denom = (float)dfsph_particle_num(h), .max_itr = 1000, .fixed_err = 0.0f,   // :212 divides by particle_num
+                       .iter = &h->last.iter_divergence, .err = &h->last.err_divergence, .batch_end = nullptr};
+    int launched = 0;
+    int rc = run_solve(h, sp, [&] {
+        // DFSPH.py:140 compute_density_derivative before the loop (dfsph_step_end has it fused into the density + alpha walk)
+        if (!first_derivative_done) { ProfScope p(h, SPH_K_DFSPH_RHO_ADV); h->L->dfsph_rho_adv(s, 0); }
+    }, [&]() -> int {
         std::swap(s.kappa_v, s.kappa_v_next);  // DFSPH.py:133 compute_kappa_v: value of the last density-derivative pass
-        if (s.slab_active && !comm_rc) comm_rc = slab_exchange_scalar(h, s.kappa_v);
+        if (s.slab_active) { int rc = slab_exchange_scalar(h, s.kappa_v); if (rc) return rc; }
         { ProfScope p(h, SPH_K_DFSPH_CORRECT); h->L->dfsph_correct(s, 0); }
-        if (s.slab_active && !comm_rc) comm_rc = slab_exchange_vel(h);
+        if (s.slab_active) { int rc = slab_exchange_vel(h); if (rc) return rc; }
         { ProfScope p(h, SPH_K_DFSPH_RHO_ADV); h->L->dfsph_rho_adv(s, 0); }
-        if (s.slab_active && !comm_rc) comm_rc = slab_finish_reduction(h, 0);
-    };
-    if (fixed <= 0 && allow_readback) {
-        const double eta = 0.001 * h->prm.density_0 / (double)s.c.dt;  // :150
-        int launched = 0; float sum = 0.0f;
-        int rc = device_loop(h, max_itr, 0, 1, n_all, eta, iteration, &itr, &launched, &sum);
-        if (rc) return rc;
-        if (comm_rc) return comm_rc;
-        if ((launched - itr) & 1) std::swap(s.kappa_v, s.kappa_v_next);   // iterations past the stop did not run
-        h->last.iter_divergence = itr; h->last.err_divergence = sum / n_all;
-        return SPH_OK;
-    }
-    while (itr < 1 || itr < max_itr) {
-        iteration();
-        if (comm_rc) return comm_rc;
-        itr++;
-        if (fixed > 0) continue;
-        if (!allow_readback) return fail(h, SPH_ERR_UNSUPPORTED, "dfsph needs host read-back unless fixed_iterations > 0");
-        float sum; int rc = read_red(h, 0, &sum); if (rc) return rc;
-        avg = sum / n_all;                                          // DFSPH.py:212 (divides by particle_num)
-        const double eta = 0.001 * h->prm.density_0 / (double)s.c.dt;  // :150
-        if ((double)avg <= eta) break;
-    }
-    h->last.iter_divergence = itr; h->last.err_divergence = avg;
+        return s.slab_active ? slab_finish_reduction(h, 0) : SPH_OK;
+    }, &launched);
+    if (rc) return rc;
+    if ((launched - h->last.iter_divergence) & 1) std::swap(s.kappa_v, s.kappa_v_next);   // iterations past the stop did not run
     return SPH_OK;
 }
 
-// DFSPH.py:225 correct_density_error
-static int dfsph_density(SphHandle *h, bool allow_readback) {
+// DFSPH.py:225 correct_density_error (sharded as the divergence solve)
+static int dfsph_density(SphHandle *h) {
     State &s = h->st;
-    SkipResidual skip(h);
-    const int fixed = h->prm.fixed_iterations;
-    const int max_itr = fixed > 0 ? fixed : 1000;
-    { ProfScope p(h, SPH_K_DFSPH_RHO_ADV); h->L->dfsph_rho_adv(s, 1); }
-    int itr = 0;
-    float avg = 0.0f;
-    const float n_all = (float)dfsph_particle_num(h);
-    int comm_rc = SPH_OK;
-    auto iteration = [&]() {
+    const SolveSpec sp{.slot = 1, .kind = 1, .thr = 0.0001, .denom = (float)dfsph_particle_num(h), .max_itr = 1000,   // :239, :293
+                       .fixed_err = 0.0f, .iter = &h->last.iter_density, .err = &h->last.err_density, .batch_end = nullptr};
+    int launched = 0;
+    int rc = run_solve(h, sp, [&] { ProfScope p(h, SPH_K_DFSPH_RHO_ADV); h->L->dfsph_rho_adv(s, 1); }, [&]() -> int {
         std::swap(s.kappa, s.kappa_next);      // DFSPH.py:218 compute_kappa
-        if (s.slab_active && !comm_rc) comm_rc = slab_exchange_scalar(h, s.kappa);
+        if (s.slab_active) { int rc = slab_exchange_scalar(h, s.kappa); if (rc) return rc; }
         { ProfScope p(h, SPH_K_DFSPH_CORRECT); h->L->dfsph_correct(s, 1); }
-        if (s.slab_active && !comm_rc) comm_rc = slab_exchange_vel(h);
+        if (s.slab_active) { int rc = slab_exchange_vel(h); if (rc) return rc; }
         { ProfScope p(h, SPH_K_DFSPH_RHO_ADV); h->L->dfsph_rho_adv(s, 1); }
-        if (s.slab_active && !comm_rc) comm_rc = slab_finish_reduction(h, 1);
-    };
-    if (fixed <= 0 && allow_readback) {
-        int launched = 0; float sum = 0.0f;
-        int rc = device_loop(h, max_itr, 1, 1, n_all, 0.0001, iteration, &itr, &launched, &sum);   // :239
-        if (rc) return rc;
-        if (comm_rc) return comm_rc;
-        if ((launched - itr) & 1) std::swap(s.kappa, s.kappa_next);
-        h->last.iter_density = itr; h->last.err_density = sum / n_all;
-        return SPH_OK;
-    }
-    while (itr < 1 || itr < max_itr) {
-        iteration();
-        if (comm_rc) return comm_rc;
-        itr++;
-        if (fixed > 0) continue;
-        if (!allow_readback) return fail(h, SPH_ERR_UNSUPPORTED, "dfsph needs host read-back unless fixed_iterations > 0");
-        float sum; int rc = read_red(h, 1, &sum); if (rc) return rc;
-        avg = sum / n_all;                                          // DFSPH.py:293
-        if ((double)avg <= 0.0001) break;                            // :239
-    }
-    h->last.iter_density = itr; h->last.err_density = avg;
+        return s.slab_active ? slab_finish_reduction(h, 1) : SPH_OK;
+    }, &launched);
+    if (rc) return rc;
+    if ((launched - h->last.iter_density) & 1) std::swap(s.kappa, s.kappa_next);
     return SPH_OK;
 }
 
 // DFSPH.py:298 _step, first half: up to (not including) rigid_solver.step() / insert_object() at :305-:308
-static int dfsph_step_begin(SphHandle *h, bool allow_readback) {
+static int dfsph_step_begin(SphHandle *h) {
     State &s = h->st;
     if (h->sort_dirty) {
         // particles were appended outside a step (plain C-ABI use): the passes below walk the cell lists, so bring them
@@ -325,7 +301,7 @@ static int dfsph_step_begin(SphHandle *h, bool allow_readback) {
     }
     int rc = run_non_pressure(h); if (rc) return rc;                          // DFSPH.py:299-300
     if (s.slab_active) { rc = slab_exchange_vel(h); if (rc) return rc; }      // the density solver reads v_j of the ghosts
-    rc = dfsph_density(h, allow_readback); if (rc) return rc;                 // :301
+    rc = dfsph_density(h); if (rc) return rc;                                 // :301
     // the sort of this step's second half follows at once when the whole step is one call (step_once): the position update hashes for it
     s.nexthash.on = (h->whole_step && !s.slab_active && s.c.all_fluid && !s.has_emitter && !h->any_rigid_object &&
                      !h->sort_dirty && !h->pose_dirty) ? 1 : 0;
@@ -335,57 +311,34 @@ static int dfsph_step_begin(SphHandle *h, bool allow_readback) {
 
 // second half: :309 renew_rigid_particle_state and :311 boundary for what the host just inserted (step_insert_tail),
 // then :316-:319
-static int dfsph_step_end(SphHandle *h, bool allow_readback) {
+static int dfsph_step_end(SphHandle *h) {
     State &s = h->st;
     if (s.slab_active) { int rc = slab_neighbor_search(h); if (rc) return rc; }   // + migration / ghost exchange
     else { s.sort_skip_rho = s.c.all_fluid; ph_neighbor_search(h); }          // :316 (the density pass below rewrites every rho: the sort need not move it)
     ph_rigid_volume(h);
     { ProfScope p(h, SPH_K_DFSPH_DENSITY_ALPHA); h->L->dfsph_density_alpha_div(s); }     // :317-318 + the D rho / Dt of :140
     if (s.slab_active) { int rc = slab_exchange_scalar(h, s.rho.cur()); if (rc) return rc; }   // ghost densities (kappa_j / rho_j, viscosity)
-    return dfsph_divergence(h, allow_readback, true);                         // :319
+    return dfsph_divergence(h, true);                                         // :319
 }
 
 // PCISPH.py:110 refine.  Under slab sharding the ghosts' p / rho^2 goes out between the two passes of an
 // iteration and their predicted positions after it; the density error is summed over the ranks.
-static int pcisph_refine(SphHandle *h, bool allow_readback) {
+static int pcisph_refine(SphHandle *h) {
     State &s = h->st;
-    SkipResidual skip(h);
-    const int fixed = h->prm.fixed_iterations;
-    const int max_itr = fixed > 0 ? fixed : 1000;
-    int itr = 0;
-    float err = 100.0f;
-    const float n_fl = (float)(s.slab_active ? h->comm_nfluid_global : (long long)h->n_fluid);   // PCISPH.py:43-46 divides by fluid_particle_num
-    int comm_rc = SPH_OK;
-    auto iteration = [&]() {
+    const SolveSpec sp{.slot = 2, .kind = 2, .thr = 0.001,                                                   // :122
+                       .denom = (float)(s.slab_active ? h->comm_nfluid_global : (long long)h->n_fluid),   // :43-46 divides by fluid_particle_num
+                       .max_itr = 1000, .fixed_err = 100.0f,                                              // :157
+                       .iter = &h->last.iter_pcisph, .err = &h->last.err_pcisph, .batch_end = nullptr};
+    return run_solve(h, sp, [] {}, [&]() -> int {
         { ProfScope p(h, SPH_K_PCISPH_RHO_STAR); h->L->pcisph_rho_star(s); }
-        if (s.slab_active && !comm_rc) comm_rc = slab_exchange_scalar(h, s.ptm);
+        if (s.slab_active) { int rc = slab_exchange_scalar(h, s.ptm); if (rc) return rc; }
         { ProfScope p(h, SPH_K_PCISPH_PRESSURE_ACCEL); h->L->pcisph_pressure_accel(s); }
-        if (s.slab_active && !comm_rc) comm_rc = slab_exchange_vel(h, s.ppos);
-        if (s.slab_active && !comm_rc) comm_rc = slab_finish_reduction(h, 2);
-    };
-    if (fixed <= 0 && allow_readback) {
-        int launched = 0; float sum = 0.0f;
-        int rc = device_loop(h, max_itr, 2, 2, n_fl, 0.001, iteration, &itr, &launched, &sum);   // PCISPH.py:43-46, :122
-        if (rc) return rc;
-        if (comm_rc) return comm_rc;
-        h->last.iter_pcisph = itr; h->last.err_pcisph = n_fl > 0 ? sum / n_fl : 0.0f;
-        return SPH_OK;
-    }
-    while (itr < max_itr) {
-        iteration();
-        if (comm_rc) return comm_rc;
-        itr++;
-        if (fixed > 0) continue;
-        if (!allow_readback) return fail(h, SPH_ERR_UNSUPPORTED, "pcisph needs host read-back unless fixed_iterations > 0");
-        float sum; int rc = read_red(h, 2, &sum); if (rc) return rc;
-        err = n_fl > 0 ? sum / n_fl : 0.0f;                          // PCISPH.py:43-46
-        if (err < 0.001f) break;                                    // :122
-    }
-    h->last.iter_pcisph = itr; h->last.err_pcisph = err;
-    return SPH_OK;
+        if (s.slab_active) { int rc = slab_exchange_vel(h, s.ppos); if (rc) return rc; }
+        return s.slab_active ? slab_finish_reduction(h, 2) : SPH_OK;
+    });
 }
 
-static int pcisph_step(SphHandle *h, bool allow_readback) {
+static int pcisph_step(SphHandle *h) {
     State &s = h->st;
     if (s.slab_active) { int rc = slab_neighbor_search(h); if (rc) return rc; }   // + migration / ghost exchange
     else { s.sort_skip_rho = s.c.all_fluid; ph_neighbor_search(h); }          // PCISPH.py:166 (:167 below rewrites every rho)
@@ -395,50 +348,39 @@ static int pcisph_step(SphHandle *h, bool allow_readback) {
     int rc = run_non_pressure(h); if (rc) return rc;                          // :168 (+ :174, v* kept aside)
     { ProfScope p(h, SPH_K_MISC); h->L->pcisph_init(s); }                     // :169
     if (s.slab_active) { rc = slab_exchange_vel(h, s.ppos); if (rc) return rc; }   // predicted positions of the ghosts
-    rc = pcisph_refine(h, allow_readback); if (rc) return rc;                 // :170
+    rc = pcisph_refine(h); if (rc) return rc;                                 // :170
     { ProfScope p(h, SPH_K_PRESSURE_INTEGRATE); h->L->pressure_integrate(s); } // :175-177, :185
     return SPH_OK;
 }
 
-// IISPH.py:185 refine: relaxed Jacobi, at least one iteration, stops when the average density error drops below eta (a negative
-// error stops it too) or after max_iterations.  The criterion is tested on the device (device_loop, kind 2: error < (float)eta,
-// error = sum / (fluid_particle_num rho0), :118-121).  fixed_iterations > 0: exactly that many, no read-back, error reported 0.
-static int iisph_refine(SphHandle *h, bool allow_readback) {
+// IISPH.py:185 refine, one iteration (also the phase SPH_PH_IISPH_ITERATION)
+static void iisph_iteration(SphHandle *h) {
     State &s = h->st;
-    SkipResidual skip(h);
-    const int fixed = h->prm.fixed_iterations;
-    const int max_itr = fixed > 0 ? fixed : SPH_IISPH_MAX_ITER;
-    const float denom = (float)h->n_fluid * (float)h->prm.density_0;
-    auto iteration = [&]() {
-        { ProfScope p(h, SPH_K_IISPH_DIJ_PJ); h->L->iisph_dij_pj(s); }     // :188
-        { ProfScope p(h, SPH_K_IISPH_SUM_I); h->L->iisph_sum_i(s); }       // :189-190 (+ the error's partial sums)
-    };
-    int itr = 0;
-    float err = 0.0f;
-    if (fixed <= 0) {
-        if (!allow_readback) return fail(h, SPH_ERR_UNSUPPORTED, "iisph needs host read-back unless fixed_iterations > 0");
-        int launched = 0; float sum = 0.0f;
-        int rc = device_loop(h, max_itr, 2, 2, denom, SPH_IISPH_ETA, iteration, &itr, &launched, &sum);   // :194-197
-        if (rc) return rc;
-        err = h->n_fluid > 0 ? sum / denom : 0.0f;
-    } else {
-        for (; itr < max_itr; ++itr) iteration();
-    }
-    h->last.iter_iisph = itr; h->last.err_iisph = err;
-    return SPH_OK;
+    { ProfScope p(h, SPH_K_IISPH_DIJ_PJ); h->L->iisph_dij_pj(s); }     // :188
+    { ProfScope p(h, SPH_K_IISPH_SUM_I); h->L->iisph_sum_i(s); }       // :189-190 (+ the error's partial sums)
+}
+
+// IISPH.py:185 refine: relaxed Jacobi, at least one iteration, stops when the average density error drops below eta (a negative
+// error stops it too) or after max_iterations.  Stop test kind 2: error < (float)eta, error = sum / (fluid_particle_num rho0),
+// :118-121.  fixed_iterations > 0: exactly that many, error reported 0.
+static int iisph_refine(SphHandle *h) {
+    const SolveSpec sp{.slot = 2, .kind = 2, .thr = SPH_IISPH_ETA, .denom = (float)h->n_fluid * (float)h->prm.density_0,   // :194-197
+                       .max_itr = SPH_IISPH_MAX_ITER, .fixed_err = 0.0f, .iter = &h->last.iter_iisph, .err = &h->last.err_iisph,
+                       .batch_end = nullptr};
+    return run_solve(h, sp, [] {}, [h] { iisph_iteration(h); return (int)SPH_OK; });
 }
 
 // IISPH.py:203 _step up to the rigid solver: the sort, compute_density (no EOS), init_step + non-pressure forces + v* (:206-208, the
 // pressures are cleared by the prepare pass), dii / aii / rho* (:210-213), refine (:215), pressure acceleration + v, x update +
 // boundary (:218-220, :227: the same tail as PCISPH's)
-static int iisph_step(SphHandle *h, bool allow_readback) {
+static int iisph_step(SphHandle *h) {
     State &s = h->st;
     s.sort_skip_rho = s.c.all_fluid; ph_neighbor_search(h);                  // :204 (:205 below rewrites every rho)
     ph_rigid_volume(h);
     { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 0); }                   // :205
     int rc = run_non_pressure(h); if (rc) return rc;                          // :207-208
     { ProfScope p(h, SPH_K_IISPH_PREPARE); h->L->iisph_prepare(s); }          // :206, :210-213
-    rc = iisph_refine(h, allow_readback); if (rc) return rc;                  // :215
+    rc = iisph_refine(h); if (rc) return rc;                                  // :215
     { ProfScope p(h, SPH_K_PRESSURE_INTEGRATE); h->L->pressure_integrate(s); } // :218-220, :227
     return SPH_OK;
 }
@@ -517,16 +459,15 @@ static int method_run_phase(SphHandle *h, int phase) {
     if (h->prm.method == SPH_METHOD_DFSPH) {
         switch (phase) {
             case SPH_PH_DFSPH_ALPHA: { ProfScope p(h, SPH_K_DFSPH_DENSITY_ALPHA); h->L->dfsph_density_alpha(s); } return SPH_OK;
-            case SPH_PH_DFSPH_DIVERGENCE: return dfsph_divergence(h, true);
-            case SPH_PH_DFSPH_DENSITY: return dfsph_density(h, true);
+            case SPH_PH_DFSPH_DIVERGENCE: return dfsph_divergence(h);
+            case SPH_PH_DFSPH_DENSITY: return dfsph_density(h);
             default: break;
         }
     } else if (h->prm.method == SPH_METHOD_IISPH) {
         switch (phase) {
             case SPH_PH_IISPH_PREPARE: { ProfScope p(h, SPH_K_IISPH_PREPARE); h->L->iisph_prepare(s); } return SPH_OK;
-            case SPH_PH_IISPH_ITERATION: {   // one iteration, no stop test; its error is read back
-                h->L->iisph_dij_pj(s);
-                h->L->iisph_sum_i(s);
+            case SPH_PH_IISPH_ITERATION: {   // one iteration of the step's refine, no stop test; its error is read back
+                iisph_iteration(h);
                 float sum = 0.0f;
                 int rc = read_red(h, 2, &sum); if (rc) return rc;
                 const float denom = (float)h->n_fluid * (float)h->prm.density_0;

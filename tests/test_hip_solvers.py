@@ -50,21 +50,32 @@ def test_solver_drift_vs_oracle(gpu, method, steps, spacing):
     assert solver.stats()["pair_interactions"] > 0
 
 
-@pytest.mark.parametrize("method", ["dfsph", "pcisph"])
-def test_fixed_iterations_async(gpu, method):
+@pytest.mark.parametrize("method,viscosity_method", [("dfsph", "standard"), ("pcisph", "standard"), ("dfsph", "implicit")],
+                         ids=["dfsph", "pcisph", "dfsph_implicit"])
+def test_fixed_iterations_async(gpu, method, viscosity_method):
     """bench mode: fixed iteration counts, no host read-back, asynchronous stepping."""
-    cfg = H.dam_break_scene(method=method, end=(0.2, 0.2, 0.2), dt=4e-4)
-    container, solver = H.build_product(cfg, fixed_iterations=2)
+    fixed = 2
+    cfg = H.dam_break_scene(method=method, end=(0.2, 0.2, 0.2), dt=4e-4, viscosity_method=viscosity_method)
+    container, solver = H.build_product(cfg, fixed_iterations=fixed)
     solver.prepare()
     container.engine.step_async(5)
     container.engine.synchronize()
-    ref = H.build_oracle(cfg, fixed_iterations=2)
+    ref = H.build_oracle(cfg, fixed_iterations=fixed)
     ref.prepare()
     ref.step(5)
     x, _ = _xv(container)
     xr, _ = _ref_xv(ref)
     assert H.drift(x, xr, container.dh).max() <= 1e-5
-    cfg2 = H.dam_break_scene(method=method, end=(0.1, 0.1, 0.1))
+    # fixed mode reports the fixed count and the reference's initial residual (PCISPH.py:157, base_solver.py:446; 0 for DFSPH)
+    st = solver.stats()
+    if method == "dfsph":
+        assert st["iter_divergence"] == st["iter_density"] == fixed
+        assert st["err_divergence"] == st["err_density"] == 0.0
+    else:
+        assert st["iter_pcisph"] == fixed and st["err_pcisph"] == 100.0
+    if viscosity_method == "implicit":
+        assert st["iter_cg"] == fixed and st["err_cg"] == 1000.0
+    cfg2 = H.dam_break_scene(method=method, end=(0.1, 0.1, 0.1), viscosity_method=viscosity_method)
     c2, s2 = H.build_product(cfg2)
     s2.prepare()
     with pytest.raises(L.SphError):
