@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the SPH hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline needs and nothing else: set-up, warm-up, pre-pass, the K timed steps, --dump-outputs, the
+line (roofline figures from the events of the timed window only).  --full adds everything below that takes runs of its own:
+the per-kernel solo event passes, `in_motion`, the copy-rate measurement, the CPU baseline and the extra scenes (C3 / C5 at
+N = 1, `c2_weak_scaling` / `c4_strong_scaling` at N > 1); --no-cpu-baseline, --no-extras, --no-c4 and --motion-step 0 trim it.
 
 A "step" is one solver.step() of the reference (neighbour search + density/EOS + non-pressure forces + pressure
 forces + symplectic integration + boundary) over the whole particle set.  N=1 workload = BASELINE.json configs[1]
@@ -74,7 +79,10 @@ def parse_args(argv=None):
     ap.add_argument("--strict-math", action="store_true", help="IEEE div/sqrt build instead of the fast build")
     ap.add_argument("--no-deterministic", action="store_true")
     ap.add_argument("--force-global", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own beyond the headline: per-kernel solo event passes, `in_motion`, "
+                         "the copy rate, the CPU baseline and the extra scenes (the --no-* options and --motion-step trim it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=1, help="repetitions of the K timed steps (median reported)")
     ap.add_argument("--measured-iterations", action="store_true",
@@ -83,19 +91,19 @@ def parse_args(argv=None):
     ap.add_argument("--presteps", type=int, default=0,
                     help="untimed steps before the warm-up (the headline `value` is always quoted with 0)")
     ap.add_argument("--motion-step", type=int, default=2500,
-                    help="after the headline measurement advance the scene to this step and time again (`in_motion`); 0: skip")
+                    help="--full: after the headline measurement advance the scene to this step and time again (`in_motion`); 0: skip")
     ap.add_argument("--all-kernels", action="store_true", help="also print the per-kernel HIP-event table (stderr)")
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
                     help="N>1: strong (default) = BASELINE.json's metric as written: the 1.23 M scene itself split over the N ranks; "
                          "weak = every z-slab gets one C2 block (N x 1.23 M particles) -- without this flag weak scaling is the extra "
                          "object `c2_weak_scaling` of the line")
     ap.add_argument("--replicas", action="store_true", help="N>1: independent copies instead of z-slab sharding")
-    ap.add_argument("--no-c4", action="store_true", help="N>1: skip the extra C4 (4 M particles, strong scaling) measurement")
+    ap.add_argument("--no-c4", action="store_true", help="--full, N>1: skip the extra C4 (4 M particles, strong scaling) measurement")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="N=1: write the state the last timed step left (positions, velocities, densities by particle id) "
                          "as DIR/<name>.npy")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra objects of the line: N=1: C3 (DFSPH) and C5 (implicit-viscosity buckling scene); "
+                    help="--full: skip the extra objects of the line: N=1: C3 (DFSPH) and C5 (implicit-viscosity buckling scene); "
                          "N>1: the 1.23 M scene and C4 under strong scaling")
     return ap.parse_args(argv)
 
@@ -601,9 +609,9 @@ def run_rank(args, rank, world, local_rank):
     # ... and every kernel that carries algorithmic bytes once more ALONE (one kernel id's events at a time): with all ids enabled the
     # event pairs of neighbouring launches serialise the stream and inflate a walk by 6-8 %.  `all_kernels` / `runner_up`
     # quote these solo figures; the all-event one is kept beside them.  They run AFTER the timed window (and the dump): how many steps they
-    # take depends on the kernels a build launches, the state the timed window starts from must not.
+    # take depends on the kernels a build launches, the state the timed window starts from must not.  --full only.
     solo = {}
-    if not os.environ.get("SPH_BENCH_NO_EVENTS"):
+    if args.full and not os.environ.get("SPH_BENCH_NO_EVENTS"):
         for k in [k for k in table if k in ALG_BYTES]:
             eng.profile_enable(names.index(k), True); eng.profile_reset()
             run(3); steps_done += 3
@@ -636,7 +644,7 @@ def run_rank(args, rank, world, local_rank):
 
     in_motion = None
     fixed_work = method == "wcsph" or not args.measured_iterations   # (measured-iteration loops: ms/step is the iteration count's)
-    if args.motion_step and not args.presteps and args.config in ("c2", "c3", "c4") and fixed_work and steps_done < args.motion_step:
+    if args.full and args.motion_step and not args.presteps and args.config in ("c2", "c3", "c4") and fixed_work and steps_done < args.motion_step:
         run(args.motion_step - steps_done); steps_done = args.motion_step
         m_el = median(timed(args.repeats))
         st2 = solver.stats()
@@ -664,7 +672,7 @@ def run_rank(args, rank, world, local_rank):
         except Exception:  # noqa: BLE001
             pass
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             copy_gbs = eng.measure_copy_rate(1 << 30, 10)   # measured now, on this GPU: the second denominator
         except Exception as ex:  # noqa: BLE001
@@ -699,8 +707,9 @@ def run_rank(args, rank, world, local_rank):
             "device": eng.device_info()["name"],
         },
         "in_motion": in_motion,
-        "value_state": "from rest (steps %d.. of the initial lattice, %s neighbours per particle); `value_in_motion` is the same scene from step %s on"
-                       % (timed_from, ("%.0f" % (evals / max(n_total, 1) / 2.0)) if method == "wcsph" else "n/a", args.motion_step),
+        "value_state": "from rest (steps %d.. of the initial lattice, %s neighbours per particle)"
+                       % (timed_from, ("%.0f" % (evals / max(n_total, 1) / 2.0)) if method == "wcsph" else "n/a")
+                       + ("; `value_in_motion` is the same scene from step %s on" % args.motion_step if args.full else ""),
         "value_in_motion": in_motion["value"] if in_motion else None,
         "roofline": {
             "bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -722,23 +731,23 @@ def run_rank(args, rank, world, local_rank):
             "secondary": secondary,
             # the two neighbour walks of a WCSPH step are within 2-3 % of each other, so which one is "dominant" can flip between runs --
             # and with it `frac` (24 vs 96 algorithmic bytes per particle).  Both, each from an event pass of its own in this run (one kernel id
-            # enabled at a time; `avg_us_with_all_events_on` is the 6-8 % higher figure of the pass with every id enabled):
+            # enabled at a time; `avg_us_with_all_events_on` is the 6-8 % higher figure of the pass with every id enabled).  --full only:
             "all_kernels": {k: {"avg_us": 1e3 * v[1] / v[0], "avg_us_with_all_events_on": 1e3 * table_all[k][1] / table_all[k][0],
                                 "alg_bytes_per_launch": alg_bytes[k] * n_fluid,
                                 "frac": alg_bytes[k] * n_fluid / (v[1] / v[0] * 1e-3) / 1e9 / HBM_PEAK_GBS}
-                            for k, v in table.items() if k in ALG_BYTES},
+                            for k, v in table.items() if k in ALG_BYTES} if args.full else None,
             "runner_up": (lambda ru: None if ru is None else {"kernel": ru, "avg_launch_us": 1e3 * table[ru][1] / table[ru][0],
                                                                "frac": alg_bytes[ru] * n_fluid / (table[ru][1] / table[ru][0] * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                                                "note": "second kernel by time; when it is within a few per cent of `kernel`, which of the two "
                                                                        "is 'dominant' -- and with it `frac` (their algorithmic bytes differ 4x) -- can flip between runs"})(
-                max((k for k in table if k in ALG_BYTES and k != dom), key=lambda k: table[k][1], default=None)),
+                max((k for k in table if k in ALG_BYTES and k != dom), key=lambda k: table[k][1], default=None)) if args.full else None,
             "note": "the neighbour passes are not HBM-bound: per the PMC passes they run at ~2.4 GHz with about half of the VALU issue "
                     "slots used and 40-50 % of the wave-cycles parked (4-5 resident waves per SIMD, about half of them runnable: occupancy, "
                     "not serialised loads -- halving a workgroup's memory round trips moved them 2 %, profiles/r03w_ab_round_trips.txt); "
                     "`secondary` (from profiles/, not this run) carries those figures; DESIGN.md 5",
         },
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cb = cpu_baseline(cfg, args.cpu_steps)
         out["cpu_baseline"] = {
             "value": cb["value"], "unit": "particle-updates/s", "cores": cb["cores"], "kind": "port",
@@ -754,7 +763,7 @@ def run_rank(args, rank, world, local_rank):
         }
     elif rank == 0:
         out["cpu_baseline"] = None
-    extras_ok = not args.no_extras and args.config == "c2" and method == "wcsph" and not args.presteps
+    extras_ok = args.full and not args.no_extras and args.config == "c2" and method == "wcsph" and not args.presteps
     if multi and sharded and extras_ok:
         eng.comm_barrier()
         eng.close()

@@ -512,7 +512,7 @@ def test_bench_line_contract(gpu):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c1", "--steps", "5", "--warmup", "2",
-                        "--cpu-steps", "1"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--cpu-steps", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -528,6 +528,29 @@ def test_bench_line_contract(gpu):
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in d["cpu_baseline"], k
     assert d["cpu_baseline"]["kind"] == "port" and d["value"] > d["cpu_baseline"]["value"] > 0
+
+
+def test_bench_plain_run_is_the_headline_only(gpu):
+    """Without --full bench.py times its steps and prints the line, and runs nothing of its own after them: no CPU baseline, no solo
+    per-kernel event passes, no copy-rate measurement, no in-motion window, no extra scenes."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c1", "--steps", "5", "--warmup", "2"],
+                       capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "particle-updates/sec" and d["unit"] == "particle-updates/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 5 and d["value"] > 0 and d["ms_per_step"] == d["repeat_ms_per_step"][0] > 0
+    assert d["config"]["state"] == "steps 7..12 from the initial lattice", d["config"]["state"]   # warm-up 2 + pre-pass 5
+    assert d["cpu_baseline"] is None and d["in_motion"] is None and "extras" not in d
+    ro = d["roofline"]
+    assert ro["achieved"] > 0 and ro["launches"] >= 5 and abs(ro["frac"] - ro["achieved"] / ro["peak"]) < 1e-12
+    assert ro["measured_copy_gbs"] is None and ro["all_kernels"] is None and ro["runner_up"] is None
 
 
 def _run_fast(cfg, steps, jitter=0.003, seed=2):

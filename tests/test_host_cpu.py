@@ -414,3 +414,11 @@ def test_bench_dump_reorders_by_id_and_samples_above_the_limit():
     bad[0] = bad[1]
     with pytest.raises(RuntimeError):
         bench.dump_arrays(bad, fields)
+
+
+def test_bench_measures_beyond_the_headline_only_with_full():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` is the headline alone; --full (off by default) turns on what takes runs of its own."""
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False and plain.steps == 20 and plain.warmup == 5
+    assert bench.parse_args(["--full"]).full is True

@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 O=gpurun_out/r06_final; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -q > $O/gpu_suite.txt 2>&1; tail -4 $O/gpu_suite.txt
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_driver_line.json 2> $O/bench_driver_line.err; tail -c 300 $O/bench_driver_line.json; echo
+timeout 600 python bench.py --steps 20 --warmup 5 --full > $O/bench_driver_line.json 2> $O/bench_driver_line.err; tail -c 300 $O/bench_driver_line.json; echo
 cp profiles/pmc_derived.json gpurun_out/pmc_derived.json
 for t in c2 c3 c5; do
   rm -rf gpurun_out/prof_r06f_$t
@@ -20,8 +20,8 @@ timeout 200 python bench.py --presteps 2500 --steps 100 --warmup 10 --no-cpu-bas
 timeout 200 python tools/bench_c5.py --no-events --steps 20 --warmup 3 2>/dev/null | tail -1 > $O/bench_c5.json; cat $O/bench_c5.json | cut -c1-300
 timeout 200 python bench.py --config c4 --steps 50 --warmup 5 --no-cpu-baseline --no-extras --motion-step 0 2>/dev/null | tail -1 | cut -c1-260 > $O/bench_c4_one_gpu.json; cat $O/bench_c4_one_gpu.json; echo
 timeout 200 python tools/slab_size_probe.py --steps 200 > $O/slab_size_probe.json 2>/dev/null; cat $O/slab_size_probe.json
-SPH_COMM_TRANSPORT=shm+ipc timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --steps 20 --warmup 5 > $O/torchrun_two_ranks.json 2> $O/torchrun_two_ranks.err; tail -c 600 $O/torchrun_two_ranks.json; echo; tail -3 $O/torchrun_two_ranks.err
+SPH_COMM_TRANSPORT=shm+ipc timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --steps 20 --warmup 5 --full > $O/torchrun_two_ranks.json 2> $O/torchrun_two_ranks.err; tail -c 600 $O/torchrun_two_ranks.json; echo; tail -3 $O/torchrun_two_ranks.err
 # the driver's 8-rank job with all ranks on this one GPU (strong scaling of the 1.23 M scene: the headline form for N > 1 since round 6)
-SPH_COMM_TRANSPORT=shm+ipc SPH_COMM_TIMEOUT_S=120 timeout 600 python bench.py --gpus 8 --steps 20 --warmup 5 --no-cpu-baseline --motion-step 0 > $O/eight_ranks_one_gpu_bench.json 2> $O/eight_ranks_one_gpu_bench.err; tail -c 900 $O/eight_ranks_one_gpu_bench.json; echo
+SPH_COMM_TRANSPORT=shm+ipc SPH_COMM_TIMEOUT_S=120 timeout 600 python bench.py --gpus 8 --steps 20 --warmup 5 --full --no-cpu-baseline --motion-step 0 > $O/eight_ranks_one_gpu_bench.json 2> $O/eight_ranks_one_gpu_bench.err; tail -c 900 $O/eight_ranks_one_gpu_bench.json; echo
 # C3 with the solvers' own stop tests, from rest and in motion
 timeout 300 python bench.py --config c3 --measured-iterations --steps 20 --warmup 5 --no-cpu-baseline --no-extras --motion-step 0 2>/dev/null | tail -1 | cut -c1-400 > $O/bench_c3_measured_rest.json

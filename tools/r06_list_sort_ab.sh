@@ -11,5 +11,5 @@ timeout 900 python -m pytest tests/test_hip_wcsph.py tests/test_hip_golden.py -m
 SPH_SORT_RANK_KERNEL=1 timeout 900 python -m pytest tests/test_hip_wcsph.py -m gpu -x -q -k "list_sort or next_hash or c2_full_size_20" 2>&1 | tail -2 | tee -a gpurun_out/r06_list_sort/tests.txt
 tools/ab.sh r06_list_sort lists="" rankk="SPH_SORT_RANK_KERNEL=1" records="SPH_NO_RUN_LISTS=1" lists2="" rankk2="SPH_SORT_RANK_KERNEL=1" records2="SPH_NO_RUN_LISTS=1" 2>&1 | tee gpurun_out/r06_list_sort/summary.txt
 for v in "X=1" "SPH_SORT_RANK_KERNEL=1" "SPH_NO_RUN_LISTS=1" "X=1" "SPH_SORT_RANK_KERNEL=1" "SPH_NO_RUN_LISTS=1"; do
-  env $v python bench.py --config c3 --steps 50 --warmup 5 --no-cpu-baseline --no-extras --motion-step 1000 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().split('\n')[-1]); print('C3 2+2 [%-24s] %.4f ms/step from rest, %.4f at step 1000' % ('$v', d['ms_per_step'], d['in_motion']['ms_per_step']))"
+  env $v python bench.py --config c3 --steps 50 --warmup 5 --full --no-cpu-baseline --no-extras --motion-step 1000 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().split('\n')[-1]); print('C3 2+2 [%-24s] %.4f ms/step from rest, %.4f at step 1000' % ('$v', d['ms_per_step'], d['in_motion']['ms_per_step']))"
 done 2>&1 | tee -a gpurun_out/r06_list_sort/summary.txt
