@@ -413,6 +413,64 @@ int sph_surface_mesh_size(SphSurface *s, int64_t *n_vertices, int64_t *n_triangl
 int sph_surface_download(SphSurface *s, float *vertices, float *normals_or_NULL, int32_t *triangles);
 int sph_surface_stats(SphSurface *s, SphSurfaceStats *out);
 
+/* --- particle rendering: particles -> one RGB frame ------------------------------------------------------------- */
+/* replaces the GGUI frame of run_simulation.py:116-135 (scene.particles(x_vis_buffer, radius=dx, per_vertex_color=...), scene.lines of
+   the domain box, scene.point_light, window.save_image -> raw_view.png).  Not GGUI's shaders: the image is defined here and in
+   DESIGN.md 15.  Camera: f = normalize(target - eye), s = normalize(f x up), u = s x f; pixel column i (from the left), row j (from the
+   top) looks along d = f + (2(i+.5)/W - 1) tan(fov/2) W/H s + (1 - 2(j+.5)/H) tan(fov/2) u (f.d = 1).  A sphere (centre c, radius r)
+   covers the pixel where disc = b^2 - (d.d)(|c-E|^2 - r^2) >= 0, b = d.(c-E), and t = (b - sqrt(disc)) / (d.d) > z_near; the pixel's
+   winner has the smallest (float_bits(t) << 32 | id) -- the image is a function of the particle SET.  Colour: col/255 (ambient +
+   max(n.L, 0) light_rgb), clamped, floor(255 x + 0.5); P = E + t d, n = (P - c)/r, L = normalize(light - P).  Box: the 12 edges of
+   [box_lo, box_hi], one pixel wide, unshaded, depth-tested with ids 0xFFFFFFF0 + edge: clipped at z_near, one pixel per step along the
+   screen major axis, the nearest pixel on the minor axis, 1/z linear on the screen.  One HIP stream per object; synchronous calls. */
+typedef struct {
+    int32_t width, height;   /* pixels (1024 x 1024 in the reference); each 1..16384, width * height <= 2^26 */
+    double eye[3];           /* camera position (5.5, 2.5, 4.0) */
+    double target[3];        /* look-at (-1, 0, 0) */
+    double up[3];            /* (0, 1, 0) */
+    double fov_deg;          /* vertical field of view, (0, 180) (70) */
+    double z_near;           /* > 0 (0.1) */
+    double radius;           /* sphere radius, > 0 (the container's dx) */
+    double light_pos[3];     /* point light (2, 2, 2) */
+    double light_rgb[3];     /* (1, 1, 1) */
+    double ambient;          /* >= 0 (0.1, our choice) */
+    int32_t background_rgb[3]; /* 0..255 each (0, 0, 0) */
+    int32_t draw_box;        /* 1: the 12 edges of [box_lo, box_hi] */
+    double box_lo[3], box_hi[3];
+    int32_t box_rgb[3];      /* 0..255 each ((0.99, 0.68, 0.28) -> (252, 173, 71)) */
+    int32_t fast_math;       /* 0: IEEE div / sqrt, no FMA contraction; 1: the fast build */
+    int32_t device;          /* HIP device ordinal, -1: current */
+    int32_t reserved;        /* 0 */
+} SphRenderParams;
+
+typedef struct {
+    int64_t particles;        /* particles given (points) / slots of the handle (handle) */
+    int64_t drawn;            /* taken (object mask, no ghost or dead slot), finite and not culled */
+    int64_t skipped_nonfinite;/* taken but with a non-finite coordinate: not drawn */
+    int64_t large;            /* drawn spheres whose screen bounds exceed 4096 pixels (one workgroup each) */
+    int64_t atomics;          /* 64-bit atomicMin issued by the sphere splat (after the plain load said the key would drop) */
+    int64_t covered_pixels;   /* pixels won by a sphere */
+    double ms_input;          /* HIP events: upload (points) / colour source (handle), clear of the depth keys */
+    double ms_splat;          /* spheres (small, large) and box lines */
+    double ms_shade;          /* the winners' colours, background and id image */
+    double ms_total;
+} SphRenderStats;
+
+typedef struct SphRender SphRender;
+int sph_render_create(const SphRenderParams *params, SphRender **out);
+void sph_render_destroy(SphRender *r);
+const char *sph_render_last_error(SphRender *r);
+/* host particles: xyz f32[n][3], rgb_or_NULL u8[n][3] (NULL: white), ids_or_NULL u32[n] (distinct, < 0xFFFFFFF0; NULL: 0 .. n-1) */
+int sph_render_points(SphRender *r, const float *xyz, const uint8_t *rgb_or_NULL, const uint32_t *ids_or_NULL, int64_t n);
+/* the particles of a live handle whose object id has its bit set in object_mask (ghosts and dead slots never), each with its persistent
+   id (SPH_F_PARTICLE_ID) and its colour as sph_download(SPH_F_COLOR) gives it; the handle's state is left untouched.  The handle must
+   be on the same device and not between sph_step_begin and sph_step_end; SPH_ERR_UNSUPPORTED on a sharded handle. */
+int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mask);
+/* the last frame: rgb u8[height][width][3] (rows from the top), ids_or_NULL i32[height][width]: the winner's id, -1 background,
+   -2 - edge a box line */
+int sph_render_download(SphRender *r, uint8_t *rgb, int32_t *ids_or_NULL);
+int sph_render_stats(SphRender *r, SphRenderStats *out);
+
 #ifdef __cplusplus
 }
 #endif

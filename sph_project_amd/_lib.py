@@ -100,6 +100,24 @@ class SphSurfaceStats(C.Structure):
     ]
 
 
+class SphRenderParams(C.Structure):
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("eye", C.c_double * 3), ("target", C.c_double * 3), ("up", C.c_double * 3),
+        ("fov_deg", C.c_double), ("z_near", C.c_double), ("radius", C.c_double), ("light_pos", C.c_double * 3),
+        ("light_rgb", C.c_double * 3), ("ambient", C.c_double), ("background_rgb", C.c_int32 * 3), ("draw_box", C.c_int32),
+        ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3), ("box_rgb", C.c_int32 * 3), ("fast_math", C.c_int32),
+        ("device", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class SphRenderStats(C.Structure):
+    _fields_ = [
+        ("particles", C.c_int64), ("drawn", C.c_int64), ("skipped_nonfinite", C.c_int64), ("large", C.c_int64),
+        ("atomics", C.c_int64), ("covered_pixels", C.c_int64),
+        ("ms_input", C.c_double), ("ms_splat", C.c_double), ("ms_shade", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class SphError(RuntimeError):
     pass
 
@@ -159,6 +177,13 @@ _SIGNATURES = [
     ("sph_surface_mesh_size", C.c_int, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("sph_surface_download", C.c_int, [_VP, _VP, _VP, _VP]),
     ("sph_surface_stats", C.c_int, [_VP, C.POINTER(SphSurfaceStats)]),
+    ("sph_render_create", C.c_int, [C.POINTER(SphRenderParams), C.POINTER(_VP)]),
+    ("sph_render_destroy", None, [_VP]),
+    ("sph_render_last_error", C.c_char_p, [_VP]),
+    ("sph_render_points", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64]),
+    ("sph_render_handle", C.c_int, [_VP, _VP, C.c_uint32]),
+    ("sph_render_download", C.c_int, [_VP, _VP, _VP]),
+    ("sph_render_stats", C.c_int, [_VP, C.POINTER(SphRenderStats)]),
     ("sph_comm_allreduce", C.c_int, [_VP, C.POINTER(C.c_double), C.c_int, C.c_int]),
     ("sph_comm_barrier", C.c_int, [_VP]),
     ("sph_comm_selftest", C.c_int, [_VP, C.c_int]),

@@ -213,6 +213,34 @@ struct SurfDev {
     hipStream_t stream;
 };
 
+// Particle rendering (sph_render.hpp): camera, shading constants, the particle source and the frame buffers of one
+// SphRender.  Source: pos[i] (xyz), id[i], colour col_home[id[i]] when col_home is set, else col[i] (r | g << 8 | b << 16; both null:
+// white); meta null = every particle drawn, else object mask / ghosts / dead from META_*.  key[p] = (float_bits(t) << 32) | id.
+#define RENDER_LINE_ID0 0xFFFFFFF0u
+struct RenderDev {
+    int W, H;
+    float E[3], f[3], s[3], u[3];      // eye, forward, right, up (f x U normalised, s x f)
+    float tx, ty;                      // tan(fov / 2) W / H, tan(fov / 2)
+    float zn, r, r2;                   // near plane, sphere radius, r^2
+    float light[3], lrgb[3], amb;      // point light - E in (s, u, f) coordinates, its colour, ambient
+    unsigned bg, box;                  // background / box line colour (r | g << 8 | b << 16)
+    int draw_box;
+    float line[12][8];                 // box edge e, clipped at zn and projected (host, double): {major0, minor0, major1, minor1, 1/z0,
+    int line_axis[12];                 //   1/z1, first step, last step} in continuous pixels (centre = integer + 0.5); axis 0: major = x,
+                                       //   1: major = y, -1: not drawn
+    int n;                             // particles of the source
+    const float4 *pos;
+    const int *meta, *id;
+    const unsigned *col, *col_home;
+    unsigned mask;                     // object mask (handle path)
+    unsigned long long *key;           // [W H]
+    unsigned char *rgb;                // [H][W][3]
+    int *ids;                          // [W H] -1 background, -2 - edge, else the particle id
+    int *large;                        // [n] particles whose screen bounds exceed RENDER_LARGE_PX pixels
+    unsigned long long *cnt;           // [8] drawn, non-finite, large, atomics issued, covered pixels
+    hipStream_t stream;
+};
+
 template <class T> struct DBuf {
     T *b[2] = {nullptr, nullptr};
     int c = 0;
@@ -434,6 +462,9 @@ struct Launch {
     void (*surf_count)(SurfDev &);              // classify cubes and edges, per-brick vertex / triangle counts and their scans
     void (*surf_emit)(SurfDev &);               // vertices and triangles
     void (*surf_normals)(SurfDev &, int nv);    // -grad phi / |grad phi| at every vertex
+    // particle rendering (sph_render.hpp)
+    void (*render_splat)(RenderDev &);          // depth keys of spheres (small per thread, large per workgroup) and box lines
+    void (*render_shade)(RenderDev &);          // the winners' colours, then background / ids / covered count per pixel
     void (*layer_hist)(State &, int *hist);      // owned particles per global cell layer
     void (*loop_criterion)(State &, int slot);   // stop test on an all-reduced residual (sharded solver loops)
     // push transport: the step message is written by halo_classify_pack itself; then

@@ -1,0 +1,159 @@
+"""Particle rendering on the GPU: particles -> one RGB frame (C-ABI sph_render_* in include/sph_hip.h).
+
+Replaces the reference's GGUI frame (run_simulation.py:116-135: scene.particles with radius dx and per-particle colours, the domain box as
+lines, a point light at (2, 2, 2), window.save_image -> raw_view.png) with the project's own image, drawn by the HIP passes of
+csrc/sph_render.hpp.  Not pixel-identical to GGUI, whose shaders are not part of this product.  No CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import struct
+import zlib
+
+import numpy as np
+
+from . import _lib as L
+
+BOX_RGB = (252, 173, 71)   # the reference's (0.99, 0.68, 0.28), floor(255 x + 0.5)
+
+
+class RenderError(L.SphError):
+    def __init__(self, msg, code):
+        super().__init__(msg)
+        self.code = code
+
+
+class FrameRenderer:
+    """One renderer (camera and frame buffers fixed at creation).  Defaults: the reference's camera, light and background; box=None
+    draws no box in from_points, while from_container draws [0, domainEnd] unless box=False."""
+
+    def __init__(self, radius, width=1024, height=1024, camera_position=(5.5, 2.5, 4.0), camera_lookat=(-1.0, 0.0, 0.0),
+                 camera_up=(0.0, 1.0, 0.0), fov=70.0, z_near=0.1, light_position=(2.0, 2.0, 2.0), light_color=(1.0, 1.0, 1.0),
+                 ambient=0.1, background=(0, 0, 0), box=None, box_color=BOX_RGB, fast_math=False, device=-1):
+        self.lib = L.load()
+        self.radius = float(radius)
+        self.width, self.height = int(width), int(height)
+        self.box = box
+        self._kw = dict(width=self.width, height=self.height, eye=camera_position, target=camera_lookat, up=camera_up, fov_deg=float(fov),
+                        z_near=float(z_near), radius=self.radius, light_pos=light_position, light_rgb=light_color, ambient=float(ambient),
+                        background_rgb=background, box_rgb=box_color, fast_math=int(bool(fast_math)), device=int(device))
+        self._handles = {}   # box (None or (lo, hi)) -> native renderer
+        self._last = None
+
+    def _params(self, box):
+        kw = dict(self._kw)
+        p = L.SphRenderParams()
+        for k in ("eye", "target", "up", "light_pos", "light_rgb"):
+            getattr(p, k)[:] = [float(v) for v in kw.pop(k)]
+        for k in ("background_rgb", "box_rgb"):
+            getattr(p, k)[:] = [int(v) for v in kw.pop(k)]
+        for k, v in kw.items():
+            setattr(p, k, v)
+        p.draw_box = int(box is not None)
+        if box is not None:
+            p.box_lo[:] = [float(v) for v in box[0]]
+            p.box_hi[:] = [float(v) for v in box[1]]
+        p.reserved = 0
+        return p
+
+    def _native(self, box):
+        key = None if box is None else (tuple(float(v) for v in box[0]), tuple(float(v) for v in box[1]))
+        h = self._handles.get(key)
+        if h is None:
+            h = C.c_void_p()
+            rc = self.lib.sph_render_create(C.byref(self._params(key)), C.byref(h))
+            if rc != 0:
+                msg = self.lib.sph_render_last_error(None)
+                raise RenderError(f"sph_render_create failed ({rc}): {msg.decode() if msg else ''}", rc)
+            self._handles[key] = h
+        return h
+
+    def close(self):
+        for h in getattr(self, "_handles", {}).values():
+            self.lib.sph_render_destroy(h)
+        self._handles = {}
+        self._last = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, h, rc, what):
+        if rc != 0:
+            msg = self.lib.sph_render_last_error(h)
+            raise RenderError(f"{what} failed ({rc}): {msg.decode() if msg else ''}", rc)
+
+    def _download(self, h):
+        rgb = np.empty((self.height, self.width, 3), np.uint8)
+        self._chk(h, self.lib.sph_render_download(h, rgb.ctypes.data, None), "sph_render_download")
+        self._last = h
+        return rgb
+
+    def from_points(self, xyz, colors=None, ids=None):
+        """uint8 (H, W, 3) of spheres at xyz f32[n, 3], colours uint8[n, 3] (None: white), distinct ids < 0xFFFFFFF0 (None: 0..n-1)."""
+        x = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        c = None if colors is None else np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 3)
+        i = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if (c is not None and len(c) != len(x)) or (i is not None and len(i) != len(x)):
+            raise ValueError("from_points: xyz, colors and ids must have one row per particle")
+        h = self._native(self.box if self.box else None)
+        self._chk(h, self.lib.sph_render_points(h, x.ctypes.data, None if c is None else c.ctypes.data,
+                                                None if i is None else i.ctypes.data, x.shape[0]), "sph_render_points")
+        return self._download(h)
+
+    def from_container(self, container, hide=()):
+        """uint8 (H, W, 3) of a live container's visible objects (object_visibility == 1, minus `hide`), drawn from the device state
+        with their persistent ids and colours; box: [0, domainEnd] as in the reference unless the renderer was made with box=False
+        (or with a box of its own)."""
+        engine = getattr(container, "engine", container)
+        vis = np.asarray(container.object_visibility)
+        mask = 0
+        for o in range(min(len(vis), 32)):
+            if vis[o] == 1 and o not in hide:
+                mask |= 1 << o
+        box = self.box
+        if box is None:
+            box = (np.zeros(3), np.asarray(container.domain_end, dtype=np.float64))
+        h = self._native(box if box is not False else None)
+        self._chk(h, self.lib.sph_render_handle(h, engine.h, C.c_uint32(mask)), "sph_render_handle")
+        return self._download(h)
+
+    def ids(self):
+        """int32 (H, W) of the last frame: the winner's particle id, -1 background, -2 - edge a box line."""
+        if self._last is None:
+            raise RenderError("ids: no frame rendered yet", -1)
+        rgb = np.empty((self.height, self.width, 3), np.uint8)
+        out = np.empty((self.height, self.width), np.int32)
+        self._chk(self._last, self.lib.sph_render_download(self._last, rgb.ctypes.data, out.ctypes.data), "sph_render_download")
+        return out
+
+    def stats(self):
+        if self._last is None:
+            raise RenderError("stats: no frame rendered yet", -1)
+        st = L.SphRenderStats()
+        self._chk(self._last, self.lib.sph_render_stats(self._last, C.byref(st)), "sph_render_stats")
+        return {k: getattr(st, k) for k, _ in L.SphRenderStats._fields_}
+
+
+def _chunk(tag, data):
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+
+def encode_png(rgb, level=6):
+    """8-bit RGB PNG bytes of uint8 (H, W, 3): filter 0 on every row, one zlib stream, stdlib only."""
+    a = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"encode_png: expected (H, W, 3), got {a.shape}")
+    h, w = a.shape[:2]
+    raw = np.zeros((h, 1 + 3 * w), np.uint8)
+    raw[:, 1:] = a.reshape(h, 3 * w)
+    ihdr = struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)
+    return b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", zlib.compress(raw.tobytes(), level)) + _chunk(b"IEND", b"")
+
+
+def write_png(path, rgb):
+    """rgb uint8 (H, W, 3) as an 8-bit RGB PNG (what window.save_image wrote as raw_view.png in the reference)."""
+    with open(path, "wb") as f:
+        f.write(encode_png(rgb))

@@ -6,8 +6,8 @@ run_simulation.py (:13-44 argument + interval arithmetic, :116-155 loop, :137-14
 
 Frames go to {scene_name}_output/{cnt:06}/particle_object_{id}.ply (ASCII PLY, x y z per vertex -- the
 layout Taichi's PLYWriter.export_ascii produces and surface_reconstruction.py / splashsurf consume).
-Rigid bodies: mesh_object_{id}.obj per frame with exportObj (:146-150).  PNG frames (exportFrame) need the reference's
-GGUI window and are not produced."""
+Rigid bodies: mesh_object_{id}.obj per frame with exportObj (:146-150).  PNG frames (exportFrame, :131-134) come from the GPU
+renderer of render.py with --render (its own image, not GGUI's: DESIGN.md 15); without --render none is written."""
 import argparse
 import os
 import sys
@@ -76,6 +76,13 @@ def main(argv=None):
     parser.add_argument("--reconstruct", action="store_true",
                         help="with every PLY frame also write particle_object_{id}.obj: the fluid object's surface, reconstructed on the "
                              "GPU from the device state (surface_reconstruction.py's defaults; not in the reference)")
+    parser.add_argument("--render", action="store_true",
+                        help="on scenes with exportFrame write {out}/{cnt:06}/raw_view.png at the reference's cadence, rendered on the GPU "
+                             "from the device state (DESIGN.md 15; not GGUI's image)")
+    parser.add_argument("--render_size", type=int, nargs=2, default=(1024, 1024), metavar=("W", "H"))
+    parser.add_argument("--camera_position", type=float, nargs=3, default=(5.5, 2.5, 4.0))
+    parser.add_argument("--camera_lookat", type=float, nargs=3, default=(-1.0, 0.0, 0.0))
+    parser.add_argument("--camera_fov", type=float, default=70.0, help="vertical, degrees")
     args = parser.parse_args(argv)
     scene_path = args.scene_file
     config = SimConfig(scene_file_path=scene_path)
@@ -94,6 +101,7 @@ def main(argv=None):
         output_interval = config.get_cfg("outputInterval")
     output_ply = config.get_cfg("exportPly")
     output_obj = config.get_cfg("exportObj")
+    output_frames = config.get_cfg("exportFrame") and args.render
     out_dir = args.output_dir or f"{scene_name}_output"
     os.makedirs(out_dir, exist_ok=True)
 
@@ -112,6 +120,11 @@ def main(argv=None):
     if args.reconstruct:
         from sph_project_amd.surface import SurfaceReconstructor
         recon = SurfaceReconstructor(container.dx)
+    renderer = None
+    if output_frames:   # run_simulation.py:70-108: the window's camera, light, particle radius dx and domain box
+        from sph_project_amd.render import FrameRenderer, write_png
+        renderer = FrameRenderer(container.dx, width=args.render_size[0], height=args.render_size[1],
+                                 camera_position=args.camera_position, camera_lookat=args.camera_lookat, fov=args.camera_fov)
     cnt = 0
     limit = total_rounds if args.max_steps is None else min(total_rounds, args.max_steps)
     limit = max(limit, 1)   # the reference's loop steps once before it looks at the round count
@@ -120,7 +133,7 @@ def main(argv=None):
     while cnt < limit:
         # run_simulation.py:126-153 steps once, writes a frame if the count of steps BEFORE this one is a multiple of the
         # interval, then counts.  Same frames here, but the steps between two frames go to the device in one call.
-        wants_frame = output_ply or output_obj
+        wants_frame = output_ply or output_obj or output_frames
         nxt = cnt if cnt % output_interval == 0 else cnt + output_interval - cnt % output_interval   # next count that gets a frame
         if not wants_frame or nxt >= limit:
             solver.advance(limit - cnt)
@@ -131,6 +144,10 @@ def main(argv=None):
         container.engine.synchronize()
         te = time.perf_counter()
         wrote = False
+        if output_frames:   # run_simulation.py:131-134
+            os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
+            write_png(f"{out_dir}/{cnt:06}/raw_view.png", renderer.from_container(container))
+            wrote = True
         if output_ply:
             os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
             for f_body_id in container.object_id_fluid_body:
