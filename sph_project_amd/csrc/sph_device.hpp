@@ -1054,10 +1054,24 @@ template <class P> constexpr bool pass_is_medium() {   // by record size, or opt
     return SPH_FAST && P::HAS_B && !pass_builds_masks<P>() &&
            (pass_slot_bytes<P>() <= SPH_NBR_MEDIUM_BYTES || (PassMediumOk<P>::value && pass_slot_bytes<P>() <= 32));
 }
+// P::FIVE_WG: a heavy functor (wide record, big pair()) that fits the medium budget all the same -- a 32 KB tile and 5 workgroups per CU
+// (<= 96 VGPRs) -- without becoming medium (its staging batches and its one-neighbour-per-trip phase 2 stay the heavy ones): the
+// all-fluid, one-mass WCSPH force pass of the fast build (WcsphForcePass::FIVE_WG)
+template <class P, class = void> struct PassFiveWg { static constexpr bool value = false; };
+template <class P> struct PassFiveWg<P, decltype((void)P::FIVE_WG)> { static constexpr bool value = P::FIVE_WG; };
+// Its staging goes in batches of SPH_FIVE_WG_SB slots (3 spill at 96 VGPRs; 4 slots per thread are two round trips either way: 3 + 1 or 2 + 2).
+// Every slot counts for it (C2 in motion wants 850-930 per group: tools/analysis/tile_slots.py), so its tile keeps the NBR_PAD slots that a
+// mask-reusing pass never allocates, and the reserve is one LDS allocation granule (1280 B) instead of 1.5 KB: 912 slots = 31,784 B =
+// 25 granules, five of them fit the CU's 160 KB.  (936 slots = 32,552 B = 26 granules: the compiler still reports 5 waves per SIMD, the
+// hardware runs 4 workgroups -- measured, the pass was back at the parent's 118 us.)
+constexpr int SPH_FIVE_WG_SB = 2;
+constexpr int SPH_LDS_GRANULE = 1280;
 template <class P> constexpr int nbr_tile_cap() {
     const int per_slot = pass_slot_bytes<P>();
-    const int budget = pass_is_medium<P>() ? 32768 : SPH_NBR_HEAVY_BUDGET;   // a fifth / a quarter of the CU's 160 KB
-    const int slots = (budget - 9 * NBR_CS_PITCH * 2 - 1536) / per_slot - NBR_PAD;   // 1.5 KB for the small arrays and the allocation granule
+    const int budget = (pass_is_medium<P>() || PassFiveWg<P>::value) ? 32768 : SPH_NBR_HEAVY_BUDGET;   // a fifth / a quarter of the CU's 160 KB
+    const int pad = (PassFiveWg<P>::value && pass_reuses_masks<P>()) ? 0 : NBR_PAD;
+    const int reserve = PassFiveWg<P>::value ? SPH_LDS_GRANULE : 1536;
+    const int slots = (budget - 9 * NBR_CS_PITCH * 2 - reserve) / per_slot - pad;   // 1.5 KB for the small arrays and the allocation granule
     // the payload-free passes (16 B per slot) could hold far more than a group ever needs: SPH_NBR_LIGHT_CAP slots, so that their tile
     // leaves room for SPH_NBR_WAVES_LIGHT workgroups per CU (1280 slots = 23.7 KB: six; 1232 = 22.9 KB: seven)
     return slots > SPH_NBR_LIGHT_CAP ? SPH_NBR_LIGHT_CAP : slots / 8 * 8;
@@ -1128,7 +1142,8 @@ template <class P, int MASKMODE> constexpr int nbr_lds_bytes() {
 // Second launch bound = minimum waves per SIMD = workgroups per CU.  Default 4 (<= 128 VGPRs).  The payload-free functors
 // with a one- or two-word accumulator (density, rigid volume: 23.7 KB of LDS) run 5 (<= 96 VGPRs) in the fast build: with
 // the 4-candidate phase-1 chunks and without SLP packing they fit without spilling, and the density pass of C2 went
-// 141 -> 127 us (profiles/r02_ab_*.txt).  The functors with payload arrays are capped at 4 by their 33-38 KB tiles; the
+// 141 -> 127 us (profiles/r02_ab_*.txt).  The functors with payload arrays are capped at 4 by their 33-38 KB tiles (except the medium ones
+// and P::FIVE_WG: 5); the
 // strict build and the 5-float DFSPH density+alpha accumulator spill at 96 and stay at 4 (tools/check_spills.py gates).
 constexpr int SPH_NBR_WAVES_LIGHT = SPH_FAST ? 6 : 4;
 constexpr int SPH_NBR_WAVES_HEAVY = SPH_FAST ? 4 : 3;   // strict build (IEEE division / sqrt sequences): 3, i.e. <= 168 VGPRs, rather than spills
@@ -1136,7 +1151,7 @@ constexpr int SPH_NBR_WAVES_HEAVY = SPH_FAST ? 4 : 3;   // strict build (IEEE di
 template <class P, class = void> struct PassMaxWaves { static constexpr int value = 8; };
 template <class P> struct PassMaxWaves<P, decltype((void)P::MAX_WAVES)> { static constexpr int value = P::MAX_WAVES; };
 template <class P, int MASKMODE> constexpr int nbr_waves_per_simd() {
-    const int w = P::HAS_B ? (pass_is_medium<P>() ? 5 : SPH_NBR_WAVES_HEAVY) : (sizeof(typename P::Own) <= 8 ? SPH_NBR_WAVES_LIGHT : 4);
+    const int w = P::HAS_B ? ((pass_is_medium<P>() || PassFiveWg<P>::value) ? 5 : SPH_NBR_WAVES_HEAVY) : (sizeof(typename P::Own) <= 8 ? SPH_NBR_WAVES_LIGHT : 4);
     return w < PassMaxWaves<P>::value ? w : PassMaxWaves<P>::value;
 }
 // P::SPLIT3 launches: gridDim.y = 3 -> workgroup (b, y) walks group y; gridDim.y = 2 -> (b, 0) walks groups 0 and 1, (b, 1) group 2
@@ -1299,7 +1314,7 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
             }
             // stage the runs that fit; consecutive t -> consecutive j: coalesced.  SB slots per batch: all of them where the
             // registers allow it (the medium functors' 96-VGPR budget and the strict build's wide records do not).
-            constexpr int SB = pass_is_medium<P>() ? (NS > SPH_MEDIUM_SB ? SPH_MEDIUM_SB : NS)
+            constexpr int SB = pass_is_medium<P>() ? (NS > SPH_MEDIUM_SB ? SPH_MEDIUM_SB : NS) : PassFiveWg<P>::value ? SPH_FIVE_WG_SB
                                                    : ((P::HAS_B && sizeof(BT) >= 16) ? ((PassUsesJ0<P>::value || !SPH_FAST) ? 2 : (SPH_HEAVY_SB < NS ? SPH_HEAVY_SB : NS)) : NS);
             const int n0 = lo_[0] != INT_MIN ? ln_[0] : 0;
             const int n01 = n0 + (lo_[1] != INT_MIN ? ln_[1] : 0);

@@ -442,7 +442,7 @@ struct WcsphForcePass {
     static constexpr bool HAS_WRENCH = !AF;
     static constexpr int BLOCK = 256, GROUPS = 3;
     static constexpr bool USES_J = !AF;   // pair() looks at j only for rigid neighbours
-    static constexpr bool HAS_B = true, HAS_C = true;
+    static constexpr bool HAS_B = true;
     static constexpr bool COUNT_PAIRS = CNT;     // false: booked by the density pass that stored the masks this pass walks (DensityPass::stat_pairs)
     static constexpr int MAX_WAVES = CNT ? (SPH_FAST ? 4 : 3) : 8;   // (the rarely used counting instantiation takes its class's register budget, never less)
     // the pair loop holds 111-124 of 128 VGPRs: batches of 3 OR the pipeline.  Round 6: the pipeline (C2 -1.2 %, in motion -1.0 %:
@@ -450,6 +450,10 @@ struct WcsphForcePass {
     static constexpr bool MASK_PIPELINE = AF;
     static constexpr int PAIR_WEIGHT = 3;  // surface tension (:210) + viscosity (:232) + pressure (:136)
     static constexpr bool HAS_REDUCE = false;
+    // FIVE_WG (fast build, all fluid, one mass: the headline's instantiation): pair() never reads the candidate's mass, so the record drops it
+    // and carries p_j / rho_j^2 in A.w instead of a third LDS array -- 32 B per slot, a 32 KB tile, 5 workgroups per CU (nbr_waves_per_simd)
+    static constexpr bool FIVE_WG = SPH_FAST && AF && UM && !CNT;
+    static constexpr bool HAS_C = !FIVE_WG;
     typedef float4 BT;
     typedef float CT;
     struct Own {
@@ -483,6 +487,11 @@ struct WcsphForcePass {
         cj = fl ? ptm[j] : 0.0f;
         return make_float4(p.x, p.y, p.z, fl ? v.w : rho0 * p.w);
     }
+    __device__ float4 stage(const Consts &c, int j, BT &bj) const {   // FIVE_WG: A = (x, y, z, p_j / rho_j^2)
+        CT cj;
+        const float4 a = stage(c, j, bj, cj);
+        return make_float4(a.x, a.y, a.z, cj);
+    }
     __device__ bool begin(const Consts &c, int i, const float4 &pi, Own &o) const {
         // no early return: the loads below are unconditional, so that they go out together with the rest of the prologue
         // (k_nbr_pass calls begin() on a clamped index; the result is only used where it returns true)
@@ -504,6 +513,12 @@ struct WcsphForcePass {
         o.st_m = fdiv(c.st, v.w);
 #endif
         o.cvm = c.cv * ((v.w + v.w) * 0.5f); o.cstm = o.st_m * v.w;
+        if (FIVE_WG) {   // one mass in the scene: the three are the same in every lane (all lanes are here: begin() runs before any branch) --
+                         // SGPRs instead of three VGPRs that stay live through the pair loops (what 96 VGPRs took, with the staging batches of 2)
+            o.m = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(o.m)));
+            o.cvm = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(o.cvm)));
+            o.cstm = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(o.cstm)));
+        }
         o.sx = o.sy = o.sz = 0.0f;
         o.ax = o.ay = o.az = 0.0f;
         o.x = pi.x; o.y = pi.y; o.z = pi.z; o.m0 = rho0 * pi.w;
@@ -591,6 +606,10 @@ struct WcsphForcePass {
             }
         }
 #endif
+    }
+    __device__ void pair(const Consts &c, Own &o, float dx, float dy, float dz, float r2, const float4 &a, const BT &bj, int j) const {
+        static_assert(FIVE_WG, "A.w is the candidate's mass everywhere else");
+        pair(c, o, dx, dy, dz, r2, a, bj, a.w, j);   // (UM: pair() takes the mass from Own, never from A.w)
     }
     __device__ float finish(const Consts &c, int i, const float4 &pi, Own &o) const {
         // non-pressure update (:643 after :203-240)
