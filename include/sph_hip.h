@@ -359,7 +359,7 @@ int sph_write_obj_ascii(const char *path, const float *vertices, int64_t nv, con
 /* --- surface reconstruction: fluid particles -> triangle mesh --------------- */
 /* replaces `splashsurf reconstruct {ply} -o {obj} -r={radius} -l={smoothing_length} -c=0.5 -t=0.6 ... --normals=on` of
    surface_reconstruction.py:8 (run per frame and fluid object by surface_reconstruction.py:20-24).  Not splashsurf's algorithm: a
-   Shepard colour field and marching cubes, defined here and in DESIGN.md 14 (no mesh cleanup, no smoothing):
+   Shepard colour field and marching cubes, defined here and in DESIGN.md 14 (no mesh cleanup; smoothing: see DESIGN.md 16 below):
      h = 2 smoothing_length radius (support of the project's cubic spline), V_j = 1 / sum_k W(x_j - x_k) over the input set,
      phi(x) = sum_j V_j W(x - x_j), surface phi = iso, inside phi > iso; grid points at integer multiples of e = cube_size radius from
      the origin; bricks of B^3 points, B = ceil(h / e), evaluated where a particle lies in the 3x3x3 coarse cells around them (phi = 0
@@ -393,7 +393,8 @@ typedef struct {
     double ms_bricks;         /* active bricks */
     double ms_field;          /* phi (the hot pass) */
     double ms_mesh;           /* classify, count, scan, emit */
-    double ms_normals;
+    double ms_normals;        /* -grad phi at the emitted vertices; ~0 when mesh smoothing is on (the normals are then taken at the
+                                 smoothed positions, timed in SphSurfacePostStats.ms_normals) */
     double ms_total;          /* first event to last (host waits for the three counts included) */
 } SphSurfaceStats;
 
@@ -412,6 +413,50 @@ int sph_surface_mesh_size(SphSurface *s, int64_t *n_vertices, int64_t *n_triangl
    triangles i32[nt][3] */
 int sph_surface_download(SphSurface *s, float *vertices, float *normals_or_NULL, int32_t *triangles);
 int sph_surface_stats(SphSurface *s, SphSurfaceStats *out);
+
+/* --- surface post-processing: smoothing of the reconstructed mesh ------------------------------------------------ */
+/* replaces `--mesh-smoothing-weights=on --mesh-smoothing-iters=25 --normals=on --normals-smoothing-iters=10` of the splashsurf command in
+   surface_reconstruction.py:8.  Not splashsurf's code: the method is defined here and in DESIGN.md 16.  Off by default (all zero); when
+   mesh_smoothing_iters or normals_smoothing_iters is positive, every reconstruction that follows (both entry points above) runs, after
+   the emit pass and inside the same synchronous call:
+     N(i) = the vertices j != i that share a triangle with i, ascending, no duplicates;
+     with mesh_smoothing_weights: c_j = sum over particles k != j with |x_j - x_k| < h of (1 - |x_j - x_k|^2 / h^2),
+       w_i = min(1, max{c_j : |P_i - x_j| < h} / weights_normalization) (0 with no particle within h) at the unsmoothed positions;
+       else w_i = 1;
+     mesh_smoothing_iters Jacobi iterations P_i <- (1 - w_i) P_i + w_i (sum_{j in N(i), ascending} P_j) / |N(i)| (no neighbour: P_i stays);
+     normals on and mesh_smoothing_iters > 0: the normals are taken at the smoothed positions (SphSurfaceStats.ms_normals is then ~0);
+     normals_smoothing_iters iterations n_i <- s_i / |s_i|, s_i = n_i + sum_{j in N(i), ascending} n_j (|s_i| = 0: s_i stays).
+   Triangles are not touched.  The mesh stays a function of the particle set, bit for bit.  New device buffers count under
+   memory_cap_bytes (SPH_ERR_CAPACITY before they are allocated). */
+typedef struct {
+    int32_t mesh_smoothing_iters;    /* --mesh-smoothing-iters (reference: 25); 0: positions untouched */
+    int32_t mesh_smoothing_weights;  /* --mesh-smoothing-weights=on (1) */
+    double weights_normalization;    /* --mesh-smoothing-weights-normalization (13) */
+    int32_t normals_smoothing_iters; /* --normals-smoothing-iters (reference: 10); needs an object created with normals */
+    int32_t reserved;                /* 0 */
+} SphSurfacePostParams;
+
+typedef struct {
+    int64_t adjacency_entries;  /* sum of |N(i)| of the last reconstruction */
+    int32_t max_degree;         /* max |N(i)| */
+    int32_t reserved;
+    double ms_adjacency;        /* HIP events: slots, sort, scans, compaction (host read of the total included) */
+    double ms_weights;
+    double ms_smoothing;        /* all mesh_smoothing_iters iterations, float4 copies included */
+    double ms_normals;          /* -grad phi at the smoothed positions */
+    double ms_normal_smoothing;
+    double ms_total;
+} SphSurfacePostStats;
+
+/* applies to the reconstructions that follow.  SPH_ERR_INVALID: a negative iteration count, a normalization that is not positive and
+   finite (in f32 too), normal smoothing on an object created without normals. */
+int sph_surface_set_postprocess(SphSurface *s, const SphSurfacePostParams *params);
+/* zeros when the last reconstruction ran no post-processing */
+int sph_surface_post_stats(SphSurface *s, SphSurfacePostStats *out);
+/* the last reconstruction's N(i) as CSR, offsets i32[nv + 1], neighbours i32[offsets[nv]], and w_i f32[nv] (all 1 without
+   mesh_smoothing_weights or with mesh_smoothing_iters = 0); any may be NULL.  SPH_ERR_INVALID when that reconstruction ran no
+   post-processing. */
+int sph_surface_download_post(SphSurface *s, int32_t *offsets, int32_t *neighbours, float *weights);
 
 /* --- particle rendering: particles -> one RGB frame ------------------------------------------------------------- */
 /* replaces the GGUI frame of run_simulation.py:116-135 (scene.particles(x_vis_buffer, radius=dx, per_vertex_color=...), scene.lines of

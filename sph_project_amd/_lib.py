@@ -100,6 +100,21 @@ class SphSurfaceStats(C.Structure):
     ]
 
 
+class SphSurfacePostParams(C.Structure):
+    _fields_ = [
+        ("mesh_smoothing_iters", C.c_int32), ("mesh_smoothing_weights", C.c_int32), ("weights_normalization", C.c_double),
+        ("normals_smoothing_iters", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class SphSurfacePostStats(C.Structure):
+    _fields_ = [
+        ("adjacency_entries", C.c_int64), ("max_degree", C.c_int32), ("reserved", C.c_int32), ("ms_adjacency", C.c_double),
+        ("ms_weights", C.c_double), ("ms_smoothing", C.c_double), ("ms_normals", C.c_double), ("ms_normal_smoothing", C.c_double),
+        ("ms_total", C.c_double),
+    ]
+
+
 class SphRenderParams(C.Structure):
     _fields_ = [
         ("width", C.c_int32), ("height", C.c_int32), ("eye", C.c_double * 3), ("target", C.c_double * 3), ("up", C.c_double * 3),
@@ -177,6 +192,9 @@ _SIGNATURES = [
     ("sph_surface_mesh_size", C.c_int, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("sph_surface_download", C.c_int, [_VP, _VP, _VP, _VP]),
     ("sph_surface_stats", C.c_int, [_VP, C.POINTER(SphSurfaceStats)]),
+    ("sph_surface_set_postprocess", C.c_int, [_VP, C.POINTER(SphSurfacePostParams)]),
+    ("sph_surface_post_stats", C.c_int, [_VP, C.POINTER(SphSurfacePostStats)]),
+    ("sph_surface_download_post", C.c_int, [_VP, _VP, _VP, _VP]),
     ("sph_render_create", C.c_int, [C.POINTER(SphRenderParams), C.POINTER(_VP)]),
     ("sph_render_destroy", None, [_VP]),
     ("sph_render_last_error", C.c_char_p, [_VP]),

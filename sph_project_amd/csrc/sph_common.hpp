@@ -212,6 +212,20 @@ struct SurfDev {
     int *scan_tmp;                     // tile sums of surf_scan
     hipStream_t stream;
 };
+// Surface post-processing (sph_surface_post.hpp): the mesh sizes and the buffers of the stage
+struct SurfPost {
+    int nv, nt;
+    const int *tri;      // [nt * 3]
+    int *raw;            // [nv + 1] 2 x incident triangles -> exclusive scan: a vertex's slot range
+    int *cnt;            // [nv + 1] fill counters, then unique counts -> exclusive scan: the CSR offsets (off)
+    int *slot;           // [6 nt] neighbour slots, sorted and deduplicated in place per vertex
+    int *adj;            // [E] CSR neighbours
+    int *maxdeg;         // [1]
+    float *pc;           // [n] c_j per binned particle
+    float *w;            // [nv] smoothing weight per vertex (null: 1)
+    float norm;          // weights normalization
+    float4 *a, *b;       // [nv] working copies (ping-pong)
+};
 
 // Particle rendering (sph_render.hpp): camera, shading constants, the particle source and the frame buffers of one
 // SphRender.  Source: pos[i] (xyz), id[i], colour col_home[id[i]] when col_home is set, else col[i] (r | g << 8 | b << 16; both null:
@@ -462,6 +476,12 @@ struct Launch {
     void (*surf_count)(SurfDev &);              // classify cubes and edges, per-brick vertex / triangle counts and their scans
     void (*surf_emit)(SurfDev &);               // vertices and triangles
     void (*surf_normals)(SurfDev &, int nv);    // -grad phi / |grad phi| at every vertex
+    // surface post-processing (sph_surface_post.hpp)
+    void (*surf_post_adjacency)(SurfDev &, SurfPost &);           // slots, sort + dedup, scan of the unique counts (cnt[nv] = entries)
+    void (*surf_post_compact)(SurfDev &, SurfPost &);             // CSR neighbours into adj
+    void (*surf_post_weights)(SurfDev &, SurfPost &);             // c_j per particle, w_i per vertex
+    void (*surf_post_smooth)(SurfDev &, SurfPost &, int iters);   // Laplacian smoothing of d.vert
+    void (*surf_post_nsmooth)(SurfDev &, SurfPost &, int iters);  // normal smoothing of d.nrm
     // particle rendering (sph_render.hpp)
     void (*render_splat)(RenderDev &);          // depth keys of spheres (small per thread, large per workgroup) and box lines
     void (*render_shade)(RenderDev &);          // the winners' colours, then background / ids / covered count per pixel

@@ -454,6 +454,7 @@ void l_clear_fresh(State &s) {
 #include "sph_pbf.hpp"
 #include "sph_contact.hpp"
 #include "sph_surface.hpp"
+#include "sph_surface_post.hpp"
 #include "sph_render.hpp"
 #include "sph_halo_impl.hpp"
 }  // namespace SPH_NS
@@ -482,6 +483,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_pbf_launchers(L);
         register_contact_launchers(L);
         register_surface_launchers(L);
+        register_surface_post_launchers(L);
         register_render_launchers(L);
         L.halo_classify_pack = l_halo_classify_pack; L.halo_unpack_append = l_halo_unpack_append;
         L.halo_build_tables = l_halo_build_tables; L.halo_pack_fields = l_halo_pack_fields;

@@ -2,10 +2,13 @@
 // host reads (coarse bounds, active bricks, vertex / triangle totals) and the stage events.  Host code, included at the end of
 // sph_api.hip; the kernels are in sph_surface.hpp, the method in DESIGN.md 14.
 #pragma once
+#include <algorithm>
 #include <climits>
 
 enum SurfBufId { SB_XIN, SB_XTMP, SB_XS, SB_PCELL, SB_PSLOT, SB_CELL_START, SB_FLAG, SB_BRICK_ID, SB_BRICK_CELL, SB_PHI, SB_EDGE, SB_VBASE,
-                 SB_TBASE, SB_VERT, SB_NRM, SB_TRI, SB_SMALL, SB_SCAN, SB_COUNT_ };
+                 SB_TBASE, SB_VERT, SB_NRM, SB_TRI, SB_SMALL, SB_SCAN,
+                 // post-processing
+                 SB_ADJ_RAW, SB_ADJ_CNT, SB_ADJ_SLOT, SB_ADJ, SB_PCOUNT, SB_WEIGHT, SB_WORK_A, SB_WORK_B, SB_COUNT_ };
 
 struct SphSurface {
     SphSurfaceParams prm;
@@ -21,6 +24,12 @@ struct SphSurface {
     int64_t nv = 0, nt = 0;
     bool have_mesh = false;
     SphSurfaceStats stats{};
+    SphSurfacePostParams post{0, 0, 13.0, 0, 0};   // off
+    hipEvent_t pev[6] = {};
+    SurfPost p{};
+    bool have_post = false;   // the last reconstruction built the adjacency
+    bool have_weights = false;
+    SphSurfacePostStats post_stats{};
 };
 
 static int surf_fail(SphSurface *s, int code, const char *fmt, ...) {
@@ -93,6 +102,8 @@ extern "C" int sph_surface_create(const SphSurfaceParams *params, SphSurface **o
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; return surf_fail(nullptr, SPH_ERR_HIP, "sph_surface_create: stream"); }
     for (auto &e_ : s->ev)
         if (hipEventCreate(&e_) != hipSuccess) { sph_surface_destroy(s); return surf_fail(nullptr, SPH_ERR_HIP, "sph_surface_create: event"); }
+    for (auto &e_ : s->pev)
+        if (hipEventCreate(&e_) != hipSuccess) { sph_surface_destroy(s); return surf_fail(nullptr, SPH_ERR_HIP, "sph_surface_create: event"); }
     SurfDev &d = s->d;
     d.h = (float)h;
     d.h2 = (float)(h * h);
@@ -115,6 +126,7 @@ extern "C" void sph_surface_destroy(SphSurface *s) {
     if (s->stream) hipStreamSynchronize(s->stream);
     for (int k = 0; k < SB_COUNT_; ++k) if (s->buf[k]) hipFree(s->buf[k]);
     for (auto e_ : s->ev) if (e_) hipEventDestroy(e_);
+    for (auto e_ : s->pev) if (e_) hipEventDestroy(e_);
     if (s->stream) hipStreamDestroy(s->stream);
     delete s;
 }
@@ -123,6 +135,9 @@ extern "C" const char *sph_surface_last_error(SphSurface *s) { return s ? s->err
 
 static float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0.0f; hipEventElapsedTime(&ms, a, b); return ms; }
 
+static bool surf_post_on(const SphSurface *s) { return s->post.mesh_smoothing_iters > 0 || s->post.normals_smoothing_iters > 0; }
+static int surf_post(SphSurface *s, int nv, int nt);
+
 // the passes after the input is in xin[0, n) and ev[0] has been recorded before it was put there
 static int surf_run(SphSurface *s, int n) {
     SurfDev &d = s->d;
@@ -130,12 +145,14 @@ static int surf_run(SphSurface *s, int n) {
     d.n = n;
     d.nb = 0;
     d.cmin[0] = d.cmin[1] = d.cmin[2] = 0;
-    if (n == 0) {   // no particle: the empty mesh
+    if (n == 0) {   // no particle: the empty mesh (and, with the post stage on, its empty adjacency)
         SURFCHK(s, hipStreamSynchronize(st));
         s->have_mesh = true;
+        s->have_post = surf_post_on(s);
         s->stats.bytes_allocated = (int64_t)surf_total(s);
         return SPH_OK;
     }
+    // SB_SMALL, 16 int slots: [0, 7) bounds, [8] counter (compaction), [10, 12) pairs (u64), [12] largest degree (post-processing)
     SURF_ENSURE(s, SB_SMALL, 64, "counters");
     d.bounds = (int *)s->buf[SB_SMALL];
     d.counter = d.bounds + 8;
@@ -199,12 +216,14 @@ static int surf_run(SphSurface *s, int n) {
     d.vert = (float *)s->buf[SB_VERT]; d.tri = (int *)s->buf[SB_TRI]; d.nrm = s->prm.normals ? (float *)s->buf[SB_NRM] : nullptr;
     s->L->surf_emit(d);
     SURFCHK(s, hipEventRecord(s->ev[4], st));
-    if (s->prm.normals) s->L->surf_normals(d, tot[0]);
+    // (smoothed positions get their normals in the post stage: none here then, and ms_normals ~ 0)
+    if (s->prm.normals && !(surf_post_on(s) && s->post.mesh_smoothing_iters > 0)) s->L->surf_normals(d, tot[0]);
     SURFCHK(s, hipEventRecord(s->ev[5], st));
     unsigned long long pairs = 0;
     SURFCHK(s, hipMemcpyAsync(&pairs, d.pairs, sizeof(pairs), hipMemcpyDeviceToHost, st));
     SURFCHK(s, hipStreamSynchronize(st));
     SURFCHK(s, hipGetLastError());
+    if (surf_post_on(s)) { const int rc = surf_post(s, tot[0], tot[1]); if (rc) return rc; }
     s->nv = tot[0];
     s->nt = tot[1];
     s->have_mesh = true;
@@ -222,6 +241,8 @@ static void surf_begin(SphSurface *s) {
     for (bool &l : s->live) l = false;
     s->stats = SphSurfaceStats{};
     s->stats.B = s->d.B;
+    s->have_post = s->have_weights = false;
+    s->post_stats = SphSurfacePostStats{};
 }
 
 extern "C" int sph_surface_reconstruct(SphSurface *s, const float *xyz, int64_t n) {
@@ -283,5 +304,101 @@ extern "C" int sph_surface_download(SphSurface *s, float *vertices, float *norma
 extern "C" int sph_surface_stats(SphSurface *s, SphSurfaceStats *out) {
     if (!s || !out) return SPH_ERR_INVALID;
     *out = s->stats;
+    return SPH_OK;
+}
+
+// --- post-processing: after the emit pass, on the mesh and the binned particles of this reconstruction ------------------
+static int surf_post(SphSurface *s, int nv, int nt) {
+    SurfDev &d = s->d;
+    SurfPost &p = s->p;
+    hipStream_t st = s->stream;
+    const SphSurfacePostParams q = s->post;
+    const bool weights = q.mesh_smoothing_weights && q.mesh_smoothing_iters > 0;
+    // the slot ranges and CSR offsets are int and reach 6 nt (2 slots per triangle corner): refuse before anything is allocated or launched
+    if ((int64_t)6 * nt > (int64_t)INT_MAX)
+        return surf_fail(s, SPH_ERR_CAPACITY, "surface: %d triangles, more than 2^31 / 6 for the smoothing's adjacency", nt);
+    SURF_ENSURE(s, SB_ADJ_RAW, sizeof(int) * ((size_t)nv + 1), "adjacency");
+    SURF_ENSURE(s, SB_ADJ_CNT, sizeof(int) * ((size_t)nv + 1), "adjacency");
+    SURF_ENSURE(s, SB_ADJ_SLOT, sizeof(int) * 6 * (size_t)nt, "adjacency");
+    SURF_ENSURE(s, SB_WORK_A, sizeof(float4) * (size_t)nv, "smoothing");
+    SURF_ENSURE(s, SB_WORK_B, sizeof(float4) * (size_t)nv, "smoothing");
+    if (weights) {
+        SURF_ENSURE(s, SB_PCOUNT, sizeof(float) * (size_t)d.n, "smoothing weights");
+        SURF_ENSURE(s, SB_WEIGHT, sizeof(float) * (size_t)nv, "smoothing weights");
+    }
+    // surf_scan's tile sums: sized for the coarse grid so far, now for nv as well
+    SURF_ENSURE(s, SB_SCAN, std::max(s->bytes[SB_SCAN], sizeof(int) * ((size_t)nv / 1024 + 2)), "scan");
+    d.scan_tmp = (int *)s->buf[SB_SCAN];
+    p = SurfPost{};
+    p.nv = nv; p.nt = nt; p.tri = d.tri;
+    p.raw = (int *)s->buf[SB_ADJ_RAW]; p.cnt = (int *)s->buf[SB_ADJ_CNT]; p.slot = (int *)s->buf[SB_ADJ_SLOT];
+    p.maxdeg = d.bounds + 12;   // (SB_SMALL: see surf_run)
+    p.pc = weights ? (float *)s->buf[SB_PCOUNT] : nullptr;
+    p.w = weights ? (float *)s->buf[SB_WEIGHT] : nullptr;
+    p.norm = (float)q.weights_normalization;
+    p.a = (float4 *)s->buf[SB_WORK_A]; p.b = (float4 *)s->buf[SB_WORK_B];
+    SURFCHK(s, hipEventRecord(s->pev[0], st));
+    s->L->surf_post_adjacency(d, p);
+    int cnt[2] = {0, 0};   // entries, largest degree
+    SURFCHK(s, hipMemcpyAsync(&cnt[0], p.cnt + nv, sizeof(int), hipMemcpyDeviceToHost, st));
+    SURFCHK(s, hipMemcpyAsync(&cnt[1], p.maxdeg, sizeof(int), hipMemcpyDeviceToHost, st));
+    SURFCHK(s, hipStreamSynchronize(st));
+    if (cnt[0] < 0 || (int64_t)cnt[0] > (int64_t)6 * nt) return surf_fail(s, SPH_ERR_INVALID, "surface: internal adjacency count %d", cnt[0]);
+    SURF_ENSURE(s, SB_ADJ, sizeof(int) * (size_t)cnt[0], "adjacency");
+    p.adj = (int *)s->buf[SB_ADJ];
+    s->L->surf_post_compact(d, p);
+    SURFCHK(s, hipEventRecord(s->pev[1], st));
+    if (weights) s->L->surf_post_weights(d, p);   // at the unsmoothed positions
+    SURFCHK(s, hipEventRecord(s->pev[2], st));
+    s->L->surf_post_smooth(d, p, q.mesh_smoothing_iters);
+    SURFCHK(s, hipEventRecord(s->pev[3], st));
+    if (s->prm.normals && q.mesh_smoothing_iters > 0) s->L->surf_normals(d, nv);   // -grad phi at the smoothed positions
+    SURFCHK(s, hipEventRecord(s->pev[4], st));
+    s->L->surf_post_nsmooth(d, p, q.normals_smoothing_iters);
+    SURFCHK(s, hipEventRecord(s->pev[5], st));
+    SURFCHK(s, hipStreamSynchronize(st));
+    SURFCHK(s, hipGetLastError());
+    s->have_post = true;
+    s->have_weights = weights;
+    SphSurfacePostStats &o = s->post_stats;
+    o.adjacency_entries = cnt[0]; o.max_degree = cnt[1];
+    o.ms_adjacency = ev_ms(s->pev[0], s->pev[1]); o.ms_weights = ev_ms(s->pev[1], s->pev[2]); o.ms_smoothing = ev_ms(s->pev[2], s->pev[3]);
+    o.ms_normals = ev_ms(s->pev[3], s->pev[4]); o.ms_normal_smoothing = ev_ms(s->pev[4], s->pev[5]); o.ms_total = ev_ms(s->pev[0], s->pev[5]);
+    return SPH_OK;
+}
+
+extern "C" int sph_surface_set_postprocess(SphSurface *s, const SphSurfacePostParams *params) {
+    if (!s || !params) return SPH_ERR_INVALID;
+    const SphSurfacePostParams q = *params;
+    if (q.mesh_smoothing_iters < 0 || q.normals_smoothing_iters < 0)
+        return surf_fail(s, SPH_ERR_INVALID, "sph_surface_set_postprocess: negative iteration count");
+    if (!std::isfinite(q.weights_normalization) || !(q.weights_normalization > 0.0) || !std::isfinite((float)q.weights_normalization) ||
+        !((float)q.weights_normalization > 0.0f))
+        return surf_fail(s, SPH_ERR_INVALID, "sph_surface_set_postprocess: weights_normalization must be positive and finite");
+    if (q.normals_smoothing_iters > 0 && !s->prm.normals)
+        return surf_fail(s, SPH_ERR_INVALID, "sph_surface_set_postprocess: normal smoothing on an object created without normals");
+    s->post = q;
+    return SPH_OK;
+}
+
+extern "C" int sph_surface_post_stats(SphSurface *s, SphSurfacePostStats *out) {
+    if (!s || !out) return SPH_ERR_INVALID;
+    *out = s->post_stats;
+    return SPH_OK;
+}
+
+extern "C" int sph_surface_download_post(SphSurface *s, int32_t *offsets, int32_t *neighbours, float *weights) {
+    if (!s) return SPH_ERR_INVALID;
+    if (!s->have_mesh || !s->have_post)
+        return surf_fail(s, SPH_ERR_INVALID, "sph_surface_download_post: the last reconstruction ran no smoothing");
+    SURFCHK(s, hipSetDevice(s->device));
+    const size_t nv = (size_t)s->nv, ne = (size_t)s->post_stats.adjacency_entries;
+    if (offsets && nv) SURFCHK(s, hipMemcpy(offsets, s->p.cnt, sizeof(int) * (nv + 1), hipMemcpyDeviceToHost));
+    else if (offsets) offsets[0] = 0;
+    if (neighbours && ne) SURFCHK(s, hipMemcpy(neighbours, s->p.adj, sizeof(int) * ne, hipMemcpyDeviceToHost));
+    if (weights) {
+        if (s->have_weights) { if (nv) SURFCHK(s, hipMemcpy(weights, s->p.w, sizeof(float) * nv, hipMemcpyDeviceToHost)); }
+        else for (size_t i = 0; i < nv; ++i) weights[i] = 1.0f;
+    }
     return SPH_OK;
 }

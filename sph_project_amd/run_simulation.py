@@ -66,7 +66,7 @@ def read_ply_ascii(path):
     return data[:, [props.index(k) for k in ("x", "y", "z")]]
 
 
-def main(argv=None):
+def parse_args(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument("--scene_file", default="", help="scene file")
     parser.add_argument("--max_steps", type=int, default=None, help="stop early (not in the reference)")
@@ -76,6 +76,9 @@ def main(argv=None):
     parser.add_argument("--reconstruct", action="store_true",
                         help="with every PLY frame also write particle_object_{id}.obj: the fluid object's surface, reconstructed on the "
                              "GPU from the device state (surface_reconstruction.py's defaults; not in the reference)")
+    parser.add_argument("--mesh_smoothing_iters", type=int, default=0, help="with --reconstruct: Laplacian smoothing iterations (DESIGN.md 16)")
+    parser.add_argument("--mesh_smoothing_weights", action="store_true", help="with --reconstruct: keep isolated particles' meshes unsmoothed")
+    parser.add_argument("--normals_smoothing_iters", type=int, default=0, help="with --reconstruct: normal smoothing iterations")
     parser.add_argument("--render", action="store_true",
                         help="on scenes with exportFrame write {out}/{cnt:06}/raw_view.png at the reference's cadence, rendered on the GPU "
                              "from the device state (DESIGN.md 15; not GGUI's image)")
@@ -83,7 +86,19 @@ def main(argv=None):
     parser.add_argument("--camera_position", type=float, nargs=3, default=(5.5, 2.5, 4.0))
     parser.add_argument("--camera_lookat", type=float, nargs=3, default=(-1.0, 0.0, 0.0))
     parser.add_argument("--camera_fov", type=float, default=70.0, help="vertical, degrees")
-    args = parser.parse_args(argv)
+    return parser.parse_args(argv)
+
+
+def surface_postprocess(args):
+    """set_postprocess keywords of the smoothing flags (normalization 13), or None when none of them is set."""
+    if not (args.mesh_smoothing_iters or args.mesh_smoothing_weights or args.normals_smoothing_iters):
+        return None
+    return dict(mesh_smoothing_iters=args.mesh_smoothing_iters, mesh_smoothing_weights=bool(args.mesh_smoothing_weights),
+                weights_normalization=13.0, normals_smoothing_iters=args.normals_smoothing_iters)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     scene_path = args.scene_file
     config = SimConfig(scene_file_path=scene_path)
     scene_name = scene_path.split("/")[-1].split(".")[0]
@@ -120,6 +135,9 @@ def main(argv=None):
     if args.reconstruct:
         from sph_project_amd.surface import SurfaceReconstructor
         recon = SurfaceReconstructor(container.dx)
+        post = surface_postprocess(args)
+        if post is not None:
+            recon.set_postprocess(**post)
     renderer = None
     if output_frames:   # run_simulation.py:70-108: the window's camera, light, particle radius dx and domain box
         from sph_project_amd.render import FrameRenderer, write_png

@@ -84,6 +84,39 @@ class SurfaceReconstructor:
         self._chk(self.lib.sph_surface_stats(self.h, C.byref(st)), "sph_surface_stats")
         return {k: getattr(st, k) for k, _ in L.SphSurfaceStats._fields_ if k != "reserved"}
 
+    def set_postprocess(self, mesh_smoothing_iters=0, mesh_smoothing_weights=False, weights_normalization=13.0, normals_smoothing_iters=0):
+        """Smoothing of the reconstructions that follow (splashsurf's --mesh-smoothing-iters, --mesh-smoothing-weights,
+        --mesh-smoothing-weights-normalization, --normals-smoothing-iters).  All zero: off (the default)."""
+        p = L.SphSurfacePostParams(mesh_smoothing_iters=int(mesh_smoothing_iters), mesh_smoothing_weights=int(bool(mesh_smoothing_weights)),
+                                   weights_normalization=float(weights_normalization), normals_smoothing_iters=int(normals_smoothing_iters),
+                                   reserved=0)
+        self._chk(self.lib.sph_surface_set_postprocess(self.h, C.byref(p)), "sph_surface_set_postprocess")
+
+    def post_stats(self):
+        st = L.SphSurfacePostStats()
+        self._chk(self.lib.sph_surface_post_stats(self.h, C.byref(st)), "sph_surface_post_stats")
+        return {k: getattr(st, k) for k, _ in L.SphSurfacePostStats._fields_ if k != "reserved"}
+
+    def adjacency(self):
+        """(offsets i32[nv+1], neighbours i32[offsets[-1]]): the vertex adjacency (CSR) of the last reconstruction's smoothing."""
+        nv = self._post_size()
+        off = np.empty(nv + 1, np.int32)
+        self._chk(self.lib.sph_surface_download_post(self.h, off.ctypes.data, None, None), "sph_surface_download_post")
+        nb = np.empty(int(off[-1]), np.int32)
+        self._chk(self.lib.sph_surface_download_post(self.h, None, nb.ctypes.data, None), "sph_surface_download_post")
+        return off, nb
+
+    def smoothing_weights(self):
+        """w f32[nv] of the last reconstruction's smoothing (all 1 without mesh_smoothing_weights)."""
+        w = np.empty(self._post_size(), np.float32)
+        self._chk(self.lib.sph_surface_download_post(self.h, None, None, w.ctypes.data), "sph_surface_download_post")
+        return w
+
+    def _post_size(self):
+        nv, nt = C.c_int64(), C.c_int64()
+        self._chk(self.lib.sph_surface_mesh_size(self.h, C.byref(nv), C.byref(nt)), "sph_surface_mesh_size")
+        return nv.value
+
     def write_obj(self, path):
         """The last mesh as ASCII OBJ (write_obj below)."""
         if self.mesh is None:

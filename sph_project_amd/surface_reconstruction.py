@@ -4,6 +4,7 @@ it -> the .obj beside it (ply_path.replace(".ply", ".obj")).  The reference runs
 here one GPU reconstructs the frames in order (sph_project_amd/surface.py), so --num_workers is accepted and ignored.
 
     python sph_project_amd/surface_reconstruction.py --input_dir final_scene0_output --radius 0.01 [--smoothing-length 3.5]
+        [--mesh-smoothing-weights=on --mesh-smoothing-iters=25 --normals-smoothing-iters=10]
 """
 import argparse
 import os
@@ -23,7 +24,22 @@ def parse_args(argv=None):
     parser.add_argument("--cube-size", type=float, default=0.5, help="splashsurf -c (multiples of the radius)")
     parser.add_argument("--surface-threshold", type=float, default=0.6, help="splashsurf -t")
     parser.add_argument("--no-normals", action="store_true", help="no vn lines (splashsurf --normals=off)")
+    # splashsurf's post-processing; the reference's command: 25 / on / 10.  Not given: no smoothing
+    parser.add_argument("--mesh-smoothing-iters", type=int, default=None)
+    parser.add_argument("--mesh-smoothing-weights", choices=["on", "off"], default=None)
+    parser.add_argument("--mesh-smoothing-weights-normalization", type=float, default=None)
+    parser.add_argument("--normals-smoothing-iters", type=int, default=None)
     return parser.parse_args(argv)
+
+
+def postprocess_settings(args):
+    """set_postprocess keywords of the smoothing flags, or None when none of them was given."""
+    given = (args.mesh_smoothing_iters, args.mesh_smoothing_weights, args.mesh_smoothing_weights_normalization, args.normals_smoothing_iters)
+    if all(g is None for g in given):
+        return None
+    return dict(mesh_smoothing_iters=args.mesh_smoothing_iters or 0, mesh_smoothing_weights=args.mesh_smoothing_weights == "on",
+                weights_normalization=13.0 if args.mesh_smoothing_weights_normalization is None else args.mesh_smoothing_weights_normalization,
+                normals_smoothing_iters=args.normals_smoothing_iters or 0)
 
 
 def frame_jobs(input_dir):
@@ -45,6 +61,9 @@ def main(argv=None):
     from sph_project_amd.surface import SurfaceReconstructor
     recon = SurfaceReconstructor(args.radius, smoothing_length=args.smoothing_length, cube_size=args.cube_size,
                                  iso=args.surface_threshold, normals=not args.no_normals)
+    post = postprocess_settings(args)
+    if post is not None:
+        recon.set_postprocess(**post)
     for ply_path, obj_path in jobs:
         try:
             recon.from_points(read_ply_ascii(ply_path))

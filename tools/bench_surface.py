@@ -3,7 +3,11 @@ in-motion steps of the bench line (bench.py --motion-step, 2500).  Per state: on
 the live handle (sph_surface_reconstruct_object, synchronous).  Reports the stage times from HIP events, the host clock around the call,
 bricks / points / pair tests / triangles, pair tests per second and the field pass's share of FP32 VALU peak from counted operations:
 8 FLOP per candidate test (3 sub, 3 mul, 2 add of the distance test; accepted pairs add W on top, so this is a lower bound) against
-157.3 TFLOPS.  One JSON line per state."""
+157.3 TFLOPS.  One JSON line per state.
+
+--postprocess adds the reference's smoothing (25 iterations with weights, 10 normal iterations) to every frame and
+reports its stage times, adjacency size and the smoothing iterations' algorithmic bytes per second: per iteration and vertex, the offsets,
+the weight, its own float4 read and write, and per neighbour an index and a float4."""
 import argparse
 import json
 import os
@@ -20,10 +24,10 @@ PEAK_FP32 = 157.3e12
 FLOP_PER_TEST = 8
 
 
-def measure(r, container, obj, frames, label, step):
+def measure(r, container, obj, frames, label, step, post=None):
     lib, eng = r.lib, container.engine
     r.from_container(container, obj)   # untimed: allocations, first touch
-    host, stats = [], []
+    host, stats, posts = [], [], []
     for _ in range(frames):
         eng.synchronize()
         t0 = time.perf_counter()
@@ -31,7 +35,8 @@ def measure(r, container, obj, frames, label, step):
         host.append(1e3 * (time.perf_counter() - t0))
         assert rc == 0, rc
         stats.append(r.stats())
-    best = min(range(frames), key=lambda k: stats[k]["ms_total"])
+        posts.append(r.post_stats() if post else None)
+    best = min(range(frames), key=lambda k: stats[k]["ms_total"] + (posts[k]["ms_total"] if post else 0.0))
     st = stats[best]
     field_s = 1e-3 * st["ms_field"]
     out = dict(state=label, step=step, particles=st["particles"], frames=frames, B=st["B"],
@@ -44,6 +49,17 @@ def measure(r, container, obj, frames, label, step):
                pair_tests_per_s=st["pair_tests"] / field_s if field_s > 0 else 0.0,
                field_fp32_valu_share=FLOP_PER_TEST * st["pair_tests"] / field_s / PEAK_FP32 if field_s > 0 else 0.0,
                identical_frames=all(s["triangles"] == st["triangles"] and s["vertices"] == st["vertices"] for s in stats))
+    if post:
+        ps = posts[best]
+        nv, ne = st["vertices"], ps["adjacency_entries"]
+        iter_bytes = nv * (4 + 4 + 16 + 16) + ne * (4 + 16)
+        sm_s = 1e-3 * ps["ms_smoothing"]
+        out.update(post=post, ms_post_total=round(ps["ms_total"], 3), ms_adjacency=round(ps["ms_adjacency"], 3),
+                   ms_weights=round(ps["ms_weights"], 3), ms_smoothing=round(ps["ms_smoothing"], 3),
+                   ms_post_normals=round(ps["ms_normals"], 3), ms_normal_smoothing=round(ps["ms_normal_smoothing"], 3),
+                   adjacency_entries=ne, max_degree=ps["max_degree"], smoothing_bytes_per_iter=iter_bytes,
+                   smoothing_bytes_per_s=iter_bytes * post["mesh_smoothing_iters"] / sm_s if sm_s > 0 else 0.0,
+                   ms_post_total_median=round(sorted(p["ms_total"] for p in posts)[frames // 2], 3))
     print(json.dumps(out), flush=True)
     return out
 
@@ -53,16 +69,21 @@ def main():
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--motion-step", type=int, default=2500, help="0: from rest only")
     ap.add_argument("--fast-math", action="store_true")
+    ap.add_argument("--postprocess", action="store_true", help="the reference's smoothing: 25 iterations, weights on, 10 normal iterations")
     a = ap.parse_args()
     container, solver = P.build_product(P.c2_scene())
     solver.prepare()
     (obj,) = tuple(container.object_id_fluid_body)
     r = SurfaceReconstructor(container.dx, fast_math=a.fast_math)
-    measure(r, container, obj, a.frames, "rest", 0)
+    post = None
+    if a.postprocess:
+        post = dict(mesh_smoothing_iters=25, mesh_smoothing_weights=True, weights_normalization=13.0, normals_smoothing_iters=10)
+        r.set_postprocess(**post)
+    measure(r, container, obj, a.frames, "rest", 0, post)
     if a.motion_step > 0:
         container.engine.step(a.motion_step)
         container.engine.synchronize()
-        measure(r, container, obj, a.frames, "in_motion", a.motion_step)
+        measure(r, container, obj, a.frames, "in_motion", a.motion_step, post)
 
 
 if __name__ == "__main__":
