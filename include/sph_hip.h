@@ -516,6 +516,50 @@ int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mask);
 int sph_render_download(SphRender *r, uint8_t *rgb, int32_t *ids_or_NULL);
 int sph_render_stats(SphRender *r, SphRenderStats *out);
 
+/* --- mesh rendering: an ordered list of triangle meshes -> one RGB frame ------------------------------------------ */
+/* stands in for the reference's render.py + rendering_script.py (every .obj of a frame directory through a Blender scene ->
+   {frame}/render.png).  Not Blender's path tracer: Lambert-shaded triangles, the camera, light, ambient, background, box lines and 8-bit
+   rounding of the particle image above, one colour per mesh.  A frame: sph_render_mesh_begin, one sph_render_mesh_add /
+   _add_surface per mesh, sph_render_mesh_end (draws; synchronous), then sph_render_download.  Triangles are numbered globally in list
+   order (mesh 0's first); their total stays below 0xFFFFFFF0, the vertices' below 2^31.
+   Hit of pixel ray d (f.d = 1) on triangle A B C, a = A - E, b = B - E, c = C - E: the edge functions d.(b x c), d.(c x a), d.(a x b) are
+   all >= 0 or all <= 0 (no back-face culling), N = (B - A) x (C - A) is finite and non-zero, and t = (a.N) / (d.N) is finite and
+   > z_near.  Each edge function is evaluated from the edge's two vertices in one canonical order, so the two triangles of a shared edge
+   get the same bits for it (in both builds): no pixel centre falls between them.  Winner: the smallest (float_bits(t) << 32 | global
+   triangle index); box lines take part with their keys as above.  Colour at P = E + t d: n = N / |N| for a mesh without normals, else the
+   normalised blend of the three vertex normals weighted by the edge functions (the flat normal when the blend is zero or non-finite);
+   n = -n if n.d > 0 (two-sided); col/255 (ambient + max(n.L, 0) light_rgb), clamped, floor(255 x + 0.5).  Skipped and counted: triangles
+   with a non-finite vertex, with N = 0, or with an index outside [0, nv) -- the last makes sph_render_mesh_end return SPH_ERR_INVALID
+   after the frame is drawn (nothing is read out of bounds; the frame can be downloaded).  SphRenderParams.radius is unused.
+   sph_render_points / _handle are unchanged: a particle frame and a mesh frame are separate frames of one renderer. */
+typedef struct {
+    int64_t meshes, triangles, vertices;  /* of the list */
+    int64_t large;              /* triangles whose screen bounds exceed 4096 pixels (one workgroup each) */
+    int64_t skipped_nonfinite;  /* a non-finite vertex (or plane): not drawn */
+    int64_t skipped_degenerate; /* N = 0: not drawn */
+    int64_t bad_index;          /* an index outside [0, nv): not drawn, SPH_ERR_INVALID from sph_render_mesh_end */
+    int64_t atomics;            /* 64-bit atomicMin issued by the depth pass (after the plain load said the key would drop) */
+    int64_t covered_pixels;     /* pixels won by a triangle */
+    int64_t hit;                /* triangles that passed the hit test at one pixel centre at least */
+    double ms_depth;            /* HIP events: triangles (small, large) and box lines */
+    double ms_shade;            /* the winners' colours */
+    double ms_finish;           /* background and id image */
+    double ms_total;            /* mesh table upload and clear of the keys included */
+} SphRenderMeshStats;
+
+/* SPH_ERR_INVALID: add / end without begin, negative counts, NULL arrays with non-zero counts, NULL rgb, too many triangles or vertices */
+int sph_render_mesh_begin(SphRender *r);
+/* host arrays: vertices f32[nv][3], normals_or_NULL f32[nv][3] (NULL: flat shading), triangles i32[nt][3] (0-based, local to this mesh) */
+int sph_render_mesh_add(SphRender *r, const float *vertices, const float *normals_or_NULL, const int32_t *triangles, int64_t nv, int64_t nt,
+                        const uint8_t rgb[3]);
+/* the last mesh of a surface object (post-processed positions and normals when that stage is on), copied device to device; the
+   surface object is left untouched and must be on the renderer's device */
+int sph_render_mesh_add_surface(SphRender *r, SphSurface *s, const uint8_t rgb[3]);
+/* draws the list; then sph_render_download: the id image holds the global triangle index (exact below 2^31 triangles), -1 background,
+   -2 - edge a box line */
+int sph_render_mesh_end(SphRender *r);
+int sph_render_mesh_stats(SphRender *r, SphRenderMeshStats *out);
+
 #ifdef __cplusplus
 }
 #endif

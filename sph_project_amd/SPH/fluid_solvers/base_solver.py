@@ -72,12 +72,22 @@ class BaseSolver:
         follows its pose, so that run_simulation.py can write mesh_object_{id}.obj."""
         if not self.cfg.get_cfg("exportObj"):
             return
-        for oid, b in self.rigid_solver.bodies.items():
-            obj = self.container.object_collection.get(oid)
-            if not isinstance(obj, dict) or "mesh" not in obj:
-                continue
-            rest = np.asarray(obj["restPosition"], dtype=np.float64) - np.asarray(obj["restCenterOfMass"], dtype=np.float64)
-            obj["mesh"].vertices = (b.rot @ rest.T).T + b.com
+        for oid in self.rigid_solver.bodies:
+            posed = self.posed_mesh_vertices(oid)
+            if posed is not None:
+                self.container.object_collection[oid]["mesh"].vertices = posed
+
+    def posed_mesh_vertices(self, oid):
+        """f64[nv, 3]: the mesh vertices of rigid body oid at its current pose (rest shape about the rest centre of mass, turned and
+        moved by the body's state); the mesh as loaded for a body the rigid solver does not move; None for a body without a mesh."""
+        obj = self.container.object_collection.get(oid)
+        if not isinstance(obj, dict) or "mesh" not in obj:
+            return None
+        b = self.rigid_solver.bodies.get(oid)
+        if b is None:
+            return np.asarray(obj["mesh"].vertices, dtype=np.float64)
+        rest = np.asarray(obj["restPosition"], dtype=np.float64) - np.asarray(obj["restCenterOfMass"], dtype=np.float64)
+        return (b.rot @ rest.T).T + b.com
 
     def _host_acts_inside_a_step(self):
         """A dynamic rigid body to integrate or an object still waiting for its entryTime: the host has to act in the middle

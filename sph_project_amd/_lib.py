@@ -133,6 +133,15 @@ class SphRenderStats(C.Structure):
     ]
 
 
+class SphRenderMeshStats(C.Structure):
+    _fields_ = [
+        ("meshes", C.c_int64), ("triangles", C.c_int64), ("vertices", C.c_int64), ("large", C.c_int64),
+        ("skipped_nonfinite", C.c_int64), ("skipped_degenerate", C.c_int64), ("bad_index", C.c_int64), ("atomics", C.c_int64),
+        ("covered_pixels", C.c_int64), ("hit", C.c_int64),
+        ("ms_depth", C.c_double), ("ms_shade", C.c_double), ("ms_finish", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class SphError(RuntimeError):
     pass
 
@@ -202,6 +211,11 @@ _SIGNATURES = [
     ("sph_render_handle", C.c_int, [_VP, _VP, C.c_uint32]),
     ("sph_render_download", C.c_int, [_VP, _VP, _VP]),
     ("sph_render_stats", C.c_int, [_VP, C.POINTER(SphRenderStats)]),
+    ("sph_render_mesh_begin", C.c_int, [_VP]),
+    ("sph_render_mesh_add", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP]),
+    ("sph_render_mesh_add_surface", C.c_int, [_VP, _VP, _VP]),
+    ("sph_render_mesh_end", C.c_int, [_VP]),
+    ("sph_render_mesh_stats", C.c_int, [_VP, C.POINTER(SphRenderMeshStats)]),
     ("sph_comm_allreduce", C.c_int, [_VP, C.POINTER(C.c_double), C.c_int, C.c_int]),
     ("sph_comm_barrier", C.c_int, [_VP]),
     ("sph_comm_selftest", C.c_int, [_VP, C.c_int]),

@@ -255,6 +255,20 @@ struct RenderDev {
     hipStream_t stream;
 };
 
+// Mesh rendering (sph_render_mesh.hpp): the frame's meshes, concatenated.  Triangle g of the frame belongs to the last
+// record with t0 <= g; its indices are local to that mesh's nv vertices, which start at slot v0 of vert / nrm.  The frame buffers,
+// camera and counters are the RenderDev's: cnt[0] triangles that passed the hit test at some pixel centre (whether or not they won it), [1] non-finite, [2] large,
+// [3] atomics issued, [4] covered pixels, [5] zero-area, [6] with an index outside [0, nv).
+struct MeshRec { long long t0, v0; int nv; unsigned col; int smooth, pad; };
+struct MeshDev {
+    int nm;                            // meshes
+    long long nt;                      // triangles of all meshes
+    const MeshRec *rec;                // [nm]
+    const float *vert, *nrm;           // [3 x vertices of all meshes] (nrm: read for the meshes with smooth = 1 only)
+    const int *tri;                    // [3 nt]
+    unsigned *large;                   // [nt] triangles whose screen bounds exceed RENDER_LARGE_PX pixels
+};
+
 template <class T> struct DBuf {
     T *b[2] = {nullptr, nullptr};
     int c = 0;
@@ -485,6 +499,10 @@ struct Launch {
     // particle rendering (sph_render.hpp)
     void (*render_splat)(RenderDev &);          // depth keys of spheres (small per thread, large per workgroup) and box lines
     void (*render_shade)(RenderDev &);          // the winners' colours, then background / ids / covered count per pixel
+    // mesh rendering (sph_render_mesh.hpp)
+    void (*render_mesh_depth)(RenderDev &, MeshDev &);   // depth keys of triangles (small per thread, large per workgroup) and box lines
+    void (*render_mesh_shade)(RenderDev &, MeshDev &);   // the winners' colours (triangles, lines)
+    void (*render_mesh_finish)(RenderDev &);             // background / ids / covered count per pixel
     void (*layer_hist)(State &, int *hist);      // owned particles per global cell layer
     void (*loop_criterion)(State &, int slot);   // stop test on an all-reduced residual (sharded solver loops)
     // push transport: the step message is written by halo_classify_pack itself; then

@@ -485,6 +485,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_surface_launchers(L);
         register_surface_post_launchers(L);
         register_render_launchers(L);
+        register_render_mesh_launchers(L);
         L.halo_classify_pack = l_halo_classify_pack; L.halo_unpack_append = l_halo_unpack_append;
         L.halo_build_tables = l_halo_build_tables; L.halo_pack_fields = l_halo_pack_fields;
         L.halo_unpack_fields = l_halo_unpack_fields;

@@ -260,3 +260,5 @@ static void register_render_launchers(Launch &L) {
     L.render_splat = l_render_splat;
     L.render_shade = l_render_shade;
 }
+
+#include "sph_render_mesh.hpp"

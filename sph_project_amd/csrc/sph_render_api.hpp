@@ -22,6 +22,14 @@ struct SphRender {
     size_t cap_pts = 0, cap_large = 0;
     bool have_frame = false;
     SphRenderStats stats{};
+    // mesh frames: the list between mesh_begin and mesh_end, concatenated on the device
+    bool mesh_open = false;
+    std::vector<MeshRec> mesh_rec;
+    int64_t mesh_nv = 0, mesh_nt = 0;
+    void *mvert = nullptr, *mnrm = nullptr, *mtri = nullptr, *mrec = nullptr;
+    size_t cap_mvert = 0, cap_mnrm = 0, cap_mtri = 0, cap_mrec = 0;   // bytes
+    hipEvent_t mev[5] = {};
+    SphRenderMeshStats mstats{};
 };
 
 static int rend_fail(SphRender *r, int code, const char *fmt, ...) {
@@ -163,9 +171,11 @@ extern "C" void sph_render_destroy(SphRender *r) {
     if (!r) return;
     hipSetDevice(r->device);
     if (r->stream) hipStreamSynchronize(r->stream);
-    for (void *b : {(void *)r->key, (void *)r->rgb, (void *)r->ids, (void *)r->cnt, (void *)r->pos, (void *)r->idv, (void *)r->large, (void *)r->col})
+    for (void *b : {(void *)r->key, (void *)r->rgb, (void *)r->ids, (void *)r->cnt, (void *)r->pos, (void *)r->idv, (void *)r->large, (void *)r->col,
+                    r->mvert, r->mnrm, r->mtri, r->mrec})
         if (b) hipFree(b);
     for (auto e_ : r->ev) if (e_) hipEventDestroy(e_);
+    for (auto e_ : r->mev) if (e_) hipEventDestroy(e_);
     if (r->stream) hipStreamDestroy(r->stream);
     delete r;
 }
@@ -279,5 +289,146 @@ extern "C" int sph_render_download(SphRender *r, uint8_t *rgb, int32_t *ids_or_N
 extern "C" int sph_render_stats(SphRender *r, SphRenderStats *out) {
     if (!r || !out) return SPH_ERR_INVALID;
     *out = r->stats;
+    return SPH_OK;
+}
+
+// --- mesh frames: begin, add ..., end; the kernels are in sph_render_mesh.hpp ----------------------------------------------
+extern "C" int sph_render_mesh_begin(SphRender *r) {
+    if (!r) return SPH_ERR_INVALID;
+    r->mesh_open = true;
+    r->mesh_rec.clear();
+    r->mesh_nv = r->mesh_nt = 0;
+    return SPH_OK;
+}
+
+// room for `need` bytes in a list buffer whose first `used` bytes belong to earlier meshes of the frame (kept, as far as the buffer
+// reaches: the normals buffer is grown for smooth meshes only, so the slots of flat meshes before them may lie beyond its end -- they are
+// never read)
+static int rend_grow(SphRender *r, void **buf, size_t *cap, size_t used, size_t need) {
+    if (need <= *cap) return SPH_OK;
+    const size_t ncap = std::max(need, *cap + *cap / 2);
+    void *nb = nullptr;
+    RENDCHK(r, hipMalloc(&nb, ncap));
+    used = std::min(used, *cap);
+    if (*buf && used) {
+        hipError_t e_ = hipMemcpyAsync(nb, *buf, used, hipMemcpyDeviceToDevice, r->stream);
+        if (e_ == hipSuccess) e_ = hipStreamSynchronize(r->stream);
+        if (e_ != hipSuccess) { hipFree(nb); return rend_fail(r, SPH_ERR_HIP, "mesh list: copy failed: %s", hipGetErrorString(e_)); }
+    }
+    if (*buf) hipFree(*buf);
+    *buf = nb;
+    *cap = ncap;
+    return SPH_OK;
+}
+
+// checks of one added mesh and room for it; the caller then copies into slots [mesh_nv, +nv) and triangles [mesh_nt, +nt)
+static int rend_mesh_room(SphRender *r, const char *who, int64_t nv, int64_t nt, bool arrays_ok, bool normals, const uint8_t *rgb) {
+    if (!r) return SPH_ERR_INVALID;
+    if (!r->mesh_open) return rend_fail(r, SPH_ERR_INVALID, "%s: no sph_render_mesh_begin before it", who);
+    if (nv < 0 || nt < 0 || !arrays_ok || !rgb) return rend_fail(r, SPH_ERR_INVALID, "%s: bad mesh arrays (nv = %lld, nt = %lld)", who, (long long)nv, (long long)nt);
+    if (r->mesh_nv + nv > (int64_t)INT_MAX || r->mesh_nt + nt >= (int64_t)RENDER_LINE_ID0)
+        return rend_fail(r, SPH_ERR_INVALID, "%s: the frame would hold %lld vertices (at most 2^31 - 1) and %lld triangles (below 0xFFFFFFF0)", who,
+                         (long long)(r->mesh_nv + nv), (long long)(r->mesh_nt + nt));
+    RENDCHK(r, hipSetDevice(r->device));
+    int rc = rend_grow(r, &r->mvert, &r->cap_mvert, 12 * (size_t)r->mesh_nv, 12 * (size_t)(r->mesh_nv + nv));
+    if (!rc) rc = rend_grow(r, &r->mtri, &r->cap_mtri, 12 * (size_t)r->mesh_nt, 12 * (size_t)(r->mesh_nt + nt));
+    if (!rc && normals) rc = rend_grow(r, &r->mnrm, &r->cap_mnrm, 12 * (size_t)r->mesh_nv, 12 * (size_t)(r->mesh_nv + nv));
+    return rc;
+}
+
+static void rend_mesh_push(SphRender *r, int64_t nv, int64_t nt, bool normals, const uint8_t *rgb) {
+    MeshRec m{};
+    m.t0 = r->mesh_nt; m.v0 = r->mesh_nv; m.nv = (int)nv;
+    m.col = (unsigned)rgb[0] | (unsigned)rgb[1] << 8 | (unsigned)rgb[2] << 16;
+    m.smooth = normals ? 1 : 0;
+    r->mesh_rec.push_back(m);
+    r->mesh_nv += nv;
+    r->mesh_nt += nt;
+}
+
+static int rend_mesh_copy(SphRender *r, const void *vertices, const void *normals, const void *triangles, int64_t nv, int64_t nt, hipMemcpyKind kind) {
+    if (nv) RENDCHK(r, hipMemcpyAsync((char *)r->mvert + 12 * (size_t)r->mesh_nv, vertices, 12 * (size_t)nv, kind, r->stream));
+    if (nv && normals) RENDCHK(r, hipMemcpyAsync((char *)r->mnrm + 12 * (size_t)r->mesh_nv, normals, 12 * (size_t)nv, kind, r->stream));
+    if (nt) RENDCHK(r, hipMemcpyAsync((char *)r->mtri + 12 * (size_t)r->mesh_nt, triangles, 12 * (size_t)nt, kind, r->stream));
+    RENDCHK(r, hipStreamSynchronize(r->stream));   // the caller's arrays are free again
+    return SPH_OK;
+}
+
+extern "C" int sph_render_mesh_add(SphRender *r, const float *vertices, const float *normals_or_NULL, const int32_t *triangles, int64_t nv,
+                                   int64_t nt, const uint8_t rgb[3]) {
+    const bool normals = normals_or_NULL != nullptr && nv > 0;
+    int rc = rend_mesh_room(r, "sph_render_mesh_add", nv, nt, (nv == 0 || vertices) && (nt == 0 || triangles), normals, rgb);
+    if (rc) return rc;
+    rc = rend_mesh_copy(r, vertices, normals ? normals_or_NULL : nullptr, triangles, nv, nt, hipMemcpyHostToDevice);
+    if (rc) return rc;
+    rend_mesh_push(r, nv, nt, normals, rgb);
+    return SPH_OK;
+}
+
+extern "C" int sph_render_mesh_add_surface(SphRender *r, SphSurface *s, const uint8_t rgb[3]) {
+    if (!r || !s) return SPH_ERR_INVALID;
+    if (!r->mesh_open) return rend_fail(r, SPH_ERR_INVALID, "sph_render_mesh_add_surface: no sph_render_mesh_begin before it");
+    if (!s->have_mesh) return rend_fail(r, SPH_ERR_INVALID, "sph_render_mesh_add_surface: the surface object holds no mesh");
+    if (s->device != r->device) return rend_fail(r, SPH_ERR_INVALID, "sph_render_mesh_add_surface: surface on device %d, renderer on %d", s->device, r->device);
+    const int64_t nv = s->nv, nt = s->nt;
+    const bool normals = s->prm.normals && s->d.nrm && nv > 0;
+    int rc = rend_mesh_room(r, "sph_render_mesh_add_surface", nv, nt, true, normals, rgb);
+    if (rc) return rc;
+    RENDCHK(r, hipStreamSynchronize(s->stream));   // (the surface calls are synchronous: its mesh is complete)
+    rc = rend_mesh_copy(r, s->d.vert, normals ? s->d.nrm : nullptr, s->d.tri, nv, nt, hipMemcpyDeviceToDevice);
+    if (rc) return rc;
+    rend_mesh_push(r, nv, nt, normals, rgb);
+    return SPH_OK;
+}
+
+extern "C" int sph_render_mesh_end(SphRender *r) {
+    if (!r) return SPH_ERR_INVALID;
+    if (!r->mesh_open) return rend_fail(r, SPH_ERR_INVALID, "sph_render_mesh_end: no sph_render_mesh_begin before it");
+    r->mesh_open = false;
+    RENDCHK(r, hipSetDevice(r->device));
+    r->have_frame = false;
+    r->stats = SphRenderStats{};
+    r->mstats = SphRenderMeshStats{};
+    for (auto &ev_ : r->mev) if (!ev_) RENDCHK(r, hipEventCreate(&ev_));
+    const size_t nm = r->mesh_rec.size();
+    { int rc = rend_room(r, (size_t)r->mesh_nt, false); if (rc) return rc; }
+    { int rc = rend_grow(r, &r->mrec, &r->cap_mrec, 0, sizeof(MeshRec) * std::max<size_t>(nm, 1)); if (rc) return rc; }
+    RenderDev &d = r->d;
+    MeshDev m{};
+    m.nm = (int)nm; m.nt = r->mesh_nt;
+    m.rec = (const MeshRec *)r->mrec; m.vert = (const float *)r->mvert; m.nrm = (const float *)r->mnrm; m.tri = (const int *)r->mtri;
+    m.large = (unsigned *)r->large;
+    d.n = 0; d.pos = nullptr; d.meta = nullptr; d.id = nullptr; d.col = nullptr; d.col_home = nullptr; d.large = r->large;
+    RENDCHK(r, hipEventRecord(r->mev[0], r->stream));
+    if (nm) RENDCHK(r, hipMemcpyAsync(r->mrec, r->mesh_rec.data(), sizeof(MeshRec) * nm, hipMemcpyHostToDevice, r->stream));
+    RENDCHK(r, hipMemsetAsync(r->key, 0xff, (size_t)d.W * d.H * 8, r->stream));
+    RENDCHK(r, hipMemsetAsync(r->cnt, 0, 64, r->stream));
+    RENDCHK(r, hipEventRecord(r->mev[1], r->stream));
+    r->L->render_mesh_depth(d, m);
+    RENDCHK(r, hipEventRecord(r->mev[2], r->stream));
+    r->L->render_mesh_shade(d, m);
+    RENDCHK(r, hipEventRecord(r->mev[3], r->stream));
+    r->L->render_mesh_finish(d);
+    RENDCHK(r, hipEventRecord(r->mev[4], r->stream));
+    unsigned long long c[8];
+    RENDCHK(r, hipMemcpyAsync(c, r->cnt, sizeof(c), hipMemcpyDeviceToHost, r->stream));
+    RENDCHK(r, hipStreamSynchronize(r->stream));
+    RENDCHK(r, hipGetLastError());
+    SphRenderMeshStats &o = r->mstats;
+    o.meshes = (int64_t)nm; o.triangles = r->mesh_nt; o.vertices = r->mesh_nv;
+    o.hit = (int64_t)c[0]; o.skipped_nonfinite = (int64_t)c[1]; o.large = (int64_t)c[2]; o.atomics = (int64_t)c[3];
+    o.covered_pixels = (int64_t)c[4]; o.skipped_degenerate = (int64_t)c[5]; o.bad_index = (int64_t)c[6];
+    o.ms_depth = ev_ms(r->mev[1], r->mev[2]); o.ms_shade = ev_ms(r->mev[2], r->mev[3]); o.ms_finish = ev_ms(r->mev[3], r->mev[4]);
+    o.ms_total = ev_ms(r->mev[0], r->mev[4]);
+    r->have_frame = true;
+    if (o.bad_index)
+        return rend_fail(r, SPH_ERR_INVALID, "sph_render_mesh_end: %lld triangle(s) with a vertex index outside their mesh (skipped; the frame holds the rest)",
+                         (long long)o.bad_index);
+    return SPH_OK;
+}
+
+extern "C" int sph_render_mesh_stats(SphRender *r, SphRenderMeshStats *out) {
+    if (!r || !out) return SPH_ERR_INVALID;
+    *out = r->mstats;
     return SPH_OK;
 }

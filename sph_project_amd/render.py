@@ -39,6 +39,8 @@ class FrameRenderer:
                         background_rgb=background, box_rgb=box_color, fast_math=int(bool(fast_math)), device=int(device))
         self._handles = {}   # box (None or (lo, hi)) -> native renderer
         self._last = None
+        self._last_kind = None      # "points" or "meshes": what the last frame was drawn from
+        self._mesh_starts = None    # first global triangle index of each mesh of the last mesh frame (and the total)
 
     def _params(self, box):
         kw = dict(self._kw)
@@ -91,6 +93,10 @@ class FrameRenderer:
         self._last = h
         return rgb
 
+    def _need(self, kind, what):
+        if self._last is None or self._last_kind != kind:
+            raise RenderError(f"{what}: the last frame is not a {'mesh' if kind == 'meshes' else 'particle'} frame", -1)
+
     def from_points(self, xyz, colors=None, ids=None):
         """uint8 (H, W, 3) of spheres at xyz f32[n, 3], colours uint8[n, 3] (None: white), distinct ids < 0xFFFFFFF0 (None: 0..n-1)."""
         x = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
@@ -101,6 +107,7 @@ class FrameRenderer:
         h = self._native(self.box if self.box else None)
         self._chk(h, self.lib.sph_render_points(h, x.ctypes.data, None if c is None else c.ctypes.data,
                                                 None if i is None else i.ctypes.data, x.shape[0]), "sph_render_points")
+        self._last_kind = "points"
         return self._download(h)
 
     def from_container(self, container, hide=()):
@@ -118,10 +125,67 @@ class FrameRenderer:
             box = (np.zeros(3), np.asarray(container.domain_end, dtype=np.float64))
         h = self._native(box if box is not False else None)
         self._chk(h, self.lib.sph_render_handle(h, engine.h, C.c_uint32(mask)), "sph_render_handle")
+        self._last_kind = "points"
         return self._download(h)
 
+    def from_meshes(self, meshes):
+        """uint8 (H, W, 3) of an ordered list of triangle meshes: each item is (vertices f32[nv, 3], triangles i32[nt, 3],
+        normals f32[nv, 3] or None, rgb) or (SurfaceReconstructor, rgb) -- the reconstructor's last mesh, copied on the device.  Flat
+        shading without normals.  Triangles are numbered through the list (ids(), mesh_of()).  `radius` plays no part.  A triangle with
+        an index outside its mesh is skipped and raises RenderError (code -1) after the frame is drawn: last_rgb() / ids() still give it."""
+        h = self._native(self.box if self.box else None)
+        self._last = self._last_kind = self._mesh_starts = None
+        self._chk(h, self.lib.sph_render_mesh_begin(h), "sph_render_mesh_begin")
+        starts = [0]
+        for item in meshes:
+            col = np.ascontiguousarray(item[-1], dtype=np.uint8).reshape(3)
+            if len(item) == 2:
+                recon = item[0]
+                self._chk(h, self.lib.sph_render_mesh_add_surface(h, recon.h, col.ctypes.data), "sph_render_mesh_add_surface")
+                nv, nt = C.c_int64(), C.c_int64()
+                recon._chk(self.lib.sph_surface_mesh_size(recon.h, C.byref(nv), C.byref(nt)), "sph_surface_mesh_size")
+                starts.append(starts[-1] + nt.value)
+                continue
+            v = np.ascontiguousarray(item[0], dtype=np.float32).reshape(-1, 3)
+            t = np.ascontiguousarray(item[1], dtype=np.int32).reshape(-1, 3)
+            n = None if item[2] is None else np.ascontiguousarray(item[2], dtype=np.float32).reshape(-1, 3)
+            if n is not None and len(n) != len(v):
+                raise ValueError("from_meshes: normals must have one row per vertex")
+            self._chk(h, self.lib.sph_render_mesh_add(h, v.ctypes.data, None if n is None else n.ctypes.data, t.ctypes.data, v.shape[0],
+                                                      t.shape[0], col.ctypes.data), "sph_render_mesh_add")
+            starts.append(starts[-1] + t.shape[0])
+        rc = self.lib.sph_render_mesh_end(h)
+        self._mesh_starts = np.asarray(starts, np.int64)
+        if rc == -1:
+            st = L.SphRenderMeshStats()
+            if self.lib.sph_render_mesh_stats(h, C.byref(st)) == 0 and st.bad_index > 0:
+                self._last, self._last_kind = h, "meshes"   # drawn, with the bad triangles skipped
+        self._chk(h, rc, "sph_render_mesh_end")
+        self._last_kind = "meshes"
+        return self._download(h)
+
+    def last_rgb(self):
+        """uint8 (H, W, 3) of the last frame once more."""
+        if self._last is None:
+            raise RenderError("last_rgb: no frame rendered yet", -1)
+        return self._download(self._last)
+
+    def mesh_stats(self):
+        self._need("meshes", "mesh_stats")
+        st = L.SphRenderMeshStats()
+        self._chk(self._last, self.lib.sph_render_mesh_stats(self._last, C.byref(st)), "sph_render_mesh_stats")
+        return {k: getattr(st, k) for k, _ in L.SphRenderMeshStats._fields_}
+
+    def mesh_of(self, ids):
+        """The index in the last from_meshes list of the mesh that owns each triangle id (negative ids -- background, lines -- stay)."""
+        self._need("meshes", "mesh_of")
+        ids = np.asarray(ids, np.int64)
+        m = np.searchsorted(self._mesh_starts, ids, side="right") - 1
+        return np.where(ids < 0, ids, m)
+
     def ids(self):
-        """int32 (H, W) of the last frame: the winner's particle id, -1 background, -2 - edge a box line."""
+        """int32 (H, W) of the last frame: the winner's particle id (particle frames) or global triangle index (mesh frames), -1
+        background, -2 - edge a box line."""
         if self._last is None:
             raise RenderError("ids: no frame rendered yet", -1)
         rgb = np.empty((self.height, self.width, 3), np.uint8)
@@ -130,8 +194,7 @@ class FrameRenderer:
         return out
 
     def stats(self):
-        if self._last is None:
-            raise RenderError("stats: no frame rendered yet", -1)
+        self._need("points", "stats")
         st = L.SphRenderStats()
         self._chk(self._last, self.lib.sph_render_stats(self._last, C.byref(st)), "sph_render_stats")
         return {k: getattr(st, k) for k, _ in L.SphRenderStats._fields_}

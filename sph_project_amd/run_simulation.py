@@ -7,7 +7,8 @@ run_simulation.py (:13-44 argument + interval arithmetic, :116-155 loop, :137-14
 Frames go to {scene_name}_output/{cnt:06}/particle_object_{id}.ply (ASCII PLY, x y z per vertex -- the
 layout Taichi's PLYWriter.export_ascii produces and surface_reconstruction.py / splashsurf consume).
 Rigid bodies: mesh_object_{id}.obj per frame with exportObj (:146-150).  PNG frames (exportFrame, :131-134) come from the GPU
-renderer of render.py with --render (its own image, not GGUI's: DESIGN.md 15); without --render none is written."""
+renderer of render.py with --render (its own image, not GGUI's: DESIGN.md 15); without --render none is written.  --render_meshes
+writes {cnt:06}/render.png, the frame's meshes drawn on the GPU, where the reference's render.py needs Blender."""
 import argparse
 import os
 import sys
@@ -82,6 +83,10 @@ def parse_args(argv=None):
     parser.add_argument("--render", action="store_true",
                         help="on scenes with exportFrame write {out}/{cnt:06}/raw_view.png at the reference's cadence, rendered on the GPU "
                              "from the device state (DESIGN.md 15; not GGUI's image)")
+    parser.add_argument("--render_meshes", action="store_true",
+                        help="at every output frame write {out}/{cnt:06}/render.png (render.py's default --rendered_image_name): the visible "
+                             "fluid objects reconstructed with the --reconstruct settings, the visible rigid bodies' meshes at their current "
+                             "pose and the domain box, drawn on the GPU (DESIGN.md 17; not Blender's image)")
     parser.add_argument("--render_size", type=int, nargs=2, default=(1024, 1024), metavar=("W", "H"))
     parser.add_argument("--camera_position", type=float, nargs=3, default=(5.5, 2.5, 4.0))
     parser.add_argument("--camera_lookat", type=float, nargs=3, default=(-1.0, 0.0, 0.0))
@@ -95,6 +100,26 @@ def surface_postprocess(args):
         return None
     return dict(mesh_smoothing_iters=args.mesh_smoothing_iters, mesh_smoothing_weights=bool(args.mesh_smoothing_weights),
                 weights_normalization=13.0, normals_smoothing_iters=args.normals_smoothing_iters)
+
+
+def frame_meshes(container, solver, recon, reconstructed=()):
+    """The mesh list of one render.png, in object-id order: every visible fluid object reconstructed in situ (the list item is the
+    reconstructor itself: FrameRenderer.from_meshes copies its mesh on the device before the generator reconstructs the next object;
+    `reconstructed` names the object whose mesh the reconstructor holds on entry, valid until the first reconstruction here), every visible rigid body's mesh at its current pose, flat
+    shaded, each in its scene colour."""
+    for oid in sorted(container.object_id_fluid_body | container.object_id_rigid_body):
+        if container.object_visibility[oid] != 1:
+            continue
+        colour = tuple(int(c) for c in container.object_collection[oid]["color"])
+        if oid in container.object_id_fluid_body:
+            if oid not in reconstructed:
+                recon.from_container(container, oid)
+                reconstructed = ()   # the reconstructor holds this object's mesh now, no longer the one it was handed with
+            yield (recon, colour)
+        else:
+            posed = solver.posed_mesh_vertices(oid)
+            if posed is not None:
+                yield (posed, np.asarray(container.object_collection[oid]["mesh"].faces), None, colour)
 
 
 def main(argv=None):
@@ -132,7 +157,7 @@ def main(argv=None):
     solver.prepare()
 
     recon = None
-    if args.reconstruct:
+    if args.reconstruct or args.render_meshes:
         from sph_project_amd.surface import SurfaceReconstructor
         recon = SurfaceReconstructor(container.dx)
         post = surface_postprocess(args)
@@ -143,6 +168,12 @@ def main(argv=None):
         from sph_project_amd.render import FrameRenderer, write_png
         renderer = FrameRenderer(container.dx, width=args.render_size[0], height=args.render_size[1],
                                  camera_position=args.camera_position, camera_lookat=args.camera_lookat, fov=args.camera_fov)
+    mesh_renderer = None
+    if args.render_meshes:
+        from sph_project_amd.render import FrameRenderer, write_png
+        mesh_renderer = FrameRenderer(container.dx, width=args.render_size[0], height=args.render_size[1],
+                                      camera_position=args.camera_position, camera_lookat=args.camera_lookat, fov=args.camera_fov,
+                                      box=(np.zeros(3), np.asarray(container.domain_end, dtype=np.float64)))
     cnt = 0
     limit = total_rounds if args.max_steps is None else min(total_rounds, args.max_steps)
     limit = max(limit, 1)   # the reference's loop steps once before it looks at the round count
@@ -151,7 +182,7 @@ def main(argv=None):
     while cnt < limit:
         # run_simulation.py:126-153 steps once, writes a frame if the count of steps BEFORE this one is a multiple of the
         # interval, then counts.  Same frames here, but the steps between two frames go to the device in one call.
-        wants_frame = output_ply or output_obj or output_frames
+        wants_frame = output_ply or output_obj or output_frames or args.render_meshes
         nxt = cnt if cnt % output_interval == 0 else cnt + output_interval - cnt % output_interval   # next count that gets a frame
         if not wants_frame or nxt >= limit:
             solver.advance(limit - cnt)
@@ -162,6 +193,7 @@ def main(argv=None):
         container.engine.synchronize()
         te = time.perf_counter()
         wrote = False
+        held = set()
         if output_frames:   # run_simulation.py:131-134
             os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
             write_png(f"{out_dir}/{cnt:06}/raw_view.png", renderer.from_container(container))
@@ -170,9 +202,10 @@ def main(argv=None):
             os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
             for f_body_id in container.object_id_fluid_body:
                 write_ply_ascii(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.ply", container.dump(obj_id=f_body_id)["position"])
-                if recon is not None:   # what surface_reconstruction.py would make of that PLY, without reading it back
+                if args.reconstruct:   # what surface_reconstruction.py would make of that PLY, without reading it back
                     recon.from_container(container, f_body_id)
                     recon.write_obj(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.obj")
+                    held = {f_body_id}   # the reconstructor still holds this object's mesh: the mesh frame below need not redo it
                 wrote = True
         if output_obj:   # run_simulation.py:146-150
             os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
@@ -182,6 +215,10 @@ def main(argv=None):
                 with open(f"{out_dir}/{cnt:06}/mesh_object_{r_body_id}.obj", "w") as f:
                     f.write(container.object_collection[r_body_id]["mesh"].export(file_type="obj"))
                 wrote = True
+        if mesh_renderer is not None:   # render.py: every mesh of the frame -> {frame}/render.png
+            os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
+            write_png(f"{out_dir}/{cnt:06}/render.png", mesh_renderer.from_meshes(frame_meshes(container, solver, recon, held)))
+            wrote = True
         frames += 1 if wrote else 0
         t_export += time.perf_counter() - te
         cnt += 1

@@ -20,6 +20,9 @@ def short(name):
     m = re.search(r"k_nbr_pass<\s*(?:sph_\w+_ns::)?(\w+)", name)
     if m:
         return "nbr_pass<" + m.group(1) + ">"
+    m = re.search(r"(k_mesh_\w+)<\s*(true|false)", name)   # the mesh renderer's passes: <false> depth, <true> shade
+    if m:
+        return m.group(1) + ("<shade>" if m.group(2) == "true" else "<depth>")
     m = re.search(r"(k_\w+)", name)
     return m.group(1) if m else name[:40]
 
