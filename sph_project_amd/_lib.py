@@ -142,8 +142,21 @@ class SphRenderMeshStats(C.Structure):
     ]
 
 
+# return codes (include/sph_hip.h)
+ERR_INVALID, ERR_CAPACITY = -1, -2
+
+
 class SphError(RuntimeError):
-    pass
+    """.code: the library's return code (None: raised on the Python side of the binding)."""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
+
+
+def struct_dict(st, skip=()):
+    """The fields of a ctypes structure as a dict."""
+    return {k: getattr(st, k) for k, _ in st._fields_ if k not in skip}
 
 
 _lib = None
@@ -244,23 +257,29 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-class Engine:
-    """Owns one SphHandle.  All arrays crossing the boundary are C-contiguous numpy f32 / i32."""
+class NativeObject:
+    """Owner of native handles of one kind: ABI + "_create" / "_destroy" / "_last_error" are its functions, Error is what a non-zero
+    return code raises.  self.h is the handle the calls of _chk are about unless they name another."""
+    ABI = "sph"
+    Error = SphError
+    h = None
 
-    def __init__(self, params: SphParams):
+    def __init__(self):
         self.lib = load()
-        self.params = params
+        self._owned = []
+
+    def _create(self, params):
         h = C.c_void_p()
-        rc = self.lib.sph_create(C.byref(params), C.byref(h))
-        if rc != 0:
-            msg = self.lib.sph_last_error(None)
-            raise SphError(f"sph_create failed ({rc}): {msg.decode() if msg else ''}")
-        self.h = h
+        name = self.ABI + "_create"
+        self._chk(getattr(self.lib, name)(C.byref(params), C.byref(h)), name, None)
+        self._owned.append(h)
+        return h
 
     def close(self):
-        if getattr(self, "h", None):
-            self.lib.sph_destroy(self.h)
-            self.h = None
+        for h in getattr(self, "_owned", []):
+            getattr(self.lib, self.ABI + "_destroy")(h)
+        self._owned = []
+        self.h = None
 
     def __del__(self):
         try:
@@ -268,10 +287,20 @@ class Engine:
         except Exception:
             pass
 
-    def _chk(self, rc, what):
+    def _chk(self, rc, what, *h):
+        """h: the handle whose message explains rc (None: the create error); default self.h."""
         if rc != 0:
-            msg = self.lib.sph_last_error(self.h)
-            raise SphError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            msg = getattr(self.lib, self.ABI + "_last_error")(h[0] if h else self.h)
+            raise self.Error(f"{what} failed ({rc}): {msg.decode() if msg else ''}", rc)
+
+
+class Engine(NativeObject):
+    """Owns one SphHandle.  All arrays crossing the boundary are C-contiguous numpy f32 / i32."""
+
+    def __init__(self, params: SphParams):
+        super().__init__()
+        self.params = params
+        self.h = self._create(params)
 
     # -- scene upload
     def append_particles(self, object_id, pos, vel, density, pressure, material, is_dynamic, color):
@@ -368,7 +397,7 @@ class Engine:
     def stats(self):
         st = SphStats()
         self._chk(self.lib.sph_get_stats(self.h, C.byref(st)), "sph_get_stats")
-        return {k: getattr(st, k) for k, _ in SphStats._fields_}
+        return struct_dict(st)
 
     # -- profiling
     def profile_enable(self, kernel_id=-1, on=True):

@@ -16,8 +16,7 @@
 #include <algorithm>
 #include "sph_voxel.hpp"
 #include "sph_export.hpp"
-
-static thread_local std::string g_create_error;
+#include "sph_devobj.hpp"
 
 struct ProfSlot {
     bool on = false;
@@ -26,11 +25,10 @@ struct ProfSlot {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
-struct SphHandle {
+struct SphHandle : ErrSink {
     SphParams prm;
     State st;
     const Launch *L = nullptr;
-    std::string err;
     int device = 0;
     int n = 0;            // particle_num (a launch BOUND while n_exact is false: asynchronous slab steps, see slab_settle)
     bool n_exact = true;
@@ -105,23 +103,6 @@ static bool set_axis_order(SphHandle *h, const char *order) {
     h->swap_axis = !(p[0] == 0 && p[1] == 1 && p[2] == 2);
     return true;
 }
-
-static int fail(SphHandle *h, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf; else g_create_error = buf;
-    return code;
-}
-
-#define HIPCHK(h, call)                                                                       \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail((h), SPH_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 template <class T> static int dalloc(SphHandle *h, T **p, size_t count) {
     void *q = nullptr;
@@ -217,7 +198,7 @@ static void refresh_counts(SphHandle *h) {
     h->st.uniform_mass = (h->st.c.all_fluid && h->fluid_mass_uniform && !h->st.slab_active && !getenv("SPH_NO_UNIFORM_MASS")) ? 1 : 0;
 }
 
-extern "C" const char *sph_last_error(SphHandle *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+extern "C" const char *sph_last_error(SphHandle *h) { return last_error(h); }
 
 extern "C" const char *sph_kernel_name(int k) {
     static const char *names[SPH_K_COUNT_] = {
@@ -264,14 +245,10 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     if (p.particle_max_num > 0x0fffffff)
         return fail(nullptr, SPH_ERR_CAPACITY, "sph_create: particle_max_num %d exceeds 268435455 per GPU; shard the scene (sph_comm_set_slab)", p.particle_max_num);
     if (p.method < 0 || p.method > SPH_METHOD_PBF) return fail(nullptr, SPH_ERR_INVALID, "sph_create: unknown method %d", p.method);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(nullptr, SPH_ERR_NO_DEVICE, "sph_create: no HIP device visible (libsph_hip has no CPU path)");
+    int dev = 0;
+    { int rc = pick_device("sph_create", p.device, &dev); if (rc) return rc; }
     SphHandle *h = new SphHandle();
     h->prm = p;
-    int dev = p.device;
-    if (dev < 0) { if (hipGetDevice(&dev) != hipSuccess) dev = 0; }
-    if (dev >= ndev) { delete h; return fail(nullptr, SPH_ERR_NO_DEVICE, "sph_create: device %d not present", dev); }
     h->device = dev;
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) h->dev_cus = cus; }
 #define CHK_CREATE(call)                                                                   \
@@ -288,14 +265,6 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
             return SPH_ERR_HIP;                                                            \
         }                                                                                  \
     } while (0)
-    HIP_CREATE(hipSetDevice(dev));
-    hipDeviceProp_t prop;
-    HIP_CREATE(hipGetDeviceProperties(&prop, dev));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        fail(nullptr, SPH_ERR_NO_DEVICE, "sph_create: device %d is %s, this library is built for gfx950 only", dev, prop.gcnArchName);
-        sph_destroy(h);
-        return SPH_ERR_NO_DEVICE;
-    }
     h->L = p.fast_math ? sph_launch_fast() : sph_launch_strict();
     State &s = h->st;
     memset(&s.c, 0, sizeof(s.c));

@@ -10,46 +10,24 @@ enum SurfBufId { SB_XIN, SB_XTMP, SB_XS, SB_PCELL, SB_PSLOT, SB_CELL_START, SB_F
                  // post-processing
                  SB_ADJ_RAW, SB_ADJ_CNT, SB_ADJ_SLOT, SB_ADJ, SB_PCOUNT, SB_WEIGHT, SB_WORK_A, SB_WORK_B, SB_COUNT_ };
 
-struct SphSurface {
+struct SphSurface : DevObj {   // clk[0]: the reconstruction's stages, clk[1]: the post-processing's
     SphSurfaceParams prm;
-    const Launch *L = nullptr;
-    int device = 0;
-    std::string err;
     SurfDev d{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {};
-    void *buf[SB_COUNT_] = {};
-    size_t bytes[SB_COUNT_] = {};
+    DevBuf buf[SB_COUNT_];
     bool live[SB_COUNT_] = {};   // holds data of the reconstruction running now
     int64_t nv = 0, nt = 0;
     bool have_mesh = false;
     SphSurfaceStats stats{};
     SphSurfacePostParams post{0, 0, 13.0, 0, 0};   // off
-    hipEvent_t pev[6] = {};
     SurfPost p{};
     bool have_post = false;   // the last reconstruction built the adjacency
     bool have_weights = false;
     SphSurfacePostStats post_stats{};
 };
 
-static int surf_fail(SphSurface *s, int code, const char *fmt, ...) {
-    char b[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(b, sizeof(b), fmt, ap);
-    va_end(ap);
-    if (s) s->err = b; else g_create_error = b;
-    return code;
-}
-#define SURFCHK(s, call)                                                                                                   \
-    do {                                                                                                                    \
-        hipError_t e_ = (call);                                                                                             \
-        if (e_ != hipSuccess) return surf_fail((s), SPH_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 static size_t surf_total(const SphSurface *s) {
     size_t t = 0;
-    for (int k = 0; k < SB_COUNT_; ++k) t += s->bytes[k];
+    for (const DevBuf &b : s->buf) t += b.bytes;
     return t;
 }
 // buffer k with room for `need` bytes.  Past the cap, the buffers that hold nothing of this reconstruction go first; if it still does not
@@ -57,53 +35,36 @@ static size_t surf_total(const SphSurface *s) {
 static int surf_ensure(SphSurface *s, int k, size_t need, const char *what) {
     if (need == 0) need = 16;
     s->live[k] = true;
-    if (s->bytes[k] >= need) return SPH_OK;
+    DevBuf &b = s->buf[k];
+    if (b.bytes >= need) return SPH_OK;
     const size_t cap = (size_t)s->prm.memory_cap_bytes;
-    if (cap && surf_total(s) - s->bytes[k] + need > cap) {
+    if (cap && surf_total(s) - b.bytes + need > cap) {
         for (int j = 0; j < SB_COUNT_; ++j)
-            if (!s->live[j] && s->buf[j]) { hipFree(s->buf[j]); s->buf[j] = nullptr; s->bytes[j] = 0; }
-        if (surf_total(s) - s->bytes[k] + need > cap)
-            return surf_fail(s, SPH_ERR_CAPACITY, "surface: %s needs %zu bytes, %zu held, cap %zu", what, need, surf_total(s) - s->bytes[k], cap);
+            if (!s->live[j]) s->buf[j].release();
+        if (surf_total(s) - b.bytes + need > cap)
+            return fail(s, SPH_ERR_CAPACITY, "surface: %s needs %zu bytes, %zu held, cap %zu", what, need, surf_total(s) - b.bytes, cap);
     }
-    if (s->buf[k]) { hipFree(s->buf[k]); s->buf[k] = nullptr; s->bytes[k] = 0; }
-    SURFCHK(s, hipMalloc(&s->buf[k], need));
-    s->bytes[k] = need;
-    return SPH_OK;
+    return b.reserve(s, need);
 }
 #define SURF_ENSURE(s, k, need, what) do { int rc_ = surf_ensure((s), (k), (need), (what)); if (rc_) return rc_; } while (0)
 
 extern "C" int sph_surface_create(const SphSurfaceParams *params, SphSurface **out) {
-    if (!params || !out) return surf_fail(nullptr, SPH_ERR_INVALID, "sph_surface_create: null argument");
+    if (!params || !out) return fail(nullptr, SPH_ERR_INVALID, "sph_surface_create: null argument");
     *out = nullptr;
     const SphSurfaceParams p = *params;
     if (!(p.radius > 0.0) || !(p.smoothing_length > 0.0) || !(p.cube_size > 0.0) || !std::isfinite(p.radius) ||
         !std::isfinite(p.smoothing_length) || !std::isfinite(p.cube_size) || !std::isfinite(p.iso) || !(p.iso > 0.0) || p.memory_cap_bytes < 0)
-        return surf_fail(nullptr, SPH_ERR_INVALID, "sph_surface_create: radius, smoothing_length, cube_size and iso must be positive and finite, the cap >= 0");
+        return fail(nullptr, SPH_ERR_INVALID, "sph_surface_create: radius, smoothing_length, cube_size and iso must be positive and finite, the cap >= 0");
     const double h = 2.0 * p.smoothing_length * p.radius, e = p.cube_size * p.radius;
     const double Bd = ceil(h / e - 1e-9);
     // the edge word keeps a vertex offset of 21 bits (3 B^3 < 2^21): B <= 64 is far beyond any useful grid
     if (!(Bd >= 1.0 && Bd <= 64.0))
-        return surf_fail(nullptr, SPH_ERR_INVALID, "sph_surface_create: %.0f grid points per brick edge (smoothing_length / cube_size * 2); at most 64", Bd);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return surf_fail(nullptr, SPH_ERR_NO_DEVICE, "sph_surface_create: no HIP device visible (libsph_hip has no CPU path)");
-    int dev = p.device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (dev >= ndev) return surf_fail(nullptr, SPH_ERR_NO_DEVICE, "sph_surface_create: device %d not present", dev);
-    hipDeviceProp_t prop;
-    if (hipSetDevice(dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-        return surf_fail(nullptr, SPH_ERR_HIP, "sph_surface_create: device %d unusable", dev);
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return surf_fail(nullptr, SPH_ERR_NO_DEVICE, "sph_surface_create: device %d is %s, this library is built for gfx950 only", dev, prop.gcnArchName);
+        return fail(nullptr, SPH_ERR_INVALID, "sph_surface_create: %.0f grid points per brick edge (smoothing_length / cube_size * 2); at most 64", Bd);
+    int dev = 0;
+    { int rc = pick_device("sph_surface_create", p.device, &dev); if (rc) return rc; }
     SphSurface *s = new SphSurface();
     s->prm = p;
-    s->device = dev;
-    s->L = p.fast_math ? sph_launch_fast() : sph_launch_strict();
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; return surf_fail(nullptr, SPH_ERR_HIP, "sph_surface_create: stream"); }
-    for (auto &e_ : s->ev)
-        if (hipEventCreate(&e_) != hipSuccess) { sph_surface_destroy(s); return surf_fail(nullptr, SPH_ERR_HIP, "sph_surface_create: event"); }
-    for (auto &e_ : s->pev)
-        if (hipEventCreate(&e_) != hipSuccess) { sph_surface_destroy(s); return surf_fail(nullptr, SPH_ERR_HIP, "sph_surface_create: event"); }
+    { int rc = devobj_open(s, "sph_surface_create", dev, p.fast_math); if (rc) { sph_surface_destroy(s); return rc; } }
     SurfDev &d = s->d;
     d.h = (float)h;
     d.h2 = (float)(h * h);
@@ -122,23 +83,16 @@ extern "C" int sph_surface_create(const SphSurfaceParams *params, SphSurface **o
 
 extern "C" void sph_surface_destroy(SphSurface *s) {
     if (!s) return;
-    hipSetDevice(s->device);
-    if (s->stream) hipStreamSynchronize(s->stream);
-    for (int k = 0; k < SB_COUNT_; ++k) if (s->buf[k]) hipFree(s->buf[k]);
-    for (auto e_ : s->ev) if (e_) hipEventDestroy(e_);
-    for (auto e_ : s->pev) if (e_) hipEventDestroy(e_);
-    if (s->stream) hipStreamDestroy(s->stream);
+    devobj_close(s, s->buf, SB_COUNT_);
     delete s;
 }
 
-extern "C" const char *sph_surface_last_error(SphSurface *s) { return s ? s->err.c_str() : g_create_error.c_str(); }
-
-static float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0.0f; hipEventElapsedTime(&ms, a, b); return ms; }
+extern "C" const char *sph_surface_last_error(SphSurface *s) { return last_error(s); }
 
 static bool surf_post_on(const SphSurface *s) { return s->post.mesh_smoothing_iters > 0 || s->post.normals_smoothing_iters > 0; }
 static int surf_post(SphSurface *s, int nv, int nt);
 
-// the passes after the input is in xin[0, n) and ev[0] has been recorded before it was put there
+// the passes after the input is in xin[0, n) and stage mark 0 has been set before it was put there
 static int surf_run(SphSurface *s, int n) {
     SurfDev &d = s->d;
     hipStream_t st = s->stream;
@@ -146,7 +100,7 @@ static int surf_run(SphSurface *s, int n) {
     d.nb = 0;
     d.cmin[0] = d.cmin[1] = d.cmin[2] = 0;
     if (n == 0) {   // no particle: the empty mesh (and, with the post stage on, its empty adjacency)
-        SURFCHK(s, hipStreamSynchronize(st));
+        HIPCHK(s, hipStreamSynchronize(st));
         s->have_mesh = true;
         s->have_post = surf_post_on(s);
         s->stats.bytes_allocated = (int64_t)surf_total(s);
@@ -154,23 +108,23 @@ static int surf_run(SphSurface *s, int n) {
     }
     // SB_SMALL, 16 int slots: [0, 7) bounds, [8] counter (compaction), [10, 12) pairs (u64), [12] largest degree (post-processing)
     SURF_ENSURE(s, SB_SMALL, 64, "counters");
-    d.bounds = (int *)s->buf[SB_SMALL];
+    d.bounds = (int *)s->buf[SB_SMALL].p;
     d.counter = d.bounds + 8;
     d.pairs = (unsigned long long *)(d.bounds + 10);
     const int init[7] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0};
-    SURFCHK(s, hipMemcpyAsync(d.bounds, init, sizeof(init), hipMemcpyHostToDevice, st));
+    HIPCHK(s, hipMemcpyAsync(d.bounds, init, sizeof(init), hipMemcpyHostToDevice, st));
     s->L->surf_bounds(d);
     int bnd[7];
-    SURFCHK(s, hipMemcpyAsync(bnd, d.bounds, sizeof(bnd), hipMemcpyDeviceToHost, st));
-    SURFCHK(s, hipStreamSynchronize(st));
-    if (bnd[6]) return surf_fail(s, SPH_ERR_INVALID, "surface: non-finite particle position (or one beyond 1e8 coarse cells)");
+    HIPCHK(s, hipMemcpyAsync(bnd, d.bounds, sizeof(bnd), hipMemcpyDeviceToHost, st));
+    HIPCHK(s, hipStreamSynchronize(st));
+    if (bnd[6]) return fail(s, SPH_ERR_INVALID, "surface: non-finite particle position (or one beyond 1e8 coarse cells)");
     int64_t G = 1;
     for (int a = 0; a < 3; ++a) {
         d.cmin[a] = bnd[a] - 1;                       // one empty coarse cell around the particles
         d.cn[a] = bnd[3 + a] - bnd[a] + 3;
         G *= d.cn[a];
     }
-    if (G > (int64_t)INT_MAX / 2) return surf_fail(s, SPH_ERR_CAPACITY, "surface: coarse grid of %lld cells", (long long)G);
+    if (G > (int64_t)INT_MAX / 2) return fail(s, SPH_ERR_CAPACITY, "surface: coarse grid of %lld cells", (long long)G);
     d.G = (int)G;
     SURF_ENSURE(s, SB_XTMP, sizeof(float4) * (size_t)n, "particles");
     SURF_ENSURE(s, SB_XS, sizeof(float4) * (size_t)n, "particles");
@@ -180,17 +134,17 @@ static int surf_run(SphSurface *s, int n) {
     SURF_ENSURE(s, SB_FLAG, sizeof(int) * ((size_t)G + 1), "coarse grid");
     SURF_ENSURE(s, SB_BRICK_ID, sizeof(int) * (size_t)G, "coarse grid");
     SURF_ENSURE(s, SB_SCAN, sizeof(int) * ((size_t)(G + 1) / 1024 + 2), "scan");
-    d.xtmp = (float4 *)s->buf[SB_XTMP]; d.xs = (float4 *)s->buf[SB_XS];
-    d.pcell = (int *)s->buf[SB_PCELL]; d.pslot = (int *)s->buf[SB_PSLOT];
-    d.cell_start = (int *)s->buf[SB_CELL_START]; d.flag = (int *)s->buf[SB_FLAG]; d.brick_id = (int *)s->buf[SB_BRICK_ID];
-    d.scan_tmp = (int *)s->buf[SB_SCAN];
+    d.xtmp = (float4 *)s->buf[SB_XTMP].p; d.xs = (float4 *)s->buf[SB_XS].p;
+    d.pcell = (int *)s->buf[SB_PCELL].p; d.pslot = (int *)s->buf[SB_PSLOT].p;
+    d.cell_start = (int *)s->buf[SB_CELL_START].p; d.flag = (int *)s->buf[SB_FLAG].p; d.brick_id = (int *)s->buf[SB_BRICK_ID].p;
+    d.scan_tmp = (int *)s->buf[SB_SCAN].p;
     s->L->surf_bin(d);   // (leaves xs = the key-ordered particles with V)
-    SURFCHK(s, hipEventRecord(s->ev[1], st));
+    HIPCHK(s, s->clk[0].mark(1));
     s->L->surf_flags(d);
-    SURFCHK(s, hipEventRecord(s->ev[2], st));
+    HIPCHK(s, s->clk[0].mark(2));
     int nb = 0;
-    SURFCHK(s, hipMemcpyAsync(&nb, d.flag + G, sizeof(int), hipMemcpyDeviceToHost, st));
-    SURFCHK(s, hipStreamSynchronize(st));
+    HIPCHK(s, hipMemcpyAsync(&nb, d.flag + G, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(s, hipStreamSynchronize(st));
     d.nb = nb;
     const size_t points = (size_t)nb * (size_t)d.P;
     SURF_ENSURE(s, SB_BRICK_CELL, sizeof(int) * (size_t)nb, "bricks");
@@ -198,31 +152,31 @@ static int surf_run(SphSurface *s, int n) {
     SURF_ENSURE(s, SB_EDGE, sizeof(unsigned) * points, "grid values");
     SURF_ENSURE(s, SB_VBASE, sizeof(int) * ((size_t)nb + 1), "bricks");
     SURF_ENSURE(s, SB_TBASE, sizeof(int) * ((size_t)nb + 1), "bricks");
-    if ((size_t)nb + 1 > (size_t)(G + 1)) return surf_fail(s, SPH_ERR_INVALID, "surface: internal brick count");
-    d.brick_cell = (int *)s->buf[SB_BRICK_CELL]; d.phi = (float *)s->buf[SB_PHI]; d.edge = (unsigned *)s->buf[SB_EDGE];
-    d.vbase = (int *)s->buf[SB_VBASE]; d.tbase = (int *)s->buf[SB_TBASE];
+    if ((size_t)nb + 1 > (size_t)(G + 1)) return fail(s, SPH_ERR_INVALID, "surface: internal brick count");
+    d.brick_cell = (int *)s->buf[SB_BRICK_CELL].p; d.phi = (float *)s->buf[SB_PHI].p; d.edge = (unsigned *)s->buf[SB_EDGE].p;
+    d.vbase = (int *)s->buf[SB_VBASE].p; d.tbase = (int *)s->buf[SB_TBASE].p;
     s->L->surf_field(d);
-    SURFCHK(s, hipEventRecord(s->ev[3], st));
+    HIPCHK(s, s->clk[0].mark(3));
     s->L->surf_count(d);
     int tot[2] = {0, 0};
-    SURFCHK(s, hipMemcpyAsync(&tot[0], d.vbase + nb, sizeof(int), hipMemcpyDeviceToHost, st));
-    SURFCHK(s, hipMemcpyAsync(&tot[1], d.tbase + nb, sizeof(int), hipMemcpyDeviceToHost, st));
-    SURFCHK(s, hipStreamSynchronize(st));
+    HIPCHK(s, hipMemcpyAsync(&tot[0], d.vbase + nb, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(s, hipMemcpyAsync(&tot[1], d.tbase + nb, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(s, hipStreamSynchronize(st));
     if (tot[0] < 0 || tot[1] < 0 || tot[1] > INT_MAX / 3 || tot[0] > INT_MAX / 3)
-        return surf_fail(s, SPH_ERR_CAPACITY, "surface: more than 2^31 / 3 vertices or triangles");
+        return fail(s, SPH_ERR_CAPACITY, "surface: more than 2^31 / 3 vertices or triangles");
     SURF_ENSURE(s, SB_VERT, sizeof(float) * 3 * (size_t)tot[0], "vertices");
     SURF_ENSURE(s, SB_TRI, sizeof(int) * 3 * (size_t)tot[1], "triangles");
     if (s->prm.normals) SURF_ENSURE(s, SB_NRM, sizeof(float) * 3 * (size_t)tot[0], "normals");
-    d.vert = (float *)s->buf[SB_VERT]; d.tri = (int *)s->buf[SB_TRI]; d.nrm = s->prm.normals ? (float *)s->buf[SB_NRM] : nullptr;
+    d.vert = (float *)s->buf[SB_VERT].p; d.tri = (int *)s->buf[SB_TRI].p; d.nrm = s->prm.normals ? (float *)s->buf[SB_NRM].p : nullptr;
     s->L->surf_emit(d);
-    SURFCHK(s, hipEventRecord(s->ev[4], st));
+    HIPCHK(s, s->clk[0].mark(4));
     // (smoothed positions get their normals in the post stage: none here then, and ms_normals ~ 0)
     if (s->prm.normals && !(surf_post_on(s) && s->post.mesh_smoothing_iters > 0)) s->L->surf_normals(d, tot[0]);
-    SURFCHK(s, hipEventRecord(s->ev[5], st));
+    HIPCHK(s, s->clk[0].mark(5));
     unsigned long long pairs = 0;
-    SURFCHK(s, hipMemcpyAsync(&pairs, d.pairs, sizeof(pairs), hipMemcpyDeviceToHost, st));
-    SURFCHK(s, hipStreamSynchronize(st));
-    SURFCHK(s, hipGetLastError());
+    HIPCHK(s, hipMemcpyAsync(&pairs, d.pairs, sizeof(pairs), hipMemcpyDeviceToHost, st));
+    HIPCHK(s, hipStreamSynchronize(st));
+    HIPCHK(s, hipGetLastError());
     if (surf_post_on(s)) { const int rc = surf_post(s, tot[0], tot[1]); if (rc) return rc; }
     s->nv = tot[0];
     s->nt = tot[1];
@@ -230,8 +184,9 @@ static int surf_run(SphSurface *s, int n) {
     SphSurfaceStats &o = s->stats;
     o.particles = n; o.active_bricks = nb; o.points_evaluated = (int64_t)points; o.pair_tests = (int64_t)pairs;
     o.vertices = s->nv; o.triangles = s->nt; o.bytes_allocated = (int64_t)surf_total(s); o.B = d.B;
-    o.ms_bin = ev_ms(s->ev[0], s->ev[1]); o.ms_bricks = ev_ms(s->ev[1], s->ev[2]); o.ms_field = ev_ms(s->ev[2], s->ev[3]);
-    o.ms_mesh = ev_ms(s->ev[3], s->ev[4]); o.ms_normals = ev_ms(s->ev[4], s->ev[5]); o.ms_total = ev_ms(s->ev[0], s->ev[5]);
+    const StageClock &c = s->clk[0];
+    o.ms_bin = c.ms(0, 1); o.ms_bricks = c.ms(1, 2); o.ms_field = c.ms(2, 3);
+    o.ms_mesh = c.ms(3, 4); o.ms_normals = c.ms(4, 5); o.ms_total = c.ms(0, 5);
     return SPH_OK;
 }
 
@@ -247,43 +202,43 @@ static void surf_begin(SphSurface *s) {
 
 extern "C" int sph_surface_reconstruct(SphSurface *s, const float *xyz, int64_t n) {
     if (!s) return SPH_ERR_INVALID;
-    if (n < 0 || n > INT_MAX / 2 || (n > 0 && !xyz)) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_reconstruct: bad particle array (n = %lld)", (long long)n);
-    SURFCHK(s, hipSetDevice(s->device));
+    if (n < 0 || n > INT_MAX / 2 || (n > 0 && !xyz)) return fail(s, SPH_ERR_INVALID, "sph_surface_reconstruct: bad particle array (n = %lld)", (long long)n);
+    HIPCHK(s, hipSetDevice(s->device));
     surf_begin(s);
     std::vector<float4> tmp((size_t)n);
     for (int64_t i = 0; i < n; ++i) tmp[i] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 0.0f);
     SURF_ENSURE(s, SB_XIN, sizeof(float4) * (size_t)n, "particles");
-    s->d.xin = (float4 *)s->buf[SB_XIN];
-    SURFCHK(s, hipEventRecord(s->ev[0], s->stream));
-    if (n) SURFCHK(s, hipMemcpyAsync(s->d.xin, tmp.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s->stream));
+    s->d.xin = (float4 *)s->buf[SB_XIN].p;
+    HIPCHK(s, s->clk[0].mark(0));
+    if (n) HIPCHK(s, hipMemcpyAsync(s->d.xin, tmp.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s->stream));
     return surf_run(s, (int)n);
 }
 
 extern "C" int sph_surface_reconstruct_object(SphSurface *s, SphHandle *h, int object_id) {
     if (!s || !h) return SPH_ERR_INVALID;
     if (h->st.slab_active || h->swap_axis)
-        return surf_fail(s, SPH_ERR_UNSUPPORTED, "sph_surface_reconstruct_object: sharded handle (reconstruct each rank's download instead)");
-    if (h->device != s->device) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_reconstruct_object: handle on device %d, surface on %d", h->device, s->device);
-    if (object_id < 0 || object_id >= SPH_MAX_OBJECTS) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_reconstruct_object: object id %d", object_id);
-    SURFCHK(s, hipSetDevice(s->device));
-    SURFCHK(s, hipStreamSynchronize(h->st.stream));   // the handle's last step has written the positions
+        return fail(s, SPH_ERR_UNSUPPORTED, "sph_surface_reconstruct_object: sharded handle (reconstruct each rank's download instead)");
+    if (h->device != s->device) return fail(s, SPH_ERR_INVALID, "sph_surface_reconstruct_object: handle on device %d, surface on %d", h->device, s->device);
+    if (object_id < 0 || object_id >= SPH_MAX_OBJECTS) return fail(s, SPH_ERR_INVALID, "sph_surface_reconstruct_object: object id %d", object_id);
+    HIPCHK(s, hipSetDevice(s->device));
+    HIPCHK(s, hipStreamSynchronize(h->st.stream));   // the handle's last step has written the positions
     surf_begin(s);
     const int n_all = h->n;
     SURF_ENSURE(s, SB_XIN, sizeof(float4) * (size_t)n_all, "particles");
     SURF_ENSURE(s, SB_SMALL, 64, "counters");
-    s->d.xin = (float4 *)s->buf[SB_XIN];
-    s->d.counter = (int *)s->buf[SB_SMALL] + 8;
-    SURFCHK(s, hipEventRecord(s->ev[0], s->stream));
+    s->d.xin = (float4 *)s->buf[SB_XIN].p;
+    s->d.counter = (int *)s->buf[SB_SMALL].p + 8;
+    HIPCHK(s, s->clk[0].mark(0));
     s->L->surf_compact(s->d, h->st.posv.cur(), h->st.meta.cur(), n_all, object_id);
     int n = 0;
-    SURFCHK(s, hipMemcpyAsync(&n, s->d.counter, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-    SURFCHK(s, hipStreamSynchronize(s->stream));
+    HIPCHK(s, hipMemcpyAsync(&n, s->d.counter, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(s, hipStreamSynchronize(s->stream));
     return surf_run(s, n);
 }
 
 extern "C" int sph_surface_mesh_size(SphSurface *s, int64_t *n_vertices, int64_t *n_triangles) {
     if (!s || !n_vertices || !n_triangles) return SPH_ERR_INVALID;
-    if (!s->have_mesh) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_mesh_size: no reconstruction has succeeded yet");
+    if (!s->have_mesh) return fail(s, SPH_ERR_INVALID, "sph_surface_mesh_size: no reconstruction has succeeded yet");
     *n_vertices = s->nv;
     *n_triangles = s->nt;
     return SPH_OK;
@@ -291,13 +246,13 @@ extern "C" int sph_surface_mesh_size(SphSurface *s, int64_t *n_vertices, int64_t
 
 extern "C" int sph_surface_download(SphSurface *s, float *vertices, float *normals_or_NULL, int32_t *triangles) {
     if (!s) return SPH_ERR_INVALID;
-    if (!s->have_mesh) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_download: no reconstruction has succeeded yet");
-    if ((s->nv && !vertices) || (s->nt && !triangles)) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_download: null output");
-    if (normals_or_NULL && !s->prm.normals) return surf_fail(s, SPH_ERR_INVALID, "sph_surface_download: created without normals");
-    SURFCHK(s, hipSetDevice(s->device));
-    if (s->nv) SURFCHK(s, hipMemcpy(vertices, s->d.vert, sizeof(float) * 3 * (size_t)s->nv, hipMemcpyDeviceToHost));
-    if (s->nv && normals_or_NULL) SURFCHK(s, hipMemcpy(normals_or_NULL, s->d.nrm, sizeof(float) * 3 * (size_t)s->nv, hipMemcpyDeviceToHost));
-    if (s->nt) SURFCHK(s, hipMemcpy(triangles, s->d.tri, sizeof(int) * 3 * (size_t)s->nt, hipMemcpyDeviceToHost));
+    if (!s->have_mesh) return fail(s, SPH_ERR_INVALID, "sph_surface_download: no reconstruction has succeeded yet");
+    if ((s->nv && !vertices) || (s->nt && !triangles)) return fail(s, SPH_ERR_INVALID, "sph_surface_download: null output");
+    if (normals_or_NULL && !s->prm.normals) return fail(s, SPH_ERR_INVALID, "sph_surface_download: created without normals");
+    HIPCHK(s, hipSetDevice(s->device));
+    if (s->nv) HIPCHK(s, hipMemcpy(vertices, s->d.vert, sizeof(float) * 3 * (size_t)s->nv, hipMemcpyDeviceToHost));
+    if (s->nv && normals_or_NULL) HIPCHK(s, hipMemcpy(normals_or_NULL, s->d.nrm, sizeof(float) * 3 * (size_t)s->nv, hipMemcpyDeviceToHost));
+    if (s->nt) HIPCHK(s, hipMemcpy(triangles, s->d.tri, sizeof(int) * 3 * (size_t)s->nt, hipMemcpyDeviceToHost));
     return SPH_OK;
 }
 
@@ -316,7 +271,7 @@ static int surf_post(SphSurface *s, int nv, int nt) {
     const bool weights = q.mesh_smoothing_weights && q.mesh_smoothing_iters > 0;
     // the slot ranges and CSR offsets are int and reach 6 nt (2 slots per triangle corner): refuse before anything is allocated or launched
     if ((int64_t)6 * nt > (int64_t)INT_MAX)
-        return surf_fail(s, SPH_ERR_CAPACITY, "surface: %d triangles, more than 2^31 / 6 for the smoothing's adjacency", nt);
+        return fail(s, SPH_ERR_CAPACITY, "surface: %d triangles, more than 2^31 / 6 for the smoothing's adjacency", nt);
     SURF_ENSURE(s, SB_ADJ_RAW, sizeof(int) * ((size_t)nv + 1), "adjacency");
     SURF_ENSURE(s, SB_ADJ_CNT, sizeof(int) * ((size_t)nv + 1), "adjacency");
     SURF_ENSURE(s, SB_ADJ_SLOT, sizeof(int) * 6 * (size_t)nt, "adjacency");
@@ -327,43 +282,44 @@ static int surf_post(SphSurface *s, int nv, int nt) {
         SURF_ENSURE(s, SB_WEIGHT, sizeof(float) * (size_t)nv, "smoothing weights");
     }
     // surf_scan's tile sums: sized for the coarse grid so far, now for nv as well
-    SURF_ENSURE(s, SB_SCAN, std::max(s->bytes[SB_SCAN], sizeof(int) * ((size_t)nv / 1024 + 2)), "scan");
-    d.scan_tmp = (int *)s->buf[SB_SCAN];
+    SURF_ENSURE(s, SB_SCAN, std::max(s->buf[SB_SCAN].bytes, sizeof(int) * ((size_t)nv / 1024 + 2)), "scan");
+    d.scan_tmp = (int *)s->buf[SB_SCAN].p;
     p = SurfPost{};
     p.nv = nv; p.nt = nt; p.tri = d.tri;
-    p.raw = (int *)s->buf[SB_ADJ_RAW]; p.cnt = (int *)s->buf[SB_ADJ_CNT]; p.slot = (int *)s->buf[SB_ADJ_SLOT];
+    p.raw = (int *)s->buf[SB_ADJ_RAW].p; p.cnt = (int *)s->buf[SB_ADJ_CNT].p; p.slot = (int *)s->buf[SB_ADJ_SLOT].p;
     p.maxdeg = d.bounds + 12;   // (SB_SMALL: see surf_run)
-    p.pc = weights ? (float *)s->buf[SB_PCOUNT] : nullptr;
-    p.w = weights ? (float *)s->buf[SB_WEIGHT] : nullptr;
+    p.pc = weights ? (float *)s->buf[SB_PCOUNT].p : nullptr;
+    p.w = weights ? (float *)s->buf[SB_WEIGHT].p : nullptr;
     p.norm = (float)q.weights_normalization;
-    p.a = (float4 *)s->buf[SB_WORK_A]; p.b = (float4 *)s->buf[SB_WORK_B];
-    SURFCHK(s, hipEventRecord(s->pev[0], st));
+    p.a = (float4 *)s->buf[SB_WORK_A].p; p.b = (float4 *)s->buf[SB_WORK_B].p;
+    HIPCHK(s, s->clk[1].mark(0));
     s->L->surf_post_adjacency(d, p);
     int cnt[2] = {0, 0};   // entries, largest degree
-    SURFCHK(s, hipMemcpyAsync(&cnt[0], p.cnt + nv, sizeof(int), hipMemcpyDeviceToHost, st));
-    SURFCHK(s, hipMemcpyAsync(&cnt[1], p.maxdeg, sizeof(int), hipMemcpyDeviceToHost, st));
-    SURFCHK(s, hipStreamSynchronize(st));
-    if (cnt[0] < 0 || (int64_t)cnt[0] > (int64_t)6 * nt) return surf_fail(s, SPH_ERR_INVALID, "surface: internal adjacency count %d", cnt[0]);
+    HIPCHK(s, hipMemcpyAsync(&cnt[0], p.cnt + nv, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(s, hipMemcpyAsync(&cnt[1], p.maxdeg, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(s, hipStreamSynchronize(st));
+    if (cnt[0] < 0 || (int64_t)cnt[0] > (int64_t)6 * nt) return fail(s, SPH_ERR_INVALID, "surface: internal adjacency count %d", cnt[0]);
     SURF_ENSURE(s, SB_ADJ, sizeof(int) * (size_t)cnt[0], "adjacency");
-    p.adj = (int *)s->buf[SB_ADJ];
+    p.adj = (int *)s->buf[SB_ADJ].p;
     s->L->surf_post_compact(d, p);
-    SURFCHK(s, hipEventRecord(s->pev[1], st));
+    HIPCHK(s, s->clk[1].mark(1));
     if (weights) s->L->surf_post_weights(d, p);   // at the unsmoothed positions
-    SURFCHK(s, hipEventRecord(s->pev[2], st));
+    HIPCHK(s, s->clk[1].mark(2));
     s->L->surf_post_smooth(d, p, q.mesh_smoothing_iters);
-    SURFCHK(s, hipEventRecord(s->pev[3], st));
+    HIPCHK(s, s->clk[1].mark(3));
     if (s->prm.normals && q.mesh_smoothing_iters > 0) s->L->surf_normals(d, nv);   // -grad phi at the smoothed positions
-    SURFCHK(s, hipEventRecord(s->pev[4], st));
+    HIPCHK(s, s->clk[1].mark(4));
     s->L->surf_post_nsmooth(d, p, q.normals_smoothing_iters);
-    SURFCHK(s, hipEventRecord(s->pev[5], st));
-    SURFCHK(s, hipStreamSynchronize(st));
-    SURFCHK(s, hipGetLastError());
+    HIPCHK(s, s->clk[1].mark(5));
+    HIPCHK(s, hipStreamSynchronize(st));
+    HIPCHK(s, hipGetLastError());
     s->have_post = true;
     s->have_weights = weights;
     SphSurfacePostStats &o = s->post_stats;
     o.adjacency_entries = cnt[0]; o.max_degree = cnt[1];
-    o.ms_adjacency = ev_ms(s->pev[0], s->pev[1]); o.ms_weights = ev_ms(s->pev[1], s->pev[2]); o.ms_smoothing = ev_ms(s->pev[2], s->pev[3]);
-    o.ms_normals = ev_ms(s->pev[3], s->pev[4]); o.ms_normal_smoothing = ev_ms(s->pev[4], s->pev[5]); o.ms_total = ev_ms(s->pev[0], s->pev[5]);
+    const StageClock &c = s->clk[1];
+    o.ms_adjacency = c.ms(0, 1); o.ms_weights = c.ms(1, 2); o.ms_smoothing = c.ms(2, 3);
+    o.ms_normals = c.ms(3, 4); o.ms_normal_smoothing = c.ms(4, 5); o.ms_total = c.ms(0, 5);
     return SPH_OK;
 }
 
@@ -371,12 +327,12 @@ extern "C" int sph_surface_set_postprocess(SphSurface *s, const SphSurfacePostPa
     if (!s || !params) return SPH_ERR_INVALID;
     const SphSurfacePostParams q = *params;
     if (q.mesh_smoothing_iters < 0 || q.normals_smoothing_iters < 0)
-        return surf_fail(s, SPH_ERR_INVALID, "sph_surface_set_postprocess: negative iteration count");
+        return fail(s, SPH_ERR_INVALID, "sph_surface_set_postprocess: negative iteration count");
     if (!std::isfinite(q.weights_normalization) || !(q.weights_normalization > 0.0) || !std::isfinite((float)q.weights_normalization) ||
         !((float)q.weights_normalization > 0.0f))
-        return surf_fail(s, SPH_ERR_INVALID, "sph_surface_set_postprocess: weights_normalization must be positive and finite");
+        return fail(s, SPH_ERR_INVALID, "sph_surface_set_postprocess: weights_normalization must be positive and finite");
     if (q.normals_smoothing_iters > 0 && !s->prm.normals)
-        return surf_fail(s, SPH_ERR_INVALID, "sph_surface_set_postprocess: normal smoothing on an object created without normals");
+        return fail(s, SPH_ERR_INVALID, "sph_surface_set_postprocess: normal smoothing on an object created without normals");
     s->post = q;
     return SPH_OK;
 }
@@ -390,14 +346,14 @@ extern "C" int sph_surface_post_stats(SphSurface *s, SphSurfacePostStats *out) {
 extern "C" int sph_surface_download_post(SphSurface *s, int32_t *offsets, int32_t *neighbours, float *weights) {
     if (!s) return SPH_ERR_INVALID;
     if (!s->have_mesh || !s->have_post)
-        return surf_fail(s, SPH_ERR_INVALID, "sph_surface_download_post: the last reconstruction ran no smoothing");
-    SURFCHK(s, hipSetDevice(s->device));
+        return fail(s, SPH_ERR_INVALID, "sph_surface_download_post: the last reconstruction ran no smoothing");
+    HIPCHK(s, hipSetDevice(s->device));
     const size_t nv = (size_t)s->nv, ne = (size_t)s->post_stats.adjacency_entries;
-    if (offsets && nv) SURFCHK(s, hipMemcpy(offsets, s->p.cnt, sizeof(int) * (nv + 1), hipMemcpyDeviceToHost));
+    if (offsets && nv) HIPCHK(s, hipMemcpy(offsets, s->p.cnt, sizeof(int) * (nv + 1), hipMemcpyDeviceToHost));
     else if (offsets) offsets[0] = 0;
-    if (neighbours && ne) SURFCHK(s, hipMemcpy(neighbours, s->p.adj, sizeof(int) * ne, hipMemcpyDeviceToHost));
+    if (neighbours && ne) HIPCHK(s, hipMemcpy(neighbours, s->p.adj, sizeof(int) * ne, hipMemcpyDeviceToHost));
     if (weights) {
-        if (s->have_weights) { if (nv) SURFCHK(s, hipMemcpy(weights, s->p.w, sizeof(float) * nv, hipMemcpyDeviceToHost)); }
+        if (s->have_weights) { if (nv) HIPCHK(s, hipMemcpy(weights, s->p.w, sizeof(float) * nv, hipMemcpyDeviceToHost)); }
         else for (size_t i = 0; i < nv; ++i) weights[i] = 1.0f;
     }
     return SPH_OK;

@@ -18,19 +18,18 @@ BOX_RGB = (252, 173, 71)   # the reference's (0.99, 0.68, 0.28), floor(255 x + 0
 
 
 class RenderError(L.SphError):
-    def __init__(self, msg, code):
-        super().__init__(msg)
-        self.code = code
+    pass
 
 
-class FrameRenderer:
+class FrameRenderer(L.NativeObject):
     """One renderer (camera and frame buffers fixed at creation).  Defaults: the reference's camera, light and background; box=None
     draws no box in from_points, while from_container draws [0, domainEnd] unless box=False."""
+    ABI, Error = "sph_render", RenderError
 
     def __init__(self, radius, width=1024, height=1024, camera_position=(5.5, 2.5, 4.0), camera_lookat=(-1.0, 0.0, 0.0),
                  camera_up=(0.0, 1.0, 0.0), fov=70.0, z_near=0.1, light_position=(2.0, 2.0, 2.0), light_color=(1.0, 1.0, 1.0),
                  ambient=0.1, background=(0, 0, 0), box=None, box_color=BOX_RGB, fast_math=False, device=-1):
-        self.lib = L.load()
+        super().__init__()
         self.radius = float(radius)
         self.width, self.height = int(width), int(height)
         self.box = box
@@ -62,40 +61,23 @@ class FrameRenderer:
         key = None if box is None else (tuple(float(v) for v in box[0]), tuple(float(v) for v in box[1]))
         h = self._handles.get(key)
         if h is None:
-            h = C.c_void_p()
-            rc = self.lib.sph_render_create(C.byref(self._params(key)), C.byref(h))
-            if rc != 0:
-                msg = self.lib.sph_render_last_error(None)
-                raise RenderError(f"sph_render_create failed ({rc}): {msg.decode() if msg else ''}", rc)
-            self._handles[key] = h
+            h = self._handles[key] = self._create(self._params(key))
         return h
 
     def close(self):
-        for h in getattr(self, "_handles", {}).values():
-            self.lib.sph_render_destroy(h)
+        super().close()
         self._handles = {}
         self._last = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, h, rc, what):
-        if rc != 0:
-            msg = self.lib.sph_render_last_error(h)
-            raise RenderError(f"{what} failed ({rc}): {msg.decode() if msg else ''}", rc)
-
     def _download(self, h):
         rgb = np.empty((self.height, self.width, 3), np.uint8)
-        self._chk(h, self.lib.sph_render_download(h, rgb.ctypes.data, None), "sph_render_download")
+        self._chk(self.lib.sph_render_download(h, rgb.ctypes.data, None), "sph_render_download", h)
         self._last = h
         return rgb
 
     def _need(self, kind, what):
         if self._last is None or self._last_kind != kind:
-            raise RenderError(f"{what}: the last frame is not a {'mesh' if kind == 'meshes' else 'particle'} frame", -1)
+            raise RenderError(f"{what}: the last frame is not a {'mesh' if kind == 'meshes' else 'particle'} frame", L.ERR_INVALID)
 
     def from_points(self, xyz, colors=None, ids=None):
         """uint8 (H, W, 3) of spheres at xyz f32[n, 3], colours uint8[n, 3] (None: white), distinct ids < 0xFFFFFFF0 (None: 0..n-1)."""
@@ -105,8 +87,8 @@ class FrameRenderer:
         if (c is not None and len(c) != len(x)) or (i is not None and len(i) != len(x)):
             raise ValueError("from_points: xyz, colors and ids must have one row per particle")
         h = self._native(self.box if self.box else None)
-        self._chk(h, self.lib.sph_render_points(h, x.ctypes.data, None if c is None else c.ctypes.data,
-                                                None if i is None else i.ctypes.data, x.shape[0]), "sph_render_points")
+        self._chk(self.lib.sph_render_points(h, x.ctypes.data, None if c is None else c.ctypes.data,
+                                             None if i is None else i.ctypes.data, x.shape[0]), "sph_render_points", h)
         self._last_kind = "points"
         return self._download(h)
 
@@ -124,7 +106,7 @@ class FrameRenderer:
         if box is None:
             box = (np.zeros(3), np.asarray(container.domain_end, dtype=np.float64))
         h = self._native(box if box is not False else None)
-        self._chk(h, self.lib.sph_render_handle(h, engine.h, C.c_uint32(mask)), "sph_render_handle")
+        self._chk(self.lib.sph_render_handle(h, engine.h, C.c_uint32(mask)), "sph_render_handle", h)
         self._last_kind = "points"
         return self._download(h)
 
@@ -135,13 +117,13 @@ class FrameRenderer:
         an index outside its mesh is skipped and raises RenderError (code -1) after the frame is drawn: last_rgb() / ids() still give it."""
         h = self._native(self.box if self.box else None)
         self._last = self._last_kind = self._mesh_starts = None
-        self._chk(h, self.lib.sph_render_mesh_begin(h), "sph_render_mesh_begin")
+        self._chk(self.lib.sph_render_mesh_begin(h), "sph_render_mesh_begin", h)
         starts = [0]
         for item in meshes:
             col = np.ascontiguousarray(item[-1], dtype=np.uint8).reshape(3)
             if len(item) == 2:
                 recon = item[0]
-                self._chk(h, self.lib.sph_render_mesh_add_surface(h, recon.h, col.ctypes.data), "sph_render_mesh_add_surface")
+                self._chk(self.lib.sph_render_mesh_add_surface(h, recon.h, col.ctypes.data), "sph_render_mesh_add_surface", h)
                 nv, nt = C.c_int64(), C.c_int64()
                 recon._chk(self.lib.sph_surface_mesh_size(recon.h, C.byref(nv), C.byref(nt)), "sph_surface_mesh_size")
                 starts.append(starts[-1] + nt.value)
@@ -151,30 +133,30 @@ class FrameRenderer:
             n = None if item[2] is None else np.ascontiguousarray(item[2], dtype=np.float32).reshape(-1, 3)
             if n is not None and len(n) != len(v):
                 raise ValueError("from_meshes: normals must have one row per vertex")
-            self._chk(h, self.lib.sph_render_mesh_add(h, v.ctypes.data, None if n is None else n.ctypes.data, t.ctypes.data, v.shape[0],
-                                                      t.shape[0], col.ctypes.data), "sph_render_mesh_add")
+            self._chk(self.lib.sph_render_mesh_add(h, v.ctypes.data, None if n is None else n.ctypes.data, t.ctypes.data, v.shape[0],
+                                                   t.shape[0], col.ctypes.data), "sph_render_mesh_add", h)
             starts.append(starts[-1] + t.shape[0])
         rc = self.lib.sph_render_mesh_end(h)
         self._mesh_starts = np.asarray(starts, np.int64)
-        if rc == -1:
+        if rc == L.ERR_INVALID:
             st = L.SphRenderMeshStats()
             if self.lib.sph_render_mesh_stats(h, C.byref(st)) == 0 and st.bad_index > 0:
                 self._last, self._last_kind = h, "meshes"   # drawn, with the bad triangles skipped
-        self._chk(h, rc, "sph_render_mesh_end")
+        self._chk(rc, "sph_render_mesh_end", h)
         self._last_kind = "meshes"
         return self._download(h)
 
     def last_rgb(self):
         """uint8 (H, W, 3) of the last frame once more."""
         if self._last is None:
-            raise RenderError("last_rgb: no frame rendered yet", -1)
+            raise RenderError("last_rgb: no frame rendered yet", L.ERR_INVALID)
         return self._download(self._last)
 
     def mesh_stats(self):
         self._need("meshes", "mesh_stats")
         st = L.SphRenderMeshStats()
-        self._chk(self._last, self.lib.sph_render_mesh_stats(self._last, C.byref(st)), "sph_render_mesh_stats")
-        return {k: getattr(st, k) for k, _ in L.SphRenderMeshStats._fields_}
+        self._chk(self.lib.sph_render_mesh_stats(self._last, C.byref(st)), "sph_render_mesh_stats", self._last)
+        return L.struct_dict(st)
 
     def mesh_of(self, ids):
         """The index in the last from_meshes list of the mesh that owns each triangle id (negative ids -- background, lines -- stay)."""
@@ -187,17 +169,17 @@ class FrameRenderer:
         """int32 (H, W) of the last frame: the winner's particle id (particle frames) or global triangle index (mesh frames), -1
         background, -2 - edge a box line."""
         if self._last is None:
-            raise RenderError("ids: no frame rendered yet", -1)
+            raise RenderError("ids: no frame rendered yet", L.ERR_INVALID)
         rgb = np.empty((self.height, self.width, 3), np.uint8)
         out = np.empty((self.height, self.width), np.int32)
-        self._chk(self._last, self.lib.sph_render_download(self._last, rgb.ctypes.data, out.ctypes.data), "sph_render_download")
+        self._chk(self.lib.sph_render_download(self._last, rgb.ctypes.data, out.ctypes.data), "sph_render_download", self._last)
         return out
 
     def stats(self):
         self._need("points", "stats")
         st = L.SphRenderStats()
-        self._chk(self._last, self.lib.sph_render_stats(self._last, C.byref(st)), "sph_render_stats")
-        return {k: getattr(st, k) for k, _ in L.SphRenderStats._fields_}
+        self._chk(self.lib.sph_render_stats(self._last, C.byref(st)), "sph_render_stats", self._last)
+        return L.struct_dict(st)
 
 
 def _chunk(tag, data):

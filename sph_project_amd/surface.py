@@ -12,49 +12,27 @@ import numpy as np
 
 from . import _lib as L
 
-SPH_ERR_CAPACITY = -2
+SPH_ERR_CAPACITY = L.ERR_CAPACITY
 
 
 class SurfaceError(L.SphError):
-    def __init__(self, msg, code):
-        super().__init__(msg)
-        self.code = code
+    pass
 
 
-class SurfaceReconstructor:
+class SurfaceReconstructor(L.NativeObject):
     """One reconstruction object (device buffers reused from frame to frame).  Defaults: the reference's splashsurf command
     (`-l 3.5 -c=0.5 -t=0.6 --normals=on`)."""
+    ABI, Error = "sph_surface", SurfaceError
 
     def __init__(self, radius, smoothing_length=3.5, cube_size=0.5, iso=0.6, normals=True, memory_cap_bytes=0, fast_math=False,
                  device=-1):
-        self.lib = L.load()
+        super().__init__()
         self.normals = bool(normals)
         p = L.SphSurfaceParams(radius=float(radius), smoothing_length=float(smoothing_length), cube_size=float(cube_size), iso=float(iso),
                                normals=int(self.normals), fast_math=int(bool(fast_math)), device=int(device), reserved=0,
                                memory_cap_bytes=int(memory_cap_bytes))
-        h = C.c_void_p()
-        rc = self.lib.sph_surface_create(C.byref(p), C.byref(h))
-        if rc != 0:
-            msg = self.lib.sph_surface_last_error(None)
-            raise SurfaceError(f"sph_surface_create failed ({rc}): {msg.decode() if msg else ''}", rc)
-        self.h = h
+        self.h = self._create(p)
         self.mesh = None
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.sph_surface_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _chk(self, rc, what):
-        if rc != 0:
-            msg = self.lib.sph_surface_last_error(self.h)
-            raise SurfaceError(f"{what} failed ({rc}): {msg.decode() if msg else ''}", rc)
 
     def _download(self):
         nv, nt = C.c_int64(), C.c_int64()
@@ -82,7 +60,7 @@ class SurfaceReconstructor:
     def stats(self):
         st = L.SphSurfaceStats()
         self._chk(self.lib.sph_surface_stats(self.h, C.byref(st)), "sph_surface_stats")
-        return {k: getattr(st, k) for k, _ in L.SphSurfaceStats._fields_ if k != "reserved"}
+        return L.struct_dict(st, skip=("reserved",))
 
     def set_postprocess(self, mesh_smoothing_iters=0, mesh_smoothing_weights=False, weights_normalization=13.0, normals_smoothing_iters=0):
         """Smoothing of the reconstructions that follow (splashsurf's --mesh-smoothing-iters, --mesh-smoothing-weights,
@@ -95,7 +73,7 @@ class SurfaceReconstructor:
     def post_stats(self):
         st = L.SphSurfacePostStats()
         self._chk(self.lib.sph_surface_post_stats(self.h, C.byref(st)), "sph_surface_post_stats")
-        return {k: getattr(st, k) for k, _ in L.SphSurfacePostStats._fields_ if k != "reserved"}
+        return L.struct_dict(st, skip=("reserved",))
 
     def adjacency(self):
         """(offsets i32[nv+1], neighbours i32[offsets[-1]]): the vertex adjacency (CSR) of the last reconstruction's smoothing."""
@@ -120,7 +98,7 @@ class SurfaceReconstructor:
     def write_obj(self, path):
         """The last mesh as ASCII OBJ (write_obj below)."""
         if self.mesh is None:
-            raise SurfaceError("write_obj: no mesh reconstructed yet", -1)
+            raise SurfaceError("write_obj: no mesh reconstructed yet", L.ERR_INVALID)
         write_obj(path, *self.mesh)
 
 
