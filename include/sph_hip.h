@@ -560,6 +560,59 @@ int sph_render_mesh_add_surface(SphRender *r, SphSurface *s, const uint8_t rgb[3
 int sph_render_mesh_end(SphRender *r);
 int sph_render_mesh_stats(SphRender *r, SphRenderMeshStats *out);
 
+/* --- video encoding: RGB frames -> baseline JPEG streams, the frames of a Motion-JPEG AVI ------------------------- */
+/* stands in for the reference's make_video.py (imageio): every frame is compressed on the device it was rendered on; the AVI
+   container around the frames is written on the host (sph_project_amd/video.py).  One frame is one complete .jpg file: baseline
+   sequential DCT (SOF0), 8 bit, three components, JFIF header, full-range BT.601 YCbCr, chroma 4:2:0 or 4:4:4, the quantisation
+   tables of T.81 Annex K scaled by `quality` with the IJG rule, the Annex K Huffman tables, a restart interval of 8 MCUs (DRI; the
+   intervals are what the device codes in parallel).  A picture whose size is no multiple of the MCU is padded by repeating its last
+   column and row.  The pixel-to-coefficient arithmetic is integer fixed point, so the bytes are a function of (pixels,
+   width, height, quality, chroma): the same from both builds and from every call.  The device does colour conversion, DCT,
+   quantisation, zigzag, run/size symbols, DC prediction, Huffman coding, bit packing, 0xFF stuffing and the restart markers; the host
+   writes the fixed headers and EOI.  The output is sized from a counting pass: a stream is never truncated.  One HIP stream per
+   object; synchronous calls.
+   Two things beyond the minimum: `fast_math` selects the strict or the fast build's launchers as it does in the surface and render
+   objects (the bytes do not depend on it; it is how one process reaches both builds to show that), and sph_video_header gives the
+   fixed headers without a device, so that the tables and segment layout can be checked against the standard on a host that has
+   no GPU (tests/test_video_host.py does) and a muxer can know the header length before the first frame. */
+typedef struct {
+    int32_t width, height;   /* pixels; each 1..16384, width * height <= 2^26 */
+    int32_t quality;         /* 1..100 */
+    int32_t chroma;          /* 420 or 444 */
+    int32_t fast_math;       /* which build's launchers run (0 strict, 1 fast); the bytes are the same */
+    int32_t device;          /* HIP device ordinal, -1: current */
+    int32_t reserved;        /* 0 */
+} SphVideoParams;
+
+typedef struct {
+    int64_t blocks;            /* 8 x 8 blocks coded (padding included) */
+    int64_t scan_bytes;        /* entropy-coded bytes between SOS and EOI: stuffed zeros and restart markers included */
+    int64_t stuffed_bytes;     /* zeros stuffed behind 0xFF bytes */
+    int64_t restart_intervals;
+    double ms_input;           /* HIP events: upload of a host image (~0 for a renderer's frame) */
+    double ms_count;           /* first pass: bytes per restart interval */
+    double ms_scan;            /* their scan, the total read by the host */
+    double ms_write;           /* second pass: the bytes */
+    double ms_total;
+} SphVideoStats;
+
+typedef struct SphVideo SphVideo;
+/* SPH_ERR_INVALID (before any device is touched): a size, quality or chroma outside the ranges above, reserved != 0 */
+int sph_video_create(const SphVideoParams *params, SphVideo **out);
+void sph_video_destroy(SphVideo *v);
+const char *sph_video_last_error(SphVideo *v);
+/* the fixed headers (SOI ... SOS) of every stream of these parameters: *bytes their length, dst_or_NULL filled when given.  Host only. */
+int sph_video_header(const SphVideoParams *params, uint8_t *dst_or_NULL, int64_t *bytes);
+/* a host image u8[height][width][3], rows from the top */
+int sph_video_encode_rgb(SphVideo *v, const uint8_t *rgb);
+/* the renderer's last frame (particles or meshes), read from its device buffer: not downloaded, nothing of the renderer modified.
+   SPH_ERR_INVALID with a message: no frame rendered yet, a frame of another size, a renderer on another device. */
+int sph_video_encode_render(SphVideo *v, SphRender *r);
+/* the last encoded frame: the length of the complete .jpg file, and the file (headers, scan, EOI) */
+int sph_video_size(SphVideo *v, int64_t *bytes);
+int sph_video_download(SphVideo *v, uint8_t *dst);
+int sph_video_stats(SphVideo *v, SphVideoStats *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,20 @@ class SphRenderMeshStats(C.Structure):
     ]
 
 
+class SphVideoParams(C.Structure):
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("quality", C.c_int32), ("chroma", C.c_int32), ("fast_math", C.c_int32),
+        ("device", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class SphVideoStats(C.Structure):
+    _fields_ = [
+        ("blocks", C.c_int64), ("scan_bytes", C.c_int64), ("stuffed_bytes", C.c_int64), ("restart_intervals", C.c_int64),
+        ("ms_input", C.c_double), ("ms_count", C.c_double), ("ms_scan", C.c_double), ("ms_write", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 # return codes (include/sph_hip.h)
 ERR_INVALID, ERR_CAPACITY = -1, -2
 
@@ -229,6 +243,15 @@ _SIGNATURES = [
     ("sph_render_mesh_add_surface", C.c_int, [_VP, _VP, _VP]),
     ("sph_render_mesh_end", C.c_int, [_VP]),
     ("sph_render_mesh_stats", C.c_int, [_VP, C.POINTER(SphRenderMeshStats)]),
+    ("sph_video_create", C.c_int, [C.POINTER(SphVideoParams), C.POINTER(_VP)]),
+    ("sph_video_destroy", None, [_VP]),
+    ("sph_video_last_error", C.c_char_p, [_VP]),
+    ("sph_video_header", C.c_int, [C.POINTER(SphVideoParams), _VP, C.POINTER(C.c_int64)]),
+    ("sph_video_encode_rgb", C.c_int, [_VP, _VP]),
+    ("sph_video_encode_render", C.c_int, [_VP, _VP]),
+    ("sph_video_size", C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    ("sph_video_download", C.c_int, [_VP, _VP]),
+    ("sph_video_stats", C.c_int, [_VP, C.POINTER(SphVideoStats)]),
     ("sph_comm_allreduce", C.c_int, [_VP, C.POINTER(C.c_double), C.c_int, C.c_int]),
     ("sph_comm_barrier", C.c_int, [_VP]),
     ("sph_comm_selftest", C.c_int, [_VP, C.c_int]),

@@ -269,6 +269,22 @@ struct MeshDev {
     unsigned *large;                   // [nt] triangles whose screen bounds exceed RENDER_LARGE_PX pixels
 };
 
+// Video encoding (sph_video.hpp): one frame -> the scan of a baseline JPEG.  A restart interval is VIDEO_RI MCUs (the
+// DRI segment says so) and the work of one workgroup.  Table entries: q the quantiser steps in natural order ([0] luminance, [1]
+// chrominance); dc / ac the Huffman code of a symbol | its length << 16.
+#define VIDEO_RI 8
+struct VideoTables { unsigned short q[2][64]; unsigned dc[2][12]; unsigned ac[2][256]; };
+struct VideoDev {
+    int W, H, c420;                    // c420: 1 = 4:2:0 (MCU 16 x 16, 6 blocks), 0 = 4:4:4 (MCU 8 x 8, 3 blocks)
+    int mw, nmcu, nint;                // MCUs across, in all; restart intervals
+    const unsigned char *rgb;          // [H][W][3] the frame (the encoder's upload or a renderer's frame buffer)
+    const VideoTables *tab;
+    int *len;                          // [nint + 1] bytes per interval, stuffing and marker included -> their exclusive scan, [nint] the total
+    unsigned long long *cnt;           // [2] stuffed bytes
+    unsigned char *out;                // the scan's bytes
+    hipStream_t stream;
+};
+
 template <class T> struct DBuf {
     T *b[2] = {nullptr, nullptr};
     int c = 0;
@@ -503,6 +519,10 @@ struct Launch {
     void (*render_mesh_depth)(RenderDev &, MeshDev &);   // depth keys of triangles (small per thread, large per workgroup) and box lines
     void (*render_mesh_shade)(RenderDev &, MeshDev &);   // the winners' colours (triangles, lines)
     void (*render_mesh_finish)(RenderDev &);             // background / ids / covered count per pixel
+    // video encoding (sph_video.hpp)
+    void (*video_count)(VideoDev &);            // bytes per restart interval (transform, symbols, stuffing; nothing stored but the counts)
+    void (*video_scan)(VideoDev &);             // their exclusive scan, the total behind it
+    void (*video_write)(VideoDev &);            // the same bytes again, stored at the scanned offsets
     void (*layer_hist)(State &, int *hist);      // owned particles per global cell layer
     void (*loop_criterion)(State &, int slot);   // stop test on an all-reduced residual (sharded solver loops)
     // push transport: the step message is written by halo_classify_pack itself; then

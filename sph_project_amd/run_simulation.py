@@ -8,7 +8,8 @@ Frames go to {scene_name}_output/{cnt:06}/particle_object_{id}.ply (ASCII PLY, x
 layout Taichi's PLYWriter.export_ascii produces and surface_reconstruction.py / splashsurf consume).
 Rigid bodies: mesh_object_{id}.obj per frame with exportObj (:146-150).  PNG frames (exportFrame, :131-134) come from the GPU
 renderer of render.py with --render (its own image, not GGUI's: DESIGN.md 15); without --render none is written.  --render_meshes
-writes {cnt:06}/render.png, the frame's meshes drawn on the GPU, where the reference's render.py needs Blender."""
+writes {cnt:06}/render.png, the frame's meshes drawn on the GPU, where the reference's render.py needs Blender.  --video
+adds {out}/raw_view.avi / {out}/render.avi, the same frames as Motion-JPEG compressed on the GPU (make_video.py)."""
 import argparse
 import os
 import sys
@@ -91,7 +92,17 @@ def parse_args(argv=None):
     parser.add_argument("--camera_position", type=float, nargs=3, default=(5.5, 2.5, 4.0))
     parser.add_argument("--camera_lookat", type=float, nargs=3, default=(-1.0, 0.0, 0.0))
     parser.add_argument("--camera_fov", type=float, default=70.0, help="vertical, degrees")
-    return parser.parse_args(argv)
+    parser.add_argument("--video", action="store_true",
+                        help="with --render also write {out}/raw_view.avi, with --render_meshes {out}/render.avi: one Motion-JPEG frame per "
+                             "output frame, compressed on the GPU from the device image the PNG is written from (DESIGN.md 18; what "
+                             "make_video.py makes of the directory afterwards)")
+    parser.add_argument("--video_fps", type=int, default=20, help="make_video.py's --fps")
+    parser.add_argument("--video_quality", type=int, default=90, help="JPEG quality 1..100")
+    parser.add_argument("--video_chroma", default="420", choices=["420", "444"])
+    args = parser.parse_args(argv)
+    if args.video and not (args.render or args.render_meshes):
+        parser.error("--video takes its frames from a renderer: give --render and / or --render_meshes as well")
+    return args
 
 
 def surface_postprocess(args):
@@ -174,55 +185,73 @@ def main(argv=None):
         mesh_renderer = FrameRenderer(container.dx, width=args.render_size[0], height=args.render_size[1],
                                       camera_position=args.camera_position, camera_lookat=args.camera_lookat, fov=args.camera_fov,
                                       box=(np.zeros(3), np.asarray(container.domain_end, dtype=np.float64)))
+    videos = {}   # renderer -> (encoder, AVI writer)
+    if args.video:
+        from sph_project_amd.video import AviWriter, VideoEncoder
+        for r, name in ((renderer, "raw_view.avi"), (mesh_renderer, "render.avi")):
+            if r is not None:
+                videos[r] = (VideoEncoder(r.width, r.height, quality=args.video_quality, chroma=args.video_chroma),
+                             AviWriter(f"{out_dir}/{name}", r.width, r.height, args.video_fps))
+
+    def add_video_frame(r):
+        if r in videos:
+            encoder, writer = videos[r]
+            writer.add(encoder.encode_last(r))
     cnt = 0
     limit = total_rounds if args.max_steps is None else min(total_rounds, args.max_steps)
     limit = max(limit, 1)   # the reference's loop steps once before it looks at the round count
     t0 = time.perf_counter()
     t_export, frames = 0.0, 0
-    while cnt < limit:
-        # run_simulation.py:126-153 steps once, writes a frame if the count of steps BEFORE this one is a multiple of the
-        # interval, then counts.  Same frames here, but the steps between two frames go to the device in one call.
-        wants_frame = output_ply or output_obj or output_frames or args.render_meshes
-        nxt = cnt if cnt % output_interval == 0 else cnt + output_interval - cnt % output_interval   # next count that gets a frame
-        if not wants_frame or nxt >= limit:
-            solver.advance(limit - cnt)
-            cnt = limit
-            break
-        solver.advance(nxt - cnt + 1)
-        cnt = nxt
+    try:
+        while cnt < limit:
+            # run_simulation.py:126-153 steps once, writes a frame if the count of steps BEFORE this one is a multiple of the
+            # interval, then counts.  Same frames here, but the steps between two frames go to the device in one call.
+            wants_frame = output_ply or output_obj or output_frames or args.render_meshes
+            nxt = cnt if cnt % output_interval == 0 else cnt + output_interval - cnt % output_interval   # next count that gets a frame
+            if not wants_frame or nxt >= limit:
+                solver.advance(limit - cnt)
+                cnt = limit
+                break
+            solver.advance(nxt - cnt + 1)
+            cnt = nxt
+            container.engine.synchronize()
+            te = time.perf_counter()
+            wrote = False
+            held = set()
+            if output_frames:   # run_simulation.py:131-134
+                os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
+                write_png(f"{out_dir}/{cnt:06}/raw_view.png", renderer.from_container(container))
+                add_video_frame(renderer)
+                wrote = True
+            if output_ply:
+                os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
+                for f_body_id in container.object_id_fluid_body:
+                    write_ply_ascii(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.ply", container.dump(obj_id=f_body_id)["position"])
+                    if args.reconstruct:   # what surface_reconstruction.py would make of that PLY, without reading it back
+                        recon.from_container(container, f_body_id)
+                        recon.write_obj(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.obj")
+                        held = {f_body_id}   # the reconstructor still holds this object's mesh: the mesh frame below need not redo it
+                    wrote = True
+            if output_obj:   # run_simulation.py:146-150
+                os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
+                for r_body_id in container.object_id_rigid_body:
+                    if "mesh" not in container.object_collection[r_body_id]:   # body given as pre-voxelised points only
+                        continue
+                    with open(f"{out_dir}/{cnt:06}/mesh_object_{r_body_id}.obj", "w") as f:
+                        f.write(container.object_collection[r_body_id]["mesh"].export(file_type="obj"))
+                    wrote = True
+            if mesh_renderer is not None:   # render.py: every mesh of the frame -> {frame}/render.png
+                os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
+                write_png(f"{out_dir}/{cnt:06}/render.png", mesh_renderer.from_meshes(frame_meshes(container, solver, recon, held)))
+                add_video_frame(mesh_renderer)
+                wrote = True
+            frames += 1 if wrote else 0
+            t_export += time.perf_counter() - te
+            cnt += 1
         container.engine.synchronize()
-        te = time.perf_counter()
-        wrote = False
-        held = set()
-        if output_frames:   # run_simulation.py:131-134
-            os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
-            write_png(f"{out_dir}/{cnt:06}/raw_view.png", renderer.from_container(container))
-            wrote = True
-        if output_ply:
-            os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
-            for f_body_id in container.object_id_fluid_body:
-                write_ply_ascii(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.ply", container.dump(obj_id=f_body_id)["position"])
-                if args.reconstruct:   # what surface_reconstruction.py would make of that PLY, without reading it back
-                    recon.from_container(container, f_body_id)
-                    recon.write_obj(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.obj")
-                    held = {f_body_id}   # the reconstructor still holds this object's mesh: the mesh frame below need not redo it
-                wrote = True
-        if output_obj:   # run_simulation.py:146-150
-            os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
-            for r_body_id in container.object_id_rigid_body:
-                if "mesh" not in container.object_collection[r_body_id]:   # body given as pre-voxelised points only
-                    continue
-                with open(f"{out_dir}/{cnt:06}/mesh_object_{r_body_id}.obj", "w") as f:
-                    f.write(container.object_collection[r_body_id]["mesh"].export(file_type="obj"))
-                wrote = True
-        if mesh_renderer is not None:   # render.py: every mesh of the frame -> {frame}/render.png
-            os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
-            write_png(f"{out_dir}/{cnt:06}/render.png", mesh_renderer.from_meshes(frame_meshes(container, solver, recon, held)))
-            wrote = True
-        frames += 1 if wrote else 0
-        t_export += time.perf_counter() - te
-        cnt += 1
-    container.engine.synchronize()
+    finally:   # an exception in the loop still leaves well-formed videos of the frames written so far
+        for _, writer in videos.values():
+            writer.close()
     dt = time.perf_counter() - t0
     # frame export (ASCII PLY of every fluid particle, OBJ of every rigid mesh: run_simulation.py:137-150) is host file I/O and can
     # dwarf the simulation -- 1.3 s per frame for the 1.23 M particles of final_scene0.json -- so it is reported apart from the steps

@@ -1,0 +1,154 @@
+"""GPU: the JPEG encoder (csrc/sph_video.hpp) against the test-owned encoder of tests/jpeg_model.py, byte for byte, in both
+builds; the stuffing path; repeat; a renderer's frame read in place (particles, meshes) with the renderer left untouched; the
+refusals; a C2 frame at full size; the driver's --video and make_video.py."""
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+
+from sph_project_amd import _lib as L
+from sph_project_amd import product as P
+from sph_project_amd.render import FrameRenderer
+from sph_project_amd.video import VideoEncoder, VideoError, decode_png
+from tests import helpers as H
+from tests import jpeg_model as JM
+from tests.test_video_host import avi_frames, picture
+
+pytestmark = pytest.mark.gpu
+
+SIZES = [(1024, 1024), (640, 480), (37, 53), (8, 8), (1, 1)]   # width, height
+
+
+@functools.lru_cache(maxsize=None)
+def _case(width, height, quality, chroma):
+    """picture, the model's file, the model's counts"""
+    kind = "discs" if width * height > 400000 else "noise" if width * height < 5000 else "mixed"
+    img = picture(kind, width, height, seed=width + height)
+    info = {}
+    return img, JM.encode(img, quality, chroma, info), info
+
+
+@pytest.mark.parametrize("fast", [False, True])
+@pytest.mark.parametrize("chroma", ["420", "444"])
+@pytest.mark.parametrize("quality", [50, 90, 100])
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_bytes_equal_the_model(gpu, size, quality, chroma, fast):
+    img, want, info = _case(size[0], size[1], quality, chroma)
+    v = VideoEncoder(size[0], size[1], quality=quality, chroma=chroma, fast_math=fast)
+    got = v.encode(img)
+    st = v.stats()
+    print(f"{size} q{quality} {chroma} fast={fast}: {len(got)} bytes (model {len(want)}), stats {st}")
+    assert {k: st[k] for k in info} == info
+    assert got == want
+    assert v.encode(img) == got   # a repeated call
+
+
+def test_stuffing_is_exercised(gpu):
+    img, want, info = _case(640, 480, 100, "444")
+    assert info["stuffed_bytes"] > 0 and info["restart_intervals"] > 8   # the model's own stream stuffs; RST0..RST7 wrap around
+    v = VideoEncoder(640, 480, quality=100, chroma="444")
+    assert v.encode(img) == want
+    st = v.stats()
+    assert st["stuffed_bytes"] == info["stuffed_bytes"]
+    hdr = len(JM.header(640, 480, 100, "444"))
+    assert st["scan_bytes"] == len(want) - hdr - 2 == info["scan_bytes"]
+
+
+def _particle_renderer(width=320, height=240):
+    rng = np.random.default_rng(11)
+    x = rng.uniform(0.0, 2.0, (4000, 3)).astype(np.float32)
+    c = rng.integers(0, 256, (4000, 3), dtype=np.uint8)
+    r = FrameRenderer(0.03, width=width, height=height, box=((0, 0, 0), (2, 2, 2)))
+    r.from_points(x, c)
+    return r
+
+
+def _mesh_renderer(width=320, height=240):
+    v = np.array([[0, 0, 0], [2, 0, 0], [2, 2, 0], [0, 2, 0], [1, 1, 1.5]], np.float32)
+    t = np.array([[0, 1, 4], [1, 2, 4], [2, 3, 4], [3, 0, 4], [0, 2, 1], [0, 3, 2]], np.int32)
+    r = FrameRenderer(0.03, width=width, height=height, box=((0, 0, 0), (2, 2, 2)))
+    r.from_meshes([(v, t, None, (60, 140, 230))])
+    return r
+
+
+@pytest.mark.parametrize("make", [_particle_renderer, _mesh_renderer], ids=["particles", "meshes"])
+def test_encode_last_reads_the_renderers_frame_in_place(gpu, make):
+    r = make()
+    rgb, ids = r.last_rgb(), r.ids()
+    assert (ids >= 0).sum() > 500
+    v = VideoEncoder(320, 240, quality=90)
+    a = v.encode_last(r)
+    assert a == v.encode(rgb) == JM.encode(rgb, 90, "420")
+    assert r.last_rgb().tobytes() == rgb.tobytes() and r.ids().tobytes() == ids.tobytes()
+
+
+def test_refusals_carry_messages(gpu):
+    v = VideoEncoder(320, 240)
+    with pytest.raises(VideoError, match="no frame"):
+        v.encode_last(FrameRenderer(0.03, width=320, height=240))
+    fresh = FrameRenderer(0.03, width=320, height=240)
+    fresh._last = fresh._native(None)   # a native renderer that has drawn nothing yet
+    with pytest.raises(VideoError, match="holds no frame"):
+        v.encode_last(fresh)
+    with pytest.raises(VideoError, match="320 x 240"):
+        v.encode_last(_particle_renderer(256, 256))
+    if L.load().sph_device_count() > 1:
+        other = VideoEncoder(320, 240, device=1)
+        with pytest.raises(VideoError, match="device"):
+            other.encode_last(_particle_renderer())
+    else:   # one device visible: no renderer can be made elsewhere, so the refusal cannot be provoked here.  This only shows that the
+        # message is compiled in; the branch above is the check, and runs wherever a second device exists (no skip: the rest of
+        # this test must run everywhere)
+        assert b"renderer on device %d, encoder on %d" in open(L.LIB_PATH, "rb").read()
+    with pytest.raises(VideoError, match="no frame has been encoded"):
+        VideoEncoder(8, 8)._download()
+    with pytest.raises(ValueError):
+        v.encode(np.zeros((10, 10, 3), np.uint8))
+
+
+def test_c2_frame_at_full_size_equals_the_model(gpu):
+    container, solver = H.build_product(P.c2_scene())
+    solver.prepare()
+    r = FrameRenderer(container.dx)
+    rgb = r.from_container(container)
+    assert container.particle_num[None] == 1231200 and rgb.shape == (1024, 1024, 3)
+    v = VideoEncoder(1024, 1024)
+    got = v.encode_last(r)
+    info = {}
+    want = JM.encode(rgb, 90, "420", info)
+    st = v.stats()
+    print(f"C2 frame: {len(got)} bytes, stats {st}")
+    assert got == want
+    assert {k: st[k] for k in info} == info and st["blocks"] == 64 * 64 * 6
+
+
+def test_driver_video_and_make_video(gpu, tmp_path):
+    from sph_project_amd import make_video, run_simulation
+    cfg = P.dam_break_scene(method="wcsph", end=(0.2, 0.2, 0.2))
+    cfg["Configuration"].update(exportFrame=True, outputInterval=2)
+    f = tmp_path / "frames.json"
+    f.write_text(json.dumps(cfg))
+    out, plain = tmp_path / "out", tmp_path / "plain"
+    common = ["--scene_file", str(f), "--max_steps", "7", "--render", "--render_meshes", "--render_size", "320", "240"]
+    c1, _ = run_simulation.main(common + ["--output_dir", str(out), "--video", "--video_fps", "25"])
+    c2, _ = run_simulation.main(common + ["--output_dir", str(plain)])
+    for field in (L.F_POSITION, L.F_VELOCITY, L.F_PARTICLE_ID):
+        assert c1.engine.download(field).tobytes() == c2.engine.download(field).tobytes()
+    frames = sorted(d for d in os.listdir(out) if (out / d).is_dir())
+    assert frames == ["000000", "000002", "000004", "000006"]
+    assert sorted(os.listdir(plain)) == frames   # nothing else is written without --video
+    for d in frames:
+        for name in ("raw_view.png", "render.png"):
+            assert (out / d / name).read_bytes() == (plain / d / name).read_bytes()
+    v = VideoEncoder(320, 240)
+    for name, png in (("raw_view.avi", "raw_view.png"), ("render.avi", "render.png")):
+        data = (out / name).read_bytes()
+        jpegs, info = avi_frames(data)
+        assert len(jpegs) == len(frames) and info["rate"] == 25 and info["scale"] == 1
+        for d, jpg in zip(frames, jpegs):
+            assert jpg == v.encode(decode_png((out / d / png).read_bytes())), (name, d)
+        again = tmp_path / ("again_" + name)
+        make_video.main(["--input_dir", str(out), "--image_name", png, "--output_path", str(again), "--fps", "25"])
+        assert again.read_bytes() == data, name

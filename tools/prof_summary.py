@@ -23,6 +23,9 @@ def short(name):
     m = re.search(r"(k_mesh_\w+)<\s*(true|false)", name)   # the mesh renderer's passes: <false> depth, <true> shade
     if m:
         return m.group(1) + ("<shade>" if m.group(2) == "true" else "<depth>")
+    m = re.search(r"(k_video_interval)<\s*(true|false)", name)   # the video encoder's passes: <false> count, <true> write
+    if m:
+        return m.group(1) + ("<write>" if m.group(2) == "true" else "<count>")
     m = re.search(r"(k_\w+)", name)
     return m.group(1) if m else name[:40]
 
