@@ -185,7 +185,7 @@ typedef enum {
     SPH_K_HALO = 17, SPH_K_WCSPH_FORCES = 18,
     SPH_K_IISPH_PREPARE = 19, SPH_K_IISPH_DIJ_PJ = 20, SPH_K_IISPH_SUM_I = 21,
     SPH_K_PBF_DENSITY_LAMBDA = 22, SPH_K_PBF_FIX_POSITION = 23, SPH_K_PBF_UPDATE = 24,
-    SPH_K_RIGID_CONTACT = 25, SPH_K_COUNT_
+    SPH_K_RIGID_CONTACT = 25, SPH_K_RIGID_INTEGRATE = 26, SPH_K_COUNT_
 } SphKernelId;
 
 /* --- lifetime -------------------------------------------------------------------------- */
@@ -243,6 +243,33 @@ int sph_get_rigid_contacts(SphHandle *h, double *table, int reset);
 /* accepted contacts (partner particles + wall planes) of the last contact pass on this handle (this rank's targets).  A query of its
    own rather than a SphStats field: the statistics struct ends at pbf_recentred by contract. */
 int sph_get_rigid_contact_pairs(SphHandle *h, int64_t *pairs);
+
+/* Device rigid integrator (opt-in; the host's "device" rigid backend).  The physics of the host's native backend
+   (SPH/rigid_solver/host_rigid_solver.py integrate: semi-implicit Euler in float64 under gravity and the fluid wrench, gyroscopic
+   term, rotation by exp([dt w]x), re-orthonormalisation, inelastic wall contact of the body's axis-aligned extent) in one kernel
+   launch between the two halves of every step, one workgroup per registered body.  With it sph_step / sph_step_async carry dynamic
+   bodies without any host work.  All arguments float64, scene frame, rot9 / inertia_body row-major.
+   sph_set_rigid_integrator stands in for PyBulletSolver.__init__ (bullet_solver.py:19-71: gravity, time step, the wall boxes);
+   wall_lo / wall_hi are the planes no part of a body may cross.  on = 0 turns the launch off.
+   sph_set_rigid_body stands in for insert_rigid_object (bullet_solver.py:75-131: mass, inertia, base position, orientation and
+   velocity of a body): it registers body object_id or replaces it, uploads its body-frame points (float64[npoints][3]) and marks
+   the pose dirty, so the next renew_rigid_particle_state applies it; com0 (may be NULL) is the rest centre of mass, as in
+   sph_set_rigid_pose.
+   sph_get_rigid_state stands in for the read-back of bullet_solver.py:158-167 and get_rigid_body_states (:169-176); it drains the
+   stream first.  Any output may be NULL.
+   sph_rigid_integrate stands in for PyBulletSolver.step (bullet_solver.py:144-167) of a host that drives the halves itself: the
+   launch on its own, valid only between sph_step_begin and sph_step_end; exactly what sph_step runs between its halves (after the
+   contact pass, if that is on).  The launch reads the wrench as sph_get_rigid_wrench returns it (rounded through float32) and
+   clears the whole wrench array, as sph_get_rigid_wrench(reset = 1) does.
+   SPH_ERR_UNSUPPORTED: a PBF handle (PBF.py moves no body), a sharded handle (the wrench would need an all-reduce inside the step),
+   a handle whose axis order is not "xyz".  SPH_ERR_INVALID: a bad object id, a singular inertia, mass <= 0, npoints < 0,
+   sph_get_rigid_state of an unregistered body, sph_rigid_integrate outside a step or with the integrator off -- and
+   sph_set_rigid_pose on a registered body while the integrator is on (one master per body). */
+int sph_set_rigid_integrator(SphHandle *h, int on, const double *gravity, const double *wall_lo, const double *wall_hi);
+int sph_set_rigid_body(SphHandle *h, int object_id, double mass, const double *inertia_body, const double *com, const double *rot9,
+                       const double *vel, const double *angvel, const double *com0, const double *points, int npoints);
+int sph_get_rigid_state(SphHandle *h, int object_id, double *com, double *rot9, double *vel, double *angvel);
+int sph_rigid_integrate(SphHandle *h);
 
 /* --- time stepping --------------------------------------------------------------------- */
 /* replaces XSolver.prepare() (base_solver.py:683, DFSPH.py:321, PCISPH.py:188); particles of

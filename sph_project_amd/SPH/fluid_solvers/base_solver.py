@@ -89,10 +89,15 @@ class BaseSolver:
         rest = np.asarray(obj["restPosition"], dtype=np.float64) - np.asarray(obj["restCenterOfMass"], dtype=np.float64)
         return (b.rot @ rest.T).T + b.com
 
+    def _bodies_on_device(self):
+        """The "device" rigid backend is active: the device integrates the dynamic bodies between the halves of its own steps."""
+        return getattr(self.rigid_solver, "on_device", False)
+
     def _host_acts_inside_a_step(self):
         """A dynamic rigid body to integrate or an object still waiting for its entryTime: the host has to act in the middle
-        of _step(), where the reference does (WCSPH.py:39-42)."""
-        return bool(self.rigid_solver.bodies) or self.container.objects_pending()
+        of _step(), where the reference does (WCSPH.py:39-42).  Bodies the device integrates itself (the "device" rigid backend)
+        need nothing from the host."""
+        return (bool(self.rigid_solver.bodies) and not self._bodies_on_device()) or self.container.objects_pending()
 
     def _device_steps(self, n):
         """n whole steps on the device.  WCSPH, PBF (and solvers with a fixed iteration count) need nothing back from the device:
@@ -106,11 +111,14 @@ class BaseSolver:
             self.engine.step_async(n)
         else:
             self.engine.step(n)
+        if self._bodies_on_device():   # the bodies moved with the steps: their state is read back when somebody looks, and the
+            self.rigid_solver.mark_stale()   # exported meshes are posed once, from the state at the end
+            self._update_exported_meshes()
 
     def step(self):
         """base_solver.py:692.  Without anything for the host to do inside the step it is one enqueue (no step_begin / step_end
         pair, no host synchronisation: tools/step_overhead.py)."""
-        if self._host_acts_inside_a_step() or self.cfg.get_cfg("exportObj"):
+        if self._host_acts_inside_a_step() or (self.cfg.get_cfg("exportObj") and not self._bodies_on_device()):
             self._step()
         else:
             self._device_steps(1)
@@ -124,6 +132,12 @@ class BaseSolver:
         n = int(n)
         if n <= 0:
             return
+        if self._bodies_on_device():   # only objects still to enter keep the host in the loop: step by step until they are in
+            while n > 0 and self._host_acts_inside_a_step():
+                self.step()
+                n -= 1
+            if n == 0:
+                return
         if self._host_acts_inside_a_step():
             for _ in range(n):
                 self.step()

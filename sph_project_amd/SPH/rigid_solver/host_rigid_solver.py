@@ -7,7 +7,7 @@ rigid_body_forces / rigid_body_torques read + reset), integrate, push centre of 
 velocity back (sph_set_rigid_pose); the device turns the pose into particle positions / velocities
 (_renew_rigid_particle_state, base_solver.py:616) at sph_step_end.
 
-Two backends:
+Built-in backends:
   * "native" (default): free rigid bodies under gravity and the fluid wrench, semi-implicit Euler, inertia tensor of the
     body's own particle set, inelastic contact of the body's particle-set EXTENT (its axis-aligned bounds in the current
     orientation) with the reference's boundary walls (bullet_solver.py:53-71) -- the reference collides the body's mesh
@@ -21,6 +21,12 @@ Two backends:
     sequential-impulse solver resolves all of them together: restitution, Coulomb friction, split-impulse position correction;
     static bodies, the domain box and the wall planes have infinite mass.  No AABB clamp.  Parameters: the optional Configuration keys
     rigidContactRestitution / rigidContactFriction / rigidContactIterations.  Unit-tested (tests/test_contact_host.py).
+  * "device" (opt-in, SPH_RIGID_BACKEND=device): the native backend's physics -- the same integrator, the same wall rule, NO body-body
+    contacts, no friction, no contact torque -- run by the device between the two halves of every step (sph_set_rigid_integrator,
+    csrc/sph_rigid.hpp), so that a scene with dynamic bodies advances in one device call: no wrench read-back, no pose upload, no
+    host synchronisation per step.  The float64 state lives on the device; `bodies[oid].com / rot / vel / angvel`,
+    get_rigid_body_states() and container.rigid_body_velocities are read back when somebody asks for them.
+    Not for PBF (which moves no body) and not for sharded scenes.
   * "pybullet": the reference's calls (URDF from the mesh file, applyExternalForce / Torque at the base,
     stepSimulation, base pose read-back) when the package is importable.  It is not installed in this image, so this
     backend has never run here; select it with SPH_RIGID_BACKEND=pybullet.
@@ -73,6 +79,47 @@ class _Body:
         self.points = None   # body-frame particle positions (wall contact uses their extent)
 
 
+class _DeviceBody(_Body):
+    """A body the device integrates: its state is read back from the device when it is looked at after a step."""
+    _solver = None
+
+    def _get(name):
+        def get(self):
+            if self._solver is not None:
+                self._solver.refresh()
+            return self.__dict__["_" + name]
+        return property(get, lambda self, v: self.__dict__.__setitem__("_" + name, v))
+    com, rot, vel, angvel = _get("com"), _get("rot"), _get("vel"), _get("angvel")
+    del _get
+
+
+class _DeviceVelocities:
+    """container.rigid_body_velocities of the device backend: the container's array, brought up to date before it is read."""
+
+    def __init__(self, array, solver):
+        self._a, self._solver = array, solver
+
+    def _fresh(self):
+        self._solver.refresh()
+        return self._a
+
+    def __getitem__(self, k):
+        return self._fresh()[k]
+
+    def __setitem__(self, k, v):
+        self._a[k] = v
+
+    def __array__(self, dtype=None, copy=None):
+        a = self._fresh()
+        return a.copy() if dtype is None else a.astype(dtype)
+
+    def __len__(self):
+        return len(self._a)
+
+    shape = property(lambda self: self._a.shape)
+    dtype = property(lambda self: self._a.dtype)
+
+
 class HostRigidSolver:
     def __init__(self, container, gravity=(0, -9.8, 0), dt=1e-3):
         self.container = container
@@ -86,6 +133,8 @@ class HostRigidSolver:
         # the container's rigid_backend option (run_simulation.py --rigid_backend) first, then SPH_RIGID_BACKEND
         self.backend = getattr(container, "rigid_backend", None) or os.environ.get("SPH_RIGID_BACKEND", "native")
         self._bullet = None
+        self.on_device = False   # the "device" backend is active: the device integrates the bodies, the host only reads them back
+        self._stale = False
         if not self.rigid_bodies and not self.rigid_blocks:
             print("No rigid body in the scene, skip bullet solver initialization.")
         elif self.backend == "pybullet":
@@ -93,8 +142,8 @@ class HostRigidSolver:
                 self._bullet = _BulletBackend(container, self.gravity, self.dt)
             except ImportError as e:   # asked for explicitly: never fall back silently
                 raise NotImplementedError("SPH_RIGID_BACKEND=pybullet, but pybullet is not importable") from e
-        elif self.backend not in ("native", "contact"):
-            raise ValueError(f"SPH_RIGID_BACKEND={self.backend!r}: expected 'native', 'contact' or 'pybullet'")
+        elif self.backend not in ("native", "contact", "device"):
+            raise ValueError(f"SPH_RIGID_BACKEND={self.backend!r}: expected 'native', 'contact', 'device' or 'pybullet'")
         # walls no part of a body may cross (bullet_solver.py:57-61)
         eps = container.padding + container.particle_diameter + container.domain_box_thickness
         self.wall_lo = np.asarray(container.domain_start, dtype=np.float64) + eps
@@ -117,6 +166,12 @@ class HostRigidSolver:
             walls = not getattr(container, "add_domain_box", False)
             container.engine.set_rigid_contact(True, self.contact_distance, self.wall_lo if walls else None,
                                                self.wall_hi if walls else None)
+        if self.backend == "device" and getattr(container, "METHOD", None) == "pbf":
+            print("SPH_RIGID_BACKEND=device: PBF moves no rigid body (PBF.py _step), the device integrator stays off.")
+        elif self.backend == "device" and dynamic:   # (a sharded scene: the library refuses, and the error is the caller's)
+            container.engine.set_rigid_integrator(True, self.gravity, self.wall_lo, self.wall_hi)
+            container.rigid_body_velocities = _DeviceVelocities(np.asarray(container.rigid_body_velocities), self)
+            self.on_device = True
 
     # ------------------------------------------------------------------ bullet_solver.py:46-51, :75-131
     def insert_rigid_object(self):
@@ -141,8 +196,14 @@ class HostRigidSolver:
             if np.linalg.matrix_rank(inertia) < 3:   # degenerate (a single row of particles): regularise
                 inertia = inertia + np.eye(3) * m_p * c.particle_diameter ** 2
             mass = float(c.rigid_body_masses[oid]) or m_p * len(pts)
-            self.bodies[oid] = _Body(oid, mass, inertia, translation, rot, vel)
+            self.refresh()   # (device backend: what the other bodies did so far, before this one joins the read-back)
+            self.bodies[oid] = (_DeviceBody if self.on_device else _Body)(oid, mass, inertia, translation, rot, vel)
             self.bodies[oid].points = pts
+            if self.on_device:   # bullet_solver.py:86-127 on the device: the body, its particle set and its first pose
+                c.engine.set_rigid_body(oid, mass, inertia, translation, rot, vel, np.zeros(3), com0=np.zeros(3), points=pts)
+                self.bodies[oid]._solver = self
+                c.rigid_body_velocities[oid] = vel
+                continue
             if self._bullet is None and self.contact is None and not _WARNED[0] and not os.environ.get("SPH_RIGID_NATIVE_OK"):
                 _WARNED[0] = True
                 print("WARNING: dynamic rigid body %d is integrated by the built-in 'native' rigid backend: free-body motion under "
@@ -164,6 +225,10 @@ class HostRigidSolver:
     # ------------------------------------------------------------------ bullet_solver.py:144-167
     def step(self):
         if not self.bodies:
+            return
+        if self.on_device:
+            self.container.engine.rigid_integrate()
+            self._stale = True
             return
         force, torque = self.container.engine.get_rigid_wrench(reset=True)
         if self.contact is not None:
@@ -203,6 +268,20 @@ class HostRigidSolver:
             elif b.com[k] + ext_hi[k] > self.wall_hi[k]:
                 b.com[k] = max(self.wall_hi[k] - ext_hi[k], self.wall_lo[k] - ext_lo[k])
                 b.vel[k] = min(b.vel[k], 0.0)
+
+    def mark_stale(self):
+        """The device has stepped: what the host holds of the bodies' state is out of date."""
+        self._stale = self.on_device and bool(self.bodies)
+
+    def refresh(self):
+        """Device backend: bring the bodies' state back (one small copy per body, after draining the stream) if the device has stepped
+        since the last time."""
+        if not self._stale:
+            return
+        self._stale = False
+        for oid, b in self.bodies.items():
+            b.com, b.rot, b.vel, b.angvel = self.container.engine.get_rigid_state(oid)
+            self.container.rigid_body_velocities[oid] = b.vel
 
     def get_rigid_body_states(self, container_idx):
         b = self.bodies[container_idx]

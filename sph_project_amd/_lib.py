@@ -52,6 +52,7 @@ KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "press
               "wcsph_forces", "iisph_prepare", "iisph_dij_pj", "iisph_sum_i", "pbf_density_lambda", "pbf_fix_position",
               "pbf_update"]
 K_RIGID_CONTACT = 25   # sph_kernel_name(25) == "rigid_contact" (KERNEL_IDS keeps its PBF tail)
+K_RIGID_INTEGRATE = 26   # sph_kernel_name(26) == "rigid_integrate": the device rigid backend's launch
 
 # rigid contact table (sph_get_rigid_contacts): [object A][partner B][normal bin][value]; partners 20..25 are the domain box /
 # the wall planes, one per bin; values: pairs, midpoint sum (3), depth * n sum (3), maximum depth
@@ -158,6 +159,7 @@ class SphVideoStats(C.Structure):
 
 # return codes (include/sph_hip.h)
 ERR_INVALID, ERR_CAPACITY = -1, -2
+ERR_UNSUPPORTED = -6
 
 
 class SphError(RuntimeError):
@@ -189,6 +191,11 @@ _SIGNATURES = [
     ("sph_set_rigid_contact", C.c_int, [_VP, C.c_int, C.c_float, _VP, _VP]),
     ("sph_get_rigid_contacts", C.c_int, [_VP, _VP, C.c_int]),
     ("sph_get_rigid_contact_pairs", C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    # device rigid integrator; what each stands in for in the reference's SPH/rigid_solver/bullet_solver.py:
+    ("sph_set_rigid_integrator", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),                        # :19-71 __init__ (gravity, dt, walls)
+    ("sph_set_rigid_body", C.c_int, [_VP, C.c_int, C.c_double] + [_VP] * 7 + [C.c_int]),        # :75-131 insert_rigid_object
+    ("sph_get_rigid_state", C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP]),                        # :158-176 pose read-back
+    ("sph_rigid_integrate", C.c_int, [_VP]),                                                     # :144-167 step
     ("sph_prepare", C.c_int, [_VP]),
     ("sph_step", C.c_int, [_VP, C.c_int]),
     ("sph_step_async", C.c_int, [_VP, C.c_int]),
@@ -373,6 +380,30 @@ class Engine(NativeObject):
         n = C.c_int64(0)
         self._chk(self.lib.sph_get_rigid_contact_pairs(self.h, C.byref(n)), "sph_get_rigid_contact_pairs")
         return n.value
+
+    # -- device rigid integrator (the "device" rigid backend)
+    def set_rigid_integrator(self, on=True, gravity=(0.0, 0.0, 0.0), wall_lo=(0.0, 0.0, 0.0), wall_hi=(0.0, 0.0, 0.0)):
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(3)
+        g, lo, hi = f(gravity), f(wall_lo), f(wall_hi)
+        self._chk(self.lib.sph_set_rigid_integrator(self.h, int(bool(on)), _ptr(g), _ptr(lo), _ptr(hi)), "sph_set_rigid_integrator")
+
+    def set_rigid_body(self, object_id, mass, inertia_body, com, rot, vel, angvel, com0=None, points=None):
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        inertia, com, rot, vel, angvel = f(inertia_body), f(com), f(rot), f(vel), f(angvel)
+        assert inertia.size == 9 and rot.size == 9 and com.size == 3 and vel.size == 3 and angvel.size == 3
+        com0 = None if com0 is None else f(com0)
+        pts = np.zeros((0, 3)) if points is None else np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        self._chk(self.lib.sph_set_rigid_body(self.h, int(object_id), float(mass), _ptr(inertia), _ptr(com), _ptr(rot), _ptr(vel),
+                                              _ptr(angvel), _ptr(com0), _ptr(pts) if len(pts) else None, len(pts)), "sph_set_rigid_body")
+
+    def get_rigid_state(self, object_id):
+        """(com, rot[3, 3], vel, angvel) of a registered body, float64; drains the stream."""
+        com, rot, vel, angvel = np.zeros(3), np.zeros((3, 3)), np.zeros(3), np.zeros(3)
+        self._chk(self.lib.sph_get_rigid_state(self.h, int(object_id), _ptr(com), _ptr(rot), _ptr(vel), _ptr(angvel)), "sph_get_rigid_state")
+        return com, rot, vel, angvel
+
+    def rigid_integrate(self):
+        self._chk(self.lib.sph_rigid_integrate(self.h), "sph_rigid_integrate")
 
     # -- stepping
     def prepare(self):

@@ -57,6 +57,11 @@ struct SphHandle : ErrSink {
     int n_mark = 0;               // particle count at the end of sph_step_begin: [n_mark, n) was appended mid-step
     int fresh_state = 0;          // rigid particles appended after prepare(): 1 = the next post-sort volume pass leaves them alone, 2 = the one after includes them (see ph_rigid_volume)
     RigidPose pose_h;
+    // device rigid integrator: host copy of the registered bodies (their constants; the state part is what was uploaded last), the
+    // capacity of each body's point array, and whether the kernel has moved the device pose since pose_h was last brought up to date
+    RigidBodyDev rb_h[SPH_NOBJ] = {};
+    int rb_cap[SPH_NOBJ] = {};
+    bool rb_pose_stale = false;
     SphStats last;
     ProfSlot prof[SPH_K_COUNT_];
     std::vector<hipEvent_t> ev_pool;
@@ -206,7 +211,7 @@ extern "C" const char *sph_kernel_name(int k) {
         "dfsph_density_alpha", "dfsph_rho_adv", "dfsph_correct", "reduce", "pcisph_rho_star",
         "pcisph_pressure_accel", "cg_prepare", "cg_ap", "cg_vector", "misc", "halo", "wcsph_forces",
         "iisph_prepare", "iisph_dij_pj", "iisph_sum_i", "pbf_density_lambda", "pbf_fix_position", "pbf_update",
-        "rigid_contact"};
+        "rigid_contact", "rigid_integrate"};
     return (k >= 0 && k < SPH_K_COUNT_) ? names[k] : "?";
 }
 
@@ -308,6 +313,7 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     s.iisph_dii = s.iisph_dij = s.iisph_w = nullptr;
     s.pbf_old = s.pbf_pos = nullptr; s.pbf_lambda = nullptr; s.pbf_recentred = nullptr; s.poly6 = 0;
     s.contact_on = 0; s.contact = ContactArgs{}; s.contact_table = s.contact_pairs = nullptr; s.contact_part = nullptr;
+    s.rigid_int_on = 0; s.rigid_int = RigidIntArgs{}; s.rigid_bodies = nullptr;
     s.cg_p2 = nullptr; s.cg_fuse = s.cg_fused_loop = 0;
     s.cg_p = s.cg_Ap = s.cg_x = s.cg_b = s.cg_r = s.cg_v0 = nullptr; s.cg_dinv = nullptr; s.cg_part = nullptr; s.cg_split = 0; s.cg_nocombine = 0; s.split_next_pass = 0;
     if (p.method == SPH_METHOD_DFSPH) {
@@ -450,6 +456,22 @@ extern "C" int sph_set_appended_ids(SphHandle *h, int n, const int32_t *ids) {
     return SPH_OK;
 }
 
+// The device integrator (sph_rigid.hpp) writes the float32 pose of its bodies on the device; before the host edits pose_h and uploads
+// the whole struct again, those entries are brought back.
+static int pose_refresh(SphHandle *h) {
+    if (!h->rb_pose_stale) return SPH_OK;
+    RigidPose dev;
+    HIPCHK(h, hipMemcpyAsync(&dev, h->st.pose, sizeof(RigidPose), hipMemcpyDeviceToHost, h->st.stream));
+    HIPCHK(h, hipStreamSynchronize(h->st.stream));
+    for (int o = 0; o < SPH_NOBJ; ++o) {
+        if (!h->rb_h[o].registered) continue;
+        memcpy(h->pose_h.com[o], dev.com[o], sizeof(dev.com[o])); memcpy(h->pose_h.rot[o], dev.rot[o], sizeof(dev.rot[o]));
+        memcpy(h->pose_h.vel[o], dev.vel[o], sizeof(dev.vel[o])); memcpy(h->pose_h.angvel[o], dev.angvel[o], sizeof(dev.angvel[o]));
+    }
+    h->rb_pose_stale = false;
+    return SPH_OK;
+}
+
 static int upload_pose(SphHandle *h) {
     HIPCHK(h, hipMemcpyAsync(h->st.pose, &h->pose_h, sizeof(RigidPose), hipMemcpyHostToDevice, h->st.stream));
     HIPCHK(h, hipStreamSynchronize(h->st.stream));  // pose_h may change right after
@@ -459,6 +481,7 @@ static int upload_pose(SphHandle *h) {
 extern "C" int sph_set_object(SphHandle *h, int object_id, int material, int is_dynamic) {
     if (!h || object_id < 0 || object_id >= SPH_MAX_OBJECTS) return fail(h, SPH_ERR_INVALID, "set_object: bad object id");
     HIPCHK(h, hipSetDevice(h->device));
+    { int rc = pose_refresh(h); if (rc) return rc; }
     h->pose_h.material[object_id] = material;
     if (material != 1) h->any_rigid_object = true;
     h->pose_h.is_dynamic[object_id] = is_dynamic ? 1 : 0;
@@ -471,7 +494,10 @@ extern "C" int sph_set_object(SphHandle *h, int object_id, int material, int is_
 extern "C" int sph_set_rigid_pose(SphHandle *h, int o, const float *com, const float *rot9, const float *vel,
                                   const float *angvel, const float *com0) {
     if (!h || o < 0 || o >= SPH_MAX_OBJECTS || !com || !rot9 || !vel || !angvel) return fail(h, SPH_ERR_INVALID, "set_rigid_pose: bad argument");
+    if (h->st.rigid_int_on && h->rb_h[o].registered)
+        return fail(h, SPH_ERR_INVALID, "set_rigid_pose: object %d is moved by the device integrator (sph_set_rigid_body)", o);
     HIPCHK(h, hipSetDevice(h->device));
+    { int rc = pose_refresh(h); if (rc) return rc; }
     // scene frame -> library frame: polar vectors P v, the axial angular velocity det(P) P w, the rotation P R P^T
     for (int a = 0; a < 3; ++a) {
         const int b = h->perm[a];
@@ -532,6 +558,91 @@ extern "C" int sph_set_rigid_contact(SphHandle *h, int on, float distance, const
     }
     s.contact = a;
     s.contact_on = 1;
+    return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------- device rigid integrator (sph_rigid.hpp)
+static int rigid_int_supported(SphHandle *h, const char *who) {
+    if (h->prm.method == SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "%s: PBF moves no rigid body (PBF.py _step)", who);
+    if (h->st.slab_active) return fail(h, SPH_ERR_UNSUPPORTED, "%s: a sharded scene would need the wrench all-reduced inside the step", who);
+    if (h->swap_axis) return fail(h, SPH_ERR_UNSUPPORTED, "%s: the library frame differs from the scene frame (axis order)", who);
+    return SPH_OK;
+}
+
+static void rigid_int_list(SphHandle *h) {
+    RigidIntArgs &a = h->st.rigid_int;
+    a.nbodies = 0;
+    for (int o = 0; o < SPH_NOBJ; ++o) if (h->rb_h[o].registered) a.ids[a.nbodies++] = o;
+    for (int q = a.nbodies; q < SPH_NOBJ; ++q) a.ids[q] = -1;
+}
+
+extern "C" int sph_set_rigid_integrator(SphHandle *h, int on, const double *gravity, const double *wall_lo, const double *wall_hi) {
+    if (!h) return SPH_ERR_INVALID;
+    if (!on) { h->st.rigid_int_on = 0; return SPH_OK; }
+    { int rc = rigid_int_supported(h, "set_rigid_integrator"); if (rc) return rc; }
+    if (!gravity || !wall_lo || !wall_hi) return fail(h, SPH_ERR_INVALID, "set_rigid_integrator: null argument");
+    RigidIntArgs &a = h->st.rigid_int;
+    for (int k = 0; k < 3; ++k) { a.g[k] = gravity[k]; a.lo[k] = wall_lo[k]; a.hi[k] = wall_hi[k]; }
+    a.dt = (double)h->st.c.dt;   // the float32 step the fluid passes use (the host solver's dt is that value too)
+    rigid_int_list(h);
+    h->st.rigid_int_on = 1;
+    return SPH_OK;
+}
+
+extern "C" int sph_set_rigid_body(SphHandle *h, int o, double mass, const double *inertia_body, const double *com, const double *rot9,
+                                  const double *vel, const double *angvel, const double *com0, const double *points, int npoints) {
+    if (!h) return SPH_ERR_INVALID;
+    if (o < 0 || o >= SPH_MAX_OBJECTS || !inertia_body || !com || !rot9 || !vel || !angvel || npoints < 0 || (npoints > 0 && !points) ||
+        !(mass > 0.0) || !std::isfinite(mass))
+        return fail(h, SPH_ERR_INVALID, "set_rigid_body: bad argument");
+    { int rc = rigid_int_supported(h, "set_rigid_body"); if (rc) return rc; }
+    const double *m = inertia_body;
+    double c[9] = {m[4] * m[8] - m[5] * m[7], m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
+                   m[5] * m[6] - m[3] * m[8], m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
+                   m[3] * m[7] - m[4] * m[6], m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};   // adjugate
+    const double det = m[0] * c[0] + m[1] * c[3] + m[2] * c[6];
+    double scale = 0.0;
+    for (int q = 0; q < 9; ++q) scale = std::max(scale, fabs(m[q]));
+    if (!std::isfinite(det) || !(fabs(det) > 1e-12 * scale * scale * scale))
+        return fail(h, SPH_ERR_INVALID, "set_rigid_body: the inertia tensor of object %d is singular", o);
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rc = pose_refresh(h); if (rc) return rc; }
+    State &s = h->st;
+    if (!s.rigid_bodies) { int rc = dalloc(h, &s.rigid_bodies, (size_t)SPH_NOBJ); if (rc) return rc; }
+    RigidBodyDev &b = h->rb_h[o];
+    if (npoints > h->rb_cap[o]) {
+        double *p = nullptr;
+        int rc = dalloc(h, &p, (size_t)npoints * 3); if (rc) return rc;
+        b.points = p; h->rb_cap[o] = npoints;
+    }
+    HIPCHK(h, hipStreamSynchronize(s.stream));
+    if (npoints > 0) HIPCHK(h, hipMemcpy((void *)b.points, points, sizeof(double) * 3 * (size_t)npoints, hipMemcpyHostToDevice));
+    b.npoints = npoints; b.registered = 1; b.mass = mass;
+    for (int q = 0; q < 9; ++q) { b.inertia[q] = m[q]; b.inertia_inv[q] = c[q] / det; b.rot[q] = rot9[q]; }
+    for (int k = 0; k < 3; ++k) { b.com[k] = com[k]; b.vel[k] = vel[k]; b.angvel[k] = angvel[k]; }
+    HIPCHK(h, hipMemcpy(s.rigid_bodies + o, &b, sizeof(RigidBodyDev), hipMemcpyHostToDevice));
+    rigid_int_list(h);
+    // the float32 pose the particles see (sph_set_rigid_pose), applied by the next renew_rigid
+    for (int k = 0; k < 3; ++k) {
+        h->pose_h.com[o][k] = (float)com[k]; h->pose_h.vel[o][k] = (float)vel[k]; h->pose_h.angvel[o][k] = (float)angvel[k];
+        if (com0) h->pose_h.com0[o][k] = (float)com0[k];
+    }
+    for (int q = 0; q < 9; ++q) h->pose_h.rot[o][q] = (float)rot9[q];
+    h->pose_dirty = true;
+    h->pose_given = true;
+    return upload_pose(h);
+}
+
+extern "C" int sph_get_rigid_state(SphHandle *h, int o, double *com, double *rot9, double *vel, double *angvel) {
+    if (!h) return SPH_ERR_INVALID;
+    if (o < 0 || o >= SPH_MAX_OBJECTS || !h->rb_h[o].registered) return fail(h, SPH_ERR_INVALID, "get_rigid_state: object %d is not registered", o);
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rc = slab_settle_if_needed(h); if (rc) return rc; }
+    RigidBodyDev b;
+    HIPCHK(h, hipMemcpyAsync(&b, h->st.rigid_bodies + o, sizeof(RigidBodyDev), hipMemcpyDeviceToHost, h->st.stream));
+    HIPCHK(h, hipStreamSynchronize(h->st.stream));
+    for (int k = 0; k < 3; ++k) { if (com) com[k] = b.com[k]; if (vel) vel[k] = b.vel[k]; if (angvel) angvel[k] = b.angvel[k]; }
+    if (rot9) for (int q = 0; q < 9; ++q) rot9[q] = b.rot[q];
     return SPH_OK;
 }
 
@@ -799,7 +910,8 @@ extern "C" int sph_prepare(SphHandle *h) {
         return fail(h, SPH_ERR_UNSUPPORTED, "sph_prepare: PBF runs on one GPU only (no sharded PBF step: sph_comm_set_slab)");
     if (h->prm.viscosity_implicit && h->prm.method == SPH_METHOD_PBF)
         return fail(h, SPH_ERR_UNSUPPORTED, "sph_prepare: PBF with implicit viscosity is not supported (its CG walks would need the spiky gradient)");
-    int rc = upload_pose(h); if (rc) return rc;
+    int rc = pose_refresh(h); if (rc) return rc;
+    rc = upload_pose(h); if (rc) return rc;
     // base_solver.py:683 prepare: prepare_emitter, renew_rigid_particle_state, neighbour search,
     // compute_rigid_particle_volume (+ DFSPH.py:321 / PCISPH.py:188)
     { ProfScope p(h, SPH_K_MISC); h->L->prepare_emitter(s); h->L->renew_rigid(s); }
@@ -831,6 +943,24 @@ extern "C" int sph_prepare(SphHandle *h) {
     HIPCHK(h, hipStreamSynchronize(s.stream));
     h->prepared = true;
     return SPH_OK;
+}
+
+// the rigid step of the device backend (bullet_solver.py:144-167 without the host): wrench -> state -> pose, between the halves of a step
+static void ph_rigid_integrate(SphHandle *h) {
+    if (!h->st.rigid_int_on || h->st.rigid_int.nbodies <= 0) return;
+    { ProfScope p(h, SPH_K_RIGID_INTEGRATE); h->L->rigid_integrate(h->st); }
+    h->pose_dirty = true;
+    h->rb_pose_stale = true;
+}
+
+extern "C" int sph_rigid_integrate(SphHandle *h) {
+    if (!h) return SPH_ERR_INVALID;
+    if (!h->in_step) return fail(h, SPH_ERR_INVALID, "sph_rigid_integrate outside sph_step_begin / sph_step_end");
+    if (!h->st.rigid_int_on) return fail(h, SPH_ERR_INVALID, "sph_rigid_integrate: sph_set_rigid_integrator is off");
+    { int rc = rigid_int_supported(h, "sph_rigid_integrate"); if (rc) return rc; }
+    HIPCHK(h, hipSetDevice(h->device));
+    ph_rigid_integrate(h);
+    return check_async(h);
 }
 
 // First half of a step: everything the reference's _step() does before `self.rigid_solver.step()`.
@@ -893,6 +1023,7 @@ static int step_once(SphHandle *h) {
         if (!rc && fail_at >= 0 && h->steps == fail_at) { fail_at = -1; h->in_step = false; rc = fail(h, SPH_ERR_INVALID, "SPH_TEST_FAIL_STEP: injected failure"); }
     }
 #endif
+    if (!rc) ph_rigid_integrate(h);   // the device rigid backend: the host has nothing to do between the halves
     if (!rc) rc = step_second_half(h);
     // a failed step may leave a hash made for a sort that will not come (NextHash: the WCSPH force pass for the next step's sort, the
     // DFSPH position update for this step's): the next sort, whoever asks for it, must hash for itself on a clean histogram

@@ -186,6 +186,15 @@ struct HaloFieldSend { int on; float4 *out[2]; const int *xidx; const SlabDyn *d
 #define SPH_CT_KEYS (SPH_NOBJ * SPH_CT_PARTNERS * SPH_CT_BINS)
 struct ContactArgs { float D; int walls; float lo[3], hi[3]; };
 
+// Device rigid integrator (sph_rigid.hpp, the host's "device" rigid backend): the float64 state of one body, and what one launch needs --
+// gravity, the walls no part of a body may cross, dt, and the object ids of the registered bodies (workgroup b integrates body ids[b])
+struct RigidBodyDev {
+    double com[3], rot[9], vel[3], angvel[3], mass, inertia[9], inertia_inv[9];
+    const double *points;   // body-frame positions of the body's particles, 3 per point
+    int npoints, registered;
+};
+struct RigidIntArgs { double g[3], lo[3], hi[3], dt; int nbodies; int ids[SPH_NOBJ]; };
+
 // Surface reconstruction (sph_surface.hpp): the constants and device buffers of one SphSurface.  Coarse cells (= bricks of
 // B^3 grid points) are counted from the absolute coarse coordinate cmin[] on a grid of cn[] cells that keeps one empty cell around the
 // particles; coarse linear index (x * cn[1] + y) * cn[2] + z.
@@ -359,6 +368,10 @@ struct State {
     ContactArgs contact;
     unsigned long long *contact_table, *contact_pairs;
     float4 *contact_part;
+    // device rigid integrator (sph_set_rigid_integrator; the body array is allocated with the first sph_set_rigid_body)
+    int rigid_int_on;
+    RigidIntArgs rigid_int;
+    RigidBodyDev *rigid_bodies;   // [SPH_NOBJ]
     // CG (implicit viscosity)
     float4 *cg_p, *cg_Ap, *cg_x, *cg_b, *cg_r, *cg_v0;
     float4 *cg_p2;       // second search-direction buffer (fused p update: the A p pass reads the old one and writes the new one)
@@ -486,6 +499,8 @@ struct Launch {
     void (*pbf_finish)(State &);                // boundary + recompute_fluid_velocity (PBF.py:156-158)
     // rigid contact: one walk over the dynamic rigid particles, per-key table + per-particle sums (sph_contact.hpp)
     void (*rigid_contact)(State &);
+    // device rigid integrator: one workgroup per registered body (sph_rigid.hpp)
+    void (*rigid_integrate)(State &);
     // z-slab sharding
     void (*halo_classify_pack)(State &, int n);
     void (*halo_unpack_append)(State &, int side, int count, int offset);

@@ -453,6 +453,7 @@ void l_clear_fresh(State &s) {
 #include "sph_solvers_impl.hpp"
 #include "sph_pbf.hpp"
 #include "sph_contact.hpp"
+#include "sph_rigid.hpp"
 #include "sph_surface.hpp"
 #include "sph_surface_post.hpp"
 #include "sph_render.hpp"
@@ -483,6 +484,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_solver_launchers(L);
         register_pbf_launchers(L);
         register_contact_launchers(L);
+        register_rigid_launchers(L);
         register_surface_launchers(L);
         register_surface_post_launchers(L);
         register_render_launchers(L);
