@@ -26,7 +26,7 @@ struct ProfSlot {
 };
 
 struct SphHandle : ErrSink {
-    SphParams prm;
+    SphParams prm = {};
     State st;
     const Launch *L = nullptr;
     int device = 0;
@@ -56,13 +56,13 @@ struct SphHandle : ErrSink {
     bool in_step = false;         // between sph_step_begin and sph_step_end
     int n_mark = 0;               // particle count at the end of sph_step_begin: [n_mark, n) was appended mid-step
     int fresh_state = 0;          // rigid particles appended after prepare(): 1 = the next post-sort volume pass leaves them alone, 2 = the one after includes them (see ph_rigid_volume)
-    RigidPose pose_h;
+    RigidPose pose_h = {};   // (sph_create sets the identity rotations)
     // device rigid integrator: host copy of the registered bodies (their constants; the state part is what was uploaded last), the
     // capacity of each body's point array, and whether the kernel has moved the device pose since pose_h was last brought up to date
     RigidBodyDev rb_h[SPH_NOBJ] = {};
     int rb_cap[SPH_NOBJ] = {};
     bool rb_pose_stale = false;
-    SphStats last;
+    SphStats last = {};
     ProfSlot prof[SPH_K_COUNT_];
     std::vector<hipEvent_t> ev_pool;
     std::vector<void *> allocs;
@@ -271,9 +271,7 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
         }                                                                                  \
     } while (0)
     h->L = p.fast_math ? sph_launch_fast() : sph_launch_strict();
-    State &s = h->st;
-    memset(&s.c, 0, sizeof(s.c));
-    s.stream = nullptr;
+    State &s = h->st;   // (every member starts from its initialiser: what follows allocates, and derives from the parameters)
     HIP_CREATE(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
     fill_consts(h);
     const size_t cap = (size_t)p.particle_max_num;
@@ -283,39 +281,22 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
         CHK_CREATE(dalloc(h, &s.meta.b[k], cap)); CHK_CREATE(dalloc(h, &s.pid.b[k], cap));
         CHK_CREATE(dalloc(h, &s.color.b[k], cap)); CHK_CREATE(dalloc(h, &s.rho.b[k], cap));
     }
-    s.orig.b[0] = s.orig.b[1] = nullptr;
     const size_t G = (size_t)s.c.G;
     CHK_CREATE(dalloc(h, &s.cell_count, G + SPH_NGRAVE + 1)); CHK_CREATE(dalloc(h, &s.cell_start, G + SPH_NGRAVE + 1));   // + graveyard cells (slab sharding)
     CHK_CREATE(dalloc(h, &s.cellid, cap)); CHK_CREATE(dalloc(h, &s.rank, cap)); CHK_CREATE(dalloc(h, &s.tmp_idx, 2 * cap));   // (int2 run records of the stable sort)
-    s.run_head = nullptr; s.run_rec = nullptr; s.sort_inv = nullptr; s.sort_epoch = 0u; s.run_lists_filed = 0; s.n_list_sorts = 0;
-    s.sort_skip_rho = 0; s.color_home = nullptr; s.color_home_ok = 0; s.color_stale = 0;
     if (h->prm.deterministic && !getenv("SPH_NO_RUN_LISTS")) { CHK_CREATE(dalloc(h, &s.run_head, G + 1)); CHK_CREATE(dalloc(h, &s.run_rec, cap + G + 1)); CHK_CREATE(dalloc(h, &s.sort_inv, cap)); CHK_CREATE(dalloc(h, &s.color_home, cap)); s.color_home_ok = 1; }   // deterministic sort by run lists (RunList, sph_common.hpp)
     s.scan_blocks = (int)((G + SPH_NGRAVE + 2047) / 2048);
     if (s.scan_blocks < SPH_STAT_SLOTS / 256) s.scan_blocks = SPH_STAT_SLOTS / 256;   // k_scan_final also clears the statistics slots
     CHK_CREATE(dalloc(h, &s.scan_tile_state, (size_t)s.scan_blocks + 1));
     CHK_CREATE(dalloc(h, &s.scan_partial, 2 * ((size_t)s.scan_blocks + 1) * 8));   // two banks of tile sums, SCAN_PARTIAL_STRIDE ints apart (State::scan_bank)
-    s.scan_bank = 0; s.tile_sums_ready = 0; s.skip_residual = 0; s.hist_taken = 0; s.state_error = 0;
-    s.cell_count_clean = 1;
     CHK_CREATE(dalloc(h, &s.rho_raw, cap)); CHK_CREATE(dalloc(h, &s.prs, cap)); CHK_CREATE(dalloc(h, &s.ptm, cap));
     CHK_CREATE(dalloc(h, &s.acc, cap));
-    s.masks_valid = 0; s.density_books_forces = 0; s.uniform_mass = 0;
     CHK_CREATE(dalloc(h, &s.nbr_mask, cap * 9 + 256)); CHK_CREATE(dalloc(h, &s.nbr_mask_hi, cap * 9 + 256));   // + 256: the lanes past the last particle of the last tile read (and drop) a word too
-    s.perm_n = -1;
-    s.loop_flag = nullptr; s.loop_slot = 0; s.loop_kind = 0; s.loop_denom = 1.0f; s.loop_thr = 0.0;
     CHK_CREATE(dalloc(h, &s.blk_hdr, (cap + 255) / 256 * (20 + 256)));   // headers of all tiles, then one cell word per particle slot (k_block_prep)
-    s.blk_flag = s.blk_list = s.blk_count = nullptr; s.list_n = -1; s.last_pass_listed = 0; s.list_count_pinned = nullptr; s.list_count_event = nullptr; s.list_count_known = -1; s.nexthash = NextHash{0, nullptr, nullptr, nullptr, nullptr, RunList{nullptr, nullptr, 0, 0u}}; s.prehashed = 0; s.n_hash_launches = s.n_prehashed_sorts = 0;
     if (!getenv("SPH_NO_BLOCK_LIST")) {
         CHK_CREATE(dalloc(h, &s.blk_flag, (cap + 255) / 256)); CHK_CREATE(dalloc(h, &s.blk_list, (cap + 255) / 256)); CHK_CREATE(dalloc(h, &s.blk_count, 1));
     }
     CHK_CREATE(dalloc(h, &s.lane_perm, (cap + 255) / 256 * 256));
-    s.alpha = s.kappa = s.kappa_v = s.rho_star = s.rho_deriv = s.kappa_next = s.kappa_v_next = nullptr; s.kr = nullptr;
-    s.pacc = s.pvel = s.ppos = s.acc_np = nullptr; s.np_acc_out = nullptr; s.np_visc_vel = nullptr;
-    s.iisph_dii = s.iisph_dij = s.iisph_w = nullptr;
-    s.pbf_old = s.pbf_pos = nullptr; s.pbf_lambda = nullptr; s.pbf_recentred = nullptr; s.poly6 = 0;
-    s.contact_on = 0; s.contact = ContactArgs{}; s.contact_table = s.contact_pairs = nullptr; s.contact_part = nullptr;
-    s.rigid_int_on = 0; s.rigid_int = RigidIntArgs{}; s.rigid_bodies = nullptr;
-    s.cg_p2 = nullptr; s.cg_fuse = s.cg_fused_loop = 0;
-    s.cg_p = s.cg_Ap = s.cg_x = s.cg_b = s.cg_r = s.cg_v0 = nullptr; s.cg_dinv = nullptr; s.cg_part = nullptr; s.cg_split = 0; s.cg_nocombine = 0; s.split_next_pass = 0;
     if (p.method == SPH_METHOD_DFSPH) {
         CHK_CREATE(dalloc(h, &s.alpha, cap)); CHK_CREATE(dalloc(h, &s.kappa, cap)); CHK_CREATE(dalloc(h, &s.kappa_v, cap));
         CHK_CREATE(dalloc(h, &s.rho_star, cap)); CHK_CREATE(dalloc(h, &s.rho_deriv, cap)); CHK_CREATE(dalloc(h, &s.kr, cap));
@@ -344,25 +325,15 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     }
     s.red_blocks = (int)((cap + 255) / 256) + 1;
     CHK_CREATE(dalloc(h, &s.red_partial, (size_t)s.red_blocks * 8));   // (also the four partial-sum arrays of the CG kernels)
-    s.cg_parity = 0;
     CHK_CREATE(dalloc(h, &s.scal, 1)); CHK_CREATE(dalloc(h, &s.pose, 1));
     HIP_CREATE(hipHostMalloc((void **)&h->scal_h, sizeof(DevScalars), hipHostMallocDefault));
     { void *lp = nullptr; HIP_CREATE(hipHostMalloc(&lp, 128, hipHostMallocDefault)); memset(lp, 0, 128); h->loop_pub = (struct LoopPub *)lp; }   // + StatsPub behind it
     { int *lc = nullptr; HIP_CREATE(hipHostMalloc((void **)&lc, 64, hipHostMallocDefault)); *lc = 0; s.list_count_pinned = lc; }
     HIP_CREATE(hipEventCreateWithFlags(&s.list_count_event, hipEventDisableTiming));
-    s.list_count_known = -1;
     memset(h->scal_h, 0, sizeof(DevScalars));
-    memset(&h->pose_h, 0, sizeof(h->pose_h));
     for (int o = 0; o < SPH_NOBJ; ++o) { h->pose_h.rot[o][0] = h->pose_h.rot[o][4] = h->pose_h.rot[o][8] = 1.0f; }
-    memset(&h->last, 0, sizeof(h->last));
-    s.has_dynamic_rigid = 0; s.has_rigid = 0;
-    s.dyn = s.dyn_cur = nullptr; s.async_counts = 0; s.tables_pending = 0; memset(&s.push, 0, sizeof(s.push));
-    s.tile_list[0] = s.tile_list[1] = nullptr; s.tile_cnt = nullptr; s.tile_class = nullptr; s.tile_sel = 0; s.tile_plan_n = -1;
-    s.tile_bound_b = 0; memset(&s.presend, 0, sizeof(s.presend)); memset(&s.fieldsend, 0, sizeof(s.fieldsend)); s.preclassified = 0;
-    s.slab_active = 0; s.xcur = 0; s.halo_cap = 0; s.z_lo = 0; s.z_hi = slab_layers_glob(s.c); s.has_down = s.has_up = 0;
-    s.xidx[0] = s.xidx[1] = nullptr; s.halo_counts = nullptr;
+    s.z_hi = slab_layers_glob(s.c);
     s.visc_rho_raw = (p.method == SPH_METHOD_WCSPH);
-    s.skip_viscosity = 0;
     refresh_counts(h);
     *out = h;
     return SPH_OK;
@@ -445,12 +416,16 @@ extern "C" int sph_append_particles(SphHandle *h, int object_id, int n, const fl
 
 // persistent ids of the n particles appended last (a rank of a sharded scene numbers its particles with their global
 // insertion indices, so that ids mean the same thing on every rank and in a single-GPU run)
+// the ids stop being the append order (ids from outside, slab sharding's global ids): the sorted copy of the colours is brought up to
+// date and the colours travel with the particles from now on
+static void colors_leave_home(SphHandle *h) { h->L->sorted_color(h->st); h->st.color_home_ok = 0; }
+
 extern "C" int sph_set_appended_ids(SphHandle *h, int n, const int32_t *ids) {
     if (h) { int rc = slab_settle_if_needed(h); if (rc) return rc; }
     if (!h || !ids || n < 0 || n > h->n) return fail(h, SPH_ERR_INVALID, "set_appended_ids: bad arguments");
     if (n == 0) return SPH_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    h->L->ensure_color(h->st); h->st.color_home_ok = 0;   // ids from outside: the colours travel with the particles from now on
+    colors_leave_home(h);
     HIPCHK(h, hipStreamSynchronize(h->st.stream));
     HIPCHK(h, hipMemcpy(h->st.pid.cur() + (size_t)(h->n - n), ids, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
     return SPH_OK;
@@ -813,11 +788,12 @@ static int check_async(SphHandle *h) {
 }
 
 // base_container.py:544 prepare_neighborhood_search
-static void ph_neighbor_search(SphHandle *h) {
+// rho_dead: the kernel the caller launches next rewrites every particle's density (Launch::scatter_stable)
+static void ph_neighbor_search(SphHandle *h, bool rho_dead = false) {
     State &s = h->st;
     { ProfScope p(h, SPH_K_HASH_COUNT); h->L->hash_count(s); }
     { ProfScope p(h, SPH_K_SCAN); h->L->scan(s); }
-    { ProfScope p(h, SPH_K_SCATTER); if (h->prm.deterministic) h->L->scatter_stable(s); else h->L->scatter(s); }
+    { ProfScope p(h, SPH_K_SCATTER); if (h->prm.deterministic) h->L->scatter_stable(s, rho_dead); else h->L->scatter(s); }
     h->sort_dirty = false;
 }
 
@@ -825,7 +801,7 @@ static void ph_neighbor_search(SphHandle *h) {
 static void ph_sort_hashed(SphHandle *h) {
     State &s = h->st;
     { ProfScope p(h, SPH_K_SCAN); h->L->scan(s); }
-    { ProfScope p(h, SPH_K_SCATTER); if (h->prm.deterministic) h->L->scatter_stable(s); else h->L->scatter(s); }
+    { ProfScope p(h, SPH_K_SCATTER); if (h->prm.deterministic) h->L->scatter_stable(s, false); else h->L->scatter(s); }
     h->sort_dirty = false;
 }
 
@@ -1094,7 +1070,7 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
     switch (phase) {
         case SPH_PH_NEIGHBOR_SEARCH: ph_neighbor_search(h); break;
         case SPH_PH_RIGID_VOLUME: h->rigid_volume_done = false; ph_rigid_volume(h); break;
-        case SPH_PH_DENSITY: { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, h->prm.method == SPH_METHOD_WCSPH); } break;
+        case SPH_PH_DENSITY: { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, h->prm.method == SPH_METHOD_WCSPH, {}); } break;
         case SPH_PH_NON_PRESSURE: { int rc = run_non_pressure(h); if (rc) return rc; } break;
         case SPH_PH_PRESSURE_INTEGRATE: { ProfScope p(h, SPH_K_PRESSURE_INTEGRATE); h->L->pressure_integrate(s); } break;
         case SPH_PH_RIGID_CONTACT: {
@@ -1228,9 +1204,9 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
     }
     if (field == SPH_F_COLOR) {
         if (bytes != n * 12) return fail(h, SPH_ERR_INVALID, "download: size mismatch");
-        h->L->ensure_color(s); HIPCHK(h, hipStreamSynchronize(s.stream));
+        const unsigned *col = h->L->sorted_color(s); HIPCHK(h, hipStreamSynchronize(s.stream));
         std::vector<unsigned> tmp(n);
-        HIPCHK(h, hipMemcpy(tmp.data(), s.color.cur(), n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(tmp.data(), col, n * 4, hipMemcpyDeviceToHost));
         int32_t *d = (int32_t *)dst;
         for (size_t i = 0; i < n; ++i) { d[3 * i] = tmp[i] & 0xff; d[3 * i + 1] = (tmp[i] >> 8) & 0xff; d[3 * i + 2] = (tmp[i] >> 16) & 0xff; }
         return SPH_OK;
@@ -1288,7 +1264,7 @@ extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes
     }
     if (field == SPH_F_PARTICLE_ID) {  // global ids when a scene is split over ranks
         if (bytes != n * 4) return fail(h, SPH_ERR_INVALID, "upload: size mismatch");
-        h->L->ensure_color(s); s.color_home_ok = 0; HIPCHK(h, hipStreamSynchronize(s.stream));
+        colors_leave_home(h); HIPCHK(h, hipStreamSynchronize(s.stream));
         HIPCHK(h, hipMemcpy(s.pid.cur(), src, n * 4, hipMemcpyHostToDevice));
         return SPH_OK;
     }

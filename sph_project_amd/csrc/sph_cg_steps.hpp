@@ -28,9 +28,7 @@ static int implicit_viscosity_non_pressure(SphHandle *h) {
     bool first = true;
     auto iteration = [&]() -> int {
         int rc = refresh(s.cg_p); if (rc) return rc;
-        s.cg_fuse = (fused && !first) ? 1 : 0;
-        { ProfScope p(h, SPH_K_CG_AP); h->L->cg_ap(s); }
-        s.cg_fuse = 0;
+        { ProfScope p(h, SPH_K_CG_AP); h->L->cg_ap(s, fused && !first); }
         rc = dots(1); if (rc) return rc;
         { ProfScope p(h, SPH_K_CG_VECTOR); h->L->cg_update_xr(s); }
         rc = dots(2); if (rc) return rc;
@@ -40,7 +38,7 @@ static int implicit_viscosity_non_pressure(SphHandle *h) {
     };
     { ProfScope p(h, SPH_K_CG_PREPARE); h->L->cg_prepare(s); }                     // :510
     int rc = refresh(s.cg_p); if (rc) return rc;                                   // the ghosts' initial guess
-    { ProfScope p(h, SPH_K_CG_AP); h->L->cg_ap(s); }                               // :511
+    { ProfScope p(h, SPH_K_CG_AP); h->L->cg_ap(s, false); }                        // :511
     { ProfScope p(h, SPH_K_CG_VECTOR); h->L->cg_prepare2(s); h->L->cg_alpha(s); }  // :512 (+ |r0|^2 for the first alpha)
     rc = dots(0); if (rc) return rc;
     // :445 conjugate_gradient_loop; tol starts at 1000 (:446), the residual reported with fixed_iterations
@@ -53,10 +51,8 @@ static int implicit_viscosity_non_pressure(SphHandle *h) {
     rc = refresh(s.cg_x); if (rc) return rc;                                       // solved velocities of the ghosts (:514)
     // :514-516: the explicit viscosity formula evaluated with the solved velocities gives the acceleration; the
     // fused pass adds gravity + surface tension and advances the ORIGINAL velocities (:470, :643)
-    s.np_visc_vel = s.cg_x;
     s.skip_viscosity = 0;
-    { ProfScope p(h, SPH_K_NON_PRESSURE); h->L->non_pressure(s); }
-    s.np_visc_vel = nullptr;
+    { ProfScope p(h, SPH_K_NON_PRESSURE); h->L->non_pressure(s, s.cg_x); }
     { ProfScope p(h, SPH_K_CG_VECTOR); h->L->cg_prepare_guess(s); }                // :517
     return SPH_OK;
 }

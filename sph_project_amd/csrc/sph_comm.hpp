@@ -48,7 +48,7 @@ struct SlabComm {
     int rebalance_moves = 0;     // cuts moved so far (this rank's lower + upper face)
     int *hist_dev = nullptr;     // nx_glob + nranks ints: layer histogram | every rank's z_lo
     int *hist_host = nullptr;    // pinned mirror
-    unsigned char id[128];
+    unsigned char id[128] = {};
     // data plane
     int push_wanted = 0;         // 0: never, 1: try, fall back to the control plane's transport if it cannot be set up, 2: required
     void *ipc_mapped[2] = {nullptr, nullptr};   // hipIpcOpenMemHandle results (closed in slab_comm_destroy)

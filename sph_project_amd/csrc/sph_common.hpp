@@ -302,177 +302,182 @@ template <class T> struct DBuf {
     void flip() { c = 1 - c; }
 };
 
-// Everything a launcher needs.  Owned by SphHandle.
+// The buffers and the carried bookkeeping of a handle.  Owned by SphHandle; every member initialises itself (sph_create allocates and
+// derives from the parameters, nothing else).  What concerns ONE launch is an argument of that launch (Launch below), not a member.
 struct State {
-    Consts c;
-    hipStream_t stream;
-    int cap;             // particle_max_num
+    Consts c = {};
+    hipStream_t stream = nullptr;
+    int cap = 0;         // particle_max_num
     // sorted, carried state
     DBuf<float4> posv, velm, orig;
     DBuf<int> meta, pid;
-    DBuf<unsigned> color;
+    DBuf<unsigned> color;   // the sorted copy of the colours: read through Launch::sorted_color (it may be out of date, see color_home)
     DBuf<float> rho;
     // grid
-    int *cell_count;     // G+1
-    int *cell_start;     // G+1 (exclusive scan, cell_start[G] = n)
-    int *cellid, *rank;  // per particle (pre-sort)
+    int *cell_count = nullptr;     // G+1
+    int *cell_start = nullptr;     // G+1 (exclusive scan, cell_start[G] = n)
+    int *cellid = nullptr, *rank = nullptr;  // per particle (pre-sort)
     // deterministic sort by run lists (RunList above; unsharded scenes): list heads per cell (G + 1, never reset), the epoch of the histogram
     // being taken / last taken, "the hashers of the coming sort filed their runs", and the sort's gather index (dest slot -> source particle)
-    unsigned long long *run_head;
-    int2 *run_rec;       // cap + G + 1 records (RunList::rec)
-    unsigned sort_epoch;
-    int run_lists_filed;
-    int *sort_inv;
-    long long n_list_sorts;   // sorts that went through k_sort_rank + k_gather_prep, since create (SphStats)
+    unsigned long long *run_head = nullptr;
+    int2 *run_rec = nullptr;       // cap + G + 1 records (RunList::rec)
+    unsigned sort_epoch = 0u;
+    int run_lists_filed = 0;
+    int *sort_inv = nullptr;
+    long long n_list_sorts = 0;   // sorts that went through k_sort_rank + k_gather_prep, since create (SphStats)
     // Bytes the sort's gather does not have to move (k_gather_prep, unsharded list sorts only):
-    //  * sort_skip_rho: set by a step whose next kernel recomputes every particle's density (WCSPH step of an all-fluid scene: the density
-    //    pass writes rho for all particles straight after the sort) -- consumed by the next sort;
+    //  * a density that the kernel launched next recomputes for every particle: the caller of Launch::scatter_stable says so (rho_dead);
     //  * colours stay AT HOME: color_home[particle id] is written when a particle is appended and never moves, while the ids are the append
     //    order (color_home_ok; ids set from outside or slab sharding end that).  color_stale: the sorted copy (State::color) is out of date --
-    //    whoever needs it (download, a sort by run records, slab activation) calls Launch::ensure_color first.
-    int sort_skip_rho;
-    unsigned *color_home;
-    int color_home_ok, color_stale;
-    int *tmp_idx;        // stable-sort scratch: int2 (first source index, length) per run, filed at the run's first slot (2 x cap ints)
+    //    Launch::sorted_color brings it up to date for whoever needs it (download, a sort by run records, slab activation).
+    unsigned *color_home = nullptr;
+    int color_home_ok = 0, color_stale = 0;
+    int *tmp_idx = nullptr;        // stable-sort scratch: int2 (first source index, length) per run, filed at the run's first slot (2 x cap ints)
     // Sums of the histogram over the scan's tiles of SCAN_TILE cells, two banks of scan_blocks + 1 ints.  Round 6: whoever takes the
     // histogram atomics (k_hash_count, the NextHash epilogue of the force pass, the slab kernels) adds its particles to the tile sums of
     // bank `scan_bank` as well -- one more atomic per WAVE, its lanes' cells lie in one tile nearly always -- so the scan is ONE launch:
     // k_scan_final reads that bank and clears the other one for the next histogram (like cell_count, which it clears behind itself).
-    int *scan_partial;
-    int scan_blocks;
-    int *scan_tile_state;   // per scan tile: (particles before it) + 1 if its cells hold that constant because it was EMPTY at the last scan, else 0 (k_scan_final)
-    int scan_bank;       // bank the hashers of the coming sort add to / the coming scan reads
-    int skip_residual;   // fixed-iteration solves (no stop test, nobody reads the residual): the walks leave their partial sums, k_reduce_partials is not launched
-    int tile_sums_ready; // ... and they did (else l_scan launches k_scan_reduce first: slab ranks)
-    int cell_count_clean;              // cell_count is all zero (the scan clears it behind itself)
-    int hist_taken;                    // the histogram of the coming sort has been taken (by k_hash_count, a NextHash epilogue, the slab kernels) and not yet scanned
-    int state_error;                   // sticky: a launcher met a state it must never see (l_scan without a histogram: ADVICE r05); reported by check_async
+    int *scan_partial = nullptr;
+    int scan_blocks = 0;
+    int *scan_tile_state = nullptr;   // per scan tile: (particles before it) + 1 if its cells hold that constant because it was EMPTY at the last scan, else 0 (k_scan_final)
+    int scan_bank = 0;       // bank the hashers of the coming sort add to / the coming scan reads
+    int skip_residual = 0;   // fixed-iteration solves (no stop test, nobody reads the residual): the walks leave their partial sums, k_reduce_partials is not launched
+    int tile_sums_ready = 0; // ... and they did (else l_scan launches k_scan_reduce first: slab ranks)
+    int cell_count_clean = 1;          // cell_count is all zero (the scan clears it behind itself)
+    int hist_taken = 0;                // the histogram of the coming sort has been taken (by k_hash_count, a NextHash epilogue, the slab kernels) and not yet scanned
+    int state_error = 0;               // sticky: a launcher met a state it must never see (l_scan without a histogram: ADVICE r05); reported by check_async
     // per-step scratch
-    float *rho_raw, *prs, *ptm;
-    float4 *acc;
+    float *rho_raw = nullptr, *prs = nullptr, *ptm = nullptr;
+    float4 *acc = nullptr;
     // DFSPH
-    float *alpha, *kappa, *kappa_v, *rho_star, *rho_deriv;
-    float *kappa_next, *kappa_v_next;  // written by the rho_adv pass, consumed (after a swap) by the next correction
-    float2 *kr;          // (kappa, rho) staging pair for the correction pass
+    float *alpha = nullptr, *kappa = nullptr, *kappa_v = nullptr, *rho_star = nullptr, *rho_deriv = nullptr;
+    float *kappa_next = nullptr, *kappa_v_next = nullptr;  // written by the rho_adv pass, consumed (after a swap) by the next correction
+    float2 *kr = nullptr;          // (kappa, rho) staging pair for the correction pass
     // PCISPH
-    float4 *pacc, *pvel, *ppos, *acc_np;
+    float4 *pacc = nullptr, *pvel = nullptr, *ppos = nullptr, *acc_np = nullptr;
     // IISPH (allocated for that method only): (dii, aii), (dij_pj, sum_i), w = dii p + dij_pj; rho* in rho_star
-    float4 *iisph_dii, *iisph_dij, *iisph_w;
+    float4 *iisph_dii = nullptr, *iisph_dij = nullptr, *iisph_w = nullptr;
     // PBF (allocated for that method only, particle_max_num each): x_old = (position at the sort, sorted cell id), lambda, the second position
     // buffer of the Jacobi fix_position (swapped with posv.cur() behind every pass), recentred walks per statistics bank
-    float4 *pbf_old, *pbf_pos; float *pbf_lambda; unsigned long long *pbf_recentred;
-    int poly6;           // the shared passes (NonPressurePass, RigidVolumePass) use PBF.py's poly6 / spiky kernels
+    float4 *pbf_old = nullptr, *pbf_pos = nullptr; float *pbf_lambda = nullptr; unsigned long long *pbf_recentred = nullptr;
+    int poly6 = 0;       // the shared passes (NonPressurePass, RigidVolumePass) use PBF.py's poly6 / spiky kernels
     // rigid contact (sph_set_rigid_contact; allocated when first enabled): the per-key table (64-bit fixed point, sph_contact.hpp),
     // the per-particle (sum of depth * n, contacts) of the targets, the accepted contacts of the last pass
-    int contact_on;
-    ContactArgs contact;
-    unsigned long long *contact_table, *contact_pairs;
-    float4 *contact_part;
+    int contact_on = 0;
+    ContactArgs contact = {};
+    unsigned long long *contact_table = nullptr, *contact_pairs = nullptr;
+    float4 *contact_part = nullptr;
     // device rigid integrator (sph_set_rigid_integrator; the body array is allocated with the first sph_set_rigid_body)
-    int rigid_int_on;
-    RigidIntArgs rigid_int;
-    RigidBodyDev *rigid_bodies;   // [SPH_NOBJ]
+    int rigid_int_on = 0;
+    RigidIntArgs rigid_int = {};
+    RigidBodyDev *rigid_bodies = nullptr;   // [SPH_NOBJ]
     // CG (implicit viscosity)
-    float4 *cg_p, *cg_Ap, *cg_x, *cg_b, *cg_r, *cg_v0;
-    float4 *cg_p2;       // second search-direction buffer (fused p update: the A p pass reads the old one and writes the new one)
-    int cg_fuse;         // the next A p pass applies the previous iteration's p update on the fly (CgApPass::fuse)
-    int cg_fused_loop;   // this solve runs the two-launch iteration (A p [+ combine], x / r update)
-    float *cg_dinv;      // 9 floats per particle
-    float4 *cg_part;     // 3 x cap: per-group parts of A p when the pass is split (CgApPass::SPLIT3)
-    int cg_nocombine;    // the last A p pass was split and left its dot-product shares itself: the x / r update adds the parts up (no k_cg_ap_combine)
-    int cg_split;        // this solve splits its A p passes (few fluid particles: see implicit_viscosity_non_pressure)
-    int split_next_pass; // launch_pass: launch the next SPLIT3 functor with gridDim.y = 3
-    int cg_parity;       // which of the two |r|^2 partial arrays the next x / r update reads
+    float4 *cg_p = nullptr, *cg_Ap = nullptr, *cg_x = nullptr, *cg_b = nullptr, *cg_r = nullptr, *cg_v0 = nullptr;
+    float4 *cg_p2 = nullptr;   // second search-direction buffer (fused p update: the A p pass reads the old one and writes the new one)
+    int cg_fused_loop = 0;     // this solve runs the two-launch iteration (A p [+ combine], x / r update)
+    float *cg_dinv = nullptr;  // 9 floats per particle
+    float4 *cg_part = nullptr; // 3 x cap: per-group parts of A p when the pass is split (CgApPass::SPLIT3)
+    int cg_nocombine = 0;      // the last A p pass was split and left its dot-product shares itself: the x / r update adds the parts up (no k_cg_ap_combine)
+    int cg_split = 0;          // this solve splits its A p passes (few fluid particles: see implicit_viscosity_non_pressure)
+    int cg_parity = 0;         // which of the two |r|^2 partial arrays the next x / r update reads
     // reductions
-    float *red_partial;  // per-block partial sums
-    int red_blocks;
-    DevScalars *scal;    // device
-    RigidPose *pose;     // device copy
-    int has_dynamic_rigid;
-    int has_rigid;
+    float *red_partial = nullptr;  // per-block partial sums
+    int red_blocks = 0;
+    DevScalars *scal = nullptr;    // device
+    RigidPose *pose = nullptr;     // device copy
+    int has_dynamic_rigid = 0;
+    int has_rigid = 0;
     // z-slab sharding (sph_halo.hpp): exchange tables and message buffers
-    int *xidx[2];        // carried through the sort: (kind << 29) | index, see HALO_KIND_*
-    int xcur;
-    int *halo_tab[8];    // slot tables, index = kind - 1 (sph_halo.hpp HALO_*): send, ghost, echo-send, echo-ghost x {down, up}
-    float4 *sendbuf[2], *recvbuf[2];     // 3 float4 per particle record
-    int *halo_counts;    // device, two banks of 4 (push transport: bank = message parity): [0..1] send counts, [2] dropped
-    SlabDyn *dyn;        // device-resident counts of a step, two banks (message parity): a kernel reads the last step's, writes this step's
-    SlabDyn *dyn_cur;    // the bank of the last step message (what c.n_dev and the field kernels look at)
-    int tables_pending;  // push transport: the next k_block_prep also fills the halo slot tables from xidx
-    int async_counts;    // the running step takes its counts from `dyn` (c.n_dev set, c.n = launch bound)
+    int *xidx[2] = {};   // carried through the sort: (kind << 29) | index, see HALO_KIND_*
+    int xcur = 0;
+    int *halo_tab[8] = {};   // slot tables, index = kind - 1 (sph_halo.hpp HALO_*): send, ghost, echo-send, echo-ghost x {down, up}
+    float4 *sendbuf[2] = {}, *recvbuf[2] = {};     // 3 float4 per particle record
+    int *halo_counts = nullptr;    // device, two banks of 4 (push transport: bank = message parity): [0..1] send counts, [2] dropped
+    SlabDyn *dyn = nullptr;        // device-resident counts of a step, two banks (message parity): a kernel reads the last step's, writes this step's
+    SlabDyn *dyn_cur = nullptr;    // the bank of the last step message (what c.n_dev and the field kernels look at)
+    int tables_pending = 0;  // push transport: the next k_block_prep also fills the halo slot tables from xidx
+    int async_counts = 0;    // the running step takes its counts from `dyn` (c.n_dev set, c.n = launch bound)
     // push transport (sph_halo.hpp): my inbox, the neighbours' inboxes mapped through hipIpc, message numbers
     struct PushState {
-        int on;                        // halo payload travels by device stores into the neighbour's inbox
-        char *inbox;                   // mine (device memory the neighbours write)
-        char *peer[2];                 // lower / upper neighbour's inbox in my address space (null: no neighbour)
-        int rec_cap;                   // records a step message can hold (normally the particle capacity)
-        size_t rec_bytes, fld_bytes;   // size of one step-message / field-message region
-        unsigned rec_seq, fld_seq;     // messages sent (= received) so far
-        long long timeout_ticks;       // bounded waits of the device (100 MHz wall clock)
-        SlabDyn *mirror;               // pinned host copy of `dyn`, written by the wait kernel
+        int on = 0;                        // halo payload travels by device stores into the neighbour's inbox
+        char *inbox = nullptr;             // mine (device memory the neighbours write)
+        char *peer[2] = {};                // lower / upper neighbour's inbox in my address space (null: no neighbour)
+        int rec_cap = 0;                   // records a step message can hold (normally the particle capacity)
+        size_t rec_bytes = 0, fld_bytes = 0;   // size of one step-message / field-message region
+        unsigned rec_seq = 0, fld_seq = 0;     // messages sent (= received) so far
+        long long timeout_ticks = 0;       // bounded waits of the device (100 MHz wall clock)
+        SlabDyn *mirror = nullptr;         // pinned host copy of `dyn`, written by the wait kernel
     } push;
     // slab sharding, compute / halo overlap: the layers of a slab are contiguous index ranges of the sorted arrays (x is the slowest axis of
     // the cell order), so the 256-particle tiles fall into a BOUNDARY set (anything within two own layers of a face, plus the ghost layers)
-    // and an INTERIOR set; k_block_prep lists both once per sort.  A pass launched with tile_sel = 1 / 2 walks one set only: boundary
-    // tiles first, their values go out, interior tiles run while the message is in flight.
-    int *tile_list[2];   // [0] boundary tiles, [1] interior tiles (XCD-remapped order), device
-    int *tile_cnt;       // their lengths (2 ints, device)
-    unsigned char *tile_class;   // per tile: 1 = boundary set.  The INTERIOR launch is an ordinary launch of every tile (no list: a list costs each
-                                 // workgroup one more dependent load in front of its header) whose boundary tiles leave at once.
-    int tile_sel;        // 0: every tile (default); 1: boundary set; 2: interior set -- read by launch_pass
-    int tile_plan_n;     // particle count (launch bound) the lists were built for, -1: none
-    int tile_bound_b;    // workgroups a boundary launch gets: last known number of boundary tiles + margin (checked on the device: SLAB_ST_BOUND)
-    HaloSend presend;    // on != 0: the next wcsph_forces launch classifies its particles and sends the next step message itself
-    HaloFieldSend fieldsend;   // on != 0: the next WCSPH density launch stores its boundary values into the field message itself
-    int preclassified;   // ... and has done so: the next step's exchange starts with the hash alone
-    NextHash nexthash;   // on != 0: the next wcsph_forces launch hashes the particles for the next step's sort itself
-    int prehashed;       // ... and has done so: the next step's sort starts with the scan (l_hash_count returns at once)
-    long long n_hash_launches, n_prehashed_sorts;   // k_hash_count launches / sorts that started from a NextHash hash, since create (SphStats)
-    int halo_cap;        // particles per message buffer
-    int halo_longest;    // longest halo message of the running step, in particles (sent or received)
-    int slab_active, z_lo, z_hi, has_down, has_up;
-    unsigned *nbr_mask;  // [9][cap]: acceptance mask of the first 32 candidates of every (particle, run), see process_run
-    unsigned *nbr_mask_hi;  // [9][cap]: candidates 32..63 of the runs that have them
-    int masks_valid;
-    int density_books_forces;   // WCSPH step with the fused force pass: the density pass counts that pass's pairs too (it walks the same masks)
-    int uniform_mass;    // all-fluid scene whose particles all carry the same mass (sph_api.hip refresh_counts): WcsphForcePass<true, true>
+    // and an INTERIOR set; k_block_prep lists both once per sort.  A density pass launched with DensityOpts::tiles = 1 / 2 walks one set
+    // only: boundary tiles first, their values go out, interior tiles run while the message is in flight.
+    int *tile_list[2] = {};   // [0] boundary tiles, [1] interior tiles (XCD-remapped order), device
+    int *tile_cnt = nullptr;  // their lengths (2 ints, device)
+    unsigned char *tile_class = nullptr;   // per tile: 1 = boundary set.  The INTERIOR launch is an ordinary launch of every tile (no list: a list costs each
+                                           // workgroup one more dependent load in front of its header) whose boundary tiles leave at once.
+    int tile_plan_n = -1;     // particle count (launch bound) the lists were built for, -1: none
+    int tile_bound_b = 0;     // workgroups a boundary launch gets: last known number of boundary tiles + margin (checked on the device: SLAB_ST_BOUND)
+    HaloSend presend = {};    // on != 0: the next wcsph_forces launch classifies its particles and sends the next step message itself
+    HaloFieldSend fieldsend = {};   // on != 0: the next WCSPH density launch stores its boundary values into the field message itself
+    int preclassified = 0;    // ... and has done so: the next step's exchange starts with the hash alone
+    int prehashed = 0;        // a force pass / position update has hashed for the coming sort (ForceOpts::hash_next, advect_boundary): that sort starts with the scan (l_hash_count returns at once)
+    long long n_hash_launches = 0, n_prehashed_sorts = 0;   // k_hash_count launches / sorts that started from a NextHash hash, since create (SphStats)
+    int halo_cap = 0;         // particles per message buffer
+    int halo_longest = 0;     // longest halo message of the running step, in particles (sent or received)
+    int slab_active = 0, z_lo = 0, z_hi = 0, has_down = 0, has_up = 0;
+    unsigned *nbr_mask = nullptr;     // [9][cap]: acceptance mask of the first 32 candidates of every (particle, run), see process_run
+    unsigned *nbr_mask_hi = nullptr;  // [9][cap]: candidates 32..63 of the runs that have them
+    int masks_valid = 0;
+    int uniform_mass = 0;     // all-fluid scene whose particles all carry the same mass (sph_api.hip refresh_counts): WcsphForcePass<true, true>
     // device-controlled solver loops (sph_steps.hpp device_loop): every kernel of an iteration starts with a look at
     // scal->flags[0] (stop) when loop_flag is set; the iteration's reduction kernel evaluates the stop criterion itself
-    const int *loop_flag;    // null outside such a loop
-    int loop_slot;           // reduction slot the criterion applies to
-    int loop_kind;           // 1: (double)(sum / denom) <= thr   2: (sum / denom) < (float)thr   3: CG, !(err > thr)
-    float loop_denom; double loop_thr;
-    unsigned char *lane_perm;  // [ceil(cap / 256) * 256]: lane -> particle map of every 256-particle workgroup (k_lane_perm)
-    int *blk_flag, *blk_list, *blk_count;   // per-workgroup 'holds fluid' flag, ascending list of those workgroups, its length (device)
-    int list_n;                // particle count the list was built for (-1: none)
+    const int *loop_flag = nullptr;   // null outside such a loop
+    int loop_slot = 0;            // reduction slot the criterion applies to
+    int loop_kind = 0;            // 1: (double)(sum / denom) <= thr   2: (sum / denom) < (float)thr   3: CG, !(err > thr)
+    float loop_denom = 1.0f; double loop_thr = 0.0;
+    unsigned char *lane_perm = nullptr;  // [ceil(cap / 256) * 256]: lane -> particle map of every 256-particle workgroup (k_lane_perm)
+    int *blk_flag = nullptr, *blk_list = nullptr, *blk_count = nullptr;   // per-workgroup 'holds fluid' flag, ascending list of those workgroups, its length (device)
+    int list_n = -1;              // particle count the list was built for (-1: none)
     // Length of the list as the HOST knows it: k_compact_blocks stores it into pinned memory, an event behind it tells when it has landed.
     // A launch over the list then gets exactly that many workgroups (list_grid, sph_kernels.hip) instead of one per tile of the scene
     // with all but the listed ones leaving at once: the buckling scene has 8,496 tiles of which ~420 hold fluid, and the 24,000 empty
     // workgroups of a three-way split A p launch cost 16 % of the walk (round 5: C5 1.63 -> 1.47 ms/step).
-    volatile int *list_count_pinned;
-    hipEvent_t list_count_event;
-    int list_count_known;      // -1: not seen yet (the launches use the full grid until the event has passed)
-    int last_pass_listed;      // the last pass with a reduction ran the listed workgroups only: so must the sum of its partials
-    int *blk_hdr;              // [ceil(cap / 256)][BLK_HDR_INTS]: cell span and candidate-run windows of every workgroup
-    int perm_n;                // particle count blk_hdr / lane_perm were built for (-1: none)
-    int has_emitter;     // gravitationUpper set (base_solver.py:18-23)
-    int visc_rho_raw;    // viscosity reads rho_raw (WCSPH: density before the EOS clamp)
-    int skip_viscosity;  // implicit viscosity: explicit term not part of the fused pass
-    float4 *np_acc_out;  // non-pressure acceleration sink (PCISPH), else null
-    const float4 *np_visc_vel; // velocities for the viscous term (implicit viscosity: cg_x), else null
+    volatile int *list_count_pinned = nullptr;
+    hipEvent_t list_count_event = nullptr;
+    int list_count_known = -1;    // -1: not seen yet (the launches use the full grid until the event has passed)
+    int last_pass_listed = 0;     // the last pass with a reduction ran the listed workgroups only: so must the sum of its partials
+    int *blk_hdr = nullptr;       // [ceil(cap / 256)][BLK_HDR_INTS]: cell span and candidate-run windows of every workgroup
+    int perm_n = -1;              // particle count blk_hdr / lane_perm were built for (-1: none)
+    int has_emitter = 0;     // gravitationUpper set (base_solver.py:18-23)
+    int visc_rho_raw = 0;    // viscosity reads rho_raw (WCSPH: density before the EOS clamp)
+    int skip_viscosity = 0;  // implicit viscosity: explicit term not part of the fused pass
+    float4 *np_acc_out = nullptr;  // non-pressure acceleration sink (PCISPH), else null
+};
+
+// Options of one launch (Launch::density, Launch::wcsph_forces)
+struct DensityOpts {
+    int tiles = 0;             // slab sharding, compute / halo overlap: 0 every tile, 1 the boundary set, 2 the interior set (State::tile_list)
+    bool books_forces = false; // WCSPH step with the fused force pass: the density pass counts that pass's pairs too (it walks the same masks)
+};
+struct ForceOpts {
+    bool booked_by_density = false;   // the density pass in front of this one has counted its pairs (DensityOpts::books_forces); else it counts its own
+    bool hash_next = false;           // hash the positions it stores for the next step's sort (NextHash): the caller knows that nothing touches the particles before it
 };
 
 // Function table implemented twice (strict / fast math), see sph_kernels.hip.
 struct Launch {
-    void (*ensure_color)(State &);   // materialise State::color in sorted order from color_home (no-op unless color_stale)
+    unsigned *(*sorted_color)(State &);   // the colours in sorted order (State::color.cur()), materialised from color_home first if color_stale
     void (*hash_count)(State &);
     void (*scan)(State &);
-    void (*scatter)(State &);
-    void (*scatter_stable)(State &);
-    void (*density)(State &, int eos);
-    void (*non_pressure)(State &);
+    void (*scatter)(State &);                   // carries every array
+    // rho_dead: the kernel launched next rewrites the density of every particle, so the gather need not carry it (list sorts of all-fluid
+    // scenes drop it; the new rho.cur() then holds garbage until that kernel has run -- 0xFF bytes in the test-hook library)
+    void (*scatter_stable)(State &, bool rho_dead);
+    void (*density)(State &, int eos, DensityOpts o);
+    void (*non_pressure)(State &, const float4 *visc_vel);   // visc_vel: velocities for the viscous term (implicit viscosity: cg_x), null: the particles' own
     void (*pressure_integrate)(State &);
-    void (*wcsph_forces)(State &);              // non_pressure + pressure_integrate in one neighbour walk (WCSPH)
+    void (*wcsph_forces)(State &, ForceOpts o); // non_pressure + pressure_integrate in one neighbour walk (WCSPH)
     void (*rigid_volume)(State &);
     void (*renew_rigid)(State &);
     void (*prepare_emitter)(State &);
@@ -483,7 +488,7 @@ struct Launch {
     void (*dfsph_density_alpha_div)(State &);   // + the first density derivative of the divergence solve (one neighbour walk less per step)
     void (*dfsph_rho_adv)(State &, int mode);   // 0: density derivative (+kappa_v), 1: density star (+kappa)
     void (*dfsph_correct)(State &, int mode);   // 0: divergence step, 1: density step
-    void (*advect_boundary)(State &);           // x += dt v, emitter, boundary (DFSPH position update)
+    void (*advect_boundary)(State &, bool hash_next);   // x += dt v, emitter, boundary (DFSPH position update); hash_next: + the hash of the sort that follows (NextHash)
     // PCISPH
     void (*pcisph_init)(State &);
     void (*pcisph_rho_star)(State &);
@@ -550,7 +555,7 @@ struct Launch {
     void (*halo_presend_begin)(State &);   // begin the next step message: the force pass launched next fills it (State::presend)
     // implicit viscosity (CG)
     void (*cg_prepare)(State &);
-    void (*cg_ap)(State &);
+    void (*cg_ap)(State &, bool fuse);   // fuse: apply the previous iteration's p update on the fly (CgApPass::fuse)
     void (*cg_prepare2)(State &);
     void (*cg_alpha)(State &);
     void (*cg_check)(State &);   // fused p update: stop test at the end of a batch of iterations

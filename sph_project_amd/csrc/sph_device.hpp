@@ -999,7 +999,7 @@ k_gather_prep(const Consts c, int n, const int *__restrict__ inv, SortArrays a, 
         a.meta_out[d] = meta_i;
         a.pid_out[d] = a.pid_in[i];
         if (a.color_in) a.color_out[d] = a.color_in[i];   // (null: the colours stay at home, State::color_home)
-        if (a.rho_in) a.rho_out[d] = a.rho_in[i];         // (null: the next kernel recomputes every density, State::sort_skip_rho)
+        if (a.rho_in) a.rho_out[d] = a.rho_in[i];         // (null: the next kernel recomputes every density, Launch::scatter_stable)
         if (a.orig_in) a.orig_out[d] = a.orig_in[i];
     }
     block_prep_tile(c, n, p, meta_i, cell_start, blk_hdr, perm, blk_flag, cellw, s_cnt, s_c);

@@ -124,32 +124,35 @@ void l_block_prep(State &s, bool launch = true) {
     s.perm_n = n;
 }
 
-void l_ensure_color(State &s) {
-    if (!s.color_stale) return;
-    s.color_stale = 0;
-    if (s.c.n > 0) hipLaunchKernelGGL(k_color_from_home, dim3(cdiv(s.c.n, 256)), dim3(256), 0, s.stream, s.c.n, s.pid.cur(), s.color_home, s.color.cur());
+// the colours in sorted order: State::color.cur(), brought up to date from the colours at home first where a list sort left them there
+unsigned *l_sorted_color(State &s) {
+    if (s.color_stale) {
+        s.color_stale = 0;
+        if (s.c.n > 0) hipLaunchKernelGGL(k_color_from_home, dim3(cdiv(s.c.n, 256)), dim3(256), 0, s.stream, s.c.n, s.pid.cur(), s.color_home, s.color.cur());
+    }
+    return s.color.cur();
 }
 
-void l_scatter_impl(State &s, bool stable) {
+// rho_dead: the kernel launched next rewrites every particle's density (Launch::scatter_stable)
+void l_scatter_impl(State &s, bool stable, bool rho_dead) {
     const int n = s.c.n;
-    if (n == 0) { s.sort_skip_rho = 0; return; }
+    if (n == 0) return;
     SortArrays a;
     a.G = s.c.G;
     a.posv_in = s.posv.cur(); a.posv_out = s.posv.alt();
     a.velm_in = s.velm.cur(); a.velm_out = s.velm.alt();
     a.meta_in = s.meta.cur(); a.meta_out = s.meta.alt();
     a.pid_in = s.pid.cur(); a.pid_out = s.pid.alt();
-    a.color_in = s.color.cur(); a.color_out = s.color.alt();
+    a.color_out = s.color.alt();
     a.rho_in = s.rho.cur(); a.rho_out = s.rho.alt();
     a.orig_in = s.orig.cur(); a.orig_out = s.orig.alt();
     a.xidx_in = s.slab_active ? s.xidx[s.xcur] : nullptr; a.xidx_out = s.slab_active ? s.xidx[1 - s.xcur] : nullptr;
     // deterministic sort of an unsharded scene whose hashers filed their runs into per-cell lists: rank from the lists, then a gather by
     // destination tile that prepares the tile for the neighbour passes as it goes -- 2 launches instead of 3 (k_scatter_index, k_scatter, k_block_prep)
     const bool by_lists = stable && s.run_lists_filed && s.run_head && s.sort_inv && !s.slab_active;
-    if (!by_lists) l_ensure_color(s);   // (k_scatter moves State::color)
+    a.color_in = by_lists ? s.color.cur() : l_sorted_color(s);   // (k_scatter moves State::color)
     s.run_lists_filed = 0;
-    const bool skip_rho = by_lists && s.sort_skip_rho && s.c.all_fluid;
-    s.sort_skip_rho = 0;
+    const bool skip_rho = by_lists && rho_dead && s.c.all_fluid;
     if (by_lists) {
         // bytes that need not move: the colours (at home, keyed by the particle id, while the ids are the append order) and a density that
         // the next kernel recomputes for every particle
@@ -172,14 +175,18 @@ void l_scatter_impl(State &s, bool stable) {
                            s.cell_start, (const int2 *)s.tmp_idx, a, s.c.n_dev);
     }
     s.posv.flip(); s.velm.flip(); s.meta.flip(); s.pid.flip(); s.color.flip(); s.rho.flip();
+#ifdef SPH_TEST_HOOKS
+    // test-hook library only: a density the gather dropped reads as NaN until the kernel that was promised has rewritten it
+    if (skip_rho) hipMemsetAsync(s.rho.cur(), 0xFF, sizeof(float) * (size_t)n, s.stream);
+#endif
     s.masks_valid = 0;  // new order, new candidate runs
     if (!s.slab_active) l_block_prep(s, !by_lists);
     else s.perm_n = s.list_n = -1;   // slab sharding: rebuilt once the dead particles behind the live ones are dropped (launch_pass)
     if (s.orig.cur()) s.orig.flip();
     if (s.slab_active) s.xcur = 1 - s.xcur;
 }
-void l_scatter(State &s) { l_scatter_impl(s, false); }
-void l_scatter_stable(State &s) { l_scatter_impl(s, true); }
+void l_scatter(State &s) { l_scatter_impl(s, false, false); }
+void l_scatter_stable(State &s, bool rho_dead) { l_scatter_impl(s, true, rho_dead); }
 
 // Workgroups a launch over the list of fluid-holding tiles needs: the list's length once the host has seen it (State::list_count_pinned),
 // one per tile of the scene until then (the kernels send the surplus home at their top).  Never zero: a functor whose prologue keeps a
@@ -196,7 +203,8 @@ int list_grid(State &s, int nb) {
 }
 
 // mask_mode: 0 compute, 1 compute + store (first pass after a sort), 2 reuse (see process_run)
-template <class P> void launch_pass(State &s, const P &p, int mask_mode = 0) {
+// tiles: 0 every tile, 1 / 2 the boundary / interior set of a slab (DensityOpts::tiles); split: gridDim.y of a PassSplit functor, 0 = not split
+template <class P> void launch_pass(State &s, const P &p, int mask_mode = 0, int tiles = 0, int split = 0) {
     const int n = s.c.n;
     if (n == 0) return;
     const int nb = cdiv(n, P::BLOCK);
@@ -212,8 +220,8 @@ template <class P> void launch_pass(State &s, const P &p, int mask_mode = 0) {
     const int *bl = use_list ? s.blk_list : nullptr, *bc = use_list ? s.blk_count : nullptr;
     int nb_launch = nb;
     const unsigned char *skip = nullptr;
-    if (s.tile_sel && s.tile_plan_n == n && !use_list) {   // one set of the slab's tiles only (compute / halo overlap)
-        if (s.tile_sel == 1) { bl = s.tile_list[0]; bc = s.tile_cnt; nb_launch = s.tile_bound_b > 0 ? s.tile_bound_b : 1; }   // the listed boundary tiles; the grid is a bound
+    if (tiles && s.tile_plan_n == n && !use_list) {   // one set of the slab's tiles only (compute / halo overlap)
+        if (tiles == 1) { bl = s.tile_list[0]; bc = s.tile_cnt; nb_launch = s.tile_bound_b > 0 ? s.tile_bound_b : 1; }   // the listed boundary tiles; the grid is a bound
         else skip = s.tile_class;   // every tile, the boundary ones leave
     }
     if (use_list) nb_launch = list_grid(s, nb);
@@ -222,8 +230,7 @@ template <class P> void launch_pass(State &s, const P &p, int mask_mode = 0) {
     if (tl) hipMemsetAsync(tl, 0, (size_t)nb * 16 * 8, s.stream);
     constexpr int MODES = PassModes<P>::value;
     if (!(MODES & (1 << mask_mode))) mask_mode = 0;   // every functor has mode 0
-    const int gy = (PassSplit<P>::value && s.split_next_pass) ? s.split_next_pass : 1;   // 3: one workgroup per (tile, x-offset group); 2: groups {0, 1} / {2}
-    s.split_next_pass = 0;
+    const int gy = (PassSplit<P>::value && split) ? split : 1;   // 3: one workgroup per (tile, x-offset group); 2: groups {0, 1} / {2}
 #define SPH_LAUNCH_NBR(M) hipLaunchKernelGGL((k_nbr_pass<P, M>), dim3(nb_launch, gy), dim3(P::BLOCK), 0, s.stream, s.c, s.cell_start, p, s.scal, nb, s.nbr_mask, s.nbr_mask_hi, s.cap, s.blk_hdr, perm, tl, s.loop_flag, bl, bc, skip)
     if (mask_mode == 1) {
         if constexpr ((MODES & 0b010) != 0) { SPH_LAUNCH_NBR(1); s.masks_valid = 1; }
@@ -258,36 +265,36 @@ template <class P> void launch_pass(State &s, const P &p, int mask_mode = 0) {
     }
 }
 
-void l_density(State &s, int eos) {
+void l_density(State &s, int eos, DensityOpts o) {
     HaloFieldSend fs = s.fieldsend;
     if (!eos) fs.on = 0;
     s.fieldsend.on = 0;
-    const int sp = s.density_books_forces ? 1 + 3 : 1, se = s.density_books_forces ? 2 : 1;   // (WcsphForcePass: PAIR_WEIGHT 3, one evaluation per pair)
+    const int sp = o.books_forces ? 1 + 3 : 1, se = o.books_forces ? 2 : 1;   // (WcsphForcePass: PAIR_WEIGHT 3, one evaluation per pair)
     if (s.c.all_fluid) {
-        if (eos) { DensityPass<true, true> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1); }
-        else { DensityPass<true, false> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1); }
+        if (eos) { DensityPass<true, true> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
+        else { DensityPass<true, false> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
     } else {
-        if (eos) { DensityPass<false, true> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1); }
-        else { DensityPass<false, false> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1); }
+        if (eos) { DensityPass<false, true> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
+        else { DensityPass<false, false> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
     }
 }
 
 // rho_src: WCSPH viscosity reads the unclamped density (rho_raw); DFSPH/PCISPH read particle_densities.
-void l_non_pressure(State &s) {
+void l_non_pressure(State &s, const float4 *visc_vel) {
     const float *rho_src = s.visc_rho_raw ? s.rho_raw : s.rho.cur();
     if (s.poly6) {   // PBF: poly6 surface tension, spiky viscosity (PBF.py:22-48)
         if (s.c.all_fluid) {
-            NonPressurePass<true, Poly6Kernel> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, s.np_visc_vel};
+            NonPressurePass<true, Poly6Kernel> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, visc_vel};
             launch_pass(s, p, 2);
         } else {
-            NonPressurePass<false, Poly6Kernel> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, s.np_visc_vel};
+            NonPressurePass<false, Poly6Kernel> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, visc_vel};
             launch_pass(s, p, 2);
         }
     } else if (s.c.all_fluid) {
-        NonPressurePass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, s.np_visc_vel};
+        NonPressurePass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, visc_vel};
         launch_pass(s, p, 2);
     } else {
-        NonPressurePass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, s.np_visc_vel};
+        NonPressurePass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, visc_vel};
         launch_pass(s, p, 2);
     }
     s.velm.flip();
@@ -329,14 +336,13 @@ void l_pressure_integrate(State &s) {
 }
 
 // WCSPH.py:30-36, 45 as one pass (see WcsphForcePass); same buffer choreography as the two passes it replaces
-void l_wcsph_forces(State &s) {
+void l_wcsph_forces(State &s, ForceOpts o) {
     // this pass as the next step's k_hash_count (NextHash): only where the histogram is clean (the scan cleared it behind itself) and
     // every particle is an active fluid particle of an unsharded scene (wcsph_step decides whether another step follows untouched)
     NextHash nh{0, s.cellid, s.rank, s.cell_count, tile_sum_bank(s), RunList{nullptr, nullptr, 0, 0u}};
-    if (s.nexthash.on && s.c.all_fluid && !s.slab_active && s.cell_count_clean && s.density_books_forces && s.c.n > 0) nh.on = 1;
-    s.nexthash.on = 0;
+    if (o.hash_next && s.c.all_fluid && !s.slab_active && s.cell_count_clean && o.booked_by_density && s.c.n > 0) nh.on = 1;
     if (nh.on) nh.rl = run_list_of(s, true);
-    if (!s.density_books_forces) {   // launched outside wcsph_step's density + forces pair: nobody has booked this walk's pairs
+    if (!o.booked_by_density) {   // launched outside wcsph_step's density + forces pair: nobody has booked this walk's pairs
         if (s.c.all_fluid) {
             WcsphForcePass<true, false, true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho_raw, s.ptm, s.prs, s.rho.cur(), s.velm.alt(), s.acc, s.posv.alt(), s.scal, s.pose, s.c.rho0, s.presend, nh};
             launch_pass(s, p, 2);
@@ -467,7 +473,7 @@ const Launch *SPH_LAUNCH_FN() {
     static Launch L;
     static bool init = false;
     if (!init) {
-        L.ensure_color = l_ensure_color;
+        L.sorted_color = l_sorted_color;
         L.hash_count = l_hash_count;
         L.scan = l_scan;
         L.scatter = l_scatter;

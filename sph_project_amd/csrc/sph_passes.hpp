@@ -435,7 +435,7 @@ struct PressurePass {
 // Per candidate: A = (x, y, z, m_j | rho0 V_j), B = (v_j, rho_raw_j | -1 static / -2 dynamic rigid), C = p_j / rho_j^2.
 // Bytes / particle: R posv 16 + velm 16 + rho_raw 4 + ptm 4 (+ own prs, rho 8) -> W acc 16 + posv 16 + velm 16.
 // CNT: the pass counts its own accepted pairs.  Inside wcsph_step they are booked by the density pass whose masks it walks
-// (DensityPass::stat_pairs, State::density_books_forces); a caller that launches this pass any other way gets the counting
+// (DensityPass::stat_pairs, DensityOpts::books_forces); a caller that launches this pass any other way gets the counting
 // instantiation (l_wcsph_forces), so that pair_interactions never under-reports.
 template <bool AF, bool UM = false, bool CNT = false>   // UM (fast build, all fluid): every particle carries the same mass -- m_ij = m, the products with it are hoisted
 struct WcsphForcePass {

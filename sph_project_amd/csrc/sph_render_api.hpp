@@ -227,8 +227,8 @@ extern "C" int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mas
     // colours as sph_download(SPH_F_COLOR) reads them: at home by particle id while the ids are the append order, else the sorted copy
     d.col_home = nullptr; d.col = nullptr;
     if (s.color_home && s.color_home_ok) d.col_home = s.color_home;
-    else { h->L->ensure_color(s); d.col = s.color.cur(); }
-    HIPCHK(r, hipStreamSynchronize(s.stream));   // the handle's last step has written the positions (and ensure_color the colours)
+    else d.col = h->L->sorted_color(s);
+    HIPCHK(r, hipStreamSynchronize(s.stream));   // the handle's last step has written the positions (and sorted_color the colours)
     const int n = h->n;
     { int rc = rend_room(r, (size_t)n, false); if (rc) return rc; }
     HIPCHK(r, r->clk[0].mark(0));

@@ -52,10 +52,9 @@ k_advect_boundary(const Consts c, float4 *posv, float4 *velm, int *meta, const R
     }
 }
 
-static void l_advect_boundary(State &s) {
+static void l_advect_boundary(State &s, bool hash_next) {
     NextHash nh{0, s.cellid, s.rank, s.cell_count, tile_sum_bank(s), RunList{nullptr, nullptr, 0, 0u}};
-    if (s.nexthash.on && s.c.all_fluid && !s.slab_active && s.cell_count_clean && s.c.n > 0) nh.on = 1;
-    s.nexthash.on = 0;
+    if (hash_next && s.c.all_fluid && !s.slab_active && s.cell_count_clean && s.c.n > 0) nh.on = 1;
     if (s.c.n == 0) return;
     if (nh.on) nh.rl = run_list_of(s, true);
     s.masks_valid = 0;  // positions move
@@ -206,11 +205,11 @@ static void l_cg_prepare(State &s) {
 #define CG_LIST CG_LISTED ? s.blk_list : nullptr, CG_LISTED ? s.blk_count : nullptr
 // grid of a per-particle CG kernel: the listed workgroups only once the host knows how many there are (list_grid)
 #define CG_GRID(nb) (CG_LISTED ? list_grid(s, (nb)) : (nb))
-static void l_cg_ap(State &s) {
+// fuse_p: this A p pass applies the previous iteration's p update on the fly (CgApPass::fuse), p_old = cg_p, p_new = cg_p2
+static void l_cg_ap(State &s, bool fuse_p) {
     const bool split = s.cg_split && s.cg_part && s.c.n > 0;
-    s.split_next_pass = split ? s.cg_split : 0;   // 3 ways (sph_cg_steps.hpp)
-    // s.cg_fuse: this A p pass applies the previous iteration's p update on the fly (CgApPass::fuse), p_old = cg_p, p_new = cg_p2
-    const int fuse = s.cg_fuse ? 1 : 0;
+    const int ways = split ? s.cg_split : 0;   // 3 ways (sph_cg_steps.hpp)
+    const int fuse = fuse_p ? 1 : 0;
     const bool lst = CG_LISTED;
     const int nb = s.c.n > 0 ? cdiv(s.c.n, 256) : 0;
     // inside the unsharded loop with the fused p update the split walks leave their shares of p . A p themselves (CG_PART(4..6)) and the
@@ -222,12 +221,12 @@ static void l_cg_ap(State &s) {
         CgApPass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), CG_RHO, s.cg_p, s.cg_dinv, s.cg_Ap, CG_PART(2), s.cg_part, s.cap,
                          s.cg_r, s.cg_p2, CG_PART(s.cg_parity), CG_PART(3), nb, lst ? s.blk_list : nullptr, lst ? s.blk_count : nullptr,
                          fuse, s.loop_flag ? 1 : 0, (float)s.loop_thr, 0.0f, pdot, s.red_blocks};
-        launch_pass(s, p, 2);
+        launch_pass(s, p, 2, 0, ways);
     } else {
         CgApPass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), CG_RHO, s.cg_p, s.cg_dinv, s.cg_Ap, CG_PART(2), s.cg_part, s.cap,
                           s.cg_r, s.cg_p2, CG_PART(s.cg_parity), CG_PART(3), nb, lst ? s.blk_list : nullptr, lst ? s.blk_count : nullptr,
                           fuse, s.loop_flag ? 1 : 0, (float)s.loop_thr, 0.0f, pdot, s.red_blocks};
-        launch_pass(s, p, 2);
+        launch_pass(s, p, 2, 0, ways);
     }
     if (split && !nocombine)   // the three parts -> A p and the partials of p . A p (what finish() and the pass's reduction do otherwise)
         hipLaunchKernelGGL(k_cg_ap_combine, dim3(CG_GRID(cdiv(s.c.n, 256))), dim3(256), 0, s.stream, s.c, s.meta.cur(), CG_AF, s.cg_part, s.cap, s.cg_p,

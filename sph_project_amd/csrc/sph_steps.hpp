@@ -181,7 +181,7 @@ static int run_non_pressure(SphHandle *h) {
         return rc;
     }
     ProfScope p(h, SPH_K_NON_PRESSURE);
-    h->L->non_pressure(h->st);
+    h->L->non_pressure(h->st, nullptr);
     return SPH_OK;
 }
 
@@ -191,32 +191,28 @@ static int wcsph_step(SphHandle *h) {
     // (slab_neighbor_search_push, "async"): implicit viscosity and the unfused force passes launch exact grids instead
     const bool fused = !h->prm.viscosity_implicit;
     if (s.slab_active) { int rc = slab_neighbor_search(h, fused); if (rc) return rc; }
-    else { s.sort_skip_rho = s.c.all_fluid; ph_neighbor_search(h); }          // WCSPH.py:28 (the density pass below rewrites every rho: the sort need not move it)
+    else ph_neighbor_search(h, true);                                         // WCSPH.py:28 (the density pass below rewrites every rho: the sort need not move it)
     ph_rigid_volume(h);                                                       // base_solver.py:696 (see ph_rigid_volume)
-    s.density_books_forces = (fused && !getenv("SPH_FORCES_COUNT_OWN")) ? 1 : 0;   // (switch: the force pass counts its own pairs -- the counting instantiation any other caller of l_wcsph_forces gets)
-    struct Unbook { State &s; ~Unbook() { s.density_books_forces = 0; } } unbook{s};
+    const bool books = fused && !getenv("SPH_FORCES_COUNT_OWN");   // (switch: the force pass counts its own pairs -- the counting instantiation any other caller of l_wcsph_forces gets)
     // Sharded over the push transport, fluid only: the density pass runs the slab's BOUNDARY tiles first, their rho / p go out to the
     // neighbours, and the INTERIOR tiles (everything more than two layers from a face) run while that message is in flight; only
     // then does the stream wait for the neighbours' (SURVEY 8e "compute interior cells while halos are in flight").
     const bool overlap = s.slab_active && s.push.on && s.tile_list[0] && s.c.all_fluid && s.tile_plan_n == s.c.n && (s.has_down || s.has_up);
     if (overlap) {
         const int hint = slab_field_hint(h);
-        s.tile_sel = 1;
-        { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1); }
+        { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1, {1, books}); }
         { ProfScope p(h, SPH_K_HALO); h->L->halo_push_fields(s, 2, nullptr, nullptr, hint); }
-        s.tile_sel = 2;
-        { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1); }
-        s.tile_sel = 0;
+        { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1, {2, books}); }
         { ProfScope p(h, SPH_K_HALO); h->L->halo_pull_fields(s, 2, nullptr, nullptr, hint); }
     } else if (s.slab_active && s.push.on) {
         // ghost rho, p: the density pass stores the values of its boundary particles straight into the neighbours' field message
         // (HaloFieldSend) -- no gather kernel, and the message travels while the pass is still running; then the usual wait + scatter
         const int hint = slab_field_hint(h);
         h->L->halo_fieldsend_begin(s);
-        { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1); }               // :29 + :33 (EOS fused)
+        { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1, {0, books}); }   // :29 + :33 (EOS fused)
         { ProfScope p(h, SPH_K_HALO); h->L->halo_pull_fields(s, 2, nullptr, nullptr, hint); }
     } else {
-        { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1); }               // :29 + :33 (EOS fused)
+        { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1, {0, books}); }   // :29 + :33 (EOS fused)
         if (s.slab_active) { int rc = slab_exchange_fields(h); if (rc) return rc; }   // ghost rho, p
     }
     if (fused) {
@@ -231,9 +227,9 @@ static int wcsph_step(SphHandle *h) {
             h->L->halo_presend_begin(s);
         // Unsharded, all fluid, another step of this call queued right behind (nothing can touch the particles in between): the force pass
         // hashes the positions it stores for the next step's sort (NextHash) -- one launch less per step.
-        s.nexthash.on = (!s.slab_active && s.c.all_fluid && h->steps_to_follow > 0 && !s.has_emitter && !h->any_rigid_object &&
-                         !h->sort_dirty) ? 1 : 0;
-        ProfScope p(h, SPH_K_WCSPH_FORCES); h->L->wcsph_forces(s);            // :30-31 + :34-36, :45 in one neighbour walk
+        const bool hash_next = !s.slab_active && s.c.all_fluid && h->steps_to_follow > 0 && !s.has_emitter && !h->any_rigid_object &&
+                               !h->sort_dirty;
+        ProfScope p(h, SPH_K_WCSPH_FORCES); h->L->wcsph_forces(s, {books, hash_next});   // :30-31 + :34-36, :45 in one neighbour walk
         return SPH_OK;
     }
     int rc = run_non_pressure(h); if (rc) return rc;                          // :30-31
@@ -303,9 +299,9 @@ static int dfsph_step_begin(SphHandle *h) {
     if (s.slab_active) { rc = slab_exchange_vel(h); if (rc) return rc; }      // the density solver reads v_j of the ghosts
     rc = dfsph_density(h); if (rc) return rc;                                 // :301
     // the sort of this step's second half follows at once when the whole step is one call (step_once): the position update hashes for it
-    s.nexthash.on = (h->whole_step && !s.slab_active && s.c.all_fluid && !s.has_emitter && !h->any_rigid_object &&
-                     !h->sort_dirty && !h->pose_dirty) ? 1 : 0;
-    { ProfScope p(h, SPH_K_MISC); h->L->advect_boundary(s); }                 // :303, :311-314 (boundary fused: it only looks at the particle itself)
+    const bool hash_next = h->whole_step && !s.slab_active && s.c.all_fluid && !s.has_emitter && !h->any_rigid_object &&
+                           !h->sort_dirty && !h->pose_dirty;
+    { ProfScope p(h, SPH_K_MISC); h->L->advect_boundary(s, hash_next); }      // :303, :311-314 (boundary fused: it only looks at the particle itself)
     return SPH_OK;
 }
 
@@ -314,7 +310,7 @@ static int dfsph_step_begin(SphHandle *h) {
 static int dfsph_step_end(SphHandle *h) {
     State &s = h->st;
     if (s.slab_active) { int rc = slab_neighbor_search(h); if (rc) return rc; }   // + migration / ghost exchange
-    else { s.sort_skip_rho = s.c.all_fluid; ph_neighbor_search(h); }          // :316 (the density pass below rewrites every rho: the sort need not move it)
+    else ph_neighbor_search(h, true);                                         // :316 (the density pass below rewrites every rho: the sort need not move it)
     ph_rigid_volume(h);
     { ProfScope p(h, SPH_K_DFSPH_DENSITY_ALPHA); h->L->dfsph_density_alpha_div(s); }     // :317-318 + the D rho / Dt of :140
     if (s.slab_active) { int rc = slab_exchange_scalar(h, s.rho.cur()); if (rc) return rc; }   // ghost densities (kappa_j / rho_j, viscosity)
@@ -341,9 +337,9 @@ static int pcisph_refine(SphHandle *h) {
 static int pcisph_step(SphHandle *h) {
     State &s = h->st;
     if (s.slab_active) { int rc = slab_neighbor_search(h); if (rc) return rc; }   // + migration / ghost exchange
-    else { s.sort_skip_rho = s.c.all_fluid; ph_neighbor_search(h); }          // PCISPH.py:166 (:167 below rewrites every rho)
+    else ph_neighbor_search(h, true);                                         // PCISPH.py:166 (:167 below rewrites every rho)
     ph_rigid_volume(h);
-    { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 0); }                   // :167
+    { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 0, {}); }               // :167
     if (s.slab_active) { int rc = slab_exchange_scalar(h, s.rho.cur()); if (rc) return rc; }   // ghost densities (viscosity)
     int rc = run_non_pressure(h); if (rc) return rc;                          // :168 (+ :174, v* kept aside)
     { ProfScope p(h, SPH_K_MISC); h->L->pcisph_init(s); }                     // :169
@@ -375,9 +371,9 @@ static int iisph_refine(SphHandle *h) {
 // boundary (:218-220, :227: the same tail as PCISPH's)
 static int iisph_step(SphHandle *h) {
     State &s = h->st;
-    s.sort_skip_rho = s.c.all_fluid; ph_neighbor_search(h);                  // :204 (:205 below rewrites every rho)
+    ph_neighbor_search(h, true);                                              // :204 (:205 below rewrites every rho)
     ph_rigid_volume(h);
-    { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 0); }                   // :205
+    { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 0, {}); }               // :205
     int rc = run_non_pressure(h); if (rc) return rc;                          // :207-208
     { ProfScope p(h, SPH_K_IISPH_PREPARE); h->L->iisph_prepare(s); }          // :206, :210-213
     rc = iisph_refine(h); if (rc) return rc;                                  // :215
@@ -399,7 +395,7 @@ static void pbf_begin_count(SphHandle *h) {
 static int pbf_step(SphHandle *h) {
     State &s = h->st;
     pbf_begin_count(h);
-    s.sort_skip_rho = 0; ph_neighbor_search(h);                              // :146
+    ph_neighbor_search(h);                                                    // :146 (it carries rho, see above)
     ph_rigid_volume(h);
     int rc = run_non_pressure(h); if (rc) return rc;                          // :147-148
     { ProfScope p(h, SPH_K_PBF_UPDATE); h->L->pbf_predict(s); }               // :149-152
