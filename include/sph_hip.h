@@ -185,7 +185,7 @@ typedef enum {
     SPH_K_HALO = 17, SPH_K_WCSPH_FORCES = 18,
     SPH_K_IISPH_PREPARE = 19, SPH_K_IISPH_DIJ_PJ = 20, SPH_K_IISPH_SUM_I = 21,
     SPH_K_PBF_DENSITY_LAMBDA = 22, SPH_K_PBF_FIX_POSITION = 23, SPH_K_PBF_UPDATE = 24,
-    SPH_K_RIGID_CONTACT = 25, SPH_K_RIGID_INTEGRATE = 26, SPH_K_COUNT_
+    SPH_K_RIGID_CONTACT = 25, SPH_K_RIGID_INTEGRATE = 26, SPH_K_RIGID_CONTACT_SOLVE = 27, SPH_K_COUNT_
 } SphKernelId;
 
 /* --- lifetime -------------------------------------------------------------------------- */
@@ -270,6 +270,30 @@ int sph_set_rigid_body(SphHandle *h, int object_id, double mass, const double *i
                        const double *vel, const double *angvel, const double *com0, const double *points, int npoints);
 int sph_get_rigid_state(SphHandle *h, int object_id, double *com, double *rot9, double *vel, double *angvel);
 int sph_rigid_integrate(SphHandle *h);
+
+/* Device contact solver (opt-in; the host's "device_contact" rigid backend).  The physics of the host's "contact" backend
+   (SPH/rigid_solver/host_rigid_solver.py: contacts_from_table, then ContactSolver.step -- the integrator's velocity half, one contact per
+   non-empty table key of a registered body in ascending (A, B, bin) order, `iterations` sweeps of sequential impulses with restitution,
+   Coulomb friction and rolling resistance, `iterations` sweeps of split impulses, positions) in ONE kernel launch of one workgroup, in
+   float64.  While it is on, that launch takes the place of the integrator's in sph_step / sph_step_async / sph_rigid_integrate: it runs
+   after the contact pass, reads the wrench as the integrator does and the table as sph_get_rigid_contacts returns it, and clears both
+   (as reset = 1 does); it does NOT apply the integrator's extent wall rule -- a body meets the walls through the contact pass (the
+   domain box's particles or the six wall planes).  sph_get_rigid_contact_pairs is left alone.
+   sph_set_rigid_contact_solver stands in for ContactSolver.__init__ and the two attributes the backend sets: restitution, friction,
+   sweeps, beta (the share of the depth the split impulses remove per step), slop (the depth a resting contact keeps) and patch (the
+   rolling-resistance radius), the last two in scene units.  on = 0 returns the launch to the integrator; turning the integrator
+   (sph_set_rigid_integrator) or the contact pass (sph_set_rigid_contact) off turns the solver off too.
+   SPH_ERR_UNSUPPORTED: as sph_set_rigid_integrator (PBF, a sharded handle, an axis order other than "xyz").  SPH_ERR_INVALID: the
+   integrator or the contact pass is off, iterations outside 1..64, a parameter that is negative or not finite.
+   sph_get_rigid_contact_rows: the rows of the last solve (diagnostics, tests); drains the stream first.  It always writes *count (the
+   rows of the last solve) and copies min(count, capacity) rows of SPH_CONTACT_ROW_VALUES doubles:
+     [0] A  [1] B (-1: an infinite-mass partner)  [2..4] point  [5..7] normal (from B towards A)  [8] depth  [9] normal impulse
+     [10..11] friction impulses  [12..13] rolling impulses  [14] split impulse  [15] the table's partner index (20 + bin: box / wall plane)
+   rows may be NULL with capacity 0. */
+#define SPH_CONTACT_ROW_VALUES 16
+int sph_set_rigid_contact_solver(SphHandle *h, int on, double restitution, double friction, int iterations, double beta, double slop,
+                                 double patch);
+int sph_get_rigid_contact_rows(SphHandle *h, double *rows, int capacity, int *count);
 
 /* --- time stepping --------------------------------------------------------------------- */
 /* replaces XSolver.prepare() (base_solver.py:683, DFSPH.py:321, PCISPH.py:188); particles of

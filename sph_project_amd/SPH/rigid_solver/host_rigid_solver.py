@@ -22,11 +22,16 @@ Built-in backends:
     static bodies, the domain box and the wall planes have infinite mass.  No AABB clamp.  Parameters: the optional Configuration keys
     rigidContactRestitution / rigidContactFriction / rigidContactIterations.  Unit-tested (tests/test_contact_host.py).
   * "device" (opt-in, SPH_RIGID_BACKEND=device): the native backend's physics -- the same integrator, the same wall rule, NO body-body
-    contacts, no friction, no contact torque -- run by the device between the two halves of every step (sph_set_rigid_integrator,
+    contacts, no friction, no contact torque (those are "device_contact") -- run by the device between the two halves of every step (sph_set_rigid_integrator,
     csrc/sph_rigid.hpp), so that a scene with dynamic bodies advances in one device call: no wrench read-back, no pose upload, no
     host synchronisation per step.  The float64 state lives on the device; `bodies[oid].com / rot / vel / angvel`,
     get_rigid_body_states() and container.rigid_body_velocities are read back when somebody asks for them.
     Not for PBF (which moves no body) and not for sharded scenes.
+  * "device_contact" (opt-in, SPH_RIGID_BACKEND=device_contact): the contact backend's physics -- the same contacts from the same table,
+    the same sequential-impulse solve, statement by statement -- run by the device between the two halves of every step
+    (sph_set_rigid_contact_solver, csrc/sph_contact_solve.hpp), with the device backend's plumbing: the float64 state on the device, lazy
+    read-back, no wrench read, no table read, no pose upload.  A scene with stacking, colliding, sliding bodies advances in one device
+    call.  Not for PBF and not for sharded scenes.
   * "pybullet": the reference's calls (URDF from the mesh file, applyExternalForce / Torque at the base,
     stepSimulation, base pose read-back) when the package is importable.  It is not installed in this image, so this
     backend has never run here; select it with SPH_RIGID_BACKEND=pybullet.
@@ -133,7 +138,7 @@ class HostRigidSolver:
         # the container's rigid_backend option (run_simulation.py --rigid_backend) first, then SPH_RIGID_BACKEND
         self.backend = getattr(container, "rigid_backend", None) or os.environ.get("SPH_RIGID_BACKEND", "native")
         self._bullet = None
-        self.on_device = False   # the "device" backend is active: the device integrates the bodies, the host only reads them back
+        self.on_device = False   # "device" / "device_contact" is active: the device moves the bodies, the host only reads them back
         self._stale = False
         if not self.rigid_bodies and not self.rigid_blocks:
             print("No rigid body in the scene, skip bullet solver initialization.")
@@ -142,34 +147,42 @@ class HostRigidSolver:
                 self._bullet = _BulletBackend(container, self.gravity, self.dt)
             except ImportError as e:   # asked for explicitly: never fall back silently
                 raise NotImplementedError("SPH_RIGID_BACKEND=pybullet, but pybullet is not importable") from e
-        elif self.backend not in ("native", "contact", "device"):
-            raise ValueError(f"SPH_RIGID_BACKEND={self.backend!r}: expected 'native', 'contact', 'device' or 'pybullet'")
+        elif self.backend not in ("native", "contact", "device", "device_contact"):
+            raise ValueError(f"SPH_RIGID_BACKEND={self.backend!r}: expected 'native', 'contact', 'device', 'device_contact' or 'pybullet'")
         # walls no part of a body may cross (bullet_solver.py:57-61)
         eps = container.padding + container.particle_diameter + container.domain_box_thickness
         self.wall_lo = np.asarray(container.domain_start, dtype=np.float64) + eps
         self.wall_hi = np.asarray(container.domain_end, dtype=np.float64) - eps
-        self.contact = None
+        self.contact = None              # the host's solver ("contact")
+        self.contact_parameters = None   # ... and the ContactSolver that holds its parameters ("contact" and "device_contact")
         dynamic = any(b["isDynamic"] for b in self.rigid_bodies)
-        if self.backend == "contact" and getattr(container, "METHOD", None) == "pbf":
-            print("SPH_RIGID_BACKEND=contact: PBF moves no rigid body (PBF.py _step), contact stays off.")
-        elif self.backend == "contact" and dynamic:   # (static bodies alone: nothing would read the table)
+        pbf = getattr(container, "METHOD", None) == "pbf"
+        if pbf and self.backend in ("contact", "device", "device_contact"):
+            what = {"contact": "contact", "device": "the device integrator", "device_contact": "the device contact solver"}[self.backend]
+            print(f"SPH_RIGID_BACKEND={self.backend}: PBF moves no rigid body (PBF.py _step), {what} stays off.")
+        elif self.backend in ("contact", "device_contact") and dynamic:   # (static bodies alone: nothing would read the table)
             cfg = container.cfg
             get = lambda k, d: d if cfg.get_cfg(k) is None else cfg.get_cfg(k)
-            self.contact = ContactSolver(restitution=float(get("rigidContactRestitution", 0.2)),
-                                         friction=float(get("rigidContactFriction", 0.5)),
-                                         iterations=int(get("rigidContactIterations", 10)),
-                                         gravity=self.gravity, dt=self.dt)
+            solver = ContactSolver(restitution=float(get("rigidContactRestitution", 0.2)),
+                                   friction=float(get("rigidContactFriction", 0.5)),
+                                   iterations=int(get("rigidContactIterations", 10)),
+                                   gravity=self.gravity, dt=self.dt)
             # D: the pitch bodies and box are sampled at; wall planes only where no domain box stands in for them
             self.contact_distance = float(getattr(container, "particle_spacing", container.particle_diameter))
-            self.contact.slop = float(get("rigidContactSlop", CONTACT_SLOP)) * self.contact_distance
-            self.contact.patch = float(get("rigidContactRollingRadius", CONTACT_ROLLING_RADIUS)) * self.contact_distance
+            solver.slop = float(get("rigidContactSlop", CONTACT_SLOP)) * self.contact_distance
+            solver.patch = float(get("rigidContactRollingRadius", CONTACT_ROLLING_RADIUS)) * self.contact_distance
             walls = not getattr(container, "add_domain_box", False)
             container.engine.set_rigid_contact(True, self.contact_distance, self.wall_lo if walls else None,
                                                self.wall_hi if walls else None)
-        if self.backend == "device" and getattr(container, "METHOD", None) == "pbf":
-            print("SPH_RIGID_BACKEND=device: PBF moves no rigid body (PBF.py _step), the device integrator stays off.")
-        elif self.backend == "device" and dynamic:   # (a sharded scene: the library refuses, and the error is the caller's)
+            self.contact_parameters = solver
+            if self.backend == "contact":
+                self.contact = solver   # the host solves
+        if self.backend in ("device", "device_contact") and dynamic and not pbf:
+            # (a sharded scene: the library refuses, and the error is the caller's)
             container.engine.set_rigid_integrator(True, self.gravity, self.wall_lo, self.wall_hi)
+            if self.backend == "device_contact":   # the device solves, with the parameters the host solver would use
+                container.engine.set_rigid_contact_solver(True, solver.e, solver.mu, solver.iterations, solver.beta, solver.slop,
+                                                          solver.patch)
             container.rigid_body_velocities = _DeviceVelocities(np.asarray(container.rigid_body_velocities), self)
             self.on_device = True
 

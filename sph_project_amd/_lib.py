@@ -53,11 +53,14 @@ KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "press
               "pbf_update"]
 K_RIGID_CONTACT = 25   # sph_kernel_name(25) == "rigid_contact" (KERNEL_IDS keeps its PBF tail)
 K_RIGID_INTEGRATE = 26   # sph_kernel_name(26) == "rigid_integrate": the device rigid backend's launch
+K_RIGID_CONTACT_SOLVE = 27   # sph_kernel_name(27) == "rigid_contact_solve": the device_contact rigid backend's launch
 
 # rigid contact table (sph_get_rigid_contacts): [object A][partner B][normal bin][value]; partners 20..25 are the domain box /
 # the wall planes, one per bin; values: pairs, midpoint sum (3), depth * n sum (3), maximum depth
 CONTACT_PARTNERS, CONTACT_BINS, CONTACT_VALUES = 26, 6, 8
 CONTACT_WALL0 = 20
+# one row of sph_get_rigid_contact_rows: A, B (-1: infinite mass), point (3), normal (3), depth, ln, lt (2), lr (2), lp, table partner
+CONTACT_ROW_VALUES = 16
 
 
 class SphParams(C.Structure):
@@ -196,6 +199,9 @@ _SIGNATURES = [
     ("sph_set_rigid_body", C.c_int, [_VP, C.c_int, C.c_double] + [_VP] * 7 + [C.c_int]),        # :75-131 insert_rigid_object
     ("sph_get_rigid_state", C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP]),                        # :158-176 pose read-back
     ("sph_rigid_integrate", C.c_int, [_VP]),                                                     # :144-167 step
+    # device contact solver: ContactSolver.__init__ + slop / patch, and the rows of the last solve
+    ("sph_set_rigid_contact_solver", C.c_int, [_VP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double]),
+    ("sph_get_rigid_contact_rows", C.c_int, [_VP, _VP, C.c_int, _VP]),
     ("sph_prepare", C.c_int, [_VP]),
     ("sph_step", C.c_int, [_VP, C.c_int]),
     ("sph_step_async", C.c_int, [_VP, C.c_int]),
@@ -404,6 +410,24 @@ class Engine(NativeObject):
 
     def rigid_integrate(self):
         self._chk(self.lib.sph_rigid_integrate(self.h), "sph_rigid_integrate")
+
+    # -- device contact solver (the "device_contact" rigid backend)
+    def set_rigid_contact_solver(self, on=True, restitution=0.2, friction=0.5, iterations=10, beta=0.2, slop=0.0, patch=0.0):
+        self._chk(self.lib.sph_set_rigid_contact_solver(self.h, int(bool(on)), float(restitution), float(friction), int(iterations),
+                                                        float(beta), float(slop), float(patch)), "sph_set_rigid_contact_solver")
+
+    def get_rigid_contact_row_count(self):
+        n = C.c_int(0)
+        self._chk(self.lib.sph_get_rigid_contact_rows(self.h, None, 0, C.byref(n)), "sph_get_rigid_contact_rows")
+        return n.value
+
+    def get_rigid_contact_rows(self):
+        """The rows of the last solve, (n, CONTACT_ROW_VALUES) float64; drains the stream."""
+        rows = np.zeros((self.get_rigid_contact_row_count(), CONTACT_ROW_VALUES), np.float64)
+        n = C.c_int(0)
+        self._chk(self.lib.sph_get_rigid_contact_rows(self.h, _ptr(rows) if len(rows) else None, len(rows), C.byref(n)),
+                  "sph_get_rigid_contact_rows")
+        return rows
 
     # -- stepping
     def prepare(self):

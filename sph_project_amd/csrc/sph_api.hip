@@ -211,7 +211,7 @@ extern "C" const char *sph_kernel_name(int k) {
         "dfsph_density_alpha", "dfsph_rho_adv", "dfsph_correct", "reduce", "pcisph_rho_star",
         "pcisph_pressure_accel", "cg_prepare", "cg_ap", "cg_vector", "misc", "halo", "wcsph_forces",
         "iisph_prepare", "iisph_dij_pj", "iisph_sum_i", "pbf_density_lambda", "pbf_fix_position", "pbf_update",
-        "rigid_contact", "rigid_integrate"};
+        "rigid_contact", "rigid_integrate", "rigid_contact_solve"};
     return (k >= 0 && k < SPH_K_COUNT_) ? names[k] : "?";
 }
 
@@ -514,7 +514,7 @@ extern "C" int sph_set_rigid_contact(SphHandle *h, int on, float distance, const
     if (!h) return SPH_ERR_INVALID;
     if (h->prm.method == SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "set_rigid_contact: PBF moves no rigid body (PBF.py _step)");
     State &s = h->st;
-    if (!on) { s.contact_on = 0; return SPH_OK; }
+    if (!on) { s.contact_on = 0; s.contact_solve_on = 0; return SPH_OK; }   // (the solver reads the table this pass fills)
     if (!(distance > 0.0f) || distance > s.c.grid_size)
         return fail(h, SPH_ERR_INVALID, "set_rigid_contact: distance %g outside (0, cell size %g]", (double)distance, (double)s.c.grid_size);
     if (!wall_lo != !wall_hi) return fail(h, SPH_ERR_INVALID, "set_rigid_contact: give both wall planes or neither");
@@ -553,7 +553,7 @@ static void rigid_int_list(SphHandle *h) {
 
 extern "C" int sph_set_rigid_integrator(SphHandle *h, int on, const double *gravity, const double *wall_lo, const double *wall_hi) {
     if (!h) return SPH_ERR_INVALID;
-    if (!on) { h->st.rigid_int_on = 0; return SPH_OK; }
+    if (!on) { h->st.rigid_int_on = 0; h->st.contact_solve_on = 0; return SPH_OK; }   // (the solver is the integrator's launch)
     { int rc = rigid_int_supported(h, "set_rigid_integrator"); if (rc) return rc; }
     if (!gravity || !wall_lo || !wall_hi) return fail(h, SPH_ERR_INVALID, "set_rigid_integrator: null argument");
     RigidIntArgs &a = h->st.rigid_int;
@@ -618,6 +618,50 @@ extern "C" int sph_get_rigid_state(SphHandle *h, int o, double *com, double *rot
     HIPCHK(h, hipStreamSynchronize(h->st.stream));
     for (int k = 0; k < 3; ++k) { if (com) com[k] = b.com[k]; if (vel) vel[k] = b.vel[k]; if (angvel) angvel[k] = b.angvel[k]; }
     if (rot9) for (int q = 0; q < 9; ++q) rot9[q] = b.rot[q];
+    return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------- device contact solver (sph_contact_solve.hpp)
+extern "C" int sph_set_rigid_contact_solver(SphHandle *h, int on, double restitution, double friction, int iterations, double beta,
+                                            double slop, double patch) {
+    if (!h) return SPH_ERR_INVALID;
+    State &s = h->st;
+    if (!on) { s.contact_solve_on = 0; return SPH_OK; }
+    { int rc = rigid_int_supported(h, "set_rigid_contact_solver"); if (rc) return rc; }
+    if (!s.rigid_int_on) return fail(h, SPH_ERR_INVALID, "set_rigid_contact_solver: sph_set_rigid_integrator is off");
+    if (!s.contact_on) return fail(h, SPH_ERR_INVALID, "set_rigid_contact_solver: sph_set_rigid_contact is off");
+    if (iterations < 1 || iterations > 64) return fail(h, SPH_ERR_INVALID, "set_rigid_contact_solver: %d iterations outside 1..64", iterations);
+    const double prm[5] = {restitution, friction, beta, slop, patch};
+    for (double v : prm)
+        if (!std::isfinite(v) || v < 0.0) return fail(h, SPH_ERR_INVALID, "set_rigid_contact_solver: parameter %g is negative or not finite", v);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!s.contact_rows) {
+        int rc = dalloc(h, &s.contact_rows, (size_t)SPH_CT_KEYS * SPH_CS_ROW); if (rc) return rc;
+        rc = dalloc(h, &s.contact_nrows, 1); if (rc) return rc;
+    }
+    s.contact_solve = ContactSolveArgs{restitution, friction, beta, slop, patch, iterations};
+    s.contact_solve_on = 1;
+    return SPH_OK;
+}
+
+extern "C" int sph_get_rigid_contact_rows(SphHandle *h, double *rows, int capacity, int *count) {
+    if (count) *count = 0;
+    if (!h || !count || capacity < 0 || (capacity > 0 && !rows)) return fail(h, SPH_ERR_INVALID, "get_rigid_contact_rows: bad argument");
+    State &s = h->st;
+    if (!s.contact_rows) return fail(h, SPH_ERR_INVALID, "get_rigid_contact_rows: sph_set_rigid_contact_solver was never enabled");
+    HIPCHK(h, hipSetDevice(h->device));
+    int n = 0;
+    HIPCHK(h, hipMemcpyAsync(&n, s.contact_nrows, sizeof(int), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(h, hipStreamSynchronize(s.stream));
+    if (n < 0 || n > SPH_CT_KEYS) return fail(h, SPH_ERR_INVALID, "get_rigid_contact_rows: row count %d outside the table", n);
+    *count = n;
+    const int m = std::min(n, capacity);
+    if (m == 0) return SPH_OK;
+    std::vector<double> dev((size_t)m * SPH_CS_ROW);
+    HIPCHK(h, hipMemcpyAsync(dev.data(), s.contact_rows, dev.size() * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(h, hipStreamSynchronize(s.stream));
+    for (int r = 0; r < m; ++r)
+        memcpy(rows + (size_t)r * SPH_CONTACT_ROW_VALUES, dev.data() + (size_t)r * SPH_CS_ROW, sizeof(double) * SPH_CONTACT_ROW_VALUES);
     return SPH_OK;
 }
 
@@ -924,7 +968,9 @@ extern "C" int sph_prepare(SphHandle *h) {
 // the rigid step of the device backend (bullet_solver.py:144-167 without the host): wrench -> state -> pose, between the halves of a step
 static void ph_rigid_integrate(SphHandle *h) {
     if (!h->st.rigid_int_on || h->st.rigid_int.nbodies <= 0) return;
-    { ProfScope p(h, SPH_K_RIGID_INTEGRATE); h->L->rigid_integrate(h->st); }
+    // with the contact solver on, its launch takes the integrator's place: the table of this step's contact pass is its input
+    if (h->st.contact_solve_on) { ProfScope p(h, SPH_K_RIGID_CONTACT_SOLVE); h->L->rigid_contact_solve(h->st); }
+    else { ProfScope p(h, SPH_K_RIGID_INTEGRATE); h->L->rigid_integrate(h->st); }
     h->pose_dirty = true;
     h->rb_pose_stale = true;
 }

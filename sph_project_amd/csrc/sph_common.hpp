@@ -194,6 +194,11 @@ struct RigidBodyDev {
     int npoints, registered;
 };
 struct RigidIntArgs { double g[3], lo[3], hi[3], dt; int nbodies; int ids[SPH_NOBJ]; };
+// Device contact solver (sph_contact_solve.hpp, the host's "device_contact" rigid backend): ContactSolver's parameters -- restitution,
+// friction, sweeps, the split impulses' share of the depth, the depth a resting contact keeps, the rolling-resistance radius
+struct ContactSolveArgs { double e, mu, beta, slop, patch; int iterations; };
+// one row of the solve, in doubles (layout: sph_contact_solve.hpp); its first SPH_CONTACT_ROW_VALUES are sph_get_rigid_contact_rows'
+#define SPH_CS_ROW 36
 
 // Surface reconstruction (sph_surface.hpp): the constants and device buffers of one SphSurface.  Coarse cells (= bricks of
 // B^3 grid points) are counted from the absolute coarse coordinate cmin[] on a grid of cn[] cells that keeps one empty cell around the
@@ -371,6 +376,12 @@ struct State {
     int rigid_int_on = 0;
     RigidIntArgs rigid_int = {};
     RigidBodyDev *rigid_bodies = nullptr;   // [SPH_NOBJ]
+    // device contact solver (sph_set_rigid_contact_solver; allocated when first enabled): the rows of the last solve, one per table key at
+    // most (sph_contact_solve.hpp), and their number
+    int contact_solve_on = 0;
+    ContactSolveArgs contact_solve = {};
+    double *contact_rows = nullptr;
+    int *contact_nrows = nullptr;
     // CG (implicit viscosity)
     float4 *cg_p = nullptr, *cg_Ap = nullptr, *cg_x = nullptr, *cg_b = nullptr, *cg_r = nullptr, *cg_v0 = nullptr;
     float4 *cg_p2 = nullptr;   // second search-direction buffer (fused p update: the A p pass reads the old one and writes the new one)
@@ -506,6 +517,8 @@ struct Launch {
     void (*rigid_contact)(State &);
     // device rigid integrator: one workgroup per registered body (sph_rigid.hpp)
     void (*rigid_integrate)(State &);
+    // device contact solver: one workgroup for the whole body system, in place of rigid_integrate (sph_contact_solve.hpp)
+    void (*rigid_contact_solve)(State &);
     // z-slab sharding
     void (*halo_classify_pack)(State &, int n);
     void (*halo_unpack_append)(State &, int side, int count, int offset);

@@ -1,6 +1,6 @@
 // sph_kernels.hip -- kernel instantiations + launchers.  Compiled twice:
 //   -DSPH_FAST=0 -ffp-contract=off   -> sph_launch_strict()  (IEEE div/sqrt, no FMA contraction)
-//   -DSPH_FAST=1 -ffp-contract=fast  -> sph_launch_fast()    (v_rcp_f32 / v_sqrt_f32, FMA)
+//   -DSPH_FAST=1 -ffp-contract=fast-honor-pragmas  -> sph_launch_fast()    (v_rcp_f32 / v_sqrt_f32, FMA except under `fp contract(off)`)
 #include "sph_common.hpp"
 
 #if SPH_FAST
@@ -460,6 +460,7 @@ void l_clear_fresh(State &s) {
 #include "sph_pbf.hpp"
 #include "sph_contact.hpp"
 #include "sph_rigid.hpp"
+#include "sph_contact_solve.hpp"
 #include "sph_surface.hpp"
 #include "sph_surface_post.hpp"
 #include "sph_render.hpp"
@@ -491,6 +492,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_pbf_launchers(L);
         register_contact_launchers(L);
         register_rigid_launchers(L);
+        register_contact_solve_launchers(L);
         register_surface_launchers(L);
         register_surface_post_launchers(L);
         register_render_launchers(L);

@@ -73,9 +73,9 @@ def parse_args(argv=None):
     parser.add_argument("--scene_file", default="", help="scene file")
     parser.add_argument("--max_steps", type=int, default=None, help="stop early (not in the reference)")
     parser.add_argument("--output_dir", default=None, help="default: {scene_name}_output in the cwd (reference behaviour)")
-    parser.add_argument("--rigid_backend", default=None, choices=["native", "contact", "device", "pybullet"],
+    parser.add_argument("--rigid_backend", default=None, choices=["native", "contact", "device", "device_contact", "pybullet"],
                         help="rigid-body backend (default: SPH_RIGID_BACKEND, else native); 'contact' adds body-body contact, "
-                             "'device' runs the native integrator on the GPU")
+                             "'device' runs the native integrator on the GPU, 'device_contact' the contact solve as well")
     parser.add_argument("--reconstruct", action="store_true",
                         help="with every PLY frame also write particle_object_{id}.obj: the fluid object's surface, reconstructed on the "
                              "GPU from the device state (surface_reconstruction.py's defaults; not in the reference)")
