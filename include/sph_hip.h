@@ -664,6 +664,61 @@ int sph_video_size(SphVideo *v, int64_t *bytes);
 int sph_video_download(SphVideo *v, uint8_t *dst);
 int sph_video_stats(SphVideo *v, SphVideoStats *out);
 
+/* --- PNG encoding: RGB frames -> lossless .png files, the frames an exporting run stores -------------------------- */
+/* stands in for the host's zlib pass over a downloaded frame: the file is made on the device the frame was rendered on.  One frame is
+   one complete .png file: 8-bit RGB (colour type 2), not interlaced; signature, IHDR, one IDAT chunk per segment of 4096 filtered
+   bytes, one IDAT chunk with the Adler-32, IEND.  The IDAT payloads are one zlib stream (header 78 01): per segment either one block
+   in the fixed Huffman code, closed by an empty stored block that brings the next segment to a byte boundary, or one stored block,
+   whichever is shorter (ties: fixed).  Tokens come from a fixed rule (candidate distances 1, 2, 3, 4, 6 inside the segment, longest
+   match first, then the smallest distance, greedy from the segment's start), row filters from the least sum of |residual as int8|
+   (ties: the lowest type) or one fixed type.  All of it is integer arithmetic, so the bytes are a function of (pixels, width, height,
+   filter): the same from both builds and from every call.  The device filters, matches, parses, codes, packs and computes the
+   Adler-32 and every IDAT chunk's CRC-32, and writes the IDAT chunks whole; the host writes the signature, IHDR and IEND and never
+   reads the payload.  The output is sized from a counting pass: a file is never truncated, and never longer than sph_png_bound.
+   One HIP stream per object; synchronous calls.  `fast_math` selects the build whose launchers run, as in the video object. */
+typedef struct {
+    int32_t width, height;   /* pixels; each 1..16384, width * height <= 2^26 */
+    int32_t filter;          /* -1: adaptive (per row), 0..4: that PNG filter type on every row */
+    int32_t fast_math;       /* which build's launchers run (0 strict, 1 fast); the bytes are the same */
+    int32_t device;          /* HIP device ordinal, -1: current */
+    int32_t reserved;        /* 0 */
+} SphPngParams;
+
+typedef struct {
+    int64_t raw_bytes;         /* the filtered stream: height * (1 + 3 * width) */
+    int64_t zlib_bytes;        /* the zlib stream: header, blocks, Adler-32 */
+    int64_t file_bytes;        /* the .png file */
+    int64_t segments;
+    int64_t stored_segments;   /* segments written as a stored block because the fixed code would have been longer */
+    int64_t literals;          /* tokens of the segments written in the fixed code */
+    int64_t matches;
+    int64_t filter_rows[5];    /* rows per filter type */
+    double ms_input;           /* HIP events: upload of a host image (~0 for a renderer's frame) */
+    double ms_filter;          /* row filters */
+    double ms_count;           /* first pass: bytes per segment, Adler sums */
+    double ms_scan;            /* their scan, the Adler-32, the total read by the host */
+    double ms_write;           /* second pass: the chunks and their CRCs */
+    double ms_total;
+} SphPngStats;
+
+typedef struct SphPng SphPng;
+/* SPH_ERR_INVALID (before any device is touched): a size or filter outside the ranges above, reserved != 0 */
+int sph_png_create(const SphPngParams *params, SphPng **out);
+void sph_png_destroy(SphPng *v);
+const char *sph_png_last_error(SphPng *v);
+/* the longest file these parameters can give: 8 + 25 + 17 * segments + raw_bytes + 2 + 16 + 12 with segments =
+   ceil(raw_bytes / 4096).  Host only: no device is touched. */
+int sph_png_bound(const SphPngParams *params, int64_t *bytes);
+/* a host image u8[height][width][3], rows from the top */
+int sph_png_encode_rgb(SphPng *v, const uint8_t *rgb);
+/* the renderer's last frame (particles or meshes), read from its device buffer: not downloaded, nothing of the renderer modified.
+   SPH_ERR_INVALID with a message: no frame rendered yet, a frame of another size, a renderer on another device. */
+int sph_png_encode_render(SphPng *v, SphRender *r);
+/* the last encoded frame: the length of the complete .png file, and the file */
+int sph_png_size(SphPng *v, int64_t *bytes);
+int sph_png_download(SphPng *v, uint8_t *dst);
+int sph_png_stats(SphPng *v, SphPngStats *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,22 @@ class SphVideoStats(C.Structure):
     ]
 
 
+class SphPngParams(C.Structure):
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("filter", C.c_int32), ("fast_math", C.c_int32), ("device", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class SphPngStats(C.Structure):
+    _fields_ = [
+        ("raw_bytes", C.c_int64), ("zlib_bytes", C.c_int64), ("file_bytes", C.c_int64), ("segments", C.c_int64),
+        ("stored_segments", C.c_int64), ("literals", C.c_int64), ("matches", C.c_int64), ("filter_rows", C.c_int64 * 5),
+        ("ms_input", C.c_double), ("ms_filter", C.c_double), ("ms_count", C.c_double), ("ms_scan", C.c_double), ("ms_write", C.c_double),
+        ("ms_total", C.c_double),
+    ]
+
+
 # return codes (include/sph_hip.h)
 ERR_INVALID, ERR_CAPACITY = -1, -2
 ERR_UNSUPPORTED = -6
@@ -265,6 +281,15 @@ _SIGNATURES = [
     ("sph_video_size", C.c_int, [_VP, C.POINTER(C.c_int64)]),
     ("sph_video_download", C.c_int, [_VP, _VP]),
     ("sph_video_stats", C.c_int, [_VP, C.POINTER(SphVideoStats)]),
+    ("sph_png_create", C.c_int, [C.POINTER(SphPngParams), C.POINTER(_VP)]),
+    ("sph_png_destroy", None, [_VP]),
+    ("sph_png_last_error", C.c_char_p, [_VP]),
+    ("sph_png_bound", C.c_int, [C.POINTER(SphPngParams), C.POINTER(C.c_int64)]),
+    ("sph_png_encode_rgb", C.c_int, [_VP, _VP]),
+    ("sph_png_encode_render", C.c_int, [_VP, _VP]),
+    ("sph_png_size", C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    ("sph_png_download", C.c_int, [_VP, _VP]),
+    ("sph_png_stats", C.c_int, [_VP, C.POINTER(SphPngStats)]),
     ("sph_comm_allreduce", C.c_int, [_VP, C.POINTER(C.c_double), C.c_int, C.c_int]),
     ("sph_comm_barrier", C.c_int, [_VP]),
     ("sph_comm_selftest", C.c_int, [_VP, C.c_int]),

@@ -1371,3 +1371,4 @@ extern "C" int sph_points_in_mesh(const double *vertices, int n_vertices, const 
 #include "sph_surface_api.hpp"
 #include "sph_render_api.hpp"
 #include "sph_video_api.hpp"
+#include "sph_png_api.hpp"

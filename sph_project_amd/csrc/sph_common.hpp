@@ -299,6 +299,38 @@ struct VideoDev {
     hipStream_t stream;
 };
 
+// PNG encoding (sph_png.hpp): one frame -> the IDAT chunks of a PNG file.  The filtered stream (H rows of 1 + 3 W bytes) is
+// cut into segments of PNG_SEG raw bytes, the work of one workgroup and one IDAT chunk each; PNG_DIST are the candidate match distances.
+// cnt: [0..4] rows per filter type, [5] stored segments, [6] literals, [7] matches (the tokens of the segments coded with the fixed code).
+#define PNG_SEG 4096
+#define PNG_ND 5
+#define PNG_DIST_LIST {1, 2, 3, 4, 6}
+#define PNG_CRC_PIECE 17               // bytes per thread of a chunk's CRC: 256 pieces cover tag + prefix + stored header + PNG_SEG bytes
+static_assert(256 * PNG_CRC_PIECE >= 4 + 2 + 5 + PNG_SEG, "the CRC pieces cover the longest chunk");
+#define PNG_CRC_POLY 0xEDB88320u
+// a b mod the CRC-32 polynomial, bit-reflected as the CRC register is: bit 31 is x^0
+__host__ __device__ static inline unsigned png_crc_mul(unsigned a, unsigned b) {
+    unsigned p = 0u;
+    for (int k = 0; k < 32; ++k) {
+        if (a & (0x80000000u >> k)) p ^= b;
+        b = (b >> 1) ^ (PNG_CRC_POLY & (0u - (b & 1u)));
+    }
+    return p;
+}
+struct PngDev {
+    int W, H, filter;                  // filter: -1 adaptive, 0..4 that type on every row
+    int stride, raw, nseg;             // 1 + 3 W; H stride; segments
+    const unsigned char *rgb;          // [H][W][3] the frame (the encoder's upload or a renderer's frame buffer)
+    unsigned char *flt;                // [raw] the filtered stream
+    int *len;                          // [nseg + 1] bytes per segment's chunk (length, tag, payload, CRC) -> their exclusive scan, [nseg] the total
+    unsigned *adler;                   // [2 nseg] per segment: sum of its bytes, sum of (bytes to its end) x byte, both mod 65521
+    unsigned long long *cnt;           // [8] see above
+    unsigned *sum;                     // [1] the Adler-32 of the filtered stream (scan pass)
+    unsigned crc_pow[8];               // x^(8 PNG_CRC_PIECE 2^j) mod the polynomial: joins two runs of 2^j pieces
+    unsigned char *out;                // the chunks, then the Adler-32's own IDAT chunk
+    hipStream_t stream;
+};
+
 template <class T> struct DBuf {
     T *b[2] = {nullptr, nullptr};
     int c = 0;
@@ -556,6 +588,11 @@ struct Launch {
     void (*video_count)(VideoDev &);            // bytes per restart interval (transform, symbols, stuffing; nothing stored but the counts)
     void (*video_scan)(VideoDev &);             // their exclusive scan, the total behind it
     void (*video_write)(VideoDev &);            // the same bytes again, stored at the scanned offsets
+    // PNG encoding (sph_png.hpp)
+    void (*png_filter)(PngDev &);               // the filtered stream: one row filter per row, by the least sum of |residual|
+    void (*png_count)(PngDev &);                // bytes per segment's chunk (tokens, fixed or stored), the Adler sums
+    void (*png_scan)(PngDev &);                 // their exclusive scan, the total behind it; the Adler-32
+    void (*png_write)(PngDev &);                // the same bytes again, stored at the scanned offsets, with every chunk's CRC
     void (*layer_hist)(State &, int *hist);      // owned particles per global cell layer
     void (*loop_criterion)(State &, int slot);   // stop test on an all-reduced residual (sharded solver loops)
     // push transport: the step message is written by halo_classify_pack itself; then

@@ -1,0 +1,403 @@
+// sph_png.hpp -- PNG encoding (one RGB frame on the device -> the IDAT chunks of a PNG file): kernels and launchers; included by
+// sph_kernels.hip inside the per-build namespace.  The stream is defined in DESIGN.md 21, the entry points in include/sph_hip.h
+// (sph_png_create), the restatement in tests/png_model.py.  Integer arithmetic only: the strict and the fast build write the same bytes.
+//
+// k_png_filter    one workgroup per row: the five costs (sum of |residual as int8|), the winner (ties: the lowest type), the filtered row
+// k_png_segment   one workgroup (4 waves) per segment of PNG_SEG filtered bytes, held in LDS; thread t owns positions [16 t, 16 t + 16):
+//   matches   per candidate distance a 16-bit mask of byte equalities; the run that starts at a position is the mask's trailing ones,
+//             continued through the following threads' masks (their leading runs lie in LDS; at most 258 / 16 + 1 of them are read)
+//   parse     next[i] = i + max(1, length[i]) is a chain from position 0.  Pointer doubling: in round r every marked position marks
+//             next_r[i], then next_{r+1}[i] = next_r[next_r[i]]; the marked set doubles (the first 2^r tokens -> the first 2^(r+1)),
+//             every lane works in every round, and the loop ends when 2^r hops from position 0 leave the segment
+//   layout    the marked positions' bit counts scanned over the workgroup: fixed-code bytes against stored bytes, the shorter wins
+//   bytes     (WRITE) every marked position ORs its bits into the segment's LDS image (deflate packs from bit 0: a little-endian word
+//             image is the byte stream), the chunk goes to its scanned offset, and its CRC-32 is 256 pieces of PNG_CRC_PIECE bytes joined
+//             by multiplication with x^(8 n) mod the polynomial (the message is right-aligned in the pieces: leading zeros leave a
+//             zero register unchanged, so every join of a level uses one constant)
+// The kernel runs twice per frame as the video encoder's does: COUNT leaves the chunk's byte count and the Adler sums, k_png_scan scans
+// the counts (the host sizes the output from the total) and joins the Adler sums, WRITE computes the same bytes again and stores them.
+#pragma once
+
+#define PNG_PER (PNG_SEG / 256)                // positions per thread
+#define PNG_IMG_WORDS (PNG_SEG / 2 + 8)        // next[PNG_SEG + 1] as 16-bit values, later the bit image (<= 2 + 5 + PNG_SEG bytes + 2 words)
+static_assert(PNG_PER == 16, "a thread's byte equalities are one 16-bit mask");
+static_assert(PNG_SEG < 65535, "positions fit 16 bits, a segment fits one stored block");
+static_assert(PNG_IMG_WORDS * 4 >= (PNG_SEG + 1) * 2 && PNG_IMG_WORDS * 4 >= 2 + 5 + PNG_SEG + 8, "the image array holds both of its uses");
+
+static __device__ const int PNG_DIST[PNG_ND] = PNG_DIST_LIST;
+
+__device__ __forceinline__ int png_abs8(int r) { return r < 128 ? r : 256 - r; }
+
+// the residual of filter type t: x the byte, a the byte of the pixel to the left, b above, c above left
+__device__ __forceinline__ int png_residual(int t, int x, int a, int b, int c) {
+    int pred = 0;
+    if (t == 1) pred = a;
+    else if (t == 2) pred = b;
+    else if (t == 3) pred = (a + b) >> 1;
+    else if (t == 4) {
+        const int p = a + b - c;
+        const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+        pred = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+    }
+    return (x - pred) & 255;
+}
+
+__global__ void __launch_bounds__(256) k_png_filter(PngDev d) {
+    __shared__ int s_cost[4][5];
+    __shared__ int s_type;
+    const int tid = threadIdx.x, y = blockIdx.x, n = 3 * d.W;
+    const unsigned char *cur = d.rgb + (size_t)y * n;
+    const unsigned char *up = y ? cur - n : nullptr;   // row 0 sees a zero row above it
+    int type = d.filter;
+    if (type < 0) {   // (workgroup-uniform)
+        int cost[5] = {0, 0, 0, 0, 0};   // <= 3 x 16384 x 128: an int
+        for (int j = tid; j < n; j += 256) {
+            const int x = cur[j], a = j >= 3 ? cur[j - 3] : 0, b = up ? up[j] : 0, c = (up && j >= 3) ? up[j - 3] : 0;
+#pragma unroll
+            for (int t = 0; t < 5; ++t) cost[t] += png_abs8(png_residual(t, x, a, b, c));
+        }
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            const int v = video_wave_sum(cost[t]);
+            if ((tid & 63) == 0) s_cost[tid >> 6][t] = v;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int best = 0, bc = 0;
+            for (int t = 0; t < 5; ++t) {
+                const int v = s_cost[0][t] + s_cost[1][t] + s_cost[2][t] + s_cost[3][t];
+                if (t == 0 || v < bc) { best = t; bc = v; }
+            }
+            s_type = best;
+        }
+        __syncthreads();
+        type = s_type;
+    }
+    unsigned char *o = d.flt + (size_t)y * d.stride;
+    if (tid == 0) { o[0] = (unsigned char)type; atomicAdd(&d.cnt[type], 1ull); }
+    for (int j = tid; j < n; j += 256) {
+        const int x = cur[j], a = j >= 3 ? cur[j - 3] : 0, b = up ? up[j] : 0, c = (up && j >= 3) ? up[j - 3] : 0;
+        o[1 + j] = (unsigned char)png_residual(type, x, a, b, c);
+    }
+}
+
+// a Huffman code enters the stream most significant bit first: the n-bit code reversed
+__device__ __forceinline__ unsigned png_rev(unsigned v, int n) { return __brev(v) >> (32 - n); }
+
+// the bits of a literal / of a match in the fixed code (RFC 1951 3.2.5, 3.2.6), in stream order from bit 0 of val
+__device__ __forceinline__ void png_literal(unsigned b, unsigned &val, int &nb) {
+    if (b < 144u) { val = png_rev(0x30u + b, 8); nb = 8; }
+    else { val = png_rev(0x190u + b - 144u, 9); nb = 9; }
+}
+__device__ __forceinline__ void png_match(int len, int dist, unsigned &val, int &nb) {
+    const int l = len - 3;
+    int sym, eb = 0;
+    unsigned ev = 0u;
+    if (len == 258) sym = 285;
+    else if (l < 8) sym = 257 + l;
+    else { eb = 29 - __clz(l); sym = 257 + 4 * eb + (l >> eb); ev = (unsigned)l & ((1u << eb) - 1u); }   // groups of four codes per extra bit
+    if (sym < 280) { val = png_rev((unsigned)sym - 256u, 7); nb = 7; }
+    else { val = png_rev(0xC0u + (unsigned)sym - 280u, 8); nb = 8; }
+    val |= ev << nb; nb += eb;
+    const int m = dist - 1;
+    int dc = m, db = 0;
+    unsigned dv = 0u;
+    if (m >= 4) { db = 30 - __clz(m); dc = 2 * db + 2 + ((m >> db) & 1); dv = (unsigned)m & ((1u << db) - 1u); }   // pairs of codes per extra bit
+    val |= png_rev((unsigned)dc, 5) << nb; nb += 5;
+    val |= dv << nb; nb += db;   // <= 8 + 5 + 5 + 13 = 31 bits
+}
+
+__device__ __forceinline__ unsigned png_crc_byte(unsigned r, unsigned b) {
+    r ^= b;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r = (r >> 1) ^ (PNG_CRC_POLY & (0u - (r & 1u)));
+    return r;
+}
+
+// what a segment's chunk is made of once the layout is known
+struct PngSeg { int n, pre, fixed, final, body; };   // raw bytes; 2 = the zlib header goes first; fixed code / stored; last segment; payload bytes
+__device__ __forceinline__ unsigned png_payload_byte(const PngSeg &s, const unsigned *img, const unsigned char *raw, int j) {
+    if (s.fixed) return (img[j >> 2] >> (8 * (j & 3))) & 255u;
+    if (j < s.pre) return j == 0 ? 0x78u : 0x01u;
+    j -= s.pre;
+    const unsigned n = (unsigned)s.n;
+    if (j == 0) return (unsigned)s.final;   // BFINAL, BTYPE 00, the rest of the byte skipped
+    if (j == 1) return n & 255u;
+    if (j == 2) return n >> 8;
+    if (j == 3) return ~n & 255u;
+    if (j == 4) return (~n >> 8) & 255u;
+    return raw[j - 5];
+}
+
+template <bool WRITE>
+__global__ void __launch_bounds__(256) k_png_segment(PngDev d) {
+    __shared__ unsigned s_raw[PNG_SEG / 4];
+    __shared__ unsigned short s_tok[PNG_SEG];          // per position: match length | index of its distance << 9 (0: a literal)
+    __shared__ unsigned s_img[PNG_IMG_WORDS];
+    __shared__ unsigned char s_mark[PNG_SEG + 4];      // 1: a token starts here ([n]: the chain's end, written and never read)
+    __shared__ unsigned short s_lead[PNG_ND][256];     // per thread and distance: the leading run of its mask | 0x8000 when that is all of it
+    __shared__ unsigned s_red[256];
+    __shared__ int s_w[4];
+    __shared__ int s_tokens[2];
+    const int tid = threadIdx.x, seg = blockIdx.x;
+    const int n = min(PNG_SEG, d.raw - seg * PNG_SEG);
+    const unsigned char *src = d.flt + (size_t)seg * PNG_SEG;
+    unsigned char *s_b = (unsigned char *)s_raw;
+    unsigned short *s_next = (unsigned short *)s_img;
+    const int base = tid * PNG_PER;
+
+    for (int w = tid; w < PNG_SEG / 4; w += 256) {   // (the segment starts on a multiple of PNG_SEG in an allocation: aligned words)
+        const int i = 4 * w;
+        unsigned v = 0u;
+        if (i + 3 < n) v = ((const unsigned *)src)[w];
+        else for (int k = 0; k < 4; ++k) if (i + k < n) v |= (unsigned)src[i + k] << (8 * k);
+        s_raw[w] = v;
+    }
+    for (int i = tid; i < PNG_SEG + 4; i += 256) s_mark[i] = i == 0 ? 1 : 0;
+    if (tid < 2) s_tokens[tid] = 0;
+    __syncthreads();
+
+    // the thread's bytes and the eight before them
+    unsigned char c[8 + PNG_PER];
+#pragma unroll
+    for (int k = 0; k < 8 + PNG_PER; ++k) c[k] = base + k >= 8 ? s_b[base + k - 8] : (unsigned char)0;
+
+    if (!WRITE) {   // Adler sums of the segment: a = sum of bytes, b = sum of (n - j) byte[j]; <= 4096 x 4097 / 2 x 255 < 2^32
+        unsigned a = 0u, b = 0u;
+#pragma unroll
+        for (int k = 0; k < PNG_PER; ++k)
+            if (base + k < n) { a += c[8 + k]; b += (unsigned)(n - base - k) * c[8 + k]; }
+        a = (unsigned)video_wave_sum((int)a); b = (unsigned)video_wave_sum((int)b);
+        if ((tid & 63) == 0) { s_red[tid >> 6] = a; s_red[4 + (tid >> 6)] = b; }
+        __syncthreads();
+        if (tid == 0) {
+            d.adler[2 * seg] = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) % 65521u;
+            d.adler[2 * seg + 1] = (s_red[4] + s_red[5] + s_red[6] + s_red[7]) % 65521u;
+        }
+    }
+
+    // byte equalities per distance
+    unsigned m[PNG_ND];
+#pragma unroll
+    for (int q = 0; q < PNG_ND; ++q) {
+        const int dist = PNG_DIST[q];
+        unsigned mk = 0u;
+#pragma unroll
+        for (int k = 0; k < PNG_PER; ++k)
+            if (base + k >= dist && base + k < n && c[8 + k] == c[8 + k - dist]) mk |= 1u << k;   // (nothing before the segment is seen)
+        m[q] = mk;
+        s_lead[q][tid] = mk == 0xFFFFu ? (unsigned short)(0x8000u | PNG_PER) : (unsigned short)__builtin_ctz(~mk);
+    }
+    __syncthreads();
+    int carry[PNG_ND];   // the run that enters the next thread's positions (as far as the longest match needs it)
+#pragma unroll
+    for (int q = 0; q < PNG_ND; ++q) {
+        int r = 0;
+        for (int u = tid + 1; u < 256 && r < 258; ++u) {
+            const unsigned v = s_lead[q][u];
+            r += (int)(v & 0x7FFFu);
+            if (!(v & 0x8000u)) break;
+        }
+        carry[q] = r;
+    }
+    // longest first, then the smallest distance (PNG_DIST ascends: a later one must be strictly longer)
+#pragma unroll
+    for (int k = 0; k < PNG_PER; ++k) {
+        int best = 0, bq = 0;
+#pragma unroll
+        for (int q = 0; q < PNG_ND; ++q) {
+            int run = __builtin_ctz(~(m[q] >> k));   // (bits 16 - k and up of the shifted mask are 0: run <= 16 - k)
+            if (run == PNG_PER - k) run += carry[q];
+            run = min(run, 258);
+            if (run > best) { best = run; bq = q; }
+        }
+        if (best < 3) { best = 0; bq = 0; }
+        const int i = base + k;
+        s_tok[i] = (unsigned short)(best | (bq << 9));
+        s_next[i] = (unsigned short)(i < n ? i + max(best, 1) : n);   // (a run ends before byte n: i + best <= n)
+    }
+    if (tid == 0) s_next[PNG_SEG] = (unsigned short)n;   // (n == PNG_SEG: the end of the chain points at itself)
+    __syncthreads();
+
+    // the greedy parse from position 0 by pointer doubling; position i of round k: tid + 256 k
+    for (int r = 0; r < 12; ++r) {   // 2^12 = PNG_SEG hops at the most
+        if (s_next[0] >= n) break;   // (workgroup-uniform: read behind a barrier, written only behind the next one)
+        unsigned short j[PNG_PER], jj[PNG_PER];
+        unsigned char mk[PNG_PER];
+#pragma unroll
+        for (int k = 0; k < PNG_PER; ++k) {
+            const int i = tid + 256 * k;
+            j[k] = s_next[i];
+            jj[k] = s_next[j[k]];
+            mk[k] = s_mark[i];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < PNG_PER; ++k) {
+            const int i = tid + 256 * k;
+            if (mk[k]) s_mark[j[k]] = 1;   // (one predecessor per position on the chain: no two lanes write one byte)
+            s_next[i] = jj[k];
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+
+    // bits per token
+    int bits = 0, nlit = 0, nmat = 0;
+#pragma unroll
+    for (int k = 0; k < PNG_PER; ++k) {
+        const int i = base + k;
+        if (i < n && s_mark[i]) {
+            const unsigned t = s_tok[i];
+            unsigned val; int nb;
+            if (t) { png_match((int)(t & 511u), PNG_DIST[t >> 9], val, nb); ++nmat; }
+            else { png_literal(c[8 + k], val, nb); ++nlit; }
+            bits += nb;
+        }
+    }
+    int tot;
+    const int before = block_excl_scan_256(bits, s_w, tot);   // (its barriers also end every use of s_next)
+    PngSeg s;
+    s.n = n;
+    s.pre = seg == 0 ? 2 : 0;
+    s.final = seg == d.nseg - 1 ? 1 : 0;
+    const int fixed_bits = 3 + tot + 7;   // block header, tokens, end of block
+    // not the last segment: an empty stored block (000, padding to a byte, 00 00 FF FF) brings the next segment to a byte boundary
+    const int fixed_bytes = s.final ? (fixed_bits + 7) >> 3 : ((fixed_bits + 3 + 7) >> 3) + 4;
+    s.fixed = fixed_bytes <= 5 + n ? 1 : 0;   // ties go to the fixed code
+    s.body = s.pre + (s.fixed ? fixed_bytes : 5 + n);
+
+    if (!WRITE) {
+        if (s.fixed) {
+            if (nlit) atomicAdd(&s_tokens[0], nlit);
+            if (nmat) atomicAdd(&s_tokens[1], nmat);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            d.len[seg] = 12 + s.body;
+            if (!s.fixed) atomicAdd(&d.cnt[5], 1ull);
+            if (s_tokens[0]) atomicAdd(&d.cnt[6], (unsigned long long)s_tokens[0]);
+            if (s_tokens[1]) atomicAdd(&d.cnt[7], (unsigned long long)s_tokens[1]);
+        }
+        return;
+    }
+
+    if (s.fixed) {   // (workgroup-uniform)
+        const int words = ((s.body + 3) >> 2) + 2;   // + the word a token's bits can spill into, + padding
+        for (int w = tid; w < words; w += 256) s_img[w] = 0u;
+        __syncthreads();
+        int o = 8 * s.pre + 3 + before;
+#pragma unroll
+        for (int k = 0; k < PNG_PER; ++k) {
+            const int i = base + k;
+            if (i < n && s_mark[i]) {
+                const unsigned t = s_tok[i];
+                unsigned val; int nb;
+                if (t) png_match((int)(t & 511u), PNG_DIST[t >> 9], val, nb);
+                else png_literal(c[8 + k], val, nb);
+                const int w = o >> 5, sh = o & 31;
+                atomicOr(&s_img[w], val << sh);
+                if (sh + nb > 32) atomicOr(&s_img[w + 1], val >> (32 - sh));   // (then sh > 0)
+                o += nb;
+            }
+        }
+        if (tid == 0) {
+            if (s.pre) atomicOr(&s_img[0], 0x0178u);                          // CMF 78, FLG 01
+            atomicOr(&s_img[s.pre >> 2], (unsigned)(s.final | 2) << (8 * s.pre));   // BFINAL, BTYPE 01 (its low bit first)
+            if (!s.final) {                                                   // LEN 0000 stays zero, NLEN FFFF
+                const int e = s.body - 2;
+                atomicOr(&s_img[e >> 2], 0xFFu << (8 * (e & 3)));
+                atomicOr(&s_img[(e + 1) >> 2], 0xFFu << (8 * ((e + 1) & 3)));
+            }
+        }
+        __syncthreads();
+    }
+
+    // the chunk: length, tag, payload at the scanned offset
+    unsigned char *out = d.out + (size_t)d.len[seg];
+    const unsigned tag = 0x54414449u;   // "IDAT", first letter in the low byte
+    for (int q = tid; q < 8 + s.body; q += 256) {
+        unsigned v;
+        if (q < 4) v = ((unsigned)s.body >> (8 * (3 - q))) & 255u;
+        else if (q < 8) v = (tag >> (8 * (q - 4))) & 255u;
+        else v = png_payload_byte(s, s_img, s_b, q - 8);
+        out[q] = (unsigned char)v;
+    }
+    // CRC-32 of tag + payload.  The register starts at all ones: the same as a zero register and the first four bytes complemented.
+    const int total = 4 + s.body, pad = 256 * PNG_CRC_PIECE - total;
+    unsigned r = 0u;
+    for (int k = 0; k < PNG_CRC_PIECE; ++k) {
+        const int v = tid * PNG_CRC_PIECE + k - pad;
+        if (v >= 0) r = png_crc_byte(r, v < 4 ? ((tag >> (8 * v)) & 255u) ^ 255u : png_payload_byte(s, s_img, s_b, v - 4));
+    }
+    s_red[tid] = r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        __syncthreads();
+        if ((tid & ((2 << j) - 1)) == 0) s_red[tid] = png_crc_mul(s_red[tid], d.crc_pow[j]) ^ s_red[tid + (1 << j)];
+    }
+    if (tid == 0) {
+        const unsigned crc = ~s_red[0];
+        unsigned char *e = out + 8 + s.body;
+        e[0] = (unsigned char)(crc >> 24); e[1] = (unsigned char)(crc >> 16); e[2] = (unsigned char)(crc >> 8); e[3] = (unsigned char)crc;
+    }
+    if (seg == 0 && tid == 64) {   // the Adler-32 closes the zlib stream in a chunk of its own (behind the last segment's)
+        unsigned char *a = d.out + (size_t)d.len[d.nseg];
+        const unsigned sum = d.sum[0];
+        unsigned cr = 0xFFFFFFFFu;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) {   // length 4, tag, the sum with its high byte first
+            const unsigned v = k < 4 ? (k == 3 ? 4u : 0u) : k < 8 ? (tag >> (8 * (k - 4))) & 255u : (sum >> (8 * (11 - k))) & 255u;
+            a[k] = (unsigned char)v;
+            if (k >= 4) cr = png_crc_byte(cr, v);
+        }
+        cr = ~cr;
+        a[12] = (unsigned char)(cr >> 24); a[13] = (unsigned char)(cr >> 16); a[14] = (unsigned char)(cr >> 8); a[15] = (unsigned char)cr;
+    }
+}
+
+// exclusive scan of len[0, nseg) in place, len[nseg] = the total (one workgroup walks the array, as k_video_scan does: 769 segments at
+// 1024^2, 49,164 at the 2^26 pixels sph_png_create accepts), and the Adler-32 of the whole stream from the segments' sums:
+//   A = 1 + sum a_k,  B = raw + sum (b_k + a_k x bytes behind segment k),  both mod 65521
+// The offsets are int: the largest file is below 2^26 x 3 + 2^14 + 17 x 49,164 + 75 < 2^31.
+__global__ void __launch_bounds__(256) k_png_scan(PngDev d) {
+    __shared__ int s_w[4];
+    __shared__ unsigned long long s_a[256], s_b[256];
+    const int tid = threadIdx.x, n = d.nseg;
+    int run = 0;
+    unsigned long long a = 0ull, b = 0ull;
+    for (int c0 = 0; c0 < n; c0 += 256) {
+        const int i = c0 + tid;
+        const int v = i < n ? d.len[i] : 0;
+        int tot;
+        const int ex = block_excl_scan_256(v, s_w, tot);
+        if (i < n) {
+            d.len[i] = run + ex;
+            const long long end = min((long long)(i + 1) * PNG_SEG, (long long)d.raw);
+            const unsigned long long ak = d.adler[2 * i], bk = d.adler[2 * i + 1];
+            a += ak;                                                        // < 2^16 each, <= 49,164 segments
+            b += bk + ak * (unsigned long long)((d.raw - end) % 65521);     // < 2^33 each
+        }
+        run += tot;
+    }
+    s_a[tid] = a; s_b[tid] = b;
+    __syncthreads();
+    if (tid == 0) {
+        d.len[n] = run;
+        unsigned long long sa = 1ull, sb = (unsigned long long)d.raw;
+        for (int k = 0; k < 256; ++k) { sa += s_a[k]; sb += s_b[k]; }
+        d.sum[0] = (unsigned)(sb % 65521ull) << 16 | (unsigned)(sa % 65521ull);
+    }
+}
+
+static void l_png_filter(PngDev &d) { hipLaunchKernelGGL(k_png_filter, dim3(d.H), dim3(256), 0, d.stream, d); }
+static void l_png_count(PngDev &d) { hipLaunchKernelGGL(k_png_segment<false>, dim3(d.nseg), dim3(256), 0, d.stream, d); }
+static void l_png_scan(PngDev &d) { hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(256), 0, d.stream, d); }
+static void l_png_write(PngDev &d) { hipLaunchKernelGGL(k_png_segment<true>, dim3(d.nseg), dim3(256), 0, d.stream, d); }
+
+static void register_png_launchers(Launch &L) {
+    L.png_filter = l_png_filter;
+    L.png_count = l_png_count;
+    L.png_scan = l_png_scan;
+    L.png_write = l_png_write;
+}

@@ -1,0 +1,191 @@
+// sph_png_api.hpp -- the SphPng object of include/sph_hip.h: the size bound, the fixed chunks (signature, IHDR, IEND), the frame source
+// (a host image, a renderer's frame buffer), the four passes and the stage marks.  Host code, included at the end of sph_api.hip; the
+// kernels are in sph_png.hpp, the stream is defined in DESIGN.md 21.
+#pragma once
+
+enum PngBufId { PB_RGB, PB_FLT, PB_LEN, PB_ADLER, PB_CNT, PB_OUT, PB_COUNT_ };
+
+struct SphPng : DevObj {   // clk[0]: the stages of an encode
+    SphPngParams prm;
+    PngDev d{};
+    DevBuf buf[PB_COUNT_];
+    std::vector<uint8_t> header;   // signature, IHDR
+    bool have_frame = false;
+    int64_t chunk_bytes = 0;       // what the device wrote: the segments' chunks and the Adler-32's
+    SphPngStats stats{};
+};
+
+static const char *png_check(const SphPngParams &p) {
+    if (p.width < 1 || p.height < 1 || p.width > 16384 || p.height > 16384 || (int64_t)p.width * p.height > ((int64_t)1 << 26))
+        return "width and height are 1..16384 each, at most 2^26 pixels in all";
+    if (p.filter < -1 || p.filter > 4) return "filter is -1 (adaptive) or a PNG filter type 0..4";
+    if (p.reserved != 0) return "reserved must be 0";
+    return nullptr;
+}
+
+static int64_t png_raw_bytes(const SphPngParams &p) { return (int64_t)p.height * (1 + 3 * (int64_t)p.width); }
+static int64_t png_segments(const SphPngParams &p) { return (png_raw_bytes(p) + PNG_SEG - 1) / PNG_SEG; }
+// signature 8, IHDR 25, per segment a chunk frame of 12 and at worst a stored block header of 5 around its raw bytes, the zlib header 2,
+// the Adler-32's chunk 16, IEND 12
+static int64_t png_bound(const SphPngParams &p) { return 8 + 25 + png_segments(p) * (12 + 5) + png_raw_bytes(p) + 2 + 16 + 12; }
+
+// CRC-32 on the host: for the 17 bytes of IHDR only (the payload's CRCs are the device's)
+static uint32_t png_crc_host(const uint8_t *p, size_t n) {
+    uint32_t r = 0xFFFFFFFFu;
+    for (size_t i = 0; i < n; ++i) {
+        r ^= p[i];
+        for (int k = 0; k < 8; ++k) r = (r >> 1) ^ (PNG_CRC_POLY & (0u - (r & 1u)));
+    }
+    return ~r;
+}
+static void png_be32(std::vector<uint8_t> &o, uint32_t v) { for (int s = 24; s >= 0; s -= 8) o.push_back((uint8_t)(v >> s)); }
+static std::vector<uint8_t> png_header(const SphPngParams &p) {
+    std::vector<uint8_t> o{0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
+    png_be32(o, 13);
+    const size_t tag = o.size();
+    o.insert(o.end(), {'I', 'H', 'D', 'R'});
+    png_be32(o, (uint32_t)p.width); png_be32(o, (uint32_t)p.height);
+    o.insert(o.end(), {8, 2, 0, 0, 0});   // 8 bits, colour type 2 (RGB), deflate, filter method 0, not interlaced
+    png_be32(o, png_crc_host(o.data() + tag, o.size() - tag));
+    return o;
+}
+static const uint8_t PNG_IEND[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xAE, 0x42, 0x60, 0x82};
+
+extern "C" int sph_png_bound(const SphPngParams *params, int64_t *bytes) {
+    if (!params || !bytes) return fail(nullptr, SPH_ERR_INVALID, "sph_png_bound: null argument");
+    if (const char *why = png_check(*params)) return fail(nullptr, SPH_ERR_INVALID, "sph_png_bound: %s", why);
+    *bytes = png_bound(*params);
+    return SPH_OK;
+}
+
+extern "C" int sph_png_create(const SphPngParams *params, SphPng **out) {
+    if (!params || !out) return fail(nullptr, SPH_ERR_INVALID, "sph_png_create: null argument");
+    *out = nullptr;
+    const SphPngParams p = *params;
+    if (const char *why = png_check(p)) return fail(nullptr, SPH_ERR_INVALID, "sph_png_create: %s", why);
+    int dev = 0;
+    { int rc = pick_device("sph_png_create", p.device, &dev); if (rc) return rc; }
+    SphPng *v = new SphPng();
+    v->prm = p;
+    v->header = png_header(p);
+    PngDev &d = v->d;
+    d.W = p.width; d.H = p.height; d.filter = p.filter;
+    d.stride = 1 + 3 * p.width;
+    d.raw = (int)png_raw_bytes(p);   // <= 3 x 2^26 + 2^14
+    d.nseg = (int)png_segments(p);
+    d.crc_pow[0] = 0x80000000u;   // x^0; a register step with no data multiplies by x
+    for (int k = 0; k < 8 * PNG_CRC_PIECE; ++k) d.crc_pow[0] = (d.crc_pow[0] >> 1) ^ (PNG_CRC_POLY & (0u - (d.crc_pow[0] & 1u)));
+    for (int j = 1; j < 8; ++j) d.crc_pow[j] = png_crc_mul(d.crc_pow[j - 1], d.crc_pow[j - 1]);
+    DevBuf *b = v->buf;
+    int rc = devobj_open(v, "sph_png_create", dev, p.fast_math);
+    if (rc && !v->stream) { sph_png_destroy(v); return rc; }
+    if (rc || b[PB_RGB].reserve(nullptr, (size_t)p.width * p.height * 3) || b[PB_FLT].reserve(nullptr, (size_t)d.nseg * PNG_SEG) ||
+        b[PB_LEN].reserve(nullptr, sizeof(int) * ((size_t)d.nseg + 1)) || b[PB_ADLER].reserve(nullptr, sizeof(unsigned) * 2 * (size_t)d.nseg) ||
+        b[PB_CNT].reserve(nullptr, 8 * sizeof(unsigned long long) + sizeof(unsigned))) {
+        sph_png_destroy(v);
+        return fail(nullptr, SPH_ERR_HIP, "sph_png_create: buffers of a %d x %d frame", p.width, p.height);
+    }
+    d.flt = (unsigned char *)b[PB_FLT].p; d.len = (int *)b[PB_LEN].p; d.adler = (unsigned *)b[PB_ADLER].p;
+    d.cnt = (unsigned long long *)b[PB_CNT].p; d.sum = (unsigned *)(d.cnt + 8);
+    d.stream = v->stream;
+    *out = v;
+    return SPH_OK;
+}
+
+extern "C" void sph_png_destroy(SphPng *v) {
+    if (!v) return;
+    devobj_close(v, v->buf, PB_COUNT_);
+    delete v;
+}
+
+extern "C" const char *sph_png_last_error(SphPng *v) { return last_error(v); }
+
+// after stage mark 0 and the source's arrival on the stream: filter, count, scan, size the output, write; synchronous
+static int png_run(SphPng *v, const unsigned char *rgb_dev) {
+    PngDev &d = v->d;
+    StageClock &k = v->clk[0];
+    d.rgb = rgb_dev;
+    HIPCHK(v, hipMemsetAsync(d.cnt, 0, 8 * sizeof(unsigned long long) + sizeof(unsigned), v->stream));
+    HIPCHK(v, k.mark(1));
+    v->L->png_filter(d);
+    HIPCHK(v, k.mark(2));
+    v->L->png_count(d);
+    HIPCHK(v, k.mark(3));
+    v->L->png_scan(d);
+    int total = 0;
+    unsigned long long c[8] = {};
+    HIPCHK(v, hipMemcpyAsync(&total, d.len + d.nseg, sizeof(int), hipMemcpyDeviceToHost, v->stream));
+    HIPCHK(v, hipMemcpyAsync(c, d.cnt, sizeof(c), hipMemcpyDeviceToHost, v->stream));
+    HIPCHK(v, k.mark(4));
+    HIPCHK(v, hipStreamSynchronize(v->stream));
+    HIPCHK(v, hipGetLastError());
+    const int64_t most = png_bound(v->prm) - (int64_t)v->header.size() - 12 - 16;
+    if (total < 13 || total > most) return fail(v, SPH_ERR_HIP, "sph_png: the count pass left %d chunk bytes (at most %lld)", total, (long long)most);
+    // the output holds exactly what the count pass found (grown with some room so that frames of similar size reuse it)
+    { int rc = v->buf[PB_OUT].reserve(v, (size_t)total + 16 + (size_t)total / 4 + 64); if (rc) return rc; }
+    d.out = (unsigned char *)v->buf[PB_OUT].p;
+    v->L->png_write(d);
+    HIPCHK(v, k.mark(5));
+    HIPCHK(v, hipStreamSynchronize(v->stream));
+    HIPCHK(v, hipGetLastError());
+    v->chunk_bytes = (int64_t)total + 16;
+    v->have_frame = true;
+    SphPngStats &o = v->stats;
+    o.raw_bytes = d.raw;
+    o.zlib_bytes = (int64_t)total - 12 * (int64_t)d.nseg + 4;
+    o.file_bytes = (int64_t)v->header.size() + v->chunk_bytes + 12;
+    o.segments = d.nseg; o.stored_segments = (int64_t)c[5]; o.literals = (int64_t)c[6]; o.matches = (int64_t)c[7];
+    for (int t = 0; t < 5; ++t) o.filter_rows[t] = (int64_t)c[t];
+    o.ms_input = k.ms(0, 1); o.ms_filter = k.ms(1, 2); o.ms_count = k.ms(2, 3); o.ms_scan = k.ms(3, 4); o.ms_write = k.ms(4, 5);
+    o.ms_total = k.ms(0, 5);
+    return SPH_OK;
+}
+
+extern "C" int sph_png_encode_rgb(SphPng *v, const uint8_t *rgb) {
+    if (!v) return SPH_ERR_INVALID;
+    if (!rgb) return fail(v, SPH_ERR_INVALID, "sph_png_encode_rgb: null image");
+    HIPCHK(v, hipSetDevice(v->device));
+    v->have_frame = false;
+    v->stats = SphPngStats{};
+    HIPCHK(v, v->clk[0].mark(0));
+    HIPCHK(v, hipMemcpyAsync(v->buf[PB_RGB].p, rgb, (size_t)v->d.W * v->d.H * 3, hipMemcpyHostToDevice, v->stream));
+    return png_run(v, (const unsigned char *)v->buf[PB_RGB].p);
+}
+
+extern "C" int sph_png_encode_render(SphPng *v, SphRender *r) {
+    if (!v || !r) return SPH_ERR_INVALID;
+    if (!r->have_frame) return fail(v, SPH_ERR_INVALID, "sph_png_encode_render: the renderer holds no frame");
+    if (r->d.W != v->d.W || r->d.H != v->d.H)
+        return fail(v, SPH_ERR_INVALID, "sph_png_encode_render: the renderer's frame is %d x %d, the encoder's %d x %d", r->d.W, r->d.H, v->d.W, v->d.H);
+    if (r->device != v->device) return fail(v, SPH_ERR_INVALID, "sph_png_encode_render: renderer on device %d, encoder on device %d", r->device, v->device);
+    HIPCHK(v, hipSetDevice(v->device));
+    v->have_frame = false;
+    v->stats = SphPngStats{};
+    HIPCHK(v, hipStreamSynchronize(r->stream));   // (the render calls are synchronous: the frame is complete)
+    HIPCHK(v, v->clk[0].mark(0));
+    return png_run(v, r->d.rgb);   // read in place: nothing of the renderer is written
+}
+
+extern "C" int sph_png_size(SphPng *v, int64_t *bytes) {
+    if (!v || !bytes) return SPH_ERR_INVALID;
+    if (!v->have_frame) return fail(v, SPH_ERR_INVALID, "sph_png_size: no frame has been encoded yet");
+    *bytes = (int64_t)v->header.size() + v->chunk_bytes + 12;
+    return SPH_OK;
+}
+
+extern "C" int sph_png_download(SphPng *v, uint8_t *dst) {
+    if (!v || !dst) return SPH_ERR_INVALID;
+    if (!v->have_frame) return fail(v, SPH_ERR_INVALID, "sph_png_download: no frame has been encoded yet");
+    HIPCHK(v, hipSetDevice(v->device));
+    const size_t nh = v->header.size();
+    memcpy(dst, v->header.data(), nh);
+    HIPCHK(v, hipMemcpy(dst + nh, v->d.out, (size_t)v->chunk_bytes, hipMemcpyDeviceToHost));
+    memcpy(dst + nh + v->chunk_bytes, PNG_IEND, 12);
+    return SPH_OK;
+}
+
+extern "C" int sph_png_stats(SphPng *v, SphPngStats *out) {
+    if (!v || !out) return SPH_ERR_INVALID;
+    *out = v->stats;
+    return SPH_OK;
+}

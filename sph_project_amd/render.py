@@ -75,6 +75,13 @@ class FrameRenderer(L.NativeObject):
         self._last = h
         return rgb
 
+    def _frame(self, h, download):
+        """The drawn frame: downloaded, or (download=False) left on the device for encode_last of an encoder."""
+        if download:
+            return self._download(h)
+        self._last = h
+        return None
+
     def _need(self, kind, what):
         if self._last is None or self._last_kind != kind:
             raise RenderError(f"{what}: the last frame is not a {'mesh' if kind == 'meshes' else 'particle'} frame", L.ERR_INVALID)
@@ -92,10 +99,10 @@ class FrameRenderer(L.NativeObject):
         self._last_kind = "points"
         return self._download(h)
 
-    def from_container(self, container, hide=()):
+    def from_container(self, container, hide=(), download=True):
         """uint8 (H, W, 3) of a live container's visible objects (object_visibility == 1, minus `hide`), drawn from the device state
         with their persistent ids and colours; box: [0, domainEnd] as in the reference unless the renderer was made with box=False
-        (or with a box of its own)."""
+        (or with a box of its own).  download=False: None is returned and the frame stays on the device."""
         engine = getattr(container, "engine", container)
         vis = np.asarray(container.object_visibility)
         mask = 0
@@ -108,13 +115,14 @@ class FrameRenderer(L.NativeObject):
         h = self._native(box if box is not False else None)
         self._chk(self.lib.sph_render_handle(h, engine.h, C.c_uint32(mask)), "sph_render_handle", h)
         self._last_kind = "points"
-        return self._download(h)
+        return self._frame(h, download)
 
-    def from_meshes(self, meshes):
+    def from_meshes(self, meshes, download=True):
         """uint8 (H, W, 3) of an ordered list of triangle meshes: each item is (vertices f32[nv, 3], triangles i32[nt, 3],
         normals f32[nv, 3] or None, rgb) or (SurfaceReconstructor, rgb) -- the reconstructor's last mesh, copied on the device.  Flat
         shading without normals.  Triangles are numbered through the list (ids(), mesh_of()).  `radius` plays no part.  A triangle with
-        an index outside its mesh is skipped and raises RenderError (code -1) after the frame is drawn: last_rgb() / ids() still give it."""
+        an index outside its mesh is skipped and raises RenderError (code -1) after the frame is drawn: last_rgb() / ids() still give it.
+        download=False: None is returned and the frame stays on the device."""
         h = self._native(self.box if self.box else None)
         self._last = self._last_kind = self._mesh_starts = None
         self._chk(self.lib.sph_render_mesh_begin(h), "sph_render_mesh_begin", h)
@@ -144,7 +152,7 @@ class FrameRenderer(L.NativeObject):
                 self._last, self._last_kind = h, "meshes"   # drawn, with the bad triangles skipped
         self._chk(rc, "sph_render_mesh_end", h)
         self._last_kind = "meshes"
-        return self._download(h)
+        return self._frame(h, download)
 
     def last_rgb(self):
         """uint8 (H, W, 3) of the last frame once more."""

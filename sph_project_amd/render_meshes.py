@@ -87,6 +87,8 @@ def parse_args(argv=None):
     parser.add_argument("--camera_position", type=float, nargs=3, default=(5.5, 2.5, 4.0))
     parser.add_argument("--camera_lookat", type=float, nargs=3, default=(-1.0, 0.0, 0.0))
     parser.add_argument("--camera_fov", type=float, default=70.0, help="vertical, degrees")
+    parser.add_argument("--png_device", action="store_true",
+                        help="compress the PNG files on the GPU from the device image (DESIGN.md 21), as run_simulation.py --png_device does")
     return parser.parse_args(argv)
 
 
@@ -100,6 +102,10 @@ def main(argv=None):
     renderer = FrameRenderer(float(cfg["Configuration"].get("particleRadius", 0.01)), width=args.render_size[0], height=args.render_size[1],
                              camera_position=args.camera_position, camera_lookat=args.camera_lookat, fov=args.camera_fov,
                              box=(np.zeros(3), dom))
+    encoder = None
+    if args.png_device:
+        from sph_project_amd.png import PngEncoder
+        encoder = PngEncoder(renderer.width, renderer.height)
     done = 0
     for frame in sorted(os.listdir(args.input_dir)):
         d = os.path.join(args.input_dir, frame)
@@ -108,7 +114,11 @@ def main(argv=None):
         meshes = frame_meshes(d, colours)
         if not meshes:
             continue
-        write_png(os.path.join(d, args.rendered_image_name), renderer.from_meshes(meshes))
+        if encoder is not None:
+            renderer.from_meshes(meshes, download=False)
+            encoder.write_png(os.path.join(d, args.rendered_image_name), renderer)
+        else:
+            write_png(os.path.join(d, args.rendered_image_name), renderer.from_meshes(meshes))
         done += 1
     print(f"Rendered {done} frame(s) of {args.input_dir}")
     return done

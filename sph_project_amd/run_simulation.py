@@ -9,7 +9,8 @@ layout Taichi's PLYWriter.export_ascii produces and surface_reconstruction.py / 
 Rigid bodies: mesh_object_{id}.obj per frame with exportObj (:146-150).  PNG frames (exportFrame, :131-134) come from the GPU
 renderer of render.py with --render (its own image, not GGUI's: DESIGN.md 15); without --render none is written.  --render_meshes
 writes {cnt:06}/render.png, the frame's meshes drawn on the GPU, where the reference's render.py needs Blender.  --video
-adds {out}/raw_view.avi / {out}/render.avi, the same frames as Motion-JPEG compressed on the GPU (make_video.py)."""
+adds {out}/raw_view.avi / {out}/render.avi, the same frames as Motion-JPEG compressed on the GPU (make_video.py).
+--png_device writes the PNG files from the device image as well: no pixel is downloaded, no zlib runs on the host."""
 import argparse
 import os
 import sys
@@ -100,7 +101,12 @@ def parse_args(argv=None):
     parser.add_argument("--video_fps", type=int, default=20, help="make_video.py's --fps")
     parser.add_argument("--video_quality", type=int, default=90, help="JPEG quality 1..100")
     parser.add_argument("--video_chroma", default="420", choices=["420", "444"])
+    parser.add_argument("--png_device", action="store_true",
+                        help="compress raw_view.png / render.png on the GPU from the renderer's device image (DESIGN.md 21: lossless, the "
+                             "same pixels, other bytes than the host's zlib) where the default downloads the frame and runs zlib on it")
     args = parser.parse_args(argv)
+    if args.png_device and not (args.render or args.render_meshes):
+        parser.error("--png_device compresses a renderer's frames: give --render and / or --render_meshes as well")
     if args.video and not (args.render or args.render_meshes):
         parser.error("--video takes its frames from a renderer: give --render and / or --render_meshes as well")
     return args
@@ -194,6 +200,19 @@ def main(argv=None):
                 videos[r] = (VideoEncoder(r.width, r.height, quality=args.video_quality, chroma=args.video_chroma),
                              AviWriter(f"{out_dir}/{name}", r.width, r.height, args.video_fps))
 
+    pngs = {}   # renderer -> device PNG encoder
+    if args.png_device:
+        from sph_project_amd.png import PngEncoder
+        pngs = {r: PngEncoder(r.width, r.height) for r in (renderer, mesh_renderer) if r is not None}
+
+    def store_png(path, r, draw):
+        """draw(download) renders r's frame; the file comes from the downloaded pixels or, with --png_device, from the device image"""
+        if r in pngs:
+            draw(False)
+            pngs[r].write_png(path, r)
+        else:
+            write_png(path, draw(True))
+
     def add_video_frame(r):
         if r in videos:
             encoder, writer = videos[r]
@@ -221,7 +240,7 @@ def main(argv=None):
             held = set()
             if output_frames:   # run_simulation.py:131-134
                 os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
-                write_png(f"{out_dir}/{cnt:06}/raw_view.png", renderer.from_container(container))
+                store_png(f"{out_dir}/{cnt:06}/raw_view.png", renderer, lambda dl: renderer.from_container(container, download=dl))
                 add_video_frame(renderer)
                 wrote = True
             if output_ply:
@@ -243,7 +262,8 @@ def main(argv=None):
                     wrote = True
             if mesh_renderer is not None:   # render.py: every mesh of the frame -> {frame}/render.png
                 os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
-                write_png(f"{out_dir}/{cnt:06}/render.png", mesh_renderer.from_meshes(frame_meshes(container, solver, recon, held)))
+                meshes = frame_meshes(container, solver, recon, held)
+                store_png(f"{out_dir}/{cnt:06}/render.png", mesh_renderer, lambda dl: mesh_renderer.from_meshes(meshes, download=dl))
                 add_video_frame(mesh_renderer)
                 wrote = True
             frames += 1 if wrote else 0
