@@ -669,10 +669,13 @@ int sph_video_stats(SphVideo *v, SphVideoStats *out);
    one complete .png file: 8-bit RGB (colour type 2), not interlaced; signature, IHDR, one IDAT chunk per segment of 4096 filtered
    bytes, one IDAT chunk with the Adler-32, IEND.  The IDAT payloads are one zlib stream (header 78 01): per segment either one block
    in the fixed Huffman code, closed by an empty stored block that brings the next segment to a byte boundary, or one stored block,
-   whichever is shorter (ties: fixed).  Tokens come from a fixed rule (candidate distances 1, 2, 3, 4, 6 inside the segment, longest
+   whichever is shorter (ties: fixed).  With sph_png_set_coding(SPH_PNG_CODING_DYNAMIC) a segment becomes a dynamic Huffman block
+   (BTYPE 10, closed like a fixed one) where that takes strictly fewer bytes than the choice above: lit/len lengths are Huffman's over
+   the segment's own tokens, the distance and code-length codes' come from package-merge (limits 4 and 7), all codes canonical, the
+   header run-length coded by a fixed greedy rule; a file in dynamic coding is never longer than the fixed one.  Tokens come from a fixed rule (candidate distances 1, 2, 3, 4, 6 inside the segment, longest
    match first, then the smallest distance, greedy from the segment's start), row filters from the least sum of |residual as int8|
    (ties: the lowest type) or one fixed type.  All of it is integer arithmetic, so the bytes are a function of (pixels, width, height,
-   filter): the same from both builds and from every call.  The device filters, matches, parses, codes, packs and computes the
+   filter, coding): the same from both builds and from every call.  The device filters, matches, parses, codes, packs and computes the
    Adler-32 and every IDAT chunk's CRC-32, and writes the IDAT chunks whole; the host writes the signature, IHDR and IEND and never
    reads the payload.  The output is sized from a counting pass: a file is never truncated, and never longer than sph_png_bound.
    One HIP stream per object; synchronous calls.  `fast_math` selects the build whose launchers run, as in the video object. */
@@ -689,8 +692,8 @@ typedef struct {
     int64_t zlib_bytes;        /* the zlib stream: header, blocks, Adler-32 */
     int64_t file_bytes;        /* the .png file */
     int64_t segments;
-    int64_t stored_segments;   /* segments written as a stored block because the fixed code would have been longer */
-    int64_t literals;          /* tokens of the segments written in the fixed code */
+    int64_t stored_segments;   /* segments written as a stored block because every code would have been longer */
+    int64_t literals;          /* tokens of the segments written in the fixed code or in a dynamic code */
     int64_t matches;
     int64_t filter_rows[5];    /* rows per filter type */
     double ms_input;           /* HIP events: upload of a host image (~0 for a renderer's frame) */
@@ -699,15 +702,23 @@ typedef struct {
     double ms_scan;            /* their scan, the Adler-32, the total read by the host */
     double ms_write;           /* second pass: the chunks and their CRCs */
     double ms_total;
+    int64_t dynamic_segments;     /* segments written as a dynamic Huffman block (0 in fixed coding) */
+    int64_t dynamic_header_bits;  /* the sum of their headers' bits: HLIT, HDIST, HCLEN, the code-length code, the coded lengths */
 } SphPngStats;
+
+#define SPH_PNG_CODING_FIXED 0     /* per segment the fixed Huffman code or a stored block (the default) */
+#define SPH_PNG_CODING_DYNAMIC 1   /* also a dynamic Huffman block where it is strictly shorter */
 
 typedef struct SphPng SphPng;
 /* SPH_ERR_INVALID (before any device is touched): a size or filter outside the ranges above, reserved != 0 */
 int sph_png_create(const SphPngParams *params, SphPng **out);
 void sph_png_destroy(SphPng *v);
 const char *sph_png_last_error(SphPng *v);
+/* the entropy coding of the encodes that follow; SPH_ERR_INVALID with a message for any other value */
+int sph_png_set_coding(SphPng *v, int32_t coding);
 /* the longest file these parameters can give: 8 + 25 + 17 * segments + raw_bytes + 2 + 16 + 12 with segments =
-   ceil(raw_bytes / 4096).  Host only: no device is touched. */
+   ceil(raw_bytes / 4096).  The same in either coding: a dynamic block replaces a segment's fixed or stored block only where it is
+   strictly shorter.  Host only: no device is touched. */
 int sph_png_bound(const SphPngParams *params, int64_t *bytes);
 /* a host image u8[height][width][3], rows from the top */
 int sph_png_encode_rgb(SphPng *v, const uint8_t *rgb);

@@ -172,9 +172,11 @@ class SphPngStats(C.Structure):
         ("raw_bytes", C.c_int64), ("zlib_bytes", C.c_int64), ("file_bytes", C.c_int64), ("segments", C.c_int64),
         ("stored_segments", C.c_int64), ("literals", C.c_int64), ("matches", C.c_int64), ("filter_rows", C.c_int64 * 5),
         ("ms_input", C.c_double), ("ms_filter", C.c_double), ("ms_count", C.c_double), ("ms_scan", C.c_double), ("ms_write", C.c_double),
-        ("ms_total", C.c_double),
+        ("ms_total", C.c_double), ("dynamic_segments", C.c_int64), ("dynamic_header_bits", C.c_int64),
     ]
 
+
+PNG_CODING_FIXED, PNG_CODING_DYNAMIC = 0, 1
 
 # return codes (include/sph_hip.h)
 ERR_INVALID, ERR_CAPACITY = -1, -2
@@ -285,6 +287,7 @@ _SIGNATURES = [
     ("sph_png_destroy", None, [_VP]),
     ("sph_png_last_error", C.c_char_p, [_VP]),
     ("sph_png_bound", C.c_int, [C.POINTER(SphPngParams), C.POINTER(C.c_int64)]),
+    ("sph_png_set_coding", C.c_int, [_VP, C.c_int32]),
     ("sph_png_encode_rgb", C.c_int, [_VP, _VP]),
     ("sph_png_encode_render", C.c_int, [_VP, _VP]),
     ("sph_png_size", C.c_int, [_VP, C.POINTER(C.c_int64)]),

@@ -301,8 +301,11 @@ struct VideoDev {
 
 // PNG encoding (sph_png.hpp): one frame -> the IDAT chunks of a PNG file.  The filtered stream (H rows of 1 + 3 W bytes) is
 // cut into segments of PNG_SEG raw bytes, the work of one workgroup and one IDAT chunk each; PNG_DIST are the candidate match distances.
-// cnt: [0..4] rows per filter type, [5] stored segments, [6] literals, [7] matches (the tokens of the segments coded with the fixed code).
+// cnt: [0..4] rows per filter type, [5] stored segments, [6] literals, [7] matches (the tokens of the segments coded with the fixed or a
+// dynamic code), [8] dynamic segments, [9] the bits of their headers.
 #define PNG_SEG 4096
+#define PNG_NCNT 10
+#define PNG_SIDE 320                   // bytes per segment of the dynamic coding's side record (sph_png.hpp)
 #define PNG_ND 5
 #define PNG_DIST_LIST {1, 2, 3, 4, 6}
 #define PNG_CRC_PIECE 17               // bytes per thread of a chunk's CRC: 256 pieces cover tag + prefix + stored header + PNG_SEG bytes
@@ -324,11 +327,12 @@ struct PngDev {
     unsigned char *flt;                // [raw] the filtered stream
     int *len;                          // [nseg + 1] bytes per segment's chunk (length, tag, payload, CRC) -> their exclusive scan, [nseg] the total
     unsigned *adler;                   // [2 nseg] per segment: sum of its bytes, sum of (bytes to its end) x byte, both mod 65521
-    unsigned long long *cnt;           // [8] see above
+    unsigned long long *cnt;           // [PNG_NCNT] see above
     unsigned *sum;                     // [1] the Adler-32 of the filtered stream (scan pass)
     unsigned crc_pow[8];               // x^(8 PNG_CRC_PIECE 2^j) mod the polynomial: joins two runs of 2^j pieces
     unsigned char *out;                // the chunks, then the Adler-32's own IDAT chunk
     hipStream_t stream;
+    unsigned char *side;               // [nseg][PNG_SIDE] coding = dynamic: the count pass's code lengths and choice; nullptr: coding = fixed
 };
 
 template <class T> struct DBuf {

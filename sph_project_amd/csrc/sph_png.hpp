@@ -14,6 +14,8 @@
 //             image is the byte stream), the chunk goes to its scanned offset, and its CRC-32 is 256 pieces of PNG_CRC_PIECE bytes joined
 //             by multiplication with x^(8 n) mod the polynomial (the message is right-aligned in the pieces: leading zeros leave a
 //             zero register unchanged, so every join of a level uses one constant)
+//   dynamic   (the DYN instantiations, coding = dynamic) COUNT also builds the segment's own codes from its tokens' histograms and keeps
+//             a dynamic block where it is strictly shorter; the lengths go to a side record from which WRITE rebuilds the canonical codes
 // The kernel runs twice per frame as the video encoder's does: COUNT leaves the chunk's byte count and the Adler sums, k_png_scan scans
 // the counts (the host sizes the output from the total) and joins the Adler sums, WRITE computes the same bytes again and stores them.
 #pragma once
@@ -89,13 +91,18 @@ __device__ __forceinline__ void png_literal(unsigned b, unsigned &val, int &nb) 
     if (b < 144u) { val = png_rev(0x30u + b, 8); nb = 8; }
     else { val = png_rev(0x190u + b - 144u, 9); nb = 9; }
 }
-__device__ __forceinline__ void png_match(int len, int dist, unsigned &val, int &nb) {
+// the lit/len symbol of a match length, its extra bits and their value
+__device__ __forceinline__ void png_len_sym(int len, int &sym, int &eb, unsigned &ev) {
     const int l = len - 3;
-    int sym, eb = 0;
-    unsigned ev = 0u;
+    eb = 0; ev = 0u;
     if (len == 258) sym = 285;
     else if (l < 8) sym = 257 + l;
     else { eb = 29 - __clz(l); sym = 257 + 4 * eb + (l >> eb); ev = (unsigned)l & ((1u << eb) - 1u); }   // groups of four codes per extra bit
+}
+__device__ __forceinline__ void png_match(int len, int dist, unsigned &val, int &nb) {
+    int sym, eb;
+    unsigned ev;
+    png_len_sym(len, sym, eb, ev);
     if (sym < 280) { val = png_rev((unsigned)sym - 256u, 7); nb = 7; }
     else { val = png_rev(0xC0u + (unsigned)sym - 280u, 8); nb = 8; }
     val |= ev << nb; nb += eb;
@@ -114,8 +121,135 @@ __device__ __forceinline__ unsigned png_crc_byte(unsigned r, unsigned b) {
     return r;
 }
 
+// --- dynamic blocks (coding = dynamic; DESIGN.md 21 'Dynamic blocks') ---
+// A segment's side record (PNG_SIDE bytes, written by the count pass, read by the write pass): the lengths of the lit/len code [286],
+// of the distance code [5] and of the code-length code [19] as bytes, then two ints: the mode (0 stored, 1 fixed, 2 dynamic) and the
+// header's bits (HLIT ... the last coded length).
+#define PNG_NLL 286
+#define PNG_NDC 5
+#define PNG_NCL 19
+#define PNG_NLEN (PNG_NLL + PNG_NDC + PNG_NCL)   // 310 lengths, padded to 312 bytes
+static_assert(PNG_ND == PNG_NDC, "the candidate distances 1, 2, 3, 4, 6 are the distance codes 0..4 (code 4: 5..6, one extra bit)");
+static_assert(PNG_SIDE == 312 + 8, "lengths, mode, header bits");
+static __device__ const unsigned char PNG_CL_ORDER[PNG_NCL] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+// the count pass's arrays inside s_img (words), which is free between the end of pointer doubling and the bit image
+#define PNG_C_HLL 0        // [288] lit/len counts
+#define PNG_C_HD 288       // [8] distance counts
+#define PNG_C_HCL 296      // [24] code-length symbol counts
+#define PNG_C_SYM 320      // [288] the symbol of every leaf, leaves sorted by (count, symbol)
+#define PNG_C_WT 608       // [572] weights of the leaves, then of the internal nodes in the order they are made
+#define PNG_C_PAR 1180     // [572] 16-bit parents
+#define PNG_C_LEN 1466     // [312] bytes: the three length arrays as in the side record
+#define PNG_C_PMW 1544     // [100] package-merge: leaf weights [20], two lists of [40]
+#define PNG_C_PML 1644     // [100] the items' symbol multiplicities, 3 bits per symbol: low words
+#define PNG_C_PMH 1744     // [100] high words
+#define PNG_C_MISC 1844    // [0] the lit/len code is deeper than 15, [1] header bits
+static_assert(PNG_C_MISC + 8 <= PNG_IMG_WORDS, "the count pass's arrays fit the image array");
+
+__device__ __forceinline__ int png_fixed_len(int s) { return s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8; }
+
+// Optimal code lengths under `limit` by package-merge, one lane.  Leaves: the used symbols sorted by (count, symbol).  List 1 is the
+// leaves; list j pairs the items of list j - 1 in order (an odd last item is dropped) and merges the packages with the leaves by weight,
+// a leaf before a package of equal weight.  A symbol's length is the number of times it occurs in the first 2 n - 2 items of the last
+// list.  An item carries its symbols' multiplicities (<= limit <= 7) in 3 bits per symbol (nsym <= 19: 57 bits, two words).
+__device__ __forceinline__ void png_package_merge(const unsigned *hist, int nsym, int limit, unsigned char *out, unsigned *w, unsigned *ml, unsigned *mh) {
+    int n = 0;
+    for (int s = 0; s < nsym; ++s) {
+        out[s] = 0;
+        const unsigned c = hist[s];
+        if (!c) continue;
+        int j = n++;
+        for (; j > 0 && w[j - 1] > c; --j) { w[j] = w[j - 1]; ml[j] = ml[j - 1]; mh[j] = mh[j - 1]; }   // (symbols ascend: behind its equals)
+        const unsigned long long m = 1ull << (3 * s);
+        w[j] = c; ml[j] = (unsigned)m; mh[j] = (unsigned)(m >> 32);
+    }
+    if (n == 0) return;
+    if (n == 1) { out[ml[0] ? __builtin_ctz(ml[0]) / 3 : (32 + __builtin_ctz(mh[0])) / 3] = 1; return; }
+    int cur = 20, nxt = 60, ncur = n;
+    for (int k = 0; k < n; ++k) { w[cur + k] = w[k]; ml[cur + k] = ml[k]; mh[cur + k] = mh[k]; }
+    for (int lev = 2; lev <= limit; ++lev) {
+        const int np = ncur >> 1;
+        int a = 0, b = 0, k = 0;
+        while (a < n || b < np) {   // (k < n + np <= 19 + 18)
+            const unsigned pw = b < np ? w[cur + 2 * b] + w[cur + 2 * b + 1] : 0u;
+            if (a < n && (b >= np || w[a] <= pw)) { w[nxt + k] = w[a]; ml[nxt + k] = ml[a]; mh[nxt + k] = mh[a]; ++a; }
+            else {
+                const unsigned long long m = ((unsigned long long)mh[cur + 2 * b] << 32 | ml[cur + 2 * b]) +
+                                             ((unsigned long long)mh[cur + 2 * b + 1] << 32 | ml[cur + 2 * b + 1]);
+                w[nxt + k] = pw; ml[nxt + k] = (unsigned)m; mh[nxt + k] = (unsigned)(m >> 32);
+                ++b;
+            }
+            ++k;
+        }
+        const int t = cur; cur = nxt; nxt = t;
+        ncur = k;
+    }
+    unsigned long long tot = 0ull;
+    for (int k = 0; k < 2 * n - 2; ++k) tot += (unsigned long long)mh[cur + k] << 32 | ml[cur + k];   // (2^limit >= n: the list is long enough)
+    for (int s = 0; s < nsym; ++s) out[s] = (unsigned char)((tot >> (3 * s)) & 7ull);
+}
+
+// The lit/len lengths [0, hlit) and the distance lengths [0, hdist) run-length coded as one sequence (RFC 1951 3.2.7), one lane.  Zeros:
+// 18 in chunks of at most 138 while at least 11 remain, then one 17 for 3..10, else single zeros.  A non-zero value: once, then 16 in
+// chunks of at most 6 while at least 3 remain, else the value again.  emit(code-length symbol, extra value, extra bits).
+template <class F>
+__device__ __forceinline__ void png_run_length(const unsigned char *len, int hlit, int hdist, F emit) {
+    const int N = hlit + hdist;
+    int i = 0;
+    while (i < N) {
+        const int v = len[i < hlit ? i : PNG_NLL + i - hlit];
+        int r = 1;
+        while (i + r < N && len[i + r < hlit ? i + r : PNG_NLL + i + r - hlit] == v) ++r;
+        i += r;
+        if (v == 0) {
+            while (r >= 11) { const int k = min(r, 138); emit(18, k - 11, 7); r -= k; }
+            if (r >= 3) { emit(17, r - 3, 3); r = 0; }
+        } else {
+            emit(v, 0, 0); --r;
+            while (r >= 3) { const int k = min(r, 6); emit(16, k - 3, 2); r -= k; }
+        }
+        for (; r > 0; --r) emit(v, 0, 0);
+    }
+}
+__device__ __forceinline__ int png_hlit(const unsigned char *len) { int h = PNG_NLL; while (h > 257 && !len[h - 1]) --h; return h; }
+__device__ __forceinline__ int png_hdist(const unsigned char *len) { int h = PNG_NDC; while (h > 1 && !len[PNG_NLL + h - 1]) --h; return h; }
+__device__ __forceinline__ int png_hclen(const unsigned char *len) {
+    int h = PNG_NCL;
+    while (h > 4 && !len[PNG_NLL + PNG_NDC + PNG_CL_ORDER[h - 1]]) --h;
+    return h;
+}
+
+// the canonical code (RFC 1951 3.2.2) of entry e of the three length arrays: the shorter codes of its array before it, then the codes
+// of its length at smaller symbols.  Returned as the code reversed (stream order) | length << 16; 0 for an unused symbol.
+__device__ __forceinline__ unsigned png_canonical(const unsigned char *len, int e) {
+    const int lo = e < PNG_NLL ? 0 : e < PNG_NLL + PNG_NDC ? PNG_NLL : PNG_NLL + PNG_NDC;
+    const int hi = e < PNG_NLL ? PNG_NLL : e < PNG_NLL + PNG_NDC ? PNG_NLL + PNG_NDC : PNG_NLEN;
+    const int l = len[e];
+    if (!l) return 0u;
+    unsigned code = 0u;
+    for (int k = lo; k < hi; ++k) {
+        const int lk = len[k];
+        if (lk && lk < l) code += 1u << (l - lk);
+        else if (lk == l && k < e) code += 1u;
+    }
+    return png_rev(code, l) | (unsigned)l << 16;
+}
+
+// a token in the segment's own code (tab: png_canonical of the 310 entries); <= 15 + 5 + 4 + 1 bits
+__device__ __forceinline__ void png_dyn_token(const unsigned *tab, unsigned t, unsigned byte, unsigned &val, int &nb) {
+    if (!t) { const unsigned e = tab[byte]; val = e & 0xFFFFu; nb = (int)(e >> 16); return; }
+    int sym, eb;
+    unsigned ev;
+    png_len_sym((int)(t & 511u), sym, eb, ev);
+    const unsigned e = tab[sym], q = t >> 9, f = tab[PNG_NLL + q];
+    val = e & 0xFFFFu; nb = (int)(e >> 16);
+    val |= ev << nb; nb += eb;
+    val |= (f & 0xFFFFu) << nb; nb += (int)(f >> 16);
+    if (q == 4u) { val |= 1u << nb; nb += 1; }   // distance 6: code 4 (5..6), extra bit 1
+}
+
 // what a segment's chunk is made of once the layout is known
-struct PngSeg { int n, pre, fixed, final, body; };   // raw bytes; 2 = the zlib header goes first; fixed code / stored; last segment; payload bytes
+struct PngSeg { int n, pre, fixed, final, body; };   // raw bytes; 2 = the zlib header goes first; a bit image (fixed or dynamic code) / stored; last segment; payload bytes
 __device__ __forceinline__ unsigned png_payload_byte(const PngSeg &s, const unsigned *img, const unsigned char *raw, int j) {
     if (s.fixed) return (img[j >> 2] >> (8 * (j & 3))) & 255u;
     if (j < s.pre) return j == 0 ? 0x78u : 0x01u;
@@ -129,8 +263,9 @@ __device__ __forceinline__ unsigned png_payload_byte(const PngSeg &s, const unsi
     return raw[j - 5];
 }
 
-template <bool WRITE>
+template <bool WRITE, bool DYN = false>
 __global__ void __launch_bounds__(256) k_png_segment(PngDev d) {
+    __shared__ unsigned s_dyn[DYN && WRITE ? 80 + PNG_NLEN + 2 : 1];   // (dynamic write pass) the lengths [312 bytes], the codes [310]
     __shared__ unsigned s_raw[PNG_SEG / 4];
     __shared__ unsigned short s_tok[PNG_SEG];          // per position: match length | index of its distance << 9 (0: a literal)
     __shared__ unsigned s_img[PNG_IMG_WORDS];
@@ -266,23 +401,196 @@ __global__ void __launch_bounds__(256) k_png_segment(PngDev d) {
     const int fixed_bytes = s.final ? (fixed_bits + 7) >> 3 : ((fixed_bits + 3 + 7) >> 3) + 4;
     s.fixed = fixed_bytes <= 5 + n ? 1 : 0;   // ties go to the fixed code
     s.body = s.pre + (s.fixed ? fixed_bytes : 5 + n);
+    bool dyn = false;     // the segment is a dynamic block (strictly shorter than the choice above)
+    int hbits = 0;        // its header's bits
+
+    if (DYN && !WRITE) {
+        // histograms of the tokens by the marked positions; the three codes' lengths; the header's bits
+        unsigned *h_ll = s_img + PNG_C_HLL, *h_d = s_img + PNG_C_HD, *h_cl = s_img + PNG_C_HCL, *l_sym = s_img + PNG_C_SYM, *wt = s_img + PNG_C_WT;
+        unsigned short *par = (unsigned short *)(s_img + PNG_C_PAR);
+        unsigned char *len = (unsigned char *)(s_img + PNG_C_LEN);
+        unsigned *misc = s_img + PNG_C_MISC;
+        for (int w = tid; w < PNG_C_SYM; w += 256) s_img[w] = 0u;
+        if (tid < 78) s_img[PNG_C_LEN + tid] = 0u;
+        if (tid < 8) misc[tid] = 0u;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < PNG_PER; ++k) {
+            const int i = base + k;
+            if (i < n && s_mark[i]) {
+                const unsigned t = s_tok[i];
+                if (t) {
+                    int sym, eb;
+                    unsigned ev;
+                    png_len_sym((int)(t & 511u), sym, eb, ev);
+                    atomicAdd(&h_ll[sym], 1u);
+                    atomicAdd(&h_d[t >> 9], 1u);
+                } else atomicAdd(&h_ll[c[8 + k]], 1u);
+            }
+        }
+        if (tid == 0) atomicAdd(&h_ll[256], 1u);   // the end of block
+        __syncthreads();
+        // the used lit/len symbols sorted by (count, symbol): every symbol counts the keys below its own
+        int nleaf = 0;
+        {
+            const int s0 = tid, s1 = tid + 256;
+            const unsigned c0 = h_ll[s0], c1 = s1 < PNG_NLL ? h_ll[s1] : 0u;
+            const unsigned k0 = c0 << 9 | (unsigned)s0, k1 = c1 << 9 | (unsigned)s1;
+            int r0 = 0, r1 = 0;
+            for (int j = 0; j < PNG_NLL; ++j) {
+                const unsigned cj = h_ll[j], kj = cj << 9 | (unsigned)j;
+                if (cj) { ++nleaf; r0 += kj < k0; r1 += kj < k1; }
+            }
+            if (c0) { l_sym[r0] = (unsigned)s0; wt[r0] = c0; }
+            if (c1) { l_sym[r1] = (unsigned)s1; wt[r1] = c1; }
+        }
+        __syncthreads();
+        const int root = 2 * nleaf - 2;   // (nleaf >= 2: the segment's first byte is a literal, and the end of block)
+        if (tid == 0) {
+            // Huffman by two queues: the leaves in order and the internal nodes in the order they are made; a node joins the two
+            // lightest heads, a leaf before an internal node of equal weight
+            int leaf = 0, inner = nleaf;
+            for (int node = nleaf; node <= root; ++node) {
+                unsigned sum = 0u;
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    int pick;
+                    if (leaf < nleaf && (inner >= node || wt[leaf] <= wt[inner])) pick = leaf++;
+                    else pick = inner++;
+                    sum += wt[pick];
+                    par[pick] = (unsigned short)node;
+                }
+                wt[node] = sum;
+            }
+        }
+        if (tid == 64) png_package_merge(h_d, PNG_NDC, 4, len + PNG_NLL, s_img + PNG_C_PMW, s_img + PNG_C_PML, s_img + PNG_C_PMH);
+        __syncthreads();
+        for (int k = tid; k < nleaf; k += 256) {   // depths: every leaf walks its parents
+            int at = k, depth = 0;
+            while (at != root && depth < 16) { at = par[at]; ++depth; }
+            if (at != root || depth > 15) atomicOr(&misc[0], 1u);   // deeper than 15: the segment is not offered a dynamic block
+            len[l_sym[k]] = (unsigned char)depth;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int extra = 0;
+            png_run_length(len, png_hlit(len), png_hdist(len), [&](int sym, int, int eb) { h_cl[sym] += 1u; extra += eb; });
+            png_package_merge(h_cl, PNG_NCL, 7, len + PNG_NLL + PNG_NDC, s_img + PNG_C_PMW, s_img + PNG_C_PML, s_img + PNG_C_PMH);
+            int hb = 5 + 5 + 4 + 3 * png_hclen(len) + extra;
+            for (int q = 0; q < PNG_NCL; ++q) hb += (int)h_cl[q] * len[PNG_NLL + PNG_NDC + q];
+            misc[1] = (unsigned)hb;
+        }
+        __syncthreads();
+        // the block's bits: the fixed block's with every code's length exchanged, and the header
+        int delta = 0;
+        for (int e = tid; e < PNG_NLL + PNG_NDC; e += 256)
+            delta += e < PNG_NLL ? (int)h_ll[e] * ((int)len[e] - png_fixed_len(e)) : (int)h_d[e - PNG_NLL] * ((int)len[e] - 5);
+        delta = video_wave_sum(delta);
+        if ((tid & 63) == 0) s_red[8 + (tid >> 6)] = (unsigned)delta;
+        __syncthreads();
+        hbits = (int)misc[1];
+        const int dyn_bits = fixed_bits + hbits + (int)(s_red[8] + s_red[9] + s_red[10] + s_red[11]);
+        const int dyn_bytes = s.final ? (dyn_bits + 7) >> 3 : ((dyn_bits + 3 + 7) >> 3) + 4;
+        dyn = !misc[0] && s.pre + dyn_bytes < s.body;
+        if (dyn) s.body = s.pre + dyn_bytes;
+        unsigned *side = (unsigned *)(d.side + (size_t)seg * PNG_SIDE);
+        if (tid < 78) side[tid] = s_img[PNG_C_LEN + tid];
+        if (tid == 78) side[78] = dyn ? 2u : (unsigned)s.fixed;
+        if (tid == 79) side[79] = (unsigned)hbits;
+    }
 
     if (!WRITE) {
-        if (s.fixed) {
+        if (s.fixed || dyn) {
             if (nlit) atomicAdd(&s_tokens[0], nlit);
             if (nmat) atomicAdd(&s_tokens[1], nmat);
         }
         __syncthreads();
         if (tid == 0) {
             d.len[seg] = 12 + s.body;
-            if (!s.fixed) atomicAdd(&d.cnt[5], 1ull);
+            if (!s.fixed && !dyn) atomicAdd(&d.cnt[5], 1ull);
             if (s_tokens[0]) atomicAdd(&d.cnt[6], (unsigned long long)s_tokens[0]);
             if (s_tokens[1]) atomicAdd(&d.cnt[7], (unsigned long long)s_tokens[1]);
+            if (DYN && dyn) { atomicAdd(&d.cnt[8], 1ull); atomicAdd(&d.cnt[9], (unsigned long long)hbits); }
         }
         return;
     }
 
-    if (s.fixed) {   // (workgroup-uniform)
+    if (DYN && WRITE) {
+        const unsigned *side = (const unsigned *)(d.side + (size_t)seg * PNG_SIDE);
+        dyn = side[78] == 2u;   // (workgroup-uniform)
+        if (dyn) {
+            hbits = (int)side[79];
+            unsigned char *len = (unsigned char *)s_dyn;
+            unsigned *tab = s_dyn + 80;
+            if (tid < 78) s_dyn[tid] = side[tid];
+            __syncthreads();
+            for (int e = tid; e < PNG_NLEN; e += 256) tab[e] = png_canonical(len, e);
+            __syncthreads();
+            int dbits = 0;
+#pragma unroll
+            for (int k = 0; k < PNG_PER; ++k) {
+                const int i = base + k;
+                if (i < n && s_mark[i]) {
+                    unsigned val; int nb;
+                    png_dyn_token(tab, s_tok[i], c[8 + k], val, nb);
+                    dbits += nb;
+                }
+            }
+            int dtot;
+            const int dbefore = block_excl_scan_256(dbits, s_w, dtot);
+            const unsigned eob = tab[256];
+            s.fixed = 1;   // (a bit image)
+            // the payload the count pass allotted: 3 + header + tokens + end of block, closed as a fixed block is; shorter than stored
+            s.body = min(d.len[seg + 1] - d.len[seg] - 12, s.pre + 5 + n);
+            const int words = ((s.body + 3) >> 2) + 2;
+            for (int w = tid; w < words; w += 256) s_img[w] = 0u;
+            __syncthreads();
+            const int top = 32 * words;   // (bits past the image are never written, whatever the side record says)
+            auto put = [&](int o, unsigned val, int nb) {
+                const int w = o >> 5, sh = o & 31;
+                if (o + nb > top) return;
+                atomicOr(&s_img[w], val << sh);
+                if (sh + nb > 32) atomicOr(&s_img[w + 1], val >> (32 - sh));
+            };
+            int o = 8 * s.pre + 3 + hbits + dbefore;
+#pragma unroll
+            for (int k = 0; k < PNG_PER; ++k) {
+                const int i = base + k;
+                if (i < n && s_mark[i]) {
+                    unsigned val; int nb;
+                    png_dyn_token(tab, s_tok[i], c[8 + k], val, nb);
+                    put(o, val, nb);
+                    o += nb;
+                }
+            }
+            if (tid == 0) {
+                if (s.pre) atomicOr(&s_img[0], 0x0178u);
+                atomicOr(&s_img[s.pre >> 2], (unsigned)(s.final | 4) << (8 * s.pre));   // BFINAL, BTYPE 10 (its low bit first)
+                put(8 * s.pre + 3 + hbits + dtot, eob & 0xFFFFu, (int)(eob >> 16));
+                if (!s.final) {
+                    const int e = s.body - 2;
+                    atomicOr(&s_img[e >> 2], 0xFFu << (8 * (e & 3)));
+                    atomicOr(&s_img[(e + 1) >> 2], 0xFFu << (8 * ((e + 1) & 3)));
+                }
+            }
+            if (tid == 64) {   // the header: HLIT, HDIST, HCLEN, the code-length code's lengths, the coded lengths
+                const int hlit = png_hlit(len), hdist = png_hdist(len), hclen = png_hclen(len);
+                int ho = 8 * s.pre + 3;
+                put(ho, (unsigned)(hlit - 257) | (unsigned)(hdist - 1) << 5 | (unsigned)(hclen - 4) << 10, 14);
+                ho += 14;
+                for (int q = 0; q < hclen; ++q) { put(ho, len[PNG_NLL + PNG_NDC + PNG_CL_ORDER[q]], 3); ho += 3; }
+                png_run_length(len, hlit, hdist, [&](int sym, int ev, int eb) {
+                    const unsigned e = tab[PNG_NLL + PNG_NDC + sym];
+                    const int nb = (int)(e >> 16);
+                    put(ho, (e & 0xFFFFu) | (unsigned)ev << nb, nb + eb);
+                    ho += nb + eb;
+                });
+            }
+            __syncthreads();
+        }
+    }
+
+    if (s.fixed && !dyn) {   // (workgroup-uniform)
         const int words = ((s.body + 3) >> 2) + 2;   // + the word a token's bits can spill into, + padding
         for (int w = tid; w < words; w += 256) s_img[w] = 0u;
         __syncthreads();
@@ -391,9 +699,15 @@ __global__ void __launch_bounds__(256) k_png_scan(PngDev d) {
 }
 
 static void l_png_filter(PngDev &d) { hipLaunchKernelGGL(k_png_filter, dim3(d.H), dim3(256), 0, d.stream, d); }
-static void l_png_count(PngDev &d) { hipLaunchKernelGGL(k_png_segment<false>, dim3(d.nseg), dim3(256), 0, d.stream, d); }
+static void l_png_count(PngDev &d) {
+    if (d.side) hipLaunchKernelGGL((k_png_segment<false, true>), dim3(d.nseg), dim3(256), 0, d.stream, d);
+    else hipLaunchKernelGGL((k_png_segment<false>), dim3(d.nseg), dim3(256), 0, d.stream, d);
+}
 static void l_png_scan(PngDev &d) { hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(256), 0, d.stream, d); }
-static void l_png_write(PngDev &d) { hipLaunchKernelGGL(k_png_segment<true>, dim3(d.nseg), dim3(256), 0, d.stream, d); }
+static void l_png_write(PngDev &d) {
+    if (d.side) hipLaunchKernelGGL((k_png_segment<true, true>), dim3(d.nseg), dim3(256), 0, d.stream, d);
+    else hipLaunchKernelGGL((k_png_segment<true>), dim3(d.nseg), dim3(256), 0, d.stream, d);
+}
 
 static void register_png_launchers(Launch &L) {
     L.png_filter = l_png_filter;

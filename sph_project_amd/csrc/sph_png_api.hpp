@@ -3,7 +3,7 @@
 // kernels are in sph_png.hpp, the stream is defined in DESIGN.md 21.
 #pragma once
 
-enum PngBufId { PB_RGB, PB_FLT, PB_LEN, PB_ADLER, PB_CNT, PB_OUT, PB_COUNT_ };
+enum PngBufId { PB_RGB, PB_FLT, PB_LEN, PB_ADLER, PB_CNT, PB_OUT, PB_SIDE, PB_COUNT_ };
 
 struct SphPng : DevObj {   // clk[0]: the stages of an encode
     SphPngParams prm;
@@ -13,6 +13,7 @@ struct SphPng : DevObj {   // clk[0]: the stages of an encode
     bool have_frame = false;
     int64_t chunk_bytes = 0;       // what the device wrote: the segments' chunks and the Adler-32's
     SphPngStats stats{};
+    int32_t coding = SPH_PNG_CODING_FIXED;
 };
 
 static const char *png_check(const SphPngParams &p) {
@@ -26,7 +27,8 @@ static const char *png_check(const SphPngParams &p) {
 static int64_t png_raw_bytes(const SphPngParams &p) { return (int64_t)p.height * (1 + 3 * (int64_t)p.width); }
 static int64_t png_segments(const SphPngParams &p) { return (png_raw_bytes(p) + PNG_SEG - 1) / PNG_SEG; }
 // signature 8, IHDR 25, per segment a chunk frame of 12 and at worst a stored block header of 5 around its raw bytes, the zlib header 2,
-// the Adler-32's chunk 16, IEND 12
+// the Adler-32's chunk 16, IEND 12.  The same in either coding: a dynamic block is written only where it is strictly shorter than the
+// fixed / stored choice, so no segment grows.
 static int64_t png_bound(const SphPngParams &p) { return 8 + 25 + png_segments(p) * (12 + 5) + png_raw_bytes(p) + 2 + 16 + 12; }
 
 // CRC-32 on the host: for the 17 bytes of IHDR only (the payload's CRCs are the device's)
@@ -81,12 +83,13 @@ extern "C" int sph_png_create(const SphPngParams *params, SphPng **out) {
     if (rc && !v->stream) { sph_png_destroy(v); return rc; }
     if (rc || b[PB_RGB].reserve(nullptr, (size_t)p.width * p.height * 3) || b[PB_FLT].reserve(nullptr, (size_t)d.nseg * PNG_SEG) ||
         b[PB_LEN].reserve(nullptr, sizeof(int) * ((size_t)d.nseg + 1)) || b[PB_ADLER].reserve(nullptr, sizeof(unsigned) * 2 * (size_t)d.nseg) ||
-        b[PB_CNT].reserve(nullptr, 8 * sizeof(unsigned long long) + sizeof(unsigned))) {
+        b[PB_CNT].reserve(nullptr, PNG_NCNT * sizeof(unsigned long long) + sizeof(unsigned)) || b[PB_SIDE].reserve(nullptr, (size_t)d.nseg * PNG_SIDE)) {
         sph_png_destroy(v);
         return fail(nullptr, SPH_ERR_HIP, "sph_png_create: buffers of a %d x %d frame", p.width, p.height);
     }
     d.flt = (unsigned char *)b[PB_FLT].p; d.len = (int *)b[PB_LEN].p; d.adler = (unsigned *)b[PB_ADLER].p;
-    d.cnt = (unsigned long long *)b[PB_CNT].p; d.sum = (unsigned *)(d.cnt + 8);
+    d.cnt = (unsigned long long *)b[PB_CNT].p; d.sum = (unsigned *)(d.cnt + PNG_NCNT);
+    d.side = nullptr;   // coding = fixed
     d.stream = v->stream;
     *out = v;
     return SPH_OK;
@@ -100,12 +103,21 @@ extern "C" void sph_png_destroy(SphPng *v) {
 
 extern "C" const char *sph_png_last_error(SphPng *v) { return last_error(v); }
 
+extern "C" int sph_png_set_coding(SphPng *v, int32_t coding) {
+    if (!v) return fail(nullptr, SPH_ERR_INVALID, "sph_png_set_coding: null encoder");
+    if (coding != SPH_PNG_CODING_FIXED && coding != SPH_PNG_CODING_DYNAMIC)
+        return fail(v, SPH_ERR_INVALID, "sph_png_set_coding: coding is %d (fixed) or %d (dynamic), not %d", SPH_PNG_CODING_FIXED, SPH_PNG_CODING_DYNAMIC, (int)coding);
+    v->coding = coding;
+    v->d.side = coding == SPH_PNG_CODING_DYNAMIC ? (unsigned char *)v->buf[PB_SIDE].p : nullptr;   // which instantiations the launchers run
+    return SPH_OK;
+}
+
 // after stage mark 0 and the source's arrival on the stream: filter, count, scan, size the output, write; synchronous
 static int png_run(SphPng *v, const unsigned char *rgb_dev) {
     PngDev &d = v->d;
     StageClock &k = v->clk[0];
     d.rgb = rgb_dev;
-    HIPCHK(v, hipMemsetAsync(d.cnt, 0, 8 * sizeof(unsigned long long) + sizeof(unsigned), v->stream));
+    HIPCHK(v, hipMemsetAsync(d.cnt, 0, PNG_NCNT * sizeof(unsigned long long) + sizeof(unsigned), v->stream));
     HIPCHK(v, k.mark(1));
     v->L->png_filter(d);
     HIPCHK(v, k.mark(2));
@@ -113,7 +125,7 @@ static int png_run(SphPng *v, const unsigned char *rgb_dev) {
     HIPCHK(v, k.mark(3));
     v->L->png_scan(d);
     int total = 0;
-    unsigned long long c[8] = {};
+    unsigned long long c[PNG_NCNT] = {};
     HIPCHK(v, hipMemcpyAsync(&total, d.len + d.nseg, sizeof(int), hipMemcpyDeviceToHost, v->stream));
     HIPCHK(v, hipMemcpyAsync(c, d.cnt, sizeof(c), hipMemcpyDeviceToHost, v->stream));
     HIPCHK(v, k.mark(4));
@@ -135,6 +147,7 @@ static int png_run(SphPng *v, const unsigned char *rgb_dev) {
     o.zlib_bytes = (int64_t)total - 12 * (int64_t)d.nseg + 4;
     o.file_bytes = (int64_t)v->header.size() + v->chunk_bytes + 12;
     o.segments = d.nseg; o.stored_segments = (int64_t)c[5]; o.literals = (int64_t)c[6]; o.matches = (int64_t)c[7];
+    o.dynamic_segments = (int64_t)c[8]; o.dynamic_header_bits = (int64_t)c[9];
     for (int t = 0; t < 5; ++t) o.filter_rows[t] = (int64_t)c[t];
     o.ms_input = k.ms(0, 1); o.ms_filter = k.ms(1, 2); o.ms_count = k.ms(2, 3); o.ms_scan = k.ms(3, 4); o.ms_write = k.ms(4, 5);
     o.ms_total = k.ms(0, 5);

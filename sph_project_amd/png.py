@@ -1,7 +1,8 @@
 """PNG files on the GPU: RGB frames -> lossless 8-bit RGB .png files (C-ABI sph_png_* in include/sph_hip.h).
 
-Stands in for the zlib pass of render.encode_png over a downloaded frame: row filters, LZ77 tokens, the fixed Huffman code, Adler-32 and
-the chunk CRCs are computed by the HIP passes of csrc/sph_png.hpp where a rendered frame already lies, and only the finished file
+Stands in for the zlib pass of render.encode_png over a downloaded frame: row filters, LZ77 tokens, the fixed Huffman code (or, with
+coding="dynamic", per segment a dynamic Huffman block where that is shorter: smaller files, a slower count pass), Adler-32 and the chunk
+CRCs are computed by the HIP passes of csrc/sph_png.hpp where a rendered frame already lies, and only the finished file
 crosses to the host.  No CPU fallback for the encoder (render.encode_png remains what the drivers use without --png_device)."""
 from __future__ import annotations
 
@@ -24,8 +25,17 @@ def _filter(f):
     return int(f)
 
 
+CODINGS = {"fixed": L.PNG_CODING_FIXED, "dynamic": L.PNG_CODING_DYNAMIC}
+
+
+def _coding(c):
+    if not isinstance(c, str) or c not in CODINGS:
+        raise ValueError(f"coding must be 'fixed' or 'dynamic', not {c!r}")
+    return CODINGS[c]
+
+
 def bound(width, height, filter="adaptive"):
-    """The longest file PngEncoder(width, height) can return (sph_png_bound: host only)."""
+    """The longest file PngEncoder(width, height) can return in either coding (sph_png_bound: host only)."""
     p = L.SphPngParams(width=int(width), height=int(height), filter=_filter(filter), fast_math=0, device=-1, reserved=0)
     n = C.c_int64()
     lib = L.load()
@@ -35,19 +45,31 @@ def bound(width, height, filter="adaptive"):
 
 
 class PngEncoder(L.NativeObject):
-    """One PNG encoder for frames of one size.  The bytes of a file depend on (pixels, width, height, filter) alone."""
+    """One PNG encoder for frames of one size.  The bytes of a file depend on (pixels, width, height, filter, coding) alone; a file in
+    coding "dynamic" is never longer than the "fixed" one of the same picture."""
     ABI, Error = "sph_png", PngError
 
-    def __init__(self, width, height, filter="adaptive", fast_math=False, device=-1):
+    def __init__(self, width, height, filter="adaptive", coding="fixed", fast_math=False, device=-1):
         super().__init__()
         self.width, self.height, self.filter = int(width), int(height), _filter(filter)
+        code = _coding(coding)
         p = L.SphPngParams(width=self.width, height=self.height, filter=self.filter, fast_math=int(bool(fast_math)),
                            device=int(device), reserved=0)
         self.h = self._create(p)
+        self.coding = "fixed"
+        if code != L.PNG_CODING_FIXED:
+            self.set_coding(coding)
 
     def _need_open(self, what):
         if self.h is None:
             raise PngError(f"{what}: the encoder is closed", L.ERR_INVALID)
+
+    def set_coding(self, coding):
+        """"fixed" | "dynamic": the entropy coding of the encodes that follow"""
+        code = _coding(coding)
+        self._need_open("set_coding")
+        self._chk(self.lib.sph_png_set_coding(self.h, code), "sph_png_set_coding")
+        self.coding = coding
 
     def _download(self):
         self._need_open("download")

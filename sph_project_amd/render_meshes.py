@@ -89,7 +89,13 @@ def parse_args(argv=None):
     parser.add_argument("--camera_fov", type=float, default=70.0, help="vertical, degrees")
     parser.add_argument("--png_device", action="store_true",
                         help="compress the PNG files on the GPU from the device image (DESIGN.md 21), as run_simulation.py --png_device does")
-    return parser.parse_args(argv)
+    parser.add_argument("--png_coding", default=None, choices=["fixed", "dynamic"],
+                        help="with --png_device: fixed (the default) or dynamic Huffman blocks, as run_simulation.py --png_coding")
+    args = parser.parse_args(argv)
+    if args.png_coding is not None and not args.png_device:
+        parser.error("--png_coding chooses the device encoder's code: give --png_device as well")
+    args.png_coding = args.png_coding or "fixed"
+    return args
 
 
 def main(argv=None):
@@ -105,7 +111,7 @@ def main(argv=None):
     encoder = None
     if args.png_device:
         from sph_project_amd.png import PngEncoder
-        encoder = PngEncoder(renderer.width, renderer.height)
+        encoder = PngEncoder(renderer.width, renderer.height, coding=args.png_coding)
     done = 0
     for frame in sorted(os.listdir(args.input_dir)):
         d = os.path.join(args.input_dir, frame)

@@ -10,7 +10,8 @@ Rigid bodies: mesh_object_{id}.obj per frame with exportObj (:146-150).  PNG fra
 renderer of render.py with --render (its own image, not GGUI's: DESIGN.md 15); without --render none is written.  --render_meshes
 writes {cnt:06}/render.png, the frame's meshes drawn on the GPU, where the reference's render.py needs Blender.  --video
 adds {out}/raw_view.avi / {out}/render.avi, the same frames as Motion-JPEG compressed on the GPU (make_video.py).
---png_device writes the PNG files from the device image as well: no pixel is downloaded, no zlib runs on the host."""
+--png_device writes the PNG files from the device image as well (DESIGN.md 21): no pixel is downloaded, no zlib runs on the host;
+--png_coding dynamic makes those files smaller (dynamic Huffman blocks) for a slower encode."""
 import argparse
 import os
 import sys
@@ -104,9 +105,15 @@ def parse_args(argv=None):
     parser.add_argument("--png_device", action="store_true",
                         help="compress raw_view.png / render.png on the GPU from the renderer's device image (DESIGN.md 21: lossless, the "
                              "same pixels, other bytes than the host's zlib) where the default downloads the frame and runs zlib on it")
+    parser.add_argument("--png_coding", default=None, choices=["fixed", "dynamic"],
+                        help="with --png_device: the entropy coding of the files (DESIGN.md 21).  fixed (the default): the fixed Huffman "
+                             "code; dynamic: per segment a dynamic Huffman block where it is shorter -- smaller files, a slower encode")
     args = parser.parse_args(argv)
     if args.png_device and not (args.render or args.render_meshes):
         parser.error("--png_device compresses a renderer's frames: give --render and / or --render_meshes as well")
+    if args.png_coding is not None and not args.png_device:
+        parser.error("--png_coding chooses the device encoder's code: give --png_device as well")
+    args.png_coding = args.png_coding or "fixed"
     if args.video and not (args.render or args.render_meshes):
         parser.error("--video takes its frames from a renderer: give --render and / or --render_meshes as well")
     return args
@@ -203,7 +210,7 @@ def main(argv=None):
     pngs = {}   # renderer -> device PNG encoder
     if args.png_device:
         from sph_project_amd.png import PngEncoder
-        pngs = {r: PngEncoder(r.width, r.height) for r in (renderer, mesh_renderer) if r is not None}
+        pngs = {r: PngEncoder(r.width, r.height, coding=args.png_coding) for r in (renderer, mesh_renderer) if r is not None}
 
     def store_png(path, r, draw):
         """draw(download) renders r's frame; the file comes from the downloaded pixels or, with --png_device, from the device image"""

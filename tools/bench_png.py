@@ -4,8 +4,10 @@ with --render_meshes, a mesh frame of the reconstructed surface (render.png): on
 the GPU encode by stage (HIP events) and around the call (host clock), the download of the file, and in the same run what storing the
 same frame costs on the parent's path: the raw download of the frame (sph_render_download) plus encode_png on the host.  Sizes: the
 device's file against encode_png (zlib level 6) and against the same filter-0 stream at zlib level 1.  The device's file is decoded
-once per state and compared with the pixels.  One JSON line per state and frame kind; with --out also written to that file
-(profiles/png_bench_c2.txt)."""
+once per state and compared with the pixels.  --coding fixed | dynamic | both: which entropy coding the encoder uses; `both` encodes every
+timed frame with two encoders in alternation (the same frame, the same host reference) and reports per coding the stage times, the file
+bytes, size_vs_host, dynamic_segments and the dynamic headers' bytes.  One JSON line per state, frame kind and coding; with --out also
+written to that file (profiles/png_bench_c2.txt, profiles/png_dynamic_bench_c2.txt)."""
 import argparse
 import json
 import os
@@ -31,34 +33,44 @@ def _ms(f):
     return 1e3 * (time.perf_counter() - t0), out
 
 
-def measure(r, v, draw, frames, label, step, kind):
+def measure(r, encoders, draw, frames, label, step, kind):
+    """encoders: {coding: PngEncoder}; every timed frame is encoded by each of them in turn"""
     draw()   # untimed: allocations, first touch
-    assert np.array_equal(decode_png(v.encode_last(r)), r.last_rgb())
-    rows = []
+    for v in encoders.values():
+        assert np.array_equal(decode_png(v.encode_last(r)), r.last_rgb())   # every coding's file decodes to the frame's pixels
+    rows = {c: [] for c in encoders}
     for _ in range(frames):
         draw()
-        enc_host, _ = _ms(lambda: v._chk(v.lib.sph_png_encode_render(v.h, r._last), "sph_png_encode_render"))
-        st = v.stats()
-        dl_host, png_dev = _ms(v._download)
         raw_host, rgb = _ms(r.last_rgb)
         png_host, png = _ms(lambda: encode_png(rgb))
-        rows.append(dict(encode_ms=st["ms_total"], filter_ms=st["ms_filter"], count_ms=st["ms_count"], scan_ms=st["ms_scan"],
-                         write_ms=st["ms_write"], encode_host_ms=enc_host, file_download_host_ms=dl_host,
-                         raw_download_host_ms=raw_host, png_encode_host_ms=png_host,
-                         gpu_path_host_ms=enc_host + dl_host, host_path_host_ms=raw_host + png_host,
-                         device_png_bytes=len(png_dev), host_png_bytes=len(png), stored_segments=st["stored_segments"],
-                         literals=st["literals"], matches=st["matches"], filter_rows=st["filter_rows"]))
+        for coding, v in encoders.items():
+            enc_host, _ = _ms(lambda: v._chk(v.lib.sph_png_encode_render(v.h, r._last), "sph_png_encode_render"))
+            st = v.stats()
+            dl_host, png_dev = _ms(v._download)
+            rows[coding].append(dict(encode_ms=st["ms_total"], filter_ms=st["ms_filter"], count_ms=st["ms_count"], scan_ms=st["ms_scan"],
+                                     write_ms=st["ms_write"], encode_host_ms=enc_host, file_download_host_ms=dl_host,
+                                     raw_download_host_ms=raw_host, png_encode_host_ms=png_host,
+                                     gpu_path_host_ms=enc_host + dl_host, host_path_host_ms=raw_host + png_host,
+                                     device_png_bytes=len(png_dev), host_png_bytes=len(png), stored_segments=st["stored_segments"],
+                                     dynamic_segments=st["dynamic_segments"], dynamic_header_bytes=(st["dynamic_header_bits"] + 7) // 8,
+                                     segments=st["segments"], literals=st["literals"], matches=st["matches"], filter_rows=st["filter_rows"]))
     raw = np.zeros((r.height, 1 + 3 * r.width), np.uint8)
     raw[:, 1:] = rgb.reshape(r.height, 3 * r.width)
+    zlib1 = len(zlib.compress(raw.tobytes(), 1)) + len(png) - len(zlib.compress(raw.tobytes(), 6))
+    return [summary(rows[c], r, frames, label, step, kind, c, zlib1) for c in encoders]
+
+
+def summary(rows, r, frames, label, step, kind, coding, zlib1):
     med = lambda key: round(float(np.median([row[key] for row in rows])), 3)  # noqa: E731
-    out = dict(state=label, kind=kind, step=step, frames=frames, width=r.width, height=r.height)
+    out = dict(state=label, kind=kind, coding=coding, step=step, frames=frames, width=r.width, height=r.height)
     out.update({k: med(k) for k in rows[0] if k.endswith("_ms")})
     out.update({k: rows[0][k] for k in rows[0] if not k.endswith("_ms")})
     host = [row["host_path_host_ms"] for row in rows]
     out["host_path_min_ms"], out["host_path_max_ms"] = round(min(host), 3), round(max(host), 3)
     out["gpu_path_max_ms"] = round(max(row["gpu_path_host_ms"] for row in rows), 3)
+    out["encode_min_ms"], out["encode_max_ms"] = round(min(row["encode_ms"] for row in rows), 3), round(max(row["encode_ms"] for row in rows), 3)
     out["speedup"] = round(out["host_path_host_ms"] / out["gpu_path_host_ms"], 1)
-    out["zlib1_png_bytes"] = len(zlib.compress(raw.tobytes(), 1)) + len(png) - len(zlib.compress(raw.tobytes(), 6))
+    out["zlib1_png_bytes"] = zlib1
     out["size_vs_host"] = round(out["device_png_bytes"] / out["host_png_bytes"], 3)
     print(json.dumps(out), flush=True)
     return out
@@ -70,13 +82,15 @@ def main():
     ap.add_argument("--motion-step", type=int, default=2500, help="0: from rest only")
     ap.add_argument("--render_meshes", action="store_true", help="also a mesh frame of the reconstructed fluid surface per state")
     ap.add_argument("--filter", default="adaptive")
+    ap.add_argument("--coding", default="fixed", choices=["fixed", "dynamic", "both"],
+                    help="both: every timed frame is encoded with a fixed and a dynamic encoder in alternation")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     container, solver = P.build_product(P.c2_scene())
     solver.prepare()
     r = FrameRenderer(container.dx)
     filt = a.filter if a.filter == "adaptive" else int(a.filter)
-    v = PngEncoder(r.width, r.height, filter=filt)
+    encoders = {c: PngEncoder(r.width, r.height, filter=filt, coding=c) for c in (("fixed", "dynamic") if a.coding == "both" else (a.coding,))}
     rm = recon = None
     if a.render_meshes:
         rm = FrameRenderer(container.dx, box=(np.zeros(3), np.asarray(container.domain_end, dtype=np.float64)))
@@ -85,10 +99,10 @@ def main():
     lines = []
 
     def state(label, step):
-        lines.append(measure(r, v, lambda: r.from_container(container, download=False), a.frames, label, step, "particles"))
+        lines.extend(measure(r, encoders, lambda: r.from_container(container, download=False), a.frames, label, step, "particles"))
         if rm is not None:
             recon.from_container(container, 0)
-            lines.append(measure(rm, v, lambda: rm.from_meshes([(recon, (50, 100, 200))], download=False), a.frames, label, step, "meshes"))
+            lines.extend(measure(rm, encoders, lambda: rm.from_meshes([(recon, (50, 100, 200))], download=False), a.frames, label, step, "meshes"))
 
     state("rest", 0)
     if a.motion_step > 0:

@@ -26,9 +26,9 @@ def short(name):
     m = re.search(r"(k_video_interval)<\s*(true|false)", name)   # the video encoder's passes: <false> count, <true> write
     if m:
         return m.group(1) + ("<write>" if m.group(2) == "true" else "<count>")
-    m = re.search(r"(k_png_segment)<\s*(true|false)", name)   # the PNG encoder's passes: <false> count, <true> write
+    m = re.search(r"(k_png_segment)<\s*(true|false)(?:,\s*(true|false))?", name)   # the PNG encoder's passes: <false> count, <true> write; second: dynamic coding
     if m:
-        return m.group(1) + ("<write>" if m.group(2) == "true" else "<count>")
+        return m.group(1) + ("<write" if m.group(2) == "true" else "<count") + (", dynamic>" if m.group(3) == "true" else ">")
     m = re.search(r"(k_\w+)", name)
     return m.group(1) if m else name[:40]
 
