@@ -398,6 +398,10 @@ int sph_points_in_mesh(const double *vertices, int n_vertices, const int32_t *fa
    blank).  xyz: f32[n][3] in the scene's frame, e.g. what sph_download(SPH_F_POSITION) returned.  SPH_ERR_UNSUPPORTED: the file could
    not be written. */
 int sph_write_ply_ascii(const char *path, const float *xyz, int64_t n);
+/* the same file in parts (a sharded scene: every rank's owned particles, in rank order): first != 0 truncates the file and writes the
+   header for n_total vertices, then this part's n rows; first == 0 appends n rows.  The parts of any split, concatenated, are byte for
+   byte sph_write_ply_ascii of the concatenated array.  The caller keeps the parts in order (sph_comm_barrier between ranks). */
+int sph_write_ply_ascii_part(const char *path, const float *xyz, int64_t n, int64_t n_total, int first);
 /* str(np.float32(v)) -- the number format of that file -- into out (>= 48 bytes, no terminator); returns the length */
 int sph_format_f32(float v, char *out);
 /* the OBJ of one reconstructed surface (what splashsurf's `-o particle_object_{id}.obj` of surface_reconstruction.py:8 wrote): "v x y z"
@@ -560,12 +564,36 @@ const char *sph_render_last_error(SphRender *r);
 int sph_render_points(SphRender *r, const float *xyz, const uint8_t *rgb_or_NULL, const uint32_t *ids_or_NULL, int64_t n);
 /* the particles of a live handle whose object id has its bit set in object_mask (ghosts and dead slots never), each with its persistent
    id (SPH_F_PARTICLE_ID) and its colour as sph_download(SPH_F_COLOR) gives it; the handle's state is left untouched.  The handle must
-   be on the same device and not between sph_step_begin and sph_step_end; SPH_ERR_UNSUPPORTED on a sharded handle. */
+   be on the same device and not between sph_step_begin and sph_step_end.
+   A sharded handle (sph_comm_set_slab) makes the call COLLECTIVE over the handle's communicator: every rank calls it with
+   the same renderer parameters and the same mask; each settles its asynchronous steps, draws its own particles, and the layers are
+   merged down the rank chain (rank nranks-1 -> ... -> 0, neighbour transport, bounded waits: a lost rank ends in SPH_ERR_COMM).  Rank 0
+   then holds the frame -- bit for bit the unsharded renderer's, persistent ids being global -- for sph_render_download and the
+   encoders; on the other ranks sph_render_download is SPH_ERR_INVALID.  SPH_ERR_UNSUPPORTED: a handle whose library frame is permuted
+   (SPH_SLAB_LAYOUT=slow). */
 int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mask);
 /* the last frame: rgb u8[height][width][3] (rows from the top), ids_or_NULL i32[height][width]: the winner's id, -1 background,
    -2 - edge a box line */
 int sph_render_download(SphRender *r, uint8_t *rgb, int32_t *ids_or_NULL);
 int sph_render_stats(SphRender *r, SphRenderStats *out);
+
+/* layers: what a particle frame holds per pixel -- the u64 key (float_bits(t) << 32 | id; ~0 where nothing was drawn) and
+   the rgb.  Renderers with the same parameters that drew disjoint particle sets with distinct ids compose: per pixel the smaller key
+   wins, and the result is the frame of the union.  key u64[height][width], rgb u8[height][width][3].
+   _download: the layer of the last particle frame.  _merge: upload a layer, fold it into the current frame, then background, id image
+   and covered_pixels again (sph_render_download / the encoders see the merged frame).  SPH_ERR_INVALID: no frame, or a mesh frame. */
+int sph_render_layer_download(SphRender *r, uint64_t *key, uint8_t *rgb);
+int sph_render_layer_merge(SphRender *r, const uint64_t *key, const uint8_t *rgb);
+
+typedef struct {
+    int32_t ranks;            /* ranks of the communicator the last sph_render_handle frame was composited over (1: not sharded) */
+    int32_t hops;             /* hops of the chain this rank sent or received in */
+    int64_t pieces_sent, pieces_recv;   /* messages (each at most the transport's message capacity) */
+    int64_t bytes_sent, bytes_recv;
+    int64_t drawn_global;     /* SphRenderStats.drawn summed over the ranks */
+    double ms_composite;      /* HIP events: from this rank's first send or receive to the end of its last merge (or send) */
+} SphRenderCompositeStats;
+int sph_render_composite_stats(SphRender *r, SphRenderCompositeStats *out);
 
 /* --- mesh rendering: an ordered list of triangle meshes -> one RGB frame ------------------------------------------ */
 /* stands in for the reference's render.py + rendering_script.py (every .obj of a frame directory through a Blender scene ->

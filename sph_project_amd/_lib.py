@@ -137,6 +137,13 @@ class SphRenderStats(C.Structure):
     ]
 
 
+class SphRenderCompositeStats(C.Structure):
+    _fields_ = [
+        ("ranks", C.c_int32), ("hops", C.c_int32), ("pieces_sent", C.c_int64), ("pieces_recv", C.c_int64),
+        ("bytes_sent", C.c_int64), ("bytes_recv", C.c_int64), ("drawn_global", C.c_int64), ("ms_composite", C.c_double),
+    ]
+
+
 class SphRenderMeshStats(C.Structure):
     _fields_ = [
         ("meshes", C.c_int64), ("triangles", C.c_int64), ("vertices", C.c_int64), ("large", C.c_int64),
@@ -249,6 +256,7 @@ _SIGNATURES = [
     ("sph_voxelize_mesh", C.c_int, [_VP, C.c_int, _VP, C.c_int, C.c_double, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     ("sph_points_in_mesh", C.c_int, [_VP, C.c_int, _VP, C.c_int] + [_VP, C.c_int] * 3 + [_VP]),
     ("sph_write_ply_ascii", C.c_int, [C.c_char_p, _VP, C.c_int64]),
+    ("sph_write_ply_ascii_part", C.c_int, [C.c_char_p, _VP, C.c_int64, C.c_int64, C.c_int]),
     ("sph_format_f32", C.c_int, [C.c_float, C.c_char_p]),
     ("sph_write_obj_ascii", C.c_int, [C.c_char_p, _VP, C.c_int64, _VP, _VP, C.c_int64]),
     ("sph_surface_create", C.c_int, [C.POINTER(SphSurfaceParams), C.POINTER(_VP)]),
@@ -269,6 +277,9 @@ _SIGNATURES = [
     ("sph_render_handle", C.c_int, [_VP, _VP, C.c_uint32]),
     ("sph_render_download", C.c_int, [_VP, _VP, _VP]),
     ("sph_render_stats", C.c_int, [_VP, C.POINTER(SphRenderStats)]),
+    ("sph_render_layer_download", C.c_int, [_VP, _VP, _VP]),
+    ("sph_render_layer_merge", C.c_int, [_VP, _VP, _VP]),
+    ("sph_render_composite_stats", C.c_int, [_VP, C.POINTER(SphRenderCompositeStats)]),
     ("sph_render_mesh_begin", C.c_int, [_VP]),
     ("sph_render_mesh_add", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP]),
     ("sph_render_mesh_add_surface", C.c_int, [_VP, _VP, _VP]),

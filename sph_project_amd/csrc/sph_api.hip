@@ -1334,6 +1334,11 @@ extern "C" int sph_write_ply_ascii(const char *path, const float *xyz, int64_t n
     const int rc = sphexp::write_ply_ascii(path, xyz, n);
     return rc == 0 ? SPH_OK : (rc == -1 ? SPH_ERR_INVALID : SPH_ERR_UNSUPPORTED);
 }
+// the same file written in parts (sharded scenes: one part per rank, in rank order)
+extern "C" int sph_write_ply_ascii_part(const char *path, const float *xyz, int64_t n, int64_t n_total, int first) {
+    const int rc = sphexp::write_ply_ascii_part(path, xyz, n, n_total, first);
+    return rc == 0 ? SPH_OK : (rc == -1 ? SPH_ERR_INVALID : SPH_ERR_UNSUPPORTED);
+}
 // the OBJ of a reconstructed surface (splashsurf's output in surface_reconstruction.py:8)
 extern "C" int sph_write_obj_ascii(const char *path, const float *vertices, int64_t nv, const float *normals_or_NULL, const int32_t *triangles,
                                    int64_t nt) {

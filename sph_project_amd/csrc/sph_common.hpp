@@ -584,6 +584,8 @@ struct Launch {
     // particle rendering (sph_render.hpp)
     void (*render_splat)(RenderDev &);          // depth keys of spheres (small per thread, large per workgroup) and box lines
     void (*render_shade)(RenderDev &);          // the winners' colours, then background / ids / covered count per pixel
+    void (*render_merge)(RenderDev &, const unsigned long long *, const unsigned char *);   // another layer's keys and colours folded in
+    void (*render_finish)(RenderDev &);         // background / ids / covered count per pixel once more (after merges)
     // mesh rendering (sph_render_mesh.hpp)
     void (*render_mesh_depth)(RenderDev &, MeshDev &);   // depth keys of triangles (small per thread, large per workgroup) and box lines
     void (*render_mesh_shade)(RenderDev &, MeshDev &);   // the winners' colours (triangles, lines)

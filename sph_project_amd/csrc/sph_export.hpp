@@ -48,12 +48,14 @@ static inline int format_f32(float v, char *out) {
     return (int)(p - out);
 }
 
-static int write_ply_ascii(const char *path, const float *xyz, int64_t n) {
-    if (!path || n < 0 || (n > 0 && !xyz)) return -1;
-    FILE *f = fopen(path, "wb");
+// one part of a PLY: first != 0 truncates the file and writes the header for n_total vertices before this part's n rows, else the rows
+// are appended.  Parts in any split give the bytes of the one-shot writer (first = 1, n_total = n).
+static int write_ply_ascii_part(const char *path, const float *xyz, int64_t n, int64_t n_total, int first) {
+    if (!path || n < 0 || n_total < 0 || n > n_total || (n > 0 && !xyz)) return -1;
+    FILE *f = fopen(path, first ? "wb" : "ab");
     if (!f) return -2;
     int rc = 0;
-    if (fprintf(f, "ply\nformat ascii 1.0\ncomment created by PLYWriter\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\nend_header\n", (long long)n) < 0) rc = -3;
+    if (first && fprintf(f, "ply\nformat ascii 1.0\ncomment created by PLYWriter\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\nend_header\n", (long long)n_total) < 0) rc = -3;
     std::vector<char> buf(1 << 20);
     size_t used = 0;
     for (int64_t i = 0; i < n && rc == 0; ++i) {
@@ -65,6 +67,8 @@ static int write_ply_ascii(const char *path, const float *xyz, int64_t n) {
     if (fclose(f) != 0 && rc == 0) rc = -3;
     return rc;
 }
+
+static int write_ply_ascii(const char *path, const float *xyz, int64_t n) { return write_ply_ascii_part(path, xyz, n, n, 1); }
 
 // one reconstructed surface as ASCII OBJ: "v x y z" per vertex, "vn x y z" per normal, "f a//a b//b c//c" (1-based; "f a b c" without
 // normals) per triangle, numbers as format_f32

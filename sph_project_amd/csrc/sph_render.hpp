@@ -239,6 +239,45 @@ __global__ void __launch_bounds__(256) k_render_finish(RenderDev d) {
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(&d.cnt[4], (unsigned long long)__popcll(c));
 }
 
+// Sort-last compositing: another layer of the same frame -- key and rgb planes of a renderer with the same parameters, drawn
+// from other particles -- folded into this one: per pixel the smaller key wins and brings its colour.  Pure streaming, so every lane
+// takes four pixels: two 16-byte key loads and one 12-byte rgb load per side, the colours chosen by byte masks, stores only where
+// something changed.  The last lane walks the W H % 4 pixels of the tail one by one.
+struct RenderRgb4 { unsigned a, b, c; };   // 4 pixels x 3 channels
+
+__global__ void __launch_bounds__(256) k_render_merge(RenderDev d, const unsigned long long *__restrict__ key_in,
+                                                      const unsigned char *__restrict__ rgb_in) {
+    const size_t px = (size_t)d.W * d.H, groups = px >> 2;
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g < groups) {
+        ulonglong2 *mk = (ulonglong2 *)d.key + 2 * g;
+        const ulonglong2 *ik = (const ulonglong2 *)key_in + 2 * g;
+        ulonglong2 m0 = mk[0], m1 = mk[1];
+        const ulonglong2 i0 = ik[0], i1 = ik[1];
+        const bool t0 = i0.x < m0.x, t1 = i0.y < m0.y, t2 = i1.x < m1.x, t3 = i1.y < m1.y;
+        if (!(t0 || t1 || t2 || t3)) return;
+        if (t0 || t1) { if (t0) m0.x = i0.x; if (t1) m0.y = i0.y; mk[0] = m0; }
+        if (t2 || t3) { if (t2) m1.x = i1.x; if (t3) m1.y = i1.y; mk[1] = m1; }
+        RenderRgb4 *mc = (RenderRgb4 *)d.rgb + g;
+        const RenderRgb4 in = ((const RenderRgb4 *)rgb_in)[g];
+        RenderRgb4 c = *mc;
+        // bytes 0-2 pixel 0, 3-5 pixel 1, 6-8 pixel 2, 9-11 pixel 3
+        const unsigned ma = (t0 ? 0x00ffffffu : 0u) | (t1 ? 0xff000000u : 0u);
+        const unsigned mb = (t1 ? 0x0000ffffu : 0u) | (t2 ? 0xffff0000u : 0u);
+        const unsigned mcw = (t2 ? 0x000000ffu : 0u) | (t3 ? 0xffffff00u : 0u);
+        c.a = (c.a & ~ma) | (in.a & ma);
+        c.b = (c.b & ~mb) | (in.b & mb);
+        c.c = (c.c & ~mcw) | (in.c & mcw);
+        *mc = c;
+    } else if (g == groups) {
+        for (size_t p = groups << 2; p < px; ++p)
+            if (key_in[p] < d.key[p]) {
+                d.key[p] = key_in[p];
+                d.rgb[3 * p] = rgb_in[3 * p]; d.rgb[3 * p + 1] = rgb_in[3 * p + 1]; d.rgb[3 * p + 2] = rgb_in[3 * p + 2];
+            }
+    }
+}
+
 static void l_render_splat(RenderDev &d) {
     if (d.n > 0) {
         hipLaunchKernelGGL(k_render_small<false>, dim3(cdiv(d.n, 256)), dim3(256), 0, d.stream, d);
@@ -256,9 +295,22 @@ static void l_render_shade(RenderDev &d) {
     hipLaunchKernelGGL(k_render_finish, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, d.stream, d);
 }
 
+// a layer folded in (both planes complete on the stream before the call); l_render_finish afterwards: the per-pixel pass of l_render_shade
+// once more -- it leaves the colour of every keyed pixel alone, rewrites background and ids, and ADDS to cnt[4], which the caller clears
+static void l_render_merge(RenderDev &d, const unsigned long long *key_in, const unsigned char *rgb_in) {
+    const size_t px = (size_t)d.W * d.H, lanes = (px >> 2) + ((px & 3) ? 1 : 0);
+    hipLaunchKernelGGL(k_render_merge, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, d.stream, d, key_in, rgb_in);
+}
+static void l_render_finish(RenderDev &d) {
+    const size_t px = (size_t)d.W * d.H;
+    hipLaunchKernelGGL(k_render_finish, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, d.stream, d);
+}
+
 static void register_render_launchers(Launch &L) {
     L.render_splat = l_render_splat;
     L.render_shade = l_render_shade;
+    L.render_merge = l_render_merge;
+    L.render_finish = l_render_finish;
 }
 
 #include "sph_render_mesh.hpp"

@@ -5,14 +5,18 @@
 #include <climits>
 
 // the frame buffers, the particle list (large: also the mesh frames' triangle list) and the mesh lists
-enum RendBufId { RB_KEY, RB_RGB, RB_IDS, RB_CNT, RB_LARGE, RB_POS, RB_IDV, RB_COL, RB_MVERT, RB_MNRM, RB_MTRI, RB_MREC, RB_COUNT_ };
+// and an incoming layer
+enum RendBufId { RB_KEY, RB_RGB, RB_IDS, RB_CNT, RB_LARGE, RB_POS, RB_IDV, RB_COL, RB_MVERT, RB_MNRM, RB_MTRI, RB_MREC, RB_LKEY, RB_LRGB, RB_COUNT_ };
 
 struct SphRender : DevObj {   // clk[0]: a particle frame's stages, clk[1]: a mesh frame's
     SphRenderParams prm;
     RenderDev d{};
     DevBuf buf[RB_COUNT_];
     bool have_frame = false;
+    bool mesh_frame = false;      // the frame is a mesh frame: it has no layer (triangle indices do not compose)
+    bool frame_elsewhere = false; // the last frame was composited over a communicator and lies on rank 0, not here
     SphRenderStats stats{};
+    SphRenderCompositeStats cstats{};
     // mesh frames: the list between mesh_begin and mesh_end, concatenated on the device
     bool mesh_open = false;
     std::vector<MeshRec> mesh_rec;
@@ -177,10 +181,130 @@ static int rend_run(SphRender *r, int64_t n_in) {
     HIPCHK(r, k.mark(3));
     unsigned long long c[8];
     { int rc = rend_close(r, c); if (rc) return rc; }
+    r->mesh_frame = false;
     SphRenderStats &o = r->stats;
     o.particles = n_in; o.drawn = (int64_t)c[0]; o.skipped_nonfinite = (int64_t)c[1]; o.large = (int64_t)c[2]; o.atomics = (int64_t)c[3];
     o.covered_pixels = (int64_t)c[4];
     o.ms_input = k.ms(0, 1); o.ms_splat = k.ms(1, 2); o.ms_shade = k.ms(2, 3); o.ms_total = k.ms(0, 3);
+    r->cstats = SphRenderCompositeStats{};
+    r->cstats.ranks = 1; r->cstats.drawn_global = o.drawn;
+    return SPH_OK;
+}
+
+// --- layers: the key and rgb planes of a particle frame, and another renderer's folded into this one ----------------------
+static int rend_layer_room(SphRender *r) {
+    const size_t px = (size_t)r->d.W * r->d.H;
+    int rc = r->buf[RB_LKEY].reserve(r, px * 8);
+    if (!rc) rc = r->buf[RB_LRGB].reserve(r, px * 3);
+    return rc;
+}
+
+// the incoming layer (complete in RB_LKEY / RB_LRGB before the call) folded in on the renderer's stream
+static void rend_merge_incoming(SphRender *r) {
+    r->L->render_merge(r->d, (const unsigned long long *)r->buf[RB_LKEY].p, (const unsigned char *)r->buf[RB_LRGB].p);
+}
+
+// after merges: background, id image and the covered-pixel count of the merged frame; synchronous
+static int rend_refinish(SphRender *r) {
+    HIPCHK(r, hipMemsetAsync(r->d.cnt + 4, 0, sizeof(unsigned long long), r->stream));
+    r->L->render_finish(r->d);
+    unsigned long long c[8];
+    { int rc = rend_close(r, c); if (rc) return rc; }
+    r->stats.covered_pixels = (int64_t)c[4];
+    return SPH_OK;
+}
+
+static int rend_layer_check(SphRender *r, const char *who) {
+    if (!r->have_frame)
+        return fail(r, SPH_ERR_INVALID, r->frame_elsewhere ? "%s: the composited frame lies on rank 0, this rank holds none" : "%s: no frame has been rendered yet", who);
+    if (r->mesh_frame) return fail(r, SPH_ERR_INVALID, "%s: the last frame is a mesh frame (triangle indices do not compose: layers are particle frames)", who);
+    return SPH_OK;
+}
+
+extern "C" int sph_render_layer_download(SphRender *r, uint64_t *key, uint8_t *rgb) {
+    if (!r || !key || !rgb) return SPH_ERR_INVALID;
+    { int rc = rend_layer_check(r, "sph_render_layer_download"); if (rc) return rc; }
+    HIPCHK(r, hipSetDevice(r->device));
+    const size_t px = (size_t)r->d.W * r->d.H;
+    HIPCHK(r, hipMemcpy(key, r->d.key, px * 8, hipMemcpyDeviceToHost));
+    HIPCHK(r, hipMemcpy(rgb, r->d.rgb, px * 3, hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
+
+extern "C" int sph_render_layer_merge(SphRender *r, const uint64_t *key, const uint8_t *rgb) {
+    if (!r || !key || !rgb) return SPH_ERR_INVALID;
+    { int rc = rend_layer_check(r, "sph_render_layer_merge"); if (rc) return rc; }
+    HIPCHK(r, hipSetDevice(r->device));
+    { int rc = rend_layer_room(r); if (rc) return rc; }
+    const size_t px = (size_t)r->d.W * r->d.H;
+    HIPCHK(r, hipMemcpyAsync(r->buf[RB_LKEY].p, key, px * 8, hipMemcpyHostToDevice, r->stream));
+    HIPCHK(r, hipMemcpyAsync(r->buf[RB_LRGB].p, rgb, px * 3, hipMemcpyHostToDevice, r->stream));
+    rend_merge_incoming(r);
+    return rend_refinish(r);   // (synchronous: the caller's arrays are free again)
+}
+
+extern "C" int sph_render_composite_stats(SphRender *r, SphRenderCompositeStats *out) {
+    if (!r || !out) return SPH_ERR_INVALID;
+    *out = r->cstats;
+    return SPH_OK;
+}
+
+// Sort-last compositing down the rank chain: this rank's frame is drawn (rend_run: the renderer's stream is idle).  Hop k
+// moves the layer of rank nranks-1-k to rank nranks-2-k, which folds it into its own and passes the result on in hop k+1; rank 0 ends
+// with the frame.  Transport: comm_exchange (mailboxes or RCCL send / recv on the handle's stream), pieces of at most the mailbox
+// capacity out of / into the renderer's device buffers.  Every rank makes the same sequence of calls -- empty-handed where a hop is not
+// its own -- which is what keeps the mailboxes' message numbers in step.  The two streams are ordered on the host: the renderer's is
+// drained before the handle's stream (or the mailbox copy) reads its planes, the handle's (bounded) before the merge reads the incoming
+// planes.
+static int rend_composite(SphRender *r, SphHandle *h) {
+    SlabComm &c = h->comm;
+    SphRenderCompositeStats &cs = r->cstats;
+    cs = SphRenderCompositeStats{};
+    cs.ranks = c.nranks;
+    r->have_frame = false;   // (rend_run's: this rank's layer alone, not a frame before the chain is through)
+    const size_t px = (size_t)r->d.W * r->d.H;
+    const size_t plane[2] = {px * 8, px * 3};
+    const size_t cap = c.kind == 2 ? (size_t)c.mbox_cap : ((size_t)16 << 20);
+    if (cap == 0) return fail(r, SPH_ERR_COMM, "sph_render_handle: the communicator has no message capacity");
+    if (c.nranks > 1) { int rc = rend_layer_room(r); if (rc) return rc; }
+    bool started = false;   // stage mark 4: this rank's first exchange, 5: behind its last merge
+    for (int hop = 0; hop < c.nranks - 1; ++hop) {
+        const int src = c.nranks - 1 - hop, dst = src - 1;
+        const bool sending = c.rank == src, receiving = c.rank == dst;
+        if (c.kind == 1 && !sending && !receiving) continue;   // (RCCL send / recv carries no message numbers)
+        if (sending || receiving) cs.hops += 1;
+        char *out[2] = {(char *)r->d.key, (char *)r->d.rgb};
+        char *in[2] = {(char *)r->buf[RB_LKEY].p, (char *)r->buf[RB_LRGB].p};
+        if (!started) { HIPCHK(r, r->clk[0].mark(4)); started = true; }
+        for (int pl = 0; pl < 2; ++pl)
+            for (size_t off = 0; off < plane[pl]; off += cap) {
+                const size_t nb = std::min(cap, plane[pl] - off);
+                const void *send[2] = {sending ? out[pl] + off : nullptr, nullptr};       // down
+                void *recv[2] = {nullptr, receiving ? in[pl] + off : nullptr};           // from above
+                const size_t bs[2] = {sending ? nb : 0, 0};
+                size_t br[2] = {0, receiving ? nb : 0};
+                int rc = comm_exchange(h, send, bs, recv, br, true);
+                if (!rc && c.kind == 1) rc = stream_sync_bounded(h, "layer exchange over RCCL");
+                if (rc) return fail(r, rc, "sph_render_handle: layer exchange (hop %d): %s", hop, last_error(h));
+                if (sending) { cs.pieces_sent += 1; cs.bytes_sent += (int64_t)nb; }
+                if (receiving) { cs.pieces_recv += 1; cs.bytes_recv += (int64_t)nb; }
+            }
+        if (receiving) {
+            rend_merge_incoming(r);
+            HIPCHK(r, hipStreamSynchronize(r->stream));   // merged before the next hop reads the planes (or finish counts them)
+        }
+    }
+    if (started) {
+        HIPCHK(r, r->clk[0].mark(5));
+        HIPCHK(r, hipStreamSynchronize(r->stream));
+        cs.ms_composite = r->clk[0].ms(4, 5);
+    }
+    double drawn = (double)r->stats.drawn;
+    { int rc = sph_comm_allreduce(h, &drawn, 1, 0); if (rc) return fail(r, rc, "sph_render_handle: %s", last_error(h)); }
+    cs.drawn_global = (int64_t)drawn;
+    if (c.rank != 0) { r->have_frame = false; r->frame_elsewhere = true; return SPH_OK; }
+    if (c.nranks > 1) return rend_refinish(r);
+    r->have_frame = true;
     return SPH_OK;
 }
 
@@ -191,7 +315,7 @@ extern "C" int sph_render_points(SphRender *r, const float *xyz, const uint8_t *
         for (int64_t i = 0; i < n; ++i)
             if (ids_or_NULL[i] >= RENDER_LINE_ID0) return fail(r, SPH_ERR_INVALID, "sph_render_points: id %u >= 0xFFFFFFF0 (reserved)", ids_or_NULL[i]);
     HIPCHK(r, hipSetDevice(r->device));
-    r->have_frame = false;
+    r->have_frame = false; r->frame_elsewhere = false;
     r->stats = SphRenderStats{};
     { int rc = rend_room(r, (size_t)n, true); if (rc) return rc; }
     std::vector<float4> p4((size_t)n);
@@ -215,15 +339,21 @@ extern "C" int sph_render_points(SphRender *r, const float *xyz, const uint8_t *
 
 extern "C" int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mask) {
     if (!r || !h) return SPH_ERR_INVALID;
-    if (h->st.slab_active || h->swap_axis)
-        return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_handle: sharded handle (render each rank's download instead)");
+    if (h->swap_axis)
+        return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_handle: the handle's library frame is a permutation of the scene's (SPH_SLAB_LAYOUT=slow): not rendered");
     if (h->device != r->device) return fail(r, SPH_ERR_INVALID, "sph_render_handle: handle on device %d, renderer on %d", h->device, r->device);
     if (h->in_step) return fail(r, SPH_ERR_INVALID, "sph_render_handle: between sph_step_begin and sph_step_end");
     HIPCHK(r, hipSetDevice(r->device));
-    r->have_frame = false;
+    r->have_frame = false; r->frame_elsewhere = false;
     r->stats = SphRenderStats{};
     State &s = h->st;
     RenderDev &d = r->d;
+    const bool sharded = s.slab_active != 0;
+    if (sharded && !h->n_exact) {   // asynchronous steps are settled first, as sph_synchronize does
+        HIPCHK(r, hipSetDevice(h->device));
+        const int rc = slab_settle(h);
+        if (rc) return fail(r, rc, "sph_render_handle: %s", last_error(h));
+    }
     // colours as sph_download(SPH_F_COLOR) reads them: at home by particle id while the ids are the append order, else the sorted copy
     d.col_home = nullptr; d.col = nullptr;
     if (s.color_home && s.color_home_ok) d.col_home = s.color_home;
@@ -233,12 +363,15 @@ extern "C" int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mas
     { int rc = rend_room(r, (size_t)n, false); if (rc) return rc; }
     HIPCHK(r, r->clk[0].mark(0));
     d.n = n; d.pos = s.posv.cur(); d.meta = s.meta.cur(); d.id = s.pid.cur(); d.mask = object_mask;
-    return rend_run(r, n);
+    { int rc = rend_run(r, n); if (rc || !sharded) return rc; }
+    return rend_composite(r, h);   // collective: every rank of the communicator is here with the same renderer parameters and mask
 }
 
 extern "C" int sph_render_download(SphRender *r, uint8_t *rgb, int32_t *ids_or_NULL) {
     if (!r || !rgb) return SPH_ERR_INVALID;
-    if (!r->have_frame) return fail(r, SPH_ERR_INVALID, "sph_render_download: no frame has been rendered yet");
+    if (!r->have_frame)
+        return fail(r, SPH_ERR_INVALID, r->frame_elsewhere ? "sph_render_download: the composited frame lies on rank 0, this rank holds none"
+                                                           : "sph_render_download: no frame has been rendered yet");
     HIPCHK(r, hipSetDevice(r->device));
     const size_t px = (size_t)r->d.W * r->d.H;
     HIPCHK(r, hipMemcpy(rgb, r->d.rgb, px * 3, hipMemcpyDeviceToHost));
@@ -335,8 +468,9 @@ extern "C" int sph_render_mesh_end(SphRender *r) {
     if (!r->mesh_open) return fail(r, SPH_ERR_INVALID, "sph_render_mesh_end: no sph_render_mesh_begin before it");
     r->mesh_open = false;
     HIPCHK(r, hipSetDevice(r->device));
-    r->have_frame = false;
+    r->have_frame = false; r->frame_elsewhere = false;
     r->stats = SphRenderStats{};
+    r->cstats = SphRenderCompositeStats{};
     r->mstats = SphRenderMeshStats{};
     const size_t nm = r->mesh_rec.size();
     { int rc = rend_room(r, (size_t)r->mesh_nt, false); if (rc) return rc; }
@@ -360,6 +494,7 @@ extern "C" int sph_render_mesh_end(SphRender *r) {
     HIPCHK(r, k.mark(4));
     unsigned long long c[8];
     { int rc = rend_close(r, c); if (rc) return rc; }
+    r->mesh_frame = true;
     SphRenderMeshStats &o = r->mstats;
     o.meshes = (int64_t)nm; o.triangles = r->mesh_nt; o.vertices = r->mesh_nv;
     o.hit = (int64_t)c[0]; o.skipped_nonfinite = (int64_t)c[1]; o.large = (int64_t)c[2]; o.atomics = (int64_t)c[3];

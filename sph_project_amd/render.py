@@ -39,6 +39,7 @@ class FrameRenderer(L.NativeObject):
         self._handles = {}   # box (None or (lo, hi)) -> native renderer
         self._last = None
         self._last_kind = None      # "points" or "meshes": what the last frame was drawn from
+        self._stats_of = None       # the native renderer of the last from_container call (composite_stats on every rank)
         self._mesh_starts = None    # first global triangle index of each mesh of the last mesh frame (and the total)
 
     def _params(self, box):
@@ -67,7 +68,7 @@ class FrameRenderer(L.NativeObject):
     def close(self):
         super().close()
         self._handles = {}
-        self._last = None
+        self._last = self._stats_of = None
 
     def _download(self, h):
         rgb = np.empty((self.height, self.width, 3), np.uint8)
@@ -102,7 +103,10 @@ class FrameRenderer(L.NativeObject):
     def from_container(self, container, hide=(), download=True):
         """uint8 (H, W, 3) of a live container's visible objects (object_visibility == 1, minus `hide`), drawn from the device state
         with their persistent ids and colours; box: [0, domainEnd] as in the reference unless the renderer was made with box=False
-        (or with a box of its own).  download=False: None is returned and the frame stays on the device."""
+        (or with a box of its own).  download=False: None is returned and the frame stays on the device.
+        A sharded container (slab=...) makes the call collective: every rank calls it with the same arguments, the
+        layers are composited down the rank chain, and rank 0 gets the frame of the whole scene; the other ranks get None and hold no
+        frame (has_frame() is False there)."""
         engine = getattr(container, "engine", container)
         vis = np.asarray(container.object_visibility)
         mask = 0
@@ -113,9 +117,51 @@ class FrameRenderer(L.NativeObject):
         if box is None:
             box = (np.zeros(3), np.asarray(container.domain_end, dtype=np.float64))
         h = self._native(box if box is not False else None)
+        self._last = self._last_kind = None
         self._chk(self.lib.sph_render_handle(h, engine.h, C.c_uint32(mask)), "sph_render_handle", h)
+        self._stats_of = h
+        slab = getattr(container, "slab", None)
+        if slab and slab["rank"] != 0:
+            return None   # the frame lies on rank 0
         self._last_kind = "points"
         return self._frame(h, download)
+
+    def has_frame(self):
+        """True when this renderer holds a frame (after a composited from_container: on rank 0 only)."""
+        return self._last is not None
+
+    def layer(self):
+        """(key uint64 (H, W), rgb uint8 (H, W, 3)) of the last particle frame: per pixel float_bits(t) << 32 | id of the
+        winner (2^64 - 1 where nothing was drawn) and the colour."""
+        if self._last is None:
+            raise RenderError("layer: no frame rendered yet", L.ERR_INVALID)
+        key = np.empty((self.height, self.width), np.uint64)
+        rgb = np.empty((self.height, self.width, 3), np.uint8)
+        self._chk(self.lib.sph_render_layer_download(self._last, key.ctypes.data, rgb.ctypes.data), "sph_render_layer_download", self._last)
+        return key, rgb
+
+    def merge_layer(self, key, rgb):
+        """The layer of another renderer with the same parameters (disjoint particles, distinct ids) folded into the last particle
+        frame: per pixel the smaller key wins.  Returns the merged frame, uint8 (H, W, 3)."""
+        k = np.ascontiguousarray(key, dtype=np.uint64)
+        c = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if k.shape != (self.height, self.width) or c.shape != (self.height, self.width, 3):
+            raise ValueError(f"merge_layer: expected key {(self.height, self.width)} and rgb {(self.height, self.width, 3)}, "
+                             f"got {k.shape} and {c.shape}")
+        if self._last is None:
+            raise RenderError("merge_layer: no frame rendered yet", L.ERR_INVALID)
+        self._chk(self.lib.sph_render_layer_merge(self._last, k.ctypes.data, c.ctypes.data), "sph_render_layer_merge", self._last)
+        return self._download(self._last)
+
+    def composite_stats(self):
+        """Of the last from_container call (every rank has them): ranks, hops, pieces and bytes sent / received, drawn_global,
+        ms_composite."""
+        h = getattr(self, "_stats_of", None) or self._last
+        if h is None:
+            raise RenderError("composite_stats: no frame rendered yet", L.ERR_INVALID)
+        st = L.SphRenderCompositeStats()
+        self._chk(self.lib.sph_render_composite_stats(h, C.byref(st)), "sph_render_composite_stats", h)
+        return L.struct_dict(st)
 
     def from_meshes(self, meshes, download=True):
         """uint8 (H, W, 3) of an ordered list of triangle meshes: each item is (vertices f32[nv, 3], triangles i32[nt, 3],
@@ -157,6 +203,8 @@ class FrameRenderer(L.NativeObject):
     def last_rgb(self):
         """uint8 (H, W, 3) of the last frame once more."""
         if self._last is None:
+            if self._stats_of is not None:   # a composited frame: the native call says where it lies
+                return self._download(self._stats_of)
             raise RenderError("last_rgb: no frame rendered yet", L.ERR_INVALID)
         return self._download(self._last)
 

@@ -11,7 +11,9 @@ renderer of render.py with --render (its own image, not GGUI's: DESIGN.md 15); w
 writes {cnt:06}/render.png, the frame's meshes drawn on the GPU, where the reference's render.py needs Blender.  --video
 adds {out}/raw_view.avi / {out}/render.avi, the same frames as Motion-JPEG compressed on the GPU (make_video.py).
 --png_device writes the PNG files from the device image as well (DESIGN.md 21): no pixel is downloaded, no zlib runs on the host;
---png_coding dynamic makes those files smaller (dynamic Huffman blocks) for a slower encode."""
+--png_coding dynamic makes those files smaller (dynamic Huffman blocks) for a slower encode.
+--gpus N shards the scene over N ranks (z-slabs, one process each, started by launch.py): the frames are composited over the ranks
+ and written by rank 0, the PLY of a fluid object is written in rank order, one part per rank."""
 import argparse
 import os
 import sys
@@ -48,6 +50,24 @@ def write_ply_ascii(path, pos):
     with open(path, "w") as f:
         f.write(f"ply\nformat ascii 1.0\ncomment {PLY_COMMENT}\n")
         f.write(f"element vertex {pos.shape[0]}\nproperty float x\nproperty float y\nproperty float z\nend_header\n")
+        if pos.shape[0]:
+            f.write(" \n".join(map(" ".join, pos.astype(str).tolist())) + " \n")
+
+
+def write_ply_ascii_part(path, pos, n_total, first):
+    """One part of the file write_ply_ascii makes of the concatenated parts: first truncates and writes the header for n_total
+    vertices, then (either way) this part's rows are appended."""
+    pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+    if not os.environ.get("SPH_PLY_PYTHON"):
+        from sph_project_amd import _lib
+        rc = _lib.load().sph_write_ply_ascii_part(os.fsencode(path), pos.ctypes.data, pos.shape[0], int(n_total), int(bool(first)))
+        if rc != 0:
+            raise OSError(f"sph_write_ply_ascii_part({path!r}) failed ({rc})")
+        return
+    with open(path, "w" if first else "a") as f:
+        if first:
+            f.write(f"ply\nformat ascii 1.0\ncomment {PLY_COMMENT}\n")
+            f.write(f"element vertex {int(n_total)}\nproperty float x\nproperty float y\nproperty float z\nend_header\n")
         if pos.shape[0]:
             f.write(" \n".join(map(" ".join, pos.astype(str).tolist())) + " \n")
 
@@ -108,7 +128,14 @@ def parse_args(argv=None):
     parser.add_argument("--png_coding", default=None, choices=["fixed", "dynamic"],
                         help="with --png_device: the entropy coding of the files (DESIGN.md 21).  fixed (the default): the fixed Huffman "
                              "code; dynamic: per segment a dynamic Huffman block where it is shorter -- smaller files, a slower encode")
+    parser.add_argument("--gpus", type=int, default=1,
+                        help="shard the scene over this many ranks, one process and (unless SPH_COMM_TRANSPORT names a shared-memory "
+                             "transport) one GPU each; frames are composited on rank 0 (DESIGN.md 22)")
     args = parser.parse_args(argv)
+    if args.gpus < 1:
+        parser.error(f"--gpus {args.gpus}: at least one rank is needed")
+    if args.gpus > 1:
+        check_sharded_args(parser, args)
     if args.png_device and not (args.render or args.render_meshes):
         parser.error("--png_device compresses a renderer's frames: give --render and / or --render_meshes as well")
     if args.png_coding is not None and not args.png_device:
@@ -117,6 +144,27 @@ def parse_args(argv=None):
     if args.video and not (args.render or args.render_meshes):
         parser.error("--video takes its frames from a renderer: give --render and / or --render_meshes as well")
     return args
+
+
+def check_sharded_args(parser, args):
+    """What --gpus N > 1 cannot do, said before any rank is started (no GPU is opened here)."""
+    n = args.gpus
+    if args.reconstruct or args.render_meshes:
+        parser.error(f"--gpus {n}: --reconstruct / --render_meshes need the whole fluid on one device (surface reconstruction of a "
+                     "sharded scene is not supported); run them with --gpus 1")
+    backend = args.rigid_backend or os.environ.get("SPH_RIGID_BACKEND") or "native"
+    if backend in ("device", "device_contact", "pybullet"):
+        parser.error(f"--gpus {n}: --rigid_backend {backend} integrates the bodies from one device's particles; sharded scenes run the "
+                     "native or contact backend")
+    config = SimConfig(scene_file_path=args.scene_file)
+    method = config.get_cfg("simulationMethod")
+    if method in ("iisph", "pbf"):
+        parser.error(f"--gpus {n}: the {method} solver is not sharded (sph_prepare refuses it on a slab); run it with --gpus 1")
+    from sph_project_amd import launch
+    try:
+        launch.plan_scene_cuts(config.config, n)
+    except ValueError as e:
+        parser.error(f"--gpus {n}: {e}")
 
 
 def surface_postprocess(args):
@@ -147,8 +195,139 @@ def frame_meshes(container, solver, recon, reconstructed=()):
                 yield (posed, np.asarray(container.object_collection[oid]["mesh"].faces), None, colour)
 
 
+METHODS = {"dfsph": (DFSPHContainer, DFSPHSolver), "wcsph": (WCSPHContainer, WCSPHSolver), "pcisph": (PCISPHContainer, PCISPHSolver),
+           "iisph": (IISPHContainer, IISPHSolver), "pbf": (PBFContainer, PBFSolver)}
+
+
+def main_sharded(args, rank, world):
+    """One rank of --gpus N: the scene's z-slab of this rank, the loop arithmetic of main(), collective output frames."""
+    from sph_project_amd import _lib, launch
+    config = SimConfig(scene_file_path=args.scene_file)
+    scene_name = args.scene_file.split("/")[-1].split(".")[0]
+    fps = config.get_cfg("fps") or 60
+    output_interval = int((1.0 / fps) / config.get_cfg("timeStepSize"))
+    total_time = config.get_cfg("totalTime")
+    total_rounds = int((10.0 if total_time is None else total_time) / config.get_cfg("timeStepSize"))
+    if config.get_cfg("outputInterval"):
+        output_interval = config.get_cfg("outputInterval")
+    output_ply = config.get_cfg("exportPly")
+    output_obj = config.get_cfg("exportObj")
+    output_frames = config.get_cfg("exportFrame") and args.render
+    out_dir = args.output_dir or f"{scene_name}_output"
+    os.makedirs(out_dir, exist_ok=True)
+
+    lib = _lib.load()
+    ndev = lib.sph_device_count()
+    if ndev < 1:
+        raise SystemExit("run_simulation: no HIP device visible")
+    if os.environ.get("SPH_COMM_TRANSPORT", "").startswith("shm"):
+        device = rank % ndev   # the shared-memory transports let several ranks share a GPU
+    elif world > ndev:
+        if rank == 0:
+            print(f"run_simulation: --gpus {world} needs one GPU per rank, {ndev} visible (SPH_COMM_TRANSPORT=shm+ipc lets ranks share "
+                  "one)", file=sys.stderr)
+        raise SystemExit(2)
+    else:
+        device = rank
+    uid = launch.exchange_unique_id(lib, rank)
+    cuts = launch.plan_scene_cuts(config.config, world)
+    method = config.get_cfg("simulationMethod")
+    container = METHODS[method][0](config, GGUI=False, rigid_backend=args.rigid_backend, device=device,
+                                   slab=dict(rank=rank, nranks=world, unique_id=uid, cuts=cuts))
+    solver = METHODS[method][1](container)
+    engine = container.engine
+    if rank == 0:
+        print(f"Simulation method: {method} on {world} ranks ({engine.comm_transport()}), slab cuts {cuts}")
+    solver.prepare()
+
+    renderer = encoder = writer = png = None
+    if output_frames:   # every rank draws its slab; the frame is composited on rank 0
+        from sph_project_amd.render import FrameRenderer, write_png
+        renderer = FrameRenderer(container.dx, width=args.render_size[0], height=args.render_size[1], camera_position=args.camera_position,
+                                 camera_lookat=args.camera_lookat, fov=args.camera_fov, device=device)
+        if rank == 0 and args.video:
+            from sph_project_amd.video import AviWriter, VideoEncoder
+            encoder = VideoEncoder(renderer.width, renderer.height, quality=args.video_quality, chroma=args.video_chroma, device=device)
+            writer = AviWriter(f"{out_dir}/raw_view.avi", renderer.width, renderer.height, args.video_fps)
+        if rank == 0 and args.png_device:
+            from sph_project_amd.png import PngEncoder
+            png = PngEncoder(renderer.width, renderer.height, coding=args.png_coding, device=device)
+
+    def owned_global():
+        return int(round(engine.comm_allreduce([engine.comm_get_slab()["n_owned"]])[0]))
+
+    cnt = 0
+    limit = total_rounds if args.max_steps is None else min(total_rounds, args.max_steps)
+    limit = max(limit, 1)
+    t0 = time.perf_counter()
+    t_export, frames = 0.0, 0
+    try:
+        while cnt < limit:   # main()'s arithmetic: the same frames at the same step counts
+            wants_frame = output_ply or output_obj or output_frames
+            nxt = cnt if cnt % output_interval == 0 else cnt + output_interval - cnt % output_interval
+            if not wants_frame or nxt >= limit:
+                solver.advance(limit - cnt)
+                cnt = limit
+                break
+            solver.advance(nxt - cnt + 1)
+            cnt = nxt
+            engine.synchronize()
+            te = time.perf_counter()
+            frame_dir = f"{out_dir}/{cnt:06}"
+            os.makedirs(frame_dir, exist_ok=True)
+            if output_frames:   # collective: every rank calls it, rank 0 holds the frame
+                rgb = renderer.from_container(container, download=png is None)
+                if rank == 0:
+                    if png is not None:
+                        png.write_png(f"{frame_dir}/raw_view.png", renderer)
+                    else:
+                        write_png(f"{frame_dir}/raw_view.png", rgb)
+                    if writer is not None:
+                        writer.add(encoder.encode_last(renderer))
+            if output_ply:   # one file per fluid object: the ranks' owned particles, appended in rank order
+                obj = engine.download(_lib.F_OBJECT_ID)
+                own = engine.download(_lib.F_GHOST) == 0   # (container.dump does not filter the ghosts)
+                pos = engine.download(_lib.F_POSITION)
+                fluid_ids = sorted(container.object_id_fluid_body)
+                totals = engine.comm_allreduce([float(((obj == i) & own).sum()) for i in fluid_ids]) if fluid_ids else []
+                for i, total in zip(fluid_ids, totals):
+                    for r in range(world):
+                        if r == rank:
+                            write_ply_ascii_part(f"{frame_dir}/particle_object_{i}.ply", pos[(obj == i) & own], int(round(total)), r == 0)
+                        engine.comm_barrier()
+            if output_obj and rank == 0:
+                for r_body_id in container.object_id_rigid_body:
+                    if "mesh" not in container.object_collection[r_body_id]:
+                        continue
+                    with open(f"{frame_dir}/mesh_object_{r_body_id}.obj", "w") as f:
+                        f.write(container.object_collection[r_body_id]["mesh"].export(file_type="obj"))
+            frames += 1
+            t_export += time.perf_counter() - te
+            cnt += 1
+        engine.synchronize()
+    finally:
+        if writer is not None:
+            writer.close()
+    n_global = owned_global()
+    dt = time.perf_counter() - t0
+    if rank == 0:
+        print(f"Simulation Finished: {cnt} steps, {n_global} particles on {world} ranks, {1e3 * (dt - t_export) / cnt:.3f} ms/step "
+              f"(+ {t_export:.2f} s writing {frames} frame(s): {1e3 * dt / cnt:.3f} ms/step all in)")
+    return container, solver
+
+
 def main(argv=None):
     args = parse_args(argv)
+    if args.gpus > 1:
+        from sph_project_amd import launch
+        me = launch.rank_of_this_process()
+        if me is None:   # the parent: starts the ranks, opens no GPU
+            rcs = launch.spawn_ranks(sys.argv[1:] if argv is None else list(argv), args.gpus, script=os.path.abspath(__file__))
+            if any(rcs):
+                print(f"run_simulation: rank exit codes {rcs}", file=sys.stderr)
+                raise SystemExit(1)
+            return None
+        return main_sharded(args, me[0], me[1])
     scene_path = args.scene_file
     config = SimConfig(scene_file_path=scene_path)
     scene_name = scene_path.split("/")[-1].split(".")[0]
