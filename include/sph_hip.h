@@ -758,6 +758,66 @@ int sph_png_size(SphPng *v, int64_t *bytes);
 int sph_png_download(SphPng *v, uint8_t *dst);
 int sph_png_stats(SphPng *v, SphPngStats *out);
 
+/* --- Text export: ASCII PLY / OBJ frame files formatted on the device -------------------------------------------- */
+/* stands in for a download followed by sph_write_ply_ascii / sph_write_obj_ascii: the same bytes, made where the particles or the
+   mesh lie.  A source is bound by one call; sph_text_write / sph_text_read then produce the file of that source in pieces of at most
+   piece_rows rows: per piece a count pass (bytes per row), a scan, and a write pass that lays the characters at the scanned offsets
+   (offsets inside a piece fit 32 bits, totals are 64-bit).  Numbers: float32 as the shortest decimal digits that round-trip, laid
+   out as sph_format_f32 does ("nan", "inf", "-0.0", positional with a digit behind the point for 1e-4 <= |v| < 1e16, else
+   d[.ddd]e+XX; at most 19 characters); indices 1-based.  Integer arithmetic only: the same bytes from both builds and from the host
+   writers.  The host writes the PLY header and copies finished pieces from two alternating pinned buffers into the file while the
+   device makes the next piece; device memory is bounded by the source plus piece_rows * (71 + 4) bytes, pinned host memory by
+   2 * 71 * piece_rows.  One HIP stream per object; synchronous calls. */
+typedef struct {
+    int32_t piece_rows;      /* rows per piece, 1..2^22; 0: the default 2^20 */
+    int32_t fast_math;       /* which build's launchers run (0 strict, 1 fast); the bytes are the same */
+    int32_t device;          /* HIP device ordinal, -1: current */
+    int32_t reserved;        /* 0 */
+} SphTextParams;
+
+typedef struct {
+    int64_t rows;            /* lines behind the header */
+    int64_t values;          /* numbers written: 3 per point, vertex and normal; 3 per face, 6 with normals */
+    int64_t bytes;           /* the file, header included */
+    int64_t pieces;
+    int64_t longest_row;     /* bytes, the line feed included */
+    double ms_source;        /* HIP events: upload / compaction of the bound source (~0 for a surface read in place) */
+    double ms_count;         /* the stages of the last write / read / size, summed over the pieces */
+    double ms_scan;
+    double ms_write;
+    double ms_copy;          /* pieces to pinned host memory */
+    double ms_file;          /* host clock: fwrite of the pieces (sph_text_write), memcpy into dst (sph_text_read) */
+    double ms_total;         /* host clock: the whole call */
+} SphTextStats;
+
+typedef struct SphText SphText;
+/* SPH_ERR_INVALID (before any device is touched): piece_rows outside the range, reserved != 0 */
+int sph_text_create(const SphTextParams *params, SphText **out);
+void sph_text_destroy(SphText *t);
+const char *sph_text_last_error(SphText *t);
+/* Sources.  Each call replaces the bound source; a failed call leaves none bound.
+   PLY of host points xyz f32[n][3] (uploaded). */
+int sph_text_ply_points(SphText *t, const float *xyz, int64_t n);
+/* PLY of one object's particles of a live handle, ghosts and dead slots left out, in the handle's current (sorted) order -- the rows
+   of sph_download(SPH_F_POSITION) whose object id matches; compacted on the device by a scan, the handle's state untouched.
+   SPH_ERR_UNSUPPORTED: a sharded handle.  SPH_ERR_INVALID: another device, between sph_step_begin and sph_step_end, a bad id. */
+int sph_text_ply_object(SphText *t, SphHandle *h, int object_id);
+/* OBJ of a host mesh (uploaded): vertices f32[nv][3], normals f32[nv][3] or NULL, triangles i32[nt][3] 0-based.  The indices are
+   checked on the device (0 <= index < nv) before anything is written: SPH_ERR_INVALID, as sph_write_obj_ascii. */
+int sph_text_obj_mesh(SphText *t, const float *vertices, int64_t nv, const float *normals_or_NULL, const int32_t *triangles, int64_t nt);
+/* OBJ of the surface's last mesh (smoothed vertices and normals included), read in place on the device: the surface must not
+   reconstruct again or be destroyed before the file has been produced.  SPH_ERR_INVALID: no mesh yet, another device. */
+int sph_text_obj_surface(SphText *t, SphSurface *surface);
+/* the file of the bound source.  SPH_ERR_INVALID: no source bound; SPH_ERR_UNSUPPORTED: the path cannot be opened or written */
+int sph_text_write(SphText *t, const char *path);
+/* the same bytes in memory: their number (a count-only run), and the file into dst[cap] (SPH_ERR_CAPACITY if it does not fit) */
+int sph_text_size(SphText *t, int64_t *bytes);
+int sph_text_read(SphText *t, void *dst, int64_t cap);
+int sph_text_stats(SphText *t, SphTextStats *out);
+/* the device's number routine run on the host (no device is touched): the n floats' characters back to back in out[cap], their
+   lengths in lengths[n].  For tests of the routine, not a product path.  SPH_ERR_CAPACITY: cap < the sum of the lengths. */
+int sph_text_format_f32_host(const float *values, int64_t n, char *out, int64_t cap, int64_t *lengths);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,19 @@ class SphPngStats(C.Structure):
 
 PNG_CODING_FIXED, PNG_CODING_DYNAMIC = 0, 1
 
+
+class SphTextParams(C.Structure):
+    _fields_ = [("piece_rows", C.c_int32), ("fast_math", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SphTextStats(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64), ("values", C.c_int64), ("bytes", C.c_int64), ("pieces", C.c_int64), ("longest_row", C.c_int64),
+        ("ms_source", C.c_double), ("ms_count", C.c_double), ("ms_scan", C.c_double), ("ms_write", C.c_double), ("ms_copy", C.c_double),
+        ("ms_file", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 # return codes (include/sph_hip.h)
 ERR_INVALID, ERR_CAPACITY = -1, -2
 ERR_UNSUPPORTED = -6
@@ -304,6 +317,18 @@ _SIGNATURES = [
     ("sph_png_size", C.c_int, [_VP, C.POINTER(C.c_int64)]),
     ("sph_png_download", C.c_int, [_VP, _VP]),
     ("sph_png_stats", C.c_int, [_VP, C.POINTER(SphPngStats)]),
+    ("sph_text_create", C.c_int, [C.POINTER(SphTextParams), C.POINTER(_VP)]),
+    ("sph_text_destroy", None, [_VP]),
+    ("sph_text_last_error", C.c_char_p, [_VP]),
+    ("sph_text_ply_points", C.c_int, [_VP, _VP, C.c_int64]),
+    ("sph_text_ply_object", C.c_int, [_VP, _VP, C.c_int]),
+    ("sph_text_obj_mesh", C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64]),
+    ("sph_text_obj_surface", C.c_int, [_VP, _VP]),
+    ("sph_text_write", C.c_int, [_VP, C.c_char_p]),
+    ("sph_text_size", C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    ("sph_text_read", C.c_int, [_VP, _VP, C.c_int64]),
+    ("sph_text_stats", C.c_int, [_VP, C.POINTER(SphTextStats)]),
+    ("sph_text_format_f32_host", C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP]),
     ("sph_comm_allreduce", C.c_int, [_VP, C.POINTER(C.c_double), C.c_int, C.c_int]),
     ("sph_comm_barrier", C.c_int, [_VP]),
     ("sph_comm_selftest", C.c_int, [_VP, C.c_int]),

@@ -335,6 +335,22 @@ struct PngDev {
     unsigned char *side;               // [nseg][PNG_SIDE] coding = dynamic: the count pass's code lengths and choice; nullptr: coding = fixed
 };
 
+// Text export (sph_text_passes.hpp): the rows of an ASCII PLY or OBJ file, one piece of them at a time.
+struct TextDev {
+    int kind;                          // 0: PLY rows "x y z \n"; 1: OBJ rows (v, then vn, then f)
+    const unsigned *xyz;               // [nv][3] the bits of the points (PLY) / vertices (OBJ)
+    const unsigned *nrm;               // [nv][3] normals, or nullptr: no vn rows, faces as "f a b c"
+    const int *tri;                    // [nt][3] 0-based
+    long long nv, nt;
+    long long row0;                    // the piece: rows [row0, row0 + rows) of the file
+    int rows;
+    int *len;                          // [rows + 1] bytes per row -> their exclusive scan, [rows] the piece's bytes (< 2^31)
+    int *scan_tmp;                     // tile sums of the scans
+    int *longest;                      // [1] the longest row so far
+    unsigned char *out;                // the piece's bytes (16-byte aligned)
+    hipStream_t stream;
+};
+
 template <class T> struct DBuf {
     T *b[2] = {nullptr, nullptr};
     int c = 0;
@@ -599,6 +615,12 @@ struct Launch {
     void (*png_count)(PngDev &);                // bytes per segment's chunk (tokens, fixed or stored), the Adler sums
     void (*png_scan)(PngDev &);                 // their exclusive scan, the total behind it; the Adler-32
     void (*png_write)(PngDev &);                // the same bytes again, stored at the scanned offsets, with every chunk's CRC
+    // text export (sph_text_passes.hpp)
+    void (*text_count)(TextDev &);              // bytes per row of the piece, the longest row
+    void (*text_scan)(TextDev &);               // their exclusive scan, the piece's bytes behind it
+    void (*text_write)(TextDev &);              // the rows' characters at the scanned offsets (staged in LDS, aligned 16-byte stores)
+    void (*text_check_tri)(TextDev &, int *bad);   // bad[0] = any triangle index outside [0, nv)
+    void (*text_compact)(TextDev &, const float4 *posv, const int *meta, int n, int obj, int *slot, float *xyz);   // one object's particles, order kept
     void (*layer_hist)(State &, int *hist);      // owned particles per global cell layer
     void (*loop_criterion)(State &, int slot);   // stop test on an all-reduced residual (sharded solver loops)
     // push transport: the step message is written by halo_classify_pack itself; then

@@ -14,6 +14,7 @@
 // every kernel lives in a per-build namespace so the strict and fast objects can be linked together
 #include <vector>
 #include <cstdio>
+#include <cstdint>
 namespace SPH_NS {
 #include "sph_device.hpp"
 #include "sph_halo_defs.hpp"
@@ -466,6 +467,7 @@ void l_clear_fresh(State &s) {
 #include "sph_render.hpp"
 #include "sph_video.hpp"
 #include "sph_png.hpp"
+#include "sph_text_passes.hpp"
 #include "sph_halo_impl.hpp"
 }  // namespace SPH_NS
 
@@ -500,6 +502,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_render_mesh_launchers(L);
         register_video_launchers(L);
         register_png_launchers(L);
+        register_text_launchers(L);
         L.halo_classify_pack = l_halo_classify_pack; L.halo_unpack_append = l_halo_unpack_append;
         L.halo_build_tables = l_halo_build_tables; L.halo_pack_fields = l_halo_pack_fields;
         L.halo_unpack_fields = l_halo_unpack_fields;

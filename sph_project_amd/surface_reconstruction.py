@@ -29,6 +29,8 @@ def parse_args(argv=None):
     parser.add_argument("--mesh-smoothing-weights", choices=["on", "off"], default=None)
     parser.add_argument("--mesh-smoothing-weights-normalization", type=float, default=None)
     parser.add_argument("--normals-smoothing-iters", type=int, default=None)
+    parser.add_argument("--export_device", action="store_true",
+                        help="format the .obj files on the GPU from the device mesh (DESIGN.md 23: the same bytes, no mesh download)")
     return parser.parse_args(argv)
 
 
@@ -64,10 +66,18 @@ def main(argv=None):
     post = postprocess_settings(args)
     if post is not None:
         recon.set_postprocess(**post)
+    exporter = None
+    if args.export_device:
+        from sph_project_amd.text import TextExporter
+        exporter = TextExporter()
     for ply_path, obj_path in jobs:
         try:
-            recon.from_points(read_ply_ascii(ply_path))
-            recon.write_obj(obj_path)
+            if exporter is not None:
+                recon.from_points(read_ply_ascii(ply_path), download=False)
+                exporter.obj_surface(recon).write(obj_path)
+            else:
+                recon.from_points(read_ply_ascii(ply_path))
+                recon.write_obj(obj_path)
         except Exception as e:   # the reference's worker reports a failed frame and goes on
             print(f"failed to process {os.path.dirname(ply_path)}")
             print(e)
