@@ -595,6 +595,58 @@ typedef struct {
 } SphRenderCompositeStats;
 int sph_render_composite_stats(SphRender *r, SphRenderCompositeStats *out);
 
+/* --- screen-space surface mode: a particle frame -> a smoothed, lit liquid surface --------------------------------- */
+/* opt-in second stage of a particle frame, as real-time fluid renderers draw liquids without a mesh.  Surface pixels: those whose
+   winner is a particle of a surface object (handle path: object_mask; points path: the per-point flag).  Depth stage, all integers:
+   q = min((u32)(t * inv_u), 2^24 - 1) with u = radius / 256 and inv_u = 256 / radius rounded to f32 once; `iterations` Jacobi steps
+   q_i' = (sum w q_j + (sum w >> 1)) / sum w over the taps (dx, dy) of the window |dx|, |dy| <= R_i that lie in the frame, are surface
+   pixels and have |q_j - q_i| <= dq; R_i = clamp(Rnum / q_i, 1, rmax) (rmax where q_i = 0), w = (R_i + 1 - |dx|)(R_i + 1 - |dy|),
+   Rnum = round(256 sigma H / (2 tan(fov / 2))), dq = round(256 range).  Colour stage (f32, contraction off: the same bytes in both
+   builds): P = q u (X, Y, 1); per screen axis the one-sided difference towards the surface neighbour with the smaller |dq| (a tie: the
+   + side; none: no difference, and the normal is the direction to the eye); n = normalised cross product turned to the eye;
+   base (ambient + max(n.L, 0) light_rgb) + spec light_rgb max(n.h, 0)^shininess, h the half vector of the directions to the light and
+   to the eye; clamped, floor(255 x + 0.5).  Every other pixel keeps the bytes of the particle frame.  While the mode is on,
+   sph_render_points / _handle also fill the base plane (colour and flag per pixel); sph_render_surface then needs no particle.
+   Not done: thickness / absorption, refraction, the narrow-range filter's one-sided clamp, anti-aliasing, sharded frames. */
+typedef struct {
+    int32_t iterations;       /* 0..64 (3) */
+    int32_t rmax;             /* largest window half-width in pixels, 1..16 (12) */
+    double sigma;             /* smoothing half-width in particle radii, > 0 (1.5); Rnum must stay below 2^31 */
+    double range;             /* depth range of a tap in particle radii, > 0 (2.0); dq in 1..2^24 */
+    double spec;              /* >= 0 (0.35) */
+    double shininess;         /* >= 1 (40) */
+    int64_t object_mask;      /* handle path: bit o = object o is a surface object; -1: the fluid particles of every drawn object */
+} SphRenderSurfaceParams;
+
+typedef struct {
+    int64_t surface_pixels;
+    int64_t iterations;       /* smoothing iterations run */
+    int64_t taps_visited;     /* (2 R_i + 1)^2 summed over surface pixels and iterations */
+    int64_t taps_accepted;    /* of these: in the frame, a surface pixel, within dq */
+    int64_t clamped_rmax;     /* surface pixels whose Rnum / q exceeded rmax in the first iteration */
+    double ms_base;           /* HIP events: the base plane (part of the frame call) */
+    double ms_smooth;         /* quantise and every iteration */
+    double ms_shade;
+} SphRenderSurfaceStats;
+
+#define SPH_RENDER_SURFACE_SENTINEL 0xFFFFFFFFu   /* sph_render_surface_download_depth: not a surface pixel */
+
+/* switches the mode on (params) or off (NULL); applies to the frames drawn afterwards.  SPH_ERR_INVALID, with a message that names the
+   field: iterations outside 0..64, rmax outside 1..16, sigma / range not finite and positive (or too large, see above), spec negative
+   or not finite, shininess below 1 or not finite, object_mask below -1 or above 2^32 - 1. */
+int sph_render_set_surface(SphRender *r, const SphRenderSurfaceParams *params_or_NULL);
+/* the per-point surface flag (u8[n], non-zero = surface) of the NEXT sph_render_points, whose n must equal this n; NULL: every point
+   (the default, restored after that call) */
+int sph_render_points_surface_mask(SphRender *r, const uint8_t *mask_or_NULL, int n);
+/* runs quantise, smooth and shade on the frame last drawn by sph_render_points / _handle and overwrites its rgb in place
+   (sph_render_download, sph_video_encode_render and sph_png_encode_render then see the surface frame; key plane and id image are
+   untouched); synchronous.  SPH_ERR_INVALID: no particle frame held, a mesh frame, the mode off (or switched on after the frame was
+   drawn), a frame changed by sph_render_layer_merge.  SPH_ERR_UNSUPPORTED: the frame was composited from a sharded handle. */
+int sph_render_surface(SphRender *r);
+/* the final integer depth plane of the last sph_render_surface: q u32[height][width], SPH_RENDER_SURFACE_SENTINEL elsewhere */
+int sph_render_surface_download_depth(SphRender *r, uint32_t *q);
+int sph_render_surface_stats(SphRender *r, SphRenderSurfaceStats *out);
+
 /* --- mesh rendering: an ordered list of triangle meshes -> one RGB frame ------------------------------------------ */
 /* stands in for the reference's render.py + rendering_script.py (every .obj of a frame directory through a Blender scene ->
    {frame}/render.png).  Not Blender's path tracer: Lambert-shaded triangles, the camera, light, ambient, background, box lines and 8-bit

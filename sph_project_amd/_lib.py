@@ -144,6 +144,20 @@ class SphRenderCompositeStats(C.Structure):
     ]
 
 
+class SphRenderSurfaceParams(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_int32), ("rmax", C.c_int32), ("sigma", C.c_double), ("range", C.c_double), ("spec", C.c_double),
+        ("shininess", C.c_double), ("object_mask", C.c_int64),
+    ]
+
+
+class SphRenderSurfaceStats(C.Structure):
+    _fields_ = [
+        ("surface_pixels", C.c_int64), ("iterations", C.c_int64), ("taps_visited", C.c_int64), ("taps_accepted", C.c_int64),
+        ("clamped_rmax", C.c_int64), ("ms_base", C.c_double), ("ms_smooth", C.c_double), ("ms_shade", C.c_double),
+    ]
+
+
 class SphRenderMeshStats(C.Structure):
     _fields_ = [
         ("meshes", C.c_int64), ("triangles", C.c_int64), ("vertices", C.c_int64), ("large", C.c_int64),
@@ -293,6 +307,11 @@ _SIGNATURES = [
     ("sph_render_layer_download", C.c_int, [_VP, _VP, _VP]),
     ("sph_render_layer_merge", C.c_int, [_VP, _VP, _VP]),
     ("sph_render_composite_stats", C.c_int, [_VP, C.POINTER(SphRenderCompositeStats)]),
+    ("sph_render_set_surface", C.c_int, [_VP, C.POINTER(SphRenderSurfaceParams)]),
+    ("sph_render_points_surface_mask", C.c_int, [_VP, _VP, C.c_int]),
+    ("sph_render_surface", C.c_int, [_VP]),
+    ("sph_render_surface_download_depth", C.c_int, [_VP, _VP]),
+    ("sph_render_surface_stats", C.c_int, [_VP, C.POINTER(SphRenderSurfaceStats)]),
     ("sph_render_mesh_begin", C.c_int, [_VP]),
     ("sph_render_mesh_add", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP]),
     ("sph_render_mesh_add_surface", C.c_int, [_VP, _VP, _VP]),

@@ -269,6 +269,31 @@ struct RenderDev {
     hipStream_t stream;
 };
 
+// Screen-space surface mode of a particle frame (sph_render_surface.hpp): the planes behind the frame's key plane and the
+// integer constants of the depth stage.  base[p] = the winner's unshaded colour (r | g << 8 | b << 16) | RSURF_FLAG where the winner is a
+// particle of a surface object, else 0.  q[k][p] = the quantised view depth of a surface pixel (units of u = r / 256, at most
+// RSURF_QMAX), RSURF_SENT elsewhere.  cnt: [0] surface pixels, [1] window taps visited, [2] taps accepted, [3] pixels clamped at rmax --
+// in RSURF_CNT_BANKS banks of 8 words, a workgroup adding to the bank of its index (thousands of waves adding to one word serialise in
+// L2: the adds alone took longer than the passes); the host sums the banks.
+#define RSURF_SENT 0xFFFFFFFFu
+#define RSURF_QMAX 0x00FFFFFFu
+#define RSURF_FLAG 0x01000000u
+#define RSURF_RMAX_CAP 16
+#define RSURF_CNT_BANKS 64
+struct RenderSurfDev {
+    unsigned *base;                    // [W H]
+    unsigned *q[2];                    // [W H] each (ping-pong of the smoothing iterations)
+    unsigned long long *cnt;           // [RSURF_CNT_BANKS][8]
+    const unsigned char *pmask;        // points path: per-point surface flag (null: every point)
+    unsigned omask;                    // handle path: surface objects
+    int fluid_only;                    // handle path: ... and of these the fluid particles only (object_mask -1)
+    float inv_u, u;                    // 256 / r and r / 256, each rounded to f32 once on the host
+    unsigned rnum, dq;                 // R_i = clamp(rnum / q_i, 1, rmax); a tap counts when |q_j - q_i| <= dq
+    int rmax;
+    float dX, dY;                      // ray step per column / per row: 2 tx / W, -2 ty / H
+    float spec, shin;
+};
+
 // Mesh rendering (sph_render_mesh.hpp): the frame's meshes, concatenated.  Triangle g of the frame belongs to the last
 // record with t0 <= g; its indices are local to that mesh's nv vertices, which start at slot v0 of vert / nrm.  The frame buffers,
 // camera and counters are the RenderDev's: cnt[0] triangles that passed the hit test at some pixel centre (whether or not they won it), [1] non-finite, [2] large,
@@ -602,6 +627,11 @@ struct Launch {
     void (*render_shade)(RenderDev &);          // the winners' colours, then background / ids / covered count per pixel
     void (*render_merge)(RenderDev &, const unsigned long long *, const unsigned char *);   // another layer's keys and colours folded in
     void (*render_finish)(RenderDev &);         // background / ids / covered count per pixel once more (after merges)
+    // screen-space surface mode (sph_render_surface.hpp)
+    void (*render_surface_base)(RenderDev &, RenderSurfDev &);      // the base plane: the shade walk once more, colour | surface flag
+    void (*render_surface_quantise)(RenderDev &, RenderSurfDev &);  // key plane -> integer depth in both q planes, surface pixels counted
+    void (*render_surface_smooth)(RenderDev &, RenderSurfDev &, int it);   // iteration it: q[it & 1] -> q[1 - (it & 1)]
+    void (*render_surface_shade)(RenderDev &, RenderSurfDev &, int plane); // normals off q[plane], colour into rgb where the flag is set
     // mesh rendering (sph_render_mesh.hpp)
     void (*render_mesh_depth)(RenderDev &, MeshDev &);   // depth keys of triangles (small per thread, large per workgroup) and box lines
     void (*render_mesh_shade)(RenderDev &, MeshDev &);   // the winners' colours (triangles, lines)

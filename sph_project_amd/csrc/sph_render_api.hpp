@@ -5,8 +5,8 @@
 #include <climits>
 
 // the frame buffers, the particle list (large: also the mesh frames' triangle list) and the mesh lists
-// and an incoming layer
-enum RendBufId { RB_KEY, RB_RGB, RB_IDS, RB_CNT, RB_LARGE, RB_POS, RB_IDV, RB_COL, RB_MVERT, RB_MNRM, RB_MTRI, RB_MREC, RB_LKEY, RB_LRGB, RB_COUNT_ };
+// and an incoming layer; RB_S*: the planes of the surface mode, allocated when the mode is first used
+enum RendBufId { RB_KEY, RB_RGB, RB_IDS, RB_CNT, RB_LARGE, RB_POS, RB_IDV, RB_COL, RB_MVERT, RB_MNRM, RB_MTRI, RB_MREC, RB_LKEY, RB_LRGB, RB_SBASE, RB_SQ0, RB_SQ1, RB_SCNT, RB_SMASK, RB_COUNT_ };
 
 struct SphRender : DevObj {   // clk[0]: a particle frame's stages, clk[1]: a mesh frame's
     SphRenderParams prm;
@@ -22,6 +22,17 @@ struct SphRender : DevObj {   // clk[0]: a particle frame's stages, clk[1]: a me
     std::vector<MeshRec> mesh_rec;
     int64_t mesh_nv = 0, mesh_nt = 0;
     SphRenderMeshStats mstats{};
+    // surface mode: sclk marks 0 / 1 around the base plane, 2 / 3 / 4 quantise + smooth / shade
+    bool surf_on = false;
+    bool base_valid = false;      // the base plane belongs to the frame held (drawn with the mode on, not merged since)
+    bool depth_valid = false;     // sph_render_surface has run on the frame held
+    int depth_plane = 0;
+    SphRenderSurfaceParams sprm{};
+    RenderSurfDev sd{};
+    StageClock sclk;
+    std::vector<uint8_t> pmask;   // sph_render_points_surface_mask: for the next sph_render_points
+    bool pmask_set = false;
+    SphRenderSurfaceStats sstats{};
 };
 
 static bool rend_finite3(const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
@@ -137,6 +148,9 @@ extern "C" int sph_render_create(const SphRenderParams *params, SphRender **out)
 
 extern "C" void sph_render_destroy(SphRender *r) {
     if (!r) return;
+    hipSetDevice(r->device);
+    if (r->stream) hipStreamSynchronize(r->stream);
+    for (hipEvent_t e : r->sclk.ev) if (e) hipEventDestroy(e);
     devobj_close(r, r->buf, RB_COUNT_);
     delete r;
 }
@@ -170,6 +184,25 @@ static int rend_close(SphRender *r, unsigned long long c[8]) {
     return SPH_OK;
 }
 
+// surface mode: its planes, counters and clock on first use
+static int rsurf_room(SphRender *r) {
+    const size_t px = (size_t)r->d.W * r->d.H;
+    DevBuf *b = r->buf;
+    int rc = b[RB_SBASE].reserve(r, px * 4);
+    if (!rc) rc = b[RB_SQ0].reserve(r, px * 4);
+    if (!rc) rc = b[RB_SQ1].reserve(r, px * 4);
+    if (!rc) rc = b[RB_SCNT].reserve(r, RSURF_CNT_BANKS * 64);
+    if (rc) return rc;
+    if (!r->sclk.stream) {
+        for (hipEvent_t &e : r->sclk.ev) HIPCHK(r, hipEventCreate(&e));
+        r->sclk.stream = r->stream;
+    }
+    RenderSurfDev &s = r->sd;
+    s.base = (unsigned *)b[RB_SBASE].p; s.q[0] = (unsigned *)b[RB_SQ0].p; s.q[1] = (unsigned *)b[RB_SQ1].p;
+    s.cnt = (unsigned long long *)b[RB_SCNT].p;
+    return SPH_OK;
+}
+
 // after the source is set in d and stage mark 0 recorded: clear, splat, shade; synchronous
 static int rend_run(SphRender *r, int64_t n_in) {
     RenderDev &d = r->d;
@@ -179,9 +212,18 @@ static int rend_run(SphRender *r, int64_t n_in) {
     HIPCHK(r, k.mark(2));
     r->L->render_shade(d);
     HIPCHK(r, k.mark(3));
+    r->base_valid = r->depth_valid = false;
+    if (r->surf_on) {   // the base plane, while the source is the one that was drawn
+        { int rc = rsurf_room(r); if (rc) return rc; }
+        HIPCHK(r, r->sclk.mark(0));
+        r->L->render_surface_base(d, r->sd);
+        HIPCHK(r, r->sclk.mark(1));
+    }
     unsigned long long c[8];
     { int rc = rend_close(r, c); if (rc) return rc; }
     r->mesh_frame = false;
+    r->sstats = SphRenderSurfaceStats{};
+    if (r->surf_on) { r->base_valid = true; r->sstats.ms_base = r->sclk.ms(0, 1); }
     SphRenderStats &o = r->stats;
     o.particles = n_in; o.drawn = (int64_t)c[0]; o.skipped_nonfinite = (int64_t)c[1]; o.large = (int64_t)c[2]; o.atomics = (int64_t)c[3];
     o.covered_pixels = (int64_t)c[4];
@@ -234,6 +276,7 @@ extern "C" int sph_render_layer_download(SphRender *r, uint64_t *key, uint8_t *r
 extern "C" int sph_render_layer_merge(SphRender *r, const uint64_t *key, const uint8_t *rgb) {
     if (!r || !key || !rgb) return SPH_ERR_INVALID;
     { int rc = rend_layer_check(r, "sph_render_layer_merge"); if (rc) return rc; }
+    r->base_valid = r->depth_valid = false;   // (the merged pixels' colours and flags are not known here)
     HIPCHK(r, hipSetDevice(r->device));
     { int rc = rend_layer_room(r); if (rc) return rc; }
     const size_t px = (size_t)r->d.W * r->d.H;
@@ -314,6 +357,11 @@ extern "C" int sph_render_points(SphRender *r, const float *xyz, const uint8_t *
     if (ids_or_NULL)
         for (int64_t i = 0; i < n; ++i)
             if (ids_or_NULL[i] >= RENDER_LINE_ID0) return fail(r, SPH_ERR_INVALID, "sph_render_points: id %u >= 0xFFFFFFF0 (reserved)", ids_or_NULL[i]);
+    if (r->pmask_set && (int64_t)r->pmask.size() != n) {
+        const size_t nm = r->pmask.size();
+        r->pmask_set = false; r->pmask.clear();   // (the mask was for this call)
+        return fail(r, SPH_ERR_INVALID, "sph_render_points: surface mask of %zu points, %lld particles", nm, (long long)n);
+    }
     HIPCHK(r, hipSetDevice(r->device));
     r->have_frame = false; r->frame_elsewhere = false;
     r->stats = SphRenderStats{};
@@ -334,7 +382,15 @@ extern "C" int sph_render_points(SphRender *r, const float *xyz, const uint8_t *
     }
     RenderDev &d = r->d;
     d.n = (int)n; d.pos = (const float4 *)pos; d.meta = nullptr; d.id = (const int *)idv; d.col = (const unsigned *)colv; d.col_home = nullptr; d.mask = ~0u;
-    return rend_run(r, n);   // (the host vectors stay alive: rend_run synchronises)
+    r->sd.pmask = nullptr;
+    if (r->pmask_set && r->surf_on && n) {
+        { int rc = r->buf[RB_SMASK].reserve(r, (size_t)n); if (rc) return rc; }
+        HIPCHK(r, hipMemcpyAsync(r->buf[RB_SMASK].p, r->pmask.data(), (size_t)n, hipMemcpyHostToDevice, r->stream));
+        r->sd.pmask = (const unsigned char *)r->buf[RB_SMASK].p;
+    }
+    const int rc = rend_run(r, n);   // (the host vectors stay alive: rend_run synchronises)
+    r->pmask_set = false; r->pmask.clear();
+    return rc;
 }
 
 extern "C" int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mask) {
@@ -382,6 +438,98 @@ extern "C" int sph_render_download(SphRender *r, uint8_t *rgb, int32_t *ids_or_N
 extern "C" int sph_render_stats(SphRender *r, SphRenderStats *out) {
     if (!r || !out) return SPH_ERR_INVALID;
     *out = r->stats;
+    return SPH_OK;
+}
+
+// --- surface mode: the kernels are in sph_render_surface.hpp ---------------------------------------------------------------
+extern "C" int sph_render_set_surface(SphRender *r, const SphRenderSurfaceParams *params) {
+    if (!r) return SPH_ERR_INVALID;
+    if (!params) { r->surf_on = false; return SPH_OK; }
+    const SphRenderSurfaceParams p = *params;
+    if (p.iterations < 0 || p.iterations > 64) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: iterations %d outside 0..64", p.iterations);
+    if (p.rmax < 1 || p.rmax > RSURF_RMAX_CAP) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: rmax %d outside 1..%d", p.rmax, RSURF_RMAX_CAP);
+    if (!(p.sigma > 0.0) || !std::isfinite(p.sigma)) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: sigma %g must be finite and positive", p.sigma);
+    if (!(p.range > 0.0) || !std::isfinite(p.range)) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: range %g must be finite and positive", p.range);
+    if (!(p.spec >= 0.0) || !std::isfinite(p.spec)) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: spec %g must be finite and not negative", p.spec);
+    if (!(p.shininess >= 1.0) || !std::isfinite(p.shininess)) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: shininess %g must be finite and at least 1", p.shininess);
+    if (p.object_mask < -1 || p.object_mask > (int64_t)0xFFFFFFFFll)
+        return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: object_mask %lld is neither -1 nor a mask of the 32 objects", (long long)p.object_mask);
+    const double ty = tan(0.5 * r->prm.fov_deg * M_PI / 180.0), tx = ty * r->prm.width / r->prm.height;
+    const double rnum = std::round(256.0 * p.sigma * r->prm.height / (2.0 * ty)), dq = std::round(256.0 * p.range);
+    if (!(rnum < 2147483648.0)) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: sigma %g gives a window numerator of %.0f (below 2^31)", p.sigma, rnum);
+    if (!(dq >= 1.0 && dq <= 16777216.0)) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: range %g gives a depth range of %.0f units (1..2^24)", p.range, dq);
+    RenderSurfDev &s = r->sd;
+    const unsigned omask = p.object_mask < 0 ? ~0u : (unsigned)p.object_mask;
+    const int fluid_only = p.object_mask < 0 ? 1 : 0;
+    if (!r->surf_on || omask != s.omask || fluid_only != s.fluid_only) r->base_valid = false;   // the frame held has no base plane for this mask
+    s.omask = omask; s.fluid_only = fluid_only;
+    s.inv_u = (float)(256.0 / (double)r->d.r);
+    s.u = (float)((double)r->d.r / 256.0);
+    s.rnum = (unsigned)rnum; s.dq = (unsigned)dq; s.rmax = p.rmax;
+    s.dX = (float)(2.0 * tx / r->prm.width); s.dY = (float)(-2.0 * ty / r->prm.height);
+    s.spec = (float)p.spec; s.shin = (float)p.shininess;
+    r->sprm = p;
+    r->surf_on = true;
+    return SPH_OK;
+}
+
+extern "C" int sph_render_points_surface_mask(SphRender *r, const uint8_t *mask, int n) {
+    if (!r) return SPH_ERR_INVALID;
+    if (n < 0) return fail(r, SPH_ERR_INVALID, "sph_render_points_surface_mask: n = %d", n);
+    r->pmask_set = mask != nullptr;
+    r->pmask.clear();
+    if (mask) r->pmask.assign(mask, mask + n);
+    return SPH_OK;
+}
+
+extern "C" int sph_render_surface(SphRender *r) {
+    if (!r) return SPH_ERR_INVALID;
+    if (r->frame_elsewhere || (r->have_frame && !r->mesh_frame && r->cstats.ranks > 1))
+        return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_surface: the frame was composited from a sharded handle (its layers carry no base colour or surface flag)");
+    if (!r->have_frame) return fail(r, SPH_ERR_INVALID, "sph_render_surface: no particle frame has been rendered yet");
+    if (r->mesh_frame) return fail(r, SPH_ERR_INVALID, "sph_render_surface: the last frame is a mesh frame");
+    if (!r->surf_on) return fail(r, SPH_ERR_INVALID, "sph_render_surface: the surface mode is off (sph_render_set_surface)");
+    if (!r->base_valid)
+        return fail(r, SPH_ERR_INVALID, "sph_render_surface: the frame held was drawn before the mode was switched on, or changed by sph_render_layer_merge");
+    HIPCHK(r, hipSetDevice(r->device));
+    RenderDev &d = r->d;
+    RenderSurfDev &s = r->sd;
+    StageClock &k = r->sclk;
+    const int iters = r->sprm.iterations;
+    r->depth_valid = false;
+    HIPCHK(r, hipMemsetAsync(s.cnt, 0, RSURF_CNT_BANKS * 64, r->stream));
+    HIPCHK(r, k.mark(2));
+    r->L->render_surface_quantise(d, s);
+    for (int it = 0; it < iters; ++it) r->L->render_surface_smooth(d, s, it);
+    HIPCHK(r, k.mark(3));
+    r->depth_plane = iters & 1;
+    r->L->render_surface_shade(d, s, r->depth_plane);
+    HIPCHK(r, k.mark(4));
+    unsigned long long bank[RSURF_CNT_BANKS][8], c[8] = {};
+    HIPCHK(r, hipMemcpyAsync(bank, s.cnt, sizeof(bank), hipMemcpyDeviceToHost, r->stream));
+    HIPCHK(r, hipStreamSynchronize(r->stream));
+    HIPCHK(r, hipGetLastError());
+    for (int b = 0; b < RSURF_CNT_BANKS; ++b)
+        for (int w = 0; w < 8; ++w) c[w] += bank[b][w];
+    r->depth_valid = true;
+    SphRenderSurfaceStats &o = r->sstats;
+    o.surface_pixels = (int64_t)c[0]; o.iterations = iters; o.taps_visited = (int64_t)c[1]; o.taps_accepted = (int64_t)c[2];
+    o.clamped_rmax = (int64_t)c[3];
+    o.ms_smooth = k.ms(2, 3); o.ms_shade = k.ms(3, 4);
+    return SPH_OK;
+}
+
+extern "C" int sph_render_surface_download_depth(SphRender *r, uint32_t *q) {
+    if (!r || !q) return SPH_ERR_INVALID;
+    if (!r->have_frame || !r->depth_valid) return fail(r, SPH_ERR_INVALID, "sph_render_surface_download_depth: no surface frame is held (sph_render_surface)");
+    HIPCHK(r, hipSetDevice(r->device));
+    HIPCHK(r, hipMemcpy(q, r->sd.q[r->depth_plane], (size_t)r->d.W * r->d.H * 4, hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
+
+extern "C" int sph_render_surface_stats(SphRender *r, SphRenderSurfaceStats *out) {
+    if (!r || !out) return SPH_ERR_INVALID;
+    *out = r->sstats;
     return SPH_OK;
 }
 
@@ -472,6 +620,7 @@ extern "C" int sph_render_mesh_end(SphRender *r) {
     r->stats = SphRenderStats{};
     r->cstats = SphRenderCompositeStats{};
     r->mstats = SphRenderMeshStats{};
+    r->base_valid = r->depth_valid = false;
     const size_t nm = r->mesh_rec.size();
     { int rc = rend_room(r, (size_t)r->mesh_nt, false); if (rc) return rc; }
     { int rc = rend_grow(r, RB_MREC, 0, sizeof(MeshRec) * std::max<size_t>(nm, 1)); if (rc) return rc; }

@@ -15,6 +15,7 @@ import numpy as np
 from . import _lib as L
 
 BOX_RGB = (252, 173, 71)   # the reference's (0.99, 0.68, 0.28), floor(255 x + 0.5)
+SURFACE_SENTINEL = 0xFFFFFFFF   # surface_depth(): not a surface pixel (SPH_RENDER_SURFACE_SENTINEL)
 
 
 class RenderError(L.SphError):
@@ -41,6 +42,7 @@ class FrameRenderer(L.NativeObject):
         self._last_kind = None      # "points" or "meshes": what the last frame was drawn from
         self._stats_of = None       # the native renderer of the last from_container call (composite_stats on every rank)
         self._mesh_starts = None    # first global triangle index of each mesh of the last mesh frame (and the total)
+        self._surface = None        # SphRenderSurfaceParams of the surface mode, None: off
 
     def _params(self, box):
         kw = dict(self._kw)
@@ -63,7 +65,62 @@ class FrameRenderer(L.NativeObject):
         h = self._handles.get(key)
         if h is None:
             h = self._handles[key] = self._create(self._params(key))
+            if self._surface is not None:
+                self._chk(self.lib.sph_render_set_surface(h, C.byref(self._surface)), "sph_render_set_surface", h)
         return h
+
+    def set_surface(self, iterations=3, sigma=1.5, range=2.0, rmax=12, spec=0.35, shininess=40.0, objects=None):
+        """Switch the screen-space surface mode on for the frames drawn afterwards: from_points / from_container also fill
+        the base plane, surface() then turns the pixels won by surface particles into a smoothed, lit surface.  objects: the object ids
+        whose particles are surface particles in from_container (None: the fluid particles of every drawn object); from_points takes a
+        per-point flag instead.  sigma and range are in particle radii, rmax in pixels."""
+        p = L.SphRenderSurfaceParams()
+        p.iterations, p.rmax = int(iterations), int(rmax)
+        p.sigma, p.range, p.spec, p.shininess = float(sigma), float(range), float(spec), float(shininess)
+        if objects is None:
+            p.object_mask = -1
+        else:
+            mask = 0
+            for o in objects:
+                if not 0 <= int(o) < 32:
+                    raise ValueError(f"set_surface: object id {o} outside 0..31")
+                mask |= 1 << int(o)
+            p.object_mask = mask
+        self._native(self.box if self.box else None)   # (one native renderer at least: a bad parameter raises here)
+        for h in self._handles.values():
+            self._chk(self.lib.sph_render_set_surface(h, C.byref(p)), "sph_render_set_surface", h)
+        self._surface = p
+
+    def clear_surface(self):
+        """Switch the surface mode off."""
+        self._surface = None
+        for h in self._handles.values():
+            self._chk(self.lib.sph_render_set_surface(h, None), "sph_render_set_surface", h)
+
+    def surface(self, download=True):
+        """The last particle frame (from_points / from_container with the mode on) as a surface frame, uint8 (H, W, 3): its rgb is
+        overwritten in place on the device, ids() and layer()'s keys stay.  download=False: None, the frame stays on the device for
+        the encoders."""
+        if self._last is None:
+            h = self._stats_of if self._stats_of is not None else self._native(self.box if self.box else None)
+        else:
+            h = self._last
+        self._chk(self.lib.sph_render_surface(h), "sph_render_surface", h)
+        return self._frame(h, download)
+
+    def surface_depth(self):
+        """uint32 (H, W) of the last surface(): the smoothed integer depth in units of radius / 256, SURFACE_SENTINEL elsewhere."""
+        h = self._last if self._last is not None else self._native(self.box if self.box else None)
+        q = np.empty((self.height, self.width), np.uint32)
+        self._chk(self.lib.sph_render_surface_download_depth(h, q.ctypes.data), "sph_render_surface_download_depth", h)
+        return q
+
+    def surface_stats(self):
+        """Of the last surface(): surface_pixels, iterations, taps_visited / _accepted, clamped_rmax, ms_base / ms_smooth / ms_shade."""
+        h = self._last if self._last is not None else self._native(self.box if self.box else None)
+        st = L.SphRenderSurfaceStats()
+        self._chk(self.lib.sph_render_surface_stats(h, C.byref(st)), "sph_render_surface_stats", h)
+        return L.struct_dict(st)
 
     def close(self):
         super().close()
@@ -87,14 +144,20 @@ class FrameRenderer(L.NativeObject):
         if self._last is None or self._last_kind != kind:
             raise RenderError(f"{what}: the last frame is not a {'mesh' if kind == 'meshes' else 'particle'} frame", L.ERR_INVALID)
 
-    def from_points(self, xyz, colors=None, ids=None):
-        """uint8 (H, W, 3) of spheres at xyz f32[n, 3], colours uint8[n, 3] (None: white), distinct ids < 0xFFFFFFF0 (None: 0..n-1)."""
+    def from_points(self, xyz, colors=None, ids=None, surface=None):
+        """uint8 (H, W, 3) of spheres at xyz f32[n, 3], colours uint8[n, 3] (None: white), distinct ids < 0xFFFFFFF0 (None: 0..n-1).
+        surface: with the surface mode on, the per-point flag bool[n] of the surface particles (None: every point)."""
         x = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
         c = None if colors is None else np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 3)
         i = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
         if (c is not None and len(c) != len(x)) or (i is not None and len(i) != len(x)):
             raise ValueError("from_points: xyz, colors and ids must have one row per particle")
         h = self._native(self.box if self.box else None)
+        if surface is not None:
+            m = np.ascontiguousarray(np.asarray(surface).reshape(-1) != 0, dtype=np.uint8)
+            if len(m) != len(x):
+                raise ValueError("from_points: surface must have one flag per particle")
+            self._chk(self.lib.sph_render_points_surface_mask(h, m.ctypes.data, len(m)), "sph_render_points_surface_mask", h)
         self._chk(self.lib.sph_render_points(h, x.ctypes.data, None if c is None else c.ctypes.data,
                                              None if i is None else i.ctypes.data, x.shape[0]), "sph_render_points", h)
         self._last_kind = "points"

@@ -10,6 +10,8 @@ Rigid bodies: mesh_object_{id}.obj per frame with exportObj (:146-150).  PNG fra
 renderer of render.py with --render (its own image, not GGUI's: DESIGN.md 15); without --render none is written.  --render_meshes
 writes {cnt:06}/render.png, the frame's meshes drawn on the GPU, where the reference's render.py needs Blender.  --video
 adds {out}/raw_view.avi / {out}/render.avi, the same frames as Motion-JPEG compressed on the GPU (make_video.py).
+--render_surface writes {cnt:06}/surface_view.png: the particle frame with the fluid drawn as a smoothed, lit surface in screen space
+(DESIGN.md 24), at the cost of a particle frame where --render_meshes pays for a reconstruction.
 --png_device writes the PNG files from the device image as well (DESIGN.md 21): no pixel is downloaded, no zlib runs on the host;
 --png_coding dynamic makes those files smaller (dynamic Huffman blocks) for a slower encode.
 --gpus N shards the scene over N ranks (z-slabs, one process each, started by launch.py): the frames are composited over the ranks
@@ -111,6 +113,13 @@ def parse_args(argv=None):
                         help="at every output frame write {out}/{cnt:06}/render.png (render.py's default --rendered_image_name): the visible "
                              "fluid objects reconstructed with the --reconstruct settings, the visible rigid bodies' meshes at their current "
                              "pose and the domain box, drawn on the GPU (DESIGN.md 17; not Blender's image)")
+    parser.add_argument("--render_surface", action="store_true",
+                        help="at every output frame write {out}/{cnt:06}/surface_view.png: the particle frame of raw_view.png with the "
+                             "visible fluid objects drawn as a surface -- sphere depths smoothed in screen space, normals off the smoothed "
+                             "depth, Lambert and a highlight (DESIGN.md 24; no mesh is reconstructed); needs --gpus 1")
+    parser.add_argument("--surface_iters", type=int, default=None, help="with --render_surface: smoothing iterations, 0..64 (3)")
+    parser.add_argument("--surface_sigma", type=float, default=None, help="with --render_surface: smoothing half-width in particle radii (1.5)")
+    parser.add_argument("--surface_range", type=float, default=None, help="with --render_surface: depth range of a tap in particle radii (2.0)")
     parser.add_argument("--render_size", type=int, nargs=2, default=(1024, 1024), metavar=("W", "H"))
     parser.add_argument("--camera_position", type=float, nargs=3, default=(5.5, 2.5, 4.0))
     parser.add_argument("--camera_lookat", type=float, nargs=3, default=(-1.0, 0.0, 0.0))
@@ -144,15 +153,21 @@ def parse_args(argv=None):
                          "on the host); run it with --gpus 1")
         if not SimConfig(scene_file_path=args.scene_file).get_cfg("exportPly"):
             parser.error("--export_device formats the PLY frames of a scene with exportPly; this scene exports none")
+    if args.render_surface and args.gpus > 1:
+        parser.error(f"--gpus {args.gpus}: --render_surface needs the base colour and surface flag of every pixel, which the layers "
+                     "composited between ranks do not carry (DESIGN.md 24); run it with --gpus 1")
+    for flag in ("surface_iters", "surface_sigma", "surface_range"):
+        if getattr(args, flag) is not None and not args.render_surface:
+            parser.error(f"--{flag} sets a parameter of the surface frames: give --render_surface as well")
     if args.gpus > 1:
         check_sharded_args(parser, args)
-    if args.png_device and not (args.render or args.render_meshes):
-        parser.error("--png_device compresses a renderer's frames: give --render and / or --render_meshes as well")
+    if args.png_device and not (args.render or args.render_meshes or args.render_surface):
+        parser.error("--png_device compresses a renderer's frames: give --render, --render_meshes and / or --render_surface as well")
     if args.png_coding is not None and not args.png_device:
         parser.error("--png_coding chooses the device encoder's code: give --png_device as well")
     args.png_coding = args.png_coding or "fixed"
-    if args.video and not (args.render or args.render_meshes):
-        parser.error("--video takes its frames from a renderer: give --render and / or --render_meshes as well")
+    if args.video and not (args.render or args.render_meshes or args.render_surface):
+        parser.error("--video takes its frames from a renderer: give --render, --render_meshes and / or --render_surface as well")
     return args
 
 
@@ -378,10 +393,14 @@ def main(argv=None):
         if post is not None:
             recon.set_postprocess(**post)
     renderer = None
-    if output_frames:   # run_simulation.py:70-108: the window's camera, light, particle radius dx and domain box
+    surface_frames = bool(args.render_surface)
+    if output_frames or surface_frames:   # run_simulation.py:70-108: the window's camera, light, particle radius dx and domain box
         from sph_project_amd.render import FrameRenderer, write_png
         renderer = FrameRenderer(container.dx, width=args.render_size[0], height=args.render_size[1],
                                  camera_position=args.camera_position, camera_lookat=args.camera_lookat, fov=args.camera_fov)
+    if surface_frames:   # the surface objects: the fluid particles of the visible objects
+        chosen = dict(iterations=args.surface_iters, sigma=args.surface_sigma, range=args.surface_range)
+        renderer.set_surface(**{k: v for k, v in chosen.items() if v is not None})
     mesh_renderer = None
     if args.render_meshes:
         from sph_project_amd.render import FrameRenderer, write_png
@@ -391,10 +410,13 @@ def main(argv=None):
     videos = {}   # renderer -> (encoder, AVI writer)
     if args.video:
         from sph_project_amd.video import AviWriter, VideoEncoder
-        for r, name in ((renderer, "raw_view.avi"), (mesh_renderer, "render.avi")):
+        for r, name in ((renderer if output_frames else None, "raw_view.avi"), (mesh_renderer, "render.avi")):
             if r is not None:
                 videos[r] = (VideoEncoder(r.width, r.height, quality=args.video_quality, chroma=args.video_chroma),
                              AviWriter(f"{out_dir}/{name}", r.width, r.height, args.video_fps))
+        if surface_frames:   # the same renderer holds the raw frame first, then the surface frame: a second encoder and file
+            videos["surface"] = (VideoEncoder(renderer.width, renderer.height, quality=args.video_quality, chroma=args.video_chroma),
+                                 AviWriter(f"{out_dir}/surface_view.avi", renderer.width, renderer.height, args.video_fps))
 
     pngs = {}   # renderer -> device PNG encoder
     if args.png_device:
@@ -414,9 +436,9 @@ def main(argv=None):
         else:
             write_png(path, draw(True))
 
-    def add_video_frame(r):
-        if r in videos:
-            encoder, writer = videos[r]
+    def add_video_frame(r, which=None):
+        if (which or r) in videos:
+            encoder, writer = videos[which or r]
             writer.add(encoder.encode_last(r))
     cnt = 0
     limit = total_rounds if args.max_steps is None else min(total_rounds, args.max_steps)
@@ -427,7 +449,7 @@ def main(argv=None):
         while cnt < limit:
             # run_simulation.py:126-153 steps once, writes a frame if the count of steps BEFORE this one is a multiple of the
             # interval, then counts.  Same frames here, but the steps between two frames go to the device in one call.
-            wants_frame = output_ply or output_obj or output_frames or args.render_meshes
+            wants_frame = output_ply or output_obj or output_frames or args.render_meshes or surface_frames
             nxt = cnt if cnt % output_interval == 0 else cnt + output_interval - cnt % output_interval   # next count that gets a frame
             if not wants_frame or nxt >= limit:
                 solver.advance(limit - cnt)
@@ -443,6 +465,13 @@ def main(argv=None):
                 os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
                 store_png(f"{out_dir}/{cnt:06}/raw_view.png", renderer, lambda dl: renderer.from_container(container, download=dl))
                 add_video_frame(renderer)
+                wrote = True
+            if surface_frames:   # the same splat: the raw frame's rgb is overwritten on the device once its file is written
+                os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
+                if not output_frames:
+                    renderer.from_container(container, download=False)
+                store_png(f"{out_dir}/{cnt:06}/surface_view.png", renderer, lambda dl: renderer.surface(download=dl))
+                add_video_frame(renderer, "surface")
                 wrote = True
             if output_ply:
                 os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
