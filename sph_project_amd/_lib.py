@@ -413,6 +413,59 @@ class NativeObject:
             raise self.Error(f"{what} failed ({rc}): {msg.decode() if msg else ''}", rc)
 
 
+class FrameEncoder(NativeObject):
+    """An encoder of RGB frames of one size into files of one format (csrc/sph_encoder_api.hpp): ABI + "_encode_rgb" / "_encode_render" /
+    "_size" / "_download" / "_stats" are its functions, Stats their statistics structure."""
+    Stats = None
+
+    def _call(self, name, *args):
+        self._need_open(name)
+        name = f"{self.ABI}_{name}"
+        self._chk(getattr(self.lib, name)(self.h, *args), name)
+
+    def _need_open(self, what):
+        if self.h is None:
+            raise self.Error(f"{what}: the encoder is closed", ERR_INVALID)
+
+    def _download(self):
+        self._need_open("download")
+        n = C.c_int64()
+        self._call("size", C.byref(n))
+        buf = np.empty(n.value, np.uint8)
+        self._call("download", buf.ctypes.data)
+        return buf.tobytes()
+
+    def encode(self, rgb):
+        """The file of uint8 (height, width, 3)."""
+        self._need_open("encode")
+        a = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if a.shape != (self.height, self.width, 3):
+            raise ValueError(f"encode: expected ({self.height}, {self.width}, 3), got {a.shape}")
+        self._call("encode_rgb", a.ctypes.data)
+        return self._download()
+
+    def encode_last(self, frame_renderer):
+        """The file of a FrameRenderer's last frame (particles or meshes), read from its device buffer."""
+        self._need_open("encode_last")
+        if frame_renderer._last is None:
+            raise self.Error("encode_last: the renderer holds no frame", ERR_INVALID)
+        self._call("encode_render", frame_renderer._last)
+        return self._download()
+
+    def _stats(self):
+        st = self.Stats()
+        self._call("stats", C.byref(st))
+        return st
+
+    def stats(self):
+        return struct_dict(self._stats())
+
+    def write(self, path, frame_renderer):
+        """{path} <- the renderer's last frame; the pixels never reach the host."""
+        with open(path, "wb") as f:
+            f.write(self.encode_last(frame_renderer))
+
+
 class Engine(NativeObject):
     """Owns one SphHandle.  All arrays crossing the boundary are C-contiguous numpy f32 / i32."""
 

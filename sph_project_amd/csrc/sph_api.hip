@@ -1375,6 +1375,7 @@ extern "C" int sph_points_in_mesh(const double *vertices, int n_vertices, const 
 
 #include "sph_surface_api.hpp"
 #include "sph_render_api.hpp"
+#include "sph_encoder_api.hpp"
 #include "sph_video_api.hpp"
 #include "sph_png_api.hpp"
 #include "sph_text_api.hpp"

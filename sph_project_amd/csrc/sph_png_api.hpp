@@ -1,24 +1,20 @@
 // sph_png_api.hpp -- the SphPng object of include/sph_hip.h: the size bound, the fixed chunks (signature, IHDR, IEND), the frame source
-// (a host image, a renderer's frame buffer), the four passes and the stage marks.  Host code, included at the end of sph_api.hip; the
-// kernels are in sph_png.hpp, the stream is defined in DESIGN.md 21.
+// (sph_encoder_api.hpp), the four passes and the stage marks.  Host code, included at the end of sph_api.hip; the kernels are in
+// sph_png.hpp, the stream is defined in DESIGN.md 21.
 #pragma once
 
-enum PngBufId { PB_RGB, PB_FLT, PB_LEN, PB_ADLER, PB_CNT, PB_OUT, PB_SIDE, PB_COUNT_ };
+enum PngBufId { PB_FLT, PB_LEN, PB_ADLER, PB_CNT, PB_SIDE, PB_COUNT_ };
 
-struct SphPng : DevObj {   // clk[0]: the stages of an encode
+struct SphPng : FrameEncoder {   // header: signature, IHDR; payload: the segments' chunks and the Adler-32's; trailer: IEND
     SphPngParams prm;
     PngDev d{};
     DevBuf buf[PB_COUNT_];
-    std::vector<uint8_t> header;   // signature, IHDR
-    bool have_frame = false;
-    int64_t chunk_bytes = 0;       // what the device wrote: the segments' chunks and the Adler-32's
-    SphPngStats stats{};
+    SphPngStats stats{};           // of the frame held
     int32_t coding = SPH_PNG_CODING_FIXED;
 };
 
 static const char *png_check(const SphPngParams &p) {
-    if (p.width < 1 || p.height < 1 || p.width > 16384 || p.height > 16384 || (int64_t)p.width * p.height > ((int64_t)1 << 26))
-        return "width and height are 1..16384 each, at most 2^26 pixels in all";
+    if (const char *why = enc_check_size(p.width, p.height)) return why;
     if (p.filter < -1 || p.filter > 4) return "filter is -1 (adaptive) or a PNG filter type 0..4";
     if (p.reserved != 0) return "reserved must be 0";
     return nullptr;
@@ -70,6 +66,7 @@ extern "C" int sph_png_create(const SphPngParams *params, SphPng **out) {
     SphPng *v = new SphPng();
     v->prm = p;
     v->header = png_header(p);
+    v->trailer.assign(PNG_IEND, PNG_IEND + 12);
     PngDev &d = v->d;
     d.W = p.width; d.H = p.height; d.filter = p.filter;
     d.stride = 1 + 3 * p.width;
@@ -79,14 +76,12 @@ extern "C" int sph_png_create(const SphPngParams *params, SphPng **out) {
     for (int k = 0; k < 8 * PNG_CRC_PIECE; ++k) d.crc_pow[0] = (d.crc_pow[0] >> 1) ^ (PNG_CRC_POLY & (0u - (d.crc_pow[0] & 1u)));
     for (int j = 1; j < 8; ++j) d.crc_pow[j] = png_crc_mul(d.crc_pow[j - 1], d.crc_pow[j - 1]);
     DevBuf *b = v->buf;
-    int rc = devobj_open(v, "sph_png_create", dev, p.fast_math);
-    if (rc && !v->stream) { sph_png_destroy(v); return rc; }
-    if (rc || b[PB_RGB].reserve(nullptr, (size_t)p.width * p.height * 3) || b[PB_FLT].reserve(nullptr, (size_t)d.nseg * PNG_SEG) ||
-        b[PB_LEN].reserve(nullptr, sizeof(int) * ((size_t)d.nseg + 1)) || b[PB_ADLER].reserve(nullptr, sizeof(unsigned) * 2 * (size_t)d.nseg) ||
-        b[PB_CNT].reserve(nullptr, PNG_NCNT * sizeof(unsigned long long) + sizeof(unsigned)) || b[PB_SIDE].reserve(nullptr, (size_t)d.nseg * PNG_SIDE)) {
-        sph_png_destroy(v);
-        return fail(nullptr, SPH_ERR_HIP, "sph_png_create: buffers of a %d x %d frame", p.width, p.height);
-    }
+    int rc = enc_open(v, "sph_png_create", p.width, p.height, dev, p.fast_math);
+    if (!rc && (b[PB_FLT].reserve(nullptr, (size_t)d.nseg * PNG_SEG) || b[PB_LEN].reserve(nullptr, sizeof(int) * ((size_t)d.nseg + 1)) ||
+                b[PB_ADLER].reserve(nullptr, sizeof(unsigned) * 2 * (size_t)d.nseg) ||
+                b[PB_CNT].reserve(nullptr, PNG_NCNT * sizeof(unsigned long long) + sizeof(unsigned)) || b[PB_SIDE].reserve(nullptr, (size_t)d.nseg * PNG_SIDE)))
+        rc = enc_no_room(v, "sph_png_create");
+    if (rc) { sph_png_destroy(v); return rc; }
     d.flt = (unsigned char *)b[PB_FLT].p; d.len = (int *)b[PB_LEN].p; d.adler = (unsigned *)b[PB_ADLER].p;
     d.cnt = (unsigned long long *)b[PB_CNT].p; d.sum = (unsigned *)(d.cnt + PNG_NCNT);
     d.side = nullptr;   // coding = fixed
@@ -97,7 +92,7 @@ extern "C" int sph_png_create(const SphPngParams *params, SphPng **out) {
 
 extern "C" void sph_png_destroy(SphPng *v) {
     if (!v) return;
-    devobj_close(v, v->buf, PB_COUNT_);
+    enc_close(v, v->buf, PB_COUNT_);
     delete v;
 }
 
@@ -112,11 +107,11 @@ extern "C" int sph_png_set_coding(SphPng *v, int32_t coding) {
     return SPH_OK;
 }
 
-// after stage mark 0 and the source's arrival on the stream: filter, count, scan, size the output, write; synchronous
-static int png_run(SphPng *v, const unsigned char *rgb_dev) {
+// after the opening of an encode: filter, count, scan, size the output, write; synchronous
+static int png_run(SphPng *v) {
     PngDev &d = v->d;
     StageClock &k = v->clk[0];
-    d.rgb = rgb_dev;
+    d.rgb = v->src;
     HIPCHK(v, hipMemsetAsync(d.cnt, 0, PNG_NCNT * sizeof(unsigned long long) + sizeof(unsigned), v->stream));
     HIPCHK(v, k.mark(1));
     v->L->png_filter(d);
@@ -133,19 +128,17 @@ static int png_run(SphPng *v, const unsigned char *rgb_dev) {
     HIPCHK(v, hipGetLastError());
     const int64_t most = png_bound(v->prm) - (int64_t)v->header.size() - 12 - 16;
     if (total < 13 || total > most) return fail(v, SPH_ERR_HIP, "sph_png: the count pass left %d chunk bytes (at most %lld)", total, (long long)most);
-    // the output holds exactly what the count pass found (grown with some room so that frames of similar size reuse it)
-    { int rc = v->buf[PB_OUT].reserve(v, (size_t)total + 16 + (size_t)total / 4 + 64); if (rc) return rc; }
-    d.out = (unsigned char *)v->buf[PB_OUT].p;
+    { int rc = enc_room(v, total, 16); if (rc) return rc; }   // (16: the Adler-32's chunk)
+    d.out = (unsigned char *)v->out.p;
     v->L->png_write(d);
     HIPCHK(v, k.mark(5));
     HIPCHK(v, hipStreamSynchronize(v->stream));
     HIPCHK(v, hipGetLastError());
-    v->chunk_bytes = (int64_t)total + 16;
     v->have_frame = true;
     SphPngStats &o = v->stats;
     o.raw_bytes = d.raw;
     o.zlib_bytes = (int64_t)total - 12 * (int64_t)d.nseg + 4;
-    o.file_bytes = (int64_t)v->header.size() + v->chunk_bytes + 12;
+    o.file_bytes = enc_file_bytes(v);
     o.segments = d.nseg; o.stored_segments = (int64_t)c[5]; o.literals = (int64_t)c[6]; o.matches = (int64_t)c[7];
     o.dynamic_segments = (int64_t)c[8]; o.dynamic_header_bits = (int64_t)c[9];
     for (int t = 0; t < 5; ++t) o.filter_rows[t] = (int64_t)c[t];
@@ -155,50 +148,21 @@ static int png_run(SphPng *v, const unsigned char *rgb_dev) {
 }
 
 extern "C" int sph_png_encode_rgb(SphPng *v, const uint8_t *rgb) {
-    if (!v) return SPH_ERR_INVALID;
-    if (!rgb) return fail(v, SPH_ERR_INVALID, "sph_png_encode_rgb: null image");
-    HIPCHK(v, hipSetDevice(v->device));
-    v->have_frame = false;
-    v->stats = SphPngStats{};
-    HIPCHK(v, v->clk[0].mark(0));
-    HIPCHK(v, hipMemcpyAsync(v->buf[PB_RGB].p, rgb, (size_t)v->d.W * v->d.H * 3, hipMemcpyHostToDevice, v->stream));
-    return png_run(v, (const unsigned char *)v->buf[PB_RGB].p);
+    const int rc = enc_begin_rgb(v, "sph_png_encode_rgb", rgb);
+    return rc ? rc : png_run(v);
 }
 
 extern "C" int sph_png_encode_render(SphPng *v, SphRender *r) {
-    if (!v || !r) return SPH_ERR_INVALID;
-    if (!r->have_frame) return fail(v, SPH_ERR_INVALID, "sph_png_encode_render: the renderer holds no frame");
-    if (r->d.W != v->d.W || r->d.H != v->d.H)
-        return fail(v, SPH_ERR_INVALID, "sph_png_encode_render: the renderer's frame is %d x %d, the encoder's %d x %d", r->d.W, r->d.H, v->d.W, v->d.H);
-    if (r->device != v->device) return fail(v, SPH_ERR_INVALID, "sph_png_encode_render: renderer on device %d, encoder on device %d", r->device, v->device);
-    HIPCHK(v, hipSetDevice(v->device));
-    v->have_frame = false;
-    v->stats = SphPngStats{};
-    HIPCHK(v, hipStreamSynchronize(r->stream));   // (the render calls are synchronous: the frame is complete)
-    HIPCHK(v, v->clk[0].mark(0));
-    return png_run(v, r->d.rgb);   // read in place: nothing of the renderer is written
+    const int rc = enc_begin_render(v, "sph_png_encode_render", r);
+    return rc ? rc : png_run(v);
 }
 
-extern "C" int sph_png_size(SphPng *v, int64_t *bytes) {
-    if (!v || !bytes) return SPH_ERR_INVALID;
-    if (!v->have_frame) return fail(v, SPH_ERR_INVALID, "sph_png_size: no frame has been encoded yet");
-    *bytes = (int64_t)v->header.size() + v->chunk_bytes + 12;
-    return SPH_OK;
-}
+extern "C" int sph_png_size(SphPng *v, int64_t *bytes) { return enc_size(v, "sph_png_size", bytes); }
 
-extern "C" int sph_png_download(SphPng *v, uint8_t *dst) {
-    if (!v || !dst) return SPH_ERR_INVALID;
-    if (!v->have_frame) return fail(v, SPH_ERR_INVALID, "sph_png_download: no frame has been encoded yet");
-    HIPCHK(v, hipSetDevice(v->device));
-    const size_t nh = v->header.size();
-    memcpy(dst, v->header.data(), nh);
-    HIPCHK(v, hipMemcpy(dst + nh, v->d.out, (size_t)v->chunk_bytes, hipMemcpyDeviceToHost));
-    memcpy(dst + nh + v->chunk_bytes, PNG_IEND, 12);
-    return SPH_OK;
-}
+extern "C" int sph_png_download(SphPng *v, uint8_t *dst) { return enc_download(v, "sph_png_download", dst); }
 
 extern "C" int sph_png_stats(SphPng *v, SphPngStats *out) {
     if (!v || !out) return SPH_ERR_INVALID;
-    *out = v->stats;
+    *out = v->have_frame ? v->stats : SphPngStats{};   // (a frame that went with the opening of an encode took its figures along)
     return SPH_OK;
 }

@@ -8,13 +8,15 @@
 // and an incoming layer; RB_S*: the planes of the surface mode, allocated when the mode is first used
 enum RendBufId { RB_KEY, RB_RGB, RB_IDS, RB_CNT, RB_LARGE, RB_POS, RB_IDV, RB_COL, RB_MVERT, RB_MNRM, RB_MTRI, RB_MREC, RB_LKEY, RB_LRGB, RB_SBASE, RB_SQ0, RB_SQ1, RB_SCNT, RB_SMASK, RB_COUNT_ };
 
+// what the renderer holds.  RF_ON_RANK0: the last frame was composited over a communicator and lies on rank 0, not here; RF_MESH: a mesh
+// frame has no layer (triangle indices do not compose)
+enum RendFrame { RF_NONE, RF_ON_RANK0, RF_PARTICLE, RF_MESH };
+
 struct SphRender : DevObj {   // clk[0]: a particle frame's stages, clk[1]: a mesh frame's
     SphRenderParams prm;
     RenderDev d{};
     DevBuf buf[RB_COUNT_];
-    bool have_frame = false;
-    bool mesh_frame = false;      // the frame is a mesh frame: it has no layer (triangle indices do not compose)
-    bool frame_elsewhere = false; // the last frame was composited over a communicator and lies on rank 0, not here
+    RendFrame frame = RF_NONE;
     SphRenderStats stats{};
     SphRenderCompositeStats cstats{};
     // mesh frames: the list between mesh_begin and mesh_end, concatenated on the device
@@ -175,12 +177,12 @@ static int rend_open(SphRender *r, StageClock &c, int k) {
     HIPCHK(r, c.mark(k));
     return SPH_OK;
 }
-// the closing: the counters in c, the stream idle, the frame there
-static int rend_close(SphRender *r, unsigned long long c[8]) {
+// the closing: the counters in c, the stream idle, the frame (of this kind) there
+static int rend_close(SphRender *r, unsigned long long c[8], RendFrame kind) {
     HIPCHK(r, hipMemcpyAsync(c, r->d.cnt, 8 * sizeof(*c), hipMemcpyDeviceToHost, r->stream));
     HIPCHK(r, hipStreamSynchronize(r->stream));
     HIPCHK(r, hipGetLastError());
-    r->have_frame = true;
+    r->frame = kind;
     return SPH_OK;
 }
 
@@ -220,8 +222,7 @@ static int rend_run(SphRender *r, int64_t n_in) {
         HIPCHK(r, r->sclk.mark(1));
     }
     unsigned long long c[8];
-    { int rc = rend_close(r, c); if (rc) return rc; }
-    r->mesh_frame = false;
+    { int rc = rend_close(r, c, RF_PARTICLE); if (rc) return rc; }
     r->sstats = SphRenderSurfaceStats{};
     if (r->surf_on) { r->base_valid = true; r->sstats.ms_base = r->sclk.ms(0, 1); }
     SphRenderStats &o = r->stats;
@@ -251,15 +252,15 @@ static int rend_refinish(SphRender *r) {
     HIPCHK(r, hipMemsetAsync(r->d.cnt + 4, 0, sizeof(unsigned long long), r->stream));
     r->L->render_finish(r->d);
     unsigned long long c[8];
-    { int rc = rend_close(r, c); if (rc) return rc; }
+    { int rc = rend_close(r, c, RF_PARTICLE); if (rc) return rc; }
     r->stats.covered_pixels = (int64_t)c[4];
     return SPH_OK;
 }
 
 static int rend_layer_check(SphRender *r, const char *who) {
-    if (!r->have_frame)
-        return fail(r, SPH_ERR_INVALID, r->frame_elsewhere ? "%s: the composited frame lies on rank 0, this rank holds none" : "%s: no frame has been rendered yet", who);
-    if (r->mesh_frame) return fail(r, SPH_ERR_INVALID, "%s: the last frame is a mesh frame (triangle indices do not compose: layers are particle frames)", who);
+    if (r->frame == RF_ON_RANK0) return fail(r, SPH_ERR_INVALID, "%s: the composited frame lies on rank 0, this rank holds none", who);
+    if (r->frame == RF_NONE) return fail(r, SPH_ERR_INVALID, "%s: no frame has been rendered yet", who);
+    if (r->frame == RF_MESH) return fail(r, SPH_ERR_INVALID, "%s: the last frame is a mesh frame (triangle indices do not compose: layers are particle frames)", who);
     return SPH_OK;
 }
 
@@ -304,7 +305,7 @@ static int rend_composite(SphRender *r, SphHandle *h) {
     SphRenderCompositeStats &cs = r->cstats;
     cs = SphRenderCompositeStats{};
     cs.ranks = c.nranks;
-    r->have_frame = false;   // (rend_run's: this rank's layer alone, not a frame before the chain is through)
+    r->frame = RF_NONE;   // (rend_run's: this rank's layer alone, not a frame before the chain is through)
     const size_t px = (size_t)r->d.W * r->d.H;
     const size_t plane[2] = {px * 8, px * 3};
     const size_t cap = c.kind == 2 ? (size_t)c.mbox_cap : ((size_t)16 << 20);
@@ -345,9 +346,9 @@ static int rend_composite(SphRender *r, SphHandle *h) {
     double drawn = (double)r->stats.drawn;
     { int rc = sph_comm_allreduce(h, &drawn, 1, 0); if (rc) return fail(r, rc, "sph_render_handle: %s", last_error(h)); }
     cs.drawn_global = (int64_t)drawn;
-    if (c.rank != 0) { r->have_frame = false; r->frame_elsewhere = true; return SPH_OK; }
+    if (c.rank != 0) { r->frame = RF_ON_RANK0; return SPH_OK; }
     if (c.nranks > 1) return rend_refinish(r);
-    r->have_frame = true;
+    r->frame = RF_PARTICLE;
     return SPH_OK;
 }
 
@@ -363,7 +364,7 @@ extern "C" int sph_render_points(SphRender *r, const float *xyz, const uint8_t *
         return fail(r, SPH_ERR_INVALID, "sph_render_points: surface mask of %zu points, %lld particles", nm, (long long)n);
     }
     HIPCHK(r, hipSetDevice(r->device));
-    r->have_frame = false; r->frame_elsewhere = false;
+    r->frame = RF_NONE;
     r->stats = SphRenderStats{};
     { int rc = rend_room(r, (size_t)n, true); if (rc) return rc; }
     std::vector<float4> p4((size_t)n);
@@ -400,7 +401,7 @@ extern "C" int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mas
     if (h->device != r->device) return fail(r, SPH_ERR_INVALID, "sph_render_handle: handle on device %d, renderer on %d", h->device, r->device);
     if (h->in_step) return fail(r, SPH_ERR_INVALID, "sph_render_handle: between sph_step_begin and sph_step_end");
     HIPCHK(r, hipSetDevice(r->device));
-    r->have_frame = false; r->frame_elsewhere = false;
+    r->frame = RF_NONE;
     r->stats = SphRenderStats{};
     State &s = h->st;
     RenderDev &d = r->d;
@@ -425,13 +426,25 @@ extern "C" int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mas
 
 extern "C" int sph_render_download(SphRender *r, uint8_t *rgb, int32_t *ids_or_NULL) {
     if (!r || !rgb) return SPH_ERR_INVALID;
-    if (!r->have_frame)
-        return fail(r, SPH_ERR_INVALID, r->frame_elsewhere ? "sph_render_download: the composited frame lies on rank 0, this rank holds none"
-                                                           : "sph_render_download: no frame has been rendered yet");
+    if (r->frame == RF_ON_RANK0) return fail(r, SPH_ERR_INVALID, "sph_render_download: the composited frame lies on rank 0, this rank holds none");
+    if (r->frame == RF_NONE) return fail(r, SPH_ERR_INVALID, "sph_render_download: no frame has been rendered yet");
     HIPCHK(r, hipSetDevice(r->device));
     const size_t px = (size_t)r->d.W * r->d.H;
     HIPCHK(r, hipMemcpy(rgb, r->d.rgb, px * 3, hipMemcpyDeviceToHost));
     if (ids_or_NULL) HIPCHK(r, hipMemcpy(ids_or_NULL, r->d.ids, px * 4, hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
+
+// the frame held, for an object on `device` that reads w x h pixels of it in place (an encoder; `o` takes its message, `who` names its
+// call): the checks, the renderer's stream drained (the render calls are synchronous: the frame is complete), the rgb plane
+static int rend_frame_rgb(SphRender *r, int w, int h, int device, ErrSink *o, const char *who, const unsigned char **rgb) {
+    if (r->frame != RF_PARTICLE && r->frame != RF_MESH) return fail(o, SPH_ERR_INVALID, "%s: the renderer holds no frame", who);
+    if (r->d.W != w || r->d.H != h)
+        return fail(o, SPH_ERR_INVALID, "%s: the renderer's frame is %d x %d, the encoder's %d x %d", who, r->d.W, r->d.H, w, h);
+    if (r->device != device) return fail(o, SPH_ERR_INVALID, "%s: renderer on device %d, encoder on %d", who, r->device, device);
+    HIPCHK(o, hipSetDevice(device));
+    HIPCHK(o, hipStreamSynchronize(r->stream));
+    *rgb = r->d.rgb;
     return SPH_OK;
 }
 
@@ -484,10 +497,10 @@ extern "C" int sph_render_points_surface_mask(SphRender *r, const uint8_t *mask,
 
 extern "C" int sph_render_surface(SphRender *r) {
     if (!r) return SPH_ERR_INVALID;
-    if (r->frame_elsewhere || (r->have_frame && !r->mesh_frame && r->cstats.ranks > 1))
+    if (r->frame == RF_ON_RANK0 || (r->frame == RF_PARTICLE && r->cstats.ranks > 1))
         return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_surface: the frame was composited from a sharded handle (its layers carry no base colour or surface flag)");
-    if (!r->have_frame) return fail(r, SPH_ERR_INVALID, "sph_render_surface: no particle frame has been rendered yet");
-    if (r->mesh_frame) return fail(r, SPH_ERR_INVALID, "sph_render_surface: the last frame is a mesh frame");
+    if (r->frame == RF_NONE) return fail(r, SPH_ERR_INVALID, "sph_render_surface: no particle frame has been rendered yet");
+    if (r->frame == RF_MESH) return fail(r, SPH_ERR_INVALID, "sph_render_surface: the last frame is a mesh frame");
     if (!r->surf_on) return fail(r, SPH_ERR_INVALID, "sph_render_surface: the surface mode is off (sph_render_set_surface)");
     if (!r->base_valid)
         return fail(r, SPH_ERR_INVALID, "sph_render_surface: the frame held was drawn before the mode was switched on, or changed by sph_render_layer_merge");
@@ -521,7 +534,7 @@ extern "C" int sph_render_surface(SphRender *r) {
 
 extern "C" int sph_render_surface_download_depth(SphRender *r, uint32_t *q) {
     if (!r || !q) return SPH_ERR_INVALID;
-    if (!r->have_frame || !r->depth_valid) return fail(r, SPH_ERR_INVALID, "sph_render_surface_download_depth: no surface frame is held (sph_render_surface)");
+    if (r->frame != RF_PARTICLE || !r->depth_valid) return fail(r, SPH_ERR_INVALID, "sph_render_surface_download_depth: no surface frame is held (sph_render_surface)");
     HIPCHK(r, hipSetDevice(r->device));
     HIPCHK(r, hipMemcpy(q, r->sd.q[r->depth_plane], (size_t)r->d.W * r->d.H * 4, hipMemcpyDeviceToHost));
     return SPH_OK;
@@ -616,7 +629,7 @@ extern "C" int sph_render_mesh_end(SphRender *r) {
     if (!r->mesh_open) return fail(r, SPH_ERR_INVALID, "sph_render_mesh_end: no sph_render_mesh_begin before it");
     r->mesh_open = false;
     HIPCHK(r, hipSetDevice(r->device));
-    r->have_frame = false; r->frame_elsewhere = false;
+    r->frame = RF_NONE;
     r->stats = SphRenderStats{};
     r->cstats = SphRenderCompositeStats{};
     r->mstats = SphRenderMeshStats{};
@@ -642,8 +655,7 @@ extern "C" int sph_render_mesh_end(SphRender *r) {
     r->L->render_mesh_finish(d);
     HIPCHK(r, k.mark(4));
     unsigned long long c[8];
-    { int rc = rend_close(r, c); if (rc) return rc; }
-    r->mesh_frame = true;
+    { int rc = rend_close(r, c, RF_MESH); if (rc) return rc; }
     SphRenderMeshStats &o = r->mstats;
     o.meshes = (int64_t)nm; o.triangles = r->mesh_nt; o.vertices = r->mesh_nv;
     o.hit = (int64_t)c[0]; o.skipped_nonfinite = (int64_t)c[1]; o.large = (int64_t)c[2]; o.atomics = (int64_t)c[3];

@@ -1,6 +1,6 @@
 // sph_video_api.hpp -- the SphVideo object of include/sph_hip.h: the tables of T.81 Annex K and the fixed headers built from them, the
-// frame source (a host image, a renderer's frame buffer), the two-pass encode and the stage marks.  Host code, included at the end of
-// sph_api.hip; the kernels are in sph_video.hpp, the stream is defined in DESIGN.md 18.
+// frame source (sph_encoder_api.hpp), the two-pass encode and the stage marks.  Host code, included at the end of sph_api.hip; the
+// kernels are in sph_video.hpp, the stream is defined in DESIGN.md 18.
 #pragma once
 
 static const unsigned char VIDEO_K1[64] = {   // T.81 table K.1 (luminance), natural order
@@ -53,21 +53,17 @@ static const unsigned char VIDEO_ZIGZAG[64] = {   // zigzag position -> natural 
     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
     58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-enum VideoBufId { VB_RGB, VB_TAB, VB_LEN, VB_CNT, VB_OUT, VB_COUNT_ };
+enum VideoBufId { VB_TAB, VB_LEN, VB_CNT, VB_COUNT_ };
 
-struct SphVideo : DevObj {   // clk[0]: the stages of an encode
+struct SphVideo : FrameEncoder {   // header: SOI ... SOS; payload: the entropy-coded scan; trailer: EOI
     SphVideoParams prm;
     VideoDev d{};
     DevBuf buf[VB_COUNT_];
-    std::vector<uint8_t> header;   // SOI ... SOS
-    bool have_frame = false;
-    int64_t scan_bytes = 0;
-    SphVideoStats stats{};
+    SphVideoStats stats{};         // of the frame held
 };
 
 static const char *video_check(const SphVideoParams &p) {
-    if (p.width < 1 || p.height < 1 || p.width > 16384 || p.height > 16384 || (int64_t)p.width * p.height > ((int64_t)1 << 26))
-        return "width and height are 1..16384 each, at most 2^26 pixels in all";
+    if (const char *why = enc_check_size(p.width, p.height)) return why;
     if (p.quality < 1 || p.quality > 100) return "quality is 1..100";
     if (p.chroma != 420 && p.chroma != 444) return "chroma is 420 or 444";
     if (p.reserved != 0) return "reserved must be 0";
@@ -153,6 +149,7 @@ extern "C" int sph_video_create(const SphVideoParams *params, SphVideo **out) {
     SphVideo *v = new SphVideo();
     v->prm = p;
     v->header = video_header(p);
+    v->trailer = {0xff, 0xd9};
     VideoDev &d = v->d;
     d.W = p.width; d.H = p.height; d.c420 = p.chroma == 420 ? 1 : 0;
     const int m = d.c420 ? 16 : 8;
@@ -160,13 +157,10 @@ extern "C" int sph_video_create(const SphVideoParams *params, SphVideo **out) {
     d.nmcu = d.mw * ((p.height + m - 1) / m);
     d.nint = (d.nmcu + VIDEO_RI - 1) / VIDEO_RI;
     DevBuf *b = v->buf;
-    int rc = devobj_open(v, "sph_video_create", dev, p.fast_math);
-    if (rc && !v->stream) { sph_video_destroy(v); return rc; }
-    if (rc || b[VB_RGB].reserve(nullptr, (size_t)p.width * p.height * 3) || b[VB_TAB].reserve(nullptr, sizeof(VideoTables)) ||
-        b[VB_LEN].reserve(nullptr, sizeof(int) * ((size_t)d.nint + 1)) || b[VB_CNT].reserve(nullptr, 16)) {
-        sph_video_destroy(v);
-        return fail(nullptr, SPH_ERR_HIP, "sph_video_create: buffers of a %d x %d frame", p.width, p.height);
-    }
+    int rc = enc_open(v, "sph_video_create", p.width, p.height, dev, p.fast_math);
+    if (!rc && (b[VB_TAB].reserve(nullptr, sizeof(VideoTables)) || b[VB_LEN].reserve(nullptr, sizeof(int) * ((size_t)d.nint + 1)) || b[VB_CNT].reserve(nullptr, 16)))
+        rc = enc_no_room(v, "sph_video_create");
+    if (rc) { sph_video_destroy(v); return rc; }
     const VideoTables t = video_tables(p.quality);
     if (hipMemcpy(b[VB_TAB].p, &t, sizeof(t), hipMemcpyHostToDevice) != hipSuccess) {
         sph_video_destroy(v);
@@ -180,17 +174,17 @@ extern "C" int sph_video_create(const SphVideoParams *params, SphVideo **out) {
 
 extern "C" void sph_video_destroy(SphVideo *v) {
     if (!v) return;
-    devobj_close(v, v->buf, VB_COUNT_);
+    enc_close(v, v->buf, VB_COUNT_);
     delete v;
 }
 
 extern "C" const char *sph_video_last_error(SphVideo *v) { return last_error(v); }
 
-// after stage mark 0 and the source's arrival on the stream: count, scan, size the output, write; synchronous
-static int video_run(SphVideo *v, const unsigned char *rgb_dev) {
+// after the opening of an encode: count, scan, size the output, write; synchronous
+static int video_run(SphVideo *v) {
     VideoDev &d = v->d;
     StageClock &k = v->clk[0];
-    d.rgb = rgb_dev;
+    d.rgb = v->src;
     HIPCHK(v, hipMemsetAsync(d.cnt, 0, 16, v->stream));
     HIPCHK(v, k.mark(1));
     v->L->video_count(d);
@@ -204,14 +198,12 @@ static int video_run(SphVideo *v, const unsigned char *rgb_dev) {
     HIPCHK(v, hipStreamSynchronize(v->stream));
     HIPCHK(v, hipGetLastError());
     if (total < 1) return fail(v, SPH_ERR_HIP, "sph_video: the count pass left %d scan bytes", total);
-    // the output holds exactly what the count pass found (grown with some room so that frames of similar size reuse it)
-    { int rc = v->buf[VB_OUT].reserve(v, (size_t)total + (size_t)total / 4 + 64); if (rc) return rc; }
-    d.out = (unsigned char *)v->buf[VB_OUT].p;
+    { int rc = enc_room(v, total, 0); if (rc) return rc; }
+    d.out = (unsigned char *)v->out.p;
     v->L->video_write(d);
     HIPCHK(v, k.mark(4));
     HIPCHK(v, hipStreamSynchronize(v->stream));
     HIPCHK(v, hipGetLastError());
-    v->scan_bytes = total;
     v->have_frame = true;
     SphVideoStats &o = v->stats;
     o.blocks = (int64_t)d.nmcu * (d.c420 ? 6 : 3);
@@ -221,50 +213,21 @@ static int video_run(SphVideo *v, const unsigned char *rgb_dev) {
 }
 
 extern "C" int sph_video_encode_rgb(SphVideo *v, const uint8_t *rgb) {
-    if (!v) return SPH_ERR_INVALID;
-    if (!rgb) return fail(v, SPH_ERR_INVALID, "sph_video_encode_rgb: null image");
-    HIPCHK(v, hipSetDevice(v->device));
-    v->have_frame = false;
-    v->stats = SphVideoStats{};
-    HIPCHK(v, v->clk[0].mark(0));
-    HIPCHK(v, hipMemcpyAsync(v->buf[VB_RGB].p, rgb, (size_t)v->d.W * v->d.H * 3, hipMemcpyHostToDevice, v->stream));
-    return video_run(v, (const unsigned char *)v->buf[VB_RGB].p);
+    const int rc = enc_begin_rgb(v, "sph_video_encode_rgb", rgb);
+    return rc ? rc : video_run(v);
 }
 
 extern "C" int sph_video_encode_render(SphVideo *v, SphRender *r) {
-    if (!v || !r) return SPH_ERR_INVALID;
-    if (!r->have_frame) return fail(v, SPH_ERR_INVALID, "sph_video_encode_render: the renderer holds no frame");
-    if (r->d.W != v->d.W || r->d.H != v->d.H)
-        return fail(v, SPH_ERR_INVALID, "sph_video_encode_render: the renderer's frame is %d x %d, the encoder's %d x %d", r->d.W, r->d.H, v->d.W, v->d.H);
-    if (r->device != v->device) return fail(v, SPH_ERR_INVALID, "sph_video_encode_render: renderer on device %d, encoder on %d", r->device, v->device);
-    HIPCHK(v, hipSetDevice(v->device));
-    v->have_frame = false;
-    v->stats = SphVideoStats{};
-    HIPCHK(v, hipStreamSynchronize(r->stream));   // (the render calls are synchronous: the frame is complete)
-    HIPCHK(v, v->clk[0].mark(0));
-    return video_run(v, r->d.rgb);   // read in place: nothing of the renderer is written
+    const int rc = enc_begin_render(v, "sph_video_encode_render", r);
+    return rc ? rc : video_run(v);
 }
 
-extern "C" int sph_video_size(SphVideo *v, int64_t *bytes) {
-    if (!v || !bytes) return SPH_ERR_INVALID;
-    if (!v->have_frame) return fail(v, SPH_ERR_INVALID, "sph_video_size: no frame has been encoded yet");
-    *bytes = (int64_t)v->header.size() + v->scan_bytes + 2;
-    return SPH_OK;
-}
+extern "C" int sph_video_size(SphVideo *v, int64_t *bytes) { return enc_size(v, "sph_video_size", bytes); }
 
-extern "C" int sph_video_download(SphVideo *v, uint8_t *dst) {
-    if (!v || !dst) return SPH_ERR_INVALID;
-    if (!v->have_frame) return fail(v, SPH_ERR_INVALID, "sph_video_download: no frame has been encoded yet");
-    HIPCHK(v, hipSetDevice(v->device));
-    const size_t nh = v->header.size();
-    memcpy(dst, v->header.data(), nh);
-    HIPCHK(v, hipMemcpy(dst + nh, v->d.out, (size_t)v->scan_bytes, hipMemcpyDeviceToHost));
-    dst[nh + v->scan_bytes] = 0xff; dst[nh + v->scan_bytes + 1] = 0xd9;   // EOI
-    return SPH_OK;
-}
+extern "C" int sph_video_download(SphVideo *v, uint8_t *dst) { return enc_download(v, "sph_video_download", dst); }
 
 extern "C" int sph_video_stats(SphVideo *v, SphVideoStats *out) {
     if (!v || !out) return SPH_ERR_INVALID;
-    *out = v->stats;
+    *out = v->have_frame ? v->stats : SphVideoStats{};   // (a frame that went with the opening of an encode took its figures along)
     return SPH_OK;
 }

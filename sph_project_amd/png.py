@@ -8,8 +8,6 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
 from . import _lib as L
 
 class PngError(L.SphError):
@@ -44,10 +42,10 @@ def bound(width, height, filter="adaptive"):
     return n.value
 
 
-class PngEncoder(L.NativeObject):
+class PngEncoder(L.FrameEncoder):
     """One PNG encoder for frames of one size.  The bytes of a file depend on (pixels, width, height, filter, coding) alone; a file in
     coding "dynamic" is never longer than the "fixed" one of the same picture."""
-    ABI, Error = "sph_png", PngError
+    ABI, Error, Stats = "sph_png", PngError, L.SphPngStats
 
     def __init__(self, width, height, filter="adaptive", coding="fixed", fast_math=False, device=-1):
         super().__init__()
@@ -60,51 +58,13 @@ class PngEncoder(L.NativeObject):
         if code != L.PNG_CODING_FIXED:
             self.set_coding(coding)
 
-    def _need_open(self, what):
-        if self.h is None:
-            raise PngError(f"{what}: the encoder is closed", L.ERR_INVALID)
-
     def set_coding(self, coding):
         """"fixed" | "dynamic": the entropy coding of the encodes that follow"""
-        code = _coding(coding)
-        self._need_open("set_coding")
-        self._chk(self.lib.sph_png_set_coding(self.h, code), "sph_png_set_coding")
+        self._call("set_coding", _coding(coding))
         self.coding = coding
 
-    def _download(self):
-        self._need_open("download")
-        n = C.c_int64()
-        self._chk(self.lib.sph_png_size(self.h, C.byref(n)), "sph_png_size")
-        buf = np.empty(n.value, np.uint8)
-        self._chk(self.lib.sph_png_download(self.h, buf.ctypes.data), "sph_png_download")
-        return buf.tobytes()
-
-    def encode(self, rgb):
-        """The .png file of uint8 (height, width, 3)."""
-        self._need_open("encode")
-        a = np.ascontiguousarray(rgb, dtype=np.uint8)
-        if a.shape != (self.height, self.width, 3):
-            raise ValueError(f"encode: expected ({self.height}, {self.width}, 3), got {a.shape}")
-        self._chk(self.lib.sph_png_encode_rgb(self.h, a.ctypes.data), "sph_png_encode_rgb")
-        return self._download()
-
-    def encode_last(self, frame_renderer):
-        """The .png file of a FrameRenderer's last frame (particles or meshes), read from its device buffer."""
-        self._need_open("encode_last")
-        if frame_renderer._last is None:
-            raise PngError("encode_last: the renderer holds no frame", L.ERR_INVALID)
-        self._chk(self.lib.sph_png_encode_render(self.h, frame_renderer._last), "sph_png_encode_render")
-        return self._download()
-
     def stats(self):
-        self._need_open("stats")
-        st = L.SphPngStats()
-        self._chk(self.lib.sph_png_stats(self.h, C.byref(st)), "sph_png_stats")
-        out = L.struct_dict(st)
-        out["filter_rows"] = list(st.filter_rows)
-        return out
+        st = self._stats()
+        return dict(L.struct_dict(st), filter_rows=list(st.filter_rows))
 
-    def write_png(self, path, frame_renderer):
-        """{path} <- the renderer's last frame; the pixels never reach the host."""
-        with open(path, "wb") as f:
-            f.write(self.encode_last(frame_renderer))
+    write_png = L.FrameEncoder.write

@@ -321,3 +321,13 @@ def write_png(path, rgb):
     """rgb uint8 (H, W, 3) as an 8-bit RGB PNG (what window.save_image wrote as raw_view.png in the reference)."""
     with open(path, "wb") as f:
         f.write(encode_png(rgb))
+
+
+def store_png(path, renderer, draw, png_encoder=None):
+    """draw(download) renders the renderer's frame; {path} comes from the downloaded pixels or, with a png.PngEncoder, from the device
+    image."""
+    if png_encoder is not None:
+        draw(False)
+        png_encoder.write_png(path, renderer)
+    else:
+        write_png(path, draw(True))

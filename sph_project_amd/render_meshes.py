@@ -100,7 +100,7 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    from sph_project_amd.render import FrameRenderer, write_png
+    from sph_project_amd.render import FrameRenderer, store_png
     with open(args.scene_file) as fh:
         cfg = json.load(fh)
     colours = scene_colours(cfg)
@@ -120,11 +120,7 @@ def main(argv=None):
         meshes = frame_meshes(d, colours)
         if not meshes:
             continue
-        if encoder is not None:
-            renderer.from_meshes(meshes, download=False)
-            encoder.write_png(os.path.join(d, args.rendered_image_name), renderer)
-        else:
-            write_png(os.path.join(d, args.rendered_image_name), renderer.from_meshes(meshes))
+        store_png(os.path.join(d, args.rendered_image_name), renderer, lambda dl: renderer.from_meshes(meshes, download=dl), encoder)
         done += 1
     print(f"Rendered {done} frame(s) of {args.input_dir}")
     return done

@@ -224,22 +224,110 @@ METHODS = {"dfsph": (DFSPHContainer, DFSPHSolver), "wcsph": (WCSPHContainer, WCS
            "iisph": (IISPHContainer, IISPHSolver), "pbf": (PBFContainer, PBFSolver)}
 
 
+class Schedule:
+    """The reference's interval arithmetic (run_simulation.py:13-44) over a scene's configuration: a frame at every step count that is a
+    multiple of output_interval, `limit` steps in all (--max_steps stops early), what a frame holds and where the frames go."""
+
+    def __init__(self, config, args):
+        fps = config.get_cfg("fps")
+        if fps is None:
+            fps = 60
+        frame_time = 1.0 / fps
+        self.output_interval = int(frame_time / config.get_cfg("timeStepSize"))
+        total_time = config.get_cfg("totalTime")
+        if total_time is None:
+            total_time = 10.0
+        total_rounds = int(total_time / config.get_cfg("timeStepSize"))
+        if config.get_cfg("outputInterval"):
+            self.output_interval = config.get_cfg("outputInterval")
+        self.limit = total_rounds if args.max_steps is None else min(total_rounds, args.max_steps)
+        self.limit = max(self.limit, 1)   # the reference's loop steps once before it looks at the round count
+        self.output_ply = config.get_cfg("exportPly")
+        self.output_obj = config.get_cfg("exportObj")
+        self.output_frames = config.get_cfg("exportFrame") and args.render
+        scene_name = args.scene_file.split("/")[-1].split(".")[0]
+        self.out_dir = args.output_dir or f"{scene_name}_output"
+
+
+def frame_dir(out_dir, cnt):
+    """{out_dir}/{cnt:06}, there from the first time a frame asks for it."""
+    d = f"{out_dir}/{cnt:06}"
+    os.makedirs(d, exist_ok=True)
+    return d
+
+
+def run_loop(solver, engine, sched, wants_frame, write_frame, avi_writers=()):
+    """run_simulation.py:126-153 steps once, writes a frame if the count of steps BEFORE this one is a multiple of the interval, then
+    counts.  Same frames here -- write_frame(cnt) writes one and returns whether anything was written -- but the steps between two frames
+    go to the device in one call.  Returns the step count, the seconds spent in write_frame and the number of frames written; an
+    exception still leaves well-formed videos of the frames written so far."""
+    cnt, limit, interval = 0, sched.limit, sched.output_interval
+    t_export, frames = 0.0, 0
+    try:
+        while cnt < limit:
+            nxt = cnt if cnt % interval == 0 else cnt + interval - cnt % interval   # next count that gets a frame
+            if not wants_frame or nxt >= limit:
+                solver.advance(limit - cnt)
+                cnt = limit
+                break
+            solver.advance(nxt - cnt + 1)
+            cnt = nxt
+            engine.synchronize()
+            te = time.perf_counter()
+            frames += 1 if write_frame(cnt) else 0
+            t_export += time.perf_counter() - te
+            cnt += 1
+        engine.synchronize()
+    finally:
+        for writer in avi_writers:
+            writer.close()
+    return cnt, t_export, frames
+
+
+def report(cnt, particles, t0, t_export, frames):
+    # frame export (ASCII PLY of every fluid particle, OBJ of every rigid mesh: run_simulation.py:137-150) is host file I/O and can
+    # dwarf the simulation -- 1.3 s per frame for the 1.23 M particles of final_scene0.json -- so it is reported apart from the steps
+    dt = time.perf_counter() - t0
+    print(f"Simulation Finished: {cnt} steps, {particles}, {1e3 * (dt - t_export) / cnt:.3f} ms/step "
+          f"(+ {t_export:.2f} s writing {frames} frame(s): {1e3 * dt / cnt:.3f} ms/step all in)")
+
+
+def make_renderer(container, args, **kw):
+    """run_simulation.py:70-108: the window's camera, light and particle radius dx"""
+    from sph_project_amd.render import FrameRenderer
+    return FrameRenderer(container.dx, width=args.render_size[0], height=args.render_size[1], camera_position=args.camera_position,
+                         camera_lookat=args.camera_lookat, fov=args.camera_fov, **kw)
+
+
+class ImageOutput:
+    """One image per frame, {frame}/{png_name}, of what `renderer` holds when store() is called; with --png_device the file is compressed
+    on the device, with --video the same device image is also a frame of {out_dir}/{avi_name}."""
+
+    def __init__(self, png_name, avi_name, renderer, args, out_dir, device=-1):
+        self.png_name, self.renderer = png_name, renderer
+        self.png = self.video = self.avi = None
+        if args.png_device:
+            from sph_project_amd.png import PngEncoder
+            self.png = PngEncoder(renderer.width, renderer.height, coding=args.png_coding, device=device)
+        if args.video:
+            from sph_project_amd.video import AviWriter, VideoEncoder
+            self.video = VideoEncoder(renderer.width, renderer.height, quality=args.video_quality, chroma=args.video_chroma, device=device)
+            self.avi = AviWriter(f"{out_dir}/{avi_name}", renderer.width, renderer.height, args.video_fps)
+
+    def store(self, frame_dir, draw):
+        """draw(download) renders the frame"""
+        from sph_project_amd.render import store_png
+        store_png(f"{frame_dir}/{self.png_name}", self.renderer, draw, self.png)
+        if self.avi is not None:
+            self.avi.add(self.video.encode_last(self.renderer))
+
+
 def main_sharded(args, rank, world):
-    """One rank of --gpus N: the scene's z-slab of this rank, the loop arithmetic of main(), collective output frames."""
+    """One rank of --gpus N: the scene's z-slab of this rank, the loop of main(), collective output frames."""
     from sph_project_amd import _lib, launch
     config = SimConfig(scene_file_path=args.scene_file)
-    scene_name = args.scene_file.split("/")[-1].split(".")[0]
-    fps = config.get_cfg("fps") or 60
-    output_interval = int((1.0 / fps) / config.get_cfg("timeStepSize"))
-    total_time = config.get_cfg("totalTime")
-    total_rounds = int((10.0 if total_time is None else total_time) / config.get_cfg("timeStepSize"))
-    if config.get_cfg("outputInterval"):
-        output_interval = config.get_cfg("outputInterval")
-    output_ply = config.get_cfg("exportPly")
-    output_obj = config.get_cfg("exportObj")
-    output_frames = config.get_cfg("exportFrame") and args.render
-    out_dir = args.output_dir or f"{scene_name}_output"
-    os.makedirs(out_dir, exist_ok=True)
+    sched = Schedule(config, args)
+    os.makedirs(sched.out_dir, exist_ok=True)
 
     lib = _lib.load()
     ndev = lib.sph_device_count()
@@ -265,79 +353,43 @@ def main_sharded(args, rank, world):
         print(f"Simulation method: {method} on {world} ranks ({engine.comm_transport()}), slab cuts {cuts}")
     solver.prepare()
 
-    renderer = encoder = writer = png = None
-    if output_frames:   # every rank draws its slab; the frame is composited on rank 0
-        from sph_project_amd.render import FrameRenderer, write_png
-        renderer = FrameRenderer(container.dx, width=args.render_size[0], height=args.render_size[1], camera_position=args.camera_position,
-                                 camera_lookat=args.camera_lookat, fov=args.camera_fov, device=device)
-        if rank == 0 and args.video:
-            from sph_project_amd.video import AviWriter, VideoEncoder
-            encoder = VideoEncoder(renderer.width, renderer.height, quality=args.video_quality, chroma=args.video_chroma, device=device)
-            writer = AviWriter(f"{out_dir}/raw_view.avi", renderer.width, renderer.height, args.video_fps)
-        if rank == 0 and args.png_device:
-            from sph_project_amd.png import PngEncoder
-            png = PngEncoder(renderer.width, renderer.height, coding=args.png_coding, device=device)
+    renderer = raw = None
+    if sched.output_frames:   # every rank draws its slab; the frame is composited on rank 0
+        renderer = make_renderer(container, args, device=device)
+        if rank == 0:
+            raw = ImageOutput("raw_view.png", "raw_view.avi", renderer, args, sched.out_dir, device)
 
-    def owned_global():
-        return int(round(engine.comm_allreduce([engine.comm_get_slab()["n_owned"]])[0]))
+    def write_frame(cnt):
+        d = frame_dir(sched.out_dir, cnt)
+        if raw is not None:   # collective: every rank draws, rank 0 holds the frame
+            raw.store(d, lambda dl: renderer.from_container(container, download=dl))
+        elif renderer is not None:
+            renderer.from_container(container)
+        if sched.output_ply:   # one file per fluid object: the ranks' owned particles, appended in rank order
+            obj = engine.download(_lib.F_OBJECT_ID)
+            own = engine.download(_lib.F_GHOST) == 0   # (container.dump does not filter the ghosts)
+            pos = engine.download(_lib.F_POSITION)
+            fluid_ids = sorted(container.object_id_fluid_body)
+            totals = engine.comm_allreduce([float(((obj == i) & own).sum()) for i in fluid_ids]) if fluid_ids else []
+            for i, total in zip(fluid_ids, totals):
+                for r in range(world):
+                    if r == rank:
+                        write_ply_ascii_part(f"{d}/particle_object_{i}.ply", pos[(obj == i) & own], int(round(total)), r == 0)
+                    engine.comm_barrier()
+        if sched.output_obj and rank == 0:
+            for r_body_id in container.object_id_rigid_body:
+                if "mesh" not in container.object_collection[r_body_id]:
+                    continue
+                with open(f"{d}/mesh_object_{r_body_id}.obj", "w") as f:
+                    f.write(container.object_collection[r_body_id]["mesh"].export(file_type="obj"))
+        return True
 
-    cnt = 0
-    limit = total_rounds if args.max_steps is None else min(total_rounds, args.max_steps)
-    limit = max(limit, 1)
     t0 = time.perf_counter()
-    t_export, frames = 0.0, 0
-    try:
-        while cnt < limit:   # main()'s arithmetic: the same frames at the same step counts
-            wants_frame = output_ply or output_obj or output_frames
-            nxt = cnt if cnt % output_interval == 0 else cnt + output_interval - cnt % output_interval
-            if not wants_frame or nxt >= limit:
-                solver.advance(limit - cnt)
-                cnt = limit
-                break
-            solver.advance(nxt - cnt + 1)
-            cnt = nxt
-            engine.synchronize()
-            te = time.perf_counter()
-            frame_dir = f"{out_dir}/{cnt:06}"
-            os.makedirs(frame_dir, exist_ok=True)
-            if output_frames:   # collective: every rank calls it, rank 0 holds the frame
-                rgb = renderer.from_container(container, download=png is None)
-                if rank == 0:
-                    if png is not None:
-                        png.write_png(f"{frame_dir}/raw_view.png", renderer)
-                    else:
-                        write_png(f"{frame_dir}/raw_view.png", rgb)
-                    if writer is not None:
-                        writer.add(encoder.encode_last(renderer))
-            if output_ply:   # one file per fluid object: the ranks' owned particles, appended in rank order
-                obj = engine.download(_lib.F_OBJECT_ID)
-                own = engine.download(_lib.F_GHOST) == 0   # (container.dump does not filter the ghosts)
-                pos = engine.download(_lib.F_POSITION)
-                fluid_ids = sorted(container.object_id_fluid_body)
-                totals = engine.comm_allreduce([float(((obj == i) & own).sum()) for i in fluid_ids]) if fluid_ids else []
-                for i, total in zip(fluid_ids, totals):
-                    for r in range(world):
-                        if r == rank:
-                            write_ply_ascii_part(f"{frame_dir}/particle_object_{i}.ply", pos[(obj == i) & own], int(round(total)), r == 0)
-                        engine.comm_barrier()
-            if output_obj and rank == 0:
-                for r_body_id in container.object_id_rigid_body:
-                    if "mesh" not in container.object_collection[r_body_id]:
-                        continue
-                    with open(f"{frame_dir}/mesh_object_{r_body_id}.obj", "w") as f:
-                        f.write(container.object_collection[r_body_id]["mesh"].export(file_type="obj"))
-            frames += 1
-            t_export += time.perf_counter() - te
-            cnt += 1
-        engine.synchronize()
-    finally:
-        if writer is not None:
-            writer.close()
-    n_global = owned_global()
-    dt = time.perf_counter() - t0
+    cnt, t_export, frames = run_loop(solver, engine, sched, sched.output_ply or sched.output_obj or sched.output_frames, write_frame,
+                                     [raw.avi] if raw is not None and raw.avi is not None else [])
+    n_global = int(round(engine.comm_allreduce([engine.comm_get_slab()["n_owned"]])[0]))
     if rank == 0:
-        print(f"Simulation Finished: {cnt} steps, {n_global} particles on {world} ranks, {1e3 * (dt - t_export) / cnt:.3f} ms/step "
-              f"(+ {t_export:.2f} s writing {frames} frame(s): {1e3 * dt / cnt:.3f} ms/step all in)")
+        report(cnt, f"{n_global} particles on {world} ranks", t0, t_export, frames)
     return container, solver
 
 
@@ -353,35 +405,16 @@ def main(argv=None):
                 raise SystemExit(1)
             return None
         return main_sharded(args, me[0], me[1])
-    scene_path = args.scene_file
-    config = SimConfig(scene_file_path=scene_path)
-    scene_name = scene_path.split("/")[-1].split(".")[0]
-
-    fps = config.get_cfg("fps")
-    if fps is None:
-        fps = 60
-    frame_time = 1.0 / fps
-    output_interval = int(frame_time / config.get_cfg("timeStepSize"))
-    total_time = config.get_cfg("totalTime")
-    if total_time is None:
-        total_time = 10.0
-    total_rounds = int(total_time / config.get_cfg("timeStepSize"))
-    if config.get_cfg("outputInterval"):
-        output_interval = config.get_cfg("outputInterval")
-    output_ply = config.get_cfg("exportPly")
-    output_obj = config.get_cfg("exportObj")
-    output_frames = config.get_cfg("exportFrame") and args.render
-    out_dir = args.output_dir or f"{scene_name}_output"
+    config = SimConfig(scene_file_path=args.scene_file)
+    sched = Schedule(config, args)
+    out_dir = sched.out_dir
     os.makedirs(out_dir, exist_ok=True)
 
     method = config.get_cfg("simulationMethod")
-    table = {"dfsph": (DFSPHContainer, DFSPHSolver), "wcsph": (WCSPHContainer, WCSPHSolver),
-             "pcisph": (PCISPHContainer, PCISPHSolver), "iisph": (IISPHContainer, IISPHSolver),
-             "pbf": (PBFContainer, PBFSolver)}
-    if method not in table:
+    if method not in METHODS:
         raise NotImplementedError(f"Simulation method {method} not implemented")
-    container = table[method][0](config, GGUI=False, rigid_backend=args.rigid_backend)
-    solver = table[method][1](container)
+    container = METHODS[method][0](config, GGUI=False, rigid_backend=args.rigid_backend)
+    solver = METHODS[method][1](container)
     print(f"Simulation method: {method}")
     solver.prepare()
 
@@ -392,129 +425,71 @@ def main(argv=None):
         post = surface_postprocess(args)
         if post is not None:
             recon.set_postprocess(**post)
-    renderer = None
-    surface_frames = bool(args.render_surface)
-    if output_frames or surface_frames:   # run_simulation.py:70-108: the window's camera, light, particle radius dx and domain box
-        from sph_project_amd.render import FrameRenderer, write_png
-        renderer = FrameRenderer(container.dx, width=args.render_size[0], height=args.render_size[1],
-                                 camera_position=args.camera_position, camera_lookat=args.camera_lookat, fov=args.camera_fov)
-    if surface_frames:   # the surface objects: the fluid particles of the visible objects
+    renderer = raw = surface = meshes_out = None
+    if sched.output_frames or args.render_surface:
+        renderer = make_renderer(container, args)
+    if sched.output_frames:   # run_simulation.py:131-134
+        raw = ImageOutput("raw_view.png", "raw_view.avi", renderer, args, out_dir)
+    if args.render_surface:   # the surface objects: the fluid particles of the visible objects.  The same renderer holds the raw frame
+        # first, then the surface frame: encoders and a video file of its own
         chosen = dict(iterations=args.surface_iters, sigma=args.surface_sigma, range=args.surface_range)
         renderer.set_surface(**{k: v for k, v in chosen.items() if v is not None})
-    mesh_renderer = None
-    if args.render_meshes:
-        from sph_project_amd.render import FrameRenderer, write_png
-        mesh_renderer = FrameRenderer(container.dx, width=args.render_size[0], height=args.render_size[1],
-                                      camera_position=args.camera_position, camera_lookat=args.camera_lookat, fov=args.camera_fov,
-                                      box=(np.zeros(3), np.asarray(container.domain_end, dtype=np.float64)))
-    videos = {}   # renderer -> (encoder, AVI writer)
-    if args.video:
-        from sph_project_amd.video import AviWriter, VideoEncoder
-        for r, name in ((renderer if output_frames else None, "raw_view.avi"), (mesh_renderer, "render.avi")):
-            if r is not None:
-                videos[r] = (VideoEncoder(r.width, r.height, quality=args.video_quality, chroma=args.video_chroma),
-                             AviWriter(f"{out_dir}/{name}", r.width, r.height, args.video_fps))
-        if surface_frames:   # the same renderer holds the raw frame first, then the surface frame: a second encoder and file
-            videos["surface"] = (VideoEncoder(renderer.width, renderer.height, quality=args.video_quality, chroma=args.video_chroma),
-                                 AviWriter(f"{out_dir}/surface_view.avi", renderer.width, renderer.height, args.video_fps))
-
-    pngs = {}   # renderer -> device PNG encoder
-    if args.png_device:
-        from sph_project_amd.png import PngEncoder
-        pngs = {r: PngEncoder(r.width, r.height, coding=args.png_coding) for r in (renderer, mesh_renderer) if r is not None}
+        surface = ImageOutput("surface_view.png", "surface_view.avi", renderer, args, out_dir)
+    if args.render_meshes:   # render.py: every mesh of the frame -> {frame}/render.png
+        mesh_renderer = make_renderer(container, args, box=(np.zeros(3), np.asarray(container.domain_end, dtype=np.float64)))
+        meshes_out = ImageOutput("render.png", "render.avi", mesh_renderer, args, out_dir)
 
     exporter = None   # --export_device: the text files come from the device state
     if args.export_device:
         from sph_project_amd.text import TextExporter
         exporter = TextExporter()
 
-    def store_png(path, r, draw):
-        """draw(download) renders r's frame; the file comes from the downloaded pixels or, with --png_device, from the device image"""
-        if r in pngs:
-            draw(False)
-            pngs[r].write_png(path, r)
-        else:
-            write_png(path, draw(True))
-
-    def add_video_frame(r, which=None):
-        if (which or r) in videos:
-            encoder, writer = videos[which or r]
-            writer.add(encoder.encode_last(r))
-    cnt = 0
-    limit = total_rounds if args.max_steps is None else min(total_rounds, args.max_steps)
-    limit = max(limit, 1)   # the reference's loop steps once before it looks at the round count
-    t0 = time.perf_counter()
-    t_export, frames = 0.0, 0
-    try:
-        while cnt < limit:
-            # run_simulation.py:126-153 steps once, writes a frame if the count of steps BEFORE this one is a multiple of the
-            # interval, then counts.  Same frames here, but the steps between two frames go to the device in one call.
-            wants_frame = output_ply or output_obj or output_frames or args.render_meshes or surface_frames
-            nxt = cnt if cnt % output_interval == 0 else cnt + output_interval - cnt % output_interval   # next count that gets a frame
-            if not wants_frame or nxt >= limit:
-                solver.advance(limit - cnt)
-                cnt = limit
-                break
-            solver.advance(nxt - cnt + 1)
-            cnt = nxt
-            container.engine.synchronize()
-            te = time.perf_counter()
-            wrote = False
-            held = set()
-            if output_frames:   # run_simulation.py:131-134
-                os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
-                store_png(f"{out_dir}/{cnt:06}/raw_view.png", renderer, lambda dl: renderer.from_container(container, download=dl))
-                add_video_frame(renderer)
-                wrote = True
-            if surface_frames:   # the same splat: the raw frame's rgb is overwritten on the device once its file is written
-                os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
-                if not output_frames:
-                    renderer.from_container(container, download=False)
-                store_png(f"{out_dir}/{cnt:06}/surface_view.png", renderer, lambda dl: renderer.surface(download=dl))
-                add_video_frame(renderer, "surface")
-                wrote = True
-            if output_ply:
-                os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
-                for f_body_id in container.object_id_fluid_body:
-                    if exporter is not None:
-                        exporter.ply_object(container, f_body_id).write(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.ply")
+    def write_frame(cnt):
+        wrote = False
+        held = set()
+        if raw is not None:
+            raw.store(frame_dir(out_dir, cnt), lambda dl: renderer.from_container(container, download=dl))
+            wrote = True
+        if surface is not None:   # the same splat: the raw frame's rgb is overwritten on the device once its file is written
+            if raw is None:
+                renderer.from_container(container, download=False)
+            surface.store(frame_dir(out_dir, cnt), lambda dl: renderer.surface(download=dl))
+            wrote = True
+        if sched.output_ply:
+            d = frame_dir(out_dir, cnt)
+            for f_body_id in container.object_id_fluid_body:
+                if exporter is not None:
+                    exporter.ply_object(container, f_body_id).write(f"{d}/particle_object_{f_body_id}.ply")
+                else:
+                    write_ply_ascii(f"{d}/particle_object_{f_body_id}.ply", container.dump(obj_id=f_body_id)["position"])
+                if args.reconstruct:   # what surface_reconstruction.py would make of that PLY, without reading it back
+                    if exporter is not None:   # the mesh stays on the device: formatted there, and the mesh frame below reads it there
+                        recon.from_container(container, f_body_id, download=False)
+                        exporter.obj_surface(recon).write(f"{d}/particle_object_{f_body_id}.obj")
                     else:
-                        write_ply_ascii(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.ply", container.dump(obj_id=f_body_id)["position"])
-                    if args.reconstruct:   # what surface_reconstruction.py would make of that PLY, without reading it back
-                        if exporter is not None:   # the mesh stays on the device: formatted there, and the mesh frame below reads it there
-                            recon.from_container(container, f_body_id, download=False)
-                            exporter.obj_surface(recon).write(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.obj")
-                        else:
-                            recon.from_container(container, f_body_id)
-                            recon.write_obj(f"{out_dir}/{cnt:06}/particle_object_{f_body_id}.obj")
-                        held = {f_body_id}   # the reconstructor still holds this object's mesh: the mesh frame below need not redo it
-                    wrote = True
-            if output_obj:   # run_simulation.py:146-150
-                os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
-                for r_body_id in container.object_id_rigid_body:
-                    if "mesh" not in container.object_collection[r_body_id]:   # body given as pre-voxelised points only
-                        continue
-                    with open(f"{out_dir}/{cnt:06}/mesh_object_{r_body_id}.obj", "w") as f:
-                        f.write(container.object_collection[r_body_id]["mesh"].export(file_type="obj"))
-                    wrote = True
-            if mesh_renderer is not None:   # render.py: every mesh of the frame -> {frame}/render.png
-                os.makedirs(f"{out_dir}/{cnt:06}", exist_ok=True)
-                meshes = frame_meshes(container, solver, recon, held)
-                store_png(f"{out_dir}/{cnt:06}/render.png", mesh_renderer, lambda dl: mesh_renderer.from_meshes(meshes, download=dl))
-                add_video_frame(mesh_renderer)
+                        recon.from_container(container, f_body_id)
+                        recon.write_obj(f"{d}/particle_object_{f_body_id}.obj")
+                    held = {f_body_id}   # the reconstructor still holds this object's mesh: the mesh frame below need not redo it
                 wrote = True
-            frames += 1 if wrote else 0
-            t_export += time.perf_counter() - te
-            cnt += 1
-        container.engine.synchronize()
-    finally:   # an exception in the loop still leaves well-formed videos of the frames written so far
-        for _, writer in videos.values():
-            writer.close()
-    dt = time.perf_counter() - t0
-    # frame export (ASCII PLY of every fluid particle, OBJ of every rigid mesh: run_simulation.py:137-150) is host file I/O and can
-    # dwarf the simulation -- 1.3 s per frame for the 1.23 M particles of final_scene0.json -- so it is reported apart from the steps
-    print(f"Simulation Finished: {cnt} steps, {container.particle_num[None]} particles, {1e3 * (dt - t_export) / cnt:.3f} ms/step "
-          f"(+ {t_export:.2f} s writing {frames} frame(s): {1e3 * dt / cnt:.3f} ms/step all in)")
+        if sched.output_obj:   # run_simulation.py:146-150
+            d = frame_dir(out_dir, cnt)
+            for r_body_id in container.object_id_rigid_body:
+                if "mesh" not in container.object_collection[r_body_id]:   # body given as pre-voxelised points only
+                    continue
+                with open(f"{d}/mesh_object_{r_body_id}.obj", "w") as f:
+                    f.write(container.object_collection[r_body_id]["mesh"].export(file_type="obj"))
+                wrote = True
+        if meshes_out is not None:
+            meshes = frame_meshes(container, solver, recon, held)
+            meshes_out.store(frame_dir(out_dir, cnt), lambda dl: mesh_renderer.from_meshes(meshes, download=dl))
+            wrote = True
+        return wrote
+
+    outputs = [o for o in (raw, surface, meshes_out) if o is not None]
+    t0 = time.perf_counter()
+    cnt, t_export, frames = run_loop(solver, container.engine, sched, sched.output_ply or sched.output_obj or outputs, write_frame,
+                                     [o.avi for o in outputs if o.avi is not None])
+    report(cnt, f"{container.particle_num[None]} particles", t0, t_export, frames)
     return container, solver
 
 

@@ -5,7 +5,6 @@ where a rendered frame already lies; the AVI container (AviWriter) and the PNG r
 code on the standard library.  No CPU fallback for the encoder."""
 from __future__ import annotations
 
-import ctypes as C
 import struct
 import zlib
 
@@ -21,9 +20,9 @@ class VideoError(L.SphError):
     pass
 
 
-class VideoEncoder(L.NativeObject):
+class VideoEncoder(L.FrameEncoder):
     """One JPEG encoder for frames of one size.  The bytes of a frame depend on (pixels, width, height, quality, chroma) alone."""
-    ABI, Error = "sph_video", VideoError
+    ABI, Error, Stats = "sph_video", VideoError, L.SphVideoStats
 
     def __init__(self, width, height, quality=90, chroma="420", device=-1, fast_math=False):
         super().__init__()
@@ -33,33 +32,6 @@ class VideoEncoder(L.NativeObject):
         p = L.SphVideoParams(width=self.width, height=self.height, quality=self.quality, chroma=CHROMA[self.chroma],
                              fast_math=int(bool(fast_math)), device=int(device), reserved=0)
         self.h = self._create(p)
-
-    def _download(self):
-        n = C.c_int64()
-        self._chk(self.lib.sph_video_size(self.h, C.byref(n)), "sph_video_size")
-        buf = np.empty(n.value, np.uint8)
-        self._chk(self.lib.sph_video_download(self.h, buf.ctypes.data), "sph_video_download")
-        return buf.tobytes()
-
-    def encode(self, rgb):
-        """The .jpg file of uint8 (height, width, 3)."""
-        a = np.ascontiguousarray(rgb, dtype=np.uint8)
-        if a.shape != (self.height, self.width, 3):
-            raise ValueError(f"encode: expected ({self.height}, {self.width}, 3), got {a.shape}")
-        self._chk(self.lib.sph_video_encode_rgb(self.h, a.ctypes.data), "sph_video_encode_rgb")
-        return self._download()
-
-    def encode_last(self, frame_renderer):
-        """The .jpg file of a FrameRenderer's last frame (particles or meshes), read from its device buffer."""
-        if frame_renderer._last is None:
-            raise VideoError("encode_last: the renderer holds no frame", L.ERR_INVALID)
-        self._chk(self.lib.sph_video_encode_render(self.h, frame_renderer._last), "sph_video_encode_render")
-        return self._download()
-
-    def stats(self):
-        st = L.SphVideoStats()
-        self._chk(self.lib.sph_video_stats(self.h, C.byref(st)), "sph_video_stats")
-        return L.struct_dict(st)
 
     def write_jpeg(self, path, rgb):
         with open(path, "wb") as f:

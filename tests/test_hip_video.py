@@ -106,6 +106,15 @@ def test_refusals_carry_messages(gpu):
         VideoEncoder(8, 8)._download()
     with pytest.raises(ValueError):
         v.encode(np.zeros((10, 10, 3), np.uint8))
+    v.close()
+    with pytest.raises(VideoError, match="closed"):
+        v.encode(np.zeros((240, 320, 3), np.uint8))
+    with pytest.raises(VideoError, match="closed"):
+        v.encode_last(_particle_renderer())
+    with pytest.raises(VideoError, match="closed"):
+        v.stats()
+    with pytest.raises(VideoError, match="closed"):
+        v._download()
 
 
 def test_c2_frame_at_full_size_equals_the_model(gpu):
