@@ -169,6 +169,8 @@ typedef struct {
     int64_t list_sorts;          /* deterministic sorts since create that ranked the particles from per-cell run lists filed by whoever
                                     hashed them (reorder_particles, base_container.py:506-515, in two launches: rank + gather with the
                                     per-tile preparation of the neighbour passes fused in) instead of run records filed after the scan */
+    int64_t carried_sorts;       /* list sorts since create whose gather left velocity + mass, meta word and particle id to the density
+                                    pass launched behind it (all-fluid unsharded WCSPH / PCISPH / IISPH steps; SPH_NO_SORT_CARRY=1: 0) */
     int32_t iter_iisph;          /* IISPH.py:185 refine: iterations of the last step (last SPH_PH_IISPH_ITERATION phase: 1) */
     float   err_iisph;           /* its density_error (IISPH.py:118-121; 0 with fixed_iterations > 0, as err_* of the others) */
     int64_t pbf_recentred;       /* PBF: refine walks of the last step (or phase) whose particle's current cell differed from its sorted cell

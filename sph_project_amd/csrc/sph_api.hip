@@ -825,7 +825,7 @@ extern "C" int sph_measure_copy_rate(SphHandle *h, size_t bytes, int reps, doubl
 
 // ---------------------------------------------------------------------------------- phases
 static int check_async(SphHandle *h) {
-    if (h->st.state_error) { const int se = h->st.state_error; h->st.state_error = 0; return fail(h, SPH_ERR_INVALID, "internal state error %d (a sort was scanned without a histogram of its own)", se); }
+    if (h->st.state_error) { const int se = h->st.state_error; h->st.state_error = 0; return fail(h, SPH_ERR_INVALID, "internal state error %d (bit 0: a sort was scanned without a histogram of its own; bit 1: a density launch could not move the arrays its sort left to it)", se); }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, SPH_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     return SPH_OK;
@@ -833,19 +833,22 @@ static int check_async(SphHandle *h) {
 
 // base_container.py:544 prepare_neighborhood_search
 // rho_dead: the kernel the caller launches next rewrites every particle's density (Launch::scatter_stable)
-static void ph_neighbor_search(SphHandle *h, bool rho_dead = false) {
+// density_next: that kernel is Launch::density over every tile; the SortCarry returned goes into its DensityOpts (SPH_NO_SORT_CARRY=1: never asked for)
+static SortCarry ph_neighbor_search(SphHandle *h, bool rho_dead = false, bool density_next = false) {
     State &s = h->st;
+    SortCarry carry;
     { ProfScope p(h, SPH_K_HASH_COUNT); h->L->hash_count(s); }
     { ProfScope p(h, SPH_K_SCAN); h->L->scan(s); }
-    { ProfScope p(h, SPH_K_SCATTER); if (h->prm.deterministic) h->L->scatter_stable(s, rho_dead); else h->L->scatter(s); }
+    { ProfScope p(h, SPH_K_SCATTER); if (h->prm.deterministic) carry = h->L->scatter_stable(s, rho_dead, density_next && !getenv("SPH_NO_SORT_CARRY")); else h->L->scatter(s); }
     h->sort_dirty = false;
+    return carry;
 }
 
 // the same without the hash kernel: the push transport's classify / unpack kernels have hashed every particle already
 static void ph_sort_hashed(SphHandle *h) {
     State &s = h->st;
     { ProfScope p(h, SPH_K_SCAN); h->L->scan(s); }
-    { ProfScope p(h, SPH_K_SCATTER); if (h->prm.deterministic) h->L->scatter_stable(s, false); else h->L->scatter(s); }
+    { ProfScope p(h, SPH_K_SCATTER); if (h->prm.deterministic) h->L->scatter_stable(s, false, false); else h->L->scatter(s); }
     h->sort_dirty = false;
 }
 
@@ -1150,6 +1153,7 @@ extern "C" int sph_get_stats(SphHandle *h, SphStats *out) {
     h->last.hash_launches = h->st.n_hash_launches;
     h->last.prehashed_sorts = h->st.n_prehashed_sorts;
     h->last.list_sorts = h->st.n_list_sorts;
+    h->last.carried_sorts = h->st.n_carried_sorts;
     if (h->st.pbf_recentred) {   // the bank of the last completed step (or phase)
         unsigned long long r[2];
         HIPCHK(h, hipMemcpy(r, h->st.pbf_recentred, sizeof(r), hipMemcpyDeviceToHost));

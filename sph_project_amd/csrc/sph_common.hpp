@@ -407,8 +407,11 @@ struct State {
     int run_lists_filed = 0;
     int *sort_inv = nullptr;
     long long n_list_sorts = 0;   // sorts that went through k_sort_rank + k_gather_prep, since create (SphStats)
+    long long n_carried_sorts = 0;   // ... whose velm / meta / pid the density pass behind them moved (SortCarry), since create (SphStats)
     // Bytes the sort's gather does not have to move (k_gather_prep, unsharded list sorts only):
     //  * a density that the kernel launched next recomputes for every particle: the caller of Launch::scatter_stable says so (rho_dead);
+    //  * velocity + mass, meta word and particle id where the kernel launched next is a density pass over every tile of an all-fluid scene
+    //    (density_next): that pass reads none of them, is far from any bandwidth limit and moves them itself (SortCarry);
     //  * colours stay AT HOME: color_home[particle id] is written when a particle is appended and never moves, while the ids are the append
     //    order (color_home_ok; ids set from outside or slab sharding end that).  color_stale: the sorted copy (State::color) is out of date --
     //    Launch::sorted_color brings it up to date for whoever needs it (download, a sort by run records, slab activation).
@@ -543,10 +546,26 @@ struct State {
     float4 *np_acc_out = nullptr;  // non-pressure acceleration sink (PCISPH), else null
 };
 
+// What a list sort's gather left behind for the density pass launched next (Launch::scatter_stable, density_next): thread d of a tile does
+// out[d] = in[inv[d]] for velocity + mass, meta word and particle id -- exactly what k_gather_prep does otherwise -- in the prologue of
+// k_nbr_pass<DensityPass<true, ...>>, on the memory round trips that prologue makes anyway.  Returned by the sort, handed to that ONE
+// density launch (DensityOpts::carry); on = 0: the gather moved everything.
+struct SortCarry {
+    const int *inv = nullptr;      // destination slot -> source particle (State::sort_inv)
+    const float4 *velm_in = nullptr; float4 *velm_out = nullptr;
+    const int *meta_in = nullptr; int *meta_out = nullptr;
+    const int *pid_in = nullptr; int *pid_out = nullptr;
+    int on = 0;
+};
+// the functor's member, as an empty base where the instantiation has nothing to carry (its kernel arguments stay what they were)
+template <bool ON> struct SortCarryOf { SortCarry carry; };
+template <> struct SortCarryOf<false> {};
+
 // Options of one launch (Launch::density, Launch::wcsph_forces)
 struct DensityOpts {
     int tiles = 0;             // slab sharding, compute / halo overlap: 0 every tile, 1 the boundary set, 2 the interior set (State::tile_list)
     bool books_forces = false; // WCSPH step with the fused force pass: the density pass counts that pass's pairs too (it walks the same masks)
+    SortCarry carry = {};      // the sort in front of this launch left velm / meta / pid for it to move (it said so: Launch::scatter_stable)
 };
 struct ForceOpts {
     bool booked_by_density = false;   // the density pass in front of this one has counted its pairs (DensityOpts::books_forces); else it counts its own
@@ -561,7 +580,10 @@ struct Launch {
     void (*scatter)(State &);                   // carries every array
     // rho_dead: the kernel launched next rewrites the density of every particle, so the gather need not carry it (list sorts of all-fluid
     // scenes drop it; the new rho.cur() then holds garbage until that kernel has run -- 0xFF bytes in the test-hook library)
-    void (*scatter_stable)(State &, bool rho_dead);
+    // density_next: the kernel launched next is a DensityPass over every tile (Launch::density with tiles = 0), so an all-fluid list sort
+    // leaves velm / meta / pid to it.  The SortCarry returned says whether it did (on) and MUST then go into that launch's DensityOpts:
+    // until that pass has run, velm.cur() / meta.cur() / pid.cur() hold garbage (0xFF bytes in the test-hook library).
+    SortCarry (*scatter_stable)(State &, bool rho_dead, bool density_next);
     void (*density)(State &, int eos, DensityOpts o);
     void (*non_pressure)(State &, const float4 *visc_vel);   // visc_vel: velocities for the viscous term (implicit viscosity: cg_x), null: the particles' own
     void (*pressure_integrate)(State &);

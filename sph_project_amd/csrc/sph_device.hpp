@@ -615,6 +615,10 @@ template <class P> struct PassStatW<P, decltype((void)P::STAT_W)> { static const
 // epilogue does for the next step's sort what k_hash_count would do (WcsphForcePass)
 template <class P, class = void> struct PassNextHash { static constexpr bool value = false; };
 template <class P> struct PassNextHash<P, decltype((void)P::NEXT_HASH)> { static constexpr bool value = P::NEXT_HASH; };
+// P::SORT_CARRY: the functor carries a SortCarry `carry`: when carry.on, the kernel's prologue moves velocity + mass, meta word and particle
+// id of its tile from the order before the sort into the sorted one (the all-fluid DensityPass, launched right behind k_gather_prep)
+template <class P, class = void> struct PassSortCarry { static constexpr bool value = false; };
+template <class P> struct PassSortCarry<P, decltype((void)P::SORT_CARRY)> { static constexpr bool value = P::SORT_CARRY; };
 template <class P, class = void> struct PassPrologue { static constexpr bool value = false; };
 template <class P> struct PassPrologue<P, decltype((void)P::HAS_PROLOGUE)> { static constexpr bool value = P::HAS_PROLOGUE; };
 
@@ -993,11 +997,13 @@ k_gather_prep(const Consts c, int n, const int *__restrict__ inv, SortArrays a, 
     if (d < n) {
         const int i = inv[d];
         p = a.posv_in[i];
-        meta_i = a.meta_in[i];
         a.posv_out[d] = p;
-        a.velm_out[d] = a.velm_in[i];
-        a.meta_out[d] = meta_i;
-        a.pid_out[d] = a.pid_in[i];
+        if (a.velm_in) {   // (null, all three: the density pass launched next moves them, SortCarry; an all-fluid tile is prepared without its meta words)
+            meta_i = a.meta_in[i];
+            a.velm_out[d] = a.velm_in[i];
+            a.meta_out[d] = meta_i;
+            a.pid_out[d] = a.pid_in[i];
+        }
         if (a.color_in) a.color_out[d] = a.color_in[i];   // (null: the colours stay at home, State::color_home)
         if (a.rho_in) a.rho_out[d] = a.rho_in[i];         // (null: the next kernel recomputes every density, Launch::scatter_stable)
         if (a.orig_in) a.orig_out[d] = a.orig_in[i];
@@ -1205,6 +1211,18 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
     const int cfirst = hdr[0], clast = hdr[1];
     const int skip_tile = tile_skip ? (int)tile_skip[b] : 0;
     const int n_live = live_n(c);
+    // Sort carry (P::SORT_CARRY; unsharded launches over every tile, so c.n is exact): slot d = i0 + tid of this tile takes velm / meta / pid
+    // of source particle inv[d].  inv[d] travels with the header; the three loads that depend on it go out below, in front of the
+    // cell_start windows, and are stored behind the prologue's barrier (below) -- no memory round trip of its own.  Clamped index, no
+    // load under a divergent `if` (see below); slots past n store nothing.
+    int carry_d = 0;
+    unsigned carry_src = 0u;   // (unsigned: a sign extension would wait for the load right here)
+    if constexpr (PassSortCarry<P>::value) {
+        if (p.carry.on) {
+            carry_d = i0 + tid;
+            carry_src = (unsigned)p.carry.inv[carry_d < c.n ? carry_d : c.n - 1];
+        }
+    }
     if constexpr (PassWrench<P>::value) wrench_init_all(p.pose);   // (published by the prologue's barrier)
     if constexpr (PassPrologue<P>::value) { if (!p.prologue(scal)) return; }   // workgroup-uniform
     if (i0 >= n_live) {   // launch bound of an asynchronous slab step: no such tile (its header was never written)
@@ -1243,6 +1261,11 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
     const float4 pi = p.posv[ic];
     Own own;
     bool active = p.begin(c, ic, pi, own) && valid;
+    float4 carry_v = make_float4(0.f, 0.f, 0.f, 0.f);
+    int carry_m = 0, carry_p = 0;
+    if constexpr (PassSortCarry<P>::value) {
+        if (p.carry.on) { carry_v = p.carry.velm_in[carry_src]; carry_m = p.carry.meta_in[carry_src]; carry_p = p.carry.pid_in[carry_src]; }
+    }
     unsigned mk0[3] = {0u, 0u, 0u};   // first mask words of the first group's runs
     if (MASKMODE == 2 && pass_mask_pipe<P>()) {
         const int g0 = (PassSplit<P>::value && gridDim.y > 1) ? split_lo((int)gridDim.y, (int)blockIdx.y) : 0;
@@ -1274,7 +1297,17 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
     const int e1 = e0 + (int)((cw >> 8) & 7u);
     const unsigned dom = cw >> 11;
     if (skip_tile) return;   // (uniform)
-    if (__syncthreads_or(active ? 1 : 0)) {  // workgroup-uniform; also publishes s_cs
+    if constexpr (PassSortCarry<P>::value) {
+        // Every wave waits for its prologue loads HERE, where the waves with a share of the windows have waited already: the carried
+        // values, and the cell word and position too.  A load left pending gets its wait behind the stores below (vmcnt counts both, in
+        // order), and that wait would be a write round trip per workgroup in front of the first staging round.
+        asm volatile("" :: "v"(cw), "v"(pi.w), "v"(carry_v.x), "v"(carry_m), "v"(carry_p));
+    }
+    const int any_active = __syncthreads_or(active ? 1 : 0);   // workgroup-uniform; also publishes s_cs
+    if constexpr (PassSortCarry<P>::value) {   // behind the barrier: the next wait is the first staging round's, whose loads are younger than these stores
+        if (p.carry.on && carry_d < c.n) { p.carry.velm_out[carry_d] = carry_v; p.carry.meta_out[carry_d] = carry_m; p.carry.pid_out[carry_d] = carry_p; }
+    }
+    if (any_active) {
         NBR_STAMP(1);
         unsigned npairs = 0;
         // split launch (uniform): this workgroup walks the x-offset groups [g_lo, g_hi) only -- one of three, or {0, 1} / {2} of a two-way split

@@ -134,10 +134,11 @@ unsigned *l_sorted_color(State &s) {
     return s.color.cur();
 }
 
-// rho_dead: the kernel launched next rewrites every particle's density (Launch::scatter_stable)
-void l_scatter_impl(State &s, bool stable, bool rho_dead) {
+// rho_dead: the kernel launched next rewrites every particle's density; density_next: it is a DensityPass over every tile (Launch::scatter_stable)
+SortCarry l_scatter_impl(State &s, bool stable, bool rho_dead, bool density_next) {
     const int n = s.c.n;
-    if (n == 0) return;
+    SortCarry carry;
+    if (n == 0) return carry;
     SortArrays a;
     a.G = s.c.G;
     a.posv_in = s.posv.cur(); a.posv_out = s.posv.alt();
@@ -154,11 +155,20 @@ void l_scatter_impl(State &s, bool stable, bool rho_dead) {
     a.color_in = by_lists ? s.color.cur() : l_sorted_color(s);   // (k_scatter moves State::color)
     s.run_lists_filed = 0;
     const bool skip_rho = by_lists && rho_dead && s.c.all_fluid;
+    // (all fluid: no blk_flag, so the tile preparation needs no meta word; an unsharded scene has neither a slab nor tile lists)
+    carry.on = by_lists && density_next && s.c.all_fluid && !s.tile_list[0];
     if (by_lists) {
-        // bytes that need not move: the colours (at home, keyed by the particle id, while the ids are the append order) and a density that
-        // the next kernel recomputes for every particle
+        // bytes that need not move: the colours (at home, keyed by the particle id, while the ids are the append order), a density that
+        // the next kernel recomputes for every particle, and what the density pass launched next moves under its own walk (SortCarry)
         if (s.color_home && s.color_home_ok) { a.color_in = nullptr; s.color_stale = 1; }
         if (skip_rho) a.rho_in = nullptr;
+        if (carry.on) {
+            carry.inv = s.sort_inv;
+            carry.velm_in = a.velm_in; carry.velm_out = a.velm_out;
+            carry.meta_in = a.meta_in; carry.meta_out = a.meta_out;
+            carry.pid_in = a.pid_in; carry.pid_out = a.pid_out;
+            a.velm_in = nullptr; a.meta_in = nullptr; a.pid_in = nullptr;
+        }
         hipLaunchKernelGGL(k_sort_rank, dim3(cdiv(n, 256)), dim3(256), 0, s.stream, n, s.cellid, s.cell_start,
                            RunList{s.run_head, s.run_rec, s.cap, s.sort_epoch}, s.sort_inv);
         const bool lst = !s.c.all_fluid && s.blk_list;
@@ -179,15 +189,22 @@ void l_scatter_impl(State &s, bool stable, bool rho_dead) {
 #ifdef SPH_TEST_HOOKS
     // test-hook library only: a density the gather dropped reads as NaN until the kernel that was promised has rewritten it
     if (skip_rho) hipMemsetAsync(s.rho.cur(), 0xFF, sizeof(float) * (size_t)n, s.stream);
+    // ... and so do velocity + mass, meta word and particle id left to the density pass that was promised
+    if (carry.on) {
+        hipMemsetAsync(s.velm.cur(), 0xFF, sizeof(float4) * (size_t)n, s.stream);
+        hipMemsetAsync(s.meta.cur(), 0xFF, sizeof(int) * (size_t)n, s.stream);
+        hipMemsetAsync(s.pid.cur(), 0xFF, sizeof(int) * (size_t)n, s.stream);
+    }
 #endif
     s.masks_valid = 0;  // new order, new candidate runs
     if (!s.slab_active) l_block_prep(s, !by_lists);
     else s.perm_n = s.list_n = -1;   // slab sharding: rebuilt once the dead particles behind the live ones are dropped (launch_pass)
     if (s.orig.cur()) s.orig.flip();
     if (s.slab_active) s.xcur = 1 - s.xcur;
+    return carry;
 }
-void l_scatter(State &s) { l_scatter_impl(s, false, false); }
-void l_scatter_stable(State &s, bool rho_dead) { l_scatter_impl(s, true, rho_dead); }
+void l_scatter(State &s) { l_scatter_impl(s, false, false, false); }
+SortCarry l_scatter_stable(State &s, bool rho_dead, bool density_next) { return l_scatter_impl(s, true, rho_dead, density_next); }
 
 // Workgroups a launch over the list of fluid-holding tiles needs: the list's length once the host has seen it (State::list_count_pinned),
 // one per tile of the scene until then (the kernels send the surplus home at their top).  Never zero: a functor whose prologue keeps a
@@ -271,12 +288,21 @@ void l_density(State &s, int eos, DensityOpts o) {
     if (!eos) fs.on = 0;
     s.fieldsend.on = 0;
     const int sp = o.books_forces ? 1 + 3 : 1, se = o.books_forces ? 2 : 1;   // (WcsphForcePass: PAIR_WEIGHT 3, one evaluation per pair)
+    SortCarry carry = o.carry;
+    // the sort left velm / meta / pid to THIS launch on the caller's word that it walks every tile of an all-fluid scene: anything else
+    // is a bug in the step orchestration (the three arrays would stay unsorted)
+    if (carry.on && (!s.c.all_fluid || o.tiles != 0 || s.c.n == 0)) { s.state_error |= 2; carry.on = 0; }
+#ifdef SPH_TEST_HOOKS
+    // test-hook library only: SPH_TEST_DROP_CARRY=1 breaks the promise -- the step ends with the 0xFF bytes l_scatter_impl left
+    if (getenv("SPH_TEST_DROP_CARRY")) carry.on = 0;
+#endif
+    if (carry.on) s.n_carried_sorts++;
     if (s.c.all_fluid) {
-        if (eos) { DensityPass<true, true> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
-        else { DensityPass<true, false> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
+        if (eos) { DensityPass<true, true> p{{carry}, s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
+        else { DensityPass<true, false> p{{carry}, s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
     } else {
-        if (eos) { DensityPass<false, true> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
-        else { DensityPass<false, false> p{s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
+        if (eos) { DensityPass<false, true> p{{}, s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
+        else { DensityPass<false, false> p{{}, s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
     }
 }
 

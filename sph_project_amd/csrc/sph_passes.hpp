@@ -53,7 +53,7 @@ __device__ __forceinline__ void add_wrench(DevScalars *, int obj, float fx, floa
 // base_solver.py:522 compute_density (+task :535); with EOS also WCSPH.py:17 compute_pressure.
 // Algorithmic HBM bytes / particle: R posv 16 -> W rho 4 (+ rho_raw 4, prs 4, ptm 4 with EOS).
 template <bool AF, bool EOS>
-struct DensityPass {
+struct DensityPass : SortCarryOf<AF> {
     static constexpr int MODES = 0b011;               // first pass after a sort: computes and stores the acceptance masks
     static constexpr bool FLUID_BLOCKS_ONLY = true;   // active for fluid only, passive() empty
     static constexpr int BLOCK = 256, GROUPS = 3;
@@ -68,6 +68,9 @@ struct DensityPass {
     HaloFieldSend fs;   // slab sharding (EOS form only): boundary values go straight into the neighbours' field message; fs.on = 0 otherwise
     static constexpr bool STAT_W = true;
     int stat_pairs, stat_evals;   // weights of this walk's accepted pairs in the pair statistics (1, 1; 4, 2 when it books the fused force pass too)
+    // All fluid: the pass reads neither velocities, meta words nor ids, so a list sort launched right in front of it leaves those three
+    // arrays to the prologue of this walk (k_nbr_pass), which has the memory system to itself: SortCarryOf<true>::carry, on = 0: nothing to move
+    static constexpr bool SORT_CARRY = AF;
 
     __device__ float4 loadA(int j) const { return posv[j]; }
     __device__ BT loadB(int) const { return 0; }

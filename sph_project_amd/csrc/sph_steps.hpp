@@ -190,8 +190,9 @@ static int wcsph_step(SphHandle *h) {
     // sharded: + migration / ghost exchange; over the push transport a plain WCSPH step needs nothing back from the device
     // (slab_neighbor_search_push, "async"): implicit viscosity and the unfused force passes launch exact grids instead
     const bool fused = !h->prm.viscosity_implicit;
+    SortCarry carry;   // what the sort leaves to the density pass below (unsharded: that pass is the next launch and walks every tile)
     if (s.slab_active) { int rc = slab_neighbor_search(h, fused); if (rc) return rc; }
-    else ph_neighbor_search(h, true);                                         // WCSPH.py:28 (the density pass below rewrites every rho: the sort need not move it)
+    else carry = ph_neighbor_search(h, true, true);                           // WCSPH.py:28 (the density pass below rewrites every rho: the sort need not move it)
     ph_rigid_volume(h);                                                       // base_solver.py:696 (see ph_rigid_volume)
     const bool books = fused && !getenv("SPH_FORCES_COUNT_OWN");   // (switch: the force pass counts its own pairs -- the counting instantiation any other caller of l_wcsph_forces gets)
     // Sharded over the push transport, fluid only: the density pass runs the slab's BOUNDARY tiles first, their rho / p go out to the
@@ -212,7 +213,7 @@ static int wcsph_step(SphHandle *h) {
         { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1, {0, books}); }   // :29 + :33 (EOS fused)
         { ProfScope p(h, SPH_K_HALO); h->L->halo_pull_fields(s, 2, nullptr, nullptr, hint); }
     } else {
-        { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1, {0, books}); }   // :29 + :33 (EOS fused)
+        { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 1, {0, books, carry}); }   // :29 + :33 (EOS fused)
         if (s.slab_active) { int rc = slab_exchange_fields(h); if (rc) return rc; }   // ghost rho, p
     }
     if (fused) {
@@ -336,10 +337,11 @@ static int pcisph_refine(SphHandle *h) {
 
 static int pcisph_step(SphHandle *h) {
     State &s = h->st;
+    SortCarry carry;
     if (s.slab_active) { int rc = slab_neighbor_search(h); if (rc) return rc; }   // + migration / ghost exchange
-    else ph_neighbor_search(h, true);                                         // PCISPH.py:166 (:167 below rewrites every rho)
+    else carry = ph_neighbor_search(h, true, true);                           // PCISPH.py:166 (:167 below rewrites every rho and moves what the sort leaves to it)
     ph_rigid_volume(h);
-    { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 0, {}); }               // :167
+    { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 0, {0, false, carry}); } // :167
     if (s.slab_active) { int rc = slab_exchange_scalar(h, s.rho.cur()); if (rc) return rc; }   // ghost densities (viscosity)
     int rc = run_non_pressure(h); if (rc) return rc;                          // :168 (+ :174, v* kept aside)
     { ProfScope p(h, SPH_K_MISC); h->L->pcisph_init(s); }                     // :169
@@ -371,9 +373,9 @@ static int iisph_refine(SphHandle *h) {
 // boundary (:218-220, :227: the same tail as PCISPH's)
 static int iisph_step(SphHandle *h) {
     State &s = h->st;
-    ph_neighbor_search(h, true);                                              // :204 (:205 below rewrites every rho)
+    const SortCarry carry = ph_neighbor_search(h, true, true);                // :204 (:205 below rewrites every rho and moves what the sort leaves to it)
     ph_rigid_volume(h);
-    { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 0, {}); }               // :205
+    { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 0, {0, false, carry}); } // :205
     int rc = run_non_pressure(h); if (rc) return rc;                          // :207-208
     { ProfScope p(h, SPH_K_IISPH_PREPARE); h->L->iisph_prepare(s); }          // :206, :210-213
     rc = iisph_refine(h); if (rc) return rc;                                  // :215
