@@ -609,7 +609,8 @@ int sph_render_composite_stats(SphRender *r, SphRenderCompositeStats *out);
    base (ambient + max(n.L, 0) light_rgb) + spec light_rgb max(n.h, 0)^shininess, h the half vector of the directions to the light and
    to the eye; clamped, floor(255 x + 0.5).  Every other pixel keeps the bytes of the particle frame.  While the mode is on,
    sph_render_points / _handle also fill the base plane (colour and flag per pixel); sph_render_surface then needs no particle.
-   Not done: thickness / absorption, refraction, the narrow-range filter's one-sided clamp, anti-aliasing, sharded frames. */
+   Thickness and absorption: sph_render_set_thickness below.
+   Not done: refraction, Fresnel, the narrow-range filter's one-sided clamp, anti-aliasing, sharded frames. */
 typedef struct {
     int32_t iterations;       /* 0..64 (3) */
     int32_t rmax;             /* largest window half-width in pixels, 1..16 (12) */
@@ -648,6 +649,50 @@ int sph_render_surface(SphRender *r);
 /* the final integer depth plane of the last sph_render_surface: q u32[height][width], SPH_RENDER_SURFACE_SENTINEL elsewhere */
 int sph_render_surface_download_depth(SphRender *r, uint32_t *q);
 int sph_render_surface_stats(SphRender *r, SphRenderSurfaceStats *out);
+
+/* --- thickness mode of the surface frames: what lies behind the fluid shows through -------------------------------- */
+/* opt-in on top of the surface mode.  While it is on, sph_render_points / _handle also draw (1) the opaque layer: the frame the ordinary
+   renderer would draw from the particles that are not surface particles plus the box lines, as a key plane (float_bits(t) << 32 | id,
+   all ones where nothing won) with its rgb; (2) the thickness plane: every surface sphere, per pixel centre of its bounds, with the ray's
+   chord [t0, t1] = k -+ sqrt(h / dd) (the quantities of the hit test, evaluated without contraction: the same bits in both builds),
+   counted when h >= 0 and t0 > z_near, its far end b = min(t1, t_opaque), adds (u32)((b - t0) * inv_u) when b > t0 -- at most 512, summed
+   in u32 with integer atomics, so the plane is a function of the particle set.  sph_render_surface then smooths it (`iterations` Jacobi
+   steps, the depth stage's integer tent with R_i from the final smoothed depth, every surface pixel of the window a tap, no range test)
+   and composites per surface pixel and channel, in f32 without contraction:
+     Tr = max(T, 1) / 256,  tau = (absorb (1 - base / 255) + scatter) Tr,  a = exp2(-tau),
+     out = byte((behind a + lit (1 - a)) + highlight),  behind = opaque rgb / 255,  lit and highlight the two terms of the surface mode.
+   absorb = scatter = 0 and spec = 0: the opaque layer's bytes; a very large scatter: the bytes of the surface mode without thickness.
+   A frame of more than 2^23 particles is refused while the mode is on (SPH_ERR_UNSUPPORTED, before any launch). */
+typedef struct {
+    float absorb;             /* per particle radius of fluid, scaled by 1 - base colour: what the fluid's colour takes away, >= 0 (0.05) */
+    float scatter;            /* per particle radius of fluid, every channel alike, >= 0 (0.01) */
+    int32_t iterations;       /* smoothing iterations of the thickness plane, 0..64 (2) */
+} SphRenderThicknessParams;
+
+typedef struct {
+    int64_t adds;             /* (sphere, pixel) pairs that added to the plane: one integer atomic each */
+    int64_t clipped;          /* of these: cut short by the opaque depth */
+    int64_t removed;          /* pairs that hit but lay wholly behind the opaque depth (no atomic) */
+    int64_t empty_pixels;     /* surface pixels whose summed thickness is 0 (they are composited with T = 1) */
+    int64_t max_thickness;    /* the largest smoothed T */
+    int64_t iterations;       /* smoothing iterations run */
+    int64_t taps_visited;     /* (2 R_i + 1)^2 summed over surface pixels and iterations */
+    double ms_opaque;         /* HIP events: the opaque layer and ... */
+    double ms_splat;          /* ... the thickness splat (parts of the frame call) */
+    double ms_smooth;         /* the thickness smoothing and ... */
+    double ms_shade;          /* ... the composite (parts of sph_render_surface, within its ms_shade) */
+} SphRenderThicknessStats;
+
+/* switches the mode on (params) or off (NULL); applies to the frames drawn afterwards.  SPH_ERR_INVALID, with a message that names the
+   field: absorb / scatter negative or not finite, iterations outside 0..64; also when the surface mode is off.  Switching the surface
+   mode off switches this off too.  While it is on, sph_render_surface refuses a frame drawn before it was switched on. */
+int sph_render_set_thickness(SphRender *r, const SphRenderThicknessParams *params_or_NULL);
+/* of the last sph_render_surface: the smoothed plane T u32[height][width] in units of radius / 256 of view depth, 0 on non-surface
+   pixels; raw != 0: the plane as the splat summed it */
+int sph_render_surface_download_thickness(SphRender *r, uint32_t *T, int raw);
+/* the opaque layer of the last particle frame, as sph_render_layer_download gives the frame's */
+int sph_render_surface_download_opaque(SphRender *r, uint64_t *key, uint8_t *rgb);
+int sph_render_thickness_stats(SphRender *r, SphRenderThicknessStats *out);
 
 /* --- mesh rendering: an ordered list of triangle meshes -> one RGB frame ------------------------------------------ */
 /* stands in for the reference's render.py + rendering_script.py (every .obj of a frame directory through a Blender scene ->

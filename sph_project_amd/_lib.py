@@ -158,6 +158,18 @@ class SphRenderSurfaceStats(C.Structure):
     ]
 
 
+class SphRenderThicknessParams(C.Structure):
+    _fields_ = [("absorb", C.c_float), ("scatter", C.c_float), ("iterations", C.c_int32)]
+
+
+class SphRenderThicknessStats(C.Structure):
+    _fields_ = [
+        ("adds", C.c_int64), ("clipped", C.c_int64), ("removed", C.c_int64), ("empty_pixels", C.c_int64), ("max_thickness", C.c_int64),
+        ("iterations", C.c_int64), ("taps_visited", C.c_int64), ("ms_opaque", C.c_double), ("ms_splat", C.c_double),
+        ("ms_smooth", C.c_double), ("ms_shade", C.c_double),
+    ]
+
+
 class SphRenderMeshStats(C.Structure):
     _fields_ = [
         ("meshes", C.c_int64), ("triangles", C.c_int64), ("vertices", C.c_int64), ("large", C.c_int64),
@@ -312,6 +324,10 @@ _SIGNATURES = [
     ("sph_render_surface", C.c_int, [_VP]),
     ("sph_render_surface_download_depth", C.c_int, [_VP, _VP]),
     ("sph_render_surface_stats", C.c_int, [_VP, C.POINTER(SphRenderSurfaceStats)]),
+    ("sph_render_set_thickness", C.c_int, [_VP, C.POINTER(SphRenderThicknessParams)]),
+    ("sph_render_surface_download_thickness", C.c_int, [_VP, _VP, C.c_int]),
+    ("sph_render_surface_download_opaque", C.c_int, [_VP, _VP, _VP]),
+    ("sph_render_thickness_stats", C.c_int, [_VP, C.POINTER(SphRenderThicknessStats)]),
     ("sph_render_mesh_begin", C.c_int, [_VP]),
     ("sph_render_mesh_add", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP]),
     ("sph_render_mesh_add_surface", C.c_int, [_VP, _VP, _VP]),

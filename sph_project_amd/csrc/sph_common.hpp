@@ -294,6 +294,23 @@ struct RenderSurfDev {
     float spec, shin;
 };
 
+// Thickness mode of the surface frames (sph_render_thickness.hpp): the opaque layer -- a key / rgb plane pair with counters
+// and a large list of its own, drawn from what is not a surface particle -- the thickness planes and the coefficients of the composite.
+// T[0]: the splat's sums (units of u per pixel, view depth), T[1]: the first plane of the smoothing ping-pong, whose second is the idle
+// depth plane of RenderSurfDev.  cnt: two groups of RSURF_CNT_BANKS banks of 8 words, banked as RenderSurfDev::cnt.  Group 0, the frame
+// call: [0] adds issued, [1] pairs the opaque depth cut short, [2] pairs it removed.  Group 1, the surface call: [0] taps visited,
+// [1] surface pixels whose summed thickness is 0, [2] the largest smoothed thickness (atomicMax).
+#define RTHICK_MAX_PARTICLES (1 << 23)   // contributions of at most 512 each in a u32
+struct RenderThickDev {
+    unsigned long long *okey;          // [W H]
+    unsigned char *orgb;               // [H][W][3]
+    unsigned long long *ocnt;          // [8] the opaque layer's RenderDev::cnt
+    int *olarge;                       // [n]
+    unsigned *T[2];                    // [W H] each
+    unsigned long long *cnt;           // [2][RSURF_CNT_BANKS][8]
+    float absorb, scatter;
+};
+
 // Mesh rendering (sph_render_mesh.hpp): the frame's meshes, concatenated.  Triangle g of the frame belongs to the last
 // record with t0 <= g; its indices are local to that mesh's nv vertices, which start at slot v0 of vert / nrm.  The frame buffers,
 // camera and counters are the RenderDev's: cnt[0] triangles that passed the hit test at some pixel centre (whether or not they won it), [1] non-finite, [2] large,
@@ -654,6 +671,11 @@ struct Launch {
     void (*render_surface_quantise)(RenderDev &, RenderSurfDev &);  // key plane -> integer depth in both q planes, surface pixels counted
     void (*render_surface_smooth)(RenderDev &, RenderSurfDev &, int it);   // iteration it: q[it & 1] -> q[1 - (it & 1)]
     void (*render_surface_shade)(RenderDev &, RenderSurfDev &, int plane); // normals off q[plane], colour into rgb where the flag is set
+    // thickness mode of the surface frames (sph_render_thickness.hpp)
+    void (*render_thick_opaque)(RenderDev &, RenderSurfDev &, RenderThickDev &);   // the opaque layer: splat, shade, lines, finish on a copy
+    void (*render_thick_splat)(RenderDev &, RenderSurfDev &, RenderThickDev &);    // T[0] = sum of the surface spheres' chords per pixel
+    void (*render_thick_smooth)(RenderDev &, RenderSurfDev &, RenderThickDev &, const unsigned *Q, const unsigned *in, unsigned *out);
+    void (*render_thick_shade)(RenderDev &, RenderSurfDev &, RenderThickDev &, const unsigned *Q, const unsigned *T);   // the composite
     // mesh rendering (sph_render_mesh.hpp)
     void (*render_mesh_depth)(RenderDev &, MeshDev &);   // depth keys of triangles (small per thread, large per workgroup) and box lines
     void (*render_mesh_shade)(RenderDev &, MeshDev &);   // the winners' colours (triangles, lines)

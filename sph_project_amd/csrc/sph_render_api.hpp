@@ -5,8 +5,10 @@
 #include <climits>
 
 // the frame buffers, the particle list (large: also the mesh frames' triangle list) and the mesh lists
-// and an incoming layer; RB_S*: the planes of the surface mode, allocated when the mode is first used
-enum RendBufId { RB_KEY, RB_RGB, RB_IDS, RB_CNT, RB_LARGE, RB_POS, RB_IDV, RB_COL, RB_MVERT, RB_MNRM, RB_MTRI, RB_MREC, RB_LKEY, RB_LRGB, RB_SBASE, RB_SQ0, RB_SQ1, RB_SCNT, RB_SMASK, RB_COUNT_ };
+// and an incoming layer; RB_S*: the planes of the surface mode, RB_T*: those of its thickness mode
+// (DESIGN.md 25), each allocated when the mode is first used
+enum RendBufId { RB_KEY, RB_RGB, RB_IDS, RB_CNT, RB_LARGE, RB_POS, RB_IDV, RB_COL, RB_MVERT, RB_MNRM, RB_MTRI, RB_MREC, RB_LKEY, RB_LRGB, RB_SBASE, RB_SQ0, RB_SQ1, RB_SCNT, RB_SMASK,
+                 RB_TOKEY, RB_TORGB, RB_TOCNT, RB_TOLARGE, RB_TT0, RB_TT1, RB_TCNT, RB_COUNT_ };
 
 // what the renderer holds.  RF_ON_RANK0: the last frame was composited over a communicator and lies on rank 0, not here; RF_MESH: a mesh
 // frame has no layer (triangle indices do not compose)
@@ -35,6 +37,15 @@ struct SphRender : DevObj {   // clk[0]: a particle frame's stages, clk[1]: a me
     std::vector<uint8_t> pmask;   // sph_render_points_surface_mask: for the next sph_render_points
     bool pmask_set = false;
     SphRenderSurfaceStats sstats{};
+    // thickness mode: tclk marks 0 / 1 / 2 around the opaque layer and the splat, 3 / 4 / 5 smooth / composite
+    bool thick_on = false;
+    bool thick_valid = false;     // the opaque layer and the summed plane belong to the frame held
+    bool thick_shaded = false;    // sph_render_surface has run on them
+    const unsigned *thick_plane = nullptr;   // the smoothed plane of that call
+    SphRenderThicknessParams tprm{};
+    RenderThickDev td{};
+    StageClock tclk;
+    SphRenderThicknessStats tstats{};
 };
 
 static bool rend_finite3(const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
@@ -153,6 +164,7 @@ extern "C" void sph_render_destroy(SphRender *r) {
     hipSetDevice(r->device);
     if (r->stream) hipStreamSynchronize(r->stream);
     for (hipEvent_t e : r->sclk.ev) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : r->tclk.ev) if (e) hipEventDestroy(e);
     devobj_close(r, r->buf, RB_COUNT_);
     delete r;
 }
@@ -205,10 +217,53 @@ static int rsurf_room(SphRender *r) {
     return SPH_OK;
 }
 
+// thickness mode: the opaque layer, the thickness planes, counters and clock on first use; the large list follows the particle count
+static int rthick_room(SphRender *r) {
+    const size_t px = (size_t)r->d.W * r->d.H;
+    DevBuf *b = r->buf;
+    int rc = b[RB_TOKEY].reserve(r, px * 8);
+    if (!rc) rc = b[RB_TORGB].reserve(r, px * 3);
+    if (!rc) rc = b[RB_TOCNT].reserve(r, 64);
+    if (!rc) rc = b[RB_TOLARGE].reserve(r, (size_t)std::max(r->d.n, 1) * 4);
+    if (!rc) rc = b[RB_TT0].reserve(r, px * 4);
+    if (!rc) rc = b[RB_TT1].reserve(r, px * 4);
+    if (!rc) rc = b[RB_TCNT].reserve(r, 2 * RSURF_CNT_BANKS * 64);
+    if (rc) return rc;
+    if (!r->tclk.stream) {
+        for (hipEvent_t &e : r->tclk.ev) HIPCHK(r, hipEventCreate(&e));
+        r->tclk.stream = r->stream;
+    }
+    RenderThickDev &t = r->td;
+    t.okey = (unsigned long long *)b[RB_TOKEY].p; t.orgb = (unsigned char *)b[RB_TORGB].p;
+    t.ocnt = (unsigned long long *)b[RB_TOCNT].p; t.olarge = (int *)b[RB_TOLARGE].p;
+    t.T[0] = (unsigned *)b[RB_TT0].p; t.T[1] = (unsigned *)b[RB_TT1].p;
+    t.cnt = (unsigned long long *)b[RB_TCNT].p;
+    return SPH_OK;
+}
+
+// the sum over the banks of counter group g
+static int rthick_counters(SphRender *r, int g, unsigned long long c[8], bool max_word2) {
+    unsigned long long bank[RSURF_CNT_BANKS][8];
+    HIPCHK(r, hipMemcpyAsync(bank, r->td.cnt + (size_t)g * RSURF_CNT_BANKS * 8, sizeof(bank), hipMemcpyDeviceToHost, r->stream));
+    HIPCHK(r, hipStreamSynchronize(r->stream));
+    HIPCHK(r, hipGetLastError());
+    for (int w = 0; w < 8; ++w) c[w] = 0;
+    for (int b = 0; b < RSURF_CNT_BANKS; ++b)
+        for (int w = 0; w < 8; ++w) c[w] = (max_word2 && w == 2) ? std::max(c[w], bank[b][w]) : c[w] + bank[b][w];
+    return SPH_OK;
+}
+
 // after the source is set in d and stage mark 0 recorded: clear, splat, shade; synchronous
 static int rend_run(SphRender *r, int64_t n_in) {
     RenderDev &d = r->d;
     StageClock &k = r->clk[0];
+    const bool thick = r->surf_on && r->thick_on;
+    r->thick_valid = r->thick_shaded = false;
+    if (thick && n_in > (int64_t)RTHICK_MAX_PARTICLES) {
+        HIPCHK(r, hipStreamSynchronize(r->stream));   // (the points path's uploads: the caller's vectors are free again)
+        return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_set_thickness: %lld particles in the frame, a pixel's u32 thickness holds %d contributions",
+                    (long long)n_in, RTHICK_MAX_PARTICLES);
+    }
     { int rc = rend_open(r, k, 1); if (rc) return rc; }
     r->L->render_splat(d);
     HIPCHK(r, k.mark(2));
@@ -221,10 +276,26 @@ static int rend_run(SphRender *r, int64_t n_in) {
         r->L->render_surface_base(d, r->sd);
         HIPCHK(r, r->sclk.mark(1));
     }
+    if (thick) {   // what lies behind the fluid, then the fluid along every ray: both need the source that was drawn
+        { int rc = rthick_room(r); if (rc) return rc; }
+        HIPCHK(r, r->tclk.mark(0));
+        r->L->render_thick_opaque(d, r->sd, r->td);
+        HIPCHK(r, r->tclk.mark(1));
+        r->L->render_thick_splat(d, r->sd, r->td);
+        HIPCHK(r, r->tclk.mark(2));
+    }
     unsigned long long c[8];
     { int rc = rend_close(r, c, RF_PARTICLE); if (rc) return rc; }
     r->sstats = SphRenderSurfaceStats{};
     if (r->surf_on) { r->base_valid = true; r->sstats.ms_base = r->sclk.ms(0, 1); }
+    r->tstats = SphRenderThicknessStats{};
+    if (thick) {
+        unsigned long long tc[8];
+        { int rc = rthick_counters(r, 0, tc, false); if (rc) return rc; }
+        r->thick_valid = true;
+        r->tstats.adds = (int64_t)tc[0]; r->tstats.clipped = (int64_t)tc[1]; r->tstats.removed = (int64_t)tc[2];
+        r->tstats.ms_opaque = r->tclk.ms(0, 1); r->tstats.ms_splat = r->tclk.ms(1, 2);
+    }
     SphRenderStats &o = r->stats;
     o.particles = n_in; o.drawn = (int64_t)c[0]; o.skipped_nonfinite = (int64_t)c[1]; o.large = (int64_t)c[2]; o.atomics = (int64_t)c[3];
     o.covered_pixels = (int64_t)c[4];
@@ -278,6 +349,7 @@ extern "C" int sph_render_layer_merge(SphRender *r, const uint64_t *key, const u
     if (!r || !key || !rgb) return SPH_ERR_INVALID;
     { int rc = rend_layer_check(r, "sph_render_layer_merge"); if (rc) return rc; }
     r->base_valid = r->depth_valid = false;   // (the merged pixels' colours and flags are not known here)
+    r->thick_valid = r->thick_shaded = false;
     HIPCHK(r, hipSetDevice(r->device));
     { int rc = rend_layer_room(r); if (rc) return rc; }
     const size_t px = (size_t)r->d.W * r->d.H;
@@ -457,7 +529,7 @@ extern "C" int sph_render_stats(SphRender *r, SphRenderStats *out) {
 // --- surface mode: the kernels are in sph_render_surface.hpp ---------------------------------------------------------------
 extern "C" int sph_render_set_surface(SphRender *r, const SphRenderSurfaceParams *params) {
     if (!r) return SPH_ERR_INVALID;
-    if (!params) { r->surf_on = false; return SPH_OK; }
+    if (!params) { r->surf_on = r->thick_on = false; return SPH_OK; }
     const SphRenderSurfaceParams p = *params;
     if (p.iterations < 0 || p.iterations > 64) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: iterations %d outside 0..64", p.iterations);
     if (p.rmax < 1 || p.rmax > RSURF_RMAX_CAP) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: rmax %d outside 1..%d", p.rmax, RSURF_RMAX_CAP);
@@ -474,7 +546,8 @@ extern "C" int sph_render_set_surface(SphRender *r, const SphRenderSurfaceParams
     RenderSurfDev &s = r->sd;
     const unsigned omask = p.object_mask < 0 ? ~0u : (unsigned)p.object_mask;
     const int fluid_only = p.object_mask < 0 ? 1 : 0;
-    if (!r->surf_on || omask != s.omask || fluid_only != s.fluid_only) r->base_valid = false;   // the frame held has no base plane for this mask
+    if (!r->surf_on || omask != s.omask || fluid_only != s.fluid_only)   // the frame held has no base plane (or thickness) for this mask
+        r->base_valid = r->thick_valid = r->thick_shaded = false;
     s.omask = omask; s.fluid_only = fluid_only;
     s.inv_u = (float)(256.0 / (double)r->d.r);
     s.u = (float)((double)r->d.r / 256.0);
@@ -504,6 +577,8 @@ extern "C" int sph_render_surface(SphRender *r) {
     if (!r->surf_on) return fail(r, SPH_ERR_INVALID, "sph_render_surface: the surface mode is off (sph_render_set_surface)");
     if (!r->base_valid)
         return fail(r, SPH_ERR_INVALID, "sph_render_surface: the frame held was drawn before the mode was switched on, or changed by sph_render_layer_merge");
+    if (r->thick_on && !r->thick_valid)
+        return fail(r, SPH_ERR_INVALID, "sph_render_surface: the frame held was drawn before the thickness mode was switched on (sph_render_set_thickness)");
     HIPCHK(r, hipSetDevice(r->device));
     RenderDev &d = r->d;
     RenderSurfDev &s = r->sd;
@@ -516,7 +591,27 @@ extern "C" int sph_render_surface(SphRender *r) {
     for (int it = 0; it < iters; ++it) r->L->render_surface_smooth(d, s, it);
     HIPCHK(r, k.mark(3));
     r->depth_plane = iters & 1;
-    r->L->render_surface_shade(d, s, r->depth_plane);
+    const bool thick = r->thick_on;
+    const int titers = r->tprm.iterations;
+    r->thick_shaded = false;
+    if (thick) {
+        // T[0] -> T[1] -> the idle depth plane -> T[1] ...: the summed plane stays as it is, a repeated call starts from it again
+        RenderThickDev &t = r->td;
+        const unsigned *Q = s.q[r->depth_plane];
+        unsigned *pong[2] = {t.T[1], s.q[1 - r->depth_plane]};
+        const unsigned *in = t.T[0];
+        HIPCHK(r, hipMemsetAsync(t.cnt + (size_t)RSURF_CNT_BANKS * 8, 0, RSURF_CNT_BANKS * 64, r->stream));   // group 1
+        HIPCHK(r, r->tclk.mark(3));
+        for (int it = 0; it < titers; ++it) {
+            r->L->render_thick_smooth(d, s, t, Q, in, pong[it & 1]);
+            in = pong[it & 1];
+        }
+        HIPCHK(r, r->tclk.mark(4));
+        r->L->render_thick_shade(d, s, t, Q, in);
+        HIPCHK(r, r->tclk.mark(5));
+        r->thick_plane = in;
+    } else
+        r->L->render_surface_shade(d, s, r->depth_plane);
     HIPCHK(r, k.mark(4));
     unsigned long long bank[RSURF_CNT_BANKS][8], c[8] = {};
     HIPCHK(r, hipMemcpyAsync(bank, s.cnt, sizeof(bank), hipMemcpyDeviceToHost, r->stream));
@@ -529,6 +624,66 @@ extern "C" int sph_render_surface(SphRender *r) {
     o.surface_pixels = (int64_t)c[0]; o.iterations = iters; o.taps_visited = (int64_t)c[1]; o.taps_accepted = (int64_t)c[2];
     o.clamped_rmax = (int64_t)c[3];
     o.ms_smooth = k.ms(2, 3); o.ms_shade = k.ms(3, 4);
+    if (thick) {
+        unsigned long long tc[8];
+        { int rc = rthick_counters(r, 1, tc, true); if (rc) return rc; }
+        r->thick_shaded = true;
+        SphRenderThicknessStats &ts = r->tstats;
+        ts.iterations = titers; ts.taps_visited = (int64_t)tc[0]; ts.empty_pixels = (int64_t)tc[1]; ts.max_thickness = (int64_t)tc[2];
+        ts.ms_smooth = r->tclk.ms(3, 4); ts.ms_shade = r->tclk.ms(4, 5);
+    }
+    return SPH_OK;
+}
+
+// --- thickness mode of the surface frames: the kernels are in sph_render_thickness.hpp -------------------------------------
+extern "C" int sph_render_set_thickness(SphRender *r, const SphRenderThicknessParams *params) {
+    if (!r) return SPH_ERR_INVALID;
+    if (!params) { r->thick_on = false; return SPH_OK; }
+    const SphRenderThicknessParams p = *params;
+    if (!r->surf_on) return fail(r, SPH_ERR_INVALID, "sph_render_set_thickness: the surface mode is off (sph_render_set_surface)");
+    if (!(p.absorb >= 0.0f) || !std::isfinite(p.absorb)) return fail(r, SPH_ERR_INVALID, "sph_render_set_thickness: absorb %g must be finite and not negative", (double)p.absorb);
+    if (!(p.scatter >= 0.0f) || !std::isfinite(p.scatter)) return fail(r, SPH_ERR_INVALID, "sph_render_set_thickness: scatter %g must be finite and not negative", (double)p.scatter);
+    if (p.iterations < 0 || p.iterations > 64) return fail(r, SPH_ERR_INVALID, "sph_render_set_thickness: iterations %d outside 0..64", p.iterations);
+    if (!r->thick_on) r->thick_valid = r->thick_shaded = false;   // the frame held has no opaque layer and no thickness
+    r->td.absorb = p.absorb; r->td.scatter = p.scatter;
+    r->tprm = p;
+    r->thick_on = true;
+    return SPH_OK;
+}
+
+static int rthick_held(SphRender *r, const char *who, bool shaded) {
+    if (r->frame != RF_PARTICLE || !r->thick_valid || (shaded && !r->thick_shaded))
+        return fail(r, SPH_ERR_INVALID, "%s: no surface frame with thickness is held (sph_render_set_thickness, a particle frame, sph_render_surface)", who);
+    return SPH_OK;
+}
+
+extern "C" int sph_render_surface_download_thickness(SphRender *r, uint32_t *T, int raw) {
+    if (!r || !T) return SPH_ERR_INVALID;
+    { int rc = rthick_held(r, "sph_render_surface_download_thickness", true); if (rc) return rc; }
+    HIPCHK(r, hipSetDevice(r->device));
+    const size_t px = (size_t)r->d.W * r->d.H;
+    HIPCHK(r, hipMemcpy(T, raw ? r->td.T[0] : r->thick_plane, px * 4, hipMemcpyDeviceToHost));
+    if (raw) return SPH_OK;
+    std::vector<uint32_t> q(px);   // the smoothing writes surface pixels only: the rest is 0 by definition
+    HIPCHK(r, hipMemcpy(q.data(), r->sd.q[r->depth_plane], px * 4, hipMemcpyDeviceToHost));
+    for (size_t p = 0; p < px; ++p)
+        if (q[p] == RSURF_SENT) T[p] = 0;
+    return SPH_OK;
+}
+
+extern "C" int sph_render_surface_download_opaque(SphRender *r, uint64_t *key, uint8_t *rgb) {
+    if (!r || !key || !rgb) return SPH_ERR_INVALID;
+    { int rc = rthick_held(r, "sph_render_surface_download_opaque", false); if (rc) return rc; }
+    HIPCHK(r, hipSetDevice(r->device));
+    const size_t px = (size_t)r->d.W * r->d.H;
+    HIPCHK(r, hipMemcpy(key, r->td.okey, px * 8, hipMemcpyDeviceToHost));
+    HIPCHK(r, hipMemcpy(rgb, r->td.orgb, px * 3, hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
+
+extern "C" int sph_render_thickness_stats(SphRender *r, SphRenderThicknessStats *out) {
+    if (!r || !out) return SPH_ERR_INVALID;
+    *out = r->tstats;
     return SPH_OK;
 }
 
@@ -633,7 +788,7 @@ extern "C" int sph_render_mesh_end(SphRender *r) {
     r->stats = SphRenderStats{};
     r->cstats = SphRenderCompositeStats{};
     r->mstats = SphRenderMeshStats{};
-    r->base_valid = r->depth_valid = false;
+    r->base_valid = r->depth_valid = r->thick_valid = r->thick_shaded = false;
     const size_t nm = r->mesh_rec.size();
     { int rc = rend_room(r, (size_t)r->mesh_nt, false); if (rc) return rc; }
     { int rc = rend_grow(r, RB_MREC, 0, sizeof(MeshRec) * std::max<size_t>(nm, 1)); if (rc) return rc; }

@@ -43,6 +43,7 @@ class FrameRenderer(L.NativeObject):
         self._stats_of = None       # the native renderer of the last from_container call (composite_stats on every rank)
         self._mesh_starts = None    # first global triangle index of each mesh of the last mesh frame (and the total)
         self._surface = None        # SphRenderSurfaceParams of the surface mode, None: off
+        self._thickness = None      # SphRenderThicknessParams of its thickness mode, None: off
 
     def _params(self, box):
         kw = dict(self._kw)
@@ -67,6 +68,8 @@ class FrameRenderer(L.NativeObject):
             h = self._handles[key] = self._create(self._params(key))
             if self._surface is not None:
                 self._chk(self.lib.sph_render_set_surface(h, C.byref(self._surface)), "sph_render_set_surface", h)
+            if self._thickness is not None:
+                self._chk(self.lib.sph_render_set_thickness(h, C.byref(self._thickness)), "sph_render_set_thickness", h)
         return h
 
     def set_surface(self, iterations=3, sigma=1.5, range=2.0, rmax=12, spec=0.35, shininess=40.0, objects=None):
@@ -92,21 +95,64 @@ class FrameRenderer(L.NativeObject):
         self._surface = p
 
     def clear_surface(self):
-        """Switch the surface mode off."""
-        self._surface = None
+        """Switch the surface mode off (and with it the thickness mode)."""
+        self._surface = self._thickness = None
         for h in self._handles.values():
             self._chk(self.lib.sph_render_set_surface(h, None), "sph_render_set_surface", h)
 
     def surface(self, download=True):
         """The last particle frame (from_points / from_container with the mode on) as a surface frame, uint8 (H, W, 3): its rgb is
-        overwritten in place on the device, ids() and layer()'s keys stay.  download=False: None, the frame stays on the device for
-        the encoders."""
+        overwritten in place on the device, ids() and layer()'s keys stay.  With the thickness mode on the surface is translucent.
+        download=False: None, the frame stays on the device for the encoders."""
         if self._last is None:
             h = self._stats_of if self._stats_of is not None else self._native(self.box if self.box else None)
         else:
             h = self._last
         self._chk(self.lib.sph_render_surface(h), "sph_render_surface", h)
         return self._frame(h, download)
+
+    def set_thickness(self, absorb=0.05, scatter=0.01, iterations=2):
+        """Switch the thickness mode of the surface frames on for the frames drawn afterwards: from_points /
+        from_container also draw the opaque layer (what is not a surface particle, and the box lines) and sum the fluid's thickness
+        along every pixel's ray; surface() then returns the translucent frame.  absorb (scaled by 1 - base colour) and scatter are per
+        particle radius of fluid, iterations smooths the thickness plane.  Needs the surface mode."""
+        p = L.SphRenderThicknessParams()
+        p.absorb, p.scatter, p.iterations = float(absorb), float(scatter), int(iterations)
+        self._native(self.box if self.box else None)
+        for h in self._handles.values():
+            self._chk(self.lib.sph_render_set_thickness(h, C.byref(p)), "sph_render_set_thickness", h)
+        self._thickness = p
+
+    def clear_thickness(self):
+        """Switch the thickness mode off: surface() gives the opaque surface again."""
+        self._thickness = None
+        for h in self._handles.values():
+            self._chk(self.lib.sph_render_set_thickness(h, None), "sph_render_set_thickness", h)
+
+    def surface_thickness(self, raw=False):
+        """uint32 (H, W) of the last surface() with the thickness mode on: the smoothed thickness in units of radius / 256 of view
+        depth, 0 on non-surface pixels; raw=True: the plane as the splat summed it."""
+        h = self._last if self._last is not None else self._native(self.box if self.box else None)
+        t = np.empty((self.height, self.width), np.uint32)
+        self._chk(self.lib.sph_render_surface_download_thickness(h, t.ctypes.data, int(bool(raw))), "sph_render_surface_download_thickness", h)
+        return t
+
+    def surface_opaque(self):
+        """(key uint64 (H, W), rgb uint8 (H, W, 3)) of the opaque layer of the last particle frame drawn with the thickness mode on:
+        what layer() would give for the particles that are not surface particles, and the box lines."""
+        h = self._last if self._last is not None else self._native(self.box if self.box else None)
+        key = np.empty((self.height, self.width), np.uint64)
+        rgb = np.empty((self.height, self.width, 3), np.uint8)
+        self._chk(self.lib.sph_render_surface_download_opaque(h, key.ctypes.data, rgb.ctypes.data), "sph_render_surface_download_opaque", h)
+        return key, rgb
+
+    def thickness_stats(self):
+        """Of the last frame and surface(): adds, clipped, removed, empty_pixels, max_thickness, iterations, taps_visited,
+        ms_opaque / ms_splat / ms_smooth / ms_shade."""
+        h = self._last if self._last is not None else self._native(self.box if self.box else None)
+        st = L.SphRenderThicknessStats()
+        self._chk(self.lib.sph_render_thickness_stats(h, C.byref(st)), "sph_render_thickness_stats", h)
+        return L.struct_dict(st)
 
     def surface_depth(self):
         """uint32 (H, W) of the last surface(): the smoothed integer depth in units of radius / 256, SURFACE_SENTINEL elsewhere."""

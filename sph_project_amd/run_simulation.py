@@ -11,7 +11,8 @@ renderer of render.py with --render (its own image, not GGUI's: DESIGN.md 15); w
 writes {cnt:06}/render.png, the frame's meshes drawn on the GPU, where the reference's render.py needs Blender.  --video
 adds {out}/raw_view.avi / {out}/render.avi, the same frames as Motion-JPEG compressed on the GPU (make_video.py).
 --render_surface writes {cnt:06}/surface_view.png: the particle frame with the fluid drawn as a smoothed, lit surface in screen space
-(DESIGN.md 24), at the cost of a particle frame where --render_meshes pays for a reconstruction.
+(DESIGN.md 24), at the cost of a particle frame where --render_meshes pays for a reconstruction.  --surface_thickness makes that
+surface translucent: the fluid's thickness along every ray lets rigid bodies and the box show through.
 --png_device writes the PNG files from the device image as well (DESIGN.md 21): no pixel is downloaded, no zlib runs on the host;
 --png_coding dynamic makes those files smaller (dynamic Huffman blocks) for a slower encode.
 --gpus N shards the scene over N ranks (z-slabs, one process each, started by launch.py): the frames are composited over the ranks
@@ -120,6 +121,15 @@ def parse_args(argv=None):
     parser.add_argument("--surface_iters", type=int, default=None, help="with --render_surface: smoothing iterations, 0..64 (3)")
     parser.add_argument("--surface_sigma", type=float, default=None, help="with --render_surface: smoothing half-width in particle radii (1.5)")
     parser.add_argument("--surface_range", type=float, default=None, help="with --render_surface: depth range of a tap in particle radii (2.0)")
+    parser.add_argument("--surface_thickness", action="store_true",
+                        help="with --render_surface: draw the surface translucent -- the fluid's thickness along every pixel's ray, summed "
+                             "from the particles, lets what lies behind (rigid bodies, the box) show through (DESIGN.md 25)")
+    parser.add_argument("--surface_absorb", type=float, default=None,
+                        help="with --surface_thickness: absorption per particle radius of fluid, scaled by 1 - base colour (0.05)")
+    parser.add_argument("--surface_scatter", type=float, default=None,
+                        help="with --surface_thickness: scattering per particle radius of fluid, every channel alike (0.01)")
+    parser.add_argument("--surface_thickness_iters", type=int, default=None,
+                        help="with --surface_thickness: smoothing iterations of the thickness plane, 0..64 (2)")
     parser.add_argument("--render_size", type=int, nargs=2, default=(1024, 1024), metavar=("W", "H"))
     parser.add_argument("--camera_position", type=float, nargs=3, default=(5.5, 2.5, 4.0))
     parser.add_argument("--camera_lookat", type=float, nargs=3, default=(-1.0, 0.0, 0.0))
@@ -159,6 +169,11 @@ def parse_args(argv=None):
     for flag in ("surface_iters", "surface_sigma", "surface_range"):
         if getattr(args, flag) is not None and not args.render_surface:
             parser.error(f"--{flag} sets a parameter of the surface frames: give --render_surface as well")
+    if args.surface_thickness and not args.render_surface:
+        parser.error("--surface_thickness makes the surface frames translucent: give --render_surface as well")
+    for flag in ("surface_absorb", "surface_scatter", "surface_thickness_iters"):
+        if getattr(args, flag) is not None and not args.surface_thickness:
+            parser.error(f"--{flag} sets a parameter of the thickness mode: give --surface_thickness as well")
     if args.gpus > 1:
         check_sharded_args(parser, args)
     if args.png_device and not (args.render or args.render_meshes or args.render_surface):
@@ -434,6 +449,9 @@ def main(argv=None):
         # first, then the surface frame: encoders and a video file of its own
         chosen = dict(iterations=args.surface_iters, sigma=args.surface_sigma, range=args.surface_range)
         renderer.set_surface(**{k: v for k, v in chosen.items() if v is not None})
+        if args.surface_thickness:
+            chosen = dict(absorb=args.surface_absorb, scatter=args.surface_scatter, iterations=args.surface_thickness_iters)
+            renderer.set_thickness(**{k: v for k, v in chosen.items() if v is not None})
         surface = ImageOutput("surface_view.png", "surface_view.avi", renderer, args, out_dir)
     if args.render_meshes:   # render.py: every mesh of the frame -> {frame}/render.png
         mesh_renderer = make_renderer(container, args, box=(np.zeros(3), np.asarray(container.domain_end, dtype=np.float64)))
