@@ -799,7 +799,11 @@ int sph_video_stats(SphVideo *v, SphVideoStats *out);
    whichever is shorter (ties: fixed).  With sph_png_set_coding(SPH_PNG_CODING_DYNAMIC) a segment becomes a dynamic Huffman block
    (BTYPE 10, closed like a fixed one) where that takes strictly fewer bytes than the choice above: lit/len lengths are Huffman's over
    the segment's own tokens, the distance and code-length codes' come from package-merge (limits 4 and 7), all codes canonical, the
-   header run-length coded by a fixed greedy rule; a file in dynamic coding is never longer than the fixed one.  Tokens come from a fixed rule (candidate distances 1, 2, 3, 4, 6 inside the segment, longest
+   header run-length coded by a fixed greedy rule; a file in dynamic coding is never longer than the fixed one.  With
+   SPH_PNG_CODING_WINDOW every position also has one match candidate in the 32 KB before it -- the most recent earlier occurrence of
+   its three bytes anywhere in the filtered stream, other segments included -- and a segment becomes one dynamic block of that parse
+   (all 30 distance symbols, distance code by package-merge under 15) where that takes strictly fewer bytes than the dynamic coding's
+   choice; a file in window coding is never longer than the dynamic one.  Tokens come from a fixed rule (candidate distances 1, 2, 3, 4, 6 inside the segment, longest
    match first, then the smallest distance, greedy from the segment's start), row filters from the least sum of |residual as int8|
    (ties: the lowest type) or one fixed type.  All of it is integer arithmetic, so the bytes are a function of (pixels, width, height,
    filter, coding): the same from both builds and from every call.  The device filters, matches, parses, codes, packs and computes the
@@ -835,6 +839,17 @@ typedef struct {
 
 #define SPH_PNG_CODING_FIXED 0     /* per segment the fixed Huffman code or a stored block (the default) */
 #define SPH_PNG_CODING_DYNAMIC 1   /* also a dynamic Huffman block where it is strictly shorter */
+#define SPH_PNG_CODING_WINDOW 3    /* also a dynamic block of the parse with matches from a 32 KB window, where that is shorter still
+                                      (2 is not a coding and stays refused) */
+
+/* what the window coding adds to SphPngStats (a struct of its own: SphPngStats keeps its size); zeros after an encode in another coding */
+typedef struct {
+    int64_t window_segments;      /* segments written as a block of the window parse; their tokens are counted in literals / matches */
+    int64_t window_matches;       /* the matches in them that came from the window candidate (no fixed distance gave that length) */
+    int64_t window_far_matches;   /* the matches in them that reach back more than 4096 bytes */
+    int64_t window_header_bits;   /* the sum of their headers' bits */
+    double ms_candidates;         /* HIP events: the candidates of the whole stream (between ms_filter and ms_count) */
+} SphPngWindowStats;
 
 typedef struct SphPng SphPng;
 /* SPH_ERR_INVALID (before any device is touched): a size or filter outside the ranges above, reserved != 0 */
@@ -844,7 +859,7 @@ const char *sph_png_last_error(SphPng *v);
 /* the entropy coding of the encodes that follow; SPH_ERR_INVALID with a message for any other value */
 int sph_png_set_coding(SphPng *v, int32_t coding);
 /* the longest file these parameters can give: 8 + 25 + 17 * segments + raw_bytes + 2 + 16 + 12 with segments =
-   ceil(raw_bytes / 4096).  The same in either coding: a dynamic block replaces a segment's fixed or stored block only where it is
+   ceil(raw_bytes / 4096).  The same in every coding: a dynamic or window block replaces a segment's block only where it is
    strictly shorter.  Host only: no device is touched. */
 int sph_png_bound(const SphPngParams *params, int64_t *bytes);
 /* a host image u8[height][width][3], rows from the top */
@@ -856,6 +871,10 @@ int sph_png_encode_render(SphPng *v, SphRender *r);
 int sph_png_size(SphPng *v, int64_t *bytes);
 int sph_png_download(SphPng *v, uint8_t *dst);
 int sph_png_stats(SphPng *v, SphPngStats *out);
+int sph_png_window_stats(SphPng *v, SphPngWindowStats *out);
+/* for tests and diagnosis: the candidates of the last encode, which was in window coding (else SPH_ERR_INVALID): prev[i] is the most
+   recent j < i with i - j <= 32768 and the same three bytes at j as at i in the filtered stream, 0xFFFFFFFF for none; n = raw_bytes */
+int sph_png_download_candidates(SphPng *v, uint32_t *prev, size_t n);
 
 /* --- Text export: ASCII PLY / OBJ frame files formatted on the device -------------------------------------------- */
 /* stands in for a download followed by sph_write_ply_ascii / sph_write_obj_ascii: the same bytes, made where the particles or the

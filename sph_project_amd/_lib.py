@@ -209,7 +209,15 @@ class SphPngStats(C.Structure):
     ]
 
 
+class SphPngWindowStats(C.Structure):
+    _fields_ = [
+        ("window_segments", C.c_int64), ("window_matches", C.c_int64), ("window_far_matches", C.c_int64), ("window_header_bits", C.c_int64),
+        ("ms_candidates", C.c_double),
+    ]
+
+
 PNG_CODING_FIXED, PNG_CODING_DYNAMIC = 0, 1
+PNG_CODING_WINDOW = 3   # (2 is no coding: the library refuses it)
 
 
 class SphTextParams(C.Structure):
@@ -352,6 +360,8 @@ _SIGNATURES = [
     ("sph_png_size", C.c_int, [_VP, C.POINTER(C.c_int64)]),
     ("sph_png_download", C.c_int, [_VP, _VP]),
     ("sph_png_stats", C.c_int, [_VP, C.POINTER(SphPngStats)]),
+    ("sph_png_window_stats", C.c_int, [_VP, C.POINTER(SphPngWindowStats)]),
+    ("sph_png_download_candidates", C.c_int, [_VP, _VP, C.c_size_t]),
     ("sph_text_create", C.c_int, [C.POINTER(SphTextParams), C.POINTER(_VP)]),
     ("sph_text_destroy", None, [_VP]),
     ("sph_text_last_error", C.c_char_p, [_VP]),

@@ -344,10 +344,16 @@ struct VideoDev {
 // PNG encoding (sph_png.hpp): one frame -> the IDAT chunks of a PNG file.  The filtered stream (H rows of 1 + 3 W bytes) is
 // cut into segments of PNG_SEG raw bytes, the work of one workgroup and one IDAT chunk each; PNG_DIST are the candidate match distances.
 // cnt: [0..4] rows per filter type, [5] stored segments, [6] literals, [7] matches (the tokens of the segments coded with the fixed or a
-// dynamic code), [8] dynamic segments, [9] the bits of their headers.
+// dynamic code), [8] dynamic segments, [9] the bits of their headers, [10] window segments, [11] the matches in them that the window
+// candidate supplied, [12] those of their matches that reach back more than PNG_FAR bytes, [13] the bits of their headers.
 #define PNG_SEG 4096
-#define PNG_NCNT 10
+#define PNG_NCNT 14
 #define PNG_SIDE 320                   // bytes per segment of the dynamic coding's side record (sph_png.hpp)
+#define PNG_WSIDE 672                  // of the window coding's: the dynamic record, then the window block's lengths, choice and header bits
+#define PNG_WINDOW 32768               // coding = window: how far back a match candidate may lie
+#define PNG_FAR 4096
+#define PNG_NONE 0xFFFFFFFFu           // prev: no candidate
+#define PNG_SORT_TILE 4096             // positions per workgroup of the candidate sort
 #define PNG_ND 5
 #define PNG_DIST_LIST {1, 2, 3, 4, 6}
 #define PNG_CRC_PIECE 17               // bytes per thread of a chunk's CRC: 256 pieces cover tag + prefix + stored header + PNG_SEG bytes
@@ -375,6 +381,11 @@ struct PngDev {
     unsigned char *out;                // the chunks, then the Adler-32's own IDAT chunk
     hipStream_t stream;
     unsigned char *side;               // [nseg][PNG_SIDE] coding = dynamic: the count pass's code lengths and choice; nullptr: coding = fixed
+    // coding = window (prev == nullptr otherwise; side then holds records of PNG_WSIDE bytes)
+    unsigned *prev;                    // [nseg PNG_SEG] per position of the stream its candidate c(i), PNG_NONE: none ([raw, ...) is not written)
+    unsigned *sort_key[2], *sort_pos[2];   // [raw] the candidate sort's two sides: 24-bit keys, positions
+    int *hist;                         // [256][nsort] digit counts per sort workgroup -> their row-wise exclusive scans, then [256] the rows' totals
+    int nsort;                         // workgroups of the sort: ceil((raw - 2) / PNG_SORT_TILE)
 };
 
 // Text export (sph_text_passes.hpp): the rows of an ASCII PLY or OBJ file, one piece of them at a time.
@@ -686,6 +697,7 @@ struct Launch {
     void (*video_write)(VideoDev &);            // the same bytes again, stored at the scanned offsets
     // PNG encoding (sph_png.hpp)
     void (*png_filter)(PngDev &);               // the filtered stream: one row filter per row, by the least sum of |residual|
+    void (*png_candidates)(PngDev &);           // coding = window: prev[] of the whole filtered stream (sort by three-byte key, predecessors)
     void (*png_count)(PngDev &);                // bytes per segment's chunk (tokens, fixed or stored), the Adler sums
     void (*png_scan)(PngDev &);                 // their exclusive scan, the total behind it; the Adler-32
     void (*png_write)(PngDev &);                // the same bytes again, stored at the scanned offsets, with every chunk's CRC

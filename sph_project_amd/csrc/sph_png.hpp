@@ -16,6 +16,10 @@
 //             zero register unchanged, so every join of a level uses one constant)
 //   dynamic   (the DYN instantiations, coding = dynamic) COUNT also builds the segment's own codes from its tokens' histograms and keeps
 //             a dynamic block where it is strictly shorter; the lengths go to a side record from which WRITE rebuilds the canonical codes
+//   window    (the WIN instantiations, coding = window) COUNT then parses the segment again with one more candidate per position -- prev[],
+//             the most recent earlier occurrence of its three bytes within 32 KB of the whole stream, from the sort at the end of this
+//             file -- builds that parse's codes over all 30 distance symbols and keeps its block where it is shorter still; WRITE
+//             parses only the parse that was chosen
 // The kernel runs twice per frame as the video encoder's does: COUNT leaves the chunk's byte count and the Adler sums, k_png_scan scans
 // the counts (the host sizes the output from the total) and joins the Adler sums, WRITE computes the same bytes again and stores them.
 #pragma once
@@ -212,18 +216,21 @@ __device__ __forceinline__ void png_run_length(const unsigned char *len, int hli
     }
 }
 __device__ __forceinline__ int png_hlit(const unsigned char *len) { int h = PNG_NLL; while (h > 257 && !len[h - 1]) --h; return h; }
-__device__ __forceinline__ int png_hdist(const unsigned char *len) { int h = PNG_NDC; while (h > 1 && !len[PNG_NLL + h - 1]) --h; return h; }
+template <int ND = PNG_NDC>   // (ND: the distance symbols of the length arrays; PNG_WND in the window coding's)
+__device__ __forceinline__ int png_hdist(const unsigned char *len) { int h = ND; while (h > 1 && !len[PNG_NLL + h - 1]) --h; return h; }
+template <int ND = PNG_NDC>
 __device__ __forceinline__ int png_hclen(const unsigned char *len) {
     int h = PNG_NCL;
-    while (h > 4 && !len[PNG_NLL + PNG_NDC + PNG_CL_ORDER[h - 1]]) --h;
+    while (h > 4 && !len[PNG_NLL + ND + PNG_CL_ORDER[h - 1]]) --h;
     return h;
 }
 
 // the canonical code (RFC 1951 3.2.2) of entry e of the three length arrays: the shorter codes of its array before it, then the codes
 // of its length at smaller symbols.  Returned as the code reversed (stream order) | length << 16; 0 for an unused symbol.
+template <int ND = PNG_NDC>
 __device__ __forceinline__ unsigned png_canonical(const unsigned char *len, int e) {
-    const int lo = e < PNG_NLL ? 0 : e < PNG_NLL + PNG_NDC ? PNG_NLL : PNG_NLL + PNG_NDC;
-    const int hi = e < PNG_NLL ? PNG_NLL : e < PNG_NLL + PNG_NDC ? PNG_NLL + PNG_NDC : PNG_NLEN;
+    const int lo = e < PNG_NLL ? 0 : e < PNG_NLL + ND ? PNG_NLL : PNG_NLL + ND;
+    const int hi = e < PNG_NLL ? PNG_NLL : e < PNG_NLL + ND ? PNG_NLL + ND : PNG_NLL + ND + PNG_NCL;
     const int l = len[e];
     if (!l) return 0u;
     unsigned code = 0u;
@@ -248,6 +255,294 @@ __device__ __forceinline__ void png_dyn_token(const unsigned *tab, unsigned t, u
     if (q == 4u) { val |= 1u << nb; nb += 1; }   // distance 6: code 4 (5..6), extra bit 1
 }
 
+// --- window matches (coding = window; DESIGN.md 21 'Window matches') ---
+// prev[i] = c(i), the most recent earlier position within PNG_WINDOW whose three bytes are those at i, comes from the candidate sort
+// below.  A token of the window parse is 32 bits: length | distance << 9 | (it came from the window candidate) << 25.  The window block's
+// lengths: lit/len [286], distance [PNG_WND], code-length code [19], padded to PNG_WLEN_WORDS words.  A segment's side record is the
+// dynamic coding's (the choice on the five-distance parse) followed by these lengths and two ints: 3 when the window block is written
+// (else 0), and its header's bits.
+#define PNG_WND 30
+#define PNG_WLEN_WORDS 84
+#define PNG_WNLEN (PNG_NLL + PNG_WND + PNG_NCL)
+static_assert(4 * PNG_WLEN_WORDS >= PNG_WNLEN && PNG_WSIDE >= PNG_SIDE + 4 * PNG_WLEN_WORDS + 8 && PNG_WSIDE % 16 == 0, "the window record holds both parts");
+// the window count pass's arrays inside s_img (words), as PNG_C_* above; its package-merge lists lie in an array of their own
+#define PNG_W_HLL 0        // [288]
+#define PNG_W_HD 288       // [32]
+#define PNG_W_HCL 320      // [24]
+#define PNG_W_SYM 344      // [288]
+#define PNG_W_WT 632       // [572]
+#define PNG_W_PAR 1204     // [572] 16-bit parents
+#define PNG_W_LEN 1490     // [PNG_WLEN_WORDS]
+#define PNG_W_MISC 1574    // [0] the lit/len code is deeper than 15, [1] header bits
+#define PNG_W_PM 750       // words of the lists: weights [150] (leaves [30], two lists of [60]), multiplicities [150][4]
+static_assert(PNG_W_MISC + 8 <= PNG_IMG_WORDS, "the window count pass's arrays fit the image array");
+
+// the distance symbol of a match distance, its extra bits and their value
+__device__ __forceinline__ void png_dist_sym(int dist, int &dc, int &db, unsigned &dv) {
+    const int m = dist - 1;
+    dc = m; db = 0; dv = 0u;
+    if (m >= 4) { db = 30 - __clz(m); dc = 2 * db + 2 + ((m >> db) & 1); dv = (unsigned)m & ((1u << db) - 1u); }   // pairs of codes per extra bit
+}
+
+// png_package_merge for the PNG_WND distance symbols under limit 15: multiplicities (<= 15) in 4 bits per symbol, four words per item;
+// a list has fewer than 2 n <= 60 items
+__device__ __forceinline__ void png_package_merge_wide(const unsigned *hist, unsigned char *out, unsigned *w, unsigned *mu) {
+    int n = 0;
+    for (int s = 0; s < PNG_WND; ++s) {
+        out[s] = 0;
+        const unsigned c = hist[s];
+        if (!c) continue;
+        int j = n++;
+        for (; j > 0 && w[j - 1] > c; --j) {
+            w[j] = w[j - 1];
+            for (int q = 0; q < 4; ++q) mu[4 * j + q] = mu[4 * (j - 1) + q];
+        }
+        w[j] = c;
+        for (int q = 0; q < 4; ++q) mu[4 * j + q] = (s >> 3) == q ? 1u << (4 * (s & 7)) : 0u;
+    }
+    if (n == 0) return;
+    if (n == 1) { for (int s = 0; s < PNG_WND; ++s) if (hist[s]) out[s] = 1; return; }
+    int cur = 30, nxt = 90, ncur = n;
+    for (int k = 0; k < n; ++k) {
+        w[cur + k] = w[k];
+        for (int q = 0; q < 4; ++q) mu[4 * (cur + k) + q] = mu[4 * k + q];
+    }
+    for (int lev = 2; lev <= 15; ++lev) {
+        const int np = ncur >> 1;
+        int a = 0, b = 0, k = 0;
+        while (a < n || b < np) {   // (k < n + np <= 30 + 29)
+            const unsigned pw = b < np ? w[cur + 2 * b] + w[cur + 2 * b + 1] : 0u;
+            if (a < n && (b >= np || w[a] <= pw)) {
+                w[nxt + k] = w[a];
+                for (int q = 0; q < 4; ++q) mu[4 * (nxt + k) + q] = mu[4 * a + q];
+                ++a;
+            } else {
+                w[nxt + k] = pw;
+                for (int q = 0; q < 4; ++q) mu[4 * (nxt + k) + q] = mu[4 * (cur + 2 * b) + q] + mu[4 * (cur + 2 * b + 1) + q];   // (no field passes 15)
+                ++b;
+            }
+            ++k;
+        }
+        const int t = cur; cur = nxt; nxt = t;
+        ncur = k;
+    }
+    unsigned tot[4] = {0u, 0u, 0u, 0u};
+    for (int k = 0; k < min(2 * n - 2, ncur); ++k)
+        for (int q = 0; q < 4; ++q) tot[q] += mu[4 * (cur + k) + q];
+    for (int s = 0; s < PNG_WND; ++s) out[s] = (unsigned char)((tot[s >> 3] >> (4 * (s & 7))) & 15u);
+}
+
+// the 32 bits at byte offset o of a little-endian word array (the word behind them is read too: the arrays have one to spare)
+__device__ __forceinline__ unsigned png_word_at(const unsigned *w, int o) {
+    return __builtin_amdgcn_alignbyte(w[(o >> 2) + 1], w[o >> 2], (unsigned)o & 3u);
+}
+// how many bytes from offset t of tgt equal the source's (src(l): its 32 bits at l bytes in), at most cap: four bytes a step
+template <class S>
+__device__ __forceinline__ int png_common_prefix(const unsigned *tgt, int t, S src, int cap) {
+    int l = 0;
+    while (l < cap) {
+        const unsigned x = png_word_at(tgt, t + l) ^ src(l);
+        if (x) { l += __builtin_ctz(x) >> 3; break; }
+        l += 4;
+    }
+    return min(l, cap);
+}
+
+// The window parse's tokens of thread tid's positions and their next pointers.  The five distances' masks and entering runs are made
+// again here as k_png_segment makes them (from the bytes and s_lead: cheaper than keeping them in registers across the count pass's
+// first code construction).  The candidate's length is compared in LDS when its source lies in the segment and in the stream when it
+// starts before it; a candidate at one of the five distances whose source lies in the segment is that distance's run and is skipped.
+__device__ __forceinline__ void png_window_tokens(const PngDev &d, int seg, int n, int tid, const unsigned *s_raw, const unsigned short (*s_lead)[256],
+                                                  unsigned *s_wtok, unsigned short *s_next) {
+    const int base = tid * PNG_PER, start = seg * PNG_SEG;
+    const unsigned char *s_b = (const unsigned char *)s_raw;
+    unsigned m[PNG_ND];
+    int carry[PNG_ND];
+    {
+        unsigned char c[8 + PNG_PER];
+#pragma unroll
+        for (int k = 0; k < 8 + PNG_PER; ++k) c[k] = base + k >= 8 ? s_b[base + k - 8] : (unsigned char)0;
+#pragma unroll
+        for (int q = 0; q < PNG_ND; ++q) {
+            const int dist = PNG_DIST[q];
+            unsigned mk = 0u;
+#pragma unroll
+            for (int k = 0; k < PNG_PER; ++k)
+                if (base + k >= dist && base + k < n && c[8 + k] == c[8 + k - dist]) mk |= 1u << k;
+            m[q] = mk;
+            int r = 0;
+            for (int u = tid + 1; u < 256 && r < 258; ++u) {
+                const unsigned v = s_lead[q][u];
+                r += (int)(v & 0x7FFFu);
+                if (!(v & 0x8000u)) break;
+            }
+            carry[q] = r;
+        }
+    }
+    unsigned pv[PNG_PER];
+#pragma unroll
+    for (int q = 0; q < PNG_PER / 4; ++q) {   // (prev is allocated in whole segments: entries behind the stream's end are read, not used)
+        const uint4 v = ((const uint4 *)(d.prev + (size_t)start + base))[q];
+        pv[4 * q] = v.x; pv[4 * q + 1] = v.y; pv[4 * q + 2] = v.z; pv[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int k = 0; k < PNG_PER; ++k) {
+        const int i = base + k;
+        int best = 0, bq = 0;
+#pragma unroll
+        for (int q = 0; q < PNG_ND; ++q) {
+            int run = __builtin_ctz(~(m[q] >> k));
+            if (run == PNG_PER - k) run += carry[q];
+            run = min(run, 258);
+            if (run > best) { best = run; bq = q; }
+        }
+        int len = best, dist = PNG_DIST[bq];
+        unsigned from = 0u;
+        const unsigned p = i < n ? pv[k] : PNG_NONE;
+        if (p != PNG_NONE) {
+            const int dw = start + i - (int)p, j = (int)p - start;
+            if (!(j >= 0 && (dw <= 4 || dw == 6))) {
+                const int cap = min(258, n - i);
+                int lw;
+                if (j >= 0) lw = png_common_prefix(s_raw, i, [&](int l) { return png_word_at(s_raw, j + l); }, cap);
+                else lw = png_common_prefix(s_raw, i, [&](int l) { return png_word_at((const unsigned *)d.flt, (int)p + l); }, cap);
+                if (lw >= 3 && (lw > best || (lw == best && dw < dist))) { len = lw; dist = dw; from = 1u; }   // equal lengths: the smaller distance
+            }
+        }
+        if (len < 3) { len = 0; dist = 0; }
+        s_wtok[i] = (unsigned)len | (unsigned)dist << 9 | from << 25;
+        s_next[i] = (unsigned short)(i < n ? i + max(len, 1) : n);
+    }
+}
+
+// the pointer doubling of k_png_segment's parse once more, for the window count pass's second parse (all threads of the workgroup)
+__device__ __forceinline__ void png_chain(unsigned short *s_next, unsigned char *s_mark, int n, int tid) {
+    for (int r = 0; r < 12; ++r) {
+        if (s_next[0] >= n) break;
+        unsigned short j[PNG_PER], jj[PNG_PER];
+        unsigned char mk[PNG_PER];
+#pragma unroll
+        for (int k = 0; k < PNG_PER; ++k) {
+            const int i = tid + 256 * k;
+            j[k] = s_next[i];
+            jj[k] = s_next[j[k]];
+            mk[k] = s_mark[i];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < PNG_PER; ++k) {
+            const int i = tid + 256 * k;
+            if (mk[k]) s_mark[j[k]] = 1;
+            s_next[i] = jj[k];
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+}
+
+// (all threads of the workgroup) The codes of the window parse's marked tokens, as the dynamic count pass builds them for the five-distance
+// parse: lit/len by two queues, the PNG_WND distance symbols by package-merge under 15, the code-length code under 7.  The lengths are
+// left at s_img + PNG_W_LEN; returns the block's bits (3 + header + tokens + end of block); ok: the lit/len code stays within 15.
+__device__ __forceinline__ int png_window_codes(unsigned *s_img, unsigned *s_pm, unsigned *s_red, const unsigned *s_wtok, const unsigned char *s_mark,
+                                                const unsigned char *s_b, int n, int tid, int &hbits, bool &ok) {
+    unsigned *h_ll = s_img + PNG_W_HLL, *h_d = s_img + PNG_W_HD, *h_cl = s_img + PNG_W_HCL, *l_sym = s_img + PNG_W_SYM, *wt = s_img + PNG_W_WT;
+    unsigned short *par = (unsigned short *)(s_img + PNG_W_PAR);
+    unsigned char *len = (unsigned char *)(s_img + PNG_W_LEN);
+    unsigned *misc = s_img + PNG_W_MISC;
+    for (int w = tid; w < PNG_W_SYM; w += 256) s_img[w] = 0u;
+    if (tid < PNG_WLEN_WORDS) s_img[PNG_W_LEN + tid] = 0u;
+    if (tid < 8) misc[tid] = 0u;
+    __syncthreads();
+    int xbits = 0;   // the extra bits of the thread's matches
+    for (int k = 0; k < PNG_PER; ++k) {
+        const int i = tid * PNG_PER + k;
+        if (i < n && s_mark[i]) {
+            const unsigned t = s_wtok[i];
+            if (t) {
+                int sym, eb, dc, db;
+                unsigned ev, dv;
+                png_len_sym((int)(t & 511u), sym, eb, ev);
+                png_dist_sym((int)((t >> 9) & 0xFFFFu), dc, db, dv);
+                atomicAdd(&h_ll[sym], 1u);
+                atomicAdd(&h_d[dc], 1u);
+                xbits += eb + db;
+            } else atomicAdd(&h_ll[s_b[i]], 1u);
+        }
+    }
+    if (tid == 0) atomicAdd(&h_ll[256], 1u);   // the end of block
+    __syncthreads();
+    int nleaf = 0;
+    {   // the used lit/len symbols sorted by (count, symbol)
+        const int s0 = tid, s1 = tid + 256;
+        const unsigned c0 = h_ll[s0], c1 = s1 < PNG_NLL ? h_ll[s1] : 0u;
+        const unsigned k0 = c0 << 9 | (unsigned)s0, k1 = c1 << 9 | (unsigned)s1;
+        int r0 = 0, r1 = 0;
+        for (int j = 0; j < PNG_NLL; ++j) {
+            const unsigned cj = h_ll[j], kj = cj << 9 | (unsigned)j;
+            if (cj) { ++nleaf; r0 += kj < k0; r1 += kj < k1; }
+        }
+        if (c0) { l_sym[r0] = (unsigned)s0; wt[r0] = c0; }
+        if (c1) { l_sym[r1] = (unsigned)s1; wt[r1] = c1; }
+    }
+    __syncthreads();
+    const int root = 2 * nleaf - 2;   // (nleaf >= 2: a literal or a length, and the end of block)
+    if (tid == 0) {
+        int leaf = 0, inner = nleaf;
+        for (int node = nleaf; node <= root; ++node) {
+            unsigned sum = 0u;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                int pick;
+                if (leaf < nleaf && (inner >= node || wt[leaf] <= wt[inner])) pick = leaf++;
+                else pick = inner++;
+                sum += wt[pick];
+                par[pick] = (unsigned short)node;
+            }
+            wt[node] = sum;
+        }
+    }
+    if (tid == 64) png_package_merge_wide(h_d, len + PNG_NLL, s_pm, s_pm + 150);
+    __syncthreads();
+    for (int k = tid; k < nleaf; k += 256) {
+        int at = k, depth = 0;
+        while (at != root && depth < 16) { at = par[at]; ++depth; }
+        if (at != root || depth > 15) atomicOr(&misc[0], 1u);
+        len[l_sym[k]] = (unsigned char)depth;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int extra = 0;
+        png_run_length(len, png_hlit(len), png_hdist<PNG_WND>(len), [&](int sym, int, int eb) { h_cl[sym] += 1u; extra += eb; });
+        png_package_merge(h_cl, PNG_NCL, 7, len + PNG_NLL + PNG_WND, s_pm, s_pm + 100, s_pm + 200);
+        int hb = 5 + 5 + 4 + 3 * png_hclen<PNG_WND>(len) + extra;
+        for (int q = 0; q < PNG_NCL; ++q) hb += (int)h_cl[q] * len[PNG_NLL + PNG_WND + q];
+        misc[1] = (unsigned)hb;
+    }
+    __syncthreads();
+    int bits = xbits;
+    for (int e = tid; e < PNG_NLL + PNG_WND; e += 256) bits += (int)s_img[e < PNG_NLL ? PNG_W_HLL + e : PNG_W_HD + e - PNG_NLL] * (int)len[e];
+    bits = video_wave_sum(bits);
+    if ((tid & 63) == 0) s_red[8 + (tid >> 6)] = (unsigned)bits;
+    __syncthreads();
+    hbits = (int)misc[1];
+    ok = !misc[0];
+    return 3 + hbits + (int)(s_red[8] + s_red[9] + s_red[10] + s_red[11]);
+}
+
+// a token of the window parse in the segment's own code (tab: png_canonical<PNG_WND> of the 335 entries), in two pieces: the literal or
+// the length with its extra bits (<= 15 + 5), the distance with its extra bits (<= 15 + 13; none for a literal)
+__device__ __forceinline__ void png_win_token(const unsigned *tab, unsigned t, unsigned byte, unsigned &v0, int &n0, unsigned &v1, int &n1) {
+    v1 = 0u; n1 = 0;
+    if (!t) { const unsigned e = tab[byte]; v0 = e & 0xFFFFu; n0 = (int)(e >> 16); return; }
+    int sym, eb, dc, db;
+    unsigned ev, dv;
+    png_len_sym((int)(t & 511u), sym, eb, ev);
+    png_dist_sym((int)((t >> 9) & 0xFFFFu), dc, db, dv);
+    const unsigned e = tab[sym], f = tab[PNG_NLL + dc];
+    n0 = (int)(e >> 16); v0 = (e & 0xFFFFu) | ev << n0; n0 += eb;
+    n1 = (int)(f >> 16); v1 = (f & 0xFFFFu) | dv << n1; n1 += db;
+}
+
 // what a segment's chunk is made of once the layout is known
 struct PngSeg { int n, pre, fixed, final, body; };   // raw bytes; 2 = the zlib header goes first; a bit image (fixed or dynamic code) / stored; last segment; payload bytes
 __device__ __forceinline__ unsigned png_payload_byte(const PngSeg &s, const unsigned *img, const unsigned char *raw, int j) {
@@ -263,17 +558,21 @@ __device__ __forceinline__ unsigned png_payload_byte(const PngSeg &s, const unsi
     return raw[j - 5];
 }
 
-template <bool WRITE, bool DYN = false>
+template <bool WRITE, bool DYN = false, bool WIN = false>   // (WIN goes with DYN: the window coding starts from the dynamic coding's choice)
 __global__ void __launch_bounds__(256) k_png_segment(PngDev d) {
-    __shared__ unsigned s_dyn[DYN && WRITE ? 80 + PNG_NLEN + 2 : 1];   // (dynamic write pass) the lengths [312 bytes], the codes [310]
-    __shared__ unsigned s_raw[PNG_SEG / 4];
-    __shared__ unsigned short s_tok[PNG_SEG];          // per position: match length | index of its distance << 9 (0: a literal)
+    static_assert(DYN || !WIN, "the window instantiations are the dynamic ones and more");
+    constexpr int SIDE = WIN ? PNG_WSIDE : PNG_SIDE;   // bytes of a segment's side record
+    __shared__ unsigned s_dyn[DYN && WRITE ? (WIN ? PNG_WLEN_WORDS + PNG_WNLEN + 1 : 80 + PNG_NLEN + 2) : 1];   // (dynamic write pass) the lengths [312 bytes], the codes [310]
+    __shared__ unsigned s_pm[WIN && !WRITE ? PNG_W_PM : 1];    // (window count pass) the package-merge lists
+    __shared__ unsigned s_raw[PNG_SEG / 4 + (WIN ? 4 : 0)];    // (window: a word to spare behind the bytes, png_word_at)
+    __shared__ __attribute__((aligned(WIN ? 4 : 2))) unsigned short s_tok[WIN ? 2 * PNG_SEG : PNG_SEG];   // per position: match length | index of its distance << 9 (0: a literal)
+    unsigned *s_tokw = (unsigned *)s_tok;              // (window) the window parse's tokens are 32 bits each
     __shared__ unsigned s_img[PNG_IMG_WORDS];
     __shared__ unsigned char s_mark[PNG_SEG + 4];      // 1: a token starts here ([n]: the chain's end, written and never read)
     __shared__ unsigned short s_lead[PNG_ND][256];     // per thread and distance: the leading run of its mask | 0x8000 when that is all of it
     __shared__ unsigned s_red[256];
     __shared__ int s_w[4];
-    __shared__ int s_tokens[2];
+    __shared__ int s_tokens[WIN ? 4 : 2];
     const int tid = threadIdx.x, seg = blockIdx.x;
     const int n = min(PNG_SEG, d.raw - seg * PNG_SEG);
     const unsigned char *src = d.flt + (size_t)seg * PNG_SEG;
@@ -289,7 +588,10 @@ __global__ void __launch_bounds__(256) k_png_segment(PngDev d) {
         s_raw[w] = v;
     }
     for (int i = tid; i < PNG_SEG + 4; i += 256) s_mark[i] = i == 0 ? 1 : 0;
-    if (tid < 2) s_tokens[tid] = 0;
+    if (tid < (WIN ? 4 : 2)) s_tokens[tid] = 0;
+    if (WIN && tid < 4) s_raw[PNG_SEG / 4 + tid] = 0u;
+    bool win = false;     // (window coding) the segment is one dynamic block of the window parse
+    if (WIN && WRITE) win = ((const unsigned *)(d.side + (size_t)seg * SIDE))[PNG_SIDE / 4 + PNG_WLEN_WORDS] == 3u;   // (workgroup-uniform)
     __syncthreads();
 
     // the thread's bytes and the eight before them
@@ -336,6 +638,8 @@ __global__ void __launch_bounds__(256) k_png_segment(PngDev d) {
         carry[q] = r;
     }
     // longest first, then the smallest distance (PNG_DIST ascends: a later one must be strictly longer)
+    if (WIN && win) png_window_tokens(d, seg, n, tid, s_raw, s_lead, s_tokw, s_next);
+    else
 #pragma unroll
     for (int k = 0; k < PNG_PER; ++k) {
         int best = 0, bq = 0;
@@ -379,6 +683,7 @@ __global__ void __launch_bounds__(256) k_png_segment(PngDev d) {
 
     // bits per token
     int bits = 0, nlit = 0, nmat = 0;
+    if (!(WIN && win))
 #pragma unroll
     for (int k = 0; k < PNG_PER; ++k) {
         const int i = base + k;
@@ -493,10 +798,45 @@ __global__ void __launch_bounds__(256) k_png_segment(PngDev d) {
         const int dyn_bytes = s.final ? (dyn_bits + 7) >> 3 : ((dyn_bits + 3 + 7) >> 3) + 4;
         dyn = !misc[0] && s.pre + dyn_bytes < s.body;
         if (dyn) s.body = s.pre + dyn_bytes;
-        unsigned *side = (unsigned *)(d.side + (size_t)seg * PNG_SIDE);
+        unsigned *side = (unsigned *)(d.side + (size_t)seg * SIDE);
         if (tid < 78) side[tid] = s_img[PNG_C_LEN + tid];
         if (tid == 78) side[78] = dyn ? 2u : (unsigned)s.fixed;
         if (tid == 79) side[79] = (unsigned)hbits;
+    }
+
+    int whbits = 0;       // the window block's header bits
+    if (WIN && !WRITE) {
+        // the window parse over the same arrays (the five-distance parse is done with them), its block against the choice above
+        __syncthreads();
+        for (int i = tid; i < PNG_SEG + 4; i += 256) s_mark[i] = i == 0 ? 1 : 0;
+        png_window_tokens(d, seg, n, tid, s_raw, s_lead, s_tokw, s_next);
+        if (tid == 0) s_next[PNG_SEG] = (unsigned short)n;
+        __syncthreads();
+        png_chain(s_next, s_mark, n, tid);
+        bool ok;
+        const int wbits = png_window_codes(s_img, s_pm, s_red, s_tokw, s_mark, s_b, n, tid, whbits, ok);
+        const int wbytes = s.final ? (wbits + 7) >> 3 : ((wbits + 3 + 7) >> 3) + 4;
+        win = ok && s.pre + wbytes < s.body;   // strictly shorter, or the choice above stands
+        unsigned *side = (unsigned *)(d.side + (size_t)seg * SIDE) + PNG_SIDE / 4;
+        if (tid < PNG_WLEN_WORDS) side[tid] = s_img[PNG_W_LEN + tid];
+        if (tid == PNG_WLEN_WORDS) side[PNG_WLEN_WORDS] = win ? 3u : 0u;
+        if (tid == PNG_WLEN_WORDS + 1) side[PNG_WLEN_WORDS + 1] = (unsigned)whbits;
+        if (win) {   // (workgroup-uniform) the counters are those of the parse written
+            s.body = s.pre + wbytes;
+            s.fixed = 1; dyn = false;
+            nlit = 0; nmat = 0;
+            int nwin = 0, nfar = 0;
+            for (int k = 0; k < PNG_PER; ++k) {
+                const int i = base + k;
+                if (i < n && s_mark[i]) {
+                    const unsigned t = s_tokw[i];
+                    if (t) { ++nmat; nwin += (int)(t >> 25); nfar += ((t >> 9) & 0xFFFFu) > PNG_FAR; }
+                    else ++nlit;
+                }
+            }
+            if (nwin) atomicAdd(&s_tokens[2], nwin);
+            if (nfar) atomicAdd(&s_tokens[3], nfar);
+        }
     }
 
     if (!WRITE) {
@@ -511,12 +851,89 @@ __global__ void __launch_bounds__(256) k_png_segment(PngDev d) {
             if (s_tokens[0]) atomicAdd(&d.cnt[6], (unsigned long long)s_tokens[0]);
             if (s_tokens[1]) atomicAdd(&d.cnt[7], (unsigned long long)s_tokens[1]);
             if (DYN && dyn) { atomicAdd(&d.cnt[8], 1ull); atomicAdd(&d.cnt[9], (unsigned long long)hbits); }
+            if (WIN && win) {
+                atomicAdd(&d.cnt[10], 1ull); atomicAdd(&d.cnt[13], (unsigned long long)whbits);
+                if (s_tokens[2]) atomicAdd(&d.cnt[11], (unsigned long long)s_tokens[2]);
+                if (s_tokens[3]) atomicAdd(&d.cnt[12], (unsigned long long)s_tokens[3]);
+            }
         }
         return;
     }
 
-    if (DYN && WRITE) {
-        const unsigned *side = (const unsigned *)(d.side + (size_t)seg * PNG_SIDE);
+    if (WIN && WRITE && win) {   // the window block, as the dynamic block below with PNG_WND distance symbols and tokens in two pieces
+        const unsigned *side = (const unsigned *)(d.side + (size_t)seg * SIDE) + PNG_SIDE / 4;
+        whbits = (int)side[PNG_WLEN_WORDS + 1];
+        unsigned char *len = (unsigned char *)s_dyn;
+        unsigned *tab = s_dyn + PNG_WLEN_WORDS;
+        if (tid < PNG_WLEN_WORDS) s_dyn[tid] = side[tid];
+        __syncthreads();
+        for (int e = tid; e < PNG_WNLEN; e += 256) tab[e] = png_canonical<PNG_WND>(len, e);
+        __syncthreads();
+        int dbits = 0;
+#pragma unroll
+        for (int k = 0; k < PNG_PER; ++k) {
+            const int i = base + k;
+            if (i < n && s_mark[i]) {
+                unsigned v0, v1; int n0, n1;
+                png_win_token(tab, s_tokw[i], c[8 + k], v0, n0, v1, n1);
+                dbits += n0 + n1;
+            }
+        }
+        int dtot;
+        const int dbefore = block_excl_scan_256(dbits, s_w, dtot);
+        const unsigned eob = tab[256];
+        s.fixed = 1; dyn = true;   // (a bit image, built here)
+        s.body = min(d.len[seg + 1] - d.len[seg] - 12, s.pre + 5 + n);   // the payload the count pass allotted
+        const int words = ((s.body + 3) >> 2) + 2;
+        for (int w = tid; w < words; w += 256) s_img[w] = 0u;
+        __syncthreads();
+        const int top = 32 * words;   // (bits past the image are never written, whatever the side record says)
+        auto put = [&](int o, unsigned val, int nb) {
+            const int w = o >> 5, sh = o & 31;
+            if (o + nb > top) return;
+            atomicOr(&s_img[w], val << sh);
+            if (sh + nb > 32) atomicOr(&s_img[w + 1], val >> (32 - sh));
+        };
+        int o = 8 * s.pre + 3 + whbits + dbefore;
+#pragma unroll
+        for (int k = 0; k < PNG_PER; ++k) {
+            const int i = base + k;
+            if (i < n && s_mark[i]) {
+                unsigned v0, v1; int n0, n1;
+                png_win_token(tab, s_tokw[i], c[8 + k], v0, n0, v1, n1);
+                put(o, v0, n0);
+                if (n1) put(o + n0, v1, n1);
+                o += n0 + n1;
+            }
+        }
+        if (tid == 0) {
+            if (s.pre) atomicOr(&s_img[0], 0x0178u);
+            atomicOr(&s_img[s.pre >> 2], (unsigned)(s.final | 4) << (8 * s.pre));   // BFINAL, BTYPE 10 (its low bit first)
+            put(8 * s.pre + 3 + whbits + dtot, eob & 0xFFFFu, (int)(eob >> 16));
+            if (!s.final) {
+                const int e = s.body - 2;
+                atomicOr(&s_img[e >> 2], 0xFFu << (8 * (e & 3)));
+                atomicOr(&s_img[(e + 1) >> 2], 0xFFu << (8 * ((e + 1) & 3)));
+            }
+        }
+        if (tid == 64) {   // the header: HLIT, HDIST, HCLEN, the code-length code's lengths, the coded lengths
+            const int hlit = png_hlit(len), hdist = png_hdist<PNG_WND>(len), hclen = png_hclen<PNG_WND>(len);
+            int ho = 8 * s.pre + 3;
+            put(ho, (unsigned)(hlit - 257) | (unsigned)(hdist - 1) << 5 | (unsigned)(hclen - 4) << 10, 14);
+            ho += 14;
+            for (int q = 0; q < hclen; ++q) { put(ho, len[PNG_NLL + PNG_WND + PNG_CL_ORDER[q]], 3); ho += 3; }
+            png_run_length(len, hlit, hdist, [&](int sym, int ev, int eb) {
+                const unsigned e = tab[PNG_NLL + PNG_WND + sym];
+                const int nb = (int)(e >> 16);
+                put(ho, (e & 0xFFFFu) | (unsigned)ev << nb, nb + eb);
+                ho += nb + eb;
+            });
+        }
+        __syncthreads();
+    }
+
+    if (DYN && WRITE && !(WIN && win)) {
+        const unsigned *side = (const unsigned *)(d.side + (size_t)seg * SIDE);
         dyn = side[78] == 2u;   // (workgroup-uniform)
         if (dyn) {
             hbits = (int)side[79];
@@ -698,19 +1115,139 @@ __global__ void __launch_bounds__(256) k_png_scan(PngDev d) {
     }
 }
 
+// --- the candidates of the whole stream (coding = window) ---
+// A stable LSD radix sort of the positions [0, raw - 2) by their three bytes, one byte a pass, leaves equal keys in stream order: a
+// position's predecessor in the sorted order is the most recent earlier position with its key, and k_png_prev keeps it when it lies
+// within PNG_WINDOW.  A pass is three kernels: k_png_sort_hist counts the digits of every workgroup's tile of PNG_SORT_TILE items,
+// k_png_sort_scan (one workgroup per digit) scans each digit's counts over the workgroups and leaves its total, k_png_sort_scatter ranks
+// its tile again and moves (key, position) to the other side.  Item g of a tile belongs to wave g / 1024, round (g / 64) % 16, lane
+// g % 64: a wave walks its 1024 items in order, 64 at a time.  The rank of an item among the wave's earlier items of its digit is the
+// wave's running count (LDS, one row per wave: nobody else touches it) plus the lanes below it with the same digit, found from eight
+// ballots -- no atomic, so nothing serialises on a flat picture (every key equal).
+#define PNG_SORT_ROUNDS (PNG_SORT_TILE / 256)
+static_assert(PNG_SORT_TILE == 4 * 64 * PNG_SORT_ROUNDS, "four waves, whole rounds");
+
+template <int PASS>
+__device__ __forceinline__ void png_sort_item(const PngDev &d, int g, int m, unsigned &key, unsigned &pos) {
+    key = 0u; pos = 0u;
+    if (g >= m) return;
+    if (PASS == 0) { key = (unsigned)d.flt[g] | (unsigned)d.flt[g + 1] << 8 | (unsigned)d.flt[g + 2] << 16; pos = (unsigned)g; }   // (g + 2 < raw)
+    else { key = d.sort_key[(PASS - 1) & 1][g]; pos = d.sort_pos[(PASS - 1) & 1][g]; }
+}
+// one round of a wave: the item's rank among the wave's items so far with its digit; cnt: the wave's counts [256]
+__device__ __forceinline__ int png_sort_rank(unsigned digit, bool valid, int *cnt, int lane) {
+    unsigned long long peers = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const bool bit = (digit >> b) & 1u;
+        const unsigned long long on = __ballot(bit);
+        peers &= bit ? on : ~on;
+    }
+    int rank = 0;
+    if (valid) {
+        const int had = cnt[digit];
+        rank = had + __popcll(peers & ((1ull << lane) - 1ull));
+        if (((peers >> lane) >> 1) == 0ull) cnt[digit] = had + __popcll(peers);   // the highest lane of the digit writes: one lane per address
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the next round reads what this one wrote, in other lanes of this wave
+    __builtin_amdgcn_wave_barrier();
+    return rank;
+}
+
+template <int PASS, bool SCATTER>
+__global__ void __launch_bounds__(256) k_png_sort(PngDev d) {
+    __shared__ int s_cnt[4][256];
+    __shared__ int s_base[256];
+    __shared__ int s_w[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, wg = blockIdx.x;
+    const int m = d.raw - 2;
+    const int first = wg * PNG_SORT_TILE + wave * (PNG_SORT_TILE / 4) + lane;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) s_cnt[w][tid] = 0;
+    __syncthreads();
+    unsigned key[PNG_SORT_ROUNDS], pos[PNG_SORT_ROUNDS];
+    int rank[PNG_SORT_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < PNG_SORT_ROUNDS; ++r) png_sort_item<PASS>(d, first + 64 * r, m, key[r], pos[r]);
+#pragma unroll
+    for (int r = 0; r < PNG_SORT_ROUNDS; ++r) rank[r] = png_sort_rank((key[r] >> (8 * PASS)) & 255u, first + 64 * r < m, s_cnt[wave], lane);
+    __syncthreads();
+    const int c0 = s_cnt[0][tid], c1 = s_cnt[1][tid], c2 = s_cnt[2][tid], c3 = s_cnt[3][tid];   // digit tid in the four waves
+    if (!SCATTER) { d.hist[(size_t)tid * d.nsort + wg] = c0 + c1 + c2 + c3; return; }
+    int total;
+    const int below = block_excl_scan_256(d.hist[(size_t)256 * d.nsort + tid], s_w, total);   // the items of the smaller digits
+    s_base[tid] = below + d.hist[(size_t)tid * d.nsort + wg];                                 // + this digit's in the earlier workgroups
+    s_cnt[0][tid] = 0; s_cnt[1][tid] = c0; s_cnt[2][tid] = c0 + c1; s_cnt[3][tid] = c0 + c1 + c2;   // + in this workgroup's earlier waves
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < PNG_SORT_ROUNDS; ++r) {
+        if (first + 64 * r >= m) continue;
+        const unsigned digit = (key[r] >> (8 * PASS)) & 255u;
+        const int to = s_base[digit] + s_cnt[wave][digit] + rank[r];   // the ranks are a permutation of [0, m)
+        if ((unsigned)to >= (unsigned)m) continue;                     // (never: no store leaves the arrays whatever the counts say)
+        d.sort_key[PASS & 1][to] = key[r];
+        d.sort_pos[PASS & 1][to] = pos[r];
+    }
+}
+
+// one workgroup per digit: its counts over the sort's workgroups -> their exclusive scan in place, the total behind the table
+__global__ void __launch_bounds__(256) k_png_sort_scan(PngDev d) {
+    __shared__ int s_w[4];
+    const int tid = threadIdx.x, n = d.nsort;
+    int *row = d.hist + (size_t)blockIdx.x * n;
+    int run = 0;
+    for (int c0 = 0; c0 < n; c0 += 256) {
+        const int i = c0 + tid;
+        int tot;
+        const int ex = block_excl_scan_256(i < n ? row[i] : 0, s_w, tot);
+        if (i < n) row[i] = run + ex;
+        run += tot;
+    }
+    if (tid == 0) d.hist[(size_t)256 * n + blockIdx.x] = run;
+}
+
+// prev of every position: the sorted predecessor where it has the same key and lies within the window (the sort is stable: it is the
+// most recent one); the stream's last two positions have no key
+__global__ void __launch_bounds__(256) k_png_prev(PngDev d) {
+    const int k = blockIdx.x * 256 + threadIdx.x, m = max(d.raw - 2, 0);
+    if (k < d.raw - m) d.prev[m + k] = PNG_NONE;
+    if (k >= m) return;
+    const unsigned i = d.sort_pos[0][k];   // (three passes: the sorted order ends on side 0)
+    unsigned p = PNG_NONE;
+    if (k > 0 && d.sort_key[0][k - 1] == d.sort_key[0][k]) {
+        const unsigned j = d.sort_pos[0][k - 1];
+        if (i - j <= PNG_WINDOW) p = j;
+    }
+    if (i < (unsigned)m) d.prev[i] = p;   // (always)
+}
+
+template <int PASS>
+static void l_png_sort_pass(PngDev &d) {
+    hipLaunchKernelGGL((k_png_sort<PASS, false>), dim3(d.nsort), dim3(256), 0, d.stream, d);
+    hipLaunchKernelGGL(k_png_sort_scan, dim3(256), dim3(256), 0, d.stream, d);
+    hipLaunchKernelGGL((k_png_sort<PASS, true>), dim3(d.nsort), dim3(256), 0, d.stream, d);
+}
+static void l_png_candidates(PngDev &d) {
+    if (d.nsort > 0) { l_png_sort_pass<0>(d); l_png_sort_pass<1>(d); l_png_sort_pass<2>(d); }
+    hipLaunchKernelGGL(k_png_prev, dim3((max(d.raw - 2, 2) + 255) / 256), dim3(256), 0, d.stream, d);
+}
+
 static void l_png_filter(PngDev &d) { hipLaunchKernelGGL(k_png_filter, dim3(d.H), dim3(256), 0, d.stream, d); }
 static void l_png_count(PngDev &d) {
-    if (d.side) hipLaunchKernelGGL((k_png_segment<false, true>), dim3(d.nseg), dim3(256), 0, d.stream, d);
+    if (d.prev) hipLaunchKernelGGL((k_png_segment<false, true, true>), dim3(d.nseg), dim3(256), 0, d.stream, d);
+    else if (d.side) hipLaunchKernelGGL((k_png_segment<false, true>), dim3(d.nseg), dim3(256), 0, d.stream, d);
     else hipLaunchKernelGGL((k_png_segment<false>), dim3(d.nseg), dim3(256), 0, d.stream, d);
 }
 static void l_png_scan(PngDev &d) { hipLaunchKernelGGL(k_png_scan, dim3(1), dim3(256), 0, d.stream, d); }
 static void l_png_write(PngDev &d) {
-    if (d.side) hipLaunchKernelGGL((k_png_segment<true, true>), dim3(d.nseg), dim3(256), 0, d.stream, d);
+    if (d.prev) hipLaunchKernelGGL((k_png_segment<true, true, true>), dim3(d.nseg), dim3(256), 0, d.stream, d);
+    else if (d.side) hipLaunchKernelGGL((k_png_segment<true, true>), dim3(d.nseg), dim3(256), 0, d.stream, d);
     else hipLaunchKernelGGL((k_png_segment<true>), dim3(d.nseg), dim3(256), 0, d.stream, d);
 }
 
 static void register_png_launchers(Launch &L) {
     L.png_filter = l_png_filter;
+    L.png_candidates = l_png_candidates;
     L.png_count = l_png_count;
     L.png_scan = l_png_scan;
     L.png_write = l_png_write;

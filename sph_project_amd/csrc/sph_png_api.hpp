@@ -3,13 +3,15 @@
 // sph_png.hpp, the stream is defined in DESIGN.md 21.
 #pragma once
 
-enum PngBufId { PB_FLT, PB_LEN, PB_ADLER, PB_CNT, PB_SIDE, PB_COUNT_ };
+enum PngBufId { PB_FLT, PB_LEN, PB_ADLER, PB_CNT, PB_SIDE, PB_WSIDE, PB_PREV, PB_KEY0, PB_KEY1, PB_POS0, PB_POS1, PB_HIST, PB_COUNT_ };   // from PB_WSIDE on: coding = window
 
 struct SphPng : FrameEncoder {   // header: signature, IHDR; payload: the segments' chunks and the Adler-32's; trailer: IEND
     SphPngParams prm;
     PngDev d{};
     DevBuf buf[PB_COUNT_];
     SphPngStats stats{};           // of the frame held
+    SphPngWindowStats wstats{};
+    bool have_candidates = false;  // the frame held was encoded in coding = window: prev[] is its candidates
     int32_t coding = SPH_PNG_CODING_FIXED;
 };
 
@@ -24,7 +26,7 @@ static int64_t png_raw_bytes(const SphPngParams &p) { return (int64_t)p.height *
 static int64_t png_segments(const SphPngParams &p) { return (png_raw_bytes(p) + PNG_SEG - 1) / PNG_SEG; }
 // signature 8, IHDR 25, per segment a chunk frame of 12 and at worst a stored block header of 5 around its raw bytes, the zlib header 2,
 // the Adler-32's chunk 16, IEND 12.  The same in either coding: a dynamic block is written only where it is strictly shorter than the
-// fixed / stored choice, so no segment grows.
+// fixed / stored choice, and a window block only where it is strictly shorter than that, so no segment grows.
 static int64_t png_bound(const SphPngParams &p) { return 8 + 25 + png_segments(p) * (12 + 5) + png_raw_bytes(p) + 2 + 16 + 12; }
 
 // CRC-32 on the host: for the 17 bytes of IHDR only (the payload's CRCs are the device's)
@@ -77,7 +79,8 @@ extern "C" int sph_png_create(const SphPngParams *params, SphPng **out) {
     for (int j = 1; j < 8; ++j) d.crc_pow[j] = png_crc_mul(d.crc_pow[j - 1], d.crc_pow[j - 1]);
     DevBuf *b = v->buf;
     int rc = enc_open(v, "sph_png_create", p.width, p.height, dev, p.fast_math);
-    if (!rc && (b[PB_FLT].reserve(nullptr, (size_t)d.nseg * PNG_SEG) || b[PB_LEN].reserve(nullptr, sizeof(int) * ((size_t)d.nseg + 1)) ||
+    if (!rc && (b[PB_FLT].reserve(nullptr, (size_t)d.nseg * PNG_SEG + 16) ||   // (+ 16: png_word_at reads the word behind a byte)
+                b[PB_LEN].reserve(nullptr, sizeof(int) * ((size_t)d.nseg + 1)) ||
                 b[PB_ADLER].reserve(nullptr, sizeof(unsigned) * 2 * (size_t)d.nseg) ||
                 b[PB_CNT].reserve(nullptr, PNG_NCNT * sizeof(unsigned long long) + sizeof(unsigned)) || b[PB_SIDE].reserve(nullptr, (size_t)d.nseg * PNG_SIDE)))
         rc = enc_no_room(v, "sph_png_create");
@@ -85,6 +88,7 @@ extern "C" int sph_png_create(const SphPngParams *params, SphPng **out) {
     d.flt = (unsigned char *)b[PB_FLT].p; d.len = (int *)b[PB_LEN].p; d.adler = (unsigned *)b[PB_ADLER].p;
     d.cnt = (unsigned long long *)b[PB_CNT].p; d.sum = (unsigned *)(d.cnt + PNG_NCNT);
     d.side = nullptr;   // coding = fixed
+    d.prev = nullptr;
     d.stream = v->stream;
     *out = v;
     return SPH_OK;
@@ -100,10 +104,29 @@ extern "C" const char *sph_png_last_error(SphPng *v) { return last_error(v); }
 
 extern "C" int sph_png_set_coding(SphPng *v, int32_t coding) {
     if (!v) return fail(nullptr, SPH_ERR_INVALID, "sph_png_set_coding: null encoder");
-    if (coding != SPH_PNG_CODING_FIXED && coding != SPH_PNG_CODING_DYNAMIC)
-        return fail(v, SPH_ERR_INVALID, "sph_png_set_coding: coding is %d (fixed) or %d (dynamic), not %d", SPH_PNG_CODING_FIXED, SPH_PNG_CODING_DYNAMIC, (int)coding);
+    if (coding != SPH_PNG_CODING_FIXED && coding != SPH_PNG_CODING_DYNAMIC && coding != SPH_PNG_CODING_WINDOW)
+        return fail(v, SPH_ERR_INVALID, "sph_png_set_coding: coding is %d (fixed), %d (dynamic) or %d (window), not %d", SPH_PNG_CODING_FIXED,
+                    SPH_PNG_CODING_DYNAMIC, SPH_PNG_CODING_WINDOW, (int)coding);
+    PngDev &d = v->d;
+    if (coding == SPH_PNG_CODING_WINDOW) {   // the sort's two sides, prev and the larger side records: only an encoder that asks has them
+        HIPCHK(v, hipSetDevice(v->device));
+        DevBuf *b = v->buf;
+        const size_t words = sizeof(unsigned) * (size_t)d.raw;
+        const int nsort = d.raw > 2 ? (d.raw - 2 + PNG_SORT_TILE - 1) / PNG_SORT_TILE : 0;
+        int rc = b[PB_WSIDE].reserve(v, (size_t)d.nseg * PNG_WSIDE);
+        if (!rc) rc = b[PB_PREV].reserve(v, sizeof(unsigned) * (size_t)d.nseg * PNG_SEG);
+        for (int k = PB_KEY0; !rc && k <= PB_POS1; ++k) rc = b[k].reserve(v, words);
+        if (!rc) rc = b[PB_HIST].reserve(v, sizeof(int) * 256 * ((size_t)nsort + 1));
+        if (rc) return rc;   // (the encoder is as it was)
+        d.nsort = nsort;
+        d.sort_key[0] = (unsigned *)b[PB_KEY0].p; d.sort_key[1] = (unsigned *)b[PB_KEY1].p;
+        d.sort_pos[0] = (unsigned *)b[PB_POS0].p; d.sort_pos[1] = (unsigned *)b[PB_POS1].p;
+        d.hist = (int *)b[PB_HIST].p;
+    }
     v->coding = coding;
-    v->d.side = coding == SPH_PNG_CODING_DYNAMIC ? (unsigned char *)v->buf[PB_SIDE].p : nullptr;   // which instantiations the launchers run
+    // which instantiations the launchers run
+    d.side = (unsigned char *)(coding == SPH_PNG_CODING_DYNAMIC ? v->buf[PB_SIDE].p : coding == SPH_PNG_CODING_WINDOW ? v->buf[PB_WSIDE].p : nullptr);
+    d.prev = coding == SPH_PNG_CODING_WINDOW ? (unsigned *)v->buf[PB_PREV].p : nullptr;
     return SPH_OK;
 }
 
@@ -116,6 +139,12 @@ static int png_run(SphPng *v) {
     HIPCHK(v, k.mark(1));
     v->L->png_filter(d);
     HIPCHK(v, k.mark(2));
+    StageClock &kc = v->clk[1];   // (its first two events: around the candidates)
+    if (d.prev) {
+        HIPCHK(v, kc.mark(0));
+        v->L->png_candidates(d);
+        HIPCHK(v, kc.mark(1));
+    }
     v->L->png_count(d);
     HIPCHK(v, k.mark(3));
     v->L->png_scan(d);
@@ -144,6 +173,15 @@ static int png_run(SphPng *v) {
     for (int t = 0; t < 5; ++t) o.filter_rows[t] = (int64_t)c[t];
     o.ms_input = k.ms(0, 1); o.ms_filter = k.ms(1, 2); o.ms_count = k.ms(2, 3); o.ms_scan = k.ms(3, 4); o.ms_write = k.ms(4, 5);
     o.ms_total = k.ms(0, 5);
+    SphPngWindowStats &w = v->wstats;
+    w = SphPngWindowStats{};
+    v->have_candidates = d.prev != nullptr;
+    if (d.prev) {
+        w.window_segments = (int64_t)c[10]; w.window_matches = (int64_t)c[11]; w.window_far_matches = (int64_t)c[12];
+        w.window_header_bits = (int64_t)c[13];
+        w.ms_candidates = kc.ms(0, 1);
+        o.ms_count = ev_ms(kc.ev[1], k.ev[3]);   // (the count pass alone, as in the other codings)
+    }
     return SPH_OK;
 }
 
@@ -160,6 +198,21 @@ extern "C" int sph_png_encode_render(SphPng *v, SphRender *r) {
 extern "C" int sph_png_size(SphPng *v, int64_t *bytes) { return enc_size(v, "sph_png_size", bytes); }
 
 extern "C" int sph_png_download(SphPng *v, uint8_t *dst) { return enc_download(v, "sph_png_download", dst); }
+
+extern "C" int sph_png_window_stats(SphPng *v, SphPngWindowStats *out) {
+    if (!v || !out) return SPH_ERR_INVALID;
+    *out = v->have_frame ? v->wstats : SphPngWindowStats{};
+    return SPH_OK;
+}
+
+extern "C" int sph_png_download_candidates(SphPng *v, uint32_t *prev, size_t n) {
+    if (!v || !prev) return SPH_ERR_INVALID;
+    if (!v->have_frame || !v->have_candidates) return fail(v, SPH_ERR_INVALID, "sph_png_download_candidates: the frame held was not encoded in the window coding");
+    if (n != (size_t)v->d.raw) return fail(v, SPH_ERR_INVALID, "sph_png_download_candidates: the filtered stream has %d bytes, not %zu", v->d.raw, n);
+    HIPCHK(v, hipSetDevice(v->device));
+    HIPCHK(v, hipMemcpy(prev, v->buf[PB_PREV].p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
 
 extern "C" int sph_png_stats(SphPng *v, SphPngStats *out) {
     if (!v || !out) return SPH_ERR_INVALID;

@@ -89,8 +89,8 @@ def parse_args(argv=None):
     parser.add_argument("--camera_fov", type=float, default=70.0, help="vertical, degrees")
     parser.add_argument("--png_device", action="store_true",
                         help="compress the PNG files on the GPU from the device image (DESIGN.md 21), as run_simulation.py --png_device does")
-    parser.add_argument("--png_coding", default=None, choices=["fixed", "dynamic"],
-                        help="with --png_device: fixed (the default) or dynamic Huffman blocks, as run_simulation.py --png_coding")
+    parser.add_argument("--png_coding", default=None, choices=["fixed", "dynamic", "window"],
+                        help="with --png_device: fixed (the default), dynamic Huffman blocks or window matches, as run_simulation.py --png_coding")
     args = parser.parse_args(argv)
     if args.png_coding is not None and not args.png_device:
         parser.error("--png_coding chooses the device encoder's code: give --png_device as well")

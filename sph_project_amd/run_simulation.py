@@ -14,7 +14,8 @@ adds {out}/raw_view.avi / {out}/render.avi, the same frames as Motion-JPEG compr
 (DESIGN.md 24), at the cost of a particle frame where --render_meshes pays for a reconstruction.  --surface_thickness makes that
 surface translucent: the fluid's thickness along every ray lets rigid bodies and the box show through.
 --png_device writes the PNG files from the device image as well (DESIGN.md 21): no pixel is downloaded, no zlib runs on the host;
---png_coding dynamic makes those files smaller (dynamic Huffman blocks) for a slower encode.
+--png_coding dynamic makes those files smaller (dynamic Huffman blocks) for a slower encode, --png_coding window smaller again (matches from
+the 32 KB before a position).
 --gpus N shards the scene over N ranks (z-slabs, one process each, started by launch.py): the frames are composited over the ranks
  and written by rank 0, the PLY of a fluid object is written in rank order, one part per rank."""
 import argparse
@@ -144,9 +145,10 @@ def parse_args(argv=None):
     parser.add_argument("--png_device", action="store_true",
                         help="compress raw_view.png / render.png on the GPU from the renderer's device image (DESIGN.md 21: lossless, the "
                              "same pixels, other bytes than the host's zlib) where the default downloads the frame and runs zlib on it")
-    parser.add_argument("--png_coding", default=None, choices=["fixed", "dynamic"],
+    parser.add_argument("--png_coding", default=None, choices=["fixed", "dynamic", "window"],
                         help="with --png_device: the entropy coding of the files (DESIGN.md 21).  fixed (the default): the fixed Huffman "
-                             "code; dynamic: per segment a dynamic Huffman block where it is shorter -- smaller files, a slower encode")
+                             "code; dynamic: per segment a dynamic Huffman block where it is shorter -- smaller files, a slower encode; window: "
+                             "also matches from the 32 KB before a position -- smaller files again, a slower encode again")
     parser.add_argument("--export_device", action="store_true",
                         help="format particle_object_{id}.ply (and with --reconstruct particle_object_{id}.obj) on the GPU from the device "
                              "state (DESIGN.md 23: the same bytes as the host writers, no position or mesh download); needs a scene with "

@@ -4,10 +4,11 @@ with --render_meshes, a mesh frame of the reconstructed surface (render.png): on
 the GPU encode by stage (HIP events) and around the call (host clock), the download of the file, and in the same run what storing the
 same frame costs on the parent's path: the raw download of the frame (sph_render_download) plus encode_png on the host.  Sizes: the
 device's file against encode_png (zlib level 6) and against the same filter-0 stream at zlib level 1.  The device's file is decoded
-once per state and compared with the pixels.  --coding fixed | dynamic | both: which entropy coding the encoder uses; `both` encodes every
-timed frame with two encoders in alternation (the same frame, the same host reference) and reports per coding the stage times, the file
-bytes, size_vs_host, dynamic_segments and the dynamic headers' bytes.  One JSON line per state, frame kind and coding; with --out also
-written to that file (profiles/png_bench_c2.txt, profiles/png_dynamic_bench_c2.txt)."""
+once per state and compared with the pixels.  --coding fixed | dynamic | window | both | all: which coding the encoder uses; `both`
+(fixed, dynamic) and `all` (fixed, dynamic, window) encode every timed frame with one encoder per coding in alternation (the same frame,
+the same host reference) and report per coding the stage times, the file bytes, size_vs_host, dynamic_segments and the dynamic headers'
+bytes, and for window the candidates' stage, window_segments and the far matches.  One JSON line per state, frame kind and coding; with
+--out also written to that file (profiles/png_bench_c2.txt, profiles/png_dynamic_bench_c2.txt, profiles/png_window_bench_c2.txt)."""
 import argparse
 import json
 import os
@@ -47,12 +48,14 @@ def measure(r, encoders, draw, frames, label, step, kind):
             enc_host, _ = _ms(lambda: v._chk(v.lib.sph_png_encode_render(v.h, r._last), "sph_png_encode_render"))
             st = v.stats()
             dl_host, png_dev = _ms(v._download)
-            rows[coding].append(dict(encode_ms=st["ms_total"], filter_ms=st["ms_filter"], count_ms=st["ms_count"], scan_ms=st["ms_scan"],
+            rows[coding].append(dict(encode_ms=st["ms_total"], filter_ms=st["ms_filter"], candidates_ms=st["ms_candidates"], count_ms=st["ms_count"], scan_ms=st["ms_scan"],
                                      write_ms=st["ms_write"], encode_host_ms=enc_host, file_download_host_ms=dl_host,
                                      raw_download_host_ms=raw_host, png_encode_host_ms=png_host,
                                      gpu_path_host_ms=enc_host + dl_host, host_path_host_ms=raw_host + png_host,
                                      device_png_bytes=len(png_dev), host_png_bytes=len(png), stored_segments=st["stored_segments"],
                                      dynamic_segments=st["dynamic_segments"], dynamic_header_bytes=(st["dynamic_header_bits"] + 7) // 8,
+                                     window_segments=st["window_segments"], window_matches=st["window_matches"],
+                                     window_far_matches=st["window_far_matches"], window_header_bytes=(st["window_header_bits"] + 7) // 8,
                                      segments=st["segments"], literals=st["literals"], matches=st["matches"], filter_rows=st["filter_rows"]))
     raw = np.zeros((r.height, 1 + 3 * r.width), np.uint8)
     raw[:, 1:] = rgb.reshape(r.height, 3 * r.width)
@@ -82,15 +85,15 @@ def main():
     ap.add_argument("--motion-step", type=int, default=2500, help="0: from rest only")
     ap.add_argument("--render_meshes", action="store_true", help="also a mesh frame of the reconstructed fluid surface per state")
     ap.add_argument("--filter", default="adaptive")
-    ap.add_argument("--coding", default="fixed", choices=["fixed", "dynamic", "both"],
-                    help="both: every timed frame is encoded with a fixed and a dynamic encoder in alternation")
+    ap.add_argument("--coding", default="fixed", choices=["fixed", "dynamic", "window", "both", "all"],
+                    help="both / all: every timed frame is encoded with a fixed and a dynamic (and a window) encoder in alternation")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     container, solver = P.build_product(P.c2_scene())
     solver.prepare()
     r = FrameRenderer(container.dx)
     filt = a.filter if a.filter == "adaptive" else int(a.filter)
-    encoders = {c: PngEncoder(r.width, r.height, filter=filt, coding=c) for c in (("fixed", "dynamic") if a.coding == "both" else (a.coding,))}
+    encoders = {c: PngEncoder(r.width, r.height, filter=filt, coding=c) for c in {"both": ("fixed", "dynamic"), "all": ("fixed", "dynamic", "window")}.get(a.coding, (a.coding,))}
     rm = recon = None
     if a.render_meshes:
         rm = FrameRenderer(container.dx, box=(np.zeros(3), np.asarray(container.domain_end, dtype=np.float64)))

@@ -26,9 +26,12 @@ def short(name):
     m = re.search(r"(k_video_interval)<\s*(true|false)", name)   # the video encoder's passes: <false> count, <true> write
     if m:
         return m.group(1) + ("<write>" if m.group(2) == "true" else "<count>")
-    m = re.search(r"(k_png_segment)<\s*(true|false)(?:,\s*(true|false))?", name)   # the PNG encoder's passes: <false> count, <true> write; second: dynamic coding
+    m = re.search(r"(k_png_segment)<\s*(true|false)(?:,\s*(true|false))?(?:,\s*(true|false))?", name)   # the PNG encoder's passes: <false> count, <true> write; second: dynamic coding; third: window coding
     if m:
-        return m.group(1) + ("<write" if m.group(2) == "true" else "<count") + (", dynamic>" if m.group(3) == "true" else ">")
+        return m.group(1) + ("<write" if m.group(2) == "true" else "<count") + (", window>" if m.group(4) == "true" else ", dynamic>" if m.group(3) == "true" else ">")
+    m = re.search(r"(k_png_sort)<\s*\d+,\s*(true|false)", name)   # the candidate sort's passes: <false> digit counts, <true> scatter (the three digits together)
+    if m:
+        return m.group(1) + ("<scatter>" if m.group(2) == "true" else "<count>")
     m = re.search(r"(k_\w+)", name)
     return m.group(1) if m else name[:40]
 
