@@ -936,6 +936,89 @@ int sph_text_stats(SphText *t, SphTextStats *out);
    lengths in lengths[n].  For tests of the routine, not a product path.  SPH_ERR_CAPACITY: cap < the sum of the lengths. */
 int sph_text_format_f32_host(const float *values, int64_t n, char *out, int64_t cap, int64_t *lengths);
 
+/* --- Diffuse particles: spray, foam and bubbles from the fluid state ---------------------------------------------- */
+/* A second particle set, generated from the fluid and carried by it, that never acts back on it (Ihmsen, Akinci, Akinci, Teschner
+   2012, as the project states it in DESIGN.md 26).  One sph_foam_step_* call: the fluid set is binned into the object's own grid of
+   edge h = 4 radius (ordered by id inside a cell), the diffuse particles are advected and classified by their fluid neighbours
+   (spray ballistic, foam with the fluid and ageing, bubbles buoyant and dragged), normals and the potentials trapped air / wave
+   crest / energy are summed per fluid particle with w(r) = 1 - r / h, children are generated from counter-based random numbers --
+   a hash of (seed, id, foam step, child, stream), no state -- and written behind the compacted survivors at scanned offsets.  No
+   float atomics: the same input gives the same bytes, and the order of the fluid input does not matter.  float32, the strict
+   build's arithmetic unless fast_math.  One HIP stream per object; synchronous calls. */
+typedef struct {
+    double radius;             /* particle radius r > 0; support h = 4 r */
+    double domain_lo[3], domain_hi[3];   /* the simulation domain: the grid covers it, with one border cell per side */
+    double padding;            /* diffuse particles live in [domain_lo + padding, domain_hi - padding], the fluid's clamp box */
+    double gravity[3];
+    double ta_min, ta_max;     /* clamp limits of the trapped-air, wave-crest and energy potentials, each max > min */
+    double wc_min, wc_max;
+    double e_min, e_max;       /* energy per unit mass, 0.5 |v|^2 */
+    double k_ta, k_wc;         /* children per second at full potential */
+    double life_min, life_max; /* seconds; life_max >= life_min > 0 */
+    double k_b, k_d;           /* bubbles: buoyancy and drag */
+    double normal_min;         /* a particle has a normal where |g_i| >= normal_min h */
+    int32_t n_spray;           /* fewer fluid neighbours: spray */
+    int32_t n_bubble;          /* more: bubble; between the two: foam */
+    int32_t max_per_particle;  /* children of one fluid particle per step, 0..255 */
+    int32_t fast_math;         /* which build's kernels run (0 strict, 1 fast) */
+    int32_t device;            /* HIP device ordinal, -1: current */
+    int32_t reserved;          /* 0 */
+    int64_t max_diffuse;       /* capacity of the diffuse set; 0: twice the fluid capacity seen at the first step */
+    uint64_t seed;
+} SphFoamParams;
+
+typedef struct {
+    int64_t step;              /* foam steps taken (the t of the keys born in the last one) */
+    int64_t fluid;             /* fluid particles of the last step */
+    int64_t diffuse;           /* diffuse particles now */
+    int64_t spray, foam, bubble;   /* the survivors' classes of the last advection */
+    int64_t born, died, dropped;   /* of the last step; dropped: children beyond max_diffuse */
+    int64_t born_total, died_total, dropped_total;
+    int64_t pairs_visited[3];  /* candidate pairs of the advect, normals and potentials walks */
+    int64_t pairs_accepted[3]; /* of those, r < h */
+    int64_t bytes_allocated;
+    double ms_grid, ms_advect, ms_normals, ms_potentials, ms_generate, ms_total;   /* HIP events (ms_grid: input and grid) */
+} SphFoamStats;
+
+typedef struct SphFoam SphFoam;
+/* SPH_ERR_INVALID (before any device is touched): non-finite or non-positive radius, an empty domain, limits with max <= min, negative
+   rates or counts, max_per_particle > 255, a grid of more than 2^30 cells, reserved != 0. */
+int sph_foam_create(const SphFoamParams *params, SphFoam **out);
+void sph_foam_destroy(SphFoam *f);
+const char *sph_foam_last_error(SphFoam *f);
+/* One step of length dt > 0 from the active fluid particles of a live handle (ghosts and dead slots left out), read on the device in
+   the handle's current order; the handle's state is untouched.  SPH_ERR_UNSUPPORTED: a sharded handle or one whose library frame is a
+   permutation of the scene's.  SPH_ERR_INVALID: another device, between sph_step_begin and sph_step_end, dt not positive and finite. */
+int sph_foam_step_handle(SphFoam *f, SphHandle *h, double dt);
+/* The same from host arrays: xyz f32[n][3], vel f32[n][3], ids i32[n] (distinct; they take the place of the handle's particle ids in
+   the random numbers and the keys).  n = 0 is legal: the diffuse particles are advected through empty space. */
+int sph_foam_step_points(SphFoam *f, const float *xyz, const float *vel, const int32_t *ids, int64_t n, double dt);
+/* The caller's own diffuse particles: xyz f32[n][3], vel f32[n][3], life f32[n].  Their keys are 2^63 | serial number (from 0, in
+   call order).  SPH_ERR_CAPACITY: more than max_diffuse in all; SPH_ERR_INVALID: max_diffuse = 0 and no step has sized the set yet. */
+int sph_foam_seed(SphFoam *f, const float *xyz, const float *vel, const float *life, int64_t n);
+int sph_foam_count(SphFoam *f, int64_t *n);
+/* The diffuse set in device order (unspecified; the key identifies a particle: foam step << 40 | id << 8 | child): xyz f32[n][3],
+   vel f32[n][3], life f32[n], key u64[n], cls i32[n] -- the class of the last advection, 0 spray, 1 foam, 2 bubble, 3 born in the
+   last step (children are not advected in their birth step) or seeded since.  Any output may be NULL. */
+int sph_foam_download(SphFoam *f, float *xyz, float *vel, float *life, uint64_t *key, int32_t *cls);
+/* The fluid quantities of the last step, one row per fluid particle of that step: in input order for sph_foam_step_points, in the
+   handle's order (active fluid only) with their particle ids for sph_foam_step_handle.  ta, wc, e, nd f32[n], normal f32[n][3]
+   (zero: no normal), ids i32[n]; any output may be NULL.  SPH_ERR_INVALID: no step yet. */
+int sph_foam_download_potentials(SphFoam *f, float *ta, float *wc, float *e, float *nd, float *normal, int32_t *ids);
+/* forget every diffuse particle (the step counter and the seed serial stay) */
+int sph_foam_clear(SphFoam *f);
+int sph_foam_stats(SphFoam *f, SphFoamStats *out);
+
+/* Diffuse particles in particle frames.  While a foam object is set, sph_render_handle draws its diffuse particles from the device
+   into the frame: spheres of radius_scale x the renderer's radius, coloured by class (rgb_* u8[3]; NULL: 250 250 255 / 255 255 255 /
+   225 235 250), ids 0x80000000 | (low 31 bits of a hash of the key), folded into the key plane before the pixels are finished.  NULL
+   clears it; without it no kernel argument or launch of sph_render_handle changes.  The object must outlive its use here.
+   SPH_ERR_UNSUPPORTED: the surface mode is on (also when it is switched on later: sph_render_handle then refuses), at
+   sph_render_handle for a sharded handle; SPH_ERR_INVALID: another device, radius_scale not positive, and at sph_render_handle a
+   handle whose particle_max_num reaches 2^31 (its ids could not be told from diffuse ones). */
+int sph_render_set_foam(SphRender *r, SphFoam *foam_or_NULL, double radius_scale, const uint8_t *rgb_spray, const uint8_t *rgb_foam,
+                        const uint8_t *rgb_bubble);
+
 #ifdef __cplusplus
 }
 #endif

@@ -232,6 +232,29 @@ class SphTextStats(C.Structure):
     ]
 
 
+class SphFoamParams(C.Structure):
+    _fields_ = [
+        ("radius", C.c_double), ("domain_lo", C.c_double * 3), ("domain_hi", C.c_double * 3), ("padding", C.c_double),
+        ("gravity", C.c_double * 3),
+        ("ta_min", C.c_double), ("ta_max", C.c_double), ("wc_min", C.c_double), ("wc_max", C.c_double),
+        ("e_min", C.c_double), ("e_max", C.c_double), ("k_ta", C.c_double), ("k_wc", C.c_double),
+        ("life_min", C.c_double), ("life_max", C.c_double), ("k_b", C.c_double), ("k_d", C.c_double), ("normal_min", C.c_double),
+        ("n_spray", C.c_int32), ("n_bubble", C.c_int32), ("max_per_particle", C.c_int32), ("fast_math", C.c_int32),
+        ("device", C.c_int32), ("reserved", C.c_int32), ("max_diffuse", C.c_int64), ("seed", C.c_uint64),
+    ]
+
+
+class SphFoamStats(C.Structure):
+    _fields_ = [
+        ("step", C.c_int64), ("fluid", C.c_int64), ("diffuse", C.c_int64), ("spray", C.c_int64), ("foam", C.c_int64), ("bubble", C.c_int64),
+        ("born", C.c_int64), ("died", C.c_int64), ("dropped", C.c_int64),
+        ("born_total", C.c_int64), ("died_total", C.c_int64), ("dropped_total", C.c_int64),
+        ("pairs_visited", C.c_int64 * 3), ("pairs_accepted", C.c_int64 * 3), ("bytes_allocated", C.c_int64),
+        ("ms_grid", C.c_double), ("ms_advect", C.c_double), ("ms_normals", C.c_double), ("ms_potentials", C.c_double),
+        ("ms_generate", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 # return codes (include/sph_hip.h)
 ERR_INVALID, ERR_CAPACITY = -1, -2
 ERR_UNSUPPORTED = -6
@@ -374,6 +397,18 @@ _SIGNATURES = [
     ("sph_text_read", C.c_int, [_VP, _VP, C.c_int64]),
     ("sph_text_stats", C.c_int, [_VP, C.POINTER(SphTextStats)]),
     ("sph_text_format_f32_host", C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP]),
+    ("sph_foam_create", C.c_int, [C.POINTER(SphFoamParams), C.POINTER(_VP)]),
+    ("sph_foam_destroy", None, [_VP]),
+    ("sph_foam_last_error", C.c_char_p, [_VP]),
+    ("sph_foam_step_handle", C.c_int, [_VP, _VP, C.c_double]),
+    ("sph_foam_step_points", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_double]),
+    ("sph_foam_seed", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64]),
+    ("sph_foam_count", C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    ("sph_foam_download", C.c_int, [_VP] * 6),
+    ("sph_foam_download_potentials", C.c_int, [_VP] * 7),
+    ("sph_foam_clear", C.c_int, [_VP]),
+    ("sph_foam_stats", C.c_int, [_VP, C.POINTER(SphFoamStats)]),
+    ("sph_render_set_foam", C.c_int, [_VP, _VP, C.c_double, _VP, _VP, _VP]),
     ("sph_comm_allreduce", C.c_int, [_VP, C.POINTER(C.c_double), C.c_int, C.c_int]),
     ("sph_comm_barrier", C.c_int, [_VP]),
     ("sph_comm_selftest", C.c_int, [_VP, C.c_int]),

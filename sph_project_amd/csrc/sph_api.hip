@@ -1383,3 +1383,4 @@ extern "C" int sph_points_in_mesh(const double *vertices, int n_vertices, const 
 #include "sph_video_api.hpp"
 #include "sph_png_api.hpp"
 #include "sph_text_api.hpp"
+#include "sph_foam_api.hpp"

@@ -241,6 +241,39 @@ struct SurfPost {
     float4 *a, *b;       // [nv] working copies (ping-pong)
 };
 
+// Diffuse particles (sph_foam.hpp): the constants and device buffers of one SphFoam.  The fluid set is binned into the
+// object's own grid of edge h over the domain plus one border cell per side (cell coordinates are clamped into it); linear index
+// (x * cn[1] + y) * cn[2] + z.  Inside a cell the particles are ordered by id, so the grid order is a function of the particle SET.
+#define FOAM_CTR_WORDS 16
+enum FoamCtr { FC_VISIT = 0, FC_ACCEPT = 3, FC_CLASS = 6, FC_DIED = 9, FC_BORN = 10, FC_DROPPED = 11, FC_COUNT = 12 };
+struct FoamDev {
+    float h, pr;                       // support radius 4 r, particle radius r
+    float glo[3];                      // grid origin (the domain's lower corner)
+    int cn[3], G;                      // cells per axis (border cells included), their product
+    float lo[3], hi[3];                // the clamp box: a diffuse particle outside it is deleted
+    float g[3];                        // gravity
+    float ta_lo, ta_hi, wc_lo, wc_hi, e_lo, e_hi, k_ta, k_wc, life_lo, life_hi, k_b, k_d, nmin_h;
+    int n_spray, n_bubble, max_pp;
+    unsigned seed_lo, seed_hi, t;      // the random stream's seed, the foam step
+    float dt;
+    int n;                             // fluid particles of this step
+    int nd, cap;                       // diffuse particles before this step, capacity
+    float4 *xin, *vin; int *idin;      // [n] the fluid set in input order
+    int *pcell, *pslot;                // [n] cell and arrival slot of input particle i
+    int *cell_start;                   // [G + 1] counts -> their exclusive scan
+    float4 *xt, *vt; int *idt, *srct;  // [n] binned, arrival order inside a cell (srct: input index)
+    float4 *xs, *vs; int *ids, *src;   // [n] binned, id order inside a cell
+    float4 *nrm;                       // [n] grid order: unit normal, w = 1 where the particle has one
+    float4 *pot;                       // [n] grid order: ta, wc, e, n_d
+    int *cnt;                          // [n + 1] children per fluid particle -> exclusive scan
+    float4 *dx[2], *dv[2];             // [cap] diffuse particles: (xyz, life) and (velocity, class as int bits); [0] current, [1] compaction target
+    unsigned long long *dkey[2];       // [cap]
+    int *keep;                         // [cap + 1] survivor flags -> exclusive scan
+    unsigned long long *ctr;           // [FOAM_CTR_WORDS] FoamCtr
+    int *scan_tmp;                     // tile sums of the scans
+    hipStream_t stream;
+};
+
 // Particle rendering (sph_render.hpp): camera, shading constants, the particle source and the frame buffers of one
 // SphRender.  Source: pos[i] (xyz), id[i], colour col_home[id[i]] when col_home is set, else col[i] (r | g << 8 | b << 16; both null:
 // white); meta null = every particle drawn, else object mask / ghosts / dead from META_*.  key[p] = (float_bits(t) << 32) | id.
@@ -707,6 +740,14 @@ struct Launch {
     void (*text_write)(TextDev &);              // the rows' characters at the scanned offsets (staged in LDS, aligned 16-byte stores)
     void (*text_check_tri)(TextDev &, int *bad);   // bad[0] = any triangle index outside [0, nv)
     void (*text_compact)(TextDev &, const float4 *posv, const int *meta, int n, int obj, int *slot, float *xyz);   // one object's particles, order kept
+    // diffuse particles (sph_foam.hpp)
+    void (*foam_compact)(FoamDev &, const float4 *posv, const float4 *velm, const int *pid, const int *meta, int n_all, int *flag);   // active fluid -> xin / vin / idin in the handle's order, flag[n_all] = n
+    void (*foam_grid)(FoamDev &);               // hash + count, scan, scatter, id order inside each cell
+    void (*foam_advect)(FoamDev &);             // the diffuse particles' walk, classes, survivors compacted into the other bank
+    void (*foam_normals)(FoamDev &);
+    void (*foam_potentials)(FoamDev &);         // ta, wc, e, n_d and the child counts
+    void (*foam_generate)(FoamDev &);           // scan of the counts, children behind the survivors, the step's counters
+    void (*foam_render_source)(const FoamDev &, int n, int *id, unsigned *col, const unsigned rgb[3]);   // renderer ids and class colours of the diffuse set
     void (*layer_hist)(State &, int *hist);      // owned particles per global cell layer
     void (*loop_criterion)(State &, int slot);   // stop test on an all-reduced residual (sharded solver loops)
     // push transport: the step message is written by halo_classify_pack itself; then

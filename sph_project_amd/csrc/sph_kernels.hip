@@ -496,6 +496,7 @@ void l_clear_fresh(State &s) {
 #include "sph_video.hpp"
 #include "sph_png.hpp"
 #include "sph_text_passes.hpp"
+#include "sph_foam.hpp"
 #include "sph_halo_impl.hpp"
 }  // namespace SPH_NS
 
@@ -533,6 +534,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_video_launchers(L);
         register_png_launchers(L);
         register_text_launchers(L);
+        register_foam_launchers(L);
         L.halo_classify_pack = l_halo_classify_pack; L.halo_unpack_append = l_halo_unpack_append;
         L.halo_build_tables = l_halo_build_tables; L.halo_pack_fields = l_halo_pack_fields;
         L.halo_unpack_fields = l_halo_unpack_fields;

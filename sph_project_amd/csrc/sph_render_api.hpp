@@ -8,7 +8,9 @@
 // and an incoming layer; RB_S*: the planes of the surface mode, RB_T*: those of its thickness mode
 // (DESIGN.md 25), each allocated when the mode is first used
 enum RendBufId { RB_KEY, RB_RGB, RB_IDS, RB_CNT, RB_LARGE, RB_POS, RB_IDV, RB_COL, RB_MVERT, RB_MNRM, RB_MTRI, RB_MREC, RB_LKEY, RB_LRGB, RB_SBASE, RB_SQ0, RB_SQ1, RB_SCNT, RB_SMASK,
-                 RB_TOKEY, RB_TORGB, RB_TOCNT, RB_TOLARGE, RB_TT0, RB_TT1, RB_TCNT, RB_COUNT_ };
+                 RB_TOKEY, RB_TORGB, RB_TOCNT, RB_TOLARGE, RB_TT0, RB_TT1, RB_TCNT,
+                 RB_FID, RB_FCOL, RB_FCNT,   // ids, colours and counters of the diffuse particles' layer
+                 RB_COUNT_ };
 
 // what the renderer holds.  RF_ON_RANK0: the last frame was composited over a communicator and lies on rank 0, not here; RF_MESH: a mesh
 // frame has no layer (triangle indices do not compose)
@@ -46,7 +48,12 @@ struct SphRender : DevObj {   // clk[0]: a particle frame's stages, clk[1]: a me
     RenderThickDev td{};
     StageClock tclk;
     SphRenderThicknessStats tstats{};
+    // diffuse particles (sph_render_set_foam in sph_foam_api.hpp): drawn by sph_render_handle while set
+    struct SphFoam *foam = nullptr;
+    double foam_scale = 0.5;
+    unsigned foam_rgb[3] = {0, 0, 0};   // spray, foam, bubble
 };
+static int rend_draw_foam(SphRender *r);
 
 static bool rend_finite3(const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 static double rend_dot(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -472,6 +479,10 @@ extern "C" int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mas
         return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_handle: the handle's library frame is a permutation of the scene's (SPH_SLAB_LAYOUT=slow): not rendered");
     if (h->device != r->device) return fail(r, SPH_ERR_INVALID, "sph_render_handle: handle on device %d, renderer on %d", h->device, r->device);
     if (h->in_step) return fail(r, SPH_ERR_INVALID, "sph_render_handle: between sph_step_begin and sph_step_end");
+    if (r->foam && (r->surf_on || h->st.slab_active))
+        return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_handle: diffuse particles are set (sph_render_set_foam): no surface mode, no sharded handle");
+    if (r->foam && (int64_t)h->st.cap > (int64_t)INT_MAX)
+        return fail(r, SPH_ERR_INVALID, "sph_render_handle: particle ids reach 2^31, diffuse ids could not be told from them");
     HIPCHK(r, hipSetDevice(r->device));
     r->frame = RF_NONE;
     r->stats = SphRenderStats{};
@@ -492,7 +503,9 @@ extern "C" int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mas
     { int rc = rend_room(r, (size_t)n, false); if (rc) return rc; }
     HIPCHK(r, r->clk[0].mark(0));
     d.n = n; d.pos = s.posv.cur(); d.meta = s.meta.cur(); d.id = s.pid.cur(); d.mask = object_mask;
-    { int rc = rend_run(r, n); if (rc || !sharded) return rc; }
+    { int rc = rend_run(r, n); if (rc) return rc; }
+    if (r->foam) return rend_draw_foam(r);
+    if (!sharded) return SPH_OK;
     return rend_composite(r, h);   // collective: every rank of the communicator is here with the same renderer parameters and mask
 }
 

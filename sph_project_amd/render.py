@@ -44,6 +44,7 @@ class FrameRenderer(L.NativeObject):
         self._mesh_starts = None    # first global triangle index of each mesh of the last mesh frame (and the total)
         self._surface = None        # SphRenderSurfaceParams of the surface mode, None: off
         self._thickness = None      # SphRenderThicknessParams of its thickness mode, None: off
+        self._foam = None           # (DiffuseParticles, radius_scale, three uint8[3] colours) drawn by from_container, None: off
 
     def _params(self, box):
         kw = dict(self._kw)
@@ -70,7 +71,39 @@ class FrameRenderer(L.NativeObject):
                 self._chk(self.lib.sph_render_set_surface(h, C.byref(self._surface)), "sph_render_set_surface", h)
             if self._thickness is not None:
                 self._chk(self.lib.sph_render_set_thickness(h, C.byref(self._thickness)), "sph_render_set_thickness", h)
+            if self._foam is not None:
+                self._set_foam(h)
         return h
+
+    def _set_foam(self, h):
+        if self._foam is None:
+            self._chk(self.lib.sph_render_set_foam(h, None, 0.5, None, None, None), "sph_render_set_foam", h)
+            return
+        diffuse, scale, cols = self._foam
+        self._chk(self.lib.sph_render_set_foam(h, diffuse.h, scale, *(c.ctypes.data for c in cols)), "sph_render_set_foam", h)
+
+    def set_foam(self, diffuse, radius_scale=0.5, colors=None):
+        """Draw the diffuse particles of `diffuse` (sph_project_amd.foam.DiffuseParticles) into every from_container
+        frame that follows: spheres of radius_scale x the renderer's radius, read on the device.  colors: three (r, g, b) for spray,
+        foam and bubbles (None: near-white).  In ids() they carry bit 31.  Not with the surface mode, not on a sharded container."""
+        cols = ((250, 250, 255), (255, 255, 255), (225, 235, 250)) if colors is None else colors
+        if len(cols) != 3:
+            raise ValueError("set_foam: colors are three (r, g, b): spray, foam, bubble")
+        old = self._foam
+        self._foam = (diffuse, float(radius_scale), [np.ascontiguousarray(c, dtype=np.uint8).reshape(3) for c in cols])
+        try:
+            self._native(self.box if self.box else None)   # (one native renderer at least: a bad parameter raises here)
+            for h in self._handles.values():
+                self._set_foam(h)
+        except Exception:
+            self._foam = old
+            raise
+
+    def clear_foam(self):
+        """from_container draws the fluid alone again."""
+        self._foam = None
+        for h in self._handles.values():
+            self._set_foam(h)
 
     def set_surface(self, iterations=3, sigma=1.5, range=2.0, rmax=12, spec=0.35, shininess=40.0, objects=None):
         """Switch the screen-space surface mode on for the frames drawn afterwards: from_points / from_container also fill

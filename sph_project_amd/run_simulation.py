@@ -153,12 +153,34 @@ def parse_args(argv=None):
                         help="format particle_object_{id}.ply (and with --reconstruct particle_object_{id}.obj) on the GPU from the device "
                              "state (DESIGN.md 23: the same bytes as the host writers, no position or mesh download); needs a scene with "
                              "exportPly and --gpus 1")
+    parser.add_argument("--foam", action="store_true",
+                        help="generate diffuse particles -- spray, foam and bubbles -- from the fluid on the GPU (DESIGN.md 26): "
+                             "{frame}/diffuse_particles.ply at every output frame, and with --render drawn into raw_view.png; the "
+                             "fluid is not affected.  Parameters: the scene's optional Configuration.foam dict")
+    parser.add_argument("--foam_every", type=int, default=None,
+                        help="simulation steps per diffuse-particle step, default 4 (its dt is that many time steps)")
+    parser.add_argument("--foam_max", type=int, default=None,
+                        help="capacity of the diffuse set, default twice the scene's particle capacity")
     parser.add_argument("--gpus", type=int, default=1,
                         help="shard the scene over this many ranks, one process and (unless SPH_COMM_TRANSPORT names a shared-memory "
                              "transport) one GPU each; frames are composited on rank 0 (DESIGN.md 22)")
     args = parser.parse_args(argv)
     if args.gpus < 1:
         parser.error(f"--gpus {args.gpus}: at least one rank is needed")
+    for flag in ("foam_every", "foam_max"):
+        if getattr(args, flag) is not None and not args.foam:
+            parser.error(f"--{flag} sets a parameter of the diffuse particles: give --foam as well")
+    if args.foam:
+        if args.gpus > 1:
+            parser.error(f"--gpus {args.gpus}: --foam reads the whole fluid on one device (sharded scenes are not supported); run it "
+                         "with --gpus 1")
+        if args.render_surface:
+            parser.error("--foam draws the diffuse particles into particle frames only: not with --render_surface (DESIGN.md 26)")
+        if args.foam_every is not None and args.foam_every < 1:
+            parser.error(f"--foam_every {args.foam_every}: at least one simulation step per diffuse-particle step")
+        if args.foam_max is not None and args.foam_max < 1:
+            parser.error(f"--foam_max {args.foam_max}: room for at least one diffuse particle")
+    args.foam_every = args.foam_every or 4
     if args.export_device:
         if args.gpus > 1:
             parser.error(f"--gpus {args.gpus}: --export_device formats one device's particles (a sharded scene writes each rank's part "
@@ -307,6 +329,39 @@ def report(cnt, particles, t0, t_export, frames):
     dt = time.perf_counter() - t0
     print(f"Simulation Finished: {cnt} steps, {particles}, {1e3 * (dt - t_export) / cnt:.3f} ms/step "
           f"(+ {t_export:.2f} s writing {frames} frame(s): {1e3 * dt / cnt:.3f} ms/step all in)")
+
+
+class FoamStepper:
+    """The solver as run_loop drives it, with one diffuse-particle step of every * dt behind every `every` simulation steps: the steps
+    of one advance() go to the device in pieces that end where a diffuse step is due."""
+
+    def __init__(self, solver, container, diffuse, every, dt):
+        self.solver, self.container, self.diffuse, self.every, self.dt = solver, container, diffuse, every, dt
+        self.since = 0
+
+    def advance(self, n):
+        while n > 0:
+            k = min(n, self.every - self.since)
+            self.solver.advance(k)
+            n -= k
+            self.since += k
+            if self.since == self.every:
+                self.diffuse.step(self.container, self.every * self.dt)
+                self.since = 0
+
+
+def make_foam(container, solver, config, args):
+    """The diffuse set of --foam: the scene's domain, radius and gravity, Configuration.foam over the defaults (keys that are no
+    parameter are ignored, as the reference ignores keys), --foam_max or twice the particle capacity."""
+    from sph_project_amd.foam import DEFAULTS, DiffuseParticles
+    given = config.get_cfg("foam") or {}
+    params = {k: v for k, v in given.items() if k in DEFAULTS and k not in ("device", "max_diffuse")}
+    params["max_diffuse"] = args.foam_max or 2 * int(container.particle_max_num)
+    params.setdefault("padding", float(container.padding))
+    lo = np.zeros(3)
+    lo[:len(container.domain_start)] = container.domain_start
+    hi = np.asarray(container.domain_end, dtype=np.float64)
+    return DiffuseParticles(container.dx, lo, hi, gravity=[float(g) for g in solver.g], **params)
 
 
 def make_renderer(container, args, **kw):
@@ -459,6 +514,14 @@ def main(argv=None):
         mesh_renderer = make_renderer(container, args, box=(np.zeros(3), np.asarray(container.domain_end, dtype=np.float64)))
         meshes_out = ImageOutput("render.png", "render.avi", mesh_renderer, args, out_dir)
 
+    diffuse = None   # --foam: a second particle set that reads the fluid and never writes it
+    stepped = solver
+    if args.foam:
+        diffuse = make_foam(container, solver, config, args)
+        stepped = FoamStepper(solver, container, diffuse, args.foam_every, float(solver.dt[None]))
+        if raw is not None:
+            renderer.set_foam(diffuse)
+
     exporter = None   # --export_device: the text files come from the device state
     if args.export_device:
         from sph_project_amd.text import TextExporter
@@ -474,6 +537,9 @@ def main(argv=None):
             if raw is None:
                 renderer.from_container(container, download=False)
             surface.store(frame_dir(out_dir, cnt), lambda dl: renderer.surface(download=dl))
+            wrote = True
+        if diffuse is not None:   # key order; a header and no vertex while there is none
+            write_ply_ascii(f"{frame_dir(out_dir, cnt)}/diffuse_particles.ply", diffuse.download()["x"])
             wrote = True
         if sched.output_ply:
             d = frame_dir(out_dir, cnt)
@@ -507,9 +573,13 @@ def main(argv=None):
 
     outputs = [o for o in (raw, surface, meshes_out) if o is not None]
     t0 = time.perf_counter()
-    cnt, t_export, frames = run_loop(solver, container.engine, sched, sched.output_ply or sched.output_obj or outputs, write_frame,
-                                     [o.avi for o in outputs if o.avi is not None])
+    cnt, t_export, frames = run_loop(stepped, container.engine, sched, sched.output_ply or sched.output_obj or outputs or diffuse is not None,
+                                     write_frame, [o.avi for o in outputs if o.avi is not None])
     report(cnt, f"{container.particle_num[None]} particles", t0, t_export, frames)
+    if diffuse is not None:
+        st = diffuse.stats()
+        print(f"Diffuse particles: {st['diffuse']} after {st['step']} steps ({st['born_total']} born, {st['died_total']} died, "
+              f"{st['dropped_total']} dropped)")
     return container, solver
 
 
