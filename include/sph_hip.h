@@ -47,7 +47,11 @@ typedef enum {
    Two deviations: fix_position is Jacobi (all deltas from the positions at the start of the pass, then applied: the reference's
    in-place update is a data race in parallel), and the PBF fields are sized particle_max_num (the reference sizes them with a
    particle_num that is still 0).  Under PBF, objects with a later entryTime are never inserted and rigid bodies never move (PBF.py's
-   _step calls neither).  sph_prepare refuses (SPH_ERR_UNSUPPORTED) a sharded handle and viscosity_implicit. */
+   _step calls neither).  sph_prepare refuses (SPH_ERR_UNSUPPORTED) a sharded handle and viscosity_implicit.
+   That is the "reference" variant, the default.  sph_set_pbf_variant selects the "consistent" one instead: the
+   project's cubic spline in every sum, a density with its self term, the one-sided constraint C = max(rho / rho0 - 1, 0), lambda =
+   -C / (sum |G|^2 + |sum G|^2 + eps), a Jacobi correction of predicted positions x* with the neighbour set fixed at the step's
+   sort, and a stop test on the mean C.  The method id stays SPH_METHOD_PBF; what the reference variant refuses, this one refuses. */
 typedef enum { SPH_METHOD_WCSPH = 0, SPH_METHOD_DFSPH = 1, SPH_METHOD_PCISPH = 2, SPH_METHOD_IISPH = 3, SPH_METHOD_PBF = 4 } SphMethod;
 
 /* Scene / solver constants.  Mirrors what BaseContainer.__init__ (base_container.py:10-60)
@@ -102,7 +106,7 @@ typedef enum {
     SPH_F_DENSITY_DERIV = 17,/* f32[n] */
     SPH_F_PRESSURE_ACCEL = 18,   /* f32[n][3] pcisph particle_pressure_accelerations */
     SPH_F_PREDICTED_VEL = 19,    /* f32[n][3] */
-    SPH_F_PREDICTED_POS = 20,    /* f32[n][3] */
+    SPH_F_PREDICTED_POS = 20,    /* f32[n][3] (PCISPH; on a consistent-PBF handle: x*, download and upload) */
     SPH_F_CG_X = 21,             /* f32[n][3] base_solver.py:46 */
     SPH_F_ORIG_POSITION = 22,    /* f32[n][3] rigid_particle_original_positions */
     SPH_F_GHOST = 23,            /* i32[n]    1 for ghost copies of a neighbour slab's particles (multi-GPU), else 0 */
@@ -120,7 +124,9 @@ typedef enum {
     SPH_F_IISPH_SUM_I = 30,        /* f32[n]    sum_i  (IISPH.py:148 compute_sum_i, last executed iteration) */
     /* PBF (pbf_container.py:11-13; allocated for SPH_METHOD_PBF only, particle_max_num): */
     SPH_F_PBF_OLD_POSITION = 31,   /* f32[n][3] particle_old_positions (PBF.py:145 save_old_position: the positions at the step's sort) */
-    SPH_F_PBF_LAMBDA = 32,         /* f32[n]    particle_pbf_lambdas (PBF.py:68 compute_lambda, last executed iteration) */
+    SPH_F_PBF_LAMBDA = 32,         /* f32[n]    particle_pbf_lambdas (PBF.py:68 compute_lambda, last executed iteration; a consistent-PBF
+                                                handle also takes it in sph_upload, and refuses SPH_F_PBF_OLD_POSITION: SPH_F_POSITION
+                                                holds the old positions for the whole step) */
     /* rigid contact (allocated by sph_set_rigid_contact; written for contact targets only, zeroed by SPH_PH_RIGID_CONTACT): */
     SPH_F_RIGID_CONTACT_DN = 33,   /* f32[n][3] sum of depth * n over the target's contacts in the last contact pass */
     SPH_F_RIGID_CONTACT_COUNT = 34,/* f32[n]    the number of those contacts (partner particles + wall planes) */
@@ -146,6 +152,11 @@ typedef enum {
     SPH_PH_PBF_FINISH = 13,         /* PBF.py:156-158 enforce_domain_boundary + recompute_fluid_velocity */
     SPH_PH_RIGID_CONTACT = 14,      /* the rigid contact pass (sph_set_rigid_contact) on the current positions and the last sort's cells;
                                        the per-particle contact fields are zeroed first; the table accumulates as in a step */
+    /* consistent PBF variant (sph_set_pbf_variant), on the masks and cell lists of the last sort: */
+    SPH_PH_PBFC_PREDICT = 15,        /* x* = x + dt v + boundary (SPH_F_PREDICTED_POS); SPH_F_POSITION stays */
+    SPH_PH_PBFC_DENSITY_LAMBDA = 16, /* walk A: rho, lambda at x*; SphPbfStats::error = mean C of this walk, iterations = 1 */
+    SPH_PH_PBFC_DELTA = 17,          /* walk B: the Jacobi correction of x* */
+    SPH_PH_PBFC_FINISH = 18,         /* x = boundary(x*), v = (x - x_old) / dt, emitter branch */
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -187,7 +198,9 @@ typedef enum {
     SPH_K_HALO = 17, SPH_K_WCSPH_FORCES = 18,
     SPH_K_IISPH_PREPARE = 19, SPH_K_IISPH_DIJ_PJ = 20, SPH_K_IISPH_SUM_I = 21,
     SPH_K_PBF_DENSITY_LAMBDA = 22, SPH_K_PBF_FIX_POSITION = 23, SPH_K_PBF_UPDATE = 24,
-    SPH_K_RIGID_CONTACT = 25, SPH_K_RIGID_INTEGRATE = 26, SPH_K_RIGID_CONTACT_SOLVE = 27, SPH_K_COUNT_
+    SPH_K_RIGID_CONTACT = 25, SPH_K_RIGID_INTEGRATE = 26, SPH_K_RIGID_CONTACT_SOLVE = 27,
+    SPH_K_PBFC_DENSITY_LAMBDA = 28, SPH_K_PBFC_DELTA = 29,   /* consistent PBF: walk A, walk B (predict / finish: SPH_K_PBF_UPDATE) */
+    SPH_K_COUNT_
 } SphKernelId;
 
 /* --- lifetime -------------------------------------------------------------------------- */
@@ -245,6 +258,21 @@ int sph_get_rigid_contacts(SphHandle *h, double *table, int reset);
 /* accepted contacts (partner particles + wall planes) of the last contact pass on this handle (this rank's targets).  A query of its
    own rather than a SphStats field: the statistics struct ends at pbf_recentred by contract. */
 int sph_get_rigid_contact_pairs(SphHandle *h, int64_t *pairs);
+
+/* PBF variant.  variant 0 = reference (PBF.py as written, the default), 1 = consistent.  For the consistent variant:
+   the solve runs at least min_iterations (>= 1) and at most max_iterations (>= min_iterations) iterations and stops after the first
+   one whose mean constraint error sum_i C_i / fluid_particle_num is <= max_error (> 0, finite); epsilon (> 0, finite) is the
+   relaxation term of lambda's denominator.  SphParams::fixed_iterations > 0 runs exactly that many and reports error 0.
+   Legal between sph_create and sph_prepare only.  SPH_ERR_UNSUPPORTED: not a PBF handle.  SPH_ERR_INVALID: after sph_prepare, or a
+   bad field (the message names it).  sph_step_async on a consistent handle needs fixed_iterations > 0: the stop test reads back. */
+typedef struct { int32_t variant, min_iterations, max_iterations; float max_error, epsilon; } SphPbfParams;
+#define SPH_PBF_VARIANT_REFERENCE 0
+#define SPH_PBF_VARIANT_CONSISTENT 1
+int sph_set_pbf_variant(SphHandle *h, const SphPbfParams *params);
+/* the variant of a PBF handle, the iterations of its last step's solve and that solve's last mean constraint error (reference variant:
+   its fixed 5, and 0).  A query of its own: the statistics struct ends at pbf_recentred by contract. */
+typedef struct { int32_t variant, iterations; float error; } SphPbfStats;
+int sph_get_pbf_stats(SphHandle *h, SphPbfStats *out);
 
 /* Device rigid integrator (opt-in; the host's "device" rigid backend).  The physics of the host's native backend
    (SPH/rigid_solver/host_rigid_solver.py integrate: semi-implicit Euler in float64 under gravity and the fluid wrench, gyroscopic

@@ -16,7 +16,12 @@ class PBFSolver(BaseSolver):
         The reference updates particle_positions[p_i] in place while other iterations of the same parallel loop read it
         (a data race on a GPU; Gauss-Seidel in index order on a serial interpreter).
       * the PBF fields are sized particle_max_num (the reference sizes them with a particle_num that is still 0).
-    Single GPU only: a sharded container fails in prepare(), and so does viscosityMethod "implicit"."""
+    Single GPU only: a sharded container fails in prepare(), and so does viscosityMethod "implicit".
+
+    With Configuration.pbfVariant "consistent" the step is the one of DESIGN.md 27 instead: the cubic spline in every sum, the
+    one-sided density constraint, a Jacobi correction of predicted positions on the neighbour set of the step's sort, and a stop
+    test on the mean constraint error (`iterations`, `density_error` report the last step's).  It moves no rigid body and inserts
+    no object either, and refuses what the reference variant refuses."""
 
     def __init__(self, container: PBFContainer):
         super().__init__(container)
@@ -37,13 +42,38 @@ class PBFSolver(BaseSolver):
     def corr_deltaQ_coeff(self):
         return self._corr_deltaQ_coeff
 
+    @property
+    def variant(self):
+        """"reference" (PBF.py as written) or "consistent" (DESIGN.md 27)."""
+        return self.container.pbf_variant
+
+    @property
+    def iterations(self):
+        """Iterations of the last step's solve (reference variant: the fixed five)."""
+        return self.engine.pbf_stats()["iterations"]
+
+    @property
+    def density_error(self):
+        """Mean constraint error sum C_i / fluid_particle_num of the last step's last iteration (0 under the reference variant and
+        with a fixed iteration count)."""
+        return self.engine.pbf_stats()["error"]
+
+    def predict_position(self):
+        """x* = x + dt v + boundary (PH_PBF_PREDICT; consistent variant: into particle_predicted_positions)."""
+        self.engine.run_phase(F.PH_PBFC_PREDICT if self.variant == "consistent" else F.PH_PBF_PREDICT)
+
     def compute_density_and_lambda(self):
-        """compute_density + compute_lambda (PBF.py:64-65) on the current positions and the last sort's cell lists."""
-        self.engine.run_phase(F.PH_PBF_DENSITY_LAMBDA)
+        """compute_density + compute_lambda (PBF.py:64-65) on the current positions and the last sort's cell lists; consistent
+        variant: walk A at the predicted positions, on the neighbour set of the last sort."""
+        self.engine.run_phase(F.PH_PBFC_DENSITY_LAMBDA if self.variant == "consistent" else F.PH_PBF_DENSITY_LAMBDA)
 
     def fix_position(self):
-        """fix_position (PBF.py:104), Jacobi, on the same."""
-        self.engine.run_phase(F.PH_PBF_FIX_POSITION)
+        """fix_position (PBF.py:104), Jacobi, on the same; consistent variant: walk B, the correction of the predicted positions."""
+        self.engine.run_phase(F.PH_PBFC_DELTA if self.variant == "consistent" else F.PH_PBF_FIX_POSITION)
+
+    def finish_position(self):
+        """Boundary + v = (x - x_old) / dt (PH_PBF_FINISH; consistent variant: from the predicted positions)."""
+        self.engine.run_phase(F.PH_PBFC_FINISH if self.variant == "consistent" else F.PH_PBF_FINISH)
 
     def _host_acts_inside_a_step(self):
         """Nothing: PBF.py's _step integrates no rigid body and inserts no object."""

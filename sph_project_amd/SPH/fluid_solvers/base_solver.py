@@ -100,11 +100,13 @@ class BaseSolver:
         return (bool(self.rigid_solver.bodies) and not self._bodies_on_device()) or self.container.objects_pending()
 
     def _device_steps(self, n):
-        """n whole steps on the device.  WCSPH, PBF (and solvers with a fixed iteration count) need nothing back from the device:
+        """n whole steps on the device.  WCSPH, reference-variant PBF (and solvers with a fixed iteration count) need nothing back from the device:
         the steps are only enqueued -- like a Taichi kernel launch, observable behaviour stays synchronous because every
         read of a field / of stats() drains the stream first.  Solver loops with their own stop tests read a flag back per
         batch of iterations anyway."""
-        asynchronous = self.container.METHOD in ("wcsph", "pbf") or self.container.params_dict.get("fixed_iterations", 0) > 0
+        free_running = self.container.METHOD == "wcsph" or (self.container.METHOD == "pbf" and   # (the consistent PBF variant has a stop test)
+                                                            getattr(self.container, "pbf_variant", "reference") == "reference")
+        asynchronous = free_running or self.container.params_dict.get("fixed_iterations", 0) > 0
         if asynchronous and os.environ.get("SPH_SYNC_STEPS", "0") not in ("", "0"):
             asynchronous = False   # opt-out: every step() returns only when the device is done, errors surface in the call that caused them
         if asynchronous:

@@ -44,6 +44,8 @@ _FIELD_SPEC = {  # field -> (dtype, components)
 (PH_NEIGHBOR_SEARCH, PH_RIGID_VOLUME, PH_DENSITY, PH_NON_PRESSURE, PH_PRESSURE_INTEGRATE, PH_DFSPH_ALPHA,
  PH_DFSPH_DIVERGENCE, PH_DFSPH_DENSITY, PH_IISPH_PREPARE, PH_IISPH_ITERATION, PH_PBF_DENSITY_LAMBDA,
  PH_PBF_FIX_POSITION, PH_PBF_PREDICT, PH_PBF_FINISH, PH_RIGID_CONTACT) = range(15)
+# the consistent PBF variant (sph_set_pbf_variant)
+PH_PBFC_PREDICT, PH_PBFC_DENSITY_LAMBDA, PH_PBFC_DELTA, PH_PBFC_FINISH = 15, 16, 17, 18
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
@@ -54,6 +56,8 @@ KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "press
 K_RIGID_CONTACT = 25   # sph_kernel_name(25) == "rigid_contact" (KERNEL_IDS keeps its PBF tail)
 K_RIGID_INTEGRATE = 26   # sph_kernel_name(26) == "rigid_integrate": the device rigid backend's launch
 K_RIGID_CONTACT_SOLVE = 27   # sph_kernel_name(27) == "rigid_contact_solve": the device_contact rigid backend's launch
+K_PBFC_DENSITY_LAMBDA = 28   # sph_kernel_name(28) == "pbfc_density_lambda": walk A of the consistent PBF variant
+K_PBFC_DELTA = 29            # sph_kernel_name(29) == "pbfc_delta": its walk B
 
 # rigid contact table (sph_get_rigid_contacts): [object A][partner B][normal bin][value]; partners 20..25 are the domain box /
 # the wall planes, one per bin; values: pairs, midpoint sum (3), depth * n sum (3), maximum depth
@@ -85,6 +89,18 @@ class SphStats(C.Structure):
         ("hash_launches", C.c_int64), ("prehashed_sorts", C.c_int64), ("list_sorts", C.c_int64),
         ("carried_sorts", C.c_int64), ("iter_iisph", C.c_int32), ("err_iisph", C.c_float), ("pbf_recentred", C.c_int64),
     ]
+
+
+PBF_VARIANTS = {"reference": 0, "consistent": 1}
+
+
+class SphPbfParams(C.Structure):
+    _fields_ = [("variant", C.c_int32), ("min_iterations", C.c_int32), ("max_iterations", C.c_int32), ("max_error", C.c_float),
+                ("epsilon", C.c_float)]
+
+
+class SphPbfStats(C.Structure):
+    _fields_ = [("variant", C.c_int32), ("iterations", C.c_int32), ("error", C.c_float)]
 
 
 class SphSurfaceParams(C.Structure):
@@ -289,6 +305,8 @@ _SIGNATURES = [
     ("sph_set_rigid_contact", C.c_int, [_VP, C.c_int, C.c_float, _VP, _VP]),
     ("sph_get_rigid_contacts", C.c_int, [_VP, _VP, C.c_int]),
     ("sph_get_rigid_contact_pairs", C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    ("sph_set_pbf_variant", C.c_int, [_VP, C.POINTER(SphPbfParams)]),
+    ("sph_get_pbf_stats", C.c_int, [_VP, C.POINTER(SphPbfStats)]),
     # device rigid integrator; what each stands in for in the reference's SPH/rigid_solver/bullet_solver.py:
     ("sph_set_rigid_integrator", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),                        # :19-71 __init__ (gravity, dt, walls)
     ("sph_set_rigid_body", C.c_int, [_VP, C.c_int, C.c_double] + [_VP] * 7 + [C.c_int]),        # :75-131 insert_rigid_object
@@ -583,6 +601,17 @@ class Engine(NativeObject):
         n = C.c_int64(0)
         self._chk(self.lib.sph_get_rigid_contact_pairs(self.h, C.byref(n)), "sph_get_rigid_contact_pairs")
         return n.value
+
+    # -- PBF variant
+    def set_pbf_variant(self, variant="consistent", min_iterations=1, max_iterations=50, max_error=1e-3, epsilon=1e-6):
+        """variant: "reference" / "consistent" (or 0 / 1); between create and prepare only."""
+        p = SphPbfParams(int(PBF_VARIANTS.get(variant, variant)), int(min_iterations), int(max_iterations), float(max_error), float(epsilon))
+        self._chk(self.lib.sph_set_pbf_variant(self.h, C.byref(p)), "sph_set_pbf_variant")
+
+    def pbf_stats(self):
+        st = SphPbfStats()
+        self._chk(self.lib.sph_get_pbf_stats(self.h, C.byref(st)), "sph_get_pbf_stats")
+        return struct_dict(st)
 
     # -- device rigid integrator (the "device" rigid backend)
     def set_rigid_integrator(self, on=True, gravity=(0.0, 0.0, 0.0), wall_lo=(0.0, 0.0, 0.0), wall_hi=(0.0, 0.0, 0.0)):

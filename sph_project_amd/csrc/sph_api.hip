@@ -40,6 +40,8 @@ struct SphHandle : ErrSink {
     bool any_rigid_object = false;   // a non-fluid object was registered (slab sharding: its particles may live on another rank)
     int64_t steps = 0;
     int pbf_bank = 0;              // PBF: statistics bank of State::pbf_recentred the last step / phase counted into
+    SphPbfParams pbf = {SPH_PBF_VARIANT_REFERENCE, 1, 50, 1e-3f, 1e-6f};   // sph_set_pbf_variant (the defaults of the scene keys)
+    SphPbfStats pbf_last = {SPH_PBF_VARIANT_REFERENCE, 0, 0.0f};          // iterations / error of the last step's solve (sph_get_pbf_stats)
     int steps_to_follow = 0;       // sph_step_async(n): steps of this call still to come after the running one
     bool whole_step = false;       // both halves of the running step are ONE call (step_once): nothing on the host happens between them
     double total_time = 0.0;
@@ -211,7 +213,7 @@ extern "C" const char *sph_kernel_name(int k) {
         "dfsph_density_alpha", "dfsph_rho_adv", "dfsph_correct", "reduce", "pcisph_rho_star",
         "pcisph_pressure_accel", "cg_prepare", "cg_ap", "cg_vector", "misc", "halo", "wcsph_forces",
         "iisph_prepare", "iisph_dij_pj", "iisph_sum_i", "pbf_density_lambda", "pbf_fix_position", "pbf_update",
-        "rigid_contact", "rigid_integrate", "rigid_contact_solve"};
+        "rigid_contact", "rigid_integrate", "rigid_contact_solve", "pbfc_density_lambda", "pbfc_delta"};
     return (k >= 0 && k < SPH_K_COUNT_) ? names[k] : "?";
 }
 
@@ -533,6 +535,40 @@ extern "C" int sph_set_rigid_contact(SphHandle *h, int on, float distance, const
     }
     s.contact = a;
     s.contact_on = 1;
+    return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------- PBF variant
+extern "C" int sph_set_pbf_variant(SphHandle *h, const SphPbfParams *p) {
+    if (!h) return SPH_ERR_INVALID;
+    if (!p) return fail(h, SPH_ERR_INVALID, "sph_set_pbf_variant: null argument");
+    if (h->prm.method != SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_pbf_variant: not a PBF handle (method %d)", h->prm.method);
+    if (h->prepared) return fail(h, SPH_ERR_INVALID, "sph_set_pbf_variant: legal between sph_create and sph_prepare only");
+    if (p->variant != SPH_PBF_VARIANT_REFERENCE && p->variant != SPH_PBF_VARIANT_CONSISTENT)
+        return fail(h, SPH_ERR_INVALID, "sph_set_pbf_variant: variant %d is neither 0 (reference) nor 1 (consistent)", p->variant);
+    if (p->variant == SPH_PBF_VARIANT_CONSISTENT) {
+        if (p->min_iterations < 1) return fail(h, SPH_ERR_INVALID, "sph_set_pbf_variant: min_iterations %d < 1", p->min_iterations);
+        if (p->max_iterations < p->min_iterations)
+            return fail(h, SPH_ERR_INVALID, "sph_set_pbf_variant: max_iterations %d < min_iterations %d", p->max_iterations, p->min_iterations);
+        if (!(p->max_error > 0.0f) || !std::isfinite(p->max_error))
+            return fail(h, SPH_ERR_INVALID, "sph_set_pbf_variant: max_error %g is not a positive finite number", (double)p->max_error);
+        if (!(p->epsilon > 0.0f) || !std::isfinite(p->epsilon))
+            return fail(h, SPH_ERR_INVALID, "sph_set_pbf_variant: epsilon %g is not a positive finite number", (double)p->epsilon);
+        h->pbf = *p;
+        h->st.pbf_eps = p->epsilon;
+    } else {
+        h->pbf.variant = SPH_PBF_VARIANT_REFERENCE;   // (the other fields mean nothing to PBF.py's fixed five iterations)
+    }
+    h->st.poly6 = h->pbf.variant == SPH_PBF_VARIANT_REFERENCE ? 1 : 0;   // the cubic spline in the shared passes of the consistent variant
+    h->pbf_last.variant = h->pbf.variant;
+    return SPH_OK;
+}
+
+extern "C" int sph_get_pbf_stats(SphHandle *h, SphPbfStats *out) {
+    if (!h || !out) return SPH_ERR_INVALID;
+    if (h->prm.method != SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "sph_get_pbf_stats: not a PBF handle (method %d)", h->prm.method);
+    *out = h->pbf_last;
+    if (h->pbf.variant == SPH_PBF_VARIANT_REFERENCE) { out->iterations = h->steps > 0 ? SPH_PBF_ITERATIONS : 0; out->error = 0.0f; }
     return SPH_OK;
 }
 
@@ -997,7 +1033,8 @@ static int step_first_half(SphHandle *h) {
         case SPH_METHOD_WCSPH: rc = wcsph_step(h); break;                     // WCSPH.py:28-36 (:45 boundary fused into the position update)
         case SPH_METHOD_DFSPH: rc = dfsph_step_begin(h); break;
         case SPH_METHOD_IISPH: rc = iisph_step(h); break;                     // IISPH.py:204-220
-        case SPH_METHOD_PBF: rc = pbf_step(h); break;                         // PBF.py:145-158 (the whole _step: no rigid step, no insertion)
+        case SPH_METHOD_PBF:                                                  // PBF.py:145-158 (the whole _step: no rigid step, no insertion)
+            rc = h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT ? pbfc_step(h) : pbf_step(h); break;
         default: rc = pcisph_step(h); break;                                  // PCISPH.py:166-177
     }
     if (rc) return rc;
@@ -1082,6 +1119,8 @@ extern "C" int sph_step_async(SphHandle *h, int nsteps) {
     // the only check that keeps the pressure solves' stop tests (a read-back per batch) out of asynchronous steps
     if (h->prm.method != SPH_METHOD_WCSPH && h->prm.method != SPH_METHOD_PBF && h->prm.fixed_iterations <= 0)
         return fail(h, SPH_ERR_UNSUPPORTED, "sph_step_async needs wcsph, pbf or fixed_iterations > 0");
+    if (h->prm.method == SPH_METHOD_PBF && h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT && h->prm.fixed_iterations <= 0)
+        return fail(h, SPH_ERR_UNSUPPORTED, "sph_step_async: the consistent PBF variant needs fixed_iterations > 0 (its stop test reads back)");
     HIPCHK(h, hipSetDevice(h->device));
     refresh_counts(h);
     for (int k = 0; k < nsteps; ++k) {
@@ -1171,12 +1210,12 @@ static const float4 *vec_field(SphHandle *h, int field) {
         case SPH_F_ACCELERATION: return s.acc;
         case SPH_F_PRESSURE_ACCEL: return s.pacc;
         case SPH_F_PREDICTED_VEL: return s.pvel;
-        case SPH_F_PREDICTED_POS: return s.ppos;
+        case SPH_F_PREDICTED_POS: return h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT ? s.pbf_old : s.ppos;   // consistent PBF: x*
         case SPH_F_CG_X: return s.cg_x;
         case SPH_F_ORIG_POSITION: return s.orig.cur() ? s.orig.cur() : s.posv.cur();
         case SPH_F_IISPH_DII: case SPH_F_IISPH_AII: return s.iisph_dii;     // (dii, aii)
         case SPH_F_IISPH_DIJ_PJ: case SPH_F_IISPH_SUM_I: return s.iisph_dij; // (dij_pj, sum_i)
-        case SPH_F_PBF_OLD_POSITION: return s.pbf_old;                       // (x_old, sorted cell id)
+        case SPH_F_PBF_OLD_POSITION: return h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT ? nullptr : s.pbf_old;   // (x_old, sorted cell id); consistent variant: posv is the old position
         case SPH_F_RIGID_CONTACT_DN: case SPH_F_RIGID_CONTACT_COUNT: return s.contact_part;   // (sum of depth * n, contacts)
         default: return nullptr;
     }
@@ -1296,6 +1335,7 @@ extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes
         case SPH_F_REST_VOLUME: vdst = s.posv.cur(); w_only = true; break;
         case SPH_F_MASS: vdst = s.velm.cur(); w_only = true; h->fluid_mass_uniform = false; refresh_counts(h); break;
         case SPH_F_CG_X: vdst = s.cg_x; break;
+        case SPH_F_PREDICTED_POS: if (h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT) vdst = s.pbf_old; break;   // x* (the phase tests)
         default: break;
     }
     if (vdst) {
@@ -1322,6 +1362,7 @@ extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes
     switch (field) {
         case SPH_F_DENSITY: fdst = s.rho.cur(); break;
         case SPH_F_PRESSURE: fdst = s.prs; break;
+        case SPH_F_PBF_LAMBDA: if (h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT) fdst = s.pbf_lambda; break;
         default: break;
     }
     if (fdst) {

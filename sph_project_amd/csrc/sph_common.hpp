@@ -507,6 +507,8 @@ struct State {
     // buffer of the Jacobi fix_position (swapped with posv.cur() behind every pass), recentred walks per statistics bank
     float4 *pbf_old = nullptr, *pbf_pos = nullptr; float *pbf_lambda = nullptr; unsigned long long *pbf_recentred = nullptr;
     int poly6 = 0;       // the shared passes (NonPressurePass, RigidVolumePass) use PBF.py's poly6 / spiky kernels
+    // consistent PBF variant (sph_pbf_consistent.hpp): pbf_old / pbf_pos hold x* and the correction pass's second x* buffer, posv the old positions
+    float pbf_eps = 1e-6f;   // SphPbfParams::epsilon, the relaxation term of lambda's denominator
     // rigid contact (sph_set_rigid_contact; allocated when first enabled): the per-key table (64-bit fixed point, sph_contact.hpp),
     // the per-particle (sum of depth * n, contacts) of the targets, the accepted contacts of the last pass
     int contact_on = 0;
@@ -673,6 +675,11 @@ struct Launch {
     void (*pbf_density_lambda)(State &);        // compute_density + compute_lambda, one walk (PBF.py:64-65)
     void (*pbf_fix_position)(State &);          // fix_position, Jacobi (PBF.py:66, :104)
     void (*pbf_finish)(State &);                // boundary + recompute_fluid_velocity (PBF.py:156-158)
+    // consistent PBF variant
+    void (*pbfc_predict)(State &);              // x* = x + dt v* + boundary
+    void (*pbfc_density_lambda)(State &, int reduce);   // walk A: rho, lambda, partial sums of C (reduce: summed at once, for a lone phase)
+    void (*pbfc_delta)(State &, int reduce);    // walk B: the Jacobi correction of x* (+ the reduction that closes the iteration)
+    void (*pbfc_finish)(State &);               // x = boundary(x*), v = (x - x_old) / dt, emitter branch
     // rigid contact: one walk over the dynamic rigid particles, per-key table + per-particle sums (sph_contact.hpp)
     void (*rigid_contact)(State &);
     // device rigid integrator: one workgroup per registered body (sph_rigid.hpp)

@@ -485,6 +485,7 @@ void l_clear_fresh(State &s) {
 
 #include "sph_solvers_impl.hpp"
 #include "sph_pbf.hpp"
+#include "sph_pbf_consistent.hpp"
 #include "sph_contact.hpp"
 #include "sph_rigid.hpp"
 #include "sph_contact_solve.hpp"
@@ -522,6 +523,7 @@ const Launch *SPH_LAUNCH_FN() {
         L.clear_fresh = l_clear_fresh;
         register_solver_launchers(L);
         register_pbf_launchers(L);
+        register_pbfc_launchers(L);
         register_contact_launchers(L);
         register_rigid_launchers(L);
         register_contact_solve_launchers(L);

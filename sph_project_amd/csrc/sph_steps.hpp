@@ -409,6 +409,51 @@ static int pbf_step(SphHandle *h) {
     return SPH_OK;
 }
 
+// The consistent PBF variant, one iteration: walk A (rho, lambda, partial sums of C), walk B (the Jacobi correction of
+// x*) and, with `reduce`, the reduction of A's sums behind B -- inside a device-controlled loop that is where the stop test runs, so
+// the iteration that meets it still applies its correction.
+static void pbfc_iteration(SphHandle *h, int reduce) {
+    State &s = h->st;
+    { ProfScope p(h, SPH_K_PBFC_DENSITY_LAMBDA); h->L->pbfc_density_lambda(s, 0); }
+    { ProfScope p(h, SPH_K_PBFC_DELTA); h->L->pbfc_delta(s, reduce); }
+}
+
+// Stop after the first iteration k >= min_iterations with err_k = sum C / fluid_particle_num <= max_error (kind 1), or after
+// max_iterations.  The first min_iterations - 1 iterations carry no stop test: they go out in front of the loop.  Reduction slot 3
+// (the CG solve's elsewhere: PBF refuses implicit viscosity, so no other solve of a PBF handle uses it).
+static int pbfc_solve(SphHandle *h) {
+    State &s = h->st;
+    const int fixed = h->prm.fixed_iterations;
+    const int pre_n = fixed > 0 ? 0 : h->pbf.min_iterations - 1;
+    const SolveSpec sp{.slot = 3, .kind = 1, .thr = (double)h->pbf.max_error, .denom = (float)h->n_fluid,
+                       .max_itr = h->pbf.max_iterations - pre_n, .fixed_err = 0.0f,
+                       .iter = &h->pbf_last.iterations, .err = &h->pbf_last.error, .batch_end = nullptr};
+    int launched = 0;
+    int rc = run_solve(h, sp, [&] { for (int k = 0; k < pre_n; ++k) pbfc_iteration(h, 0); },
+                       [&]() -> int { pbfc_iteration(h, 1); return (int)SPH_OK; }, &launched);
+    if (rc) return rc;
+    if (fixed <= 0) {
+        if ((launched - h->pbf_last.iterations) & 1) std::swap(s.pbf_old, s.pbf_pos);   // iterations past the stop did not run: their swaps go back
+        h->pbf_last.iterations += pre_n;
+    }
+    return SPH_OK;
+}
+
+// One step: the sort, the rigid volumes, the density at the sorted positions (it stores the acceptance masks every later walk of the
+// step reuses, and is the density the viscosity reads), v* = v + dt a with the cubic kernel, x* = x + dt v*, the solve, the finish.
+// As under the reference variant: no rigid_solver.step(), no insert_object().
+static int pbfc_step(SphHandle *h) {
+    State &s = h->st;
+    const SortCarry carry = ph_neighbor_search(h, true, true);
+    ph_rigid_volume(h);
+    { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, 0, {0, false, carry}); }
+    int rc = run_non_pressure(h); if (rc) return rc;
+    { ProfScope p(h, SPH_K_PBF_UPDATE); h->L->pbfc_predict(s); }
+    rc = pbfc_solve(h); if (rc) return rc;
+    { ProfScope p(h, SPH_K_PBF_UPDATE); h->L->pbfc_finish(s); }
+    return SPH_OK;
+}
+
 // host replica of PCISPH.py:129 compute_pcisph_k (same arithmetic as oracle/sph_ref.c)
 static float host_pcisph_k(const SphParams &p) {
     const double hd = p.support_radius;
@@ -472,6 +517,20 @@ static int method_run_phase(SphHandle *h, int phase) {
                 h->last.iter_iisph = 1; h->last.err_iisph = h->n_fluid > 0 ? sum / denom : 0.0f;
                 return SPH_OK;
             }
+            default: break;
+        }
+    } else if (h->prm.method == SPH_METHOD_PBF && h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT) {
+        switch (phase) {
+            case SPH_PH_PBFC_PREDICT: { ProfScope p(h, SPH_K_PBF_UPDATE); h->L->pbfc_predict(s); } return SPH_OK;
+            case SPH_PH_PBFC_DENSITY_LAMBDA: {   // its mean C is read back
+                { ProfScope p(h, SPH_K_PBFC_DENSITY_LAMBDA); h->L->pbfc_density_lambda(s, 1); }
+                float sum = 0.0f;
+                int rc = read_red(h, 3, &sum); if (rc) return rc;
+                h->pbf_last.iterations = 1; h->pbf_last.error = h->n_fluid > 0 ? sum / (float)h->n_fluid : 0.0f;
+                return SPH_OK;
+            }
+            case SPH_PH_PBFC_DELTA: { ProfScope p(h, SPH_K_PBFC_DELTA); h->L->pbfc_delta(s, 0); } return SPH_OK;
+            case SPH_PH_PBFC_FINISH: { ProfScope p(h, SPH_K_PBF_UPDATE); h->L->pbfc_finish(s); } return SPH_OK;
             default: break;
         }
     } else if (h->prm.method == SPH_METHOD_PBF) {   // one refine walk on the current positions and the last sort's cell lists

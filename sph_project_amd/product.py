@@ -130,6 +130,15 @@ def pbf_scene(domain_end=(2.0, 1.6, 1.0), start=(0.1, 0.1, 0.1), end=(0.6, 1.0, 
     }
 
 
+def pbf_consistent_scene(domain_end=(2.0, 1.6, 1.0), start=(0.1, 0.1, 0.1), end=(0.6, 1.0, 0.9), add_domain_box=True, dt=4e-4, **pbf_keys):
+    """pbf_scene under the consistent variant (Configuration.pbfVariant "consistent"); pbf_keys: pbfMaxError,
+    pbfMinIterations, pbfMaxIterations, pbfEpsilon."""
+    cfg = pbf_scene(domain_end=domain_end, start=start, end=end, add_domain_box=add_domain_box, dt=dt)
+    cfg["Configuration"]["pbfVariant"] = "consistent"
+    cfg["Configuration"].update(pbf_keys)
+    return cfg
+
+
 def coupling_scene(method="dfsph", models_dir=None, fluid_end=(2.3, 1.4, 2.38)):
     """The reference's rigid-fluid coupling showcase data/scenes/final_scene1.json: its box, fluid block, dt and the placements of its
     nine dynamic bodies, with tests/golden/models/cube.obj in place of the dragon and sphere.obj in place of the rubber ducks (those
