@@ -1047,6 +1047,58 @@ int sph_foam_stats(SphFoam *f, SphFoamStats *out);
 int sph_render_set_foam(SphRender *r, SphFoam *foam_or_NULL, double radius_scale, const uint8_t *rgb_spray, const uint8_t *rgb_foam,
                         const uint8_t *rgb_bubble);
 
+/* --- Diffuse particles in the surface frames: white water over and under the surface ------------------------------- */
+/* opt-in on top of the surface mode, entered through these calls only.  While a foam object is set, sph_render_handle -- behind the
+   frame, the base plane and, thickness mode, the opaque layer and the thickness plane -- walks every diffuse sphere (radius rf =
+   radius_scale x the renderer's) over the pixel centres of its bounds with the chord [t0, t1] of the thickness splat (counted when
+   h >= 0 and t0 > z_near).  The limit L of a pixel is the frame's own depth t_w in the opaque surface mode and the opaque layer's depth
+   in thickness mode (absent where that key is all ones); c = (u32)((min(t1, L) - t0) * inv_u) when min(t1, L) > t0.  Thickness mode, on a
+   surface pixel with t0 >= t_w + depth_bias r: the pair is UNDER the surface -- fu += c, du = min(du, (u32)((t0 - t_w) * inv_u)) --
+   otherwise OVER it: fo += c.  Integer atomics only: the three u32 planes are functions of the particle sets.  With raw_spheres the
+   diffuse spheres are then also drawn into the particle frame as sph_render_set_foam draws them (its default class colours), after the
+   frame's key plane has been copied; the frame's rgb is copied in either case, so that a repeated sph_render_surface starts from it.
+   sph_render_surface then, behind its shade, with I(F) = 1 - exp2(-(density F / 256)) and f = rgb / 255, in f32 without contraction:
+     under (thickness mode, surface pixels with fu > 0, I(fu) != 0): Tm = max(T, 1), T1 = min(Tm, du) / 256, T2 = (Tm - min(Tm, du)) / 256,
+       k = absorb (1 - base) + scatter, a1 = exp2(-(k T1)), a2 = exp2(-(k T2)),
+       out = byte((lit (1 - a1) + a1 (f I(fu) + (1 - I(fu)) (lit (1 - a2) + a2 behind))) + highlight);
+     over (every pixel with fo > 0, I(fo) != 0): out = byte((cur / 255) (1 - I(fo)) + f I(fo)), cur the byte the pixel holds.
+   The points path ignores the mode.  Without it no launch, allocation or byte of any call changes. */
+typedef struct {
+    double radius_scale;      /* the diffuse sphere's radius in renderer radii, > 0 (0.5) */
+    double density;           /* per particle radius of diffuse chord, >= 0 (1.0) */
+    double depth_bias;        /* particle radii behind the surface depth from which a chord counts as under it, >= 0 (1.0) */
+    uint8_t rgb[3];           /* the white water's colour (255 255 255) */
+    uint8_t raw_spheres;      /* != 0: the diffuse spheres are also drawn into the particle frame (1) */
+    int32_t reserved;         /* 0 */
+} SphRenderSurfaceFoamParams;
+
+typedef struct {
+    int64_t diffuse;          /* diffuse particles of the frame */
+    int64_t large;            /* of these: walked by one workgroup each */
+    int64_t adds_over;        /* (sphere, pixel) pairs that added to fo: one integer atomic each */
+    int64_t adds_under;       /* ... to fu (and lowered du): two */
+    int64_t clipped;          /* of both: cut short by the limit */
+    int64_t removed;          /* pairs that hit but lay wholly behind the limit (no atomic) */
+    int64_t pixels_over;      /* of the last sph_render_surface: pixels with fo > 0 */
+    int64_t pixels_under;     /* ... with fu > 0 */
+    double ms_splat;          /* HIP events: the copies and the splat, ... */
+    double ms_raw;            /* ... the raw spheres' layer and its merge (parts of the frame call) */
+    double ms_composite;      /* the under and over passes (part of sph_render_surface, behind its ms_shade) */
+} SphRenderSurfaceFoamStats;
+
+/* sets the diffuse set (params NULL: the defaults above) or clears it (foam NULL); applies to the frames sph_render_handle draws
+   afterwards.  The object must outlive its use here.  SPH_ERR_INVALID, with a message that names the field: the surface mode is off,
+   another device, radius_scale not positive or not finite, density / depth_bias negative or not finite, reserved not 0;
+   SPH_ERR_UNSUPPORTED: sph_render_set_foam is set at the same time (which in turn stays refused while the surface mode is on).  At
+   sph_render_handle: SPH_ERR_UNSUPPORTED for a sharded handle and, before any launch, for a diffuse count n with n ceil(512
+   radius_scale) >= 2^32; SPH_ERR_INVALID with raw_spheres for a handle whose particle_max_num reaches 2^31.  sph_render_surface refuses
+   (SPH_ERR_INVALID) a handle frame drawn before the set was given or its parameters changed, or before the thickness mode was
+   switched.  Switching the surface mode off clears the set. */
+int sph_render_set_surface_foam(SphRender *r, SphFoam *foam_or_NULL, const SphRenderSurfaceFoamParams *params_or_NULL);
+/* a plane of the last sph_render_handle frame drawn with the set: plane 0 fo, 1 fu, 2 du (all ones: none), out u32[height][width] */
+int sph_render_surface_download_foam(SphRender *r, int plane, uint32_t *out);
+int sph_render_surface_foam_stats(SphRender *r, SphRenderSurfaceFoamStats *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,19 @@ class SphRenderThicknessStats(C.Structure):
     ]
 
 
+class SphRenderSurfaceFoamParams(C.Structure):
+    _fields_ = [("radius_scale", C.c_double), ("density", C.c_double), ("depth_bias", C.c_double), ("rgb", C.c_uint8 * 3),
+                ("raw_spheres", C.c_uint8), ("reserved", C.c_int32)]
+
+
+class SphRenderSurfaceFoamStats(C.Structure):
+    _fields_ = [
+        ("diffuse", C.c_int64), ("large", C.c_int64), ("adds_over", C.c_int64), ("adds_under", C.c_int64), ("clipped", C.c_int64),
+        ("removed", C.c_int64), ("pixels_over", C.c_int64), ("pixels_under", C.c_int64), ("ms_splat", C.c_double), ("ms_raw", C.c_double),
+        ("ms_composite", C.c_double),
+    ]
+
+
 class SphRenderMeshStats(C.Structure):
     _fields_ = [
         ("meshes", C.c_int64), ("triangles", C.c_int64), ("vertices", C.c_int64), ("large", C.c_int64),
@@ -427,6 +440,9 @@ _SIGNATURES = [
     ("sph_foam_clear", C.c_int, [_VP]),
     ("sph_foam_stats", C.c_int, [_VP, C.POINTER(SphFoamStats)]),
     ("sph_render_set_foam", C.c_int, [_VP, _VP, C.c_double, _VP, _VP, _VP]),
+    ("sph_render_set_surface_foam", C.c_int, [_VP, _VP, C.POINTER(SphRenderSurfaceFoamParams)]),
+    ("sph_render_surface_download_foam", C.c_int, [_VP, C.c_int, _VP]),
+    ("sph_render_surface_foam_stats", C.c_int, [_VP, C.POINTER(SphRenderSurfaceFoamStats)]),
     ("sph_comm_allreduce", C.c_int, [_VP, C.POINTER(C.c_double), C.c_int, C.c_int]),
     ("sph_comm_barrier", C.c_int, [_VP]),
     ("sph_comm_selftest", C.c_int, [_VP, C.c_int]),

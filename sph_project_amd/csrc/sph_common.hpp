@@ -344,6 +344,27 @@ struct RenderThickDev {
     float absorb, scatter;
 };
 
+// Diffuse particles in the surface frames (sph_render_foam.hpp): the diffuse set, the three integer planes and the constants
+// of the composite.  fo / fu: the summed chords of the diffuse spheres over / under the surface (units of u per pixel), du: the nearest
+// start of an under chord below the surface (all ones: none).  key0: the frame's key plane as rend_run left it (a copy once the raw
+// spheres are merged into the frame's), okey: the opaque layer's in thickness mode, else null.  cnt: two groups of RSURF_CNT_BANKS banks
+// of 8 words, banked as RenderSurfDev::cnt.  Group 0, the frame call: [0] adds issued over, [1] under, [2] pairs the limit cut short,
+// [3] pairs it removed.  Group 1, the surface call: [0] pixels with fo > 0, [1] with fu > 0.
+struct RenderFoamDev {
+    int n;                             // diffuse particles
+    const float4 *pos;                 // [n] xyz
+    int *large;                        // [n] spheres whose screen bounds exceed RENDER_LARGE_PX pixels
+    unsigned long long *nlarge;        // [1] their number
+    const unsigned long long *key0;    // [W H]
+    const unsigned long long *okey;    // [W H] or null
+    unsigned *fo, *fu, *du;            // [W H] each
+    unsigned long long *cnt;           // [2][RSURF_CNT_BANKS][8]
+    float rf, rf2;                     // the diffuse sphere's radius and its square
+    float bias;                        // depth_bias r, rounded once on the host
+    float density;
+    unsigned rgb;                      // r | g << 8 | b << 16
+};
+
 // Mesh rendering (sph_render_mesh.hpp): the frame's meshes, concatenated.  Triangle g of the frame belongs to the last
 // record with t0 <= g; its indices are local to that mesh's nv vertices, which start at slot v0 of vert / nrm.  The frame buffers,
 // camera and counters are the RenderDev's: cnt[0] triangles that passed the hit test at some pixel centre (whether or not they won it), [1] non-finite, [2] large,
@@ -727,6 +748,10 @@ struct Launch {
     void (*render_thick_splat)(RenderDev &, RenderSurfDev &, RenderThickDev &);    // T[0] = sum of the surface spheres' chords per pixel
     void (*render_thick_smooth)(RenderDev &, RenderSurfDev &, RenderThickDev &, const unsigned *Q, const unsigned *in, unsigned *out);
     void (*render_thick_shade)(RenderDev &, RenderSurfDev &, RenderThickDev &, const unsigned *Q, const unsigned *T);   // the composite
+    // diffuse particles in the surface frames (sph_render_foam.hpp)
+    void (*render_foam_splat)(RenderDev &, RenderSurfDev &, RenderFoamDev &);   // fo / fu / du from the diffuse spheres' chords
+    void (*render_foam_under)(RenderDev &, RenderSurfDev &, RenderThickDev &, RenderFoamDev &, const unsigned *Q, const unsigned *T);
+    void (*render_foam_over)(RenderDev &, RenderFoamDev &);                     // the over layer on the bytes held; both layers' pixels counted
     // mesh rendering (sph_render_mesh.hpp)
     void (*render_mesh_depth)(RenderDev &, MeshDev &);   // depth keys of triangles (small per thread, large per workgroup) and box lines
     void (*render_mesh_shade)(RenderDev &, MeshDev &);   // the winners' colours (triangles, lines)

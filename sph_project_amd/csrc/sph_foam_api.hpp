@@ -343,7 +343,9 @@ extern "C" int sph_render_set_foam(SphRender *r, SphFoam *foam, double radius_sc
                                    const uint8_t *rgb_bubble) {
     if (!r) return SPH_ERR_INVALID;
     if (!foam) { r->foam = nullptr; return SPH_OK; }
-    if (r->surf_on) return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_set_foam: the surface mode is on (diffuse particles are drawn into particle frames only)");
+    if (r->surf_on)
+        return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_set_foam: the surface mode is on (diffuse particles are drawn into particle frames only; "
+                                            "sph_render_set_surface_foam draws them into surface frames)");
     if (foam->device != r->device) return fail(r, SPH_ERR_INVALID, "sph_render_set_foam: foam on device %d, renderer on %d", foam->device, r->device);
     if (!(radius_scale > 0.0) || !std::isfinite(radius_scale) || !((float)(radius_scale * r->prm.radius) > 0.0f))
         return fail(r, SPH_ERR_INVALID, "sph_render_set_foam: radius_scale %g must be positive and finite", radius_scale);
@@ -357,8 +359,7 @@ extern "C" int sph_render_set_foam(SphRender *r, SphFoam *foam, double radius_sc
 
 // The diffuse set as a layer of its own -- the splat and shade passes on the layer planes with the diffuse particles as their source --
 // folded into the frame just drawn, and the pixels finished again.  Called by sph_render_handle behind rend_run (which has synchronised).
-static int rend_draw_foam(SphRender *r) {
-    SphFoam *f = r->foam;
+static int rend_draw_foam(SphRender *r, SphFoam *f, double scale, const unsigned rgb[3]) {
     const int n = (int)f->count;
     if (n == 0) return SPH_OK;
     const size_t px = (size_t)r->d.W * r->d.H;
@@ -370,14 +371,14 @@ static int rend_draw_foam(SphRender *r) {
     r->d.large = (int *)r->buf[RB_LARGE].p;
     FoamDev src = f->d;
     src.stream = r->stream;   // (the foam's own stream is idle: its calls are synchronous)
-    r->L->foam_render_source(src, n, (int *)r->buf[RB_FID].p, (unsigned *)r->buf[RB_FCOL].p, r->foam_rgb);
+    r->L->foam_render_source(src, n, (int *)r->buf[RB_FID].p, (unsigned *)r->buf[RB_FCOL].p, rgb);
     RenderDev l = r->d;
     l.key = (unsigned long long *)r->buf[RB_LKEY].p; l.rgb = (unsigned char *)r->buf[RB_LRGB].p;
     l.cnt = (unsigned long long *)r->buf[RB_FCNT].p;
     l.n = n; l.pos = f->d.dx[0]; l.meta = nullptr; l.id = (const int *)r->buf[RB_FID].p; l.col = (const unsigned *)r->buf[RB_FCOL].p;
     l.col_home = nullptr; l.mask = ~0u;
     l.ids = nullptr;   // (the id image is written when the merged frame is finished)
-    const double rad = r->foam_scale * r->prm.radius;
+    const double rad = scale * r->prm.radius;
     l.r = (float)rad; l.r2 = (float)(rad * rad);
     l.draw_box = 0;
     for (int e = 0; e < 12; ++e) l.line_axis[e] = -1;
@@ -387,4 +388,134 @@ static int rend_draw_foam(SphRender *r) {
     r->L->render_shade(l);
     rend_merge_incoming(r);
     return rend_refinish(r);
+}
+
+// --- diffuse particles in the surface frames: the kernels are in sph_render_foam.hpp ---------------------------------------
+static const uint8_t RFOAM_CLASS_RGB[3][3] = {{250, 250, 255}, {255, 255, 255}, {225, 235, 250}};   // sph_render_set_foam's defaults
+
+extern "C" int sph_render_set_surface_foam(SphRender *r, SphFoam *foam, const SphRenderSurfaceFoamParams *params) {
+    if (!r) return SPH_ERR_INVALID;
+    // (a frame whose raw spheres are merged in no longer matches its base plane without the copies: sph_render_surface refuses it)
+    if (!foam) { if (r->sfoam_valid && r->fprm.raw_spheres) r->base_valid = false; r->sfoam = nullptr; r->sfoam_valid = false; return SPH_OK; }
+    SphRenderSurfaceFoamParams p{};
+    p.radius_scale = 0.5; p.density = 1.0; p.depth_bias = 1.0; p.rgb[0] = p.rgb[1] = p.rgb[2] = 255; p.raw_spheres = 1;
+    if (params) p = *params;
+    if (!r->surf_on) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface_foam: the surface mode is off (sph_render_set_surface)");
+    if (r->foam)
+        return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_set_surface_foam: diffuse particles are set for the particle frames (sph_render_set_foam): clear them first");
+    if (foam->device != r->device) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface_foam: foam on device %d, renderer on %d", foam->device, r->device);
+    if (!(p.radius_scale > 0.0) || !std::isfinite(p.radius_scale) || !((float)(p.radius_scale * r->prm.radius) > 0.0f) ||
+        !std::isfinite((float)(p.radius_scale * r->prm.radius)))
+        return fail(r, SPH_ERR_INVALID, "sph_render_set_surface_foam: radius_scale %g must be positive and finite", p.radius_scale);
+    if (!(p.density >= 0.0) || !std::isfinite(p.density) || !std::isfinite((float)p.density))
+        return fail(r, SPH_ERR_INVALID, "sph_render_set_surface_foam: density %g must be finite and not negative", p.density);
+    if (!(p.depth_bias >= 0.0) || !std::isfinite(p.depth_bias) || !std::isfinite((float)(p.depth_bias * (double)r->d.r)))
+        return fail(r, SPH_ERR_INVALID, "sph_render_set_surface_foam: depth_bias %g must be finite and not negative", p.depth_bias);
+    if (p.reserved != 0) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface_foam: reserved must be 0");
+    p.raw_spheres = p.raw_spheres ? 1 : 0;
+    if (r->sfoam != foam || memcmp(&p, &r->fprm, sizeof(p)) != 0) {   // the frame held has no planes for these
+        if (r->sfoam_valid && r->fprm.raw_spheres) r->base_valid = false;
+        r->sfoam_valid = false;
+    }
+    r->fprm = p;
+    r->sfoam = foam;
+    return SPH_OK;
+}
+
+// what sph_render_handle refuses before anything is launched
+static int rend_surface_foam_check(SphRender *r, SphHandle *h) {
+    if (h->st.slab_active)
+        return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_handle: diffuse particles are set (sph_render_set_surface_foam): no sharded handle");
+    if (!r->surf_on) { r->sfoam = nullptr; return SPH_OK; }   // (sph_render_set_surface(NULL) clears it: not reached)
+    const double per = ceil(512.0 * r->fprm.radius_scale);
+    if ((double)r->sfoam->count * per >= 4294967296.0)
+        return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_set_surface_foam: %lld diffuse particles of at most %.0f units each (radius_scale %g): a pixel's u32 "
+                                            "holds fewer than 2^32", (long long)r->sfoam->count, per, r->fprm.radius_scale);
+    if (r->fprm.raw_spheres && (int64_t)h->st.cap > (int64_t)INT_MAX)
+        return fail(r, SPH_ERR_INVALID, "sph_render_handle: particle ids reach 2^31, diffuse ids could not be told from them (raw_spheres)");
+    return SPH_OK;
+}
+
+// behind rend_run (which has synchronised): the three planes from the diffuse set as it is now, then -- raw_spheres -- section 26's layer
+// folded into the particle frame, whose key and rgb planes are copied first
+static int rend_surface_foam_draw(SphRender *r) {
+    SphFoam *f = r->sfoam;
+    const SphRenderSurfaceFoamParams &p = r->fprm;
+    const int n = (int)f->count;
+    const size_t px = (size_t)r->d.W * r->d.H;
+    DevBuf *b = r->buf;
+    int rc = b[RB_WFO].reserve(r, px * 4);
+    if (!rc) rc = b[RB_WFU].reserve(r, px * 4);
+    if (!rc) rc = b[RB_WDU].reserve(r, px * 4);
+    if (!rc) rc = b[RB_WCNT].reserve(r, 2 * RSURF_CNT_BANKS * 64);
+    if (!rc) rc = b[RB_WLARGE].reserve(r, 4 * (size_t)std::max(n, 1));
+    if (!rc) rc = b[RB_WNL].reserve(r, 64);
+    if (!rc) rc = b[RB_WRGB0].reserve(r, px * 3);
+    if (!rc && p.raw_spheres) rc = b[RB_WKEY0].reserve(r, px * 8);
+    if (rc) return rc;
+    if (!r->fclk.stream) {
+        for (hipEvent_t &e : r->fclk.ev) HIPCHK(r, hipEventCreate(&e));
+        r->fclk.stream = r->stream;
+    }
+    const bool thick = r->thick_on;
+    const double rad = p.radius_scale * r->prm.radius;
+    RenderFoamDev &w = r->fd;
+    w.n = n; w.pos = f->d.dx[0];
+    w.large = (int *)b[RB_WLARGE].p; w.nlarge = (unsigned long long *)b[RB_WNL].p;
+    w.fo = (unsigned *)b[RB_WFO].p; w.fu = (unsigned *)b[RB_WFU].p; w.du = (unsigned *)b[RB_WDU].p;
+    w.cnt = (unsigned long long *)b[RB_WCNT].p;
+    w.rf = (float)rad; w.rf2 = (float)(rad * rad);
+    w.bias = (float)(p.depth_bias * (double)r->d.r);
+    w.density = (float)p.density;
+    w.rgb = (unsigned)p.rgb[0] | (unsigned)p.rgb[1] << 8 | (unsigned)p.rgb[2] << 16;
+    w.key0 = r->d.key;
+    w.okey = thick ? r->td.okey : nullptr;
+    HIPCHK(r, r->fclk.mark(0));
+    HIPCHK(r, hipMemcpyAsync(b[RB_WRGB0].p, r->d.rgb, px * 3, hipMemcpyDeviceToDevice, r->stream));
+    if (p.raw_spheres) {
+        HIPCHK(r, hipMemcpyAsync(b[RB_WKEY0].p, r->d.key, px * 8, hipMemcpyDeviceToDevice, r->stream));
+        w.key0 = (const unsigned long long *)b[RB_WKEY0].p;
+    }
+    r->L->render_foam_splat(r->d, r->sd, w);   // (the foam's own stream is idle: its calls are synchronous)
+    HIPCHK(r, r->fclk.mark(1));
+    unsigned long long bank[RSURF_CNT_BANKS][8], nl = 0;
+    HIPCHK(r, hipMemcpyAsync(bank, w.cnt, sizeof(bank), hipMemcpyDeviceToHost, r->stream));
+    HIPCHK(r, hipMemcpyAsync(&nl, w.nlarge, 8, hipMemcpyDeviceToHost, r->stream));
+    HIPCHK(r, hipStreamSynchronize(r->stream));
+    HIPCHK(r, hipGetLastError());
+    if (p.raw_spheres) {
+        unsigned cls[3];
+        for (int k = 0; k < 3; ++k) cls[k] = (unsigned)RFOAM_CLASS_RGB[k][0] | (unsigned)RFOAM_CLASS_RGB[k][1] << 8 | (unsigned)RFOAM_CLASS_RGB[k][2] << 16;
+        const int rcd = rend_draw_foam(r, f, p.radius_scale, cls);
+        if (rcd) return rcd;
+    }
+    HIPCHK(r, r->fclk.mark(2));
+    HIPCHK(r, hipStreamSynchronize(r->stream));
+    SphRenderSurfaceFoamStats &o = r->fstats;
+    o = SphRenderSurfaceFoamStats{};
+    o.diffuse = n; o.large = (int64_t)nl;
+    for (int k = 0; k < RSURF_CNT_BANKS; ++k) {
+        o.adds_over += (int64_t)bank[k][0]; o.adds_under += (int64_t)bank[k][1]; o.clipped += (int64_t)bank[k][2]; o.removed += (int64_t)bank[k][3];
+    }
+    o.ms_splat = r->fclk.ms(0, 1); o.ms_raw = r->fclk.ms(1, 2);
+    r->sfoam_valid = true;
+    r->sfoam_thick = thick;
+    return SPH_OK;
+}
+
+extern "C" int sph_render_surface_download_foam(SphRender *r, int plane, uint32_t *out) {
+    if (!r || !out) return SPH_ERR_INVALID;
+    if (plane < 0 || plane > 2) return fail(r, SPH_ERR_INVALID, "sph_render_surface_download_foam: plane %d is none of 0 (fo), 1 (fu), 2 (du)", plane);
+    if (r->frame != RF_PARTICLE || !r->sfoam_valid)
+        return fail(r, SPH_ERR_INVALID, "sph_render_surface_download_foam: no frame with diffuse particles is held (sph_render_set_surface_foam, sph_render_handle)");
+    HIPCHK(r, hipSetDevice(r->device));
+    const unsigned *src = plane == 0 ? r->fd.fo : plane == 1 ? r->fd.fu : r->fd.du;
+    HIPCHK(r, hipMemcpy(out, src, (size_t)r->d.W * r->d.H * 4, hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
+
+extern "C" int sph_render_surface_foam_stats(SphRender *r, SphRenderSurfaceFoamStats *out) {
+    if (!r || !out) return SPH_ERR_INVALID;
+    *out = r->fstats;
+    return SPH_OK;
 }

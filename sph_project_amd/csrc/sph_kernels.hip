@@ -494,6 +494,7 @@ void l_clear_fresh(State &s) {
 #include "sph_render.hpp"
 #include "sph_render_surface.hpp"
 #include "sph_render_thickness.hpp"
+#include "sph_render_foam.hpp"
 #include "sph_video.hpp"
 #include "sph_png.hpp"
 #include "sph_text_passes.hpp"
@@ -533,6 +534,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_render_mesh_launchers(L);
         register_render_surface_launchers(L);
         register_render_thickness_launchers(L);
+        register_render_foam_launchers(L);
         register_video_launchers(L);
         register_png_launchers(L);
         register_text_launchers(L);

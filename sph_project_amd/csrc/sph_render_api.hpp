@@ -10,6 +10,7 @@
 enum RendBufId { RB_KEY, RB_RGB, RB_IDS, RB_CNT, RB_LARGE, RB_POS, RB_IDV, RB_COL, RB_MVERT, RB_MNRM, RB_MTRI, RB_MREC, RB_LKEY, RB_LRGB, RB_SBASE, RB_SQ0, RB_SQ1, RB_SCNT, RB_SMASK,
                  RB_TOKEY, RB_TORGB, RB_TOCNT, RB_TOLARGE, RB_TT0, RB_TT1, RB_TCNT,
                  RB_FID, RB_FCOL, RB_FCNT,   // ids, colours and counters of the diffuse particles' layer
+                 RB_WFO, RB_WFU, RB_WDU, RB_WCNT, RB_WLARGE, RB_WNL, RB_WKEY0, RB_WRGB0,   // diffuse particles in the surface frames
                  RB_COUNT_ };
 
 // what the renderer holds.  RF_ON_RANK0: the last frame was composited over a communicator and lies on rank 0, not here; RF_MESH: a mesh
@@ -52,8 +53,20 @@ struct SphRender : DevObj {   // clk[0]: a particle frame's stages, clk[1]: a me
     struct SphFoam *foam = nullptr;
     double foam_scale = 0.5;
     unsigned foam_rgb[3] = {0, 0, 0};   // spray, foam, bubble
+    // diffuse particles in the surface frames (sph_render_set_surface_foam in sph_foam_api.hpp): fclk marks 0 / 1 / 2 around
+    // the splat and the raw spheres' merge, 3 / 4 around the composite
+    struct SphFoam *sfoam = nullptr;
+    SphRenderSurfaceFoamParams fprm{};
+    RenderFoamDev fd{};
+    bool from_handle = false;     // the frame held was drawn by sph_render_handle (the points path ignores the mode)
+    bool sfoam_valid = false;     // the three planes belong to the frame held
+    bool sfoam_thick = false;     // ... and were summed against the thickness mode's limits
+    StageClock fclk;
+    SphRenderSurfaceFoamStats fstats{};
 };
-static int rend_draw_foam(SphRender *r);
+static int rend_draw_foam(SphRender *r, struct SphFoam *f, double scale, const unsigned rgb[3]);
+static int rend_surface_foam_check(SphRender *r, SphHandle *h);
+static int rend_surface_foam_draw(SphRender *r);
 
 static bool rend_finite3(const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 static double rend_dot(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -172,6 +185,7 @@ extern "C" void sph_render_destroy(SphRender *r) {
     if (r->stream) hipStreamSynchronize(r->stream);
     for (hipEvent_t e : r->sclk.ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : r->tclk.ev) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : r->fclk.ev) if (e) hipEventDestroy(e);
     devobj_close(r, r->buf, RB_COUNT_);
     delete r;
 }
@@ -266,6 +280,7 @@ static int rend_run(SphRender *r, int64_t n_in) {
     StageClock &k = r->clk[0];
     const bool thick = r->surf_on && r->thick_on;
     r->thick_valid = r->thick_shaded = false;
+    r->sfoam_valid = false;
     if (thick && n_in > (int64_t)RTHICK_MAX_PARTICLES) {
         HIPCHK(r, hipStreamSynchronize(r->stream));   // (the points path's uploads: the caller's vectors are free again)
         return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_set_thickness: %lld particles in the frame, a pixel's u32 thickness holds %d contributions",
@@ -357,6 +372,7 @@ extern "C" int sph_render_layer_merge(SphRender *r, const uint64_t *key, const u
     { int rc = rend_layer_check(r, "sph_render_layer_merge"); if (rc) return rc; }
     r->base_valid = r->depth_valid = false;   // (the merged pixels' colours and flags are not known here)
     r->thick_valid = r->thick_shaded = false;
+    r->sfoam_valid = false;
     HIPCHK(r, hipSetDevice(r->device));
     { int rc = rend_layer_room(r); if (rc) return rc; }
     const size_t px = (size_t)r->d.W * r->d.H;
@@ -444,6 +460,7 @@ extern "C" int sph_render_points(SphRender *r, const float *xyz, const uint8_t *
     }
     HIPCHK(r, hipSetDevice(r->device));
     r->frame = RF_NONE;
+    r->from_handle = false;
     r->stats = SphRenderStats{};
     { int rc = rend_room(r, (size_t)n, true); if (rc) return rc; }
     std::vector<float4> p4((size_t)n);
@@ -483,6 +500,7 @@ extern "C" int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mas
         return fail(r, SPH_ERR_UNSUPPORTED, "sph_render_handle: diffuse particles are set (sph_render_set_foam): no surface mode, no sharded handle");
     if (r->foam && (int64_t)h->st.cap > (int64_t)INT_MAX)
         return fail(r, SPH_ERR_INVALID, "sph_render_handle: particle ids reach 2^31, diffuse ids could not be told from them");
+    if (r->sfoam) { int rc = rend_surface_foam_check(r, h); if (rc) return rc; }
     HIPCHK(r, hipSetDevice(r->device));
     r->frame = RF_NONE;
     r->stats = SphRenderStats{};
@@ -504,7 +522,9 @@ extern "C" int sph_render_handle(SphRender *r, SphHandle *h, uint32_t object_mas
     HIPCHK(r, r->clk[0].mark(0));
     d.n = n; d.pos = s.posv.cur(); d.meta = s.meta.cur(); d.id = s.pid.cur(); d.mask = object_mask;
     { int rc = rend_run(r, n); if (rc) return rc; }
-    if (r->foam) return rend_draw_foam(r);
+    r->from_handle = true;
+    if (r->foam) return rend_draw_foam(r, r->foam, r->foam_scale, r->foam_rgb);
+    if (r->sfoam) return rend_surface_foam_draw(r);   // (never with a sharded handle: rend_surface_foam_check)
     if (!sharded) return SPH_OK;
     return rend_composite(r, h);   // collective: every rank of the communicator is here with the same renderer parameters and mask
 }
@@ -542,7 +562,7 @@ extern "C" int sph_render_stats(SphRender *r, SphRenderStats *out) {
 // --- surface mode: the kernels are in sph_render_surface.hpp ---------------------------------------------------------------
 extern "C" int sph_render_set_surface(SphRender *r, const SphRenderSurfaceParams *params) {
     if (!r) return SPH_ERR_INVALID;
-    if (!params) { r->surf_on = r->thick_on = false; return SPH_OK; }
+    if (!params) { r->surf_on = r->thick_on = false; r->sfoam = nullptr; r->sfoam_valid = false; return SPH_OK; }
     const SphRenderSurfaceParams p = *params;
     if (p.iterations < 0 || p.iterations > 64) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: iterations %d outside 0..64", p.iterations);
     if (p.rmax < 1 || p.rmax > RSURF_RMAX_CAP) return fail(r, SPH_ERR_INVALID, "sph_render_set_surface: rmax %d outside 1..%d", p.rmax, RSURF_RMAX_CAP);
@@ -560,7 +580,7 @@ extern "C" int sph_render_set_surface(SphRender *r, const SphRenderSurfaceParams
     const unsigned omask = p.object_mask < 0 ? ~0u : (unsigned)p.object_mask;
     const int fluid_only = p.object_mask < 0 ? 1 : 0;
     if (!r->surf_on || omask != s.omask || fluid_only != s.fluid_only)   // the frame held has no base plane (or thickness) for this mask
-        r->base_valid = r->thick_valid = r->thick_shaded = false;
+        r->base_valid = r->thick_valid = r->thick_shaded = r->sfoam_valid = false;
     s.omask = omask; s.fluid_only = fluid_only;
     s.inv_u = (float)(256.0 / (double)r->d.r);
     s.u = (float)((double)r->d.r / 256.0);
@@ -592,6 +612,12 @@ extern "C" int sph_render_surface(SphRender *r) {
         return fail(r, SPH_ERR_INVALID, "sph_render_surface: the frame held was drawn before the mode was switched on, or changed by sph_render_layer_merge");
     if (r->thick_on && !r->thick_valid)
         return fail(r, SPH_ERR_INVALID, "sph_render_surface: the frame held was drawn before the thickness mode was switched on (sph_render_set_thickness)");
+    const bool wfoam = r->sfoam && r->from_handle;   // diffuse particles over and under the surface
+    if (wfoam && !r->sfoam_valid)
+        return fail(r, SPH_ERR_INVALID, "sph_render_surface: the frame held was drawn before the diffuse particles were set (sph_render_set_surface_foam)");
+    if (wfoam && r->sfoam_thick != r->thick_on)
+        return fail(r, SPH_ERR_INVALID, "sph_render_surface: the thickness mode was switched after the frame held was drawn with diffuse particles "
+                                        "(sph_render_set_surface_foam): its planes were summed against the other limits");
     HIPCHK(r, hipSetDevice(r->device));
     RenderDev &d = r->d;
     RenderSurfDev &s = r->sd;
@@ -600,7 +626,12 @@ extern "C" int sph_render_surface(SphRender *r) {
     r->depth_valid = false;
     HIPCHK(r, hipMemsetAsync(s.cnt, 0, RSURF_CNT_BANKS * 64, r->stream));
     HIPCHK(r, k.mark(2));
-    r->L->render_surface_quantise(d, s);
+    RenderDev dq = d;   // what the quantise pass reads: the frame's key plane, or its copy from before the raw spheres were merged in
+    if (wfoam) {
+        HIPCHK(r, hipMemcpyAsync(d.rgb, r->buf[RB_WRGB0].p, (size_t)d.W * d.H * 3, hipMemcpyDeviceToDevice, r->stream));   // a repeat starts from the frame
+        dq.key = (unsigned long long *)r->fd.key0;
+    }
+    r->L->render_surface_quantise(dq, s);
     for (int it = 0; it < iters; ++it) r->L->render_surface_smooth(d, s, it);
     HIPCHK(r, k.mark(3));
     r->depth_plane = iters & 1;
@@ -626,6 +657,12 @@ extern "C" int sph_render_surface(SphRender *r) {
     } else
         r->L->render_surface_shade(d, s, r->depth_plane);
     HIPCHK(r, k.mark(4));
+    if (wfoam) {
+        HIPCHK(r, r->fclk.mark(3));
+        if (thick) r->L->render_foam_under(d, s, r->td, r->fd, s.q[r->depth_plane], r->thick_plane);
+        r->L->render_foam_over(d, r->fd);
+        HIPCHK(r, r->fclk.mark(4));
+    }
     unsigned long long bank[RSURF_CNT_BANKS][8], c[8] = {};
     HIPCHK(r, hipMemcpyAsync(bank, s.cnt, sizeof(bank), hipMemcpyDeviceToHost, r->stream));
     HIPCHK(r, hipStreamSynchronize(r->stream));
@@ -644,6 +681,13 @@ extern "C" int sph_render_surface(SphRender *r) {
         SphRenderThicknessStats &ts = r->tstats;
         ts.iterations = titers; ts.taps_visited = (int64_t)tc[0]; ts.empty_pixels = (int64_t)tc[1]; ts.max_thickness = (int64_t)tc[2];
         ts.ms_smooth = r->tclk.ms(3, 4); ts.ms_shade = r->tclk.ms(4, 5);
+    }
+    if (wfoam) {
+        HIPCHK(r, hipMemcpy(bank, r->fd.cnt + (size_t)RSURF_CNT_BANKS * 8, sizeof(bank), hipMemcpyDeviceToHost));   // group 1 (the stream is idle)
+        int64_t po = 0, pu = 0;
+        for (int b = 0; b < RSURF_CNT_BANKS; ++b) { po += (int64_t)bank[b][0]; pu += (int64_t)bank[b][1]; }
+        r->fstats.pixels_over = po; r->fstats.pixels_under = pu;
+        r->fstats.ms_composite = r->fclk.ms(3, 4);
     }
     return SPH_OK;
 }

@@ -13,6 +13,8 @@ adds {out}/raw_view.avi / {out}/render.avi, the same frames as Motion-JPEG compr
 --render_surface writes {cnt:06}/surface_view.png: the particle frame with the fluid drawn as a smoothed, lit surface in screen space
 (DESIGN.md 24), at the cost of a particle frame where --render_meshes pays for a reconstruction.  --surface_thickness makes that
 surface translucent: the fluid's thickness along every ray lets rigid bodies and the box show through.
+--foam --render_surface --surface_foam draws the diffuse particles into surface_view.png as white water, over the surface and, with
+--surface_thickness, under it.
 --png_device writes the PNG files from the device image as well (DESIGN.md 21): no pixel is downloaded, no zlib runs on the host;
 --png_coding dynamic makes those files smaller (dynamic Huffman blocks) for a slower encode, --png_coding window smaller again (matches from
 the 32 KB before a position).
@@ -157,6 +159,14 @@ def parse_args(argv=None):
                         help="generate diffuse particles -- spray, foam and bubbles -- from the fluid on the GPU (DESIGN.md 26): "
                              "{frame}/diffuse_particles.ply at every output frame, and with --render drawn into raw_view.png; the "
                              "fluid is not affected.  Parameters: the scene's optional Configuration.foam dict")
+    parser.add_argument("--surface_foam", action="store_true",
+                        help="with --foam and --render_surface: draw the diffuse particles into surface_view.png as white water -- the "
+                             "summed chords of their spheres along every pixel's ray, over the surface and, with --surface_thickness, "
+                             "under it, dimmed by the water in front (DESIGN.md 28); with --render raw_view.png shows them as spheres")
+    parser.add_argument("--surface_foam_density", type=float, default=None,
+                        help="with --surface_foam: whiteness per particle radius of diffuse chord (1.0)")
+    parser.add_argument("--surface_foam_bias", type=float, default=None,
+                        help="with --surface_foam: particle radii behind the surface from which a diffuse particle counts as under it (1.0)")
     parser.add_argument("--foam_every", type=int, default=None,
                         help="simulation steps per diffuse-particle step, default 4 (its dt is that many time steps)")
     parser.add_argument("--foam_max", type=int, default=None,
@@ -170,12 +180,20 @@ def parse_args(argv=None):
     for flag in ("foam_every", "foam_max"):
         if getattr(args, flag) is not None and not args.foam:
             parser.error(f"--{flag} sets a parameter of the diffuse particles: give --foam as well")
+    if args.surface_foam and not args.foam:
+        parser.error("--surface_foam draws the diffuse particles into the surface frames: give --foam as well")
+    if args.surface_foam and not args.render_surface:
+        parser.error("--surface_foam draws the diffuse particles into the surface frames: give --render_surface as well")
+    for flag in ("surface_foam_density", "surface_foam_bias"):
+        if getattr(args, flag) is not None and not args.surface_foam:
+            parser.error(f"--{flag} sets a parameter of the diffuse particles in the surface frames: give --surface_foam as well")
     if args.foam:
         if args.gpus > 1:
             parser.error(f"--gpus {args.gpus}: --foam reads the whole fluid on one device (sharded scenes are not supported); run it "
                          "with --gpus 1")
-        if args.render_surface:
-            parser.error("--foam draws the diffuse particles into particle frames only: not with --render_surface (DESIGN.md 26)")
+        if args.render_surface and not args.surface_foam:
+            parser.error("--foam draws the diffuse particles into particle frames only: not with --render_surface (DESIGN.md 26) "
+                         "unless --surface_foam draws them into the surface frames")
         if args.foam_every is not None and args.foam_every < 1:
             parser.error(f"--foam_every {args.foam_every}: at least one simulation step per diffuse-particle step")
         if args.foam_max is not None and args.foam_max < 1:
@@ -519,7 +537,10 @@ def main(argv=None):
     if args.foam:
         diffuse = make_foam(container, solver, config, args)
         stepped = FoamStepper(solver, container, diffuse, args.foam_every, float(solver.dt[None]))
-        if raw is not None:
+        if args.surface_foam:   # into the surface frames; as spheres into the particle frame exactly when that frame is written
+            chosen = dict(density=args.surface_foam_density, depth_bias=args.surface_foam_bias)
+            renderer.set_surface_foam(diffuse, raw_spheres=raw is not None, **{k: v for k, v in chosen.items() if v is not None})
+        elif raw is not None:
             renderer.set_foam(diffuse)
 
     exporter = None   # --export_device: the text files come from the device state
