@@ -130,6 +130,9 @@ typedef enum {
     /* rigid contact (allocated by sph_set_rigid_contact; written for contact targets only, zeroed by SPH_PH_RIGID_CONTACT): */
     SPH_F_RIGID_CONTACT_DN = 33,   /* f32[n][3] sum of depth * n over the target's contacts in the last contact pass */
     SPH_F_RIGID_CONTACT_COUNT = 34,/* f32[n]    the number of those contacts (partner particles + wall planes) */
+    /* PCISPH only: the non-pressure acceleration the last SPH_PH_NON_PRESSURE stored (PCISPH.py:22 keeps it in particle_accelerations
+       until the refine loop is over; this library keeps it in a buffer of its own, SPH_F_ACCELERATION is the pressure pass's): */
+    SPH_F_NON_PRESSURE_ACCEL = 35, /* f32[n][3] gravity + surface tension + viscosity (base_solver.py:190), download only */
     SPH_F_COUNT_
 } SphField;
 

@@ -23,7 +23,7 @@ METHOD = {"wcsph": 0, "dfsph": 1, "pcisph": 2, "iisph": 3, "pbf": 4}
  F_DFSPH_KAPPA_V, F_DENSITY_STAR, F_DENSITY_DERIV, F_PRESSURE_ACCEL, F_PREDICTED_VEL, F_PREDICTED_POS,
  F_CG_X, F_ORIG_POSITION, F_GHOST, F_DFSPH_KAPPA_NEXT, F_DFSPH_KAPPA_V_NEXT, F_DEBUG_CAPTURE,
  F_IISPH_DII, F_IISPH_AII, F_IISPH_DIJ_PJ, F_IISPH_SUM_I, F_PBF_OLD_POSITION, F_PBF_LAMBDA, F_RIGID_CONTACT_DN,
- F_RIGID_CONTACT_COUNT) = range(35)
+ F_RIGID_CONTACT_COUNT, F_NON_PRESSURE_ACCEL) = range(36)
 
 _FIELD_SPEC = {  # field -> (dtype, components)
     F_POSITION: (np.float32, 3), F_VELOCITY: (np.float32, 3), F_ACCELERATION: (np.float32, 3),
@@ -37,7 +37,7 @@ _FIELD_SPEC = {  # field -> (dtype, components)
     F_DFSPH_KAPPA_NEXT: (np.float32, 1), F_DFSPH_KAPPA_V_NEXT: (np.float32, 1), F_DEBUG_CAPTURE: (np.float32, 1),
     F_IISPH_DII: (np.float32, 3), F_IISPH_AII: (np.float32, 1), F_IISPH_DIJ_PJ: (np.float32, 3), F_IISPH_SUM_I: (np.float32, 1),
     F_PBF_OLD_POSITION: (np.float32, 3), F_PBF_LAMBDA: (np.float32, 1),
-    F_RIGID_CONTACT_DN: (np.float32, 3), F_RIGID_CONTACT_COUNT: (np.float32, 1),
+    F_RIGID_CONTACT_DN: (np.float32, 3), F_RIGID_CONTACT_COUNT: (np.float32, 1), F_NON_PRESSURE_ACCEL: (np.float32, 3),
 }
 
 # enum SphPhase

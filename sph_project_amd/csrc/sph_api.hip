@@ -1217,6 +1217,7 @@ static const float4 *vec_field(SphHandle *h, int field) {
         case SPH_F_IISPH_DIJ_PJ: case SPH_F_IISPH_SUM_I: return s.iisph_dij; // (dij_pj, sum_i)
         case SPH_F_PBF_OLD_POSITION: return h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT ? nullptr : s.pbf_old;   // (x_old, sorted cell id); consistent variant: posv is the old position
         case SPH_F_RIGID_CONTACT_DN: case SPH_F_RIGID_CONTACT_COUNT: return s.contact_part;   // (sum of depth * n, contacts)
+        case SPH_F_NON_PRESSURE_ACCEL: return s.acc_np;   // (PCISPH only; null otherwise)
         default: return nullptr;
     }
 }
@@ -1248,7 +1249,7 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
     const bool is_vec3 = field == SPH_F_POSITION || field == SPH_F_VELOCITY || field == SPH_F_ACCELERATION ||
                          field == SPH_F_PRESSURE_ACCEL || field == SPH_F_PREDICTED_VEL || field == SPH_F_PREDICTED_POS ||
                          field == SPH_F_CG_X || field == SPH_F_ORIG_POSITION || field == SPH_F_IISPH_DII || field == SPH_F_IISPH_DIJ_PJ ||
-                         field == SPH_F_PBF_OLD_POSITION || field == SPH_F_RIGID_CONTACT_DN;
+                         field == SPH_F_PBF_OLD_POSITION || field == SPH_F_RIGID_CONTACT_DN || field == SPH_F_NON_PRESSURE_ACCEL;
     if (is_vec3) {
         const float4 *src = vec_field(h, field);
         if (!src) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);

@@ -213,14 +213,16 @@ def _pair_list(x, h, rows=None):
     return o[keep], i[keep], j[keep]
 
 
-def wcsph_pressure_accel_f64(x, rho, prs, mass, vol, mat, h, rho0, rows=None):
+def wcsph_pressure_accel_f64(x, rho, prs, mass, vol, mat, h, rho0, rows=None, pair_terms=False):
     """The reference's pressure acceleration (base_solver.py:136-178 with the cubic kernel gradient of base_solver.py:41-58)
     restated in float64 over a KD-tree pair list -- an independent evaluation, not the oracle: a_i = -sum_j m_j (p_i / rho_i^2 +
     p_j / rho_j^2) grad W_ij over fluid neighbours, -rho0 V_j p_i / rho_i^2 grad W_ij over boundary neighbours.
     Returns per particle and component (rows of non-fluid particles are zero): the sum, sum_j |term_j|, and sum_j |term_j| amp_j with
     amp_j = |q W'' / W'| the factor by which a relative error of q = r / h shows up in the term: 2 q / (1 - q) on the outer branch
     ((1 - q)^2 cancels towards the edge of the support), |6 q - 2| / |3 q - 2| <= 2 on the inner one.
-    `rows`: evaluate only these particles (rows of the result follow `rows`); their neighbours come from the whole state."""
+    `rows`: evaluate only these particles (rows of the result follow `rows`); their neighbours come from the whole state.
+    `pair_terms`: a fourth result, the pair terms themselves -- dict(o, i, j, t, t_amp) with t the (pairs, 3) terms of the sum and t_amp
+    their |term| amp -- for the reaction onto rigid bodies (tests/nonpressure_terms.py pressure_wrench_f64)."""
     x = x.astype(np.float64)
     o, i, j = _pair_list(x, h, rows)
     n = len(x) if rows is None else len(rows)
@@ -238,7 +240,10 @@ def wcsph_pressure_accel_f64(x, rho, prs, mass, vol, mat, h, rho0, rows=None):
     a, mag, mag_amp = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))
     np.add.at(a, o, t)
     np.add.at(mag, o, np.abs(t))
-    np.add.at(mag_amp, o, np.abs((coef * s_amp)[:, None] * R))
+    t_amp = np.abs((coef * s_amp)[:, None] * R)
+    np.add.at(mag_amp, o, t_amp)
+    if pair_terms:
+        return a, mag, mag_amp, dict(o=o, i=i, j=j, t=t, t_amp=t_amp)
     return a, mag, mag_amp
 
 
