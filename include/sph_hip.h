@@ -160,6 +160,14 @@ typedef enum {
     SPH_PH_PBFC_DENSITY_LAMBDA = 16, /* walk A: rho, lambda at x*; SphPbfStats::error = mean C of this walk, iterations = 1 */
     SPH_PH_PBFC_DELTA = 17,          /* walk B: the Jacobi correction of x* */
     SPH_PH_PBFC_FINISH = 18,         /* x = boundary(x*), v = (x - x_old) / dt, emitter branch */
+    /* PCISPH, the passes of the step one by one (after SPH_PH_NON_PRESSURE, on the cell lists of the last sort): */
+    SPH_PH_PCISPH_INIT = 19,           /* PCISPH.py:154 init_step: p = 0, predicted velocity and position without a pressure term */
+    SPH_PH_PCISPH_RHO_STAR = 20,       /* first walk of an iteration of PCISPH.py:110 refine: :33 compute_density_star + :66 update_pressure;
+                                          SphStats::err_pcisph = density_error of this walk, iter_pcisph = 1 */
+    SPH_PH_PCISPH_PRESSURE_ACCEL = 21, /* second walk: :75 compute_temp_pressure_acceleration + :19, :26 predicted velocity and position */
+    SPH_PH_DFSPH_ALPHA_DIVERGENCE = 22, /* the end of a DFSPH step behind the sort and the rigid volumes, as the step runs it: density + alpha + the
+                                           first D rho / Dt in ONE walk (DFSPH.py:317-318, :140), then the loop of :139.  The fast build's fused walk
+                                           evaluates that first D rho / Dt in another order than the pass SPH_PH_DFSPH_DIVERGENCE starts with */
     SPH_PH_COUNT_
 } SphPhase;
 

@@ -1166,6 +1166,9 @@ static void pcisph_init_step(SphRef *s) {
         }
 }
 
+/* the same, callable by itself (tests look between init_step and refine) */
+void sphref_pcisph_init_step(SphRef *s) { pcisph_init_step(s); }
+
 /* PCISPH.py:110 refine */
 int sphref_pcisph_refine(SphRef *s) {
     int num_itr = 0;

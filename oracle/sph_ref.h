@@ -93,6 +93,7 @@ int  sphref_dfsph_correct_divergence_error(SphRef *s); /* :139 */
 int  sphref_dfsph_correct_density_error(SphRef *s);    /* :225 */
 void sphref_pcisph_compute_k(SphRef *s);          /* PCISPH.py:129 */
 int  sphref_pcisph_refine(SphRef *s);             /* :110 */
+void sphref_pcisph_init_step(SphRef *s);          /* :154 */
 
 void sphref_prepare(SphRef *s);                   /* base_solver.py:683 (+ DFSPH.py:321, PCISPH.py:188) */
 void sphref_step(SphRef *s);                      /* base_solver.py:692 */

@@ -46,6 +46,10 @@ _FIELD_SPEC = {  # field -> (dtype, components)
  PH_PBF_FIX_POSITION, PH_PBF_PREDICT, PH_PBF_FINISH, PH_RIGID_CONTACT) = range(15)
 # the consistent PBF variant (sph_set_pbf_variant)
 PH_PBFC_PREDICT, PH_PBFC_DENSITY_LAMBDA, PH_PBFC_DELTA, PH_PBFC_FINISH = 15, 16, 17, 18
+# PCISPH pass by pass (after PH_NON_PRESSURE): init_step, and the two walks of one iteration of refine
+PH_PCISPH_INIT, PH_PCISPH_RHO_STAR, PH_PCISPH_PRESSURE_ACCEL = 19, 20, 21
+# DFSPH: the end of a step behind the sort as the step runs it (density + alpha + first D rho / Dt in one walk, then the divergence loop)
+PH_DFSPH_ALPHA_DIVERGENCE = 22
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",

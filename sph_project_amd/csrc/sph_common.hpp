@@ -687,6 +687,7 @@ struct Launch {
     void (*pcisph_init)(State &);
     void (*pcisph_rho_star)(State &);
     void (*pcisph_pressure_accel)(State &);
+    void (*pcisph_reduce_error)(State &);       // adds up the rho* walk's partial sums where no second walk follows (SPH_PH_PCISPH_RHO_STAR)
     // IISPH
     void (*iisph_prepare)(State &);             // dii + aii + rho* (IISPH.py:18-90), p = 0
     void (*iisph_dij_pj)(State &);              // first walk of an iteration (IISPH.py:125, + w = dii p + dij_pj)

@@ -67,7 +67,9 @@ struct DfsphDensityAlphaPass {
 // The three neighbour sums that follow DFSPH's end-of-step sort in ONE walk: compute_density (base_solver.py:522), compute_alpha
 // (DFSPH.py:23) and the compute_density_derivative that opens correct_divergence_error (DFSPH.py:66, :140) -- the first depends on
 // the positions only, the third on positions and velocities, none on the results of the others (kappa_v = D rho / Dt * alpha is
-// per particle: finish()).  One pass less per step than DfsphDensityAlphaPass + DfsphRhoAdvPass<0> (same arithmetic, same order).
+// per particle: finish()).  One pass less per step than DfsphDensityAlphaPass + DfsphRhoAdvPass<0>: the same arithmetic in the same order
+// (the same bits) in the strict build; the fast build's DfsphRhoAdvPass takes the scalar-coefficient form, this pass the gradient it
+// needs for alpha anyway, so there the first D rho / Dt of a step differs from that pass's by roundings (tests/test_hip_pressure_solve.py).
 // Bytes / particle: R posv 16 + velm 16 -> W rho 4 + alpha 4 + D rho / Dt 4 + kappa_v 4.
 template <bool AF>
 struct DfsphDensityAlphaDivPass {

@@ -162,6 +162,8 @@ static void l_pcisph_pressure_accel(State &s) {
     if (s.c.n > 0 && !s.skip_residual) l_reduce_sum(s, 2, cdiv(s.c.n, NBR_BLOCK));   // density error of this iteration's rho* pass
 }
 
+static void l_pcisph_reduce_error(State &s) { if (s.c.n > 0) l_reduce_sum(s, 2, cdiv(s.c.n, NBR_BLOCK)); }
+
 // IISPH.py:18-90 (dii, aii, rho*; p = 0): after the non-pressure pass, velm.cur() = v*
 static void l_iisph_prepare(State &s) {
     if (s.c.all_fluid) { IisphPreparePass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.iisph_dii, s.rho_star, s.prs, s.ptm, s.c.rho0, s.red_partial}; launch_pass(s, p, 2); }
@@ -293,6 +295,7 @@ static void register_solver_launchers(Launch &L) {
     L.pcisph_init = l_pcisph_init;
     L.pcisph_rho_star = l_pcisph_rho_star;
     L.pcisph_pressure_accel = l_pcisph_pressure_accel;
+    L.pcisph_reduce_error = l_pcisph_reduce_error;
     L.iisph_prepare = l_iisph_prepare;
     L.iisph_dij_pj = l_iisph_dij_pj;
     L.iisph_sum_i = l_iisph_sum_i;

@@ -504,6 +504,24 @@ static int method_run_phase(SphHandle *h, int phase) {
             case SPH_PH_DFSPH_ALPHA: { ProfScope p(h, SPH_K_DFSPH_DENSITY_ALPHA); h->L->dfsph_density_alpha(s); } return SPH_OK;
             case SPH_PH_DFSPH_DIVERGENCE: return dfsph_divergence(h);
             case SPH_PH_DFSPH_DENSITY: return dfsph_density(h);
+            case SPH_PH_DFSPH_ALPHA_DIVERGENCE: {   // dfsph_step_end behind the sort and the rigid volumes (unsharded: no exchanges)
+                { ProfScope p(h, SPH_K_DFSPH_DENSITY_ALPHA); h->L->dfsph_density_alpha_div(s); }
+                return dfsph_divergence(h, true);
+            }
+            default: break;
+        }
+    } else if (h->prm.method == SPH_METHOD_PCISPH) {   // the passes of pcisph_step / pcisph_refine one by one (unsharded: no exchanges)
+        switch (phase) {
+            case SPH_PH_PCISPH_INIT: { ProfScope p(h, SPH_K_MISC); h->L->pcisph_init(s); } return SPH_OK;
+            case SPH_PH_PCISPH_RHO_STAR: {   // the first walk of an iteration, no stop test; its density error is read back
+                { ProfScope p(h, SPH_K_PCISPH_RHO_STAR); h->L->pcisph_rho_star(s); }
+                { ProfScope p(h, SPH_K_REDUCE); h->L->pcisph_reduce_error(s); }   // (inside a step the second walk's launcher finishes these sums)
+                float sum = 0.0f;
+                int rc = read_red(h, 2, &sum); if (rc) return rc;
+                h->last.iter_pcisph = 1; h->last.err_pcisph = h->n_fluid > 0 ? sum / (float)h->n_fluid : 0.0f;
+                return SPH_OK;
+            }
+            case SPH_PH_PCISPH_PRESSURE_ACCEL: { ProfScope p(h, SPH_K_PCISPH_PRESSURE_ACCEL); h->L->pcisph_pressure_accel(s); } return SPH_OK;   // (adds the same partial sums up once more, as in a step)
             default: break;
         }
     } else if (h->prm.method == SPH_METHOD_IISPH) {
