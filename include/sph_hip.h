@@ -133,6 +133,17 @@ typedef enum {
     /* PCISPH only: the non-pressure acceleration the last SPH_PH_NON_PRESSURE stored (PCISPH.py:22 keeps it in particle_accelerations
        until the refine loop is over; this library keeps it in a buffer of its own, SPH_F_ACCELERATION is the pressure pass's): */
     SPH_F_NON_PRESSURE_ACCEL = 35, /* f32[n][3] gravity + surface tension + viscosity (base_solver.py:190), download only */
+    /* implicit viscosity (viscosity_implicit handles only), download only: the vectors of the CG solve (base_solver.py:282-517) as the
+       last launch left them.  Written on fluid rows only: any other row keeps what it held (zero, or a former occupant's value). */
+    SPH_F_CG_B = 36,               /* f32[n][3] cg_b (:310) */
+    SPH_F_CG_R = 37,               /* f32[n][3] cg_r */
+    SPH_F_CG_P = 38,               /* f32[n][3] cg_p, the search direction of the running iteration */
+    SPH_F_CG_AP = 39,              /* f32[n][3] cg_Ap.  NOT written by an A p walk that leaves its three parts only (the split walk inside the
+                                      unsharded loop, SPH_F_CG_AP_PARTS): it then still holds the last combined A p */
+    SPH_F_CG_V0 = 40,              /* f32[n][3] original_velocity (:298) */
+    SPH_F_CG_DINV = 41,            /* f32[n][9] cg_diagnol_ii_inv, row-major (:303-308) */
+    SPH_F_CG_AP_PARTS = 42,        /* f32[3][n][3] the per-x-offset-group parts of sum_j D_i^-1 (-A_ij) p_j of the last SPLIT A p walk, before
+                                      dt / rho0 and + p_i: A p = ((part_0 + part_1) + part_2) dt / rho0 + p */
     SPH_F_COUNT_
 } SphField;
 
@@ -168,6 +179,17 @@ typedef enum {
     SPH_PH_DFSPH_ALPHA_DIVERGENCE = 22, /* the end of a DFSPH step behind the sort and the rigid volumes, as the step runs it: density + alpha + the
                                            first D rho / Dt in ONE walk (DFSPH.py:317-318, :140), then the loop of :139.  The fast build's fused walk
                                            evaluates that first D rho / Dt in another order than the pass SPH_PH_DFSPH_DIVERGENCE starts with */
+    /* Implicit viscosity (viscosity_implicit handles of any method, unsharded), the launches of the CG solve inside SPH_PH_NON_PRESSURE one
+       pass each, with no stop test.  SPH_PH_CG_PREPARE, k x (AP, UPDATE_XR, UPDATE_P), SPH_PH_CG_END is SPH_PH_NON_PRESSURE with
+       fixed_iterations = k, bit for bit. */
+    SPH_PH_CG_PREPARE = 23,    /* base_solver.py:510-512: prepare_conjugate_gradient_solver1, the first compute_Ap, prepare_..._solver2, |r0|^2 */
+    SPH_PH_CG_AP = 24,         /* :374 compute_Ap as the loop's next A p pass runs it: from the second one on it also applies the p update of
+                                  the iteration before, where the step folds that update into it (every unsharded solve) */
+    SPH_PH_CG_UPDATE_XR = 25,  /* :394 alpha, :409 update_cg_x, :415 update_cg_r_and_beta (the sums) */
+    SPH_PH_CG_UPDATE_P = 26,   /* :427-437 beta, error, update_p.  Where the step folds the p update into the next A p pass this phase launches
+                                  NOTHING and returns SPH_OK: cg_p, beta and the error change only with the next SPH_PH_CG_AP */
+    SPH_PH_CG_END = 27,        /* :514-517: the viscous acceleration from the solved velocities + gravity + surface tension, v += dt a on the
+                                  original velocities, the reaction on dynamic bodies, prepare_guess */
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -367,6 +389,9 @@ int sph_upload(SphHandle *h, int field, const void *src, size_t bytes);
 int sph_particle_num(SphHandle *h);       /* container.particle_num[None] */
 int sph_fluid_particle_num(SphHandle *h); /* container.fluid_particle_num[None] */
 int sph_get_stats(SphHandle *h, SphStats *out);
+/* implicit viscosity: alpha, beta and error (base_solver.py:403, :428, :431) as the last launch that computes them left them on the
+   device, out[0..2].  A query of its own rather than SphStats fields: the statistics struct ends at pbf_recentred by contract. */
+int sph_get_cg_scalars(SphHandle *h, float *out);
 
 /* --- profiling (HIP events on the compute stream) -------------------------------------- */
 /* record a HIP event pair around every launch of `kernel_id` (-1: all kernels); accumulates. */

@@ -61,7 +61,7 @@ def load():
         for name in ("init_grid", "prefix_sum", "reorder_particles", "prepare_neighborhood_search",
                      "compute_rigid_particle_volume", "compute_density", "compute_gravity_acceleration",
                      "compute_surface_tension_acceleration", "compute_viscosity_acceleration_standard",
-                     "implicit_viscosity_solve", "compute_non_pressure_acceleration", "update_fluid_velocity",
+                     "implicit_viscosity_solve", "cg_prepare", "cg_iteration", "cg_end", "compute_non_pressure_acceleration", "update_fluid_velocity",
                      "update_fluid_position", "compute_pressure_acceleration", "enforce_domain_boundary_3D",
                      "prepare_emitter", "renew_rigid_particle_state", "wcsph_compute_pressure",
                      "dfsph_compute_alpha", "dfsph_compute_density_derivative", "dfsph_compute_density_star",

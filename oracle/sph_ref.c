@@ -215,6 +215,8 @@ double sphref_scalar(SphRef *s, const char *name) {
     if (!strcmp(name, "density_error")) return s->density_error;
     if (!strcmp(name, "pcisph_k")) return s->pcisph_k;
     if (!strcmp(name, "cg_error")) return s->cg_error;
+    if (!strcmp(name, "cg_alpha")) return s->cg_alpha;
+    if (!strcmp(name, "cg_beta")) return s->cg_beta;
     if (!strcmp(name, "total_time")) return s->total_time;
     if (!strcmp(name, "last_iter_div")) return s->last_iter_div;
     if (!strcmp(name, "last_iter_den")) return s->last_iter_den;
@@ -763,8 +765,9 @@ static void prepare_cg1(SphRef *s) {
     s->last_pairs += npairs_;
 }
 
-/* base_solver.py:509 implicit_viscosity_solve (and :318-:470 helpers) */
-void sphref_implicit_viscosity_solve(SphRef *s) {
+/* base_solver.py:509 implicit_viscosity_solve (and :318-:470 helpers) in its three pieces */
+/* :510-512: prepare_conjugate_gradient_solver1, compute_Ap, prepare_conjugate_gradient_solver2 */
+void sphref_cg_prepare(SphRef *s) {
     const int N = s->particle_num;
     prepare_cg1(s);
     compute_Ap(s);
@@ -773,44 +776,45 @@ void sphref_implicit_viscosity_solve(SphRef *s) {
             s->cg_r[p] = v3_sub(m3_mulv(&s->cg_diagnol_ii_inv[p], s->cg_b[p]), s->cg_Ap[p]);
             s->cg_p[p] = s->cg_r[p];
         }
-    float tol = 1000.0f;
-    int num_itr = 0;
-    const int max_itr = s->prm.fixed_iterations > 0 ? s->prm.fixed_iterations : 1000;
-    while ((s->prm.fixed_iterations > 0 || tol > 1e-6f) && num_itr < max_itr) { /* :445 conjugate_gradient_loop */
-        compute_Ap(s);
-        { /* :394 compute_cg_alpha */
-            float numerator = 0.0f, denominator = 0.0f;
-            for (int p = 0; p < N; p++)
-                if (s->particle_materials[p] == SPHREF_MAT_FLUID) {
-                    numerator += v3_norm_sqr(s->cg_r[p]);
-                    denominator += v3_dot(s->cg_p[p], s->cg_Ap[p]);
-                }
-            s->cg_alpha = denominator > 1e-18f ? numerator / denominator : 0.0f;
-        }
-        for (int p = 0; p < N; p++) /* :409 update_cg_x */
-            if (s->particle_materials[p] == SPHREF_MAT_FLUID)
-                s->cg_x[p] = v3_add(s->cg_x[p], v3_scale_l(s->cg_alpha, s->cg_p[p]));
-        { /* :415 update_cg_r_and_beta */
-            float numerator = 0.0f, denominator = 0.0f, err = 0.0f;
-            for (int p = 0; p < N; p++)
-                if (s->particle_materials[p] == SPHREF_MAT_FLUID) {
-                    v3 new_r = v3_sub(s->cg_r[p], v3_scale_l(s->cg_alpha, s->cg_Ap[p]));
-                    numerator += v3_norm_sqr(new_r);
-                    denominator += v3_norm_sqr(s->cg_r[p]);
-                    err += v3_norm_sqr(new_r);
-                    s->cg_r[p] = new_r;
-                }
-            s->cg_error = sqrtf(err);
-            s->cg_beta = denominator > 1e-18f ? numerator / denominator : 0.0f;
-        }
-        for (int p = 0; p < N; p++) /* :434 update_p */
-            if (s->particle_materials[p] == SPHREF_MAT_FLUID)
-                s->cg_p[p] = v3_add(s->cg_r[p], v3_scale_l(s->cg_beta, s->cg_p[p]));
-        tol = s->cg_error;
-        num_itr++;
+}
+
+/* one body of :445 conjugate_gradient_loop */
+void sphref_cg_iteration(SphRef *s) {
+    const int N = s->particle_num;
+    compute_Ap(s);
+    { /* :394 compute_cg_alpha */
+        float numerator = 0.0f, denominator = 0.0f;
+        for (int p = 0; p < N; p++)
+            if (s->particle_materials[p] == SPHREF_MAT_FLUID) {
+                numerator += v3_norm_sqr(s->cg_r[p]);
+                denominator += v3_dot(s->cg_p[p], s->cg_Ap[p]);
+            }
+        s->cg_alpha = denominator > 1e-18f ? numerator / denominator : 0.0f;
     }
-    s->last_iter_cg = num_itr;
-    s->last_err_cg = tol;
+    for (int p = 0; p < N; p++) /* :409 update_cg_x */
+        if (s->particle_materials[p] == SPHREF_MAT_FLUID)
+            s->cg_x[p] = v3_add(s->cg_x[p], v3_scale_l(s->cg_alpha, s->cg_p[p]));
+    { /* :415 update_cg_r_and_beta */
+        float numerator = 0.0f, denominator = 0.0f, err = 0.0f;
+        for (int p = 0; p < N; p++)
+            if (s->particle_materials[p] == SPHREF_MAT_FLUID) {
+                v3 new_r = v3_sub(s->cg_r[p], v3_scale_l(s->cg_alpha, s->cg_Ap[p]));
+                numerator += v3_norm_sqr(new_r);
+                denominator += v3_norm_sqr(s->cg_r[p]);
+                err += v3_norm_sqr(new_r);
+                s->cg_r[p] = new_r;
+            }
+        s->cg_error = sqrtf(err);
+        s->cg_beta = denominator > 1e-18f ? numerator / denominator : 0.0f;
+    }
+    for (int p = 0; p < N; p++) /* :434 update_p */
+        if (s->particle_materials[p] == SPHREF_MAT_FLUID)
+            s->cg_p[p] = v3_add(s->cg_r[p], v3_scale_l(s->cg_beta, s->cg_p[p]));
+}
+
+/* :514-517 */
+void sphref_cg_end(SphRef *s) {
+    const int N = s->particle_num;
     for (int p = 0; p < N; p++) /* :464 viscosity_update_velocity */
         if (s->particle_materials[p] == SPHREF_MAT_FLUID) s->particle_velocities[p] = s->cg_x[p];
     sphref_compute_viscosity_acceleration_standard(s); /* :515 */
@@ -818,6 +822,21 @@ void sphref_implicit_viscosity_solve(SphRef *s) {
         if (s->particle_materials[p] == SPHREF_MAT_FLUID) s->particle_velocities[p] = s->original_velocity[p];
     for (int p = 0; p < N; p++) /* :440 prepare_guess */
         if (s->particle_materials[p] == SPHREF_MAT_FLUID) s->cg_x[p] = v3_sub(s->cg_x[p], s->original_velocity[p]);
+}
+
+void sphref_implicit_viscosity_solve(SphRef *s) {
+    sphref_cg_prepare(s);
+    float tol = 1000.0f;
+    int num_itr = 0;
+    const int max_itr = s->prm.fixed_iterations > 0 ? s->prm.fixed_iterations : 1000;
+    while ((s->prm.fixed_iterations > 0 || tol > 1e-6f) && num_itr < max_itr) { /* :445 conjugate_gradient_loop */
+        sphref_cg_iteration(s);
+        tol = s->cg_error;
+        num_itr++;
+    }
+    s->last_iter_cg = num_itr;
+    s->last_err_cg = tol;
+    sphref_cg_end(s);
 }
 
 /* base_solver.py:190 */

@@ -78,6 +78,10 @@ void sphref_compute_gravity_acceleration(SphRef *s); /* :203 */
 void sphref_compute_surface_tension_acceleration(SphRef *s); /* :210 */
 void sphref_compute_viscosity_acceleration_standard(SphRef *s); /* :232 */
 void sphref_implicit_viscosity_solve(SphRef *s);  /* :509 */
+/* its three pieces: :510-512, one body of the loop :445, :514-517 */
+void sphref_cg_prepare(SphRef *s);
+void sphref_cg_iteration(SphRef *s);
+void sphref_cg_end(SphRef *s);
 void sphref_compute_non_pressure_acceleration(SphRef *s); /* :190 */
 void sphref_update_fluid_velocity(SphRef *s);     /* :643 */
 void sphref_update_fluid_position(SphRef *s);     /* :652 */

@@ -24,6 +24,8 @@ METHOD = {"wcsph": 0, "dfsph": 1, "pcisph": 2, "iisph": 3, "pbf": 4}
  F_CG_X, F_ORIG_POSITION, F_GHOST, F_DFSPH_KAPPA_NEXT, F_DFSPH_KAPPA_V_NEXT, F_DEBUG_CAPTURE,
  F_IISPH_DII, F_IISPH_AII, F_IISPH_DIJ_PJ, F_IISPH_SUM_I, F_PBF_OLD_POSITION, F_PBF_LAMBDA, F_RIGID_CONTACT_DN,
  F_RIGID_CONTACT_COUNT, F_NON_PRESSURE_ACCEL) = range(36)
+# implicit viscosity, download only: the CG vectors, D^-1 (n, 9) and the three parts of a split A p walk (3, n, 3)
+F_CG_B, F_CG_R, F_CG_P, F_CG_AP, F_CG_V0, F_CG_DINV, F_CG_AP_PARTS = range(36, 43)
 
 _FIELD_SPEC = {  # field -> (dtype, components)
     F_POSITION: (np.float32, 3), F_VELOCITY: (np.float32, 3), F_ACCELERATION: (np.float32, 3),
@@ -38,6 +40,8 @@ _FIELD_SPEC = {  # field -> (dtype, components)
     F_IISPH_DII: (np.float32, 3), F_IISPH_AII: (np.float32, 1), F_IISPH_DIJ_PJ: (np.float32, 3), F_IISPH_SUM_I: (np.float32, 1),
     F_PBF_OLD_POSITION: (np.float32, 3), F_PBF_LAMBDA: (np.float32, 1),
     F_RIGID_CONTACT_DN: (np.float32, 3), F_RIGID_CONTACT_COUNT: (np.float32, 1), F_NON_PRESSURE_ACCEL: (np.float32, 3),
+    F_CG_B: (np.float32, 3), F_CG_R: (np.float32, 3), F_CG_P: (np.float32, 3), F_CG_AP: (np.float32, 3), F_CG_V0: (np.float32, 3),
+    F_CG_DINV: (np.float32, 9), F_CG_AP_PARTS: (np.float32, 9),
 }
 
 # enum SphPhase
@@ -50,6 +54,9 @@ PH_PBFC_PREDICT, PH_PBFC_DENSITY_LAMBDA, PH_PBFC_DELTA, PH_PBFC_FINISH = 15, 16,
 PH_PCISPH_INIT, PH_PCISPH_RHO_STAR, PH_PCISPH_PRESSURE_ACCEL = 19, 20, 21
 # DFSPH: the end of a step behind the sort as the step runs it (density + alpha + first D rho / Dt in one walk, then the divergence loop)
 PH_DFSPH_ALPHA_DIVERGENCE = 22
+# implicit viscosity: the launches of the CG solve inside PH_NON_PRESSURE one pass each (PH_CG_UPDATE_P launches nothing where the step
+# folds the p update into the next A p pass)
+PH_CG_PREPARE, PH_CG_AP, PH_CG_UPDATE_XR, PH_CG_UPDATE_P, PH_CG_END = 23, 24, 25, 26, 27
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
@@ -344,6 +351,7 @@ _SIGNATURES = [
     ("sph_particle_num", C.c_int, [_VP]),
     ("sph_fluid_particle_num", C.c_int, [_VP]),
     ("sph_get_stats", C.c_int, [_VP, C.POINTER(SphStats)]),
+    ("sph_get_cg_scalars", C.c_int, [_VP, C.POINTER(C.c_float)]),
     ("sph_profile_enable", C.c_int, [_VP, C.c_int, C.c_int]),
     ("sph_profile_reset", C.c_int, [_VP]),
     ("sph_profile_read", C.c_int, [_VP, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -711,7 +719,7 @@ class Engine(NativeObject):
         n = self.particle_num
         out = np.empty((n, comp) if comp > 1 else (n,), dtype=dtype)
         self._chk(self.lib.sph_download(self.h, int(field), _ptr(out), out.nbytes), f"sph_download({field})")
-        return out
+        return out.reshape(3, n, 3) if field == F_CG_AP_PARTS else out
 
     def upload(self, field, arr):
         dtype, comp = _FIELD_SPEC[field]
@@ -722,6 +730,12 @@ class Engine(NativeObject):
         st = SphStats()
         self._chk(self.lib.sph_get_stats(self.h, C.byref(st)), "sph_get_stats")
         return struct_dict(st)
+
+    def cg_scalars(self):
+        """(alpha, beta, error) of the implicit-viscosity solve as the last launch left them on the device, f32"""
+        out = (C.c_float * 3)()
+        self._chk(self.lib.sph_get_cg_scalars(self.h, out), "sph_get_cg_scalars")
+        return np.array(out[:], np.float32)
 
     # -- profiling
     def profile_enable(self, kernel_id=-1, on=True):

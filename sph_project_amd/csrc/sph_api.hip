@@ -1166,6 +1166,8 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
             HIPCHK(h, hipMemsetAsync(s.contact_part, 0, sizeof(float4) * (size_t)s.cap, s.stream));
             ProfScope p(h, SPH_K_RIGID_CONTACT); h->L->rigid_contact(s);
         } break;
+        case SPH_PH_CG_PREPARE: case SPH_PH_CG_AP: case SPH_PH_CG_UPDATE_XR: case SPH_PH_CG_UPDATE_P: case SPH_PH_CG_END:
+            { int rc = cg_run_phase(h, phase); if (rc) return rc; } break;
         default: { int rc = method_run_phase(h, phase); if (rc) return rc; }
     }
     int rc = check_async(h); if (rc) return rc;
@@ -1202,6 +1204,18 @@ extern "C" int sph_get_stats(SphHandle *h, SphStats *out) {
     return SPH_OK;
 }
 
+extern "C" int sph_get_cg_scalars(SphHandle *h, float *out) {
+    if (!h || !out) return SPH_ERR_INVALID;
+    if (!h->prm.viscosity_implicit) return fail(h, SPH_ERR_UNSUPPORTED, "sph_get_cg_scalars: no implicit viscosity on this handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    State &s = h->st;
+    HIPCHK(h, hipStreamSynchronize(s.stream));
+    float red[8];
+    HIPCHK(h, hipMemcpy(red, &s.scal->red[0], sizeof(red), hipMemcpyDeviceToHost));
+    out[0] = red[4]; out[1] = red[5]; out[2] = red[3];   // cg_alpha, cg_beta, cg_error
+    return SPH_OK;
+}
+
 static const float4 *vec_field(SphHandle *h, int field) {
     State &s = h->st;
     switch (field) {
@@ -1218,6 +1232,11 @@ static const float4 *vec_field(SphHandle *h, int field) {
         case SPH_F_PBF_OLD_POSITION: return h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT ? nullptr : s.pbf_old;   // (x_old, sorted cell id); consistent variant: posv is the old position
         case SPH_F_RIGID_CONTACT_DN: case SPH_F_RIGID_CONTACT_COUNT: return s.contact_part;   // (sum of depth * n, contacts)
         case SPH_F_NON_PRESSURE_ACCEL: return s.acc_np;   // (PCISPH only; null otherwise)
+        case SPH_F_CG_B: return s.cg_b;     // (implicit viscosity only; null otherwise)
+        case SPH_F_CG_R: return s.cg_r;
+        case SPH_F_CG_P: return s.cg_p;
+        case SPH_F_CG_AP: return s.cg_Ap;
+        case SPH_F_CG_V0: return s.cg_v0;
         default: return nullptr;
     }
 }
@@ -1249,7 +1268,8 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
     const bool is_vec3 = field == SPH_F_POSITION || field == SPH_F_VELOCITY || field == SPH_F_ACCELERATION ||
                          field == SPH_F_PRESSURE_ACCEL || field == SPH_F_PREDICTED_VEL || field == SPH_F_PREDICTED_POS ||
                          field == SPH_F_CG_X || field == SPH_F_ORIG_POSITION || field == SPH_F_IISPH_DII || field == SPH_F_IISPH_DIJ_PJ ||
-                         field == SPH_F_PBF_OLD_POSITION || field == SPH_F_RIGID_CONTACT_DN || field == SPH_F_NON_PRESSURE_ACCEL;
+                         field == SPH_F_PBF_OLD_POSITION || field == SPH_F_RIGID_CONTACT_DN || field == SPH_F_NON_PRESSURE_ACCEL ||
+                         (field >= SPH_F_CG_B && field <= SPH_F_CG_V0);
     if (is_vec3) {
         const float4 *src = vec_field(h, field);
         if (!src) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);
@@ -1259,6 +1279,30 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
         float *d = (float *)dst;
         const int ix0 = h->inv[0], ix1 = h->inv[1], ix2 = h->inv[2];   // library frame -> scene frame
         for (size_t i = 0; i < n; ++i) { const float v[3] = {tmp[i].x, tmp[i].y, tmp[i].z}; d[3 * i] = v[ix0]; d[3 * i + 1] = v[ix1]; d[3 * i + 2] = v[ix2]; }
+        return SPH_OK;
+    }
+    if (field == SPH_F_CG_DINV) {   // library frame -> scene frame on both indices
+        if (!s.cg_dinv) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);
+        if (bytes != n * 36) return fail(h, SPH_ERR_INVALID, "download: field %d needs %zu bytes, got %zu", field, n * 36, bytes);
+        std::vector<float> tmp(n * 9);
+        HIPCHK(h, hipMemcpy(tmp.data(), s.cg_dinv, n * 36, hipMemcpyDeviceToHost));
+        float *d = (float *)dst;
+        for (size_t i = 0; i < n; ++i)
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) d[9 * i + 3 * a + b] = tmp[9 * i + 3 * h->inv[a] + h->inv[b]];
+        return SPH_OK;
+    }
+    if (field == SPH_F_CG_AP_PARTS) {
+        if (!s.cg_part) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);
+        if (bytes != n * 36) return fail(h, SPH_ERR_INVALID, "download: field %d needs %zu bytes, got %zu", field, n * 36, bytes);
+        std::vector<float4> tmp(n);
+        float *d = (float *)dst;
+        const int ix0 = h->inv[0], ix1 = h->inv[1], ix2 = h->inv[2];
+        for (int g = 0; g < 3; ++g) {   // the parts lie s.cap apart (CgApPass::part_stride)
+            HIPCHK(h, hipMemcpy(tmp.data(), s.cg_part + (size_t)g * s.cap, n * sizeof(float4), hipMemcpyDeviceToHost));
+            float *dg = d + (size_t)g * n * 3;
+            for (size_t i = 0; i < n; ++i) { const float v[3] = {tmp[i].x, tmp[i].y, tmp[i].z}; dg[3 * i] = v[ix0]; dg[3 * i + 1] = v[ix1]; dg[3 * i + 2] = v[ix2]; }
+        }
         return SPH_OK;
     }
     if (field == SPH_F_REST_VOLUME || field == SPH_F_MASS || field == SPH_F_IISPH_AII || field == SPH_F_IISPH_SUM_I ||

@@ -555,6 +555,7 @@ struct State {
     int cg_nocombine = 0;      // the last A p pass was split and left its dot-product shares itself: the x / r update adds the parts up (no k_cg_ap_combine)
     int cg_split = 0;          // this solve splits its A p passes (few fluid particles: see implicit_viscosity_non_pressure)
     int cg_parity = 0;         // which of the two |r|^2 partial arrays the next x / r update reads
+    int cg_first = 1;          // the next A p pass of the loop is its first: no p update to fold into it (sph_cg_steps.hpp)
     // reductions
     float *red_partial = nullptr;  // per-block partial sums
     int red_blocks = 0;

@@ -161,7 +161,7 @@ def add_wrenches(a, b):
     return {k: a.get(k, 0.0) + b.get(k, 0.0) for k in set(a) | set(b)}
 
 
-def non_pressure_f64(x, v, rho, mass, vol, mat, is_dynamic, obj, com, params, mutant=None, rho_bound=None):
+def non_pressure_f64(x, v, rho, mass, vol, mat, is_dynamic, obj, com, params, mutant=None, rho_bound=None, visc_v=None):
     """compute_non_pressure_acceleration (base_solver.py:190-200) for viscosityMethod "standard", fluid particles i:
       gravity (:203-207)            a_i  = g
       surface tension (:210-229)    a_i -= st / m_i m_j R W(r)        fluid j; W(diameter) in place of W(r) where R.R <= diameter^2
@@ -174,7 +174,8 @@ def non_pressure_f64(x, v, rho, mass, vol, mat, is_dynamic, obj, com, params, mu
                                     force_j = -m_i a_ij), torque_j = (x_j - com_j) x force_j.
     R = x_i - x_j, v_ij = v_i - v_j, h = support radius.  `rho`: the density the viscous term reads (module docstring); per
     particle f32 / f64, with `rho_bound` (per particle, default 0) the bound of its error -- every term that divides by a density
-    then carries |term| rho_bound / rho on top.  `mass`: particle_masses; `com`: (bodies, 3) centres of mass indexed by object id.
+    then carries |term| rho_bound / rho on top.  `visc_v` (default: v): the velocity the viscous term reads -- the end of the implicit
+    solve (base_solver.py:514-516) evaluates the formula with the solved velocities of the fluid rows.  `mass`: particle_masses; `com`: (bodies, 3) centres of mass indexed by object id.
     params: dict(h, rho0, diameter, st, mu, mu_b, g, dim).
     Returns dict: a, mag, mag_amp, extra (n, 3; rows of non-fluid particles zero) -- bound(a) = C1 mag + C2 mag_amp + extra;
     st_mag, visc_mag (n, 3) the two parts of mag; n_terms (n,) summed terms of the longer accumulator; pairs: the pair arrays
@@ -211,7 +212,8 @@ def non_pressure_f64(x, v, rho, mass, vol, mat, is_dynamic, obj, com, params, mu
     st_amp = _sum(i, n, (c_st * w_amp)[:, None] * aR)
     # ---- viscosity
     s, s_amp = kernel_grad_scale(r, h)
-    dv = v[i] - v[j]
+    vv = v if visc_v is None else np.asarray(visc_v, np.float64)
+    dv = vv[i] - vv[j]
     v_xy = (dv * R).sum(axis=1)
     v_xy_mag = (np.abs(dv) * aR).sum(axis=1)
     m_ij = m[i] if mutant == "mij_is_mi" else 0.5 * (m[i] + m[j])
@@ -334,17 +336,21 @@ BODY = 2                 # object id of the rigid cube
 BODY_VEL, BODY_ANGVEL = (0.1, -0.2, 0.05), (0.5, 1.5, -0.8)
 
 
-def scene(method, rigid=True, masses=2, seed=7, noise=1.0, converge=0.0, dt=4e-4):
+def scene(method, rigid=True, masses=2, seed=7, noise=1.0, converge=0.0, dt=4e-4, viscosity=1.0, viscosity_b=4.0,
+          viscosity_method="standard"):
     """dict(cfg, pd, batches, com, params): `batches` in insertion order (box, fluid objects 0 and 1, the cube), each with pos /
     vel / density / material / is_dynamic / object_id; `pd` the flat parameters of both the engine and the oracle.  rigid=False:
     the all-fluid twin (same block, no box, no body); masses=1: both fluid objects of density 1000.  noise, converge, dt: the
     velocity noise in units of 0.5 m/s, a velocity -converge (x - centre of the block) on top (1 / s) and the time step -- the
-    defaults are the scene of the non-pressure tests; tests/pressure_solve_terms.py compresses the block with them."""
+    defaults are the scene of the non-pressure tests; tests/pressure_solve_terms.py compresses the block with them.  viscosity,
+    viscosity_b, viscosity_method: mu, mu_b and the method (tests/implicit_viscosity_terms.py: "implicit", with mu and mu_b raised
+    until D is far from the identity)."""
     from sph_project_amd import scene as S
     from sph_project_amd.product import dam_break_scene, scene_particles
     lo = np.array([0.085, 0.085, 0.15])
     cfg = dam_break_scene(method=method, domain_end=(0.48, 0.44, 0.44), start=(0, 0, 0), end=(0, 0, 0), add_domain_box=rigid,
-                          particleSpacing=SPACING, viscosity=1.0, viscosity_b=4.0, dt=dt)
+                          particleSpacing=SPACING, viscosity=viscosity, viscosity_b=viscosity_b, dt=dt,
+                          viscosity_method=viscosity_method)
     cfg["FluidBlocks"] = []
     c, geo, batches = scene_particles(cfg)
     sol = S.derive_solver_constants(c)

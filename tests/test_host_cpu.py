@@ -67,12 +67,13 @@ RETIRED_SWITCHES = (
 
 def test_test_hooks_live_in_their_own_library():
     """the pre-round-5 single halo header (a protocol with a known race), the consumer stall, the injected step failure and
-    the rank that cannot set the push transport up are compiled into libsph_hip_testhooks.so only (-DSPH_TEST_HOOKS); the production
+    the rank that cannot set the push transport up, and the two switches of the implicit-viscosity launch forms are compiled into libsph_hip_testhooks.so only (-DSPH_TEST_HOOKS); the production
     library does not even contain the switches' names.  Nor does it contain the name of any retired switch."""
     here = os.path.join(ROOT, "sph_project_amd")
     prod = open(os.path.join(here, "libsph_hip.so"), "rb").read()
     hooks = open(os.path.join(here, "libsph_hip_testhooks.so"), "rb").read()
-    for name in (b"SPH_TEST_SINGLE_HEADER", b"SPH_TEST_HALO_DELAY_US", b"SPH_TEST_FAIL_STEP", b"SPH_COMM_TEST_FAIL_PUSH_RANK"):
+    for name in (b"SPH_TEST_SINGLE_HEADER", b"SPH_TEST_HALO_DELAY_US", b"SPH_TEST_FAIL_STEP", b"SPH_COMM_TEST_FAIL_PUSH_RANK",
+                 b"SPH_TEST_CG_SPLIT_LIMIT", b"SPH_TEST_CG_SEPARATE_P"):
         assert name not in prod and name in hooks, name
     for name in RETIRED_SWITCHES:
         word = re.compile(re.escape(name.encode()) + rb"(?![A-Z0-9_])")   # the whole name, not a prefix of a longer one
