@@ -579,6 +579,51 @@ int sph_surface_post_stats(SphSurface *s, SphSurfacePostStats *out);
    post-processing. */
 int sph_surface_download_post(SphSurface *s, int32_t *offsets, int32_t *neighbours, float *weights);
 
+/* --- surface reconstruction with anisotropic kernels ----------------------------------------------------------------- */
+/* Opt-in; off by default, and with the mode off every kernel launched and every byte written is what it is without this section.  The
+   isotropic kernel's support h = 7 r meshes a one-particle sheet 4.2 r thick; here every particle gets a kernel shrunk along the
+   directions in which its neighbourhood is thin (after Yu & Turk 2013, without their position smoothing: centres are not moved).  The
+   project's own definition, with h, W, e, bricks, marching cubes and every order of section 14; for every input particle i:
+     N_i = the number of k != i with |x_k - x_i| < h;  w_ik = 1 - (|x_k - x_i| / h)^3 over the same set, self included (w = 1);
+     mean_i = sum w_ik x_k / sum w_ik;  C_i = sum w_ik (x_k - mean_i)(x_k - mean_i)^T / sum w_ik (accumulated relative to x_i);
+     C_i = sum_k lambda_k v_k v_k^T, lambda_1 the largest (a fixed number of cyclic Jacobi sweeps in f32);
+     N_i < min_neighbours or lambda_1 <= 0:  A_i = I / sparse_scale (the isolated rule);
+     else a_k = 1 / max(lambda_k / lambda_1, 1 / max_ratio), A_i = sum a_k v_k v_k^T: symmetric, every a_k in [1, max_ratio], so
+       kernels only shrink and kernel i vanishes outside the ball of radius h around x_i;
+     w_j(x) = det(A_j) W(|A_j (x - x_j)|);  V_j = 1 / sum_k w_k(x_j);  phi(x) = sum_j V_j w_j(x);  normals -grad phi / |grad phi| with
+       grad w_j = det(A_j) W'(|y|) / |y| A_j y, y = A_j (x - x_j).
+   A = I everywhere gives section 14's V_j bit for bit.  The mesh stays a function of the particle set, bit for bit, in both builds; no
+   float atomics.  New device buffers (36 bytes per particle) count under memory_cap_bytes (SPH_ERR_CAPACITY before they are
+   allocated).  The smoothing of DESIGN.md 16 runs on the anisotropic mesh unchanged (its normals from the anisotropic field). */
+typedef struct {
+    int32_t enabled;         /* 0: off */
+    int32_t min_neighbours;  /* below this N_i the isolated rule applies (25) */
+    double max_ratio;        /* the largest a_k: >= 1 (2) */
+    double sparse_scale;     /* the isolated rule's support in multiples of h: in (0, 1] (0.5) */
+} SphSurfaceAnisoParams;
+
+typedef struct {
+    int64_t sparse_particles;   /* particles under the isolated rule in the last reconstruction */
+    int64_t clamped_particles;  /* the others with at least one lambda_k / lambda_1 below 1 / max_ratio */
+    double ms_moments;          /* HIP events: N_i, covariance, eigen-decomposition and clamp */
+    double ms_volume;           /* V_j.  Both lie inside SphSurfaceStats.ms_bin; the anisotropic field is timed in ms_field */
+} SphSurfaceAnisoStats;
+
+/* applies from the next reconstruction on, through both entry points; NULL or enabled == 0 switches the mode off.  SPH_ERR_INVALID: a
+   negative min_neighbours, a max_ratio below 1 or not finite (in f32 too), a sparse_scale outside (0, 1] or with 1 / scale not finite in
+   f32 */
+int sph_surface_set_anisotropy(SphSurface *s, const SphSurfaceAnisoParams *params_or_NULL);
+/* zeros after a reconstruction without the mode */
+int sph_surface_anisotropy_stats(SphSurface *s, SphSurfaceAnisoStats *out);
+/* the last reconstruction's particles in the binned key order: xyz f32[n][3], A6 f32[n][6] = (xx, xy, xz, yy, yz, zz) of A_i,
+   neighbours i32[n] = N_i, V f32[n]; n = SphSurfaceStats.particles; any may be NULL.  SPH_ERR_INVALID when that reconstruction ran
+   without the mode. */
+int sph_surface_download_anisotropy(SphSurface *s, float *xyz, float *A6, int32_t *neighbours, float *V);
+/* the device's eigen and clamp routine, compiled from the same source, run on the host (no GPU involved): A6[i] from the covariance
+   C6[i] (same six-entry layout) and neighbours[i] (NULL: every particle has enough); p->enabled is ignored.  SPH_ERR_INVALID as the
+   setter. */
+int sph_surface_aniso_matrix_host(const float *C6, int64_t n, const int32_t *neighbours, const SphSurfaceAnisoParams *p, float *A6);
+
 /* --- particle rendering: particles -> one RGB frame ------------------------------------------------------------- */
 /* replaces the GGUI frame of run_simulation.py:116-135 (scene.particles(x_vis_buffer, radius=dx, per_vertex_color=...), scene.lines of
    the domain box, scene.point_light, window.save_image -> raw_view.png).  Not GGUI's shaders: the image is defined here and in

@@ -146,6 +146,14 @@ class SphSurfacePostStats(C.Structure):
     ]
 
 
+class SphSurfaceAnisoParams(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("min_neighbours", C.c_int32), ("max_ratio", C.c_double), ("sparse_scale", C.c_double)]
+
+
+class SphSurfaceAnisoStats(C.Structure):
+    _fields_ = [("sparse_particles", C.c_int64), ("clamped_particles", C.c_int64), ("ms_moments", C.c_double), ("ms_volume", C.c_double)]
+
+
 class SphRenderParams(C.Structure):
     _fields_ = [
         ("width", C.c_int32), ("height", C.c_int32), ("eye", C.c_double * 3), ("target", C.c_double * 3), ("up", C.c_double * 3),
@@ -383,6 +391,10 @@ _SIGNATURES = [
     ("sph_surface_set_postprocess", C.c_int, [_VP, C.POINTER(SphSurfacePostParams)]),
     ("sph_surface_post_stats", C.c_int, [_VP, C.POINTER(SphSurfacePostStats)]),
     ("sph_surface_download_post", C.c_int, [_VP, _VP, _VP, _VP]),
+    ("sph_surface_set_anisotropy", C.c_int, [_VP, C.POINTER(SphSurfaceAnisoParams)]),
+    ("sph_surface_anisotropy_stats", C.c_int, [_VP, C.POINTER(SphSurfaceAnisoStats)]),
+    ("sph_surface_download_anisotropy", C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    ("sph_surface_aniso_matrix_host", C.c_int, [_VP, C.c_int64, _VP, C.POINTER(SphSurfaceAnisoParams), _VP]),
     ("sph_render_create", C.c_int, [C.POINTER(SphRenderParams), C.POINTER(_VP)]),
     ("sph_render_destroy", None, [_VP]),
     ("sph_render_last_error", C.c_char_p, [_VP]),

@@ -226,6 +226,17 @@ struct SurfDev {
     int *scan_tmp;                     // tile sums of surf_scan
     hipStream_t stream;
 };
+// Anisotropic kernels of the surface reconstruction (sph_surface_aniso.hpp): the clamp's constants and the per-particle
+// kernel matrices, in the binned key order of SurfDev::xs.  A symmetric 3x3 is kept as (xx, xy, xz, yy, yz, zz).
+struct SurfAnisoPrm { int min_nb; float inv_ratio, inv_scale; };   // min_neighbours, 1 / max_ratio, 1 / sparse_scale
+struct SurfAniso {
+    SurfAnisoPrm prm;
+    double h;            // the support in double (the moments pass)
+    float4 *am;          // [n] A: xx, xy, xz, yy
+    float4 *an;          // [n] A: yz, zz; det A; the bits of N_i
+    float *vol;          // [n] V_j = 1 / sum_k det A_k W(|A_k (x_j - x_k)|)
+    int *cnt;            // [2] particles under the sparse rule, particles with a clamped ratio
+};
 // Surface post-processing (sph_surface_post.hpp): the mesh sizes and the buffers of the stage
 struct SurfPost {
     int nv, nt;
@@ -729,6 +740,11 @@ struct Launch {
     void (*surf_count)(SurfDev &);              // classify cubes and edges, per-brick vertex / triangle counts and their scans
     void (*surf_emit)(SurfDev &);               // vertices and triangles
     void (*surf_normals)(SurfDev &, int nv);    // -grad phi / |grad phi| at every vertex
+    // anisotropic kernels (sph_surface_aniso.hpp)
+    void (*surf_aniso_moments)(SurfDev &, SurfAniso &);           // N_i, weighted covariance, eigen-decomposition and clamp -> A_i, det A_i
+    void (*surf_aniso_volume)(SurfDev &, SurfAniso &);            // V_j from the anisotropic kernels of the 27 cells
+    void (*surf_field_aniso)(SurfDev &, SurfAniso &);             // surf_field with w_j(x) = det A_j W(|A_j (x - x_j)|)
+    void (*surf_normals_aniso)(SurfDev &, SurfAniso &, int nv);   // surf_normals with the analytic gradient of w_j
     // surface post-processing (sph_surface_post.hpp)
     void (*surf_post_adjacency)(SurfDev &, SurfPost &);           // slots, sort + dedup, scan of the unique counts (cnt[nv] = entries)
     void (*surf_post_compact)(SurfDev &, SurfPost &);             // CSR neighbours into adj

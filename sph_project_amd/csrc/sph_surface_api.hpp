@@ -1,14 +1,17 @@
 // sph_surface_api.hpp -- the SphSurface object of include/sph_hip.h: its buffers under the memory cap, the pass sequence with its three
 // host reads (coarse bounds, active bricks, vertex / triangle totals) and the stage events.  Host code, included at the end of
-// sph_api.hip; the kernels are in sph_surface.hpp, the method in DESIGN.md 14.
+// sph_api.hip; the kernels are in sph_surface.hpp (anisotropic kernels: sph_surface_aniso.hpp), the method in DESIGN.md 14 and 29.
 #pragma once
 #include <algorithm>
 #include <climits>
+#include "sph_surface_aniso_eig.hpp"
 
 enum SurfBufId { SB_XIN, SB_XTMP, SB_XS, SB_PCELL, SB_PSLOT, SB_CELL_START, SB_FLAG, SB_BRICK_ID, SB_BRICK_CELL, SB_PHI, SB_EDGE, SB_VBASE,
                  SB_TBASE, SB_VERT, SB_NRM, SB_TRI, SB_SMALL, SB_SCAN,
                  // post-processing
-                 SB_ADJ_RAW, SB_ADJ_CNT, SB_ADJ_SLOT, SB_ADJ, SB_PCOUNT, SB_WEIGHT, SB_WORK_A, SB_WORK_B, SB_COUNT_ };
+                 SB_ADJ_RAW, SB_ADJ_CNT, SB_ADJ_SLOT, SB_ADJ, SB_PCOUNT, SB_WEIGHT, SB_WORK_A, SB_WORK_B,
+                 // anisotropic kernels
+                 SB_ANISO_M, SB_ANISO_N, SB_ANISO_V, SB_COUNT_ };
 
 struct SphSurface : DevObj {   // clk[0]: the reconstruction's stages, clk[1]: the post-processing's
     SphSurfaceParams prm;
@@ -23,6 +26,11 @@ struct SphSurface : DevObj {   // clk[0]: the reconstruction's stages, clk[1]: t
     bool have_post = false;   // the last reconstruction built the adjacency
     bool have_weights = false;
     SphSurfacePostStats post_stats{};
+    SphSurfaceAnisoParams aniso{0, 25, 2.0, 0.5};   // off
+    SurfAniso a{};
+    StageClock aclk;             // moments + eigen, V_j
+    bool have_aniso = false;     // the last reconstruction ran with anisotropic kernels
+    SphSurfaceAnisoStats aniso_stats{};
 };
 
 static size_t surf_total(const SphSurface *s) {
@@ -65,6 +73,9 @@ extern "C" int sph_surface_create(const SphSurfaceParams *params, SphSurface **o
     SphSurface *s = new SphSurface();
     s->prm = p;
     { int rc = devobj_open(s, "sph_surface_create", dev, p.fast_math); if (rc) { sph_surface_destroy(s); return rc; } }
+    s->aclk.stream = s->stream;
+    for (int k = 0; k < 3; ++k)
+        if (hipEventCreate(&s->aclk.ev[k]) != hipSuccess) { sph_surface_destroy(s); return fail(nullptr, SPH_ERR_HIP, "sph_surface_create: event"); }
     SurfDev &d = s->d;
     d.h = (float)h;
     d.h2 = (float)(h * h);
@@ -84,6 +95,7 @@ extern "C" int sph_surface_create(const SphSurfaceParams *params, SphSurface **o
 extern "C" void sph_surface_destroy(SphSurface *s) {
     if (!s) return;
     devobj_close(s, s->buf, SB_COUNT_);
+    for (hipEvent_t e : s->aclk.ev) if (e) hipEventDestroy(e);
     delete s;
 }
 
@@ -99,14 +111,17 @@ static int surf_run(SphSurface *s, int n) {
     d.n = n;
     d.nb = 0;
     d.cmin[0] = d.cmin[1] = d.cmin[2] = 0;
+    const bool aniso = s->aniso.enabled != 0;
     if (n == 0) {   // no particle: the empty mesh (and, with the post stage on, its empty adjacency)
         HIPCHK(s, hipStreamSynchronize(st));
         s->have_mesh = true;
+        s->have_aniso = aniso;
         s->have_post = surf_post_on(s);
         s->stats.bytes_allocated = (int64_t)surf_total(s);
         return SPH_OK;
     }
-    // SB_SMALL, 16 int slots: [0, 7) bounds, [8] counter (compaction), [10, 12) pairs (u64), [12] largest degree (post-processing)
+    // SB_SMALL, 16 int slots: [0, 7) bounds, [8] counter (compaction), [10, 12) pairs (u64), [12] largest degree (post-processing),
+    // [13, 15) sparse / clamped particles (anisotropic kernels)
     SURF_ENSURE(s, SB_SMALL, 64, "counters");
     d.bounds = (int *)s->buf[SB_SMALL].p;
     d.counter = d.bounds + 8;
@@ -138,7 +153,26 @@ static int surf_run(SphSurface *s, int n) {
     d.pcell = (int *)s->buf[SB_PCELL].p; d.pslot = (int *)s->buf[SB_PSLOT].p;
     d.cell_start = (int *)s->buf[SB_CELL_START].p; d.flag = (int *)s->buf[SB_FLAG].p; d.brick_id = (int *)s->buf[SB_BRICK_ID].p;
     d.scan_tmp = (int *)s->buf[SB_SCAN].p;
-    s->L->surf_bin(d);   // (leaves xs = the key-ordered particles with V)
+    SurfAniso &a = s->a;
+    if (aniso) {
+        SURF_ENSURE(s, SB_ANISO_M, sizeof(float4) * (size_t)n, "kernel matrices");
+        SURF_ENSURE(s, SB_ANISO_N, sizeof(float4) * (size_t)n, "kernel matrices");
+        SURF_ENSURE(s, SB_ANISO_V, sizeof(float) * (size_t)n, "kernel matrices");
+        a.h = 2.0 * s->prm.smoothing_length * s->prm.radius;
+        a.prm.min_nb = s->aniso.min_neighbours;
+        a.prm.inv_ratio = (float)(1.0 / s->aniso.max_ratio);
+        a.prm.inv_scale = (float)(1.0 / s->aniso.sparse_scale);
+        a.am = (float4 *)s->buf[SB_ANISO_M].p; a.an = (float4 *)s->buf[SB_ANISO_N].p; a.vol = (float *)s->buf[SB_ANISO_V].p;
+        a.cnt = d.bounds + 13;
+    }
+    s->L->surf_bin(d);   // (leaves xs = the key-ordered particles with the isotropic V)
+    if (aniso) {
+        HIPCHK(s, s->aclk.mark(0));
+        s->L->surf_aniso_moments(d, a);
+        HIPCHK(s, s->aclk.mark(1));
+        s->L->surf_aniso_volume(d, a);
+        HIPCHK(s, s->aclk.mark(2));
+    }
     HIPCHK(s, s->clk[0].mark(1));
     s->L->surf_flags(d);
     HIPCHK(s, s->clk[0].mark(2));
@@ -155,7 +189,8 @@ static int surf_run(SphSurface *s, int n) {
     if ((size_t)nb + 1 > (size_t)(G + 1)) return fail(s, SPH_ERR_INVALID, "surface: internal brick count");
     d.brick_cell = (int *)s->buf[SB_BRICK_CELL].p; d.phi = (float *)s->buf[SB_PHI].p; d.edge = (unsigned *)s->buf[SB_EDGE].p;
     d.vbase = (int *)s->buf[SB_VBASE].p; d.tbase = (int *)s->buf[SB_TBASE].p;
-    s->L->surf_field(d);
+    if (aniso) s->L->surf_field_aniso(d, a);
+    else s->L->surf_field(d);
     HIPCHK(s, s->clk[0].mark(3));
     s->L->surf_count(d);
     int tot[2] = {0, 0};
@@ -171,10 +206,15 @@ static int surf_run(SphSurface *s, int n) {
     s->L->surf_emit(d);
     HIPCHK(s, s->clk[0].mark(4));
     // (smoothed positions get their normals in the post stage: none here then, and ms_normals ~ 0)
-    if (s->prm.normals && !(surf_post_on(s) && s->post.mesh_smoothing_iters > 0)) s->L->surf_normals(d, tot[0]);
+    if (s->prm.normals && !(surf_post_on(s) && s->post.mesh_smoothing_iters > 0)) {
+        if (aniso) s->L->surf_normals_aniso(d, a, tot[0]);
+        else s->L->surf_normals(d, tot[0]);
+    }
     HIPCHK(s, s->clk[0].mark(5));
     unsigned long long pairs = 0;
+    int acnt[2] = {0, 0};
     HIPCHK(s, hipMemcpyAsync(&pairs, d.pairs, sizeof(pairs), hipMemcpyDeviceToHost, st));
+    if (aniso) HIPCHK(s, hipMemcpyAsync(acnt, a.cnt, sizeof(acnt), hipMemcpyDeviceToHost, st));
     HIPCHK(s, hipStreamSynchronize(st));
     HIPCHK(s, hipGetLastError());
     if (surf_post_on(s)) { const int rc = surf_post(s, tot[0], tot[1]); if (rc) return rc; }
@@ -187,6 +227,10 @@ static int surf_run(SphSurface *s, int n) {
     const StageClock &c = s->clk[0];
     o.ms_bin = c.ms(0, 1); o.ms_bricks = c.ms(1, 2); o.ms_field = c.ms(2, 3);
     o.ms_mesh = c.ms(3, 4); o.ms_normals = c.ms(4, 5); o.ms_total = c.ms(0, 5);
+    if (aniso) {
+        s->have_aniso = true;
+        s->aniso_stats = SphSurfaceAnisoStats{acnt[0], acnt[1], s->aclk.ms(0, 1), s->aclk.ms(1, 2)};
+    }
     return SPH_OK;
 }
 
@@ -198,6 +242,8 @@ static void surf_begin(SphSurface *s) {
     s->stats.B = s->d.B;
     s->have_post = s->have_weights = false;
     s->post_stats = SphSurfacePostStats{};
+    s->have_aniso = false;
+    s->aniso_stats = SphSurfaceAnisoStats{};
 }
 
 extern "C" int sph_surface_reconstruct(SphSurface *s, const float *xyz, int64_t n) {
@@ -307,7 +353,10 @@ static int surf_post(SphSurface *s, int nv, int nt) {
     HIPCHK(s, s->clk[1].mark(2));
     s->L->surf_post_smooth(d, p, q.mesh_smoothing_iters);
     HIPCHK(s, s->clk[1].mark(3));
-    if (s->prm.normals && q.mesh_smoothing_iters > 0) s->L->surf_normals(d, nv);   // -grad phi at the smoothed positions
+    if (s->prm.normals && q.mesh_smoothing_iters > 0) {   // -grad phi at the smoothed positions
+        if (s->aniso.enabled) s->L->surf_normals_aniso(d, s->a, nv);
+        else s->L->surf_normals(d, nv);
+    }
     HIPCHK(s, s->clk[1].mark(4));
     s->L->surf_post_nsmooth(d, p, q.normals_smoothing_iters);
     HIPCHK(s, s->clk[1].mark(5));
@@ -355,6 +404,65 @@ extern "C" int sph_surface_download_post(SphSurface *s, int32_t *offsets, int32_
     if (weights) {
         if (s->have_weights) { if (nv) HIPCHK(s, hipMemcpy(weights, s->p.w, sizeof(float) * nv, hipMemcpyDeviceToHost)); }
         else for (size_t i = 0; i < nv; ++i) weights[i] = 1.0f;
+    }
+    return SPH_OK;
+}
+
+// --- anisotropic kernels ----------------------------------------------------------------------------------------------
+static const char *surf_aniso_check(const SphSurfaceAnisoParams &q) {
+    if (q.min_neighbours < 0) return "min_neighbours must not be negative";
+    if (!std::isfinite(q.max_ratio) || !std::isfinite((float)q.max_ratio) || !(q.max_ratio >= 1.0)) return "max_ratio must be finite and >= 1";
+    if (!std::isfinite(q.sparse_scale) || !(q.sparse_scale > 0.0) || !(q.sparse_scale <= 1.0) || !std::isfinite((float)(1.0 / q.sparse_scale)))
+        return "sparse_scale must lie in (0, 1]";
+    return nullptr;
+}
+
+extern "C" int sph_surface_set_anisotropy(SphSurface *s, const SphSurfaceAnisoParams *params_or_NULL) {
+    if (!s) return SPH_ERR_INVALID;
+    if (!params_or_NULL || !params_or_NULL->enabled) { s->aniso.enabled = 0; return SPH_OK; }
+    if (const char *why = surf_aniso_check(*params_or_NULL)) return fail(s, SPH_ERR_INVALID, "sph_surface_set_anisotropy: %s", why);
+    s->aniso = *params_or_NULL;
+    s->aniso.enabled = 1;
+    return SPH_OK;
+}
+
+extern "C" int sph_surface_anisotropy_stats(SphSurface *s, SphSurfaceAnisoStats *out) {
+    if (!s || !out) return SPH_ERR_INVALID;
+    *out = s->aniso_stats;
+    return SPH_OK;
+}
+
+extern "C" int sph_surface_download_anisotropy(SphSurface *s, float *xyz, float *A6, int32_t *neighbours, float *V) {
+    if (!s) return SPH_ERR_INVALID;
+    if (!s->have_mesh || !s->have_aniso)
+        return fail(s, SPH_ERR_INVALID, "sph_surface_download_anisotropy: the last reconstruction ran without anisotropic kernels");
+    HIPCHK(s, hipSetDevice(s->device));
+    const size_t n = (size_t)s->stats.particles;
+    if (!n) return SPH_OK;
+    std::vector<float4> t(n), u(n);
+    if (xyz) {
+        HIPCHK(s, hipMemcpy(t.data(), s->d.xs, sizeof(float4) * n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) { xyz[3 * i] = t[i].x; xyz[3 * i + 1] = t[i].y; xyz[3 * i + 2] = t[i].z; }
+    }
+    if (A6 || neighbours) {
+        HIPCHK(s, hipMemcpy(t.data(), s->a.am, sizeof(float4) * n, hipMemcpyDeviceToHost));
+        HIPCHK(s, hipMemcpy(u.data(), s->a.an, sizeof(float4) * n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) {
+            if (A6) { float *o = A6 + 6 * i; o[0] = t[i].x; o[1] = t[i].y; o[2] = t[i].z; o[3] = t[i].w; o[4] = u[i].x; o[5] = u[i].y; }
+            if (neighbours) memcpy(&neighbours[i], &u[i].w, sizeof(int32_t));
+        }
+    }
+    if (V) HIPCHK(s, hipMemcpy(V, s->a.vol, sizeof(float) * n, hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
+
+// the device's eigen and clamp routine (sph_surface_aniso_eig.hpp) on the host: no GPU involved
+extern "C" int sph_surface_aniso_matrix_host(const float *C6, int64_t n, const int32_t *neighbours, const SphSurfaceAnisoParams *p, float *A6) {
+    if (n < 0 || !p || (n > 0 && (!C6 || !A6)) || surf_aniso_check(*p)) return SPH_ERR_INVALID;
+    const SurfAnisoPrm prm = {p->min_neighbours, (float)(1.0 / p->max_ratio), (float)(1.0 / p->sparse_scale)};
+    for (int64_t i = 0; i < n; ++i) {
+        float det;
+        surf_aniso_matrix(C6 + 6 * i, neighbours ? neighbours[i] : INT_MAX, prm, A6 + 6 * i, &det);
     }
     return SPH_OK;
 }

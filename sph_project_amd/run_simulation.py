@@ -21,6 +21,7 @@ the 32 KB before a position).
 --gpus N shards the scene over N ranks (z-slabs, one process each, started by launch.py): the frames are composited over the ranks
  and written by rank 0, the PLY of a fluid object is written in rank order, one part per rank."""
 import argparse
+import math
 import os
 import sys
 import time
@@ -110,6 +111,14 @@ def parse_args(argv=None):
     parser.add_argument("--mesh_smoothing_iters", type=int, default=0, help="with --reconstruct: Laplacian smoothing iterations (DESIGN.md 16)")
     parser.add_argument("--mesh_smoothing_weights", action="store_true", help="with --reconstruct: keep isolated particles' meshes unsmoothed")
     parser.add_argument("--normals_smoothing_iters", type=int, default=0, help="with --reconstruct: normal smoothing iterations")
+    parser.add_argument("--anisotropic", action="store_true",
+                        help="with --reconstruct / --render_meshes: anisotropic kernels (DESIGN.md 29) -- thin sheets, rims and droplets "
+                             "are meshed about one particle radius outside their outermost centres where the isotropic kernel adds two")
+    parser.add_argument("--aniso_ratio", type=float, default=None, help="with --anisotropic: the most a kernel shrinks along a direction, >= 1 (2)")
+    parser.add_argument("--aniso_min_neighbours", type=int, default=None,
+                        help="with --anisotropic: below this many neighbours a particle gets the isolated rule (25)")
+    parser.add_argument("--aniso_sparse_scale", type=float, default=None,
+                        help="with --anisotropic: the isolated rule's support in multiples of h, in (0, 1] (0.5)")
     parser.add_argument("--render", action="store_true",
                         help="on scenes with exportFrame write {out}/{cnt:06}/raw_view.png at the reference's cadence, rendered on the GPU "
                              "from the device state (DESIGN.md 15; not GGUI's image)")
@@ -205,6 +214,15 @@ def parse_args(argv=None):
                          "on the host); run it with --gpus 1")
         if not SimConfig(scene_file_path=args.scene_file).get_cfg("exportPly"):
             parser.error("--export_device formats the PLY frames of a scene with exportPly; this scene exports none")
+    if args.anisotropic and not (args.reconstruct or args.render_meshes):
+        parser.error("--anisotropic chooses the kernels of the surface reconstruction: give --reconstruct and / or --render_meshes as well")
+    for flag in ("aniso_ratio", "aniso_min_neighbours", "aniso_sparse_scale"):
+        if getattr(args, flag) is not None and not args.anisotropic:
+            parser.error(f"--{flag} sets a parameter of the anisotropic kernels: give --anisotropic as well")
+    if args.anisotropic:
+        why = anisotropy_error(args.aniso_ratio, args.aniso_min_neighbours, args.aniso_sparse_scale)
+        if why:
+            parser.error(why)
     if args.render_surface and args.gpus > 1:
         parser.error(f"--gpus {args.gpus}: --render_surface needs the base colour and surface flag of every pixel, which the layers "
                      "composited between ranks do not carry (DESIGN.md 24); run it with --gpus 1")
@@ -247,6 +265,23 @@ def check_sharded_args(parser, args):
         launch.plan_scene_cuts(config.config, n)
     except ValueError as e:
         parser.error(f"--gpus {n}: {e}")
+
+
+def anisotropy_error(ratio, min_neighbours, sparse_scale):
+    """Why sph_surface_set_anisotropy would refuse these values (None: not given), or None: said before a GPU is opened."""
+    if ratio is not None and not (math.isfinite(ratio) and ratio >= 1.0):
+        return f"--aniso_ratio {ratio}: a finite ratio of at least 1"
+    if min_neighbours is not None and min_neighbours < 0:
+        return f"--aniso_min_neighbours {min_neighbours}: not negative"
+    if sparse_scale is not None and not (math.isfinite(sparse_scale) and 0.0 < sparse_scale <= 1.0):
+        return f"--aniso_sparse_scale {sparse_scale}: in (0, 1]"
+    return None
+
+
+def surface_anisotropy(args):
+    """set_anisotropy keywords of the --aniso_* flags that were given (the others keep the library's defaults)."""
+    chosen = dict(max_ratio=args.aniso_ratio, min_neighbours=args.aniso_min_neighbours, sparse_scale=args.aniso_sparse_scale)
+    return {k: v for k, v in chosen.items() if v is not None}
 
 
 def surface_postprocess(args):
@@ -515,6 +550,8 @@ def main(argv=None):
         post = surface_postprocess(args)
         if post is not None:
             recon.set_postprocess(**post)
+        if args.anisotropic:
+            recon.set_anisotropy(**surface_anisotropy(args))
     renderer = raw = surface = meshes_out = None
     if sched.output_frames or args.render_surface:
         renderer = make_renderer(container, args)

@@ -101,6 +101,33 @@ class SurfaceReconstructor(L.NativeObject):
         self._chk(self.lib.sph_surface_download_post(self.h, None, None, w.ctypes.data), "sph_surface_download_post")
         return w
 
+    def set_anisotropy(self, max_ratio=2.0, min_neighbours=25, sparse_scale=0.5):
+        """Anisotropic kernels for the reconstructions that follow: every particle's kernel shrinks, by at most
+        max_ratio, along the directions in which its neighbourhood is thin; a particle with fewer than min_neighbours neighbours
+        gets the support sparse_scale h.  Off by default; clear_anisotropy() switches it off again."""
+        p = L.SphSurfaceAnisoParams(enabled=1, min_neighbours=int(min_neighbours), max_ratio=float(max_ratio),
+                                    sparse_scale=float(sparse_scale))
+        self._chk(self.lib.sph_surface_set_anisotropy(self.h, C.byref(p)), "sph_surface_set_anisotropy")
+
+    def clear_anisotropy(self):
+        self._chk(self.lib.sph_surface_set_anisotropy(self.h, None), "sph_surface_set_anisotropy")
+
+    def anisotropy(self):
+        """The last (anisotropic) reconstruction's particles in the binned key order: dict of xyz f32[n,3], A f32[n,6] = (xx, xy, xz,
+        yy, yz, zz) of the kernel matrices, neighbours i32[n], V f32[n]."""
+        n = self.stats()["particles"]
+        out = dict(xyz=np.empty((n, 3), np.float32), A=np.empty((n, 6), np.float32), neighbours=np.empty(n, np.int32),
+                   V=np.empty(n, np.float32))
+        self._chk(self.lib.sph_surface_download_anisotropy(self.h, out["xyz"].ctypes.data, out["A"].ctypes.data,
+                                                           out["neighbours"].ctypes.data, out["V"].ctypes.data),
+                  "sph_surface_download_anisotropy")
+        return out
+
+    def anisotropy_stats(self):
+        st = L.SphSurfaceAnisoStats()
+        self._chk(self.lib.sph_surface_anisotropy_stats(self.h, C.byref(st)), "sph_surface_anisotropy_stats")
+        return L.struct_dict(st)
+
     def _post_size(self):
         nv, nt = C.c_int64(), C.c_int64()
         self._chk(self.lib.sph_surface_mesh_size(self.h, C.byref(nv), C.byref(nt)), "sph_surface_mesh_size")
@@ -114,6 +141,20 @@ class SurfaceReconstructor(L.NativeObject):
         if self.mesh is None:
             raise SurfaceError("write_obj: no mesh reconstructed yet", L.ERR_INVALID)
         write_obj(path, *self.mesh)
+
+
+def aniso_matrix_host(C6, neighbours=None, max_ratio=2.0, min_neighbours=25, sparse_scale=0.5):
+    """A f32[n,6] from covariances C6 f32[n,6] by the device's eigen and clamp routine, run on the host (no GPU)."""
+    c = np.ascontiguousarray(C6, dtype=np.float32).reshape(-1, 6)
+    nb = None if neighbours is None else np.ascontiguousarray(neighbours, dtype=np.int32).reshape(-1)
+    if nb is not None and len(nb) != len(c):
+        raise ValueError("aniso_matrix_host: one neighbour count per matrix")
+    p = L.SphSurfaceAnisoParams(enabled=1, min_neighbours=int(min_neighbours), max_ratio=float(max_ratio), sparse_scale=float(sparse_scale))
+    out = np.empty_like(c)
+    rc = L.load().sph_surface_aniso_matrix_host(c.ctypes.data, len(c), None if nb is None else nb.ctypes.data, C.byref(p), out.ctypes.data)
+    if rc != 0:
+        raise SurfaceError(f"sph_surface_aniso_matrix_host: invalid parameters ({rc})", rc)
+    return out
 
 
 def write_obj(path, vertices, triangles, normals=None):

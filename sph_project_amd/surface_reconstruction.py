@@ -5,6 +5,7 @@ here one GPU reconstructs the frames in order (sph_project_amd/surface.py, DESIG
 
     python sph_project_amd/surface_reconstruction.py --input_dir final_scene0_output --radius 0.01 [--smoothing-length 3.5]
         [--mesh-smoothing-weights=on --mesh-smoothing-iters=25 --normals-smoothing-iters=10]
+        [--anisotropic [--aniso-ratio 2 --aniso-min-neighbours 25 --aniso-sparse-scale 0.5]]
 """
 import argparse
 import os
@@ -29,9 +30,23 @@ def parse_args(argv=None):
     parser.add_argument("--mesh-smoothing-weights", choices=["on", "off"], default=None)
     parser.add_argument("--mesh-smoothing-weights-normalization", type=float, default=None)
     parser.add_argument("--normals-smoothing-iters", type=int, default=None)
+    # anisotropic kernels (run_simulation.py's --anisotropic, --aniso_ratio, ...).  Not given: the isotropic kernel
+    parser.add_argument("--anisotropic", action="store_true")
+    parser.add_argument("--aniso-ratio", type=float, default=None, help="with --anisotropic: >= 1 (2)")
+    parser.add_argument("--aniso-min-neighbours", type=int, default=None, help="with --anisotropic (25)")
+    parser.add_argument("--aniso-sparse-scale", type=float, default=None, help="with --anisotropic: in (0, 1] (0.5)")
     parser.add_argument("--export_device", action="store_true",
                         help="format the .obj files on the GPU from the device mesh (DESIGN.md 23: the same bytes, no mesh download)")
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    for flag in ("aniso_ratio", "aniso_min_neighbours", "aniso_sparse_scale"):
+        if getattr(args, flag) is not None and not args.anisotropic:
+            parser.error(f"--{flag.replace('_', '-')} sets a parameter of the anisotropic kernels: give --anisotropic as well")
+    if args.anisotropic:
+        from sph_project_amd.run_simulation import anisotropy_error
+        why = anisotropy_error(args.aniso_ratio, args.aniso_min_neighbours, args.aniso_sparse_scale)
+        if why:
+            parser.error(why.replace("--aniso_", "--aniso-").replace("min_neighbours", "min-neighbours").replace("sparse_scale", "sparse-scale"))
+    return args
 
 
 def postprocess_settings(args):
@@ -66,6 +81,9 @@ def main(argv=None):
     post = postprocess_settings(args)
     if post is not None:
         recon.set_postprocess(**post)
+    if args.anisotropic:
+        from sph_project_amd.run_simulation import surface_anisotropy
+        recon.set_anisotropy(**surface_anisotropy(args))
     exporter = None
     if args.export_device:
         from sph_project_amd.text import TextExporter
