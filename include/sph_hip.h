@@ -847,6 +847,66 @@ int sph_render_mesh_add_surface(SphRender *r, SphSurface *s, const uint8_t rgb[3
 int sph_render_mesh_end(SphRender *r);
 int sph_render_mesh_stats(SphRender *r, SphRenderMeshStats *out);
 
+/* --- traced mesh frames: shadows and refracting water --------------------------------------------------------------- */
+/* An opt-in mode of the mesh frames above: while it is on, sph_render_mesh_end traces the list instead of rasterising it -- a bounding
+   volume hierarchy over the frame's triangles is built on the device (Morton codes of the centroids, radix sort, Karras 2012, boxes
+   fitted bottom-up) and one Whitted-style path per pixel is followed through it: hard shadows from the point light, water meshes as a
+   dielectric (Snell refraction, Schlick's Fresnel term with one reflection segment that is followed no further, Beer-Lambert absorption
+   tinted by the mesh's colour), and the bottom face of the box as a checkered floor that takes the shadows.  Camera, pixel rays, near
+   plane, light, ambient, background, box lines and 8-bit rounding are those of the mesh frames; without the mode every frame is what it
+   was.  Deterministic: no random numbers, no float atomics; the winner of a ray is the smallest (float_bits(t) << 32 | global triangle
+   index), so the image is a function of the mesh list.  A ray never hits the triangle it starts on (by index).  The id image holds the
+   primary hit: a triangle index, SPH_RENDER_TRACE_FLOOR_ID for the floor, the line ids, -1.
+   Not done: soft shadows, caustics (water does not block light), further reflection bounces, an environment map, anti-aliasing, sharded
+   handles, particles in the same frame. */
+#define SPH_RENDER_MATERIAL_DIFFUSE 0
+#define SPH_RENDER_MATERIAL_WATER 1
+#define SPH_RENDER_TRACE_FLOOR_ID (-14)
+#define SPH_RENDER_TRACE_SEGMENT_WORDS 24
+typedef struct {
+    int32_t max_depth;          /* 1..64 segments of a path; a path cut there adds the background times its throughput */
+    float ior;                  /* >= 1, the fluid's index of refraction */
+    float absorb;               /* >= 0: a segment of length l in the fluid multiplies the throughput per channel by
+                                   exp2(-absorb (1 - rgb / 255) l / radius), rgb the colour of the water mesh it entered */
+    int32_t shadows;            /* 0 / 1: shadow rays towards the light */
+    int32_t floor;              /* 0 / 1: the bottom face of the box (if the renderer draws one) as a diffuse checkered rectangle */
+    float floor_cell;           /* > 0, the checker's cell in units of radius */
+    int32_t use_bvh;            /* 0: every ray tests every triangle with the same routines (the check of the culling) */
+    int32_t record;             /* 1: the segments of every path are kept for sph_render_trace_download_paths */
+} SphRenderTraceParams;
+
+typedef struct {
+    int64_t triangles;          /* kept: leaves of the hierarchy */
+    int64_t nodes;              /* 2 triangles - 1 */
+    int64_t depth;              /* inner nodes above the deepest leaf (at most 64: the sort keys are distinct) */
+    int64_t skipped_nonfinite, skipped_degenerate, bad_index;   /* left out, as the mesh frames count them */
+    int64_t rays_primary, rays_path, rays_reflect, rays_shadow; /* pixels; refracted or totally reflected segments; reflection segments;
+                                                                   shadow rays */
+    int64_t node_visits, triangle_tests;
+    int64_t truncated;          /* paths cut at max_depth */
+    int64_t aborted_rays;       /* rays that reached the visit cap of 2 nt nodes (a miss; 0 unless the hierarchy is broken) */
+    double ms_setup, ms_sort, ms_hierarchy, ms_fit, ms_trace, ms_finish, ms_total;   /* HIP events */
+} SphRenderTraceStats;
+
+/* the mode for the mesh frames that follow; NULL: off, and what it allocated is freed.  SPH_ERR_INVALID: a parameter outside its
+   range, between mesh_begin and mesh_end; SPH_ERR_UNSUPPORTED: the renderer composites the layers of a sharded handle */
+int sph_render_set_trace(SphRender *r, const SphRenderTraceParams *params_or_NULL);
+/* the material of the mesh added last (between its _add and _end; default diffuse); flip = 1: the mesh is wound inwards.  Read by the
+   traced frames only */
+int sph_render_mesh_material(SphRender *r, int material, int flip);
+/* of the traced frame held; SPH_ERR_INVALID while the mode is off or the frame held is not a traced one */
+int sph_render_trace_stats(SphRender *r, SphRenderTraceStats *out);
+/* the hierarchy of the traced frame held, n = triangles: left / right i32[n - 1] (node ids: inner node i is i, the leaf of sorted
+   position j is n - 1 + j, the root is 0), boxes f32[2 n - 1][6] (lo xyz, hi xyz per node id), leaf_triangle i32[n] (the global
+   triangle index of leaf j); each may be NULL */
+int sph_render_trace_download_bvh(SphRender *r, int32_t *left, int32_t *right, float *boxes, int32_t *leaf_triangle);
+/* the segments of a frame traced with record = 1: f32[height][width][max_depth][24].  Words: 0-2 origin, 3-5 direction, 6 hit id (i32:
+   a triangle, the floor id, -1), 7 t, 8-10 the unit normal used (shading or refraction), 11-13 throughput at the start, 14-16
+   throughput handed on (0: the path ends), 17-19 what the segment added to the pixel (its reflection included), 20 shadow ray of the
+   hit (i32: -1 none, 0 lit, 1 blocked), 21 the reflection segment's hit id (i32, -1 none or a miss), 22 F, 23 flags (i32: 1 used,
+   2 entering, 4 total internal reflection, 8 the segment ran inside the fluid, 16 the reflection's hit was in shadow) */
+int sph_render_trace_download_paths(SphRender *r, float *segments);
+
 /* --- video encoding: RGB frames -> baseline JPEG streams, the frames of a Motion-JPEG AVI ------------------------- */
 /* stands in for the reference's make_video.py (imageio): every frame is compressed on the device it was rendered on; the AVI
    container around the frames is written on the host (sph_project_amd/video.py).  One frame is one complete .jpg file: baseline

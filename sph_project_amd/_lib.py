@@ -227,6 +227,29 @@ class SphRenderMeshStats(C.Structure):
     ]
 
 
+class SphRenderTraceParams(C.Structure):
+    _fields_ = [
+        ("max_depth", C.c_int32), ("ior", C.c_float), ("absorb", C.c_float), ("shadows", C.c_int32), ("floor", C.c_int32),
+        ("floor_cell", C.c_float), ("use_bvh", C.c_int32), ("record", C.c_int32),
+    ]
+
+
+class SphRenderTraceStats(C.Structure):
+    _fields_ = [
+        ("triangles", C.c_int64), ("nodes", C.c_int64), ("depth", C.c_int64), ("skipped_nonfinite", C.c_int64),
+        ("skipped_degenerate", C.c_int64), ("bad_index", C.c_int64), ("rays_primary", C.c_int64), ("rays_path", C.c_int64),
+        ("rays_reflect", C.c_int64), ("rays_shadow", C.c_int64), ("node_visits", C.c_int64), ("triangle_tests", C.c_int64),
+        ("truncated", C.c_int64), ("aborted_rays", C.c_int64),
+        ("ms_setup", C.c_double), ("ms_sort", C.c_double), ("ms_hierarchy", C.c_double), ("ms_fit", C.c_double), ("ms_trace", C.c_double),
+        ("ms_finish", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
+RENDER_MATERIALS = {"diffuse": 0, "water": 1}   # SPH_RENDER_MATERIAL_*
+RENDER_TRACE_FLOOR_ID = -14                      # SPH_RENDER_TRACE_FLOOR_ID
+RENDER_TRACE_SEGMENT_WORDS = 24                  # SPH_RENDER_TRACE_SEGMENT_WORDS
+
+
 class SphVideoParams(C.Structure):
     _fields_ = [
         ("width", C.c_int32), ("height", C.c_int32), ("quality", C.c_int32), ("chroma", C.c_int32), ("fast_math", C.c_int32),
@@ -419,6 +442,11 @@ _SIGNATURES = [
     ("sph_render_mesh_add_surface", C.c_int, [_VP, _VP, _VP]),
     ("sph_render_mesh_end", C.c_int, [_VP]),
     ("sph_render_mesh_stats", C.c_int, [_VP, C.POINTER(SphRenderMeshStats)]),
+    ("sph_render_set_trace", C.c_int, [_VP, C.POINTER(SphRenderTraceParams)]),
+    ("sph_render_mesh_material", C.c_int, [_VP, C.c_int, C.c_int]),
+    ("sph_render_trace_stats", C.c_int, [_VP, C.POINTER(SphRenderTraceStats)]),
+    ("sph_render_trace_download_bvh", C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    ("sph_render_trace_download_paths", C.c_int, [_VP, _VP]),
     ("sph_video_create", C.c_int, [C.POINTER(SphVideoParams), C.POINTER(_VP)]),
     ("sph_video_destroy", None, [_VP]),
     ("sph_video_last_error", C.c_char_p, [_VP]),

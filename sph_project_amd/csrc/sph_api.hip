@@ -1465,6 +1465,7 @@ extern "C" int sph_points_in_mesh(const double *vertices, int n_vertices, const 
 
 #include "sph_surface_api.hpp"
 #include "sph_render_api.hpp"
+#include "sph_render_trace_api.hpp"
 #include "sph_encoder_api.hpp"
 #include "sph_video_api.hpp"
 #include "sph_png_api.hpp"

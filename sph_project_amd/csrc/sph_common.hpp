@@ -380,7 +380,8 @@ struct RenderFoamDev {
 // record with t0 <= g; its indices are local to that mesh's nv vertices, which start at slot v0 of vert / nrm.  The frame buffers,
 // camera and counters are the RenderDev's: cnt[0] triangles that passed the hit test at some pixel centre (whether or not they won it), [1] non-finite, [2] large,
 // [3] atomics issued, [4] covered pixels, [5] zero-area, [6] with an index outside [0, nv).
-struct MeshRec { long long t0, v0; int nv; unsigned col; int smooth, pad; };
+// mat: read by the traced frames only (TraceDev below): bit 0 water, bit 1 the mesh is wound inwards.
+struct MeshRec { long long t0, v0; int nv; unsigned col; int smooth, mat; };
 struct MeshDev {
     int nm;                            // meshes
     long long nt;                      // triangles of all meshes
@@ -388,6 +389,34 @@ struct MeshDev {
     const float *vert, *nrm;           // [3 x vertices of all meshes] (nrm: read for the meshes with smooth = 1 only)
     const int *tri;                    // [3 nt]
     unsigned *large;                   // [nt] triangles whose screen bounds exceed RENDER_LARGE_PX pixels
+};
+
+// Traced mesh frames (sph_render_trace.hpp): the set-up triangles, the sort's keys, the hierarchy and the frame's constants.
+// n = ctr[TC_KEPT] triangles are kept (read on the device: no host read between the stages).  Node ids: inner node i of the n - 1 is i,
+// the leaf of sorted position j is n - 1 + j, the root is 0 (n = 1: the one leaf).  key = morton30 << 32 | g for a kept triangle g,
+// 0x40000000 << 32 | g for a skipped one (sorted behind the kept).
+#define TRACE_FLOOR_ID 0xFFFFFFEFu     // the floor's id in a key (below the line ids, above every triangle index)
+#define TRACE_REC_WORDS 24             // words of one recorded segment (include/sph_hip.h, sph_render_trace_download_paths)
+#define TRACE_SORT_TILE 2048           // keys of one workgroup of the sort
+enum TraceCtr { TC_KEPT, TC_NONFINITE, TC_DEGENERATE, TC_BAD_INDEX, TC_DEPTH, TC_RAYS_PRIMARY, TC_RAYS_PATH, TC_RAYS_REFLECT,
+                TC_RAYS_SHADOW, TC_VISITS, TC_TESTS, TC_TRUNCATED, TC_ABORTED, TC_COUNT_ = 16 };
+struct TraceDev {
+    float4 *corner;                    // [3 nt] world corners of triangle g in canonical order (w: the corner's vertex slot, as int bits)
+    int *st;                           // [nt] -1 skipped, else mesh << 1 | (canonical order is an odd permutation of the stored one)
+    unsigned long long *key[2];        // [nt] each (ping-pong of the radix sort; the sorted keys end in key[0])
+    unsigned *hist;                    // [tiles + 1][256] digit counts per tile -> exclusive over the tiles; last row: the digits' bases
+    int *left, *right;                 // [nt] children of inner node i
+    int *parent, *skip;                // [2 nt] per node id: parent (-1 root); where a ray goes when it is done with the subtree (-1: out)
+    int *arrive;                       // [nt] arrival counters of the fit (zeroed every frame)
+    float *box;                        // [2 nt][6] lo xyz, hi xyz per node id
+    unsigned *bnd;                     // [8] centroid bounds, floats in an order-keeping unsigned code: [0..2] min, [3..5] max
+    unsigned long long *ctr;           // [TC_COUNT_]
+    float *rec;                        // [W H][max_depth][TRACE_REC_WORDS] or null
+    float light[3];                    // the point light, world coordinates
+    float floor_y, floor_lo[2], floor_hi[2];   // the floor: y = floor_y, x and z inside [lo, hi]
+    float cell;                        // checker cell (world units)
+    float ior, absorb;                 // absorb: per world unit of length (the parameter / radius)
+    int max_depth, shadows, floor, use_bvh;
 };
 
 // Video encoding (sph_video.hpp): one frame -> the scan of a baseline JPEG.  A restart interval is VIDEO_RI MCUs (the
@@ -774,6 +803,13 @@ struct Launch {
     void (*render_mesh_depth)(RenderDev &, MeshDev &);   // depth keys of triangles (small per thread, large per workgroup) and box lines
     void (*render_mesh_shade)(RenderDev &, MeshDev &);   // the winners' colours (triangles, lines)
     void (*render_mesh_finish)(RenderDev &);             // background / ids / covered count per pixel
+    // traced mesh frames (sph_render_trace.hpp)
+    void (*render_trace_setup)(MeshDev &, TraceDev &, hipStream_t);   // corners, skipped triangles counted, centroid bounds; then the keys
+    void (*render_trace_sort)(MeshDev &, TraceDev &, hipStream_t);    // four 8-bit passes over the code bits
+    void (*render_trace_hierarchy)(MeshDev &, TraceDev &, hipStream_t);   // Karras 2012: children and parents
+    void (*render_trace_fit)(MeshDev &, TraceDev &, hipStream_t);     // boxes bottom-up, then the skip links and the depth
+    void (*render_trace_shade)(RenderDev &, MeshDev &, TraceDev &);   // one path per pixel: rgb and the primary key
+    void (*render_trace_finish)(RenderDev &);                         // box lines over the frame, the id image
     // video encoding (sph_video.hpp)
     void (*video_count)(VideoDev &);            // bytes per restart interval (transform, symbols, stuffing; nothing stored but the counts)
     void (*video_scan)(VideoDev &);             // their exclusive scan, the total behind it

@@ -534,6 +534,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_surface_post_launchers(L);
         register_render_launchers(L);
         register_render_mesh_launchers(L);
+        register_render_trace_launchers(L);
         register_render_surface_launchers(L);
         register_render_thickness_launchers(L);
         register_render_foam_launchers(L);

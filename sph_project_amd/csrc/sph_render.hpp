@@ -314,3 +314,4 @@ static void register_render_launchers(Launch &L) {
 }
 
 #include "sph_render_mesh.hpp"
+#include "sph_render_trace.hpp"

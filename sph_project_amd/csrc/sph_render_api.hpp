@@ -63,7 +63,11 @@ struct SphRender : DevObj {   // clk[0]: a particle frame's stages, clk[1]: a me
     bool sfoam_thick = false;     // ... and were summed against the thickness mode's limits
     StageClock fclk;
     SphRenderSurfaceFoamStats fstats{};
+    // traced mesh frames (sph_render_set_trace in sph_render_trace_api.hpp): set while the mode is on
+    struct RendTrace *tr = nullptr;
 };
+static void rend_trace_free(SphRender *r);
+static int rend_trace_end(SphRender *r, MeshDev &m);
 static int rend_draw_foam(SphRender *r, struct SphFoam *f, double scale, const unsigned rgb[3]);
 static int rend_surface_foam_check(SphRender *r, SphHandle *h);
 static int rend_surface_foam_draw(SphRender *r);
@@ -186,6 +190,7 @@ extern "C" void sph_render_destroy(SphRender *r) {
     for (hipEvent_t e : r->sclk.ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : r->tclk.ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : r->fclk.ev) if (e) hipEventDestroy(e);
+    rend_trace_free(r);
     devobj_close(r, r->buf, RB_COUNT_);
     delete r;
 }
@@ -859,6 +864,7 @@ extern "C" int sph_render_mesh_end(SphRender *r) {
     d.n = 0; d.pos = nullptr; d.meta = nullptr; d.id = nullptr; d.col = nullptr; d.col_home = nullptr;
     HIPCHK(r, k.mark(0));
     if (nm) HIPCHK(r, hipMemcpyAsync(r->buf[RB_MREC].p, r->mesh_rec.data(), sizeof(MeshRec) * nm, hipMemcpyHostToDevice, r->stream));
+    if (r->tr) { HIPCHK(r, k.mark(1)); return rend_trace_end(r, m); }   // the mode is on: the traced frame instead
     { int rc = rend_open(r, k, 1); if (rc) return rc; }
     r->L->render_mesh_depth(d, m);
     HIPCHK(r, k.mark(2));

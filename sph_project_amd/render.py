@@ -46,6 +46,7 @@ class FrameRenderer(L.NativeObject):
         self._thickness = None      # SphRenderThicknessParams of its thickness mode, None: off
         self._foam = None           # (DiffuseParticles, radius_scale, three uint8[3] colours) drawn by from_container, None: off
         self._surface_foam = None   # (DiffuseParticles, SphRenderSurfaceFoamParams) drawn into the surface frames, None: off
+        self._trace = None          # SphRenderTraceParams of the traced mesh frames, None: off
 
     def _params(self, box):
         kw = dict(self._kw)
@@ -76,7 +77,58 @@ class FrameRenderer(L.NativeObject):
                 self._set_foam(h)
             if self._surface_foam is not None:
                 self._set_surface_foam(h)
+            if self._trace is not None:
+                self._chk(self.lib.sph_render_set_trace(h, C.byref(self._trace)), "sph_render_set_trace", h)
         return h
+
+    def set_trace(self, max_depth=6, ior=1.33, absorb=0.05, shadows=True, floor=True, floor_cell=10.0, bvh=True, record=False):
+        """Trace the mesh frames that follow instead of rasterising them: a hierarchy over the frame's triangles is built
+        on the device and one path per pixel followed through it -- hard shadows from the point light, "water" meshes as a dielectric
+        (refraction, Fresnel reflection, absorption tinted by the mesh's colour: absorb per particle radius of path), the bottom face of
+        the box as a checkered floor (floor_cell particle radii a cell).  bvh=False: every ray tests every triangle (the check of the
+        culling); record=True keeps every path's segments for trace_paths()."""
+        p = L.SphRenderTraceParams()
+        p.max_depth, p.ior, p.absorb, p.floor_cell = int(max_depth), float(ior), float(absorb), float(floor_cell)
+        p.shadows, p.floor, p.use_bvh, p.record = int(bool(shadows)), int(bool(floor)), int(bool(bvh)), int(bool(record))
+        self._native(self.box if self.box else None)   # (one native renderer at least: a bad parameter raises here)
+        for h in self._handles.values():
+            self._chk(self.lib.sph_render_set_trace(h, C.byref(p)), "sph_render_set_trace", h)
+        self._trace = p
+
+    def clear_trace(self):
+        """Mesh frames are rasterised again; what the mode allocated on the device is freed."""
+        self._trace = None
+        for h in self._handles.values():
+            self._chk(self.lib.sph_render_set_trace(h, None), "sph_render_set_trace", h)
+
+    def trace_stats(self):
+        """Of the last traced frame: triangles (kept), nodes, depth, skipped_*, bad_index, rays_primary / _path / _reflect / _shadow,
+        node_visits, triangle_tests, truncated, aborted_rays, ms_setup / _sort / _hierarchy / _fit / _trace / _finish / _total."""
+        self._need("meshes", "trace_stats")
+        st = L.SphRenderTraceStats()
+        self._chk(self.lib.sph_render_trace_stats(self._last, C.byref(st)), "sph_render_trace_stats", self._last)
+        return L.struct_dict(st)
+
+    def trace_bvh(self):
+        """The hierarchy of the last traced frame: dict of left / right int32[n - 1] (node ids: inner node i is i, the leaf of sorted
+        position j is n - 1 + j, the root is 0), boxes float32[2 n - 1, 6] (lo, hi) and leaf_triangle int32[n]."""
+        n = self.trace_stats()["triangles"]
+        out = dict(left=np.empty(max(n - 1, 0), np.int32), right=np.empty(max(n - 1, 0), np.int32),
+                   boxes=np.empty((max(2 * n - 1, 0), 6), np.float32), leaf_triangle=np.empty(n, np.int32))
+        self._chk(self.lib.sph_render_trace_download_bvh(self._last, out["left"].ctypes.data, out["right"].ctypes.data,
+                                                         out["boxes"].ctypes.data, out["leaf_triangle"].ctypes.data),
+                  "sph_render_trace_download_bvh", self._last)
+        return out
+
+    def trace_paths(self):
+        """float32 (H, W, max_depth, 24) of the last frame traced with record=True: the words of sph_render_trace_download_paths
+        (include/sph_hip.h); the integer words (6, 20, 21, 23) are read with .view(np.int32)."""
+        self._need("meshes", "trace_paths")
+        if self._trace is None:
+            raise RenderError("trace_paths: the trace mode is off", L.ERR_INVALID)
+        out = np.empty((self.height, self.width, int(self._trace.max_depth), L.RENDER_TRACE_SEGMENT_WORDS), np.float32)
+        self._chk(self.lib.sph_render_trace_download_paths(self._last, out.ctypes.data), "sph_render_trace_download_paths", self._last)
+        return out
 
     def _set_foam(self, h):
         if self._foam is None:
@@ -366,7 +418,8 @@ class FrameRenderer(L.NativeObject):
     def from_meshes(self, meshes, download=True):
         """uint8 (H, W, 3) of an ordered list of triangle meshes: each item is (vertices f32[nv, 3], triangles i32[nt, 3],
         normals f32[nv, 3] or None, rgb) or (SurfaceReconstructor, rgb) -- the reconstructor's last mesh, copied on the device.  Flat
-        shading without normals.  Triangles are numbered through the list (ids(), mesh_of()).  `radius` plays no part.  A triangle with
+        shading without normals.  An item may carry a material as a further element, "diffuse" (the default) or "water", and behind it
+        True for a mesh wound inwards: read by the traced frames (set_trace) only.  Triangles are numbered through the list (ids(), mesh_of()).  `radius` plays no part.  A triangle with
         an index outside its mesh is skipped and raises RenderError (code -1) after the frame is drawn: last_rgb() / ids() still give it.
         download=False: None is returned and the frame stays on the device."""
         h = self._native(self.box if self.box else None)
@@ -374,6 +427,7 @@ class FrameRenderer(L.NativeObject):
         self._chk(self.lib.sph_render_mesh_begin(h), "sph_render_mesh_begin", h)
         starts = [0]
         for item in meshes:
+            item, material, flip = _split_material(item)
             col = np.ascontiguousarray(item[-1], dtype=np.uint8).reshape(3)
             if len(item) == 2:
                 recon = item[0]
@@ -381,6 +435,8 @@ class FrameRenderer(L.NativeObject):
                 nv, nt = C.c_int64(), C.c_int64()
                 recon._chk(self.lib.sph_surface_mesh_size(recon.h, C.byref(nv), C.byref(nt)), "sph_surface_mesh_size")
                 starts.append(starts[-1] + nt.value)
+                if material is not None:
+                    self._chk(self.lib.sph_render_mesh_material(h, material, flip), "sph_render_mesh_material", h)
                 continue
             v = np.ascontiguousarray(item[0], dtype=np.float32).reshape(-1, 3)
             t = np.ascontiguousarray(item[1], dtype=np.int32).reshape(-1, 3)
@@ -390,6 +446,8 @@ class FrameRenderer(L.NativeObject):
             self._chk(self.lib.sph_render_mesh_add(h, v.ctypes.data, None if n is None else n.ctypes.data, t.ctypes.data, v.shape[0],
                                                    t.shape[0], col.ctypes.data), "sph_render_mesh_add", h)
             starts.append(starts[-1] + t.shape[0])
+            if material is not None:
+                self._chk(self.lib.sph_render_mesh_material(h, material, flip), "sph_render_mesh_material", h)
         rc = self.lib.sph_render_mesh_end(h)
         self._mesh_starts = np.asarray(starts, np.int64)
         if rc == L.ERR_INVALID:
@@ -436,6 +494,27 @@ class FrameRenderer(L.NativeObject):
         st = L.SphRenderStats()
         self._chk(self.lib.sph_render_stats(self._last, C.byref(st)), "sph_render_stats", self._last)
         return L.struct_dict(st)
+
+
+def _split_material(item):
+    """A from_meshes item without its material elements, the material's code (None: not given) and the flip flag: the 4-tuples and
+    (SurfaceReconstructor, rgb) pairs may carry "diffuse" or "water" as a further element, and behind it True for a mesh wound inwards;
+    or, explicitly, a dict {"material": ..., "flip": ...} as their last element."""
+    item = tuple(item)
+    flip = 0
+    if item and isinstance(item[-1], dict):   # the explicit form: {"material": "water", "flip": True}
+        spec, item = dict(item[-1]), item[:-1]
+        material, flip = spec.pop("material", "diffuse"), int(bool(spec.pop("flip", False)))
+        if spec or material not in L.RENDER_MATERIALS:
+            raise ValueError(f"from_meshes: material {material!r} is neither 'diffuse' nor 'water' (keys: material, flip; got also {sorted(spec)})")
+        return item, L.RENDER_MATERIALS[material], flip
+    if len(item) >= 4 and isinstance(item[-1], (bool, np.bool_)) and isinstance(item[-2], str):
+        flip, item = int(item[-1]), item[:-1]
+    if len(item) in (3, 5) and isinstance(item[-1], str):
+        if item[-1] not in L.RENDER_MATERIALS:
+            raise ValueError(f"from_meshes: material {item[-1]!r} is neither 'diffuse' nor 'water'")
+        return item[:-1], L.RENDER_MATERIALS[item[-1]], flip
+    return item, None, 0
 
 
 def _chunk(tag, data):

@@ -62,8 +62,9 @@ def scene_colours(cfg):
     return out
 
 
-def frame_meshes(frame_dir, colours):
-    """The mesh list of one frame directory: its OBJ files in object-id order (the driver's order), each in its object's colour."""
+def frame_meshes(frame_dir, colours, water=False):
+    """The mesh list of one frame directory: its OBJ files in object-id order (the driver's order), each in its object's colour.
+    water: particle_object_*.obj carry the water material of the traced frames (mesh_object_*.obj stay diffuse)."""
     items = []
     for name in os.listdir(frame_dir):
         m = re.fullmatch(r".*_object_(\d+)\.obj", name)
@@ -72,7 +73,8 @@ def frame_meshes(frame_dir, colours):
     out = []
     for oid, name in sorted(items):
         v, t, n = read_obj(os.path.join(frame_dir, name))
-        out.append((v, t, n, colours.get(oid, (255, 255, 255))))
+        item = (v, t, n, colours.get(oid, (255, 255, 255)))
+        out.append(item + ("water",) if water and name.startswith("particle_object_") else item)
     return out
 
 
@@ -91,7 +93,17 @@ def parse_args(argv=None):
                         help="compress the PNG files on the GPU from the device image (DESIGN.md 21), as run_simulation.py --png_device does")
     parser.add_argument("--png_coding", default=None, choices=["fixed", "dynamic", "window"],
                         help="with --png_device: fixed (the default), dynamic Huffman blocks or window matches, as run_simulation.py --png_coding")
+    parser.add_argument("--raytrace", action="store_true",
+                        help="trace the frames instead of rasterising them (DESIGN.md 30), as run_simulation.py --render_meshes --raytrace does")
+    parser.add_argument("--trace_depth", type=int, default=None)
+    parser.add_argument("--trace_ior", type=float, default=None)
+    parser.add_argument("--trace_absorb", type=float, default=None)
+    parser.add_argument("--trace_no_shadows", action="store_true")
+    parser.add_argument("--trace_no_floor", action="store_true")
     args = parser.parse_args(argv)
+    for flag in ("trace_depth", "trace_ior", "trace_absorb", "trace_no_shadows", "trace_no_floor"):
+        if getattr(args, flag) not in (None, False) and not args.raytrace:
+            parser.error(f"--{flag} sets a parameter of the traced frames: give --raytrace as well")
     if args.png_coding is not None and not args.png_device:
         parser.error("--png_coding chooses the device encoder's code: give --png_device as well")
     args.png_coding = args.png_coding or "fixed"
@@ -108,6 +120,9 @@ def main(argv=None):
     renderer = FrameRenderer(float(cfg["Configuration"].get("particleRadius", 0.01)), width=args.render_size[0], height=args.render_size[1],
                              camera_position=args.camera_position, camera_lookat=args.camera_lookat, fov=args.camera_fov,
                              box=(np.zeros(3), dom))
+    if args.raytrace:
+        chosen = dict(max_depth=args.trace_depth, ior=args.trace_ior, absorb=args.trace_absorb)
+        renderer.set_trace(shadows=not args.trace_no_shadows, floor=not args.trace_no_floor, **{k: v for k, v in chosen.items() if v is not None})
     encoder = None
     if args.png_device:
         from sph_project_amd.png import PngEncoder
@@ -117,7 +132,7 @@ def main(argv=None):
         d = os.path.join(args.input_dir, frame)
         if not os.path.isdir(d):
             continue
-        meshes = frame_meshes(d, colours)
+        meshes = frame_meshes(d, colours, water=args.raytrace)
         if not meshes:
             continue
         store_png(os.path.join(d, args.rendered_image_name), renderer, lambda dl: renderer.from_meshes(meshes, download=dl), encoder)

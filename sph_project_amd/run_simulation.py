@@ -136,6 +136,15 @@ def parse_args(argv=None):
     parser.add_argument("--surface_thickness", action="store_true",
                         help="with --render_surface: draw the surface translucent -- the fluid's thickness along every pixel's ray, summed "
                              "from the particles, lets what lies behind (rigid bodies, the box) show through (DESIGN.md 25)")
+    parser.add_argument("--raytrace", action="store_true",
+                        help="with --render_meshes: trace the mesh frames instead of rasterising them (DESIGN.md 30) -- hard shadows, the "
+                             "fluid as refracting, absorbing water, the bottom of the domain box as a checkered floor")
+    parser.add_argument("--trace_depth", type=int, default=None, help="with --raytrace: segments of a path (default 6)")
+    parser.add_argument("--trace_ior", type=float, default=None, help="with --raytrace: the fluid's index of refraction (default 1.33)")
+    parser.add_argument("--trace_absorb", type=float, default=None,
+                        help="with --raytrace: absorption per particle radius of path in the fluid, tinted by the fluid's colour (default 0.05)")
+    parser.add_argument("--trace_no_shadows", action="store_true", help="with --raytrace: no shadow rays")
+    parser.add_argument("--trace_no_floor", action="store_true", help="with --raytrace: no floor")
     parser.add_argument("--surface_absorb", type=float, default=None,
                         help="with --surface_thickness: absorption per particle radius of fluid, scaled by 1 - base colour (0.05)")
     parser.add_argument("--surface_scatter", type=float, default=None,
@@ -236,6 +245,11 @@ def parse_args(argv=None):
             parser.error(f"--{flag} sets a parameter of the thickness mode: give --surface_thickness as well")
     if args.gpus > 1:
         check_sharded_args(parser, args)
+    if args.raytrace and not args.render_meshes:
+        parser.error("--raytrace traces the mesh frames: give --render_meshes as well")
+    for flag in ("trace_depth", "trace_ior", "trace_absorb", "trace_no_shadows", "trace_no_floor"):
+        if getattr(args, flag) not in (None, False) and not args.raytrace:
+            parser.error(f"--{flag} sets a parameter of the traced mesh frames: give --raytrace as well")
     if args.png_device and not (args.render or args.render_meshes or args.render_surface):
         parser.error("--png_device compresses a renderer's frames: give --render, --render_meshes and / or --render_surface as well")
     if args.png_coding is not None and not args.png_device:
@@ -292,11 +306,19 @@ def surface_postprocess(args):
                 weights_normalization=13.0, normals_smoothing_iters=args.normals_smoothing_iters)
 
 
-def frame_meshes(container, solver, recon, reconstructed=()):
+def trace_keywords(args):
+    """set_trace keywords of the --trace_* flags (the renderer's defaults where a flag is not given)."""
+    chosen = dict(max_depth=args.trace_depth, ior=args.trace_ior, absorb=args.trace_absorb)
+    kw = {k: v for k, v in chosen.items() if v is not None}
+    kw.update(shadows=not args.trace_no_shadows, floor=not args.trace_no_floor)
+    return kw
+
+
+def frame_meshes(container, solver, recon, reconstructed=(), water=False):
     """The mesh list of one render.png, in object-id order: every visible fluid object reconstructed in situ (the list item is the
     reconstructor itself: FrameRenderer.from_meshes copies its mesh on the device before the generator reconstructs the next object;
     `reconstructed` names the object whose mesh the reconstructor holds on entry, valid until the first reconstruction here), every visible rigid body's mesh at its current pose, flat
-    shaded, each in its scene colour."""
+    shaded, each in its scene colour.  water: the fluid meshes carry the material of the traced frames."""
     for oid in sorted(container.object_id_fluid_body | container.object_id_rigid_body):
         if container.object_visibility[oid] != 1:
             continue
@@ -305,7 +327,7 @@ def frame_meshes(container, solver, recon, reconstructed=()):
             if oid not in reconstructed:
                 recon.from_container(container, oid)
                 reconstructed = ()   # the reconstructor holds this object's mesh now, no longer the one it was handed with
-            yield (recon, colour)
+            yield (recon, colour, "water") if water else (recon, colour)
         else:
             posed = solver.posed_mesh_vertices(oid)
             if posed is not None:
@@ -567,6 +589,8 @@ def main(argv=None):
         surface = ImageOutput("surface_view.png", "surface_view.avi", renderer, args, out_dir)
     if args.render_meshes:   # render.py: every mesh of the frame -> {frame}/render.png
         mesh_renderer = make_renderer(container, args, box=(np.zeros(3), np.asarray(container.domain_end, dtype=np.float64)))
+        if args.raytrace:
+            mesh_renderer.set_trace(**trace_keywords(args))
         meshes_out = ImageOutput("render.png", "render.avi", mesh_renderer, args, out_dir)
 
     diffuse = None   # --foam: a second particle set that reads the fluid and never writes it
@@ -624,7 +648,7 @@ def main(argv=None):
                     f.write(container.object_collection[r_body_id]["mesh"].export(file_type="obj"))
                 wrote = True
         if meshes_out is not None:
-            meshes = frame_meshes(container, solver, recon, held)
+            meshes = frame_meshes(container, solver, recon, held, water=args.raytrace)
             meshes_out.store(frame_dir(out_dir, cnt), lambda dl: mesh_renderer.from_meshes(meshes, download=dl))
             wrote = True
         return wrote
