@@ -233,6 +233,8 @@ typedef enum {
     SPH_K_PBF_DENSITY_LAMBDA = 22, SPH_K_PBF_FIX_POSITION = 23, SPH_K_PBF_UPDATE = 24,
     SPH_K_RIGID_CONTACT = 25, SPH_K_RIGID_INTEGRATE = 26, SPH_K_RIGID_CONTACT_SOLVE = 27,
     SPH_K_PBFC_DENSITY_LAMBDA = 28, SPH_K_PBFC_DELTA = 29,   /* consistent PBF: walk A, walk B (predict / finish: SPH_K_PBF_UPDATE) */
+    SPH_K_RIGID_MOTION = 30,   /* scripted rigid bodies: the launch that evaluates their motion programs (sph_set_rigid_motion);
+                                  sph_kernel_name's table ends at 29 and answers "?" for this id */
     SPH_K_COUNT_
 } SphKernelId;
 
@@ -357,6 +359,65 @@ int sph_rigid_integrate(SphHandle *h);
 int sph_set_rigid_contact_solver(SphHandle *h, int on, double restitution, double friction, int iterations, double beta, double slop,
                                  double patch);
 int sph_get_rigid_contact_rows(SphHandle *h, double *rows, int capacity, int *count);
+
+/* Scripted rigid bodies (opt-in; the scene key "motion" of a RigidBodies entry).  A scripted body is neither frozen nor
+   free: its pose is a function of time, the superposition of up to three blocks -- keyframes, a harmonic oscillation, a constant drift.
+   The program is given in canonical form (angles in radians, directions and axes normalised or zero, end = +infinity for "never"):
+     dt  = (double)(float)timeStepSize,  t_k = k * dt  (k = steps completed since sph_prepare: a product, never a running sum)
+     tau = clamp(t, start, end) - start
+     h   = min(1, tau / ramp) * sin(2 pi frequency tau + phase)                                        (ramp = 0: no ramp)
+     d     = key_translation(tau) + (h * amplitude) * direction + tau * drift_velocity
+     theta = key_rotation(tau) + ((h * angle) * axis + (tau * drift_rate) * drift_axis)                (a rotation vector, radians)
+     E = exp([theta]x),  rot(t) = E rot_rest,  com(t) = com_rest + rot_rest pivot + d - E rot_rest pivot
+   key_*: the piecewise interpolant (linear, or smooth: s <- s s (3 - 2 s)) of the key values at tau mapped into [0, T] by the repeat mode
+   (hold, loop, pingpong), T the last key time; zero without keys.  All of it in float64 with every product rounded, in both builds.
+   The velocities of step k -> k + 1 are the step's backward differences, so that every particle of the body moves by dt times the
+   velocity the fluid passes saw:  vel = (com(t_k+1) - com(t_k)) / dt;  M = rot(t_k+1) rot(t_k)^T, a = vee(M - M^T) / 2, s = |a|,
+   c = (tr M - 1) / 2, angvel = (atan2(s, c) / s) a / dt  (a / dt for s <= 1e-12).
+   sph_set_rigid_motion registers (or replaces) the program of object_id and its rest pose (com_rest, rot_rest row-major; com0, may be NULL,
+   the rest centre of mass as in sph_set_rigid_pose).  Legal before and after sph_prepare.  The body takes the zero-velocity pose of the
+   time the running step ends at (between sph_step_begin and sph_step_end: t_k+1; otherwise t_k) and the pose is marked dirty, as by
+   sph_set_rigid_body.  From then on ONE launch (SPH_K_RIGID_MOTION, one wave per scripted body) runs in every step where the device
+   integrator's does -- in sph_step, sph_step_async and sph_rigid_integrate, before that launch, with or without sph_set_rigid_integrator:
+   it writes the float64 record and the float32 pose, reads the body's six wrench words as sph_get_rigid_wrench returns them (rounded
+   through float32), clears them and adds dt * force, dt * torque to float64 impulse sums.  A handle without scripted bodies launches
+   nothing.  A scripted body is no registered body of the integrator or the contact solver: to them it is an infinite-mass partner.
+   sph_get_rigid_motion_state drains the stream and returns the record.
+   sph_rigid_motion_eval_host: the device's routine on the CPU (the same source): pose and velocities of step k -> k + 1 into
+   out->com / rot / vel / angvel, out->steps = k + 1; the other fields are zeroed.  No device is touched.
+   SPH_ERR_UNSUPPORTED: as sph_set_rigid_integrator (PBF, a sharded handle, an axis order other than "xyz").  SPH_ERR_INVALID, with a
+   message that names the field: a bad object id, a bad program (more than SPH_RIGID_MOTION_MAX_KEYS keys, times that do not start at 0
+   or do not increase strictly, a non-finite number, an unknown interpolation or repeat mode, a direction or axis that is neither zero
+   nor of unit length, a negative frequency or ramp, end <= start), a body registered through sph_set_rigid_body -- and
+   sph_set_rigid_body or sph_set_rigid_pose on a scripted body (one master per body). */
+#define SPH_RIGID_MOTION_MAX_KEYS 64
+typedef struct {
+    double start, end;                 /* scene time, seconds; end = +infinity: never */
+    double pivot[3];                   /* body frame: the point rotations turn about */
+    int32_t nkeys;                     /* 0: no keyframes */
+    int32_t interpolation;             /* 0 linear, 1 smooth */
+    int32_t repeat;                    /* 0 hold, 1 loop, 2 pingpong */
+    int32_t reserved;                  /* 0 */
+    double key_times[SPH_RIGID_MOTION_MAX_KEYS];
+    double key_translations[SPH_RIGID_MOTION_MAX_KEYS][3];
+    double key_rotations[SPH_RIGID_MOTION_MAX_KEYS][3];   /* rotation vectors, radians */
+    double frequency, phase, ramp;     /* Hz, radians, seconds */
+    double direction[3], amplitude;    /* unit or zero, metres */
+    double axis[3], angle;             /* unit or zero, radians */
+    double drift_velocity[3];          /* m/s */
+    double drift_axis[3], drift_rate;  /* unit or zero, rad/s */
+} SphRigidMotion;
+typedef struct {
+    double com[3], rot[9], vel[3], angvel[3];   /* pose at t_steps, velocities of the step that led there */
+    double force[3], torque[3];                 /* the wrench the last launch consumed */
+    double impulse[3], angular_impulse[3];      /* sums of dt * force, dt * torque over the launches */
+    int64_t steps;                              /* the step count the pose holds at */
+} SphRigidMotionState;
+int sph_set_rigid_motion(SphHandle *h, int object_id, const SphRigidMotion *program, const double *com_rest, const double *rot_rest,
+                         const double *com0);
+int sph_get_rigid_motion_state(SphHandle *h, int object_id, SphRigidMotionState *out);
+int sph_rigid_motion_eval_host(const SphRigidMotion *program, const double *com_rest, const double *rot_rest, double dt, int64_t k,
+                               SphRigidMotionState *out);
 
 /* --- time stepping --------------------------------------------------------------------- */
 /* replaces XSolver.prepare() (base_solver.py:683, DFSPH.py:321, PCISPH.py:188); particles of

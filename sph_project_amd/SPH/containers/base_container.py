@@ -18,6 +18,7 @@ import numpy as np
 
 from sph_project_amd import _lib as F
 from ..utils import SimConfig
+from ..rigid_solver import motion
 
 from sph_project_amd import scene  # noqa: E402
 
@@ -64,6 +65,8 @@ class BaseContainer:
         self.cfg = config
         self.GGUI = GGUI
         self.total_time = 0.0
+        self.step_count = 0     # steps completed since prepare(): scripted rigid bodies take their time from it (t_k = k dt)
+        self.in_step = False    # between the halves of a step: what is inserted now enters at the time the step ends at
 
         geo = scene.derive_geometry(config)
         self.geometry = geo
@@ -111,6 +114,10 @@ class BaseContainer:
             fluid_n += max(blk["particleNum"], actual)
         self.rigid_bodies = self.cfg.get_rigid_bodies()
         for body in self.rigid_bodies:
+            if motion.is_scripted(body):   # a scripted body: parsed and refused here, before a device is opened
+                backend = engine_opts.get("rigid_backend") or os.environ.get("SPH_RIGID_BACKEND", "native")
+                body["motionProgram"] = motion.RigidMotion.from_body(body, self.cfg.get_cfg("timeStepSize"), method=self.METHOD,
+                                                                      dim=self.dim, backend=backend)
             pts = self.load_rigid_body(body, pitch=self.particle_spacing)
             body["particleNum"], body["voxelizedPoints"] = pts.shape[0], pts
             rigid_n += pts.shape[0]
@@ -241,8 +248,10 @@ class BaseContainer:
             n = body["particleNum"]
             self.rigid_body_particle_num[obj_id] = n
             pts = np.asarray(body["voxelizedPoints"], dtype=np.float32)
-            is_dynamic = int(bool(body["isDynamic"]))
-            velocity = np.asarray(body["velocity"], np.float32) if is_dynamic else np.zeros(self.dim, np.float32)
+            # a scripted body takes the dynamic body's route: body coordinates, is_dynamic flags, placed by its first pose
+            scripted = body.get("motionProgram")
+            is_dynamic = int(bool(body["isDynamic"]) or scripted is not None)
+            velocity = np.asarray(body["velocity"], np.float32) if body["isDynamic"] else np.zeros(self.dim, np.float32)
             self.object_visibility[obj_id] = body.get("visible", 1)
             self.object_materials[obj_id] = self.material_rigid
             self.object_collection[obj_id] = body
@@ -252,8 +261,11 @@ class BaseContainer:
                 # a dynamic body's particles are inserted in BODY coordinates (the rigid solver's first pose places them, :616);
                 # which slab they belong to is decided by where that pose puts them
                 from ..rigid_solver.host_rigid_solver import _rotation
-                rot = _rotation(body["rotationAngle"] / 360 * (2 * np.pi), body["rotationAxis"])
-                where = (np.asarray(body["translation"], np.float64) + pts.astype(np.float64) @ rot.T).astype(np.float32)
+                if scripted is not None:
+                    com, rot = scripted.pose(self.entry_step() * scripted.dt)
+                else:
+                    com, rot = np.asarray(body["translation"], np.float64), _rotation(body["rotationAngle"] / 360 * (2 * np.pi), body["rotationAxis"])
+                where = (com + pts.astype(np.float64) @ rot.T).astype(np.float32)
             self.add_particles(obj_id, n, pts, np.tile(velocity, (n, 1)), body["density"] * np.ones(n, np.float32),
                                np.zeros(n, np.float32), np.full(n, self.material_rigid, np.int32),
                                is_dynamic * np.ones(n, np.int32), np.tile(np.asarray(body["color"], np.int32), (n, 1)),
@@ -266,6 +278,10 @@ class BaseContainer:
 
         for _ in self.rigid_blocks:
             raise NotImplementedError
+
+    def entry_step(self):
+        """The step count whose time an object inserted now enters at: the end of the running step, or the steps completed so far."""
+        return self.step_count + (1 if self.in_step else 0)
 
     def objects_pending(self):
         """True while some object of the scene has not entered yet (entryTime, base_container.py:218-221)."""
@@ -381,7 +397,7 @@ class BaseContainer:
         if tm is None:
             from sph_project_amd import meshgen
             mesh = meshgen.load_obj(rigid_body["geometryFile"])
-            if rigid_body["isDynamic"]:   # :616-626: dynamic bodies are scaled only, the rigid solver places them
+            if rigid_body["isDynamic"] or motion.is_scripted(rigid_body):   # :616-626: dynamic (and scripted) bodies are scaled only, the rigid solver places them
                 mesh = meshgen.place(mesh, rigid_body["scale"], 0.0, [0.0, 1.0, 0.0], [0.0, 0.0, 0.0])
             else:
                 mesh = meshgen.place(mesh, rigid_body["scale"], angle, rigid_body["rotationAxis"], rigid_body["translation"])
@@ -391,7 +407,7 @@ class BaseContainer:
             return meshgen.voxel_points(mesh, pitch)
         mesh = tm.load(rigid_body["geometryFile"])
         mesh.apply_scale(rigid_body["scale"])
-        if not rigid_body["isDynamic"]:
+        if not rigid_body["isDynamic"] and not motion.is_scripted(rigid_body):
             rot = tm.transformations.rotation_matrix(angle, rigid_body["rotationAxis"], mesh.vertices.mean(axis=0))
             mesh.apply_transform(rot)
             mesh.vertices += np.array(rigid_body["translation"])

@@ -61,9 +61,13 @@ class BaseSolver:
         has come (base_container.py:218-221) exactly where the reference does; the device finishes the step
         (renew_rigid_particle_state, boundary, DFSPH's neighbour search + density + alpha + divergence solve)."""
         self.engine.step_begin()
-        self.rigid_solver.step()
-        self.container.insert_object()
-        self.rigid_solver.insert_rigid_object()
+        self.container.in_step = True   # what enters now enters at the time this step ends at (scripted bodies: motion.py)
+        try:
+            self.rigid_solver.step()
+            self.container.insert_object()
+            self.rigid_solver.insert_rigid_object()
+        finally:
+            self.container.in_step = False
         self.engine.step_end()
         self._update_exported_meshes()
 
@@ -72,7 +76,7 @@ class BaseSolver:
         follows its pose, so that run_simulation.py can write mesh_object_{id}.obj."""
         if not self.cfg.get_cfg("exportObj"):
             return
-        for oid in self.rigid_solver.bodies:
+        for oid in list(self.rigid_solver.bodies) + list(self._scripted()):
             posed = self.posed_mesh_vertices(oid)
             if posed is not None:
                 self.container.object_collection[oid]["mesh"].vertices = posed
@@ -83,11 +87,19 @@ class BaseSolver:
         obj = self.container.object_collection.get(oid)
         if not isinstance(obj, dict) or "mesh" not in obj:
             return None
-        b = self.rigid_solver.bodies.get(oid)
+        b = self.rigid_solver.bodies.get(oid) or self._scripted().get(oid)   # (a scripted body follows its program's pose)
         if b is None:
             return np.asarray(obj["mesh"].vertices, dtype=np.float64)
         rest = np.asarray(obj["restPosition"], dtype=np.float64) - np.asarray(obj["restCenterOfMass"], dtype=np.float64)
         return (b.rot @ rest.T).T + b.com
+
+    def _scripted(self):
+        """The rigid solver's scripted bodies (object id -> body)."""
+        return getattr(self.rigid_solver, "scripted", None) or {}
+
+    def _count_step(self):
+        """A step is complete: scripted bodies take their time from the count (t_k = k dt, a product)."""
+        self.container.step_count = getattr(self.container, "step_count", 0) + 1
 
     def _bodies_on_device(self):
         """The "device" rigid backend is active: the device integrates the dynamic bodies between the halves of its own steps."""
@@ -97,7 +109,8 @@ class BaseSolver:
         """A dynamic rigid body to integrate or an object still waiting for its entryTime: the host has to act in the middle
         of _step(), where the reference does (WCSPH.py:39-42).  Bodies the device integrates itself (the "device" rigid backend)
         need nothing from the host."""
-        return (bool(self.rigid_solver.bodies) and not self._bodies_on_device()) or self.container.objects_pending()
+        moved = bool(self.rigid_solver.bodies) or bool(self._scripted())   # (scripted bodies: the host evaluates their programs)
+        return (moved and not self._bodies_on_device()) or self.container.objects_pending()
 
     def _device_steps(self, n):
         """n whole steps on the device.  WCSPH, reference-variant PBF (and solvers with a fixed iteration count) need nothing back from the device:
@@ -126,6 +139,7 @@ class BaseSolver:
             self._device_steps(1)
         self.container.total_time += self.dt[None]
         self.rigid_solver.total_time += self.dt[None]
+        self._count_step()
 
     def advance(self, n):
         """n calls of step().  Where the host has nothing to do inside a step -- no dynamic rigid body to integrate, no object
@@ -148,6 +162,7 @@ class BaseSolver:
         for _ in range(n):   # the same float additions as n calls of step()
             self.container.total_time += self.dt[None]
             self.rigid_solver.total_time += self.dt[None]
+            self._count_step()
 
     def stats(self):
         return self.engine.stats()

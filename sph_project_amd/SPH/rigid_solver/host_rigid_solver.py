@@ -36,12 +36,19 @@ Built-in backends:
     stepSimulation, base pose read-back) when the package is importable.  It is not installed in this image, so this
     backend has never run here; select it with SPH_RIGID_BACKEND=pybullet.
 Static bodies need no backend at all (bullet_solver.py:31-42 makes the same distinction).
+
+Scripted bodies (a RigidBodies entry with a "motion" key, motion.py) are a third kind: their pose is a function of the step
+count.  They live in `scripted`, not in `bodies` -- no integrator, contact solver or wall rule touches them, and to the contact backends
+they are infinite-mass partners.  The native and contact backends evaluate the next pose on the host every step and push it; the device
+backends hand the program to the library once (sph_set_rigid_motion) and read the state back when somebody looks.
 """
 import math
 import os
 import sys
 
 import numpy as np
+
+from .motion import RigidMotion, is_scripted
 
 _WARNED = [False]
 # contact backend: resting contacts keep this much depth (in units of the contact distance D), so that the touching particle set of a
@@ -98,6 +105,31 @@ class _DeviceBody(_Body):
     del _get
 
 
+class _Scripted:
+    """A scripted body: its program, its state after the last step, the wrench that step consumed and the impulse sums."""
+
+    def __init__(self, oid, motion, com, rot, points):
+        self.oid, self.motion, self.points = oid, motion, points
+        self.com, self.rot = np.asarray(com, np.float64).copy(), np.asarray(rot, np.float64).copy()
+        self.vel, self.angvel = np.zeros(3), np.zeros(3)
+        self.force, self.torque, self.impulse, self.angular_impulse = np.zeros(3), np.zeros(3), np.zeros(3), np.zeros(3)
+
+
+class _DeviceScripted(_Scripted):
+    """A scripted body the device moves: its record is read back from the device when it is looked at after a step."""
+    _solver = None
+
+    def _get(name):
+        def get(self):
+            if self._solver is not None:
+                self._solver.refresh()
+            return self.__dict__["_" + name]
+        return property(get, lambda self, v: self.__dict__.__setitem__("_" + name, v))
+    com, rot, vel, angvel = _get("com"), _get("rot"), _get("vel"), _get("angvel")
+    force, torque, impulse, angular_impulse = _get("force"), _get("torque"), _get("impulse"), _get("angular_impulse")
+    del _get
+
+
 class _DeviceVelocities:
     """container.rigid_body_velocities of the device backend: the container's array, brought up to date before it is read."""
 
@@ -135,6 +167,7 @@ class HostRigidSolver:
         self.rigid_bodies = container.cfg.get_rigid_bodies()
         self.rigid_blocks = container.cfg.get_rigid_blocks()
         self.bodies = {}   # object id -> _Body (dynamic ones)
+        self.scripted = {}   # object id -> _Scripted (bodies with a motion program)
         # the container's rigid_backend option (run_simulation.py --rigid_backend) first, then SPH_RIGID_BACKEND
         self.backend = getattr(container, "rigid_backend", None) or os.environ.get("SPH_RIGID_BACKEND", "native")
         self._bullet = None
@@ -156,6 +189,9 @@ class HostRigidSolver:
         self.contact = None              # the host's solver ("contact")
         self.contact_parameters = None   # ... and the ContactSolver that holds its parameters ("contact" and "device_contact")
         dynamic = any(b["isDynamic"] for b in self.rigid_bodies)
+        scripted = any(is_scripted(b) for b in self.rigid_bodies)
+        if scripted and self.backend == "pybullet":
+            raise ValueError("motion: the pybullet rigid backend does not move scripted bodies")
         pbf = getattr(container, "METHOD", None) == "pbf"
         if pbf and self.backend in ("contact", "device", "device_contact"):
             what = {"contact": "contact", "device": "the device integrator", "device_contact": "the device contact solver"}[self.backend]
@@ -177,10 +213,10 @@ class HostRigidSolver:
             self.contact_parameters = solver
             if self.backend == "contact":
                 self.contact = solver   # the host solves
-        if self.backend in ("device", "device_contact") and dynamic and not pbf:
+        if self.backend in ("device", "device_contact") and (dynamic or scripted) and not pbf:
             # (a sharded scene: the library refuses, and the error is the caller's)
             container.engine.set_rigid_integrator(True, self.gravity, self.wall_lo, self.wall_hi)
-            if self.backend == "device_contact":   # the device solves, with the parameters the host solver would use
+            if self.backend == "device_contact" and dynamic:   # the device solves, with the parameters the host solver would use
                 container.engine.set_rigid_contact_solver(True, solver.e, solver.mu, solver.iterations, solver.beta, solver.slop,
                                                           solver.patch)
             container.rigid_body_velocities = _DeviceVelocities(np.asarray(container.rigid_body_velocities), self)
@@ -193,6 +229,9 @@ class HostRigidSolver:
             if oid in self.present_rigid_object or body["entryTime"] > self.total_time:
                 continue
             self.present_rigid_object.append(oid)
+            if is_scripted(body):
+                self._insert_scripted(body)
+                continue
             if not body["isDynamic"]:
                 continue
             c = self.container
@@ -231,19 +270,49 @@ class HostRigidSolver:
         for _ in self.rigid_blocks:
             raise NotImplementedError  # bullet_solver.py:133-135
 
+    def _insert_scripted(self, body):
+        """A scripted body enters with the zero-velocity pose of the time the running step ends at (prepare(): t = 0)."""
+        c, oid = self.container, body["objectId"]
+        motion = body.get("motionProgram") or RigidMotion.from_body(body, self.dt, method=getattr(c, "METHOD", None), dim=c.dim,
+                                                                    backend=self.backend)
+        pts = np.asarray(body["voxelizedPoints"], dtype=np.float64)
+        com, rot = motion.pose(c.entry_step() * motion.dt)
+        self.refresh()
+        s = (_DeviceScripted if self.on_device else _Scripted)(oid, motion, com, rot, pts)
+        self.scripted[oid] = s
+        if self.on_device:   # the program goes to the device once; its launch moves the body from the next step on
+            com_rest, rot_rest = motion.rest()
+            c.engine.set_rigid_motion(oid, motion.to_struct(), com_rest, rot_rest, com0=np.zeros(3))
+            s._solver = self
+        else:
+            self._push(s, com0=np.zeros(3))
+        c.rigid_body_velocities[oid] = np.zeros(3)
+
+    def scripted_wrench(self, oid):
+        """(force, torque, impulse, angular impulse) of a scripted body: the fluid wrench its last step consumed and the sums of
+        dt * force, dt * torque since it entered -- what wave tanks are validated with."""
+        s = self.scripted[oid]
+        return s.force.copy(), s.torque.copy(), s.impulse.copy(), s.angular_impulse.copy()
+
     def _push(self, b, com0=None):
         self.container.engine.set_rigid_pose(b.oid, b.com, b.rot, b.vel, b.angvel, com0=com0)
         self.container.rigid_body_velocities[b.oid] = b.vel
 
     # ------------------------------------------------------------------ bullet_solver.py:144-167
     def step(self):
-        if not self.bodies:
+        if not self.bodies and not self.scripted:
             return
         if self.on_device:
             self.container.engine.rigid_integrate()
             self._stale = True
             return
         force, torque = self.container.engine.get_rigid_wrench(reset=True)
+        for s in self.scripted.values():   # every rank of a sharded scene evaluates the same closed form of the step count
+            s.com, s.rot, s.vel, s.angvel = s.motion.step(self.container.step_count)
+            s.force, s.torque = force[s.oid].astype(np.float64), torque[s.oid].astype(np.float64)
+            s.impulse = s.impulse + self.dt * s.force
+            s.angular_impulse = s.angular_impulse + self.dt * s.torque
+            self._push(s)
         if self.contact is not None:
             table = self.container.engine.get_rigid_contacts(reset=True)
             self.contact.step(self.bodies, force.astype(np.float64), torque.astype(np.float64), contacts_from_table(table, self.bodies))
@@ -284,7 +353,7 @@ class HostRigidSolver:
 
     def mark_stale(self):
         """The device has stepped: what the host holds of the bodies' state is out of date."""
-        self._stale = self.on_device and bool(self.bodies)
+        self._stale = self.on_device and bool(self.bodies or self.scripted)
 
     def refresh(self):
         """Device backend: bring the bodies' state back (one small copy per body, after draining the stream) if the device has stepped
@@ -295,9 +364,14 @@ class HostRigidSolver:
         for oid, b in self.bodies.items():
             b.com, b.rot, b.vel, b.angvel = self.container.engine.get_rigid_state(oid)
             self.container.rigid_body_velocities[oid] = b.vel
+        for oid, s in self.scripted.items():
+            st = self.container.engine.get_rigid_motion_state(oid)
+            for name in ("com", "rot", "vel", "angvel", "force", "torque", "impulse", "angular_impulse"):
+                setattr(s, name, st[name])
+            self.container.rigid_body_velocities[oid] = st["vel"]
 
     def get_rigid_body_states(self, container_idx):
-        b = self.bodies[container_idx]
+        b = self.bodies.get(container_idx) or self.scripted[container_idx]
         return {"position": b.com.copy(), "rotation_matrix": b.rot.copy(), "linear_velocity": b.vel.copy(),
                 "angular_velocity": b.angvel.copy()}
 

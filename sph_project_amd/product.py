@@ -175,6 +175,39 @@ def coupling_scene(method="dfsph", models_dir=None, fluid_end=(2.3, 1.4, 2.38)):
     }
 
 
+def wave_tank_scene(method="wcsph", length=2.4, width=0.5, depth=0.24, stroke=0.03, frequency=1.0, dt=4e-4, radius=0.01,
+                    models_dir=None):
+    """A wave tank with a piston paddle, the first scene a scripted rigid body is for: a shallow layer of water (depth)
+    in a long tank (length along x, width along z) and, at the -x end, a plate -- tests/golden/models/cube.obj scaled to three particle
+    layers in x, one and a half water depths in y, the water's width in z -- that a harmonic program moves along x with amplitude
+    `stroke` at `frequency`, ramped in over one period.  The sizes go down to a few hundred particles
+    (length=0.5, width=0.2, depth=0.06)."""
+    import os
+    models = models_dir or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "models")
+    d, edge, m = 2.0 * radius, 0.298142, 6.0 * radius   # particle diameter, cube.obj's edge, margin to the domain faces
+    plate = [3 * d, 1.5 * depth, width - 2 * m]
+    plate_x = m + 0.5 * plate[0] + stroke + d
+    return {
+        "Configuration": {
+            "domainStart": [0.0, 0.0, 0.0], "domainEnd": [length, max(3.0 * depth, 0.3), width], "addDomainBox": False,
+            "particleRadius": radius, "density0": 1000, "simulationMethod": method, "viscosityMethod": "standard",
+            "gravitation": [0.0, -9.81, 0.0], "timeStepSize": dt, "viscosity": 10.0,
+        },
+        "RigidBodies": [{
+            "objectId": 1, "geometryFile": os.path.join(models, "cube.obj"), "translation": [plate_x, m + 0.5 * plate[1], 0.5 * width],
+            "rotationAxis": [0.0, 1.0, 0.0], "rotationAngle": 0.0, "scale": [p / edge for p in plate], "velocity": [0.0, 0.0, 0.0],
+            "density": 1000.0, "color": [230, 180, 60], "isDynamic": False, "entryTime": -1.0,
+            "motion": {"harmonic": {"frequency": frequency, "ramp": 1.0 / frequency if frequency > 0 else 0.0,
+                                    "direction": [1.0, 0.0, 0.0], "amplitude": stroke}},
+        }],
+        "FluidBlocks": [{
+            "objectId": 0, "start": [plate_x + 0.5 * plate[0] + stroke + 2 * d, m, m], "end": [length - m, m + depth, width - m],
+            "translation": [0.0, 0.0, 0.0], "scale": [1, 1, 1], "velocity": [0.0, 0.0, 0.0], "density": 1000.0,
+            "color": [50, 100, 200], "entryTime": -1.0,
+        }],
+    }
+
+
 def scene_particles(cfg_dict):
     """Host lattice of every object present at prepare(), in the reference's insertion order
     (domain box first: base_container.py:192, then FluidBlocks: :215).  Blocks with entryTime > 0 are listed with
