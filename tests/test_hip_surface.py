@@ -10,75 +10,34 @@ from sph_project_amd import _lib as L
 from sph_project_amd import product as P
 from sph_project_amd.surface import SPH_ERR_CAPACITY, SurfaceError, SurfaceReconstructor
 from tests import helpers as H
+from tests import surface_cases as SC
 from tests import surface_model as SM
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24   # unit roundoff of f32
-
-# (name, particles, cube_size): a jittered block with a coarse grid (B = 7, 4 points per thread), a ball at the defaults (B = 14, 12 per
-# thread), a torus in between (B = 10)
-CASES = {
-    "block": (lambda: SM.jittered_block((0.1, 0.12, 0.09), (14, 12, 10), 0.02, 0.3, 7), 1.0),
-    "ball": (lambda: SM.lattice_ball((0.31, 0.27, 0.33), 0.1, 0.02), 0.5),
-    "torus": (lambda: SM.lattice_torus((0.5, 0.5, 0.5), 0.15, 0.06, 0.02), 0.75),
-}
+# the three smooth shapes (tests/surface_cases.py): a jittered block with a coarse grid (B = 7, P = 343: 4 points per thread), a ball at
+# the defaults (B = 14, 12 per thread, one part) and a torus at B = 10 (P = 1000: the 4-points-per-thread kernel again).  The paths these
+# three never take -- 8 per thread, bricks in parts, chunked runs, the scan's carry, the other table rows -- are forced in
+# tests/test_hip_surface_paths.py
+CASES = SC.SMOOTH_CASES
 
 
 @pytest.fixture(scope="module")
 def models():
-    out = {}
-    for name, (make, c) in CASES.items():
-        x = make()
-        t = SM.clear_iso(SM.reconstruct(x, 0.01, cube_size=c, normals=False)["phi"])
-        out[name] = (x, c, t, SM.reconstruct(x, 0.01, cube_size=c, iso=t))
-    return out
+    return {name: SC.model(name) for name in CASES}
 
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_mesh_matches_the_model(gpu, models, name):
-    x, c, t, m = models[name]
-    # no grid value near the iso value: the f32 field has the model's signs (bound below), so the topology must match exactly
-    margin = np.abs(m["phi"] - t).min()
-    assert margin > 1e-4, margin
-    # error estimate of one f32 grid value: V_j = 1 / (a sum of <= N terms) and phi = a sum of <= N terms V_j W_j, every term within a few
-    # ulp of its f64 value, recursive summation (N - 1) u of the sum of |terms| (phi itself: all terms are positive), plus the f32
-    # rounding of the grid point's position (u |x|) times the largest |grad phi|.  N = the most particles within h of a point.
-    N = m["field"].n_max
-    assert N > 50
-    ga = m["grad_abs"].max()
-    d_phi = (2 * N + 12) * U * 1.0 + U * np.abs(m["vertices"]).max() * ga
-    assert d_phi < 0.5 * margin, (d_phi, margin)
+    SC.check_mesh_against_model(*models[name], label=name)
 
-    r = SurfaceReconstructor(0.01, cube_size=c, iso=t)
-    v, tri, nrm = r.from_points(x)
-    st = r.stats()
-    assert (st["vertices"], st["triangles"]) == (len(m["vertices"]), len(m["triangles"]))
-    assert st["active_bricks"] == len(m["bricks"]) and st["points_evaluated"] == len(m["bricks"]) * m["B"] ** 3
-    assert st["B"] == m["B"]
-    assert np.array_equal(tri, m["triangles"])
-    # vertices: the interpolation parameter s = (t - f0) / (f1 - f0) moves by <= 2 d_phi / |f1 - f0| (+ a few ulp of the division and of
-    # the grid coordinate); in units of the cube edge
-    e = m["e"]
-    f0, f1 = m["v_phi"][:, 0], m["v_phi"][:, 1]
-    tol_s = 2 * d_phi / np.abs(f1 - f0) + 8 * U * (1 + np.abs(m["vertices"]).max() / e)
-    err = np.abs(v.astype(np.float64) - m["vertices"]).max(axis=1) / e
-    assert (err <= tol_s).all(), (err / tol_s).max()
-    firm = tol_s <= 1e-3
-    assert firm.mean() > 0.8 and (err[firm] <= 1e-3).all()
-    # normals: grad phi is a sum of <= N terms (error (2 N + 12) u sum |V grad W|), evaluated at a vertex that moved by err e; the
-    # change of grad phi over that distance is bounded by |Hessian| <= 6 sum |V grad W| / h (cubic spline: |W''| <= 6 |W'|_max / h
-    # scale), so the direction turns by at most that over |grad phi|
-    g, gabs = m["grad_norm"], m["grad_abs"]
-    tol_a = ((2 * N + 12) * U * gabs + 6 * gabs / m["h"] * tol_s * e) / g + 4 * U
-    ang = np.arccos(np.clip(np.einsum("ij,ij->i", nrm.astype(np.float64), m["normals"]), -1.0, 1.0))
-    # (arccos near 1 loses digits: compare through the chord as well)
-    chord = np.linalg.norm(nrm.astype(np.float64) - m["normals"], axis=1)
-    ang = np.minimum(ang, 2 * np.arcsin(np.clip(chord / 2, 0, 1)))
-    assert (ang <= tol_a + 1e-6).all(), (ang - tol_a).max()
-    firm_n = tol_a <= 1e-3
-    assert firm_n.mean() > 0.8 and (ang[firm_n] <= 1e-3).all()
-    assert SM.closed_and_oriented(tri)
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_fast_build_mesh_matches_the_model(gpu, models, name):
+    """The fast build (reciprocal-multiply binning, q = r * (1 / h), fused multiply-adds) gives the model's triangles and counts, and
+    vertices and normals within the strict build's bounds: the extra rounding of 1 / h is one more ulp per term, inside the 12 u the
+    bound allows per term."""
+    SC.check_mesh_against_model(*models[name], fast_math=True, label=name)
 
 
 def test_bytes_do_not_depend_on_runs_or_particle_order(gpu, models):

@@ -29,8 +29,9 @@ def _mixed():
     return np.concatenate([block, sheet, drop]).astype(np.float32)
 
 
-# (particles, cube_size): B = 7 (4 points per thread) except the ball at the defaults (B = 14, 12 per thread) and a small sheet at
-# cube_size 0.6 (B = 12, 8 per thread)
+# (particles, cube_size): B = 7 (4 points per thread) except the ball at the defaults (B = 14, 12 per thread, one part) and a small sheet
+# at cube_size 0.6 (B = 12, 8 per thread, one part), 0.45 (B = 16, 8 per thread, two full parts) and 0.42 (B = 17, 12 per thread, two
+# parts, the last one partial: 1841 of 3072 points)
 CASES = {
     "sheet1": (lambda: AM.lattice((12, 12, 1), SPACING, ORIGIN).astype(np.float32), 1.0),
     "sheet2": (lambda: AM.lattice((12, 12, 2), SPACING, ORIGIN).astype(np.float32), 1.0),
@@ -39,6 +40,8 @@ CASES = {
     "mixed": (_mixed, 1.0),
     "ball": (lambda: SM.lattice_ball((0.31, 0.27, 0.33), 0.1, 0.02), 0.5),
     "sheet_b12": (lambda: AM.lattice((8, 7, 1), SPACING, ORIGIN).astype(np.float32), 0.6),
+    "sheet_b16": (lambda: AM.lattice((8, 7, 1), SPACING, ORIGIN).astype(np.float32), 0.45),
+    "sheet_b17": (lambda: AM.lattice((8, 7, 1), SPACING, ORIGIN).astype(np.float32), 0.42),
 }
 
 
@@ -163,7 +166,8 @@ def test_particles_and_mesh_match_the_model(gpu, models, name):
 
 
 def test_every_field_instantiation_is_covered(models):
-    assert {models[n][3]["B"] ** 3 for n in CASES} >= {343, 1728, 2744}   # 4, 8 and 12 points per thread (l_surf_field_aniso)
+    # 4, 8 and 12 points per thread in one part, 8 in two full parts, 12 in two parts with a partial one (l_surf_field_aniso)
+    assert {models[n][3]["B"] ** 3 for n in CASES} >= {343, 1728, 2744, 4096, 4913}
 
 
 def test_bytes_do_not_depend_on_runs_or_particle_order(gpu, models):

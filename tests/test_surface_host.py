@@ -124,6 +124,59 @@ def test_model_mesh_does_not_depend_on_particle_order():
     assert np.array_equal(a["triangles"], b["triangles"]) and np.allclose(a["vertices"], b["vertices"], rtol=0, atol=1e-12)
 
 
+# --- the inputs of tests/test_hip_surface_paths.py force what they claim ------------------------------------------------------------
+
+def test_path_cases_force_their_device_paths():
+    """On the model alone: every condition under which a case of tests/surface_cases.py takes the device path it is there for, so that an
+    edit of an input that loses the path fails here, on any machine, and not silently on the GPU."""
+    from tests import surface_cases as SC
+    hist = {name: SM.case_histogram(SC.model(name)[3], SC.model(name)[2]) for name in list(SC.PATH_CASES) + list(SC.SMOOTH_CASES)}
+    for name, (_, c, B, _) in list(SC.PATH_CASES.items()) + list(SC.SMOOTH_CASES.items()):
+        x, c_, t, m = SC.model(name)
+        assert c_ == c and m["B"] == B == SM.derived(SC.RADIUS, cube_size=c)[2], name
+        assert SM.closed_and_oriented(m["triangles"]), name
+        margin, N, d_phi = SC.field_error(m, t)
+        print(f"{name}: n {len(x)} B {B} iso {t:.6f} margin {margin:.2e} N {N} d_phi {d_phi:.2e} vertices {len(m['vertices'])} "
+              f"triangles {len(m['triangles'])} bricks {len(m['bricks'])} cases {np.count_nonzero(hist[name])}")
+        assert margin > 1e-4 and d_phi < 0.5 * margin, (name, margin, d_phi)
+        assert hist[name].sum() == len(m["bricks"]) * B ** 3
+    # the case table: the smooth shapes read fewer than half of its rows, the path cases all but UNREAD_ROWS (250 is a floor that a smooth
+    # input cannot meet, not the target)
+    old = sum(hist[name] for name in SC.SMOOTH_CASES)
+    new = sum(hist[name] for name in SC.PATH_CASES)
+    assert np.count_nonzero(old) < 128
+    assert np.count_nonzero(new) >= 250
+    assert tuple(np.nonzero(new == 0)[0]) == SC.UNREAD_ROWS
+    assert np.count_nonzero(hist["cloud"]) >= 250 and hist["cloud2"][150] > 0 and hist["cloud2"][182] > 0
+    # the field pass: points per thread and parts as l_surf_field chooses them from P = B^3
+    def dispatch(B):
+        P = B ** 3
+        parts = -(-P // (256 * 12))
+        need = -(-P // (256 * parts))
+        ppt = 4 if need <= 4 else 8 if need <= 8 else 12
+        launched = -(-P // (256 * ppt))
+        return ppt, launched, P - (launched - 1) * 256 * ppt
+    assert [dispatch(SC.PATH_CASES[n][2]) for n in ("cloud", "ball_b11", "ball_b12", "ball_b16", "ball_b17", "dense_b4")] == \
+        [(4, 1, 8), (8, 1, 1331), (8, 1, 1728), (8, 2, 2048), (12, 2, 1841), (4, 1, 64)]
+    assert {dispatch(SC.SMOOTH_CASES[n][2])[:2] for n in SC.SMOOTH_CASES} == {(4, 1), (12, 1)}   # what the smooth shapes cover
+    # chunks of 1024: a run longer than one chunk, in both dense cases; no other input comes near
+    for name in ("dense_b2", "dense_b4"):
+        x, c, _, m = SC.model(name)
+        assert SM.longest_run(x, SC.RADIUS, c) >= 1025
+        assert SC.model_pair_tests(m) == 27 * len(x) * m["B"] ** 3   # every particle is staged by the 27 bricks around its cell
+    assert max(SM.longest_run(SC.model(n)[0], SC.RADIUS, SC.model(n)[1]) for n in SC.SMOOTH_CASES) < 1024
+    # the scan: more than 256 tiles of 1024 coarse cells, so that its top level runs a second round; one cluster all negative
+    x, c, _, _ = SC.model("wide")
+    assert SM.coarse_cells(x, SC.RADIUS, c) > 262144
+    assert (x[:33] < 0).all() and (x[33:] > 0).all()
+    assert max(SM.coarse_cells(SC.model(n)[0], SC.RADIUS, SC.model(n)[1]) for n in SC.SMOOTH_CASES) < 262144
+    # one particle; bit-identical duplicates in one cell
+    assert len(SC.model("one")[0]) == 1
+    x = SC.model("dup")[0]
+    _, counts = np.unique(x.view(np.dtype((np.void, 12))), return_counts=True)
+    assert sorted(counts)[-10:] == [1, 1, 1, 2, 2, 2, 2, 3, 3, 3] and len(x) == 43
+
+
 # --- OBJ writer ------------------------------------------------------------------------------------------------------------------
 
 def _read_obj(path):
