@@ -144,6 +144,11 @@ typedef enum {
     SPH_F_CG_DINV = 41,            /* f32[n][9] cg_diagnol_ii_inv, row-major (:303-308) */
     SPH_F_CG_AP_PARTS = 42,        /* f32[3][n][3] the per-x-offset-group parts of sum_j D_i^-1 (-A_ij) p_j of the last SPLIT A p walk, before
                                       dt / rho0 and + p_i: A p = ((part_0 + part_1) + part_2) dt / rho0 + p */
+    /* Akinci surface tension (allocated when sph_set_surface_tension first switches the mode on), download only: the colour-field
+       normals n_i = h sum_j (m_j / rho_j) gradW_ij the last SPH_PH_SURFACE_NORMALS (or step) stored.  Written on fluid rows only.  Not
+       carried through the sort (recomputed every step): valid until the next sort, like SPH_F_NON_PRESSURE_ACCEL of a handle that is
+       not PCISPH's (DFSPH sorts in the second half of its step: read both between sph_step_begin and sph_step_end). */
+    SPH_F_SURFACE_NORMAL = 43,     /* f32[n][3] */
     SPH_F_COUNT_
 } SphField;
 
@@ -190,6 +195,10 @@ typedef enum {
                                   NOTHING and returns SPH_OK: cg_p, beta and the error change only with the next SPH_PH_CG_AP */
     SPH_PH_CG_END = 27,        /* :514-517: the viscous acceleration from the solved velocities + gravity + surface tension, v += dt a on the
                                   original velocities, the reaction on dynamic bodies, prepare_guess */
+    /* Akinci surface tension (sph_set_surface_tension; SPH_ERR_INVALID while the mode is off): the normal pass alone, on the masks of
+       the last sort.  In this mode SPH_PH_NON_PRESSURE (and SPH_PH_CG_END) run the Akinci pass on the STORED normals, without
+       recomputing them; a step computes them in front of its non-pressure pass. */
+    SPH_PH_SURFACE_NORMALS = 28,
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -235,6 +244,7 @@ typedef enum {
     SPH_K_PBFC_DENSITY_LAMBDA = 28, SPH_K_PBFC_DELTA = 29,   /* consistent PBF: walk A, walk B (predict / finish: SPH_K_PBF_UPDATE) */
     SPH_K_RIGID_MOTION = 30,   /* scripted rigid bodies: the launch that evaluates their motion programs (sph_set_rigid_motion);
                                   sph_kernel_name's table ends at 29 and answers "?" for this id */
+    SPH_K_SURFACE_NORMALS = 31, /* Akinci surface tension: the normal pass (the Akinci force pass itself is SPH_K_NON_PRESSURE); "?" as well */
     SPH_K_COUNT_
 } SphKernelId;
 
@@ -308,6 +318,27 @@ int sph_set_pbf_variant(SphHandle *h, const SphPbfParams *params);
    its fixed 5, and 0).  A query of its own: the statistics struct ends at pbf_recentred by contract. */
 typedef struct { int32_t variant, iterations; float error; } SphPbfStats;
 int sph_get_pbf_stats(SphHandle *h, SphPbfStats *out);
+
+/* Surface tension model (opt-in).  method 0 = reference (the reference's pairwise -sigma m_j / m_i R W(r) with
+   SphParams::surface_tension, the default), 1 = akinci: Akinci, Akinci, Teschner 2013.  With h the support radius, W the cubic spline,
+   rho the density the viscous term of the method reads, j fluid and k boundary neighbours of an active fluid particle i:
+     n_i = h sum_j (m_j / rho_j) gradW_ij,   K_ij = 2 rho0 / (rho_i + rho_j),   Psi_k = rho0 V_k
+     a_i = -gamma sum_j K_ij (m_j C(r) (x_i - x_j) / r + n_i - n_j)  -  beta sum_k Psi_k A(r) (x_i - x_k) / r
+     C(r) = 32 / (pi h^9) { (h-r)^3 r^3 : h/2 < r <= h;  2 (h-r)^3 r^3 - h^6 / 64 : 0 < r <= h/2 },
+     A(r) = 0.007 / h^3.25 (-4 r^2 / h + 6 r - 2 h)^(1/4) : h/2 < r <= h   (radicand clamped at 0)
+   in the place of the reference's term; gravity, viscosity and v += dt a stay.  A dynamic rigid neighbour k receives
+   +m_i beta Psi_k A(r) (x_i - x_k) / r at x_k.  WCSPH takes its unfused route in this mode (density, normals, non-pressure,
+   pressure: SPH_K_WCSPH_FORCES does not run).  Legal at any time between steps; switching back to 0 restores the reference path
+   bit for bit.  gamma, beta are kept while the method is 0.
+   SPH_ERR_UNSUPPORTED: a PBF handle (either variant), a sharded handle (and sph_comm_set_slab while the mode is on).  This library
+   has no 2-D handles; the Python front end refuses 2-D scenes.  SPH_ERR_INVALID: gamma or beta negative or not finite, an unknown method.
+   sph_surface_tension_kernels_host: C(r) and A(r) of the kernels' source on the CPU, strict (fast = 0) or fast form.  No device. */
+#define SPH_SURFACE_TENSION_REFERENCE 0
+#define SPH_SURFACE_TENSION_AKINCI 1
+typedef struct { int32_t method; double gamma, beta; } SphSurfaceTensionParams;
+int sph_set_surface_tension(SphHandle *h, const SphSurfaceTensionParams *params);
+int sph_get_surface_tension(SphHandle *h, SphSurfaceTensionParams *out);
+int sph_surface_tension_kernels_host(double h, const float *r, int64_t n, float *C_out, float *A_out, int fast);
 
 /* Device rigid integrator (opt-in; the host's "device" rigid backend).  The physics of the host's native backend
    (SPH/rigid_solver/host_rigid_solver.py integrate: semi-implicit Euler in float64 under gravity and the fluid wrench, gyroscopic

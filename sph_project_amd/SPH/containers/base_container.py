@@ -73,6 +73,10 @@ class BaseContainer:
         self.domain_start, self.domain_end, self.domain_size = geo.domain_start, geo.domain_end, geo.domain_size
         assert self.domain_start[1] >= 0.0, "domain start y should be greater than 0"
         self.dim = geo.dim
+        # surface tension model: a bad key raises here, before a device is opened
+        self.surface_tension_method, self.surface_tension, self.surface_adhesion = scene.surface_tension_of(config, self.METHOD, geo.dim)
+        if self.surface_tension_method == "akinci" and engine_opts.get("slab"):
+            raise ValueError("Configuration.surfaceTensionMethod \"akinci\" is not available on a sharded scene (--gpus > 1)")
         self.material_rigid, self.material_fluid = scene.MATERIAL_RIGID, scene.MATERIAL_FLUID
         self.dx, self.particle_diameter, self.dh = geo.dx, geo.particle_diameter, geo.dh
         self.particle_spacing, self.V0 = geo.particle_spacing, geo.V0
@@ -151,6 +155,8 @@ class BaseContainer:
         p.deterministic = int(engine_opts.get("deterministic", 1))
         self.params_dict = pd
         self.engine = F.Engine(p)
+        if self.surface_tension_method == "akinci":
+            self.engine.set_surface_tension("akinci", self.surface_tension, self.surface_adhesion)
         # multi-GPU: engine_opts["slab"] = dict(rank=, nranks=, unique_id=<128 bytes>, cuts=[...]) -> this container
         # only inserts the particles of its own z-slab (sph_project_amd/slab.py)
         self.slab = engine_opts.get("slab")

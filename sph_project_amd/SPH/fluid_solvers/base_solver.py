@@ -31,7 +31,12 @@ class BaseSolver:
         self.viscosity = sol.viscosity
         self.viscosity_b = sol.viscosity_b
         self.density_0 = sol.density_0
-        self.surface_tension = sol.surface_tension
+        # the surface tension model: under "reference" the coefficient is the reference's fixed 0.01 (base_solver.py:32),
+        # under "akinci" it is gamma (scene key surfaceTension) and surface_adhesion is beta (surfaceAdhesion)
+        self.surface_tension_method = getattr(container, "surface_tension_method", "reference")
+        akinci = self.surface_tension_method == "akinci"
+        self.surface_tension = container.surface_tension if akinci else sol.surface_tension
+        self.surface_adhesion = container.surface_adhesion if akinci else 0.0
         self.dt = _DtField(sol.dt)
         self.rigid_solver = PyBulletSolver(container, gravity=self.g, dt=self.dt[None])
         self.engine = container.engine

@@ -26,6 +26,8 @@ METHOD = {"wcsph": 0, "dfsph": 1, "pcisph": 2, "iisph": 3, "pbf": 4}
  F_RIGID_CONTACT_COUNT, F_NON_PRESSURE_ACCEL) = range(36)
 # implicit viscosity, download only: the CG vectors, D^-1 (n, 9) and the three parts of a split A p walk (3, n, 3)
 F_CG_B, F_CG_R, F_CG_P, F_CG_AP, F_CG_V0, F_CG_DINV, F_CG_AP_PARTS = range(36, 43)
+# Akinci surface tension, download only: the colour-field normals (fluid rows)
+F_SURFACE_NORMAL = 43
 
 _FIELD_SPEC = {  # field -> (dtype, components)
     F_POSITION: (np.float32, 3), F_VELOCITY: (np.float32, 3), F_ACCELERATION: (np.float32, 3),
@@ -41,7 +43,7 @@ _FIELD_SPEC = {  # field -> (dtype, components)
     F_PBF_OLD_POSITION: (np.float32, 3), F_PBF_LAMBDA: (np.float32, 1),
     F_RIGID_CONTACT_DN: (np.float32, 3), F_RIGID_CONTACT_COUNT: (np.float32, 1), F_NON_PRESSURE_ACCEL: (np.float32, 3),
     F_CG_B: (np.float32, 3), F_CG_R: (np.float32, 3), F_CG_P: (np.float32, 3), F_CG_AP: (np.float32, 3), F_CG_V0: (np.float32, 3),
-    F_CG_DINV: (np.float32, 9), F_CG_AP_PARTS: (np.float32, 9),
+    F_CG_DINV: (np.float32, 9), F_CG_AP_PARTS: (np.float32, 9), F_SURFACE_NORMAL: (np.float32, 3),
 }
 
 # enum SphPhase
@@ -57,6 +59,8 @@ PH_DFSPH_ALPHA_DIVERGENCE = 22
 # implicit viscosity: the launches of the CG solve inside PH_NON_PRESSURE one pass each (PH_CG_UPDATE_P launches nothing where the step
 # folds the p update into the next A p pass)
 PH_CG_PREPARE, PH_CG_AP, PH_CG_UPDATE_XR, PH_CG_UPDATE_P, PH_CG_END = 23, 24, 25, 26, 27
+# Akinci surface tension: the normal pass alone (PH_NON_PRESSURE then runs on the stored normals)
+PH_SURFACE_NORMALS = 28
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
@@ -70,6 +74,7 @@ K_RIGID_CONTACT_SOLVE = 27   # sph_kernel_name(27) == "rigid_contact_solve": the
 K_PBFC_DENSITY_LAMBDA = 28   # sph_kernel_name(28) == "pbfc_density_lambda": walk A of the consistent PBF variant
 K_PBFC_DELTA = 29            # sph_kernel_name(29) == "pbfc_delta": its walk B
 K_RIGID_MOTION = 30          # SPH_K_RIGID_MOTION: the launch that moves the scripted rigid bodies (sph_kernel_name's table ends at 29)
+K_SURFACE_NORMALS = 31       # SPH_K_SURFACE_NORMALS: the normal pass of the Akinci surface tension
 RIGID_MOTION_MAX_KEYS = 64
 
 # rigid contact table (sph_get_rigid_contacts): [object A][partner B][normal bin][value]; partners 20..25 are the domain box /
@@ -147,6 +152,24 @@ PBF_VARIANTS = {"reference": 0, "consistent": 1}
 class SphPbfParams(C.Structure):
     _fields_ = [("variant", C.c_int32), ("min_iterations", C.c_int32), ("max_iterations", C.c_int32), ("max_error", C.c_float),
                 ("epsilon", C.c_float)]
+
+
+SURFACE_TENSION_METHODS = {"reference": 0, "akinci": 1}
+
+
+class SphSurfaceTensionParams(C.Structure):
+    _fields_ = [("method", C.c_int32), ("gamma", C.c_double), ("beta", C.c_double)]
+
+
+def surface_tension_kernels_host(h, r, fast=False):
+    """(C(r), A(r)) of the Akinci splines from the kernels' own source run on the CPU (sph_surface_tension_kernels_host), float32.
+    No device."""
+    r = np.ascontiguousarray(r, dtype=np.float32).reshape(-1)
+    c_out, a_out = np.empty_like(r), np.empty_like(r)
+    rc = load().sph_surface_tension_kernels_host(float(h), _ptr(r), r.shape[0], _ptr(c_out), _ptr(a_out), int(bool(fast)))
+    if rc:
+        raise SphError(f"sph_surface_tension_kernels_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
+    return c_out, a_out
 
 
 class SphPbfStats(C.Structure):
@@ -401,6 +424,9 @@ _SIGNATURES = [
     ("sph_get_rigid_contact_pairs", C.c_int, [_VP, C.POINTER(C.c_int64)]),
     ("sph_set_pbf_variant", C.c_int, [_VP, C.POINTER(SphPbfParams)]),
     ("sph_get_pbf_stats", C.c_int, [_VP, C.POINTER(SphPbfStats)]),
+    ("sph_set_surface_tension", C.c_int, [_VP, C.POINTER(SphSurfaceTensionParams)]),
+    ("sph_get_surface_tension", C.c_int, [_VP, C.POINTER(SphSurfaceTensionParams)]),
+    ("sph_surface_tension_kernels_host", C.c_int, [C.c_double, _VP, C.c_int64, _VP, _VP, C.c_int]),
     # device rigid integrator; what each stands in for in the reference's SPH/rigid_solver/bullet_solver.py:
     ("sph_set_rigid_integrator", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),                        # :19-71 __init__ (gravity, dt, walls)
     ("sph_set_rigid_body", C.c_int, [_VP, C.c_int, C.c_double] + [_VP] * 7 + [C.c_int]),        # :75-131 insert_rigid_object
@@ -723,6 +749,17 @@ class Engine(NativeObject):
         st = SphPbfStats()
         self._chk(self.lib.sph_get_pbf_stats(self.h, C.byref(st)), "sph_get_pbf_stats")
         return struct_dict(st)
+
+    # -- surface tension model
+    def set_surface_tension(self, method="akinci", gamma=1.0, beta=0.0):
+        """method: "reference" / "akinci" (or 0 / 1); gamma, beta: cohesion and adhesion coefficients of the Akinci model."""
+        p = SphSurfaceTensionParams(int(SURFACE_TENSION_METHODS.get(method, method)), float(gamma), float(beta))
+        self._chk(self.lib.sph_set_surface_tension(self.h, C.byref(p)), "sph_set_surface_tension")
+
+    def get_surface_tension(self):
+        p = SphSurfaceTensionParams()
+        self._chk(self.lib.sph_get_surface_tension(self.h, C.byref(p)), "sph_get_surface_tension")
+        return {"method": {v: k for k, v in SURFACE_TENSION_METHODS.items()}[p.method], "gamma": p.gamma, "beta": p.beta}
 
     # -- device rigid integrator (the "device" rigid backend)
     def set_rigid_integrator(self, on=True, gravity=(0.0, 0.0, 0.0), wall_lo=(0.0, 0.0, 0.0), wall_hi=(0.0, 0.0, 0.0)):

@@ -578,6 +578,48 @@ extern "C" int sph_get_pbf_stats(SphHandle *h, SphPbfStats *out) {
     return SPH_OK;
 }
 
+// ---------------------------------------------------------------------------------- Akinci surface tension
+#include "sph_surface_tension.hpp"
+extern "C" int sph_set_surface_tension(SphHandle *h, const SphSurfaceTensionParams *p) {
+    if (!h) return SPH_ERR_INVALID;
+    if (!p) return fail(h, SPH_ERR_INVALID, "sph_set_surface_tension: null argument");
+    if (h->prm.method == SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_surface_tension: not on a PBF handle (either variant)");
+    if (h->st.slab_active || h->comm.slab_ready)
+        return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_surface_tension: not on a sharded handle (the ghosts' normals would need an exchange)");
+    if (p->method != SPH_SURFACE_TENSION_REFERENCE && p->method != SPH_SURFACE_TENSION_AKINCI)
+        return fail(h, SPH_ERR_INVALID, "sph_set_surface_tension: method %d is neither 0 (reference) nor 1 (akinci)", p->method);
+    if (!(p->gamma >= 0.0) || !std::isfinite(p->gamma)) return fail(h, SPH_ERR_INVALID, "sph_set_surface_tension: gamma %g is not a finite number >= 0", p->gamma);
+    if (!(p->beta >= 0.0) || !std::isfinite(p->beta)) return fail(h, SPH_ERR_INVALID, "sph_set_surface_tension: beta %g is not a finite number >= 0", p->beta);
+    State &s = h->st;
+    if (p->method == SPH_SURFACE_TENSION_AKINCI) {
+        HIPCHK(h, hipSetDevice(h->device));
+        if (!s.st_normal) { int rc = dalloc(h, &s.st_normal, (size_t)s.cap); if (rc) return rc; }
+        if (!s.st_acc && !s.np_acc_out) { int rc = dalloc(h, &s.st_acc, (size_t)s.cap); if (rc) return rc; }
+    }
+    s.st_akinci = p->method == SPH_SURFACE_TENSION_AKINCI ? 1 : 0;
+    s.st_gamma = p->gamma; s.st_beta = p->beta; s.st_h = h->prm.support_radius;
+    return SPH_OK;
+}
+
+extern "C" int sph_get_surface_tension(SphHandle *h, SphSurfaceTensionParams *out) {
+    if (!h || !out) return SPH_ERR_INVALID;
+    out->method = h->st.st_akinci ? SPH_SURFACE_TENSION_AKINCI : SPH_SURFACE_TENSION_REFERENCE;
+    out->gamma = h->st.st_gamma; out->beta = h->st.st_beta;
+    return SPH_OK;
+}
+
+extern "C" int sph_surface_tension_kernels_host(double h, const float *r, int64_t n, float *C_out, float *A_out, int fast) {
+    if (!(h > 0.0) || !std::isfinite(h)) return fail(nullptr, SPH_ERR_INVALID, "sph_surface_tension_kernels_host: h %g is not a positive finite number", h);
+    if (n < 0) return fail(nullptr, SPH_ERR_INVALID, "sph_surface_tension_kernels_host: negative count");
+    if (n > 0 && (!r || !C_out || !A_out)) return fail(nullptr, SPH_ERR_INVALID, "sph_surface_tension_kernels_host: null argument");
+    const StSpline k = st_spline(h);
+    for (int64_t i = 0; i < n; ++i) {
+        C_out[i] = fast ? st_cohesion<true>(k, r[i]) : st_cohesion<false>(k, r[i]);
+        A_out[i] = fast ? st_adhesion<true>(k, r[i]) : st_adhesion<false>(k, r[i]);
+    }
+    return SPH_OK;
+}
+
 // ---------------------------------------------------------------------------------- device rigid integrator (sph_rigid.hpp)
 static int rigid_int_supported(SphHandle *h, const char *who) {
     if (h->prm.method == SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "%s: PBF moves no rigid body (PBF.py _step)", who);
@@ -1290,7 +1332,11 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
         case SPH_PH_NEIGHBOR_SEARCH: ph_neighbor_search(h); break;
         case SPH_PH_RIGID_VOLUME: h->rigid_volume_done = false; ph_rigid_volume(h); break;
         case SPH_PH_DENSITY: { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, h->prm.method == SPH_METHOD_WCSPH, {}); } break;
-        case SPH_PH_NON_PRESSURE: { int rc = run_non_pressure(h); if (rc) return rc; } break;
+        case SPH_PH_NON_PRESSURE: { int rc = run_non_pressure(h, false); if (rc) return rc; } break;   // (Akinci surface tension: on the STORED normals)
+        case SPH_PH_SURFACE_NORMALS:
+            if (!s.st_akinci) return fail(h, SPH_ERR_INVALID, "SPH_PH_SURFACE_NORMALS: the Akinci surface tension is off (sph_set_surface_tension)");
+            ph_surface_normals(h);
+            break;
         case SPH_PH_PRESSURE_INTEGRATE: { ProfScope p(h, SPH_K_PRESSURE_INTEGRATE); h->L->pressure_integrate(s); } break;
         case SPH_PH_RIGID_CONTACT: {
             if (!s.contact_on) return fail(h, SPH_ERR_INVALID, "SPH_PH_RIGID_CONTACT: sph_set_rigid_contact is off");
@@ -1362,7 +1408,8 @@ static const float4 *vec_field(SphHandle *h, int field) {
         case SPH_F_IISPH_DIJ_PJ: case SPH_F_IISPH_SUM_I: return s.iisph_dij; // (dij_pj, sum_i)
         case SPH_F_PBF_OLD_POSITION: return h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT ? nullptr : s.pbf_old;   // (x_old, sorted cell id); consistent variant: posv is the old position
         case SPH_F_RIGID_CONTACT_DN: case SPH_F_RIGID_CONTACT_COUNT: return s.contact_part;   // (sum of depth * n, contacts)
-        case SPH_F_NON_PRESSURE_ACCEL: return s.acc_np;   // (PCISPH only; null otherwise)
+        case SPH_F_NON_PRESSURE_ACCEL: return s.acc_np ? s.acc_np : s.st_acc;   // (PCISPH, or the last Akinci pass of any method; null otherwise)
+        case SPH_F_SURFACE_NORMAL: return s.st_normal;   // (allocated with the Akinci surface tension; null otherwise)
         case SPH_F_CG_B: return s.cg_b;     // (implicit viscosity only; null otherwise)
         case SPH_F_CG_R: return s.cg_r;
         case SPH_F_CG_P: return s.cg_p;
@@ -1400,7 +1447,7 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
                          field == SPH_F_PRESSURE_ACCEL || field == SPH_F_PREDICTED_VEL || field == SPH_F_PREDICTED_POS ||
                          field == SPH_F_CG_X || field == SPH_F_ORIG_POSITION || field == SPH_F_IISPH_DII || field == SPH_F_IISPH_DIJ_PJ ||
                          field == SPH_F_PBF_OLD_POSITION || field == SPH_F_RIGID_CONTACT_DN || field == SPH_F_NON_PRESSURE_ACCEL ||
-                         (field >= SPH_F_CG_B && field <= SPH_F_CG_V0);
+                         field == SPH_F_SURFACE_NORMAL || (field >= SPH_F_CG_B && field <= SPH_F_CG_V0);
     if (is_vec3) {
         const float4 *src = vec_field(h, field);
         if (!src) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);

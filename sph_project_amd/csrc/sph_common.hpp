@@ -685,6 +685,12 @@ struct State {
     int visc_rho_raw = 0;    // viscosity reads rho_raw (WCSPH: density before the EOS clamp)
     int skip_viscosity = 0;  // implicit viscosity: explicit term not part of the fused pass
     float4 *np_acc_out = nullptr;  // non-pressure acceleration sink (PCISPH), else null
+    // Akinci surface tension (sph_set_surface_tension; sph_surface_tension.hpp): off unless st_akinci; the buffers are allocated when the
+    // mode is first switched on (normals: recomputed every step, not carried through the sort; st_acc: the non-pressure acceleration
+    // of the last Akinci pass where the method keeps none of its own)
+    int st_akinci = 0;
+    double st_gamma = 1.0, st_beta = 0.0, st_h = 0.0;
+    float4 *st_normal = nullptr, *st_acc = nullptr;
 };
 
 // What a list sort's gather left behind for the density pass launched next (Launch::scatter_stable, density_next): thread d of a tile does
@@ -726,6 +732,7 @@ struct Launch {
     // until that pass has run, velm.cur() / meta.cur() / pid.cur() hold garbage (0xFF bytes in the test-hook library).
     SortCarry (*scatter_stable)(State &, bool rho_dead, bool density_next);
     void (*density)(State &, int eos, DensityOpts o);
+    void (*surface_normals)(State &);   // Akinci surface tension: the colour-field normals (State::st_normal), before non_pressure
     void (*non_pressure)(State &, const float4 *visc_vel);   // visc_vel: velocities for the viscous term (implicit viscosity: cg_x), null: the particles' own
     void (*pressure_integrate)(State &);
     void (*wcsph_forces)(State &, ForceOpts o); // non_pressure + pressure_integrate in one neighbour walk (WCSPH)

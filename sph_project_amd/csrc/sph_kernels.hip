@@ -19,6 +19,7 @@ namespace SPH_NS {
 #include "sph_device.hpp"
 #include "sph_halo_defs.hpp"
 #include "sph_passes.hpp"
+#include "sph_surface_tension.hpp"
 #include "sph_solvers.hpp"
 #include "sph_cg.hpp"
 #include "sph_halo.hpp"
@@ -307,9 +308,28 @@ void l_density(State &s, int eos, DensityOpts o) {
 }
 
 // rho_src: WCSPH viscosity reads the unclamped density (rho_raw); DFSPH/PCISPH read particle_densities.
+// the colour-field normals of the Akinci surface tension (sph_surface_tension.hpp), on the masks of the last sort
+void l_surface_normals(State &s) {
+    const float *rho_src = s.visc_rho_raw ? s.rho_raw : s.rho.cur();
+    if (s.c.all_fluid) { SurfaceNormalPass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.st_normal}; launch_pass(s, p, 2); }
+    else { SurfaceNormalPass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.st_normal}; launch_pass(s, p, 2); }
+}
+
 void l_non_pressure(State &s, const float4 *visc_vel) {
     const float *rho_src = s.visc_rho_raw ? s.rho_raw : s.rho.cur();
-    if (s.poly6) {   // PBF: poly6 surface tension, spiky viscosity (PBF.py:22-48)
+    if (s.st_akinci) {   // cohesion + curvature + adhesion in the place of the reference's term, on the stored normals
+        StSpline sp = st_spline(s.st_h);
+        sp.cA = (float)(s.st_beta * 0.007 / pow(s.st_h, 3.25));
+        const float g2r = (float)(s.st_gamma * 2.0 * (double)s.c.rho0);
+        float4 *acc_out = s.np_acc_out ? s.np_acc_out : s.st_acc;
+        if (s.c.all_fluid) {
+            AkinciNonPressurePass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, acc_out, visc_vel, s.st_normal, sp, g2r, s.st_beta != 0.0};
+            launch_pass(s, p, 2);
+        } else {
+            AkinciNonPressurePass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, acc_out, visc_vel, s.st_normal, sp, g2r, s.st_beta != 0.0};
+            launch_pass(s, p, 2);
+        }
+    } else if (s.poly6) {   // PBF: poly6 surface tension, spiky viscosity (PBF.py:22-48)
         if (s.c.all_fluid) {
             NonPressurePass<true, Poly6Kernel> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, visc_vel};
             launch_pass(s, p, 2);
@@ -517,6 +537,7 @@ const Launch *SPH_LAUNCH_FN() {
         L.scatter_stable = l_scatter_stable;
         L.density = l_density;
         L.non_pressure = l_non_pressure;
+        L.surface_normals = l_surface_normals;
         L.pressure_integrate = l_pressure_integrate;
         L.wcsph_forces = l_wcsph_forces;
         L.rigid_volume = l_rigid_volume;

@@ -174,8 +174,18 @@ static int run_solve(SphHandle *h, const SolveSpec &sp, Pre pre, Body body, int 
     return SPH_OK;
 }
 
+// Akinci surface tension (sph_set_surface_tension): the colour-field normals the non-pressure pass reads, from the positions and
+// densities as they are now, on the masks of the last sort.  Nothing without the mode.
+static void ph_surface_normals(SphHandle *h) {
+    if (!h->st.st_akinci) return;
+    ProfScope p(h, SPH_K_SURFACE_NORMALS);
+    h->L->surface_normals(h->st);
+}
+
 // base_solver.py:190 compute_non_pressure_acceleration + :643 update_fluid_velocity
-static int run_non_pressure(SphHandle *h) {
+// normals = false (SPH_PH_NON_PRESSURE): the Akinci pass runs on the normals the last SPH_PH_SURFACE_NORMALS / step stored
+static int run_non_pressure(SphHandle *h, bool normals = true) {
+    if (normals) ph_surface_normals(h);   // (positions and densities do not change under the CG solve: its end reads these too)
     if (h->prm.viscosity_implicit) {
         int rc = implicit_viscosity_non_pressure(h);
         return rc;
@@ -189,7 +199,7 @@ static int wcsph_step(SphHandle *h) {
     State &s = h->st;
     // sharded: + migration / ghost exchange; over the push transport a plain WCSPH step needs nothing back from the device
     // (slab_neighbor_search_push, "async"): implicit viscosity and the unfused force passes launch exact grids instead
-    const bool fused = !h->prm.viscosity_implicit;
+    const bool fused = !h->prm.viscosity_implicit && !s.st_akinci;   // (the Akinci surface tension needs the densities of ALL neighbours first)
     SortCarry carry;   // what the sort leaves to the density pass below (unsharded: that pass is the next launch and walks every tile)
     if (s.slab_active) { int rc = slab_neighbor_search(h, fused); if (rc) return rc; }
     else carry = ph_neighbor_search(h, true, true);                           // WCSPH.py:28 (the density pass below rewrites every rho: the sort need not move it)

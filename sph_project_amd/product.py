@@ -208,6 +208,51 @@ def wave_tank_scene(method="wcsph", length=2.4, width=0.5, depth=0.24, stroke=0.
     }
 
 
+def droplet_scene(edge=10, method="wcsph", gamma=1.0, beta=0.0, gravity=0.0, plate_gap=None, cube_gap=None, cube_edge=4,
+                  radius=0.01, dt=4e-4, viscosity=10.0, viscosity_b=None, margin=12, viscosity_method="standard"):
+    """The first scene of the Akinci surface tension: a cube of edge^3 fluid particles on the rest lattice in the middle
+    of a box it never touches (`margin` particle diameters to every face, no domain box), surfaceTensionMethod "akinci" with
+    gamma / beta; gravity is the magnitude along -y.  gamma = None leaves the three keys out (the reference's term).
+    plate_gap (particle diameters, None: no plate): a static, lattice-aligned plate of two layers under the cube, its upper layer
+    plate_gap diameters below the cube's lowest one, four particles wider than the cube on every side.
+    cube_gap (diameters, None: no cube): a dynamic rigid cube of cube_edge^3 particles on the same lattice beside the +x face."""
+    d = 2.0 * radius
+    lo = margin * d
+    size = lo + edge * d + lo
+    cfg = {
+        "Configuration": {
+            "domainStart": [0.0, 0.0, 0.0], "domainEnd": [size + (cube_edge + 2) * d * (cube_gap is not None), size, size],
+            "addDomainBox": False, "particleRadius": radius, "density0": 1000, "simulationMethod": method,
+            "viscosityMethod": viscosity_method, "gravitation": [0.0, -float(gravity), 0.0], "timeStepSize": dt, "viscosity": viscosity,
+        },
+        "FluidBlocks": [{
+            "objectId": 0, "start": [lo, lo, lo], "end": [lo + (edge - 0.5) * d] * 3, "translation": [0.0, 0.0, 0.0],
+            "scale": [1, 1, 1], "velocity": [0.0, 0.0, 0.0], "density": 1000.0, "color": [50, 100, 200], "entryTime": -1.0,
+        }],
+    }
+    if viscosity_b is not None:
+        cfg["Configuration"]["viscosity_b"] = viscosity_b
+    if gamma is not None:
+        cfg["Configuration"].update(surfaceTensionMethod="akinci", surfaceTension=float(gamma), surfaceAdhesion=float(beta))
+    body = lambda oid, pts, t, dyn: {
+        "objectId": oid, "geometryFile": "unused.obj", "voxelizedPoints": np.asarray(pts, np.float32).tolist(), "translation": list(t),
+        "rotationAxis": [0.0, 1.0, 0.0], "rotationAngle": 0.0, "scale": [1, 1, 1], "velocity": [0.0, 0.0, 0.0], "density": 1000.0,
+        "color": [230, 180, 60], "isDynamic": dyn, "entryTime": -1.0}
+    lattice = lambda n: np.stack(np.meshgrid(*[d * np.arange(k) for k in n], indexing="ij"), -1).reshape(-1, 3)
+    bodies = []
+    if plate_gap is not None:
+        corner = np.array([lo - 4 * d, lo - (plate_gap + 1) * d, lo - 4 * d])
+        bodies.append(body(1, corner + lattice((edge + 8, 2, edge + 8)), (0.0, 0.0, 0.0), False))
+    if cube_gap is not None:   # a dynamic body's particles are given in body coordinates (about its centre), its translation places it
+        pts = lattice((cube_edge,) * 3)
+        centre = pts.mean(0)
+        corner = np.array([lo + (edge - 1 + cube_gap) * d, lo, lo])
+        bodies.append(body(2, pts - centre, corner + centre, True))
+    if bodies:
+        cfg["RigidBodies"] = bodies
+    return cfg
+
+
 def scene_particles(cfg_dict):
     """Host lattice of every object present at prepare(), in the reference's insertion order
     (domain box first: base_container.py:192, then FluidBlocks: :215).  Blocks with entryTime > 0 are listed with
