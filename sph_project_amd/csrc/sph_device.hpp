@@ -599,10 +599,12 @@ template <class P> constexpr bool pass_reuses_masks() { return (PassModes<P>::va
 // then loaded at the top of the round (still without a wait of their own).
 template <class P, class = void> struct PassMaskPipe { static constexpr bool value = true; };
 template <class P> struct PassMaskPipe<P, decltype((void)P::MASK_PIPELINE)> { static constexpr bool value = P::MASK_PIPELINE; };
-template <class P, class = void> struct PassUsesJ0 { static constexpr bool value = true; };
-template <class P> struct PassUsesJ0<P, decltype((void)P::USES_J)> { static constexpr bool value = P::USES_J; };
+// pair() receives the neighbour's sorted index j only where the functor needs it (rigid-body wrench):
+// P::USES_J = false lets the merged loop drop the bookkeeping.
+template <class P, class = void> struct PassUsesJ { static constexpr bool value = true; };
+template <class P> struct PassUsesJ<P, decltype((void)P::USES_J)> { static constexpr bool value = P::USES_J; };
 // (default: the all-fluid instantiations pipeline; the ones that tell rigid neighbours apart -- USES_J -- run closer to their limit)
-template <class P> constexpr bool pass_mask_pipe() { return PassMaskPipe<P>::value && !(P::HAS_B && PassUsesJ0<P>::value); }
+template <class P> constexpr bool pass_mask_pipe() { return PassMaskPipe<P>::value && !(P::HAS_B && PassUsesJ<P>::value); }
 // P::HAS_WRENCH: pair() may call add_wrench (fluid -- dynamic rigid body pairs): the kernel opens the per-wave LDS rows at its start and
 // flushes them behind its pair loops (sph_passes.hpp)
 template <class P, class = void> struct PassWrench { static constexpr bool value = false; };
@@ -754,11 +756,6 @@ template <class P> constexpr bool pass_is_medium();
 template <class P> constexpr bool pass_pair2() {
     return SPH_P2_PAIR2_MEDIUM && pass_is_medium<P>();
 }
-
-// pair() receives the neighbour's sorted index j only where the functor needs it (rigid-body wrench):
-// P::USES_J = false lets the merged loop drop the bookkeeping.
-template <class P, class = void> struct PassUsesJ { static constexpr bool value = true; };
-template <class P> struct PassUsesJ<P, decltype((void)P::USES_J)> { static constexpr bool value = P::USES_J; };
 
 // Phase 2 of one staging group: the accepted candidates of the group's three runs (masks m0..m2, bit t = tile slot
 // base_q + t, byte offsets a_q = 8 base_q) are consumed in ONE loop, run after run in ascending order -- the
@@ -1348,7 +1345,7 @@ k_nbr_pass(const Consts c, const int *__restrict__ cell_start, const P p, DevSca
             // stage the runs that fit; consecutive t -> consecutive j: coalesced.  SB slots per batch: all of them where the
             // registers allow it (the medium functors' 96-VGPR budget and the strict build's wide records do not).
             constexpr int SB = pass_is_medium<P>() ? (NS > SPH_MEDIUM_SB ? SPH_MEDIUM_SB : NS) : PassFiveWg<P>::value ? SPH_FIVE_WG_SB
-                                                   : ((P::HAS_B && sizeof(BT) >= 16) ? ((PassUsesJ0<P>::value || !SPH_FAST) ? 2 : (SPH_HEAVY_SB < NS ? SPH_HEAVY_SB : NS)) : NS);
+                                                   : ((P::HAS_B && sizeof(BT) >= 16) ? ((PassUsesJ<P>::value || !SPH_FAST) ? 2 : (SPH_HEAVY_SB < NS ? SPH_HEAVY_SB : NS)) : NS);
             const int n0 = lo_[0] != INT_MIN ? ln_[0] : 0;
             const int n01 = n0 + (lo_[1] != INT_MIN ? ln_[1] : 0);
             const bool stage_now = total > 0 && c.force_global != 10;   // uniform

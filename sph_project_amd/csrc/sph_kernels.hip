@@ -15,6 +15,7 @@
 #include <vector>
 #include <cstdio>
 #include <cstdint>
+#include <type_traits>
 namespace SPH_NS {
 #include "sph_device.hpp"
 #include "sph_halo_defs.hpp"
@@ -284,6 +285,23 @@ template <class P> void launch_pass(State &s, const P &p, int mask_mode = 0, int
     }
 }
 
+// A run-time flag as a template argument: f(std::true_type{}) or f(std::false_type{}).  f is a generic lambda whose parameter names the
+// template argument (`[&](auto af) { ... Pass<af> ... }`), so a launcher that picks between instantiations states its arguments once.
+template <class F> void dispatch_bool(bool on, F &&f) {
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+// the common case: make(af) builds the functor for AF = "the scene holds nothing but active fluid", launch_pass takes it
+template <class F> void launch_pass_af(State &s, int mask_mode, F &&make, int tiles = 0, int split = 0) {
+    dispatch_bool(s.c.all_fluid, [&](auto af) { launch_pass(s, make(af), mask_mode, tiles, split); });
+}
+
+// the base of DensityPass<AF, EOS>: the sort's carry for the all-fluid functor, nothing for the other (l_density has refused it by then)
+template <bool AF> SortCarryOf<AF> sort_carry_of(const SortCarry &carry) {
+    if constexpr (AF) return {carry};
+    else return {};
+}
+
 void l_density(State &s, int eos, DensityOpts o) {
     HaloFieldSend fs = s.fieldsend;
     if (!eos) fs.on = 0;
@@ -298,51 +316,36 @@ void l_density(State &s, int eos, DensityOpts o) {
     if (getenv("SPH_TEST_DROP_CARRY")) carry.on = 0;
 #endif
     if (carry.on) s.n_carried_sorts++;
-    if (s.c.all_fluid) {
-        if (eos) { DensityPass<true, true> p{{carry}, s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
-        else { DensityPass<true, false> p{{carry}, s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
-    } else {
-        if (eos) { DensityPass<false, true> p{{}, s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
-        else { DensityPass<false, false> p{{}, s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}; launch_pass(s, p, 1, o.tiles); }
-    }
+    dispatch_bool(s.c.all_fluid, [&](auto af) { dispatch_bool(eos, [&](auto with_eos) {
+        launch_pass(s, DensityPass<af, with_eos>{sort_carry_of<af>(carry), s.posv.cur(), s.meta.cur(), s.rho_raw, s.rho.cur(), s.prs, s.ptm, fs, sp, se}, 1, o.tiles);
+    }); });
 }
 
-// rho_src: WCSPH viscosity reads the unclamped density (rho_raw); DFSPH/PCISPH read particle_densities.
 // the colour-field normals of the Akinci surface tension (sph_surface_tension.hpp), on the masks of the last sort
 void l_surface_normals(State &s) {
     const float *rho_src = s.visc_rho_raw ? s.rho_raw : s.rho.cur();
-    if (s.c.all_fluid) { SurfaceNormalPass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.st_normal}; launch_pass(s, p, 2); }
-    else { SurfaceNormalPass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.st_normal}; launch_pass(s, p, 2); }
+    launch_pass_af(s, 2, [&](auto af) { return SurfaceNormalPass<af>{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.st_normal}; });
+}
+
+// P: a non-pressure functor.  All of them begin with the same members; own: what P declares behind visc_vel
+// rho_src: WCSPH viscosity reads the unclamped density (rho_raw); DFSPH/PCISPH read particle_densities.
+template <class P, class... Own> void launch_non_pressure(State &s, float4 *acc_out, const float4 *visc_vel, Own... own) {
+    const float *rho_src = s.visc_rho_raw ? s.rho_raw : s.rho.cur();
+    launch_pass(s, P{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, acc_out, visc_vel, own...}, 2);
 }
 
 void l_non_pressure(State &s, const float4 *visc_vel) {
-    const float *rho_src = s.visc_rho_raw ? s.rho_raw : s.rho.cur();
     if (s.st_akinci) {   // cohesion + curvature + adhesion in the place of the reference's term, on the stored normals
         StSpline sp = st_spline(s.st_h);
         sp.cA = (float)(s.st_beta * 0.007 / pow(s.st_h, 3.25));
         const float g2r = (float)(s.st_gamma * 2.0 * (double)s.c.rho0);
         float4 *acc_out = s.np_acc_out ? s.np_acc_out : s.st_acc;
-        if (s.c.all_fluid) {
-            AkinciNonPressurePass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, acc_out, visc_vel, s.st_normal, sp, g2r, s.st_beta != 0.0};
-            launch_pass(s, p, 2);
-        } else {
-            AkinciNonPressurePass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, acc_out, visc_vel, s.st_normal, sp, g2r, s.st_beta != 0.0};
-            launch_pass(s, p, 2);
-        }
+        const int adhesion = s.st_beta != 0.0;
+        dispatch_bool(s.c.all_fluid, [&](auto af) { launch_non_pressure<AkinciNonPressurePass<af>>(s, acc_out, visc_vel, s.st_normal, sp, g2r, adhesion); });
     } else if (s.poly6) {   // PBF: poly6 surface tension, spiky viscosity (PBF.py:22-48)
-        if (s.c.all_fluid) {
-            NonPressurePass<true, Poly6Kernel> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, visc_vel};
-            launch_pass(s, p, 2);
-        } else {
-            NonPressurePass<false, Poly6Kernel> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, visc_vel};
-            launch_pass(s, p, 2);
-        }
-    } else if (s.c.all_fluid) {
-        NonPressurePass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, visc_vel};
-        launch_pass(s, p, 2);
+        dispatch_bool(s.c.all_fluid, [&](auto af) { launch_non_pressure<NonPressurePass<af, Poly6Kernel>>(s, s.np_acc_out, visc_vel); });
     } else {
-        NonPressurePass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, s.np_acc_out, visc_vel};
-        launch_pass(s, p, 2);
+        dispatch_bool(s.c.all_fluid, [&](auto af) { launch_non_pressure<NonPressurePass<af>>(s, s.np_acc_out, visc_vel); });
     }
     s.velm.flip();
 }
@@ -368,18 +371,19 @@ k_emitter_advance(const Consts c, float4 *posv, const float4 *velm, int *meta, c
 }
 
 void l_pressure_integrate(State &s) {
-    if (s.c.all_fluid) {
-        PressurePass<true> p{s.posv.cur(), s.meta.cur(), s.ptm, s.prs, s.rho.cur(), s.velm.cur(), s.acc, s.posv.alt(), s.scal, s.pose, s.c.rho0, 1};
-        launch_pass(s, p, 2);
-    } else {
-        PressurePass<false> p{s.posv.cur(), s.meta.cur(), s.ptm, s.prs, s.rho.cur(), s.velm.cur(), s.acc, s.posv.alt(), s.scal, s.pose, s.c.rho0, 1};
-        launch_pass(s, p, 2);
-    }
+    launch_pass_af(s, 2, [&](auto af) {
+        return PressurePass<af>{s.posv.cur(), s.meta.cur(), s.ptm, s.prs, s.rho.cur(), s.velm.cur(), s.acc, s.posv.alt(), s.scal, s.pose, s.c.rho0, 1};
+    });
     s.posv.flip();
     s.masks_valid = 0;  // positions moved
     if (s.has_emitter && s.c.n > 0)
         hipLaunchKernelGGL(k_emitter_advance, dim3(cdiv(s.c.n, 256)), dim3(256), 0, s.stream, s.c, s.posv.cur(),
                            s.velm.cur(), s.meta.cur(), s.pose);
+}
+
+// P: an instantiation of WcsphForcePass
+template <class P> void launch_wcsph_forces(State &s, const NextHash &nh) {
+    launch_pass(s, P{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho_raw, s.ptm, s.prs, s.rho.cur(), s.velm.alt(), s.acc, s.posv.alt(), s.scal, s.pose, s.c.rho0, s.presend, nh}, 2);
 }
 
 // WCSPH.py:30-36, 45 as one pass (see WcsphForcePass); same buffer choreography as the two passes it replaces
@@ -390,27 +394,14 @@ void l_wcsph_forces(State &s, ForceOpts o) {
     if (o.hash_next && s.c.all_fluid && !s.slab_active && s.cell_count_clean && o.booked_by_density && s.c.n > 0) nh.on = 1;
     if (nh.on) nh.rl = run_list_of(s, true);
     if (!o.booked_by_density) {   // launched outside wcsph_step's density + forces pair: nobody has booked this walk's pairs
-        if (s.c.all_fluid) {
-            WcsphForcePass<true, false, true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho_raw, s.ptm, s.prs, s.rho.cur(), s.velm.alt(), s.acc, s.posv.alt(), s.scal, s.pose, s.c.rho0, s.presend, nh};
-            launch_pass(s, p, 2);
-        } else {
-            WcsphForcePass<false, false, true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho_raw, s.ptm, s.prs, s.rho.cur(), s.velm.alt(), s.acc, s.posv.alt(), s.scal, s.pose, s.c.rho0, s.presend, nh};
-            launch_pass(s, p, 2);
-        }
+        dispatch_bool(s.c.all_fluid, [&](auto af) { launch_wcsph_forces<WcsphForcePass<af, false, true>>(s, nh); });
     } else
 #if SPH_FAST
     if (s.c.all_fluid && s.uniform_mass && !s.slab_active) {   // one fluid mass in the whole scene: the instantiation with the mass products hoisted (same sums)
-        WcsphForcePass<true, true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho_raw, s.ptm, s.prs, s.rho.cur(), s.velm.alt(), s.acc, s.posv.alt(), s.scal, s.pose, s.c.rho0, s.presend, nh};
-        launch_pass(s, p, 2);
+        launch_wcsph_forces<WcsphForcePass<true, true>>(s, nh);
     } else
 #endif
-    if (s.c.all_fluid) {
-        WcsphForcePass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho_raw, s.ptm, s.prs, s.rho.cur(), s.velm.alt(), s.acc, s.posv.alt(), s.scal, s.pose, s.c.rho0, s.presend, nh};
-        launch_pass(s, p, 2);
-    } else {
-        WcsphForcePass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho_raw, s.ptm, s.prs, s.rho.cur(), s.velm.alt(), s.acc, s.posv.alt(), s.scal, s.pose, s.c.rho0, s.presend, nh};
-        launch_pass(s, p, 2);
-    }
+    dispatch_bool(s.c.all_fluid, [&](auto af) { launch_wcsph_forces<WcsphForcePass<af>>(s, nh); });
     if (s.presend.on) { s.presend.on = 0; s.preclassified = 1; }
     if (nh.on) { s.prehashed = 1; s.cell_count_clean = 0; s.tile_sums_ready = nh.tile_sum != nullptr; s.hist_taken = 1; s.run_lists_filed = nh.rl.head != nullptr; }
     s.velm.flip();

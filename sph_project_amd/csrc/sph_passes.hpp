@@ -48,6 +48,14 @@ __device__ __forceinline__ void add_wrench(DevScalars *, int obj, float fx, floa
     atomicAdd(r + 0, fx); atomicAdd(r + 1, fy); atomicAdd(r + 2, fz);
     atomicAdd(r + 3, tx); atomicAdd(r + 4, ty); atomicAdd(r + 5, tz);
 }
+// the force f on body obj, acting at x: f and its torque about the body's centre of mass
+__device__ __forceinline__ void add_wrench_at(DevScalars *scal, int obj, float x, float y, float z, float fx, float fy, float fz) {
+    const float rx = x - wrench_com()[obj][0], ry = y - wrench_com()[obj][1], rz = z - wrench_com()[obj][2];
+    add_wrench(scal, obj, fx, fy, fz, ry * fz - rz * fy, rz * fx - rx * fz, rx * fy - ry * fx);
+}
+// what a rigid neighbour stages in the place of a fluid neighbour's density (always >= 0): -2 - body for a dynamic body's particle, which
+// rides along so that the pair loop loads no meta word, -1 for any other
+__device__ __forceinline__ float rigid_tag(int m) { return META_DYN(m) ? -2.0f - (float)META_OBJ(m) : -1.0f; }
 
 // ---------------------------------------------------------------------------------------
 // base_solver.py:522 compute_density (+task :535); with EOS also WCSPH.py:17 compute_pressure.
@@ -233,7 +241,7 @@ struct NonPressurePass {
             const int m = meta[j];
             const bool fl = META_MAT(m) == 1;
             aw = fl ? v.w : rho0 * p.w;
-            bw = fl ? rho_raw[j] : (META_DYN(m) ? -2.0f - (float)META_OBJ(m) : -1.0f);   // dynamic rigid: the body rides along (no meta load in the pair loop)
+            bw = fl ? rho_raw[j] : rigid_tag(m);
         }
         bj = make_float4(v.x, v.y, v.z, bw);
         return make_float4(p.x, p.y, p.z, aw);
@@ -278,8 +286,7 @@ struct NonPressurePass {
             if (bj.w <= -2.0f) {  // dynamic rigid neighbour: base_solver.py:272-278
                 const int obj = (int)(-bj.w) - 2;
                 const float fx = fdiv(-acx * o.m, c.rho0), fy = fdiv(-acy * o.m, c.rho0), fz = fdiv(-acz * o.m, c.rho0);
-                const float rx = a.x - wrench_com()[obj][0], ry = a.y - wrench_com()[obj][1], rz = a.z - wrench_com()[obj][2];
-                add_wrench(scal, obj, fx, fy, fz, ry * fz - rz * fy, rz * fx - rx * fz, rx * fy - ry * fx);
+                add_wrench_at(scal, obj, a.x, a.y, a.z, fx, fy, fz);
             }
         }
 #else
@@ -306,8 +313,7 @@ struct NonPressurePass {
             if (bj.w <= -2.0f) {  // dynamic rigid neighbour: base_solver.py:272-278
                 const int obj = (int)(-bj.w) - 2;
                 const float fx = fdiv(-acx * o.m, c.rho0), fy = fdiv(-acy * o.m, c.rho0), fz = fdiv(-acz * o.m, c.rho0);
-                const float rx = a.x - wrench_com()[obj][0], ry = a.y - wrench_com()[obj][1], rz = a.z - wrench_com()[obj][2];
-                add_wrench(scal, obj, fx, fy, fz, ry * fz - rz * fy, rz * fx - rx * fz, rx * fy - ry * fx);
+                add_wrench_at(scal, obj, a.x, a.y, a.z, fx, fy, fz);
             }
         }
 #endif
@@ -408,8 +414,7 @@ struct PressurePass {
                 const int obj = (int)(-bj) - 2;
                 const float cf = fdiv(a.w * o.p, o.rho2);
                 const float fx = (cf * gx) * o.m0, fy = (cf * gy) * o.m0, fz = (cf * gz) * o.m0;
-                const float rx = o.x - wrench_com()[obj][0], ry = o.y - wrench_com()[obj][1], rz = o.z - wrench_com()[obj][2];
-                add_wrench(scal, obj, fx, fy, fz, ry * fz - rz * fy, rz * fx - rx * fz, rx * fy - ry * fx);
+                add_wrench_at(scal, obj, o.x, o.y, o.z, fx, fy, fz);
             }
         }
     }
@@ -486,7 +491,7 @@ struct WcsphForcePass {
         }
         const int m = meta[j];
         const bool fl = META_MAT(m) == 1;
-        bj = make_float4(v.x, v.y, v.z, fl ? rho_raw[j] : (META_DYN(m) ? -2.0f - (float)META_OBJ(m) : -1.0f));
+        bj = make_float4(v.x, v.y, v.z, fl ? rho_raw[j] : rigid_tag(m));
         cj = fl ? ptm[j] : 0.0f;
         return make_float4(p.x, p.y, p.z, fl ? v.w : rho0 * p.w);
     }

@@ -220,24 +220,20 @@ static void l_pbf_predict(State &s) {
 
 static void l_pbf_density_lambda(State &s) {
     if (s.c.n == 0) return;
-    if (s.c.all_fluid)
-        hipLaunchKernelGGL(k_pbf_density_lambda<true>, dim3(cdiv(s.c.n, 256)), dim3(256), 0, s.stream, s.c, s.cell_start, s.posv.cur(),
+    dispatch_bool(s.c.all_fluid, [&](auto af) {
+        hipLaunchKernelGGL(k_pbf_density_lambda<af>, dim3(cdiv(s.c.n, 256)), dim3(256), 0, s.stream, s.c, s.cell_start, s.posv.cur(),
                            s.velm.cur(), s.meta.cur(), s.pbf_old, s.rho.cur(), s.pbf_lambda, s.scal, s.pbf_recentred);
-    else
-        hipLaunchKernelGGL(k_pbf_density_lambda<false>, dim3(cdiv(s.c.n, 256)), dim3(256), 0, s.stream, s.c, s.cell_start, s.posv.cur(),
-                           s.velm.cur(), s.meta.cur(), s.pbf_old, s.rho.cur(), s.pbf_lambda, s.scal, s.pbf_recentred);
+    });
 }
 
 // the new positions go to the scratch buffer, which then takes the place of the current one (the old one is the next scratch)
 static void l_pbf_fix_position(State &s) {
     if (s.c.n == 0) return;
     s.masks_valid = 0;
-    if (s.c.all_fluid)
-        hipLaunchKernelGGL(k_pbf_fix_position<true>, dim3(cdiv(s.c.n, 256)), dim3(256), 0, s.stream, s.c, s.cell_start, s.posv.cur(),
+    dispatch_bool(s.c.all_fluid, [&](auto af) {
+        hipLaunchKernelGGL(k_pbf_fix_position<af>, dim3(cdiv(s.c.n, 256)), dim3(256), 0, s.stream, s.c, s.cell_start, s.posv.cur(),
                            s.velm.cur(), s.meta.cur(), s.pbf_old, s.pbf_lambda, s.pbf_pos, s.scal, s.pbf_recentred);
-    else
-        hipLaunchKernelGGL(k_pbf_fix_position<false>, dim3(cdiv(s.c.n, 256)), dim3(256), 0, s.stream, s.c, s.cell_start, s.posv.cur(),
-                           s.velm.cur(), s.meta.cur(), s.pbf_old, s.pbf_lambda, s.pbf_pos, s.scal, s.pbf_recentred);
+    });
     float4 *t = s.posv.b[s.posv.c]; s.posv.b[s.posv.c] = s.pbf_pos; s.pbf_pos = t;
 }
 

@@ -205,16 +205,16 @@ static void l_pbfc_predict(State &s) {
 // a device-controlled loop the stop flag must not rise before the second walk has run (as PCISPH's, l_pcisph_rho_star)
 // (reduce: a lone SPH_PH_PBFC_DENSITY_LAMBDA phase, which reports its own sum)
 static void l_pbfc_density_lambda(State &s, int reduce) {
-    if (s.c.all_fluid) { PbfcDensityLambdaPass<true> p{s.posv.cur(), s.pbf_old, s.meta.cur(), s.rho.cur(), s.pbf_lambda, s.pbf_eps, s.red_partial}; launch_pass(s, p, 2); }
-    else { PbfcDensityLambdaPass<false> p{s.posv.cur(), s.pbf_old, s.meta.cur(), s.rho.cur(), s.pbf_lambda, s.pbf_eps, s.red_partial}; launch_pass(s, p, 2); }
+    launch_pass_af(s, 2, [&](auto af) {
+        return PbfcDensityLambdaPass<af>{s.posv.cur(), s.pbf_old, s.meta.cur(), s.rho.cur(), s.pbf_lambda, s.pbf_eps, s.red_partial};
+    });
     if (reduce && s.c.n > 0) l_reduce_sum(s, 3, cdiv(s.c.n, NBR_BLOCK));
 }
 
 // the corrected x* go to the second buffer, which then takes the first one's place; reduce: this walk closes an iteration whose walk
 // A left partial sums (a lone SPH_PH_PBFC_DELTA phase has none to finish)
 static void l_pbfc_delta(State &s, int reduce) {
-    if (s.c.all_fluid) { PbfcDeltaPass<true> p{s.posv.cur(), s.pbf_old, s.meta.cur(), s.pbf_lambda, s.pbf_pos}; launch_pass(s, p, 2); }
-    else { PbfcDeltaPass<false> p{s.posv.cur(), s.pbf_old, s.meta.cur(), s.pbf_lambda, s.pbf_pos}; launch_pass(s, p, 2); }
+    launch_pass_af(s, 2, [&](auto af) { return PbfcDeltaPass<af>{s.posv.cur(), s.pbf_old, s.meta.cur(), s.pbf_lambda, s.pbf_pos}; });
     std::swap(s.pbf_old, s.pbf_pos);
     if (reduce && s.c.n > 0 && !s.skip_residual) l_reduce_sum(s, 3, cdiv(s.c.n, NBR_BLOCK));   // (State::last_pass_listed is still walk A's)
 }

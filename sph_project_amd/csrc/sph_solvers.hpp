@@ -255,8 +255,7 @@ struct DfsphCorrectPass {
                 if (bj.x >= 1.0f) {  // dynamic rigid: DFSPH.py:195-204 / :277-285 (body and position staged with the neighbour, centre of mass in LDS)
                     const int obj = (int)bj.x - 1;
                     const float fx = fdiv(tx, c.dt) * o.m0, fy = fdiv(ty, c.dt) * o.m0, fz = fdiv(tz, c.dt) * o.m0;
-                    const float rx = a.x - wrench_com()[obj][0], ry = a.y - wrench_com()[obj][1], rz = a.z - wrench_com()[obj][2];
-                    add_wrench(scal, obj, fx, fy, fz, ry * fz - rz * fy, rz * fx - rx * fz, rx * fy - ry * fx);
+                    add_wrench_at(scal, obj, a.x, a.y, a.z, fx, fy, fz);
                 }
             }
         }
@@ -279,8 +278,7 @@ struct DfsphCorrectPass {
                 if (bj.x >= 1.0f) {  // dynamic rigid: DFSPH.py:195-204 / :277-285 (body and position staged with the neighbour, centre of mass in LDS)
                     const int obj = (int)bj.x - 1;
                     const float fx = fdiv(tx, c.dt) * o.m0, fy = fdiv(ty, c.dt) * o.m0, fz = fdiv(tz, c.dt) * o.m0;
-                    const float rx = a.x - wrench_com()[obj][0], ry = a.y - wrench_com()[obj][1], rz = a.z - wrench_com()[obj][2];
-                    add_wrench(scal, obj, fx, fy, fz, ry * fz - rz * fy, rz * fx - rx * fz, rx * fy - ry * fx);
+                    add_wrench_at(scal, obj, a.x, a.y, a.z, fx, fy, fz);
                 }
             }
         }

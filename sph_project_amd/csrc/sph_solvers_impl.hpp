@@ -72,40 +72,32 @@ static void l_reduce_sum(State &s, int slot, int nblocks) {
 }
 
 static void l_dfsph_density_alpha(State &s) {
-    if (s.c.all_fluid) { DfsphDensityAlphaPass<true> p{s.posv.cur(), s.meta.cur(), s.rho.cur(), s.alpha, s.red_partial}; launch_pass(s, p, 1); }
-    else { DfsphDensityAlphaPass<false> p{s.posv.cur(), s.meta.cur(), s.rho.cur(), s.alpha, s.red_partial}; launch_pass(s, p, 1); }
+    launch_pass_af(s, 1, [&](auto af) { return DfsphDensityAlphaPass<af>{s.posv.cur(), s.meta.cur(), s.rho.cur(), s.alpha, s.red_partial}; });
 }
 
 // density + alpha + the density derivative that opens the divergence solve, one walk (DfsphDensityAlphaDivPass); the partial sums
 // of the residual are left unreduced: the reference does not look at the pre-loop value either (DFSPH.py:140-150)
 static void l_dfsph_density_alpha_div(State &s) {
-    if (s.c.all_fluid) { DfsphDensityAlphaDivPass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.alpha, s.rho_deriv, s.kappa_v_next, s.red_partial}; launch_pass(s, p, 1); }
-    else { DfsphDensityAlphaDivPass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.alpha, s.rho_deriv, s.kappa_v_next, s.red_partial}; launch_pass(s, p, 1); }
+    launch_pass_af(s, 1, [&](auto af) {
+        return DfsphDensityAlphaDivPass<af>{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.alpha, s.rho_deriv, s.kappa_v_next, s.red_partial};
+    });
 }
 
 template <int MODE> static void dfsph_rho_adv_t(State &s, int slot) {
     float *out_adv = MODE == 0 ? s.rho_deriv : s.rho_star;
     float *out_k = MODE == 0 ? s.kappa_v_next : s.kappa_next;
-    if (s.c.all_fluid) {
-        DfsphRhoAdvPass<true, MODE> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.alpha, out_adv, out_k, s.red_partial};
-        launch_pass(s, p, 2);
-    } else {
-        DfsphRhoAdvPass<false, MODE> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.alpha, out_adv, out_k, s.red_partial};
-        launch_pass(s, p, 2);
-    }
+    launch_pass_af(s, 2, [&](auto af) {
+        return DfsphRhoAdvPass<af, MODE>{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.alpha, out_adv, out_k, s.red_partial};
+    });
     if (s.c.n > 0 && !s.skip_residual) l_reduce_sum(s, slot, cdiv(s.c.n, NBR_BLOCK));
 }
 static void l_dfsph_rho_adv(State &s, int mode) { if (mode == 0) dfsph_rho_adv_t<0>(s, 0); else dfsph_rho_adv_t<1>(s, 1); }
 
 template <int MODE> static void dfsph_correct_t(State &s) {
     const float *kap = MODE == 0 ? s.kappa_v : s.kappa;
-    if (s.c.all_fluid) {
-        DfsphCorrectPass<true, MODE> p{s.posv.cur(), s.meta.cur(), kap, s.rho.cur(), s.velm.cur(), s.scal, s.pose, s.c.rho0, s.red_partial};
-        launch_pass(s, p, 2);
-    } else {
-        DfsphCorrectPass<false, MODE> p{s.posv.cur(), s.meta.cur(), kap, s.rho.cur(), s.velm.cur(), s.scal, s.pose, s.c.rho0, s.red_partial};
-        launch_pass(s, p, 2);
-    }
+    launch_pass_af(s, 2, [&](auto af) {
+        return DfsphCorrectPass<af, MODE>{s.posv.cur(), s.meta.cur(), kap, s.rho.cur(), s.velm.cur(), s.scal, s.pose, s.c.rho0, s.red_partial};
+    });
 }
 static void l_dfsph_correct(State &s, int mode) { if (mode == 0) dfsph_correct_t<0>(s); else dfsph_correct_t<1>(s); }
 
@@ -132,33 +124,21 @@ static void l_pcisph_init(State &s) {
 }
 
 static void l_pcisph_rho_star(State &s) {
-    if (s.c.all_fluid) {
-        PcisphRhoStarPass<true> p{s.posv.cur(), s.ppos, s.meta.cur(), s.rho.cur(), s.rho_star, s.prs, s.ptm, s.red_partial
+    launch_pass_af(s, 2, [&](auto af) {
+        return PcisphRhoStarPass<af>{s.posv.cur(), s.ppos, s.meta.cur(), s.rho.cur(), s.rho_star, s.prs, s.ptm, s.red_partial
 #ifdef SPH_TEST_HOOKS
-                                  , s.rho_raw   // (PCISPH reads rho_raw nowhere after the density pass)
+                                     , s.rho_raw   // (PCISPH reads rho_raw nowhere after the density pass)
 #endif
         };
-        launch_pass(s, p, 2);
-    } else {
-        PcisphRhoStarPass<false> p{s.posv.cur(), s.ppos, s.meta.cur(), s.rho.cur(), s.rho_star, s.prs, s.ptm, s.red_partial
-#ifdef SPH_TEST_HOOKS
-                                   , s.rho_raw
-#endif
-        };
-        launch_pass(s, p, 2);
-    }
+    });
     // the partial sums are finished by l_pcisph_pressure_accel: the criterion (PCISPH.py:122) is tested after the whole
     // iteration, so inside a device-controlled loop the stop flag must not rise before the second pass has run
 }
 
 static void l_pcisph_pressure_accel(State &s) {
-    if (s.c.all_fluid) {
-        PcisphPressureAccelPass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.ptm, s.acc_np, s.velm.alt(), s.pacc, s.pvel, s.ppos, s.c.rho0, s.red_partial};
-        launch_pass(s, p, 2);
-    } else {
-        PcisphPressureAccelPass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.ptm, s.acc_np, s.velm.alt(), s.pacc, s.pvel, s.ppos, s.c.rho0, s.red_partial};
-        launch_pass(s, p, 2);
-    }
+    launch_pass_af(s, 2, [&](auto af) {
+        return PcisphPressureAccelPass<af>{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.ptm, s.acc_np, s.velm.alt(), s.pacc, s.pvel, s.ppos, s.c.rho0, s.red_partial};
+    });
     if (s.c.n > 0 && !s.skip_residual) l_reduce_sum(s, 2, cdiv(s.c.n, NBR_BLOCK));   // density error of this iteration's rho* pass
 }
 
@@ -166,25 +146,23 @@ static void l_pcisph_reduce_error(State &s) { if (s.c.n > 0) l_reduce_sum(s, 2, 
 
 // IISPH.py:18-90 (dii, aii, rho*; p = 0): after the non-pressure pass, velm.cur() = v*
 static void l_iisph_prepare(State &s) {
-    if (s.c.all_fluid) { IisphPreparePass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.iisph_dii, s.rho_star, s.prs, s.ptm, s.c.rho0, s.red_partial}; launch_pass(s, p, 2); }
-    else { IisphPreparePass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.iisph_dii, s.rho_star, s.prs, s.ptm, s.c.rho0, s.red_partial}; launch_pass(s, p, 2); }
+    launch_pass_af(s, 2, [&](auto af) {
+        return IisphPreparePass<af>{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.rho.cur(), s.iisph_dii, s.rho_star, s.prs, s.ptm, s.c.rho0, s.red_partial};
+    });
 }
 
 // IISPH.py:125 compute_dij_pj (+ w = dii p + dij_pj), the first walk of an iteration of refine (:185)
 static void l_iisph_dij_pj(State &s) {
-    if (s.c.all_fluid) { IisphDijPjPass<true> p{s.posv.cur(), s.meta.cur(), s.ptm, s.prs, s.iisph_dii, s.iisph_dij, s.iisph_w, s.c.rho0, s.red_partial}; launch_pass(s, p, 2); }
-    else { IisphDijPjPass<false> p{s.posv.cur(), s.meta.cur(), s.ptm, s.prs, s.iisph_dii, s.iisph_dij, s.iisph_w, s.c.rho0, s.red_partial}; launch_pass(s, p, 2); }
+    launch_pass_af(s, 2, [&](auto af) {
+        return IisphDijPjPass<af>{s.posv.cur(), s.meta.cur(), s.ptm, s.prs, s.iisph_dii, s.iisph_dij, s.iisph_w, s.c.rho0, s.red_partial};
+    });
 }
 
 // IISPH.py:148 compute_sum_i + :98 update_pressure, the second walk; the error's reduction closes the iteration
 static void l_iisph_sum_i(State &s) {
-    if (s.c.all_fluid) {
-        IisphSumIPass<true> p{s.posv.cur(), s.iisph_w, s.meta.cur(), s.rho.cur(), s.rho_star, s.iisph_dii, s.iisph_dij, s.prs, s.ptm, s.c.rho0, SPH_IISPH_OMEGA, s.red_partial};
-        launch_pass(s, p, 2);
-    } else {
-        IisphSumIPass<false> p{s.posv.cur(), s.iisph_w, s.meta.cur(), s.rho.cur(), s.rho_star, s.iisph_dii, s.iisph_dij, s.prs, s.ptm, s.c.rho0, SPH_IISPH_OMEGA, s.red_partial};
-        launch_pass(s, p, 2);
-    }
+    launch_pass_af(s, 2, [&](auto af) {
+        return IisphSumIPass<af>{s.posv.cur(), s.iisph_w, s.meta.cur(), s.rho.cur(), s.rho_star, s.iisph_dii, s.iisph_dij, s.prs, s.ptm, s.c.rho0, SPH_IISPH_OMEGA, s.red_partial};
+    });
     if (s.c.n > 0 && !s.skip_residual) l_reduce_sum(s, 2, cdiv(s.c.n, NBR_BLOCK));   // IISPH.py:114-121 (slot 2: the pressure solve's, as PCISPH's)
 }
 
@@ -193,8 +171,9 @@ static void l_iisph_sum_i(State &s) {
 // densities, like the explicit viscosity does (see l_non_pressure)
 #define CG_RHO (s.visc_rho_raw ? s.rho_raw : s.rho.cur())
 static void l_cg_prepare(State &s) {
-    if (s.c.all_fluid) { CgPreparePass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), CG_RHO, s.cg_x, s.cg_p, s.cg_b, s.cg_r, s.cg_Ap, s.cg_v0, s.cg_dinv, s.c.rho0, s.red_partial}; launch_pass(s, p, 2); }
-    else { CgPreparePass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), CG_RHO, s.cg_x, s.cg_p, s.cg_b, s.cg_r, s.cg_Ap, s.cg_v0, s.cg_dinv, s.c.rho0, s.red_partial}; launch_pass(s, p, 2); }
+    launch_pass_af(s, 2, [&](auto af) {
+        return CgPreparePass<af>{s.posv.cur(), s.velm.cur(), s.meta.cur(), CG_RHO, s.cg_x, s.cg_p, s.cg_b, s.cg_r, s.cg_Ap, s.cg_v0, s.cg_dinv, s.c.rho0, s.red_partial};
+    });
 }
 // partial-sum arrays of the CG kernels inside red_partial (each red_blocks floats): rr ping-pong, p . Ap, |r_old|^2
 #define CG_PART(k) (s.red_partial + (size_t)(k) * s.red_blocks)
@@ -219,17 +198,11 @@ static void l_cg_ap(State &s, bool fuse_p) {
     const bool nocombine = split && s.cg_fused_loop && !s.slab_active && s.red_blocks >= nb;
     s.cg_nocombine = nocombine ? 1 : 0;
     float *pdot = nocombine ? CG_PART(4) : nullptr;
-    if (s.c.all_fluid) {
-        CgApPass<true> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), CG_RHO, s.cg_p, s.cg_dinv, s.cg_Ap, CG_PART(2), s.cg_part, s.cap,
-                         s.cg_r, s.cg_p2, CG_PART(s.cg_parity), CG_PART(3), nb, lst ? s.blk_list : nullptr, lst ? s.blk_count : nullptr,
-                         fuse, s.loop_flag ? 1 : 0, (float)s.loop_thr, 0.0f, pdot, s.red_blocks};
-        launch_pass(s, p, 2, 0, ways);
-    } else {
-        CgApPass<false> p{s.posv.cur(), s.velm.cur(), s.meta.cur(), CG_RHO, s.cg_p, s.cg_dinv, s.cg_Ap, CG_PART(2), s.cg_part, s.cap,
-                          s.cg_r, s.cg_p2, CG_PART(s.cg_parity), CG_PART(3), nb, lst ? s.blk_list : nullptr, lst ? s.blk_count : nullptr,
-                          fuse, s.loop_flag ? 1 : 0, (float)s.loop_thr, 0.0f, pdot, s.red_blocks};
-        launch_pass(s, p, 2, 0, ways);
-    }
+    launch_pass_af(s, 2, [&](auto af) {
+        return CgApPass<af>{s.posv.cur(), s.velm.cur(), s.meta.cur(), CG_RHO, s.cg_p, s.cg_dinv, s.cg_Ap, CG_PART(2), s.cg_part, s.cap,
+                            s.cg_r, s.cg_p2, CG_PART(s.cg_parity), CG_PART(3), nb, lst ? s.blk_list : nullptr, lst ? s.blk_count : nullptr,
+                            fuse, s.loop_flag ? 1 : 0, (float)s.loop_thr, 0.0f, pdot, s.red_blocks};
+    }, 0, ways);
     if (split && !nocombine)   // the three parts -> A p and the partials of p . A p (what finish() and the pass's reduction do otherwise)
         hipLaunchKernelGGL(k_cg_ap_combine, dim3(CG_GRID(cdiv(s.c.n, 256))), dim3(256), 0, s.stream, s.c, s.meta.cur(), CG_AF, s.cg_part, s.cap, s.cg_p,
                            s.cg_Ap, CG_PART(2), s.loop_flag, CG_LIST, fuse ? s.cg_r : (const float4 *)nullptr, s.cg_p2, s.scal);

@@ -154,7 +154,7 @@ struct AkinciNonPressurePass {
             const int m = meta[j];
             const bool fl = META_MAT(m) == 1;
             aw = fl ? v.w : rho0 * p.w;
-            bw = fl ? rho_raw[j] : (META_DYN(m) ? -2.0f - (float)META_OBJ(m) : -1.0f);
+            bw = fl ? rho_raw[j] : rigid_tag(m);
         }
         bj = make_float4(v.x, v.y, v.z, bw);
         return make_float4(p.x, p.y, p.z, aw);
@@ -222,8 +222,7 @@ struct AkinciNonPressurePass {
             if (bj.w <= -2.0f) {  // dynamic rigid neighbour: both reactions act at x_k, arm x_k - com (base_solver.py:272-278)
                 const int obj = (int)(-bj.w) - 2;
                 fx *= o.m; fy *= o.m; fz *= o.m;
-                const float rx = a.x - wrench_com()[obj][0], ry = a.y - wrench_com()[obj][1], rz = a.z - wrench_com()[obj][2];
-                add_wrench(scal, obj, fx, fy, fz, ry * fz - rz * fy, rz * fx - rx * fz, rx * fy - ry * fx);
+                add_wrench_at(scal, obj, a.x, a.y, a.z, fx, fy, fz);
             }
         }
     }
