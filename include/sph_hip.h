@@ -149,6 +149,13 @@ typedef enum {
        carried through the sort (recomputed every step): valid until the next sort, like SPH_F_NON_PRESSURE_ACCEL of a handle that is
        not PCISPH's (DFSPH sorts in the second half of its step: read both between sph_step_begin and sph_step_end). */
     SPH_F_SURFACE_NORMAL = 43,     /* f32[n][3] */
+    /* Micropolar vorticity model (allocated when sph_set_micropolar first switches the mode on; SPH_ERR_UNSUPPORTED before).  The angular
+       velocity belongs to the particle and follows it through every sort: download and upload in the CURRENT order, like every other field;
+       particles appended later start at zero; rows that are not fluid read zero and an upload leaves them alone.  An axial vector:
+       its sign follows the parity of the handle's axis order, as the rigid bodies' angular velocity does. */
+    SPH_F_ANGULAR_VELOCITY = 44,   /* f32[n][3] */
+    /* download only: a_mp of the last SPH_PH_MICROPOLAR (or step), written on active fluid rows only; valid until the next sort */
+    SPH_F_MICROPOLAR_ACCEL = 45,   /* f32[n][3] */
     SPH_F_COUNT_
 } SphField;
 
@@ -199,6 +206,11 @@ typedef enum {
        the last sort.  In this mode SPH_PH_NON_PRESSURE (and SPH_PH_CG_END) run the Akinci pass on the STORED normals, without
        recomputing them; a step computes them in front of its non-pressure pass. */
     SPH_PH_SURFACE_NORMALS = 28,
+    /* Micropolar vorticity model (sph_set_micropolar; SPH_ERR_INVALID while the mode is off): the walk alone, on the masks of the last
+       sort: it stores a_mp (SPH_F_MICROPOLAR_ACCEL) and the new angular velocities and adds the reaction on dynamic bodies.  In this
+       mode SPH_PH_NON_PRESSURE (and SPH_PH_CG_END) add the STORED a_mp behind their pass, v += dt a_mp, without walking again; a
+       step walks in front of its non-pressure pass. */
+    SPH_PH_MICROPOLAR = 29,
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -245,6 +257,7 @@ typedef enum {
     SPH_K_RIGID_MOTION = 30,   /* scripted rigid bodies: the launch that evaluates their motion programs (sph_set_rigid_motion);
                                   sph_kernel_name's table ends at 29 and answers "?" for this id */
     SPH_K_SURFACE_NORMALS = 31, /* Akinci surface tension: the normal pass (the Akinci force pass itself is SPH_K_NON_PRESSURE); "?" as well */
+    SPH_K_MICROPOLAR = 32,      /* micropolar vorticity model: the gather of the angular velocities + the walk (v += dt a_mp: SPH_K_MISC); "?" as well */
     SPH_K_COUNT_
 } SphKernelId;
 
@@ -339,6 +352,33 @@ typedef struct { int32_t method; double gamma, beta; } SphSurfaceTensionParams;
 int sph_set_surface_tension(SphHandle *h, const SphSurfaceTensionParams *params);
 int sph_get_surface_tension(SphHandle *h, SphSurfaceTensionParams *out);
 int sph_surface_tension_kernels_host(double h, const float *r, int64_t n, float *C_out, float *A_out, int fast);
+
+/* Micropolar vorticity model (opt-in).  method 0 = none (the default), 1 = micropolar: Bender, Koschier, Kugelstadt,
+   Weiler 2017.  Every fluid particle carries an angular velocity w (SPH_F_ANGULAR_VELOCITY, zero when inserted).  With R = x_i - x,
+   gradW = gradW(R), W the cubic spline, rho the density the viscous term of the method reads, j fluid and k boundary neighbours of an
+   active fluid particle i, Psi_k = rho0 V_k:
+     a_mp_i  = nu_t / rho_i [ sum_j m_j (w_i - w_j) x gradW_ij + sum_k Psi_k w_i x gradW_ik ]
+     alpha_i = theta_inv { nu_t / rho_i [ sum_j m_j (v_i - v_j) x gradW_ij + sum_k Psi_k (v_i - v_k) x gradW_ik ]
+                           - 2 nu_t w_i - zeta sum_j (m_j / rho_j) (w_i - w_j) W_ij }
+     v_i <- v_i + dt (a_np_i + a_mp_i),   w_i <- w_i + dt alpha_i
+   All sums read the state at the start of the non-pressure phase (the w update is Jacobi).  A dynamic rigid neighbour k receives
+   -m_i nu_t / rho_i Psi_k w_i x gradW_ik at x_k.  a_mp also enters the non-pressure acceleration, which every method keeps in this
+   mode (SPH_F_NON_PRESSURE_ACCEL).  WCSPH takes its unfused route (SPH_K_WCSPH_FORCES does not run).  Legal at any time between
+   steps; switching back to 0 restores the plain path bit for bit and keeps w and the three values.
+   The angular velocities are stored by persistent particle id, which has to be the append order: while the mode is on
+   sph_set_appended_ids and an upload of SPH_F_PARTICLE_ID are refused with SPH_ERR_UNSUPPORTED, and so is the mode once either has
+   been used.  SPH_ERR_UNSUPPORTED too: a PBF handle (either variant), a sharded handle (and sph_comm_set_slab while the mode is on).
+   This library has no 2-D handles; the Python front end refuses 2-D scenes.  SPH_ERR_INVALID: nu_t, zeta or theta_inv negative or
+   not finite, an unknown method.
+   sph_micropolar_pair_host: the kernels' pair arithmetic on the CPU, strict (fast = 0) or fast form.  in: n records of 24 floats
+   (v_i[3], w_i[3], nu_t / rho_i, m_j, v_j[3], w_j[3], m_j / rho_j, zeta, R[3], gs, gradW[3], W; gradW = gs R: the fast form reads gs and
+   R, the strict form gradW); out: n records of 6 floats, the pair's share of the two sums (sph_micropolar.hpp MpSums).  No device. */
+#define SPH_VORTICITY_NONE 0
+#define SPH_VORTICITY_MICROPOLAR 1
+typedef struct { int32_t method; double nu_t, zeta, theta_inv; } SphMicropolarParams;
+int sph_set_micropolar(SphHandle *h, const SphMicropolarParams *params);
+int sph_get_micropolar(SphHandle *h, SphMicropolarParams *out);
+int sph_micropolar_pair_host(const float *in, int64_t n, float *out, int fast);
 
 /* Device rigid integrator (opt-in; the host's "device" rigid backend).  The physics of the host's native backend
    (SPH/rigid_solver/host_rigid_solver.py integrate: semi-implicit Euler in float64 under gravity and the fluid wrench, gyroscopic

@@ -77,6 +77,10 @@ class BaseContainer:
         self.surface_tension_method, self.surface_tension, self.surface_adhesion = scene.surface_tension_of(config, self.METHOD, geo.dim)
         if self.surface_tension_method == "akinci" and engine_opts.get("slab"):
             raise ValueError("Configuration.surfaceTensionMethod \"akinci\" is not available on a sharded scene (--gpus > 1)")
+        # micropolar vorticity model: likewise
+        self.vorticity_method, self.vorticity, self.viscosity_omega, self.inertia_inverse = scene.micropolar_of(config, self.METHOD, geo.dim)
+        if self.vorticity_method == "micropolar" and engine_opts.get("slab"):
+            raise ValueError("Configuration.vorticityMethod \"micropolar\" is not available on a sharded scene (--gpus > 1)")
         self.material_rigid, self.material_fluid = scene.MATERIAL_RIGID, scene.MATERIAL_FLUID
         self.dx, self.particle_diameter, self.dh = geo.dx, geo.particle_diameter, geo.dh
         self.particle_spacing, self.V0 = geo.particle_spacing, geo.V0
@@ -157,6 +161,8 @@ class BaseContainer:
         self.engine = F.Engine(p)
         if self.surface_tension_method == "akinci":
             self.engine.set_surface_tension("akinci", self.surface_tension, self.surface_adhesion)
+        if self.vorticity_method == "micropolar":
+            self.engine.set_micropolar("micropolar", self.vorticity, self.viscosity_omega, self.inertia_inverse)
         # multi-GPU: engine_opts["slab"] = dict(rank=, nranks=, unique_id=<128 bytes>, cuts=[...]) -> this container
         # only inserts the particles of its own z-slab (sph_project_amd/slab.py)
         self.slab = engine_opts.get("slab")
@@ -226,7 +232,8 @@ class BaseContainer:
             self.engine.set_object(obj_id, self.material_fluid, 0)
             self.add_cube(object_id=obj_id, lower_corner=start, cube_size=(end - start) * scale,
                           velocity=fluid["velocity"], density=fluid["density"], is_dynamic=1, color=fluid["color"],
-                          material=self.material_fluid, space=self.particle_spacing)
+                          material=self.material_fluid, space=self.particle_spacing,
+                          angular_velocity=fluid.get("angularVelocity"))
             self.present_object.append(obj_id)
 
         for body in self.fluid_bodies:
@@ -332,13 +339,17 @@ class BaseContainer:
                 np.tile(np.asarray(color, np.int32), (n, 1)))
 
     def add_cube(self, object_id, lower_corner, cube_size, material, is_dynamic, color=(0, 0, 0), density=None,
-                 pressure=None, velocity=None, space=None):
-        """base_container.py:753."""
+                 pressure=None, velocity=None, space=None, angular_velocity=None):
+        """base_container.py:753.  angular_velocity (block key angularVelocity, this project's: the reference ignores it): the block
+        starts in rigid rotation about the centre of its particles, v += W x (x - centre)."""
         space = self.particle_diameter if space is None else space
         pos = scene.cube_lattice(lower_corner, cube_size, space)
         n = pos.shape[0]
         vel, den, prs, mat, dyn, col = self._uniform_attributes(n, material, is_dynamic, color, density, pressure,
                                                                 velocity, pos)
+        if angular_velocity is not None and n > 0 and self.dim == 3:
+            w = np.asarray(angular_velocity, np.float64).reshape(3)
+            vel = (vel + np.cross(w, pos.astype(np.float64) - pos.astype(np.float64).mean(0))).astype(np.float32)
         self.add_particles(object_id, n, pos, vel, den, prs, mat, dyn, col)
 
     def add_box(self, object_id, lower_corner, cube_size, thickness, material, is_dynamic, color=(0, 0, 0),
@@ -360,8 +371,11 @@ class BaseContainer:
     def dump(self, obj_id):
         """base_container.py:599."""
         mask = self.engine.download(F.F_OBJECT_ID) == obj_id
-        return {"position": self.engine.download(F.F_POSITION)[mask],
-                "velocity": self.engine.download(F.F_VELOCITY)[mask]}
+        out = {"position": self.engine.download(F.F_POSITION)[mask],
+               "velocity": self.engine.download(F.F_VELOCITY)[mask]}
+        if self.vorticity_method == "micropolar":   # (only then: the reference's dump has the two keys above)
+            out["angular_velocity"] = self.engine.download(F.F_ANGULAR_VELOCITY)[mask]
+        return out
 
     def copy_to_vis_buffer(self, invisible_objects=[], dim=3):
         """base_container.py:567 (host arrays instead of GGUI fields)."""

@@ -37,6 +37,12 @@ class BaseSolver:
         akinci = self.surface_tension_method == "akinci"
         self.surface_tension = container.surface_tension if akinci else sol.surface_tension
         self.surface_adhesion = container.surface_adhesion if akinci else 0.0
+        # the vorticity model: "none", or "micropolar" with nu_t (scene key vorticity), zeta (viscosityOmega) and
+        # theta_inv (inertiaInverse)
+        self.vorticity_method = getattr(container, "vorticity_method", "none")
+        self.vorticity = getattr(container, "vorticity", 0.01)
+        self.viscosity_omega = getattr(container, "viscosity_omega", 0.1)
+        self.inertia_inverse = getattr(container, "inertia_inverse", 0.5)
         self.dt = _DtField(sol.dt)
         self.rigid_solver = PyBulletSolver(container, gravity=self.g, dt=self.dt[None])
         self.engine = container.engine

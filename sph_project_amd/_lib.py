@@ -28,6 +28,8 @@ METHOD = {"wcsph": 0, "dfsph": 1, "pcisph": 2, "iisph": 3, "pbf": 4}
 F_CG_B, F_CG_R, F_CG_P, F_CG_AP, F_CG_V0, F_CG_DINV, F_CG_AP_PARTS = range(36, 43)
 # Akinci surface tension, download only: the colour-field normals (fluid rows)
 F_SURFACE_NORMAL = 43
+# micropolar vorticity model: the angular velocities (up- and download, current order) and a_mp of the last walk (download only)
+F_ANGULAR_VELOCITY, F_MICROPOLAR_ACCEL = 44, 45
 
 _FIELD_SPEC = {  # field -> (dtype, components)
     F_POSITION: (np.float32, 3), F_VELOCITY: (np.float32, 3), F_ACCELERATION: (np.float32, 3),
@@ -44,6 +46,7 @@ _FIELD_SPEC = {  # field -> (dtype, components)
     F_RIGID_CONTACT_DN: (np.float32, 3), F_RIGID_CONTACT_COUNT: (np.float32, 1), F_NON_PRESSURE_ACCEL: (np.float32, 3),
     F_CG_B: (np.float32, 3), F_CG_R: (np.float32, 3), F_CG_P: (np.float32, 3), F_CG_AP: (np.float32, 3), F_CG_V0: (np.float32, 3),
     F_CG_DINV: (np.float32, 9), F_CG_AP_PARTS: (np.float32, 9), F_SURFACE_NORMAL: (np.float32, 3),
+    F_ANGULAR_VELOCITY: (np.float32, 3), F_MICROPOLAR_ACCEL: (np.float32, 3),
 }
 
 # enum SphPhase
@@ -61,6 +64,8 @@ PH_DFSPH_ALPHA_DIVERGENCE = 22
 PH_CG_PREPARE, PH_CG_AP, PH_CG_UPDATE_XR, PH_CG_UPDATE_P, PH_CG_END = 23, 24, 25, 26, 27
 # Akinci surface tension: the normal pass alone (PH_NON_PRESSURE then runs on the stored normals)
 PH_SURFACE_NORMALS = 28
+# micropolar vorticity model: the walk alone (PH_NON_PRESSURE / PH_CG_END then add the stored a_mp)
+PH_MICROPOLAR = 29
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
@@ -75,6 +80,7 @@ K_PBFC_DENSITY_LAMBDA = 28   # sph_kernel_name(28) == "pbfc_density_lambda": wal
 K_PBFC_DELTA = 29            # sph_kernel_name(29) == "pbfc_delta": its walk B
 K_RIGID_MOTION = 30          # SPH_K_RIGID_MOTION: the launch that moves the scripted rigid bodies (sph_kernel_name's table ends at 29)
 K_SURFACE_NORMALS = 31       # SPH_K_SURFACE_NORMALS: the normal pass of the Akinci surface tension
+K_MICROPOLAR = 32            # SPH_K_MICROPOLAR: the gather + walk of the micropolar vorticity model
 RIGID_MOTION_MAX_KEYS = 64
 
 # rigid contact table (sph_get_rigid_contacts): [object A][partner B][normal bin][value]; partners 20..25 are the domain box /
@@ -170,6 +176,24 @@ def surface_tension_kernels_host(h, r, fast=False):
     if rc:
         raise SphError(f"sph_surface_tension_kernels_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
     return c_out, a_out
+
+
+VORTICITY_METHODS = {"none": 0, "micropolar": 1}
+
+
+class SphMicropolarParams(C.Structure):
+    _fields_ = [("method", C.c_int32), ("nu_t", C.c_double), ("zeta", C.c_double), ("theta_inv", C.c_double)]
+
+
+def micropolar_pair_host(records, fast=False):
+    """The micropolar walk's pair arithmetic from the kernels' own source run on the CPU (sph_micropolar_pair_host): records (n, 24)
+    float32 as sph_hip.h lists them -> (n, 6) float32, each pair's share of the two sums.  No device."""
+    rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 24)
+    out = np.empty((rec.shape[0], 6), np.float32)
+    rc = load().sph_micropolar_pair_host(_ptr(rec), rec.shape[0], _ptr(out), int(bool(fast)))
+    if rc:
+        raise SphError(f"sph_micropolar_pair_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
+    return out
 
 
 class SphPbfStats(C.Structure):
@@ -427,6 +451,9 @@ _SIGNATURES = [
     ("sph_set_surface_tension", C.c_int, [_VP, C.POINTER(SphSurfaceTensionParams)]),
     ("sph_get_surface_tension", C.c_int, [_VP, C.POINTER(SphSurfaceTensionParams)]),
     ("sph_surface_tension_kernels_host", C.c_int, [C.c_double, _VP, C.c_int64, _VP, _VP, C.c_int]),
+    ("sph_set_micropolar", C.c_int, [_VP, C.POINTER(SphMicropolarParams)]),
+    ("sph_get_micropolar", C.c_int, [_VP, C.POINTER(SphMicropolarParams)]),
+    ("sph_micropolar_pair_host", C.c_int, [_VP, C.c_int64, _VP, C.c_int]),
     # device rigid integrator; what each stands in for in the reference's SPH/rigid_solver/bullet_solver.py:
     ("sph_set_rigid_integrator", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),                        # :19-71 __init__ (gravity, dt, walls)
     ("sph_set_rigid_body", C.c_int, [_VP, C.c_int, C.c_double] + [_VP] * 7 + [C.c_int]),        # :75-131 insert_rigid_object
@@ -760,6 +787,17 @@ class Engine(NativeObject):
         p = SphSurfaceTensionParams()
         self._chk(self.lib.sph_get_surface_tension(self.h, C.byref(p)), "sph_get_surface_tension")
         return {"method": {v: k for k, v in SURFACE_TENSION_METHODS.items()}[p.method], "gamma": p.gamma, "beta": p.beta}
+
+    # -- micropolar vorticity model
+    def set_micropolar(self, method="micropolar", nu_t=0.01, zeta=0.1, theta_inv=0.5):
+        """method: "none" / "micropolar" (or 0 / 1); nu_t: transfer coefficient, zeta: angular dissipation, theta_inv: inverse microinertia."""
+        p = SphMicropolarParams(int(VORTICITY_METHODS.get(method, method)), float(nu_t), float(zeta), float(theta_inv))
+        self._chk(self.lib.sph_set_micropolar(self.h, C.byref(p)), "sph_set_micropolar")
+
+    def get_micropolar(self):
+        p = SphMicropolarParams()
+        self._chk(self.lib.sph_get_micropolar(self.h, C.byref(p)), "sph_get_micropolar")
+        return {"method": {v: k for k, v in VORTICITY_METHODS.items()}[p.method], "nu_t": p.nu_t, "zeta": p.zeta, "theta_inv": p.theta_inv}
 
     # -- device rigid integrator (the "device" rigid backend)
     def set_rigid_integrator(self, on=True, gravity=(0.0, 0.0, 0.0), wall_lo=(0.0, 0.0, 0.0), wall_hi=(0.0, 0.0, 0.0)):

@@ -430,6 +430,8 @@ extern "C" int sph_set_appended_ids(SphHandle *h, int n, const int32_t *ids) {
     if (h) { int rc = slab_settle_if_needed(h); if (rc) return rc; }
     if (!h || !ids || n < 0 || n > h->n) return fail(h, SPH_ERR_INVALID, "set_appended_ids: bad arguments");
     if (n == 0) return SPH_OK;
+    if (h->st.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: the micropolar model is on (its angular velocities are stored by id, in append order)");
+    h->st.ids_custom = 1;
     HIPCHK(h, hipSetDevice(h->device));
     colors_leave_home(h);
     HIPCHK(h, hipStreamSynchronize(h->st.stream));
@@ -616,6 +618,59 @@ extern "C" int sph_surface_tension_kernels_host(double h, const float *r, int64_
     for (int64_t i = 0; i < n; ++i) {
         C_out[i] = fast ? st_cohesion<true>(k, r[i]) : st_cohesion<false>(k, r[i]);
         A_out[i] = fast ? st_adhesion<true>(k, r[i]) : st_adhesion<false>(k, r[i]);
+    }
+    return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------- micropolar vorticity model
+#include "sph_micropolar.hpp"
+extern "C" int sph_set_micropolar(SphHandle *h, const SphMicropolarParams *p) {
+    if (!h) return SPH_ERR_INVALID;
+    if (!p) return fail(h, SPH_ERR_INVALID, "sph_set_micropolar: null argument");
+    if (h->prm.method == SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_micropolar: not on a PBF handle (either variant)");
+    if (h->st.slab_active || h->comm.slab_ready)
+        return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_micropolar: not on a sharded handle (the ghosts' angular velocities would need an exchange)");
+    if (p->method != SPH_VORTICITY_NONE && p->method != SPH_VORTICITY_MICROPOLAR)
+        return fail(h, SPH_ERR_INVALID, "sph_set_micropolar: method %d is neither 0 (none) nor 1 (micropolar)", p->method);
+    if (!(p->nu_t >= 0.0) || !std::isfinite(p->nu_t)) return fail(h, SPH_ERR_INVALID, "sph_set_micropolar: nu_t %g is not a finite number >= 0", p->nu_t);
+    if (!(p->zeta >= 0.0) || !std::isfinite(p->zeta)) return fail(h, SPH_ERR_INVALID, "sph_set_micropolar: zeta %g is not a finite number >= 0", p->zeta);
+    if (!(p->theta_inv >= 0.0) || !std::isfinite(p->theta_inv))
+        return fail(h, SPH_ERR_INVALID, "sph_set_micropolar: theta_inv %g is not a finite number >= 0", p->theta_inv);
+    State &s = h->st;
+    if (p->method == SPH_VORTICITY_MICROPOLAR) {
+        if (s.ids_custom)
+            return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_micropolar: particle ids were set from outside (sph_set_appended_ids / SPH_F_PARTICLE_ID): "
+                                                "the angular velocities are stored by id and need the append order");
+        HIPCHK(h, hipSetDevice(h->device));
+        // (dalloc clears: the rows of particles appended later read zero until their first walk)
+        if (!s.mp_w_home) { int rc = dalloc(h, &s.mp_w_home, (size_t)s.cap); if (rc) return rc; }
+        if (!s.mp_w_sorted) { int rc = dalloc(h, &s.mp_w_sorted, (size_t)s.cap); if (rc) return rc; }
+        if (!s.mp_acc) { int rc = dalloc(h, &s.mp_acc, (size_t)s.cap); if (rc) return rc; }
+        if (!s.st_acc && !s.np_acc_out) { int rc = dalloc(h, &s.st_acc, (size_t)s.cap); if (rc) return rc; }
+    }
+    s.mp_on = p->method == SPH_VORTICITY_MICROPOLAR ? 1 : 0;
+    s.mp_nu_t = p->nu_t; s.mp_zeta = p->zeta; s.mp_theta_inv = p->theta_inv;
+    return SPH_OK;
+}
+
+extern "C" int sph_get_micropolar(SphHandle *h, SphMicropolarParams *out) {
+    if (!h || !out) return SPH_ERR_INVALID;
+    out->method = h->st.mp_on ? SPH_VORTICITY_MICROPOLAR : SPH_VORTICITY_NONE;
+    out->nu_t = h->st.mp_nu_t; out->zeta = h->st.mp_zeta; out->theta_inv = h->st.mp_theta_inv;
+    return SPH_OK;
+}
+
+extern "C" int sph_micropolar_pair_host(const float *in, int64_t n, float *out, int fast) {
+    if (n < 0) return fail(nullptr, SPH_ERR_INVALID, "sph_micropolar_pair_host: negative count");
+    if (n > 0 && (!in || !out)) return fail(nullptr, SPH_ERR_INVALID, "sph_micropolar_pair_host: null argument");
+    for (int64_t k = 0; k < n; ++k) {
+        const float *q = in + 24 * k;
+        MpSums s = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        float cx, cy, cz;
+        if (fast) mp_pair<true>(s, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9], q[10], q[11], q[12], q[13], q[14], q[15], q[16], q[17], q[18], q[19], q[20], q[21], q[22], q[23], cx, cy, cz);
+        else mp_pair<false>(s, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9], q[10], q[11], q[12], q[13], q[14], q[15], q[16], q[17], q[18], q[19], q[20], q[21], q[22], q[23], cx, cy, cz);
+        float *o = out + 6 * k;
+        o[0] = s.ax; o[1] = s.ay; o[2] = s.az; o[3] = s.bx; o[4] = s.by; o[5] = s.bz;
     }
     return SPH_OK;
 }
@@ -1332,10 +1387,14 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
         case SPH_PH_NEIGHBOR_SEARCH: ph_neighbor_search(h); break;
         case SPH_PH_RIGID_VOLUME: h->rigid_volume_done = false; ph_rigid_volume(h); break;
         case SPH_PH_DENSITY: { ProfScope p(h, SPH_K_DENSITY); h->L->density(s, h->prm.method == SPH_METHOD_WCSPH, {}); } break;
-        case SPH_PH_NON_PRESSURE: { int rc = run_non_pressure(h, false); if (rc) return rc; } break;   // (Akinci surface tension: on the STORED normals)
+        case SPH_PH_NON_PRESSURE: { int rc = run_non_pressure(h, false); if (rc) return rc; } break;   // (Akinci surface tension: on the STORED normals; micropolar model: + the STORED a_mp)
         case SPH_PH_SURFACE_NORMALS:
             if (!s.st_akinci) return fail(h, SPH_ERR_INVALID, "SPH_PH_SURFACE_NORMALS: the Akinci surface tension is off (sph_set_surface_tension)");
             ph_surface_normals(h);
+            break;
+        case SPH_PH_MICROPOLAR:
+            if (!s.mp_on) return fail(h, SPH_ERR_INVALID, "SPH_PH_MICROPOLAR: the micropolar model is off (sph_set_micropolar)");
+            ph_micropolar(h);
             break;
         case SPH_PH_PRESSURE_INTEGRATE: { ProfScope p(h, SPH_K_PRESSURE_INTEGRATE); h->L->pressure_integrate(s); } break;
         case SPH_PH_RIGID_CONTACT: {
@@ -1344,7 +1403,7 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
             ProfScope p(h, SPH_K_RIGID_CONTACT); h->L->rigid_contact(s);
         } break;
         case SPH_PH_CG_PREPARE: case SPH_PH_CG_AP: case SPH_PH_CG_UPDATE_XR: case SPH_PH_CG_UPDATE_P: case SPH_PH_CG_END:
-            { int rc = cg_run_phase(h, phase); if (rc) return rc; } break;
+            { int rc = cg_run_phase(h, phase); if (rc) return rc; if (phase == SPH_PH_CG_END) ph_micropolar_apply(h); } break;   // (micropolar model: + the STORED a_mp)
         default: { int rc = method_run_phase(h, phase); if (rc) return rc; }
     }
     int rc = check_async(h); if (rc) return rc;
@@ -1408,7 +1467,8 @@ static const float4 *vec_field(SphHandle *h, int field) {
         case SPH_F_IISPH_DIJ_PJ: case SPH_F_IISPH_SUM_I: return s.iisph_dij; // (dij_pj, sum_i)
         case SPH_F_PBF_OLD_POSITION: return h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT ? nullptr : s.pbf_old;   // (x_old, sorted cell id); consistent variant: posv is the old position
         case SPH_F_RIGID_CONTACT_DN: case SPH_F_RIGID_CONTACT_COUNT: return s.contact_part;   // (sum of depth * n, contacts)
-        case SPH_F_NON_PRESSURE_ACCEL: return s.acc_np ? s.acc_np : s.st_acc;   // (PCISPH, or the last Akinci pass of any method; null otherwise)
+        case SPH_F_NON_PRESSURE_ACCEL: return s.acc_np ? s.acc_np : s.st_acc;   // (PCISPH, or the last Akinci pass / micropolar-mode pass of any method; null otherwise)
+        case SPH_F_MICROPOLAR_ACCEL: return s.mp_acc;   // (allocated with the micropolar model; null otherwise)
         case SPH_F_SURFACE_NORMAL: return s.st_normal;   // (allocated with the Akinci surface tension; null otherwise)
         case SPH_F_CG_B: return s.cg_b;     // (implicit viscosity only; null otherwise)
         case SPH_F_CG_R: return s.cg_r;
@@ -1447,7 +1507,7 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
                          field == SPH_F_PRESSURE_ACCEL || field == SPH_F_PREDICTED_VEL || field == SPH_F_PREDICTED_POS ||
                          field == SPH_F_CG_X || field == SPH_F_ORIG_POSITION || field == SPH_F_IISPH_DII || field == SPH_F_IISPH_DIJ_PJ ||
                          field == SPH_F_PBF_OLD_POSITION || field == SPH_F_RIGID_CONTACT_DN || field == SPH_F_NON_PRESSURE_ACCEL ||
-                         field == SPH_F_SURFACE_NORMAL || (field >= SPH_F_CG_B && field <= SPH_F_CG_V0);
+                         field == SPH_F_SURFACE_NORMAL || field == SPH_F_MICROPOLAR_ACCEL || (field >= SPH_F_CG_B && field <= SPH_F_CG_V0);
     if (is_vec3) {
         const float4 *src = vec_field(h, field);
         if (!src) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);
@@ -1457,6 +1517,23 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
         float *d = (float *)dst;
         const int ix0 = h->inv[0], ix1 = h->inv[1], ix2 = h->inv[2];   // library frame -> scene frame
         for (size_t i = 0; i < n; ++i) { const float v[3] = {tmp[i].x, tmp[i].y, tmp[i].z}; d[3 * i] = v[ix0]; d[3 * i + 1] = v[ix1]; d[3 * i + 2] = v[ix2]; }
+        return SPH_OK;
+    }
+    if (field == SPH_F_ANGULAR_VELOCITY) {   // at home by particle id -> the current order; library frame -> scene frame, axial
+        if (!s.mp_w_home) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated (sph_set_micropolar)", field);
+        if (bytes != n * 12) return fail(h, SPH_ERR_INVALID, "download: field %d needs %zu bytes, got %zu", field, n * 12, bytes);
+        std::vector<float4> home((size_t)s.cap);
+        std::vector<int> id(n);
+        HIPCHK(h, hipMemcpy(home.data(), s.mp_w_home, (size_t)s.cap * sizeof(float4), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(id.data(), s.pid.cur(), n * 4, hipMemcpyDeviceToHost));
+        float *d = (float *)dst;
+        const int ix0 = h->inv[0], ix1 = h->inv[1], ix2 = h->inv[2];
+        for (size_t i = 0; i < n; ++i) {
+            if (id[i] < 0 || id[i] >= s.cap) return fail(h, SPH_ERR_INVALID, "download: particle id %d outside [0, %d)", id[i], s.cap);
+            const float4 w = home[(size_t)id[i]];
+            const float v[3] = {w.x, w.y, w.z};
+            d[3 * i] = h->axial * v[ix0]; d[3 * i + 1] = h->axial * v[ix1]; d[3 * i + 2] = h->axial * v[ix2];
+        }
         return SPH_OK;
     }
     if (field == SPH_F_CG_DINV) {   // library frame -> scene frame on both indices
@@ -1575,8 +1652,28 @@ extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes
         HIPCHK(h, hipMemcpy(vdst, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice));
         return SPH_OK;
     }
+    if (field == SPH_F_ANGULAR_VELOCITY) {   // the current order -> home by particle id; scene frame -> library frame, axial
+        if (!s.mp_w_home) return fail(h, SPH_ERR_UNSUPPORTED, "upload: field %d not allocated (sph_set_micropolar)", field);
+        if (bytes != n * 12) return fail(h, SPH_ERR_INVALID, "upload: field %d needs %zu bytes", field, n * 12);
+        std::vector<float4> home((size_t)s.cap);
+        std::vector<int> id(n), mt(n);
+        HIPCHK(h, hipMemcpy(home.data(), s.mp_w_home, (size_t)s.cap * sizeof(float4), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(id.data(), s.pid.cur(), n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(mt.data(), s.meta.cur(), n * 4, hipMemcpyDeviceToHost));
+        const float *f = (const float *)src;
+        const int ix0 = h->perm[0], ix1 = h->perm[1], ix2 = h->perm[2];
+        for (size_t i = 0; i < n; ++i) {
+            if (id[i] < 0 || id[i] >= s.cap) return fail(h, SPH_ERR_INVALID, "upload: particle id %d outside [0, %d)", id[i], s.cap);
+            if (META_MAT(mt[i]) != SPH_MAT_FLUID) continue;   // (only fluid carries one: the other rows stay zero)
+            home[(size_t)id[i]] = make_float4(h->axial * f[3 * i + ix0], h->axial * f[3 * i + ix1], h->axial * f[3 * i + ix2], 0.0f);
+        }
+        HIPCHK(h, hipMemcpy(s.mp_w_home, home.data(), (size_t)s.cap * sizeof(float4), hipMemcpyHostToDevice));
+        return SPH_OK;
+    }
     if (field == SPH_F_PARTICLE_ID) {  // global ids when a scene is split over ranks
         if (bytes != n * 4) return fail(h, SPH_ERR_INVALID, "upload: size mismatch");
+        if (s.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while the micropolar model is on (its angular velocities are stored by id, in append order)");
+        s.ids_custom = 1;
         colors_leave_home(h); HIPCHK(h, hipStreamSynchronize(s.stream));
         HIPCHK(h, hipMemcpy(s.pid.cur(), src, n * 4, hipMemcpyHostToDevice));
         return SPH_OK;

@@ -691,6 +691,14 @@ struct State {
     int st_akinci = 0;
     double st_gamma = 1.0, st_beta = 0.0, st_h = 0.0;
     float4 *st_normal = nullptr, *st_acc = nullptr;
+    // Micropolar vorticity model (sph_set_micropolar; sph_micropolar.hpp): off unless mp_on; the buffers are allocated when the mode is
+    // first switched on.  mp_w_home[particle id]: the angular velocities AT HOME (no sort moves them; ids = append order, which
+    // ids_custom ends: the mode and ids from outside exclude each other); mp_w_sorted: their copy in sorted order for the walk's
+    // candidate records; mp_acc: a_mp of the last walk in sorted order (valid until the next sort).  With the mode on and no
+    // non-pressure acceleration kept otherwise, st_acc takes it.
+    int mp_on = 0, ids_custom = 0;
+    double mp_nu_t = 0.01, mp_zeta = 0.1, mp_theta_inv = 0.5;
+    float4 *mp_w_home = nullptr, *mp_w_sorted = nullptr, *mp_acc = nullptr;
 };
 
 // What a list sort's gather left behind for the density pass launched next (Launch::scatter_stable, density_next): thread d of a tile does
@@ -733,6 +741,8 @@ struct Launch {
     SortCarry (*scatter_stable)(State &, bool rho_dead, bool density_next);
     void (*density)(State &, int eos, DensityOpts o);
     void (*surface_normals)(State &);   // Akinci surface tension: the colour-field normals (State::st_normal), before non_pressure
+    void (*micropolar)(State &);         // micropolar model: gather w, the walk (State::mp_acc, mp_w_home), before non_pressure
+    void (*micropolar_apply)(State &);   // ... and v += dt a_mp (+ the kept non-pressure acceleration) behind it
     void (*non_pressure)(State &, const float4 *visc_vel);   // visc_vel: velocities for the viscous term (implicit viscosity: cg_x), null: the particles' own
     void (*pressure_integrate)(State &);
     void (*wcsph_forces)(State &, ForceOpts o); // non_pressure + pressure_integrate in one neighbour walk (WCSPH)

@@ -21,6 +21,7 @@ namespace SPH_NS {
 #include "sph_halo_defs.hpp"
 #include "sph_passes.hpp"
 #include "sph_surface_tension.hpp"
+#include "sph_micropolar.hpp"
 #include "sph_solvers.hpp"
 #include "sph_cg.hpp"
 #include "sph_halo.hpp"
@@ -334,7 +335,27 @@ template <class P, class... Own> void launch_non_pressure(State &s, float4 *acc_
     launch_pass(s, P{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.velm.alt(), s.scal, s.pose, s.c.rho0, s.skip_viscosity, acc_out, visc_vel, own...}, 2);
 }
 
+// the micropolar model's walk (sph_micropolar.hpp), on the masks of the last sort: w in sorted order first, then a_mp and the new w
+void l_micropolar(State &s) {
+    const int n = s.c.n;
+    if (n == 0) return;
+    const float *rho_src = s.visc_rho_raw ? s.rho_raw : s.rho.cur();
+    hipLaunchKernelGGL(k_micropolar_gather, dim3(cdiv(n, 256)), dim3(256), 0, s.stream, n, s.pid.cur(), s.mp_w_home, s.mp_w_sorted);
+    launch_pass_af(s, 2, [&](auto af) {
+        return MicropolarPass<af>{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.mp_w_sorted, s.pid.cur(), s.mp_acc, s.mp_w_home, s.scal, s.pose,
+                                  s.c.rho0, (float)s.mp_nu_t, (float)s.mp_zeta, (float)s.mp_theta_inv};
+    });
+}
+// v += dt a_mp on the velocities the non-pressure phase left, acc += a_mp where a non-pressure acceleration is kept
+void l_micropolar_apply(State &s) {
+    const int n = s.c.n;
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_micropolar_apply, dim3(cdiv(n, 256)), dim3(256), 0, s.stream, s.c, s.meta.cur(), s.mp_acc, s.velm.cur(),
+                       s.np_acc_out ? s.np_acc_out : s.st_acc);
+}
+
 void l_non_pressure(State &s, const float4 *visc_vel) {
+    float4 *np_acc = s.np_acc_out ? s.np_acc_out : (s.mp_on ? s.st_acc : nullptr);   // (micropolar model: every method keeps it)
     if (s.st_akinci) {   // cohesion + curvature + adhesion in the place of the reference's term, on the stored normals
         StSpline sp = st_spline(s.st_h);
         sp.cA = (float)(s.st_beta * 0.007 / pow(s.st_h, 3.25));
@@ -343,9 +364,9 @@ void l_non_pressure(State &s, const float4 *visc_vel) {
         const int adhesion = s.st_beta != 0.0;
         dispatch_bool(s.c.all_fluid, [&](auto af) { launch_non_pressure<AkinciNonPressurePass<af>>(s, acc_out, visc_vel, s.st_normal, sp, g2r, adhesion); });
     } else if (s.poly6) {   // PBF: poly6 surface tension, spiky viscosity (PBF.py:22-48)
-        dispatch_bool(s.c.all_fluid, [&](auto af) { launch_non_pressure<NonPressurePass<af, Poly6Kernel>>(s, s.np_acc_out, visc_vel); });
+        dispatch_bool(s.c.all_fluid, [&](auto af) { launch_non_pressure<NonPressurePass<af, Poly6Kernel>>(s, np_acc, visc_vel); });
     } else {
-        dispatch_bool(s.c.all_fluid, [&](auto af) { launch_non_pressure<NonPressurePass<af>>(s, s.np_acc_out, visc_vel); });
+        dispatch_bool(s.c.all_fluid, [&](auto af) { launch_non_pressure<NonPressurePass<af>>(s, np_acc, visc_vel); });
     }
     s.velm.flip();
 }
@@ -529,6 +550,8 @@ const Launch *SPH_LAUNCH_FN() {
         L.density = l_density;
         L.non_pressure = l_non_pressure;
         L.surface_normals = l_surface_normals;
+        L.micropolar = l_micropolar;
+        L.micropolar_apply = l_micropolar_apply;
         L.pressure_integrate = l_pressure_integrate;
         L.wcsph_forces = l_wcsph_forces;
         L.rigid_volume = l_rigid_volume;

@@ -182,16 +182,32 @@ static void ph_surface_normals(SphHandle *h) {
     h->L->surface_normals(h->st);
 }
 
+// Micropolar vorticity model (sph_set_micropolar): the walk reads positions, the step's starting velocities, densities and last step's
+// w -- nothing the non-pressure pass writes -- so it runs in front of that pass; v += dt a_mp follows behind it (behind the end of the
+// implicit-viscosity solve).  Nothing without the mode.
+static void ph_micropolar(SphHandle *h) {
+    if (!h->st.mp_on) return;
+    ProfScope p(h, SPH_K_MICROPOLAR);
+    h->L->micropolar(h->st);
+}
+static void ph_micropolar_apply(SphHandle *h) {
+    if (!h->st.mp_on) return;
+    ProfScope p(h, SPH_K_MISC);
+    h->L->micropolar_apply(h->st);
+}
+
 // base_solver.py:190 compute_non_pressure_acceleration + :643 update_fluid_velocity
-// normals = false (SPH_PH_NON_PRESSURE): the Akinci pass runs on the normals the last SPH_PH_SURFACE_NORMALS / step stored
-static int run_non_pressure(SphHandle *h, bool normals = true) {
-    if (normals) ph_surface_normals(h);   // (positions and densities do not change under the CG solve: its end reads these too)
+// walks = false (SPH_PH_NON_PRESSURE): the Akinci pass runs on the normals the last SPH_PH_SURFACE_NORMALS / step stored, and the
+// micropolar model's a_mp is the one the last SPH_PH_MICROPOLAR / step stored
+static int run_non_pressure(SphHandle *h, bool walks = true) {
+    if (walks) { ph_surface_normals(h); ph_micropolar(h); }   // (positions and densities do not change under the CG solve: its end reads these too)
     if (h->prm.viscosity_implicit) {
-        int rc = implicit_viscosity_non_pressure(h);
-        return rc;
+        int rc = implicit_viscosity_non_pressure(h); if (rc) return rc;
+        ph_micropolar_apply(h);
+        return SPH_OK;
     }
-    ProfScope p(h, SPH_K_NON_PRESSURE);
-    h->L->non_pressure(h->st, nullptr);
+    { ProfScope p(h, SPH_K_NON_PRESSURE); h->L->non_pressure(h->st, nullptr); }
+    ph_micropolar_apply(h);
     return SPH_OK;
 }
 
@@ -199,7 +215,7 @@ static int wcsph_step(SphHandle *h) {
     State &s = h->st;
     // sharded: + migration / ghost exchange; over the push transport a plain WCSPH step needs nothing back from the device
     // (slab_neighbor_search_push, "async"): implicit viscosity and the unfused force passes launch exact grids instead
-    const bool fused = !h->prm.viscosity_implicit && !s.st_akinci;   // (the Akinci surface tension needs the densities of ALL neighbours first)
+    const bool fused = !h->prm.viscosity_implicit && !s.st_akinci && !s.mp_on;   // (the Akinci surface tension and the micropolar walk need the densities of ALL neighbours first)
     SortCarry carry;   // what the sort leaves to the density pass below (unsharded: that pass is the next launch and walks every tile)
     if (s.slab_active) { int rc = slab_neighbor_search(h, fused); if (rc) return rc; }
     else carry = ph_neighbor_search(h, true, true);                           // WCSPH.py:28 (the density pass below rewrites every rho: the sort need not move it)

@@ -253,6 +253,33 @@ def droplet_scene(edge=10, method="wcsph", gamma=1.0, beta=0.0, gravity=0.0, pla
     return cfg
 
 
+def stirred_tank_scene(edge=10, omega=10.0, method="wcsph", gravity=0.0, radius=0.01, dt=4e-4, viscosity=0.01, margin=8,
+                       vorticity_method="micropolar", **keys):
+    """The first scene of the micropolar vorticity model: a block of edge^3 fluid particles on the rest lattice in a
+    closed box (sampled domain box; `margin` particle diameters from the domain's faces, of which the box's shell takes the first 3.5), started in rigid rotation v = W x (x - centre)
+    with W = omega about the vertical (y) axis (block key angularVelocity); gravity is the magnitude along -y.  keys: further
+    Configuration keys (vorticity, viscosityOmega, inertiaInverse, ...); vorticity_method = None leaves the vorticity keys out."""
+    d = 2.0 * radius
+    lo = margin * d
+    size = lo + edge * d + lo
+    cfg = {
+        "Configuration": {
+            "domainStart": [0.0, 0.0, 0.0], "domainEnd": [size, size, size], "addDomainBox": True, "particleRadius": radius,
+            "density0": 1000, "simulationMethod": method, "viscosityMethod": "standard", "gravitation": [0.0, -float(gravity), 0.0],
+            "timeStepSize": dt, "viscosity": viscosity,
+        },
+        "FluidBlocks": [{
+            "objectId": 0, "start": [lo, lo, lo], "end": [lo + (edge - 0.5) * d] * 3, "translation": [0.0, 0.0, 0.0],
+            "scale": [1, 1, 1], "velocity": [0.0, 0.0, 0.0], "angularVelocity": [0.0, float(omega), 0.0], "density": 1000.0,
+            "color": [50, 100, 200], "entryTime": -1.0,
+        }],
+    }
+    if vorticity_method is not None:
+        cfg["Configuration"]["vorticityMethod"] = vorticity_method
+    cfg["Configuration"].update(keys)
+    return cfg
+
+
 def scene_particles(cfg_dict):
     """Host lattice of every object present at prepare(), in the reference's insertion order
     (domain box first: base_container.py:192, then FluidBlocks: :215).  Blocks with entryTime > 0 are listed with
@@ -274,7 +301,11 @@ def scene_particles(cfg_dict):
         s, e = np.array(blk["start"]) + off, np.array(blk["end"]) + off
         pos = scene.cube_lattice(s, (e - s) * np.array(blk["scale"]), geo.particle_spacing)
         n = pos.shape[0]
-        batches.append(dict(object_id=blk["objectId"], pos=pos, vel=np.tile(np.asarray(blk["velocity"], np.float32), (n, 1)),
+        vel = np.tile(np.asarray(blk["velocity"], np.float32), (n, 1))
+        if blk.get("angularVelocity") is not None and n > 0:   # (this project's block key: BaseContainer.add_cube)
+            w = np.asarray(blk["angularVelocity"], np.float64).reshape(3)
+            vel = (vel + np.cross(w, pos.astype(np.float64) - pos.astype(np.float64).mean(0))).astype(np.float32)
+        batches.append(dict(object_id=blk["objectId"], pos=pos, vel=vel,
                             density=np.full(n, blk["density"], np.float32), material=np.full(n, 1, np.int32),
                             is_dynamic=np.ones(n, np.int32), entry_time=float(blk.get("entryTime", -1.0))))
     return cfg, geo, batches

@@ -277,6 +277,9 @@ def check_sharded_args(parser, args):
     if config.get_cfg("surfaceTensionMethod") == "akinci":
         parser.error(f"--gpus {n}: surfaceTensionMethod \"akinci\" is not sharded (the normals of the ghost particles would need an "
                      "exchange of their own; sph_set_surface_tension refuses a slab); run it with --gpus 1")
+    if config.get_cfg("vorticityMethod") == "micropolar":
+        parser.error(f"--gpus {n}: vorticityMethod \"micropolar\" is not sharded (the angular velocities of the ghost particles would "
+                     "need an exchange of their own; sph_set_micropolar refuses a slab); run it with --gpus 1")
     from sph_project_amd import launch
     try:
         launch.plan_scene_cuts(config.config, n)
