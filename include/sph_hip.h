@@ -156,6 +156,15 @@ typedef enum {
     SPH_F_ANGULAR_VELOCITY = 44,   /* f32[n][3] */
     /* download only: a_mp of the last SPH_PH_MICROPOLAR (or step), written on active fluid rows only; valid until the next sort */
     SPH_F_MICROPOLAR_ACCEL = 45,   /* f32[n][3] */
+    /* Elastic solids (allocated when sph_set_elastic_object first marks an object; SPH_ERR_UNSUPPORTED before).  All four in the CURRENT
+       order like every field; rows that do not belong to a captured elastic object read zero.  The first three are download only: a_el of
+       the last SPH_PH_ELASTIC (or step), valid until the next sort; the deformation gradient F (row-major) and the stress
+       (xx, xy, xz, yy, yz, zz) that pass stored.  The rotation is the unit quaternion (x, y, z, w) the next pass warm-starts from:
+       up- and downloadable (an upload leaves rows outside captured elastic objects alone). */
+    SPH_F_ELASTIC_ACCEL = 46,      /* f32[n][3] */
+    SPH_F_ELASTIC_DEFGRAD = 47,    /* f32[n][9] */
+    SPH_F_ELASTIC_STRESS = 48,     /* f32[n][6] */
+    SPH_F_ELASTIC_ROTATION = 49,   /* f32[n][4] */
     SPH_F_COUNT_
 } SphField;
 
@@ -211,6 +220,11 @@ typedef enum {
        mode SPH_PH_NON_PRESSURE (and SPH_PH_CG_END) add the STORED a_mp behind their pass, v += dt a_mp, without walking again; a
        step walks in front of its non-pressure pass. */
     SPH_PH_MICROPOLAR = 29,
+    /* Elastic solids (sph_set_elastic_object; SPH_ERR_INVALID while no object is marked): the scatter and the passes A and B alone, on
+       the order of the last sort: they store a_el (SPH_F_ELASTIC_ACCEL), F, the stress and the new rotations.  SPH_PH_NON_PRESSURE
+       (and SPH_PH_CG_END) then add the STORED a_el behind their pass, v += dt a_el; a step runs the passes in front of its
+       non-pressure pass. */
+    SPH_PH_ELASTIC = 30,
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -258,6 +272,7 @@ typedef enum {
                                   sph_kernel_name's table ends at 29 and answers "?" for this id */
     SPH_K_SURFACE_NORMALS = 31, /* Akinci surface tension: the normal pass (the Akinci force pass itself is SPH_K_NON_PRESSURE); "?" as well */
     SPH_K_MICROPOLAR = 32,      /* micropolar vorticity model: the gather of the angular velocities + the walk (v += dt a_mp: SPH_K_MISC); "?" as well */
+    SPH_K_ELASTIC = 33,         /* elastic solids: the scatter + pass A + pass B (v += dt a_el: SPH_K_MISC; the capture: SPH_K_MISC); "?" as well */
     SPH_K_COUNT_
 } SphKernelId;
 
@@ -379,6 +394,48 @@ typedef struct { int32_t method; double nu_t, zeta, theta_inv; } SphMicropolarPa
 int sph_set_micropolar(SphHandle *h, const SphMicropolarParams *params);
 int sph_get_micropolar(SphHandle *h, SphMicropolarParams *out);
 int sph_micropolar_pair_host(const float *in, int64_t n, float *out, int fast);
+
+/* Elastic solids (opt-in, per fluid object): corotated linear SPH elasticity on a kernel-corrected rest configuration
+   (Becker, Ihmsen, Teschner 2009; the rotation extraction of Mueller et al. 2016).  The object's particles stay fluid: every other pass
+   treats them as before, and one more acceleration is added where a_mp is.  With x0 the positions at capture, x0_ji = x0_j - x0_i,
+   gradW0_ij = gradW(x0_i - x0_j), V0 the rest volume, N0_i the particles j != i of the SAME object that the step's neighbour test
+   accepts at capture (symmetric bit for bit):
+     capture:  M_i = sum_{j in N0_i} V0 x0_ji (x) gradW0_ij;  g0_ij = M_i^-1 gradW0_ij (float64, rounded to f32);  q_i = identity
+     step:     F_i = sum_j V0 (x_j - x_i) (x) g0_ij;  R_i = rotation of F_i (10 warm-started iterations on q_i, which is stored)
+               eps_i = 1/2 (F_i R_i^T + R_i F_i^T) - I;  sig_i = 2 mu eps_i + lambda tr(eps_i) I
+               a_el_i = (V0^2 / m_i) sum_j (sig_i R_i g0_ij - sig_j R_j g0_ji);  v_i <- v_i + dt (a_np_i + a_mp_i + a_el_i)
+     mu = E / (2 (1 + nu)), lambda = E nu / ((1 + nu)(1 - 2 nu)).  All sums read the positions at the start of the non-pressure phase.
+   sph_set_elastic_object marks the object; the NEXT neighbour search that holds particles of it captures it (sph_prepare, or the first
+   step after a late entry) and that call returns the capture's error: SPH_ERR_CAPACITY when a list would exceed
+   SPH_ELASTIC_MAX_NEIGHBOURS entries (no list is ever truncated), SPH_ERR_INVALID when a particle is degenerate (the smallest
+   eigenvalue of M below 1e-3 of the largest: a sheet, fewer than three non-coplanar neighbours; the message names the object and the
+   count), SPH_ERR_UNSUPPORTED when the object's ids are not one contiguous append range.  A refused object stays plain fluid.  Marking
+   a captured object again changes its parameters only.  a_el also enters the non-pressure acceleration where a method keeps one.
+   WCSPH takes its unfused route while an object is marked.  The lists are stored by persistent particle id, which has to be the
+   append order: while an object is marked sph_set_appended_ids and an upload of SPH_F_PARTICLE_ID are refused with
+   SPH_ERR_UNSUPPORTED, and so is marking once either has been used.  SPH_ERR_UNSUPPORTED too: a PBF handle, a sharded handle (and
+   sph_comm_set_slab while an object is marked), particles appended to an object after its capture (sph_append_particles).
+   SPH_ERR_INVALID: E <= 0 or not finite, nu outside [0, 0.49], an object that is unknown or not fluid.
+   sph_get_elastic_rest: the captured lists, row r = particle id first_id + r: nbr int32[count][SPH_ELASTIC_MAX_NEIGHBOURS] (ascending
+   ids, -1 behind the end), g0_ij and g0_ji f32[count][SPH_ELASTIC_MAX_NEIGHBOURS][3] in the scene's frame (zero behind the end).
+   sph_elastic_particle_host: passes A and B of ONE particle from the kernels' own source on the CPU, strict (fast = 0) or fast form,
+   no device.  nnb list entries: xj[nnb][3], g0_ij[nnb][3], g0_ji[nnb][3], the neighbours' pass-A results q_j[nnb][4] and
+   sigma_j[nnb][6]; xi[3], the warm start q_prev[4]; out: F[9], q[4], sigma[6] (pass A) and a_el[3] (pass B on them). */
+#define SPH_ELASTIC_MAX_NEIGHBOURS 64
+typedef struct { double youngs_modulus, poisson_ratio; } SphElasticParams;
+typedef struct {
+    int32_t captured;        /* 0: not marked, 1: marked and waiting for its capture, 2: captured, 3: refused at capture */
+    int32_t count, first_id; /* particles of the object and the first of their ids (captured objects) */
+    int32_t longest_list;
+    float min_eig_ratio;     /* smallest eigenvalue ratio of M over the object's particles */
+    SphElasticParams params;
+} SphElasticObjectInfo;
+int sph_set_elastic_object(SphHandle *h, int object_id, const SphElasticParams *params);
+int sph_get_elastic_object(SphHandle *h, int object_id, SphElasticObjectInfo *out);
+int sph_get_elastic_rest(SphHandle *h, int object_id, int32_t *nbr, float *g0_ij, float *g0_ji);
+int sph_elastic_particle_host(int nnb, const float *xi, const float *xj, const float *g0_ij, const float *g0_ji, const float *q_prev,
+                              const float *q_j, const float *sigma_j, double V0, double mass, double mu, double lambda, float *F_out,
+                              float *q_out, float *sigma_out, float *a_out, int fast);
 
 /* Device rigid integrator (opt-in; the host's "device" rigid backend).  The physics of the host's native backend
    (SPH/rigid_solver/host_rigid_solver.py integrate: semi-implicit Euler in float64 under gravity and the fluid wrench, gyroscopic

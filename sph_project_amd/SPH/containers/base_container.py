@@ -13,6 +13,7 @@ Fields are exposed as small views (`container.particle_positions.to_numpy()`,
 from __future__ import annotations
 
 import os
+import warnings
 
 import numpy as np
 
@@ -81,6 +82,27 @@ class BaseContainer:
         self.vorticity_method, self.vorticity, self.viscosity_omega, self.inertia_inverse = scene.micropolar_of(config, self.METHOD, geo.dim)
         if self.vorticity_method == "micropolar" and engine_opts.get("slab"):
             raise ValueError("Configuration.vorticityMethod \"micropolar\" is not available on a sharded scene (--gpus > 1)")
+        # elastic solids: fluid objects that carry the key "elasticity"; likewise parsed and refused here
+        self.elastic_objects = {}
+        emitter = config.get_cfg("gravitationUpper") is not None
+        for entry in list(config.get_fluid_blocks()) + list(config.get_fluid_bodies()):
+            el = scene.elasticity_of(entry, self.METHOD, geo.dim, emitter=emitter)
+            if el is not None:
+                if engine_opts.get("slab"):
+                    raise ValueError(f"object {entry.get('objectId')}: elasticity is not available on a sharded scene (--gpus > 1)")
+                self.elastic_objects[entry["objectId"]] = el
+        # The time step stays the scene's.  Past the conventional CFL limit 0.4 spacing / c, c = sqrt((lambda + 2 mu) / rho) the elastic
+        # wave speed of the stiffest object, this warns: advice, not a guarantee, and nothing asserts on it.
+        self.elastic_dt_limit = None
+        for entry in list(config.get_fluid_blocks()) + list(config.get_fluid_bodies()):
+            if entry["objectId"] in self.elastic_objects:
+                mu, lam = F.elastic_lame(*self.elastic_objects[entry["objectId"]])
+                limit = 0.4 * float(geo.particle_spacing) / float(np.sqrt((lam + 2.0 * mu) / float(entry["density"])))
+                self.elastic_dt_limit = limit if self.elastic_dt_limit is None else min(self.elastic_dt_limit, limit)
+                dt = float(config.get_cfg("timeStepSize"))
+                if dt > limit:
+                    warnings.warn(f"object {entry['objectId']}: timeStepSize {dt:g} exceeds the elastic limit {limit:g} "
+                                  "(0.4 * particle spacing / sqrt((lambda + 2 mu) / density)); the elastic object may be unstable")
         self.material_rigid, self.material_fluid = scene.MATERIAL_RIGID, scene.MATERIAL_FLUID
         self.dx, self.particle_diameter, self.dh = geo.dx, geo.particle_diameter, geo.dh
         self.particle_spacing, self.V0 = geo.particle_spacing, geo.V0
@@ -215,6 +237,12 @@ class BaseContainer:
             self.engine.set_object(box_id, self.material_rigid, 0)
 
     # ------------------------------------------------------------------ insertion
+    def _mark_elastic(self, obj_id, entry):
+        """Behind the insertion of a fluid object that carries the key "elasticity": the engine captures its rest configuration at the
+        next neighbour search."""
+        if obj_id in self.elastic_objects:
+            self.engine.set_elastic_object(obj_id, *self.elastic_objects[obj_id])
+
     def insert_object(self):
         """base_container.py:212: add every object whose entryTime has come (once)."""
         for fluid in self.fluid_blocks:
@@ -234,6 +262,7 @@ class BaseContainer:
                           velocity=fluid["velocity"], density=fluid["density"], is_dynamic=1, color=fluid["color"],
                           material=self.material_fluid, space=self.particle_spacing,
                           angular_velocity=fluid.get("angularVelocity"))
+            self._mark_elastic(obj_id, fluid)
             self.present_object.append(obj_id)
 
         for body in self.fluid_bodies:
@@ -251,6 +280,7 @@ class BaseContainer:
                                body["density"] * np.ones(n, np.float32), np.zeros(n, np.float32),
                                np.full(n, self.material_fluid, np.int32), np.ones(n, np.int32),
                                np.tile(np.asarray(body["color"], np.int32), (n, 1)))
+            self._mark_elastic(obj_id, body)
             self.present_object.append(obj_id)
 
         for body in self.rigid_bodies:

@@ -43,6 +43,9 @@ class BaseSolver:
         self.vorticity = getattr(container, "vorticity", 0.01)
         self.viscosity_omega = getattr(container, "viscosity_omega", 0.1)
         self.inertia_inverse = getattr(container, "inertia_inverse", 0.5)
+        # elastic solids: {object id: (E, nu)} of the scene's elastic objects
+        self.elastic_objects = dict(getattr(container, "elastic_objects", {}))
+        self.elastic_dt_limit = getattr(container, "elastic_dt_limit", None)   # 0.4 spacing / c of the stiffest object (advice), or None
         self.dt = _DtField(sol.dt)
         self.rigid_solver = PyBulletSolver(container, gravity=self.g, dt=self.dt[None])
         self.engine = container.engine

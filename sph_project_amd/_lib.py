@@ -30,6 +30,9 @@ F_CG_B, F_CG_R, F_CG_P, F_CG_AP, F_CG_V0, F_CG_DINV, F_CG_AP_PARTS = range(36, 4
 F_SURFACE_NORMAL = 43
 # micropolar vorticity model: the angular velocities (up- and download, current order) and a_mp of the last walk (download only)
 F_ANGULAR_VELOCITY, F_MICROPOLAR_ACCEL = 44, 45
+# elastic solids, current order, zero outside captured elastic objects: a_el, F (row-major) and the stress (xx, xy, xz, yy, yz, zz) of the
+# last pass (download only) and the rotation quaternions (x, y, z, w; up- and download)
+F_ELASTIC_ACCEL, F_ELASTIC_DEFGRAD, F_ELASTIC_STRESS, F_ELASTIC_ROTATION = 46, 47, 48, 49
 
 _FIELD_SPEC = {  # field -> (dtype, components)
     F_POSITION: (np.float32, 3), F_VELOCITY: (np.float32, 3), F_ACCELERATION: (np.float32, 3),
@@ -47,6 +50,8 @@ _FIELD_SPEC = {  # field -> (dtype, components)
     F_CG_B: (np.float32, 3), F_CG_R: (np.float32, 3), F_CG_P: (np.float32, 3), F_CG_AP: (np.float32, 3), F_CG_V0: (np.float32, 3),
     F_CG_DINV: (np.float32, 9), F_CG_AP_PARTS: (np.float32, 9), F_SURFACE_NORMAL: (np.float32, 3),
     F_ANGULAR_VELOCITY: (np.float32, 3), F_MICROPOLAR_ACCEL: (np.float32, 3),
+    F_ELASTIC_ACCEL: (np.float32, 3), F_ELASTIC_DEFGRAD: (np.float32, 9), F_ELASTIC_STRESS: (np.float32, 6),
+    F_ELASTIC_ROTATION: (np.float32, 4),
 }
 
 # enum SphPhase
@@ -66,6 +71,8 @@ PH_CG_PREPARE, PH_CG_AP, PH_CG_UPDATE_XR, PH_CG_UPDATE_P, PH_CG_END = 23, 24, 25
 PH_SURFACE_NORMALS = 28
 # micropolar vorticity model: the walk alone (PH_NON_PRESSURE / PH_CG_END then add the stored a_mp)
 PH_MICROPOLAR = 29
+# elastic solids: the scatter and the passes A and B alone (PH_NON_PRESSURE / PH_CG_END then add the stored a_el)
+PH_ELASTIC = 30
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
@@ -81,7 +88,9 @@ K_PBFC_DELTA = 29            # sph_kernel_name(29) == "pbfc_delta": its walk B
 K_RIGID_MOTION = 30          # SPH_K_RIGID_MOTION: the launch that moves the scripted rigid bodies (sph_kernel_name's table ends at 29)
 K_SURFACE_NORMALS = 31       # SPH_K_SURFACE_NORMALS: the normal pass of the Akinci surface tension
 K_MICROPOLAR = 32            # SPH_K_MICROPOLAR: the gather + walk of the micropolar vorticity model
+K_ELASTIC = 33               # SPH_K_ELASTIC: scatter + pass A + pass B of the elastic solids
 RIGID_MOTION_MAX_KEYS = 64
+ELASTIC_MAX_NEIGHBOURS = 64  # SPH_ELASTIC_MAX_NEIGHBOURS
 
 # rigid contact table (sph_get_rigid_contacts): [object A][partner B][normal bin][value]; partners 20..25 are the domain box /
 # the wall planes, one per bin; values: pairs, midpoint sum (3), depth * n sum (3), maximum depth
@@ -194,6 +203,40 @@ def micropolar_pair_host(records, fast=False):
     if rc:
         raise SphError(f"sph_micropolar_pair_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
     return out
+
+
+class SphElasticParams(C.Structure):
+    _fields_ = [("youngs_modulus", C.c_double), ("poisson_ratio", C.c_double)]
+
+
+class SphElasticObjectInfo(C.Structure):
+    _fields_ = [("captured", C.c_int32), ("count", C.c_int32), ("first_id", C.c_int32), ("longest_list", C.c_int32),
+                ("min_eig_ratio", C.c_float), ("params", SphElasticParams)]
+
+
+def elastic_lame(E, nu):
+    """(mu, lambda) of Young's modulus E and Poisson's ratio nu."""
+    return E / (2.0 * (1.0 + nu)), E * nu / ((1.0 + nu) * (1.0 - 2.0 * nu))
+
+
+def elastic_particle_host(xi, xj, g0_ij, g0_ji, q_prev, q_j, sigma_j, V0, mass, mu, lam, fast=False):
+    """Passes A and B of one elastic particle from the kernels' own source run on the CPU (sph_elastic_particle_host): the list's
+    current positions xj (k, 3), rest vectors g0_ij / g0_ji (k, 3), the neighbours' pass-A results q_j (k, 4) and sigma_j (k, 6), the
+    particle's position xi and warm start q_prev -> (F (3, 3), q (4,), sigma (6,), a_el (3,)).  No device."""
+    f = lambda a, c: np.ascontiguousarray(a, dtype=np.float32).reshape(-1, c)
+    xj, g0_ij, g0_ji, q_j, sigma_j = f(xj, 3), f(g0_ij, 3), f(g0_ji, 3), f(q_j, 4), f(sigma_j, 6)
+    k = xj.shape[0]
+    if not (g0_ij.shape[0] == g0_ji.shape[0] == q_j.shape[0] == sigma_j.shape[0] == k):
+        raise ValueError("elastic_particle_host: the list arrays differ in length")
+    xi = np.ascontiguousarray(xi, dtype=np.float32).reshape(3)
+    q_prev = np.ascontiguousarray(q_prev, dtype=np.float32).reshape(4)
+    F, q, sig, a = np.empty(9, np.float32), np.empty(4, np.float32), np.empty(6, np.float32), np.empty(3, np.float32)
+    rc = load().sph_elastic_particle_host(k, _ptr(xi), _ptr(xj), _ptr(g0_ij), _ptr(g0_ji), _ptr(q_prev), _ptr(q_j), _ptr(sigma_j),
+                                          float(V0), float(mass), float(mu), float(lam), _ptr(F), _ptr(q), _ptr(sig), _ptr(a),
+                                          int(bool(fast)))
+    if rc:
+        raise SphError(f"sph_elastic_particle_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
+    return F.reshape(3, 3), q, sig, a
 
 
 class SphPbfStats(C.Structure):
@@ -454,6 +497,10 @@ _SIGNATURES = [
     ("sph_set_micropolar", C.c_int, [_VP, C.POINTER(SphMicropolarParams)]),
     ("sph_get_micropolar", C.c_int, [_VP, C.POINTER(SphMicropolarParams)]),
     ("sph_micropolar_pair_host", C.c_int, [_VP, C.c_int64, _VP, C.c_int]),
+    ("sph_set_elastic_object", C.c_int, [_VP, C.c_int, C.POINTER(SphElasticParams)]),
+    ("sph_get_elastic_object", C.c_int, [_VP, C.c_int, C.POINTER(SphElasticObjectInfo)]),
+    ("sph_get_elastic_rest", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
+    ("sph_elastic_particle_host", C.c_int, [C.c_int] + [_VP] * 7 + [C.c_double] * 4 + [_VP] * 4 + [C.c_int]),
     # device rigid integrator; what each stands in for in the reference's SPH/rigid_solver/bullet_solver.py:
     ("sph_set_rigid_integrator", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),                        # :19-71 __init__ (gravity, dt, walls)
     ("sph_set_rigid_body", C.c_int, [_VP, C.c_int, C.c_double] + [_VP] * 7 + [C.c_int]),        # :75-131 insert_rigid_object
@@ -798,6 +845,27 @@ class Engine(NativeObject):
         p = SphMicropolarParams()
         self._chk(self.lib.sph_get_micropolar(self.h, C.byref(p)), "sph_get_micropolar")
         return {"method": {v: k for k, v in VORTICITY_METHODS.items()}[p.method], "nu_t": p.nu_t, "zeta": p.zeta, "theta_inv": p.theta_inv}
+
+    # -- elastic solids
+    def set_elastic_object(self, object_id, youngs_modulus, poisson_ratio=0.3):
+        """Marks a fluid object as an elastic solid; the next neighbour search that holds its particles captures its rest configuration."""
+        p = SphElasticParams(float(youngs_modulus), float(poisson_ratio))
+        self._chk(self.lib.sph_set_elastic_object(self.h, int(object_id), C.byref(p)), "sph_set_elastic_object")
+
+    def get_elastic_object(self, object_id):
+        p = SphElasticObjectInfo()
+        self._chk(self.lib.sph_get_elastic_object(self.h, int(object_id), C.byref(p)), "sph_get_elastic_object")
+        return {"captured": p.captured == 2, "state": p.captured, "count": p.count, "first_id": p.first_id, "longest_list": p.longest_list,
+                "min_eig_ratio": p.min_eig_ratio, "youngs_modulus": p.params.youngs_modulus, "poisson_ratio": p.params.poisson_ratio}
+
+    def get_elastic_rest(self, object_id):
+        """(nbr int32 (count, 64), g0_ij float32 (count, 64, 3), g0_ji likewise) of a captured object; row r = particle id first_id + r."""
+        n = self.get_elastic_object(object_id)["count"]
+        nbr = np.empty((n, ELASTIC_MAX_NEIGHBOURS), np.int32)
+        gij = np.empty((n, ELASTIC_MAX_NEIGHBOURS, 3), np.float32)
+        gji = np.empty((n, ELASTIC_MAX_NEIGHBOURS, 3), np.float32)
+        self._chk(self.lib.sph_get_elastic_rest(self.h, int(object_id), _ptr(nbr), _ptr(gij), _ptr(gji)), "sph_get_elastic_rest")
+        return nbr, gij, gji
 
     # -- device rigid integrator (the "device" rigid backend)
     def set_rigid_integrator(self, on=True, gravity=(0.0, 0.0, 0.0), wall_lo=(0.0, 0.0, 0.0), wall_hi=(0.0, 0.0, 0.0)):

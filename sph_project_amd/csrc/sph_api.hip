@@ -25,6 +25,9 @@ struct ProfSlot {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// elastic solids: one object as the host keeps it (sph_elastic_api.hpp).  state: the values of SphElasticObjectInfo::captured
+struct ElObjHost { int state = 0; double E = 0.0, nu = 0.0; int id0 = 0, n = 0, longest = 0, slot = -1; float min_ratio = 0.0f; float4 *rest = nullptr; };
+
 struct SphHandle : ErrSink {
     SphParams prm = {};
     State st;
@@ -84,6 +87,12 @@ struct SphHandle : ErrSink {
     int inv[3] = {0, 1, 2};        // scene axis k    = library axis inv[k]
     float axial = 1.0f;            // parity of the permutation: sign of axial vectors (torque, angular velocity) across the boundary
     int slab_axis = 2;             // library axis the slabs are cut along (Consts::slab_axis): 2 = z (default), 0 = x (SPH_SLAB_LAYOUT=slow)
+    // elastic solids: the objects, and for EVERY object the id range its appends made (first id, count, whether another object's append
+    // split it); el_rc: the error of a capture that ran inside a neighbour search, returned by the call that searched (check_async)
+    ElObjHost el[SPH_NOBJ];
+    int obj_first[SPH_NOBJ] = {}, obj_n[SPH_NOBJ] = {};
+    bool obj_split[SPH_NOBJ] = {};
+    int el_rc = 0;
 };
 
 // layers of the whole scene along the slab axis / setting the local window [lo_ghost, top) of a rank
@@ -367,6 +376,8 @@ extern "C" int sph_append_particles(SphHandle *h, int object_id, int n, const fl
     if (n == 0) return SPH_OK;
     if (!pos || !vel || !density || !material || !is_dynamic) return fail(h, SPH_ERR_INVALID, "append: null array");
     { int rc = slab_settle_if_needed(h); if (rc) return rc; }
+    if (object_id >= 0 && object_id < SPH_NOBJ && h->el[object_id].state == 2)
+        return fail(h, SPH_ERR_UNSUPPORTED, "append: object %d is an elastic solid whose rest configuration has been captured", object_id);
     if (h->n + n > h->st.cap) return fail(h, SPH_ERR_CAPACITY, "append: %d + %d exceeds particle_max_num %d", h->n, n, h->st.cap);
     HIPCHK(h, hipSetDevice(h->device));
     State &s = h->st;
@@ -409,6 +420,11 @@ extern "C" int sph_append_particles(SphHandle *h, int object_id, int n, const fl
     HIPCHK(h, hipMemcpy(s.rho.cur() + off, hr.data(), sizeof(float) * n, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(s.prs + off, hpr.data(), sizeof(float) * n, hipMemcpyHostToDevice));
     if (s.orig.cur()) HIPCHK(h, hipMemcpy(s.orig.cur() + off, hp.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
+    if (object_id >= 0 && object_id < SPH_NOBJ) {   // the id range of the object (ids = append order)
+        if (h->obj_n[object_id] == 0) h->obj_first[object_id] = h->n;
+        else if (h->obj_first[object_id] + h->obj_n[object_id] != h->n) h->obj_split[object_id] = true;
+        h->obj_n[object_id] += n;
+    }
     h->n += n;
     h->n_fluid += nfl;
     h->n_nonfluid += n - nfl;
@@ -431,6 +447,7 @@ extern "C" int sph_set_appended_ids(SphHandle *h, int n, const int32_t *ids) {
     if (!h || !ids || n < 0 || n > h->n) return fail(h, SPH_ERR_INVALID, "set_appended_ids: bad arguments");
     if (n == 0) return SPH_OK;
     if (h->st.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: the micropolar model is on (its angular velocities are stored by id, in append order)");
+    if (h->st.el_marked) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: an elastic object exists (its rest lists are stored by id, in append order)");
     h->st.ids_custom = 1;
     HIPCHK(h, hipSetDevice(h->device));
     colors_leave_home(h);
@@ -1077,11 +1094,14 @@ extern "C" int sph_measure_copy_rate(SphHandle *h, size_t bytes, int reps, doubl
 
 // ---------------------------------------------------------------------------------- phases
 static int check_async(SphHandle *h) {
+    if (h->el_rc) { const int rc = h->el_rc; h->el_rc = 0; return rc; }   // (a capture inside this call's neighbour search failed: its message stands)
     if (h->st.state_error) { const int se = h->st.state_error; h->st.state_error = 0; return fail(h, SPH_ERR_INVALID, "internal state error %d (bit 0: a sort was scanned without a histogram of its own; bit 1: a density launch could not move the arrays its sort left to it)", se); }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, SPH_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     return SPH_OK;
 }
+
+#include "sph_elastic_api.hpp"
 
 // base_container.py:544 prepare_neighborhood_search
 // rho_dead: the kernel the caller launches next rewrites every particle's density (Launch::scatter_stable)
@@ -1089,10 +1109,12 @@ static int check_async(SphHandle *h) {
 static SortCarry ph_neighbor_search(SphHandle *h, bool rho_dead = false, bool density_next = false) {
     State &s = h->st;
     SortCarry carry;
+    const bool capture = s.el_pending && el_capture_due(h);   // (the capture reads meta and ids in sorted order: this sort leaves nothing to the density pass)
     { ProfScope p(h, SPH_K_HASH_COUNT); h->L->hash_count(s); }
     { ProfScope p(h, SPH_K_SCAN); h->L->scan(s); }
-    { ProfScope p(h, SPH_K_SCATTER); if (h->prm.deterministic) carry = h->L->scatter_stable(s, rho_dead, density_next && !getenv("SPH_NO_SORT_CARRY")); else h->L->scatter(s); }
+    { ProfScope p(h, SPH_K_SCATTER); if (h->prm.deterministic) carry = h->L->scatter_stable(s, rho_dead, density_next && !capture && !getenv("SPH_NO_SORT_CARRY")); else h->L->scatter(s); }
     h->sort_dirty = false;
+    if (capture) { const int rc = el_capture_pending(h); if (rc && !h->el_rc) h->el_rc = rc; }
     return carry;
 }
 
@@ -1396,6 +1418,10 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
             if (!s.mp_on) return fail(h, SPH_ERR_INVALID, "SPH_PH_MICROPOLAR: the micropolar model is off (sph_set_micropolar)");
             ph_micropolar(h);
             break;
+        case SPH_PH_ELASTIC:
+            if (!s.el_marked) return fail(h, SPH_ERR_INVALID, "SPH_PH_ELASTIC: no elastic object (sph_set_elastic_object)");
+            ph_elastic(h);
+            break;
         case SPH_PH_PRESSURE_INTEGRATE: { ProfScope p(h, SPH_K_PRESSURE_INTEGRATE); h->L->pressure_integrate(s); } break;
         case SPH_PH_RIGID_CONTACT: {
             if (!s.contact_on) return fail(h, SPH_ERR_INVALID, "SPH_PH_RIGID_CONTACT: sph_set_rigid_contact is off");
@@ -1403,7 +1429,7 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
             ProfScope p(h, SPH_K_RIGID_CONTACT); h->L->rigid_contact(s);
         } break;
         case SPH_PH_CG_PREPARE: case SPH_PH_CG_AP: case SPH_PH_CG_UPDATE_XR: case SPH_PH_CG_UPDATE_P: case SPH_PH_CG_END:
-            { int rc = cg_run_phase(h, phase); if (rc) return rc; if (phase == SPH_PH_CG_END) ph_micropolar_apply(h); } break;   // (micropolar model: + the STORED a_mp)
+            { int rc = cg_run_phase(h, phase); if (rc) return rc; if (phase == SPH_PH_CG_END) { ph_micropolar_apply(h); ph_elastic_apply(h); } } break;   // (micropolar model: + the STORED a_mp; elastic solids: + the STORED a_el)
         default: { int rc = method_run_phase(h, phase); if (rc) return rc; }
     }
     int rc = check_async(h); if (rc) return rc;
@@ -1519,6 +1545,7 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
         for (size_t i = 0; i < n; ++i) { const float v[3] = {tmp[i].x, tmp[i].y, tmp[i].z}; d[3 * i] = v[ix0]; d[3 * i + 1] = v[ix1]; d[3 * i + 2] = v[ix2]; }
         return SPH_OK;
     }
+    if (field >= SPH_F_ELASTIC_ACCEL && field <= SPH_F_ELASTIC_ROTATION) return el_download(h, field, (float *)dst, bytes);
     if (field == SPH_F_ANGULAR_VELOCITY) {   // at home by particle id -> the current order; library frame -> scene frame, axial
         if (!s.mp_w_home) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated (sph_set_micropolar)", field);
         if (bytes != n * 12) return fail(h, SPH_ERR_INVALID, "download: field %d needs %zu bytes, got %zu", field, n * 12, bytes);
@@ -1652,6 +1679,7 @@ extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes
         HIPCHK(h, hipMemcpy(vdst, tmp.data(), n * sizeof(float4), hipMemcpyHostToDevice));
         return SPH_OK;
     }
+    if (field == SPH_F_ELASTIC_ROTATION) return el_upload_rotation(h, (const float *)src, bytes);
     if (field == SPH_F_ANGULAR_VELOCITY) {   // the current order -> home by particle id; scene frame -> library frame, axial
         if (!s.mp_w_home) return fail(h, SPH_ERR_UNSUPPORTED, "upload: field %d not allocated (sph_set_micropolar)", field);
         if (bytes != n * 12) return fail(h, SPH_ERR_INVALID, "upload: field %d needs %zu bytes", field, n * 12);
@@ -1673,6 +1701,7 @@ extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes
     if (field == SPH_F_PARTICLE_ID) {  // global ids when a scene is split over ranks
         if (bytes != n * 4) return fail(h, SPH_ERR_INVALID, "upload: size mismatch");
         if (s.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while the micropolar model is on (its angular velocities are stored by id, in append order)");
+        if (s.el_marked) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while an elastic object exists (its rest lists are stored by id, in append order)");
         s.ids_custom = 1;
         colors_leave_home(h); HIPCHK(h, hipStreamSynchronize(s.stream));
         HIPCHK(h, hipMemcpy(s.pid.cur(), src, n * 4, hipMemcpyHostToDevice));

@@ -511,6 +511,13 @@ struct TextDev {
     hipStream_t stream;
 };
 
+// Elastic solids (sph_elastic.hpp).  One captured object as its two passes see it: rows = ids id0 .. id0 + n - 1 (a contiguous append
+// range), the rest table rest[(2 k + plane) n + row] for k < kmax (k-major; plane 0 = (g0_ij, bits of j), plane 1 = (g0_ji, 0); j = -1
+// ends a list), the Lame constants.
+struct ElObjDev { int id0, n, kmax; float mu, lambda; float4 *rest; };
+// one capture: the object, its id range, a table of all ELASTIC_MAX_NEIGHBOURS entries, the counters (k_elastic_capture)
+struct ElCaptureArgs { int obj, id0, n; float4 *rest; unsigned *cnt; };
+
 template <class T> struct DBuf {
     T *b[2] = {nullptr, nullptr};
     int c = 0;
@@ -699,6 +706,18 @@ struct State {
     int mp_on = 0, ids_custom = 0;
     double mp_nu_t = 0.01, mp_zeta = 0.1, mp_theta_inv = 0.5;
     float4 *mp_w_home = nullptr, *mp_w_sorted = nullptr, *mp_acc = nullptr;
+    // Elastic solids (sph_set_elastic_object; sph_elastic.hpp): nothing is allocated or launched until an object is marked.  el_marked:
+    // objects marked elastic, captured or waiting (WCSPH takes its unfused route while > 0); el_pending: those waiting for the next
+    // sort that holds their particles; el_obj[0 .. el_nobj): the captured ones, el_mask: bit o = object o is among them.  At home by
+    // particle id (ids = append order, as mp_w_home): positions and slots (the scatter's), q (double-buffered: pass A reads
+    // el_q[el_qi] and writes the other, then el_qi flips), sigma (2 float4 per id), F (3 float4 per id).  el_acc: a_el of the last
+    // pass B in sorted order (valid until the next sort).  el_cnt: the capture's counters (k_elastic_capture).
+    int el_marked = 0, el_pending = 0, el_nobj = 0, el_qi = 0;
+    unsigned el_mask = 0;
+    ElObjDev el_obj[SPH_NOBJ] = {};
+    float4 *el_x_home = nullptr, *el_q[2] = {nullptr, nullptr}, *el_sig = nullptr, *el_F = nullptr, *el_acc = nullptr;
+    int *el_slot_home = nullptr;
+    unsigned *el_cnt = nullptr;
 };
 
 // What a list sort's gather left behind for the density pass launched next (Launch::scatter_stable, density_next): thread d of a tile does
@@ -743,6 +762,9 @@ struct Launch {
     void (*surface_normals)(State &);   // Akinci surface tension: the colour-field normals (State::st_normal), before non_pressure
     void (*micropolar)(State &);         // micropolar model: gather w, the walk (State::mp_acc, mp_w_home), before non_pressure
     void (*micropolar_apply)(State &);   // ... and v += dt a_mp (+ the kept non-pressure acceleration) behind it
+    void (*elastic)(State &);            // elastic solids: scatter, pass A, pass B over the captured objects (State::el_acc), before non_pressure
+    void (*elastic_apply)(State &);      // ... and v += dt a_el (+ the kept non-pressure acceleration) behind it
+    void (*elastic_capture)(State &, const ElCaptureArgs &);   // one object's rest configuration, on the cell lists of the sort that has just run
     void (*non_pressure)(State &, const float4 *visc_vel);   // visc_vel: velocities for the viscous term (implicit viscosity: cg_x), null: the particles' own
     void (*pressure_integrate)(State &);
     void (*wcsph_forces)(State &, ForceOpts o); // non_pressure + pressure_integrate in one neighbour walk (WCSPH)

@@ -524,6 +524,7 @@ void l_clear_fresh(State &s) {
 #include "sph_rigid_motion.hpp"
 #include "sph_surface.hpp"
 #include "sph_surface_aniso.hpp"
+#include "sph_elastic.hpp"
 #include "sph_surface_post.hpp"
 #include "sph_render.hpp"
 #include "sph_render_surface.hpp"
@@ -563,6 +564,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_pbf_launchers(L);
         register_pbfc_launchers(L);
         register_contact_launchers(L);
+        register_elastic_launchers(L);
         register_rigid_launchers(L);
         register_contact_solve_launchers(L);
         register_rigid_motion_launchers(L);

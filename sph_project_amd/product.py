@@ -280,6 +280,43 @@ def stirred_tank_scene(edge=10, omega=10.0, method="wcsph", gravity=0.0, radius=
     return cfg
 
 
+def jelly_scene(edge=8, young=2.0e4, poisson=0.3, drop=2, pool=0, method="dfsph", radius=0.01, dt=2.5e-4, gravity=9.81, viscosity=0.01,
+                margin=6, **keys):
+    """The first scene of the elastic solids: a cube of edge^3 particles on the rest lattice, `drop` particle diameters
+    above the floor of a closed sampled box (or above the surface of a pool of plain fluid, `pool` layers deep, that fills the box from
+    wall to wall), under gravity (the magnitude along -y).  The cube is object 0 and carries the key "elasticity" (young = None leaves
+    the key out: the same cube as plain fluid); the pool is object 1.  `margin`: particle diameters between the cube and the box's
+    faces sideways (the shell takes the first 3.5).  keys: further Configuration keys."""
+    d = 2.0 * radius
+    floor = 4 * d                      # first lattice plane above the box's shell
+    lo = margin * d
+    side = lo + edge * d + lo
+    y0 = floor + (pool + drop) * d if pool else floor + drop * d
+    height = y0 + (edge + 6) * d + 4 * d
+    cfg = {
+        "Configuration": {
+            "domainStart": [0.0, 0.0, 0.0], "domainEnd": [side, height, side], "addDomainBox": True, "particleRadius": radius,
+            "density0": 1000, "simulationMethod": method, "viscosityMethod": "standard", "gravitation": [0.0, -float(gravity), 0.0],
+            "timeStepSize": dt, "viscosity": viscosity,
+        },
+        "FluidBlocks": [{
+            "objectId": 0, "start": [lo, y0, lo], "end": [lo + (edge - 0.5) * d, y0 + (edge - 0.5) * d, lo + (edge - 0.5) * d],
+            "translation": [0.0, 0.0, 0.0], "scale": [1, 1, 1], "velocity": [0.0, 0.0, 0.0], "density": 1000.0,
+            "color": [230, 90, 120], "entryTime": -1.0,
+        }],
+    }
+    if young is not None:
+        cfg["FluidBlocks"][0]["elasticity"] = {"youngsModulus": float(young), "poissonRatio": float(poisson)}
+    if pool:
+        cfg["FluidBlocks"].append({
+            "objectId": 1, "start": [floor, floor, floor], "end": [side - floor - 0.5 * d, floor + (pool - 0.5) * d, side - floor - 0.5 * d],
+            "translation": [0.0, 0.0, 0.0], "scale": [1, 1, 1], "velocity": [0.0, 0.0, 0.0], "density": 1000.0,
+            "color": [50, 100, 200], "entryTime": -1.0,
+        })
+    cfg["Configuration"].update(keys)
+    return cfg
+
+
 def scene_particles(cfg_dict):
     """Host lattice of every object present at prepare(), in the reference's insertion order
     (domain box first: base_container.py:192, then FluidBlocks: :215).  Blocks with entryTime > 0 are listed with
