@@ -225,6 +225,10 @@ typedef enum {
        (and SPH_PH_CG_END) then add the STORED a_el behind their pass, v += dt a_el; a step runs the passes in front of its
        non-pressure pass. */
     SPH_PH_ELASTIC = 30,
+    /* Fluid emitters (sph_set_emitter; SPH_ERR_INVALID while none is set): the hold and the emission of the CURRENT step count alone --
+       what sph_prepare's emission did for count 0 -- i.e. the held layers are put on their closed form at T_steps and the layers
+       born(steps) not emitted yet are emitted.  Idempotent: a second run emits nothing. */
+    SPH_PH_EMIT = 31,
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -273,6 +277,7 @@ typedef enum {
     SPH_K_SURFACE_NORMALS = 31, /* Akinci surface tension: the normal pass (the Akinci force pass itself is SPH_K_NON_PRESSURE); "?" as well */
     SPH_K_MICROPOLAR = 32,      /* micropolar vorticity model: the gather of the angular velocities + the walk (v += dt a_mp: SPH_K_MISC); "?" as well */
     SPH_K_ELASTIC = 33,         /* elastic solids: the scatter + pass A + pass B (v += dt a_el: SPH_K_MISC; the capture: SPH_K_MISC); "?" as well */
+    SPH_K_EMIT = 34,            /* fluid emitters: the hold launch and the emit launch (sph_set_emitter); "?" as well */
     SPH_K_COUNT_
 } SphKernelId;
 
@@ -546,6 +551,78 @@ int sph_set_rigid_motion(SphHandle *h, int object_id, const SphRigidMotion *prog
 int sph_get_rigid_motion_state(SphHandle *h, int object_id, SphRigidMotionState *out);
 int sph_rigid_motion_eval_host(const SphRigidMotion *program, const double *com_rest, const double *rot_rest, double dt, int64_t k,
                                SphRigidMotionState *out);
+
+/* Fluid emitters (opt-in; the scene list "Emitters"): a nozzle -- a rectangle or a circle in a plane -- that emits layers
+   of fluid particles on the device.  The program is given in canonical form: direction, tangent1, tangent2 an orthonormal basis computed
+   once on the host, end = +infinity for "until the budget is spent".  With spacing = 2 particle_radius:
+     lattice:  nu = floor(width / spacing), nv = floor(height / spacing) (circle: both floor(2 radius / spacing)); point (i, j) lies at
+               ((i + 0.5 - nu / 2) spacing) tangent1 + ((j + 0.5 - nv / 2) spacing) tangent2; a circle keeps a^2 + b^2 <= radius^2;
+               layer_n = the number of points; order j slow, i fast, the circle's gaps closed
+     schedule: dt = (double)(float)timeStepSize, T_k = k dt (k = steps completed since sph_prepare: a product, never a running sum)
+               s(k) = speed max(0, min(T_k, end) - start);  max_layers = floor(max_particles / layer_n)
+               born(k) = 0 if T_k < start, else min(max_layers, floor(s(k) / spacing) + 1);  a_j(k) = s(k) - j spacing
+               layer j < born(k) is HELD while a_j(k) < hold spacing and T_k <= end
+   All of it in float64 with every product rounded, in both builds; a position  position + a_j direction + a tangent1 + b tangent2  is
+   rounded to float32 once.  sph_prepare emits born(0); the step that takes the count from k - 1 to k emits the layers born(k - 1) ..
+   born(k) - 1 at its insertion point (sph_step / sph_step_async: behind the rigid integrator's launch; sph_step_end: behind the
+   boundary pass of what the host appended), ONE launch (k_emit, one thread per newborn particle of all emitters) that writes what
+   sph_append_particles writes -- ids = the particle count at that moment + the index within the batch, emitters in index order --
+   and applies the domain boundary; before it ONE elementwise launch (k_emit_hold) overwrites position and velocity of every held particle
+   (found by id) with the closed form at T_k.  Both are profiled as SPH_K_EMIT; steps in which no layer is born / held launch
+   neither.  The host evaluates the schedule itself: no read-back, no copy, no synchronisation per step.  The capacity
+   max_layers layer_n of every emitter is reserved inside particle_max_num: sph_set_emitter returns SPH_ERR_CAPACITY when the budgets
+   do not fit, sph_append_particles when an append would eat into them, emission never.
+   sph_set_emitter: before sph_prepare only (SPH_ERR_INVALID after it); index 0 .. SPH_MAX_EMITTERS - 1 (a set index may be replaced).
+   SPH_ERR_UNSUPPORTED, with a message that names the emitter: a sharded handle (and sph_comm_set_slab while an emitter is set), a PBF handle
+   (either variant: PBF never inserts), a handle with g_upper set (gravitationUpper), an axis order other than "xyz"; and, once an
+   emitter is set, sph_set_appended_ids, an upload of SPH_F_PARTICLE_ID, sph_set_elastic_object on an emitter's object and
+   sph_append_particles into it.  SPH_ERR_INVALID, with a message that names the emitter and the field: an object id that is out of
+   range, owns particles or belongs to another emitter, an unknown shape, a basis that is not orthonormal, a size, speed, density or
+   max_particles that is not positive and finite, layer_n == 0, max_particles < layer_n, hold outside 0 .. SPH_EMITTER_MAX_HOLD,
+   end <= start, speed dt > 0.5 spacing (so at most one layer per emitter is born per step).
+   sph_get_emitter_state: what the host knows, no device access.  sph_emitter_eval_host: the kernels' routine on the CPU (the same
+   source): the schedule after k steps and, with layer >= 0 and xyz != NULL, the float32 positions xyz[layer_n][3] of that layer at
+   that count (the domain boundary not applied).  No device is touched. */
+#define SPH_MAX_EMITTERS 8
+#define SPH_EMITTER_MAX_HOLD 8
+#define SPH_EMITTER_RECTANGLE 0
+#define SPH_EMITTER_CIRCLE 1
+typedef struct {
+    int32_t object_id;                 /* a fluid object of its own */
+    int32_t shape;                     /* SPH_EMITTER_RECTANGLE, SPH_EMITTER_CIRCLE */
+    int32_t max_particles;             /* the emitter's budget */
+    int32_t hold;                      /* layers kept kinematic behind the plane, 0 .. SPH_EMITTER_MAX_HOLD */
+    double position[3];                /* centre of the nozzle plane */
+    double direction[3], tangent1[3], tangent2[3];   /* orthonormal; tangent1 carries "width", tangent2 "height" */
+    double width, height;              /* rectangle, metres */
+    double radius;                     /* circle, metres */
+    double speed;                      /* m/s along direction */
+    double start, end;                 /* scene time, seconds; end = +infinity: until the budget is spent */
+    double density;                    /* kg/m^3: mass = V0 density */
+    int32_t color[3];                  /* 0 .. 255 */
+    int32_t reserved;                  /* 0 */
+} SphEmitter;
+typedef struct {
+    int32_t object_id, layer_particles, max_layers;
+    int32_t layers;                    /* layers born so far */
+    int32_t emitted;                   /* particles emitted so far = layers * layer_particles */
+    int32_t held_layers;               /* layers the last slot held (the schedule at the current step count) */
+    int32_t held_first;                /* index of the first of them */
+    int32_t exhausted;                 /* layers == max_layers, or the current time is past `end` */
+    int32_t held_id_base[SPH_EMITTER_MAX_HOLD + 1];   /* persistent id of the first particle of each held layer */
+    int32_t reserved[3];
+} SphEmitterState;
+typedef struct {
+    double T, s;                       /* T_k, s(k) */
+    int32_t born;                      /* born(k) */
+    int32_t held_first, held_layers;   /* the held range [held_first, held_first + held_layers) */
+    int32_t layer_particles, max_layers, nu, nv;
+    int32_t reserved;
+    double layer_offset;               /* a_layer(k) of the layer asked for (0 when layer < 0) */
+} SphEmitterEval;
+int sph_set_emitter(SphHandle *h, int index, const SphEmitter *emitter);
+int sph_get_emitter_state(SphHandle *h, int index, SphEmitterState *out);
+int sph_emitter_eval_host(const SphEmitter *emitter, double dt, double spacing, int64_t k, int layer, SphEmitterEval *out, float *xyz);
 
 /* --- time stepping --------------------------------------------------------------------- */
 /* replaces XSolver.prepare() (base_solver.py:683, DFSPH.py:321, PCISPH.py:188); particles of

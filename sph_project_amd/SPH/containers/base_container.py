@@ -91,6 +91,10 @@ class BaseContainer:
                 if engine_opts.get("slab"):
                     raise ValueError(f"object {entry.get('objectId')}: elasticity is not available on a sharded scene (--gpus > 1)")
                 self.elastic_objects[entry["objectId"]] = el
+        # fluid emitters: the top-level list "Emitters"; likewise parsed and refused here
+        self.emitters = scene.emitters_of(config, self.METHOD, geo.dim)
+        if self.emitters and engine_opts.get("slab"):
+            raise ValueError("Emitters are not available on a sharded scene (--gpus > 1)")
         # The time step stays the scene's.  Past the conventional CFL limit 0.4 spacing / c, c = sqrt((lambda + 2 mu) / rho) the elastic
         # wave speed of the stiffest object, this warns: advice, not a guarantee, and nothing asserts on it.
         self.elastic_dt_limit = None
@@ -154,11 +158,14 @@ class BaseContainer:
         self.rigid_blocks = self.cfg.get_rigid_blocks()
         for _ in self.rigid_blocks:
             raise NotImplementedError  # base_container.py:105-106
-        n_objects = len(self.fluid_blocks) + len(self.fluid_bodies) + len(self.rigid_blocks) + len(self.rigid_bodies)
+        n_objects = len(self.fluid_blocks) + len(self.fluid_bodies) + len(self.rigid_blocks) + len(self.rigid_bodies) + len(self.emitters)
+        emitter_n = sum(e["maxLayers"] * e["layerParticles"] for e in self.emitters)   # the emitters' budgets: reserved up front
         self.rigid_body_particle_num_total = rigid_n
         box_n = (scene.box_particle_num(self.domain_box_start, self.domain_box_size, self.domain_box_thickness,
                                         self.particle_spacing) if self.add_domain_box else 0)
-        self.particle_max_num = fluid_n + rigid_n + box_n
+        self.particle_max_num = fluid_n + rigid_n + box_n + emitter_n
+        if self.add_domain_box and any(e["objectId"] == n_objects for e in self.emitters):
+            raise ValueError(f"Emitters: objectId {n_objects} is the domain box's (addDomainBox takes the id behind the scene's objects)")
         self._object_num = n_objects + (1 if self.add_domain_box else 0)
         self.object_num = _Scalar(lambda: self._object_num)
 
@@ -200,6 +207,17 @@ class BaseContainer:
             self.engine.comm_init(self.slab["rank"], self.slab["nranks"], self.slab["unique_id"])
             cuts = self.slab["cuts"]
             self.engine.comm_set_slab(cuts[self.slab["rank"]], cuts[self.slab["rank"] + 1])
+
+        # every emitter's object is a fluid object with zero particles that grows on the device (sph_set_emitter)
+        for index, e in enumerate(self.emitters):
+            oid = e["objectId"]
+            self.object_id_fluid_body.add(oid)
+            self.object_visibility[oid] = 1
+            self.object_materials[oid] = self.material_fluid
+            self.object_collection[oid] = e
+            self.engine.set_object(oid, self.material_fluid, 0)
+            self.engine.set_emitter(index, F.emitter_program(e))
+            self.present_object.append(oid)
 
         self.particle_num = _Scalar(lambda: self.engine.particle_num)
         self.fluid_particle_num = _Scalar(lambda: self.engine.fluid_particle_num)

@@ -20,6 +20,24 @@ class _DtField:
         return self._v
 
 
+class EmitterView:
+    """Read-only view of one fluid emitter; every attribute is read from sph_get_emitter_state when somebody looks."""
+
+    def __init__(self, engine, index):
+        self._engine, self.index = engine, index
+
+    def _state(self):
+        return self._engine.get_emitter_state(self.index)
+
+    object_id = property(lambda self: self._state()["object_id"])
+    layer_particles = property(lambda self: self._state()["layer_particles"])
+    max_layers = property(lambda self: self._state()["max_layers"])
+    emitted = property(lambda self: self._state()["emitted"])
+    layers = property(lambda self: self._state()["layers"])
+    held_layers = property(lambda self: self._state()["held_layers"])
+    exhausted = property(lambda self: bool(self._state()["exhausted"]))
+
+
 class BaseSolver:
     def __init__(self, container: BaseContainer):
         self.container = container
@@ -49,6 +67,7 @@ class BaseSolver:
         self.dt = _DtField(sol.dt)
         self.rigid_solver = PyBulletSolver(container, gravity=self.g, dt=self.dt[None])
         self.engine = container.engine
+        self.emitters = [EmitterView(self.engine, k) for k in range(len(getattr(container, "emitters", [])))]
         if self.viscosity_method == "implicit":
             self.cg_tol = 1e-6
 

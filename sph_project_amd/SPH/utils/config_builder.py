@@ -37,3 +37,7 @@ class SimConfig:
 
     def get_fluid_blocks(self):
         return self._list("FluidBlocks")
+
+    def get_emitters(self):
+        """The top-level list "Emitters" (this project's; the reference ignores unknown top-level lists)."""
+        return self._list("Emitters")

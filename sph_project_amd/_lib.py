@@ -73,6 +73,7 @@ PH_SURFACE_NORMALS = 28
 PH_MICROPOLAR = 29
 # elastic solids: the scatter and the passes A and B alone (PH_NON_PRESSURE / PH_CG_END then add the stored a_el)
 PH_ELASTIC = 30
+PH_EMIT = 31   # fluid emitters: the hold and the emission of the current step count alone
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
@@ -89,7 +90,11 @@ K_RIGID_MOTION = 30          # SPH_K_RIGID_MOTION: the launch that moves the scr
 K_SURFACE_NORMALS = 31       # SPH_K_SURFACE_NORMALS: the normal pass of the Akinci surface tension
 K_MICROPOLAR = 32            # SPH_K_MICROPOLAR: the gather + walk of the micropolar vorticity model
 K_ELASTIC = 33               # SPH_K_ELASTIC: scatter + pass A + pass B of the elastic solids
+K_EMIT = 34                  # SPH_K_EMIT: the hold launch and the emit launch of the fluid emitters
 RIGID_MOTION_MAX_KEYS = 64
+MAX_EMITTERS = 8             # SPH_MAX_EMITTERS
+EMITTER_MAX_HOLD = 8         # SPH_EMITTER_MAX_HOLD
+EMITTER_SHAPES = {"rectangle": 0, "circle": 1}
 ELASTIC_MAX_NEIGHBOURS = 64  # SPH_ELASTIC_MAX_NEIGHBOURS
 
 # rigid contact table (sph_get_rigid_contacts): [object A][partner B][normal bin][value]; partners 20..25 are the domain box /
@@ -159,6 +164,58 @@ def rigid_motion_eval_host(program, com_rest, rot_rest, dt, k):
     if rc:
         raise SphError(f"sph_rigid_motion_eval_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
     return rigid_motion_state_dict(st)
+
+
+class SphEmitter(C.Structure):
+    """A fluid emitter's program in canonical form (include/sph_hip.h): an orthonormal basis, end = +inf for never."""
+    _fields_ = [
+        ("object_id", C.c_int32), ("shape", C.c_int32), ("max_particles", C.c_int32), ("hold", C.c_int32),
+        ("position", C.c_double * 3), ("direction", C.c_double * 3), ("tangent1", C.c_double * 3), ("tangent2", C.c_double * 3),
+        ("width", C.c_double), ("height", C.c_double), ("radius", C.c_double), ("speed", C.c_double),
+        ("start", C.c_double), ("end", C.c_double), ("density", C.c_double),
+        ("color", C.c_int32 * 3), ("reserved", C.c_int32),
+    ]
+
+
+class SphEmitterState(C.Structure):
+    _fields_ = [("object_id", C.c_int32), ("layer_particles", C.c_int32), ("max_layers", C.c_int32), ("layers", C.c_int32),
+                ("emitted", C.c_int32), ("held_layers", C.c_int32), ("held_first", C.c_int32), ("exhausted", C.c_int32),
+                ("held_id_base", C.c_int32 * 9), ("reserved", C.c_int32 * 3)]
+
+
+class SphEmitterEval(C.Structure):
+    _fields_ = [("T", C.c_double), ("s", C.c_double), ("born", C.c_int32), ("held_first", C.c_int32), ("held_layers", C.c_int32),
+                ("layer_particles", C.c_int32), ("max_layers", C.c_int32), ("nu", C.c_int32), ("nv", C.c_int32), ("reserved", C.c_int32),
+                ("layer_offset", C.c_double)]
+
+
+def emitter_program(spec):
+    """SphEmitter from a canonical emitter dict (scene.emitters_of)."""
+    e = SphEmitter()
+    e.object_id, e.shape = int(spec["objectId"]), EMITTER_SHAPES[spec["shape"]]
+    e.max_particles, e.hold = int(spec["maxParticles"]), int(spec["hold"])
+    for name, key in (("position", "position"), ("direction", "direction"), ("tangent1", "tangent1"), ("tangent2", "tangent2")):
+        getattr(e, name)[:] = [float(x) for x in spec[key]]
+    e.width, e.height, e.radius = float(spec["width"]), float(spec["height"]), float(spec["radius"])
+    e.speed, e.start, e.end, e.density = float(spec["speed"]), float(spec["start"]), float(spec["end"]), float(spec["density"])
+    e.color[:] = [int(c) for c in spec["color"]]
+    return e
+
+
+def emitter_eval_host(program, dt, spacing, k, layer=-1, positions=False):
+    """The kernels' evaluator run on the CPU (sph_emitter_eval_host): the schedule after k steps as a dict and, with positions, the
+    float32 positions (layer_particles, 3) of `layer` at that count.  No device."""
+    out = SphEmitterEval()
+    lib = load()
+    rc = lib.sph_emitter_eval_host(C.byref(program), float(dt), float(spacing), int(k), -1, C.byref(out), None)
+    xyz = None
+    if not rc and (layer >= 0 or positions):
+        xyz = np.zeros((out.layer_particles, 3), np.float32) if positions else None
+        rc = lib.sph_emitter_eval_host(C.byref(program), float(dt), float(spacing), int(k), int(layer), C.byref(out), _ptr(xyz) if positions else None)
+    if rc:
+        raise SphError(f"sph_emitter_eval_host failed ({rc}): " + (lib.sph_last_error(None) or b"").decode(), rc)
+    d = struct_dict(out, skip=("reserved",))
+    return (d, xyz) if positions else d
 
 
 PBF_VARIANTS = {"reference": 0, "consistent": 1}
@@ -513,6 +570,9 @@ _SIGNATURES = [
     ("sph_set_rigid_motion", C.c_int, [_VP, C.c_int, C.POINTER(SphRigidMotion), _VP, _VP, _VP]),
     ("sph_get_rigid_motion_state", C.c_int, [_VP, C.c_int, C.POINTER(SphRigidMotionState)]),
     ("sph_rigid_motion_eval_host", C.c_int, [C.POINTER(SphRigidMotion), _VP, _VP, C.c_double, C.c_int64, C.POINTER(SphRigidMotionState)]),
+    ("sph_set_emitter", C.c_int, [_VP, C.c_int, C.POINTER(SphEmitter)]),
+    ("sph_get_emitter_state", C.c_int, [_VP, C.c_int, C.POINTER(SphEmitterState)]),
+    ("sph_emitter_eval_host", C.c_int, [C.POINTER(SphEmitter), C.c_double, C.c_double, C.c_int64, C.c_int, C.POINTER(SphEmitterEval), _VP]),
     ("sph_prepare", C.c_int, [_VP]),
     ("sph_step", C.c_int, [_VP, C.c_int]),
     ("sph_step_async", C.c_int, [_VP, C.c_int]),
@@ -905,6 +965,19 @@ class Engine(NativeObject):
         st = SphRigidMotionState()
         self._chk(self.lib.sph_get_rigid_motion_state(self.h, int(object_id), C.byref(st)), "sph_get_rigid_motion_state")
         return rigid_motion_state_dict(st)
+
+    # -- fluid emitters
+    def set_emitter(self, index, program):
+        self._chk(self.lib.sph_set_emitter(self.h, int(index), C.byref(program)), "sph_set_emitter")
+
+    def get_emitter_state(self, index):
+        """dict(object_id, layer_particles, max_layers, layers, emitted, held_layers, held_first, exhausted, held_id_base) of an emitter:
+        what the host knows, no device access."""
+        st = SphEmitterState()
+        self._chk(self.lib.sph_get_emitter_state(self.h, int(index), C.byref(st)), "sph_get_emitter_state")
+        d = struct_dict(st, skip=("reserved", "held_id_base"))
+        d["held_id_base"] = [int(x) for x in st.held_id_base[:st.held_layers]]
+        return d
 
     # -- device contact solver (the "device_contact" rigid backend)
     def set_rigid_contact_solver(self, on=True, restitution=0.2, friction=0.5, iterations=10, beta=0.2, slop=0.0, patch=0.0):

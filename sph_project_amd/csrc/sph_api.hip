@@ -28,6 +28,10 @@ struct ProfSlot {
 // elastic solids: one object as the host keeps it (sph_elastic_api.hpp).  state: the values of SphElasticObjectInfo::captured
 struct ElObjHost { int state = 0; double E = 0.0, nu = 0.0; int id0 = 0, n = 0, longest = 0, slot = -1; float min_ratio = 0.0f; float4 *rest = nullptr; };
 
+// fluid emitters: one emitter as the host keeps it (sph_emitter_api.hpp): the program, the lattice counts derived from it, the layers born
+// so far and the persistent id of each layer's first particle
+struct EmHost { bool on = false; SphEmitter e = {}; int nu = 0, nv = 0, layer_n = 0, max_layers = 0, layers = 0; std::vector<int> base; };
+
 struct SphHandle : ErrSink {
     SphParams prm = {};
     State st;
@@ -93,7 +97,14 @@ struct SphHandle : ErrSink {
     int obj_first[SPH_NOBJ] = {}, obj_n[SPH_NOBJ] = {};
     bool obj_split[SPH_NOBJ] = {};
     int el_rc = 0;
+    // fluid emitters (sph_set_emitter): em_n of the SPH_MAX_EMITTERS slots are set; em_touch: the slot of the running step holds or emits
+    // (known before the step's first launch: no pass of that step hashes for the coming sort)
+    EmHost em[SPH_MAX_EMITTERS];
+    int em_n = 0;
+    bool em_touch = false;
 };
+static long long em_reserved(const SphHandle *h);
+static int em_of_object(const SphHandle *h, int object_id);
 
 // layers of the whole scene along the slab axis / setting the local window [lo_ghost, top) of a rank
 static inline int slab_layers_glob(const Consts &c) { return c.slab_axis == 0 ? c.nx_glob : c.nz_glob; }
@@ -379,6 +390,11 @@ extern "C" int sph_append_particles(SphHandle *h, int object_id, int n, const fl
     if (object_id >= 0 && object_id < SPH_NOBJ && h->el[object_id].state == 2)
         return fail(h, SPH_ERR_UNSUPPORTED, "append: object %d is an elastic solid whose rest configuration has been captured", object_id);
     if (h->n + n > h->st.cap) return fail(h, SPH_ERR_CAPACITY, "append: %d + %d exceeds particle_max_num %d", h->n, n, h->st.cap);
+    if (h->em_n > 0) {
+        if (em_of_object(h, object_id) >= 0) return fail(h, SPH_ERR_UNSUPPORTED, "append: object %d belongs to emitter %d (an emitter's object takes no other particles)", object_id, em_of_object(h, object_id));
+        if ((long long)h->n + n + em_reserved(h) > (long long)h->st.cap)
+            return fail(h, SPH_ERR_CAPACITY, "append: %d + %d + the emitters' reserved %lld exceed particle_max_num %d", h->n, n, em_reserved(h), h->st.cap);
+    }
     HIPCHK(h, hipSetDevice(h->device));
     State &s = h->st;
     const float V0 = (float)h->prm.V0;
@@ -448,6 +464,7 @@ extern "C" int sph_set_appended_ids(SphHandle *h, int n, const int32_t *ids) {
     if (n == 0) return SPH_OK;
     if (h->st.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: the micropolar model is on (its angular velocities are stored by id, in append order)");
     if (h->st.el_marked) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: an elastic object exists (its rest lists are stored by id, in append order)");
+    if (h->em_n > 0) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: an emitter is set (its held layers are found by id, in append order)");
     h->st.ids_custom = 1;
     HIPCHK(h, hipSetDevice(h->device));
     colors_leave_home(h);
@@ -1152,6 +1169,7 @@ static void step_begin(SphHandle *h) {
 }
 
 #include "sph_comm_api.hpp"
+#include "sph_emitter_api.hpp"
 #include "sph_steps.hpp"
 
 static int read_scalars(SphHandle *h) {
@@ -1199,6 +1217,7 @@ static int finish_sync(SphHandle *h) {
 extern "C" int sph_prepare(SphHandle *h) {
     if (!h) return SPH_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->device));
+    if (h->em_n > 0 && !h->prepared) { const int rc = ph_emit(h, 0); if (rc) return rc; }   // born(0), as insert_object does for entryTime <= 0
     refresh_counts(h);
     State &s = h->st;
     if (s.slab_active && h->prm.method == SPH_METHOD_IISPH)
@@ -1278,6 +1297,7 @@ extern "C" int sph_rigid_integrate(SphHandle *h) {
 static int step_first_half(SphHandle *h) {
     if (h->in_step) return fail(h, SPH_ERR_INVALID, "sph_step_begin: the previous step was not ended");
     step_begin(h);
+    h->em_touch = em_slot_touches(h, (long long)h->steps + 1);
     int rc;
     switch (h->prm.method) {
         case SPH_METHOD_WCSPH: rc = wcsph_step(h); break;                     // WCSPH.py:28-36 (:45 boundary fused into the position update)
@@ -1307,6 +1327,9 @@ static int step_second_half(SphHandle *h) {
         ProfScope p(h, SPH_K_MISC);
         h->L->post_insert(s, h->n_mark, h->prm.method != SPH_METHOD_DFSPH);
     }
+    // fluid emitters: the insertion point of the step (the reference's insert_object()), behind the rigid integrator / motion launch of
+    // the same slot.  k_emit applies the boundary itself; what it adds takes part in the next sort (DFSPH: the one right below)
+    { const int rc = ph_emit(h, (long long)h->steps + 1); h->em_touch = false; if (rc) return rc; }
     // (late entry under sharding: every rank appended the part of the object that lies in its slab, possibly nothing; the
     //  host tells the library the object's whole size through sph_comm_add_global_count -- no collective per step)
     if (h->prm.method == SPH_METHOD_DFSPH) {
@@ -1417,6 +1440,11 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
         case SPH_PH_MICROPOLAR:
             if (!s.mp_on) return fail(h, SPH_ERR_INVALID, "SPH_PH_MICROPOLAR: the micropolar model is off (sph_set_micropolar)");
             ph_micropolar(h);
+            break;
+        case SPH_PH_EMIT:
+            if (h->em_n <= 0) return fail(h, SPH_ERR_INVALID, "SPH_PH_EMIT: no emitter is set (sph_set_emitter)");
+            if (!h->prepared) return fail(h, SPH_ERR_INVALID, "SPH_PH_EMIT before sph_prepare");
+            { const int rc = ph_emit(h, (long long)h->steps); if (rc) return rc; }
             break;
         case SPH_PH_ELASTIC:
             if (!s.el_marked) return fail(h, SPH_ERR_INVALID, "SPH_PH_ELASTIC: no elastic object (sph_set_elastic_object)");
@@ -1702,6 +1730,7 @@ extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes
         if (bytes != n * 4) return fail(h, SPH_ERR_INVALID, "upload: size mismatch");
         if (s.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while the micropolar model is on (its angular velocities are stored by id, in append order)");
         if (s.el_marked) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while an elastic object exists (its rest lists are stored by id, in append order)");
+        if (h->em_n > 0) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while an emitter is set (its held layers are found by id, in append order)");
         s.ids_custom = 1;
         colors_leave_home(h); HIPCHK(h, hipStreamSynchronize(s.stream));
         HIPCHK(h, hipMemcpy(s.pid.cur(), src, n * 4, hipMemcpyHostToDevice));

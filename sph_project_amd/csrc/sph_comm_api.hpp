@@ -195,6 +195,7 @@ extern "C" int sph_comm_set_slab(SphHandle *h, int z_lo, int z_hi) {
     if (s.st_akinci) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: the Akinci surface tension is on (the ghosts' normals would need an exchange)");
     if (s.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: the micropolar model is on (the ghosts' angular velocities would need an exchange)");
     if (s.el_marked) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: an elastic object exists (its rest lists name particles by id across every slab)");
+    if (h->em_n > 0) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: an emitter is set (its schedule knows one particle count)");
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->comm.slab_ready) {
         // Which library axis the slabs are cut along (Consts::slab_axis, sph_common.hpp).  Default: z, the scene's own z and the fastest

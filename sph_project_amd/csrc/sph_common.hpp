@@ -213,6 +213,15 @@ struct RigidMotionDev {
 };
 struct RigidMotionArgs { double dt; long long k; int nbodies; int ids[SPH_NOBJ]; };
 
+// Fluid emitters (sph_emitter.hpp): the record of one emitter on the device -- its program and the lattice counts derived from it when it
+// was set -- and the by-value tables of the two launches.  EmitArgs: the layers born in this slot, at most one per emitter (speed dt <=
+// spacing / 2); first[q] = slot (= persistent id) of the layer's first particle, start[q] = its offset among the launch's threads.
+// EmitHoldArgs: the held layers, at most SPH_EMITTER_MAX_HOLD per emitter, by the id of their first particle.
+struct EmitterDev { SphEmitter e; int nu, nv, layer_n, max_layers; };
+struct EmitArgs { double spacing; int nlayers, total; int emitter[SPH_MAX_EMITTERS], first[SPH_MAX_EMITTERS], start[SPH_MAX_EMITTERS + 1]; double offset[SPH_MAX_EMITTERS]; };
+#define SPH_EMIT_HOLD_ENTRIES (SPH_MAX_EMITTERS * SPH_EMITTER_MAX_HOLD)
+struct EmitHoldArgs { double spacing; int nlayers, id_lo, id_hi; int emitter[SPH_EMIT_HOLD_ENTRIES], id_base[SPH_EMIT_HOLD_ENTRIES]; double offset[SPH_EMIT_HOLD_ENTRIES]; };
+
 // Surface reconstruction (sph_surface.hpp): the constants and device buffers of one SphSurface.  Coarse cells (= bricks of
 // B^3 grid points) are counted from the absolute coarse coordinate cmin[] on a grid of cn[] cells that keeps one empty cell around the
 // particles; coarse linear index (x * cn[1] + y) * cn[2] + z.
@@ -609,6 +618,8 @@ struct State {
     // scripted rigid bodies (sph_set_rigid_motion; the record array is allocated with the first one)
     RigidMotionArgs rigid_motion_args = {};
     RigidMotionDev *rigid_motion = nullptr;   // [SPH_NOBJ]
+    // fluid emitters (sph_set_emitter; the record array is allocated with the first one)
+    EmitterDev *emitters = nullptr;           // [SPH_MAX_EMITTERS]
     // CG (implicit viscosity)
     float4 *cg_p = nullptr, *cg_Ap = nullptr, *cg_x = nullptr, *cg_b = nullptr, *cg_r = nullptr, *cg_v0 = nullptr;
     float4 *cg_p2 = nullptr;   // second search-direction buffer (fused p update: the A p pass reads the old one and writes the new one)
@@ -806,6 +817,10 @@ struct Launch {
     void (*rigid_contact_solve)(State &);
     // scripted rigid bodies: one wave per body, before rigid_integrate / rigid_contact_solve (sph_rigid_motion.hpp)
     void (*rigid_motion)(State &);
+    // fluid emitters (sph_emitter.hpp): the held layers onto their closed form (an elementwise pass over the n live particles), and the
+    // newborn layers into the slots behind them (the caller raises the counts afterwards)
+    void (*emit_hold)(State &, const EmitHoldArgs &);
+    void (*emit)(State &, const EmitArgs &);
     // z-slab sharding
     void (*halo_classify_pack)(State &, int n);
     void (*halo_unpack_append)(State &, int side, int count, int offset);

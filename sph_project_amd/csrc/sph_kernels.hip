@@ -522,6 +522,7 @@ void l_clear_fresh(State &s) {
 #include "sph_rigid.hpp"
 #include "sph_contact_solve.hpp"
 #include "sph_rigid_motion.hpp"
+#include "sph_emitter.hpp"
 #include "sph_surface.hpp"
 #include "sph_surface_aniso.hpp"
 #include "sph_elastic.hpp"
@@ -568,6 +569,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_rigid_launchers(L);
         register_contact_solve_launchers(L);
         register_rigid_motion_launchers(L);
+        register_emitter_launchers(L);
         register_surface_launchers(L);
         register_surface_aniso_launchers(L);
         register_surface_post_launchers(L);

@@ -265,12 +265,13 @@ static int wcsph_step(SphHandle *h) {
         const SlabComm &cm = h->comm;
         const bool rebalance_next = cm.rebalance_every > 0 && (h->steps + 1) % cm.rebalance_every == 0 && !h->any_rigid_object;
         if (s.slab_active && s.push.on && h->steps_to_follow > 0 && !rebalance_next && !s.has_emitter && !h->any_rigid_object &&
-            !h->sort_dirty)
+            !h->sort_dirty && !h->em_touch)
             h->L->halo_presend_begin(s);
         // Unsharded, all fluid, another step of this call queued right behind (nothing can touch the particles in between): the force pass
         // hashes the positions it stores for the next step's sort (NextHash) -- one launch less per step.
+        // Not in a step whose slot holds or emits (fluid emitters: the slot moves / adds particles behind this pass; the host knows now).
         const bool hash_next = !s.slab_active && s.c.all_fluid && h->steps_to_follow > 0 && !s.has_emitter && !h->any_rigid_object &&
-                               !h->sort_dirty;
+                               !h->sort_dirty && !h->em_touch;
         ProfScope p(h, SPH_K_WCSPH_FORCES); h->L->wcsph_forces(s, {books, hash_next});   // :30-31 + :34-36, :45 in one neighbour walk
         return SPH_OK;
     }
@@ -342,7 +343,7 @@ static int dfsph_step_begin(SphHandle *h) {
     rc = dfsph_density(h); if (rc) return rc;                                 // :301
     // the sort of this step's second half follows at once when the whole step is one call (step_once): the position update hashes for it
     const bool hash_next = h->whole_step && !s.slab_active && s.c.all_fluid && !s.has_emitter && !h->any_rigid_object &&
-                           !h->sort_dirty && !h->pose_dirty;
+                           !h->sort_dirty && !h->pose_dirty && !h->em_touch;
     { ProfScope p(h, SPH_K_MISC); h->L->advect_boundary(s, hash_next); }      // :303, :311-314 (boundary fused: it only looks at the particle itself)
     return SPH_OK;
 }

@@ -317,6 +317,43 @@ def jelly_scene(edge=8, young=2.0e4, poisson=0.3, drop=2, pool=0, method="dfsph"
     return cfg
 
 
+def faucet_scene(nozzle=(6, 6), speed=1.0, hold=2, basin=0, method="wcsph", radius=0.01, dt=4e-4, side=24, height=30, max_layers=40,
+                 shape="rectangle", viscosity=0.01, gravity=9.81, **keys):
+    """The first scene of the fluid emitters: a nozzle of nozzle[0] x nozzle[1] lattice points (shape "circle": a circle of
+    diameter nozzle[0] points) under the lid of a closed sampled box of side x height x side particle diameters, pointing down, over
+    a pool `basin` layers deep (0: a dry floor).  The emitter is object 0 (budget: max_layers layers), the pool object 1.  keys:
+    further Configuration keys."""
+    d = 2.0 * radius
+    floor = 4 * d                      # first lattice plane above the box's shell
+    w, h = side * d, height * d
+    emitter = {"objectId": 0, "shape": shape, "position": [0.5 * w, h - 6 * d, 0.5 * w], "direction": [0.0, -1.0, 0.0],
+               "speed": float(speed), "start": 0.0, "end": None, "hold": int(hold), "density": 1000.0, "color": [50, 100, 200]}
+    if shape == "circle":
+        emitter["radius"] = 0.5 * (nozzle[0] + 0.2) * d
+        layer = int(scene.emitter_lattice("circle", 0.0, 0.0, emitter["radius"], d).shape[0])
+    else:
+        emitter.update(width=(nozzle[0] + 0.5) * d, height=(nozzle[1] + 0.5) * d, up=[0.0, 0.0, 1.0])
+        layer = int(nozzle[0]) * int(nozzle[1])
+    emitter["maxParticles"] = int(max_layers) * layer
+    cfg = {
+        "Configuration": {
+            "domainStart": [0.0, 0.0, 0.0], "domainEnd": [w, h, w], "addDomainBox": True, "particleRadius": radius,
+            "density0": 1000, "simulationMethod": method, "viscosityMethod": "standard", "gravitation": [0.0, -float(gravity), 0.0],
+            "timeStepSize": dt, "viscosity": viscosity,
+        },
+        "FluidBlocks": [],
+        "Emitters": [emitter],
+    }
+    if basin:
+        cfg["FluidBlocks"].append({
+            "objectId": 1, "start": [floor, floor, floor], "end": [w - floor - 0.5 * d, floor + (basin - 0.5) * d, w - floor - 0.5 * d],
+            "translation": [0.0, 0.0, 0.0], "scale": [1, 1, 1], "velocity": [0.0, 0.0, 0.0], "density": 1000.0,
+            "color": [50, 100, 200], "entryTime": -1.0,
+        })
+    cfg["Configuration"].update(keys)
+    return cfg
+
+
 def scene_particles(cfg_dict):
     """Host lattice of every object present at prepare(), in the reference's insertion order
     (domain box first: base_container.py:192, then FluidBlocks: :215).  Blocks with entryTime > 0 are listed with

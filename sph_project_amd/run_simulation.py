@@ -284,6 +284,9 @@ def check_sharded_args(parser, args):
     if elastic:
         parser.error(f"--gpus {n}: object {elastic[0]} carries the key \"elasticity\": elastic solids are not sharded (a rest list names "
                      "particles by id across every slab; sph_set_elastic_object refuses a slab); run it with --gpus 1")
+    if config.get_emitters():
+        parser.error(f"--gpus {n}: the scene has Emitters: fluid emitters are not sharded (their schedule knows one particle count; "
+                     "sph_set_emitter refuses a slab); run it with --gpus 1")
     from sph_project_amd import launch
     try:
         launch.plan_scene_cuts(config.config, n)
