@@ -165,6 +165,10 @@ typedef enum {
     SPH_F_ELASTIC_DEFGRAD = 47,    /* f32[n][9] */
     SPH_F_ELASTIC_STRESS = 48,     /* f32[n][6] */
     SPH_F_ELASTIC_ROTATION = 49,   /* f32[n][4] */
+    /* Air drag (allocated when sph_set_drag first switches the mode on; SPH_ERR_UNSUPPORTED before).  Download only, in the CURRENT
+       order: what the last SPH_PH_DRAG (or step) stored, written on active fluid rows only; valid until the next sort. */
+    SPH_F_DRAG_ACCEL = 50,         /* f32[n][3]: a_drag */
+    SPH_F_DRAG_TERMS = 51,         /* f32[n][5]: n_i, w, C_D, A_un, y */
     SPH_F_COUNT_
 } SphField;
 
@@ -229,6 +233,10 @@ typedef enum {
        what sph_prepare's emission did for count 0 -- i.e. the held layers are put on their closed form at T_steps and the layers
        born(steps) not emitted yet are emitted.  Idempotent: a second run emits nothing. */
     SPH_PH_EMIT = 31,
+    /* Air drag (sph_set_drag; SPH_ERR_INVALID while the mode is off): the walk alone, on the masks of the last sort: it stores a_drag
+       (SPH_F_DRAG_ACCEL) and its terms (SPH_F_DRAG_TERMS) and nothing else.  In this mode SPH_PH_NON_PRESSURE (and SPH_PH_CG_END) add
+       the STORED a_drag behind their pass, v += dt a_drag, without walking again; a step walks in front of its non-pressure pass. */
+    SPH_PH_DRAG = 32,
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -278,6 +286,7 @@ typedef enum {
     SPH_K_MICROPOLAR = 32,      /* micropolar vorticity model: the gather of the angular velocities + the walk (v += dt a_mp: SPH_K_MISC); "?" as well */
     SPH_K_ELASTIC = 33,         /* elastic solids: the scatter + pass A + pass B (v += dt a_el: SPH_K_MISC; the capture: SPH_K_MISC); "?" as well */
     SPH_K_EMIT = 34,            /* fluid emitters: the hold launch and the emit launch (sph_set_emitter); "?" as well */
+    SPH_K_DRAG = 35,            /* air drag: the walk (v += dt a_drag: SPH_K_MISC); "?" as well */
     SPH_K_COUNT_
 } SphKernelId;
 
@@ -441,6 +450,51 @@ int sph_get_elastic_rest(SphHandle *h, int object_id, int32_t *nbr, float *g0_ij
 int sph_elastic_particle_host(int nnb, const float *xi, const float *xj, const float *g0_ij, const float *g0_ji, const float *q_prev,
                               const float *q_j, const float *sigma_j, double V0, double mass, double mu, double lambda, float *F_out,
                               float *q_out, float *sigma_out, float *a_out, int fast);
+
+/* Air drag and wind (opt-in).  method 0 = none (the default), 1 = gissler: Gissler, Band, Peer, Ihmsen, Teschner 2017,
+   "Approximate air-fluid interactions for SPH".  The air is not simulated: a constant wind u (air_velocity) of density rho_air acts
+   on every active fluid particle; nothing receives a reaction, momentum is not conserved, by design.
+   Constants (water in air): sigma = 0.0724, mu_l = 0.00102, mu_a = 1.845e-5, C_F = 1/3, C_k = 8, C_d = 5, C_b = 0.5, n_full = 38.
+   Per handle, once on the host in double, d = 2 r the particle diameter, rho_l = density_0:
+     L       = cbrt(3 / (4 pi)) d
+     1/t_d   = C_d mu_l / (2 rho_l L^2)
+     omega^2 = C_k sigma / (rho_l L^3) - 1/t_d^2          (refused if <= 0)
+     t_max   = -2 (atan(sqrt(t_d^2 omega^2)) - pi) / omega
+     c_def   = 1 - exp(-t_max / t_d) (cos(omega t_max) + sin(omega t_max) / (omega t_d))
+     y_coeff = C_F (rho_air L / sigma) c_def / (C_k C_b)
+     n23     = 2 n_full / 3
+   Per active fluid particle i with velocity v_i at the start of the non-pressure phase and mass m_i; j ranges over its fluid
+   neighbours (material fluid, any object, r_ij < h, self excluded: the pairs every other walk accepts); rigid and boundary particles
+   neither count nor shield:
+     v_rel = u - v_i ;  s2 = |v_rel|^2 ;  if s2 < 1e-6: a_drag_i = 0, all terms 0, done
+     s = sqrt(s2) ;  e = v_rel / s
+     y     = min(s2 y_coeff, 1)
+     Re    = 2 max(rho_air s L / mu_a, 0.1)
+     C_sph = Re <= 1000 ? 24 / Re (1 + Re^(2/3) / 6) : 0.424
+     C_liu = C_sph (1 + 2.632 y)
+     n_i   = number of j ;  f = min(n23, n_i) / n23
+     C_D   = (1 - f) C_liu + f                                  (n_i = 0: C_liu)
+     A_drop = pi (L + C_b L y)^2 ;  A_un = (1 - f) A_drop + f d^2
+     q     = max over j of  e . (x_i - x_j) / |x_i - x_j|       (0 when n_i = 0; never below 0)
+     w     = clamp(1 - q, 0, 1)                                 (a w below 2^-20, the roundoff q carries, is stored as 0)
+     a_drag_i = k (1 / (2 m_i)) rho_air s v_rel C_D w A_un
+     v_i <- v_i + dt (a_np_i + ... + a_drag_i)
+   a_drag also enters the non-pressure acceleration, which every method keeps in this mode (SPH_F_NON_PRESSURE_ACCEL).  WCSPH takes its
+   unfused route (SPH_K_WCSPH_FORCES does not run).  Legal at any time between steps; switching back to 0 restores the plain path bit
+   for bit and keeps the values.  SPH_ERR_UNSUPPORTED: a PBF handle (either variant), a sharded handle (and sph_comm_set_slab while
+   the mode is on).  This library has no 2-D handles; the Python front end refuses 2-D scenes.  SPH_ERR_INVALID: an unknown method,
+   k or rho_air negative or not finite, a wind component that is not finite, omega^2 <= 0 for the handle's radius and density.
+   sph_drag_particle_host: everything behind the walk (drag_finish of csrc/sph_drag.hpp) from the kernels' own source on the CPU,
+   strict (fast = 0) or fast form.  in: n records of 6 floats (v_i[3], m_i, n_i, q); out: n records of 7 floats (a_drag[3], w, C_D,
+   A_un, y).  sph_drag_constants_host: the per-handle constants above, out[8] = L, 1/t_d, omega^2, t_max, c_def, y_coeff, n23,
+   rho_air L / mu_a; SPH_ERR_INVALID (and only the first three filled) where omega^2 <= 0.  Neither touches a device. */
+#define SPH_DRAG_NONE 0
+#define SPH_DRAG_GISSLER 1
+typedef struct { int32_t method; double k, rho_air, air_velocity[3]; } SphDragParams;
+int sph_set_drag(SphHandle *h, const SphDragParams *params);
+int sph_get_drag(SphHandle *h, SphDragParams *out);
+int sph_drag_particle_host(const SphDragParams *params, double radius, double rho0, int64_t n, const float *in, float *out, int fast);
+int sph_drag_constants_host(const SphDragParams *params, double radius, double rho0, double *out);
 
 /* Device rigid integrator (opt-in; the host's "device" rigid backend).  The physics of the host's native backend
    (SPH/rigid_solver/host_rigid_solver.py integrate: semi-implicit Euler in float64 under gravity and the fluid wrench, gyroscopic

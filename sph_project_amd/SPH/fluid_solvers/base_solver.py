@@ -61,6 +61,11 @@ class BaseSolver:
         self.vorticity = getattr(container, "vorticity", 0.01)
         self.viscosity_omega = getattr(container, "viscosity_omega", 0.1)
         self.inertia_inverse = getattr(container, "inertia_inverse", 0.5)
+        # air drag and wind: "none", or "gissler" with k (scene key drag), the wind u (airVelocity) and rho_a (airDensity)
+        self.drag_method = getattr(container, "drag_method", "none")
+        self.drag = getattr(container, "drag", 1.0)
+        self.air_velocity = tuple(getattr(container, "air_velocity", (0.0, 0.0, 0.0)))
+        self.air_density = getattr(container, "air_density", 1.2041)
         # elastic solids: {object id: (E, nu)} of the scene's elastic objects
         self.elastic_objects = dict(getattr(container, "elastic_objects", {}))
         self.elastic_dt_limit = getattr(container, "elastic_dt_limit", None)   # 0.4 spacing / c of the stiffest object (advice), or None

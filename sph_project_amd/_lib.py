@@ -33,6 +33,8 @@ F_ANGULAR_VELOCITY, F_MICROPOLAR_ACCEL = 44, 45
 # elastic solids, current order, zero outside captured elastic objects: a_el, F (row-major) and the stress (xx, xy, xz, yy, yz, zz) of the
 # last pass (download only) and the rotation quaternions (x, y, z, w; up- and download)
 F_ELASTIC_ACCEL, F_ELASTIC_DEFGRAD, F_ELASTIC_STRESS, F_ELASTIC_ROTATION = 46, 47, 48, 49
+# air drag, download only, written on active fluid rows by the last walk: a_drag and (n_i, w, C_D, A_un, y)
+F_DRAG_ACCEL, F_DRAG_TERMS = 50, 51
 
 _FIELD_SPEC = {  # field -> (dtype, components)
     F_POSITION: (np.float32, 3), F_VELOCITY: (np.float32, 3), F_ACCELERATION: (np.float32, 3),
@@ -51,7 +53,7 @@ _FIELD_SPEC = {  # field -> (dtype, components)
     F_CG_DINV: (np.float32, 9), F_CG_AP_PARTS: (np.float32, 9), F_SURFACE_NORMAL: (np.float32, 3),
     F_ANGULAR_VELOCITY: (np.float32, 3), F_MICROPOLAR_ACCEL: (np.float32, 3),
     F_ELASTIC_ACCEL: (np.float32, 3), F_ELASTIC_DEFGRAD: (np.float32, 9), F_ELASTIC_STRESS: (np.float32, 6),
-    F_ELASTIC_ROTATION: (np.float32, 4),
+    F_ELASTIC_ROTATION: (np.float32, 4), F_DRAG_ACCEL: (np.float32, 3), F_DRAG_TERMS: (np.float32, 5),
 }
 
 # enum SphPhase
@@ -74,6 +76,7 @@ PH_MICROPOLAR = 29
 # elastic solids: the scatter and the passes A and B alone (PH_NON_PRESSURE / PH_CG_END then add the stored a_el)
 PH_ELASTIC = 30
 PH_EMIT = 31   # fluid emitters: the hold and the emission of the current step count alone
+PH_DRAG = 32   # air drag: the walk alone (PH_NON_PRESSURE / PH_CG_END then add the stored a_drag)
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
@@ -91,6 +94,7 @@ K_SURFACE_NORMALS = 31       # SPH_K_SURFACE_NORMALS: the normal pass of the Aki
 K_MICROPOLAR = 32            # SPH_K_MICROPOLAR: the gather + walk of the micropolar vorticity model
 K_ELASTIC = 33               # SPH_K_ELASTIC: scatter + pass A + pass B of the elastic solids
 K_EMIT = 34                  # SPH_K_EMIT: the hold launch and the emit launch of the fluid emitters
+K_DRAG = 35                  # SPH_K_DRAG: the walk of the air drag
 RIGID_MOTION_MAX_KEYS = 64
 MAX_EMITTERS = 8             # SPH_MAX_EMITTERS
 EMITTER_MAX_HOLD = 8         # SPH_EMITTER_MAX_HOLD
@@ -294,6 +298,41 @@ def elastic_particle_host(xi, xj, g0_ij, g0_ji, q_prev, q_j, sigma_j, V0, mass, 
     if rc:
         raise SphError(f"sph_elastic_particle_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
     return F.reshape(3, 3), q, sig, a
+
+
+DRAG_METHODS = {"none": 0, "gissler": 1}
+
+
+class SphDragParams(C.Structure):
+    _fields_ = [("method", C.c_int32), ("k", C.c_double), ("rho_air", C.c_double), ("air_velocity", C.c_double * 3)]
+
+
+def _drag_params(method, k, rho_air, air_velocity):
+    u = np.asarray(air_velocity, np.float64).reshape(3)
+    return SphDragParams(int(DRAG_METHODS.get(method, method)), float(k), float(rho_air), (C.c_double * 3)(*u))
+
+
+def drag_particle_host(records, radius, rho0, k=1.0, rho_air=1.2041, air_velocity=(0.0, 0.0, 0.0), fast=False):
+    """Everything behind the air drag's walk (drag_finish of csrc/sph_drag.hpp) from the kernels' own source run on the CPU
+    (sph_drag_particle_host): records (n, 6) float32 = (v_i[3], m_i, n_i, q) -> (n, 7) float32 = (a_drag[3], w, C_D, A_un, y).  No device."""
+    rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 6)
+    out = np.empty((rec.shape[0], 7), np.float32)
+    p = _drag_params("gissler", k, rho_air, air_velocity)
+    rc = load().sph_drag_particle_host(C.byref(p), float(radius), float(rho0), rec.shape[0], _ptr(rec), _ptr(out), int(bool(fast)))
+    if rc:
+        raise SphError(f"sph_drag_particle_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
+    return out
+
+
+def drag_constants_host(radius, rho0, rho_air=1.2041):
+    """The air drag's per-handle constants as the library derives them (sph_drag_constants_host): dict(L, inv_td, omega2, t_max, c_def,
+    y_coeff, n23, re_coeff).  SphError (ERR_INVALID) where omega^2 <= 0.  No device."""
+    out = np.zeros(8, np.float64)
+    p = _drag_params("gissler", 1.0, rho_air, (0.0, 0.0, 0.0))
+    rc = load().sph_drag_constants_host(C.byref(p), float(radius), float(rho0), _ptr(out))
+    if rc:
+        raise SphError(f"sph_drag_constants_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
+    return dict(zip(("L", "inv_td", "omega2", "t_max", "c_def", "y_coeff", "n23", "re_coeff"), (float(v) for v in out)))
 
 
 class SphPbfStats(C.Structure):
@@ -554,6 +593,10 @@ _SIGNATURES = [
     ("sph_set_micropolar", C.c_int, [_VP, C.POINTER(SphMicropolarParams)]),
     ("sph_get_micropolar", C.c_int, [_VP, C.POINTER(SphMicropolarParams)]),
     ("sph_micropolar_pair_host", C.c_int, [_VP, C.c_int64, _VP, C.c_int]),
+    ("sph_set_drag", C.c_int, [_VP, C.POINTER(SphDragParams)]),
+    ("sph_get_drag", C.c_int, [_VP, C.POINTER(SphDragParams)]),
+    ("sph_drag_particle_host", C.c_int, [C.POINTER(SphDragParams), C.c_double, C.c_double, C.c_int64, _VP, _VP, C.c_int]),
+    ("sph_drag_constants_host", C.c_int, [C.POINTER(SphDragParams), C.c_double, C.c_double, _VP]),
     ("sph_set_elastic_object", C.c_int, [_VP, C.c_int, C.POINTER(SphElasticParams)]),
     ("sph_get_elastic_object", C.c_int, [_VP, C.c_int, C.POINTER(SphElasticObjectInfo)]),
     ("sph_get_elastic_rest", C.c_int, [_VP, C.c_int, _VP, _VP, _VP]),
@@ -905,6 +948,18 @@ class Engine(NativeObject):
         p = SphMicropolarParams()
         self._chk(self.lib.sph_get_micropolar(self.h, C.byref(p)), "sph_get_micropolar")
         return {"method": {v: k for k, v in VORTICITY_METHODS.items()}[p.method], "nu_t": p.nu_t, "zeta": p.zeta, "theta_inv": p.theta_inv}
+
+    # -- air drag and wind
+    def set_drag(self, method="gissler", k=1.0, rho_air=1.2041, air_velocity=(0.0, 0.0, 0.0)):
+        """method: "none" / "gissler" (or 0 / 1); k: scales the force, rho_air: the air's density, air_velocity: a constant wind, m / s."""
+        p = _drag_params(method, k, rho_air, air_velocity)
+        self._chk(self.lib.sph_set_drag(self.h, C.byref(p)), "sph_set_drag")
+
+    def get_drag(self):
+        p = SphDragParams()
+        self._chk(self.lib.sph_get_drag(self.h, C.byref(p)), "sph_get_drag")
+        return {"method": {v: k for k, v in DRAG_METHODS.items()}[p.method], "k": p.k, "rho_air": p.rho_air,
+                "air_velocity": tuple(float(v) for v in p.air_velocity)}
 
     # -- elastic solids
     def set_elastic_object(self, object_id, youngs_modulus, poisson_ratio=0.3):

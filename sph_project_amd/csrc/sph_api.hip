@@ -709,6 +709,88 @@ extern "C" int sph_micropolar_pair_host(const float *in, int64_t n, float *out, 
     return SPH_OK;
 }
 
+// ---------------------------------------------------------------------------------- air drag and wind
+#include "sph_drag.hpp"
+// what sph_set_drag and the two host entries refuse in the values themselves
+static int drag_check_values(SphHandle *h, const char *who, const SphDragParams *p) {
+    if (p->method != SPH_DRAG_NONE && p->method != SPH_DRAG_GISSLER)
+        return fail(h, SPH_ERR_INVALID, "%s: method %d is neither 0 (none) nor 1 (gissler)", who, p->method);
+    if (!(p->k >= 0.0) || !std::isfinite(p->k)) return fail(h, SPH_ERR_INVALID, "%s: k %g is not a finite number >= 0", who, p->k);
+    if (!(p->rho_air >= 0.0) || !std::isfinite(p->rho_air)) return fail(h, SPH_ERR_INVALID, "%s: rho_air %g is not a finite number >= 0", who, p->rho_air);
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(p->air_velocity[a])) return fail(h, SPH_ERR_INVALID, "%s: air_velocity[%d] %g is not finite", who, a, p->air_velocity[a]);
+    return SPH_OK;
+}
+
+extern "C" int sph_set_drag(SphHandle *h, const SphDragParams *p) {
+    if (!h) return SPH_ERR_INVALID;
+    if (!p) return fail(h, SPH_ERR_INVALID, "sph_set_drag: null argument");
+    if (h->prm.method == SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_drag: not on a PBF handle (either variant)");
+    if (h->st.slab_active || h->comm.slab_ready)
+        return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_drag: not on a sharded handle (not done, although the walk would need the ghosts' positions only)");
+    { int rc = drag_check_values(h, "sph_set_drag", p); if (rc) return rc; }
+    State &s = h->st;
+    if (p->method == SPH_DRAG_GISSLER) {
+        DragHost hk;
+        if (!drag_host_constants(h->prm.particle_radius, h->prm.density_0, p->rho_air, hk))
+            return fail(h, SPH_ERR_INVALID, "sph_set_drag: omega^2 = %g <= 0 for radius %g and density %g (the droplet's oscillation is overdamped: "
+                                            "the deformation model does not apply)", hk.omega2, h->prm.particle_radius, h->prm.density_0);
+        HIPCHK(h, hipSetDevice(h->device));
+        if (!s.dr_acc) { int rc = dalloc(h, &s.dr_acc, (size_t)s.cap); if (rc) return rc; }
+        if (!s.dr_terms) { int rc = dalloc(h, &s.dr_terms, (size_t)s.cap); if (rc) return rc; }
+        if (!s.st_acc && !s.np_acc_out) { int rc = dalloc(h, &s.st_acc, (size_t)s.cap); if (rc) return rc; }
+    }
+    s.dr_on = p->method == SPH_DRAG_GISSLER ? 1 : 0;
+    s.dr_k = p->k; s.dr_rho_a = p->rho_air;
+    s.dr_radius = h->prm.particle_radius; s.dr_rho_l = h->prm.density_0;
+    for (int a = 0; a < 3; ++a) s.dr_u[a] = p->air_velocity[a];
+    for (int a = 0; a < 3; ++a) s.dr_u_lib[a] = p->air_velocity[h->perm[a]];   // scene frame -> library frame
+    return SPH_OK;
+}
+
+extern "C" int sph_get_drag(SphHandle *h, SphDragParams *out) {
+    if (!h || !out) return SPH_ERR_INVALID;
+    out->method = h->st.dr_on ? SPH_DRAG_GISSLER : SPH_DRAG_NONE;
+    out->k = h->st.dr_k; out->rho_air = h->st.dr_rho_a;
+    for (int a = 0; a < 3; ++a) out->air_velocity[a] = h->st.dr_u[a];
+    return SPH_OK;
+}
+
+extern "C" int sph_drag_constants_host(const SphDragParams *p, double radius, double rho0, double *out) {
+    if (!p || !out) return fail(nullptr, SPH_ERR_INVALID, "sph_drag_constants_host: null argument");
+    { int rc = drag_check_values(nullptr, "sph_drag_constants_host", p); if (rc) return rc; }
+    if (!(radius > 0.0) || !std::isfinite(radius) || !(rho0 > 0.0) || !std::isfinite(rho0))
+        return fail(nullptr, SPH_ERR_INVALID, "sph_drag_constants_host: radius %g and density %g must be finite numbers > 0", radius, rho0);
+    DragHost hk;
+    const bool ok = drag_host_constants(radius, rho0, p->rho_air, hk);
+    out[0] = hk.L; out[1] = hk.inv_td; out[2] = hk.omega2; out[3] = hk.t_max; out[4] = hk.c_def; out[5] = hk.y_coeff; out[6] = hk.n23;
+    out[7] = hk.re_coeff;
+    if (!ok) return fail(nullptr, SPH_ERR_INVALID, "sph_drag_constants_host: omega^2 = %g <= 0 for radius %g and density %g", hk.omega2, radius, rho0);
+    return SPH_OK;
+}
+
+extern "C" int sph_drag_particle_host(const SphDragParams *p, double radius, double rho0, int64_t n, const float *in, float *out, int fast) {
+    if (!p) return fail(nullptr, SPH_ERR_INVALID, "sph_drag_particle_host: null argument");
+    if (n < 0) return fail(nullptr, SPH_ERR_INVALID, "sph_drag_particle_host: negative count");
+    if (n > 0 && (!in || !out)) return fail(nullptr, SPH_ERR_INVALID, "sph_drag_particle_host: null argument");
+    { int rc = drag_check_values(nullptr, "sph_drag_particle_host", p); if (rc) return rc; }
+    if (!(radius > 0.0) || !std::isfinite(radius) || !(rho0 > 0.0) || !std::isfinite(rho0))
+        return fail(nullptr, SPH_ERR_INVALID, "sph_drag_particle_host: radius %g and density %g must be finite numbers > 0", radius, rho0);
+    DragHost hk;
+    if (!drag_host_constants(radius, rho0, p->rho_air, hk))
+        return fail(nullptr, SPH_ERR_INVALID, "sph_drag_particle_host: omega^2 = %g <= 0 for radius %g and density %g", hk.omega2, radius, rho0);
+    const DragConsts k = drag_consts(hk, radius, p->rho_air, p->k, p->air_velocity);
+    for (int64_t r = 0; r < n; ++r) {
+        const float *q = in + 6 * r;
+        DragOut o;
+        if (fast) drag_finish<true>(k, q[0], q[1], q[2], q[3], q[4], q[5], o);
+        else drag_finish<false>(k, q[0], q[1], q[2], q[3], q[4], q[5], o);
+        float *d = out + 7 * r;
+        d[0] = o.ax; d[1] = o.ay; d[2] = o.az; d[3] = o.w; d[4] = o.cd; d[5] = o.a_un; d[6] = o.y;
+    }
+    return SPH_OK;
+}
+
 // ---------------------------------------------------------------------------------- device rigid integrator (sph_rigid.hpp)
 static int rigid_int_supported(SphHandle *h, const char *who) {
     if (h->prm.method == SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "%s: PBF moves no rigid body (PBF.py _step)", who);
@@ -1446,6 +1528,10 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
             if (!h->prepared) return fail(h, SPH_ERR_INVALID, "SPH_PH_EMIT before sph_prepare");
             { const int rc = ph_emit(h, (long long)h->steps); if (rc) return rc; }
             break;
+        case SPH_PH_DRAG:
+            if (!s.dr_on) return fail(h, SPH_ERR_INVALID, "SPH_PH_DRAG: the air drag is off (sph_set_drag)");
+            ph_drag(h);
+            break;
         case SPH_PH_ELASTIC:
             if (!s.el_marked) return fail(h, SPH_ERR_INVALID, "SPH_PH_ELASTIC: no elastic object (sph_set_elastic_object)");
             ph_elastic(h);
@@ -1457,7 +1543,7 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
             ProfScope p(h, SPH_K_RIGID_CONTACT); h->L->rigid_contact(s);
         } break;
         case SPH_PH_CG_PREPARE: case SPH_PH_CG_AP: case SPH_PH_CG_UPDATE_XR: case SPH_PH_CG_UPDATE_P: case SPH_PH_CG_END:
-            { int rc = cg_run_phase(h, phase); if (rc) return rc; if (phase == SPH_PH_CG_END) { ph_micropolar_apply(h); ph_elastic_apply(h); } } break;   // (micropolar model: + the STORED a_mp; elastic solids: + the STORED a_el)
+            { int rc = cg_run_phase(h, phase); if (rc) return rc; if (phase == SPH_PH_CG_END) { ph_micropolar_apply(h); ph_elastic_apply(h); ph_drag_apply(h); } } break;   // (micropolar model: + the STORED a_mp; elastic solids: + the STORED a_el; air drag: + the STORED a_drag)
         default: { int rc = method_run_phase(h, phase); if (rc) return rc; }
     }
     int rc = check_async(h); if (rc) return rc;
@@ -1523,6 +1609,7 @@ static const float4 *vec_field(SphHandle *h, int field) {
         case SPH_F_RIGID_CONTACT_DN: case SPH_F_RIGID_CONTACT_COUNT: return s.contact_part;   // (sum of depth * n, contacts)
         case SPH_F_NON_PRESSURE_ACCEL: return s.acc_np ? s.acc_np : s.st_acc;   // (PCISPH, or the last Akinci pass / micropolar-mode pass of any method; null otherwise)
         case SPH_F_MICROPOLAR_ACCEL: return s.mp_acc;   // (allocated with the micropolar model; null otherwise)
+        case SPH_F_DRAG_ACCEL: return s.dr_acc;         // (allocated with the air drag; null otherwise.  w = n_i: SPH_F_DRAG_TERMS)
         case SPH_F_SURFACE_NORMAL: return s.st_normal;   // (allocated with the Akinci surface tension; null otherwise)
         case SPH_F_CG_B: return s.cg_b;     // (implicit viscosity only; null otherwise)
         case SPH_F_CG_R: return s.cg_r;
@@ -1561,7 +1648,7 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
                          field == SPH_F_PRESSURE_ACCEL || field == SPH_F_PREDICTED_VEL || field == SPH_F_PREDICTED_POS ||
                          field == SPH_F_CG_X || field == SPH_F_ORIG_POSITION || field == SPH_F_IISPH_DII || field == SPH_F_IISPH_DIJ_PJ ||
                          field == SPH_F_PBF_OLD_POSITION || field == SPH_F_RIGID_CONTACT_DN || field == SPH_F_NON_PRESSURE_ACCEL ||
-                         field == SPH_F_SURFACE_NORMAL || field == SPH_F_MICROPOLAR_ACCEL || (field >= SPH_F_CG_B && field <= SPH_F_CG_V0);
+                         field == SPH_F_SURFACE_NORMAL || field == SPH_F_MICROPOLAR_ACCEL || field == SPH_F_DRAG_ACCEL || (field >= SPH_F_CG_B && field <= SPH_F_CG_V0);
     if (is_vec3) {
         const float4 *src = vec_field(h, field);
         if (!src) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated for this method", field);
@@ -1574,6 +1661,18 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
         return SPH_OK;
     }
     if (field >= SPH_F_ELASTIC_ACCEL && field <= SPH_F_ELASTIC_ROTATION) return el_download(h, field, (float *)dst, bytes);
+    if (field == SPH_F_DRAG_TERMS) {   // (n_i, w, C_D, A_un, y): scalars, no frame
+        if (!s.dr_terms) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated (sph_set_drag)", field);
+        if (bytes != n * 20) return fail(h, SPH_ERR_INVALID, "download: field %d needs %zu bytes, got %zu", field, n * 20, bytes);
+        std::vector<float4> a(n), t(n);
+        if (n) {
+            HIPCHK(h, hipMemcpy(a.data(), s.dr_acc, n * sizeof(float4), hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(t.data(), s.dr_terms, n * sizeof(float4), hipMemcpyDeviceToHost));
+        }
+        float *d = (float *)dst;
+        for (size_t i = 0; i < n; ++i) { d[5 * i] = a[i].w; d[5 * i + 1] = t[i].x; d[5 * i + 2] = t[i].y; d[5 * i + 3] = t[i].z; d[5 * i + 4] = t[i].w; }
+        return SPH_OK;
+    }
     if (field == SPH_F_ANGULAR_VELOCITY) {   // at home by particle id -> the current order; library frame -> scene frame, axial
         if (!s.mp_w_home) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated (sph_set_micropolar)", field);
         if (bytes != n * 12) return fail(h, SPH_ERR_INVALID, "download: field %d needs %zu bytes, got %zu", field, n * 12, bytes);

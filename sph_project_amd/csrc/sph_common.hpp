@@ -729,6 +729,14 @@ struct State {
     float4 *el_x_home = nullptr, *el_q[2] = {nullptr, nullptr}, *el_sig = nullptr, *el_F = nullptr, *el_acc = nullptr;
     int *el_slot_home = nullptr;
     unsigned *el_cnt = nullptr;
+    // Air drag (sph_set_drag; sph_drag.hpp): off unless dr_on; the two buffers are allocated when the mode is first switched on.
+    // dr_acc = (a_drag, n_i), dr_terms = (w, C_D, A_un, y) of the last walk, in sorted order (valid until the next sort).  dr_u: the
+    // wind in the scene's frame (what sph_get_drag returns), dr_u_lib: in the library's; dr_radius, dr_rho_l: the handle's particle
+    // radius and rest density, from which the launcher derives the model's constants.  With the mode on and no non-pressure
+    // acceleration kept otherwise, st_acc takes it.
+    int dr_on = 0;
+    double dr_k = 1.0, dr_rho_a = 1.2041, dr_u[3] = {0.0, 0.0, 0.0}, dr_u_lib[3] = {0.0, 0.0, 0.0}, dr_radius = 0.0, dr_rho_l = 0.0;
+    float4 *dr_acc = nullptr, *dr_terms = nullptr;
 };
 
 // What a list sort's gather left behind for the density pass launched next (Launch::scatter_stable, density_next): thread d of a tile does
@@ -775,6 +783,8 @@ struct Launch {
     void (*micropolar_apply)(State &);   // ... and v += dt a_mp (+ the kept non-pressure acceleration) behind it
     void (*elastic)(State &);            // elastic solids: scatter, pass A, pass B over the captured objects (State::el_acc), before non_pressure
     void (*elastic_apply)(State &);      // ... and v += dt a_el (+ the kept non-pressure acceleration) behind it
+    void (*drag)(State &);               // air drag: the walk (State::dr_acc, dr_terms), before non_pressure
+    void (*drag_apply)(State &);         // ... and v += dt a_drag (+ the kept non-pressure acceleration) behind it, behind the elastic solids'
     void (*elastic_capture)(State &, const ElCaptureArgs &);   // one object's rest configuration, on the cell lists of the sort that has just run
     void (*non_pressure)(State &, const float4 *visc_vel);   // visc_vel: velocities for the viscous term (implicit viscosity: cg_x), null: the particles' own
     void (*pressure_integrate)(State &);

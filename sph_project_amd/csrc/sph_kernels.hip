@@ -22,6 +22,7 @@ namespace SPH_NS {
 #include "sph_passes.hpp"
 #include "sph_surface_tension.hpp"
 #include "sph_micropolar.hpp"
+#include "sph_drag.hpp"
 #include "sph_solvers.hpp"
 #include "sph_cg.hpp"
 #include "sph_halo.hpp"
@@ -354,8 +355,24 @@ void l_micropolar_apply(State &s) {
                        s.np_acc_out ? s.np_acc_out : s.st_acc);
 }
 
+// the air drag's walk (sph_drag.hpp), on the masks of the last sort: a_drag and its terms
+void l_drag(State &s) {
+    if (s.c.n == 0) return;
+    DragHost hk;
+    drag_host_constants(s.dr_radius, s.dr_rho_l, s.dr_rho_a, hk);   // (sph_set_drag has refused what this refuses)
+    const DragConsts k = drag_consts(hk, s.dr_radius, s.dr_rho_a, s.dr_k, s.dr_u_lib);
+    launch_pass_af(s, 2, [&](auto af) { return DragPass<af>{s.posv.cur(), s.velm.cur(), s.meta.cur(), s.dr_acc, s.dr_terms, k}; });
+}
+// v += dt a_drag on the velocities the non-pressure phase left, acc += a_drag where a non-pressure acceleration is kept
+void l_drag_apply(State &s) {
+    const int n = s.c.n;
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_drag_apply, dim3(cdiv(n, 256)), dim3(256), 0, s.stream, s.c, s.meta.cur(), s.dr_acc, s.velm.cur(),
+                       s.np_acc_out ? s.np_acc_out : s.st_acc);
+}
+
 void l_non_pressure(State &s, const float4 *visc_vel) {
-    float4 *np_acc = s.np_acc_out ? s.np_acc_out : (s.mp_on ? s.st_acc : nullptr);   // (micropolar model: every method keeps it)
+    float4 *np_acc = s.np_acc_out ? s.np_acc_out : ((s.mp_on || s.dr_on) ? s.st_acc : nullptr);   // (micropolar model, air drag: every method keeps it)
     if (s.st_akinci) {   // cohesion + curvature + adhesion in the place of the reference's term, on the stored normals
         StSpline sp = st_spline(s.st_h);
         sp.cA = (float)(s.st_beta * 0.007 / pow(s.st_h, 3.25));
@@ -554,6 +571,8 @@ const Launch *SPH_LAUNCH_FN() {
         L.surface_normals = l_surface_normals;
         L.micropolar = l_micropolar;
         L.micropolar_apply = l_micropolar_apply;
+        L.drag = l_drag;
+        L.drag_apply = l_drag_apply;
         L.pressure_integrate = l_pressure_integrate;
         L.wcsph_forces = l_wcsph_forces;
         L.rigid_volume = l_rigid_volume;

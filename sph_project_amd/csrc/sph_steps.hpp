@@ -209,20 +209,35 @@ static void ph_elastic_apply(SphHandle *h) {
     h->L->elastic_apply(h->st);
 }
 
+// Air drag (sph_set_drag): the walk reads positions and the step's starting velocities -- nothing another pass of the phase writes --
+// so it runs in front of the non-pressure pass; v += dt a_drag follows behind it, behind the elastic solids'.  Nothing without the mode.
+static void ph_drag(SphHandle *h) {
+    if (!h->st.dr_on) return;
+    ProfScope p(h, SPH_K_DRAG);
+    h->L->drag(h->st);
+}
+static void ph_drag_apply(SphHandle *h) {
+    if (!h->st.dr_on) return;
+    ProfScope p(h, SPH_K_MISC);
+    h->L->drag_apply(h->st);
+}
+
 // base_solver.py:190 compute_non_pressure_acceleration + :643 update_fluid_velocity
 // walks = false (SPH_PH_NON_PRESSURE): the Akinci pass runs on the normals the last SPH_PH_SURFACE_NORMALS / step stored, and the
-// micropolar model's a_mp is the one the last SPH_PH_MICROPOLAR / step stored
+// micropolar model's a_mp is the one the last SPH_PH_MICROPOLAR / step stored (likewise a_el and a_drag)
 static int run_non_pressure(SphHandle *h, bool walks = true) {
-    if (walks) { ph_surface_normals(h); ph_micropolar(h); ph_elastic(h); }   // (positions and densities do not change under the CG solve: its end reads these too)
+    if (walks) { ph_surface_normals(h); ph_micropolar(h); ph_elastic(h); ph_drag(h); }   // (positions and densities do not change under the CG solve: its end reads these too)
     if (h->prm.viscosity_implicit) {
         int rc = implicit_viscosity_non_pressure(h); if (rc) return rc;
         ph_micropolar_apply(h);
         ph_elastic_apply(h);
+        ph_drag_apply(h);
         return SPH_OK;
     }
     { ProfScope p(h, SPH_K_NON_PRESSURE); h->L->non_pressure(h->st, nullptr); }
     ph_micropolar_apply(h);
     ph_elastic_apply(h);
+    ph_drag_apply(h);
     return SPH_OK;
 }
 
@@ -230,7 +245,7 @@ static int wcsph_step(SphHandle *h) {
     State &s = h->st;
     // sharded: + migration / ghost exchange; over the push transport a plain WCSPH step needs nothing back from the device
     // (slab_neighbor_search_push, "async"): implicit viscosity and the unfused force passes launch exact grids instead
-    const bool fused = !h->prm.viscosity_implicit && !s.st_akinci && !s.mp_on && !s.el_marked;   // (the Akinci surface tension and the micropolar walk need the densities of ALL neighbours first; an elastic object adds a_el behind the non-pressure pass)
+    const bool fused = !h->prm.viscosity_implicit && !s.st_akinci && !s.mp_on && !s.el_marked && !s.dr_on;   // (the Akinci surface tension and the micropolar walk need the densities of ALL neighbours first; an elastic object adds a_el behind the non-pressure pass, the air drag a_drag)
     SortCarry carry;   // what the sort leaves to the density pass below (unsharded: that pass is the next launch and walks every tile)
     if (s.slab_active) { int rc = slab_neighbor_search(h, fused); if (rc) return rc; }
     else carry = ph_neighbor_search(h, true, true);                           // WCSPH.py:28 (the density pass below rewrites every rho: the sort need not move it)

@@ -354,6 +354,23 @@ def faucet_scene(nozzle=(6, 6), speed=1.0, hold=2, basin=0, method="wcsph", radi
     return cfg
 
 
+def wind_jet_scene(nozzle=(4, 4), speed=3.0, wind=(5.0, 0.0, 0.0), drag=1.0, method="wcsph", side=20, height=36, max_layers=24,
+                   drag_method="gissler", **keys):
+    """The first scene of the air drag: faucet_scene's downward nozzle (nozzle[0] x nozzle[1] lattice points, `speed`
+    m / s) under the lid of a tall closed sampled box of side x height x side particle diameters with a dry floor, in a constant
+    wind (Configuration.airVelocity) with the drag scaled by `drag`.  The emitter is object 0 (budget: max_layers layers).
+    drag_method = None leaves the drag keys out (the jet in a vacuum); keys: further Configuration keys (airDensity, ...) and
+    faucet_scene's radius, dt, viscosity, gravity, hold."""
+    faucet = {k: keys.pop(k) for k in ("radius", "dt", "viscosity", "gravity", "hold", "shape") if k in keys}
+    cfg = faucet_scene(nozzle=nozzle, speed=speed, basin=0, method=method, side=side, height=height, max_layers=max_layers, **faucet)
+    if drag_method is not None:
+        cfg["Configuration"]["dragMethod"] = drag_method
+        if drag_method == "gissler":
+            cfg["Configuration"].update(drag=float(drag), airVelocity=[float(c) for c in wind])
+    cfg["Configuration"].update(keys)
+    return cfg
+
+
 def scene_particles(cfg_dict):
     """Host lattice of every object present at prepare(), in the reference's insertion order
     (domain box first: base_container.py:192, then FluidBlocks: :215).  Blocks with entryTime > 0 are listed with

@@ -1,0 +1,527 @@
+"""GPU: the air drag (sph_set_drag) against the float64 model of tests/drag_terms.py -- the walk term by term through the
+C-ABI, three hand-made shapes, the methods it reaches through the shared non-pressure phase, the other opt-in models beside it, the
+mode switched off (the old code, bit for bit), determinism, a falling particle over whole steps, a jet in the wind, the refusals and
+the driver."""
+import json
+import os
+import subprocess
+import sys
+import threading
+
+import numpy as np
+import pytest
+
+from sph_project_amd import _lib as L
+from sph_project_amd import product as P
+from tests import helpers as H
+from tests import nonpressure_terms as T
+from tests import micropolar_terms as M
+from tests import drag_terms as D
+
+pytestmark = pytest.mark.gpu
+U = D.U
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+K_DRAG, RHO_A = 1.5, 1.1   # (off the defaults)
+
+_FIELDS = dict(x=L.F_POSITION, v=L.F_VELOCITY, rho=L.F_DENSITY, vol=L.F_REST_VOLUME, mass=L.F_MASS, mat=L.F_MATERIAL, obj=L.F_OBJECT_ID,
+               dyn=L.F_IS_DYNAMIC)
+_SCENES = {}
+
+
+def _scene(method, kind, implicit=False):
+    key = (method, kind, implicit)
+    if key not in _SCENES:
+        _SCENES[key] = D.scene(method, kind, viscosity_method="implicit" if implicit else "standard")
+    return _SCENES[key]
+
+
+def _params(sc, method, fast_math=0, fixed_iterations=0):
+    pd = sc["pd"]
+    p = L.SphParams()
+    for k in ("particle_radius", "support_radius", "V0", "padding", "g_upper", "viscosity", "viscosity_b", "density_0",
+              "surface_tension", "dt", "particle_max_num", "viscosity_implicit"):
+        setattr(p, k, pd[k])
+    p.domain_size[:] = pd["domain_size"]; p.grid_num[:] = pd["grid_num"]; p.gravity[:] = pd["gravity"]
+    p.method = L.METHOD[method]; p.device = -1; p.deterministic = 1; p.fast_math = fast_math; p.fixed_iterations = fixed_iterations
+    return p
+
+
+def _engine(sc, method, fast_math, drag=(K_DRAG, RHO_A), wind=(0.0, 0.0, 0.0), fixed_iterations=0, before_prepare=None):
+    """drag: (k, rho_air) or None (mode never touched)"""
+    eng = L.Engine(_params(sc, method, fast_math, fixed_iterations))
+    T.feed(eng, sc, oracle=False)
+    if before_prepare is not None:
+        before_prepare(eng)
+    if drag is not None:
+        eng.set_drag("gissler", drag[0], drag[1], wind)
+    eng.prepare()
+    eng.get_rigid_wrench(reset=True)
+    return eng
+
+
+def _state(eng, extra=()):
+    ids = eng.download(L.F_PARTICLE_ID)
+    st = {k: H.by_id(ids, eng.download(f)) for k, f in _FIELDS.items()}
+    for k, f in extra:
+        st[k] = H.by_id(ids, eng.download(f))
+    return st
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _got(st):
+    t = st["terms"]
+    return dict(a=st["a_drag"], n=t[:, 0], w=t[:, 1], cd=t[:, 2], a_un=t[:, 3], y=t[:, 4])
+
+
+def _model(sc, st, wind, fast_math, mutant=None, drag=(K_DRAG, RHO_A)):
+    Pm = sc["params"]
+    return D.drag_f64(st["x"], st["v"], st["mass"], st["mat"], Pm["h"], Pm["radius"], Pm["rho0"], k=drag[0], rho_a=drag[1], u=wind,
+                      mutant=mutant, fast=bool(fast_math))
+
+
+_WALK_PHASES = (L.PH_NEIGHBOR_SEARCH, L.PH_RIGID_VOLUME, L.PH_DENSITY)
+
+
+def _check_walk(eng, sc, wind, fast_math, tag, mutants=True):
+    """The phases up to SPH_PH_DRAG: SPH_F_DRAG_TERMS and SPH_F_DRAG_ACCEL against the model fed with the device's own inputs."""
+    for ph in _WALK_PHASES:
+        eng.run_phase(ph)
+    st0 = _state(eng)
+    fl = st0["mat"] == 1
+    eng.run_phase(L.PH_DRAG)
+    st1 = _state(eng, extra=[("a_drag", L.F_DRAG_ACCEL), ("terms", L.F_DRAG_TERMS)])
+    for k in ("x", "v", "rho", "mass", "vol"):
+        np.testing.assert_array_equal(_bits(st1[k]), _bits(st0[k]), err_msg=k)   # the walk writes nothing else
+    assert (st1["a_drag"][~fl] == 0).all() and (st1["terms"][~fl] == 0).all()     # rows that are not fluid: as allocated, untouched
+    res = _model(sc, st0, wind, fast_math)
+    got = _got(st1)
+    assert np.isfinite(st1["a_drag"]).all() and np.isfinite(st1["terms"]).all()
+    fr = D.worst(got, res, rows=fl)
+    print("drag walk [%s, fast_math=%d, wind=%s]: " % (tag, fast_math, wind) + ", ".join("%s %.3f" % kv for kv in fr.items())
+          + "; n_i %d ... %d, shielded (w = 0) %d, off %d" % (res["n"][fl].min(), res["n"][fl].max(), int((got["w"][fl & res["on"]] == 0).sum()),
+                                                             int((fl & ~res["on"]).sum())))
+    np.testing.assert_array_equal(got["n"][fl].astype(np.float64), res["n"][fl])            # exact
+    assert not D.misses(got, res, rows=fl), D.misses(got, res, rows=fl)
+    off = fl & ~res["on"]
+    assert (st1["a_drag"][off] == 0).all() and (st1["terms"][off][:, 1:] == 0).all()
+    if mutants:
+        for mutant in D.MUTANTS:
+            if (mutant in D.RIGID_MUTANTS and not sc["rigid"]) or (mutant in D.WIND_MUTANTS and not any(wind)):
+                continue
+            if mutant == "threshold_dropped" and not off.any():
+                continue
+            assert D.misses(got, _model(sc, st0, wind, fast_math, mutant=mutant), rows=fl), mutant
+    return st0, st1, fl, res
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+@pytest.mark.parametrize("wind", D.WINDS)
+@pytest.mark.parametrize("kind", ["block", "rigid", "fluid"])
+def test_walk_term_by_term(gpu, kind, wind, fast_math):
+    """DragPass<true> (the block, the all-fluid scene) and <false> (the scene with the plate and the cube); every mutant of the model
+    that the scene can tell apart misses a bound against the device's output."""
+    sc = _scene("wcsph", kind)
+    eng = _engine(sc, "wcsph", fast_math, wind=wind)
+    try:
+        st0, st1, fl, res = _check_walk(eng, sc, wind, fast_math, kind)
+        if kind == "block":
+            D.assert_alive(res, wind)
+            assert len(fl) == 343
+    finally:
+        eng.close()
+
+
+def _shape(pos, vel, rigid_pos=None, fast_math=0, wind=(0.0, 0.0, 0.0)):
+    sc = D.particles_scene("wcsph", np.asarray(pos, np.float64), np.asarray(vel, np.float64), rigid_pos=rigid_pos)
+    eng = _engine(sc, "wcsph", fast_math, wind=wind)
+    try:
+        st0, st1, fl, res = _check_walk(eng, sc, wind, fast_math, "shape", mutants=False)
+    finally:
+        eng.close()
+    return st1, _got(st1), res
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+def test_three_hand_made_shapes(gpu, fast_math):
+    r = 0.01
+    # one isolated particle: the n_i = 0 branch, w = 1, C_D = C_liu
+    st, got, res = _shape([[0.3, 0.3, 0.3]], [[2.0, 0.0, 0.0]], fast_math=fast_math)
+    assert got["n"][0] == 0 and got["w"][0] == 1.0 and got["a"][0, 0] < 0 and (got["a"][0, 1:] == 0).all()
+    re = 2 * D.constants(r, 1000.0, RHO_A)["re_coeff"] * 2.0
+    assert abs(got["cd"][0] - 0.424 * (1 + 2.632 * got["y"][0])) < 1e-5 and re > 1000
+    # two particles 1.5 r apart along the velocity: the leading one w = 1, the trailing one w = 0 and a_drag = 0 EXACTLY
+    st, got, res = _shape([[0.3, 0.3, 0.3], [0.3 + 1.5 * r, 0.3, 0.3]], [[2.0, 0.0, 0.0], [2.0, 0.0, 0.0]], fast_math=fast_math)
+    assert (got["n"] == 1).all()
+    assert got["w"][1] == 1.0 and got["a"][1, 0] < 0
+    assert got["w"][0] == 0.0 and (st["a_drag"][0] == 0).all()
+    # ... and the same pair across the diagonal: the directions are no powers of two
+    d = np.array([1.0, 2.0, -0.5]) / np.linalg.norm([1.0, 2.0, -0.5])
+    st, got, res = _shape([[0.3, 0.3, 0.3], np.array([0.3, 0.3, 0.3]) + 1.5 * r * d], [3.0 * d, 3.0 * d], fast_math=fast_math)
+    assert got["w"][1] == 1.0 and got["w"][0] == 0.0 and (st["a_drag"][0] == 0).all() and np.dot(st["a_drag"][1], d) < 0
+    # a particle whose only neighbours are rigid: treated as isolated
+    ring = [[0.3 + 1.5 * r * c, 0.3 + 1.5 * r * s, 0.3] for c, s in ((1, 0), (-1, 0), (0, 1), (0, -1))]
+    alone, got_alone, _ = _shape([[0.3, 0.3, 0.3]], [[2.0, 1.0, 0.0]], fast_math=fast_math)
+    st, got, res = _shape([[0.3, 0.3, 0.3]], [[2.0, 1.0, 0.0]], rigid_pos=ring, fast_math=fast_math)
+    fl = st["mat"] == 1
+    assert fl.sum() == 1 and len(fl) == 5 and got["n"][fl][0] == 0 and got["w"][fl][0] == 1.0
+    np.testing.assert_array_equal(_bits(st["a_drag"][fl]), _bits(alone["a_drag"]))
+    np.testing.assert_array_equal(_bits(st["terms"][fl]), _bits(alone["terms"]))
+
+
+def _visc_density(eng, st, method, rho0):
+    """The density the viscous term of the method reads, as the device holds it (tests/test_hip_micropolar.py)."""
+    if method != "wcsph":
+        return st["rho"]
+    raw = H.by_id(eng.download(L.F_PARTICLE_ID), eng.download(L.F_DEBUG_CAPTURE))
+    fl = st["mat"] == 1
+    np.testing.assert_array_equal(np.maximum(raw, np.float32(rho0))[fl], st["rho"][fl])
+    return raw
+
+
+def _check_phase(eng, sc, method, wind, fast_math, tag, implicit=0):
+    """SPH_PH_DRAG, then SPH_PH_NON_PRESSURE (or the pieces of the CG solve up to SPH_PH_CG_END), which adds the STORED a_drag:
+    v = v0 + dt (a_np + a_drag), and the kept non-pressure acceleration is a_np + a_drag."""
+    Pm = sc["params"]
+    st0, st1, fl, res = _check_walk(eng, sc, wind, fast_math, tag, mutants=False)
+    rho = np.where(fl, _visc_density(eng, st0, method, Pm["rho0"]), 1.0)
+    if implicit:
+        eng.run_phase(L.PH_CG_PREPARE)
+        for _ in range(implicit):
+            for ph in (L.PH_CG_AP, L.PH_CG_UPDATE_XR, L.PH_CG_UPDATE_P):
+                eng.run_phase(ph)
+        solved = H.by_id(eng.download(L.F_PARTICLE_ID), eng.download(L.F_CG_X))
+        eng.run_phase(L.PH_CG_END)
+    else:
+        eng.run_phase(L.PH_NON_PRESSURE)
+    st2 = _state(eng, extra=[("a_np", L.F_NON_PRESSURE_ACCEL), ("a_drag", L.F_DRAG_ACCEL), ("terms", L.F_DRAG_TERMS)])
+    np.testing.assert_array_equal(_bits(st2["a_drag"]), _bits(st1["a_drag"]))       # no second walk
+    np.testing.assert_array_equal(_bits(st2["terms"]), _bits(st1["terms"]))
+    visc_v = np.where(fl[:, None], solved, st0["v"]) if implicit else None
+    Pn = dict(Pm, st=sc["pd"]["surface_tension"])
+    rv = T.non_pressure_f64(st0["x"], st0["v"], rho, st0["mass"], st0["vol"], st0["mat"], st0["dyn"], st0["obj"], sc["com"], Pn, visc_v=visc_v)
+    a_np, b_np = rv["a"], T.accel_bound(rv)
+    a = a_np + res["a"]
+    bound = b_np + res["b_a"] + 2 * U * (np.abs(a_np) + np.abs(a))     # (two stored f32 accelerations added)
+    err = np.abs(st2["a_np"].astype(np.float64) - a)[fl]
+    fr = {"acceleration": float((err / bound[fl]).max())}
+    assert np.isfinite(st2["a_np"][fl]).all() and (err <= bound[fl]).all(), fr
+    v_np = st0["v"].astype(np.float64) + Pm["dt"] * a_np
+    vs = v_np + Pm["dt"] * res["a"]
+    err = np.abs(st2["v"].astype(np.float64) - vs)[fl]
+    vb = (Pm["dt"] * bound + 2 * U * (np.abs(v_np) + np.abs(vs)))[fl]   # (two updates, each rounded once)
+    fr["v*"] = float((err / vb).max())
+    assert np.isfinite(st2["v"]).all() and (err <= vb).all(), fr
+    assert np.abs(Pm["dt"] * res["a"])[fl].max() > 100 * vb.max()        # a_drag is far above what the bound could hide
+    np.testing.assert_array_equal(st2["v"][~fl], st0["v"][~fl])
+    print("drag phase [%s, fast_math=%d]: " % (tag, fast_math) + ", ".join("%s %.3f" % kv for kv in fr.items()))
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+@pytest.mark.parametrize("method", ["wcsph", "dfsph", "pcisph", "iisph"])
+def test_phase_under_every_method(gpu, method, fast_math):
+    sc = _scene(method, "block")
+    eng = _engine(sc, method, fast_math, wind=D.WINDS[1])
+    try:
+        _check_phase(eng, sc, method, D.WINDS[1], fast_math, method + ", block")
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+def test_phase_under_implicit_viscosity(gpu, fast_math):
+    """The stored a_drag goes in behind SPH_PH_CG_END."""
+    sc = _scene("dfsph", "rigid", implicit=True)
+    eng = _engine(sc, "dfsph", fast_math, wind=D.WINDS[1], fixed_iterations=4)
+    try:
+        _check_phase(eng, sc, "dfsph", D.WINDS[1], fast_math, "dfsph implicit, rigid", implicit=4)
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+def test_beside_the_other_opt_in_models(gpu, fast_math):
+    """Akinci surface tension, the micropolar model and an elastic object (object 3) all on: a twin without the drag keeps a_np + a_mp
+    + a_el; the drag is applied last, so the handle with it keeps exactly fl(that + a_drag) and v = fl(v_twin + fl(dt a_drag)) up to the
+    fast build's contraction -- and a_drag itself is the model's."""
+    sc = _scene("wcsph", "rigid")
+    w = M.angular_velocities(sc)
+    wind = D.WINDS[1]
+    outs = {}
+    for how in ("twin", "drag"):
+        def others(eng):
+            eng.set_surface_tension("akinci", 1.0, 1.0)
+            eng.set_micropolar("micropolar", 0.3, 0.5, 2.0)
+            eng.upload(L.F_ANGULAR_VELOCITY, np.ascontiguousarray(w[eng.download(L.F_PARTICLE_ID)]))
+            eng.set_elastic_object(3, 2e4, 0.3)
+        eng = _engine(sc, "wcsph", fast_math, drag=(K_DRAG, RHO_A) if how == "drag" else None, wind=wind, before_prepare=others)
+        try:
+            for ph in _WALK_PHASES + (L.PH_SURFACE_NORMALS, L.PH_MICROPOLAR, L.PH_ELASTIC):
+                eng.run_phase(ph)
+            st0 = _state(eng)
+            if how == "drag":
+                eng.run_phase(L.PH_DRAG)
+            eng.run_phase(L.PH_NON_PRESSURE)
+            extra = [("a_np", L.F_NON_PRESSURE_ACCEL), ("a_mp", L.F_MICROPOLAR_ACCEL), ("a_el", L.F_ELASTIC_ACCEL)]
+            outs[how] = (st0, _state(eng, extra=extra + ([("a_drag", L.F_DRAG_ACCEL), ("terms", L.F_DRAG_TERMS)] if how == "drag" else [])))
+        finally:
+            eng.close()
+    (t0, t1), (d0, d1) = outs["twin"], outs["drag"]
+    fl = t0["mat"] == 1
+    for k in ("x", "v", "rho"):
+        np.testing.assert_array_equal(_bits(d0[k]), _bits(t0[k]), err_msg=k)
+    for k in ("a_mp", "a_el"):
+        np.testing.assert_array_equal(_bits(d1[k][fl]), _bits(t1[k][fl]), err_msg=k)
+    assert np.abs(t1["a_mp"][fl]).max() > 1.0
+    res = _model(sc, d0, wind, fast_math)
+    got = _got(d1)
+    np.testing.assert_array_equal(got["n"][fl].astype(np.float64), res["n"][fl])
+    assert not D.misses(got, res, rows=fl), D.misses(got, res, rows=fl)
+    a_d = d1["a_drag"].astype(np.float64)
+    acc = t1["a_np"].astype(np.float64) + a_d
+    assert (np.abs(d1["a_np"].astype(np.float64) - acc)[fl] <= U * np.abs(acc)[fl] + 1e-45).all()          # one rounded addition
+    dt = sc["params"]["dt"]
+    vs = t1["v"].astype(np.float64) + dt * a_d
+    assert (np.abs(d1["v"].astype(np.float64) - vs)[fl] <= U * (np.abs(vs) + np.abs(dt * a_d))[fl] + 1e-45).all()
+    assert np.abs(dt * a_d)[fl].max() > 1e-5
+
+
+_EVERY_FIELD = (L.F_POSITION, L.F_VELOCITY, L.F_ACCELERATION, L.F_DENSITY, L.F_PRESSURE, L.F_REST_VOLUME, L.F_MASS, L.F_MATERIAL,
+                L.F_OBJECT_ID, L.F_IS_DYNAMIC, L.F_COLOR, L.F_PARTICLE_ID, L.F_GRID_ID, L.F_DFSPH_ALPHA, L.F_DFSPH_KAPPA, L.F_DFSPH_KAPPA_V,
+                L.F_DENSITY_STAR, L.F_DENSITY_DERIV, L.F_PRESSURE_ACCEL, L.F_NON_PRESSURE_ACCEL)
+
+
+def _every_field(eng):
+    out = {}
+    for f in _EVERY_FIELD:
+        try:
+            out[f] = eng.download(f)
+        except L.SphError as e:
+            out[f] = "refused %d" % e.code
+    return out
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+@pytest.mark.parametrize("method", ["wcsph", "dfsph"])
+def test_mode_off_is_the_old_code(gpu, method, fast_math):
+    """Never touched, set to "none", set to "gissler" and back: 20 steps, every downloadable field bit-identical; the fused force pass
+    (kernel id 18) ran under WCSPH on all three and SPH_K_DRAG never did.  With the mode on it runs every step, 18 does not."""
+    sc = _scene(method, "rigid")
+    outs, profs = [], []
+    for how in ("untouched", "none", "back", "on"):
+        eng = _engine(sc, method, fast_math, drag=None)
+        if how == "none":
+            eng.set_drag("none")
+        elif how == "back":
+            eng.set_drag("gissler", 0.7, 1.0, (1.0, 2.0, 3.0))
+            assert eng.get_drag() == dict(method="gissler", k=0.7, rho_air=1.0, air_velocity=(1.0, 2.0, 3.0))
+            eng.set_drag("none", 0.7, 1.0, (1.0, 2.0, 3.0))
+            assert eng.get_drag() == dict(method="none", k=0.7, rho_air=1.0, air_velocity=(1.0, 2.0, 3.0))
+        elif how == "on":
+            eng.set_drag("gissler", K_DRAG, RHO_A, D.WINDS[1])
+        eng.profile_enable(-1, True)
+        eng.step(20)
+        profs.append({k: eng.profile_read(k)[0] for k in (4, 18, L.K_DRAG)})
+        outs.append(_every_field(eng))
+        eng.close()
+    for o, how in zip(outs[1:3], ("none", "back")):
+        for f in _EVERY_FIELD:
+            if how == "back" and f == L.F_NON_PRESSURE_ACCEL and isinstance(outs[0][f], str):
+                continue   # (the buffer the mode allocated stays downloadable: the one field that is not "as before"; nothing reads it)
+            if isinstance(outs[0][f], str):
+                assert o[f] == outs[0][f], f
+            else:
+                np.testing.assert_array_equal(np.ascontiguousarray(o[f]).view(np.uint8), np.ascontiguousarray(outs[0][f]).view(np.uint8), err_msg=str(f))
+    for pr in profs[:3]:
+        assert pr[L.K_DRAG] == 0 and (pr[18] == 20 and pr[4] == 0 if method == "wcsph" else pr[18] == 0), pr
+    assert profs[3][L.K_DRAG] == 20 and profs[3][18] == 0 and profs[3][4] >= 20, profs[3]
+    assert np.abs(outs[3][L.F_POSITION] - outs[0][L.F_POSITION]).max() > 1e-6 and np.isfinite(outs[3][L.F_POSITION]).all()
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+def test_determinism(gpu, fast_math):
+    """Mode on: two runs give the same bits, one sph_step(h, 25) is 25 calls of one step bit for bit."""
+    sc = _scene("wcsph", "rigid")
+    outs = []
+    for how in ("once", "again", "one_by_one"):
+        eng = _engine(sc, "wcsph", fast_math, wind=D.WINDS[1])
+        if how == "one_by_one":
+            for _ in range(25):
+                eng.step(1)
+        else:
+            eng.step(25)
+        outs.append(_state(eng, extra=[("a_drag", L.F_DRAG_ACCEL), ("terms", L.F_DRAG_TERMS)]))
+        eng.close()
+    fl = outs[0]["mat"] == 1
+    assert np.isfinite(outs[0]["x"]).all() and np.abs(outs[0]["a_drag"][fl]).max() > 0
+    for o in outs[1:]:
+        for k in ("x", "v", "rho"):
+            np.testing.assert_array_equal(_bits(o[k]), _bits(outs[0][k]), err_msg=k)
+        for k in ("a_drag", "terms"):
+            np.testing.assert_array_equal(_bits(o[k][fl]), _bits(outs[0][k][fl]), err_msg=k)
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+def test_falling_particle_over_whole_steps(gpu, fast_math):
+    """One isolated particle under gravity, drag = 50, 400 WCSPH steps against explicit Euler on the same ODE in float64:
+        V_{n+1} = V_n + dt (g + a_drag(V_n)),  X_{n+1} = X_n + dt V_{n+1}.
+    The device does, per step and component: v' = fl(v + fl(dt g)), v'' = fl(v' + fl(dt a_drag(v))), x' = fl(x + fl(dt v'')) (an isolated
+    particle has no other force: its density is below rho0, its pressure 0).  With e_n = |v_n - V_n|, b_n the model's bound of a_drag
+    at V_n and Lam_n a bound of |d a_drag / d v| there (central difference over +-1 % of the speed, doubled: a_drag is piecewise smooth
+    and its one-sided slopes at the kinks Re = 1000 and y = 1 differ by less than that):
+        e_{n+1} <= (1 + dt Lam_n) e_n + dt b_n + u (dt |g| + dt |a_n|) + 2 u |V_{n+1}|
+        ex_{n+1} <= ex_n + dt e_{n+1} + u dt |V_{n+1}| + u |X_{n+1}|
+    Nothing here is fitted: the recursion is evaluated along the model's own trajectory."""
+    drag = (50.0, D.RHO_AIR)
+    x0 = np.array([0.3, 0.45, 0.26])
+    sc = D.particles_scene("wcsph", x0[None, :], np.zeros((1, 3)), gravity=(0.0, -9.81, 0.0))
+    Pm = sc["params"]
+    dt, g = Pm["dt"], np.asarray(sc["pd"]["gravity"], np.float32).astype(np.float64)
+    eng = _engine(sc, "wcsph", fast_math, drag=drag)
+    try:
+        mass = float(eng.download(L.F_MASS)[0])
+        xs = eng.download(L.F_POSITION)[0].astype(np.float64)
+        eng.step(400)
+        v_dev, x_dev = eng.download(L.F_VELOCITY)[0].astype(np.float64), eng.download(L.F_POSITION)[0].astype(np.float64)
+        n_last = eng.download(L.F_DRAG_TERMS)[0, 0]
+    finally:
+        eng.close()
+
+    def acc(V):
+        return D.particle_f64(V[None, :], mass, 0.0, 0.0, Pm["radius"], Pm["rho0"], k=drag[0], rho_a=drag[1], fast=bool(fast_math))
+    V, X = np.zeros(3), xs.copy()
+    e, ex = np.zeros(3), np.zeros(3)
+    for n in range(400):
+        r = acc(V)
+        a, b = r["a"][0], r["b_a"][0]
+        s = np.linalg.norm(V)
+        lam = 0.0
+        if r["on"][0]:
+            h = 0.01 * s
+            lam = 2.0 * np.abs(acc(V * (1 + h / s))["a"][0] - acc(V * (1 - h / s))["a"][0]).max() / (2 * h)
+        Vn = V + dt * (g + a)
+        e = (1 + dt * lam) * e + dt * b + U * dt * (np.abs(g) + np.abs(a)) + 2 * U * np.abs(Vn)
+        V = Vn
+        X = X + dt * V
+        ex = ex + dt * e + U * dt * np.abs(V) + U * np.abs(X)
+    free = dt * 400 * 9.81
+    print("falling particle [fast_math=%d]: v_y %.6f (model %.6f, free fall %.4f), |err| / bound v %.3f x %.3f"
+          % (fast_math, v_dev[1], V[1], -free, (np.abs(v_dev - V) / np.maximum(e, 1e-300)).max(), (np.abs(x_dev - X) / np.maximum(ex, 1e-300)).max()))
+    assert n_last == 0 and np.isfinite(v_dev).all()
+    assert (np.abs(v_dev - V) <= e).all() and (np.abs(x_dev - X) <= ex).all()
+    assert free - abs(V[1]) > 1000 * e.max() and e.max() < 1e-3 * abs(V[1])      # the drag's effect is far above what the bound could hide
+
+
+def run_wind_jet(fast_math, steps=300):
+    """wind_jet_scene for `steps` steps, three twins: {how: dict(x, v: the emitter's particles; box: the domain's end; n)}"""
+    out = {}
+    for how, keys in (("off", dict(drag_method=None)), ("drag", dict(wind=(0.0, 0.0, 0.0))), ("wind", dict(wind=(5.0, 0.0, 0.0)))):
+        cfg = P.wind_jet_scene(**keys)
+        container, solver = P.build_product(cfg, fast_math=fast_math)
+        solver.prepare()
+        solver.advance(steps)
+        eng = container.engine
+        x, v = eng.download(L.F_POSITION), eng.download(L.F_VELOCITY)
+        jet = (eng.download(L.F_OBJECT_ID) == 0) & (eng.download(L.F_MATERIAL) == 1)
+        assert solver.drag_method == ("none" if how == "off" else "gissler") and solver.air_velocity == tuple(keys.get("wind", (0.0, 0.0, 0.0)))
+        out[how] = dict(x=x[jet].astype(np.float64), v=v[jet].astype(np.float64), all_x=x, all_v=v, box=np.asarray(cfg["Configuration"]["domainEnd"]),
+                        n=int(jet.sum()))
+        eng.close()
+    return out
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+def test_a_jet_in_the_wind(gpu, fast_math):
+    """Every state finite and inside the box; the wind along +x carries the jet along (a strictly larger mean x than in a vacuum);
+    still air slows its fall (a strictly smaller mean downward speed)."""
+    out = run_wind_jet(fast_math)
+    for how, o in out.items():
+        assert o["n"] > 100 and np.isfinite(o["all_x"]).all() and np.isfinite(o["all_v"]).all(), how
+        assert (o["all_x"] > 0).all() and (o["all_x"] < o["box"]).all(), how
+    mx = {how: o["x"][:, 0].mean() for how, o in out.items()}
+    down = {how: -o["v"][:, 1].mean() for how, o in out.items()}
+    print("wind jet [fast_math=%d]: %d particles; mean x off %.5f drag %.5f wind %.5f (shift %.5f m); mean downward speed off %.4f drag %.4f "
+          "wind %.4f m / s" % (fast_math, out["off"]["n"], mx["off"], mx["drag"], mx["wind"], mx["wind"] - mx["off"], down["off"], down["drag"],
+                               down["wind"]))
+    assert mx["wind"] > mx["off"]
+    assert down["drag"] < down["off"]
+
+
+def _rc(call, *words):
+    try:
+        call()
+    except L.SphError as e:
+        assert all(w in str(e) for w in words), (str(e), words)
+        return e.code
+    return 0
+
+
+def test_refusals(gpu, monkeypatch, tmp_path):
+    sc = _scene("wcsph", "fluid")
+    eng = L.Engine(_params(sc, "pbf"))
+    assert _rc(lambda: eng.set_drag("gissler"), "sph_set_drag", "PBF") == L.ERR_UNSUPPORTED
+    eng.set_pbf_variant("consistent")
+    assert _rc(lambda: eng.set_drag("gissler"), "sph_set_drag", "PBF") == L.ERR_UNSUPPORTED
+    eng.close()
+    eng = L.Engine(_params(sc, "wcsph"))
+    for bad, word in ((dict(k=-1.0), "k"), (dict(rho_air=-0.5), "rho_air"), (dict(k=float("nan")), "k"), (dict(rho_air=float("inf")), "rho_air"),
+                      (dict(air_velocity=(0.0, float("nan"), 0.0)), "air_velocity[1]"), (dict(method=2), "method 2")):
+        assert _rc(lambda: eng.set_drag(**bad), "sph_set_drag", word) == L.ERR_INVALID, bad
+    assert eng.get_drag() == dict(method="none", k=1.0, rho_air=1.2041, air_velocity=(0.0, 0.0, 0.0))
+    assert _rc(lambda: eng.run_phase(L.PH_DRAG), "SPH_PH_DRAG") == L.ERR_INVALID
+    assert _rc(lambda: eng.download(L.F_DRAG_ACCEL)) == L.ERR_UNSUPPORTED
+    assert _rc(lambda: eng.download(L.F_DRAG_TERMS), "sph_set_drag") == L.ERR_UNSUPPORTED
+    T.feed(eng, sc, oracle=False)
+    eng.set_drag("gissler")
+    n = eng.particle_num
+    assert _rc(lambda: eng.upload(L.F_DRAG_ACCEL, np.zeros((n, 3), np.float32))) != 0      # download only
+    assert _rc(lambda: eng.upload(L.F_DRAG_TERMS, np.zeros((n, 5), np.float32))) != 0
+    eng.close()
+    # omega^2 <= 0 for the handle's radius and density: a handle of 1e-9 m particles
+    p = _params(sc, "wcsph")
+    p.particle_radius = 1e-9
+    eng = L.Engine(p)
+    assert _rc(lambda: eng.set_drag("gissler"), "sph_set_drag", "omega^2") == L.ERR_INVALID
+    eng.set_drag("none")
+    eng.close()
+    # sharded handles: two ranks on one GPU over the shared-memory transport, one thread each
+    monkeypatch.setenv("SPH_COMM_TRANSPORT", "shm")
+    monkeypatch.setenv("SPH_COMM_TIMEOUT_S", "20")
+    engs = [L.Engine(_params(sc, "wcsph")) for _ in range(2)]
+    uid = engs[0].comm_unique_id()
+    nz = int(_params(sc, "wcsph").grid_num[2])
+    got = [None, None]
+
+    def rank(k):
+        engs[k].comm_init(k, 2, uid)
+        if k == 1:   # the other order: the mode first, then the slab
+            engs[k].set_drag("gissler")
+            got[k] = _rc(lambda: engs[k].comm_set_slab(nz // 2, nz), "comm_set_slab", "drag")
+            engs[k].set_drag("none")
+        engs[k].comm_set_slab(*((0, nz // 2) if k == 0 else (nz // 2, nz)))
+        if k == 0:
+            got[k] = _rc(lambda: engs[k].set_drag("gissler"), "sph_set_drag", "sharded")
+
+    threads = [threading.Thread(target=rank, args=(k,), daemon=True) for k in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(60)
+    assert not any(t.is_alive() for t in threads)
+    assert got == [L.ERR_UNSUPPORTED, L.ERR_UNSUPPORTED], got
+    for e in engs:
+        e.close()
+
+
+def test_driver_runs_a_scene_file_with_the_keys(gpu, tmp_path):
+    """The driver takes the keys from a scene file; --gpus 2 ends in the parent with code 2, before a rank starts."""
+    cfg = P.wind_jet_scene(side=16, height=24, max_layers=8, airDensity=1.3)
+    path = tmp_path / "jet.json"
+    path.write_text(json.dumps(cfg))
+    driver = [sys.executable, os.path.join(ROOT, "sph_project_amd", "run_simulation.py"), "--scene_file", str(path)]
+    r = subprocess.run(driver + ["--max_steps", "40", "--output_dir", str(tmp_path / "out")], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert r.returncode == 0, (r.stdout[-600:], r.stderr[-600:])
+    r = subprocess.run(driver + ["--gpus", "2"], capture_output=True, text=True, cwd=ROOT, timeout=120)
+    assert r.returncode == 2 and "gissler" in r.stderr, (r.returncode, r.stderr[-400:])
