@@ -237,6 +237,10 @@ typedef enum {
        (SPH_F_DRAG_ACCEL) and its terms (SPH_F_DRAG_TERMS) and nothing else.  In this mode SPH_PH_NON_PRESSURE (and SPH_PH_CG_END) add
        the STORED a_drag behind their pass, v += dt a_drag, without walking again; a step walks in front of its non-pressure pass. */
     SPH_PH_DRAG = 32,
+    /* Outflow (sph_set_outflow; SPH_ERR_INVALID while no volume is set): the mark and the count of the CURRENT step count alone -- every
+       active fluid particle inside a volume whose time window holds T_steps gets its dead bit, the per-volume counters are read back.  No
+       sort: the particle count shrinks in the next SPH_PH_NEIGHBOR_SEARCH (or step). */
+    SPH_PH_OUTFLOW = 33,
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -287,6 +291,7 @@ typedef enum {
     SPH_K_ELASTIC = 33,         /* elastic solids: the scatter + pass A + pass B (v += dt a_el: SPH_K_MISC; the capture: SPH_K_MISC); "?" as well */
     SPH_K_EMIT = 34,            /* fluid emitters: the hold launch and the emit launch (sph_set_emitter); "?" as well */
     SPH_K_DRAG = 35,            /* air drag: the walk (v += dt a_drag: SPH_K_MISC); "?" as well */
+    SPH_K_OUTFLOW = 36,         /* outflow: the mark launch (by volume, or by id for sph_remove_particles); "?" as well */
     SPH_K_COUNT_
 } SphKernelId;
 
@@ -677,6 +682,70 @@ typedef struct {
 int sph_set_emitter(SphHandle *h, int index, const SphEmitter *emitter);
 int sph_get_emitter_state(SphHandle *h, int index, SphEmitterState *out);
 int sph_emitter_eval_host(const SphEmitter *emitter, double dt, double spacing, int64_t k, int layer, SphEmitterEval *out, float *xyz);
+
+/* Outflow (opt-in; the scene list "Outflows"): up to SPH_MAX_OUTFLOWS kill volumes -- an axis-aligned box or a sphere, in
+   the scene frame -- that remove fluid on the device, and removal by persistent id from the host.
+     predicate: float32, on the stored position.  The bounds are rounded to float32 once, at sph_set_outflow.  Box: min <= x <= max in
+               every component (faces inclusive).  Sphere: dx = x - cx, ...; (dx dx + dy dy) + dz dz <= r r, every product and sum
+               rounded (no contraction in either build).  invert negates the result (a keep-region).  A particle inside several volumes
+               counts for the lowest index.  Only active fluid particles (SPH_MAT_FLUID) of the listed objects (n_objects == 0: of every
+               object) are tested; rigid particles never leave.
+     window:   T_k = k dt, dt = (double)(float)timeStepSize, k = the step count the running step ends at; a volume is active while
+               start <= T_k <= end (end = +infinity: for ever).  Evaluated on the host; the kernel sees the active volumes only.
+     slot:     the insertion point of a step, between the emitters' hold and their emission: newborn particles are first tested one step
+               later, a held particle that is removed is gone (the hold pass finds ids; an id it does not find costs nothing).
+   ONE elementwise launch (k_outflow_mark, profiled as SPH_K_OUTFLOW) sets the dead bit and counts per volume; the host reads the eight
+   counters back once per step while a volume is active (one small copy into pinned memory and one stream wait).  The next neighbour
+   search files the dead behind the grid (the graveyard cells a slab rank drops its ghosts into) and particle_num / fluid_particle_num
+   shrink; sph_step and sph_step_end run that search before they return when their last slot removed something, so a caller never
+   sees a dead particle.  Both sort modes (deterministic on or off) take the graveyard route for such a sort; every other sort is the
+   one it was.  While a volume is set no step is pre-hashed by its own force pass / position update (SphStats::prehashed_sorts stays),
+   and sph_step_async returns SPH_ERR_UNSUPPORTED (the count needs the host); sph_step(h, n) works for any n.
+   Ids stop being slots with the first removal: new particles (sph_append_particles, emitters) get ids from a counter that only grows,
+   and particle_max_num then bounds the particles EVER created (the arrays kept by id -- colours at home, micropolar angular velocities
+   -- are indexed by it): SPH_ERR_CAPACITY from sph_append_particles / sph_set_emitter accordingly.  Ids are not recycled.
+   SPH_F_CG_X (slot-indexed, not reordered by the sort) is only a warm start after a removal.
+   sph_set_outflow: any time outside a step (between sph_step_begin and sph_step_end: SPH_ERR_INVALID); volume == NULL clears the index.
+   SPH_ERR_UNSUPPORTED, with the reason: a PBF handle (either variant), a sharded handle (and sph_comm_set_slab while a volume is set),
+   g_upper set, an axis order other than "xyz" (unreachable today: only sph_comm_set_slab permutes the axes, and a sharded handle is
+   refused first), ids set from outside (sph_set_appended_ids / SPH_F_PARTICLE_ID; and those two while a
+   volume is set), an elastic object present (and sph_set_elastic_object while a volume is set).  SPH_ERR_INVALID, naming the field:
+   an unknown shape, a bound that is not finite, min >= max in a component, radius <= 0, end <= start, an object id outside the
+   handle's objects or one that is not a fluid object.
+   sph_get_outflow_state: what the host knows (no device access).
+   sph_remove_particles: removal by persistent id, between steps or between sph_step_begin and sph_step_end (there the dead leave in
+   sph_step_end, as what a volume marks in the slot).  Every id must name a live active fluid particle and appear once: otherwise
+   SPH_ERR_INVALID and nothing is removed.  The device counts what it marks and the call checks that count against n.  The same
+   refusals as sph_set_outflow.  A second kernel marks by binary search in the sorted
+   id list (k_outflow_mark_ids, SPH_K_OUTFLOW).
+   sph_outflow_test_host: the kernels' predicate on the CPU (the same source), one volume over n points xyz[n][3]: inside[k] = 0 / 1
+   (geometry and invert; no window, no object list).  sph_outflow_active_host: the window test at step count k (0 / 1; < 0: an error).
+   No device is touched. */
+#define SPH_MAX_OUTFLOWS 8
+#define SPH_OUTFLOW_MAX_OBJECTS 16
+#define SPH_OUTFLOW_BOX 0
+#define SPH_OUTFLOW_SPHERE 1
+typedef struct {
+    int32_t shape;                     /* SPH_OUTFLOW_BOX, SPH_OUTFLOW_SPHERE */
+    int32_t invert;                    /* != 0: remove what is OUTSIDE the shape */
+    double min[3], max[3];             /* box, scene frame, metres */
+    double center[3], radius;          /* sphere */
+    double start, end;                 /* scene time, seconds; end = +infinity: for ever */
+    int32_t n_objects;                 /* 0: every fluid object; else objects[0 .. n_objects) */
+    int32_t objects[SPH_OUTFLOW_MAX_OBJECTS];
+    int32_t reserved;                  /* 0 */
+} SphOutflow;
+typedef struct {
+    int64_t removed;                   /* particles this volume has removed since it was set */
+    int32_t removed_last_step;         /* ... in the last slot (step or SPH_PH_OUTFLOW) */
+    int32_t active;                    /* the window holds the current step count */
+    int32_t reserved[4];
+} SphOutflowState;
+int sph_set_outflow(SphHandle *h, int index, const SphOutflow *volume);
+int sph_get_outflow_state(SphHandle *h, int index, SphOutflowState *out);
+int sph_remove_particles(SphHandle *h, const int32_t *ids, int n);
+int sph_outflow_test_host(const SphOutflow *volume, const float *xyz, int n, uint8_t *inside);
+int sph_outflow_active_host(const SphOutflow *volume, double dt, int64_t k);
 
 /* --- time stepping --------------------------------------------------------------------- */
 /* replaces XSolver.prepare() (base_solver.py:683, DFSPH.py:321, PCISPH.py:188); particles of

@@ -99,6 +99,10 @@ class BaseContainer:
         self.emitters = scene.emitters_of(config, self.METHOD, geo.dim)
         if self.emitters and engine_opts.get("slab"):
             raise ValueError("Emitters are not available on a sharded scene (--gpus > 1)")
+        # outflow: the top-level list "Outflows"; likewise parsed and refused here
+        self.outflows = scene.outflows_of(config, self.METHOD, geo.dim)
+        if self.outflows and engine_opts.get("slab"):
+            raise ValueError("Outflows are not available on a sharded scene (--gpus > 1)")
         # The time step stays the scene's.  Past the conventional CFL limit 0.4 spacing / c, c = sqrt((lambda + 2 mu) / rho) the elastic
         # wave speed of the stiffest object, this warns: advice, not a guarantee, and nothing asserts on it.
         self.elastic_dt_limit = None
@@ -224,6 +228,13 @@ class BaseContainer:
             self.engine.set_object(oid, self.material_fluid, 0)
             self.engine.set_emitter(index, F.emitter_program(e))
             self.present_object.append(oid)
+
+        # outflow volumes: set on the device before the first particle (sph_set_outflow wants every listed object known as a fluid
+        # object: an object that enters later is announced here, as its insertion will announce it again)
+        for index, v in enumerate(self.outflows):
+            for oid in v["objects"] or []:
+                self.engine.set_object(oid, self.material_fluid, 0)
+            self.engine.set_outflow(index, F.outflow_program(v))
 
         self.particle_num = _Scalar(lambda: self.engine.particle_num)
         self.fluid_particle_num = _Scalar(lambda: self.engine.fluid_particle_num)

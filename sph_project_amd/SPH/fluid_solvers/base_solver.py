@@ -38,6 +38,20 @@ class EmitterView:
     exhausted = property(lambda self: bool(self._state()["exhausted"]))
 
 
+class OutflowView:
+    """Read-only view of one outflow volume; every attribute is read from sph_get_outflow_state when somebody looks."""
+
+    def __init__(self, engine, index):
+        self._engine, self.index = engine, index
+
+    def _state(self):
+        return self._engine.outflow_state(self.index)
+
+    removed = property(lambda self: self._state()["removed"])
+    removed_last_step = property(lambda self: self._state()["removed_last_step"])
+    active = property(lambda self: bool(self._state()["active"]))
+
+
 class BaseSolver:
     def __init__(self, container: BaseContainer):
         self.container = container
@@ -73,6 +87,7 @@ class BaseSolver:
         self.rigid_solver = PyBulletSolver(container, gravity=self.g, dt=self.dt[None])
         self.engine = container.engine
         self.emitters = [EmitterView(self.engine, k) for k in range(len(getattr(container, "emitters", [])))]
+        self.outflows = [OutflowView(self.engine, k) for k in range(len(getattr(container, "outflows", [])))]
         if self.viscosity_method == "implicit":
             self.cg_tol = 1e-6
 
@@ -160,6 +175,8 @@ class BaseSolver:
         asynchronous = free_running or self.container.params_dict.get("fixed_iterations", 0) > 0
         if asynchronous and os.environ.get("SPH_SYNC_STEPS", "0") not in ("", "0"):
             asynchronous = False   # opt-out: every step() returns only when the device is done, errors surface in the call that caused them
+        if getattr(self, "outflows", None):
+            asynchronous = False   # outflow volumes: the removed count is read back at every slot, sph_step_async refuses
         if asynchronous:
             self.engine.step_async(n)
         else:

@@ -41,3 +41,7 @@ class SimConfig:
     def get_emitters(self):
         """The top-level list "Emitters" (this project's; the reference ignores unknown top-level lists)."""
         return self._list("Emitters")
+
+    def get_outflows(self):
+        """The top-level list "Outflows" (this project's; the reference ignores unknown top-level lists)."""
+        return self._list("Outflows")

@@ -77,6 +77,7 @@ PH_MICROPOLAR = 29
 PH_ELASTIC = 30
 PH_EMIT = 31   # fluid emitters: the hold and the emission of the current step count alone
 PH_DRAG = 32   # air drag: the walk alone (PH_NON_PRESSURE / PH_CG_END then add the stored a_drag)
+PH_OUTFLOW = 33   # outflow: the mark and the count of the current step count alone (no sort)
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
@@ -95,6 +96,7 @@ K_MICROPOLAR = 32            # SPH_K_MICROPOLAR: the gather + walk of the microp
 K_ELASTIC = 33               # SPH_K_ELASTIC: scatter + pass A + pass B of the elastic solids
 K_EMIT = 34                  # SPH_K_EMIT: the hold launch and the emit launch of the fluid emitters
 K_DRAG = 35                  # SPH_K_DRAG: the walk of the air drag
+K_OUTFLOW = 36               # SPH_K_OUTFLOW: the mark launch of the outflow volumes / of a removal by id
 RIGID_MOTION_MAX_KEYS = 64
 MAX_EMITTERS = 8             # SPH_MAX_EMITTERS
 EMITTER_MAX_HOLD = 8         # SPH_EMITTER_MAX_HOLD
@@ -220,6 +222,61 @@ def emitter_eval_host(program, dt, spacing, k, layer=-1, positions=False):
         raise SphError(f"sph_emitter_eval_host failed ({rc}): " + (lib.sph_last_error(None) or b"").decode(), rc)
     d = struct_dict(out, skip=("reserved",))
     return (d, xyz) if positions else d
+
+
+MAX_OUTFLOWS = 8             # SPH_MAX_OUTFLOWS
+OUTFLOW_MAX_OBJECTS = 16     # SPH_OUTFLOW_MAX_OBJECTS
+OUTFLOW_SHAPES = {"box": 0, "sphere": 1}
+
+
+class SphOutflow(C.Structure):
+    """An outflow volume in canonical form (include/sph_hip.h): an axis-aligned box or a sphere, end = +inf for ever."""
+    _fields_ = [
+        ("shape", C.c_int32), ("invert", C.c_int32),
+        ("min", C.c_double * 3), ("max", C.c_double * 3), ("center", C.c_double * 3), ("radius", C.c_double),
+        ("start", C.c_double), ("end", C.c_double),
+        ("n_objects", C.c_int32), ("objects", C.c_int32 * OUTFLOW_MAX_OBJECTS), ("reserved", C.c_int32),
+    ]
+
+
+class SphOutflowState(C.Structure):
+    _fields_ = [("removed", C.c_int64), ("removed_last_step", C.c_int32), ("active", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+def outflow_program(spec):
+    """SphOutflow from a canonical outflow dict (scene.outflows_of)."""
+    v = SphOutflow()
+    v.shape, v.invert = OUTFLOW_SHAPES[spec["shape"]], int(bool(spec["invert"]))
+    v.min[:] = [float(x) for x in spec["min"]]
+    v.max[:] = [float(x) for x in spec["max"]]
+    v.center[:] = [float(x) for x in spec["center"]]
+    v.radius, v.start, v.end = float(spec["radius"]), float(spec["start"]), float(spec["end"])
+    objects = spec.get("objects") or []
+    v.n_objects = len(objects)
+    for k, o in enumerate(objects):
+        v.objects[k] = int(o)
+    return v
+
+
+def outflow_test_host(program, xyz):
+    """The kernels' predicate run on the CPU (sph_outflow_test_host): bool (n,) for float32 positions (n, 3); geometry and invert.
+    No device."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    inside = np.zeros(len(xyz), np.uint8)
+    lib = load()
+    rc = lib.sph_outflow_test_host(C.byref(program), _ptr(xyz) if len(xyz) else None, len(xyz), _ptr(inside) if len(xyz) else None)
+    if rc:
+        raise SphError(f"sph_outflow_test_host failed ({rc}): " + (lib.sph_last_error(None) or b"").decode(), rc)
+    return inside.astype(bool)
+
+
+def outflow_active_host(program, dt, k):
+    """The window test of a volume at step count k (sph_outflow_active_host).  No device."""
+    lib = load()
+    rc = lib.sph_outflow_active_host(C.byref(program), float(dt), int(k))
+    if rc < 0:
+        raise SphError(f"sph_outflow_active_host failed ({rc}): " + (lib.sph_last_error(None) or b"").decode(), rc)
+    return bool(rc)
 
 
 PBF_VARIANTS = {"reference": 0, "consistent": 1}
@@ -616,6 +673,11 @@ _SIGNATURES = [
     ("sph_set_emitter", C.c_int, [_VP, C.c_int, C.POINTER(SphEmitter)]),
     ("sph_get_emitter_state", C.c_int, [_VP, C.c_int, C.POINTER(SphEmitterState)]),
     ("sph_emitter_eval_host", C.c_int, [C.POINTER(SphEmitter), C.c_double, C.c_double, C.c_int64, C.c_int, C.POINTER(SphEmitterEval), _VP]),
+    ("sph_set_outflow", C.c_int, [_VP, C.c_int, C.POINTER(SphOutflow)]),
+    ("sph_get_outflow_state", C.c_int, [_VP, C.c_int, C.POINTER(SphOutflowState)]),
+    ("sph_remove_particles", C.c_int, [_VP, _VP, C.c_int]),
+    ("sph_outflow_test_host", C.c_int, [C.POINTER(SphOutflow), _VP, C.c_int, _VP]),
+    ("sph_outflow_active_host", C.c_int, [C.POINTER(SphOutflow), C.c_double, C.c_int64]),
     ("sph_prepare", C.c_int, [_VP]),
     ("sph_step", C.c_int, [_VP, C.c_int]),
     ("sph_step_async", C.c_int, [_VP, C.c_int]),
@@ -1033,6 +1095,22 @@ class Engine(NativeObject):
         d = struct_dict(st, skip=("reserved", "held_id_base"))
         d["held_id_base"] = [int(x) for x in st.held_id_base[:st.held_layers]]
         return d
+
+    # -- outflow
+    def set_outflow(self, index, program):
+        """Sets (program: SphOutflow) or clears (None) the outflow volume `index`."""
+        self._chk(self.lib.sph_set_outflow(self.h, int(index), C.byref(program) if program is not None else None), "sph_set_outflow")
+
+    def outflow_state(self, index):
+        """dict(removed, removed_last_step, active) of an outflow volume: what the host knows, no device access."""
+        st = SphOutflowState()
+        self._chk(self.lib.sph_get_outflow_state(self.h, int(index), C.byref(st)), "sph_get_outflow_state")
+        return struct_dict(st, skip=("reserved",))
+
+    def remove_particles(self, ids):
+        """Removes the live fluid particles with these persistent ids (sph_remove_particles)."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        self._chk(self.lib.sph_remove_particles(self.h, _ptr(ids) if len(ids) else None, len(ids)), "sph_remove_particles")
 
     # -- device contact solver (the "device_contact" rigid backend)
     def set_rigid_contact_solver(self, on=True, restitution=0.2, friction=0.5, iterations=10, beta=0.2, slop=0.0, patch=0.0):

@@ -32,6 +32,9 @@ struct ElObjHost { int state = 0; double E = 0.0, nu = 0.0; int id0 = 0, n = 0, 
 // so far and the persistent id of each layer's first particle
 struct EmHost { bool on = false; SphEmitter e = {}; int nu = 0, nv = 0, layer_n = 0, max_layers = 0, layers = 0; std::vector<int> base; };
 
+// outflow: one volume as the host keeps it (sph_outflow_api.hpp): the program, what it has removed in all and in the last slot
+struct OfHost { bool on = false; SphOutflow v = {}; long long removed = 0; int last = 0; };
+
 struct SphHandle : ErrSink {
     SphParams prm = {};
     State st;
@@ -102,7 +105,17 @@ struct SphHandle : ErrSink {
     EmHost em[SPH_MAX_EMITTERS];
     int em_n = 0;
     bool em_touch = false;
+    // outflow (sph_set_outflow, sph_remove_particles): of_n of the SPH_MAX_OUTFLOWS slots are set; of_pending: particles that carry the
+    // dead bit and leave with the next sort; of_seen: the device counters as read last; id_next: the id of the next new particle once
+    // something has been removed (until then ids are the append slots: next_id)
+    OfHost of[SPH_MAX_OUTFLOWS];
+    int of_n = 0, of_pending = 0;
+    unsigned of_seen[SPH_MAX_OUTFLOWS] = {}, of_seen_ids = 0;   // (of_seen_ids: the counter of k_outflow_mark_ids)
+    unsigned *of_pinned = nullptr;
+    bool of_removed_any = false;
+    int id_next = 0;
 };
+static inline int next_id(const SphHandle *h);
 static long long em_reserved(const SphHandle *h);
 static int em_of_object(const SphHandle *h, int object_id);
 
@@ -256,6 +269,7 @@ extern "C" void sph_destroy(SphHandle *h) {
     for (void *p : h->allocs) hipFree(p);
     if (h->scal_h) hipHostFree(h->scal_h);
     if (h->loop_pub) hipHostFree((void *)h->loop_pub);
+    if (h->of_pinned) hipHostFree((void *)h->of_pinned);
     if (h->st.list_count_pinned) { hipHostFree((void *)h->st.list_count_pinned); h->st.list_count_pinned = nullptr; }
     if (h->st.list_count_event) { hipEventDestroy(h->st.list_count_event); h->st.list_count_event = nullptr; }
     if (h->st.stream) hipStreamDestroy(h->st.stream);
@@ -390,10 +404,12 @@ extern "C" int sph_append_particles(SphHandle *h, int object_id, int n, const fl
     if (object_id >= 0 && object_id < SPH_NOBJ && h->el[object_id].state == 2)
         return fail(h, SPH_ERR_UNSUPPORTED, "append: object %d is an elastic solid whose rest configuration has been captured", object_id);
     if (h->n + n > h->st.cap) return fail(h, SPH_ERR_CAPACITY, "append: %d + %d exceeds particle_max_num %d", h->n, n, h->st.cap);
+    const int id0 = next_id(h);   // (= h->n until a particle has been removed: outflow)
+    if (id0 + n > h->st.cap) return fail(h, SPH_ERR_CAPACITY, "append: %d particles created so far + %d exceed particle_max_num %d (ids of removed particles are not reused)", id0, n, h->st.cap);
     if (h->em_n > 0) {
         if (em_of_object(h, object_id) >= 0) return fail(h, SPH_ERR_UNSUPPORTED, "append: object %d belongs to emitter %d (an emitter's object takes no other particles)", object_id, em_of_object(h, object_id));
-        if ((long long)h->n + n + em_reserved(h) > (long long)h->st.cap)
-            return fail(h, SPH_ERR_CAPACITY, "append: %d + %d + the emitters' reserved %lld exceed particle_max_num %d", h->n, n, em_reserved(h), h->st.cap);
+        if ((long long)id0 + n + em_reserved(h) > (long long)h->st.cap)
+            return fail(h, SPH_ERR_CAPACITY, "append: %d + %d + the emitters' reserved %lld exceed particle_max_num %d", id0, n, em_reserved(h), h->st.cap);
     }
     HIPCHK(h, hipSetDevice(h->device));
     State &s = h->st;
@@ -411,7 +427,7 @@ extern "C" int sph_append_particles(SphHandle *h, int object_id, int n, const fl
         hv[k] = make_float4(vel[3 * k + ix0], vel[3 * k + ix1], vel[3 * k + ix2], V0 * density[k]);
         hm[k] = META_PACK(object_id, material[k], is_dynamic[k] ? 1 : 0);
         if (h->prepared && material[k] == SPH_MAT_RIGID) { hm[k] |= META_FRESH_BIT; h->fresh_state = 1; }
-        hid[k] = h->n + k;
+        hid[k] = id0 + k;
         unsigned r = color ? (unsigned)(color[3 * k] & 0xff) : 0, g = color ? (unsigned)(color[3 * k + 1] & 0xff) : 0,
                  b = color ? (unsigned)(color[3 * k + 2] & 0xff) : 0;
         hc[k] = r | (g << 8) | (b << 16);
@@ -432,16 +448,17 @@ extern "C" int sph_append_particles(SphHandle *h, int object_id, int n, const fl
     HIPCHK(h, hipMemcpy(s.meta.cur() + off, hm.data(), sizeof(int) * n, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(s.pid.cur() + off, hid.data(), sizeof(int) * n, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(s.color.cur() + off, hc.data(), sizeof(unsigned) * n, hipMemcpyHostToDevice));
-    if (s.color_home) HIPCHK(h, hipMemcpy(s.color_home + off, hc.data(), sizeof(unsigned) * n, hipMemcpyHostToDevice));   // (particle id = append index: hid above)
+    if (s.color_home) HIPCHK(h, hipMemcpy(s.color_home + (size_t)id0, hc.data(), sizeof(unsigned) * n, hipMemcpyHostToDevice));   // (particle id = append index: hid above)
     HIPCHK(h, hipMemcpy(s.rho.cur() + off, hr.data(), sizeof(float) * n, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(s.prs + off, hpr.data(), sizeof(float) * n, hipMemcpyHostToDevice));
     if (s.orig.cur()) HIPCHK(h, hipMemcpy(s.orig.cur() + off, hp.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
     if (object_id >= 0 && object_id < SPH_NOBJ) {   // the id range of the object (ids = append order)
-        if (h->obj_n[object_id] == 0) h->obj_first[object_id] = h->n;
-        else if (h->obj_first[object_id] + h->obj_n[object_id] != h->n) h->obj_split[object_id] = true;
+        if (h->obj_n[object_id] == 0) h->obj_first[object_id] = id0;
+        else if (h->obj_first[object_id] + h->obj_n[object_id] != id0) h->obj_split[object_id] = true;
         h->obj_n[object_id] += n;
     }
     h->n += n;
+    h->id_next = id0 + n;
     h->n_fluid += nfl;
     h->n_nonfluid += n - nfl;
     if (!h->prepared) h->rigid_volume_done = false;   // later arrivals: see fresh_state
@@ -465,6 +482,7 @@ extern "C" int sph_set_appended_ids(SphHandle *h, int n, const int32_t *ids) {
     if (h->st.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: the micropolar model is on (its angular velocities are stored by id, in append order)");
     if (h->st.el_marked) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: an elastic object exists (its rest lists are stored by id, in append order)");
     if (h->em_n > 0) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: an emitter is set (its held layers are found by id, in append order)");
+    if (h->of_n > 0 || h->of_removed_any) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: an outflow volume is set or particles have been removed (new ids come from the library's own counter)");
     h->st.ids_custom = 1;
     HIPCHK(h, hipSetDevice(h->device));
     colors_leave_home(h);
@@ -1194,7 +1212,7 @@ extern "C" int sph_measure_copy_rate(SphHandle *h, size_t bytes, int reps, doubl
 // ---------------------------------------------------------------------------------- phases
 static int check_async(SphHandle *h) {
     if (h->el_rc) { const int rc = h->el_rc; h->el_rc = 0; return rc; }   // (a capture inside this call's neighbour search failed: its message stands)
-    if (h->st.state_error) { const int se = h->st.state_error; h->st.state_error = 0; return fail(h, SPH_ERR_INVALID, "internal state error %d (bit 0: a sort was scanned without a histogram of its own; bit 1: a density launch could not move the arrays its sort left to it)", se); }
+    if (h->st.state_error) { const int se = h->st.state_error; h->st.state_error = 0; return fail(h, SPH_ERR_INVALID, "internal state error %d (bit 0: a sort was scanned without a histogram of its own; bit 1: a density launch could not move the arrays its sort left to it; bit 2: a sort that drops removed particles met a hash made before they were marked)", se); }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, SPH_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     return SPH_OK;
@@ -1209,10 +1227,20 @@ static SortCarry ph_neighbor_search(SphHandle *h, bool rho_dead = false, bool de
     State &s = h->st;
     SortCarry carry;
     const bool capture = s.el_pending && el_capture_due(h);   // (the capture reads meta and ids in sorted order: this sort leaves nothing to the density pass)
+    // outflow: particles that carry the dead bit leave with this sort -- it files them into the graveyard cells behind the grid (the
+    // launchers take a slab rank's route while State::drop_n is set), then the counts shrink
+    const int drop = s.slab_active ? 0 : h->of_pending;
+    s.drop_n = drop;
     { ProfScope p(h, SPH_K_HASH_COUNT); h->L->hash_count(s); }
     { ProfScope p(h, SPH_K_SCAN); h->L->scan(s); }
     { ProfScope p(h, SPH_K_SCATTER); if (h->prm.deterministic) carry = h->L->scatter_stable(s, rho_dead, density_next && !capture && !getenv("SPH_NO_SORT_CARRY")); else h->L->scatter(s); }
     h->sort_dirty = false;
+    if (drop > 0) {
+        s.drop_n = 0;
+        h->n -= drop; h->n_fluid -= drop; h->of_pending = 0;
+        if (h->n_mark > h->n) h->n_mark = h->n;
+        refresh_counts(h);
+    }
     if (capture) { const int rc = el_capture_pending(h); if (rc && !h->el_rc) h->el_rc = rc; }
     return carry;
 }
@@ -1252,6 +1280,7 @@ static void step_begin(SphHandle *h) {
 
 #include "sph_comm_api.hpp"
 #include "sph_emitter_api.hpp"
+#include "sph_outflow_api.hpp"
 #include "sph_steps.hpp"
 
 static int read_scalars(SphHandle *h) {
@@ -1379,7 +1408,7 @@ extern "C" int sph_rigid_integrate(SphHandle *h) {
 static int step_first_half(SphHandle *h) {
     if (h->in_step) return fail(h, SPH_ERR_INVALID, "sph_step_begin: the previous step was not ended");
     step_begin(h);
-    h->em_touch = em_slot_touches(h, (long long)h->steps + 1);
+    h->em_touch = em_slot_touches(h, (long long)h->steps + 1) || h->of_n > 0;   // (outflow: the slot may mark particles dead behind a hash)
     int rc;
     switch (h->prm.method) {
         case SPH_METHOD_WCSPH: rc = wcsph_step(h); break;                     // WCSPH.py:28-36 (:45 boundary fused into the position update)
@@ -1411,7 +1440,8 @@ static int step_second_half(SphHandle *h) {
     }
     // fluid emitters: the insertion point of the step (the reference's insert_object()), behind the rigid integrator / motion launch of
     // the same slot.  k_emit applies the boundary itself; what it adds takes part in the next sort (DFSPH: the one right below)
-    { const int rc = ph_emit(h, (long long)h->steps + 1); h->em_touch = false; if (rc) return rc; }
+    // outflow: between the emitters' hold and their emission -- a newborn particle is first tested one step later
+    { int rc = ph_emit(h, (long long)h->steps + 1, 1); if (!rc) rc = ph_outflow(h, (long long)h->steps + 1); if (!rc) rc = ph_emit(h, (long long)h->steps + 1, 2); h->em_touch = false; if (rc) return rc; }
     // (late entry under sharding: every rank appended the part of the object that lies in its slab, possibly nothing; the
     //  host tells the library the object's whole size through sph_comm_add_global_count -- no collective per step)
     if (h->prm.method == SPH_METHOD_DFSPH) {
@@ -1464,6 +1494,7 @@ extern "C" int sph_step_end(SphHandle *h) {
     HIPCHK(h, hipSetDevice(h->device));
     refresh_counts(h);
     int rc = step_second_half(h); if (rc) return rc;
+    outflow_settle(h);   // (what the slot marked leaves before the call returns; DFSPH's own sort has dropped it already)
     rc = check_async(h); if (rc) return rc;
     return finish_sync(h);
 }
@@ -1476,6 +1507,7 @@ extern "C" int sph_step_async(SphHandle *h, int nsteps) {
         return fail(h, SPH_ERR_UNSUPPORTED, "sph_step_async needs wcsph, pbf or fixed_iterations > 0");
     if (h->prm.method == SPH_METHOD_PBF && h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT && h->prm.fixed_iterations <= 0)
         return fail(h, SPH_ERR_UNSUPPORTED, "sph_step_async: the consistent PBF variant needs fixed_iterations > 0 (its stop test reads back)");
+    if (h->of_n > 0) return fail(h, SPH_ERR_UNSUPPORTED, "sph_step_async: an outflow volume is set (the removed count is read back at every slot: sph_step)");
     HIPCHK(h, hipSetDevice(h->device));
     refresh_counts(h);
     for (int k = 0; k < nsteps; ++k) {
@@ -1500,6 +1532,7 @@ extern "C" int sph_step(SphHandle *h, int nsteps) {
     HIPCHK(h, hipSetDevice(h->device));
     refresh_counts(h);
     for (int k = 0; k < nsteps; ++k) { int rc = step_once(h); if (rc) return rc; }
+    outflow_settle(h);   // (what the last slot marked leaves before the call returns)
     int rc = check_async(h); if (rc) return rc;
     return finish_sync(h);
 }
@@ -1527,6 +1560,10 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
             if (h->em_n <= 0) return fail(h, SPH_ERR_INVALID, "SPH_PH_EMIT: no emitter is set (sph_set_emitter)");
             if (!h->prepared) return fail(h, SPH_ERR_INVALID, "SPH_PH_EMIT before sph_prepare");
             { const int rc = ph_emit(h, (long long)h->steps); if (rc) return rc; }
+            break;
+        case SPH_PH_OUTFLOW:
+            if (h->of_n <= 0) return fail(h, SPH_ERR_INVALID, "SPH_PH_OUTFLOW: no outflow volume is set (sph_set_outflow)");
+            { const int rc = ph_outflow(h, (long long)h->steps); if (rc) return rc; }
             break;
         case SPH_PH_DRAG:
             if (!s.dr_on) return fail(h, SPH_ERR_INVALID, "SPH_PH_DRAG: the air drag is off (sph_set_drag)");
@@ -1830,6 +1867,7 @@ extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes
         if (s.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while the micropolar model is on (its angular velocities are stored by id, in append order)");
         if (s.el_marked) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while an elastic object exists (its rest lists are stored by id, in append order)");
         if (h->em_n > 0) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while an emitter is set (its held layers are found by id, in append order)");
+        if (h->of_n > 0 || h->of_removed_any) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while an outflow volume is set or after particles have been removed (new ids come from the library's own counter)");
         s.ids_custom = 1;
         colors_leave_home(h); HIPCHK(h, hipStreamSynchronize(s.stream));
         HIPCHK(h, hipMemcpy(s.pid.cur(), src, n * 4, hipMemcpyHostToDevice));

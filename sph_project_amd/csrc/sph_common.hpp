@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/sph_hip.h"   // (SphRigidMotion: the program a scripted body's record holds)
+#include <math.h>
+#include "sph_outflow_eval.hpp"      // (OutflowDev: one outflow volume as the mark kernel takes it, by value)
 
 #define SPH_NOBJ 20
 // IISPH.py:12-14: relaxation factor, stop threshold of the average density error, iteration cap
@@ -218,8 +220,13 @@ struct RigidMotionArgs { double dt; long long k; int nbodies; int ids[SPH_NOBJ];
 // spacing / 2); first[q] = slot (= persistent id) of the layer's first particle, start[q] = its offset among the launch's threads.
 // EmitHoldArgs: the held layers, at most SPH_EMITTER_MAX_HOLD per emitter, by the id of their first particle.
 struct EmitterDev { SphEmitter e; int nu, nv, layer_n, max_layers; };
-struct EmitArgs { double spacing; int nlayers, total; int emitter[SPH_MAX_EMITTERS], first[SPH_MAX_EMITTERS], start[SPH_MAX_EMITTERS + 1]; double offset[SPH_MAX_EMITTERS]; };
+struct EmitArgs { double spacing; int nlayers, total; int emitter[SPH_MAX_EMITTERS], first[SPH_MAX_EMITTERS], id_first[SPH_MAX_EMITTERS], start[SPH_MAX_EMITTERS + 1]; double offset[SPH_MAX_EMITTERS]; };
 #define SPH_EMIT_HOLD_ENTRIES (SPH_MAX_EMITTERS * SPH_EMITTER_MAX_HOLD)
+// Outflow (sph_outflow.hpp): the volumes whose window holds the slot's step count, by value, in index order (the lowest index wins);
+// the counters sit SPH_OUTFLOW_CTR_STRIDE unsigned apart (one 128-byte line each: atomics on one line are served one at a time), entry
+// SPH_MAX_OUTFLOWS counts what k_outflow_mark_ids marked.  They only grow: the host keeps what it read last.
+#define SPH_OUTFLOW_CTR_STRIDE 32
+struct OutflowArgs { int nvol; OutflowDev v[SPH_MAX_OUTFLOWS]; };
 struct EmitHoldArgs { double spacing; int nlayers, id_lo, id_hi; int emitter[SPH_EMIT_HOLD_ENTRIES], id_base[SPH_EMIT_HOLD_ENTRIES]; double offset[SPH_EMIT_HOLD_ENTRIES]; };
 
 // Surface reconstruction (sph_surface.hpp): the constants and device buffers of one SphSurface.  Coarse cells (= bricks of
@@ -620,6 +627,12 @@ struct State {
     RigidMotionDev *rigid_motion = nullptr;   // [SPH_NOBJ]
     // fluid emitters (sph_set_emitter; the record array is allocated with the first one)
     EmitterDev *emitters = nullptr;           // [SPH_MAX_EMITTERS]
+    // outflow (sph_set_outflow / sph_remove_particles; allocated with the first use): the counters of the mark kernels, the sorted id list
+    // of a removal by id; drop_n: the COMING sort files that many dead particles into the graveyard cells behind the grid (the route of
+    // a slab rank: hash with the meta words, scan over G + SPH_NGRAVE, run records; no run lists, no tile sums from the hasher)
+    unsigned *outflow_ctr = nullptr;          // [(SPH_MAX_OUTFLOWS + 1) * SPH_OUTFLOW_CTR_STRIDE]
+    int *outflow_ids = nullptr; int outflow_ids_cap = 0;
+    int drop_n = 0;
     // CG (implicit viscosity)
     float4 *cg_p = nullptr, *cg_Ap = nullptr, *cg_x = nullptr, *cg_b = nullptr, *cg_r = nullptr, *cg_v0 = nullptr;
     float4 *cg_p2 = nullptr;   // second search-direction buffer (fused p update: the A p pass reads the old one and writes the new one)
@@ -831,6 +844,9 @@ struct Launch {
     // newborn layers into the slots behind them (the caller raises the counts afterwards)
     void (*emit_hold)(State &, const EmitHoldArgs &);
     void (*emit)(State &, const EmitArgs &);
+    // outflow (sph_outflow.hpp): the dead bit for every active fluid particle inside an active volume / whose id is in the sorted list
+    void (*outflow_mark)(State &, const OutflowArgs &);
+    void (*outflow_mark_ids)(State &, int nids);
     // z-slab sharding
     void (*halo_classify_pack)(State &, int n);
     void (*halo_unpack_append)(State &, int side, int count, int offset);

@@ -35,6 +35,8 @@ extern "C" int sph_set_elastic_object(SphHandle *h, int o, const SphElasticParam
     if (h->st.slab_active || h->comm.slab_ready)
         return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_elastic_object: not on a sharded handle (the rest lists name particles by id across every slab)");
     if (o < 0 || o >= SPH_NOBJ) return fail(h, SPH_ERR_INVALID, "sph_set_elastic_object: unknown object %d", o);
+    if (h->of_n > 0 || h->of_removed_any)
+        return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_elastic_object: object %d: an outflow volume is set or particles have been removed (a rest list names particles that must not leave)", o);
     if (em_of_object(h, o) >= 0)
         return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_elastic_object: object %d belongs to emitter %d (a growing object has no rest configuration)", o, em_of_object(h, o));
     if (!(p->youngs_modulus > 0.0) || !std::isfinite(p->youngs_modulus))

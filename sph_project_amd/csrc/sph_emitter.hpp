@@ -49,7 +49,8 @@ k_emit(const Consts c, const EmitArgs a, const EmitterDev *emitters, const EmitO
     const EmitterDev *d = emitters + a.emitter[q];
     const int idx = t - a.start[q];
     if (idx >= d->layer_n) return;
-    const int slot = a.first[q] + idx;   // = the persistent id: the particle count at the emission + the index within the batch
+    const int slot = a.first[q] + idx;   // the particle count at the emission + the index within the batch
+    const int id = a.id_first[q] + idx;  // the persistent id: equal to the slot until a particle has been removed (outflow)
     double la, lb;
     em_point(&d->e, d->nu, d->nv, a.spacing, idx, &la, &lb);
     float x[3], v[3];
@@ -62,13 +63,13 @@ k_emit(const Consts c, const EmitArgs a, const EmitterDev *emitters, const EmitO
     o.posv[slot] = p;
     o.velm[slot] = u;
     o.meta[slot] = META_PACK(d->e.object_id, SPH_MAT_FLUID, 1);
-    o.pid[slot] = slot;
+    o.pid[slot] = id;
     const unsigned col = (unsigned)(d->e.color[0] & 0xff) | ((unsigned)(d->e.color[1] & 0xff) << 8) | ((unsigned)(d->e.color[2] & 0xff) << 16);
     o.color[slot] = col;
-    if (o.color_home) o.color_home[slot] = col;
+    if (o.color_home) o.color_home[id] = col;
     o.rho[slot] = rho;
     o.prs[slot] = 0.0f;
-    if (o.mp_w_home) o.mp_w_home[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (o.mp_w_home) o.mp_w_home[id] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (o.cg_x) o.cg_x[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 

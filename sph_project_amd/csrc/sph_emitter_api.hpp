@@ -72,7 +72,7 @@ extern "C" int sph_set_emitter(SphHandle *h, int index, const SphEmitter *e) {
     { int rc = emitter_check(h, "sph_set_emitter", index, e, em_dt(h), em_spacing(h), &m.nu, &m.nv, &m.layer_n, &m.max_layers); if (rc) return rc; }
     const EmHost old = h->em[index];
     h->em[index].on = false;
-    const long long need = (long long)h->n + em_reserved(h) + (long long)m.max_layers * m.layer_n;
+    const long long need = (long long)next_id(h) + em_reserved(h) + (long long)m.max_layers * m.layer_n;
     if (need > (long long)h->st.cap) {
         h->em[index] = old;
         return fail(h, SPH_ERR_CAPACITY, "sph_set_emitter: emitter %d: %d particles + the emitters' budgets = %lld exceed particle_max_num %d", index, h->n, need, h->st.cap);
@@ -156,13 +156,14 @@ static bool em_slot_touches(const SphHandle *h, long long k) {
 }
 
 // the slot: hold, then emit, for the step count k the running step ends at (sph_prepare: 0).  No synchronisation, no copy.
-static int ph_emit(SphHandle *h, long long k) {
+// stage 0: both; 1: the hold alone; 2: the emission alone (a step's slot: the outflow mark runs between them)
+static int ph_emit(SphHandle *h, long long k, int stage = 0) {
     if (h->em_n <= 0) return SPH_OK;
     State &s = h->st;
     const double spacing = em_spacing(h);
     EmitHoldArgs ha; EmitArgs ea;
     ha.spacing = ea.spacing = spacing; ha.nlayers = 0; ha.id_lo = 0x7fffffff; ha.id_hi = 0; ea.nlayers = 0; ea.total = 0;
-    int n_new = h->n;
+    int n_new = h->n, id_new = next_id(h);   // slots behind the last particle (dead ones included), ids from the counter
     for (int q = 0; q < SPH_MAX_EMITTERS; ++q) {
         EmHost &m = h->em[q];
         if (!m.on) continue;
@@ -179,25 +180,26 @@ static int ph_emit(SphHandle *h, long long k) {
             // (speed dt <= spacing / 2: one layer per emitter and slot; a caller that skipped slots catches up one layer per slot)
             if ((long long)n_new + m.layer_n > (long long)s.cap) return fail(h, SPH_ERR_CAPACITY, "emitter %d: internal: the reserved capacity is gone (%d + %d > %d)", q, n_new, m.layer_n, s.cap);
             const int j = m.layers;
-            ea.emitter[ea.nlayers] = q; ea.first[ea.nlayers] = n_new; ea.start[ea.nlayers] = ea.total; ea.offset[ea.nlayers] = em_layer_offset(sc.s, j, spacing);
+            ea.emitter[ea.nlayers] = q; ea.first[ea.nlayers] = n_new; ea.id_first[ea.nlayers] = id_new; ea.start[ea.nlayers] = ea.total; ea.offset[ea.nlayers] = em_layer_offset(sc.s, j, spacing);
             ea.nlayers++; ea.total += m.layer_n; ea.start[ea.nlayers] = ea.total;
-            n_new += m.layer_n;
+            n_new += m.layer_n; id_new += m.layer_n;
         }
     }
-    if (ha.nlayers > 0 && h->n > 0) { ProfScope p(h, SPH_K_EMIT); h->L->emit_hold(s, ha); }
-    if (ea.nlayers <= 0) return SPH_OK;
+    if (stage != 2 && ha.nlayers > 0 && h->n > 0) { ProfScope p(h, SPH_K_EMIT); h->L->emit_hold(s, ha); }
+    if (stage == 1 || ea.nlayers <= 0) return SPH_OK;
     { ProfScope p(h, SPH_K_EMIT); h->L->emit(s, ea); }
     // the counts, as sph_append_particles changes them
     for (int t = 0; t < ea.nlayers; ++t) {
         EmHost &m = h->em[ea.emitter[t]];
         const int o = m.e.object_id;
-        if (h->obj_n[o] == 0) h->obj_first[o] = ea.first[t];
-        else if (h->obj_first[o] + h->obj_n[o] != ea.first[t]) h->obj_split[o] = true;
+        if (h->obj_n[o] == 0) h->obj_first[o] = ea.id_first[t];
+        else if (h->obj_first[o] + h->obj_n[o] != ea.id_first[t]) h->obj_split[o] = true;
         h->obj_n[o] += m.layer_n;
-        m.base.push_back(ea.first[t]);
+        m.base.push_back(ea.id_first[t]);
         m.layers++;
     }
     h->n = n_new;
+    h->id_next = id_new;
     h->n_fluid += ea.total;
     if (!h->prepared) h->rigid_volume_done = false;
     if (h->prepared) h->sort_dirty = true;

@@ -33,7 +33,7 @@ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // rank -- there the fold LOSES: the arrivals take one more atomic each in a waiting kernel of 64 workgroups and a thin slab's
 // waves straddle tiles; two ranks on one GPU +1.4 ... +2.3 %, eight ranks +19 %, profiles/r06_two_ranks_scanfold_ab.txt)
 static int *tile_sum_bank(State &s) {
-    if (s.slab_active) return nullptr;
+    if (s.slab_active || s.drop_n > 0) return nullptr;   // (a sort that drops dead particles, State::drop_n: the slab's route)
     return s.scan_partial + (size_t)s.scan_bank * (s.scan_blocks + 1) * SCAN_PARTIAL_STRIDE;
 }
 // the histogram is about to be taken on a cell_count that is not known to be clean: clear it, and the tile sums with it
@@ -46,13 +46,14 @@ static void clear_histogram(State &s) {
 // Unsharded scenes only (a slab's arrivals take their slots one by one, in kernels of their own); SPH_NO_RUN_LISTS=1: never allocated.
 // open_epoch: a new histogram begins (the lists of every earlier one die with their epoch).
 static RunList run_list_of(State &s, bool open_epoch) {
-    if (!s.run_head || s.slab_active) { s.run_lists_filed = 0; return RunList{nullptr, nullptr, 0, 0u}; }
+    if (!s.run_head || s.slab_active || s.drop_n > 0) { s.run_lists_filed = 0; return RunList{nullptr, nullptr, 0, 0u}; }
     if (open_epoch) { if (++s.sort_epoch == 0u) s.sort_epoch = 1u; }
     return RunList{s.run_head, s.run_rec, s.cap, s.sort_epoch};
 }
 
 void l_hash_count(State &s) {
     const int n = s.c.n;
+    if (s.prehashed && s.drop_n > 0) s.state_error |= 4;   // (a hash made before the dead were marked: the host drops it when it marks)
     if (s.prehashed) {   // the last step's force pass has hashed for this sort (NextHash): cell ids, histogram and ranks are in place
         s.prehashed = 0;
         s.cell_count_clean = 0;
@@ -69,7 +70,7 @@ void l_hash_count(State &s) {
     s.n_hash_launches++;
     const RunList rl = run_list_of(s, true);
     hipLaunchKernelGGL(k_hash_count, dim3(cdiv(n, 256)), dim3(256), 0, s.stream, s.c, s.posv.cur(), s.cellid,
-                       s.rank, s.cell_count, s.slab_active ? s.meta.cur() : nullptr, ts, rl);
+                       s.rank, s.cell_count, (s.slab_active || s.drop_n > 0) ? s.meta.cur() : nullptr, ts, rl);
     s.run_lists_filed = rl.head != nullptr;
 }
 
@@ -78,7 +79,8 @@ void l_scan(State &s) {
     // the slab kernels.  Anything else is a bug in the step orchestration; the sort would file every particle into cell 0.
     if (!s.hist_taken) s.state_error |= 1;
     s.hist_taken = 0;
-    const int G = s.c.G + (s.slab_active ? SPH_NGRAVE : 0);   // + graveyard cells
+    const bool grave = s.slab_active || s.drop_n > 0;
+    const int G = s.c.G + (grave ? SPH_NGRAVE : 0);   // + graveyard cells
     int nb = cdiv(G, SCAN_TILE);                      // <= s.scan_blocks (sized for the global grid)
     if (nb < SPH_STAT_SLOTS / SCAN_TPB) nb = SPH_STAT_SLOTS / SCAN_TPB;   // k_scan_final also clears the statistics slots
     int *part = s.scan_partial + (size_t)s.scan_bank * (s.scan_blocks + 1) * SCAN_PARTIAL_STRIDE;
@@ -87,7 +89,9 @@ void l_scan(State &s) {
     if (!s.tile_sums_ready) hipLaunchKernelGGL(k_scan_reduce, dim3(nb), dim3(SCAN_TPB), 0, s.stream, s.cell_count, G, part);
     hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(SCAN_TPB), 0, s.stream, s.cell_count, G, part,
                        s.cell_start, s.c.n, s.scal, 1 - s.c.stat_bank, s.c.n_dev, part_next,
-                       s.slab_active ? nullptr : s.scan_tile_state);   // (a slab's grid moves with its cuts: every tile scanned)
+                       grave ? nullptr : s.scan_tile_state);   // (a slab's grid moves with its cuts: every tile scanned)
+    // a graveyard scan of an unsharded scene rewrote every tile behind the back of the empty-tile states: they all read "a real scan"
+    if (grave && !s.slab_active) hipMemsetAsync(s.scan_tile_state, 0, sizeof(int) * ((size_t)s.scan_blocks + 1), s.stream);
     s.cell_count_clean = 1;   // ... and so is the bank of tile sums the next histogram adds to
     s.scan_bank = 1 - s.scan_bank;
     s.tile_sums_ready = 0;
@@ -201,6 +205,7 @@ SortCarry l_scatter_impl(State &s, bool stable, bool rho_dead, bool density_next
     }
 #endif
     s.masks_valid = 0;  // new order, new candidate runs
+    if (!s.slab_active && s.drop_n > 0) s.c.n = n - s.drop_n;   // the dead sit behind the live particles now: the tiles are prepared for the live ones
     if (!s.slab_active) l_block_prep(s, !by_lists);
     else s.perm_n = s.list_n = -1;   // slab sharding: rebuilt once the dead particles behind the live ones are dropped (launch_pass)
     if (s.orig.cur()) s.orig.flip();
@@ -540,6 +545,7 @@ void l_clear_fresh(State &s) {
 #include "sph_contact_solve.hpp"
 #include "sph_rigid_motion.hpp"
 #include "sph_emitter.hpp"
+#include "sph_outflow.hpp"
 #include "sph_surface.hpp"
 #include "sph_surface_aniso.hpp"
 #include "sph_elastic.hpp"
@@ -589,6 +595,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_contact_solve_launchers(L);
         register_rigid_motion_launchers(L);
         register_emitter_launchers(L);
+        register_outflow_launchers(L);
         register_surface_launchers(L);
         register_surface_aniso_launchers(L);
         register_surface_post_launchers(L);

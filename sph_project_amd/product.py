@@ -354,6 +354,38 @@ def faucet_scene(nozzle=(6, 6), speed=1.0, hold=2, basin=0, method="wcsph", radi
     return cfg
 
 
+def channel_scene(nozzle=(6, 6), speed=2.0, length=40, method="wcsph", radius=0.01, dt=4e-4, side=None, hold=2, max_layers=None,
+                  kill=3, viscosity=0.01, gravity=9.81, **keys):
+    """The first scene of the outflow volumes: a closed sampled box of length x side x side particle diameters (side:
+    the nozzle's larger edge + 12 unless given) with a nozzle of nozzle[0] x nozzle[1] lattice points at its x = 0 end, pointing along
+    +x at `speed` m / s, and a kill box `kill` diameters thick across the whole cross-section in front of the far wall.  The emitter is
+    object 0 (budget: max_layers layers, 4 * length unless given).  keys: further Configuration keys."""
+    d = 2.0 * radius
+    floor = 4 * d                      # first lattice plane inside the box's shell
+    if side is None:
+        side = max(int(nozzle[0]), int(nozzle[1])) + 12
+    if max_layers is None:
+        max_layers = 4 * int(length)
+    L, w = length * d, side * d
+    emitter = {"objectId": 0, "shape": "rectangle", "position": [floor + 2 * d, 0.5 * w, 0.5 * w], "direction": [1.0, 0.0, 0.0],
+               "up": [0.0, 1.0, 0.0], "width": (nozzle[0] + 0.5) * d, "height": (nozzle[1] + 0.5) * d,
+               "speed": float(speed), "start": 0.0, "end": None, "hold": int(hold), "density": 1000.0, "color": [50, 100, 200],
+               "maxParticles": int(max_layers) * int(nozzle[0]) * int(nozzle[1])}
+    cfg = {
+        "Configuration": {
+            "domainStart": [0.0, 0.0, 0.0], "domainEnd": [L, w, w], "addDomainBox": True, "particleRadius": radius,
+            "density0": 1000, "simulationMethod": method, "viscosityMethod": "standard", "gravitation": [0.0, -float(gravity), 0.0],
+            "timeStepSize": dt, "viscosity": viscosity,
+        },
+        "FluidBlocks": [],
+        "Emitters": [emitter],
+        "Outflows": [{"shape": "box", "min": [L - floor - kill * d, 0.0, 0.0], "max": [L, w, w], "invert": False, "start": 0.0,
+                      "end": None, "objects": None}],
+    }
+    cfg["Configuration"].update(keys)
+    return cfg
+
+
 def wind_jet_scene(nozzle=(4, 4), speed=3.0, wind=(5.0, 0.0, 0.0), drag=1.0, method="wcsph", side=20, height=36, max_layers=24,
                    drag_method="gissler", **keys):
     """The first scene of the air drag: faucet_scene's downward nozzle (nozzle[0] x nozzle[1] lattice points, `speed`

@@ -290,6 +290,9 @@ def check_sharded_args(parser, args):
     if config.get_emitters():
         parser.error(f"--gpus {n}: the scene has Emitters: fluid emitters are not sharded (their schedule knows one particle count; "
                      "sph_set_emitter refuses a slab); run it with --gpus 1")
+    if config.get_outflows():
+        parser.error(f"--gpus {n}: the scene has Outflows: outflow volumes are not sharded (a slab rank's graveyard cells are its halo "
+                     "exchange's; sph_set_outflow refuses a slab); run it with --gpus 1")
     from sph_project_amd import launch
     try:
         launch.plan_scene_cuts(config.config, n)
