@@ -782,6 +782,32 @@ int sph_get_stats(SphHandle *h, SphStats *out);
    device, out[0..2].  A query of its own rather than SphStats fields: the statistics struct ends at pbf_recentred by contract. */
 int sph_get_cg_scalars(SphHandle *h, float *out);
 
+/* The tables of the uniform grid as the last sort left them on the device (for tests and diagnosis).
+   sph_download_grid_table waits for the stream and copies; sph_get_grid_layout reads what the host knows (an unsharded handle's counts
+   are exact on the host).  Neither launches anything nor changes a state flag, so a step behaves the same whether or not they were
+   called.  All of it is in the LIBRARY's frame: library axis k is scene axis axis_map[k], library x is the slowest axis of the
+   cell order, lin = (cx * ny + cy) * nz + cz.  SPH_ERR_UNSUPPORTED on a sharded handle (sph_comm_set_slab: a slab's grid is local).
+   SPH_ERR_INVALID: a NULL argument, an unknown table, bytes that differ from the table's size. */
+typedef struct {
+    int32_t nx, ny, nz;        /* cells per library axis */
+    int32_t G;                 /* nx * ny * nz */
+    int32_t scan_tile;         /* cells per tile of the prefix scan (2048) */
+    int32_t axis_map[3];       /* scene axis of each library axis */
+    float cell_size;           /* edge of a cell = the support radius, as the kernels divide by it */
+    int32_t n;                 /* live particles */
+    int32_t tiles;             /* tiles of 256 consecutive particle slots: ceil(n / 256) */
+    int32_t tile_header_ints;  /* ints per tile header (20): first cell, last cell, 9 run starts, 9 run lengths */
+    int32_t tiles_valid;       /* 1: tile headers, lane permutation and cell words were built for the current order of these n particles */
+} SphGridLayout;
+typedef enum {
+    SPH_GRID_CELL_START = 0,   /* i32[G + 1]: exclusive prefix sum of the cell populations, [G] = n */
+    SPH_GRID_TILE_HEADER = 1,  /* i32[tiles][tile_header_ints] */
+    SPH_GRID_LANE_PERM = 2,    /* u8[tiles][256]: lane -> slot inside the tile */
+    SPH_GRID_CELL_WORD = 3     /* u32[n]: per particle, bits 0-7 window entry of (.., .., z0), 8-10 z1 - z0 + 1, 11-19 column-exists bits */
+} SphGridTable;
+int sph_get_grid_layout(SphHandle *h, SphGridLayout *out);
+int sph_download_grid_table(SphHandle *h, int which, void *dst, size_t bytes);
+
 /* --- profiling (HIP events on the compute stream) -------------------------------------- */
 /* record a HIP event pair around every launch of `kernel_id` (-1: all kernels); accumulates. */
 int sph_profile_enable(SphHandle *h, int kernel_id, int on);

@@ -135,6 +135,18 @@ class SphStats(C.Structure):
     ]
 
 
+class SphGridLayout(C.Structure):
+    """The uniform grid in the library's frame and the sizes of its device tables (include/sph_hip.h)."""
+    _fields_ = [
+        ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("G", C.c_int32), ("scan_tile", C.c_int32),
+        ("axis_map", C.c_int32 * 3), ("cell_size", C.c_float), ("n", C.c_int32), ("tiles", C.c_int32),
+        ("tile_header_ints", C.c_int32), ("tiles_valid", C.c_int32),
+    ]
+
+
+GRID_CELL_START, GRID_TILE_HEADER, GRID_LANE_PERM, GRID_CELL_WORD = 0, 1, 2, 3   # SphGridTable
+
+
 class SphRigidMotion(C.Structure):
     """A scripted body's program in canonical form (include/sph_hip.h): radians, unit-or-zero vectors, end = +inf for never."""
     _fields_ = [
@@ -803,6 +815,8 @@ _SIGNATURES = [
     ("sph_render_set_surface_foam", C.c_int, [_VP, _VP, C.POINTER(SphRenderSurfaceFoamParams)]),
     ("sph_render_surface_download_foam", C.c_int, [_VP, C.c_int, _VP]),
     ("sph_render_surface_foam_stats", C.c_int, [_VP, C.POINTER(SphRenderSurfaceFoamStats)]),
+    ("sph_get_grid_layout", C.c_int, [_VP, C.POINTER(SphGridLayout)]),
+    ("sph_download_grid_table", C.c_int, [_VP, C.c_int, _VP, C.c_size_t]),
     ("sph_comm_allreduce", C.c_int, [_VP, C.POINTER(C.c_double), C.c_int, C.c_int]),
     ("sph_comm_barrier", C.c_int, [_VP]),
     ("sph_comm_selftest", C.c_int, [_VP, C.c_int]),
@@ -1177,6 +1191,24 @@ class Engine(NativeObject):
         st = SphStats()
         self._chk(self.lib.sph_get_stats(self.h, C.byref(st)), "sph_get_stats")
         return struct_dict(st)
+
+    def grid_layout(self):
+        """The grid in the library's frame and the sizes of its tables, as a dict (axis_map: a tuple)."""
+        lay = SphGridLayout()
+        self._chk(self.lib.sph_get_grid_layout(self.h, C.byref(lay)), "sph_get_grid_layout")
+        d = struct_dict(lay)
+        d["axis_map"] = tuple(lay.axis_map)
+        return d
+
+    def download_grid_table(self, which, layout=None):
+        """One table of the last sort (GRID_*), read only: cell_start i32[G + 1], tile headers i32[tiles][20], lane permutation
+        u8[tiles][256], cell words u32[n]."""
+        lay = layout or self.grid_layout()
+        shape, dtype = {GRID_CELL_START: ((lay["G"] + 1,), np.int32), GRID_TILE_HEADER: ((lay["tiles"], lay["tile_header_ints"]), np.int32),
+                        GRID_LANE_PERM: ((lay["tiles"], 256), np.uint8), GRID_CELL_WORD: ((lay["n"],), np.uint32)}[which]
+        out = np.empty(shape, dtype)
+        self._chk(self.lib.sph_download_grid_table(self.h, int(which), out.ctypes.data_as(C.c_void_p), out.nbytes), f"sph_download_grid_table({which})")
+        return out
 
     def cg_scalars(self):
         """(alpha, beta, error) of the implicit-viscosity solve as the last launch left them on the device, f32"""

@@ -1810,6 +1810,44 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
     return fail(h, SPH_ERR_INVALID, "download: unknown field %d", field);
 }
 
+// The grid tables of the last sort, read only (include/sph_hip.h): no launch, no state flag touched -- in particular not l_sorted_color's.
+extern "C" int sph_get_grid_layout(SphHandle *h, SphGridLayout *out) {
+    if (!h || !out) return SPH_ERR_INVALID;
+    if (h->st.slab_active) return fail(h, SPH_ERR_UNSUPPORTED, "get_grid_layout: a sharded handle (a slab's grid is local)");
+    const State &s = h->st;
+    memset(out, 0, sizeof(*out));
+    out->nx = s.c.nx; out->ny = s.c.ny; out->nz = s.c.nz; out->G = s.c.G;
+    out->scan_tile = 2048;   // (SCAN_TILE, sph_device.hpp; sph_create sizes scan_blocks by the same number)
+    for (int k = 0; k < 3; ++k) out->axis_map[k] = h->perm[k];
+    out->cell_size = s.c.grid_size;
+    out->n = h->n;
+    out->tiles = (h->n + 255) / 256;
+    out->tile_header_ints = 20;   // (BLK_HDR_INTS, sph_device.hpp; sph_create sizes blk_hdr by the same number)
+    out->tiles_valid = (s.perm_n == h->n && h->n > 0) ? 1 : 0;
+    return SPH_OK;
+}
+
+extern "C" int sph_download_grid_table(SphHandle *h, int which, void *dst, size_t bytes) {
+    if (!h || !dst) return SPH_ERR_INVALID;
+    if (h->st.slab_active) return fail(h, SPH_ERR_UNSUPPORTED, "download_grid_table: a sharded handle (a slab's grid is local)");
+    HIPCHK(h, hipSetDevice(h->device));
+    const State &s = h->st;
+    const size_t n = (size_t)h->n, tiles = (n + 255) / 256, tiles_cap = ((size_t)s.cap + 255) / 256;
+    const void *src = nullptr;
+    size_t want = 0;
+    switch (which) {
+        case SPH_GRID_CELL_START: src = s.cell_start; want = ((size_t)s.c.G + 1) * sizeof(int); break;
+        case SPH_GRID_TILE_HEADER: src = s.blk_hdr; want = tiles * 20 * sizeof(int); break;
+        case SPH_GRID_LANE_PERM: src = s.lane_perm; want = tiles * 256; break;
+        case SPH_GRID_CELL_WORD: src = s.blk_hdr + tiles_cap * 20; want = n * sizeof(unsigned); break;   // behind the headers of all tiles (l_block_prep)
+        default: return fail(h, SPH_ERR_INVALID, "download_grid_table: unknown table %d", which);
+    }
+    if (bytes != want) return fail(h, SPH_ERR_INVALID, "download_grid_table: table %d needs %zu bytes, got %zu", which, want, bytes);
+    HIPCHK(h, hipStreamSynchronize(s.stream));
+    if (want) HIPCHK(h, hipMemcpy(dst, src, want, hipMemcpyDeviceToHost));
+    return SPH_OK;
+}
+
 extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes) {
     if (!h || !src) return SPH_ERR_INVALID;
     HIPCHK(h, hipSetDevice(h->device));

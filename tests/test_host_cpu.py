@@ -36,7 +36,8 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_struct_layout_matches_header(tmp_path):
-    """ctypes mirrors of SphParams / SphStats have the size and field offsets the C compiler gives the header."""
+    """ctypes mirrors of SphParams / SphStats / SphGridLayout have the size and field offsets the C compiler gives the header, and the
+    table ids are the header's."""
     import subprocess
     src = tmp_path / "layout.c"
     src.write_text('''#include <stdio.h>
@@ -46,13 +47,19 @@ int main(void) {
   printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(SphParams), offsetof(SphParams, grid_num), offsetof(SphParams, gravity),
          offsetof(SphParams, dt), offsetof(SphParams, particle_max_num), offsetof(SphParams, deterministic), sizeof(SphStats));
   printf("%zu %zu\\n", offsetof(SphStats, err_divergence), offsetof(SphStats, total_time));
+  printf("%zu %zu %zu %zu %zu\\n", sizeof(SphGridLayout), offsetof(SphGridLayout, scan_tile), offsetof(SphGridLayout, axis_map),
+         offsetof(SphGridLayout, cell_size), offsetof(SphGridLayout, tiles_valid));
+  printf("%d %d %d %d\\n", SPH_GRID_CELL_START, SPH_GRID_TILE_HEADER, SPH_GRID_LANE_PERM, SPH_GRID_CELL_WORD);
   return 0; }''')
     exe = tmp_path / "layout"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
     out = subprocess.check_output([str(exe)]).decode().split()
     got = [ctypes.sizeof(L.SphParams), L.SphParams.grid_num.offset, L.SphParams.gravity.offset, L.SphParams.dt.offset,
            L.SphParams.particle_max_num.offset, L.SphParams.deterministic.offset, ctypes.sizeof(L.SphStats),
-           L.SphStats.err_divergence.offset, L.SphStats.total_time.offset]
+           L.SphStats.err_divergence.offset, L.SphStats.total_time.offset,
+           ctypes.sizeof(L.SphGridLayout), L.SphGridLayout.scan_tile.offset, L.SphGridLayout.axis_map.offset,
+           L.SphGridLayout.cell_size.offset, L.SphGridLayout.tiles_valid.offset,
+           L.GRID_CELL_START, L.GRID_TILE_HEADER, L.GRID_LANE_PERM, L.GRID_CELL_WORD]
     assert [int(x) for x in out] == got
 
 
