@@ -241,6 +241,10 @@ typedef enum {
        active fluid particle inside a volume whose time window holds T_steps gets its dead bit, the per-volume counters are read back.  No
        sort: the particle count shrinks in the next SPH_PH_NEIGHBOR_SEARCH (or step). */
     SPH_PH_OUTFLOW = 33,
+    /* Adaptive time stepping (sph_set_cfl; SPH_ERR_INVALID while the mode is off): the reduce alone -- the maximum of |v|^2 over the
+       particles that count is read back into SphTimeState::vmax2; the step size does not change.  A non-finite square:
+       SPH_ERR_INVALID ("non-finite velocity"). */
+    SPH_PH_CFL = 34,
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -292,6 +296,7 @@ typedef enum {
     SPH_K_EMIT = 34,            /* fluid emitters: the hold launch and the emit launch (sph_set_emitter); "?" as well */
     SPH_K_DRAG = 35,            /* air drag: the walk (v += dt a_drag: SPH_K_MISC); "?" as well */
     SPH_K_OUTFLOW = 36,         /* outflow: the mark launch (by volume, or by id for sph_remove_particles); "?" as well */
+    SPH_K_CFL = 37,             /* adaptive time stepping: the reduce of the largest speed (sph_set_cfl); "?" as well */
     SPH_K_COUNT_
 } SphKernelId;
 
@@ -746,6 +751,72 @@ int sph_get_outflow_state(SphHandle *h, int index, SphOutflowState *out);
 int sph_remove_particles(SphHandle *h, const int32_t *ids, int n);
 int sph_outflow_test_host(const SphOutflow *volume, const float *xyz, int n, uint8_t *inside);
 int sph_outflow_active_host(const SphOutflow *volume, double dt, int64_t k);
+
+/* Adaptive time stepping (opt-in; the scene keys cflMethod / cflFactor / cflMinTimeStepSize / cflMaxTimeStepSize): the
+   device finds the largest particle speed at the end of every step and the library sets the next step's dt from it.
+     who counts: active fluid particles that have not been removed, and the rigid particles of dynamic bodies (their stored velocity is
+               v + w x r).  Static rigid particles, ghosts and the dead do not.
+     speed:    float32, (vx vx + vy vy) + vz vz with every product and sum rounded: the same bits in the strict and the fast build.  ONE
+               elementwise launch (k_cfl_speed, profiled as SPH_K_CFL) reduces it: a maximum per thread, across the 64 lanes of a wave,
+               one atomic maximum per wave on the bit pattern; the host reads the maximum and a non-finite flag back once per step (one
+               small copy into pinned memory and one stream wait).
+     rule:     in double, d = 2 particle_radius, v = sqrt(vmax2):
+                   dt = v max_dt > factor 0.4 d ? factor 0.4 d / v : max_dt;   dt = max(dt, min_dt);
+                   with a time target: n = ceil(remaining / dt), dt = remaining / n;   dt = (double)(float)dt
+               The landing step is never above the CFL step and, while the target is at least one CFL step away, never below half of it.
+     slot:     the end of a step, behind everything that changes a velocity, before the scene time advances.  The first step size comes
+               from a reduce in sph_prepare (or in sph_set_cfl on a prepared handle).  Particles appended and fields uploaded since the
+               last reduce make the next step begin with one.
+     time:     the scene time is the double sum of the float32 steps taken.  A target counts as reached when t_end - t <= 2^-20 max_dt.
+   A non-finite square is SPH_ERR_INVALID ("non-finite velocity") from the call that stepped; the step size stays what it was.
+   While the mode is on sph_step_async returns SPH_ERR_UNSUPPORTED (the maximum needs the host); sph_step(h, n) and the sph_step_begin /
+   sph_step_end pair work.  A velocity criterion knows nothing of a sound speed: under WCSPH max_dt has to stay at the stiff limit.
+   sph_set_time_step: a new step size between steps (SPH_ERR_INVALID inside one, and for a dt that is not positive and finite as a
+   float32).  SPH_ERR_UNSUPPORTED while the CFL mode is on, and on every handle the mode refuses (below).
+   sph_set_cfl: params == NULL or method SPH_CFL_NONE switches the mode off and restores the step size the handle was created with.
+   SPH_ERR_INVALID, naming the field: an unknown method, a number that is not positive and finite, min_dt > max_dt.
+   SPH_ERR_UNSUPPORTED, with the reason: an emitter, a motion program or an outflow volume is set (their programs are closed forms of
+   k dt; and sph_set_emitter / sph_set_rigid_motion / sph_set_outflow while the mode is on), a PBF handle (either variant), a sharded
+   handle (and sph_comm_set_slab while the mode is on), g_upper set (its frozen particles carry the rigid material).
+   sph_get_cfl: the parameters (method SPH_CFL_NONE while the mode is off).
+   sph_get_time_state: what the host knows (no device access).
+   sph_set_time_target: the step sizes from now on land on t_end; a value that is not finite clears the target.  The pending dt is
+   computed again from the stored maximum (host arithmetic only).  SPH_ERR_INVALID while the mode is off.
+   sph_advance_until: sets the target, steps until it is reached or max_steps steps are done (SPH_OK both ways; steps_done says how
+   many), then clears the target and restores the pending dt.
+   sph_cfl_dt_host: the rule on the CPU (the same source).  remaining: not finite = no target.  sph_cfl_speed2_host: the reduce on the
+   CPU (the same source) over vel[n][3]; meta[i]: material << 8 | (is_dynamic ? 1 << 10 : 0) | (ghost ? 1 << 11 : 0) | (removed ?
+   1 << 12 : 0), the library's particle word.  No device is touched. */
+#define SPH_CFL_NONE 0
+#define SPH_CFL_VELOCITY 1
+#define SPH_CFL_CLAMPED_MAX 1          /* SphTimeState::flags: the step is max_dt */
+#define SPH_CFL_CLAMPED_MIN 2          /* ... is min_dt */
+#define SPH_CFL_LANDING 4              /* ... was shortened to land on the time target */
+#define SPH_CFL_STALE 8                /* ... will be computed again: the next step begins with a reduce */
+typedef struct {
+    int32_t method;                    /* SPH_CFL_NONE, SPH_CFL_VELOCITY */
+    int32_t reserved;                  /* 0 */
+    double factor;                     /* cflFactor */
+    double min_dt, max_dt;             /* cflMinTimeStepSize, cflMaxTimeStepSize, seconds */
+} SphCflParams;
+typedef struct {
+    double time;                       /* scene time, seconds */
+    double dt_next;                    /* the step size the next step takes */
+    double dt_last;                    /* ... the last step took (0 before the first) */
+    double target;                     /* the time target (NaN: none) */
+    float vmax2;                       /* the maximum of |v|^2 the last reduce found */
+    int32_t flags;                     /* SPH_CFL_* of dt_next */
+    int64_t steps;
+    int32_t reserved[4];
+} SphTimeState;
+int sph_set_time_step(SphHandle *h, double dt);
+int sph_set_cfl(SphHandle *h, const SphCflParams *params);
+int sph_get_cfl(SphHandle *h, SphCflParams *out);
+int sph_get_time_state(SphHandle *h, SphTimeState *out);
+int sph_set_time_target(SphHandle *h, double t_end);
+int sph_advance_until(SphHandle *h, double t_end, int max_steps, int *steps_done);
+int sph_cfl_dt_host(const SphCflParams *params, double diameter, float vmax2, double remaining, double *dt, int32_t *flags);
+int sph_cfl_speed2_host(int64_t n, const float *vel, const int32_t *meta, float *vmax2, int32_t *nonfinite);
 
 /* --- time stepping --------------------------------------------------------------------- */
 /* replaces XSolver.prepare() (base_solver.py:683, DFSPH.py:321, PCISPH.py:188); particles of

@@ -115,6 +115,20 @@ class BaseContainer:
                 if dt > limit:
                     warnings.warn(f"object {entry['objectId']}: timeStepSize {dt:g} exceeds the elastic limit {limit:g} "
                                   "(0.4 * particle spacing / sqrt((lambda + 2 mu) / density)); the elastic object may be unstable")
+        # adaptive time stepping: likewise parsed and refused here.  With elastic objects the effective maximum is
+        # min(cflMaxTimeStepSize, elastic_dt_limit)
+        self.cfl_method, self.cfl_factor, self.cfl_min_time_step, self.cfl_max_time_step = scene.cfl_of(config, self.METHOD, geo.dim)
+        if self.cfl_method == "velocity":
+            if engine_opts.get("slab"):
+                raise ValueError("Configuration.cflMethod \"velocity\" is not available on a sharded scene (--gpus > 1)")
+            backend = engine_opts.get("rigid_backend") or os.environ.get("SPH_RIGID_BACKEND", "native")
+            if backend == "pybullet" and config.get_rigid_bodies():
+                raise ValueError("Configuration.cflMethod \"velocity\" is not available with the pybullet rigid backend (its world keeps one step size)")
+            if self.elastic_dt_limit is not None and self.elastic_dt_limit < self.cfl_max_time_step:
+                warnings.warn(f"cflMaxTimeStepSize {self.cfl_max_time_step:g} exceeds the elastic limit {self.elastic_dt_limit:g}: the "
+                              "effective maximum step is the elastic limit")
+                self.cfl_max_time_step = self.elastic_dt_limit
+                self.cfl_min_time_step = min(self.cfl_min_time_step, self.cfl_max_time_step)
         self.material_rigid, self.material_fluid = scene.MATERIAL_RIGID, scene.MATERIAL_FLUID
         self.dx, self.particle_diameter, self.dh = geo.dx, geo.particle_diameter, geo.dh
         self.particle_spacing, self.V0 = geo.particle_spacing, geo.V0
@@ -202,6 +216,8 @@ class BaseContainer:
             self.engine.set_micropolar("micropolar", self.vorticity, self.viscosity_omega, self.inertia_inverse)
         if self.drag_method == "gissler":
             self.engine.set_drag("gissler", self.drag, self.air_density, self.air_velocity)
+        if self.cfl_method == "velocity":
+            self.engine.set_cfl("velocity", self.cfl_factor, self.cfl_min_time_step, self.cfl_max_time_step)
         # multi-GPU: engine_opts["slab"] = dict(rank=, nranks=, unique_id=<128 bytes>, cuts=[...]) -> this container
         # only inserts the particles of its own z-slab (sph_project_amd/slab.py)
         self.slab = engine_opts.get("slab")

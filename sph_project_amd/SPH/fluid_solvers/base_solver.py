@@ -83,6 +83,12 @@ class BaseSolver:
         # elastic solids: {object id: (E, nu)} of the scene's elastic objects
         self.elastic_objects = dict(getattr(container, "elastic_objects", {}))
         self.elastic_dt_limit = getattr(container, "elastic_dt_limit", None)   # 0.4 spacing / c of the stiffest object (advice), or None
+        # adaptive time stepping: "none", or "velocity" with cflFactor and the clamps; while it is on, dt[None] and the
+        # total_time of container and rigid solver are the library's (_sync_time)
+        self.cfl_method = getattr(container, "cfl_method", "none")
+        self.cfl_factor = getattr(container, "cfl_factor", 0.5)
+        self.cfl_min_time_step = getattr(container, "cfl_min_time_step", 0.0)
+        self.cfl_max_time_step = getattr(container, "cfl_max_time_step", 0.0)
         self.dt = _DtField(sol.dt)
         self.rigid_solver = PyBulletSolver(container, gravity=self.g, dt=self.dt[None])
         self.engine = container.engine
@@ -107,6 +113,19 @@ class BaseSolver:
         self.container.insert_object()
         self.rigid_solver.insert_rigid_object()
         self.engine.prepare()
+        self._sync_time()
+
+    def _adaptive(self):
+        return getattr(self, "cfl_method", "none") == "velocity"
+
+    def _sync_time(self):
+        """Adaptive time stepping: the step size and the scene time are the library's."""
+        if not self._adaptive():
+            return
+        st = self.engine.time_state()
+        self.dt._v = st["dt_next"]
+        self.container.total_time = st["time"]
+        self.rigid_solver.total_time = st["time"]
 
     def _step(self):
         """WCSPH.py:27 / DFSPH.py:298 / PCISPH.py:165: the device runs _step() up to the point where the reference
@@ -114,6 +133,9 @@ class BaseSolver:
         has come (base_container.py:218-221) exactly where the reference does; the device finishes the step
         (renew_rigid_particle_state, boundary, DFSPH's neighbour search + density + alpha + divergence solve)."""
         self.engine.step_begin()
+        if self._adaptive():   # the host rigid backends take the running step's size (a stale maximum may just have changed it)
+            self.dt._v = self.engine.time_state()["dt_next"]
+            self.rigid_solver.set_dt(self.dt[None])
         self.container.in_step = True   # what enters now enters at the time this step ends at (scripted bodies: motion.py)
         try:
             self.rigid_solver.step()
@@ -175,6 +197,8 @@ class BaseSolver:
         asynchronous = free_running or self.container.params_dict.get("fixed_iterations", 0) > 0
         if asynchronous and os.environ.get("SPH_SYNC_STEPS", "0") not in ("", "0"):
             asynchronous = False   # opt-out: every step() returns only when the device is done, errors surface in the call that caused them
+        if self._adaptive():
+            asynchronous = False   # adaptive time stepping: the largest speed is read back at every step, sph_step_async refuses
         if getattr(self, "outflows", None):
             asynchronous = False   # outflow volumes: the removed count is read back at every slot, sph_step_async refuses
         if asynchronous:
@@ -195,6 +219,34 @@ class BaseSolver:
         self.container.total_time += self.dt[None]
         self.rigid_solver.total_time += self.dt[None]
         self._count_step()
+        self._sync_time()
+
+    def advance_to(self, t, max_steps=None):
+        """Adaptive time stepping: steps until the scene time reaches t (the last steps land on it) or max_steps steps are done;
+        returns the steps done.  One sph_advance_until where the host has nothing to do inside a step, else sph_set_time_target and
+        step() until the target is reached."""
+        if not self._adaptive():
+            raise ValueError("advance_to needs Configuration.cflMethod \"velocity\"")
+        cap = (1 << 30) if max_steps is None else int(max_steps)
+        if not (self._host_acts_inside_a_step() or (self.cfg.get_cfg("exportObj") and not self._bodies_on_device())):
+            done = self.engine.advance_until(t, cap)
+            for _ in range(done):
+                self._count_step()
+            if done and self._bodies_on_device():
+                self.rigid_solver.mark_stale()
+                self._update_exported_meshes()
+            self._sync_time()
+            return done
+        done = 0
+        self.engine.set_time_target(t)
+        try:
+            while done < cap and t - self.engine.time_state()["time"] > self.cfl_max_time_step / 1048576.0:
+                self.step()
+                done += 1
+        finally:
+            self.engine.set_time_target(None)
+            self._sync_time()
+        return done
 
     def advance(self, n):
         """n calls of step().  Where the host has nothing to do inside a step -- no dynamic rigid body to integrate, no object
@@ -218,6 +270,7 @@ class BaseSolver:
             self.container.total_time += self.dt[None]
             self.rigid_solver.total_time += self.dt[None]
             self._count_step()
+        self._sync_time()
 
     def stats(self):
         return self.engine.stats()

@@ -351,6 +351,12 @@ class HostRigidSolver:
                 b.com[k] = max(self.wall_hi[k] - ext_hi[k], self.wall_lo[k] - ext_lo[k])
                 b.vel[k] = min(b.vel[k], 0.0)
 
+    def set_dt(self, dt):
+        """Adaptive time stepping: the size of the running step, for the integrator and the host contact solver."""
+        self.dt = float(dt)
+        if self.contact_parameters is not None:
+            self.contact_parameters.dt = self.dt
+
     def mark_stale(self):
         """The device has stepped: what the host holds of the bodies' state is out of date."""
         self._stale = self.on_device and bool(self.bodies or self.scripted)

@@ -78,6 +78,7 @@ PH_ELASTIC = 30
 PH_EMIT = 31   # fluid emitters: the hold and the emission of the current step count alone
 PH_DRAG = 32   # air drag: the walk alone (PH_NON_PRESSURE / PH_CG_END then add the stored a_drag)
 PH_OUTFLOW = 33   # outflow: the mark and the count of the current step count alone (no sort)
+PH_CFL = 34       # adaptive time stepping: the reduce of the largest speed alone (no new step size)
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
@@ -97,6 +98,7 @@ K_ELASTIC = 33               # SPH_K_ELASTIC: scatter + pass A + pass B of the e
 K_EMIT = 34                  # SPH_K_EMIT: the hold launch and the emit launch of the fluid emitters
 K_DRAG = 35                  # SPH_K_DRAG: the walk of the air drag
 K_OUTFLOW = 36               # SPH_K_OUTFLOW: the mark launch of the outflow volumes / of a removal by id
+K_CFL = 37                   # SPH_K_CFL: the reduce of the largest speed (adaptive time stepping)
 RIGID_MOTION_MAX_KEYS = 64
 MAX_EMITTERS = 8             # SPH_MAX_EMITTERS
 EMITTER_MAX_HOLD = 8         # SPH_EMITTER_MAX_HOLD
@@ -292,6 +294,59 @@ def outflow_active_host(program, dt, k):
 
 
 PBF_VARIANTS = {"reference": 0, "consistent": 1}
+
+
+CFL_METHODS = {"none": 0, "velocity": 1}
+CFL_CLAMPED_MAX, CFL_CLAMPED_MIN, CFL_LANDING, CFL_STALE = 1, 2, 4, 8   # SphTimeState::flags
+
+
+class SphCflParams(C.Structure):
+    """Adaptive time stepping (include/sph_hip.h): the method, cflFactor and the clamps of the step size."""
+    _fields_ = [("method", C.c_int32), ("reserved", C.c_int32), ("factor", C.c_double), ("min_dt", C.c_double), ("max_dt", C.c_double)]
+
+
+class SphTimeState(C.Structure):
+    _fields_ = [("time", C.c_double), ("dt_next", C.c_double), ("dt_last", C.c_double), ("target", C.c_double), ("vmax2", C.c_float),
+                ("flags", C.c_int32), ("steps", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+def cfl_params(method="velocity", factor=0.5, min_dt=0.0, max_dt=0.0):
+    return SphCflParams(int(CFL_METHODS.get(method, method)), 0, float(factor), float(min_dt), float(max_dt))
+
+
+def cfl_dt_host(params, diameter, vmax2, remaining=float("nan")):
+    """The rule on the CPU (sph_cfl_dt_host): (dt, flags) for a float32 maximum of |v|^2; remaining not finite: no time target.
+    No device."""
+    lib = load()
+    dt, flags = C.c_double(), C.c_int32()
+    rc = lib.sph_cfl_dt_host(C.byref(params), float(diameter), C.c_float(vmax2), float(remaining), C.byref(dt), C.byref(flags))
+    if rc != 0:
+        raise SphError(f"sph_cfl_dt_host failed ({rc}): " + (lib.sph_last_error(None) or b"").decode(), rc)
+    return dt.value, flags.value
+
+
+def cfl_meta(material, is_dynamic, ghost=None, removed=None):
+    """The particle words sph_cfl_speed2_host takes, from per-particle materials and dynamic flags."""
+    m = (np.asarray(material, np.int32) << 8) | ((np.asarray(is_dynamic, np.int32) != 0).astype(np.int32) << 10)
+    if ghost is not None:
+        m = m | ((np.asarray(ghost, np.int32) != 0).astype(np.int32) << 11)
+    if removed is not None:
+        m = m | ((np.asarray(removed, np.int32) != 0).astype(np.int32) << 12)
+    return np.ascontiguousarray(m, np.int32)
+
+
+def cfl_speed2_host(vel, meta):
+    """The reduce on the CPU (sph_cfl_speed2_host): (float32 maximum of |v|^2 over the particles that count, non-finite flag).
+    No device."""
+    lib = load()
+    vel = np.ascontiguousarray(vel, np.float32).reshape(-1, 3)
+    meta = np.ascontiguousarray(meta, np.int32).reshape(-1)
+    assert len(vel) == len(meta)
+    v, bad = C.c_float(), C.c_int32()
+    rc = lib.sph_cfl_speed2_host(len(vel), _ptr(vel) if len(vel) else None, _ptr(meta) if len(vel) else None, C.byref(v), C.byref(bad))
+    if rc != 0:
+        raise SphError(f"sph_cfl_speed2_host failed ({rc}): " + (lib.sph_last_error(None) or b"").decode(), rc)
+    return np.float32(v.value), bool(bad.value)
 
 
 class SphPbfParams(C.Structure):
@@ -690,6 +745,14 @@ _SIGNATURES = [
     ("sph_remove_particles", C.c_int, [_VP, _VP, C.c_int]),
     ("sph_outflow_test_host", C.c_int, [C.POINTER(SphOutflow), _VP, C.c_int, _VP]),
     ("sph_outflow_active_host", C.c_int, [C.POINTER(SphOutflow), C.c_double, C.c_int64]),
+    ("sph_set_time_step", C.c_int, [_VP, C.c_double]),
+    ("sph_set_cfl", C.c_int, [_VP, C.POINTER(SphCflParams)]),
+    ("sph_get_cfl", C.c_int, [_VP, C.POINTER(SphCflParams)]),
+    ("sph_get_time_state", C.c_int, [_VP, C.POINTER(SphTimeState)]),
+    ("sph_set_time_target", C.c_int, [_VP, C.c_double]),
+    ("sph_advance_until", C.c_int, [_VP, C.c_double, C.c_int, C.POINTER(C.c_int)]),
+    ("sph_cfl_dt_host", C.c_int, [C.POINTER(SphCflParams), C.c_double, C.c_float, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    ("sph_cfl_speed2_host", C.c_int, [C.c_int64, _VP, _VP, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     ("sph_prepare", C.c_int, [_VP]),
     ("sph_step", C.c_int, [_VP, C.c_int]),
     ("sph_step_async", C.c_int, [_VP, C.c_int]),
@@ -1125,6 +1188,40 @@ class Engine(NativeObject):
         """Removes the live fluid particles with these persistent ids (sph_remove_particles)."""
         ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
         self._chk(self.lib.sph_remove_particles(self.h, _ptr(ids) if len(ids) else None, len(ids)), "sph_remove_particles")
+
+    # -- adaptive time stepping
+    def set_time_step(self, dt):
+        """A new step size between steps (sph_set_time_step); refused while the CFL mode is on."""
+        self._chk(self.lib.sph_set_time_step(self.h, float(dt)), "sph_set_time_step")
+
+    def set_cfl(self, method="velocity", factor=0.5, min_dt=0.0, max_dt=0.0):
+        """method: "none" / "velocity" (or 0 / 1); "none" switches the mode off and restores the creation step size."""
+        if CFL_METHODS.get(method, method) == 0:
+            self._chk(self.lib.sph_set_cfl(self.h, None), "sph_set_cfl")
+            return
+        p = cfl_params(method, factor, min_dt, max_dt)
+        self._chk(self.lib.sph_set_cfl(self.h, C.byref(p)), "sph_set_cfl")
+
+    def get_cfl(self):
+        p = SphCflParams()
+        self._chk(self.lib.sph_get_cfl(self.h, C.byref(p)), "sph_get_cfl")
+        return {"method": {v: k for k, v in CFL_METHODS.items()}[p.method], "factor": p.factor, "min_dt": p.min_dt, "max_dt": p.max_dt}
+
+    def time_state(self):
+        """dict(time, dt_next, dt_last, target, vmax2, flags, steps): what the host knows, no device access."""
+        st = SphTimeState()
+        self._chk(self.lib.sph_get_time_state(self.h, C.byref(st)), "sph_get_time_state")
+        return struct_dict(st, skip=("reserved",))
+
+    def set_time_target(self, t_end):
+        """The step sizes land on t_end from now on; None (or a value that is not finite) clears the target."""
+        self._chk(self.lib.sph_set_time_target(self.h, float("nan") if t_end is None else float(t_end)), "sph_set_time_target")
+
+    def advance_until(self, t_end, max_steps=1 << 30):
+        """Steps until the scene time reaches t_end or max_steps steps are done; returns the steps done."""
+        done = C.c_int(0)
+        self._chk(self.lib.sph_advance_until(self.h, float(t_end), int(max_steps), C.byref(done)), "sph_advance_until")
+        return done.value
 
     # -- device contact solver (the "device_contact" rigid backend)
     def set_rigid_contact_solver(self, on=True, restitution=0.2, friction=0.5, iterations=10, beta=0.2, slop=0.0, patch=0.0):

@@ -35,6 +35,19 @@ struct EmHost { bool on = false; SphEmitter e = {}; int nu = 0, nv = 0, layer_n 
 // outflow: one volume as the host keeps it (sph_outflow_api.hpp): the program, what it has removed in all and in the last slot
 struct OfHost { bool on = false; SphOutflow v = {}; long long removed = 0; int last = 0; };
 
+// adaptive time stepping (sph_cfl_api.hpp): the parameters, the step size the handle was created with, the time target (NaN: none), what
+// the last reduce found, and the flags of the pending step size.  stale: the maximum no longer describes the state (the next step begins
+// with a reduce).  irregular: a step was taken with another size than the creation one (the scene time is no closed form of the count)
+struct CflHost {
+    bool on = false, stale = true, irregular = false;
+    SphCflParams p = {};
+    double dt_create = 0.0; float dt_create_f = 0.0f;
+    double target = NAN, dt_last = 0.0;
+    float vmax2 = 0.0f;
+    int flags = 0, bank = 0;
+    unsigned *pinned = nullptr;
+};
+
 struct SphHandle : ErrSink {
     SphParams prm = {};
     State st;
@@ -114,6 +127,7 @@ struct SphHandle : ErrSink {
     unsigned *of_pinned = nullptr;
     bool of_removed_any = false;
     int id_next = 0;
+    CflHost cfl;
 };
 static inline int next_id(const SphHandle *h);
 static long long em_reserved(const SphHandle *h);
@@ -270,6 +284,7 @@ extern "C" void sph_destroy(SphHandle *h) {
     if (h->scal_h) hipHostFree(h->scal_h);
     if (h->loop_pub) hipHostFree((void *)h->loop_pub);
     if (h->of_pinned) hipHostFree((void *)h->of_pinned);
+    if (h->cfl.pinned) hipHostFree((void *)h->cfl.pinned);
     if (h->st.list_count_pinned) { hipHostFree((void *)h->st.list_count_pinned); h->st.list_count_pinned = nullptr; }
     if (h->st.list_count_event) { hipEventDestroy(h->st.list_count_event); h->st.list_count_event = nullptr; }
     if (h->st.stream) hipStreamDestroy(h->st.stream);
@@ -314,6 +329,7 @@ extern "C" int sph_create(const SphParams *params, SphHandle **out) {
     State &s = h->st;   // (every member starts from its initialiser: what follows allocates, and derives from the parameters)
     HIP_CREATE(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
     fill_consts(h);
+    h->cfl.dt_create = p.dt; h->cfl.dt_create_f = s.c.dt;
     const size_t cap = (size_t)p.particle_max_num;
     s.cap = p.particle_max_num;
     for (int k = 0; k < 2; ++k) {
@@ -465,6 +481,7 @@ extern "C" int sph_append_particles(SphHandle *h, int object_id, int n, const fl
     if (h->prepared) h->sort_dirty = true;
     s.masks_valid = 0;
     s.perm_n = -1; s.list_n = -1;
+    h->cfl.stale = true;
     refresh_counts(h);
     return SPH_OK;
 }
@@ -945,6 +962,7 @@ extern "C" int sph_set_rigid_motion(SphHandle *h, int o, const SphRigidMotion *p
     if (o < 0 || o >= SPH_MAX_OBJECTS || !program || !com_rest || !rot_rest) return fail(h, SPH_ERR_INVALID, "set_rigid_motion: bad argument");
     { int rc = rigid_int_supported(h, "set_rigid_motion"); if (rc) return rc; }
     { int rc = rigid_motion_check(h, "set_rigid_motion", program); if (rc) return rc; }
+    if (h->cfl.on || h->cfl.irregular) return fail(h, SPH_ERR_UNSUPPORTED, "set_rigid_motion: the step size changes or has changed (sph_set_cfl / sph_set_time_step: a motion program is a closed form of k dt)");
     for (int q = 0; q < 9; ++q)
         if (!std::isfinite(rot_rest[q]) || !std::isfinite(com_rest[q % 3])) return fail(h, SPH_ERR_INVALID, "set_rigid_motion: the rest pose is not finite");
     if (h->rb_h[o].registered)
@@ -1282,6 +1300,9 @@ static void step_begin(SphHandle *h) {
 #include "sph_emitter_api.hpp"
 #include "sph_outflow_api.hpp"
 #include "sph_steps.hpp"
+static int step_once(SphHandle *h);
+static int finish_sync(SphHandle *h);
+#include "sph_cfl_api.hpp"
 
 static int read_scalars(SphHandle *h) {
     { int rc = slab_settle_if_needed(h); if (rc) return rc; }
@@ -1368,6 +1389,7 @@ extern "C" int sph_prepare(SphHandle *h) {
     HIPCHK(h, hipMemsetAsync((char *)s.scal + offsetof(DevScalars, fallback), 0, sizeof(unsigned long long) * SPH_STAT_SLOTS, s.stream));
     rc = check_async(h); if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(s.stream));
+    if (h->cfl.on) { rc = cfl_reduce(h); if (rc) return rc; cfl_pending(h); }   // the first step size
     h->prepared = true;
     return SPH_OK;
 }
@@ -1407,6 +1429,7 @@ extern "C" int sph_rigid_integrate(SphHandle *h) {
 // First half of a step: everything the reference's _step() does before `self.rigid_solver.step()`.
 static int step_first_half(SphHandle *h) {
     if (h->in_step) return fail(h, SPH_ERR_INVALID, "sph_step_begin: the previous step was not ended");
+    { int rc = cfl_step_begin(h); if (rc) return rc; }
     step_begin(h);
     h->em_touch = em_slot_touches(h, (long long)h->steps + 1) || h->of_n > 0;   // (outflow: the slot may mark particles dead behind a hash)
     int rc;
@@ -1453,9 +1476,7 @@ static int step_second_half(SphHandle *h) {
         // rigid particles (static ones have not moved), which is all this pass looks at.
         ph_rigid_volume(h);
     }
-    h->total_time += (double)s.c.dt;  // base_solver.py:694
-    h->steps++;
-    return SPH_OK;
+    return cfl_step_end(h);   // the scene time and the step count advance; adaptive time stepping: the reduce and the next step size
 }
 
 static int step_once(SphHandle *h) {
@@ -1508,6 +1529,7 @@ extern "C" int sph_step_async(SphHandle *h, int nsteps) {
     if (h->prm.method == SPH_METHOD_PBF && h->pbf.variant == SPH_PBF_VARIANT_CONSISTENT && h->prm.fixed_iterations <= 0)
         return fail(h, SPH_ERR_UNSUPPORTED, "sph_step_async: the consistent PBF variant needs fixed_iterations > 0 (its stop test reads back)");
     if (h->of_n > 0) return fail(h, SPH_ERR_UNSUPPORTED, "sph_step_async: an outflow volume is set (the removed count is read back at every slot: sph_step)");
+    if (h->cfl.on) return fail(h, SPH_ERR_UNSUPPORTED, "sph_step_async: the CFL mode is on (the largest speed is read back at every step: sph_step)");
     HIPCHK(h, hipSetDevice(h->device));
     refresh_counts(h);
     for (int k = 0; k < nsteps; ++k) {
@@ -1565,6 +1587,13 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
             if (h->of_n <= 0) return fail(h, SPH_ERR_INVALID, "SPH_PH_OUTFLOW: no outflow volume is set (sph_set_outflow)");
             { const int rc = ph_outflow(h, (long long)h->steps); if (rc) return rc; }
             break;
+        case SPH_PH_CFL: {
+            if (!h->cfl.on) return fail(h, SPH_ERR_INVALID, "SPH_PH_CFL: the CFL mode is off (sph_set_cfl)");
+            const bool stale = h->cfl.stale;   // (the pending step size is not computed again here: a stale maximum stays stale)
+            const int rc = cfl_reduce(h);
+            h->cfl.stale = h->cfl.stale || stale;
+            if (rc) return rc;
+        } break;
         case SPH_PH_DRAG:
             if (!s.dr_on) return fail(h, SPH_ERR_INVALID, "SPH_PH_DRAG: the air drag is off (sph_set_drag)");
             ph_drag(h);
@@ -1856,6 +1885,7 @@ extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes
     const size_t n = (size_t)h->n;
     HIPCHK(h, hipStreamSynchronize(s.stream));
     s.masks_valid = 0;  // state edited from outside
+    h->cfl.stale = true;
     float4 *vdst = nullptr;
     bool w_only = false;
     switch (field) {

@@ -198,6 +198,7 @@ extern "C" int sph_comm_set_slab(SphHandle *h, int z_lo, int z_hi) {
     if (s.el_marked) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: an elastic object exists (its rest lists name particles by id across every slab)");
     if (h->em_n > 0) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: an emitter is set (its schedule knows one particle count)");
     if (h->of_n > 0 || h->of_removed_any) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: an outflow volume is set or particles have been removed (outflow runs on one GPU)");
+    if (h->cfl.on) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: the CFL mode is on (adaptive time stepping runs on one GPU)");
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->comm.slab_ready) {
         // Which library axis the slabs are cut along (Consts::slab_axis, sph_common.hpp).  Default: z, the scene's own z and the fastest

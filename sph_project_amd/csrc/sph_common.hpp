@@ -16,6 +16,8 @@
 #include "../../include/sph_hip.h"   // (SphRigidMotion: the program a scripted body's record holds)
 #include <math.h>
 #include "sph_outflow_eval.hpp"      // (OutflowDev: one outflow volume as the mark kernel takes it, by value)
+#include <string.h>
+#include "sph_cfl_eval.hpp"          // (adaptive time stepping: which particles count and how a speed is squared, kernel and host)
 
 #define SPH_NOBJ 20
 // IISPH.py:12-14: relaxation factor, stop threshold of the average density error, iteration cap
@@ -227,6 +229,11 @@ struct EmitArgs { double spacing; int nlayers, total; int emitter[SPH_MAX_EMITTE
 // SPH_MAX_OUTFLOWS counts what k_outflow_mark_ids marked.  They only grow: the host keeps what it read last.
 #define SPH_OUTFLOW_CTR_STRIDE 32
 struct OutflowArgs { int nvol; OutflowDev v[SPH_MAX_OUTFLOWS]; };
+// Adaptive time stepping (sph_cfl.hpp): two pairs of result words, SPH_CFL_BANK_STRIDE unsigned apart; in a pair the maximum of |v|^2 (its
+// bit pattern) at 0 and the non-finite flag at SPH_CFL_WORD_STRIDE, each on a 128-byte line of its own.  A launch writes one pair and
+// clears the other.
+#define SPH_CFL_WORD_STRIDE 32
+#define SPH_CFL_BANK_STRIDE 64
 struct EmitHoldArgs { double spacing; int nlayers, id_lo, id_hi; int emitter[SPH_EMIT_HOLD_ENTRIES], id_base[SPH_EMIT_HOLD_ENTRIES]; double offset[SPH_EMIT_HOLD_ENTRIES]; };
 
 // Surface reconstruction (sph_surface.hpp): the constants and device buffers of one SphSurface.  Coarse cells (= bricks of
@@ -633,6 +640,8 @@ struct State {
     unsigned *outflow_ctr = nullptr;          // [(SPH_MAX_OUTFLOWS + 1) * SPH_OUTFLOW_CTR_STRIDE]
     int *outflow_ids = nullptr; int outflow_ids_cap = 0;
     int drop_n = 0;
+    // adaptive time stepping (sph_set_cfl; allocated when the mode is first switched on): the result words of k_cfl_speed
+    unsigned *cfl_words = nullptr;            // [2 * SPH_CFL_BANK_STRIDE]
     // CG (implicit viscosity)
     float4 *cg_p = nullptr, *cg_Ap = nullptr, *cg_x = nullptr, *cg_b = nullptr, *cg_r = nullptr, *cg_v0 = nullptr;
     float4 *cg_p2 = nullptr;   // second search-direction buffer (fused p update: the A p pass reads the old one and writes the new one)
@@ -847,6 +856,8 @@ struct Launch {
     // outflow (sph_outflow.hpp): the dead bit for every active fluid particle inside an active volume / whose id is in the sorted list
     void (*outflow_mark)(State &, const OutflowArgs &);
     void (*outflow_mark_ids)(State &, int nids);
+    // adaptive time stepping (sph_cfl.hpp): the maximum of |v|^2 over the particles that count, into the result pair `bank`
+    void (*cfl_speed)(State &, int bank);
     // z-slab sharding
     void (*halo_classify_pack)(State &, int n);
     void (*halo_unpack_append)(State &, int side, int count, int offset);

@@ -61,6 +61,7 @@ extern "C" int sph_set_emitter(SphHandle *h, int index, const SphEmitter *e) {
     if (h->prm.method == SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_emitter: emitter %d: not on a PBF handle (either variant: PBF never inserts)", index);
     if (h->st.slab_active || h->comm.slab_ready) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_emitter: emitter %d: not on a sharded handle (the schedule knows one particle count)", index);
     if (h->prm.g_upper < 9999.0) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_emitter: emitter %d: not with g_upper set (gravitationUpper, the reference's frozen-block emitter)", index);
+    if (h->cfl.on || h->cfl.irregular) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_emitter: emitter %d: the step size changes or has changed (sph_set_cfl / sph_set_time_step: the schedule is a closed form of k dt)", index);
     if (h->swap_axis) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_emitter: emitter %d: the handle's axis order is not \"xyz\"", index);
     if (h->st.ids_custom) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_emitter: emitter %d: particle ids were set from outside (sph_set_appended_ids / SPH_F_PARTICLE_ID): held layers are found by id and need the append order", index);
     const int o = e->object_id;

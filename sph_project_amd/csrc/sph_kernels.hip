@@ -546,6 +546,7 @@ void l_clear_fresh(State &s) {
 #include "sph_rigid_motion.hpp"
 #include "sph_emitter.hpp"
 #include "sph_outflow.hpp"
+#include "sph_cfl.hpp"
 #include "sph_surface.hpp"
 #include "sph_surface_aniso.hpp"
 #include "sph_elastic.hpp"
@@ -596,6 +597,7 @@ const Launch *SPH_LAUNCH_FN() {
         register_rigid_motion_launchers(L);
         register_emitter_launchers(L);
         register_outflow_launchers(L);
+        register_cfl_launchers(L);
         register_surface_launchers(L);
         register_surface_aniso_launchers(L);
         register_surface_post_launchers(L);

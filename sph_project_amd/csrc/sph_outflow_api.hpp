@@ -64,6 +64,7 @@ extern "C" int sph_set_outflow(SphHandle *h, int index, const SphOutflow *v) {
         return SPH_OK;
     }
     { int rc = outflow_supported(h, "sph_set_outflow"); if (rc) return rc; }
+    if (h->cfl.on || h->cfl.irregular) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_outflow: outflow %d: the step size changes or has changed (sph_set_cfl / sph_set_time_step: the time window is a closed form of k dt)", index);
     { int rc = outflow_check(h, "sph_set_outflow", index, v); if (rc) return rc; }
     HIPCHK(h, hipSetDevice(h->device));
     { int rc = outflow_alloc(h); if (rc) return rc; }
