@@ -90,11 +90,12 @@ def unchanged(before, after, keys, sel, what):
         np.testing.assert_array_equal(_rows(after[k], sel), _rows(before[k], sel), err_msg="%s: %s" % (what, k))
 
 
-def pass_by_pass(kind, state, fast_math, method="dfsph"):
+def pass_by_pass(kind, state, fast_math, method="dfsph", layers=None):
     """prepare, ITERATIONS iterations and the end of the solve pass by pass on the DFSPH handle; returns the worst fractions.  Every
-    solver vector is held bit-unchanged on the non-fluid rows across every phase, positions and densities on every row."""
+    solver vector is held bit-unchanged on the non-fluid rows across every phase, positions and densities on every row.  layers: on
+    the scene's twin in a domain of that many cell layers in z (tests/helpers.py with_layers)."""
     split, fused = forms()
-    sc = M.scene(method, rigid=kind == "rigid")
+    sc = M.scene(method, rigid=kind == "rigid", layers=layers)
     eng = engine(sc, method, fast_math, steps=M.K_STEPS if state else 0)
     ids = eng.download(L.F_PARTICLE_ID)
     s0 = get(eng, BASE, ids)
@@ -214,10 +215,13 @@ def scalars_only(eng, fl, P, iterations=2):
 
 
 if __name__ == "__main__":
+    # arguments (tests/test_hip_tall_grid.py): --layers N: the scenes' twins in a domain of N cell layers in z; --builds 1: the fast build only
+    layers = int(sys.argv[sys.argv.index("--layers") + 1]) if "--layers" in sys.argv else None
+    builds = [int(b) for b in sys.argv[sys.argv.index("--builds") + 1].split(",")] if "--builds" in sys.argv else [0, 1]
     out = {}
-    for fast_math in (0, 1):
+    for fast_math in builds:
         for kind in ("rigid", "fluid"):
             for state in (0, 1):
-                out["%s, state %d, fast_math=%d" % (kind, state, fast_math)] = pass_by_pass(kind, state, fast_math)
+                out["%s, state %d, fast_math=%d" % (kind, state, fast_math)] = pass_by_pass(kind, state, fast_math, layers=layers)
     split, fused = forms()
     print(json.dumps(dict(split=split, fused=fused, cases=out)))

@@ -267,9 +267,9 @@ K_STEPS = 1
 FIXED_ITERATIONS = 2
 
 
-def scene(method="dfsph", rigid=True):
+def scene(method="dfsph", rigid=True, layers=None):
     from tests import nonpressure_terms as T
-    sc = T.scene(method, rigid=rigid, viscosity=MU, viscosity_b=MU_B, viscosity_method="implicit")
+    sc = T.scene(method, rigid=rigid, viscosity=MU, viscosity_b=MU_B, viscosity_method="implicit", layers=layers)
     assert sc["pd"]["viscosity_implicit"] == 1
     sc["pd"]["fixed_iterations"] = FIXED_ITERATIONS
     return sc

@@ -34,7 +34,7 @@ behind, so for WCSPH the model computes its own float64 density (density_f64) an
 bound of every term that divides by it (`rho_bound` of non_pressure_f64, wcsph_step_check)."""
 import numpy as np
 
-from tests.helpers import _pair_list, wcsph_pressure_accel_f64
+from tests.helpers import _pair_list, wcsph_pressure_accel_f64, with_layers
 
 U = 2.0 ** -24
 C1, C2 = 1e-5, 5e-7
@@ -337,20 +337,23 @@ BODY_VEL, BODY_ANGVEL = (0.1, -0.2, 0.05), (0.5, 1.5, -0.8)
 
 
 def scene(method, rigid=True, masses=2, seed=7, noise=1.0, converge=0.0, dt=4e-4, viscosity=1.0, viscosity_b=4.0,
-          viscosity_method="standard"):
+          viscosity_method="standard", layers=None):
     """dict(cfg, pd, batches, com, params): `batches` in insertion order (box, fluid objects 0 and 1, the cube), each with pos /
     vel / density / material / is_dynamic / object_id; `pd` the flat parameters of both the engine and the oracle.  rigid=False:
     the all-fluid twin (same block, no box, no body); masses=1: both fluid objects of density 1000.  noise, converge, dt: the
     velocity noise in units of 0.5 m/s, a velocity -converge (x - centre of the block) on top (1 / s) and the time step -- the
     defaults are the scene of the non-pressure tests; tests/pressure_solve_terms.py compresses the block with them.  viscosity,
     viscosity_b, viscosity_method: mu, mu_b and the method (tests/implicit_viscosity_terms.py: "implicit", with mu and mu_b raised
-    until D is far from the identity)."""
+    until D is far from the identity).  layers: the same particles in a domain of that many cell layers in z (tests/helpers.py
+    with_layers; the domain box of the rigid scene grows with it)."""
     from sph_project_amd import scene as S
     from sph_project_amd.product import dam_break_scene, scene_particles
     lo = np.array([0.085, 0.085, 0.15])
     cfg = dam_break_scene(method=method, domain_end=(0.48, 0.44, 0.44), start=(0, 0, 0), end=(0, 0, 0), add_domain_box=rigid,
                           particleSpacing=SPACING, viscosity=viscosity, viscosity_b=viscosity_b, dt=dt,
                           viscosity_method=viscosity_method)
+    if layers is not None:
+        cfg = with_layers(cfg, layers)
     cfg["FluidBlocks"] = []
     c, geo, batches = scene_particles(cfg)
     sol = S.derive_solver_constants(c)

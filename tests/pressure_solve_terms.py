@@ -296,9 +296,9 @@ K_STEPS = {"dfsph": 0, "pcisph": 1}
 NOISE, CONVERGE, DT = 4.0, 45.0, 1e-3
 
 
-def scene(method, rigid=True):
+def scene(method, rigid=True, layers=None):
     from tests import nonpressure_terms as T
-    sc = T.scene(method, rigid=rigid, noise=NOISE, converge=CONVERGE, dt=DT)
+    sc = T.scene(method, rigid=rigid, noise=NOISE, converge=CONVERGE, dt=DT, layers=layers)
     sc["pd"]["fixed_iterations"] = 1
     return sc
 

@@ -31,7 +31,7 @@ fast form.  Where the radicand x is at least 2 eps the root is smooth between x 
 eps / (4 (x - eps)^(3/4)) holds as well; the model takes the smaller of the two.  Everything else of the adhesion term is relative (C1)."""
 import numpy as np
 
-from tests.helpers import _pair_list
+from tests.helpers import _pair_list, with_layers
 from tests import nonpressure_terms as T
 
 U, C1, C2, N_MAX = T.U, T.C1, T.C2, T.N_MAX
@@ -181,13 +181,16 @@ def _grid(corner, n, d):
     return np.stack(np.meshgrid(*ax, indexing="ij"), -1).reshape(-1, 3)
 
 
-def scene(method, kind="rigid", seed=11, dt=4e-4, viscosity=1.0, viscosity_b=4.0, viscosity_method="standard"):
-    """dict(cfg, pd, batches, com, params, rigid) in the form of nonpressure_terms.scene (its feed() inserts it)."""
+def scene(method, kind="rigid", seed=11, dt=4e-4, viscosity=1.0, viscosity_b=4.0, viscosity_method="standard", layers=None):
+    """dict(cfg, pd, batches, com, params, rigid) in the form of nonpressure_terms.scene (its feed() inserts it); layers: the same
+    particles in a domain of that many cell layers in z (tests/helpers.py with_layers)."""
     from sph_project_amd import scene as S
     from sph_project_amd.product import dam_break_scene, scene_particles
     rigid, jitter = kind in ("rigid", "lattice"), kind in ("rigid", "fluid")
     cfg = dam_break_scene(method=method, domain_end=(0.6, 0.52, 0.52), start=(0, 0, 0), end=(0, 0, 0), add_domain_box=False,
                           viscosity=viscosity, viscosity_b=viscosity_b, dt=dt, viscosity_method=viscosity_method)
+    if layers is not None:
+        cfg = with_layers(cfg, layers)
     cfg["FluidBlocks"] = []
     c, geo, batches = scene_particles(cfg)
     sol = S.derive_solver_constants(c)

@@ -137,13 +137,15 @@ def test_iisph_per_term_c2(gpu, fast_math, moved):
     _per_term(container, solver, 3000, 7 + moved, live=bool(moved))
 
 
-@pytest.mark.parametrize("fast_math", [0, 1])
-def test_iisph_per_term_boundary(gpu, fast_math):
-    """Next to sampled domain-box particles: the rigid branches of dii (rho_i^2, DESIGN.md 11), aii, rho* and sum_i."""
+def check_per_term_boundary(fast_math, layers=None):
+    """layers: in a domain of that many cell layers in z (tests/helpers.py with_layers; tests/test_hip_tall_grid.py)"""
     cfg = P.dam_break_scene(method="iisph", domain_end=(0.32, 0.32, 0.32), start=(0.06, 0.045, 0.06), end=(0.16, 0.16, 0.16),
                             translation=(0.0, 0.0, 0.0), add_domain_box=True, viscosity_b=0.3, velocity=(0.1, -1.0, 0.0))
+    if layers is not None:
+        cfg = H.with_layers(cfg, layers)
     container, solver = H.build_product(cfg, fast_math=fast_math)
     solver.prepare()
+    assert layers is None or container.engine.grid_layout()["nz"] == layers
     solver.advance(5)
     s, rows = _per_term(container, solver, 100000, 3)
     # the sample holds fluid particles with boundary neighbours (otherwise this test would not reach the rigid branch)
@@ -151,6 +153,12 @@ def test_iisph_per_term_boundary(gpu, fast_math):
     rig = s["x"][s["mat"] == 2]
     near = cKDTree(rig).query(s["x"][rows], distance_upper_bound=container.dh)[0] < container.dh
     assert near.sum() > 50, int(near.sum())
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+def test_iisph_per_term_boundary(gpu, fast_math):
+    """Next to sampled domain-box particles: the rigid branches of dii (rho_i^2, DESIGN.md 11), aii, rho* and sum_i."""
+    check_per_term_boundary(fast_math)
 
 
 def test_iisph_shipped_scene(gpu):

@@ -33,10 +33,15 @@ def _report(tag, fr):
 def test_every_pass_against_the_model(gpu, kind, state, fast_math):
     """The production forms: split, k_cg_ap_combine in front of the loop, parts only inside it, the p update folded into the next A p pass
     (the second A p pass is the first folded one, the second x / r update reads the other parity)."""
+    check_every_pass(kind, state, fast_math)
+
+
+def check_every_pass(kind, state, fast_math, layers=None):
+    """layers: on the scene's twin in a domain of that many cell layers in z (tests/test_hip_tall_grid.py)"""
     assert PR.forms() == (True, True)
-    fr = PR.pass_by_pass(kind, state, fast_math)
+    fr = PR.pass_by_pass(kind, state, fast_math, layers=layers)
     assert any(k.endswith("A p (parts)") for k in fr) and "it 2 beta" in fr and "end v" in fr
-    _report("split, folded p update; %s, state %d, fast_math=%d" % (kind, state, fast_math), fr)
+    _report("split, folded p update; %s, state %d, fast_math=%d%s" % (kind, state, fast_math, ", %d layers" % layers if layers else ""), fr)
 
 
 @pytest.mark.parametrize("switches", [dict(SPH_TEST_CG_SPLIT_LIMIT="0"), dict(SPH_TEST_CG_SEPARATE_P="1"),
@@ -45,13 +50,18 @@ def test_every_pass_against_the_model(gpu, kind, state, fast_math):
 def test_every_pass_in_the_other_launch_forms(gpu, switches):
     """The same sequence (both builds, both scenes, both states) in a child process on the test-hook library: the unsplit A p pass with
     the folded own_p(), k_cg_update_p2 with k_cg_ap_combine inside the loop, and both."""
+    check_other_launch_forms(switches)
+
+
+def check_other_launch_forms(switches, probe_args=(), cases=8):
+    """probe_args: arguments of tests/implicit_viscosity_probe.py (tests/test_hip_tall_grid.py: the tall twins, the fast build only)"""
     hooks = os.path.join(ROOT, "sph_project_amd", "libsph_hip_testhooks.so")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "implicit_viscosity_probe.py")],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "implicit_viscosity_probe.py"), *probe_args],
                        env=dict(os.environ, SPH_HIP_LIB=hooks, **switches), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     got = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert got["split"] == ("SPH_TEST_CG_SPLIT_LIMIT" not in switches) and got["fused"] == ("SPH_TEST_CG_SEPARATE_P" not in switches)
-    assert len(got["cases"]) == 8
+    assert len(got["cases"]) == cases
     for tag, fr in got["cases"].items():
         assert max(fr.values()) <= 1, (tag, fr)
         assert ("it 1 A p (parts)" in fr) == (got["split"] and got["fused"]) and "it 2 beta" in fr

@@ -27,10 +27,11 @@ _FIELDS = dict(x=L.F_POSITION, v=L.F_VELOCITY, rho=L.F_DENSITY, vol=L.F_REST_VOL
 _SCENES = {}
 
 
-def _scene(method, kind, implicit=False):
-    key = (method, kind, implicit)
+def _scene(method, kind, implicit=False, layers=None):
+    """layers: the scene's twin in a domain of that many cell layers in z (tests/helpers.py with_layers)"""
+    key = (method, kind, implicit, layers)
     if key not in _SCENES:
-        sc = M.scene(method, kind, viscosity_method="implicit" if implicit else "standard")
+        sc = M.scene(method, kind, viscosity_method="implicit" if implicit else "standard", layers=layers)
         sc["w"] = M.angular_velocities(sc)
         _SCENES[key] = sc
     return _SCENES[key]

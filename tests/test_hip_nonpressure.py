@@ -57,8 +57,9 @@ def _report(tag, fast_math, fr):
     print("nonpressure bounds [%s, fast_math=%d]: " % (tag, fast_math) + ", ".join("%s %.3f" % kv for kv in fr.items()))
 
 
-def _scene(kind):
-    return T.scene("wcsph", rigid=kind == "rigid", masses=1 if kind == "fluid_one_mass" else 2)
+def _scene(kind, layers=None):
+    """layers: the scene's twin in a domain of that many cell layers in z (tests/helpers.py with_layers)"""
+    return T.scene("wcsph", rigid=kind == "rigid", masses=1 if kind == "fluid_one_mass" else 2, layers=layers)
 
 
 def _phase_model(sc, st0, st1):

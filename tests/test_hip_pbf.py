@@ -165,16 +165,25 @@ def test_pbf_per_term_c2(gpu, fast_math, steps):
     c.engine.close()
 
 
-@pytest.mark.parametrize("fast_math", [0, 1])
-def test_pbf_per_term_boundary(gpu, fast_math):
-    """A block in the domain box: rigid neighbours in lambda and fix_position, poly6 rigid volumes."""
-    c, s = H.build_product(P.pbf_scene(domain_end=(0.5, 0.5, 0.5), end=(0.3, 0.3, 0.3)), fast_math=fast_math)
+def check_per_term_boundary(fast_math, layers=None):
+    """layers: in a domain of that many cell layers in z (tests/helpers.py with_layers; tests/test_hip_tall_grid.py)"""
+    cfg = P.pbf_scene(domain_end=(0.5, 0.5, 0.5), end=(0.3, 0.3, 0.3))
+    if layers is not None:
+        cfg = H.with_layers(cfg, layers)
+    c, s = H.build_product(cfg, fast_math=fast_math)
     s.prepare()
+    assert layers is None or c.engine.grid_layout()["nz"] == layers
     s.advance(3)
     mat = c.engine.download(L.F_MATERIAL)
     assert (mat == 2).any()
     _check_refine_terms(c, s, nrows=3000)
     c.engine.close()
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+def test_pbf_per_term_boundary(gpu, fast_math):
+    """A block in the domain box: rigid neighbours in lambda and fix_position, poly6 rigid volumes."""
+    check_per_term_boundary(fast_math)
 
 
 def _small(**opts):

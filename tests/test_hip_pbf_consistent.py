@@ -37,7 +37,10 @@ def _start(case, **opts):
     """The product on the seeded state of a phase case, prepared: (container, solver, x, v, vol, mat, geo) in device order."""
     scene, spacing, jitter, seed = M.PHASE_CASES[case]
     keys = opts.pop("keys", {})
+    layers = opts.pop("layers", None)   # in a domain of that many cell layers in z (tests/helpers.py with_layers)
     cfg = scene(**keys)
+    if layers is not None:
+        cfg = H.with_layers(cfg, layers)
     c, s = H.build_product(cfg, **opts)
     c.insert_object()
     s.rigid_solver.insert_rigid_object()
@@ -54,12 +57,11 @@ def _start(case, **opts):
     return c, s, x, v, e.download(L.F_REST_VOLUME), e.download(L.F_MATERIAL), geo
 
 
-@pytest.mark.parametrize("fast_math", [0, 1])
-@pytest.mark.parametrize("case", sorted(M.PHASE_CASES))
-def test_phases_match_the_model(gpu, case, fast_math):
-    """predict, three iterations of walk A and walk B, finish; every phase starts from inputs uploaded from the model."""
-    c, s, x, v, vol, mat, geo = _start(case, fast_math=fast_math)
+def check_phases(case, fast_math, layers=None):
+    """layers: on the case's twin in a domain of that many cell layers in z (tests/test_hip_tall_grid.py)"""
+    c, s, x, v, vol, mat, geo = _start(case, fast_math=fast_math, layers=layers)
     e = c.engine
+    assert layers is None or (e.grid_layout()["nz"] == layers == int(geo.grid_num[2]))
     fl = mat == 1
     assert s.variant == "consistent" and (case == "box") == bool((~fl).any())
     pairs = M.sorted_pairs(x, geo.h, geo.grid_num, fl)
@@ -100,6 +102,13 @@ def test_phases_match_the_model(gpu, case, fast_math):
     _check("finish v", ve, v32, v64, fl)
     assert xe[~fl].tobytes() == x[~fl].tobytes() and ve[~fl].tobytes() == v[~fl].tobytes()
     c.engine.close()
+
+
+@pytest.mark.parametrize("fast_math", [0, 1])
+@pytest.mark.parametrize("case", sorted(M.PHASE_CASES))
+def test_phases_match_the_model(gpu, case, fast_math):
+    """predict, three iterations of walk A and walk B, finish; every phase starts from inputs uploaded from the model."""
+    check_phases(case, fast_math)
 
 
 def _solve_start(**opts):

@@ -19,6 +19,11 @@ _BASE = dict(x=L.F_POSITION, v=L.F_VELOCITY, rho=L.F_DENSITY, vol=L.F_REST_VOLUM
 _SORTED = (L.PH_NEIGHBOR_SEARCH, L.PH_RIGID_VOLUME, L.PH_DENSITY)
 
 
+def _scene(method, rigid=True, layers=None):
+    """layers: the scene's twin in a domain of that many cell layers in z (tests/helpers.py with_layers)"""
+    return M.scene(method, rigid=rigid, layers=layers)
+
+
 def _engine(sc, method, fast_math):
     pd = sc["pd"]
     p = L.SphParams()
@@ -64,7 +69,7 @@ def test_dfsph_solve_correction_wrench_and_residual_field(gpu, kind, mode, fast_
     """The phases up to PH_DFSPH_ALPHA, then PH_DFSPH_DENSITY (DfsphCorrectPass<AF, 1>, DfsphRhoAdvPass<AF, 1>) or PH_DFSPH_DIVERGENCE
     (<AF, 0>): v1 - v0 against the model fed with the product's own kappa, rho, x and V, the wrench of the correction, the rho* /
     D rho / Dt stored last against the model at the product's own v1, and the velocities of the other rows bit for bit."""
-    sc = M.scene("dfsph", rigid=kind == "rigid")
+    sc = _scene("dfsph", rigid=kind == "rigid")
     eng = _engine(sc, "dfsph", fast_math)
     for ph in _SORTED + (L.PH_NON_PRESSURE, L.PH_DFSPH_ALPHA):
         eng.run_phase(ph)
@@ -88,7 +93,7 @@ def test_dfsph_solve_correction_wrench_and_residual_field(gpu, kind, mode, fast_
 def pcisph_k():
     """pcisph_k as the f32 the reference's arithmetic gives (the oracle's; tests/test_pressure_solve_host.py holds it against the
     float64 model)"""
-    sim = oracle_ref.RefSim(M.scene("pcisph")["pd"])
+    sim = oracle_ref.RefSim(_scene("pcisph")["pd"])
     sim.call("pcisph_compute_k")
     k = sim.scalar("pcisph_k")
     sim.close()
@@ -100,7 +105,7 @@ def pcisph_k():
 def test_pcisph_init_and_two_iterations_pass_by_pass(gpu, pcisph_k, kind, fast_math):
     """PH_NON_PRESSURE, PH_PCISPH_INIT, then twice PH_PCISPH_RHO_STAR + PH_PCISPH_PRESSURE_ACCEL; the second round's predicted
     positions carry a pressure term."""
-    sc = M.scene("pcisph", rigid=kind == "rigid")
+    sc = _scene("pcisph", rigid=kind == "rigid")
     eng = _engine(sc, "pcisph", fast_math)
     for ph in _SORTED:
         eng.run_phase(ph)
@@ -134,7 +139,7 @@ def test_pcisph_init_and_two_iterations_pass_by_pass(gpu, pcisph_k, kind, fast_m
 
 
 def test_pcisph_phases_refused_on_other_methods(gpu):
-    sc = M.scene("dfsph", rigid=False)
+    sc = _scene("dfsph", rigid=False)
     eng = _engine(sc, "dfsph", 0)
     for ph in (L.PH_PCISPH_INIT, L.PH_PCISPH_RHO_STAR, L.PH_PCISPH_PRESSURE_ACCEL):
         with pytest.raises(L.SphError):
@@ -163,7 +168,7 @@ def test_dfsph_whole_step_is_the_phase_sequence(gpu, kind, fast_math):
     first D rho / Dt, and with it kappa_v and the corrected velocity, differ by roundings (measured: kappa_v in 55 % of the rows, at
     most 2.9e-5 relative) -- there x, rho and alpha, which no D rho / Dt enters, are held to the bits, and each pass is held to the
     model by test_dfsph_solve_correction_wrench_and_residual_field."""
-    sc = M.scene("dfsph", rigid=kind == "rigid")
+    sc = _scene("dfsph", rigid=kind == "rigid")
     solve = dict(v=L.F_VELOCITY, kappa=L.F_DFSPH_KAPPA, star=L.F_DENSITY_STAR)
     end = dict(kappa_v=L.F_DFSPH_KAPPA_V, deriv=L.F_DENSITY_DERIV, alpha=L.F_DFSPH_ALPHA, **_ALL)
     a = _engine(sc, "dfsph", fast_math)
@@ -197,7 +202,7 @@ def test_dfsph_whole_step_is_the_phase_sequence(gpu, kind, fast_math):
 @pytest.mark.parametrize("fast_math", [0, 1])
 @pytest.mark.parametrize("kind", ["rigid", "fluid"])
 def test_pcisph_whole_step_is_the_phase_sequence(gpu, kind, fast_math):
-    sc = M.scene("pcisph", rigid=kind == "rigid")
+    sc = _scene("pcisph", rigid=kind == "rigid")
     fields = dict(prs=L.F_PRESSURE, star=L.F_DENSITY_STAR, pvel=L.F_PREDICTED_VEL, ppos=L.F_PREDICTED_POS, **_ALL)
     a = _engine(sc, "pcisph", fast_math)
     a.step(1)

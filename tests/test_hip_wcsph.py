@@ -153,7 +153,15 @@ def test_all_neighbour_paths_agree(gpu, spacing, label):
     assert d.max() <= 1e-5
 
 
-@pytest.mark.parametrize("method,spacing", [("dfsph", 0.0060), ("dfsph", 0.0064), ("pcisph", 0.0060), ("wcsph", 0.0060)])
+OVERSIZED = [("dfsph", 0.0060), ("dfsph", 0.0064), ("pcisph", 0.0060), ("wcsph", 0.0060)]
+
+
+def oversized_scene(method, spacing):
+    """(scene, jitter, seed) of test_oversized_runs_through_the_tile_in_chunks (tests/test_hip_tall_grid.py runs its tall twin)"""
+    return H.dam_break_scene(method=method, end=(0.118, 0.118, 0.118), particleSpacing=spacing, dt=1e-5), 0.3 * spacing, 5
+
+
+@pytest.mark.parametrize("method,spacing", OVERSIZED)
 def test_oversized_runs_through_the_tile_in_chunks(gpu, method, spacing):
     """A run longer than a functor's tile goes through the tile in chunks (process_chunk), and tiles differ between functors (1280 slots
     for the payload-free passes, ~1064 for the 32-36-byte records, in between for the solver walks): the pass that STORES the
@@ -161,10 +169,10 @@ def test_oversized_runs_through_the_tile_in_chunks(gpu, method, spacing):
     the other way round.  ~300 particles per cell puts the run lengths right across those capacities.  One step (the block is far
     too dense to be stepped further), default paths against debug mode 1 (every run through the chunk path, every mask recomputed):
     bitwise the same state and the same number of pairs."""
-    cfg = H.dam_break_scene(method=method, end=(0.118, 0.118, 0.118), particleSpacing=spacing, dt=1e-5)
+    cfg, jitter, seed = oversized_scene(method, spacing)
     out = []
     for fg in (0, 1):
-        container, solver = H.build_product(cfg, jitter=0.3 * spacing, seed=5, force_global=fg, fixed_iterations=2)
+        container, solver = H.build_product(cfg, jitter=jitter, seed=seed, force_global=fg, fixed_iterations=2)
         solver.prepare()
         solver.step()
         out.append((_state(container), solver.stats()))
@@ -174,16 +182,24 @@ def test_oversized_runs_through_the_tile_in_chunks(gpu, method, spacing):
     assert out[0][1]["pair_interactions"] == out[1][1]["pair_interactions"]
 
 
-@pytest.mark.parametrize("spacing,label", [(0.0080, "125 particles per cell: a group's three runs exceed the tile -> staged in rounds"),
-                                           (0.0058, "~330 per cell: single runs exceed the tile -> through the tile in chunks")])
+PILED_UP = [(0.0080, "125 particles per cell: a group's three runs exceed the tile -> staged in rounds"),
+            (0.0058, "~330 per cell: single runs exceed the tile -> through the tile in chunks")]
+
+
+def piled_up_scene(spacing):
+    """(scene, jitter, seed) of test_piled_up_cells_density (tests/test_hip_tall_grid.py runs its tall twin)"""
+    return H.dam_break_scene(end=(0.118, 0.118, 0.118), particleSpacing=spacing), 0.3 * spacing, 4
+
+
+@pytest.mark.parametrize("spacing,label", PILED_UP)
 def test_piled_up_cells_density(gpu, spacing, label):
     """Extreme pile-ups (the domain clamp of the reference parks particles in the boundary cells): the density pass alone -- a
     full step would blow such a block apart -- through every path: default (rounds / chunks as the tile allows), ordered LDS
     walk (mode 4), every run in chunks (mode 1); bitwise the same densities and pair counts, and the oracle's."""
-    cfg = H.dam_break_scene(end=(0.118, 0.118, 0.118), particleSpacing=spacing)
+    cfg, jitter, seed = piled_up_scene(spacing)
     out = []
     for fg in (0, 4, 1):
-        container, solver = H.build_product(cfg, jitter=0.3 * spacing, seed=4, force_global=fg)
+        container, solver = H.build_product(cfg, jitter=jitter, seed=seed, force_global=fg)
         solver.prepare()
         e = container.engine
         e.run_phase(L.PH_DENSITY)
@@ -192,7 +208,7 @@ def test_piled_up_cells_density(gpu, spacing, label):
     for rho, st in out[1:]:
         np.testing.assert_array_equal(out[0][0], rho)
         assert st["pair_interactions"] == out[0][1]["pair_interactions"]
-    ref = H.build_oracle(cfg, jitter=0.3 * spacing, seed=4)
+    ref = H.build_oracle(cfg, jitter=jitter, seed=seed)
     ref.prepare()
     ref.call("compute_density")
     rho_ref = H.by_id(H.oracle_ids(ref), ref.field("particle_densities").copy())
