@@ -169,6 +169,12 @@ typedef enum {
        order: what the last SPH_PH_DRAG (or step) stored, written on active fluid rows only; valid until the next sort. */
     SPH_F_DRAG_ACCEL = 50,         /* f32[n][3]: a_drag */
     SPH_F_DRAG_TERMS = 51,         /* f32[n][5]: n_i, w, C_D, A_un, y */
+    /* Heat (allocated when sph_set_thermal first switches the mode on; SPH_ERR_UNSUPPORTED before).  The temperature belongs to the
+       particle and follows it through every sort: download and upload in the CURRENT order, like every other field.  A row that is not
+       fluid reads the temperature its object is held at (the reference temperature where it has none); an upload writes fluid rows only. */
+    SPH_F_TEMPERATURE = 52,        /* f32[n] */
+    /* download only: dT/dt of the last SPH_PH_HEAT (or step), written on active fluid rows only; valid until the next sort */
+    SPH_F_TEMPERATURE_RATE = 53,   /* f32[n] */
     SPH_F_COUNT_
 } SphField;
 
@@ -245,6 +251,11 @@ typedef enum {
        particles that count is read back into SphTimeState::vmax2; the step size does not change.  A non-finite square:
        SPH_ERR_INVALID ("non-finite velocity"). */
     SPH_PH_CFL = 34,
+    /* Heat (sph_set_thermal; SPH_ERR_INVALID while the mode is off): the gather and the walk alone, on the masks of the last sort: they
+       store the new temperatures (SPH_F_TEMPERATURE) and dT/dt (SPH_F_TEMPERATURE_RATE) and nothing else.  In this mode, with
+       beta != 0, SPH_PH_NON_PRESSURE (and SPH_PH_CG_END) add the buoyancy of the GATHERED temperatures -- those the last walk read --
+       behind their pass, v += dt a_b, without walking again; a step walks in front of its non-pressure pass. */
+    SPH_PH_HEAT = 35,
     SPH_PH_COUNT_
 } SphPhase;
 
@@ -297,6 +308,7 @@ typedef enum {
     SPH_K_DRAG = 35,            /* air drag: the walk (v += dt a_drag: SPH_K_MISC); "?" as well */
     SPH_K_OUTFLOW = 36,         /* outflow: the mark launch (by volume, or by id for sph_remove_particles); "?" as well */
     SPH_K_CFL = 37,             /* adaptive time stepping: the reduce of the largest speed (sph_set_cfl); "?" as well */
+    SPH_K_HEAT = 38,            /* heat: the gather of the temperatures + the walk (v += dt a_b and the fills: SPH_K_MISC); "?" as well */
     SPH_K_COUNT_
 } SphKernelId;
 
@@ -505,6 +517,43 @@ int sph_set_drag(SphHandle *h, const SphDragParams *params);
 int sph_get_drag(SphHandle *h, SphDragParams *out);
 int sph_drag_particle_host(const SphDragParams *params, double radius, double rho0, int64_t n, const float *in, float *out, int fast);
 int sph_drag_constants_host(const SphDragParams *params, double radius, double rho0, double *out);
+
+/* Heat: a temperature per fluid particle, conduction and Boussinesq buoyancy (opt-in).  method 0 = none (the default),
+   1 = conduction: Cleary and Monaghan 1999 with constant conductivity.  With R = x_i - x, gradW = gradW(R),
+   F = (R . gradW) / (|R|^2 + 0.01 h^2), j the fluid and k the boundary neighbours of an active fluid particle i (r < h, self excluded:
+   the pairs every other walk accepts; domain box, static, scripted and dynamic bodies, held emitter particles), rho the density the
+   method's viscous term reads (WCSPH: before the clamp of the equation of state), at the start of the non-pressure phase:
+     dT_i/dt = 2 alpha (rho0 / rho_i) [ sum_j (m_j / rho_j) (T_i - T_j) F_ij + sum_k c_k (T_i - T_k) F_ik ]
+               c_k = V_k (rest volume) where k's object has a temperature T_k (sph_set_object_temperature), else 0: adiabatic
+     T_i <- T_i + dt dT_i/dt                  (Jacobi: every sum reads the T of the previous step)
+     a_b_i = -beta (T_i - t_ref) g            (T_i: the previous step's);   v_i <- v_i + dt (a_np_i + ... + a_b_i)
+   A body is never heated or cooled by the fluid, and nothing receives a reaction.  alpha in m^2 / s (0: T is only carried), beta in
+   1 / K.  With beta == 0 nothing is added to v and WCSPH keeps its fused force pass (SPH_K_WCSPH_FORCES); with beta != 0 it takes its
+   unfused route and a_b enters the non-pressure acceleration where one is kept.  The update is explicit: it stays a convex combination
+   of neighbour temperatures while dt 2 alpha (rho0 / rho_i) sum c |F| <= 1; nothing here checks that.
+   Temperatures are stored by particle id, which must be the append order: SPH_ERR_UNSUPPORTED after sph_set_appended_ids / an upload of
+   SPH_F_PARTICLE_ID, and both are refused while the mode is on.  New particles (sph_append_particles, an emitter's layers) start at
+   their object's temperature, or at t_ref where it has none; so does every particle present when the mode is first switched on.
+   sph_set_thermal: legal at any time between steps; a null pointer or method 0 switches the mode off, restores the plain path bit for
+   bit and keeps the temperatures.  SPH_ERR_UNSUPPORTED: a PBF handle (either variant), a sharded handle (and sph_comm_set_slab while
+   the mode is on).  This library has no 2-D handles; the Python front end refuses 2-D scenes.  SPH_ERR_INVALID: an unknown method,
+   alpha or beta negative or not finite, t_ref not finite.
+   sph_set_object_temperature: object -1 (the domain box) .. SPH_MAX_OBJECTS - 1; has_T = 0 takes the temperature away.  Legal in either
+   mode and before the object exists.  A fluid object's (an emitter's) temperature is what its particles are inserted with from then
+   on -- and what its held layers, which are boundary particles, are held at.
+   sph_heat_pair_host: the walk's pair arithmetic (heat_pair of csrc/sph_thermal.hpp) from the kernels' own source on the CPU, strict
+   (fast = 0) or fast form.  in: n records of 12 floats (T_i, c_j, T_j, dx, dy, dz, r2, eps, gs, gx, gy, gz; the strict form reads the
+   gradient, the fast form gs with gradW = gs R); out: n floats, c_j (T_i - T_j) F_ij.  sph_heat_finish_host (an addition): what follows
+   the sum, and the buoyancy.  in: n records of 12 floats (sum, 2 alpha, rho0, rho_i, dt, T_i, -beta, t_ref, g[3], unused); out: n
+   records of 5 floats (dT/dt, T_new, a_b[3]).  Neither touches a device. */
+#define SPH_THERMAL_NONE 0
+#define SPH_THERMAL_CONDUCTION 1
+typedef struct { int32_t method; double alpha, beta, t_ref; } SphThermal;
+int sph_set_thermal(SphHandle *h, const SphThermal *params);
+int sph_get_thermal(SphHandle *h, SphThermal *out);
+int sph_set_object_temperature(SphHandle *h, int object_id, double temperature, int has_T);
+int sph_heat_pair_host(const float *in, int64_t n, float *out, int fast);
+int sph_heat_finish_host(const float *in, int64_t n, float *out, int fast);
 
 /* Device rigid integrator (opt-in; the host's "device" rigid backend).  The physics of the host's native backend
    (SPH/rigid_solver/host_rigid_solver.py integrate: semi-implicit Euler in float64 under gravity and the fluid wrench, gyroscopic

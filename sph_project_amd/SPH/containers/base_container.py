@@ -86,6 +86,12 @@ class BaseContainer:
         self.drag_method, self.drag, self.air_velocity, self.air_density = scene.drag_of(config, self.METHOD, geo.dim)
         if self.drag_method == "gissler" and engine_opts.get("slab"):
             raise ValueError("Configuration.dragMethod \"gissler\" is not available on a sharded scene (--gpus > 1)")
+        # heat: likewise
+        th = scene.thermal_of(config, self.METHOD, geo.dim)
+        self.thermal_method, self.thermal_diffusivity, self.thermal_expansion = th["method"], th["alpha"], th["beta"]
+        self.reference_temperature, self.domain_box_temperature, self.object_temperatures = th["t_ref"], th["box"], dict(th["objects"])
+        if self.thermal_method == "conduction" and engine_opts.get("slab"):
+            raise ValueError("Configuration.thermalMethod \"conduction\" is not available on a sharded scene (--gpus > 1)")
         # elastic solids: fluid objects that carry the key "elasticity"; likewise parsed and refused here
         self.elastic_objects = {}
         emitter = config.get_cfg("gravitationUpper") is not None
@@ -129,6 +135,16 @@ class BaseContainer:
                               "effective maximum step is the elastic limit")
                 self.cfl_max_time_step = self.elastic_dt_limit
                 self.cfl_min_time_step = min(self.cfl_min_time_step, self.cfl_max_time_step)
+        # The explicit heat update stays a convex combination of neighbour temperatures below twice this step (scene.thermal_dt_limit);
+        # past it this warns, as the elastic limit does: advice, and the step stays the author's.
+        self.thermal_dt_limit = None
+        if self.thermal_method == "conduction":
+            self.thermal_dt_limit = scene.thermal_dt_limit(self.thermal_diffusivity, float(geo.dh), float(geo.particle_diameter))
+            for key, dt in (("timeStepSize", float(config.get_cfg("timeStepSize"))),
+                            ("cflMaxTimeStepSize", self.cfl_max_time_step if self.cfl_method == "velocity" else None)):
+                if dt is not None and dt > self.thermal_dt_limit:
+                    warnings.warn(f"{key} {dt:g} exceeds the thermal limit {self.thermal_dt_limit:g} (0.5 / (2 thermalDiffusivity 1.25 S), "
+                                  "S the rest lattice's sum of V |F|); temperatures may leave the range of their neighbours'")
         self.material_rigid, self.material_fluid = scene.MATERIAL_RIGID, scene.MATERIAL_FLUID
         self.dx, self.particle_diameter, self.dh = geo.dx, geo.particle_diameter, geo.dh
         self.particle_spacing, self.V0 = geo.particle_spacing, geo.V0
@@ -216,6 +232,12 @@ class BaseContainer:
             self.engine.set_micropolar("micropolar", self.vorticity, self.viscosity_omega, self.inertia_inverse)
         if self.drag_method == "gissler":
             self.engine.set_drag("gissler", self.drag, self.air_density, self.air_velocity)
+        if self.thermal_method == "conduction":   # (before the first particle: every insertion starts at its object's temperature)
+            self.engine.set_thermal("conduction", self.thermal_diffusivity, self.thermal_expansion, self.reference_temperature)
+            for oid, temp in self.object_temperatures.items():
+                self.engine.set_object_temperature(oid, temp)
+            if self.domain_box_temperature is not None:
+                self.engine.set_object_temperature(-1, self.domain_box_temperature)
         if self.cfl_method == "velocity":
             self.engine.set_cfl("velocity", self.cfl_factor, self.cfl_min_time_step, self.cfl_max_time_step)
         # multi-GPU: engine_opts["slab"] = dict(rank=, nranks=, unique_id=<128 bytes>, cuts=[...]) -> this container
@@ -456,6 +478,8 @@ class BaseContainer:
                "velocity": self.engine.download(F.F_VELOCITY)[mask]}
         if self.vorticity_method == "micropolar":   # (only then: the reference's dump has the two keys above)
             out["angular_velocity"] = self.engine.download(F.F_ANGULAR_VELOCITY)[mask]
+        if self.thermal_method == "conduction":
+            out["temperature"] = self.engine.download(F.F_TEMPERATURE)[mask]
         return out
 
     def copy_to_vis_buffer(self, invisible_objects=[], dim=3):

@@ -80,6 +80,13 @@ class BaseSolver:
         self.drag = getattr(container, "drag", 1.0)
         self.air_velocity = tuple(getattr(container, "air_velocity", (0.0, 0.0, 0.0)))
         self.air_density = getattr(container, "air_density", 1.2041)
+        # heat: "none", or "conduction" with alpha (scene key thermalDiffusivity), beta (thermalExpansion) and T_ref
+        # (referenceTemperature); thermal_dt_limit: the explicit update's step limit on the rest lattice (advice), or None
+        self.thermal_method = getattr(container, "thermal_method", "none")
+        self.thermal_diffusivity = getattr(container, "thermal_diffusivity", 1.0e-4)
+        self.thermal_expansion = getattr(container, "thermal_expansion", 0.0)
+        self.reference_temperature = getattr(container, "reference_temperature", 0.0)
+        self.thermal_dt_limit = getattr(container, "thermal_dt_limit", None)
         # elastic solids: {object id: (E, nu)} of the scene's elastic objects
         self.elastic_objects = dict(getattr(container, "elastic_objects", {}))
         self.elastic_dt_limit = getattr(container, "elastic_dt_limit", None)   # 0.4 spacing / c of the stiffest object (advice), or None

@@ -35,6 +35,9 @@ F_ANGULAR_VELOCITY, F_MICROPOLAR_ACCEL = 44, 45
 F_ELASTIC_ACCEL, F_ELASTIC_DEFGRAD, F_ELASTIC_STRESS, F_ELASTIC_ROTATION = 46, 47, 48, 49
 # air drag, download only, written on active fluid rows by the last walk: a_drag and (n_i, w, C_D, A_un, y)
 F_DRAG_ACCEL, F_DRAG_TERMS = 50, 51
+# heat, current order: the temperatures (up- and download through the ids; an upload writes fluid rows only) and dT/dt of the last
+# walk (download only, valid until the next sort)
+F_TEMPERATURE, F_TEMPERATURE_RATE = 52, 53
 
 _FIELD_SPEC = {  # field -> (dtype, components)
     F_POSITION: (np.float32, 3), F_VELOCITY: (np.float32, 3), F_ACCELERATION: (np.float32, 3),
@@ -54,6 +57,7 @@ _FIELD_SPEC = {  # field -> (dtype, components)
     F_ANGULAR_VELOCITY: (np.float32, 3), F_MICROPOLAR_ACCEL: (np.float32, 3),
     F_ELASTIC_ACCEL: (np.float32, 3), F_ELASTIC_DEFGRAD: (np.float32, 9), F_ELASTIC_STRESS: (np.float32, 6),
     F_ELASTIC_ROTATION: (np.float32, 4), F_DRAG_ACCEL: (np.float32, 3), F_DRAG_TERMS: (np.float32, 5),
+    F_TEMPERATURE: (np.float32, 1), F_TEMPERATURE_RATE: (np.float32, 1),
 }
 
 # enum SphPhase
@@ -79,6 +83,7 @@ PH_EMIT = 31   # fluid emitters: the hold and the emission of the current step c
 PH_DRAG = 32   # air drag: the walk alone (PH_NON_PRESSURE / PH_CG_END then add the stored a_drag)
 PH_OUTFLOW = 33   # outflow: the mark and the count of the current step count alone (no sort)
 PH_CFL = 34       # adaptive time stepping: the reduce of the largest speed alone (no new step size)
+PH_HEAT = 35      # heat: the gather and the walk alone (PH_NON_PRESSURE / PH_CG_END then add the buoyancy of the gathered T)
 
 # enum SphKernelId
 KERNEL_IDS = ["hash_count", "scan", "scatter", "density", "non_pressure", "pressure_integrate",
@@ -99,6 +104,7 @@ K_EMIT = 34                  # SPH_K_EMIT: the hold launch and the emit launch o
 K_DRAG = 35                  # SPH_K_DRAG: the walk of the air drag
 K_OUTFLOW = 36               # SPH_K_OUTFLOW: the mark launch of the outflow volumes / of a removal by id
 K_CFL = 37                   # SPH_K_CFL: the reduce of the largest speed (adaptive time stepping)
+K_HEAT = 38                  # SPH_K_HEAT: the gather + walk of the heat conduction
 RIGID_MOTION_MAX_KEYS = 64
 MAX_EMITTERS = 8             # SPH_MAX_EMITTERS
 EMITTER_MAX_HOLD = 8         # SPH_EMITTER_MAX_HOLD
@@ -370,6 +376,36 @@ def surface_tension_kernels_host(h, r, fast=False):
     if rc:
         raise SphError(f"sph_surface_tension_kernels_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
     return c_out, a_out
+
+
+THERMAL_METHODS = {"none": 0, "conduction": 1}
+
+
+class SphThermal(C.Structure):
+    _fields_ = [("method", C.c_int32), ("alpha", C.c_double), ("beta", C.c_double), ("t_ref", C.c_double)]
+
+
+def heat_pair_host(records, fast=False):
+    """The heat walk's pair arithmetic from the kernels' own source run on the CPU (sph_heat_pair_host): records (n, 12) float32 =
+    (T_i, c_j, T_j, dx, dy, dz, r2, eps, gs, gx, gy, gz) -> (n,) float32, each pair's term c_j (T_i - T_j) F_ij.  No device."""
+    rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 12)
+    out = np.empty(rec.shape[0], np.float32)
+    rc = load().sph_heat_pair_host(_ptr(rec), rec.shape[0], _ptr(out), int(bool(fast)))
+    if rc:
+        raise SphError(f"sph_heat_pair_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
+    return out
+
+
+def heat_finish_host(records, fast=False):
+    """What follows the walk's sum and the buoyancy (heat_finish, heat_buoyancy of csrc/sph_thermal.hpp) run on the CPU
+    (sph_heat_finish_host): records (n, 12) float32 = (sum, 2 alpha, rho0, rho_i, dt, T_i, -beta, T_ref, g[3], unused) -> (n, 5)
+    float32 = (dT/dt, T_new, a_b[3]).  No device."""
+    rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 12)
+    out = np.empty((rec.shape[0], 5), np.float32)
+    rc = load().sph_heat_finish_host(_ptr(rec), rec.shape[0], _ptr(out), int(bool(fast)))
+    if rc:
+        raise SphError(f"sph_heat_finish_host failed ({rc}): " + (load().sph_last_error(None) or b"").decode(), rc)
+    return out
 
 
 VORTICITY_METHODS = {"none": 0, "micropolar": 1}
@@ -746,6 +782,11 @@ _SIGNATURES = [
     ("sph_outflow_test_host", C.c_int, [C.POINTER(SphOutflow), _VP, C.c_int, _VP]),
     ("sph_outflow_active_host", C.c_int, [C.POINTER(SphOutflow), C.c_double, C.c_int64]),
     ("sph_set_time_step", C.c_int, [_VP, C.c_double]),
+    ("sph_set_thermal", C.c_int, [_VP, C.POINTER(SphThermal)]),
+    ("sph_get_thermal", C.c_int, [_VP, C.POINTER(SphThermal)]),
+    ("sph_set_object_temperature", C.c_int, [_VP, C.c_int, C.c_double, C.c_int]),
+    ("sph_heat_pair_host", C.c_int, [_VP, C.c_int64, _VP, C.c_int]),
+    ("sph_heat_finish_host", C.c_int, [_VP, C.c_int64, _VP, C.c_int]),
     ("sph_set_cfl", C.c_int, [_VP, C.POINTER(SphCflParams)]),
     ("sph_get_cfl", C.c_int, [_VP, C.POINTER(SphCflParams)]),
     ("sph_get_time_state", C.c_int, [_VP, C.POINTER(SphTimeState)]),
@@ -1082,6 +1123,29 @@ class Engine(NativeObject):
         """method: "none" / "micropolar" (or 0 / 1); nu_t: transfer coefficient, zeta: angular dissipation, theta_inv: inverse microinertia."""
         p = SphMicropolarParams(int(VORTICITY_METHODS.get(method, method)), float(nu_t), float(zeta), float(theta_inv))
         self._chk(self.lib.sph_set_micropolar(self.h, C.byref(p)), "sph_set_micropolar")
+
+    # -- heat
+    def set_thermal(self, method="conduction", alpha=1.0e-4, beta=0.0, t_ref=0.0):
+        """method: "none" / "conduction" (or 0 / 1; None: off); alpha: thermal diffusivity, m^2 / s; beta: thermal expansion, 1 / K (0: no
+        buoyancy); t_ref: the reference temperature (a_b = -beta (T - t_ref) g, and what particles without a temperature of their own
+        are inserted with)."""
+        if method is None:
+            self._chk(self.lib.sph_set_thermal(self.h, None), "sph_set_thermal")
+            return
+        p = SphThermal(int(THERMAL_METHODS.get(method, method)), float(alpha), float(beta), float(t_ref))
+        self._chk(self.lib.sph_set_thermal(self.h, C.byref(p)), "sph_set_thermal")
+
+    def get_thermal(self):
+        p = SphThermal()
+        self._chk(self.lib.sph_get_thermal(self.h, C.byref(p)), "sph_get_thermal")
+        return {"method": {v: k for k, v in THERMAL_METHODS.items()}[p.method], "alpha": p.alpha, "beta": p.beta, "t_ref": p.t_ref}
+
+    def set_object_temperature(self, object_id, temperature=None):
+        """A fluid object: the temperature its particles are inserted with from now on; a rigid object (-1: the domain box): the
+        temperature it is held at.  None: none of its own (fluid: the reference temperature; rigid: adiabatic)."""
+        has = temperature is not None
+        self._chk(self.lib.sph_set_object_temperature(self.h, int(object_id), float(temperature) if has else 0.0, int(has)),
+                  "sph_set_object_temperature")
 
     def get_micropolar(self):
         p = SphMicropolarParams()

@@ -128,8 +128,17 @@ struct SphHandle : ErrSink {
     bool of_removed_any = false;
     int id_next = 0;
     CflHost cfl;
+    // heat (sph_set_thermal): the per-object temperatures as the host keeps them, by the low byte of the meta word (object id + 1);
+    // the device copy (State::heat_obj_T) follows every change while it exists
+    bool heat_obj_has[256] = {};
+    double heat_obj_T_h[256] = {};
 };
 static inline int next_id(const SphHandle *h);
+// heat: the temperature a particle of this object (-1: the domain box) is inserted with
+static inline float heat_insert_T(const SphHandle *h, int object_id) {
+    const int b = (object_id + 1) & 0xff;
+    return (float)(h->heat_obj_has[b] ? h->heat_obj_T_h[b] : h->st.heat_t_ref);
+}
 static long long em_reserved(const SphHandle *h);
 static int em_of_object(const SphHandle *h, int object_id);
 
@@ -468,6 +477,7 @@ extern "C" int sph_append_particles(SphHandle *h, int object_id, int n, const fl
     HIPCHK(h, hipMemcpy(s.rho.cur() + off, hr.data(), sizeof(float) * n, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(s.prs + off, hpr.data(), sizeof(float) * n, hipMemcpyHostToDevice));
     if (s.orig.cur()) HIPCHK(h, hipMemcpy(s.orig.cur() + off, hp.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
+    if (s.heat_T_home) h->L->heat_fill(s, id0, n, heat_insert_T(h, object_id));   // (heat: the new rows start at their object's temperature)
     if (object_id >= 0 && object_id < SPH_NOBJ) {   // the id range of the object (ids = append order)
         if (h->obj_n[object_id] == 0) h->obj_first[object_id] = id0;
         else if (h->obj_first[object_id] + h->obj_n[object_id] != id0) h->obj_split[object_id] = true;
@@ -496,6 +506,7 @@ extern "C" int sph_set_appended_ids(SphHandle *h, int n, const int32_t *ids) {
     if (h) { int rc = slab_settle_if_needed(h); if (rc) return rc; }
     if (!h || !ids || n < 0 || n > h->n) return fail(h, SPH_ERR_INVALID, "set_appended_ids: bad arguments");
     if (n == 0) return SPH_OK;
+    if (h->st.heat_on) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: heat is on (its temperatures are stored by id, in append order)");
     if (h->st.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: the micropolar model is on (its angular velocities are stored by id, in append order)");
     if (h->st.el_marked) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: an elastic object exists (its rest lists are stored by id, in append order)");
     if (h->em_n > 0) return fail(h, SPH_ERR_UNSUPPORTED, "set_appended_ids: an emitter is set (its held layers are found by id, in append order)");
@@ -822,6 +833,103 @@ extern "C" int sph_drag_particle_host(const SphDragParams *p, double radius, dou
         else drag_finish<false>(k, q[0], q[1], q[2], q[3], q[4], q[5], o);
         float *d = out + 7 * r;
         d[0] = o.ax; d[1] = o.ay; d[2] = o.az; d[3] = o.w; d[4] = o.cd; d[5] = o.a_un; d[6] = o.y;
+    }
+    return SPH_OK;
+}
+
+// ---------------------------------------------------------------------------------- heat
+#include "sph_thermal.hpp"
+static int heat_upload_table(SphHandle *h) {
+    State &s = h->st;
+    if (!s.heat_obj_T) return SPH_OK;
+    float tab[256];
+    for (int b = 0; b < 256; ++b) tab[b] = h->heat_obj_has[b] ? (float)h->heat_obj_T_h[b] : HT_ADIABATIC;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(s.stream));   // (a walk in flight reads the table)
+    HIPCHK(h, hipMemcpy(s.heat_obj_T, tab, sizeof(tab), hipMemcpyHostToDevice));
+    return SPH_OK;
+}
+
+extern "C" int sph_set_thermal(SphHandle *h, const SphThermal *p) {
+    if (!h) return SPH_ERR_INVALID;
+    State &s = h->st;
+    if (!p || p->method == SPH_THERMAL_NONE) { s.heat_on = 0; return SPH_OK; }   // (the values and the temperatures stay)
+    if (p->method != SPH_THERMAL_CONDUCTION) return fail(h, SPH_ERR_INVALID, "sph_set_thermal: method %d is neither 0 (none) nor 1 (conduction)", p->method);
+    if (h->prm.method == SPH_METHOD_PBF) return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_thermal: not on a PBF handle (either variant)");
+    if (s.slab_active || h->comm.slab_ready)
+        return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_thermal: not on a sharded handle (the ghosts' temperatures would need an exchange)");
+    if (!(p->alpha >= 0.0) || !std::isfinite(p->alpha)) return fail(h, SPH_ERR_INVALID, "sph_set_thermal: alpha %g is not a finite number >= 0", p->alpha);
+    if (!(p->beta >= 0.0) || !std::isfinite(p->beta)) return fail(h, SPH_ERR_INVALID, "sph_set_thermal: beta %g is not a finite number >= 0", p->beta);
+    if (!std::isfinite(p->t_ref)) return fail(h, SPH_ERR_INVALID, "sph_set_thermal: t_ref %g is not finite", p->t_ref);
+    if (s.ids_custom)
+        return fail(h, SPH_ERR_UNSUPPORTED, "sph_set_thermal: particle ids were set from outside (sph_set_appended_ids / SPH_F_PARTICLE_ID): "
+                                            "the temperatures are stored by id and need the append order");
+    s.heat_alpha = p->alpha; s.heat_beta = p->beta; s.heat_t_ref = p->t_ref;
+    HIPCHK(h, hipSetDevice(h->device));
+    // (each buffer on its own: a call that failed half way is finished by the next one)
+    if (!s.heat_T_sorted) { int rc = dalloc(h, &s.heat_T_sorted, (size_t)s.cap); if (rc) return rc; }
+    if (!s.heat_rate) { int rc = dalloc(h, &s.heat_rate, (size_t)s.cap); if (rc) return rc; }
+    if (!s.heat_obj_T) { int rc = dalloc(h, &s.heat_obj_T, (size_t)256); if (rc) return rc; { int rc2 = heat_upload_table(h); if (rc2) return rc2; } }
+    if (!s.heat_T_home) {   // the home array exists only once it holds every present particle's temperature
+        // every particle present: its object's temperature, or t_ref (later ones: sph_append_particles, the emitters' slot)
+        const size_t n = (size_t)h->n;
+        std::vector<float> home((size_t)s.cap, (float)s.heat_t_ref);
+        if (n) {
+            std::vector<int> id(n), mt(n);
+            HIPCHK(h, hipStreamSynchronize(s.stream));
+            HIPCHK(h, hipMemcpy(id.data(), s.pid.cur(), n * 4, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(mt.data(), s.meta.cur(), n * 4, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n; ++i) {
+                if (id[i] < 0 || id[i] >= s.cap) return fail(h, SPH_ERR_INVALID, "sph_set_thermal: particle id %d outside [0, %d)", id[i], s.cap);
+                home[(size_t)id[i]] = heat_insert_T(h, META_OBJ(mt[i]));
+            }
+        }
+        float *dev = nullptr;
+        { int rc = dalloc(h, &dev, (size_t)s.cap); if (rc) return rc; }
+        HIPCHK(h, hipMemcpy(dev, home.data(), (size_t)s.cap * 4, hipMemcpyHostToDevice));
+        s.heat_T_home = dev;
+    }
+    s.heat_on = 1;
+    return SPH_OK;
+}
+
+extern "C" int sph_get_thermal(SphHandle *h, SphThermal *out) {
+    if (!h || !out) return SPH_ERR_INVALID;
+    out->method = h->st.heat_on ? SPH_THERMAL_CONDUCTION : SPH_THERMAL_NONE;
+    out->alpha = h->st.heat_alpha; out->beta = h->st.heat_beta; out->t_ref = h->st.heat_t_ref;
+    return SPH_OK;
+}
+
+extern "C" int sph_set_object_temperature(SphHandle *h, int object_id, double temperature, int has_T) {
+    if (!h) return SPH_ERR_INVALID;
+    if (object_id < -1 || object_id >= SPH_MAX_OBJECTS) return fail(h, SPH_ERR_INVALID, "sph_set_object_temperature: object id %d outside [-1, %d)", object_id, SPH_MAX_OBJECTS);
+    if (has_T && !std::isfinite(temperature)) return fail(h, SPH_ERR_INVALID, "sph_set_object_temperature: temperature %g is not finite", temperature);
+    if (has_T && !(fabs(temperature) < 1.0e38)) return fail(h, SPH_ERR_INVALID, "sph_set_object_temperature: temperature %g is outside (-1e38, 1e38)", temperature);
+    h->heat_obj_has[object_id + 1] = has_T != 0;
+    h->heat_obj_T_h[object_id + 1] = has_T ? temperature : 0.0;
+    return heat_upload_table(h);
+}
+
+extern "C" int sph_heat_pair_host(const float *in, int64_t n, float *out, int fast) {
+    if (n < 0) return fail(nullptr, SPH_ERR_INVALID, "sph_heat_pair_host: negative count");
+    if (n > 0 && (!in || !out)) return fail(nullptr, SPH_ERR_INVALID, "sph_heat_pair_host: null argument");
+    for (int64_t k = 0; k < n; ++k) {
+        const float *q = in + 12 * k;
+        out[k] = fast ? heat_pair<true>(q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9], q[10], q[11])
+                      : heat_pair<false>(q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9], q[10], q[11]);
+    }
+    return SPH_OK;
+}
+
+extern "C" int sph_heat_finish_host(const float *in, int64_t n, float *out, int fast) {
+    if (n < 0) return fail(nullptr, SPH_ERR_INVALID, "sph_heat_finish_host: negative count");
+    if (n > 0 && (!in || !out)) return fail(nullptr, SPH_ERR_INVALID, "sph_heat_finish_host: null argument");
+    for (int64_t k = 0; k < n; ++k) {
+        const float *q = in + 12 * k;
+        float *o = out + 5 * k;
+        if (fast) heat_finish<true>(q[0], q[1], q[2], q[3], q[4], q[5], o, o + 1);
+        else heat_finish<false>(q[0], q[1], q[2], q[3], q[4], q[5], o, o + 1);
+        heat_buoyancy(q[6], q[5], q[7], q[8], q[9], q[10], o + 2);
     }
     return SPH_OK;
 }
@@ -1598,6 +1706,10 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
             if (!s.dr_on) return fail(h, SPH_ERR_INVALID, "SPH_PH_DRAG: the air drag is off (sph_set_drag)");
             ph_drag(h);
             break;
+        case SPH_PH_HEAT:
+            if (!s.heat_on) return fail(h, SPH_ERR_INVALID, "SPH_PH_HEAT: heat is off (sph_set_thermal)");
+            ph_heat(h);
+            break;
         case SPH_PH_ELASTIC:
             if (!s.el_marked) return fail(h, SPH_ERR_INVALID, "SPH_PH_ELASTIC: no elastic object (sph_set_elastic_object)");
             ph_elastic(h);
@@ -1609,7 +1721,7 @@ extern "C" int sph_run_phase(SphHandle *h, int phase) {
             ProfScope p(h, SPH_K_RIGID_CONTACT); h->L->rigid_contact(s);
         } break;
         case SPH_PH_CG_PREPARE: case SPH_PH_CG_AP: case SPH_PH_CG_UPDATE_XR: case SPH_PH_CG_UPDATE_P: case SPH_PH_CG_END:
-            { int rc = cg_run_phase(h, phase); if (rc) return rc; if (phase == SPH_PH_CG_END) { ph_micropolar_apply(h); ph_elastic_apply(h); ph_drag_apply(h); } } break;   // (micropolar model: + the STORED a_mp; elastic solids: + the STORED a_el; air drag: + the STORED a_drag)
+            { int rc = cg_run_phase(h, phase); if (rc) return rc; if (phase == SPH_PH_CG_END) { ph_micropolar_apply(h); ph_elastic_apply(h); ph_drag_apply(h); ph_heat_apply(h); } } break;   // (micropolar model: + the STORED a_mp; elastic solids: + the STORED a_el; air drag: + the STORED a_drag)
         default: { int rc = method_run_phase(h, phase); if (rc) return rc; }
     }
     int rc = check_async(h); if (rc) return rc;
@@ -1737,6 +1849,29 @@ extern "C" int sph_download(SphHandle *h, int field, void *dst, size_t bytes) {
         }
         float *d = (float *)dst;
         for (size_t i = 0; i < n; ++i) { d[5 * i] = a[i].w; d[5 * i + 1] = t[i].x; d[5 * i + 2] = t[i].y; d[5 * i + 3] = t[i].z; d[5 * i + 4] = t[i].w; }
+        return SPH_OK;
+    }
+    if (field == SPH_F_TEMPERATURE) {   // at home by particle id -> the current order; a row that is not fluid: what its object is held at
+        if (!s.heat_T_home) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated (sph_set_thermal)", field);
+        if (bytes != n * 4) return fail(h, SPH_ERR_INVALID, "download: field %d needs %zu bytes, got %zu", field, n * 4, bytes);
+        std::vector<float> home((size_t)s.cap);
+        std::vector<int> id(n), mt(n);
+        HIPCHK(h, hipMemcpy(home.data(), s.heat_T_home, (size_t)s.cap * 4, hipMemcpyDeviceToHost));
+        if (n) {
+            HIPCHK(h, hipMemcpy(id.data(), s.pid.cur(), n * 4, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(mt.data(), s.meta.cur(), n * 4, hipMemcpyDeviceToHost));
+        }
+        float *d = (float *)dst;
+        for (size_t i = 0; i < n; ++i) {
+            if (id[i] < 0 || id[i] >= s.cap) return fail(h, SPH_ERR_INVALID, "download: particle id %d outside [0, %d)", id[i], s.cap);
+            d[i] = META_MAT(mt[i]) == SPH_MAT_FLUID ? home[(size_t)id[i]] : heat_insert_T(h, META_OBJ(mt[i]));
+        }
+        return SPH_OK;
+    }
+    if (field == SPH_F_TEMPERATURE_RATE) {
+        if (!s.heat_rate) return fail(h, SPH_ERR_UNSUPPORTED, "download: field %d not allocated (sph_set_thermal)", field);
+        if (bytes != n * 4) return fail(h, SPH_ERR_INVALID, "download: field %d needs %zu bytes, got %zu", field, n * 4, bytes);
+        if (n) HIPCHK(h, hipMemcpy(dst, s.heat_rate, n * 4, hipMemcpyDeviceToHost));
         return SPH_OK;
     }
     if (field == SPH_F_ANGULAR_VELOCITY) {   // at home by particle id -> the current order; library frame -> scene frame, axial
@@ -1912,6 +2047,26 @@ extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes
         return SPH_OK;
     }
     if (field == SPH_F_ELASTIC_ROTATION) return el_upload_rotation(h, (const float *)src, bytes);
+    if (field == SPH_F_TEMPERATURE) {   // the current order -> home by particle id; fluid rows only
+        if (!s.heat_T_home) return fail(h, SPH_ERR_UNSUPPORTED, "upload: field %d not allocated (sph_set_thermal)", field);
+        if (bytes != n * 4) return fail(h, SPH_ERR_INVALID, "upload: field %d needs %zu bytes", field, n * 4);
+        std::vector<float> home((size_t)s.cap);
+        std::vector<int> id(n), mt(n);
+        HIPCHK(h, hipMemcpy(home.data(), s.heat_T_home, (size_t)s.cap * 4, hipMemcpyDeviceToHost));
+        if (n) {
+            HIPCHK(h, hipMemcpy(id.data(), s.pid.cur(), n * 4, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(mt.data(), s.meta.cur(), n * 4, hipMemcpyDeviceToHost));
+        }
+        const float *f = (const float *)src;
+        for (size_t i = 0; i < n; ++i) {
+            if (id[i] < 0 || id[i] >= s.cap) return fail(h, SPH_ERR_INVALID, "upload: particle id %d outside [0, %d)", id[i], s.cap);
+            if (META_MAT(mt[i]) != SPH_MAT_FLUID) continue;
+            if (!std::isfinite(f[i])) return fail(h, SPH_ERR_INVALID, "upload: temperature %g of row %zu is not finite", f[i], i);
+            home[(size_t)id[i]] = f[i];
+        }
+        HIPCHK(h, hipMemcpy(s.heat_T_home, home.data(), (size_t)s.cap * 4, hipMemcpyHostToDevice));
+        return SPH_OK;
+    }
     if (field == SPH_F_ANGULAR_VELOCITY) {   // the current order -> home by particle id; scene frame -> library frame, axial
         if (!s.mp_w_home) return fail(h, SPH_ERR_UNSUPPORTED, "upload: field %d not allocated (sph_set_micropolar)", field);
         if (bytes != n * 12) return fail(h, SPH_ERR_INVALID, "upload: field %d needs %zu bytes", field, n * 12);
@@ -1932,6 +2087,7 @@ extern "C" int sph_upload(SphHandle *h, int field, const void *src, size_t bytes
     }
     if (field == SPH_F_PARTICLE_ID) {  // global ids when a scene is split over ranks
         if (bytes != n * 4) return fail(h, SPH_ERR_INVALID, "upload: size mismatch");
+        if (s.heat_on) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while heat is on (its temperatures are stored by id, in append order)");
         if (s.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while the micropolar model is on (its angular velocities are stored by id, in append order)");
         if (s.el_marked) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while an elastic object exists (its rest lists are stored by id, in append order)");
         if (h->em_n > 0) return fail(h, SPH_ERR_UNSUPPORTED, "upload: SPH_F_PARTICLE_ID while an emitter is set (its held layers are found by id, in append order)");

@@ -194,6 +194,7 @@ extern "C" int sph_comm_set_slab(SphHandle *h, int z_lo, int z_hi) {
     if (h->n > 0) return fail(h, SPH_ERR_INVALID, "comm_set_slab: set the slab before particles are appended");
     if (s.st_akinci) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: the Akinci surface tension is on (the ghosts' normals would need an exchange)");
     if (s.mp_on) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: the micropolar model is on (the ghosts' angular velocities would need an exchange)");
+    if (s.heat_on) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: heat is on (the ghosts' temperatures would need an exchange)");
     if (s.dr_on) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: the air drag is on (sharded handles are not done: sph_set_drag)");
     if (s.el_marked) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: an elastic object exists (its rest lists name particles by id across every slab)");
     if (h->em_n > 0) return fail(h, SPH_ERR_UNSUPPORTED, "comm_set_slab: an emitter is set (its schedule knows one particle count)");

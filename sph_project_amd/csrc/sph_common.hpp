@@ -759,7 +759,22 @@ struct State {
     int dr_on = 0;
     double dr_k = 1.0, dr_rho_a = 1.2041, dr_u[3] = {0.0, 0.0, 0.0}, dr_u_lib[3] = {0.0, 0.0, 0.0}, dr_radius = 0.0, dr_rho_l = 0.0;
     float4 *dr_acc = nullptr, *dr_terms = nullptr;
+    // Heat (sph_set_thermal; sph_thermal.hpp): off unless heat_on; the buffers are allocated when the mode is first switched on.
+    // heat_T_home[particle id]: the temperatures AT HOME (no sort moves them; ids = append order, as mp_w_home: the mode and ids from
+    // outside exclude each other); heat_T_sorted: their copy in sorted order, for the walk's candidate records and the buoyancy;
+    // heat_rate: dT/dt of the last walk in sorted order (valid until the next sort); heat_obj_T: the per-object table on the device,
+    // indexed by the low byte of the meta word (object id + 1; 0: the domain box), HT_ADIABATIC where the object has no temperature.
+    int heat_on = 0;
+    double heat_alpha = 1.0e-4, heat_beta = 0.0, heat_t_ref = 0.0;
+    float *heat_T_home = nullptr, *heat_T_sorted = nullptr, *heat_rate = nullptr, *heat_obj_T = nullptr;
 };
+
+// Where the non-pressure acceleration is kept, or null where nobody keeps one: PCISPH's own buffer, else the buffer the Akinci pass
+// writes and the micropolar model and the air drag make every method keep.  ONE statement of the rule for the non-pressure launcher
+// and for every launch that adds an acceleration behind it.
+static inline float4 *kept_np_acc(const State &s) {
+    return s.np_acc_out ? s.np_acc_out : ((s.st_akinci || s.mp_on || s.dr_on) ? s.st_acc : nullptr);
+}
 
 // What a list sort's gather left behind for the density pass launched next (Launch::scatter_stable, density_next): thread d of a tile does
 // out[d] = in[inv[d]] for velocity + mass, meta word and particle id -- exactly what k_gather_prep does otherwise -- in the prologue of
@@ -807,6 +822,9 @@ struct Launch {
     void (*elastic_apply)(State &);      // ... and v += dt a_el (+ the kept non-pressure acceleration) behind it
     void (*drag)(State &);               // air drag: the walk (State::dr_acc, dr_terms), before non_pressure
     void (*drag_apply)(State &);         // ... and v += dt a_drag (+ the kept non-pressure acceleration) behind it, behind the elastic solids'
+    void (*heat)(State &);               // heat: gather T, the walk (State::heat_T_home, heat_rate), before non_pressure
+    void (*heat_apply)(State &);         // ... and v += dt a_b (+ the kept non-pressure acceleration) behind it, behind the air drag's
+    void (*heat_fill)(State &, int first_id, int count, float T);   // rows of new particles: heat_T_home[first_id, first_id + count) = T
     void (*elastic_capture)(State &, const ElCaptureArgs &);   // one object's rest configuration, on the cell lists of the sort that has just run
     void (*non_pressure)(State &, const float4 *visc_vel);   // visc_vel: velocities for the viscous term (implicit viscosity: cg_x), null: the particles' own
     void (*pressure_integrate)(State &);

@@ -373,7 +373,7 @@ static void l_elastic_apply(State &s) {
     const int n = s.c.n;
     if (n == 0 || s.el_nobj == 0) return;
     hipLaunchKernelGGL(k_elastic_apply, dim3(cdiv(n, 256)), dim3(256), 0, s.stream, s.c, s.el_mask, s.meta.cur(), s.el_acc, s.velm.cur(),
-                       s.np_acc_out ? s.np_acc_out : ((s.st_akinci || s.mp_on || s.dr_on) ? s.st_acc : nullptr));
+                       kept_np_acc(s));
 }
 // the capture of one object on the cell lists of the sort that has just run (arrays in sorted order, nothing left to a density pass)
 static void l_elastic_capture(State &s, const ElCaptureArgs &a) {

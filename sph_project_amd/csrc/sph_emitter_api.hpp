@@ -189,6 +189,11 @@ static int ph_emit(SphHandle *h, long long k, int stage = 0) {
     if (stage != 2 && ha.nlayers > 0 && h->n > 0) { ProfScope p(h, SPH_K_EMIT); h->L->emit_hold(s, ha); }
     if (stage == 1 || ea.nlayers <= 0) return SPH_OK;
     { ProfScope p(h, SPH_K_EMIT); h->L->emit(s, ea); }
+    if (s.heat_T_home)   // heat: the newborn rows start at their emitter's temperature (ids and counts are known here in closed form)
+        for (int t = 0; t < ea.nlayers; ++t) {
+            const EmHost &m = h->em[ea.emitter[t]];
+            h->L->heat_fill(s, ea.id_first[t], m.layer_n, heat_insert_T(h, m.e.object_id));
+        }
     // the counts, as sph_append_particles changes them
     for (int t = 0; t < ea.nlayers; ++t) {
         EmHost &m = h->em[ea.emitter[t]];

@@ -23,6 +23,7 @@ namespace SPH_NS {
 #include "sph_surface_tension.hpp"
 #include "sph_micropolar.hpp"
 #include "sph_drag.hpp"
+#include "sph_thermal.hpp"
 #include "sph_solvers.hpp"
 #include "sph_cg.hpp"
 #include "sph_halo.hpp"
@@ -376,13 +377,38 @@ void l_drag_apply(State &s) {
                        s.np_acc_out ? s.np_acc_out : s.st_acc);
 }
 
+// heat (sph_thermal.hpp), on the masks of the last sort: T in sorted order first, then the walk: dT/dt and the new T
+void l_heat(State &s) {
+    const int n = s.c.n;
+    if (n == 0) return;
+    const float *rho_src = s.visc_rho_raw ? s.rho_raw : s.rho.cur();
+    const HeatConsts k = heat_consts(s.heat_alpha, s.heat_beta, s.heat_t_ref);
+    hipLaunchKernelGGL(k_heat_gather, dim3(cdiv(n, 256)), dim3(256), 0, s.stream, n, s.pid.cur(), s.heat_T_home, s.heat_T_sorted);
+    launch_pass_af(s, 2, [&](auto af) {
+        return HeatPass<af>{s.posv.cur(), s.velm.cur(), s.meta.cur(), rho_src, s.heat_T_sorted, s.pid.cur(), s.heat_obj_T, s.heat_T_home, s.heat_rate, k};
+    });
+}
+// v += dt a_b on the velocities the non-pressure phase left, acc += a_b where a non-pressure acceleration is kept
+void l_heat_apply(State &s) {
+    const int n = s.c.n;
+    if (n == 0) return;
+    const HeatConsts k = heat_consts(s.heat_alpha, s.heat_beta, s.heat_t_ref);
+    hipLaunchKernelGGL(k_heat_apply, dim3(cdiv(n, 256)), dim3(256), 0, s.stream, s.c, s.meta.cur(), s.heat_T_sorted, k, s.velm.cur(),
+                       kept_np_acc(s));
+}
+// the rows of new particles, by id
+void l_heat_fill(State &s, int first_id, int count, float T) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_heat_fill, dim3(cdiv(count, 256)), dim3(256), 0, s.stream, s.heat_T_home, first_id, count, T);
+}
+
 void l_non_pressure(State &s, const float4 *visc_vel) {
-    float4 *np_acc = s.np_acc_out ? s.np_acc_out : ((s.mp_on || s.dr_on) ? s.st_acc : nullptr);   // (micropolar model, air drag: every method keeps it)
+    float4 *np_acc = kept_np_acc(s);   // (micropolar model, air drag: every method keeps it; Akinci: its pass writes it)
     if (s.st_akinci) {   // cohesion + curvature + adhesion in the place of the reference's term, on the stored normals
         StSpline sp = st_spline(s.st_h);
         sp.cA = (float)(s.st_beta * 0.007 / pow(s.st_h, 3.25));
         const float g2r = (float)(s.st_gamma * 2.0 * (double)s.c.rho0);
-        float4 *acc_out = s.np_acc_out ? s.np_acc_out : s.st_acc;
+        float4 *acc_out = np_acc;
         const int adhesion = s.st_beta != 0.0;
         dispatch_bool(s.c.all_fluid, [&](auto af) { launch_non_pressure<AkinciNonPressurePass<af>>(s, acc_out, visc_vel, s.st_normal, sp, g2r, adhesion); });
     } else if (s.poly6) {   // PBF: poly6 surface tension, spiky viscosity (PBF.py:22-48)
@@ -580,6 +606,9 @@ const Launch *SPH_LAUNCH_FN() {
         L.micropolar_apply = l_micropolar_apply;
         L.drag = l_drag;
         L.drag_apply = l_drag_apply;
+        L.heat = l_heat;
+        L.heat_apply = l_heat_apply;
+        L.heat_fill = l_heat_fill;
         L.pressure_integrate = l_pressure_integrate;
         L.wcsph_forces = l_wcsph_forces;
         L.rigid_volume = l_rigid_volume;

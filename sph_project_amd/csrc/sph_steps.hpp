@@ -222,22 +222,38 @@ static void ph_drag_apply(SphHandle *h) {
     h->L->drag_apply(h->st);
 }
 
+// Heat (sph_set_thermal): the gather and the walk read positions, densities and last step's T -- no velocity, nothing another pass of
+// the phase writes -- so they run in front of the non-pressure pass (WCSPH's fused route: in front of its force pass); the buoyancy
+// v += dt a_b follows behind it, behind the air drag's, and only with beta != 0.  Nothing without the mode.
+static void ph_heat(SphHandle *h) {
+    if (!h->st.heat_on) return;
+    ProfScope p(h, SPH_K_HEAT);
+    h->L->heat(h->st);
+}
+static void ph_heat_apply(SphHandle *h) {
+    if (!h->st.heat_on || h->st.heat_beta == 0.0) return;
+    ProfScope p(h, SPH_K_MISC);
+    h->L->heat_apply(h->st);
+}
+
 // base_solver.py:190 compute_non_pressure_acceleration + :643 update_fluid_velocity
 // walks = false (SPH_PH_NON_PRESSURE): the Akinci pass runs on the normals the last SPH_PH_SURFACE_NORMALS / step stored, and the
 // micropolar model's a_mp is the one the last SPH_PH_MICROPOLAR / step stored (likewise a_el and a_drag)
 static int run_non_pressure(SphHandle *h, bool walks = true) {
-    if (walks) { ph_surface_normals(h); ph_micropolar(h); ph_elastic(h); ph_drag(h); }   // (positions and densities do not change under the CG solve: its end reads these too)
+    if (walks) { ph_surface_normals(h); ph_micropolar(h); ph_elastic(h); ph_drag(h); ph_heat(h); }   // (positions and densities do not change under the CG solve: its end reads these too)
     if (h->prm.viscosity_implicit) {
         int rc = implicit_viscosity_non_pressure(h); if (rc) return rc;
         ph_micropolar_apply(h);
         ph_elastic_apply(h);
         ph_drag_apply(h);
+        ph_heat_apply(h);
         return SPH_OK;
     }
     { ProfScope p(h, SPH_K_NON_PRESSURE); h->L->non_pressure(h->st, nullptr); }
     ph_micropolar_apply(h);
     ph_elastic_apply(h);
     ph_drag_apply(h);
+    ph_heat_apply(h);
     return SPH_OK;
 }
 
@@ -245,7 +261,7 @@ static int wcsph_step(SphHandle *h) {
     State &s = h->st;
     // sharded: + migration / ghost exchange; over the push transport a plain WCSPH step needs nothing back from the device
     // (slab_neighbor_search_push, "async"): implicit viscosity and the unfused force passes launch exact grids instead
-    const bool fused = !h->prm.viscosity_implicit && !s.st_akinci && !s.mp_on && !s.el_marked && !s.dr_on;   // (the Akinci surface tension and the micropolar walk need the densities of ALL neighbours first; an elastic object adds a_el behind the non-pressure pass, the air drag a_drag)
+    const bool fused = !h->prm.viscosity_implicit && !s.st_akinci && !s.mp_on && !s.el_marked && !s.dr_on && !(s.heat_on && s.heat_beta != 0.0);   // (heat without buoyancy adds nothing to v: the walk runs in front of the fused pass; the Akinci surface tension and the micropolar walk need the densities of ALL neighbours first; an elastic object adds a_el behind the non-pressure pass, the air drag a_drag)
     SortCarry carry;   // what the sort leaves to the density pass below (unsharded: that pass is the next launch and walks every tile)
     if (s.slab_active) { int rc = slab_neighbor_search(h, fused); if (rc) return rc; }
     else carry = ph_neighbor_search(h, true, true);                           // WCSPH.py:28 (the density pass below rewrites every rho: the sort need not move it)
@@ -287,6 +303,7 @@ static int wcsph_step(SphHandle *h) {
         // Not in a step whose slot holds or emits (fluid emitters: the slot moves / adds particles behind this pass; the host knows now).
         const bool hash_next = !s.slab_active && s.c.all_fluid && h->steps_to_follow > 0 && !s.has_emitter && !h->any_rigid_object &&
                                !h->sort_dirty && !h->em_touch;
+        ph_heat(h);   // (heat with beta == 0: positions, densities and T only -- nothing the force pass has written yet)
         ProfScope p(h, SPH_K_WCSPH_FORCES); h->L->wcsph_forces(s, {books, hash_next});   // :30-31 + :34-36, :45 in one neighbour walk
         return SPH_OK;
     }

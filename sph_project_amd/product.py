@@ -403,6 +403,45 @@ def wind_jet_scene(nozzle=(4, 4), speed=3.0, wind=(5.0, 0.0, 0.0), drag=1.0, met
     return cfg
 
 
+def heated_tank_scene(edge=8, hot=60.0, cold=20.0, alpha=1.0e-4, beta=0.0, plate=True, method="wcsph", gravity=9.81, radius=0.01,
+                      dt=4e-4, viscosity=0.01, margin=8, **keys):
+    """The first scene of the heat conduction: a block of edge^3 fluid particles on the rest lattice at temperature
+    `cold` in a closed sampled box (adiabatic; `margin` particle diameters from the domain's faces, of which the shell takes the first
+    3.5), one particle diameter above a static, lattice-aligned plate of two layers (object 1, two particles wider than the block on
+    every side) held at `hot`.  thermalMethod "conduction" with thermalDiffusivity alpha, thermalExpansion beta and
+    referenceTemperature cold; gravity is the magnitude along -y.  hot = None leaves the plate's key out (an adiabatic plate),
+    plate = False the plate itself; alpha = None leaves every thermal key out.  keys: further Configuration keys."""
+    d = 2.0 * radius
+    lo = margin * d
+    size = lo + edge * d + lo
+    cfg = {
+        "Configuration": {
+            "domainStart": [0.0, 0.0, 0.0], "domainEnd": [size, size, size], "addDomainBox": True, "particleRadius": radius,
+            "density0": 1000, "simulationMethod": method, "viscosityMethod": "standard", "gravitation": [0.0, -float(gravity), 0.0],
+            "timeStepSize": dt, "viscosity": viscosity,
+        },
+        "FluidBlocks": [{
+            "objectId": 0, "start": [lo, lo, lo], "end": [lo + (edge - 0.5) * d] * 3, "translation": [0.0, 0.0, 0.0],
+            "scale": [1, 1, 1], "velocity": [0.0, 0.0, 0.0], "density": 1000.0, "color": [50, 100, 200], "entryTime": -1.0,
+        }],
+    }
+    if plate:
+        n = (edge + 4, 2, edge + 4)
+        pts = np.stack(np.meshgrid(*[d * np.arange(k) for k in n], indexing="ij"), -1).reshape(-1, 3) + np.array([lo - 2 * d, lo - 2 * d, lo - 2 * d])
+        cfg["RigidBodies"] = [{
+            "objectId": 1, "geometryFile": "unused.obj", "voxelizedPoints": np.asarray(pts, np.float32).tolist(),
+            "translation": [0.0, 0.0, 0.0], "rotationAxis": [0.0, 1.0, 0.0], "rotationAngle": 0.0, "scale": [1, 1, 1],
+            "velocity": [0.0, 0.0, 0.0], "density": 1000.0, "color": [230, 180, 60], "isDynamic": False, "entryTime": -1.0}]
+    if alpha is not None:
+        cfg["Configuration"].update(thermalMethod="conduction", thermalDiffusivity=float(alpha), thermalExpansion=float(beta),
+                                    referenceTemperature=float(cold))
+        cfg["FluidBlocks"][0]["temperature"] = float(cold)
+        if plate and hot is not None:
+            cfg["RigidBodies"][0]["temperature"] = float(hot)
+    cfg["Configuration"].update(keys)
+    return cfg
+
+
 def scene_particles(cfg_dict):
     """Host lattice of every object present at prepare(), in the reference's insertion order
     (domain box first: base_container.py:192, then FluidBlocks: :215).  Blocks with entryTime > 0 are listed with

@@ -283,6 +283,9 @@ def check_sharded_args(parser, args):
     if config.get_cfg("dragMethod") == "gissler":
         parser.error(f"--gpus {n}: dragMethod \"gissler\" is not sharded (not done, although the walk would need the ghosts' positions "
                      "only; sph_set_drag refuses a slab); run it with --gpus 1")
+    if config.get_cfg("thermalMethod") == "conduction":
+        parser.error(f"--gpus {n}: thermalMethod \"conduction\" is not sharded (the temperatures of the ghost particles would need an "
+                     "exchange of their own; sph_set_thermal refuses a slab); run it with --gpus 1")
     elastic = [e.get("objectId") for e in list(config.get_fluid_blocks()) + list(config.get_fluid_bodies()) if e.get("elasticity") is not None]
     if elastic:
         parser.error(f"--gpus {n}: object {elastic[0]} carries the key \"elasticity\": elastic solids are not sharded (a rest list names "
